@@ -14,6 +14,10 @@ sharded, no data-path collective (weak scaling).
         touches the GPU) and exits with its code.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
+    --dump-outputs DIR   after the timed steps, the amplitudes the last timed step returned -> DIR/amplitudes.npy
+                         (float64; inputs are seeded, so two builds can be compared output for output)
+    --details FILE       the full record of every leg -> FILE (stdout carries a compact line of a few KB)
+
 The JSON line carries, besides the headline leg (the SURVEY 8(d) synthetic state, numerically of low rank),
 a second leg `full_rank` on i.i.d. random site tensors (--noise 1.0) of the same shapes: the regime in which the
 dense MFMA GEMMs and the chi-truncation of full 256 x 256 blocks dominate.
@@ -73,6 +77,11 @@ def parse():
     ap.add_argument("--no-other-modes", action="store_true", help="skip the short runs of the f64 / variational / complex / C5 modes")
     ap.add_argument("--no-latency", action="store_true", help="skip the one-walker latency measurement (n1_ms)")
     ap.add_argument("--energy-n", type=int, default=8, help="configurations of the E_loc parity sample of the main leg (half of it on the extra legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (the amplitudes of the "
+                         "main leg) as DIR/<name>.npy, float64, at most 64 MB (a fixed, seeded sample of a larger batch)")
+    ap.add_argument("--details", metavar="FILE", default=None,
+                    help="write the full JSON record of every leg to FILE; stdout carries the compact result line only")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous / reduction plumbing only, NO device work: value is null (CPU tests of --gpus N)")
     args = ap.parse_args()
@@ -278,6 +287,7 @@ class Leg:
                 amps_first = a
         barrier(ctx)
         elapsed = time.perf_counter() - t0
+        self.amps_last = a
         self.local_elapsed = elapsed
         prof = ctx.profile_read()
         ctx.profile_enable(False)
@@ -720,6 +730,100 @@ def real_state_rank(capi, device, dt):
             "carry_live_fraction": st["carry_live_fraction"], "jacobi_sweeps_max": st["jacobi_sweeps_max"]}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: each array as <directory>/<name>.npy in float64 (the precision the C ABI returns).  A batch above
+    DUMP_MAX_BYTES in all is cut to the same fixed, seeded sample of indices for every array, stored as <name>_index.npy."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    n = len(next(iter(arrays.values())))
+    idx = None
+    if total > DUMP_MAX_BYTES:
+        keep = max(1, int(n * DUMP_MAX_BYTES // (2 * total)))       # room for the index arrays as well
+        idx = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+    files = []
+    for name, a in arrays.items():
+        if idx is not None:
+            np.save(os.path.join(directory, name + "_index.npy"), idx.astype(np.float64))
+            files.append(name + "_index.npy")
+            a = a[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
+        files.append(name + ".npy")
+    return {"dir": directory, "files": files, "sampled": idx is not None}
+
+
+def _pick(d, keys):
+    if not isinstance(d, dict):
+        return d
+    if "error" in d:
+        return {"error": str(d["error"])[:300]}
+    return {k: d[k] for k in keys if k in d}
+
+
+def result_line(out):
+    """The one JSON line on stdout: every top-level figure plus the headline of each nested record, a few KB in all (the full
+    record runs to 25 KB and goes to --details FILE).  A reader that keeps only the end of the output still gets a whole line."""
+    line = {k: v for k, v in out.items() if not isinstance(v, (dict, list)) and not (isinstance(v, str) and len(v) > 120)}
+    for k in ("ms_per_step_by_rank", "kernel_ms", "workload_rank", "route_consistency", "dump_outputs", "collective"):
+        if k in out:
+            line[k] = out[k]
+    if "config" in out:
+        line["config"] = {k: v for k, v in out["config"].items() if k != "note"}
+    if "roofline" in out:
+        line["roofline"] = _pick(out["roofline"], ("bound", "kernel", "category", "achieved", "peak", "unit", "frac", "frac_priced_with",
+                                                   "avg_launch_us", "launches_per_step", "share_of_kernel_time", "mfma_tflops", "mfma_frac"))
+    if "mfma" in out:
+        line["mfma"] = _pick(out["mfma"], ("mfma_tflops_in_mfma_kernels", "mfma_tflops_over_whole_step", "mfma_kernel_time_share"))
+    if "cpu_baseline" in out:
+        cb = out["cpu_baseline"]
+        line["cpu_baseline"] = _pick(cb, ("value", "unit", "cores", "kind"))
+        if "single_thread" in cb:
+            line["cpu_baseline"]["single_thread"] = cb["single_thread"].get("value")
+    if "parity_on_sample" in out:
+        line["parity_on_sample"] = _pick(out["parity_on_sample"], ("max_rel_err_amplitude", "n", "tolerance"))
+    if "energy_parity" in out:
+        line["energy_parity"] = _pick(out["energy_parity"], ("max_rel_err_energy", "n", "tolerance"))
+    if "vmc" in out:
+        line["vmc"] = _pick(out["vmc"], ("mc_sweeps_per_s", "vmc_samples_per_s", "walkers"))
+    for name in ("full_rank", "real_rank"):
+        if name not in out:
+            continue
+        leg = out[name]
+        r = _pick(leg, ("value", "unit", "walkers_per_gpu", "steps", "ms_per_step"))
+        if isinstance(leg, dict) and "error" not in leg:
+            if isinstance(leg.get("roofline"), dict):
+                r["roofline"] = _pick(leg["roofline"], ("bound", "category", "frac"))
+            for k, keys in (("parity_on_sample", ("max_rel_err_amplitude", "n")), ("energy_parity", ("max_rel_err_energy", "n")),
+                            ("f64_mode", ("amp_per_s",)), ("complex128", ("amp_per_s",)),
+                            ("vmc", ("mc_sweeps_per_s", "vmc_samples_per_s"))):
+                if k in leg:
+                    r[k] = _pick(leg[k], keys)
+        line[name] = r
+    if "other_modes" in out:
+        om = out["other_modes"]
+        line["other_modes"] = {k: _pick(v, ("amp_per_s",)) for k, v in om.items()} if "error" not in om else _pick(om, ())
+        c5 = om.get("C5_spinless_tV_8x8_D6_chi24")
+        if isinstance(c5, dict) and isinstance(c5.get("f64_mode"), dict):
+            line["other_modes"]["C5_spinless_tV_8x8_D6_chi24"]["f64_mode"] = _pick(c5["f64_mode"], ("amp_per_s",))
+    if "baseline_configs" in out:
+        bc = out["baseline_configs"]
+        line["baseline_configs"] = ({k: _pick(v, ("amp_per_s", "mc_sweeps_per_s")) for k, v in bc.items()}
+                                    if "error" not in bc else _pick(bc, ()))
+    return line
+
+
+def emit(out, details):
+    """print the result line; the full record to `details` when asked for"""
+    if details:
+        with open(details, "w") as f:
+            json.dump(out, f)
+            f.write("\n")
+    print(json.dumps(result_line(out)), flush=True)
+
+
 # exactly one JSON line per run: the main thread and the collective watchdog agree through these
 emit_lock = threading.Lock()
 emitted = [False]
@@ -805,6 +909,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         return [float(v) for v in t.tolist()]
     rank_ms = gather_ms(leg.local_elapsed / args.steps * 1e3)
+    dumped = None
+    if args.dump_outputs:
+        # what the caller of the timed path received in the last timed step: one amplitude per walker of this rank's shard
+        dumped = dump_outputs(args.dump_outputs, {"amplitudes" if world == 1 else "amplitudes_rank%d" % rank: leg.amps_last})
 
     NOTE = ("roofline = the dominant single kernel of the step (largest HIP-event time among the profiling categories that are one "
             "kernel; the event pair brackets exactly that kernel's launch on the launch stream).  bound: the launches contract "
@@ -859,6 +967,8 @@ def main():
             "mfma": mfma_summary(prof, args.dtype, elapsed),
             "walkers_with_vanishing_amplitude": nz,
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         out["workload_rank"] = leg.rank_diagnostics()
         # size-independent property at the full size, outside the timed region: the amplitude of the same configuration
         # contracted row-wise (DOWN stack, trace at row 0) and column-wise (RIGHT stack, trace at column 0) must agree
@@ -1078,7 +1188,7 @@ def main():
                         emitted[0] = True
                         line = dict(out)
                         line["collective"] = {"error": "collective section did not finish within 240 s (watchdog); the timed legs above are unaffected"}
-                        print(json.dumps(line), flush=True)
+                        emit(line, args.details)
                     os._exit(3)
 
         threading.Thread(target=watchdog, daemon=True).start()
@@ -1178,7 +1288,7 @@ def main():
         with emit_lock:
             if not emitted[0]:
                 emitted[0] = True
-                print(json.dumps(out), flush=True)
+                emit(out, args.details)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

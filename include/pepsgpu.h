@@ -44,8 +44,9 @@ enum {
  * BMPS tensor 2 x elements; pepsgpu_state_upload additionally accepts host_dtype = PEPSGPU_C128.  The complex type covers
  * SVD and (since round 5) variational compression, every contraction / trace / hole entry point, the walker calls, the gradient
  * accumulation (pepsgpu_grad_* below, with the reference's conjugations: psi, eloc and the accumulators are interleaved pairs) and
- * the SR / MinSR family (pepsgpu_sr_*) and (round 6) the device-side sweep slices; the device-side ENERGY slice
- * (pepsgpu_nn_exchange_slice) is real only and returns PEPSGPU_EINVAL. */
+ * the SR / MinSR family (pepsgpu_sr_*), the device-side sweep slices and the device-side energy slices
+ * pepsgpu_nn_exchange_slice_tab / pepsgpu_onsite_slice.  pepsgpu_nn_exchange_slice alone is real only and returns
+ * PEPSGPU_EINVAL on a complex context. */
 enum { PEPSGPU_F32 = 0, PEPSGPU_F64 = 1, PEPSGPU_C128 = 3 };
 enum { PEPSGPU_LEFT = 0, PEPSGPU_DOWN = 1, PEPSGPU_RIGHT = 2, PEPSGPU_UP = 3 };
 enum { PEPSGPU_HORIZONTAL = 0, PEPSGPU_VERTICAL = 1 };
@@ -135,6 +136,28 @@ int pepsgpu_sweep_slice_fullspace(pepsgpu_ctx *ctx, int orientation, int slice, 
  * j exchanged; for equal states it is psi).  punch_holes != 0: the holes of the slice's sites are stored in HBM as pepsgpu_punch_hole
  * with out == NULL does.  The BMPS pair of the slice must be in place.  Real element types only. */
 int pepsgpu_nn_exchange_slice(pepsgpu_ctx *ctx, int orientation, int slice, int punch_holes, double *psi_out, double *psi_exchanged_out);
+/* The exchange slice of every element type (a PEPSGPU_C128 context returns interleaved (re, im) amplitudes), with the move as a table
+ * and, for the fermionic models, psi per bond.  Replaces the per-bond hooks of SquareNNNModelEnergySolver (square_nnn_energy_solver.h:
+ * 142-200, bond_traversal_mixin.h:120-144) for complex states and for the fermionic EvaluateBondEnergy (square_spinless_fermion.h:
+ * 134-159, square_tJ_model.h:301-345: Trace + ReplaceNNSiteTrace per bond).
+ *   pair_table    [phys_dim^2][2] as for pepsgpu_sweep_slice_exchange_tab (fermions: the exchange of two extended states adjacent in
+ *                 the current mode order); NULL = the swap (b, a).  A table entry outside [0, phys_dim) is PEPSGPU_ERANGE;
+ *   psi_per_bond  0: psi_out [n], the Trace of the slice's first window (as pepsgpu_nn_exchange_slice);
+ *                 != 0: psi_out [n][slice length - 1], per bond the Trace of the window before that bond's replacement trace;
+ *   psi_exchanged_out [n][slice length - 1] the amplitude with the move of bond j applied (psi of bond j where it is the identity).
+ * With a NULL table and psi_per_bond = 0 a real context returns exactly what pepsgpu_nn_exchange_slice returns. */
+int pepsgpu_nn_exchange_slice_tab(pepsgpu_ctx *ctx, int orientation, int slice, int punch_holes, const int32_t *pair_table,
+                                  int psi_per_bond, double *psi_out, double *psi_exchanged_out);
+/* One row / column of one-site moves on the device, every element type: TransverseFieldIsingSquareOBC's row pass
+ * (transverse_field_ising_square_obc.h:195-203: InitBTen, GrowFullBTen(.., 1, true), psi = Trace, per site PunchHole and
+ * ReplaceOneSiteTrace of the flipped state, ShiftBTenWindow) with SquareNNNModelEnergySolver's PunchHole, ONE read-back.
+ *   site_table   [phys_dim][n_cand]: candidate k of a site in state s is site_table[s * n_cand + k] (TFIM: {1, 0}, n_cand = 1);
+ *                an entry outside [0, phys_dim) is PEPSGPU_ERANGE, n_cand < 1 PEPSGPU_EINVAL;
+ *   psi_out [n]; psi_cand_out [n][slice length][n_cand] the amplitude with site j of the slice in candidate state k;
+ *   punch_holes != 0: the holes of the slice's sites are stored in HBM as pepsgpu_punch_hole with out == NULL does.
+ * The BMPS pair of the slice must be in place; the BTen stacks are left as the per-site calls leave them. */
+int pepsgpu_onsite_slice(pepsgpu_ctx *ctx, int orientation, int slice, int punch_holes, int n_cand, const int32_t *site_table,
+                         double *psi_out, double *psi_cand_out);
 
 /* BMPSWalker as an object -- BMPSContractor::GetWalker / class BMPSWalker, bmps_contractor.h:357-646, bmps/impl/bmps_walker.h:13-465.
  * A walker holds the fork of the top BMPS of stack `pos` for every Monte-Carlo walker of the context (deep copy; the stacks are not

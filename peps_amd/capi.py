@@ -26,7 +26,7 @@ SYMBOLS = [
     "pepsgpu_walkers_set_configs", "pepsgpu_walkers_get_configs", "pepsgpu_n_walkers",
     "pepsgpu_grow_bmps_step", "pepsgpu_grow_full_bmps", "pepsgpu_grow_bmps_for_row", "pepsgpu_grow_bmps_for_col",
     "pepsgpu_shift_bmps_window", "pepsgpu_delete_inner_bmps", "pepsgpu_bmps_park", "pepsgpu_bmps_unpark", "pepsgpu_generate_bmps_approach",
-    "pepsgpu_sweep_slice_exchange", "pepsgpu_sweep_slice_exchange_tab", "pepsgpu_sweep_slice_fullspace", "pepsgpu_nn_exchange_slice", "pepsgpu_walker_create", "pepsgpu_walker_clone", "pepsgpu_walker_destroy", "pepsgpu_walker_info", "pepsgpu_walker_set_mpo", "pepsgpu_walker_evolve",
+    "pepsgpu_sweep_slice_exchange", "pepsgpu_sweep_slice_exchange_tab", "pepsgpu_sweep_slice_fullspace", "pepsgpu_nn_exchange_slice", "pepsgpu_nn_exchange_slice_tab", "pepsgpu_onsite_slice", "pepsgpu_walker_create", "pepsgpu_walker_clone", "pepsgpu_walker_destroy", "pepsgpu_walker_info", "pepsgpu_walker_set_mpo", "pepsgpu_walker_evolve",
     "pepsgpu_walker_evolve_step", "pepsgpu_walker_contract_row", "pepsgpu_walker_init_bten", "pepsgpu_walker_grow_bten_step",
     "pepsgpu_walker_shift_bten_window", "pepsgpu_walker_trace_with_bten", "pepsgpu_walker_clear_bten", "pepsgpu_walker_get_bmps_tensor",
     "pepsgpu_bmps_stack_size", "pepsgpu_get_bmps_tensor", "pepsgpu_init_bten", "pepsgpu_grow_full_bten",
@@ -104,6 +104,8 @@ def load_library(path=LIB_PATH):
     lib.pepsgpu_sweep_slice_exchange_tab.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, ip, dp, ip, ip, ip]
     lib.pepsgpu_sweep_slice_fullspace.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), dp, ip, ip]
     lib.pepsgpu_nn_exchange_slice.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, dp]
+    lib.pepsgpu_nn_exchange_slice_tab.argtypes = [vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, dp, dp]
+    lib.pepsgpu_onsite_slice.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, dp, dp]
     lib.pepsgpu_walker_create.argtypes = [vp, C.c_int, C.c_int, ip]
     lib.pepsgpu_walker_clone.argtypes = [vp, C.c_int, ip]
     lib.pepsgpu_walker_destroy.argtypes = [vp, C.c_int]
@@ -314,6 +316,31 @@ class Context:
         psi, ex = np.zeros(self.n), np.zeros((self.n, N - 1))
         self._ck(self._l.pepsgpu_nn_exchange_slice(self._h, orientation, slice_num, int(punch_holes), _dp(psi), _dp(ex)))
         return psi, ex
+
+    def nn_exchange_slice_tab(self, orientation, slice_num, punch_holes=False, pair_table=None, psi_per_bond=False):
+        """the exchange slice of every element type: pair_table [d * d][2] (None: the swap); returns (psi, psi_ex [n][N-1]) with
+        psi [n], or [n][N-1] (the Trace before every bond's replacement trace) when psi_per_bond"""
+        N = self.cols if orientation == HORIZONTAL else self.rows
+        psi = np.zeros((self.n, N - 1) if psi_per_bond else self.n, dtype=self._ot)
+        ex = np.zeros((self.n, N - 1), dtype=self._ot)
+        tab = None
+        if pair_table is not None:
+            tab = np.ascontiguousarray(pair_table, dtype=np.int32)
+            assert tab.shape == (self.d * self.d, 2), tab.shape
+        self._ck(self._l.pepsgpu_nn_exchange_slice_tab(self._h, orientation, slice_num, int(punch_holes), _ip(tab) if tab is not None else None,
+                                                       int(psi_per_bond), _dp(psi), _dp(ex)))
+        return psi, ex
+
+    def onsite_slice(self, orientation, slice_num, site_table, punch_holes=False):
+        """one-site moves along a row / column: site_table [d][n_cand] (candidate k of state s); returns (psi [n],
+        psi_cand [n][N][n_cand])"""
+        tab = np.ascontiguousarray(site_table, dtype=np.int32)
+        assert tab.ndim == 2 and tab.shape[0] == self.d, tab.shape
+        N = self.cols if orientation == HORIZONTAL else self.rows
+        psi = np.zeros(self.n, dtype=self._ot)
+        cand = np.zeros((self.n, N, tab.shape[1]), dtype=self._ot)
+        self._ck(self._l.pepsgpu_onsite_slice(self._h, orientation, slice_num, int(punch_holes), tab.shape[1], _ip(tab), _dp(psi), _dp(cand)))
+        return psi, cand
 
     def get_walker(self, pos, level=-1):
         """BMPSContractor::GetWalker(tn, pos) (bmps_walker.h:51-58): a Walker object forked from the top of stack `pos`

@@ -142,6 +142,16 @@ int pepsgpu_nn_exchange_slice(pepsgpu_ctx *ctx, int orientation, int slice, int 
   CTX_CALL(PG_REQUIRE(psi_out && psi_exchanged_out, 1, "null buffer");
            ctx->eng->nn_exchange_slice(orientation, slice, punch_holes, psi_out, psi_exchanged_out));
 }
+int pepsgpu_nn_exchange_slice_tab(pepsgpu_ctx *ctx, int orientation, int slice, int punch_holes, const int32_t *pair_table,
+                                  int psi_per_bond, double *psi_out, double *psi_exchanged_out) {
+  CTX_CALL(PG_REQUIRE(psi_out && psi_exchanged_out, 1, "null buffer");
+           ctx->eng->energy_slice_impl(0, orientation, slice, punch_holes, pair_table, 1, psi_per_bond, psi_out, psi_exchanged_out));
+}
+int pepsgpu_onsite_slice(pepsgpu_ctx *ctx, int orientation, int slice, int punch_holes, int n_cand, const int32_t *site_table,
+                         double *psi_out, double *psi_cand_out) {
+  CTX_CALL(PG_REQUIRE(site_table && psi_out && psi_cand_out, 1, "null buffer"); PG_REQUIRE(n_cand >= 1, 1, "n_cand < 1");
+           ctx->eng->energy_slice_impl(1, orientation, slice, punch_holes, site_table, n_cand, 0, psi_out, psi_cand_out));
+}
 int pepsgpu_walker_create(pepsgpu_ctx *ctx, int pos, int level, int *walker_out) {
   CTX_CALL(check_pos(pos); PG_REQUIRE(walker_out != nullptr, 1, "null output"); *walker_out = ctx->eng->walker_create(pos, level));
 }

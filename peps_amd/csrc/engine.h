@@ -113,6 +113,10 @@ struct EngineBase {
                                 int phys_dim, const uint32_t *words, double *amp_inout, int32_t *consumed_out, int32_t *accepted_out,
                                 int32_t *slice_states_out) = 0;
   virtual void nn_exchange_slice(int orient, int slice, int punch_holes, double *psi_out, double *psi_ex_out) = 0;
+  // mode 0: exchange move per bond (pair_table nullable, psi_per_bond), mode 1: one-site move per site (site table [dp][n_cand]);
+  // engine_sweep.h
+  virtual void energy_slice_impl(int mode, int orient, int slice, int punch_holes, const int32_t *table, int n_cand, int psi_per_bond,
+                                 double *psi_out, double *val_out) = 0;
   // BMPSWalker (bmps_contractor.h:357-646)
   virtual int walker_create(int pos, int level) = 0;
   virtual int walker_clone(int id) = 0;
@@ -552,15 +556,28 @@ class Engine : public EngineBase {
     ArenaScope scope(arena_);
     PG_REQUIRE(row >= 0 && col >= 0 && row < Ly_ && col < Lx_, 1, "ReplaceOneSiteTrace: site outside the lattice");
     const int nc = ncand > 0 ? ncand : 1;
-    SiteSel sa = cfg_site(row, col);
     int *dcand = nullptr;
     if (ncand > 0) {
       size_t cnt = (size_t)nw_ * ncand;
       for (size_t i = 0; i < cnt; ++i) PG_REQUIRE(cand[i] >= 0 && cand[i] < dp_, 4, "candidate state out of range");
       dcand = (int *)arena_.alloc(cnt * sizeof(int));
       PG_CHECK_HIP(hipMemcpyAsync(dcand, cand, cnt * sizeof(int), hipMemcpyHostToDevice, stream_));
-      sa.sel = dcand; sa.inc = 1; sa.per_walker = false;
     }
+    double *lsum = nullptr;
+    Acc *res = one_trace_device(row, col, orient, nc, dcand, &lsum);
+    finish_read(res, nw_ * nc, nc, lsum, out);
+    arena_.free(res);
+    arena_.free(lsum);
+    if (dcand) arena_.free(dcand);
+  }
+
+  // ReplaceOneSiteTrace with everything left on the device (the one-site energy slice, engine_sweep.h): candidate table
+  // dcand [walker][nc] (nullptr: the configuration), result res [walker x nc] (mantissa) and lsum [walker]: psi' = res exp(lsum).
+  // Caller frees both.
+  Acc *one_trace_device(int row, int col, int orient, int nc, const int *dcand, double **lsum_out) {
+    PG_REQUIRE(row >= 0 && col >= 0 && row < Ly_ && col < Lx_, 1, "ReplaceOneSiteTrace: site outside the lattice");
+    SiteSel sa = cfg_site(row, col);
+    if (dcand) { sa.sel = dcand; sa.inc = 1; sa.per_walker = false; }
     BTenDev t2;
     double *lsum = zeros_f64();
     const DTen<T> *other;
@@ -579,10 +596,10 @@ class Engine : public EngineBase {
       add_logs(lsum, lf.logscale, rt.logscale, bten_[UP][row].logscale, db.logscale);
       other = &db.t;
     }
-    finish_dot(t2.t, nc, *other, 1, nc, lsum, out);
+    Acc *res = finish_dot_device(t2.t, nc, *other, 1, nc);
     free_ten(t2.t);
-    arena_.free(lsum);
-    if (dcand) arena_.free(dcand);
+    *lsum_out = lsum;
+    return res;
   }
 
   void punch_hole(int row, int col, int orient, double *out) override {   // grow.h:150-183
@@ -927,6 +944,8 @@ class Engine : public EngineBase {
                         const uint32_t *words, double *amp_inout, int32_t *consumed_out, int32_t *accepted_out,
                         int32_t *slice_states_out) override;
   void nn_exchange_slice(int orient, int slice, int punch_holes, double *psi_out, double *psi_ex_out) override;
+  void energy_slice_impl(int mode, int orient, int slice, int punch_holes, const int32_t *table, int n_cand, int psi_per_bond,
+                         double *psi_out, double *val_out) override;
   // ---- BMPSWalker (engine_walker.h) ----
   int walker_create(int pos, int level) override;
   int walker_clone(int id) override;

@@ -181,13 +181,36 @@ __global__ void sweep_gather_slice_kernel(const int *__restrict__ cfg, int sites
   out[e] = cfg[(long)w * sites + first + j * stride];
 }
 
-// psi'[w][j] = res[w] exp(lsum[w]) into column j of a [n][stride] table
-// (same[w] != 0: the exchange was the identity and its trace was skipped -- psi' = psi, column 0 of the table)
+// one scalar of the accumulation type into a host-layout double array (complex: an interleaved (re, im) pair)
+__device__ __forceinline__ void sw_put(double *o, double x) { o[0] = x; }
+__device__ __forceinline__ void sw_put(double *o, const cplx<double> &x) { o[0] = x.re; o[1] = x.im; }
+
+// One-site candidates of site s from a table: cand[w][k] = tab[cfg[w][s] * nc + k] (the one-site energy slice; TFIM: tab = {1, 0})
+__global__ void slice_onsite_cand_kernel(const int *__restrict__ cfg, int sites, int s, const int *__restrict__ tab, int nc,
+                                         int *__restrict__ cand, int n) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n * nc) return;
+  const int w = e / nc, k = e - w * nc;
+  cand[e] = tab[cfg[(long)w * sites + s] * nc + k];
+}
+
+// psi'[w][k] = res[w][k] exp(lsum[w]) into columns col .. col + nc - 1 of a [n][stride] table of AccT scalars, stored as doubles
+// (complex: interleaved).  same[w] != 0 (nc == 1): the move was the identity and its trace was skipped -- psi' = psi, the value
+// already in column same_col.
 template <typename AccT>
-__global__ void sweep_store_value_kernel(const AccT *__restrict__ res, const double *__restrict__ lsum, double *__restrict__ out,
-                                         int stride, int j, const int *__restrict__ same, int n) {
-  const int w = blockIdx.x * blockDim.x + threadIdx.x;
-  if (w < n) out[(long)w * stride + j] = (same && same[w]) ? out[(long)w * stride] : (double)res[w] * exp(lsum[w]);
+__global__ void slice_store_value_kernel(const AccT *__restrict__ res, const double *__restrict__ lsum, double *__restrict__ out,
+                                         int stride, int col, int nc, const int *__restrict__ same, int same_col, int n) {
+  constexpr int ko = (int)(sizeof(AccT) / sizeof(double));
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n * nc) return;
+  const int w = e / nc, k = e - w * nc;
+  double *o = out + ((long)w * stride + col + k) * ko;
+  if (same && same[w]) {
+    const double *src = out + ((long)w * stride + same_col) * ko;
+    for (int q = 0; q < ko; ++q) o[q] = src[q];
+    return;
+  }
+  sw_put(o, sw_scaled(res[e], exp(lsum[w])));
 }
 
 // One row / column of the energy evaluation (SquareNNNModelEnergySolver::CalEnergyAndHolesImpl, square_nnn_energy_solver.h:
@@ -195,64 +218,122 @@ __global__ void sweep_store_value_kernel(const AccT *__restrict__ res, const dou
 // exchange of the two site states (XXZ, J1-J2, t-J ...): InitBTen + GrowFullBTen, psi of the slice, and for every bond the
 // amplitude of the configuration with the two states exchanged -- all on the device, ONE read-back per slice (psi [n] and
 // psi_ex [n][N-1]); with punch_holes the hole of every site of the slice is stored in HBM on the way (PunchHole, :163).
+// Real element types only (the contract of pepsgpu_nn_exchange_slice; energy_slice_impl covers both).
 template <typename T>
 void Engine<T>::nn_exchange_slice(int orient, int slice, int punch_holes, double *psi_out, double *psi_ex_out) {
   require_ready();
-  if constexpr (kCplx) {
-    PG_REQUIRE(false, 1, "device-side energy slice: real element types only (complex contexts use the per-bond calls)");
-  } else {
-    PG_REQUIRE(orient == HORIZONTAL || orient == VERTICAL, 1, "bad orientation");
-    const int N = orient == HORIZONTAL ? Lx_ : Ly_, lim = orient == HORIZONTAL ? Ly_ : Lx_;
-    PG_REQUIRE(slice >= 0 && slice < lim, 1, "slice outside the lattice");
-    const int sites = Ly_ * Lx_;
-    if (punch_holes && !holes_) {
-      holes_ = (T *)arena_.alloc(sizeof(T) * (size_t)maxw_ * Ly_ * Lx_ * slot_);
-      holes_ls_ = (double *)arena_.alloc(sizeof(double) * (size_t)maxw_ * Ly_ * Lx_);
+  PG_REQUIRE(!kCplx, 1, "pepsgpu_nn_exchange_slice: real element types only (complex contexts: pepsgpu_nn_exchange_slice_tab)");
+  energy_slice_impl(0, orient, slice, punch_holes, nullptr, 1, 0, psi_out, psi_ex_out);
+}
+
+// The energy slice of both element types (results in Acc, host arrays interleaved for complex), two kinds of move:
+//   mode 0, the exchange move on each bond: table = the pair table [dp^2][2] of sweep_swap_cand_kernel (nullptr: the swap);
+//     psi_per_bond != 0: per bond the Trace of the window before that bond's replacement trace as well (the fermionic hooks,
+//     SquareSpinlessFermion / SquaretJVModel::EvaluateBondEnergy), psi_out [n][N-1]; else psi_out [n] from the first window.
+//     val_out [n][N-1]: the exchanged amplitude of bond j (psi of the bond where the move is the identity).
+//     remain: GrowFullBTen(.., 1) with holes (the row pass, :143), 2 without (the column pass).
+//   mode 1, the one-site move on each site (TransverseFieldIsingSquareOBC::CalEnergyAndHoles, transverse_field_ising_square_obc.h:
+//     211-247): per site j and candidate k the amplitude with the site's state s replaced by table[s * n_cand + k] (ReplaceOneSiteTrace,
+//     :195-203), the BTen window shifted after every site; val_out [n][N][n_cand].  GrowFullBTen(.., 1): the trace of the first site
+//     needs the far environment down to the second site, with or without holes.
+// Both leave the environments as the per-site / per-bond host path does and punch the holes of the slice into HBM when asked.
+template <typename T>
+void Engine<T>::energy_slice_impl(int mode, int orient, int slice, int punch_holes, const int32_t *table, int n_cand, int psi_per_bond,
+                                  double *psi_out, double *val_out) {
+  require_ready();
+  PG_REQUIRE(mode == 0 || mode == 1, 1, "energy slice: bad mode");
+  PG_REQUIRE(orient == HORIZONTAL || orient == VERTICAL, 1, "bad orientation");
+  const int N = orient == HORIZONTAL ? Lx_ : Ly_, lim = orient == HORIZONTAL ? Ly_ : Lx_;
+  PG_REQUIRE(slice >= 0 && slice < lim, 1, "slice outside the lattice");
+  PG_REQUIRE(psi_out && val_out, 1, "null buffer");
+  const int nc = mode == 1 ? n_cand : 1;
+  PG_REQUIRE(nc >= 1, 1, "energy slice: n_cand < 1");
+  PG_REQUIRE(mode == 0 || table, 1, "one-site slice: null site table");
+  const int tab_len = mode == 0 ? 2 * dp_ * dp_ : dp_ * nc;
+  if (table)
+    for (int e = 0; e < tab_len; ++e) PG_REQUIRE(table[e] >= 0 && table[e] < dp_, 4, "energy slice table: state out of range");
+  const bool per_bond = mode == 0 && psi_per_bond;
+  const int sites = Ly_ * Lx_;
+  if (punch_holes && !holes_) {
+    holes_ = (T *)arena_.alloc(sizeof(T) * (size_t)maxw_ * Ly_ * Lx_ * slot_);
+    holes_ls_ = (double *)arena_.alloc(sizeof(double) * (size_t)maxw_ * Ly_ * Lx_);
+  }
+  // value table [n][stride] of Acc scalars.  mode 0: psi in column psi_col(j), psi_ex of bond j in column ex_col(j); mode 1: psi in
+  // column 0, candidate k of site j in column 1 + j nc + k
+  const int stride = mode == 1 ? 1 + N * nc : (per_bond ? 2 * (N - 1) : N);
+  auto psi_col = [&](int j) { return per_bond ? j : 0; };
+  auto ex_col = [&](int j) { return per_bond ? N - 1 + j : 1 + j; };
+  double *dval = (double *)arena_.alloc(sizeof(double) * kOut * (size_t)nw_ * stride);
+  int *dcand = (int *)arena_.alloc(sizeof(int) * (mode == 1 ? (size_t)nc : 3) * (size_t)nw_);
+  int *dsame = mode == 0 ? dcand + 2 * (size_t)nw_ : nullptr;
+  int *dtab = table ? (int *)arena_.alloc(sizeof(int) * (size_t)tab_len) : nullptr;
+  auto release = [&]() { arena_.free(dval); arena_.free(dcand); if (dtab) arena_.free(dtab); };
+  try {
+    if (dtab) PG_CHECK_HIP(hipMemcpyAsync(dtab, table, sizeof(int) * (size_t)tab_len, hipMemcpyHostToDevice, stream_));
+    const int lo = orient == HORIZONTAL ? LEFT : UP, hi = orient == HORIZONTAL ? RIGHT : DOWN;
+    const int remain = (mode == 1 || punch_holes) ? 1 : 2;
+    init_bten(lo, slice);
+    grow_full_bten(hi, slice, remain, 1);
+    const int gb = (nw_ + 255) / 256;
+    // res exp(lsum) of a trace into column col (frees res and lsum)
+    auto store = [&](Acc *res, double *lsum, int col, int ncs, const int *same, int same_col) {
+      hipLaunchKernelGGL(slice_store_value_kernel<Acc>, dim3((nw_ * ncs + 255) / 256), dim3(256), 0, stream_, (const Acc *)res,
+                         (const double *)lsum, dval, stride, col, ncs, same, same_col, nw_);
+      PG_CHECK_HIP(hipGetLastError());
+      arena_.free(res); arena_.free(lsum);
+    };
+    if (!per_bond) {
+      double *lsum = nullptr;
+      Acc *res = nn_trace_device(orient == HORIZONTAL ? slice : 0, orient == HORIZONTAL ? 0 : slice, orient, 1, nullptr, &lsum);
+      store(res, lsum, 0, 1, nullptr, 0);
     }
-    double *dval = (double *)arena_.alloc(sizeof(double) * (size_t)nw_ * N);     // column 0: psi, columns 1..N-1: psi_ex of bond j-1
-    int *dcand = (int *)arena_.alloc(sizeof(int) * 3 * (size_t)nw_);
-    int *dsame = dcand + 2 * (size_t)nw_;
-    auto release = [&]() { arena_.free(dval); arena_.free(dcand); };
-    try {
-      const int lo = orient == HORIZONTAL ? LEFT : UP, hi = orient == HORIZONTAL ? RIGHT : DOWN;
-      const int remain = punch_holes ? 1 : 2;         // :143 GrowFullBTen(RIGHT, row, 1, true) with holes, 2 in the column pass
-      init_bten(lo, slice);
-      grow_full_bten(hi, slice, remain, 1);
-      const int gb = (nw_ + 255) / 256;
-      {
-        double *lsum = nullptr;
-        Acc *res = nn_trace_device(orient == HORIZONTAL ? slice : 0, orient == HORIZONTAL ? 0 : slice, orient, 1, nullptr, &lsum);
-        hipLaunchKernelGGL(sweep_store_value_kernel<Acc>, dim3(gb), dim3(256), 0, stream_, (const Acc *)res, (const double *)lsum, dval, N, 0, (const int *)nullptr, nw_);
+    for (int j = 0; j < N; ++j) {
+      const int r1 = orient == HORIZONTAL ? slice : j, c1 = orient == HORIZONTAL ? j : slice;
+      if (punch_holes) punch_hole(r1, c1, orient, nullptr);
+      if (mode == 1) {
+        hipLaunchKernelGGL(slice_onsite_cand_kernel, dim3((nw_ * nc + 255) / 256), dim3(256), 0, stream_, (const int *)cfg_, sites,
+                           r1 * Lx_ + c1, (const int *)dtab, nc, dcand, nw_);
         PG_CHECK_HIP(hipGetLastError());
-        arena_.free(res); arena_.free(lsum);
-      }
-      for (int j = 0; j < N; ++j) {
-        const int r1 = orient == HORIZONTAL ? slice : j, c1 = orient == HORIZONTAL ? j : slice;
-        if (punch_holes) punch_hole(r1, c1, orient, nullptr);
-        if (j + 1 < N) {
-          const int r2 = orient == HORIZONTAL ? slice : j + 1, c2 = orient == HORIZONTAL ? j + 1 : slice;
-          hipLaunchKernelGGL(sweep_swap_cand_kernel, dim3(gb), dim3(256), 0, stream_, (const int *)cfg_, sites, r1 * Lx_ + c1, r2 * Lx_ + c2,
-                             dcand, dsame, nw_);
-          PG_CHECK_HIP(hipGetLastError());
+        double *lsum = nullptr;
+        Acc *res = one_trace_device(r1, c1, orient, nc, dcand, &lsum);
+        store(res, lsum, 1 + j * nc, nc, nullptr, 0);
+        if (j + 1 < N) shift_bten_window(hi);
+      } else if (j + 1 < N) {
+        const int r2 = orient == HORIZONTAL ? slice : j + 1, c2 = orient == HORIZONTAL ? j + 1 : slice;
+        if (per_bond) {
           double *lsum = nullptr;
-          Acc *res = nn_trace_device(r1, c1, orient, 1, dcand, &lsum, dsame);
-          hipLaunchKernelGGL(sweep_store_value_kernel<Acc>, dim3(gb), dim3(256), 0, stream_, (const Acc *)res, (const double *)lsum, dval, N,
-                             j + 1, (const int *)dsame, nw_);
-          PG_CHECK_HIP(hipGetLastError());
-          arena_.free(res); arena_.free(lsum);
-          if (remain == 1 || j + 2 < N) shift_bten_window(hi);
+          Acc *res = nn_trace_device(r1, c1, orient, 1, nullptr, &lsum);
+          store(res, lsum, psi_col(j), 1, nullptr, 0);
+        }
+        hipLaunchKernelGGL(sweep_swap_cand_kernel, dim3(gb), dim3(256), 0, stream_, (const int *)cfg_, sites, r1 * Lx_ + c1, r2 * Lx_ + c2,
+                           dcand, dsame, nw_, (const int *)dtab, dp_);
+        PG_CHECK_HIP(hipGetLastError());
+        double *lsum = nullptr;
+        Acc *res = nn_trace_device(r1, c1, orient, 1, dcand, &lsum, dsame);
+        store(res, lsum, ex_col(j), 1, dsame, psi_col(j));
+        if (remain == 1 || j + 2 < N) shift_bten_window(hi);
+      }
+    }
+    std::vector<double> h((size_t)kOut * nw_ * stride);
+    PG_CHECK_HIP(hipMemcpyAsync(h.data(), dval, sizeof(double) * h.size(), hipMemcpyDeviceToHost, stream_));
+    PG_CHECK_HIP(hipStreamSynchronize(stream_));
+    auto put = [&](double *dst, size_t i, int w, int col) {
+      for (int q = 0; q < kOut; ++q) dst[i * kOut + q] = h[((size_t)w * stride + col) * kOut + q];
+    };
+    for (int w = 0; w < nw_; ++w) {
+      if (mode == 1) {
+        put(psi_out, w, w, 0);
+        for (int e = 0; e < N * nc; ++e) put(val_out, (size_t)w * N * nc + e, w, 1 + e);
+      } else {
+        if (!per_bond) put(psi_out, w, w, 0);
+        for (int j = 0; j + 1 < N; ++j) {
+          if (per_bond) put(psi_out, (size_t)w * (N - 1) + j, w, psi_col(j));
+          put(val_out, (size_t)w * (N - 1) + j, w, ex_col(j));
         }
       }
-      std::vector<double> h((size_t)nw_ * N);
-      PG_CHECK_HIP(hipMemcpyAsync(h.data(), dval, sizeof(double) * h.size(), hipMemcpyDeviceToHost, stream_));
-      PG_CHECK_HIP(hipStreamSynchronize(stream_));
-      for (int w = 0; w < nw_; ++w) {
-        psi_out[w] = h[(size_t)w * N];
-        for (int j = 0; j + 1 < N; ++j) psi_ex_out[(size_t)w * (N - 1) + j] = h[(size_t)w * N + j + 1];
-      }
-    } catch (...) { release(); throw; }
-    release();
-  }
+    }
+  } catch (...) { release(); throw; }
+  release();
 }
 
 template <typename T>

@@ -776,6 +776,31 @@ struct TPSWaveFunctionComponentT {
                                          const std::vector<int32_t> &cand) const {
     return contractor.ReplaceNNSiteTrace(s1, dir, n_cand, DeviceStatesNN(s1, s2, n_cand, cand));
   }
+  // Fermions: the exchange of two sites adjacent in the current mode order, DeviceStatesNN tabulated over the pair of extended states
+  // (state + d * variant, dp = 4 d): the pair table [dp^2][2] of the device-side sweep and energy slices.  A pair whose variants do
+  // not belong to the current order maps to itself.
+  std::vector<int32_t> ExchangeTable() const {
+    if (!fermion) throw std::logic_error("ExchangeTable: the component has no fermionic decoration");
+    const FermionDecoration &fd = *fermion;
+    const int32_t d = (int32_t)fd.d(), dp = 4 * d;
+    std::vector<int32_t> tab((size_t)dp * dp * 2);
+    for (int32_t e1 = 0; e1 < dp; ++e1)
+      for (int32_t e2 = 0; e2 < dp; ++e2) {
+        const int32_t a1 = e1 % d, var1 = e1 / d, a2 = e2 % d, var2 = e2 / d;
+        int32_t c1 = e1, c2 = e2;
+        const bool row_ok = order == ROW_MAJOR && var1 < 2 && var2 < 2, col_ok = order == COL_MAJOR && var1 >= 2 && var2 >= 2;
+        if (row_ok || col_ok) {
+          const int32_t a = a2, b = a1;                     // the exchanged physical states
+          const int na = fd.n(a), nb = fd.n(b);
+          const int before = row_ok ? ((var1 & 1) ^ fd.n(a1)) : (var1 & 1);
+          if (row_ok) { c1 = a + d * (before ^ na); c2 = b + d * (before ^ na ^ nb); }
+          else { c1 = a + d * (2 + before); c2 = b + d * (2 + (before ^ na)); }
+        }
+        tab[2 * ((size_t)e1 * dp + e2)] = c1;
+        tab[2 * ((size_t)e1 * dp + e2) + 1] = c2;
+      }
+    return tab;
+  }
   // UpdateLocal (:345-378) for the walkers with mask != 0; new_states are physical, [walker][site]
   void UpdateLocal(const std::vector<TenElemT> &new_amplitude, const std::vector<SiteIdx> &sites,
                    const std::vector<int32_t> &new_states, const std::vector<uint8_t> &mask) {
@@ -862,9 +887,13 @@ class MonteCarloSweepUpdaterBase {
 };
 
 // a model opts into the device-side energy slice with `static constexpr bool kExchangeBondEnergy = true` + the scalar hook
-// double BondEnergyFromExchange(config1, config2, psi_exchanged / psi)
+// TenElemT BondEnergyFromExchange(config1, config2, ratio), ratio = ComplexConjugate(psi_exchanged / psi) as its EvaluateBondEnergy
+// forms it.  `kExchangeBondPsiPerBond = true`: its EvaluateBondEnergy divides by a Trace of the bond's own window (the fermionic
+// models) -- the slice returns that psi per bond, and fermionic components are admitted (the exchange as the pair table).
 template <typename U, typename = void> struct HasExchangeBondEnergy : std::false_type {};
 template <typename U> struct HasExchangeBondEnergy<U, std::void_t<decltype(U::kExchangeBondEnergy)>> : std::bool_constant<U::kExchangeBondEnergy> {};
+template <typename U, typename = void> struct HasExchangeBondPsiPerBond : std::false_type {};
+template <typename U> struct HasExchangeBondPsiPerBond<U, std::void_t<decltype(U::kExchangeBondPsiPerBond)>> : std::bool_constant<U::kExchangeBondPsiPerBond> {};
 
 // an updater opts into the device-side slice sweep with `static constexpr bool kDeviceSliceSweep = true` + SweepSliceOnDevice
 template <typename U, typename = void> struct HasDeviceSliceSweep : std::false_type {};
@@ -964,23 +993,8 @@ class MCUpdateSquareNNExchangeOBC : public MCUpdateSquareNNUpdateBaseOBC<MCUpdat
     // in that order is DeviceStatesNN tabulated over the pair of extended states.  The slice returns decorated amplitudes (the
     // Metropolis test sees moduli only); a walker that moved gets its signs back from its new configuration, as UpdateLocal does.
     const FermionDecoration &fd = *comp.fermion;
-    const int32_t d = (int32_t)fd.d(), dp = 4 * d;
-    std::vector<int32_t> tab((size_t)dp * dp * 2);
-    for (int32_t e1 = 0; e1 < dp; ++e1)
-      for (int32_t e2 = 0; e2 < dp; ++e2) {
-        const int32_t a1 = e1 % d, var1 = e1 / d, a2 = e2 % d, var2 = e2 / d;
-        int32_t c1 = e1, c2 = e2;
-        const bool row_ok = comp.order == ROW_MAJOR && var1 < 2 && var2 < 2, col_ok = comp.order == COL_MAJOR && var1 >= 2 && var2 >= 2;
-        if (row_ok || col_ok) {
-          const int32_t a = a2, b = a1;                     // the exchanged physical states
-          const int na = fd.n(a), nb = fd.n(b);
-          const int before = row_ok ? ((var1 & 1) ^ fd.n(a1)) : (var1 & 1);
-          if (row_ok) { c1 = a + d * (before ^ na); c2 = b + d * (before ^ na ^ nb); }
-          else { c1 = a + d * (2 + before); c2 = b + d * (2 + (before ^ na)); }
-        }
-        tab[2 * ((size_t)e1 * dp + e2)] = c1;
-        tab[2 * ((size_t)e1 * dp + e2) + 1] = c2;
-      }
+    const int32_t d = (int32_t)fd.d();
+    const std::vector<int32_t> tab = comp.ExchangeTable();
     std::vector<TenElemT> amp = comp.amplitude;
     check_rc(pepsgpu_sweep_slice_exchange_tab(c.ctx(), dir, (int)slice, (int)nu, uni.data(), tab.data(), dptr(amp.data()), consumed.data(),
                                               accepted.data(), states.data()), c.ctx());
@@ -1097,29 +1111,36 @@ class SquareNNNModelEnergySolver {
     if (calchols && !holes_on_device) out.holes.assign(n * rows * cols * slot, TenElemT(0.0));
     auto *self = static_cast<ExplicitlyModel *>(this);
     // A model whose NN off-diagonal term exchanges the two site states (it declares kExchangeBondEnergy and the scalar hook
-    // BondEnergyFromExchange) gets a whole row / column from ONE device call (pepsgpu_nn_exchange_slice: psi, the exchanged
+    // BondEnergyFromExchange) gets a whole row / column from ONE device call (pepsgpu_nn_exchange_slice_tab: psi, the exchanged
     // amplitudes of every bond and -- with holes resident in HBM -- the holes of the row, one read-back) instead of a
-    // ReplaceNNSiteTrace round trip per bond; same operations in the same order on the device, same numbers.
+    // ReplaceNNSiteTrace round trip per bond; same operations in the same order on the device, same numbers.  Real and complex;
+    // fermionic components for the models with kExchangeBondPsiPerBond (the exchange as ExchangeTable, psi per bond).
     // PEPSHOST_NO_DEVICE_SWEEP=1 keeps the per-bond hook path.
     static const bool no_dev = std::getenv("PEPSHOST_NO_DEVICE_SWEEP") != nullptr;
+    constexpr bool per_bond = HasExchangeBondPsiPerBond<ExplicitlyModel>::value;
     bool dev_slice = false;
-    if constexpr (std::is_same<TenElemT, double>::value && HasExchangeBondEnergy<ExplicitlyModel>::value)
-      dev_slice = !no_dev && !comp.fermion && (!calchols || holes_on_device);
+    if constexpr (HasExchangeBondEnergy<ExplicitlyModel>::value)
+      dev_slice = !no_dev && (!comp.fermion || per_bond) && (!calchols || holes_on_device);
     auto slice_energy = [&](BondOrientation dir, size_t slice, bool holes) {
-      if constexpr (std::is_same<TenElemT, double>::value && HasExchangeBondEnergy<ExplicitlyModel>::value) {
+      if constexpr (HasExchangeBondEnergy<ExplicitlyModel>::value) {
         const size_t N = dir == HORIZONTAL ? cols : rows;
-        std::vector<double> psi(n), ex(n * (N - 1));
-        check_rc(pepsgpu_nn_exchange_slice(c.ctx(), dir, (int)slice, holes ? 1 : 0, psi.data(), ex.data()), c.ctx());
+        std::vector<TenElemT> psi(per_bond ? n * (N - 1) : n), ex(n * (N - 1)), psi0(n);
+        const std::vector<int32_t> tab = comp.fermion ? comp.ExchangeTable() : std::vector<int32_t>();
+        check_rc(pepsgpu_nn_exchange_slice_tab(c.ctx(), dir, (int)slice, holes ? 1 : 0, tab.empty() ? nullptr : tab.data(), per_bond ? 1 : 0,
+                                               dptr(psi.data()), dptr(ex.data())), c.ctx());
         for (size_t w = 0; w < n; ++w) {
-          if (psi[w] == 0.0) throw std::runtime_error("Wavefunction amplitude is near zero, causing division by zero.");
-          const double inv = 1.0 / psi[w];
+          psi0[w] = psi[per_bond ? w * (N - 1) : w];          // (per bond: the first bond's window is the slice's first window)
+          if (psi0[w] == TenElemT(0.0)) throw std::runtime_error("Wavefunction amplitude is near zero, causing division by zero.");
+          const TenElemT inv = TenElemT(1.0) / psi0[w];
           for (size_t j = 0; j + 1 < N; ++j) {
             const SiteIdx s1 = dir == HORIZONTAL ? SiteIdx{slice, j} : SiteIdx{j, slice};
             const SiteIdx s2 = dir == HORIZONTAL ? SiteIdx{slice, j + 1} : SiteIdx{j + 1, slice};
-            out.energy[w] += self->BondEnergyFromExchange(comp.config(w, s1), comp.config(w, s2), ex[w * (N - 1) + j] * inv);
+            const size_t k = w * (N - 1) + j;
+            const TenElemT ratio = per_bond ? ComplexConjugate(TenElemT(ex[k] / psi[k])) : ComplexConjugate(TenElemT(ex[k] * inv));
+            out.energy[w] += self->BondEnergyFromExchange(comp.config(w, s1), comp.config(w, s2), ratio);
           }
         }
-        out.psi_list.push_back(psi);
+        out.psi_list.push_back(psi0);
       }
     };
     comp.SetOrder(ROW_MAJOR);                // fermions: holes are those of the row-major decorated network
@@ -1593,8 +1614,9 @@ class SquareSpinOneHalfXXZModelMixIn {
   }
   // the bond term as a function of the two states and psi(exchanged) / psi (:98-100): what EvaluateBondEnergy computes per walker
   static constexpr bool kExchangeBondEnergy = true;
-  double BondEnergyFromExchange(int32_t config1, int32_t config2, double ratio) const {
-    return config1 == config2 ? 0.25 * jz_ : -0.25 * jz_ + ratio * (0.5 * jxy_);
+  template <typename TenElemT>
+  TenElemT BondEnergyFromExchange(int32_t config1, int32_t config2, TenElemT ratio) const {
+    return config1 == config2 ? TenElemT(0.25 * jz_) : TenElemT(-0.25 * jz_ + ratio * (0.5 * jxy_));
   }
  protected:
   double jz_, jxy_, jz2_, jxy2_, pinning00_;
@@ -2060,6 +2082,15 @@ class SquareSpinlessFermion : public SquareNNModelEnergySolver<SquareSpinlessFer
       if (comp.config(w, s1) != comp.config(w, s2)) e[w] += -t_ * ComplexConjugate(TenElemT(psi_ex[w] / psi[w]));   // :156
     return e;
   }
+  // EvaluateBondEnergy of one walker from ratio = ComplexConjugate(psi_ex / psi) (the device-side energy slice)
+  static constexpr bool kExchangeBondEnergy = true;
+  static constexpr bool kExchangeBondPsiPerBond = true;
+  template <typename TenElemT>
+  TenElemT BondEnergyFromExchange(int32_t config1, int32_t config2, TenElemT ratio) const {
+    TenElemT e = V_ * CalDensityImpl(config1) * CalDensityImpl(config2);
+    if (config1 != config2) e += -t_ * ratio;
+    return e;
+  }
   double EvaluateTotalOnsiteEnergy(const Configuration &, size_t) const { return 0.0; }   // :92
  private:
   double t_, t2_, V_;
@@ -2098,6 +2129,14 @@ class SquaretJVModel : public SquareNNModelEnergySolver<SquaretJVModel> {
     }
     return e;
   }
+  // EvaluateBondEnergy of one walker from ratio = ComplexConjugate(psi_ex / psi) (the device-side energy slice)
+  static constexpr bool kExchangeBondEnergy = true;
+  static constexpr bool kExchangeBondPsiPerBond = true;
+  template <typename TenElemT>
+  TenElemT BondEnergyFromExchange(int32_t c1, int32_t c2, TenElemT ratio) const {
+    if (c1 == c2) return TenElemT((c1 == 2) ? 0.0 : V_);
+    return (c1 == 2 || c2 == 2) ? TenElemT(-t_ * ratio) : TenElemT((-0.5 + 0.5 * ratio) * J_ + V_);
+  }
   double EvaluateTotalOnsiteEnergy(const Configuration &config, size_t w) const {   // :215-228
     if (mu_ == 0.0) return 0.0;
     size_t ele = 0;
@@ -2129,8 +2168,20 @@ class TransverseFieldIsingSquareOBC {
     EnergyAndHolesT<TenElemT> out;
     out.energy.assign(n, TenElemT(0.0));
     if (calchols && !holes_on_device) out.holes.assign(n * rows * cols * slot, TenElemT(0.0));
+    // a whole row from ONE device call (pepsgpu_onsite_slice with the flip table; holes kept in HBM) when the holes are not wanted on
+    // the host; PEPSHOST_NO_DEVICE_SWEEP=1 keeps the per-site hook path
+    const bool dev_slice = !NoDeviceSlice() && (!calchols || holes_on_device);
     c.GenerateBMPSApproach(UP);
     for (size_t row = 0; row < rows; row++) {
+      if (dev_slice) {
+        std::vector<TenElemT> psi, psi_ex;
+        FlipSlice(c, row, calchols, psi, psi_ex);
+        out.psi_list.push_back(psi);
+        for (size_t col = 0; col < cols; col++)
+          for (size_t w = 0; w < n; ++w) out.energy[w] += (-h_) * ComplexConjugate(TenElemT(psi_ex[w * cols + col] / psi[w]));
+        if (row + 1 < rows) c.ShiftBMPSWindow(DOWN);
+        continue;
+      }
       c.InitBTen(LEFT, row);
       c.GrowFullBTen(RIGHT, row, 1, true);
       std::vector<TenElemT> psi = c.Trace({row, 0}, HORIZONTAL);
@@ -2169,23 +2220,35 @@ class TransverseFieldIsingSquareOBC {
     auto &sz = out.make("spin_z", ly * lx);
     auto &en = out.make("energy", 1);
     std::vector<std::vector<TenElemT>> psi_list;
+    const bool dev_slice = !NoDeviceSlice();
     c.GenerateBMPSApproach(UP);
     for (size_t row = 0; row < ly; ++row) {
-      c.InitBTen(LEFT, row);
-      c.GrowFullBTen(RIGHT, row, 1, true);
-      psi_list.push_back(c.Trace({row, 0}, HORIZONTAL));
+      std::vector<TenElemT> row_ex;                     // (device slice: the flipped amplitudes of the whole row, [walker][col])
+      if (dev_slice) {
+        psi_list.emplace_back();
+        FlipSlice(c, row, false, psi_list.back(), row_ex);
+      } else {
+        c.InitBTen(LEFT, row);
+        c.GrowFullBTen(RIGHT, row, 1, true);
+        psi_list.push_back(c.Trace({row, 0}, HORIZONTAL));
+      }
       const std::vector<TenElemT> &psi = psi_list.back();
       for (size_t col = 0; col < lx; ++col) {
-        std::vector<int32_t> cand(n);
-        for (size_t w = 0; w < n; ++w) cand[w] = 1 - comp.config(w, {row, col});
-        std::vector<TenElemT> psi_ex = c.ReplaceOneSiteTrace({row, col}, HORIZONTAL, 1, cand);        // :195-203
+        std::vector<TenElemT> psi_ex(n);
+        if (dev_slice) {
+          for (size_t w = 0; w < n; ++w) psi_ex[w] = row_ex[w * lx + col];
+        } else {
+          std::vector<int32_t> cand(n);
+          for (size_t w = 0; w < n; ++w) cand[w] = 1 - comp.config(w, {row, col});
+          psi_ex = c.ReplaceOneSiteTrace({row, col}, HORIZONTAL, 1, cand);                             // :195-203
+        }
         for (size_t w = 0; w < n; ++w) {
           if (psi[w] == TenElemT(0.0)) throw std::runtime_error("Wavefunction amplitude is near zero, causing division by zero.");
           const TenElemT ex = (-h_) * ComplexConjugate(TenElemT(psi_ex[w] / psi[w]));                 // :202
           en[w] += ex;
           sx[w * ly * lx + row * lx + col] = h_ != 0.0 ? TenElemT(-ex / h_) : TenElemT(0.0);          // :96
         }
-        if (col + 1 < lx) c.ShiftBTenWindow(RIGHT);
+        if (col + 1 < lx && !dev_slice) c.ShiftBTenWindow(RIGHT);
       }
       if (row == ly / 2 && half > 0) {                                                                  // :101-110
         auto &szsz = out.make("SzSz_row", half);
@@ -2218,6 +2281,20 @@ class TransverseFieldIsingSquareOBC {
             {"SzSz_row", "SzSz correlations along middle row (flat)", {lx / 2}, {"segment"}}};
   }
  private:
+  static bool NoDeviceSlice() {
+    static const bool no_dev = std::getenv("PEPSHOST_NO_DEVICE_SWEEP") != nullptr;
+    return no_dev;
+  }
+  // the row pass of one row on the device: InitBTen, GrowFullBTen(RIGHT, row, 1, true), psi = Trace, per site (PunchHoleStore and)
+  // ReplaceOneSiteTrace of the flipped spin + ShiftBTenWindow -- psi [walker], psi_ex [walker][col]
+  template <typename TenElemT>
+  static void FlipSlice(BMPSContractorT<TenElemT> &c, size_t row, bool holes, std::vector<TenElemT> &psi, std::vector<TenElemT> &psi_ex) {
+    static const int32_t flip[2] = {1, 0};
+    const size_t n = c.walkers(), cols = c.cols();
+    psi.assign(n, TenElemT(0.0));
+    psi_ex.assign(n * cols, TenElemT(0.0));
+    check_rc(pepsgpu_onsite_slice(c.ctx(), HORIZONTAL, (int)row, holes ? 1 : 0, 1, flip, dptr(psi.data()), dptr(psi_ex.data())), c.ctx());
+  }
   double h_;
   PsiSummaryStore last_psi_;
 };

@@ -382,6 +382,31 @@ int pepsgpu_grad_device_ptr(pepsgpu_ctx *ctx, void **so_dev, void **seo_dev, lon
 /* ---- diagnostics (unit tests of the kernels; not part of the reference surface) ---- */
 int pepsgpu_diag_tgemm(int dtype_in, int dtype_out, const int *desc_ints, int n_ints, const void *A, size_t a_elems,
                        const void *B, size_t b_elems, void *C, size_t c_elems, int nbatch, long wA, long wB, long wC);
+/* the whole tensor-GEMM descriptor (tgemm.h TGemmDesc) through tgemm_launch, for the kernel tests.
+ * types: (A, B, C, accumulation) = 0 f32/f32/f32/f32, 1 f32/f32/f32/f64, 2 f32/f32/f64/f64, 3 f64 x 4, 4 c128 x 4.
+ * desc_ints[89]: 0..26 I, J, K, sAi, sAk, sBk, sBj, sCi, sCj (3 each); then for dI[0..2], dJ[0..2], dK[0..2] (9 each):
+ * 27 pool offset of p (-1 = none), 36 mul, 45 mask, 54 div; 63 dynI, 64 dynK (pool offsets), 65 dynI_mul, 66 dynK_mul,
+ * 67 selA, 68 selB (pool offsets), 69 selA_inc, 70 selB_inc, 71 bdivA, 72 bdivB, 73 bdivC, 74 seldivA, 75 seldivB, 76 nbatch,
+ * 77 accumulate, 78 upper_only, 79 conjA, 80 conjB, 81 batch_flag (pool offset), 82 prefer_tiled, 83 acc64, 84 scale_out on,
+ * 85 norm_log on, 86 norm_flag on, 87 scale_in on, 88 reserved (0).  desc_longs[5] = wA, wB, wC, selA_mul, selB_mul;
+ * desc_dbls[1] = alpha.  pool = the per-batch int arrays the offsets point into; scale_in / scale_out / norm_log / norm_flag:
+ * nbatch each (the last three in/out).  The launch reads A from A + a_offset and B from B + b_offset (elements); C is
+ * uploaded first, so what the kernel does not write keeps its value.  route_out[4] = {route (tgemm.h TgRouteKind), avec,
+ * bvec, acc64}, written before the launch (also when it is refused); flops_out = the launch's flop counter. */
+int pepsgpu_diag_tgemm_desc(int types, const int *desc_ints, int n_ints, const long *desc_longs, int n_longs,
+                            const double *desc_dbls, int n_dbls, const int32_t *pool, long pool_n, const float *scale_in,
+                            const void *A, size_t a_elems, long a_offset, const void *B, size_t b_elems, long b_offset,
+                            void *C, size_t c_elems, float *scale_out, double *norm_log, int32_t *norm_flag,
+                            int32_t *route_out, unsigned long long *flops_out);
+/* the route tgemm_launch would take for the same descriptor, without a device (operands at a 256-byte aligned base
+ * advanced by the offsets) */
+int pepsgpu_diag_tgemm_route(int types, const int *desc_ints, int n_ints, const long *desc_longs, int n_longs,
+                             const double *desc_dbls, int n_dbls, long a_offset, long b_offset, int32_t *route_out);
+/* one BTen growth step through tgemm_chain3_kernel with the descriptors of the engine's bten_step; see capi.hip */
+int pepsgpu_diag_tgemm_chain3(const int *dims8, const int *site_strides4, long slot, int nslots, const int32_t *sel, int sel_inc,
+                              const int32_t *live4, const int32_t *skip, int nbatch, const int *offs3, const float *mps1,
+                              const float *bten, const float *site, const float *mps2, float *out, int32_t *flags_out,
+                              int32_t *launched_out, int32_t *variant_out);
 int pepsgpu_diag_chol(int dtype_out, const double *G, int n, int nbatch, void *R_out);
 /* the streaming f64 Gram kernel of the forward pass (gram.h): P = [nbatch][K][n], klive (nullable) = live rows per entry */
 int pepsgpu_diag_gram_cols(int dtype, const void *P, int K, int n, int nbatch, const int32_t *klive, double *G_out);

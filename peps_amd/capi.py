@@ -43,7 +43,7 @@ SYMBOLS = [
     "pepsgpu_sr_cg_solve", "pepsgpu_sr_gram", "pepsgpu_sr_weighted_sum", "pepsgpu_sr_copy_samples",
     "pepsgpu_update_local", "pepsgpu_erase_envs_after_update", "pepsgpu_evaluate_amplitude",
     "pepsgpu_walker_flags", "pepsgpu_sync", "pepsgpu_stats", "pepsgpu_profile_enable", "pepsgpu_profile_read",
-    "pepsgpu_diag_tgemm", "pepsgpu_diag_tgemm_chain", "pepsgpu_diag_chol", "pepsgpu_diag_chol_adaptive", "pepsgpu_diag_chol_pivot", "pepsgpu_diag_rows_qr", "pepsgpu_diag_suwa_todo", "pepsgpu_diag_gram_chol", "pepsgpu_diag_gram_cols", "pepsgpu_diag_gram_rows", "pepsgpu_diag_mgemm_dense", "pepsgpu_diag_jacobi", "pepsgpu_version",
+    "pepsgpu_diag_tgemm", "pepsgpu_diag_tgemm_desc", "pepsgpu_diag_tgemm_route", "pepsgpu_diag_tgemm_chain", "pepsgpu_diag_tgemm_chain3", "pepsgpu_diag_chol", "pepsgpu_diag_chol_adaptive", "pepsgpu_diag_chol_pivot", "pepsgpu_diag_rows_qr", "pepsgpu_diag_suwa_todo", "pepsgpu_diag_gram_chol", "pepsgpu_diag_gram_cols", "pepsgpu_diag_gram_rows", "pepsgpu_diag_mgemm_dense", "pepsgpu_diag_jacobi", "pepsgpu_version",
 ]
 
 
@@ -140,6 +140,13 @@ def load_library(path=LIB_PATH):
     lib.pepsgpu_profile_read.argtypes = [vp, dp]
     lib.pepsgpu_diag_tgemm.argtypes = [C.c_int, C.c_int, ip, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t,
                                        C.c_int, C.c_long, C.c_long, C.c_long]
+    lp, ullp = C.POINTER(C.c_long), C.POINTER(C.c_ulonglong)
+    lib.pepsgpu_diag_tgemm_desc.argtypes = [C.c_int, ip, C.c_int, lp, C.c_int, dp, C.c_int, ip, C.c_long, C.POINTER(C.c_float),
+                                            vp, C.c_size_t, C.c_long, vp, C.c_size_t, C.c_long, vp, C.c_size_t,
+                                            C.POINTER(C.c_float), dp, ip, ip, ullp]
+    lib.pepsgpu_diag_tgemm_route.argtypes = [C.c_int, ip, C.c_int, lp, C.c_int, dp, C.c_int, C.c_long, C.c_long, ip]
+    lib.pepsgpu_diag_tgemm_chain3.argtypes = [ip, ip, C.c_long, C.c_int, ip, C.c_int, ip, ip, C.c_int, ip, vp, vp, vp, vp, vp,
+                                              ip, ip, ip]
     lib.pepsgpu_diag_chol.argtypes = [C.c_int, dp, C.c_int, C.c_int, vp]
     lib.pepsgpu_diag_chol_adaptive.argtypes = [C.c_int, dp, C.c_int, C.c_int, vp, ip]
     lib.pepsgpu_diag_gram_chol.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, ip]
@@ -617,6 +624,127 @@ def diag_tgemm(dtype_in, dtype_out, I, J, K, sAi, sAk, sBk, sBj, sCi, sCj, A, B,
     if rc != 0:
         raise RuntimeError("diag_tgemm failed: %s" % lib().pepsgpu_last_error(None).decode())
     return Cc
+
+
+# element types of pepsgpu_diag_tgemm_desc: (A, B, C, accumulation)
+TG_F32, TG_F32_ACC64, TG_F32_TO_F64, TG_F64, TG_C128 = 0, 1, 2, 3, 4
+TG_TYPES = {TG_F32: (np.float32, np.float32, np.float32, np.float32), TG_F32_ACC64: (np.float32, np.float32, np.float32, np.float64),
+            TG_F32_TO_F64: (np.float32, np.float32, np.float64, np.float64), TG_F64: (np.float64,) * 4,
+            TG_C128: (np.complex128,) * 4}
+# tgemm.h TgRouteKind
+TG_ROUTE_EMPTY, TG_ROUTE_DIRECT, TG_ROUTE_SKINNY_128x32, TG_ROUTE_SKINNY_32x128, TG_ROUTE_TILED_MFMA, TG_ROUTE_TILED_VALU, \
+    TG_ROUTE_REFUSED = range(7)
+_DYN = ("dI0", "dI1", "dI2", "dJ0", "dJ1", "dJ2", "dK0", "dK1", "dK2")
+
+
+def tgemm_desc_arrays(desc):
+    """Flat (ints, longs, doubles, pool) of a descriptor given as a dict (keys as the TGemmDesc fields; a per-batch array is
+    a sequence of ints; the TgDyn fields as desc["dI1"] = dict(p=..., mul=1, mask=0, div=1))."""
+    pool = []
+
+    def off(a):
+        if a is None:
+            return -1
+        o = len(pool)
+        pool.extend(int(v) for v in np.asarray(a).ravel())
+        return o
+
+    g = desc.get
+    ints = [0] * 89
+    for q, key in enumerate(("I", "J", "K", "sAi", "sAk", "sBk", "sBj", "sCi", "sCj")):
+        dflt = (1, 1, 1) if q < 3 else (0, 0, 0)
+        ints[3 * q:3 * q + 3] = [int(v) for v in g(key, dflt)]
+    for q, key in enumerate(_DYN):
+        t = g(key) or {}
+        ints[27 + q] = off(t.get("p"))
+        ints[36 + q] = int(t.get("mul", 1))
+        ints[45 + q] = int(t.get("mask", 0))
+        ints[54 + q] = int(t.get("div", 1))
+    ints[63], ints[64] = off(g("dynI")), off(g("dynK"))
+    ints[65], ints[66] = int(g("dynI_mul", 1)), int(g("dynK_mul", 1))
+    ints[67], ints[68] = off(g("selA")), off(g("selB"))
+    ints[69], ints[70] = int(g("selA_inc", 0)), int(g("selB_inc", 0))
+    ints[71:76] = [int(g(k, 1)) for k in ("bdivA", "bdivB", "bdivC", "seldivA", "seldivB")]
+    ints[76] = int(g("nbatch", 1))
+    ints[77:81] = [int(g(k, 0)) for k in ("accumulate", "upper_only", "conjA", "conjB")]
+    ints[81] = off(g("batch_flag"))
+    ints[82], ints[83] = int(g("prefer_tiled", 0)), int(g("acc64", 0))
+    ints[84:88] = [int(bool(g(k, False))) for k in ("scale_out", "norm_log", "norm_flag", "scale_in")]
+    longs = [int(g(k, 0)) for k in ("wA", "wB", "wC", "selA_mul", "selB_mul")]
+    return (np.array(ints, dtype=np.int32), np.array(longs, dtype=np.int64), np.array([float(g("alpha", 1.0))]),
+            np.array(pool if pool else [0], dtype=np.int32))
+
+
+def diag_tgemm_route(types, desc, a_offset=0, b_offset=0):
+    """(route, avec, bvec, acc64) tgemm_launch takes for the descriptor; no device is touched."""
+    ints, longs, dbls, _ = tgemm_desc_arrays(desc)
+    r = np.zeros(4, dtype=np.int32)
+    rc = lib().pepsgpu_diag_tgemm_route(types, _ip(ints), ints.size, longs.ctypes.data_as(C.POINTER(C.c_long)), longs.size,
+                                        _dp(dbls), dbls.size, a_offset, b_offset, _ip(r))
+    if rc != 0:
+        raise RuntimeError("diag_tgemm_route failed: %s" % lib().pepsgpu_last_error(None).decode())
+    return tuple(int(v) for v in r)
+
+
+def diag_tgemm_desc(types, desc, A, B, C_init, a_offset=0, b_offset=0, scale_in=None, scale_out=None, norm_log=None,
+                    norm_flag=None):
+    """One tgemm_launch of the descriptor (see tgemm_desc_arrays) on flat operand buffers; A is read from A[a_offset:], B from
+    B[b_offset:].  scale_in: per-entry input scales (desc["scale_in"] set); scale_out / norm_log / norm_flag: initial values of
+    the outputs the descriptor enables.  Returns a dict: status (0 or the library's error code), C, route (route, avec, bvec,
+    acc64), flops, scale_out, norm_log, norm_flag."""
+    ints, longs, dbls, pool = tgemm_desc_arrays(desc)
+    ta, tb, tc, _ = TG_TYPES[types]
+    nb = int(ints[76])
+    A = np.ascontiguousarray(A, dtype=ta)
+    B = np.ascontiguousarray(B, dtype=tb)
+    Cc = np.ascontiguousarray(C_init, dtype=tc).copy()
+    si = np.ascontiguousarray(np.ones(max(nb, 1)) if scale_in is None else scale_in, dtype=np.float32)
+    so = np.ascontiguousarray(np.zeros(max(nb, 1)) if scale_out is None else scale_out, dtype=np.float32).copy()
+    nl = np.ascontiguousarray(np.zeros(max(nb, 1)) if norm_log is None else norm_log, dtype=np.float64).copy()
+    nf = np.ascontiguousarray(np.zeros(max(nb, 1)) if norm_flag is None else norm_flag, dtype=np.int32).copy()
+    route = np.full(4, -1, dtype=np.int32)
+    flops = C.c_ulonglong(0)
+    fp = C.POINTER(C.c_float)
+    rc = lib().pepsgpu_diag_tgemm_desc(types, _ip(ints), ints.size, longs.ctypes.data_as(C.POINTER(C.c_long)), longs.size,
+                                       _dp(dbls), dbls.size, _ip(pool), pool.size, si.ctypes.data_as(fp),
+                                       A.ctypes.data_as(C.c_void_p), A.size, a_offset, B.ctypes.data_as(C.c_void_p), B.size, b_offset,
+                                       Cc.ctypes.data_as(C.c_void_p), Cc.size, so.ctypes.data_as(fp), _dp(nl), _ip(nf), _ip(route),
+                                       C.byref(flops))
+    return dict(status=int(rc), C=Cc, route=tuple(int(v) for v in route), flops=int(flops.value), scale_out=so, norm_log=nl,
+                norm_flag=nf, error=lib().pepsgpu_last_error(None).decode() if rc else "")
+
+
+def diag_tgemm_chain3(dims, site_strides, site, slot, sel, sel_inc, mps1, bten, mps2, out_init, live=None, skip=None, offs=(0, 0, 0)):
+    """One BTen growth step through tgemm_chain3_kernel with the engine's descriptors (bten_chain_descs).  dims = (x, p1, cdim,
+    b1, b2, s1, s2, y); site = flat store of slot-element tensors (legs p1, b1, s1, s2 at site_strides), entry b uses tensor
+    sel[b * sel_inc]; mps1 / bten / mps2 = flat per-entry buffers, offs = element offsets of the mps1 / bten / site bases in
+    theirs; live = per entry (vx, vc, vb, vy) or None; out_init = the initial output.  Returns (out, flags, launched, variant)."""
+    d8 = np.ascontiguousarray(dims, dtype=np.int32)
+    st = np.ascontiguousarray(site_strides, dtype=np.int32)
+    sel = np.ascontiguousarray(sel, dtype=np.int32)
+    nb = int(np.asarray(out_init).shape[0])
+    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32).ravel()   # noqa: E731
+    m1, bt, sv, m2 = f32(mps1), f32(bten), f32(site), f32(mps2)
+    out = np.ascontiguousarray(out_init, dtype=np.float32).copy()
+    lv = None if live is None else np.ascontiguousarray(live, dtype=np.int32)
+    sk = None if skip is None else np.ascontiguousarray(skip, dtype=np.int32)
+    o3 = np.ascontiguousarray(offs, dtype=np.int32)
+    x, p1, c, b1, b2, s1, _, y = (int(v) for v in d8)
+    for buf, n, o in ((m1, x * p1 * c, o3[0]), (bt, c * b1 * b2, o3[1]), (m2, b2 * s1 * y, 0)):
+        if buf.size != n * nb + o:
+            raise ValueError("diag_tgemm_chain3: operand buffer of %d elements, expected %d" % (buf.size, n * nb + o))
+    if sel.size < (nb - 1) * sel_inc + 1 or (sv.size - int(o3[2])) < slot * (int(sel.max()) + 1):
+        raise ValueError("diag_tgemm_chain3: selector or site store too small")
+    flags = np.full(nb, 7, dtype=np.int32)
+    launched = np.zeros(1, dtype=np.int32)
+    variant = np.zeros(3, dtype=np.int32)
+    vpp = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    rc = lib().pepsgpu_diag_tgemm_chain3(_ip(d8), _ip(st), slot, (sv.size - int(offs[2])) // slot, _ip(sel), sel_inc,
+                                         None if lv is None else _ip(lv), None if sk is None else _ip(sk), nb, _ip(o3),
+                                         vpp(m1), vpp(bt), vpp(sv), vpp(m2), vpp(out), _ip(flags), _ip(launched), _ip(variant))
+    if rc != 0:
+        raise RuntimeError("diag_tgemm_chain3 failed: %s" % lib().pepsgpu_last_error(None).decode())
+    return out, flags, int(launched[0]), tuple(int(v) for v in variant)
 
 
 def diag_tgemm_chain(R, A, W, live):

@@ -400,6 +400,176 @@ extern "C" int pepsgpu_diag_tgemm(int dtype_in, int dtype_out, const int *di, in
   });
 }
 
+// ---- the whole TGemmDesc from flat arrays (pepsgpu_diag_tgemm_desc / pepsgpu_diag_tgemm_route; layout in include/pepsgpu.h) ----
+constexpr int TGD_NI = 89, TGD_NL = 5, TGD_ND = 1;
+// pool: base of the per-batch int arrays the descriptor points into (an offset < 0 = null pointer); scale_in: the per-entry
+// input scales (used when desc_ints[87] != 0)
+static TGemmDesc tgd_unpack(const int *di, const long *dl, const double *dd, const int *pool, const float *scale_in) {
+  TGemmDesc d;
+  auto ptr = [&](int off) -> const int * { return off >= 0 ? pool + off : nullptr; };
+  for (int k = 0; k < 3; ++k) {
+    d.I[k] = di[k]; d.J[k] = di[3 + k]; d.K[k] = di[6 + k];
+    d.sAi[k] = di[9 + k]; d.sAk[k] = di[12 + k]; d.sBk[k] = di[15 + k];
+    d.sBj[k] = di[18 + k]; d.sCi[k] = di[21 + k]; d.sCj[k] = di[24 + k];
+  }
+  TgDyn *dyn[9] = {&d.dI[0], &d.dI[1], &d.dI[2], &d.dJ[0], &d.dJ[1], &d.dJ[2], &d.dK[0], &d.dK[1], &d.dK[2]};
+  for (int q = 0; q < 9; ++q) {
+    dyn[q]->p = ptr(di[27 + q]); dyn[q]->mul = di[36 + q]; dyn[q]->mask = di[45 + q]; dyn[q]->div = di[54 + q];
+  }
+  d.dynI = ptr(di[63]); d.dynK = ptr(di[64]); d.dynI_mul = di[65]; d.dynK_mul = di[66];
+  d.selA = ptr(di[67]); d.selB = ptr(di[68]); d.selA_inc = di[69]; d.selB_inc = di[70];
+  d.bdivA = di[71]; d.bdivB = di[72]; d.bdivC = di[73]; d.seldivA = di[74]; d.seldivB = di[75];
+  d.nbatch = di[76]; d.accumulate = di[77]; d.upper_only = di[78]; d.conjA = di[79]; d.conjB = di[80];
+  d.batch_flag = ptr(di[81]); d.prefer_tiled = di[82]; d.acc64 = di[83];
+  d.scale_in = di[87] ? scale_in : nullptr;
+  d.wA = dl[0]; d.wB = dl[1]; d.wC = dl[2]; d.selA_mul = dl[3]; d.selB_mul = dl[4];
+  d.alpha = dd[0];
+  return d;
+}
+
+static void tgd_check(int n_ints, int n_longs, int n_dbls) {
+  PG_REQUIRE(n_ints == TGD_NI && n_longs == TGD_NL && n_dbls == TGD_ND, 1, "descriptor needs 89 ints, 5 longs, 1 double");
+}
+
+static void tgd_put_route(const TgRoute &r, int32_t *route_out) {
+  route_out[0] = r.kind; route_out[1] = r.avec; route_out[2] = r.bvec; route_out[3] = r.acc64;
+}
+
+// the five element-type instantiations tgemm_launch is called with: (TA, TB, TC, TAcc)
+template <typename F>
+static void tgd_dispatch(int types, F &&f) {
+  switch (types) {
+    case 0: f((float *)nullptr, (float *)nullptr, (float *)nullptr, (float *)nullptr); break;
+    case 1: f((float *)nullptr, (float *)nullptr, (float *)nullptr, (double *)nullptr); break;
+    case 2: f((float *)nullptr, (float *)nullptr, (double *)nullptr, (double *)nullptr); break;
+    case 3: f((double *)nullptr, (double *)nullptr, (double *)nullptr, (double *)nullptr); break;
+    case 4: f((c128 *)nullptr, (c128 *)nullptr, (c128 *)nullptr, (c128 *)nullptr); break;
+    default: throw Error(1, "unsupported element types");
+  }
+}
+
+struct DevBufs {     // device allocations of one diagnostic call, freed on every exit
+  std::vector<void *> p;
+  template <typename T> T *alloc(size_t n, const void *init = nullptr) {
+    void *q = nullptr;
+    PG_CHECK_HIP(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
+    p.push_back(q);
+    if (init && n) PG_CHECK_HIP(hipMemcpy(q, init, n * sizeof(T), hipMemcpyHostToDevice));
+    return (T *)q;
+  }
+  ~DevBufs() { for (void *q : p) (void)hipFree(q); }
+};
+
+extern "C" int pepsgpu_diag_tgemm_route(int types, const int *desc_ints, int n_ints, const long *desc_longs, int n_longs,
+                                        const double *desc_dbls, int n_dbls, long a_offset, long b_offset, int32_t *route_out) {
+  return guarded(nullptr, [&]() {
+    tgd_check(n_ints, n_longs, n_dbls);
+    // no device access: the operand pointers are only tested for alignment (a buffer from hipMalloc, advanced by the offsets)
+    static const int fake_pool[1] = {0};
+    static const float fake_scale[1] = {1.f};
+    static float fake_out[1];
+    TGemmDesc d = tgd_unpack(desc_ints, desc_longs, desc_dbls, fake_pool, fake_scale);
+    if (desc_ints[84]) d.scale_out = fake_out;
+    tgd_dispatch(types, [&](auto *ta, auto *tb, auto *tc, auto *tacc) {
+      using TA = std::remove_pointer_t<decltype(ta)>; using TB = std::remove_pointer_t<decltype(tb)>;
+      using TC = std::remove_pointer_t<decltype(tc)>; using TAcc = std::remove_pointer_t<decltype(tacc)>;
+      (void)tc; (void)tacc;
+      const TA *A = (const TA *)(uintptr_t)4096 + a_offset;
+      const TB *B = (const TB *)(uintptr_t)4096 + b_offset;
+      tgd_put_route(tgemm_route<TA, TB, TC, TAcc>(d, A, B), route_out);
+    });
+  });
+}
+
+extern "C" int pepsgpu_diag_tgemm_desc(int types, const int *desc_ints, int n_ints, const long *desc_longs, int n_longs,
+                                       const double *desc_dbls, int n_dbls, const int32_t *pool, long pool_n, const float *scale_in,
+                                       const void *A, size_t a_elems, long a_offset, const void *B, size_t b_elems, long b_offset,
+                                       void *C, size_t c_elems, float *scale_out, double *norm_log, int32_t *norm_flag,
+                                       int32_t *route_out, unsigned long long *flops_out) {
+  unsigned long long *const saved_flop = tg_flop_counter, *const saved_byte = tg_byte_counter;
+  const int rc = guarded(nullptr, [&]() {
+    tgd_check(n_ints, n_longs, n_dbls);
+    PG_REQUIRE(a_offset >= 0 && (size_t)a_offset <= a_elems && b_offset >= 0 && (size_t)b_offset <= b_elems, 1, "operand offset outside its buffer");
+    const int nbatch = desc_ints[76];
+    DevBufs m;
+    const int *dpool = m.alloc<int>(pool_n > 0 ? (size_t)pool_n : 0, pool);
+    const float *dscale_in = desc_ints[87] ? m.alloc<float>(std::max(nbatch, 0), scale_in) : nullptr;
+    TGemmDesc d = tgd_unpack(desc_ints, desc_longs, desc_dbls, dpool, dscale_in);
+    float *dso = nullptr;
+    double *dnl = nullptr;
+    int *dnf = nullptr;
+    if (desc_ints[84]) d.scale_out = dso = m.alloc<float>(std::max(nbatch, 0), scale_out);
+    if (desc_ints[85]) d.norm_log = dnl = m.alloc<double>(std::max(nbatch, 0), norm_log);
+    if (desc_ints[86]) d.norm_flag = dnf = m.alloc<int>(std::max(nbatch, 0), norm_flag);
+    unsigned long long *dflop = m.alloc<unsigned long long>(1);
+    PG_CHECK_HIP(hipMemset(dflop, 0, sizeof(unsigned long long)));
+    tgd_dispatch(types, [&](auto *ta, auto *tb, auto *tc, auto *tacc) {
+      using TA = std::remove_pointer_t<decltype(ta)>; using TB = std::remove_pointer_t<decltype(tb)>;
+      using TC = std::remove_pointer_t<decltype(tc)>; using TAcc = std::remove_pointer_t<decltype(tacc)>;
+      (void)tacc;
+      const TA *dA = m.alloc<TA>(a_elems, A) + a_offset;
+      const TB *dB = m.alloc<TB>(b_elems, B) + b_offset;
+      TC *dC = m.alloc<TC>(c_elems, C);
+      tgd_put_route(tgemm_route<TA, TB, TC, TAcc>(d, dA, dB), route_out);
+      tg_flop_counter = dflop;
+      tg_byte_counter = nullptr;
+      tgemm_launch<TA, TB, TC, TAcc>(0, d, dA, dB, dC);
+      PG_CHECK_HIP(hipDeviceSynchronize());
+      PG_CHECK_HIP(hipMemcpy(C, dC, c_elems * sizeof(TC), hipMemcpyDeviceToHost));
+      (void)tc;
+    });
+    if (dso) PG_CHECK_HIP(hipMemcpy(scale_out, dso, nbatch * sizeof(float), hipMemcpyDeviceToHost));
+    if (dnl) PG_CHECK_HIP(hipMemcpy(norm_log, dnl, nbatch * sizeof(double), hipMemcpyDeviceToHost));
+    if (dnf) PG_CHECK_HIP(hipMemcpy(norm_flag, dnf, nbatch * sizeof(int), hipMemcpyDeviceToHost));
+    PG_CHECK_HIP(hipMemcpy(flops_out, dflop, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  });
+  tg_flop_counter = saved_flop;
+  tg_byte_counter = saved_byte;
+  return rc;
+}
+
+// One BTen growth step through tgemm_chain3_kernel with the descriptors of Engine::bten_step (bten_chain_descs):
+//   out[b][x,s2,y] = sum mps1[b][x,p1,c] bten[b][c,b1,b2] site[sel[b*sel_inc]][p1,b1,s1,s2] mps2[b][b2,s1,y]
+// dims8 = {x, p1, cdim, b1, b2, s1, s2, y}; site_strides4 = element strides of the site legs (p1, b1, s1, s2), one tensor per
+// slot of `slot` elements, nslots of them; live4 (nullable) = per entry {vx, vc, vb, vy}; skip (nullable) = per entry;
+// offs3 = element offsets of the mps1 / bten / site bases in their buffers (alignment variants).  out holds the initial
+// contents (entries the kernel does not write keep them).  launched_out = the launcher's return (0: shapes declined, nothing
+// launched; 2: launched), flags_out[b] = the kernel's flag, variant_out = {avec1, bvec1, avec2}.
+extern "C" int pepsgpu_diag_tgemm_chain3(const int *dims8, const int *site_strides4, long slot, int nslots, const int32_t *sel, int sel_inc,
+                                         const int32_t *live4, const int32_t *skip, int nbatch, const int *offs3, const float *mps1,
+                                         const float *bten, const float *site, const float *mps2, float *out, int32_t *flags_out,
+                                         int32_t *launched_out, int32_t *variant_out) {
+  return guarded(nullptr, [&]() {
+    const int x = dims8[0], p1 = dims8[1], cdim = dims8[2], b1 = dims8[3], b2 = dims8[4], s1 = dims8[5], s2 = dims8[6], y = dims8[7];
+    PG_REQUIRE(nbatch > 0 && nslots > 0 && sel_inc >= 0 && offs3[0] >= 0 && offs3[1] >= 0 && offs3[2] >= 0, 1, "bad arguments");
+    const long n1 = (long)x * p1 * cdim, nbt = (long)cdim * b1 * b2, n2 = (long)b2 * s1 * y, no = (long)x * s2 * y;
+    DevBufs m;
+    const float *dm1 = m.alloc<float>(n1 * nbatch + offs3[0], mps1) + offs3[0];
+    const float *dbt = m.alloc<float>(nbt * nbatch + offs3[1], bten) + offs3[1];
+    const float *dsite = m.alloc<float>((size_t)slot * nslots + offs3[2], site) + offs3[2];
+    const float *dm2 = m.alloc<float>(n2 * nbatch, mps2);
+    float *dout = m.alloc<float>(no * nbatch, out);
+    const int *dsel = m.alloc<int>((size_t)(nbatch - 1) * sel_inc + 1, sel);
+    int *dflag = m.alloc<int>(nbatch, flags_out);
+    const int *dskip = skip ? m.alloc<int>(nbatch, skip) : nullptr;
+    const int *vl[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (live4) {
+      std::vector<int> h(4 * (size_t)nbatch);     // [vx | vc | vb | vy] as four arrays
+      for (int b = 0; b < nbatch; ++b)
+        for (int q = 0; q < 4; ++q) h[(size_t)q * nbatch + b] = live4[4 * b + q];
+      const int *dl = m.alloc<int>(h.size(), h.data());
+      for (int q = 0; q < 4; ++q) vl[q] = dl + (size_t)q * nbatch;
+    }
+    const BTenChainDescs cd = bten_chain_descs(x, p1, cdim, b1, b2, s1, s2, y, site_strides4[0], site_strides4[1], site_strides4[2],
+                                               site_strides4[3], n1, nbt, n2, dsel, sel_inc, slot, nbatch, vl[0], vl[1], vl[2], vl[3]);
+    variant_out[0] = tg_vec_a(cd.g1, dm1); variant_out[1] = tg_vec_b(cd.g1, dbt); variant_out[2] = tg_vec_a(cd.g2, dsite);
+    launched_out[0] = tgemm_chain3_launch(0, cd.g1, cd.g2, cd.g3, cd.mp, cd.mp3, dm1, dbt, dsite, dm2, dout, dflag, dskip);
+    PG_CHECK_HIP(hipDeviceSynchronize());
+    PG_CHECK_HIP(hipMemcpy(out, dout, no * nbatch * sizeof(float), hipMemcpyDeviceToHost));
+    PG_CHECK_HIP(hipMemcpy(flags_out, dflag, nbatch * sizeof(int), hipMemcpyDeviceToHost));
+  });
+}
+
 // Forward pair of an absorption through tgemm_chain_kernel exactly as Engine::absorb_impl sets it up:
 //   X[m,l,p,a2] = sum_a R[m,l,a] A[a,p,a2]  (kept in LDS),   P[m,u,l2,a2] = sum_{l,p} W[l,p,l2,u] X[m,l,p,a2]
 // dims = {m, l, a, p, a2, l2, u} (static), live = per entry {m_live, a_live, a2_live}; W is one tensor per entry.

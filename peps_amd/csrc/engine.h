@@ -1194,22 +1194,10 @@ class Engine : public EngineBase {
       if (!no_btc && ncand == 1 && bt_ncand == 1 && x * p1 > 1 && b1 * b2 > 1) {
         tmp2c = alloc_ten(b2, x, s1, s2, nb);
         bt_chain_flag = (int *)arena_.alloc(sizeof(int) * nb);
-        TGemmDesc g1, g2;
-        g1.I[1] = x; g1.I[2] = p1; g1.sAi[1] = p1 * cdim; g1.sAi[2] = cdim; g1.sCi[1] = p1 * b1 * b2; g1.sCi[2] = b1 * b2;
-        g1.K[2] = cdim; g1.sAk[2] = 1; g1.sBk[2] = b1 * b2;
-        g1.J[1] = b1; g1.J[2] = b2; g1.sBj[1] = b2; g1.sBj[2] = 1; g1.sCj[1] = b2; g1.sCj[2] = 1;
-        g1.wA = mps1.n; g1.wB = bt.t.n; g1.wC = (long)x * p1 * b1 * b2; g1.nbatch = nb;
-        g1.dI[1].p = vx; g1.dK[2].p = vc; g1.dJ[2].p = vb;
-        // tmp2[b2,x,s1,s2] = sum_{p1,b1} site[p1,b1,s1,s2] tmp1[x,p1,b1,b2]:  I2 = (s1, s2), K2 = (p1, b1), J2 = (x, b2)
-        g2.I[1] = s1; g2.I[2] = s2; g2.sAi[1] = st[l1]; g2.sAi[2] = st[l2]; g2.sCi[1] = s2; g2.sCi[2] = 1;
-        g2.K[1] = p1; g2.K[2] = b1; g2.sAk[1] = st[lc]; g2.sAk[2] = st[lb]; g2.sBk[1] = b1 * b2; g2.sBk[2] = b2;
-        g2.J[1] = x; g2.J[2] = b2; g2.sBj[1] = p1 * b1 * b2; g2.sBj[2] = 1; g2.sCj[1] = s1 * s2; g2.sCj[2] = x * s1 * s2;
-        g2.wB = g1.wC; g2.wC = tmp2c.n; g2.nbatch = nb;
-        g2.dJ[1].p = vx; g2.dJ[2].p = vb;
-        g2.selA = ss.sel; g2.selA_mul = slot_; g2.selA_inc = ss.inc; g2.seldivA = 1; g2.wA = 0;
-        TGemmChainMap mp;
-        mp.mapK[1] = 2; mp.mapK[2] = 4;      // K2 = (p1, b1): p1 = I1[2], b1 = J1[1]
-        mp.mapJ[1] = 1; mp.mapJ[2] = 5;      // J2 = (x, b2):  x = I1[1],  b2 = J1[2]
+        const BTenChainDescs cd = bten_chain_descs(x, p1, cdim, b1, b2, s1, s2, y, st[lc], st[lb], st[l1], st[l2], mps1.n, bt.t.n, mps2.n,
+                                                   ss.sel, ss.inc, slot_, nb, vx, vc, vb, vy);
+        const TGemmDesc &g1 = cd.g1, &g2 = cd.g2;
+        const TGemmChainMap &mp = cd.mp;
         const double fl = 2.0 * nb * ((double)(x * p1) * cdim * (double)(b1 * b2) + (double)(b2 * x) * (double)(p1 * b1) * (double)(s1 * s2));
         // round 4: all three contractions in one launch (tgemm_chain3_kernel: tmp1 and tmp2 resident in LDS, the bond x walked in
         // chunks when the live intermediates exceed the buffers) (the two-stage chain + separate launch of round 3 was a switch until round 6)
@@ -1220,21 +1208,10 @@ class Engine : public EngineBase {
         const long per_x = (long)p1 * b1 * b2;
         const bool few_chunks = per_x <= 4096 && (x + (4096 / per_x) - 1) / (4096 / per_x) <= 3;
         if (!no_bt3 && few_chunks) {
-          TGemmDesc g3;
-          g3.I[1] = x; g3.I[2] = s2; g3.sCi[1] = s2 * y; g3.sCi[2] = y;
-          g3.K[1] = b2; g3.K[2] = s1; g3.sBk[1] = s1 * y; g3.sBk[2] = y;
-          g3.J[2] = y; g3.sBj[2] = 1; g3.sCj[2] = 1;
-          g3.wB = mps2.n; g3.nbatch = nb;
-          g3.dI[1].p = vx; g3.dI[1].mask = 1;     // the new BTen is written in full
-          g3.dK[1].p = vb;
-          g3.dJ[2].p = vy; g3.dJ[2].mask = 1;
-          TGemmChain3Map mp3;
-          mp3.mapI[1] = 4; mp3.mapI[2] = 2;    // I3 = (x, s2):  x = J2[1],  s2 = I2[2]
-          mp3.mapK[1] = 5; mp3.mapK[2] = 1;    // K3 = (b2, s1): b2 = J2[2], s1 = I2[1]
-          mp3.chunkI = 1;
+          const TGemmDesc &g3 = cd.g3;
+          const TGemmChain3Map &mp3 = cd.mp3;
           BTenDev o3;
           o3.t = alloc_ten(x, s2, y, 1, nb);
-          g3.wC = o3.t.n;
           const double fl3 = fl + 2.0 * nb * (double)(x * s2) * (double)(b2 * s1) * (double)y;
           prof_begin(PROF_ENV, fl3, fl3);
           const int done = tgemm_chain3_launch(stream_, g1, g2, g3, mp, mp3, (const float *)mps1.p, (const float *)bt.t.p,

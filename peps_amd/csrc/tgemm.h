@@ -1112,13 +1112,20 @@ __global__ __launch_bounds__(256, MINB) void tgemm_chain3_kernel(TGemmDesc d1, T
   const int n1 = d1.I[1];                                   // live extent of the chunked sub-index
   const int per1 = lds1[1], per2 = n1 > 0 ? st2 / n1 : 0;   // floats of C1 / C2 per value of it
   if (jsub < 0 || jsub > 2 || mp3.chunkI < 0 || d1.I[0] != 1 || d1.dynI || d2.dynI || d3.dynI || d1.Imask[1] != 0x7fffffff ||
-      per1 > LDSF || per2 > LDSF || I1 <= 0 || J1 <= 0 || I2 <= 0 || J2 <= 0 || J3 <= 0 || d3.Ktot() <= 0) {
+      per1 > LDSF || per2 > LDSF) {
     if (threadIdx.x == 0) flag[b] = -1;
     return;
   }
   if (threadIdx.x == 0) flag[b] = 0;
-  const int chunk = min(n1, min(LDSF / per1, LDSF / per2));
   const int sC3 = mp3.chunkI == 0 ? d3.sCi[0] : mp3.chunkI == 1 ? d3.sCi[1] : d3.sCi[2];
+  float *C3 = C3g + (long)b * d3.wC;
+  if (I1 <= 0 || J1 <= 0 || I2 <= 0 || J2 <= 0 || J3 <= 0 || d3.Ktot() <= 0) {
+    // a live extent 0 (the environment of a configuration of zero amplitude): the result is zero, written in full as below
+    // (the launcher promises that no entry is declined: the caller reads C3 of every entry)
+    for (long e = threadIdx.x; e < (long)x_static * sC3; e += 256) C3[e] = 0.f;
+    return;
+  }
+  const int chunk = min(n1, min(LDSF / per1, LDSF / per2));
   if (d1.flopc && threadIdx.x == 0 && b % d1.flop_stride == 0) {
     const unsigned long long i3 = (unsigned long long)(d3.Itot() / max(1, x_static)) * n1;
     atomicAdd(d1.flopc, 2ull * d1.flop_stride * ((unsigned long long)I1 * J1 * d1.Ktot() + (unsigned long long)I2 * J2 * d2.Ktot() + i3 * J3 * d3.Ktot()));
@@ -1132,7 +1139,6 @@ __global__ __launch_bounds__(256, MINB) void tgemm_chain3_kernel(TGemmDesc d1, T
   if (d2.selA) baseA2 += (long)d2.selA[(long)(b / d2.seldivA) * d2.selA_inc] * d2.selA_mul;
   d1.accumulate = 0; d2.accumulate = 0;
   const float in_scale = d1.scale_in ? d1.scale_in[b] : 1.f;
-  float *C3 = C3g + (long)b * d3.wC;
   const int sA1 = d1.sAi[1];
   for (int c0 = 0; c0 < n1; c0 += chunk) {
     const int cn = min(chunk, n1 - c0);
@@ -1186,6 +1192,49 @@ inline int tgemm_chain3_launch(hipStream_t s, const TGemmDesc &d1_in, const TGem
                                const TGemmChain3Map &mp3, const float *A1, const float *B1, const float *A2, const float *B3, float *C3, int *flag,
                                const int *skip = nullptr);
 
+// The descriptors of one BTen growth step (Engine::bten_step), shared by the engine and its kernel test:
+//   tmp1[x,p1,b1,b2] = sum_c mps1[x,p1,c] bten[c,b1,b2]                      (g1)
+//   tmp2[b2,x,s1,s2] = sum_{p1,b1} site[p1,b1,s1,s2] tmp1[x,p1,b1,b2]         (g2, site selected by sel)
+//   out[x,s2,y]      = sum_{b2,s1} tmp2[b2,x,s1,s2] mps2[b2,s1,y]             (g3, through tgemm_chain3_kernel)
+// st_c / st_b / st_1 / st_2: element strides of the site tensor's legs p1, b1, s1, s2; wA1 / wB1 / wB3: batch strides of mps1,
+// bten and mps2; vx / vc / vb / vy (nullable, per entry): live extents of the bonds x, c, b2, y.
+struct BTenChainDescs {
+  TGemmDesc g1, g2, g3;
+  TGemmChainMap mp;
+  TGemmChain3Map mp3;
+};
+inline BTenChainDescs bten_chain_descs(int x, int p1, int cdim, int b1, int b2, int s1, int s2, int y, int st_c, int st_b, int st_1,
+                                       int st_2, long wA1, long wB1, long wB3, const int *sel, int sel_inc, long slot, int nb,
+                                       const int *vx, const int *vc, const int *vb, const int *vy) {
+  BTenChainDescs c;
+  TGemmDesc &g1 = c.g1, &g2 = c.g2, &g3 = c.g3;
+  g1.I[1] = x; g1.I[2] = p1; g1.sAi[1] = p1 * cdim; g1.sAi[2] = cdim; g1.sCi[1] = p1 * b1 * b2; g1.sCi[2] = b1 * b2;
+  g1.K[2] = cdim; g1.sAk[2] = 1; g1.sBk[2] = b1 * b2;
+  g1.J[1] = b1; g1.J[2] = b2; g1.sBj[1] = b2; g1.sBj[2] = 1; g1.sCj[1] = b2; g1.sCj[2] = 1;
+  g1.wA = wA1; g1.wB = wB1; g1.wC = (long)x * p1 * b1 * b2; g1.nbatch = nb;
+  g1.dI[1].p = vx; g1.dK[2].p = vc; g1.dJ[2].p = vb;
+  // tmp2[b2,x,s1,s2] = sum_{p1,b1} site[p1,b1,s1,s2] tmp1[x,p1,b1,b2]:  I2 = (s1, s2), K2 = (p1, b1), J2 = (x, b2)
+  g2.I[1] = s1; g2.I[2] = s2; g2.sAi[1] = st_1; g2.sAi[2] = st_2; g2.sCi[1] = s2; g2.sCi[2] = 1;
+  g2.K[1] = p1; g2.K[2] = b1; g2.sAk[1] = st_c; g2.sAk[2] = st_b; g2.sBk[1] = b1 * b2; g2.sBk[2] = b2;
+  g2.J[1] = x; g2.J[2] = b2; g2.sBj[1] = p1 * b1 * b2; g2.sBj[2] = 1; g2.sCj[1] = s1 * s2; g2.sCj[2] = x * s1 * s2;
+  g2.wB = g1.wC; g2.wC = (long)b2 * x * s1 * s2; g2.nbatch = nb;
+  g2.dJ[1].p = vx; g2.dJ[2].p = vb;
+  g2.selA = sel; g2.selA_mul = slot; g2.selA_inc = sel_inc; g2.seldivA = 1; g2.wA = 0;
+  c.mp.mapK[1] = 2; c.mp.mapK[2] = 4;      // K2 = (p1, b1): p1 = I1[2], b1 = J1[1]
+  c.mp.mapJ[1] = 1; c.mp.mapJ[2] = 5;      // J2 = (x, b2):  x = I1[1],  b2 = J1[2]
+  g3.I[1] = x; g3.I[2] = s2; g3.sCi[1] = s2 * y; g3.sCi[2] = y;
+  g3.K[1] = b2; g3.K[2] = s1; g3.sBk[1] = s1 * y; g3.sBk[2] = y;
+  g3.J[2] = y; g3.sBj[2] = 1; g3.sCj[2] = 1;
+  g3.wB = wB3; g3.wC = (long)x * s2 * y; g3.nbatch = nb;
+  g3.dI[1].p = vx; g3.dI[1].mask = 1;     // the new BTen is written in full
+  g3.dK[1].p = vb;
+  g3.dJ[2].p = vy; g3.dJ[2].mask = 1;
+  c.mp3.mapI[1] = 4; c.mp3.mapI[2] = 2;    // I3 = (x, s2):  x = J2[1],  s2 = I2[2]
+  c.mp3.mapK[1] = 5; c.mp3.mapK[2] = 1;    // K3 = (b2, s1): b2 = J2[2], s1 = I2[1]
+  c.mp3.chunkI = 1;
+  return c;
+}
+
 bool tgemm_use_mfma();
 
 // device counter the launches of the current profiling bracket add their contracted flops to (engine.h prof_begin)
@@ -1203,19 +1252,47 @@ inline bool tgemm_one_block_direct(const TGemmDesc &d) {
          !d.batch_flag && d.nbatch > 0 && d.Itot() > 0 && d.Jtot() > 0 && !d.prefer_tiled;
 }
 
+// 16-byte loads along k2 (the AVEC / BVEC forms of the wave-per-tile bodies): the operand is contiguous there and every other
+// offset keeps the alignment
+inline bool tg_vec_a(const TGemmDesc &d, const void *A) {
+  auto al4 = [](long v) { return (v & 3) == 0; };
+  return d.sAk[2] == 1 && al4(d.K[2]) && al4(d.sAi[0]) && al4(d.sAi[1]) && al4(d.sAi[2]) && al4(d.sAk[0]) && al4(d.sAk[1]) &&
+         al4(d.wA) && al4(d.selA_mul) && (((uintptr_t)A) & 15) == 0;
+}
+inline bool tg_vec_b(const TGemmDesc &d, const void *B) {
+  auto al4 = [](long v) { return (v & 3) == 0; };
+  return d.sBk[2] == 1 && al4(d.K[2]) && al4(d.sBj[0]) && al4(d.sBj[1]) && al4(d.sBj[2]) && al4(d.sBk[0]) && al4(d.sBk[1]) &&
+         al4(d.wB) && al4(d.selB_mul) && (((uintptr_t)B) & 15) == 0;
+}
+
+// The kernel tgemm_launch takes for a descriptor (host-side, no device access: the pointers are only tested for alignment).
+enum TgRouteKind : int {
+  TG_ROUTE_EMPTY = 0,          // nothing to compute (no batch entry, or a static extent 0): no launch
+  TG_ROUTE_DIRECT = 1,         // tgemm_direct_kernel<avec, bvec, acc64> (wave per 32 x 32 tile, f32 in / out)
+  TG_ROUTE_SKINNY_128x32 = 2,  // tgemm_skinny_f64_kernel<.., 128, 32> (float64 accumulation, J <= 32)
+  TG_ROUTE_SKINNY_32x128 = 3,  // tgemm_skinny_f64_kernel<.., 32, 128> (float64 accumulation, I <= 32)
+  TG_ROUTE_TILED_MFMA = 4,     // tgemm_kernel<.., true> (64 x 64 LDS tiles on the matrix cores)
+  TG_ROUTE_TILED_VALU = 5,     // tgemm_kernel<.., false> (the same tiling on the vector ALUs)
+  TG_ROUTE_REFUSED = 6,        // the descriptor is rejected: status `code`, message `msg`
+};
+struct TgRoute {
+  int kind = TG_ROUTE_EMPTY;
+  bool avec = false, bvec = false, acc64 = false;   // direct kernel: 16-byte loads of A / B along k2, float64 accumulation
+  dim3 grid;
+  int code = 0;
+  const char *msg = nullptr;
+};
+
 template <typename TA, typename TB, typename TC, typename TAcc>
-void tgemm_launch(hipStream_t s, const TGemmDesc &d_in, const TA *A, const TB *B, TC *C) {
-  if (d_in.nbatch <= 0 || d_in.Itot() <= 0 || d_in.Jtot() <= 0) return;
-  TGemmDesc d = d_in;
-  PG_REQUIRE(d.nbatch <= 65535, 1, "walkers x candidates exceeds 65535 (grid z limit): use a smaller walker batch");
-  d.flopc = tg_flop_counter;
-  d.bytec = tg_byte_counter;
-  d.flop_stride = d.nbatch >= 256 ? 64 : 1;   // one atomic per 64 walkers: a same-address atomic per block costs ~10 %
-  bool fused_norm_ok = false;
+TgRoute tgemm_route(const TGemmDesc &d, const void *A, const void *B) {
+  TgRoute r;
+  if (d.nbatch <= 0 || d.Itot() <= 0 || d.Jtot() <= 0) return r;
+  auto refuse = [&](int code, const char *msg) { r.kind = TG_ROUTE_REFUSED; r.code = code; r.msg = msg; return r; };
+  if (!(d.nbatch <= 65535)) return refuse(1, "walkers x candidates exceeds 65535 (grid z limit): use a smaller walker batch");
   int gx = (d.Itot() + TG_BM - 1) / TG_BM;
   const bool dyn_i = d.dynI || (d.dI[0].p && !d.dI[0].mask) || (d.dI[1].p && !d.dI[1].mask) || (d.dI[2].p && !d.dI[2].mask);
   if (dyn_i && gx > TG_DYN_GRIDX) gx = TG_DYN_GRIDX;
-  dim3 grid(gx, (d.Jtot() + TG_BN - 1) / TG_BN, d.nbatch);
+  r.grid = dim3(gx, (d.Jtot() + TG_BN - 1) / TG_BN, d.nbatch);
   if constexpr (sizeof(TA) == 4 && sizeof(TB) == 4 && sizeof(TC) == 4 && sizeof(TAcc) == 4) {
     // small per-walker extents (rank-adaptive absorption): wave-per-tile kernel without LDS staging
     constexpr int direct_mode = 1;
@@ -1223,40 +1300,23 @@ void tgemm_launch(hipStream_t s, const TGemmDesc &d_in, const TA *A, const TB *B
     const bool any_dyn = dyn_i || d.dK[0].p || d.dK[1].p || d.dK[2].p || d.dJ[0].p || d.dJ[1].p || d.dJ[2].p;
     if (tgemm_use_mfma() && !d.dynK && !d.prefer_tiled && (direct_mode == 2 || (direct_mode == 1 && any_dyn))) {
       // 16-byte loads along k2 where the operand is contiguous there and every other offset keeps the alignment
-      auto al4 = [](long v) { return (v & 3) == 0; };
-      const bool avec = !no_vec && d.sAk[2] == 1 && al4(d.K[2]) && al4(d.sAi[0]) && al4(d.sAi[1]) && al4(d.sAi[2]) &&
-                        al4(d.sAk[0]) && al4(d.sAk[1]) && al4(d.wA) && al4(d.selA_mul) && (((uintptr_t)A) & 15) == 0;
-      const bool bvec = !no_vec && d.sBk[2] == 1 && al4(d.K[2]) && al4(d.sBj[0]) && al4(d.sBj[1]) && al4(d.sBj[2]) &&
-                        al4(d.sBk[0]) && al4(d.sBk[1]) && al4(d.wB) && al4(d.selB_mul) && (((uintptr_t)B) & 15) == 0;
+      r.avec = !no_vec && tg_vec_a(d, A);
+      r.bvec = !no_vec && tg_vec_b(d, B);
+      r.acc64 = d.acc64 != 0;
       // (the wave-per-tile body splits row / column indices through a float reciprocal and addresses in 32-bit bytes)
-      PG_REQUIRE(d.Itot() < (1 << 22) && d.Jtot() < (1 << 22), 1, "tensor GEMM: more than 2^22 rows / columns in one batch entry");
-      fused_norm_ok = true;
+      if (!(d.Itot() < (1 << 22) && d.Jtot() < (1 << 22))) return refuse(1, "tensor GEMM: more than 2^22 rows / columns in one batch entry");
       const int tiles = ((d.Itot() + 31) / 32) * ((d.Jtot() + 31) / 32);
       // with per-walker live extents the tile count is a few: one block (four waves) walks them; extra blocks
       // would only pay the chain of dependent loads (extents, selector, offsets) and exit
       constexpr int gx_dyn = 1;
-      const dim3 gd(any_dyn ? std::min(gx_dyn, std::max(1, tiles / 4)) : (tiles >= 64 ? 4 : tiles >= 16 ? 2 : 1), 1,
-                    d.nbatch);
-      PG_REQUIRE(!d.scale_out || (gd.x == 1 && d.bdivC == 1 && !d.accumulate && !d.batch_flag), 5,
-                 "tensor GEMM: the norm of the result needs one block per batch entry");
-      const float *Af = (const float *)A, *Bf = (const float *)B;
-      float *Cf = (float *)C;
-      if (d.acc64) {
-        if (avec && bvec) hipLaunchKernelGGL((tgemm_direct_kernel<true, true, true>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
-        else if (avec) hipLaunchKernelGGL((tgemm_direct_kernel<true, false, true>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
-        else if (bvec) hipLaunchKernelGGL((tgemm_direct_kernel<false, true, true>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
-        else hipLaunchKernelGGL((tgemm_direct_kernel<false, false, true>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
-      }
-      else if (avec && bvec) hipLaunchKernelGGL((tgemm_direct_kernel<true, true>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
-      else if (avec) hipLaunchKernelGGL((tgemm_direct_kernel<true, false>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
-      else if (bvec) hipLaunchKernelGGL((tgemm_direct_kernel<false, true>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
-      else hipLaunchKernelGGL((tgemm_direct_kernel<false, false>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
-      PG_CHECK_HIP(hipGetLastError());
-      return;
+      r.grid = dim3(any_dyn ? std::min(gx_dyn, std::max(1, tiles / 4)) : (tiles >= 64 ? 4 : tiles >= 16 ? 2 : 1), 1, d.nbatch);
+      if (!(!d.scale_out || (r.grid.x == 1 && d.bdivC == 1 && !d.accumulate && !d.batch_flag)))
+        return refuse(5, "tensor GEMM: the norm of the result needs one block per batch entry");
+      r.kind = TG_ROUTE_DIRECT;
+      return r;
     }
   }
-  (void)fused_norm_ok;
-  PG_REQUIRE(!d.scale_out && !d.scale_in, 5, "tensor GEMM: scale_in / scale_out need the wave-per-tile kernel");
+  if (!(!d.scale_out && !d.scale_in)) return refuse(5, "tensor GEMM: scale_in / scale_out need the wave-per-tile kernel");
   if constexpr (std::is_same<TAcc, double>::value && !is_cplx<TA>::value && !is_cplx<TB>::value && !is_cplx<TC>::value) {
     // skinny float64-accumulated products (one side <= 32): 128 x 32 / 32 x 128 block tiles, every wave on a live quadrant
     constexpr bool no_skinny = false;
@@ -1264,14 +1324,14 @@ void tgemm_launch(hipStream_t s, const TGemmDesc &d_in, const TA *A, const TB *B
       if (d.Jtot() <= 32 && d.Itot() >= 64) {
         int gxs = (d.Itot() + 127) / 128;
         if (dyn_i && gxs > TG_DYN_GRIDX) gxs = TG_DYN_GRIDX;
-        hipLaunchKernelGGL((tgemm_skinny_f64_kernel<TA, TB, TC, 128, 32>), dim3(gxs, 1, d.nbatch), dim3(256), 0, s, d, A, B, C);
-        PG_CHECK_HIP(hipGetLastError());
-        return;
+        r.grid = dim3(gxs, 1, d.nbatch);
+        r.kind = TG_ROUTE_SKINNY_128x32;
+        return r;
       }
       if (d.Itot() <= 32 && d.Jtot() >= 64) {
-        hipLaunchKernelGGL((tgemm_skinny_f64_kernel<TA, TB, TC, 32, 128>), dim3(1, (d.Jtot() + 127) / 128, d.nbatch), dim3(256), 0, s, d, A, B, C);
-        PG_CHECK_HIP(hipGetLastError());
-        return;
+        r.grid = dim3(1, (d.Jtot() + 127) / 128, d.nbatch);
+        r.kind = TG_ROUTE_SKINNY_32x128;
+        return r;
       }
     }
   }
@@ -1279,19 +1339,57 @@ void tgemm_launch(hipStream_t s, const TGemmDesc &d_in, const TA *A, const TB *B
     // complex element type: four real v_mfma_f64_16x16x4_f64 products per tile from the interleaved LDS operands
     // (the same tiling on the vector ALUs was round 2's path: USE_MFMA = false)
     constexpr bool no_cmfma = false;
-    if constexpr (std::is_same<TAcc, c128>::value) {
-      if (tgemm_use_mfma() && !no_cmfma) {
-        hipLaunchKernelGGL((tgemm_kernel<TA, TB, TC, TAcc, true>), grid, dim3(256), 0, s, d, A, B, C);
-        PG_CHECK_HIP(hipGetLastError());
-        return;
-      }
-    }
-    hipLaunchKernelGGL((tgemm_kernel<TA, TB, TC, TAcc, false>), grid, dim3(256), 0, s, d, A, B, C);
+    r.kind = (std::is_same<TAcc, c128>::value && tgemm_use_mfma() && !no_cmfma) ? TG_ROUTE_TILED_MFMA : TG_ROUTE_TILED_VALU;
   } else {
-    if (tgemm_use_mfma())
-      hipLaunchKernelGGL((tgemm_kernel<TA, TB, TC, TAcc, true>), grid, dim3(256), 0, s, d, A, B, C);
-    else
-      hipLaunchKernelGGL((tgemm_kernel<TA, TB, TC, TAcc, false>), grid, dim3(256), 0, s, d, A, B, C);
+    r.kind = tgemm_use_mfma() ? TG_ROUTE_TILED_MFMA : TG_ROUTE_TILED_VALU;
+  }
+  return r;
+}
+
+template <typename TA, typename TB, typename TC, typename TAcc>
+void tgemm_launch(hipStream_t s, const TGemmDesc &d_in, const TA *A, const TB *B, TC *C) {
+  const TgRoute r = tgemm_route<TA, TB, TC, TAcc>(d_in, A, B);
+  if (r.kind == TG_ROUTE_EMPTY) return;
+  PG_REQUIRE(r.kind != TG_ROUTE_REFUSED, r.code, r.msg);
+  TGemmDesc d = d_in;
+  d.flopc = tg_flop_counter;
+  d.bytec = tg_byte_counter;
+  d.flop_stride = d.nbatch >= 256 ? 64 : 1;   // one atomic per 64 walkers: a same-address atomic per block costs ~10 %
+  switch (r.kind) {
+    case TG_ROUTE_DIRECT:
+      if constexpr (sizeof(TA) == 4 && sizeof(TB) == 4 && sizeof(TC) == 4 && sizeof(TAcc) == 4) {
+        const float *Af = (const float *)A, *Bf = (const float *)B;
+        float *Cf = (float *)C;
+        const dim3 gd = r.grid;
+        const bool avec = r.avec, bvec = r.bvec;
+        if (r.acc64) {
+          if (avec && bvec) hipLaunchKernelGGL((tgemm_direct_kernel<true, true, true>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
+          else if (avec) hipLaunchKernelGGL((tgemm_direct_kernel<true, false, true>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
+          else if (bvec) hipLaunchKernelGGL((tgemm_direct_kernel<false, true, true>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
+          else hipLaunchKernelGGL((tgemm_direct_kernel<false, false, true>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
+        }
+        else if (avec && bvec) hipLaunchKernelGGL((tgemm_direct_kernel<true, true>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
+        else if (avec) hipLaunchKernelGGL((tgemm_direct_kernel<true, false>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
+        else if (bvec) hipLaunchKernelGGL((tgemm_direct_kernel<false, true>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
+        else hipLaunchKernelGGL((tgemm_direct_kernel<false, false>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
+      }
+      break;
+    case TG_ROUTE_SKINNY_128x32:
+    case TG_ROUTE_SKINNY_32x128:
+      if constexpr (std::is_same<TAcc, double>::value && !is_cplx<TA>::value && !is_cplx<TB>::value && !is_cplx<TC>::value) {
+        if (r.kind == TG_ROUTE_SKINNY_128x32)
+          hipLaunchKernelGGL((tgemm_skinny_f64_kernel<TA, TB, TC, 128, 32>), r.grid, dim3(256), 0, s, d, A, B, C);
+        else
+          hipLaunchKernelGGL((tgemm_skinny_f64_kernel<TA, TB, TC, 32, 128>), r.grid, dim3(256), 0, s, d, A, B, C);
+      }
+      break;
+    case TG_ROUTE_TILED_MFMA:
+      if constexpr (!is_cplx<TAcc>::value || std::is_same<TAcc, c128>::value)
+        hipLaunchKernelGGL((tgemm_kernel<TA, TB, TC, TAcc, true>), r.grid, dim3(256), 0, s, d, A, B, C);
+      break;
+    default:
+      hipLaunchKernelGGL((tgemm_kernel<TA, TB, TC, TAcc, false>), r.grid, dim3(256), 0, s, d, A, B, C);
+      break;
   }
   PG_CHECK_HIP(hipGetLastError());
 }
@@ -1308,13 +1406,7 @@ inline int tgemm_chain_launch(hipStream_t s, const TGemmDesc &d1_in, const TGemm
   d1.flopc = tg_flop_counter; d1.bytec = tg_byte_counter;
   d1.flop_stride = d1.nbatch >= 256 ? 64 : 1;
   constexpr bool no_vec = false;
-  auto al4 = [](long v) { return (v & 3) == 0; };
-  const bool avec1 = !no_vec && d1.sAk[2] == 1 && al4(d1.K[2]) && al4(d1.sAi[0]) && al4(d1.sAi[1]) && al4(d1.sAi[2]) &&
-                     al4(d1.sAk[0]) && al4(d1.sAk[1]) && al4(d1.wA) && al4(d1.selA_mul) && (((uintptr_t)A1) & 15) == 0;
-  const bool bvec1 = !no_vec && d1.sBk[2] == 1 && al4(d1.K[2]) && al4(d1.sBj[0]) && al4(d1.sBj[1]) && al4(d1.sBj[2]) &&
-                     al4(d1.sBk[0]) && al4(d1.sBk[1]) && al4(d1.wB) && al4(d1.selB_mul) && (((uintptr_t)B1) & 15) == 0;
-  const bool avec2 = !no_vec && d2.sAk[2] == 1 && al4(d2.K[2]) && al4(d2.sAi[0]) && al4(d2.sAi[1]) && al4(d2.sAi[2]) &&
-                     al4(d2.sAk[0]) && al4(d2.sAk[1]) && al4(d2.wA) && al4(d2.selA_mul) && (((uintptr_t)A2) & 15) == 0;
+  const bool avec1 = !no_vec && tg_vec_a(d1, A1), bvec1 = !no_vec && tg_vec_b(d1, B1), avec2 = !no_vec && tg_vec_a(d2, A2);
   const dim3 g(d1.nbatch), blk(256);
   // dense walker batch (hint of the caller): the intermediate is walked in chunks anyway; a 32 KB buffer holds four values of
   // the chunked sub-index = 32 full rows per stage-1 tile and eight balanced stage-2 tiles (24 KB: 24 rows, six tiles), at four
@@ -1381,13 +1473,7 @@ inline int tgemm_chain3_launch(hipStream_t s, const TGemmDesc &d1_in, const TGem
   d1.flopc = tg_flop_counter; d1.bytec = tg_byte_counter;
   d1.flop_stride = d1.nbatch >= 256 ? 64 : 1;
   constexpr bool no_vec = false;
-  auto al4 = [](long v) { return (v & 3) == 0; };
-  const bool avec1 = !no_vec && d1.sAk[2] == 1 && al4(d1.K[2]) && al4(d1.sAi[0]) && al4(d1.sAi[1]) && al4(d1.sAi[2]) &&
-                     al4(d1.sAk[0]) && al4(d1.sAk[1]) && al4(d1.wA) && al4(d1.selA_mul) && (((uintptr_t)A1) & 15) == 0;
-  const bool bvec1 = !no_vec && d1.sBk[2] == 1 && al4(d1.K[2]) && al4(d1.sBj[0]) && al4(d1.sBj[1]) && al4(d1.sBj[2]) &&
-                     al4(d1.sBk[0]) && al4(d1.sBk[1]) && al4(d1.wB) && al4(d1.selB_mul) && (((uintptr_t)B1) & 15) == 0;
-  const bool avec2 = !no_vec && d2.sAk[2] == 1 && al4(d2.K[2]) && al4(d2.sAi[0]) && al4(d2.sAi[1]) && al4(d2.sAi[2]) &&
-                     al4(d2.sAk[0]) && al4(d2.sAk[1]) && al4(d2.wA) && al4(d2.selA_mul) && (((uintptr_t)A2) & 15) == 0;
+  const bool avec1 = !no_vec && tg_vec_a(d1, A1), bvec1 = !no_vec && tg_vec_b(d1, B1), avec2 = !no_vec && tg_vec_a(d2, A2);
   const dim3 g(d1.nbatch), blk(256);
 #define PG_CHAIN3(a1, b1, a2)                                                                                                               \
   do {                                                                                                                                      \

@@ -17,10 +17,15 @@ sharded, no data-path collective (weak scaling).
     --dump-outputs DIR   after the timed steps, the amplitudes the last timed step returned -> DIR/amplitudes.npy
                          (float64; inputs are seeded, so two builds can be compared output for output)
     --details FILE       the full record of every leg -> FILE (stdout carries a compact line of a few KB)
+    --full               everything else the benchmark measures or checks (below); off by default
 
-The JSON line carries, besides the headline leg (the SURVEY 8(d) synthetic state, numerically of low rank),
-a second leg `full_rank` on i.i.d. random site tensors (--noise 1.0) of the same shapes: the regime in which the
-dense MFMA GEMMs and the chi-truncation of full 256 x 256 blocks dominate.
+A plain run sets up, warms up, times the steps, dumps if asked and prints its line: the headline leg (the SURVEY 8(d)
+synthetic state, numerically of low rank) with the kernel times and the roofline of its own timed steps.  With --full
+the line also carries the legs `full_rank` (i.i.d. random site tensors, --noise 1.0, same shapes: the regime in which
+the dense MFMA GEMMs and the chi-truncation of full 256 x 256 blocks dominate) and `real_rank`
+(the reference's optimised state tiled to L x L), the CPU baseline and the oracle parity samples, the route check, the
+one-walker latency, the MC sweep / VMC sample rates, the other modes and BASELINE configs and, for N > 1 over RCCL, the
+exchange step.  The --no-* switches skip parts of a --full run.
 """
 import argparse
 import json
@@ -82,6 +87,9 @@ def parse():
                          "main leg) as DIR/<name>.npy, float64, at most 64 MB (a fixed, seeded sample of a larger batch)")
     ap.add_argument("--details", metavar="FILE", default=None,
                     help="write the full JSON record of every leg to FILE; stdout carries the compact result line only")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline leg, also run the extra legs, the CPU baseline, the parity checks and the secondary "
+                         "rates (several minutes); a plain run measures the headline only")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous / reduction plumbing only, NO device work: value is null (CPU tests of --gpus N)")
     args = ap.parse_args()
@@ -149,6 +157,14 @@ def host_cpu_info():
     return info
 
 
+def usable_cpus(info):
+    """CPUs this process may actually use: the cgroup CPU quota when there is one (cpu.max = "1600000 100000" gives 16 CPUs'
+    worth of time however many logical CPUs the host shows and however many processes run), else the affinity mask"""
+    logical = info.get("affinity_cpus") or info.get("logical_cpus") or 1
+    eff = info.get("cgroup_effective_cpus")
+    return int(max(1, min(logical, round(eff)))) if eff else int(logical)
+
+
 def cpu_baseline(flat, cfgs, chi, budget_s):
     """The reference's CPU path restated in plain C on LAPACK (oracle/cbmps.c: bmps_impl.h:756-862, :225-263 op for op,
     float64), timed on this host in the reference's execution model (independent walkers, one per PROCESS as one per MPI
@@ -159,10 +175,7 @@ def cpu_baseline(flat, cfgs, chi, budget_s):
     from oracle import cbmps
     info = host_cpu_info()
     logical = info.get("affinity_cpus") or info.get("logical_cpus") or 1
-    # CPUs this process may actually use: the cgroup CPU quota when there is one (a container on a 256-thread host with
-    # cpu.max = "1600000 100000" gets 16 CPUs' worth of time however many processes it starts)
-    eff = info.get("cgroup_effective_cpus")
-    cores = int(max(1, min(logical, round(eff)))) if eff else int(logical)
+    cores = usable_cpus(info)
 
     def leg(n, nproc):
         d = cbmps.amplitudes_multiprocess_detail(flat, cfgs[:n], chi, nproc)
@@ -219,6 +232,53 @@ def pmc_traffic_bytes(kernel, leg_tag, nw, launches_per_step):
             "source": meta.get("source"), "launches_per_step_profiled": prof_lps}
 
 
+def batch_seeds(nw, total, rank, world):
+    """seed of the first walker of each of the `total` batches of this rank (walker w of a batch draws from rng(seed + w))"""
+    return [7 + (s * world + rank) * nw for s in range(total)]
+
+
+def config_chunk(real, L, n, seed0):
+    """walkers seed0 .. seed0 + n - 1: configurations near the Neel state on the real-state leg, random Sz = 0 shuffles
+    elsewhere.  Each walker draws from its own rng(seed0 + w), so a batch made in chunks equals the batch made in one piece."""
+    from peps_amd import synthetic
+    if real:
+        return synthetic.make_configs_near_neel(L, n, seed0=seed0)
+    return synthetic.make_configs(L, n, "heisenberg", seed0=seed0)
+
+
+class ConfigPool:
+    """The configurations of every warm-up and timed step of the main leg, made by worker processes while this process sets up
+    the device: a walker costs ~30 us of NumPy, so 49152 walkers x 25 steps take ~40 s on one core.  The workers are forked
+    before anything here touches the GPU or imports torch, and batches() joins them before the first step: none is alive
+    inside the timed region.  The result is what Leg.run would make itself, array for array."""
+    CHUNK = 4096
+
+    def __init__(self, real, L, nw, seeds, workers):
+        self.per_batch = -(-nw // self.CHUNK)
+        self.tasks = [(real, L, min(self.CHUNK, nw - a), s + a) for s in seeds for a in range(0, nw, self.CHUNK)]
+        self.pool = self.pending = None
+        workers = min(workers, len(self.tasks))
+        if workers > 1:
+            import multiprocessing
+            self.pool = multiprocessing.get_context("fork").Pool(workers)
+            self.pending = self.pool.starmap_async(config_chunk, self.tasks, chunksize=1)
+            self.pool.close()
+
+    def batches(self):
+        if self.pool is None:
+            parts = [config_chunk(*t) for t in self.tasks]
+        else:
+            try:
+                parts = self.pending.get()
+            except BaseException:
+                self.pool.terminate()
+                raise
+            finally:
+                self.pool.join()
+        k = self.per_batch
+        return [np.concatenate(parts[i:i + k]) for i in range(0, len(parts), k)]
+
+
 class Leg:
     """One timed pass: `steps` batches of `nw` fresh configurations through EvaluateAmplitude on this rank's GPU."""
 
@@ -258,11 +318,13 @@ class Leg:
         self.flat = synthetic.sitps_to_flat(self.sitps, D, np.float64)
         self.ctx.state_upload(self.flat)
 
-    def run(self, steps, warmup, rank, world, barrier):
+    def run(self, steps, warmup, rank, world, barrier, batches=None):
+        """`batches`: the configurations of the warm-up and timed steps as ConfigPool made them; generated here when None"""
         ctx, nw = self.ctx, self.nw
         total = warmup + steps
-        gen = self.synthetic.make_configs_near_neel if self.real else (lambda L, n, seed0: self.synthetic.make_configs(L, n, "heisenberg", seed0=seed0))
-        self.batches = [gen(self.L, nw, seed0=7 + (s * world + rank) * nw) for s in range(total)]
+        if batches is None:
+            batches = [config_chunk(self.real, self.L, nw, seed0) for seed0 in batch_seeds(nw, total, rank, world)]
+        self.batches = batches
         sig = None
         if self.fermion is not None:      # half filling: state 0 = occupied; device labels + graded sign per configuration
             self.phys = self.batches
@@ -836,6 +898,15 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    from peps_amd import synthetic
+    fermionic = args.workload == "C5"
+    L, D, chi, model = (8, 6, 24, "spinless_tV") if fermionic else synthetic.CONFIGS[args.workload]
+    nw = args.walkers
+    configs = None
+    if not args.dry_run:
+        # the inputs of the main leg's steps, made while the device is set up (the ranks of one node share its CPUs)
+        workers = min(16, usable_cpus(host_cpu_info())) // int(os.environ.get("LOCAL_WORLD_SIZE", "1"))
+        configs = ConfigPool(args.state == "real", L, nw, batch_seeds(nw, args.warmup + args.steps, rank, world), workers)
     dist = None
     torch = None
     backend = None
@@ -866,11 +937,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    from peps_amd import synthetic
     from peps_amd.flops import reference_flops
-    fermionic = args.workload == "C5"
-    L, D, chi, model = (8, 6, 24, "spinless_tV") if fermionic else synthetic.CONFIGS[args.workload]
-    nw = args.walkers
     fl = reference_flops(L, D, chi)
     workload = ("%s: %dx%d %s PEPS, D=%d, chi=%d, fresh EvaluateAmplitude per configuration (SVD(chi,chi,0) truncation)"
                 % (args.workload, L, L, "spinless-fermion t-V (fZ2-graded, sign-decorated components)" if fermionic
@@ -897,7 +964,7 @@ def main():
     from peps_amd import capi
     dt = capi.F32 if args.dtype == "f32" else capi.F64
     leg = Leg(capi, synthetic, L, D, chi, dt, local_rank, nw, args.noise, fermionic, real=args.state == "real")
-    elapsed, prof, nz = leg.run(args.steps, args.warmup, rank, world, barrier)
+    elapsed, prof, nz = leg.run(args.steps, args.warmup, rank, world, barrier, configs.batches())
     elapsed = max_over_ranks(elapsed)
 
     # per-rank step time (stragglers show in the first scaling record)
@@ -953,7 +1020,7 @@ def main():
                 "synthetic_noise": args.noise,
                 "state": args.state,
                 "note": ("the SURVEY 8(d) synthetic state (rank-1 background + 0.1 N(0,1)) is numerically of LOW rank (workload_rank: "
-                         "~10 live carry rows of 256): the headline value is the throughput on that state; `real_rank` below is the "
+                         "~10 live carry rows of 256): the headline value is the throughput on that state; `real_rank` of a --full run is the "
                          "same shapes on the reference's optimised D = 8 state tiled to 12x12 (the regime a VMC user runs in), "
                          "`full_rank` on i.i.d. random site tensors") if args.state == "synthetic" and args.noise <= 0.15 else None,
             },
@@ -969,10 +1036,11 @@ def main():
         }
         if dumped is not None:
             out["dump_outputs"] = dumped
-        out["workload_rank"] = leg.rank_diagnostics()
+        if args.full:
+            out["workload_rank"] = leg.rank_diagnostics()
         # size-independent property at the full size, outside the timed region: the amplitude of the same configuration
         # contracted row-wise (DOWN stack, trace at row 0) and column-wise (RIGHT stack, trace at column 0) must agree
-        nrc = 0 if args.no_route_check else min(nw, 2048)
+        nrc = 0 if args.no_route_check or not args.full else min(nw, 2048)
         if nrc:
             rctx = capi.Context(L, L, D, leg.pdim, chi, dtype=dt, device=local_rank, max_walkers=nrc)
             rctx.state_upload(leg.flat)
@@ -989,12 +1057,12 @@ def main():
             out["route_consistency"] = {"max_rel_spread_row_vs_column_contraction": float(np.max(np.abs(ratio - 1))),
                                         "n": int(nrc)}
             rctx.close()
-        if world == 1 and not args.no_latency:
+        if world == 1 and args.full and not args.no_latency:
             try:
                 out["n1_ms"] = n1_latency(leg)
             except Exception as e:
                 out["n1_ms"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cb = cpu_baseline(leg.flat, leg.batches[0][:512], chi, args.cpu_seconds)
             amps = cb.pop("amps")
             ac, sg = cb["all_cores"], cb["single"]
@@ -1032,9 +1100,9 @@ def main():
                                                    "tolerance 1e-4 applies to the rms error over the rms amplitude, the f64 mode is the "
                                                    "parity-grade path (DESIGN.md 3b)")
                 out["parity_on_sample"]["tolerance"] = 1e-4
-        if world == 1 and not args.no_cpu_baseline and not args.no_energy_check and not fermionic:
+        if world == 1 and args.full and not args.no_cpu_baseline and not args.no_energy_check and not fermionic:
             pend_energy["main"] = ((L, chi, 0 if dt == capi.F32 else 1, local_rank, leg.flat), leg.batches[0][:args.energy_n])
-        if world == 1 and not args.no_sweeps and not fermionic:
+        if world == 1 and args.full and not args.no_sweeps and not fermionic:
             try:
                 out["vmc"] = vmc_rates(leg, min(args.sweep_walkers, nw), args.sweep_count)
                 out["mc_sweeps_per_s"] = out["vmc"]["mc_sweeps_per_s"]
@@ -1043,7 +1111,7 @@ def main():
                 out["vmc"] = {"error": repr(e)}
     leg.close()
     del leg
-    if rank == 0 and world == 1 and not args.no_other_modes and args.workload == "C4" and args.state == "synthetic":
+    if rank == 0 and world == 1 and args.full and not args.no_other_modes and args.workload == "C4" and args.state == "synthetic":
         try:
             out["other_modes"] = other_modes(capi, synthetic, local_rank, L, D, chi)
         except Exception as e:
@@ -1156,13 +1224,13 @@ def main():
         fleg.close()
         return fr
 
-    if not args.no_full_rank and args.noise < 0.5 and not fermionic and args.state == "synthetic":
+    if args.full and not args.no_full_rank and args.noise < 0.5 and not fermionic and args.state == "synthetic":
         fr = extra_leg("full_rank", False, 1.0, args.full_rank_walkers, args.full_rank_steps)
         if rank == 0:
             if fr is not None and "error" not in fr:
                 fr["real_state_rank"] = real_state_rank(capi, local_rank, dt)
             out["full_rank"] = fr
-    if not args.no_real_rank and args.noise < 0.5 and not fermionic and args.state == "synthetic" and D == 8 and os.path.isdir(REAL_STATE):
+    if args.full and not args.no_real_rank and args.noise < 0.5 and not fermionic and args.state == "synthetic" and D == 8 and os.path.isdir(REAL_STATE):
         rr = extra_leg("real_rank", True, 0.0, args.real_rank_walkers, args.real_rank_steps)
         if rank == 0:
             out["real_rank"] = rr
@@ -1170,7 +1238,7 @@ def main():
     # ---- the exchange step, outside the timed region: all-reduce of the HBM-resident accumulators and the state broadcast
     #      over RCCL.  Phased: after every phase the ranks agree (all-reduce MAX of a failure flag) whether to go on, so that a
     #      rank-local failure never leaves the others waiting inside a collective ----
-    if dist is not None and backend == "nccl":
+    if args.full and dist is not None and backend == "nccl":
         coll = {}
         st = {}
         # Watchdog: the measured line must survive a collective that never returns (RCCL has not seen N > 1 ranks of this code

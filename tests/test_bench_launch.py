@@ -56,6 +56,40 @@ def test_result_line_stays_compact_and_complete():
     assert err["real_rank"] == {"error": "x" * 300}
 
 
+def test_config_pool_makes_the_batches_of_the_serial_generators(monkeypatch):
+    """the inputs of the timed steps made in chunks by worker processes are, array for array, what the generators of
+    peps_amd.synthetic make in one piece per batch (a batch that is not a whole number of chunks included)"""
+    import numpy as np
+    from peps_amd import synthetic
+    bench = _bench_module()
+    monkeypatch.setattr(bench.ConfigPool, "CHUNK", 96)
+    L, nw, total = 12, 250, 3
+    for rank, world in ((0, 1), (1, 2)):
+        seeds = bench.batch_seeds(nw, total, rank, world)
+        assert seeds == [7 + (s * world + rank) * nw for s in range(total)]
+        for real, workers in ((False, 3), (True, 3), (False, 1)):
+            got = bench.ConfigPool(real, L, nw, seeds, workers).batches()
+            want = [synthetic.make_configs_near_neel(L, nw, seed0=s) if real else synthetic.make_configs(L, nw, "heisenberg", seed0=s)
+                    for s in seeds]
+            assert len(got) == total
+            for g, w in zip(got, want):
+                assert g.dtype == w.dtype and g.shape == w.shape and np.array_equal(g, w)
+
+
+def test_plain_run_leaves_the_extras_to_full():
+    """--full is off by default; a plain run's parser still accepts every switch of a --full run"""
+    bench = _bench_module()
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1"]
+        assert bench.parse().full is False
+        sys.argv = sys.argv + ["--full", "--no-real-rank"]
+        args = bench.parse()
+        assert args.full is True and args.no_real_rank is True
+    finally:
+        sys.argv = argv
+
+
 def test_dump_outputs_writes_float64_and_samples_large_batches(tmp_path, monkeypatch):
     import numpy as np
     bench = _bench_module()

@@ -127,6 +127,29 @@ int pepsgpu_sweep_slice_exchange_tab(pepsgpu_ctx *ctx, int orientation, int slic
  *   amplitude_inout, accepted_out, slice_states_out as above (accepted = moves that changed the pair). */
 int pepsgpu_sweep_slice_fullspace(pepsgpu_ctx *ctx, int orientation, int slice, int phys_dim, const uint32_t *engine_words,
                                   double *amplitude_inout, int32_t *accepted_out, int32_t *slice_states_out);
+/* One row / column of MCUpdateSquareTNN3SiteExchange on the device (MCUpdateSquareTNN3SiteUpdateBase::operator(),
+ * square_3site_updater.h:36-56 row pass, :61-81 column pass; TNN3SiteUpdateImpl :109-158): InitBTen + GrowFullBTen(.., 3, true), the
+ * amplitude reset to the ReplaceTNNSiteTrace of the first window (:39-42, :64-67), then per triple of consecutive sites its distinct
+ * permutations as candidates (ReplaceTNNSiteTrace; a triple of three equal states does no trace and draws nothing, :118), the weights
+ * norm(psi_i / max |psi|) with the stored amplitude at the current triple, SuwaTodoStateUpdate, UpdateLocal and ShiftBTenWindow.
+ *   triple_table [phys_dim^3][20] (phys_dim = that of the context), indexed by e1 phys_dim^2 + e2 phys_dim + e3: m (1, 3 or 6 distinct
+ *                permutations), init (the slot of the triple itself), six slots of three states in std::next_permutation order of the
+ *                sorted triple, unused slots repeating slot 0; NULL = the bosonic table of the context's phys_dim.  Fermions: the
+ *                permutations of the physical triple as extended states (the three sites are consecutive modes of the current order);
+ *                phys_dim == 2 takes 3 candidate slots per triple, every other phys_dim 6;
+ *   engine_words [n][n_words], n_words >= 2 (slice length - 2): the next raw 32-bit outputs of each walker's std::mt19937 (the long double
+ *                draw of SuwaTodoStateUpdate = two words); consumed_out [n] how many walker w took (0 or 2 per triple);
+ *   amplitude_out [n] the amplitude after the slice (interleaved (re, im) for PEPSGPU_C128; fermions: of the decorated network, the
+ *                caller restores Sigma / Kappa); not read on entry -- the slice resets it;
+ *   accepted_out [n] moves that changed the triple; slice_states_out [n][slice length] (may be NULL) as above.
+ * Status 1: bad orientation or slice, a lattice with fewer than 3 rows or columns, n_words < 2 (slice length - 2); 4: a table entry out
+ * of range.  Either leaves the configuration untouched. */
+int pepsgpu_sweep_slice_tnn3(pepsgpu_ctx *ctx, int orientation, int slice, const int32_t *triple_table, int n_words,
+                             const uint32_t *engine_words, double *amplitude_out, int32_t *consumed_out, int32_t *accepted_out,
+                             int32_t *slice_states_out);
+/* The bosonic triple table pepsgpu_sweep_slice_tnn3 builds when it is given none: out [phys_dim^3][20], 1 <= phys_dim <= 64 (else
+ * PEPSGPU_EINVAL).  Host only: needs no context and no device. */
+int pepsgpu_diag_tnn3_table(int phys_dim, int32_t *out);
 
 /* One row / column of the energy evaluation for models whose nearest-neighbour off-diagonal term exchanges the two site states (XXZ,
  * J1-J2, t-J ...): the slice part of SquareNNNModelEnergySolver::CalEnergyAndHolesImpl (square_nnn_energy_solver.h:142-200 row pass:

@@ -26,7 +26,7 @@ SYMBOLS = [
     "pepsgpu_walkers_set_configs", "pepsgpu_walkers_get_configs", "pepsgpu_n_walkers",
     "pepsgpu_grow_bmps_step", "pepsgpu_grow_full_bmps", "pepsgpu_grow_bmps_for_row", "pepsgpu_grow_bmps_for_col",
     "pepsgpu_shift_bmps_window", "pepsgpu_delete_inner_bmps", "pepsgpu_bmps_park", "pepsgpu_bmps_unpark", "pepsgpu_generate_bmps_approach",
-    "pepsgpu_sweep_slice_exchange", "pepsgpu_sweep_slice_exchange_tab", "pepsgpu_sweep_slice_fullspace", "pepsgpu_nn_exchange_slice", "pepsgpu_nn_exchange_slice_tab", "pepsgpu_onsite_slice", "pepsgpu_walker_create", "pepsgpu_walker_clone", "pepsgpu_walker_destroy", "pepsgpu_walker_info", "pepsgpu_walker_set_mpo", "pepsgpu_walker_evolve",
+    "pepsgpu_sweep_slice_exchange", "pepsgpu_sweep_slice_exchange_tab", "pepsgpu_sweep_slice_fullspace", "pepsgpu_sweep_slice_tnn3", "pepsgpu_diag_tnn3_table", "pepsgpu_nn_exchange_slice", "pepsgpu_nn_exchange_slice_tab", "pepsgpu_onsite_slice", "pepsgpu_walker_create", "pepsgpu_walker_clone", "pepsgpu_walker_destroy", "pepsgpu_walker_info", "pepsgpu_walker_set_mpo", "pepsgpu_walker_evolve",
     "pepsgpu_walker_evolve_step", "pepsgpu_walker_contract_row", "pepsgpu_walker_init_bten", "pepsgpu_walker_grow_bten_step",
     "pepsgpu_walker_shift_bten_window", "pepsgpu_walker_trace_with_bten", "pepsgpu_walker_clear_bten", "pepsgpu_walker_get_bmps_tensor",
     "pepsgpu_bmps_stack_size", "pepsgpu_get_bmps_tensor", "pepsgpu_init_bten", "pepsgpu_grow_full_bten",
@@ -103,6 +103,8 @@ def load_library(path=LIB_PATH):
     lib.pepsgpu_sweep_slice_exchange.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, dp, ip, ip, ip]
     lib.pepsgpu_sweep_slice_exchange_tab.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, ip, dp, ip, ip, ip]
     lib.pepsgpu_sweep_slice_fullspace.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), dp, ip, ip]
+    lib.pepsgpu_sweep_slice_tnn3.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int, C.POINTER(C.c_uint32), dp, ip, ip, ip]
+    lib.pepsgpu_diag_tnn3_table.argtypes = [C.c_int, ip]
     lib.pepsgpu_nn_exchange_slice.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, dp]
     lib.pepsgpu_nn_exchange_slice_tab.argtypes = [vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, dp, dp]
     lib.pepsgpu_onsite_slice.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, dp, dp]
@@ -316,6 +318,24 @@ class Context:
         self._ck(self._l.pepsgpu_sweep_slice_fullspace(self._h, orientation, slice_num, phys_dim, wd.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                        _dp(amp), _ip(acc), _ip(st)))
         return amp, acc, st
+
+    def sweep_slice_tnn3(self, orientation, slice_num, engine_words, triple_table=None):
+        """one row / column of the three-site exchange updater on the device; engine_words [n][n_words] uint32 (n_words >= 2 (N - 2)) =
+        the next raw outputs of each walker's mt19937; triple_table [d^3][20] (None: the bosonic table of the context's d); returns
+        (amplitude [n] after the slice, consumed words [n], accepted moves [n], slice_states [n][N])"""
+        N = self.cols if orientation == HORIZONTAL else self.rows
+        wd = np.ascontiguousarray(engine_words, dtype=np.uint32)
+        assert wd.ndim == 2 and wd.shape[0] == self.n, wd.shape
+        amp = np.zeros(self.n, dtype=self._ot)
+        cons, acc = np.zeros(self.n, dtype=np.int32), np.zeros(self.n, dtype=np.int32)
+        st = np.zeros((self.n, N), dtype=np.int32)
+        tab = None
+        if triple_table is not None:
+            tab = np.ascontiguousarray(triple_table, dtype=np.int32)
+            assert tab.shape == (self.d ** 3, 20), tab.shape
+        self._ck(self._l.pepsgpu_sweep_slice_tnn3(self._h, orientation, slice_num, None if tab is None else _ip(tab), wd.shape[1],
+                                                  wd.ctypes.data_as(C.POINTER(C.c_uint32)), _dp(amp), _ip(cons), _ip(acc), _ip(st)))
+        return amp, cons, acc, st
 
     def nn_exchange_slice(self, orientation, slice_num, punch_holes=False):
         """psi [n] and the amplitudes with the two sites of every bond of the slice exchanged [n][N-1], one read-back"""
@@ -673,6 +693,14 @@ def tgemm_desc_arrays(desc):
     longs = [int(g(k, 0)) for k in ("wA", "wB", "wC", "selA_mul", "selB_mul")]
     return (np.array(ints, dtype=np.int32), np.array(longs, dtype=np.int64), np.array([float(g("alpha", 1.0))]),
             np.array(pool if pool else [0], dtype=np.int32))
+
+
+def diag_tnn3_table(phys_dim):
+    """the bosonic triple table [phys_dim^3][20] pepsgpu_sweep_slice_tnn3 builds for a NULL table; no device is touched"""
+    out = np.zeros((phys_dim ** 3, 20), dtype=np.int32)
+    if lib().pepsgpu_diag_tnn3_table(phys_dim, _ip(out)) != 0:
+        raise ValueError("diag_tnn3_table: 1 <= phys_dim <= 64")
+    return out
 
 
 def diag_tgemm_route(types, desc, a_offset=0, b_offset=0):

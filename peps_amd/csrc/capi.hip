@@ -138,6 +138,21 @@ int pepsgpu_sweep_slice_fullspace(pepsgpu_ctx *ctx, int orientation, int slice, 
            ctx->eng->sweep_slice_impl(1, orientation, slice, 0, nullptr, nullptr, phys_dim, engine_words, amplitude_inout, nullptr,
                                       accepted_out, slice_states_out));
 }
+// the bosonic triple table pepsgpu_sweep_slice_tnn3 builds for a NULL table (host only, no context)
+int pepsgpu_diag_tnn3_table(int phys_dim, int32_t *out) {
+  if (phys_dim < 1 || phys_dim > 64 || !out) return PEPSGPU_EINVAL;
+  const std::vector<int32_t> tab = pepsgpu::tnn3_boson_table(phys_dim);
+  std::copy(tab.begin(), tab.end(), out);
+  return 0;
+}
+// square_3site_updater.h:36-56 / :61-81 (one slice of MCUpdateSquareTNN3SiteUpdateBase::operator()) + :109-158 per triple
+int pepsgpu_sweep_slice_tnn3(pepsgpu_ctx *ctx, int orientation, int slice, const int32_t *triple_table, int n_words,
+                             const uint32_t *engine_words, double *amplitude_out, int32_t *consumed_out, int32_t *accepted_out,
+                             int32_t *slice_states_out) {
+  CTX_CALL(PG_REQUIRE(engine_words && amplitude_out && consumed_out && accepted_out, 1, "null buffer");
+           ctx->eng->sweep_slice_tnn3(orientation, slice, triple_table, n_words, engine_words, amplitude_out, consumed_out,
+                                      accepted_out, slice_states_out));
+}
 int pepsgpu_nn_exchange_slice(pepsgpu_ctx *ctx, int orientation, int slice, int punch_holes, double *psi_out, double *psi_exchanged_out) {
   CTX_CALL(PG_REQUIRE(psi_out && psi_exchanged_out, 1, "null buffer");
            ctx->eng->nn_exchange_slice(orientation, slice, punch_holes, psi_out, psi_exchanged_out));

@@ -29,6 +29,12 @@ namespace pepsgpu {
 enum { LEFT = 0, DOWN = 1, RIGHT = 2, UP = 3 };      // include/qlpeps/basic.h:58-63
 enum { HORIZONTAL = 0, VERTICAL = 1 };               // include/qlpeps/basic.h:19-22
 
+// batch_flag of the tensor GEMM from a per-walker skip mask: entry b (walker b / div) runs only when skip[b / div] == 0
+__global__ void skip_batch_flag_kernel(const int *__restrict__ skip, int div, int *__restrict__ flag, int nb) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < nb) flag[b] = skip[b / div] ? 0 : -1;
+}
+
 // kernel categories of the event profile (pepsgpu_profile_read)
 enum { PROF_CONTRACT = 0, PROF_GRAM = 1, PROF_CHOL = 2, PROF_JACOBI = 3, PROF_SELECT = 4, PROF_NORM = 5,
        PROF_ENV = 6, PROF_JACOBI_EDGE = 7, PROF_TRUNC_GRAM = 8, PROF_TRUNC_APPLY = 9,
@@ -112,6 +118,9 @@ struct EngineBase {
   virtual void sweep_slice_impl(int mode, int orient, int slice, int n_uniform, const double *uniforms, const int32_t *pair_table,
                                 int phys_dim, const uint32_t *words, double *amp_inout, int32_t *consumed_out, int32_t *accepted_out,
                                 int32_t *slice_states_out) = 0;
+  // one row / column of three-site exchange moves (MCUpdateSquareTNN3SiteExchange); engine_sweep.h
+  virtual void sweep_slice_tnn3(int orient, int slice, const int32_t *triple_table, int n_words, const uint32_t *words,
+                                double *amp_out, int32_t *consumed_out, int32_t *accepted_out, int32_t *slice_states_out) = 0;
   virtual void nn_exchange_slice(int orient, int slice, int punch_holes, double *psi_out, double *psi_ex_out) = 0;
   // mode 0: exchange move per bond (pair_table nullable, psi_per_bond), mode 1: one-site move per site (site table [dp][n_cand]);
   // engine_sweep.h
@@ -402,6 +411,11 @@ class Engine : public EngineBase {
   void cfg_override_slice(int orient, int num, const int32_t *states) override;
   void replace_plaquette_trace(int row, int col, int ncand, const int32_t *cand, int left_set, int right_set, double *out) override;
   void replace_tnn_trace(int row, int col, int orient, int ncand, const int32_t *cand, double *out) override;
+  // ReplaceTNNSiteTrace with everything left on the device (the three-site slice sweep, engine_sweep.h): candidate table
+  // dcand [walker][nc][3] (nullptr: the configuration), result res [walker x nc] and lsum [walker]: psi' = res exp(lsum).
+  // skip (optional, per walker): nonzero = no environment step runs for this walker (its entries of res are undefined).
+  // Caller frees res and lsum.
+  Acc *tnn_trace_device(int row, int col, int orient, int nc, const int *dcand, double **lsum_out, const int *skip = nullptr);
   void replace_sqrt5_trace(int row, int col, int diag_dir, int orient, int ncand, const int32_t *cand, double *out) override;
 
   const BMPSDev &bmps_at_slice(int pos, int idx) const {   // bmps_contractor.h:985-999
@@ -943,6 +957,8 @@ class Engine : public EngineBase {
   void sweep_slice_impl(int mode, int orient, int slice, int n_uniform, const double *uniforms, const int32_t *pair_table, int phys_dim,
                         const uint32_t *words, double *amp_inout, int32_t *consumed_out, int32_t *accepted_out,
                         int32_t *slice_states_out) override;
+  void sweep_slice_tnn3(int orient, int slice, const int32_t *triple_table, int n_words, const uint32_t *words, double *amp_out,
+                        int32_t *consumed_out, int32_t *accepted_out, int32_t *slice_states_out) override;
   void nn_exchange_slice(int orient, int slice, int punch_holes, double *psi_out, double *psi_ex_out) override;
   void energy_slice_impl(int mode, int orient, int slice, int punch_holes, const int32_t *table, int n_cand, int psi_per_bond,
                          double *psi_out, double *val_out) override;
@@ -1238,6 +1254,16 @@ class Engine : public EngineBase {
         if (!bt_chained) { arena_.free(bt_chain_flag); bt_chain_flag = nullptr; }
       }
     }
+    // skip with several candidates (or a step the chain did not take): the separate launches below honour it through batch_flag
+    // (entries of skipped walkers return at once; every other entry runs the same kernel on the same operands)
+    int *skip_ent = nullptr, *skip_ent1 = nullptr;
+    if (skip && !bt_chain_flag && ncand > 1) {
+      skip_ent = (int *)arena_.alloc(sizeof(int) * ((size_t)nb + nb1));
+      skip_ent1 = skip_ent + nb;
+      hipLaunchKernelGGL(skip_batch_flag_kernel, dim3((nb + 255) / 256), dim3(256), 0, stream_, skip, ncand, skip_ent, nb);
+      hipLaunchKernelGGL(skip_batch_flag_kernel, dim3((nb1 + 255) / 256), dim3(256), 0, stream_, skip, bt_ncand, skip_ent1, nb1);
+      PG_CHECK_HIP(hipGetLastError());
+    }
     // tmp1[x,p1,b1,b2] = sum_c mps1[x,p1,c] bten[c,b1,b2]     (per walker)
     DTen<T> tmp1;
     if (bt_chained < 2) tmp1 = alloc_ten(x, p1, b1, b2, nb1);
@@ -1252,7 +1278,7 @@ class Engine : public EngineBase {
         g.dI[1].p = vx; g.dI[1].div = bt_ncand; g.dK[2].p = vc; g.dK[2].div = bt_ncand; g.dJ[2].p = vb; g.dJ[2].div = bt_ncand;
       }
       g.wA = mps1.n; g.bdivA = bt_ncand; g.wB = bt.t.n; g.wC = tmp1.n; g.nbatch = nb1;
-      g.batch_flag = bt_chain_flag;
+      g.batch_flag = bt_chain_flag ? bt_chain_flag : skip_ent1;
       const double fl = 2.0 * nb1 * (double)(x * p1) * cdim * (double)(b1 * b2);
       prof_begin(PROF_ENV, bt_chained ? 0.0 : fl, bt_chained ? 0.0 : fl);
       tgemm_launch<T, T, T, T>(stream_, g, mps1.p, bt.t.p, tmp1.p);
@@ -1267,7 +1293,7 @@ class Engine : public EngineBase {
       g.J[1] = s1; g.J[2] = s2; g.sBj[1] = st[l1]; g.sBj[2] = st[l2]; g.sCj[1] = s2; g.sCj[2] = 1;
       g.wA = tmp1.n; g.bdivA = ncand / bt_ncand; g.wC = tmp2.n; g.nbatch = nb;
       g.dI[1].p = vb; g.dI[1].div = ncand; g.dI[2].p = vx; g.dI[2].div = ncand;
-      g.batch_flag = bt_chain_flag;
+      g.batch_flag = bt_chain_flag ? bt_chain_flag : skip_ent;
       const double fl = 2.0 * nb * (double)(b2 * x) * (double)(p1 * b1) * (double)(s1 * s2);
       prof_begin(PROF_ENV, bt_chained ? 0.0 : fl, bt_chained ? 0.0 : fl);
       launch_site_gemm(g, ss, ncand, tmp1.p, tmp2.p);
@@ -1286,6 +1312,7 @@ class Engine : public EngineBase {
       g.dI[1].p = vx; g.dI[1].div = ncand; g.dI[1].mask = 1;     // the new BTen is written in full
       g.dK[1].p = vb; g.dK[1].div = ncand;
       g.dJ[2].p = vy; g.dJ[2].div = ncand; g.dJ[2].mask = 1;
+      g.batch_flag = skip_ent;
       const double fl = 2.0 * nb * (double)(x * s2) * (double)(b2 * s1) * (double)y;
       prof_begin(PROF_ENV, fl, fl);
       tgemm_launch<T, T, T, T>(stream_, g, tmp2.p, mps2.p, o.t.p);
@@ -1293,6 +1320,7 @@ class Engine : public EngineBase {
     }
     if (tmp1.p) free_ten(tmp1);
     free_ten(tmp2);
+    if (skip_ent) arena_.free(skip_ent);
     inject(INJ_E, o.t.p, o.t.n, nb);
     o.logscale = nullptr;
     if (normalise) {

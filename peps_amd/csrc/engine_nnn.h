@@ -317,6 +317,21 @@ void Engine<T>::replace_tnn_trace(int row, int col, int orient, int ncand, const
   PG_REQUIRE(row >= 0 && col >= 0 && (orient == HORIZONTAL ? (col + 2 < Lx_ && row < Ly_) : (row + 2 < Ly_ && col < Lx_)), 1,
              "ReplaceTNNSiteTrace: sites outside the lattice");
   int *dc = upload_cand(ncand, 3, cand);
+  double *lsum = nullptr;
+  Acc *res = tnn_trace_device(row, col, orient, nc, dc, &lsum);
+  finish_read(res, nw_ * nc, nc, lsum, out);
+  arena_.free(res);
+  arena_.free(lsum);
+  if (dc) arena_.free(dc);
+}
+
+// the device part of ReplaceTNNSiteTrace: the LEFT (UP) environment grown over the three sites with the candidate states, closed
+// with the RIGHT (DOWN) environment behind the third site
+template <typename T>
+typename Engine<T>::Acc *Engine<T>::tnn_trace_device(int row, int col, int orient, int nc, const int *dcand, double **lsum_out,
+                                                     const int *skip) {
+  PG_REQUIRE(row >= 0 && col >= 0 && (orient == HORIZONTAL ? (col + 2 < Lx_ && row < Ly_) : (row + 2 < Ly_ && col < Lx_)), 1,
+             "ReplaceTNNSiteTrace: sites outside the lattice");
   double *lsum = zeros_f64();
   BTenDev cur;
   const DTen<T> *closing;
@@ -326,9 +341,9 @@ void Engine<T>::replace_tnn_trace(int row, int col, int orient, int ncand, const
     const BTenDev &rb = bten_at_slice(RIGHT, col + 2);
     BTenDev prev = bten_[LEFT][col];
     for (int k = 0; k < 3; ++k) {
-      SitePick s{row, col + k, ncand > 0 ? k : -1};
-      cur = bten_step(LEFT, prev, at_logical(up, UP, col + k), pick(s, dc, 3), at_logical(dn, DOWN, col + k), nc, false,
-                      k == 0 ? 1 : nc);
+      SitePick s{row, col + k, dcand ? k : -1};
+      cur = bten_step(LEFT, prev, at_logical(up, UP, col + k), pick(s, dcand, 3), at_logical(dn, DOWN, col + k), nc, false,
+                      k == 0 ? 1 : nc, nullptr, nullptr, nullptr, nullptr, skip);
       if (k > 0) free_ten(prev.t);
       prev = cur;
     }
@@ -340,19 +355,19 @@ void Engine<T>::replace_tnn_trace(int row, int col, int orient, int ncand, const
     const BTenDev &bb = bten_at_slice(DOWN, row + 2);
     BTenDev prev = bten_[UP][row];
     for (int k = 0; k < 3; ++k) {
-      SitePick s{row + k, col, ncand > 0 ? k : -1};
-      cur = bten_step(UP, prev, at_logical(rt, RIGHT, row + k), pick(s, dc, 3), at_logical(lf, LEFT, row + k), nc, false,
-                      k == 0 ? 1 : nc);
+      SitePick s{row + k, col, dcand ? k : -1};
+      cur = bten_step(UP, prev, at_logical(rt, RIGHT, row + k), pick(s, dcand, 3), at_logical(lf, LEFT, row + k), nc, false,
+                      k == 0 ? 1 : nc, nullptr, nullptr, nullptr, nullptr, skip);
       if (k > 0) free_ten(prev.t);
       prev = cur;
     }
     add_logs(lsum, lf.logscale, rt.logscale, bten_[UP][row].logscale, bb.logscale);
     closing = &bb.t;
   }
-  finish_dot(cur.t, nc, *closing, 1, nc, lsum, out);
+  Acc *res = finish_dot_device(cur.t, nc, *closing, 1, nc);
   free_ten(cur.t);
-  arena_.free(lsum);
-  if (dc) arena_.free(dc);
+  *lsum_out = lsum;
+  return res;
 }
 
 // ReplaceSqrt5DistTwoSiteTrace (trace.h:425-536).  cand[w][k][2] = states of (ten_left, ten_right).

@@ -18,6 +18,8 @@
 // pass that erase never removes anything the pass still holds (LEFT covers [0, col), RIGHT covers (col + 1, N): checked against
 // the reference's flow), so it is applied unconditionally -- the decision "did any walker accept" would cost a read-back per bond.
 #pragma once
+#include <algorithm>
+#include <vector>
 #include "engine.h"
 
 namespace pepsgpu {
@@ -333,6 +335,201 @@ void Engine<T>::energy_slice_impl(int mode, int orient, int slice, int punch_hol
       }
     }
   } catch (...) { release(); throw; }
+  release();
+}
+
+// ---- three-site exchange (MCUpdateSquareTNN3SiteExchange::TNN3SiteUpdateImpl, square_3site_updater.h:109-158) ----
+// Triple table [dp^3][TNN3_TAB]: entry e1 dp^2 + e2 dp + e3 holds m (the number of distinct permutations of the triple: 1, 3 or 6),
+// init (the position of the triple itself among them) and six slots of three states, the permutations in std::next_permutation order
+// of the sorted triple (fermions: of the sorted physical triple, as extended states); unused slots repeat slot 0.
+constexpr int TNN3_TAB = 2 + 6 * 3;
+
+// Bosonic triple table of dp states (the table pepsgpu_sweep_slice_tnn3 builds when it is given none).  The host layer states the same
+// rule (TNN3TripleTable, peps_amd/host/qlpeps_gpu.h); pepsgpu_diag_tnn3_table exposes this copy so that tests/test_cpu_tnn3.py checks
+// the two against each other.
+inline std::vector<int32_t> tnn3_boson_table(int dp) {
+  std::vector<int32_t> tab((size_t)dp * dp * dp * TNN3_TAB);
+  for (int e = 0; e < dp * dp * dp; ++e) {
+    const int t0[3] = {e / (dp * dp), (e / dp) % dp, e % dp};
+    int p[3] = {t0[0], t0[1], t0[2]};
+    std::sort(p, p + 3);
+    int32_t *row = tab.data() + (size_t)e * TNN3_TAB;
+    int m = 0, init = 0;
+    do {
+      if (p[0] == t0[0] && p[1] == t0[1] && p[2] == t0[2]) init = m;
+      for (int q = 0; q < 3; ++q) row[2 + 3 * m + q] = p[q];
+      ++m;
+    } while (std::next_permutation(p, p + 3));
+    for (int k = m; k < 6; ++k)
+      for (int q = 0; q < 3; ++q) row[2 + 3 * k + q] = row[2 + q];
+    row[0] = m;
+    row[1] = init;
+  }
+  return tab;
+}
+
+// Per walker: the triple (s1, s2, s3) of the configuration looked up in the table -> nslot candidate slots cand [w][nslot][3],
+// m and init (meta [w][2]) and skip[w] = (m == 1: all three states equal, no trace and no draw, :118)
+__global__ void tnn3_cand_kernel(const int *__restrict__ cfg, int sites, int s1, int s2, int s3, const int *__restrict__ tab, int dp,
+                                 int nslot, int *__restrict__ cand, int *__restrict__ meta, int *__restrict__ skip, int n) {
+  const int w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= n) return;
+  const long cw = (long)w * sites;
+  const int e = (cfg[cw + s1] * dp + cfg[cw + s2]) * dp + cfg[cw + s3];
+  const int *t = tab + (long)e * TNN3_TAB;
+  for (int k = 0; k < 3 * nslot; ++k) cand[(long)w * 3 * nslot + k] = t[2 + k];
+  meta[2 * w] = t[0];
+  meta[2 * w + 1] = t[1];
+  skip[w] = t[0] <= 1;
+}
+
+// amp[w] = res[w] exp(lsum[w]): the amplitude reset at the start of a slice (square_3site_updater.h:39-42)
+template <typename AccT>
+__global__ void tnn3_reset_amp_kernel(const AccT *__restrict__ res, const double *__restrict__ lsum, AccT *__restrict__ amp, int n) {
+  const int w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w < n) amp[w] = sw_scaled(res[w], exp(lsum[w]));
+}
+
+__device__ __forceinline__ double sw_norm_div(double x, double s) { const double r = x / s; return r * r; }
+__device__ __forceinline__ double sw_norm_div(const cplx<double> &x, double s) {
+  const double re = x.re / s, im = x.im / s;
+  return re * re + im * im;
+}
+
+// :123-156 for one triple: psis (the stored amplitude at init), weights norm(psi / max |psi|), SuwaTodoStateUpdate with the walker's
+// next two engine words (taken only when m > 1, counted in used[w]), and the move
+template <typename AccT>
+__global__ void tnn3_decide_kernel(int *__restrict__ cfg, int sites, int s1, int s2, int s3, const AccT *__restrict__ res,
+                                   const double *__restrict__ lsum, AccT *__restrict__ amp, const int *__restrict__ cand,
+                                   const int *__restrict__ meta, int nslot, const unsigned *__restrict__ words, int n_words,
+                                   int *__restrict__ used, int *__restrict__ acc, int n) {
+  const int w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= n) return;
+  const int m = meta[2 * w], init = meta[2 * w + 1];
+  if (m <= 1) return;
+  const double sc = exp(lsum[w]);
+  const AccT a0 = amp[w];
+  // (psi_i recomputed in each unrolled loop rather than kept in an array indexed at run time: that array went to scratch)
+  auto psi = [&](int i) { return i == init ? a0 : sw_scaled(AccT(res[(long)w * nslot + i]), sc); };
+  double mx = 0.0;
+#pragma unroll
+  for (int i = 0; i < 6; ++i)
+    if (i < m) mx = fmax(mx, sw_abs(psi(i)));
+  double wt[SW_MAXC];
+#pragma unroll
+  for (int i = 0; i < 6; ++i)
+    if (i < m) wt[i] = sw_norm_div(psi(i), mx);
+  const int q = used[w];
+  const unsigned *wd = words + (long)w * n_words + q;
+  const int fin = sw_suwa_todo_decide(wt, m, init, wd[0], wd[1]);
+  used[w] = q + 2;
+  if (fin != init) {
+    const int *c = cand + ((long)w * nslot + fin) * 3;
+    cfg[(long)w * sites + s1] = c[0];
+    cfg[(long)w * sites + s2] = c[1];
+    cfg[(long)w * sites + s3] = c[2];
+    amp[w] = psi(fin);
+    acc[w] += 1;
+  }
+}
+
+// One row / column of three-site exchange moves (MCUpdateSquareTNN3SiteUpdateBase::operator(), square_3site_updater.h:28-91):
+// InitBTen + GrowFullBTen(.., 3), the amplitude reset to the trace of the first window, then per triple the candidates from the
+// triple table, their replacement traces (walkers with three equal states skipped), the Suwa-Todo decision and the move, and the
+// BTen window shift -- one read-back at the end.
+// Environment bookkeeping: at triple j the pass holds LEFT over [0, j), RIGHT over [j + 3, N) and the BMPS of the other rows
+// (columns); EraseEnvsAfterUpdate of the sites j .. j + 2 only drops LEFT beyond j + 1 .. j + 3 and RIGHT beyond N - j - 2 .. N - j,
+// levels the pass does not hold, so it is applied unconditionally as in the two-site slice.
+template <typename T>
+void Engine<T>::sweep_slice_tnn3(int orient, int slice, const int32_t *triple_table, int n_words, const uint32_t *words, double *amp_out,
+                                 int32_t *consumed_out, int32_t *accepted_out, int32_t *slice_states_out) {
+  require_ready();
+  PG_REQUIRE(orient == HORIZONTAL || orient == VERTICAL, 1, "bad orientation");
+  PG_REQUIRE(Ly_ >= 3 && Lx_ >= 3, 1, "three-site slice: the lattice needs at least 3 rows and 3 columns");
+  const int N = orient == HORIZONTAL ? Lx_ : Ly_, lim = orient == HORIZONTAL ? Ly_ : Lx_;
+  PG_REQUIRE(slice >= 0 && slice < lim, 1, "slice outside the lattice");
+  PG_REQUIRE(words && n_words >= 2 * (N - 2), 1, "three-site slice: two engine words per triple of the slice are needed");
+  const int sites = Ly_ * Lx_, nslot = dp_ == 2 ? 3 : 6;
+  const size_t ntab = (size_t)dp_ * dp_ * dp_ * TNN3_TAB;
+  std::vector<int32_t> own;
+  if (!triple_table) { own = tnn3_boson_table(dp_); triple_table = own.data(); }
+  for (size_t e = 0; e < ntab / TNN3_TAB; ++e) {
+    const int32_t *t = triple_table + e * TNN3_TAB;
+    PG_REQUIRE((t[0] == 1 || t[0] == 3 || t[0] == 6) && t[0] <= nslot && t[1] >= 0 && t[1] < t[0], 4,
+               "triple table: bad permutation count or initial slot");
+    for (int k = 2; k < TNN3_TAB; ++k) PG_REQUIRE(t[k] >= 0 && t[k] < dp_, 4, "triple table: state out of range");
+  }
+  Acc *damp = (Acc *)arena_.alloc(sizeof(Acc) * nw_);
+  unsigned *dwords = (unsigned *)arena_.alloc(sizeof(unsigned) * (size_t)nw_ * n_words);
+  int *dcnt = (int *)arena_.alloc(sizeof(int) * 2 * (size_t)nw_);          // used words [n], accepted moves [n]
+  int *dcand = (int *)arena_.alloc(sizeof(int) * (3 * (size_t)nslot + 3) * (size_t)nw_);
+  int *dmeta = dcand + 3 * (size_t)nslot * nw_, *dskip = dmeta + 2 * (size_t)nw_;
+  int *dslice = (int *)arena_.alloc(sizeof(int) * (size_t)nw_ * N);
+  int *dtab = (int *)arena_.alloc(sizeof(int) * ntab);
+  auto release = [&]() {
+    arena_.free(damp); arena_.free(dwords); arena_.free(dcnt); arena_.free(dcand); arena_.free(dslice); arena_.free(dtab);
+  };
+  try {
+    PG_CHECK_HIP(hipMemcpyAsync(dwords, words, sizeof(unsigned) * (size_t)nw_ * n_words, hipMemcpyHostToDevice, stream_));
+    PG_CHECK_HIP(hipMemcpyAsync(dtab, triple_table, sizeof(int) * ntab, hipMemcpyHostToDevice, stream_));
+    PG_CHECK_HIP(hipMemsetAsync(dcnt, 0, sizeof(int) * 2 * (size_t)nw_, stream_));
+    const int lo = orient == HORIZONTAL ? LEFT : UP, hi = orient == HORIZONTAL ? RIGHT : DOWN;
+    init_bten(lo, slice);
+    grow_full_bten(hi, slice, 3, 1);
+    const int gb = (nw_ + 255) / 256;
+    {
+      double *lsum = nullptr;
+      Acc *res = tnn_trace_device(orient == HORIZONTAL ? slice : 0, orient == HORIZONTAL ? 0 : slice, orient, 1, nullptr, &lsum);
+      hipLaunchKernelGGL(tnn3_reset_amp_kernel<Acc>, dim3(gb), dim3(256), 0, stream_, (const Acc *)res, (const double *)lsum, damp, nw_);
+      PG_CHECK_HIP(hipGetLastError());
+      arena_.free(res);
+      arena_.free(lsum);
+    }
+    for (int j = 0; j + 2 < N; ++j) {
+      int r[3], c[3], s[3];
+      for (int k = 0; k < 3; ++k) {
+        r[k] = orient == HORIZONTAL ? slice : j + k;
+        c[k] = orient == HORIZONTAL ? j + k : slice;
+        s[k] = r[k] * Lx_ + c[k];
+      }
+      hipLaunchKernelGGL(tnn3_cand_kernel, dim3(gb), dim3(256), 0, stream_, (const int *)cfg_, sites, s[0], s[1], s[2], (const int *)dtab,
+                         dp_, nslot, dcand, dmeta, dskip, nw_);
+      PG_CHECK_HIP(hipGetLastError());
+      double *lsum = nullptr;
+      Acc *res = tnn_trace_device(r[0], c[0], orient, nslot, dcand, &lsum, dskip);
+      hipLaunchKernelGGL(tnn3_decide_kernel<Acc>, dim3(gb), dim3(256), 0, stream_, cfg_, sites, s[0], s[1], s[2], (const Acc *)res,
+                         (const double *)lsum, damp, (const int *)dcand, (const int *)dmeta, nslot, (const unsigned *)dwords, n_words,
+                         dcnt, dcnt + nw_, nw_);
+      PG_CHECK_HIP(hipGetLastError());
+      arena_.free(res);
+      arena_.free(lsum);
+      for (int k = 0; k < 3; ++k) erase_envs_after_update(r[k], c[k]);
+      if (j + 3 < N) shift_bten_window(hi);
+    }
+    hipLaunchKernelGGL(sweep_gather_slice_kernel, dim3((nw_ * N + 255) / 256), dim3(256), 0, stream_, (const int *)cfg_, sites,
+                       orient == HORIZONTAL ? slice * Lx_ : slice, orient == HORIZONTAL ? 1 : Lx_, N, dslice, nw_);
+    PG_CHECK_HIP(hipGetLastError());
+    std::vector<int> hs((size_t)nw_ * N), hc(2 * (size_t)nw_);
+    PG_CHECK_HIP(hipMemcpyAsync(amp_out, damp, sizeof(Acc) * nw_, hipMemcpyDeviceToHost, stream_));
+    PG_CHECK_HIP(hipMemcpyAsync(hs.data(), dslice, sizeof(int) * hs.size(), hipMemcpyDeviceToHost, stream_));
+    PG_CHECK_HIP(hipMemcpyAsync(hc.data(), dcnt, sizeof(int) * hc.size(), hipMemcpyDeviceToHost, stream_));
+    PG_CHECK_HIP(hipStreamSynchronize(stream_));
+    for (int w = 0; w < nw_; ++w) {
+      if (consumed_out) consumed_out[w] = hc[w];
+      if (accepted_out) accepted_out[w] = hc[nw_ + w];
+      for (int j = 0; j < N; ++j) {
+        const int v = hs[(size_t)w * N + j];
+        const int rr = orient == HORIZONTAL ? slice : j, cc = orient == HORIZONTAL ? j : slice;
+        hcfg_[(size_t)w * sites + rr * Lx_ + cc] = v;          // host mirror of the configuration table
+        if (slice_states_out) slice_states_out[(size_t)w * N + j] = v;
+      }
+    }
+  } catch (...) {
+    // the device table may hold moves the host has not seen: bring the mirror back in step before reporting the failure
+    (void)hipMemcpy(hcfg_.data(), cfg_, sizeof(int) * (size_t)nw_ * sites, hipMemcpyDeviceToHost);
+    release();
+    throw;
+  }
   release();
 }
 

@@ -132,8 +132,13 @@ void mc_energy_grad_partial_impl(int rows, int cols, int D, int d, int chi, int 
   std::vector<uint64_t> sd(seeds, seeds + n);
   MCUpdateSquareNNExchangeOBC ex(sd);
   MCUpdateSquareNNFullSpaceUpdateOBC fs(sd);
+  MCUpdateSquareTNN3SiteExchange t3(sd);
   std::vector<double> rates, acc_rate(n, 0.0);
-  auto sweep = [&]() { if (updater == 0) ex(sitps, comp, rates); else fs(sitps, comp, rates); };
+  auto sweep = [&]() {
+    if (updater == 0) ex(sitps, comp, rates);
+    else if (updater == 2) t3(sitps, comp, rates);
+    else fs(sitps, comp, rates);
+  };
   for (int s = 0; s < warmup_sweeps; ++s) sweep();
   SquareSpinOneHalfXXZModelOBC xxz(p[0], p[1], p[2]);
   SquareSpinOneHalfJ1J2XXZModelOBC j1j2(p[0], p[1], p[2], p[3], p[4]);
@@ -166,6 +171,9 @@ void mc_sweeps_impl(int rows, int cols, int D, int d, int chi, int dtype, const 
   std::vector<double> rates, acc(n, 0.0);
   if (updater == 0) {
     MCUpdateSquareNNExchangeOBC upd(sd);
+    for (int s = 0; s < n_sweeps; ++s) { upd(sitps, comp, rates); for (int w = 0; w < n; ++w) acc[w] += rates[w]; }
+  } else if (updater == 2) {
+    MCUpdateSquareTNN3SiteExchange upd(sd);
     for (int s = 0; s < n_sweeps; ++s) { upd(sitps, comp, rates); for (int w = 0; w < n; ++w) acc[w] += rates[w]; }
   } else {
     MCUpdateSquareNNFullSpaceUpdateOBC upd(sd);
@@ -229,10 +237,15 @@ void measure_impl(int rows, int cols, int D, int d, int chi, int dtype, const do
     };
     MCUpdateSquareNNExchangeOBC ex(sd);
     MCUpdateSquareNNFullSpaceUpdateOBC fs(sd);
+    MCUpdateSquareTNN3SiteExchange t3(sd);
     if (updater == 0 && model == 0) run(ex, xxz);
     else if (updater == 0 && model == 1) run(ex, tfim);
     else if (updater == 0 && model == 2) run(ex, j1j2);
     else if (updater == 0) run(ex, trij);
+    else if (updater == 2 && model == 0) run(t3, xxz);
+    else if (updater == 2 && model == 1) run(t3, tfim);
+    else if (updater == 2 && model == 2) run(t3, j1j2);
+    else if (updater == 2) run(t3, trij);
     else if (model == 0) run(fs, xxz);
     else if (model == 1) run(fs, tfim);
     else if (model == 2) run(fs, j1j2);
@@ -335,7 +348,7 @@ void fermion_exact_sum_partial_impl(int rows, int cols, int D, int d, const int3
 template <typename TenElemT>
 void fermion_mc_sweeps_impl(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype,
                             const double *sitps_ext_flat, int n, int32_t *configs, const uint64_t *seeds, int n_sweeps,
-                            double *amplitudes_out, double *accept_out) {
+                            double *amplitudes_out, double *accept_out, int updater = 0) {
   SplitIndexTPST<TenElemT> sitps = make_state_t<TenElemT>(rows, cols, D, 4 * d, sitps_ext_flat);
   FermionDecoration dec;
   dec.nf.assign(nf, nf + d);
@@ -343,9 +356,11 @@ void fermion_mc_sweeps_impl(int rows, int cols, int D, int d, const int32_t *nf,
   TPSWaveFunctionComponentT<TenElemT> comp(sitps, make_cfg(n, rows, cols, configs), contractor, &dec);
   std::vector<uint64_t> sd(seeds, seeds + n);
   MCUpdateSquareNNExchangeOBC ex(sd);
+  MCUpdateSquareTNN3SiteExchange t3(sd);
   std::vector<double> rates, acc(n, 0.0);
   for (int s = 0; s < n_sweeps; ++s) {
-    ex(sitps, comp, rates);
+    if (updater == 2) t3(sitps, comp, rates);
+    else ex(sitps, comp, rates);
     for (int w = 0; w < n; ++w) acc[w] += rates[w];
   }
   std::copy(comp.config.data(), comp.config.data() + (size_t)n * rows * cols, configs);
@@ -408,7 +423,7 @@ int pepshost_set_truncate_params(int d_min, double trunc_err, int scheme, double
 }
 
 // n_sweeps Monte-Carlo sweeps (square_nn_updater.h:30-81) of n walkers; updater 0 = NN exchange,
-// 1 = NN full-space (Suwa-Todo).  configs are updated in place; one std::mt19937(seed[w]) per walker.
+// 1 = NN full-space (Suwa-Todo), 2 = three-site exchange (square_3site_updater.h:28-158).  configs are updated in place; one std::mt19937(seed[w]) per walker.
 int pepshost_mc_sweeps(int rows, int cols, int D, int d, int chi, int dtype, const double *sitps_flat, int n,
                        int32_t *configs, const uint64_t *seeds, int updater, int n_sweeps, double *amplitudes_out,
                        double *accept_rates_out) {
@@ -692,6 +707,36 @@ int pepshost_fermion_mc_sweeps_c128(int rows, int cols, int D, int d, const int3
   return guarded([&]() {
     fermion_mc_sweeps_impl<QLTEN_Complex>(rows, cols, D, d, nf, chi, PEPSGPU_C128, sitps_ext_flat, n, configs, seeds, n_sweeps, amplitudes_out,
                                           accept_out);
+  });
+}
+
+// The same with the updater named: 0 = MCUpdateSquareNNExchangeOBC (as pepshost_fermion_mc_sweeps), 2 = MCUpdateSquareTNN3SiteExchange
+int pepshost_fermion_mc_sweeps_updater(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype,
+                                       const double *sitps_ext_flat, int n, int32_t *configs, const uint64_t *seeds, int updater,
+                                       int n_sweeps, double *amplitudes_out, double *accept_out) {
+  return guarded([&]() {
+    if (updater != 0 && updater != 2) throw std::invalid_argument("pepshost_fermion_mc_sweeps_updater: updater must be 0 (exchange) or 2 (tnn3)");
+    fermion_mc_sweeps_impl<double>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, n, configs, seeds, n_sweeps, amplitudes_out, accept_out,
+                                   updater);
+  });
+}
+
+// The triple table of the three-site exchange (pepsgpu_sweep_slice_tnn3) on the host: nf == NULL -> bosonic, dp_or_d states per site,
+// out [dp^3][20]; else fermionic, d = dp_or_d physical states of parities nf[d], over the 4 d extended states of mode order `order`
+// (0 row-major, 1 column-major), out [(4 d)^3][20].
+int pepshost_tnn3_table(int dp_or_d, const int32_t *nf, int order, int32_t *out) {
+  return guarded([&]() {
+    if (dp_or_d < 1 || dp_or_d > 64) throw std::invalid_argument("pepshost_tnn3_table: 1 <= states per site <= 64");
+    if (order != 0 && order != 1) throw std::invalid_argument("pepshost_tnn3_table: order must be 0 (row-major) or 1 (column-major)");
+    std::vector<int32_t> tab;
+    if (nf) {
+      FermionDecoration dec;
+      dec.nf.assign(nf, nf + dp_or_d);
+      tab = FermionTNN3Table(dec, order == 0 ? ROW_MAJOR : COL_MAJOR);
+    } else {
+      tab = TNN3TripleTable(dp_or_d);
+    }
+    std::copy(tab.begin(), tab.end(), out);
   });
 }
 

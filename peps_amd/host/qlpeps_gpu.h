@@ -344,6 +344,7 @@ class BMPSContractorT {
   size_t rows() const { return rows_; }
   size_t cols() const { return cols_; }
   size_t walkers() const { return (size_t)pepsgpu_n_walkers(ctx_); }
+  size_t phys_dim() const { return d_; }                  // states per site on the device (fermions: the 4 d extended states)
   const BMPSTruncateParams &GetTruncateParams() const { return trunc_; }
 
   void UploadState(const SplitIndexTPST<TenElemT> &s) { check_rc(pepsgpu_state_upload(ctx_, dptr(s.flat().data()), ElemTraits<TenElemT>::host_dtype), ctx_); }
@@ -694,6 +695,72 @@ struct FermionDecoration {
   }
 };
 
+// Triple table of the three-site exchange (pepsgpu_sweep_slice_tnn3, square_3site_updater.h:118-127): [dp^3][kTNN3Tab], entry
+// e1 dp^2 + e2 dp + e3 = {m, init, six slots of three states}: the m distinct permutations of the sorted triple in
+// std::next_permutation order, init the slot of the triple itself, unused slots repeating slot 0.  (The engine builds the bosonic
+// table itself for a NULL table -- tnn3_boson_table of engine_sweep.h, the same rule; tests/test_cpu_tnn3.py pins the two together
+// through pepsgpu_diag_tnn3_table.)
+constexpr int kTNN3Tab = 20;
+// the distinct permutations of t in std::next_permutation order of the sorted triple; *init = the slot of t itself; returns their number
+inline int TNN3Permutations(const int32_t t[3], int32_t perm[6][3], int *init) {
+  int32_t p[3] = {t[0], t[1], t[2]};
+  std::sort(p, p + 3);
+  int m = 0;
+  do {
+    if (p[0] == t[0] && p[1] == t[1] && p[2] == t[2]) *init = m;
+    std::copy(p, p + 3, perm[m++]);
+  } while (std::next_permutation(p, p + 3));
+  return m;
+}
+inline void TNN3PutEntry(int32_t *row, int m, int init, const int32_t perm[6][3]) {
+  row[0] = m;
+  row[1] = init;
+  for (int k = 0; k < 6; ++k) std::copy(perm[k < m ? k : 0], perm[k < m ? k : 0] + 3, row + 2 + 3 * k);
+}
+inline std::vector<int32_t> TNN3TripleTable(int dp) {      // bosonic states
+  std::vector<int32_t> tab((size_t)dp * dp * dp * kTNN3Tab);
+  for (int e = 0; e < dp * dp * dp; ++e) {
+    const int32_t t[3] = {e / (dp * dp), (e / dp) % dp, e % dp};
+    int32_t perm[6][3];
+    int init = 0;
+    const int m = TNN3Permutations(t, perm, &init);
+    TNN3PutEntry(tab.data() + (size_t)e * kTNN3Tab, m, init, perm);
+  }
+  return tab;
+}
+// fermions: over the extended states (dp = 4 d) of three sites consecutive in `order`, the permutations of the PHYSICAL triple, each
+// as extended states (the variants follow the parity before the first site, read off its extended state, as DeviceStatesRun does).
+// A triple whose variants do not belong to `order`, or of three equal physical states, maps to itself alone.
+inline std::vector<int32_t> FermionTNN3Table(const FermionDecoration &fd, ModeOrder order) {
+  const int32_t d = (int32_t)fd.d(), dp = 4 * d;
+  std::vector<int32_t> tab((size_t)dp * dp * dp * kTNN3Tab);
+  for (int32_t e = 0; e < dp * dp * dp; ++e) {
+    const int32_t ex[3] = {e / (dp * dp), (e / dp) % dp, e % dp};
+    const int32_t ph[3] = {ex[0] % d, ex[1] % d, ex[2] % d};
+    bool ok = true;
+    for (int q = 0; q < 3; ++q) ok = ok && (order == ROW_MAJOR ? ex[q] / d < 2 : ex[q] / d >= 2);
+    int32_t perm[6][3];
+    int init = 0, m = 1;
+    if (!ok || (ph[0] == ph[1] && ph[1] == ph[2])) {
+      std::copy(ex, ex + 3, perm[0]);
+    } else {
+      m = TNN3Permutations(ph, perm, &init);
+      const int var1 = ex[0] / d, before = order == ROW_MAJOR ? ((var1 & 1) ^ fd.n(ph[0])) : (var1 & 1);
+      for (int k = 0; k < m; ++k) {
+        int par = before;
+        for (int q = 0; q < 3; ++q) {
+          const int32_t a = perm[k][q];
+          const int na = fd.n(a);
+          perm[k][q] = order == ROW_MAJOR ? a + d * (par ^ na) : a + d * (2 + par);
+          par ^= na;
+        }
+      }
+    }
+    TNN3PutEntry(tab.data() + (size_t)e * kTNN3Tab, m, init, perm);
+  }
+  return tab;
+}
+
 // TPSWaveFunctionComponent (wave_function_component.h:136-379), one entry per walker.  `config` is always the
 // PHYSICAL configuration; for a fermionic state (`fermion` set) the device is given the extended states of the
 // current mode order.
@@ -748,29 +815,32 @@ struct TPSWaveFunctionComponentT {
     InitDevice();
     EvaluateAmplitude();
   }
-  // physical candidate states of a nearest-neighbour bond (s1 before s2 in the current mode order) -> device states
-  std::vector<int32_t> DeviceStatesNN(const SiteIdx &s1, const SiteIdx &s2, int n_cand, const std::vector<int32_t> &cand) const {
+  // physical candidate states of a run of sites consecutive in the current mode order (a nearest-neighbour bond, or the three sites
+  // of a row / column triple) -> device states; cand [walker][n_cand][sites.size()]
+  std::vector<int32_t> DeviceStatesRun(const std::vector<SiteIdx> &sites, int n_cand, const std::vector<int32_t> &cand) const {
     if (!fermion) return cand;
-    const size_t nw = config.walkers(), d = fermion->d();
+    const size_t nw = config.walkers(), d = fermion->d(), len = sites.size();
     std::vector<int32_t> out(cand.size());
     for (size_t w = 0; w < nw; ++w) {
-      // parity of the fermions before s1 in the current order (does not depend on the states of s1, s2)
-      const int32_t e1 = fermion->Ext(config, w, s1, order);
+      // parity of the fermions before the first site in the current order (does not depend on the states of the run)
+      const int32_t e1 = fermion->Ext(config, w, sites[0], order);
       const int var1 = e1 / (int32_t)d;                                   // 0/1 (row: inclusive) or 2/3 (col: before)
-      const int before = order == ROW_MAJOR ? ((var1 & 1) ^ fermion->n(config(w, s1))) : (var1 & 1);
+      const int before = order == ROW_MAJOR ? ((var1 & 1) ^ fermion->n(config(w, sites[0]))) : (var1 & 1);
       for (int k = 0; k < n_cand; ++k) {
-        const int32_t a = cand[(w * n_cand + k) * 2], b = cand[(w * n_cand + k) * 2 + 1];
-        const int na = fermion->n(a), nb = fermion->n(b);
-        if (order == ROW_MAJOR) {
-          out[(w * n_cand + k) * 2] = a + (int32_t)d * (before ^ na);
-          out[(w * n_cand + k) * 2 + 1] = b + (int32_t)d * (before ^ na ^ nb);
-        } else {
-          out[(w * n_cand + k) * 2] = a + (int32_t)d * (2 + before);
-          out[(w * n_cand + k) * 2 + 1] = b + (int32_t)d * (2 + (before ^ na));
+        int par = before;
+        for (size_t q = 0; q < len; ++q) {
+          const size_t i = (w * n_cand + k) * len + q;
+          const int32_t a = cand[i];
+          const int na = fermion->n(a);
+          out[i] = order == ROW_MAJOR ? a + (int32_t)d * (par ^ na) : a + (int32_t)d * (2 + par);
+          par ^= na;
         }
       }
     }
     return out;
+  }
+  std::vector<int32_t> DeviceStatesNN(const SiteIdx &s1, const SiteIdx &s2, int n_cand, const std::vector<int32_t> &cand) const {
+    return DeviceStatesRun({s1, s2}, n_cand, cand);
   }
   std::vector<TenElemT> ReplaceNNSiteTrace(const SiteIdx &s1, const SiteIdx &s2, BondOrientation dir, int n_cand,
                                          const std::vector<int32_t> &cand) const {
@@ -801,14 +871,23 @@ struct TPSWaveFunctionComponentT {
       }
     return tab;
   }
+  // Fermions: the three-site exchange of three sites consecutive in the current mode order, the triple table [dp^3][20] of
+  // pepsgpu_sweep_slice_tnn3 over the extended states (dp = 4 d): the distinct permutations of the PHYSICAL triple in
+  // std::next_permutation order, each as the extended states DeviceStatesRun gives it.  A triple whose variants do not belong to the
+  // current order (or whose physical states are equal) maps to itself alone.
+  std::vector<int32_t> TNN3Table() const {
+    if (!fermion) throw std::logic_error("TNN3Table: the component has no fermionic decoration");
+    return FermionTNN3Table(*fermion, order);
+  }
   // UpdateLocal (:345-378) for the walkers with mask != 0; new_states are physical, [walker][site]
   void UpdateLocal(const std::vector<TenElemT> &new_amplitude, const std::vector<SiteIdx> &sites,
                    const std::vector<int32_t> &new_states, const std::vector<uint8_t> &mask) {
     std::vector<int32_t> flat_sites;
     for (auto &s : sites) { flat_sites.push_back((int32_t)s.r); flat_sites.push_back((int32_t)s.c); }
     if (fermion) {
-      if (sites.size() != 2) throw std::invalid_argument("fermionic UpdateLocal: nearest-neighbour pairs only");
-      contractor.UpdateLocal(flat_sites, DeviceStatesNN(sites[0], sites[1], 1, new_states), mask);
+      // (a run of sites consecutive in the current mode order: a nearest-neighbour pair, or a triple of a row / column)
+      if (sites.size() != 2 && sites.size() != 3) throw std::invalid_argument("fermionic UpdateLocal: pairs or triples of consecutive sites only");
+      contractor.UpdateLocal(flat_sites, DeviceStatesRun(sites, 1, new_states), mask);
     } else {
       contractor.UpdateLocal(flat_sites, new_states, mask);
     }
@@ -884,6 +963,34 @@ class MonteCarloSweepUpdaterBase {
     return q.data() + ahead_head_[w];
   }
   void ConsumeUniforms(size_t w, size_t cnt) { ahead_head_[w] += cnt; }
+  // Raw engine words drawn ahead (the three-site slice hands the next words of every walker to the device, which consumes a prefix):
+  // the same discipline as the deviates above.  An updater draws either deviates or raw words, never both.
+  std::vector<std::vector<uint32_t>> words_;   // [walker] drawn, not yet consumed (front = words_head_[w])
+  std::vector<size_t> words_head_;
+  uint32_t NextWord(size_t w) {
+    if (w < words_.size() && words_head_[w] < words_[w].size()) return words_[w][words_head_[w]++];
+    return (uint32_t)engines_[w]();
+  }
+  const uint32_t *PeekWords(size_t w, size_t cnt) {
+    if (words_.size() < engines_.size()) { words_.resize(engines_.size()); words_head_.resize(engines_.size(), 0); }
+    auto &q = words_[w];
+    if (words_head_[w] > 0 && words_head_[w] == q.size()) { q.clear(); words_head_[w] = 0; }
+    else if (words_head_[w] > 64) { q.erase(q.begin(), q.begin() + (long)words_head_[w]); words_head_[w] = 0; }
+    while (q.size() - words_head_[w] < cnt) q.push_back((uint32_t)engines_[w]());
+    return q.data() + words_head_[w];
+  }
+  void ConsumeWords(size_t w, size_t cnt) { words_head_[w] += cnt; }
+  // walker w's std::mt19937 with the queued words served first (a URBG with the engine's range: a distribution draws from it exactly
+  // the words it would draw from the engine)
+  struct QueuedEngine {
+    using result_type = std::mt19937::result_type;
+    MonteCarloSweepUpdaterBase *base;
+    size_t w;
+    static constexpr result_type min() { return std::mt19937::min(); }
+    static constexpr result_type max() { return std::mt19937::max(); }
+    result_type operator()() { return base->NextWord(w); }
+  };
+  QueuedEngine Engine(size_t w) { return QueuedEngine{this, w}; }
 };
 
 // a model opts into the device-side energy slice with `static constexpr bool kExchangeBondEnergy = true` + the scalar hook
@@ -1080,6 +1187,166 @@ class MCUpdateSquareNNFullSpaceUpdateOBC : public MCUpdateSquareNNUpdateBaseOBC<
       new_amp[w] = alt[w * nc + fin];
     }
     comp.UpdateLocal(new_amp, {s1, s2}, ns, changed);
+    return changed;
+  }
+};
+
+// square_3site_updater.h:22-93: sweep schedule of the three-site updaters, CRTP hook TNN3SiteUpdateImpl(site1, site2, site3, dir, sitps,
+// comp) -> changed[w].  Every row (column) starts from the ReplaceTNNSiteTrace of its first window as the amplitude (:39-42, :64-67).
+template <typename MCUpdater>
+class MCUpdateSquareTNN3SiteUpdateBase : public MonteCarloSweepUpdaterBase {
+ public:
+  using MonteCarloSweepUpdaterBase::MonteCarloSweepUpdaterBase;
+  template <typename TenElemT>
+  void operator()(const SplitIndexTPST<TenElemT> &sitps, TPSWaveFunctionComponentT<TenElemT> &comp, std::vector<double> &accept_rates) {
+    auto &c = comp.contractor;
+    const size_t rows = c.rows(), cols = c.cols(), n = comp.config.walkers();
+    // (the reference indexes {row, 2} and {2, col})
+    if (rows < 3 || cols < 3) throw std::invalid_argument("MCUpdateSquareTNN3SiteUpdateBase: the lattice needs at least 3 rows and 3 columns");
+    std::vector<size_t> acc(n, 0);
+    auto add = [&](const std::vector<uint8_t> &a) { for (size_t w = 0; w < n; ++w) acc[w] += a[w]; };
+    // a whole row / column in ONE call (pepsgpu_sweep_slice_tnn3) for an updater that opts in; PEPSHOST_NO_DEVICE_SWEEP=1 forces the
+    // per-triple hook path
+    static const bool no_dev = std::getenv("PEPSHOST_NO_DEVICE_SWEEP") != nullptr;
+    bool dev_slice = false;
+    if constexpr (HasDeviceSliceSweep<MCUpdater>::value) dev_slice = !no_dev && (!comp.fermion || MCUpdater::kDeviceSliceSweepFermions);
+    auto slice = [&](BondOrientation dir, size_t num) {
+      const size_t N = dir == HORIZONTAL ? cols : rows;
+      auto at = [&](size_t j) { return dir == HORIZONTAL ? SiteIdx{num, j} : SiteIdx{j, num}; };
+      if (dev_slice) {
+        if constexpr (HasDeviceSliceSweep<MCUpdater>::value)
+          static_cast<MCUpdater *>(this)->SweepSliceOnDevice(dir, num, sitps, comp, acc);
+        return;
+      }
+      const BTenPOSITION lo = dir == HORIZONTAL ? LEFT : UP, hi = dir == HORIZONTAL ? RIGHT : DOWN;
+      c.InitBTen(lo, num);
+      c.GrowFullBTen(hi, num, 3, true);
+      const std::vector<TenElemT> psi0 = c.ReplaceTNNSiteTrace(at(0), dir, 0, {});
+      for (size_t w = 0; w < n; ++w) comp.amplitude[w] = psi0[w] * GradedSign(comp, w);
+      for (size_t j = 0; j + 2 < N; ++j) {
+        add(static_cast<MCUpdater *>(this)->TNN3SiteUpdateImpl(at(j), at(j + 1), at(j + 2), dir, sitps, comp));
+        if (j + 3 < N) c.ShiftBTenWindow(hi);
+      }
+    };
+    comp.SetOrder(ROW_MAJOR);                // fermions: a row triple is three consecutive modes of the row-major order
+    c.GenerateBMPSApproach(UP);
+    for (size_t row = 0; row < rows; row++) {
+      slice(HORIZONTAL, row);
+      if (row + 1 < rows) c.ShiftBMPSWindow(DOWN);
+    }
+    c.DeleteInnerBMPS(LEFT);
+    c.DeleteInnerBMPS(RIGHT);
+    comp.SetOrder(COL_MAJOR);                // ... and a column triple of the column-major order
+    c.GenerateBMPSApproach(LEFT);
+    for (size_t col = 0; col < cols; col++) {
+      slice(VERTICAL, col);
+      if (col + 1 < cols) c.ShiftBMPSWindow(RIGHT);
+    }
+    c.DeleteInnerBMPS(UP);
+    const double total = double(cols * (rows - 2) + rows * (cols - 2));
+    accept_rates.assign(n, 0.0);
+    for (size_t w = 0; w < n; ++w) accept_rates[w] = double(acc[w]) / total;
+  }
+
+ protected:
+  // the factor from a contraction of the decorated network of the current mode order to the stored (graded, row-major) amplitude
+  template <typename TenElemT>
+  static double GradedSign(const TPSWaveFunctionComponentT<TenElemT> &comp, size_t w) {
+    if (!comp.fermion) return 1.0;
+    return double(comp.fermion->Sigma(comp.config, w) * (comp.order == COL_MAJOR ? comp.fermion->Kappa(comp.config, w) : 1));
+  }
+  // the triple table of the component (bosons: of its physical dimension; fermions: TNN3Table of the current mode order), cached
+  // under everything it depends on: the states per site, the mode order and the parities of the decoration
+  template <typename TenElemT>
+  const std::vector<int32_t> &TripleTable(const TPSWaveFunctionComponentT<TenElemT> &comp) {
+    std::vector<int> key{(int)comp.contractor.phys_dim(), comp.fermion ? (int)comp.order : -1};
+    if (comp.fermion) key.insert(key.end(), comp.fermion->nf.begin(), comp.fermion->nf.end());
+    if (key != tab_key_) { tab_ = comp.fermion ? comp.TNN3Table() : TNN3TripleTable(key[0]); tab_key_ = key; }
+    return tab_;
+  }
+
+ private:
+  std::vector<int32_t> tab_;
+  std::vector<int> tab_key_;
+};
+
+// square_3site_updater.h:98-160
+class MCUpdateSquareTNN3SiteExchange : public MCUpdateSquareTNN3SiteUpdateBase<MCUpdateSquareTNN3SiteExchange> {
+ public:
+  using MCUpdateSquareTNN3SiteUpdateBase<MCUpdateSquareTNN3SiteExchange>::MCUpdateSquareTNN3SiteUpdateBase;
+  static constexpr bool kDeviceSliceSweep = true;
+  static constexpr bool kDeviceSliceSweepFermions = true;   // (a permutation of three consecutive modes is local in the extended states)
+  // one row / column on the device (pepsgpu_sweep_slice_tnn3): walker w consumes the next consumed[w] words of its engine, exactly those
+  // TNN3SiteUpdateImpl would draw.  The slice resets the amplitude, so every walker gets its signs back, not only those that moved.
+  template <typename TenElemT>
+  void SweepSliceOnDevice(BondOrientation dir, size_t slice, const SplitIndexTPST<TenElemT> &, TPSWaveFunctionComponentT<TenElemT> &comp,
+                          std::vector<size_t> &acc) {
+    auto &c = comp.contractor;
+    const size_t n = comp.config.walkers(), N = dir == HORIZONTAL ? c.cols() : c.rows(), nwd = 2 * (N - 2);
+    std::vector<uint32_t> words(n * nwd);
+    for (size_t w = 0; w < n; ++w) {
+      const uint32_t *q = PeekWords(w, nwd);
+      std::copy(q, q + nwd, words.begin() + (long)(w * nwd));
+    }
+    std::vector<int32_t> consumed(n), accepted(n), states(n * N);
+    std::vector<TenElemT> amp(n);
+    check_rc(pepsgpu_sweep_slice_tnn3(c.ctx(), dir, (int)slice, comp.fermion ? TripleTable(comp).data() : nullptr, (int)nwd, words.data(),
+                                      dptr(amp.data()), consumed.data(), accepted.data(), states.data()), c.ctx());
+    const int32_t d = comp.fermion ? (int32_t)comp.fermion->d() : 0;
+    for (size_t w = 0; w < n; ++w) {
+      ConsumeWords(w, (size_t)consumed[w]);
+      acc[w] += (size_t)accepted[w];
+      for (size_t j = 0; j < N; ++j)
+        comp.config(w, dir == HORIZONTAL ? SiteIdx{slice, j} : SiteIdx{j, slice}) = comp.fermion ? states[w * N + j] % d : states[w * N + j];
+      comp.amplitude[w] = amp[w] * GradedSign(comp, w);
+    }
+  }
+  // :109-158 batched over the walkers: one ReplaceTNNSiteTrace with the fixed number of candidate slots of the device path (3 for
+  // phys_dim 2, else 6), so that both paths run the same kernels on the same operands
+  template <typename TenElemT>
+  std::vector<uint8_t> TNN3SiteUpdateImpl(const SiteIdx &s1, const SiteIdx &s2, const SiteIdx &s3, BondOrientation dir,
+                                          const SplitIndexTPST<TenElemT> &, TPSWaveFunctionComponentT<TenElemT> &comp) {
+    auto &c = comp.contractor;
+    const size_t n = comp.config.walkers();
+    const int dp = (int)c.phys_dim(), nslot = dp == 2 ? 3 : 6;
+    const std::vector<int32_t> &tab = TripleTable(comp);
+    const int32_t d = comp.fermion ? (int32_t)comp.fermion->d() : dp;
+    std::vector<int32_t> cand(n * nslot * 3), meta(n * 2);
+    bool any = false;
+    for (size_t w = 0; w < n; ++w) {
+      int32_t e[3];
+      const SiteIdx st[3] = {s1, s2, s3};
+      for (int q = 0; q < 3; ++q) e[q] = comp.fermion ? comp.fermion->Ext(comp.config, w, st[q], comp.order) : comp.config(w, st[q]);
+      const int32_t *row = tab.data() + ((size_t)(e[0] * dp + e[1]) * dp + e[2]) * kTNN3Tab;
+      std::copy(row + 2, row + 2 + 3 * nslot, cand.begin() + (long)(w * nslot * 3));
+      meta[2 * w] = row[0];
+      meta[2 * w + 1] = row[1];
+      any |= row[0] > 1;
+    }
+    std::vector<uint8_t> changed(n, 0);
+    if (!any) return changed;                 // every walker has three equal states (:118)
+    const std::vector<TenElemT> alt = c.ReplaceTNNSiteTrace(s1, dir, nslot, cand);
+    std::vector<int32_t> ns(n * 3);
+    std::vector<TenElemT> new_amp(n);
+    for (size_t w = 0; w < n; ++w) {
+      const int m = meta[2 * w], init = meta[2 * w + 1];
+      if (m <= 1) continue;
+      std::vector<TenElemT> psis(m);
+      double psi_abs_max = 0;
+      for (int i = 0; i < m; ++i) {
+        psis[i] = i == init ? comp.amplitude[w] : alt[w * nslot + i];
+        psi_abs_max = std::max(psi_abs_max, std::abs(psis[i]));
+      }
+      std::vector<double> weights(m);
+      for (int i = 0; i < m; ++i) weights[i] = std::norm(psis[i] / psi_abs_max);
+      QueuedEngine eng = Engine(w);
+      const int fin = (int)SuwaTodoStateUpdate((size_t)init, weights, eng);
+      if (fin == init) continue;
+      changed[w] = 1;
+      for (int q = 0; q < 3; ++q) ns[3 * w + q] = cand[(w * nslot + fin) * 3 + q] % d;     // physical states
+      new_amp[w] = psis[fin];
+    }
+    comp.UpdateLocal(new_amp, {s1, s2, s3}, ns, changed);
     return changed;
   }
 };

@@ -17,9 +17,18 @@ SYMBOLS = ["pepshost_last_error", "pepshost_mc_sweeps", "pepshost_energy_and_hol
            "pepshost_mc_energy_grad_partial_c128", "pepshost_mc_sweeps_c128", "pepshost_load_sitps_c128", "pepshost_dump_sitps_c128",
            "pepshost_mc_engine_warmup", "pepshost_mc_engine_warmup_dist", "pepshost_suwa_todo_chain", "pepshost_load_configuration2", "pepshost_configuration_from_text",
            "pepshost_fermion_measure_energy", "pepshost_measure_c128", "pepshost_exact_sum_measure_partial_c128", "pepshost_fermion_energy_c128",
-           "pepshost_fermion_exact_sum_partial_c128", "pepshost_fermion_mc_sweeps_c128", "pepshost_fermion_measure_energy_c128"]
+           "pepshost_fermion_exact_sum_partial_c128", "pepshost_fermion_mc_sweeps_c128", "pepshost_fermion_measure_energy_c128",
+           "pepshost_fermion_mc_sweeps_updater", "pepshost_tnn3_table"]
 
 _lib = None
+
+# updater ids of the shim: MCUpdateSquareNNExchangeOBC, MCUpdateSquareNNFullSpaceUpdateOBC, MCUpdateSquareTNN3SiteExchange
+UPDATER_ID = {"exchange": 0, "fullspace": 1, "tnn3": 2}
+
+
+def _updater_id(updater):
+    # (any other name has always meant the full-space updater in these calls)
+    return UPDATER_ID.get(updater, 1)
 
 
 def lib():
@@ -84,7 +93,7 @@ def mc_sweeps(flat, configs, seeds, chi, updater="exchange", n_sweeps=1, dtype=1
     amps = np.zeros(n)
     rates = np.zeros(n)
     _ck(lib().pepshost_mc_sweeps(rows, cols, D, d, chi, dtype, _p(flat, C.c_double), n, _p(cfg, C.c_int32),
-                                 _p(sd, C.c_uint64), 0 if updater == "exchange" else 1, n_sweeps,
+                                 _p(sd, C.c_uint64), _updater_id(updater), n_sweeps,
                                  _p(amps, C.c_double), _p(rates, C.c_double)))
     return cfg, amps, rates
 
@@ -223,7 +232,7 @@ def mc_energy_grad_partial(flat, configs, seeds, chi, updater="exchange", model=
     packed = np.zeros(2 * flat.size + 4)
     acc = np.zeros(n)
     _ck(lib().pepshost_mc_energy_grad_partial(rows, cols, D, d, chi, dtype, _p(flat, C.c_double), n, _p(cfg, C.c_int32),
-                                              _p(sd, C.c_uint64), 0 if updater == "exchange" else 1,
+                                              _p(sd, C.c_uint64), _updater_id(updater),
                                               MODEL_ID[model], _p(p, C.c_double), warmup_sweeps, n_samples,
                                               _p(packed, C.c_double), _p(acc, C.c_double)))
     return packed, cfg, acc
@@ -256,13 +265,13 @@ def measure(flat, configs, chi, model="xxz", params=(1.0, 1.0, 0.0), seeds=None,
     l.pepshost_measure_c128.argtypes = [C.c_int] * 5 + l.pepshost_measure.argtypes[6:]
     if cplx:
         _ck(l.pepshost_measure_c128(rows, cols, D, d, chi, _cp(flat), n, _p(cfg, C.c_int32), _p(sd, C.c_uint64),
-                                    {"exchange": 0, "fullspace": 1}[updater], MODEL_ID[model], _p(p, C.c_double), warmup_sweeps,
+                                    UPDATER_ID[updater], MODEL_ID[model], _p(p, C.c_double), warmup_sweeps,
                                     n_samples, sweeps_between_samples, dump_dir.encode(), keys, 4096, _p(vals, C.c_double), cap,
                                     C.byref(nvals)))
         vals = vals[:nvals.value].view(np.complex128)          # every number is a (re, im) pair
     else:
         _ck(l.pepshost_measure(rows, cols, D, d, chi, dtype, _p(flat, C.c_double), n, _p(cfg, C.c_int32), _p(sd, C.c_uint64),
-                               {"exchange": 0, "fullspace": 1}[updater], MODEL_ID[model], _p(p, C.c_double), warmup_sweeps,
+                               UPDATER_ID[updater], MODEL_ID[model], _p(p, C.c_double), warmup_sweeps,
                                n_samples, sweeps_between_samples, dump_dir.encode(), keys, 4096, _p(vals, C.c_double), cap,
                                C.byref(nvals)))
     out, off = {}, 0
@@ -342,7 +351,11 @@ def fermion_energy(state, configs, chi, t, V=0.0, dtype=1, model="spinless", J=0
     return amps, en, psi[:npsi.value]
 
 
-def fermion_mc_sweeps(state, configs, seeds, chi, n_sweeps=1, dtype=1):
+def fermion_mc_sweeps(state, configs, seeds, chi, n_sweeps=1, dtype=1, updater="exchange"):
+    """n_sweeps sweeps of a fermionic state; updater "exchange" (MCUpdateSquareNNExchangeOBC) or "tnn3"
+    (MCUpdateSquareTNN3SiteExchange, real element types)"""
+    if updater not in ("exchange", "tnn3"):
+        raise ValueError("fermion_mc_sweeps: updater must be 'exchange' or 'tnn3'")
     cplx = state.is_complex
     et = np.complex128 if cplx else np.float64
     flat = np.ascontiguousarray(state.extended_flat(), dtype=et)
@@ -352,7 +365,13 @@ def fermion_mc_sweeps(state, configs, seeds, chi, n_sweeps=1, dtype=1):
     nf = np.ascontiguousarray(state.nf, dtype=np.int32)
     sd = np.ascontiguousarray(seeds, dtype=np.uint64)
     amps, rates = np.zeros(n, et), np.zeros(n)
-    if cplx:
+    if updater == "tnn3":
+        if cplx:
+            raise ValueError("fermion_mc_sweeps: the three-site updater takes real fermionic states")
+        _ck(lib().pepshost_fermion_mc_sweeps_updater(rows, cols, D, state.d, _p(nf, C.c_int32), chi, dtype, _p(flat, C.c_double), n,
+                                                     _p(cfg, C.c_int32), _p(sd, C.c_uint64), UPDATER_ID[updater], n_sweeps,
+                                                     _p(amps, C.c_double), _p(rates, C.c_double)))
+    elif cplx:
         _ck(lib().pepshost_fermion_mc_sweeps_c128(rows, cols, D, state.d, _p(nf, C.c_int32), chi, _cp(flat), n,
                                                   _p(cfg, C.c_int32), _p(sd, C.c_uint64), n_sweeps, _cp(amps), _p(rates, C.c_double)))
     else:
@@ -488,7 +507,7 @@ def mc_sweeps_complex(flat, configs, seeds, chi, updater="exchange", n_sweeps=1)
     amps = np.zeros(n, dtype=np.complex128)
     rates = np.zeros(n)
     _ck(lib().pepshost_mc_sweeps_c128(rows, cols, D, d, chi, _cp(flat), n, _p(cfg, C.c_int32), _p(sd, C.c_uint64),
-                                      0 if updater == "exchange" else 1, n_sweeps, _cp(amps), _p(rates, C.c_double)))
+                                      _updater_id(updater), n_sweeps, _cp(amps), _p(rates, C.c_double)))
     return cfg, amps, rates
 
 
@@ -503,7 +522,7 @@ def mc_energy_grad_complex(flat, configs, seeds, chi, updater="exchange", model=
     packed = np.zeros(4 * flat.size + 5)
     acc = np.zeros(n)
     _ck(lib().pepshost_mc_energy_grad_partial_c128(rows, cols, D, d, chi, _cp(flat), n, _p(cfg, C.c_int32), _p(sd, C.c_uint64),
-                                                   0 if updater == "exchange" else 1, MODEL_ID[model], _p(p, C.c_double), warmup_sweeps,
+                                                   _updater_id(updater), MODEL_ID[model], _p(p, C.c_double), warmup_sweeps,
                                                    n_samples, _p(packed, C.c_double), _p(acc, C.c_double)))
     e = np.zeros(2)
     grad = np.zeros(flat.shape, dtype=np.complex128)
@@ -518,4 +537,17 @@ def suwa_todo_chain(init_state, weights, seed, n_steps):
     out = np.zeros(int(n_steps), dtype=np.int32)
     _ck(lib().pepshost_suwa_todo_chain(int(init_state), _p(w, C.c_double), int(w.size), C.c_uint64(int(seed)), C.c_long(int(n_steps)),
                                        _p(out, C.c_int32)))
+    return out
+
+
+def tnn3_table(d, nf=None, order=0):
+    """The triple table of the three-site exchange (pepsgpu_sweep_slice_tnn3), built by the host layer without a device.
+    nf None: bosonic, d states per site -> [d^3][20]; else fermionic (parities nf[d]) over the 4 d extended states of mode
+    order `order` (0 row-major, 1 column-major) -> [(4 d)^3][20]."""
+    l = lib()
+    l.pepshost_tnn3_table.argtypes = [C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32)]
+    dp = d if nf is None else 4 * d
+    out = np.zeros((dp ** 3, 20), dtype=np.int32)
+    nfa = None if nf is None else np.ascontiguousarray(nf, dtype=np.int32)
+    _ck(l.pepshost_tnn3_table(d, None if nfa is None else _p(nfa, C.c_int32), order, _p(out, C.c_int32)))
     return out

@@ -136,4 +136,21 @@ class ArenaScope {
   int exc_;
 };
 
+// A typed pointer that owns one arena block for as long as it lives: `count` elements taken in the constructor (0: no block, a
+// null pointer), given back in the destructor, on either way out of the scope.  reset(p) gives the block back early and adopts p.
+template <typename T>
+class ArenaBuf {
+ public:
+  ArenaBuf(Arena &a, size_t count) : a_(a), p_(count ? (T *)a.alloc(sizeof(T) * count) : nullptr) {}
+  ~ArenaBuf() { a_.free(p_); }
+  ArenaBuf(const ArenaBuf &) = delete;
+  ArenaBuf &operator=(const ArenaBuf &) = delete;
+  void reset(T *p = nullptr) { a_.free(p_); p_ = p; }
+  operator T *() const { return p_; }
+
+ private:
+  Arena &a_;
+  T *p_;
+};
+
 }  // namespace pepsgpu

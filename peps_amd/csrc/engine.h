@@ -28,6 +28,7 @@ namespace pepsgpu {
 
 enum { LEFT = 0, DOWN = 1, RIGHT = 2, UP = 3 };      // include/qlpeps/basic.h:58-63
 enum { HORIZONTAL = 0, VERTICAL = 1 };               // include/qlpeps/basic.h:19-22
+struct SliceGeom;                                    // one row / column as the slice functions walk it (engine_sweep.h)
 
 // batch_flag of the tensor GEMM from a per-walker skip mask: entry b (walker b / div) runs only when skip[b / div] == 0
 __global__ void skip_batch_flag_kernel(const int *__restrict__ skip, int div, int *__restrict__ flag, int nb) {
@@ -114,10 +115,11 @@ struct EngineBase {
   virtual void sr_gram(const void *remote_o, const int32_t *remote_cfg, int n_remote, double *out) = 0;
   virtual void sr_weighted_sum(const double *y, double *out) = 0;
   virtual void sr_copy_samples(void *dst_o, int32_t *dst_cfg) = 0;
-  // mode 0: exchange move (pair_table nullable), mode 1: full-space move (Suwa-Todo over phys_dim^2 states); engine_sweep.h
-  virtual void sweep_slice_impl(int mode, int orient, int slice, int n_uniform, const double *uniforms, const int32_t *pair_table,
-                                int phys_dim, const uint32_t *words, double *amp_inout, int32_t *consumed_out, int32_t *accepted_out,
-                                int32_t *slice_states_out) = 0;
+  // one row / column of exchange moves (pair_table nullable) and of full-space moves (Suwa-Todo over phys_dim^2 states); engine_sweep.h
+  virtual void sweep_slice_exchange(int orient, int slice, int n_uniform, const double *uniforms, const int32_t *pair_table,
+                                    double *amp_inout, int32_t *consumed_out, int32_t *accepted_out, int32_t *slice_states_out) = 0;
+  virtual void sweep_slice_fullspace(int orient, int slice, int phys_dim, const uint32_t *words, double *amp_inout,
+                                     int32_t *accepted_out, int32_t *slice_states_out) = 0;
   // one row / column of three-site exchange moves (MCUpdateSquareTNN3SiteExchange); engine_sweep.h
   virtual void sweep_slice_tnn3(int orient, int slice, const int32_t *triple_table, int n_words, const uint32_t *words,
                                 double *amp_out, int32_t *consumed_out, int32_t *accepted_out, int32_t *slice_states_out) = 0;
@@ -490,8 +492,9 @@ class Engine : public EngineBase {
     bten_[pos].push_back(nb);
   }
   // GrowBTenStep for the slice sweep (engine_sweep.h): walkers with take[w] != 0 adopt `half` (the un-normalised step tensor the
-  // replacement trace already computed with their NEW state of the site), the step runs for the others only; consumes `half`
-  void grow_bten_step_reuse(int pos, BTenDev &half, const int *take);
+  // replacement trace already computed with their NEW state of the site, half_n elements), the step runs for the others only;
+  // gives `half` back to the arena once it is consumed
+  void grow_bten_step_reuse(int pos, ArenaBuf<T> &half, long half_n, const int *take);
   void shift_bten_window(int pos) override {   // grow.h:517-521
     PG_REQUIRE(bten_size(pos) > 0, 3, "ShiftBTenWindow: BTen empty");
     clear_bten(pos, bten_size(pos) - 1);
@@ -954,14 +957,20 @@ class Engine : public EngineBase {
   }
   hipStream_t stream() const { return stream_; }
   // ---- Monte-Carlo sweep of one row / column of bonds on the device (engine_sweep.h) ----
-  void sweep_slice_impl(int mode, int orient, int slice, int n_uniform, const double *uniforms, const int32_t *pair_table, int phys_dim,
-                        const uint32_t *words, double *amp_inout, int32_t *consumed_out, int32_t *accepted_out,
-                        int32_t *slice_states_out) override;
+  void sweep_slice_exchange(int orient, int slice, int n_uniform, const double *uniforms, const int32_t *pair_table, double *amp_inout,
+                            int32_t *consumed_out, int32_t *accepted_out, int32_t *slice_states_out) override;
+  void sweep_slice_fullspace(int orient, int slice, int phys_dim, const uint32_t *words, double *amp_inout, int32_t *accepted_out,
+                             int32_t *slice_states_out) override;
   void sweep_slice_tnn3(int orient, int slice, const int32_t *triple_table, int n_words, const uint32_t *words, double *amp_out,
                         int32_t *consumed_out, int32_t *accepted_out, int32_t *slice_states_out) override;
   void nn_exchange_slice(int orient, int slice, int punch_holes, double *psi_out, double *psi_ex_out) override;
   void energy_slice_impl(int mode, int orient, int slice, int punch_holes, const int32_t *table, int n_cand, int psi_per_bond,
                          double *psi_out, double *val_out) override;
+  // the parts the slice functions share (engine_sweep.h)
+  void begin_slice(const SliceGeom &g, int remain);
+  template <typename Moves>
+  void sweep_slice_frame(const SliceGeom &g, int window, const Acc *damp, int *dcnt, double *amp_out, int32_t *consumed_out,
+                         int32_t *accepted_out, int32_t *slice_states_out, Moves &&moves);
   // ---- BMPSWalker (engine_walker.h) ----
   int walker_create(int pos, int level) override;
   int walker_clone(int id) override;

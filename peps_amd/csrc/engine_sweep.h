@@ -11,7 +11,7 @@
 //
 // Identical chains: the reference draws a uniform deviate only when the spins differ and |psi'| < |psi| (square_nn_updater.h:
 // 160-170).  The host hands over, per walker, the NEXT `n_uniform` deviates of that walker's std::mt19937 stream (drawn ahead into
-// a queue, qlpeps_gpu.h: UniformQueue); the kernel consumes them in order and reports how many it took, the host pops exactly
+// a queue, qlpeps_gpu.h: LookAhead); the kernel consumes them in order and reports how many it took, the host pops exactly
 // those -- the deviates a walker consumes are the ones the reference's updater would have drawn, in the same order.
 //
 // Environment bookkeeping: UpdateLocal erases the environments that cross an updated site (EraseEnvsAfterUpdate).  Inside a slice
@@ -215,6 +215,76 @@ __global__ void slice_store_value_kernel(const AccT *__restrict__ res, const dou
   sw_put(o, sw_scaled(res[e], exp(lsum[w])));
 }
 
+// One row (HORIZONTAL) or column (VERTICAL) of the lattice as the slice functions below walk it: N positions j = 0 .. N - 1, the
+// environment that grows with j (lo: LEFT / UP) and the one that shrinks (hi: RIGHT / DOWN).  All the orientation logic of a slice.
+struct SliceGeom {
+  int orient, slice, Lx, N, lo, hi;
+  SliceGeom(int orient_, int slice_, int Lx_, int Ly_) : orient(orient_), slice(slice_), Lx(Lx_) {
+    PG_REQUIRE(orient == HORIZONTAL || orient == VERTICAL, 1, "bad orientation");
+    const bool h = orient == HORIZONTAL;
+    PG_REQUIRE(slice >= 0 && slice < (h ? Ly_ : Lx_), 1, "slice outside the lattice");
+    N = h ? Lx_ : Ly_;
+    lo = h ? LEFT : UP;
+    hi = h ? RIGHT : DOWN;
+  }
+  int row(int j) const { return orient == HORIZONTAL ? slice : j; }
+  int col(int j) const { return orient == HORIZONTAL ? j : slice; }
+  int site(int j) const { return row(j) * Lx + col(j); }                    // flat index into a walker's configuration
+  int first() const { return site(0); }                                      // sweep_gather_slice_kernel: site(j) = first + j stride
+  int stride() const { return site(1) - site(0); }
+};
+
+// status 4 unless every state of a table handed over by the host is one of the dp states of a site
+inline void require_states(const int32_t *tab, size_t len, int dp, const char *msg) {
+  for (size_t e = 0; e < len; ++e) PG_REQUIRE(tab[e] >= 0 && tab[e] < dp, 4, msg);
+}
+
+// InitBTen + GrowFullBTen of the slice: the growing environment empty, the shrinking one down to the last `remain` positions
+template <typename T>
+void Engine<T>::begin_slice(const SliceGeom &g, int remain) {
+  init_bten(g.lo, g.slice);
+  grow_full_bten(g.hi, g.slice, remain, 1);
+}
+
+// The part every sweep slice shares.  dcnt = [consumed n][accepted n][overrun 1] is zeroed, the slice's environments are set up
+// (begin_slice with the width of the move's window), `moves` runs the slice's moves on the device, and ONE read-back ends the call: the
+// amplitudes damp [n] into amp_out, the counters, and the states of the slice, which also go into the host mirror hcfg_.
+// From the first move on the device's configuration table may hold moves the host has not seen: whatever fails after that, the
+// mirror is brought back in step before the failure is reported.
+template <typename T>
+template <typename Moves>
+void Engine<T>::sweep_slice_frame(const SliceGeom &g, int window, const Acc *damp, int *dcnt, double *amp_out, int32_t *consumed_out,
+                                  int32_t *accepted_out, int32_t *slice_states_out, Moves &&moves) {
+  const int sites = Ly_ * Lx_, N = g.N;
+  ArenaBuf<int> dslice(arena_, (size_t)nw_ * N);
+  std::vector<int> hs((size_t)nw_ * N), hc(2 * (size_t)nw_ + 1);
+  try {
+    PG_CHECK_HIP(hipMemsetAsync(dcnt, 0, sizeof(int) * hc.size(), stream_));
+    begin_slice(g, window);
+    moves();
+    hipLaunchKernelGGL(sweep_gather_slice_kernel, dim3((nw_ * N + 255) / 256), dim3(256), 0, stream_, (const int *)cfg_, sites, g.first(),
+                       g.stride(), N, dslice, nw_);
+    PG_CHECK_HIP(hipGetLastError());
+    PG_CHECK_HIP(hipMemcpyAsync(amp_out, damp, sizeof(Acc) * nw_, hipMemcpyDeviceToHost, stream_));
+    PG_CHECK_HIP(hipMemcpyAsync(hs.data(), dslice, sizeof(int) * hs.size(), hipMemcpyDeviceToHost, stream_));
+    PG_CHECK_HIP(hipMemcpyAsync(hc.data(), dcnt, sizeof(int) * hc.size(), hipMemcpyDeviceToHost, stream_));
+    PG_CHECK_HIP(hipStreamSynchronize(stream_));
+    PG_REQUIRE(hc[2 * (size_t)nw_] == 0, 5, "device-side slice sweep: uniform deviates exhausted");
+    for (int w = 0; w < nw_; ++w) {
+      if (consumed_out) consumed_out[w] = hc[w];
+      if (accepted_out) accepted_out[w] = hc[nw_ + w];
+      for (int j = 0; j < N; ++j) {
+        const int v = hs[(size_t)w * N + j];
+        hcfg_[(size_t)w * sites + g.site(j)] = v;
+        if (slice_states_out) slice_states_out[(size_t)w * N + j] = v;
+      }
+    }
+  } catch (...) {
+    (void)hipMemcpy(hcfg_.data(), cfg_, sizeof(int) * (size_t)nw_ * sites, hipMemcpyDeviceToHost);
+    throw;
+  }
+}
+
 // One row / column of the energy evaluation (SquareNNNModelEnergySolver::CalEnergyAndHolesImpl, square_nnn_energy_solver.h:
 // 116-200 row pass, bond_traversal_mixin.h:120-144 column pass) for models whose nearest-neighbour off-diagonal term is the
 // exchange of the two site states (XXZ, J1-J2, t-J ...): InitBTen + GrowFullBTen, psi of the slice, and for every bond the
@@ -244,16 +314,14 @@ void Engine<T>::energy_slice_impl(int mode, int orient, int slice, int punch_hol
                                   double *psi_out, double *val_out) {
   require_ready();
   PG_REQUIRE(mode == 0 || mode == 1, 1, "energy slice: bad mode");
-  PG_REQUIRE(orient == HORIZONTAL || orient == VERTICAL, 1, "bad orientation");
-  const int N = orient == HORIZONTAL ? Lx_ : Ly_, lim = orient == HORIZONTAL ? Ly_ : Lx_;
-  PG_REQUIRE(slice >= 0 && slice < lim, 1, "slice outside the lattice");
+  const SliceGeom g(orient, slice, Lx_, Ly_);
+  const int N = g.N;
   PG_REQUIRE(psi_out && val_out, 1, "null buffer");
   const int nc = mode == 1 ? n_cand : 1;
   PG_REQUIRE(nc >= 1, 1, "energy slice: n_cand < 1");
   PG_REQUIRE(mode == 0 || table, 1, "one-site slice: null site table");
-  const int tab_len = mode == 0 ? 2 * dp_ * dp_ : dp_ * nc;
-  if (table)
-    for (int e = 0; e < tab_len; ++e) PG_REQUIRE(table[e] >= 0 && table[e] < dp_, 4, "energy slice table: state out of range");
+  const size_t tab_len = !table ? 0 : mode == 0 ? 2 * (size_t)dp_ * dp_ : (size_t)dp_ * nc;
+  require_states(table, tab_len, dp_, "energy slice table: state out of range");
   const bool per_bond = mode == 0 && psi_per_bond;
   const int sites = Ly_ * Lx_;
   if (punch_holes && !holes_) {
@@ -265,77 +333,70 @@ void Engine<T>::energy_slice_impl(int mode, int orient, int slice, int punch_hol
   const int stride = mode == 1 ? 1 + N * nc : (per_bond ? 2 * (N - 1) : N);
   auto psi_col = [&](int j) { return per_bond ? j : 0; };
   auto ex_col = [&](int j) { return per_bond ? N - 1 + j : 1 + j; };
-  double *dval = (double *)arena_.alloc(sizeof(double) * kOut * (size_t)nw_ * stride);
-  int *dcand = (int *)arena_.alloc(sizeof(int) * (mode == 1 ? (size_t)nc : 3) * (size_t)nw_);
+  ArenaBuf<double> dval(arena_, kOut * (size_t)nw_ * stride);
+  ArenaBuf<int> dcand(arena_, (mode == 1 ? (size_t)nc : 3) * (size_t)nw_);
   int *dsame = mode == 0 ? dcand + 2 * (size_t)nw_ : nullptr;
-  int *dtab = table ? (int *)arena_.alloc(sizeof(int) * (size_t)tab_len) : nullptr;
-  auto release = [&]() { arena_.free(dval); arena_.free(dcand); if (dtab) arena_.free(dtab); };
-  try {
-    if (dtab) PG_CHECK_HIP(hipMemcpyAsync(dtab, table, sizeof(int) * (size_t)tab_len, hipMemcpyHostToDevice, stream_));
-    const int lo = orient == HORIZONTAL ? LEFT : UP, hi = orient == HORIZONTAL ? RIGHT : DOWN;
-    const int remain = (mode == 1 || punch_holes) ? 1 : 2;
-    init_bten(lo, slice);
-    grow_full_bten(hi, slice, remain, 1);
-    const int gb = (nw_ + 255) / 256;
-    // res exp(lsum) of a trace into column col (frees res and lsum)
-    auto store = [&](Acc *res, double *lsum, int col, int ncs, const int *same, int same_col) {
-      hipLaunchKernelGGL(slice_store_value_kernel<Acc>, dim3((nw_ * ncs + 255) / 256), dim3(256), 0, stream_, (const Acc *)res,
-                         (const double *)lsum, dval, stride, col, ncs, same, same_col, nw_);
+  ArenaBuf<int> dtab(arena_, tab_len);
+  if (dtab) PG_CHECK_HIP(hipMemcpyAsync(dtab, table, sizeof(int) * tab_len, hipMemcpyHostToDevice, stream_));
+  const int remain = (mode == 1 || punch_holes) ? 1 : 2;
+  begin_slice(g, remain);
+  const int gb = (nw_ + 255) / 256;
+  // res exp(lsum) of a trace into column col (frees res and lsum)
+  auto store = [&](Acc *res, double *lsum, int col, int ncs, const int *same, int same_col) {
+    hipLaunchKernelGGL(slice_store_value_kernel<Acc>, dim3((nw_ * ncs + 255) / 256), dim3(256), 0, stream_, (const Acc *)res,
+                       (const double *)lsum, dval, stride, col, ncs, same, same_col, nw_);
+    PG_CHECK_HIP(hipGetLastError());
+    arena_.free(res); arena_.free(lsum);
+  };
+  if (!per_bond) {
+    double *lsum = nullptr;
+    Acc *res = nn_trace_device(g.row(0), g.col(0), orient, 1, nullptr, &lsum);
+    store(res, lsum, 0, 1, nullptr, 0);
+  }
+  for (int j = 0; j < N; ++j) {
+    const int r1 = g.row(j), c1 = g.col(j);
+    if (punch_holes) punch_hole(r1, c1, orient, nullptr);
+    if (mode == 1) {
+      hipLaunchKernelGGL(slice_onsite_cand_kernel, dim3((nw_ * nc + 255) / 256), dim3(256), 0, stream_, (const int *)cfg_, sites,
+                         g.site(j), (const int *)dtab, nc, dcand, nw_);
       PG_CHECK_HIP(hipGetLastError());
-      arena_.free(res); arena_.free(lsum);
-    };
-    if (!per_bond) {
       double *lsum = nullptr;
-      Acc *res = nn_trace_device(orient == HORIZONTAL ? slice : 0, orient == HORIZONTAL ? 0 : slice, orient, 1, nullptr, &lsum);
-      store(res, lsum, 0, 1, nullptr, 0);
+      Acc *res = one_trace_device(r1, c1, orient, nc, dcand, &lsum);
+      store(res, lsum, 1 + j * nc, nc, nullptr, 0);
+      if (j + 1 < N) shift_bten_window(g.hi);
+    } else if (j + 1 < N) {
+      if (per_bond) {
+        double *lsum = nullptr;
+        Acc *res = nn_trace_device(r1, c1, orient, 1, nullptr, &lsum);
+        store(res, lsum, psi_col(j), 1, nullptr, 0);
+      }
+      hipLaunchKernelGGL(sweep_swap_cand_kernel, dim3(gb), dim3(256), 0, stream_, (const int *)cfg_, sites, g.site(j), g.site(j + 1),
+                         dcand, dsame, nw_, (const int *)dtab, dp_);
+      PG_CHECK_HIP(hipGetLastError());
+      double *lsum = nullptr;
+      Acc *res = nn_trace_device(r1, c1, orient, 1, dcand, &lsum, dsame);
+      store(res, lsum, ex_col(j), 1, dsame, psi_col(j));
+      if (remain == 1 || j + 2 < N) shift_bten_window(g.hi);
     }
-    for (int j = 0; j < N; ++j) {
-      const int r1 = orient == HORIZONTAL ? slice : j, c1 = orient == HORIZONTAL ? j : slice;
-      if (punch_holes) punch_hole(r1, c1, orient, nullptr);
-      if (mode == 1) {
-        hipLaunchKernelGGL(slice_onsite_cand_kernel, dim3((nw_ * nc + 255) / 256), dim3(256), 0, stream_, (const int *)cfg_, sites,
-                           r1 * Lx_ + c1, (const int *)dtab, nc, dcand, nw_);
-        PG_CHECK_HIP(hipGetLastError());
-        double *lsum = nullptr;
-        Acc *res = one_trace_device(r1, c1, orient, nc, dcand, &lsum);
-        store(res, lsum, 1 + j * nc, nc, nullptr, 0);
-        if (j + 1 < N) shift_bten_window(hi);
-      } else if (j + 1 < N) {
-        const int r2 = orient == HORIZONTAL ? slice : j + 1, c2 = orient == HORIZONTAL ? j + 1 : slice;
-        if (per_bond) {
-          double *lsum = nullptr;
-          Acc *res = nn_trace_device(r1, c1, orient, 1, nullptr, &lsum);
-          store(res, lsum, psi_col(j), 1, nullptr, 0);
-        }
-        hipLaunchKernelGGL(sweep_swap_cand_kernel, dim3(gb), dim3(256), 0, stream_, (const int *)cfg_, sites, r1 * Lx_ + c1, r2 * Lx_ + c2,
-                           dcand, dsame, nw_, (const int *)dtab, dp_);
-        PG_CHECK_HIP(hipGetLastError());
-        double *lsum = nullptr;
-        Acc *res = nn_trace_device(r1, c1, orient, 1, dcand, &lsum, dsame);
-        store(res, lsum, ex_col(j), 1, dsame, psi_col(j));
-        if (remain == 1 || j + 2 < N) shift_bten_window(hi);
+  }
+  std::vector<double> h((size_t)kOut * nw_ * stride);
+  PG_CHECK_HIP(hipMemcpyAsync(h.data(), dval, sizeof(double) * h.size(), hipMemcpyDeviceToHost, stream_));
+  PG_CHECK_HIP(hipStreamSynchronize(stream_));
+  auto put = [&](double *dst, size_t i, int w, int col) {
+    for (int q = 0; q < kOut; ++q) dst[i * kOut + q] = h[((size_t)w * stride + col) * kOut + q];
+  };
+  for (int w = 0; w < nw_; ++w) {
+    if (mode == 1) {
+      put(psi_out, w, w, 0);
+      for (int e = 0; e < N * nc; ++e) put(val_out, (size_t)w * N * nc + e, w, 1 + e);
+    } else {
+      if (!per_bond) put(psi_out, w, w, 0);
+      for (int j = 0; j + 1 < N; ++j) {
+        if (per_bond) put(psi_out, (size_t)w * (N - 1) + j, w, psi_col(j));
+        put(val_out, (size_t)w * (N - 1) + j, w, ex_col(j));
       }
     }
-    std::vector<double> h((size_t)kOut * nw_ * stride);
-    PG_CHECK_HIP(hipMemcpyAsync(h.data(), dval, sizeof(double) * h.size(), hipMemcpyDeviceToHost, stream_));
-    PG_CHECK_HIP(hipStreamSynchronize(stream_));
-    auto put = [&](double *dst, size_t i, int w, int col) {
-      for (int q = 0; q < kOut; ++q) dst[i * kOut + q] = h[((size_t)w * stride + col) * kOut + q];
-    };
-    for (int w = 0; w < nw_; ++w) {
-      if (mode == 1) {
-        put(psi_out, w, w, 0);
-        for (int e = 0; e < N * nc; ++e) put(val_out, (size_t)w * N * nc + e, w, 1 + e);
-      } else {
-        if (!per_bond) put(psi_out, w, w, 0);
-        for (int j = 0; j + 1 < N; ++j) {
-          if (per_bond) put(psi_out, (size_t)w * (N - 1) + j, w, psi_col(j));
-          put(val_out, (size_t)w * (N - 1) + j, w, ex_col(j));
-        }
-      }
-    }
-  } catch (...) { release(); throw; }
-  release();
+  }
 }
 
 // ---- three-site exchange (MCUpdateSquareTNN3SiteExchange::TNN3SiteUpdateImpl, square_3site_updater.h:109-158) ----
@@ -444,97 +505,57 @@ template <typename T>
 void Engine<T>::sweep_slice_tnn3(int orient, int slice, const int32_t *triple_table, int n_words, const uint32_t *words, double *amp_out,
                                  int32_t *consumed_out, int32_t *accepted_out, int32_t *slice_states_out) {
   require_ready();
-  PG_REQUIRE(orient == HORIZONTAL || orient == VERTICAL, 1, "bad orientation");
+  const SliceGeom g(orient, slice, Lx_, Ly_);
   PG_REQUIRE(Ly_ >= 3 && Lx_ >= 3, 1, "three-site slice: the lattice needs at least 3 rows and 3 columns");
-  const int N = orient == HORIZONTAL ? Lx_ : Ly_, lim = orient == HORIZONTAL ? Ly_ : Lx_;
-  PG_REQUIRE(slice >= 0 && slice < lim, 1, "slice outside the lattice");
-  PG_REQUIRE(words && n_words >= 2 * (N - 2), 1, "three-site slice: two engine words per triple of the slice are needed");
-  const int sites = Ly_ * Lx_, nslot = dp_ == 2 ? 3 : 6;
+  PG_REQUIRE(words && n_words >= 2 * (g.N - 2), 1, "three-site slice: two engine words per triple of the slice are needed");
+  const int sites = Ly_ * Lx_, nslot = dp_ == 2 ? 3 : 6, gb = (nw_ + 255) / 256;
   const size_t ntab = (size_t)dp_ * dp_ * dp_ * TNN3_TAB;
   std::vector<int32_t> own;
   if (!triple_table) { own = tnn3_boson_table(dp_); triple_table = own.data(); }
-  for (size_t e = 0; e < ntab / TNN3_TAB; ++e) {
-    const int32_t *t = triple_table + e * TNN3_TAB;
+  for (size_t e = 0; e < ntab; e += TNN3_TAB) {
+    const int32_t *t = triple_table + e;
     PG_REQUIRE((t[0] == 1 || t[0] == 3 || t[0] == 6) && t[0] <= nslot && t[1] >= 0 && t[1] < t[0], 4,
                "triple table: bad permutation count or initial slot");
-    for (int k = 2; k < TNN3_TAB; ++k) PG_REQUIRE(t[k] >= 0 && t[k] < dp_, 4, "triple table: state out of range");
+    require_states(t + 2, TNN3_TAB - 2, dp_, "triple table: state out of range");
   }
-  Acc *damp = (Acc *)arena_.alloc(sizeof(Acc) * nw_);
-  unsigned *dwords = (unsigned *)arena_.alloc(sizeof(unsigned) * (size_t)nw_ * n_words);
-  int *dcnt = (int *)arena_.alloc(sizeof(int) * 2 * (size_t)nw_);          // used words [n], accepted moves [n]
-  int *dcand = (int *)arena_.alloc(sizeof(int) * (3 * (size_t)nslot + 3) * (size_t)nw_);
+  ArenaBuf<Acc> damp(arena_, nw_);
+  ArenaBuf<unsigned> dwords(arena_, (size_t)nw_ * n_words);
+  ArenaBuf<int> dcnt(arena_, 2 * (size_t)nw_ + 1);                          // used words [n], accepted moves [n], (overrun: never set)
+  ArenaBuf<int> dcand(arena_, (3 * (size_t)nslot + 3) * (size_t)nw_);
   int *dmeta = dcand + 3 * (size_t)nslot * nw_, *dskip = dmeta + 2 * (size_t)nw_;
-  int *dslice = (int *)arena_.alloc(sizeof(int) * (size_t)nw_ * N);
-  int *dtab = (int *)arena_.alloc(sizeof(int) * ntab);
-  auto release = [&]() {
-    arena_.free(damp); arena_.free(dwords); arena_.free(dcnt); arena_.free(dcand); arena_.free(dslice); arena_.free(dtab);
-  };
-  try {
-    PG_CHECK_HIP(hipMemcpyAsync(dwords, words, sizeof(unsigned) * (size_t)nw_ * n_words, hipMemcpyHostToDevice, stream_));
-    PG_CHECK_HIP(hipMemcpyAsync(dtab, triple_table, sizeof(int) * ntab, hipMemcpyHostToDevice, stream_));
-    PG_CHECK_HIP(hipMemsetAsync(dcnt, 0, sizeof(int) * 2 * (size_t)nw_, stream_));
-    const int lo = orient == HORIZONTAL ? LEFT : UP, hi = orient == HORIZONTAL ? RIGHT : DOWN;
-    init_bten(lo, slice);
-    grow_full_bten(hi, slice, 3, 1);
-    const int gb = (nw_ + 255) / 256;
+  ArenaBuf<int> dtab(arena_, ntab);
+  PG_CHECK_HIP(hipMemcpyAsync(dwords, words, sizeof(unsigned) * (size_t)nw_ * n_words, hipMemcpyHostToDevice, stream_));
+  PG_CHECK_HIP(hipMemcpyAsync(dtab, triple_table, sizeof(int) * ntab, hipMemcpyHostToDevice, stream_));
+  sweep_slice_frame(g, 3, damp, dcnt, amp_out, consumed_out, accepted_out, slice_states_out, [&] {
     {
       double *lsum = nullptr;
-      Acc *res = tnn_trace_device(orient == HORIZONTAL ? slice : 0, orient == HORIZONTAL ? 0 : slice, orient, 1, nullptr, &lsum);
+      Acc *res = tnn_trace_device(g.row(0), g.col(0), orient, 1, nullptr, &lsum);
       hipLaunchKernelGGL(tnn3_reset_amp_kernel<Acc>, dim3(gb), dim3(256), 0, stream_, (const Acc *)res, (const double *)lsum, damp, nw_);
       PG_CHECK_HIP(hipGetLastError());
       arena_.free(res);
       arena_.free(lsum);
     }
-    for (int j = 0; j + 2 < N; ++j) {
-      int r[3], c[3], s[3];
-      for (int k = 0; k < 3; ++k) {
-        r[k] = orient == HORIZONTAL ? slice : j + k;
-        c[k] = orient == HORIZONTAL ? j + k : slice;
-        s[k] = r[k] * Lx_ + c[k];
-      }
-      hipLaunchKernelGGL(tnn3_cand_kernel, dim3(gb), dim3(256), 0, stream_, (const int *)cfg_, sites, s[0], s[1], s[2], (const int *)dtab,
-                         dp_, nslot, dcand, dmeta, dskip, nw_);
+    for (int j = 0; j + 2 < g.N; ++j) {
+      const int s1 = g.site(j), s2 = g.site(j + 1), s3 = g.site(j + 2);
+      hipLaunchKernelGGL(tnn3_cand_kernel, dim3(gb), dim3(256), 0, stream_, (const int *)cfg_, sites, s1, s2, s3, (const int *)dtab, dp_,
+                         nslot, dcand, dmeta, dskip, nw_);
       PG_CHECK_HIP(hipGetLastError());
       double *lsum = nullptr;
-      Acc *res = tnn_trace_device(r[0], c[0], orient, nslot, dcand, &lsum, dskip);
-      hipLaunchKernelGGL(tnn3_decide_kernel<Acc>, dim3(gb), dim3(256), 0, stream_, cfg_, sites, s[0], s[1], s[2], (const Acc *)res,
+      Acc *res = tnn_trace_device(g.row(j), g.col(j), orient, nslot, dcand, &lsum, dskip);
+      hipLaunchKernelGGL(tnn3_decide_kernel<Acc>, dim3(gb), dim3(256), 0, stream_, cfg_, sites, s1, s2, s3, (const Acc *)res,
                          (const double *)lsum, damp, (const int *)dcand, (const int *)dmeta, nslot, (const unsigned *)dwords, n_words,
                          dcnt, dcnt + nw_, nw_);
       PG_CHECK_HIP(hipGetLastError());
       arena_.free(res);
       arena_.free(lsum);
-      for (int k = 0; k < 3; ++k) erase_envs_after_update(r[k], c[k]);
-      if (j + 3 < N) shift_bten_window(hi);
+      for (int k = 0; k < 3; ++k) erase_envs_after_update(g.row(j + k), g.col(j + k));
+      if (j + 3 < g.N) shift_bten_window(g.hi);
     }
-    hipLaunchKernelGGL(sweep_gather_slice_kernel, dim3((nw_ * N + 255) / 256), dim3(256), 0, stream_, (const int *)cfg_, sites,
-                       orient == HORIZONTAL ? slice * Lx_ : slice, orient == HORIZONTAL ? 1 : Lx_, N, dslice, nw_);
-    PG_CHECK_HIP(hipGetLastError());
-    std::vector<int> hs((size_t)nw_ * N), hc(2 * (size_t)nw_);
-    PG_CHECK_HIP(hipMemcpyAsync(amp_out, damp, sizeof(Acc) * nw_, hipMemcpyDeviceToHost, stream_));
-    PG_CHECK_HIP(hipMemcpyAsync(hs.data(), dslice, sizeof(int) * hs.size(), hipMemcpyDeviceToHost, stream_));
-    PG_CHECK_HIP(hipMemcpyAsync(hc.data(), dcnt, sizeof(int) * hc.size(), hipMemcpyDeviceToHost, stream_));
-    PG_CHECK_HIP(hipStreamSynchronize(stream_));
-    for (int w = 0; w < nw_; ++w) {
-      if (consumed_out) consumed_out[w] = hc[w];
-      if (accepted_out) accepted_out[w] = hc[nw_ + w];
-      for (int j = 0; j < N; ++j) {
-        const int v = hs[(size_t)w * N + j];
-        const int rr = orient == HORIZONTAL ? slice : j, cc = orient == HORIZONTAL ? j : slice;
-        hcfg_[(size_t)w * sites + rr * Lx_ + cc] = v;          // host mirror of the configuration table
-        if (slice_states_out) slice_states_out[(size_t)w * N + j] = v;
-      }
-    }
-  } catch (...) {
-    // the device table may hold moves the host has not seen: bring the mirror back in step before reporting the failure
-    (void)hipMemcpy(hcfg_.data(), cfg_, sizeof(int) * (size_t)nw_ * sites, hipMemcpyDeviceToHost);
-    release();
-    throw;
-  }
-  release();
+  });
 }
 
 template <typename T>
-void Engine<T>::grow_bten_step_reuse(int pos, BTenDev &half, const int *take) {
+void Engine<T>::grow_bten_step_reuse(int pos, ArenaBuf<T> &half, long half_n, const int *take) {
   require_ready();
   int pre = (pos + 3) % 4, nxt = (pos + 1) % 4;
   int bs = bten_size(pos);
@@ -553,13 +574,12 @@ void Engine<T>::grow_bten_step_reuse(int pos, BTenDev &half, const int *take) {
   const BTenDev &bt = bten_[pos].back();
   BTenDev nb = bten_step(pos, bt, b1.t[n - bs], sel, b2.t[bs - 1], 1, false, 1, lv(b1, n - bs), lv(b1, n - bs + 1), lv(b2, bs - 1),
                          lv(b2, bs), take);
-  try {      // (nb is not owned by anything yet: an error below must not leave it in the arena; `half` stays the caller's until consumed)
-    PG_REQUIRE(nb.t.n == half.t.n, 3, "GrowBTenStep: the kept half step has another shape");
+  try {      // (nb is not owned by anything yet: an error below must not leave it in the arena)
+    PG_REQUIRE(nb.t.n == half_n, 3, "GrowBTenStep: the kept half step has another shape");
     hipLaunchKernelGGL(sweep_take_kernel<T>, dim3((unsigned)std::min<long>(8, (nb.t.n + 255) / 256), nw_), dim3(256), 0, stream_, nb.t.p,
-                       (const T *)half.t.p, (long)nb.t.n, take);
+                       (const T *)half, (long)nb.t.n, take);
     PG_CHECK_HIP(hipGetLastError());
-    free_ten(half.t);
-    half.t.p = nullptr;
+    half.reset();
     nb.logscale = (double *)arena_.alloc(sizeof(double) * nw_);
     PG_CHECK_HIP(hipMemcpyAsync(nb.logscale, bt.logscale, sizeof(double) * nw_, hipMemcpyDeviceToDevice, stream_));
     normalize(nb.t.p, nb.t.n, nb.t.n, nw_, nb.logscale);
@@ -571,124 +591,90 @@ void Engine<T>::grow_bten_step_reuse(int pos, BTenDev &half, const int *take) {
   bten_[pos].push_back(nb);
 }
 
-// One slice of a sweep of a two-site updater on the device.  mode 0: the exchange move (pair_table == nullptr: swap of the two
-// states; else the tabulated pair, see sweep_swap_cand_kernel) with the Metropolis test; mode 1: the full-space move (Suwa-Todo over
-// the phys_dim^2 states of the pair, sweep_suwa_todo_kernel).  amp_inout: [n] amplitudes of the element type (complex: interleaved).
+// One slice of the sweep of the exchange updater on the device: per bond the candidate (pair_table == nullptr: the swap of the two
+// states; else the tabulated pair, see sweep_swap_cand_kernel), its replacement trace, the Metropolis test and the move.
+// amp_inout: [n] amplitudes of the accumulation type (complex: interleaved).
 template <typename T>
-void Engine<T>::sweep_slice_impl(int mode, int orient, int slice, int n_uniform, const double *uniforms, const int32_t *pair_table,
-                                 int phys_dim, const uint32_t *words, double *amp_inout, int32_t *consumed_out, int32_t *accepted_out,
-                                 int32_t *slice_states_out) {
+void Engine<T>::sweep_slice_exchange(int orient, int slice, int n_uniform, const double *uniforms, const int32_t *pair_table,
+                                     double *amp_inout, int32_t *consumed_out, int32_t *accepted_out, int32_t *slice_states_out) {
   require_ready();
-  PG_REQUIRE(orient == HORIZONTAL || orient == VERTICAL, 1, "bad orientation");
-  const int N = orient == HORIZONTAL ? Lx_ : Ly_, lim = orient == HORIZONTAL ? Ly_ : Lx_;
-  PG_REQUIRE(slice >= 0 && slice < lim, 1, "slice outside the lattice");
-  if (mode == 0) PG_REQUIRE(n_uniform >= N - 1 && uniforms, 1, "one uniform deviate per bond of the slice is needed");
-  else PG_REQUIRE(phys_dim >= 1 && phys_dim <= dp_ && phys_dim * phys_dim <= SW_MAXC && words, 1, "full-space slice: 1 <= phys_dim, phys_dim^2 <= 16, two engine words per bond");
-  const int sites = Ly_ * Lx_;
-  const int nc = mode == 0 ? 1 : phys_dim * phys_dim;
-  const int nwords = 2 * (N - 1);
-  // persistent-for-the-call buffers (outside the ArenaScope'd operations they bracket)
-  Acc *damp = (Acc *)arena_.alloc(sizeof(Acc) * nw_);
-  double *duni = mode == 0 ? (double *)arena_.alloc(sizeof(double) * (size_t)nw_ * n_uniform) : nullptr;
-  unsigned *dwords = mode == 1 ? (unsigned *)arena_.alloc(sizeof(unsigned) * (size_t)nw_ * nwords) : nullptr;
-  int *dptr = (int *)arena_.alloc(sizeof(int) * (2 * (size_t)nw_ + 1));
-  int *dacc = dptr + nw_, *dover = dptr + 2 * nw_;
-  int *dcand = (int *)arena_.alloc(sizeof(int) * (2 * (size_t)nc + 2) * (size_t)nw_);
-  int *dsame = dcand + 2 * (size_t)nc * nw_, *dnow = dsame + nw_;
-  int *dslice = (int *)arena_.alloc(sizeof(int) * (size_t)nw_ * N);
-  int *dtab = (mode == 0 && pair_table) ? (int *)arena_.alloc(sizeof(int) * 2 * (size_t)dp_ * dp_) : nullptr;
-  BTenDev half;       // the kept half step of the bond in flight (owned here until grow_bten_step_reuse consumes it)
-  half.t.p = nullptr;
-  auto release = [&]() {
-    if (half.t.p) { arena_.free(half.t.p); half.t.p = nullptr; }
-    arena_.free(damp); arena_.free(dptr); arena_.free(dcand); arena_.free(dslice);
-    if (duni) arena_.free(duni);
-    if (dwords) arena_.free(dwords);
-    if (dtab) arena_.free(dtab);
-  };
-  try {
-    PG_CHECK_HIP(hipMemcpyAsync(damp, amp_inout, sizeof(Acc) * nw_, hipMemcpyHostToDevice, stream_));
-    if (duni) PG_CHECK_HIP(hipMemcpyAsync(duni, uniforms, sizeof(double) * (size_t)nw_ * n_uniform, hipMemcpyHostToDevice, stream_));
-    if (dwords) PG_CHECK_HIP(hipMemcpyAsync(dwords, words, sizeof(unsigned) * (size_t)nw_ * nwords, hipMemcpyHostToDevice, stream_));
-    if (dtab) {
-      for (int e = 0; e < 2 * dp_ * dp_; ++e) PG_REQUIRE(pair_table[e] >= 0 && pair_table[e] < dp_, 4, "pair table: state out of range");
-      PG_CHECK_HIP(hipMemcpyAsync(dtab, pair_table, sizeof(int) * 2 * (size_t)dp_ * dp_, hipMemcpyHostToDevice, stream_));
-    }
-    PG_CHECK_HIP(hipMemsetAsync(dptr, 0, sizeof(int) * (2 * (size_t)nw_ + 1), stream_));
-    const int lo = orient == HORIZONTAL ? LEFT : UP, hi = orient == HORIZONTAL ? RIGHT : DOWN;
-    init_bten(lo, slice);
-    grow_full_bten(hi, slice, 2, 1);
-    const int gb = (nw_ + 255) / 256;
-    if (mode == 1) {
-      hipLaunchKernelGGL(sweep_all_cand_kernel, dim3((nw_ * nc + 255) / 256), dim3(256), 0, stream_, dcand, phys_dim, nw_);
+  const SliceGeom g(orient, slice, Lx_, Ly_);
+  PG_REQUIRE(n_uniform >= g.N - 1 && uniforms, 1, "one uniform deviate per bond of the slice is needed");
+  const size_t ntab = pair_table ? 2 * (size_t)dp_ * dp_ : 0;
+  require_states(pair_table, ntab, dp_, "pair table: state out of range");
+  const int sites = Ly_ * Lx_, gb = (nw_ + 255) / 256;
+  ArenaBuf<Acc> damp(arena_, nw_);
+  ArenaBuf<double> duni(arena_, (size_t)nw_ * n_uniform);
+  ArenaBuf<int> dcnt(arena_, 2 * (size_t)nw_ + 1);
+  int *dacc = dcnt + nw_, *dover = dcnt + 2 * nw_;
+  ArenaBuf<int> dcand(arena_, 4 * (size_t)nw_);                             // candidate pair [n][2], same [n], accepted on this bond [n]
+  int *dsame = dcand + 2 * (size_t)nw_, *dnow = dsame + nw_;
+  ArenaBuf<int> dtab(arena_, ntab);
+  ArenaBuf<T> half(arena_, 0);                                               // the kept half step of the bond in flight
+  PG_CHECK_HIP(hipMemcpyAsync(damp, amp_inout, sizeof(Acc) * nw_, hipMemcpyHostToDevice, stream_));
+  PG_CHECK_HIP(hipMemcpyAsync(duni, uniforms, sizeof(double) * (size_t)nw_ * n_uniform, hipMemcpyHostToDevice, stream_));
+  if (dtab) PG_CHECK_HIP(hipMemcpyAsync(dtab, pair_table, sizeof(int) * ntab, hipMemcpyHostToDevice, stream_));
+  sweep_slice_frame(g, 2, damp, dcnt, amp_inout, consumed_out, accepted_out, slice_states_out, [&] {
+    for (int j = 0; j + 1 < g.N; ++j) {
+      const int r1 = g.row(j), c1 = g.col(j), s1 = g.site(j), s2 = g.site(j + 1);
+      hipLaunchKernelGGL(sweep_swap_cand_kernel, dim3(gb), dim3(256), 0, stream_, (const int *)cfg_, sites, s1, s2, dcand, dsame, nw_,
+                         (const int *)dtab, dp_);
       PG_CHECK_HIP(hipGetLastError());
-    }
-    for (int j = 0; j + 1 < N; ++j) {
-      const int r1 = orient == HORIZONTAL ? slice : j, c1 = orient == HORIZONTAL ? j : slice;
-      const int r2 = orient == HORIZONTAL ? slice : j + 1, c2 = orient == HORIZONTAL ? j + 1 : slice;
-      const int s1 = r1 * Lx_ + c1, s2 = r2 * Lx_ + c2;
+      // the left half of the replacement trace IS the next environment tensor of the walkers that accept the exchange (the same
+      // kernel on the same operands): it is kept, and the growth step behind the Metropolis test runs for the others only
+      const bool reuse = j + 2 < g.N;
+      BTenDev t2;
       double *lsum = nullptr;
-      if (mode == 0) {
-        hipLaunchKernelGGL(sweep_swap_cand_kernel, dim3(gb), dim3(256), 0, stream_, (const int *)cfg_, sites, s1, s2, dcand, dsame, nw_,
-                           (const int *)dtab, dp_);
-        PG_CHECK_HIP(hipGetLastError());
-        // the left half of the replacement trace IS the next environment tensor of the walkers that accept the exchange (the same
-        // kernel on the same operands): it is kept, and the growth step behind the Metropolis test runs for the others only
-        constexpr bool no_reuse = false;
-        const bool reuse = j + 2 < N && !no_reuse;
-        Acc *res = nn_trace_device(r1, c1, orient, 1, dcand, &lsum, dsame, reuse ? &half : nullptr);
-        hipLaunchKernelGGL(sweep_metropolis_exchange_kernel<Acc>, dim3(gb), dim3(256), 0, stream_, cfg_, sites, s1, s2, (const Acc *)res,
-                           (const double *)lsum, damp, (const double *)duni, n_uniform, dptr, dacc, dover, dnow, nw_, (const int *)dcand,
-                           (const int *)dsame);
-        PG_CHECK_HIP(hipGetLastError());
-        arena_.free(res);
-        arena_.free(lsum);
-        erase_envs_after_update(r1, c1);
-        erase_envs_after_update(r2, c2);
-        if (reuse) {
-          clear_bten(hi, bten_size(hi) - 1);
-          grow_bten_step_reuse(lo, half, dnow);
-        } else if (j + 2 < N) {
-          shift_bten_window(hi);
-        }
-      } else {
-        Acc *res = nn_trace_device(r1, c1, orient, nc, dcand, &lsum);
-        hipLaunchKernelGGL(sweep_suwa_todo_kernel<Acc>, dim3(gb), dim3(256), 0, stream_, cfg_, sites, s1, s2, phys_dim, (const Acc *)res,
-                           (const double *)lsum, damp, (const unsigned *)dwords, nwords, j, dacc, dnow, nw_);
-        PG_CHECK_HIP(hipGetLastError());
-        arena_.free(res);
-        arena_.free(lsum);
-        erase_envs_after_update(r1, c1);
-        erase_envs_after_update(r2, c2);
-        if (j + 2 < N) shift_bten_window(hi);
+      Acc *res = nn_trace_device(r1, c1, orient, 1, dcand, &lsum, dsame, reuse ? &t2 : nullptr);
+      if (reuse) half.reset(t2.t.p);
+      hipLaunchKernelGGL(sweep_metropolis_exchange_kernel<Acc>, dim3(gb), dim3(256), 0, stream_, cfg_, sites, s1, s2, (const Acc *)res,
+                         (const double *)lsum, damp, (const double *)duni, n_uniform, dcnt, dacc, dover, dnow, nw_, (const int *)dcand,
+                         (const int *)dsame);
+      PG_CHECK_HIP(hipGetLastError());
+      arena_.free(res);
+      arena_.free(lsum);
+      erase_envs_after_update(r1, c1);
+      erase_envs_after_update(g.row(j + 1), g.col(j + 1));
+      if (reuse) {
+        clear_bten(g.hi, bten_size(g.hi) - 1);
+        grow_bten_step_reuse(g.lo, half, (long)t2.t.n, dnow);
       }
     }
-    hipLaunchKernelGGL(sweep_gather_slice_kernel, dim3((nw_ * N + 255) / 256), dim3(256), 0, stream_, (const int *)cfg_, sites,
-                       orient == HORIZONTAL ? slice * Lx_ : slice, orient == HORIZONTAL ? 1 : Lx_, N, dslice, nw_);
+  });
+}
+
+// One slice of the sweep of the full-space updater on the device: per bond ONE replacement trace over all phys_dim^2 states of the
+// pair, then the Suwa-Todo decision and the move (sweep_suwa_todo_kernel).  words: [n][2 (N - 1)], two engine words per bond.
+template <typename T>
+void Engine<T>::sweep_slice_fullspace(int orient, int slice, int phys_dim, const uint32_t *words, double *amp_inout,
+                                      int32_t *accepted_out, int32_t *slice_states_out) {
+  require_ready();
+  const SliceGeom g(orient, slice, Lx_, Ly_);
+  PG_REQUIRE(phys_dim >= 1 && phys_dim <= dp_ && phys_dim * phys_dim <= SW_MAXC && words, 1, "full-space slice: 1 <= phys_dim, phys_dim^2 <= 16, two engine words per bond");
+  const int sites = Ly_ * Lx_, gb = (nw_ + 255) / 256, nc = phys_dim * phys_dim, nwords = 2 * (g.N - 1);
+  ArenaBuf<Acc> damp(arena_, nw_);
+  ArenaBuf<unsigned> dwords(arena_, (size_t)nw_ * nwords);
+  ArenaBuf<int> dcnt(arena_, 2 * (size_t)nw_ + 1);                          // (consumed: unused, the count is fixed), accepted [n]
+  ArenaBuf<int> dcand(arena_, (2 * (size_t)nc + 1) * (size_t)nw_);          // candidate pairs [n][nc][2], changed on this bond [n]
+  int *dnow = dcand + 2 * (size_t)nc * nw_;
+  PG_CHECK_HIP(hipMemcpyAsync(damp, amp_inout, sizeof(Acc) * nw_, hipMemcpyHostToDevice, stream_));
+  PG_CHECK_HIP(hipMemcpyAsync(dwords, words, sizeof(unsigned) * (size_t)nw_ * nwords, hipMemcpyHostToDevice, stream_));
+  sweep_slice_frame(g, 2, damp, dcnt, amp_inout, nullptr, accepted_out, slice_states_out, [&] {
+    hipLaunchKernelGGL(sweep_all_cand_kernel, dim3((nw_ * nc + 255) / 256), dim3(256), 0, stream_, dcand, phys_dim, nw_);
     PG_CHECK_HIP(hipGetLastError());
-    std::vector<int> hs((size_t)nw_ * N), hp(2 * (size_t)nw_ + 1);
-    PG_CHECK_HIP(hipMemcpyAsync(amp_inout, damp, sizeof(Acc) * nw_, hipMemcpyDeviceToHost, stream_));
-    PG_CHECK_HIP(hipMemcpyAsync(hs.data(), dslice, sizeof(int) * hs.size(), hipMemcpyDeviceToHost, stream_));
-    PG_CHECK_HIP(hipMemcpyAsync(hp.data(), dptr, sizeof(int) * hp.size(), hipMemcpyDeviceToHost, stream_));
-    PG_CHECK_HIP(hipStreamSynchronize(stream_));
-    PG_REQUIRE(hp[2 * (size_t)nw_] == 0, 5, "device-side slice sweep: uniform deviates exhausted");
-    for (int w = 0; w < nw_; ++w) {
-      if (consumed_out) consumed_out[w] = hp[w];
-      accepted_out[w] = hp[nw_ + w];
-      for (int j = 0; j < N; ++j) {
-        const int v = hs[(size_t)w * N + j];
-        const int r = orient == HORIZONTAL ? slice : j, c = orient == HORIZONTAL ? j : slice;
-        hcfg_[(size_t)w * sites + r * Lx_ + c] = v;          // host mirror of the configuration table
-        if (slice_states_out) slice_states_out[(size_t)w * N + j] = v;
-      }
+    for (int j = 0; j + 1 < g.N; ++j) {
+      double *lsum = nullptr;
+      Acc *res = nn_trace_device(g.row(j), g.col(j), orient, nc, dcand, &lsum);
+      hipLaunchKernelGGL(sweep_suwa_todo_kernel<Acc>, dim3(gb), dim3(256), 0, stream_, cfg_, sites, g.site(j), g.site(j + 1), phys_dim,
+                         (const Acc *)res, (const double *)lsum, damp, (const unsigned *)dwords, nwords, j, dcnt + nw_, dnow, nw_);
+      PG_CHECK_HIP(hipGetLastError());
+      arena_.free(res);
+      arena_.free(lsum);
+      erase_envs_after_update(g.row(j), g.col(j));
+      erase_envs_after_update(g.row(j + 1), g.col(j + 1));
+      if (j + 2 < g.N) shift_bten_window(g.hi);
     }
-  } catch (...) {
-    // the device table may hold moves the host has not seen: bring the mirror back in step before reporting the failure
-    (void)hipMemcpy(hcfg_.data(), cfg_, sizeof(int) * (size_t)nw_ * sites, hipMemcpyDeviceToHost);
-    release();
-    throw;
-  }
-  release();
+  });
 }
 
 }  // namespace pepsgpu

@@ -935,51 +935,84 @@ size_t SuwaTodoStateUpdate(size_t init_state, std::vector<double> weights, RandG
   return final_state;
 }
 
+// an updater opts into the device-side slice sweep with `static constexpr bool kDeviceSliceSweep = true` + SweepSliceOnDevice
+template <typename U, typename = void> struct HasDeviceSliceSweep : std::false_type {};
+template <typename U> struct HasDeviceSliceSweep<U, std::void_t<decltype(U::kDeviceSliceSweep)>> : std::bool_constant<U::kDeviceSliceSweep> {};
+
+// PEPSHOST_NO_DEVICE_SWEEP=1 keeps the updaters and the energy solvers on their per-site / per-bond hook paths (A/B and the
+// identical-chain tests of the two paths); read once per process
+inline bool DeviceSlicesEnabled() {
+  static const bool enabled = std::getenv("PEPSHOST_NO_DEVICE_SWEEP") == nullptr;
+  return enabled;
+}
+// Does this updater run a whole row / column in ONE device call for this component?  (An updater whose move the device implements:
+// traces, acceptance tests and moves on the device, the walker's random stream consumed in the same order -> the same chain.
+// Every other combination goes through its hook, bond by bond.)
+template <typename MCUpdater, typename TenElemT>
+bool TakesDeviceSlicePath(const TPSWaveFunctionComponentT<TenElemT> &comp) {
+  if constexpr (HasDeviceSliceSweep<MCUpdater>::value) return DeviceSlicesEnabled() && (!comp.fermion || MCUpdater::kDeviceSliceSweepFermions);
+  else return false;
+}
+
+// one row (HORIZONTAL) or column (VERTICAL) of the lattice as a sweep walks it: N sites at(0) .. at(N - 1), the BTen that grows (lo)
+// and the one that shrinks (hi)
+struct SliceSites {
+  BondOrientation dir;
+  size_t num, N;
+  template <typename Contractor>
+  SliceSites(const Contractor &c, BondOrientation dir_, size_t num_) : dir(dir_), num(num_), N(dir_ == HORIZONTAL ? c.cols() : c.rows()) {}
+  SiteIdx at(size_t j) const { return dir == HORIZONTAL ? SiteIdx{num, j} : SiteIdx{j, num}; }
+  BTenPOSITION lo() const { return dir == HORIZONTAL ? LEFT : UP; }
+  BTenPOSITION hi() const { return dir == HORIZONTAL ? RIGHT : DOWN; }
+};
+
 // MonteCarloSweepUpdaterBase (monte_carlo_sweep_updater_base.h:18-47): one std::mt19937 per walker
 class MonteCarloSweepUpdaterBase {
  public:
-  explicit MonteCarloSweepUpdaterBase(const std::vector<uint64_t> &seeds) : u_double_(0.0, 1.0) {
+  explicit MonteCarloSweepUpdaterBase(const std::vector<uint64_t> &seeds) {
     for (auto s : seeds) engines_.emplace_back((std::mt19937::result_type)s);
   }
  protected:
   std::vector<std::mt19937> engines_;
-  std::uniform_real_distribution<double> u_double_;
-  // Deviates drawn AHEAD of their use (device-side slice sweeps hand the next few of every walker's stream to the kernel, which
-  // consumes a prefix): a walker's deviates are always taken from the front of its queue first, so the sequence it consumes is
-  // the sequence u_double_(engines_[w]) yields -- whichever path (device slice, per-bond host test) asks for the next one.
-  std::vector<std::vector<double>> ahead_;     // [walker] drawn, not yet consumed (front = ahead_head_[w])
-  std::vector<size_t> ahead_head_;
-  double NextUniform(size_t w) {
-    if (w < ahead_.size() && ahead_head_[w] < ahead_[w].size()) return ahead_[w][ahead_head_[w]++];
-    return u_double_(engines_[w]);
-  }
-  // the next `cnt` deviates of walker w without consuming them
-  const double *PeekUniforms(size_t w, size_t cnt) {
-    if (ahead_.size() < engines_.size()) { ahead_.resize(engines_.size()); ahead_head_.resize(engines_.size(), 0); }
-    auto &q = ahead_[w];
-    if (ahead_head_[w] > 0 && ahead_head_[w] == q.size()) { q.clear(); ahead_head_[w] = 0; }
-    else if (ahead_head_[w] > 64) { q.erase(q.begin(), q.begin() + (long)ahead_head_[w]); ahead_head_[w] = 0; }
-    while (q.size() - ahead_head_[w] < cnt) q.push_back(u_double_(engines_[w]));
-    return q.data() + ahead_head_[w];
-  }
-  void ConsumeUniforms(size_t w, size_t cnt) { ahead_head_[w] += cnt; }
-  // Raw engine words drawn ahead (the three-site slice hands the next words of every walker to the device, which consumes a prefix):
-  // the same discipline as the deviates above.  An updater draws either deviates or raw words, never both.
-  std::vector<std::vector<uint32_t>> words_;   // [walker] drawn, not yet consumed (front = words_head_[w])
-  std::vector<size_t> words_head_;
-  uint32_t NextWord(size_t w) {
-    if (w < words_.size() && words_head_[w] < words_[w].size()) return words_[w][words_head_[w]++];
-    return (uint32_t)engines_[w]();
-  }
-  const uint32_t *PeekWords(size_t w, size_t cnt) {
-    if (words_.size() < engines_.size()) { words_.resize(engines_.size()); words_head_.resize(engines_.size(), 0); }
-    auto &q = words_[w];
-    if (words_head_[w] > 0 && words_head_[w] == q.size()) { q.clear(); words_head_[w] = 0; }
-    else if (words_head_[w] > 64) { q.erase(q.begin(), q.begin() + (long)words_head_[w]); words_head_[w] = 0; }
-    while (q.size() - words_head_[w] < cnt) q.push_back((uint32_t)engines_[w]());
-    return q.data() + words_head_[w];
-  }
-  void ConsumeWords(size_t w, size_t cnt) { words_head_[w] += cnt; }
+  // Values drawn AHEAD of their use (a device-side slice sweep hands the next few of every walker's stream to the kernel, which
+  // consumes a prefix): a walker's values are always taken from the front of its queue first, so the sequence it consumes is the
+  // sequence draw(engines_[w]) yields -- whichever path (device slice, host hook) asks for the next one.
+  template <typename V, typename Draw>         // Draw: V operator()(std::mt19937 &), one value off the engine
+  class LookAhead {
+   public:
+    V Next(std::vector<std::mt19937> &engines, size_t w) {
+      if (w < q_.size() && head_[w] < q_[w].size()) return q_[w][head_[w]++];
+      return draw_(engines[w]);
+    }
+    // the next `cnt` values of every walker, [walker][cnt], without consuming them
+    std::vector<V> PeekAll(std::vector<std::mt19937> &engines, size_t cnt) {
+      if (q_.size() < engines.size()) { q_.resize(engines.size()); head_.resize(engines.size(), 0); }
+      std::vector<V> out(engines.size() * cnt);
+      for (size_t w = 0; w < engines.size(); ++w) {
+        auto &q = q_[w];
+        if (head_[w] > 0 && head_[w] == q.size()) { q.clear(); head_[w] = 0; }
+        else if (head_[w] > 64) { q.erase(q.begin(), q.begin() + (long)head_[w]); head_[w] = 0; }
+        while (q.size() - head_[w] < cnt) q.push_back(draw_(engines[w]));
+        std::copy(q.begin() + (long)head_[w], q.begin() + (long)(head_[w] + cnt), out.begin() + (long)(w * cnt));
+      }
+      return out;
+    }
+    void Consume(size_t w, size_t cnt) { head_[w] += cnt; }
+   private:
+    std::vector<std::vector<V>> q_;            // [walker] drawn, not yet consumed (front = head_[w])
+    std::vector<size_t> head_;
+    Draw draw_;
+  };
+  struct DrawUniform {
+    std::uniform_real_distribution<double> dist{0.0, 1.0};
+    double operator()(std::mt19937 &e) { return dist(e); }
+  };
+  struct DrawWord { uint32_t operator()(std::mt19937 &e) { return (uint32_t)e(); } };
+  // An updater draws either deviates or raw engine words, never both.
+  LookAhead<double, DrawUniform> uniforms_;
+  LookAhead<uint32_t, DrawWord> words_;
+  double NextUniform(size_t w) { return uniforms_.Next(engines_, w); }
+  uint32_t NextWord(size_t w) { return words_.Next(engines_, w); }
   // walker w's std::mt19937 with the queued words served first (a URBG with the engine's range: a distribution draws from it exactly
   // the words it would draw from the engine)
   struct QueuedEngine {
@@ -991,6 +1024,59 @@ class MonteCarloSweepUpdaterBase {
     result_type operator()() { return base->NextWord(w); }
   };
   QueuedEngine Engine(size_t w) { return QueuedEngine{this, w}; }
+
+  // The schedule of a sweep (square_nn_updater.h:28-82, square_3site_updater.h:28-91): every row under the row-major mode order
+  // (fermions: the W sites of a row window are consecutive modes of it), then every column under the column-major one.  A slice goes
+  // to self->SweepSliceOnDevice when the updater takes the device path, else to hook_slice(sites, acc); both add a walker's accepted
+  // moves to acc.  accept_rates = acc / the number of windows of W sites on the lattice.
+  template <typename MCUpdater, typename TenElemT, typename HookSlice>
+  static void SweepRowsThenColumns(MCUpdater *self, const SplitIndexTPST<TenElemT> &sitps, TPSWaveFunctionComponentT<TenElemT> &comp, size_t W,
+                                   std::vector<double> &accept_rates, HookSlice &&hook_slice) {
+    auto &c = comp.contractor;
+    const size_t rows = c.rows(), cols = c.cols(), n = comp.config.walkers();
+    std::vector<size_t> acc(n, 0);
+    const bool dev_slice = TakesDeviceSlicePath<MCUpdater>(comp);
+    auto slice = [&](BondOrientation dir, size_t num) {
+      if (!dev_slice) hook_slice(SliceSites(c, dir, num), acc);
+      else if constexpr (HasDeviceSliceSweep<MCUpdater>::value) self->SweepSliceOnDevice(dir, num, sitps, comp, acc);
+    };
+    comp.SetOrder(ROW_MAJOR);
+    c.GenerateBMPSApproach(UP);
+    for (size_t row = 0; row < rows; row++) {
+      slice(HORIZONTAL, row);
+      if (row + 1 < rows) c.ShiftBMPSWindow(DOWN);
+    }
+    c.DeleteInnerBMPS(LEFT);
+    c.DeleteInnerBMPS(RIGHT);
+    comp.SetOrder(COL_MAJOR);
+    c.GenerateBMPSApproach(LEFT);
+    for (size_t col = 0; col < cols; col++) {
+      slice(VERTICAL, col);
+      if (col + 1 < cols) c.ShiftBMPSWindow(RIGHT);
+    }
+    c.DeleteInnerBMPS(UP);
+    const double total = double(cols * (rows - (W - 1)) + rows * (cols - (W - 1)));
+    accept_rates.assign(n, 0.0);
+    for (size_t w = 0; w < n; ++w) accept_rates[w] = double(acc[w]) / total;
+  }
+  // what a device slice returned into the component: the states of the slice [walker][N] (fermions: extended states, taken % d) and
+  // the accepted moves of every walker
+  template <typename TenElemT>
+  static void StoreSlice(TPSWaveFunctionComponentT<TenElemT> &comp, BondOrientation dir, size_t slice, const std::vector<int32_t> &states,
+                         const std::vector<int32_t> &accepted, std::vector<size_t> &acc) {
+    const SliceSites s(comp.contractor, dir, slice);
+    const int32_t d = comp.fermion ? (int32_t)comp.fermion->d() : 0;
+    for (size_t w = 0; w < acc.size(); ++w) {
+      acc[w] += (size_t)accepted[w];
+      for (size_t j = 0; j < s.N; ++j) comp.config(w, s.at(j)) = d ? states[w * s.N + j] % d : states[w * s.N + j];
+    }
+  }
+  // the factor from a contraction of the decorated network of the current mode order to the stored (graded, row-major) amplitude
+  template <typename TenElemT>
+  static double GradedSign(const TPSWaveFunctionComponentT<TenElemT> &comp, size_t w) {
+    if (!comp.fermion) return 1.0;
+    return double(comp.fermion->Sigma(comp.config, w) * (comp.order == COL_MAJOR ? comp.fermion->Kappa(comp.config, w) : 1));
+  }
 };
 
 // a model opts into the device-side energy slice with `static constexpr bool kExchangeBondEnergy = true` + the scalar hook
@@ -1002,10 +1088,6 @@ template <typename U> struct HasExchangeBondEnergy<U, std::void_t<decltype(U::kE
 template <typename U, typename = void> struct HasExchangeBondPsiPerBond : std::false_type {};
 template <typename U> struct HasExchangeBondPsiPerBond<U, std::void_t<decltype(U::kExchangeBondPsiPerBond)>> : std::bool_constant<U::kExchangeBondPsiPerBond> {};
 
-// an updater opts into the device-side slice sweep with `static constexpr bool kDeviceSliceSweep = true` + SweepSliceOnDevice
-template <typename U, typename = void> struct HasDeviceSliceSweep : std::false_type {};
-template <typename U> struct HasDeviceSliceSweep<U, std::void_t<decltype(U::kDeviceSliceSweep)>> : std::bool_constant<U::kDeviceSliceSweep> {};
-
 // square_nn_updater.h:25-83: sweep schedule, CRTP hook TwoSiteNNUpdateLocalImpl(site1, site2, dir, sitps, comp) -> accepted[w]
 template <typename MCUpdater>
 class MCUpdateSquareNNUpdateBaseOBC : public MonteCarloSweepUpdaterBase {
@@ -1014,56 +1096,18 @@ class MCUpdateSquareNNUpdateBaseOBC : public MonteCarloSweepUpdaterBase {
   template <typename TenElemT>
   void operator()(const SplitIndexTPST<TenElemT> &sitps, TPSWaveFunctionComponentT<TenElemT> &comp, std::vector<double> &accept_rates) {
     auto &c = comp.contractor;
-    const size_t rows = c.rows(), cols = c.cols(), n = comp.config.walkers();
-    std::vector<size_t> acc(n, 0);
-    auto add = [&](const std::vector<uint8_t> &a) { for (size_t w = 0; w < n; ++w) acc[w] += a[w]; };
-    // An updater whose bond move the device implements runs a whole row / column of bonds in ONE call (traces, acceptance tests and
-    // moves on the device, the walker's random stream consumed in the same order -> the same chain): the exchange updater (round 4:
-    // real bosonic states; round 6: complex states and -- through the tabulated move of pepsgpu_sweep_slice_exchange_tab --
-    // fermionic states) and the full-space updater (round 6: pepsgpu_sweep_slice_fullspace, bosonic states, real and complex).
-    // Every other combination goes through its TwoSiteNNUpdateLocalImpl hook bond by bond.
-    // PEPSHOST_NO_DEVICE_SWEEP=1 forces the hook path (A/B and the identical-chain tests of the two paths).
-    static const bool no_dev = std::getenv("PEPSHOST_NO_DEVICE_SWEEP") != nullptr;
-    bool dev_slice = false;
-    if constexpr (HasDeviceSliceSweep<MCUpdater>::value) dev_slice = !no_dev && (!comp.fermion || MCUpdater::kDeviceSliceSweepFermions);
-    comp.SetOrder(ROW_MAJOR);                // fermions: horizontal bonds are local in the row-major mode order
-    c.GenerateBMPSApproach(UP);
-    for (size_t row = 0; row < rows; row++) {
-      if (dev_slice) {
-        if constexpr (HasDeviceSliceSweep<MCUpdater>::value)
-          static_cast<MCUpdater *>(this)->SweepSliceOnDevice(HORIZONTAL, row, sitps, comp, acc);
-      } else {
-        c.InitBTen(LEFT, row);
-        c.GrowFullBTen(RIGHT, row, 2, true);
-        for (size_t col = 0; col + 1 < cols; col++) {
-          add(static_cast<MCUpdater *>(this)->TwoSiteNNUpdateLocalImpl({row, col}, {row, col + 1}, HORIZONTAL, sitps, comp));
-          if (col + 2 < cols) c.ShiftBTenWindow(RIGHT);
-        }
+    auto *self = static_cast<MCUpdater *>(this);
+    // the device path: the exchange updater (pepsgpu_sweep_slice_exchange, real and complex states; fermionic ones through the
+    // tabulated move of pepsgpu_sweep_slice_exchange_tab) and the full-space updater (pepsgpu_sweep_slice_fullspace, bosonic states)
+    SweepRowsThenColumns(self, sitps, comp, 2, accept_rates, [&](const SliceSites &s, std::vector<size_t> &acc) {
+      c.InitBTen(s.lo(), s.num);
+      c.GrowFullBTen(s.hi(), s.num, 2, true);
+      for (size_t j = 0; j + 1 < s.N; ++j) {
+        const std::vector<uint8_t> a = self->TwoSiteNNUpdateLocalImpl(s.at(j), s.at(j + 1), s.dir, sitps, comp);
+        for (size_t w = 0; w < acc.size(); ++w) acc[w] += a[w];
+        if (j + 2 < s.N) c.ShiftBTenWindow(s.hi());
       }
-      if (row + 1 < rows) c.ShiftBMPSWindow(DOWN);
-    }
-    c.DeleteInnerBMPS(LEFT);
-    c.DeleteInnerBMPS(RIGHT);
-    comp.SetOrder(COL_MAJOR);                // fermions: vertical bonds are local in the column-major mode order
-    c.GenerateBMPSApproach(LEFT);
-    for (size_t col = 0; col < cols; col++) {
-      if (dev_slice) {
-        if constexpr (HasDeviceSliceSweep<MCUpdater>::value)
-          static_cast<MCUpdater *>(this)->SweepSliceOnDevice(VERTICAL, col, sitps, comp, acc);
-      } else {
-        c.InitBTen(UP, col);
-        c.GrowFullBTen(DOWN, col, 2, true);
-        for (size_t row = 0; row + 1 < rows; row++) {
-          add(static_cast<MCUpdater *>(this)->TwoSiteNNUpdateLocalImpl({row, col}, {row + 1, col}, VERTICAL, sitps, comp));
-          if (row + 2 < rows) c.ShiftBTenWindow(DOWN);
-        }
-      }
-      if (col + 1 < cols) c.ShiftBMPSWindow(RIGHT);
-    }
-    c.DeleteInnerBMPS(UP);
-    const double bond_num = double(cols * (rows - 1) + rows * (cols - 1));
-    accept_rates.assign(n, 0.0);
-    for (size_t w = 0; w < n; ++w) accept_rates[w] = double(acc[w]) / bond_num;
+    });
   }
 };
 
@@ -1080,37 +1124,23 @@ class MCUpdateSquareNNExchangeOBC : public MCUpdateSquareNNUpdateBaseOBC<MCUpdat
                           std::vector<size_t> &acc) {
     auto &c = comp.contractor;
     const size_t n = comp.config.walkers(), N = dir == HORIZONTAL ? c.cols() : c.rows(), nu = N - 1;
-    std::vector<double> uni(n * nu);
-    for (size_t w = 0; w < n; ++w) {
-      const double *q = PeekUniforms(w, nu);
-      std::copy(q, q + nu, uni.begin() + (long)(w * nu));
-    }
+    const std::vector<double> uni = uniforms_.PeekAll(engines_, nu);
     std::vector<int32_t> consumed(n), accepted(n), states(n * N);
-    if (!comp.fermion) {
-      check_rc(pepsgpu_sweep_slice_exchange(c.ctx(), dir, (int)slice, (int)nu, uni.data(), dptr(comp.amplitude.data()), consumed.data(),
-                                            accepted.data(), states.data()), c.ctx());
-      for (size_t w = 0; w < n; ++w) {
-        ConsumeUniforms(w, (size_t)consumed[w]);
-        acc[w] += (size_t)accepted[w];
-        for (size_t j = 0; j < N; ++j) comp.config(w, dir == HORIZONTAL ? SiteIdx{slice, j} : SiteIdx{j, slice}) = states[w * N + j];
-      }
-      return;
-    }
+    std::vector<TenElemT> amp = comp.amplitude;
     // Fermions: the device holds extended states (state + d * variant) of the current mode order; the exchange of two sites adjacent
     // in that order is DeviceStatesNN tabulated over the pair of extended states.  The slice returns decorated amplitudes (the
     // Metropolis test sees moduli only); a walker that moved gets its signs back from its new configuration, as UpdateLocal does.
-    const FermionDecoration &fd = *comp.fermion;
-    const int32_t d = (int32_t)fd.d();
-    const std::vector<int32_t> tab = comp.ExchangeTable();
-    std::vector<TenElemT> amp = comp.amplitude;
-    check_rc(pepsgpu_sweep_slice_exchange_tab(c.ctx(), dir, (int)slice, (int)nu, uni.data(), tab.data(), dptr(amp.data()), consumed.data(),
-                                              accepted.data(), states.data()), c.ctx());
+    if (!comp.fermion)
+      check_rc(pepsgpu_sweep_slice_exchange(c.ctx(), dir, (int)slice, (int)nu, uni.data(), dptr(amp.data()), consumed.data(), accepted.data(),
+                                            states.data()), c.ctx());
+    else
+      check_rc(pepsgpu_sweep_slice_exchange_tab(c.ctx(), dir, (int)slice, (int)nu, uni.data(), comp.ExchangeTable().data(), dptr(amp.data()),
+                                                consumed.data(), accepted.data(), states.data()), c.ctx());
+    StoreSlice(comp, dir, slice, states, accepted, acc);
     for (size_t w = 0; w < n; ++w) {
-      ConsumeUniforms(w, (size_t)consumed[w]);
-      acc[w] += (size_t)accepted[w];
-      for (size_t j = 0; j < N; ++j) comp.config(w, dir == HORIZONTAL ? SiteIdx{slice, j} : SiteIdx{j, slice}) = states[w * N + j] % d;
-      if (accepted[w] > 0)
-        comp.amplitude[w] = amp[w] * double(fd.Sigma(comp.config, w) * (comp.order == COL_MAJOR ? fd.Kappa(comp.config, w) : 1));
+      uniforms_.Consume(w, (size_t)consumed[w]);
+      if (!comp.fermion) comp.amplitude[w] = amp[w];
+      else if (accepted[w] > 0) comp.amplitude[w] = amp[w] * GradedSign(comp, w);
     }
   }
   template <typename TenElemT>
@@ -1160,10 +1190,7 @@ class MCUpdateSquareNNFullSpaceUpdateOBC : public MCUpdateSquareNNUpdateBaseOBC<
     std::vector<int32_t> accepted(n), states(n * N);
     check_rc(pepsgpu_sweep_slice_fullspace(c.ctx(), dir, (int)slice, (int)sitps.PhysicalDim(), words.data(), dptr(comp.amplitude.data()),
                                            accepted.data(), states.data()), c.ctx());
-    for (size_t w = 0; w < n; ++w) {
-      acc[w] += (size_t)accepted[w];
-      for (size_t j = 0; j < N; ++j) comp.config(w, dir == HORIZONTAL ? SiteIdx{slice, j} : SiteIdx{j, slice}) = states[w * N + j];
-    }
+    StoreSlice(comp, dir, slice, states, accepted, acc);
   }
   template <typename TenElemT>
   std::vector<uint8_t> TwoSiteNNUpdateLocalImpl(const SiteIdx &s1, const SiteIdx &s2, BondOrientation dir,
@@ -1200,61 +1227,23 @@ class MCUpdateSquareTNN3SiteUpdateBase : public MonteCarloSweepUpdaterBase {
   template <typename TenElemT>
   void operator()(const SplitIndexTPST<TenElemT> &sitps, TPSWaveFunctionComponentT<TenElemT> &comp, std::vector<double> &accept_rates) {
     auto &c = comp.contractor;
-    const size_t rows = c.rows(), cols = c.cols(), n = comp.config.walkers();
     // (the reference indexes {row, 2} and {2, col})
-    if (rows < 3 || cols < 3) throw std::invalid_argument("MCUpdateSquareTNN3SiteUpdateBase: the lattice needs at least 3 rows and 3 columns");
-    std::vector<size_t> acc(n, 0);
-    auto add = [&](const std::vector<uint8_t> &a) { for (size_t w = 0; w < n; ++w) acc[w] += a[w]; };
-    // a whole row / column in ONE call (pepsgpu_sweep_slice_tnn3) for an updater that opts in; PEPSHOST_NO_DEVICE_SWEEP=1 forces the
-    // per-triple hook path
-    static const bool no_dev = std::getenv("PEPSHOST_NO_DEVICE_SWEEP") != nullptr;
-    bool dev_slice = false;
-    if constexpr (HasDeviceSliceSweep<MCUpdater>::value) dev_slice = !no_dev && (!comp.fermion || MCUpdater::kDeviceSliceSweepFermions);
-    auto slice = [&](BondOrientation dir, size_t num) {
-      const size_t N = dir == HORIZONTAL ? cols : rows;
-      auto at = [&](size_t j) { return dir == HORIZONTAL ? SiteIdx{num, j} : SiteIdx{j, num}; };
-      if (dev_slice) {
-        if constexpr (HasDeviceSliceSweep<MCUpdater>::value)
-          static_cast<MCUpdater *>(this)->SweepSliceOnDevice(dir, num, sitps, comp, acc);
-        return;
+    if (c.rows() < 3 || c.cols() < 3) throw std::invalid_argument("MCUpdateSquareTNN3SiteUpdateBase: the lattice needs at least 3 rows and 3 columns");
+    auto *self = static_cast<MCUpdater *>(this);
+    SweepRowsThenColumns(self, sitps, comp, 3, accept_rates, [&](const SliceSites &s, std::vector<size_t> &acc) {
+      c.InitBTen(s.lo(), s.num);
+      c.GrowFullBTen(s.hi(), s.num, 3, true);
+      const std::vector<TenElemT> psi0 = c.ReplaceTNNSiteTrace(s.at(0), s.dir, 0, {});
+      for (size_t w = 0; w < acc.size(); ++w) comp.amplitude[w] = psi0[w] * GradedSign(comp, w);
+      for (size_t j = 0; j + 2 < s.N; ++j) {
+        const std::vector<uint8_t> a = self->TNN3SiteUpdateImpl(s.at(j), s.at(j + 1), s.at(j + 2), s.dir, sitps, comp);
+        for (size_t w = 0; w < acc.size(); ++w) acc[w] += a[w];
+        if (j + 3 < s.N) c.ShiftBTenWindow(s.hi());
       }
-      const BTenPOSITION lo = dir == HORIZONTAL ? LEFT : UP, hi = dir == HORIZONTAL ? RIGHT : DOWN;
-      c.InitBTen(lo, num);
-      c.GrowFullBTen(hi, num, 3, true);
-      const std::vector<TenElemT> psi0 = c.ReplaceTNNSiteTrace(at(0), dir, 0, {});
-      for (size_t w = 0; w < n; ++w) comp.amplitude[w] = psi0[w] * GradedSign(comp, w);
-      for (size_t j = 0; j + 2 < N; ++j) {
-        add(static_cast<MCUpdater *>(this)->TNN3SiteUpdateImpl(at(j), at(j + 1), at(j + 2), dir, sitps, comp));
-        if (j + 3 < N) c.ShiftBTenWindow(hi);
-      }
-    };
-    comp.SetOrder(ROW_MAJOR);                // fermions: a row triple is three consecutive modes of the row-major order
-    c.GenerateBMPSApproach(UP);
-    for (size_t row = 0; row < rows; row++) {
-      slice(HORIZONTAL, row);
-      if (row + 1 < rows) c.ShiftBMPSWindow(DOWN);
-    }
-    c.DeleteInnerBMPS(LEFT);
-    c.DeleteInnerBMPS(RIGHT);
-    comp.SetOrder(COL_MAJOR);                // ... and a column triple of the column-major order
-    c.GenerateBMPSApproach(LEFT);
-    for (size_t col = 0; col < cols; col++) {
-      slice(VERTICAL, col);
-      if (col + 1 < cols) c.ShiftBMPSWindow(RIGHT);
-    }
-    c.DeleteInnerBMPS(UP);
-    const double total = double(cols * (rows - 2) + rows * (cols - 2));
-    accept_rates.assign(n, 0.0);
-    for (size_t w = 0; w < n; ++w) accept_rates[w] = double(acc[w]) / total;
+    });
   }
 
  protected:
-  // the factor from a contraction of the decorated network of the current mode order to the stored (graded, row-major) amplitude
-  template <typename TenElemT>
-  static double GradedSign(const TPSWaveFunctionComponentT<TenElemT> &comp, size_t w) {
-    if (!comp.fermion) return 1.0;
-    return double(comp.fermion->Sigma(comp.config, w) * (comp.order == COL_MAJOR ? comp.fermion->Kappa(comp.config, w) : 1));
-  }
   // the triple table of the component (bosons: of its physical dimension; fermions: TNN3Table of the current mode order), cached
   // under everything it depends on: the states per site, the mode order and the parities of the decoration
   template <typename TenElemT>
@@ -1283,21 +1272,14 @@ class MCUpdateSquareTNN3SiteExchange : public MCUpdateSquareTNN3SiteUpdateBase<M
                           std::vector<size_t> &acc) {
     auto &c = comp.contractor;
     const size_t n = comp.config.walkers(), N = dir == HORIZONTAL ? c.cols() : c.rows(), nwd = 2 * (N - 2);
-    std::vector<uint32_t> words(n * nwd);
-    for (size_t w = 0; w < n; ++w) {
-      const uint32_t *q = PeekWords(w, nwd);
-      std::copy(q, q + nwd, words.begin() + (long)(w * nwd));
-    }
+    const std::vector<uint32_t> words = words_.PeekAll(engines_, nwd);
     std::vector<int32_t> consumed(n), accepted(n), states(n * N);
     std::vector<TenElemT> amp(n);
     check_rc(pepsgpu_sweep_slice_tnn3(c.ctx(), dir, (int)slice, comp.fermion ? TripleTable(comp).data() : nullptr, (int)nwd, words.data(),
                                       dptr(amp.data()), consumed.data(), accepted.data(), states.data()), c.ctx());
-    const int32_t d = comp.fermion ? (int32_t)comp.fermion->d() : 0;
+    StoreSlice(comp, dir, slice, states, accepted, acc);
     for (size_t w = 0; w < n; ++w) {
-      ConsumeWords(w, (size_t)consumed[w]);
-      acc[w] += (size_t)accepted[w];
-      for (size_t j = 0; j < N; ++j)
-        comp.config(w, dir == HORIZONTAL ? SiteIdx{slice, j} : SiteIdx{j, slice}) = comp.fermion ? states[w * N + j] % d : states[w * N + j];
+      words_.Consume(w, (size_t)consumed[w]);
       comp.amplitude[w] = amp[w] * GradedSign(comp, w);
     }
   }
@@ -1383,11 +1365,10 @@ class SquareNNNModelEnergySolver {
     // ReplaceNNSiteTrace round trip per bond; same operations in the same order on the device, same numbers.  Real and complex;
     // fermionic components for the models with kExchangeBondPsiPerBond (the exchange as ExchangeTable, psi per bond).
     // PEPSHOST_NO_DEVICE_SWEEP=1 keeps the per-bond hook path.
-    static const bool no_dev = std::getenv("PEPSHOST_NO_DEVICE_SWEEP") != nullptr;
     constexpr bool per_bond = HasExchangeBondPsiPerBond<ExplicitlyModel>::value;
     bool dev_slice = false;
     if constexpr (HasExchangeBondEnergy<ExplicitlyModel>::value)
-      dev_slice = !no_dev && (!comp.fermion || per_bond) && (!calchols || holes_on_device);
+      dev_slice = DeviceSlicesEnabled() && (!comp.fermion || per_bond) && (!calchols || holes_on_device);
     auto slice_energy = [&](BondOrientation dir, size_t slice, bool holes) {
       if constexpr (HasExchangeBondEnergy<ExplicitlyModel>::value) {
         const size_t N = dir == HORIZONTAL ? cols : rows;
@@ -2437,7 +2418,7 @@ class TransverseFieldIsingSquareOBC {
     if (calchols && !holes_on_device) out.holes.assign(n * rows * cols * slot, TenElemT(0.0));
     // a whole row from ONE device call (pepsgpu_onsite_slice with the flip table; holes kept in HBM) when the holes are not wanted on
     // the host; PEPSHOST_NO_DEVICE_SWEEP=1 keeps the per-site hook path
-    const bool dev_slice = !NoDeviceSlice() && (!calchols || holes_on_device);
+    const bool dev_slice = DeviceSlicesEnabled() && (!calchols || holes_on_device);
     c.GenerateBMPSApproach(UP);
     for (size_t row = 0; row < rows; row++) {
       if (dev_slice) {
@@ -2487,7 +2468,7 @@ class TransverseFieldIsingSquareOBC {
     auto &sz = out.make("spin_z", ly * lx);
     auto &en = out.make("energy", 1);
     std::vector<std::vector<TenElemT>> psi_list;
-    const bool dev_slice = !NoDeviceSlice();
+    const bool dev_slice = DeviceSlicesEnabled();
     c.GenerateBMPSApproach(UP);
     for (size_t row = 0; row < ly; ++row) {
       std::vector<TenElemT> row_ex;                     // (device slice: the flipped amplitudes of the whole row, [walker][col])
@@ -2548,10 +2529,6 @@ class TransverseFieldIsingSquareOBC {
             {"SzSz_row", "SzSz correlations along middle row (flat)", {lx / 2}, {"segment"}}};
   }
  private:
-  static bool NoDeviceSlice() {
-    static const bool no_dev = std::getenv("PEPSHOST_NO_DEVICE_SWEEP") != nullptr;
-    return no_dev;
-  }
   // the row pass of one row on the device: InitBTen, GrowFullBTen(RIGHT, row, 1, true), psi = Trace, per site (PunchHoleStore and)
   // ReplaceOneSiteTrace of the flipped spin + ShiftBTenWindow -- psi [walker], psi_ex [walker][col]
   template <typename TenElemT>

@@ -181,6 +181,22 @@ int pepsgpu_nn_exchange_slice_tab(pepsgpu_ctx *ctx, int orientation, int slice, 
  * The BMPS pair of the slice must be in place; the BTen stacks are left as the per-site calls leave them. */
 int pepsgpu_onsite_slice(pepsgpu_ctx *ctx, int orientation, int slice, int punch_holes, int n_cand, const int32_t *site_table,
                          double *psi_out, double *psi_cand_out);
+/* The next-nearest-neighbour (diagonal) bonds of the row pair (row1, row1 + 1) on the device, every element type: the NNN block of
+ * SquareNNNModelEnergySolver::CalEnergyAndHolesImpl (square_nnn_energy_solver.h:203-265: InitBTen2(LEFT, row1), GrowFullBTen2(RIGHT,
+ * row1, 2, true), then per column the ReplaceNNNSiteTrace of each diagonal with its two end states exchanged and ShiftBTen2Window(RIGHT,
+ * row1), after the last column too) with ONE read-back.  Preconditions of the row pass: the UP boundary MPS at row1 and the DOWN one at
+ * row1 + 1, i.e. the state after that row's nearest-neighbour slice and before ShiftBMPSWindow(DOWN).
+ *   diag_mask  bit 0: LEFTUP_TO_RIGHTDOWN, (row1, c) <-> (row1 + 1, c + 1); bit 1: LEFTDOWN_TO_RIGHTUP, (row1 + 1, c) <-> (row1, c + 1);
+ *   val_out    [n][cols - 1][2] (PEPSGPU_C128: interleaved (re, im)): the amplitude of the configuration with the two ends of diagonal
+ *              `kind` of plaquette c exchanged; 0.0 for a diagonal that is not in the mask and for equal end states (the identity: the
+ *              reference contracts nothing there, square_spin_onehalf_xxz_obc.h:107-134; the caller decides it from the configuration).
+ * The BTen2 stacks end as the per-plaquette calls leave them.  Status PEPSGPU_EINVAL: row1 outside [0, rows - 2], diag_mask outside 1..3,
+ * a NULL buffer; PEPSGPU_ESTATE: a boundary MPS of the row pair is missing, or a configuration override (pepsgpu_cfg_override_slice) is
+ * active -- the slice reads the walkers' own configuration table, i.e. it serves bosonic configurations of every element type; the
+ * fermionic diagonal hop keeps the per-plaquette calls.  A refused call leaves the context usable. */
+int pepsgpu_nnn_exchange_slice(pepsgpu_ctx *ctx, int row1, int diag_mask, double *val_out);
+/* Completed pepsgpu_nnn_exchange_slice calls of this process (all contexts): lets a caller prove which path computed its numbers. */
+long pepsgpu_diag_nnn_slice_calls(void);
 
 /* BMPSWalker as an object -- BMPSContractor::GetWalker / class BMPSWalker, bmps_contractor.h:357-646, bmps/impl/bmps_walker.h:13-465.
  * A walker holds the fork of the top BMPS of stack `pos` for every Monte-Carlo walker of the context (deep copy; the stacks are not
@@ -430,6 +446,12 @@ int pepsgpu_diag_tgemm_chain3(const int *dims8, const int *site_strides4, long s
                               const int32_t *live4, const int32_t *skip, int nbatch, const int *offs3, const float *mps1,
                               const float *bten, const float *site, const float *mps2, float *out, int32_t *flags_out,
                               int32_t *launched_out, int32_t *variant_out);
+/* trace_dot4_kernel alone (the closure of the two-row traces): out[b] = exp(lsum[b]) sum_{ijkl} a[b][i][j][k][l] b[b][l][k][j][i] for
+ * nbatch entries of dims4 = (I, J, K, L), no conjugation, float64 / complex float64 accumulation; dtype PEPSGPU_F32 / F64 / C128 (out
+ * then holds interleaved pairs).  flag (may be NULL, the batch_flag convention of the tensor GEMM): an entry with flag[b] >= 0 is
+ * skipped and writes 0.0. */
+int pepsgpu_diag_dot4(int dtype, const void *a, const void *b, const int *dims4, int nbatch, const double *lsum, const int32_t *flag,
+                      double *out);
 int pepsgpu_diag_chol(int dtype_out, const double *G, int n, int nbatch, void *R_out);
 /* the streaming f64 Gram kernel of the forward pass (gram.h): P = [nbatch][K][n], klive (nullable) = live rows per entry */
 int pepsgpu_diag_gram_cols(int dtype, const void *P, int K, int n, int nbatch, const int32_t *klive, double *G_out);

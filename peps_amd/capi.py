@@ -26,7 +26,7 @@ SYMBOLS = [
     "pepsgpu_walkers_set_configs", "pepsgpu_walkers_get_configs", "pepsgpu_n_walkers",
     "pepsgpu_grow_bmps_step", "pepsgpu_grow_full_bmps", "pepsgpu_grow_bmps_for_row", "pepsgpu_grow_bmps_for_col",
     "pepsgpu_shift_bmps_window", "pepsgpu_delete_inner_bmps", "pepsgpu_bmps_park", "pepsgpu_bmps_unpark", "pepsgpu_generate_bmps_approach",
-    "pepsgpu_sweep_slice_exchange", "pepsgpu_sweep_slice_exchange_tab", "pepsgpu_sweep_slice_fullspace", "pepsgpu_sweep_slice_tnn3", "pepsgpu_diag_tnn3_table", "pepsgpu_nn_exchange_slice", "pepsgpu_nn_exchange_slice_tab", "pepsgpu_onsite_slice", "pepsgpu_walker_create", "pepsgpu_walker_clone", "pepsgpu_walker_destroy", "pepsgpu_walker_info", "pepsgpu_walker_set_mpo", "pepsgpu_walker_evolve",
+    "pepsgpu_sweep_slice_exchange", "pepsgpu_sweep_slice_exchange_tab", "pepsgpu_sweep_slice_fullspace", "pepsgpu_sweep_slice_tnn3", "pepsgpu_diag_tnn3_table", "pepsgpu_nn_exchange_slice", "pepsgpu_nn_exchange_slice_tab", "pepsgpu_onsite_slice", "pepsgpu_nnn_exchange_slice", "pepsgpu_diag_nnn_slice_calls", "pepsgpu_walker_create", "pepsgpu_walker_clone", "pepsgpu_walker_destroy", "pepsgpu_walker_info", "pepsgpu_walker_set_mpo", "pepsgpu_walker_evolve",
     "pepsgpu_walker_evolve_step", "pepsgpu_walker_contract_row", "pepsgpu_walker_init_bten", "pepsgpu_walker_grow_bten_step",
     "pepsgpu_walker_shift_bten_window", "pepsgpu_walker_trace_with_bten", "pepsgpu_walker_clear_bten", "pepsgpu_walker_get_bmps_tensor",
     "pepsgpu_bmps_stack_size", "pepsgpu_get_bmps_tensor", "pepsgpu_init_bten", "pepsgpu_grow_full_bten",
@@ -43,7 +43,7 @@ SYMBOLS = [
     "pepsgpu_sr_cg_solve", "pepsgpu_sr_gram", "pepsgpu_sr_weighted_sum", "pepsgpu_sr_copy_samples",
     "pepsgpu_update_local", "pepsgpu_erase_envs_after_update", "pepsgpu_evaluate_amplitude",
     "pepsgpu_walker_flags", "pepsgpu_sync", "pepsgpu_stats", "pepsgpu_profile_enable", "pepsgpu_profile_read",
-    "pepsgpu_diag_tgemm", "pepsgpu_diag_tgemm_desc", "pepsgpu_diag_tgemm_route", "pepsgpu_diag_tgemm_chain", "pepsgpu_diag_tgemm_chain3", "pepsgpu_diag_chol", "pepsgpu_diag_chol_adaptive", "pepsgpu_diag_chol_pivot", "pepsgpu_diag_rows_qr", "pepsgpu_diag_suwa_todo", "pepsgpu_diag_gram_chol", "pepsgpu_diag_gram_cols", "pepsgpu_diag_gram_rows", "pepsgpu_diag_mgemm_dense", "pepsgpu_diag_jacobi", "pepsgpu_version",
+    "pepsgpu_diag_tgemm", "pepsgpu_diag_tgemm_desc", "pepsgpu_diag_tgemm_route", "pepsgpu_diag_tgemm_chain", "pepsgpu_diag_tgemm_chain3", "pepsgpu_diag_chol", "pepsgpu_diag_chol_adaptive", "pepsgpu_diag_chol_pivot", "pepsgpu_diag_rows_qr", "pepsgpu_diag_suwa_todo", "pepsgpu_diag_dot4", "pepsgpu_diag_gram_chol", "pepsgpu_diag_gram_cols", "pepsgpu_diag_gram_rows", "pepsgpu_diag_mgemm_dense", "pepsgpu_diag_jacobi", "pepsgpu_version",
 ]
 
 
@@ -107,6 +107,10 @@ def load_library(path=LIB_PATH):
     lib.pepsgpu_diag_tnn3_table.argtypes = [C.c_int, ip]
     lib.pepsgpu_nn_exchange_slice.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, dp]
     lib.pepsgpu_nn_exchange_slice_tab.argtypes = [vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, dp, dp]
+    lib.pepsgpu_nnn_exchange_slice.argtypes = [vp, C.c_int, C.c_int, dp]
+    lib.pepsgpu_diag_nnn_slice_calls.argtypes = []
+    lib.pepsgpu_diag_nnn_slice_calls.restype = C.c_long
+    lib.pepsgpu_diag_dot4.argtypes = [C.c_int, vp, vp, ip, C.c_int, dp, ip, dp]
     lib.pepsgpu_onsite_slice.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, dp, dp]
     lib.pepsgpu_walker_create.argtypes = [vp, C.c_int, C.c_int, ip]
     lib.pepsgpu_walker_clone.argtypes = [vp, C.c_int, ip]
@@ -357,6 +361,14 @@ class Context:
         self._ck(self._l.pepsgpu_nn_exchange_slice_tab(self._h, orientation, slice_num, int(punch_holes), _ip(tab) if tab is not None else None,
                                                        int(psi_per_bond), _dp(psi), _dp(ex)))
         return psi, ex
+
+    def nnn_exchange_slice(self, row1, diag_mask=3):
+        """the diagonal bonds of the row pair (row1, row1 + 1): [n][cols - 1][2] amplitudes with the two ends of the diagonal exchanged
+        (kind 0 LEFTUP_TO_RIGHTDOWN, kind 1 LEFTDOWN_TO_RIGHTUP; diag_mask bit per kind), 0 for a masked-off diagonal and for equal
+        end states; one read-back"""
+        val = np.zeros((self.n, self.cols - 1, 2), dtype=self._ot)
+        self._ck(self._l.pepsgpu_nnn_exchange_slice(self._h, row1, diag_mask, _dp(val)))
+        return val
 
     def onsite_slice(self, orientation, slice_num, site_table, punch_holes=False):
         """one-site moves along a row / column: site_table [d][n_cand] (candidate k of state s); returns (psi [n],
@@ -920,6 +932,31 @@ def diag_suwa_todo(weights, init, words):
     rc = f(_dp(w), len(w), int(init), wd.ctypes.data_as(C.POINTER(C.c_uint32)), steps, _ip(out))
     if rc != 0:
         raise RuntimeError("diag_suwa_todo failed: %s" % lib().pepsgpu_last_error(None).decode())
+    return out
+
+
+def diag_nnn_slice_calls():
+    """completed pepsgpu_nnn_exchange_slice calls of this process"""
+    return int(lib().pepsgpu_diag_nnn_slice_calls())
+
+
+def diag_dot4(a, b, lsum, flag=None):
+    """trace_dot4_kernel alone: a [nb][I][J][K][L], b [nb][L][K][J][I] (float32, float64 or complex128) ->
+    out[e] = exp(lsum[e]) sum a[e][i][j][k][l] b[e][l][k][j][i]; entries with flag[e] >= 0 are skipped and come back as 0"""
+    a = np.ascontiguousarray(a)
+    b = np.ascontiguousarray(b, dtype=a.dtype)
+    dtype = {np.dtype(np.float32): F32, np.dtype(np.float64): F64, np.dtype(np.complex128): C128}[a.dtype]
+    nb = a.shape[0]
+    dims = np.ascontiguousarray(a.shape[1:], dtype=np.int32)
+    assert dims.size == 4 and b.shape == (nb,) + tuple(int(x) for x in dims[::-1]), (a.shape, b.shape)
+    ls = np.ascontiguousarray(lsum, dtype=np.float64)
+    assert ls.shape == (nb,)
+    fl = None if flag is None else np.ascontiguousarray(flag, dtype=np.int32)
+    out = np.zeros(nb, dtype=np.complex128 if dtype == C128 else np.float64)
+    rc = lib().pepsgpu_diag_dot4(dtype, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), _ip(dims), nb, _dp(ls),
+                                 None if fl is None else _ip(fl), _dp(out))
+    if rc != 0:
+        raise RuntimeError("diag_dot4 failed: %s" % lib().pepsgpu_last_error(None).decode())
     return out
 
 

@@ -166,6 +166,11 @@ int pepsgpu_onsite_slice(pepsgpu_ctx *ctx, int orientation, int slice, int punch
   CTX_CALL(PG_REQUIRE(site_table && psi_out && psi_cand_out, 1, "null buffer"); PG_REQUIRE(n_cand >= 1, 1, "n_cand < 1");
            ctx->eng->energy_slice_impl(1, orientation, slice, punch_holes, site_table, n_cand, 0, psi_out, psi_cand_out));
 }
+// square_nnn_energy_solver.h:203-265: the diagonal bonds of one row pair
+int pepsgpu_nnn_exchange_slice(pepsgpu_ctx *ctx, int row1, int diag_mask, double *val_out) {
+  CTX_CALL(PG_REQUIRE(val_out, 1, "null buffer"); ctx->eng->nnn_exchange_slice(row1, diag_mask, val_out));
+}
+long pepsgpu_diag_nnn_slice_calls(void) { return pepsgpu::nnn_slice_calls().load(); }
 int pepsgpu_walker_create(pepsgpu_ctx *ctx, int pos, int level, int *walker_out) {
   CTX_CALL(check_pos(pos); PG_REQUIRE(walker_out != nullptr, 1, "null output"); *walker_out = ctx->eng->walker_create(pos, level));
 }
@@ -885,6 +890,44 @@ extern "C" int pepsgpu_diag_rows_qr(const float *X, int k, int len, int nbatch, 
     PG_CHECK_HIP(hipMemcpy(V_out, dV, ne * sizeof(float), hipMemcpyDeviceToHost));
     PG_CHECK_HIP(hipMemcpy(klive_out, dm, nbatch * sizeof(int), hipMemcpyDeviceToHost));
     (void)hipFree(dX); (void)hipFree(dV); (void)hipFree(dn); (void)hipFree(dm);
+  });
+}
+// trace_dot4_kernel alone: out[b] = exp(lsum[b]) sum_{ijkl} a[b][i][j][k][l] b[b][l][k][j][i], 0.0 where flag[b] >= 0
+template <typename T>
+static void diag_dot4_t(const void *a, const void *b, const int *dims4, int nbatch, const double *lsum, const int32_t *flag, double *out) {
+  typedef typename acc64_of<T>::type Acc;
+  constexpr int ko = (int)(sizeof(Acc) / sizeof(double));
+  const long n = (long)dims4[0] * dims4[1] * dims4[2] * dims4[3];
+  const size_t bytes = sizeof(T) * (size_t)n * nbatch;
+  T *da, *db; double *dl, *dout; int *df = nullptr;
+  PG_CHECK_HIP(hipMalloc(&da, bytes));
+  PG_CHECK_HIP(hipMalloc(&db, bytes));
+  PG_CHECK_HIP(hipMalloc(&dl, nbatch * sizeof(double)));
+  PG_CHECK_HIP(hipMalloc(&dout, (size_t)ko * nbatch * sizeof(double)));
+  PG_CHECK_HIP(hipMemcpy(da, a, bytes, hipMemcpyHostToDevice));
+  PG_CHECK_HIP(hipMemcpy(db, b, bytes, hipMemcpyHostToDevice));
+  PG_CHECK_HIP(hipMemcpy(dl, lsum, nbatch * sizeof(double), hipMemcpyHostToDevice));
+  if (flag) {
+    PG_CHECK_HIP(hipMalloc(&df, nbatch * sizeof(int)));
+    PG_CHECK_HIP(hipMemcpy(df, flag, nbatch * sizeof(int), hipMemcpyHostToDevice));
+  }
+  hipLaunchKernelGGL((trace_dot4_kernel<T, Acc>), dim3(nbatch), dim3(256), 0, 0, (const T *)da, (const T *)db, n, dims4[0], dims4[1],
+                     dims4[2], dims4[3], (const double *)dl, (const int *)df, 1, 0, 0, 1L, dout);
+  PG_CHECK_HIP(hipGetLastError());
+  PG_CHECK_HIP(hipDeviceSynchronize());
+  PG_CHECK_HIP(hipMemcpy(out, dout, (size_t)ko * nbatch * sizeof(double), hipMemcpyDeviceToHost));
+  (void)hipFree(da); (void)hipFree(db); (void)hipFree(dl); (void)hipFree(dout); if (df) (void)hipFree(df);
+}
+extern "C" int pepsgpu_diag_dot4(int dtype, const void *a, const void *b, const int *dims4, int nbatch, const double *lsum,
+                                 const int32_t *flag, double *out) {
+  return guarded(nullptr, [&]() {
+    PG_REQUIRE(a && b && dims4 && lsum && out && nbatch >= 1, 1, "bad arguments");
+    PG_REQUIRE(dims4[0] >= 1 && dims4[1] >= 1 && dims4[2] >= 1 && dims4[3] >= 1 &&
+                   (double)dims4[0] * dims4[1] * dims4[2] * dims4[3] * nbatch < 2147483648.0, 1, "bad sizes");
+    if (dtype == PEPSGPU_F32) diag_dot4_t<float>(a, b, dims4, nbatch, lsum, flag, out);
+    else if (dtype == PEPSGPU_F64) diag_dot4_t<double>(a, b, dims4, nbatch, lsum, flag, out);
+    else if (dtype == PEPSGPU_C128) diag_dot4_t<c128>(a, b, dims4, nbatch, lsum, flag, out);
+    else throw Error(1, "unknown dtype");
   });
 }
 // The device's SuwaTodoStateUpdate alone (round 6): a chain of `steps` updates on one weight vector (n <= 16 states), fed with the

@@ -128,6 +128,8 @@ struct EngineBase {
   // engine_sweep.h
   virtual void energy_slice_impl(int mode, int orient, int slice, int punch_holes, const int32_t *table, int n_cand, int psi_per_bond,
                                  double *psi_out, double *val_out) = 0;
+  // the diagonal bonds of the row pair (row1, row1 + 1) (square_nnn_energy_solver.h:203-265); engine_sweep.h
+  virtual void nnn_exchange_slice(int row1, int diag_mask, double *val_out) = 0;
   // BMPSWalker (bmps_contractor.h:357-646)
   virtual int walker_create(int pos, int level) = 0;
   virtual int walker_clone(int id) = 0;
@@ -966,6 +968,7 @@ class Engine : public EngineBase {
   void nn_exchange_slice(int orient, int slice, int punch_holes, double *psi_out, double *psi_ex_out) override;
   void energy_slice_impl(int mode, int orient, int slice, int punch_holes, const int32_t *table, int n_cand, int psi_per_bond,
                          double *psi_out, double *val_out) override;
+  void nnn_exchange_slice(int row1, int diag_mask, double *val_out) override;
   // the parts the slice functions share (engine_sweep.h)
   void begin_slice(const SliceGeom &g, int remain);
   template <typename Moves>
@@ -1402,7 +1405,7 @@ class Engine : public EngineBase {
     return SiteSel{s.r, s.c, dcand + s.cand, ncols};
   }
   BTenDev bten2_step(int post, const BTenDev &bt, const DTen<T> &mps1, const SiteSel &s1, const SiteSel &s2,
-                     const DTen<T> &mps2, int ncand, int bt_ncand, bool normalise);
+                     const DTen<T> &mps2, int ncand, int bt_ncand, bool normalise, const int *entry_flag = nullptr);
   void finish_dot4(const DTen<T> &a, const DTen<T> &b, int nc, double *lsum, double *out);
   int *upload_cand(int ncand, int ncols, const int32_t *cand);
   // sel (optional, f32): the kernel of the walkers with at most JR_BR live rows selects / normalises their rows into Vt

@@ -16,10 +16,12 @@ enum { LEFTUP_TO_RIGHTDOWN = 0, LEFTDOWN_TO_RIGHTUP = 1 };   // basic.h:89-92 DI
 //   tmp2[b2,b3,x,o1,n1] = sum_{p1,b1} tmp1 . site1[(post+3)<-p1, post<-b1 | (post+2)->o1, (post+1)->n1]
 //   tmp3[b3,x,o1,n2,o2] = sum_{n1,b2} tmp2 . site2[(post+3)<-n1, post<-b2 | (post+1)->n2, (post+2)->o2]
 //   out                 = sum_{b3,n2} tmp3 . mps2
+// entry_flag (optional, one per walker x candidate entry, the batch_flag convention of the tensor GEMM): an entry whose flag is >= 0
+// launches no work and leaves its part of `out` undefined, as `skip` does in bten_step.
 template <typename T>
 typename Engine<T>::BTenDev Engine<T>::bten2_step(int post, const BTenDev &bt, const DTen<T> &mps1, const SiteSel &s1,
                                                   const SiteSel &s2, const DTen<T> &mps2, int ncand, int bt_ncand,
-                                                  bool normalise) {
+                                                  bool normalise, const int *entry_flag) {
   ArenaScope scope(arena_);
   const int nb = nw_ * ncand, nb1 = nw_ * bt_ncand;
   PG_REQUIRE(ncand % bt_ncand == 0 && (!normalise || ncand == 1), 1, "BTen2 step: bad candidate batching");
@@ -39,6 +41,7 @@ typename Engine<T>::BTenDev Engine<T>::bten2_step(int post, const BTenDev &bt, c
     g.K[2] = cdim; g.sAk[2] = 1; g.sBk[2] = b1 * b2 * b3;
     g.J[2] = b1 * b2 * b3; g.sBj[2] = 1; g.sCj[2] = 1;
     g.wA = mps1.n; g.bdivA = bt_ncand; g.wB = bt.t.n; g.wC = tmp1.n; g.nbatch = nb1;
+    if (bt_ncand == ncand) g.batch_flag = entry_flag;     // (else tmp1 is shared by the candidates of a walker)
     tgemm_launch<T, T, T, T>(stream_, g, mps1.p, bt.t.p, tmp1.p);
   }
   // tmp1 layout [x][p1][b1][b2][b3]
@@ -51,6 +54,7 @@ typename Engine<T>::BTenDev Engine<T>::bten2_step(int post, const BTenDev &bt, c
     g.K[1] = p1; g.K[2] = b1; g.sAk[1] = b1 * b2 * b3; g.sAk[2] = b2 * b3; g.sBk[1] = st1[lc]; g.sBk[2] = st1[lb];
     g.J[1] = o1; g.J[2] = n1; g.sBj[1] = st1[lo]; g.sBj[2] = st1[ln]; g.sCj[1] = n1; g.sCj[2] = 1;
     g.wA = tmp1.n; g.bdivA = ncand / bt_ncand; g.wC = tmp2.n; g.nbatch = nb;
+    g.batch_flag = entry_flag;
     launch_site_gemm(g, s1, ncand, tmp1.p, tmp2.p);
   }
   // tmp2 layout [b2][b3][x][o1][n1]
@@ -63,6 +67,7 @@ typename Engine<T>::BTenDev Engine<T>::bten2_step(int post, const BTenDev &bt, c
     g.K[1] = n1; g.K[2] = b2; g.sAk[1] = 1; g.sAk[2] = b3 * x * o1 * n1; g.sBk[1] = st2[lc]; g.sBk[2] = st2[lb];
     g.J[1] = n2; g.J[2] = o2; g.sBj[1] = st2[ln]; g.sBj[2] = st2[lo]; g.sCj[1] = o2; g.sCj[2] = 1;
     g.wA = tmp2.n; g.wC = tmp3.n; g.nbatch = nb;
+    g.batch_flag = entry_flag;
     launch_site_gemm(g, s2, ncand, tmp2.p, tmp3.p);
   }
   // tmp3 layout [b3][x][o1][n2][o2]
@@ -76,6 +81,7 @@ typename Engine<T>::BTenDev Engine<T>::bten2_step(int post, const BTenDev &bt, c
     g.K[1] = b3; g.K[2] = n2; g.sAk[1] = x * o1 * n2 * o2; g.sAk[2] = o2; g.sBk[1] = n2 * y; g.sBk[2] = y;
     g.J[2] = y; g.sBj[2] = 1; g.sCj[2] = 1;
     g.wA = tmp3.n; g.wB = mps2.n; g.bdivB = ncand; g.wC = o.t.n; g.nbatch = nb;
+    g.batch_flag = entry_flag;
     tgemm_launch<T, T, T, T>(stream_, g, tmp3.p, mps2.p, o.t.p);
   }
   free_ten(tmp1); free_ten(tmp2); free_ten(tmp3);

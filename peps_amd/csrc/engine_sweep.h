@@ -19,8 +19,10 @@
 // the reference's flow), so it is applied unconditionally -- the decision "did any walker accept" would cost a read-back per bond.
 #pragma once
 #include <algorithm>
+#include <atomic>
 #include <vector>
 #include "engine.h"
+#include "engine_nnn.h"
 
 namespace pepsgpu {
 
@@ -397,6 +399,102 @@ void Engine<T>::energy_slice_impl(int mode, int orient, int slice, int punch_hol
       }
     }
   }
+}
+
+// ---- the diagonal bonds of a row pair (SquareNNNModelEnergySolver::CalEnergyAndHolesImpl, square_nnn_energy_solver.h:203-265) ----
+// Both diagonal exchanges of the plaquette (row1, col1) .. (row2, col2) are candidates of ONE four-site replacement, as
+// replace_plaquette_trace batches candidates: cand[w][q][4] = the states of (row1, col1), (row2, col1), (row2, col2), (row1, col2) with
+// the two ends of the q-th requested diagonal exchanged -- LEFTUP_TO_RIGHTDOWN exchanges (row1, col1) and (row2, col2),
+// LEFTDOWN_TO_RIGHTUP (row2, col1) and (row1, col2) -- and the other two sites in their own states.  flag[w][q] (the batch_flag
+// convention of the tensor GEMM): >= 0 where the move is the identity (equal end states; the reference returns before any
+// contraction, square_spin_onehalf_xxz_obc.h:107-134), -1 where the entry has work.
+__global__ void nnn_diag_cand_kernel(const int *__restrict__ cfg, int sites, int s0, int s1, int s2, int s3, int nc, int kind0, int kind1,
+                                     int *__restrict__ cand, int *__restrict__ flag, int n) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n * nc) return;
+  const int w = e / nc, q = e - w * nc, kind = q ? kind1 : kind0;
+  const long cw = (long)w * sites;
+  const int c0 = cfg[cw + s0], c1 = cfg[cw + s1], c2 = cfg[cw + s2], c3 = cfg[cw + s3];
+  int *c = cand + 4 * (long)e;
+  if (kind == LEFTUP_TO_RIGHTDOWN) { c[0] = c2; c[1] = c1; c[2] = c0; c[3] = c3; flag[e] = c0 == c2 ? 1 : -1; }
+  else { c[0] = c0; c[1] = c3; c[2] = c2; c[3] = c1; flag[e] = c1 == c3 ? 1 : -1; }
+}
+
+inline std::atomic<long> &nnn_slice_calls() {   // completed nnn_exchange_slice calls of the process (pepsgpu_diag_nnn_slice_calls)
+  static std::atomic<long> n{0};
+  return n;
+}
+
+// One row pair of the diagonal-bond pass on the device: InitBTen2(LEFT, row1), GrowFullBTen2(RIGHT, row1, 2, init), then for every
+// column the amplitudes of the configuration with the ends of each requested diagonal exchanged and ShiftBTen2Window(RIGHT, row1)
+// (after the last column too, as the host loop does) -- ONE read-back at the end.  Bosonic configurations: the walkers' own table, no
+// configuration override active (status 3 otherwise).  diag_mask: bit 0 LEFTUP_TO_RIGHTDOWN, bit 1
+// LEFTDOWN_TO_RIGHTUP.  val_out [n][Lx - 1][2] (complex: interleaved): 0.0 for a diagonal that is not in the mask and for an identity
+// move.  The intermediate tensors of a plaquette are those of replace_nnn_trace (one pair of bten2_steps over the candidates); the
+// closure is trace_dot4_kernel, which writes psi' = res exp(lsum) straight into the value table.
+// A diagonal that is masked off, or the identity for EVERY walker (the host mirror of the configurations tells), is no candidate at
+// all: it launches nothing and keeps the zero the table starts with (the `any` test of the per-bond hooks); a plaquette without
+// candidates only shifts the window.
+template <typename T>
+void Engine<T>::nnn_exchange_slice(int row1, int diag_mask, double *val_out) {
+  require_ready();
+  PG_REQUIRE(val_out, 1, "null buffer");
+  PG_REQUIRE(row1 >= 0 && row1 + 1 < Ly_ && Lx_ >= 2, 1, "diagonal slice: row pair outside the lattice");
+  PG_REQUIRE(diag_mask >= 1 && diag_mask <= 3, 1, "diagonal slice: diag_mask must be 1, 2 or 3");
+  const int row2 = row1 + 1, sites = Ly_ * Lx_, np = Lx_ - 1;
+  // (the candidate kernel reads the walkers' own configuration table for all four sites of a plaquette: a configuration override
+  // -- cfg_override_slice, a BMPSWalker operation -- would be ignored where the per-plaquette calls honour it, so it is refused)
+  PG_REQUIRE(!ovr_on_, 3, "diagonal slice: a configuration override is active (bosonic configurations only)");
+  (void)bmps_at_slice(UP, row1);                                              // (status 3 before anything is touched)
+  (void)bmps_at_slice(DOWN, row2);
+  const size_t nval = (size_t)kOut * nw_ * np * 2;
+  ArenaBuf<double> dval(arena_, nval);
+  ArenaBuf<int> dcand(arena_, 10 * (size_t)nw_);                              // candidates [n][2][4], flags [n][2]
+  int *dflag = dcand + 8 * (size_t)nw_;
+  PG_CHECK_HIP(hipMemsetAsync(dval, 0, sizeof(double) * nval, stream_));
+  init_bten2(LEFT, row1);
+  grow_full_bten2(RIGHT, row1, 2, 1);
+  for (int col1 = 0; col1 < np; ++col1) {
+    const int col2 = col1 + 1;
+    const int s0 = row1 * Lx_ + col1, s1 = row2 * Lx_ + col1, s2 = row2 * Lx_ + col2, s3 = row1 * Lx_ + col2;
+    int kinds[2] = {0, 0}, nc = 0;
+    for (int kind = 0; kind < 2; ++kind) {
+      if (!((diag_mask >> kind) & 1)) continue;
+      const int sa = kind == LEFTUP_TO_RIGHTDOWN ? s0 : s1, sb = kind == LEFTUP_TO_RIGHTDOWN ? s2 : s3;
+      bool any = false;
+      for (int w = 0; w < nw_ && !any; ++w) any = hcfg_[(size_t)w * sites + sa] != hcfg_[(size_t)w * sites + sb];
+      if (any) kinds[nc++] = kind;
+    }
+    if (nc > 0) {
+      ArenaScope scope(arena_);
+      const int nb = nw_ * nc;
+      hipLaunchKernelGGL(nnn_diag_cand_kernel, dim3((nb + 255) / 256), dim3(256), 0, stream_, (const int *)cfg_, sites, s0, s1, s2, s3, nc,
+                         kinds[0], kinds[nc - 1], dcand, dflag, nw_);
+      PG_CHECK_HIP(hipGetLastError());
+      const BMPSDev &up = bmps_at_slice(UP, row1), &dn = bmps_at_slice(DOWN, row2);
+      PG_REQUIRE(bten2_size(LEFT) > col1, 3, "diagonal slice: LEFT BTen2 missing");
+      const BTenDev &lb = bten2_[LEFT][col1], &rb = bten2_at_slice(RIGHT, col2);
+      const SitePick t0{row1, col1, 0}, t1{row2, col1, 1}, t2{row2, col2, 2}, t3{row1, col2, 3};
+      double *lsum = zeros_f64();
+      BTenDev a = bten2_step(LEFT, lb, at_logical(up, UP, col1), pick(t0, dcand, 4), pick(t1, dcand, 4), at_logical(dn, DOWN, col1), nc, 1,
+                             false, dflag);
+      BTenDev b = bten2_step(RIGHT, rb, at_logical(dn, DOWN, col2), pick(t2, dcand, 4), pick(t3, dcand, 4), at_logical(up, UP, col2), nc, 1,
+                             false, dflag);
+      add_logs(lsum, up.logscale, dn.logscale, lb.logscale, rb.logscale);
+      PG_REQUIRE(a.t.d[0] == b.t.d[3] && a.t.d[1] == b.t.d[2] && a.t.d[2] == b.t.d[1] && a.t.d[3] == b.t.d[0], 3,
+                 "trace: two-row environment bond mismatch");
+      hipLaunchKernelGGL((trace_dot4_kernel<T, Acc>), dim3(nb), dim3(256), 0, stream_, (const T *)a.t.p, (const T *)b.t.p, a.t.n, a.t.d[0],
+                         a.t.d[1], a.t.d[2], a.t.d[3], (const double *)lsum, (const int *)dflag, nc, kinds[0], kinds[nc - 1], (long)np * 2,
+                         dval + (size_t)kOut * 2 * col1);
+      PG_CHECK_HIP(hipGetLastError());
+      free_ten(a.t); free_ten(b.t);
+      arena_.free(lsum);
+    }
+    shift_bten2_window(RIGHT, row1);
+  }
+  PG_CHECK_HIP(hipMemcpyAsync(val_out, dval, sizeof(double) * nval, hipMemcpyDeviceToHost, stream_));
+  PG_CHECK_HIP(hipStreamSynchronize(stream_));
+  nnn_slice_calls() += 1;
 }
 
 // ---- three-site exchange (MCUpdateSquareTNN3SiteExchange::TNN3SiteUpdateImpl, square_3site_updater.h:109-158) ----

@@ -1865,6 +1865,78 @@ __global__ __launch_bounds__(256) void trace_dot_kernel(const T *__restrict__ t2
   if (tid == 0) res[b] = s_red[0] + s_red[1] + s_red[2] + s_red[3];
 }
 
+// The closing contraction of the two-row traces: res[b] = sum_{i,j,k,l} a[b][i][j][k][l] * b4[b][l][k][j][i]  (no conjugation, as
+// trace_dot_kernel).  One block per batch entry.  The operands are transposes of each other -- a is contiguous in l, b4 in i -- and at the
+// bulk shapes (32 x 8 x 8 x 32) b4 is past the LDS trace_dot_kernel stages its second operand in, so: for every (j, k) the (i, l) plane
+// is cut into DOT4_T x DOT4_T tiles; the b4 tile is read along i (coalesced), staged in LDS [l][i] and read back along l with the odd
+// row pitch DOT4_T + 1 (the lanes of a read walk l: consecutive rows, consecutive banks), the a tile streams along l.  Elements outside
+// the operands enter as zeros, so the tile loop has no branch.  Two LDS buffers take turns, so one barrier per tile; the operands of
+// the next tile are loaded into registers before the current one is summed.  No integer division inside the loops.  float64 (complex float64) accumulation.
+// Fused epilogue: thread 0 writes res * exp(lsum[w]) (w = b / nc, candidate q = b - w nc) as doubles (complex: interleaved) to
+// out[(w * w_stride + (q ? slot1 : slot0)) * ko]: the host layout of the slice's value table.  flag (optional, the batch_flag
+// convention of the tensor GEMM): an entry with flag[b] >= 0 has no operands and writes 0.0.
+constexpr int DOT4_T = 32;
+__device__ __forceinline__ void dot4_put(double *o, double x, double s) { o[0] = x * s; }
+__device__ __forceinline__ void dot4_put(double *o, const cplx<double> &x, double s) { o[0] = x.re * s; o[1] = x.im * s; }
+template <typename T, typename AccT>
+__global__ __launch_bounds__(256) void trace_dot4_kernel(const T *__restrict__ ag, const T *__restrict__ bg, long wn, int I, int J, int K,
+                                                         int L, const double *__restrict__ lsum, const int *__restrict__ flag, int nc,
+                                                         int slot0, int slot1, long w_stride, double *__restrict__ out) {
+  constexpr int ko = (int)(sizeof(AccT) / sizeof(double));
+  constexpr int P = DOT4_T + 1;
+  __shared__ T s_b[2][DOT4_T * P];
+  __shared__ AccT s_red[4];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int w = b / nc, q = b - w * nc;
+  double *o = out + ((long)w * w_stride + (q ? slot1 : slot0)) * ko;
+  if (flag && flag[b] >= 0) {
+    if (tid == 0)
+      for (int z = 0; z < ko; ++z) o[z] = 0.0;
+    return;
+  }
+  const T *a = ag + (long)b * wn, *b4 = bg + (long)b * wn;
+  const int lo = tid & (DOT4_T - 1), hi = tid >> 5;                      // 32 x 8 threads: lo walks the contiguous index
+  const long sAi = (long)J * K * L, sBl = (long)K * J * I;               // a[i][j][k][l], b4[l][k][j][i]
+  AccT acc = AccT(0);
+  constexpr int R = DOT4_T / 8;                                          // rows of a tile per thread
+  // the tiles in order (j, k, i0, l0), walked by increments; the operands of a tile are loaded into registers one tile ahead, so
+  // the loads of tile t + 1 are in flight while tile t goes through LDS (a block is often alone on its SIMDs: 2 entries per walker)
+  int j = 0, k = 0, i0 = 0, l0 = 0;
+  T av[R], bv[R];
+  auto load = [&]() {
+    const T *ajk = a + ((long)j * K + k) * L, *bjk = b4 + ((long)k * J + j) * I;
+    const int i_ld = i0 + lo, l_ld = l0 + lo;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int l = l0 + hi + 8 * r, i = i0 + hi + 8 * r;
+      bv[r] = (l < L && i_ld < I) ? bjk[(long)l * sBl + i_ld] : T(0);   // b4[l][k][j][i0 + lo]
+      av[r] = (i < I && l_ld < L) ? ajk[(long)i * sAi + l_ld] : T(0);   // a[i][j][k][l0 + lo]
+    }
+  };
+  load();
+  int buf = 0;
+  while (j < J) {
+    T *sb = s_b[buf];
+    T ac[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) { sb[(hi + 8 * r) * P + lo] = bv[r]; ac[r] = av[r]; }
+    __syncthreads();
+    l0 += DOT4_T;
+    if (l0 >= L) { l0 = 0; i0 += DOT4_T; }
+    if (i0 >= I) { i0 = 0; ++k; }
+    if (k >= K) { k = 0; ++j; }
+    if (j < J) load();
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc += AccT(ac[r]) * AccT(sb[lo * P + hi + 8 * r]);   // a[i0 + r'][..][l0 + lo] * tile[lo][r']
+    buf ^= 1;
+  }
+  if constexpr (is_cplx<AccT>::value) { acc.re = wave_sum(acc.re); acc.im = wave_sum(acc.im); }
+  else acc = wave_sum(acc);
+  if ((tid & 63) == 0) s_red[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) dot4_put(o, AccT(s_red[0] + s_red[1] + s_red[2] + s_red[3]), exp(lsum[w]));
+}
+
 // error-budget experiments: a float64 buffer rounded to float32 values in place (Engine::inject)
 __global__ void round_f32_kernel(double *p, long n) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -193,9 +193,10 @@ void measure_impl(int rows, int cols, int D, int d, int chi, int dtype, const do
   TPSWaveFunctionComponentT<TenElemT> comp(sitps, make_cfg(n, rows, cols, configs), contractor);
   SquareSpinOneHalfXXZModelOBC xxz(p[0], p[1], p[2]);
   SquareSpinOneHalfJ1J2XXZModelOBC j1j2(p[0], p[1], p[2], p[3], p[4]);
+  SpinOneHalfTriHeisenbergSqrPEPS tri;
   SpinOneHalfTriJ1J2HeisenbergSqrPEPS trij(p[0]);
   TransverseFieldIsingSquareOBC tfim(p[0]);
-  if (model < 0 || model > 4 || model == 3) throw std::invalid_argument("pepshost_measure: model must be xxz, tfim, j1j2 or trij1j2");
+  if (model < 0 || model > 4) throw std::invalid_argument("pepshost_measure: model must be xxz, tfim, j1j2, triangle or trij1j2");
   xxz.SetEnableStructureFactor(p[7] != 0.0);                  // params[7]: structure factor switch (xxz only)
   xxz.SetStructureFactorReferenceStackState(p[6] != 0.0);     // params[6]: the DOWN stack as the reference's traversal leaves it (K8; off)
   std::string keys;
@@ -217,11 +218,13 @@ void measure_impl(int rows, int cols, int D, int d, int chi, int dtype, const do
     ObservableMapT<TenElemT> obs = model == 0   ? xxz.EvaluateObservables(sitps, comp)
                                    : model == 1 ? tfim.EvaluateObservables(sitps, comp)
                                    : model == 2 ? j1j2.EvaluateObservables(sitps, comp)
+                                   : model == 3 ? tri.EvaluateObservables(sitps, comp)
                                                 : trij.EvaluateObservables(sitps, comp);
     for (const auto &kv : obs.values) emit(kv.first, kv.second, nullptr, obs.len(kv.first));
     psi = model == 0   ? xxz.SquareNNModelMeasurementSolver<SquareSpinOneHalfXXZModelOBC>::template EvaluatePsiSummaryT<TenElemT>()
           : model == 1 ? tfim.template EvaluatePsiSummaryT<TenElemT>()
           : model == 2 ? j1j2.SquareNNNModelMeasurementSolver<SquareSpinOneHalfJ1J2XXZModelOBC>::template EvaluatePsiSummaryT<TenElemT>()
+          : model == 3 ? tri.SquareNNNModelMeasurementSolver<SpinOneHalfTriHeisenbergSqrPEPS>::template EvaluatePsiSummaryT<TenElemT>()
                        : trij.template EvaluatePsiSummaryT<TenElemT>();
   } else {
     std::vector<uint64_t> sd(seeds, seeds + n);
@@ -241,14 +244,17 @@ void measure_impl(int rows, int cols, int D, int d, int chi, int dtype, const do
     if (updater == 0 && model == 0) run(ex, xxz);
     else if (updater == 0 && model == 1) run(ex, tfim);
     else if (updater == 0 && model == 2) run(ex, j1j2);
+    else if (updater == 0 && model == 3) run(ex, tri);
     else if (updater == 0) run(ex, trij);
     else if (updater == 2 && model == 0) run(t3, xxz);
     else if (updater == 2 && model == 1) run(t3, tfim);
     else if (updater == 2 && model == 2) run(t3, j1j2);
+    else if (updater == 2 && model == 3) run(t3, tri);
     else if (updater == 2) run(t3, trij);
     else if (model == 0) run(fs, xxz);
     else if (model == 1) run(fs, tfim);
     else if (model == 2) run(fs, j1j2);
+    else if (model == 3) run(fs, tri);
     else run(fs, trij);
     std::copy(comp.config.data(), comp.config.data() + (size_t)n * rows * cols, configs);
   }

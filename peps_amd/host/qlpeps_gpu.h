@@ -1088,6 +1088,36 @@ template <typename U> struct HasExchangeBondEnergy<U, std::void_t<decltype(U::kE
 template <typename U, typename = void> struct HasExchangeBondPsiPerBond : std::false_type {};
 template <typename U> struct HasExchangeBondPsiPerBond<U, std::void_t<decltype(U::kExchangeBondPsiPerBond)>> : std::bool_constant<U::kExchangeBondPsiPerBond> {};
 
+// `kExchangeNNNEnergy = true` + the scalar hook NNNEnergyFromExchange(config1, config2, ratio), the twin of BondEnergyFromExchange
+// for a diagonal link: the diagonal bonds of a row pair come from ONE pepsgpu_nnn_exchange_slice call.  `kNNNDiagMask` (optional, bit 0
+// LEFTUP_TO_RIGHTDOWN, bit 1 LEFTDOWN_TO_RIGHTUP; default both) names the diagonals that interact: the others contribute exactly 0.
+template <typename U, typename = void> struct HasExchangeNNNEnergy : std::false_type {};
+template <typename U> struct HasExchangeNNNEnergy<U, std::void_t<decltype(U::kExchangeNNNEnergy)>> : std::bool_constant<U::kExchangeNNNEnergy> {};
+template <typename U, typename = void> struct NNNDiagMask : std::integral_constant<int, 3> {};
+template <typename U> struct NNNDiagMask<U, std::void_t<decltype(U::kNNNDiagMask)>> : std::integral_constant<int, U::kNNNDiagMask> {};
+
+// The diagonal bonds of the row pair (row, row + 1) from the device slice (square_nnn_energy_solver.h:203-265 in one call): sink(w, col,
+// e1, e2) gets, per walker and plaquette, what EvaluateNNNEnergy returns for LEFTUP_TO_RIGHTDOWN and LEFTDOWN_TO_RIGHTUP.  The BMPS
+// pair of the row must be in place (the row pass before ShiftBMPSWindow(DOWN)); the BTen2 stacks end as the hook loop leaves them.
+template <class Model, typename TenElemT, class Sink>
+void NNNSliceEnergies(Model &model, TPSWaveFunctionComponentT<TenElemT> &comp, size_t row, const std::vector<TenElemT> &inv_psi, Sink &&sink) {
+  auto &c = comp.contractor;
+  const size_t n = comp.config.walkers(), np = c.cols() - 1;
+  constexpr int mask = NNNDiagMask<Model>::value;
+  std::vector<TenElemT> val(n * np * 2);
+  check_rc(pepsgpu_nnn_exchange_slice(c.ctx(), (int)row, mask, dptr(val.data())), c.ctx());
+  for (size_t w = 0; w < n; ++w)
+    for (size_t col = 0; col < np; ++col) {
+      const TenElemT *v = &val[(w * np + col) * 2];
+      TenElemT e1(0.0), e2(0.0);
+      if constexpr ((mask & 1) != 0)
+        e1 = model.NNNEnergyFromExchange(comp.config(w, {row, col}), comp.config(w, {row + 1, col + 1}), ComplexConjugate(TenElemT(v[0] * inv_psi[w])));
+      if constexpr ((mask & 2) != 0)
+        e2 = model.NNNEnergyFromExchange(comp.config(w, {row + 1, col}), comp.config(w, {row, col + 1}), ComplexConjugate(TenElemT(v[1] * inv_psi[w])));
+      sink(w, col, e1, e2);
+    }
+}
+
 // square_nn_updater.h:25-83: sweep schedule, CRTP hook TwoSiteNNUpdateLocalImpl(site1, site2, dir, sitps, comp) -> accepted[w]
 template <typename MCUpdater>
 class MCUpdateSquareNNUpdateBaseOBC : public MonteCarloSweepUpdaterBase {
@@ -1424,7 +1454,15 @@ class SquareNNNModelEnergySolver {
       }
       }
       if constexpr (has_nnn_interaction) {                                    // :203-265
-        if (row + 1 < rows) {
+        // (the diagonal bonds of the row pair: ONE pepsgpu_nnn_exchange_slice for a model with the scalar hook NNNEnergyFromExchange;
+        // a fermionic diagonal hop keeps its twisted-environment path through the hooks.  The slice needs the BMPS pair of the row and
+        // inv_psi only, both there on either branch above: unlike dev_slice it does not depend on where the holes go.)
+        bool nnn_slice = false;
+        if constexpr (HasExchangeNNNEnergy<ExplicitlyModel>::value) nnn_slice = DeviceSlicesEnabled() && !comp.fermion;
+        if (row + 1 < rows && nnn_slice) {
+          if constexpr (HasExchangeNNNEnergy<ExplicitlyModel>::value)
+            NNNSliceEnergies(*self, comp, row, inv_psi, [&](size_t w, size_t, TenElemT e1, TenElemT e2) { out.energy[w] += e1 + e2; });
+        } else if (row + 1 < rows) {
           c.InitBTen2(LEFT, row);
           c.GrowFullBTen2(RIGHT, row, 2, true);
           for (size_t col = 0; col + 1 < cols; col++) {
@@ -1613,20 +1651,61 @@ class SquareNNNModelMeasurementSolver {
       }
       return inv;
     };
+    // A model of the diagonal-bond traversal with both scalar hooks (BondEnergyFromExchange, NNNEnergyFromExchange) on a bosonic
+    // component takes the device slices of the energy solver: pepsgpu_nn_exchange_slice_tab per row / column (no holes) and
+    // pepsgpu_nnn_exchange_slice per row pair -- the same operations in the same order, one read-back each.
+    // PEPSHOST_NO_DEVICE_SWEEP=1 keeps the hooks.
+    // MeasureSpinOneHalfOffDiagOrderInRow continues from the BTen stacks the row's bonds leave.  The slice (GrowFullBTen(RIGHT, row, 2)
+    // and no shift behind the last bond) ends with LEFT over [0, lx - 2) where the hook loop ends with LEFT over [0, lx - 1), both with the
+    // RIGHT stack down to its vacuum; the routine's UpdateLocal at column lx / 4 cuts LEFT back to [0, lx / 4) either way (lx / 4 <=
+    // lx - 2 whenever a row has a bond), so it grows the same tensors from the same state.
+    bool meas_slice = false;
+    if constexpr (has_nnn_interaction && HasExchangeBondEnergy<ModelType>::value && HasExchangeNNNEnergy<ModelType>::value)
+      meas_slice = DeviceSlicesEnabled() && !comp.fermion;
+    // psi of the slice into psi_list, the bond energies through put(w, j, e)
+    auto slice_bonds = [&](BondOrientation dir, size_t slice, auto &&put) {
+      if constexpr (HasExchangeBondEnergy<ModelType>::value) {
+        const size_t N = dir == HORIZONTAL ? lx : ly;
+        std::vector<TenElemT> psi(n), ex(n * (N - 1));
+        check_rc(pepsgpu_nn_exchange_slice_tab(c.ctx(), dir, (int)slice, 0, nullptr, 0, dptr(psi.data()), dptr(ex.data())), c.ctx());
+        psi_list.push_back(psi);
+        const std::vector<TenElemT> inv = inverse(psi);
+        for (size_t w = 0; w < n; ++w)
+          for (size_t j = 0; j + 1 < N; ++j) {
+            const SiteIdx s1 = dir == HORIZONTAL ? SiteIdx{slice, j} : SiteIdx{j, slice};
+            const SiteIdx s2 = dir == HORIZONTAL ? SiteIdx{slice, j + 1} : SiteIdx{j + 1, slice};
+            const TenElemT e = derived->BondEnergyFromExchange(comp.config(w, s1), comp.config(w, s2),
+                                                               ComplexConjugate(TenElemT(ex[w * (N - 1) + j] * inv[w])));
+            put(w, j, e);
+            total[w] += e;
+          }
+      }
+    };
     comp.SetOrder(ROW_MAJOR);
     c.GenerateBMPSApproach(UP);
     for (size_t row = 0; row < ly; ++row) {
-      c.InitBTen(LEFT, row);
-      c.GrowFullBTen(RIGHT, row, 1, true);
-      psi_list.push_back(c.Trace({row, 0}, HORIZONTAL));
+      if (meas_slice) {
+        slice_bonds(HORIZONTAL, row, [&](size_t w, size_t col, TenElemT e) { e_h[w * ly * (lx - 1) + row * (lx - 1) + col] = e; });
+      } else {
+        c.InitBTen(LEFT, row);
+        c.GrowFullBTen(RIGHT, row, 1, true);
+        psi_list.push_back(c.Trace({row, 0}, HORIZONTAL));
+      }
       const std::vector<TenElemT> inv_psi = inverse(psi_list.back());
-      for (size_t col = 0; col + 1 < lx; ++col) {
+      for (size_t col = 0; !meas_slice && col + 1 < lx; ++col) {
         std::vector<TenElemT> e = derived->EvaluateBondEnergy({row, col}, {row, col + 1}, HORIZONTAL, comp, inv_psi);
         for (size_t w = 0; w < n; ++w) { e_h[w * ly * (lx - 1) + row * (lx - 1) + col] = e[w]; total[w] += e[w]; }
         c.ShiftBTenWindow(RIGHT);
       }
       if constexpr (has_nnn_interaction) {
-        if (row + 1 < ly) {
+        if (row + 1 < ly && meas_slice) {
+          if constexpr (HasExchangeNNNEnergy<ModelType>::value)
+            NNNSliceEnergies(*derived, comp, row, inv_psi, [&](size_t w, size_t col, TenElemT e1, TenElemT e2) {
+              const size_t k = w * (ly - 1) * (lx - 1) + row * (lx - 1) + col;
+              (*e_dr)[k] = e1; (*e_ur)[k] = e2;
+              total[w] += e1 + e2;
+            });
+        } else if (row + 1 < ly) {
           c.InitBTen2(LEFT, row);
           c.GrowFullBTen2(RIGHT, row, 2, true);
           for (size_t col = 0; col + 1 < lx; ++col) {
@@ -1647,6 +1726,11 @@ class SquareNNNModelMeasurementSolver {
     comp.SetOrder(COL_MAJOR);
     c.GenerateBMPSApproach(LEFT);
     for (size_t col = 0; col < lx; ++col) {
+      if (meas_slice) {
+        slice_bonds(VERTICAL, col, [&](size_t w, size_t row, TenElemT e) { e_v[w * (ly - 1) * lx + row * lx + col] = e; });
+        if (col + 1 < lx) c.ShiftBMPSWindow(RIGHT);
+        continue;
+      }
       c.InitBTen(UP, col);
       c.GrowFullBTen(DOWN, col, 2, true);
       psi_list.push_back(c.Trace({0, col}, VERTICAL));
@@ -1866,6 +1950,12 @@ class SquareSpinOneHalfXXZModelMixIn {
   TenElemT BondEnergyFromExchange(int32_t config1, int32_t config2, TenElemT ratio) const {
     return config1 == config2 ? TenElemT(0.25 * jz_) : TenElemT(-0.25 * jz_ + ratio * (0.5 * jxy_));
   }
+  // the diagonal-link term likewise (:107-134): what EvaluateNNNEnergy computes per walker
+  static constexpr bool kExchangeNNNEnergy = true;
+  template <typename TenElemT>
+  TenElemT NNNEnergyFromExchange(int32_t config1, int32_t config2, TenElemT ratio) const {
+    return config1 == config2 ? TenElemT(0.25 * jz2_) : TenElemT(-0.25 * jz2_ + ratio * (0.5 * jxy2_));
+  }
  protected:
   double jz_, jxy_, jz2_, jxy2_, pinning00_;
 };
@@ -1925,6 +2015,7 @@ class SpinOneHalfTriHeisenbergSqrPEPS : public SquareNNNModelEnergySolver<SpinOn
                                         public SquareSpinOneHalfXXZModelMixIn {
  public:
   SpinOneHalfTriHeisenbergSqrPEPS() : SquareSpinOneHalfXXZModelMixIn(1, 1, 1, 1, 0) {}
+  static constexpr int kNNNDiagMask = 2;              // only LEFTDOWN_TO_RIGHTUP interacts (:98-100): the other diagonal is exactly 0
   template <typename TenElemT>
   std::vector<TenElemT> EvaluateNNNEnergy(const SiteIdx &s1, const SiteIdx &s2, DIAGONAL_DIR diagonal_dir,
                                           TPSWaveFunctionComponentT<TenElemT> &comp, const std::vector<TenElemT> &inv_psi) {

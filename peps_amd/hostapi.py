@@ -54,7 +54,7 @@ def _ck(rc):
 
 
 MODEL_ID = {"xxz": 0, "tfim": 1, "j1j2": 2, "triangle": 3, "trij1j2": 4}   # params: xxz (jz, jxy, pinning00); tfim (h,); j1j2 (jz, jxy, jz2, jxy2, pinning00);
-# triangle (SpinOneHalfTriHeisenbergSqrPEPS: none; energy_and_holes / exact_sum_partial); trij1j2 (SpinOneHalfTriJ1J2HeisenbergSqrPEPS: (j2,);
+# triangle (SpinOneHalfTriHeisenbergSqrPEPS: none; energy_and_holes / exact_sum_partial / measure); trij1j2 (SpinOneHalfTriJ1J2HeisenbergSqrPEPS: (j2,);
 # energy_and_holes / exact_sum_partial / measure)
 
 

@@ -18,6 +18,7 @@
 #include "common.h"
 #include "linalg.h"
 #include "tgemm.h"
+#include "absorb_desc.h"
 #include "gram.h"
 #include "trunc_mid.h"
 #include "mgemm_dense.h"
@@ -1377,6 +1378,80 @@ class Engine : public EngineBase {
   BMPSDev absorb_simple(int pos, int num, const BMPSDev &in);   // engine_cplx.h
   BMPSDev absorb_svd(int pos, int num, const BMPSDev &in);
   bool absorb_impl(int pos, int num, bool full_bonds, const BMPSDev &in, BMPSDev &out);
+  // ---- the stages of one row absorption (engine_impl.h; complex element type: engine_cplx.h) ----
+  // What lives across the sites of one absorption.
+  struct AbsorbState {
+    int pos = 0, num = 0, N = 0;
+    bool full_bonds = false;             // no hint-sized bonds, no skipped launches (the redo of a failed attempt)
+    const BMPSDev *in = nullptr;
+    BMPSDev *out = nullptr;
+    int ll = 0, lp = 0, lr = 0, lu = 0;  // storage positions of the site legs: left, physical-side (absorbed), right, up
+    std::vector<DTen<T>> R;              // carry: R[i] enters site i
+    std::vector<int *> mdyn;             // live rows of R[i] = mdyn[i][w] * mmul[i] (nullptr: all rows)
+    std::vector<int> mmul;
+    std::vector<char> R_tri;             // R[i] is a Cholesky factor with compacted rows (row j zero before column j)
+    std::vector<int *> kn, clive;        // live sizes of the new bonds / of the bonds of the absorbing BMPS (per walker, device)
+    std::vector<int> cur_kmax, kstat, kfull;   // hint / static size chosen / full static size of each new bond
+    std::vector<int> assume_fused;       // per carry: the Gram + Cholesky fallback of the fused factor was not launched (hint)
+    std::vector<int> assume_rows;        // per site: the live-row cap the Jacobi launches relied on (0: none)
+    DTen<T> Y;                           // [l2, a2, k2]
+    float *yscale = nullptr;             // 1 / |Y| per walker when Y was left unnormalised by the launch that wrote it (y_scaled)
+    bool y_scaled = false;
+  };
+  // What a truncation route hands to the shared tail of truncate_site.  Ownership: a route frees every buffer it allocated
+  // before it returns, except the ones named here (and, for the mid route, in MidRoute between its two halves);
+  // truncate_site frees those once the launches that read them are issued.
+  struct TruncOut {
+    DTen<T> V;                  // the new tensor (k x u x k2), rows selected and normalised by whichever route took the walker
+    int *kn_i = nullptr;        // live size of the new bond per walker (nullptr: static)
+    int k = 0, k_full = 0;
+    int *route_flag = nullptr;  // f64 routes: < 0 = the walker was taken by the route
+    int *gen_rows = nullptr;    // ... live rows left for the general Jacobi (0 for the route's walkers)
+    int *select_skip = nullptr; // walkers (< 0) the general select leaves alone: the routes' own (f64) or midflag (f32 mid route)
+    int *early = nullptr, *fb_early = nullptr;   // f64 two-Cholesky route: the walkers whose general Jacobi runs on the side stream
+    bool sel_done = false;      // the short-row Jacobi selected its walkers itself
+    int *ortho_skip = nullptr;  // walkers (< 0) whose rows of V are orthonormal to float64 accuracy already (rows_qr.h)
+  };
+  // The f32 mid route between trunc_mid_prepare and trunc_mid_finish.
+  struct MidRoute {
+    bool on = false, two_level = false, pivoted = false, side_pending = false;
+    int MID_HI = 128, GS = 0;
+    int *midflag = nullptr, *nmid = nullptr, *mB = nullptr;
+    int *flagA = nullptr, *rowsA = nullptr, *flag2 = nullptr, *rows2 = nullptr, *mB2 = nullptr;   // two-level form
+    int *big_list = nullptr;    // walkers whose first factor kept more than 128 rows (+ their count behind the list)
+    DTen<T> Bt, B2;
+  };
+  static bool rank_adapt() { static const bool on = getenv("PEPSGPU_NO_RANK_ADAPT") == nullptr; return on; }
+  // error-budget experiments (scripts/error_budget.py): contractions of the f32 engine with float64 accumulation, by stage
+  // (1: X / P, 2: Z1 / Tt, 4: M = R Tt, 8: Y = Tt V^T; the separate LDS-tiled launches on the f64 matrix cores)
+  static int acc64_stages() {
+    static const int v = (sizeof(T) == 4 && getenv("PEPSGPU_ACC64")) ? atoi(getenv("PEPSGPU_ACC64")) : 0;
+    return v;
+  }
+  bool dbg_verbose() const { return dbg_sweeps_ && getenv("PEPSGPU_DEBUG_VERBOSE"); }
+  template <typename U> std::vector<U> dbg_read(const U *dev);
+  void absorb_begin(AbsorbState &s, int pos, int num, bool full_bonds, const BMPSDev &in, BMPSDev &out);
+  SiteDims absorb_site(const AbsorbState &s, int i) const;
+  DTen<T> forward_pair(AbsorbState &s, const SiteDims &d, int i);
+  void forward_factor(AbsorbState &s, const SiteDims &d, int i, DTen<T> P);
+  void forward_gram_chol(AbsorbState &s, const SiteDims &d, int i, DTen<T> &P, int *ml, bool fused);
+  bool precise_site(const AbsorbState &s, int i) const;
+  DTen<T> backward_pair(AbsorbState &s, const SiteDims &d, int i, bool tsw, bool tt_f64);
+  DTen<T> carry_times_tt(AbsorbState &s, const SiteDims &d, int i, const DTen<T> &Tt, bool tsw, bool &dense_site);
+  TruncOut truncate_site(AbsorbState &s, const SiteDims &d, int i, DTen<T> &M, bool precise);
+  MidRoute trunc_mid_prepare(AbsorbState &s, const SiteDims &d, int i, const DTen<T> &M);
+  void trunc_mid_two_level(MidRoute &mr, const int *hiflag, int i);
+  void trunc_mid_jacobi(MidRoute &mr);
+  void trunc_mid_finish(AbsorbState &s, const SiteDims &d, int i, const DTen<T> &M, MidRoute &mr, TruncOut &t);
+  bool trunc_mid_polish(const SiteDims &d, MidRoute &mr, TruncOut &t, DTen<T> &Vp, const int *kB);
+  void trunc_f64_pivot(AbsorbState &s, const SiteDims &d, int i, const DTen<T> &M, int kq, TruncOut &t);
+  void trunc_f64_two_chol(AbsorbState &s, const SiteDims &d, int i, const DTen<T> &M, int kq, TruncOut &t);
+  void trunc_jacobi(AbsorbState &s, const SiteDims &d, int i, DTen<T> &M, MidRoute &mr, TruncOut &t);
+  void next_y(AbsorbState &s, const SiteDims &d, int i, const DTen<T> &Tt, const TruncOut &t, bool tsw, bool dense_site, bool precise);
+  bool absorb_verify(AbsorbState &s);
+  // complex element type (engine_cplx.h)
+  int *trunc_c128_rangefinder(const SiteDims &d, const DTen<T> &M, int k, int kq, DTen<T> &V);
+  int *trunc_c128_two_chol(const SiteDims &d, int i, const DTen<T> &M, int k, int kq, DTen<T> &V);
   // ---- variational compression schemes (engine_var.h) ----
   BMPSDev absorb_variational(int pos, int num, const BMPSDev &in);
   BMPSDev truncate_bmps(const BMPSDev &in, int kmax);

@@ -96,32 +96,17 @@ def main():
         ("f64+floors_f32", capi.F64, {"PEPSGPU_F64_EPS": EPS32}),
         ("f64+round(all)+floors_f32", capi.F64, {"PEPSGPU_INJECT_F32": "SPRTMVYE", "PEPSGPU_F64_EPS": EPS32}),
         ("f32", capi.F32, {}),
-        ("f32 no ortho polish", capi.F32, {"PEPSGPU_ORTHO_POLISH": "0"}),
-        ("f32 Y f32 chain (round 3)", capi.F32, {"PEPSGPU_Y_ACC64": "0"}),
-        ("f32 round 3 (no ortho polish, Y f32 chain)", capi.F32, {"PEPSGPU_ORTHO_POLISH": "0", "PEPSGPU_Y_ACC64": "0"}),
         ("f32 acc64 X,P", capi.F32, {"PEPSGPU_ACC64": "1"}),
         ("f32 acc64 Z,Tt", capi.F32, {"PEPSGPU_ACC64": "2"}),
         ("f32 acc64 M", capi.F32, {"PEPSGPU_ACC64": "4"}),
         ("f32 acc64 Y", capi.F32, {"PEPSGPU_ACC64": "8"}),
         ("f32 acc64 all contractions", capi.F32, {"PEPSGPU_ACC64": "15"}),
-        ("f32 backward pair in f32 (round 4)", capi.F32, {"PEPSGPU_TT_ACC64": "0"}),
-        ("f32 Y on the wave-per-tile f64 body", capi.F32, {"PEPSGPU_Y_ACC64": "1"}),
         ("f32 acc64 X,P,Z,Tt", capi.F32, {"PEPSGPU_ACC64": "3"}),
         ("f32 acc64 Z,Tt,M", capi.F32, {"PEPSGPU_ACC64": "6"}),
         ("f32 acc64 X,P,Z,Tt,M", capi.F32, {"PEPSGPU_ACC64": "7"}),
-        ("f32 acc64 all, no ortho polish", capi.F32, {"PEPSGPU_ACC64": "15", "PEPSGPU_ORTHO_POLISH": "0"}),
-        ("f32 Y on the LDS-tiled f32 kernel", capi.F32, {"PEPSGPU_Y_TILED": "1"}),
-        ("f32 no fused norm", capi.F32, {"PEPSGPU_NO_FUSED_NORM": "1"}),
-        ("f32 no tt swap", capi.F32, {"PEPSGPU_NO_TT_SWAP": "1"}),
-        ("f32 no vector loads", capi.F32, {"PEPSGPU_TGEMM_NOVEC": "1"}),
-        ("f32 no hints/shrink", capi.F32, {"PEPSGPU_NO_RANK_HINT_SKIP": "1", "PEPSGPU_NO_BOND_SHRINK": "1"}),
-        ("f32 no two-level", capi.F32, {"PEPSGPU_NO_TWO_LEVEL": "1"}),
         ("f32 no mid route (Jacobi on M)", capi.F32, {"PEPSGPU_NO_MIDROUTE": "1"}),
-        ("f32 no mid route, no ortho polish", capi.F32, {"PEPSGPU_NO_MIDROUTE": "1", "PEPSGPU_ORTHO_POLISH": "0"}),
-        ("f32 no chain", capi.F32, {"PEPSGPU_NO_CHAIN": "1"}),
         ("f32 no rank adapt", capi.F32, {"PEPSGPU_NO_RANK_ADAPT": "1"}),
         ("f32 Grams on the f64 matrix cores (no i8)", capi.F32, {"PEPSGPU_NO_I8_GRAM": "1"}),
-        ("f32 i8 column Gram only", capi.F32, {"PEPSGPU_NO_I8_ROWGRAM": "1"}),
     ]
     if args.only:
         want = set(args.only.split(";"))

@@ -193,10 +193,37 @@ int pepsgpu_onsite_slice(pepsgpu_ctx *ctx, int orientation, int slice, int punch
  * The BTen2 stacks end as the per-plaquette calls leave them.  Status PEPSGPU_EINVAL: row1 outside [0, rows - 2], diag_mask outside 1..3,
  * a NULL buffer; PEPSGPU_ESTATE: a boundary MPS of the row pair is missing, or a configuration override (pepsgpu_cfg_override_slice) is
  * active -- the slice reads the walkers' own configuration table, i.e. it serves bosonic configurations of every element type; the
- * fermionic diagonal hop keeps the per-plaquette calls.  A refused call leaves the context usable. */
+ * fermionic diagonal hop has its own slice, pepsgpu_nnn_hop_slice_fermion.  A refused call leaves the context usable. */
 int pepsgpu_nnn_exchange_slice(pepsgpu_ctx *ctx, int row1, int diag_mask, double *val_out);
 /* Completed pepsgpu_nnn_exchange_slice calls of this process (all contexts): lets a caller prove which path computed its numbers. */
 long pepsgpu_diag_nnn_slice_calls(void);
+/* The diagonal hops of the row pair (row1, row1 + 1) of a FERMIONIC state on the device, every element type (square_spinless_fermion.h:
+ * 161-200, square_tJ_model.h:424-463).  The walkers' configurations are extended states e = s + d * variant in row-major order (variant
+ * 0 / 1), the context's physical dimension is 4 d; occ [d] (0 / 1) is the fermion number of each physical state.  A hop along a diagonal
+ * exchanges the physical states of its two ends and flips the variant of every site between them in row-major order, so the hopped
+ * amplitude is a replacement of the four plaquette tensors against twisted environments.  In order: BTen2 set 0 gets GrowFullBTen2(RIGHT,
+ * row1, 2, true) and InitBTen2(LEFT, row1); set 1 gets the RIGHT chain grown with row row1 variant-flipped and the LEFT chain with row
+ * row1 + 1 variant-flipped; per plaquette psi comes from the walkers' own four states between the set-0 environments and the hopped
+ * amplitude of each requested diagonal from the hopped states between the set-1 environments; then both LEFT chains advance one column.
+ * ONE read-back, no upload: the flipped tables, the candidates and the signs are built on the device.
+ *   diag_mask  as for pepsgpu_nnn_exchange_slice;
+ *   psi_out    [n][cols - 1] (PEPSGPU_C128: interleaved (re, im)): psi of plaquette c along the same contraction path; 0.0 for a plaquette
+ *              where no walker has an allowed hop on a requested diagonal (it only advances the chains);
+ *   val_out    [n][cols - 1][2]: jw * psi' of diagonal `kind` of plaquette c, jw = (-1)^(fermions strictly between the two ends in row-major
+ *              order) already applied; 0.0 for a diagonal outside the mask and for a forbidden hop, occ[state_a] == occ[state_b].
+ * On return, and after any error, BTen2 set 0 is selected and no configuration override is active; the BMPS stacks are untouched.
+ * Status PEPSGPU_EINVAL: row1 outside [0, rows - 2], diag_mask outside 1..3, a NULL buffer, 4 * d != the context's physical dimension, an
+ * occ entry outside {0, 1}; PEPSGPU_ESTATE: a boundary MPS of the row pair is missing, a configuration override or BTen2 set 1 is
+ * active on entry, or a state of variant >= 2 (a column-major table) in either row.  A refused call leaves the context usable. */
+int pepsgpu_nnn_hop_slice_fermion(pepsgpu_ctx *ctx, int row1, int d, const int32_t *occ, int diag_mask, double *psi_out, double *val_out);
+/* Completed pepsgpu_nnn_hop_slice_fermion calls of this process (all contexts). */
+long pepsgpu_diag_nnn_hop_slice_calls(void);
+/* The candidate kernel of pepsgpu_nnn_hop_slice_fermion alone, on the caller's extended configurations ext [n][rows][cols] (states in
+ * [0, 2 d)) for the plaquette (row1, col1): cand_out [n][2][4] the hopped extended states of (row1, col1), (row1 + 1, col1),
+ * (row1 + 1, col1 + 1), (row1, col1 + 1) for LEFTUP_TO_RIGHTDOWN and LEFTDOWN_TO_RIGHTUP; sign_out [n][2] = +1 / -1, 0 for a forbidden
+ * hop; flag_out [n][2] = -1 where the hop is allowed, else 1 (the skip-flag convention of the slice).  Needs a device, no context. */
+int pepsgpu_diag_fermion_hop_cand(int rows, int cols, int d, const int32_t *occ, int n, const int32_t *ext, int row1, int col1,
+                                  int32_t *cand_out, int32_t *sign_out, int32_t *flag_out);
 
 /* BMPSWalker as an object -- BMPSContractor::GetWalker / class BMPSWalker, bmps_contractor.h:357-646, bmps/impl/bmps_walker.h:13-465.
  * A walker holds the fork of the top BMPS of stack `pos` for every Monte-Carlo walker of the context (deep copy; the stacks are not

@@ -26,7 +26,7 @@ SYMBOLS = [
     "pepsgpu_walkers_set_configs", "pepsgpu_walkers_get_configs", "pepsgpu_n_walkers",
     "pepsgpu_grow_bmps_step", "pepsgpu_grow_full_bmps", "pepsgpu_grow_bmps_for_row", "pepsgpu_grow_bmps_for_col",
     "pepsgpu_shift_bmps_window", "pepsgpu_delete_inner_bmps", "pepsgpu_bmps_park", "pepsgpu_bmps_unpark", "pepsgpu_generate_bmps_approach",
-    "pepsgpu_sweep_slice_exchange", "pepsgpu_sweep_slice_exchange_tab", "pepsgpu_sweep_slice_fullspace", "pepsgpu_sweep_slice_tnn3", "pepsgpu_diag_tnn3_table", "pepsgpu_nn_exchange_slice", "pepsgpu_nn_exchange_slice_tab", "pepsgpu_onsite_slice", "pepsgpu_nnn_exchange_slice", "pepsgpu_diag_nnn_slice_calls", "pepsgpu_walker_create", "pepsgpu_walker_clone", "pepsgpu_walker_destroy", "pepsgpu_walker_info", "pepsgpu_walker_set_mpo", "pepsgpu_walker_evolve",
+    "pepsgpu_sweep_slice_exchange", "pepsgpu_sweep_slice_exchange_tab", "pepsgpu_sweep_slice_fullspace", "pepsgpu_sweep_slice_tnn3", "pepsgpu_diag_tnn3_table", "pepsgpu_nn_exchange_slice", "pepsgpu_nn_exchange_slice_tab", "pepsgpu_onsite_slice", "pepsgpu_nnn_exchange_slice", "pepsgpu_diag_nnn_slice_calls", "pepsgpu_nnn_hop_slice_fermion", "pepsgpu_diag_nnn_hop_slice_calls", "pepsgpu_diag_fermion_hop_cand", "pepsgpu_walker_create", "pepsgpu_walker_clone", "pepsgpu_walker_destroy", "pepsgpu_walker_info", "pepsgpu_walker_set_mpo", "pepsgpu_walker_evolve",
     "pepsgpu_walker_evolve_step", "pepsgpu_walker_contract_row", "pepsgpu_walker_init_bten", "pepsgpu_walker_grow_bten_step",
     "pepsgpu_walker_shift_bten_window", "pepsgpu_walker_trace_with_bten", "pepsgpu_walker_clear_bten", "pepsgpu_walker_get_bmps_tensor",
     "pepsgpu_bmps_stack_size", "pepsgpu_get_bmps_tensor", "pepsgpu_init_bten", "pepsgpu_grow_full_bten",
@@ -110,6 +110,10 @@ def load_library(path=LIB_PATH):
     lib.pepsgpu_nnn_exchange_slice.argtypes = [vp, C.c_int, C.c_int, dp]
     lib.pepsgpu_diag_nnn_slice_calls.argtypes = []
     lib.pepsgpu_diag_nnn_slice_calls.restype = C.c_long
+    lib.pepsgpu_nnn_hop_slice_fermion.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int, dp, dp]
+    lib.pepsgpu_diag_nnn_hop_slice_calls.argtypes = []
+    lib.pepsgpu_diag_nnn_hop_slice_calls.restype = C.c_long
+    lib.pepsgpu_diag_fermion_hop_cand.argtypes = [C.c_int, C.c_int, C.c_int, ip, C.c_int, ip, C.c_int, C.c_int, ip, ip, ip]
     lib.pepsgpu_diag_dot4.argtypes = [C.c_int, vp, vp, ip, C.c_int, dp, ip, dp]
     lib.pepsgpu_onsite_slice.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, dp, dp]
     lib.pepsgpu_walker_create.argtypes = [vp, C.c_int, C.c_int, ip]
@@ -369,6 +373,17 @@ class Context:
         val = np.zeros((self.n, self.cols - 1, 2), dtype=self._ot)
         self._ck(self._l.pepsgpu_nnn_exchange_slice(self._h, row1, diag_mask, _dp(val)))
         return val
+
+    def nnn_hop_slice_fermion(self, row1, nf, diag_mask=3):
+        """the diagonal hops of the row pair (row1, row1 + 1) of a fermionic state (extended row-major configurations; nf [d] the
+        fermion number of each physical state, 4 d = the context's physical dimension): (psi [n][cols - 1], val [n][cols - 1][2]) with
+        val = jw psi' of each diagonal (kind 0 LEFTUP_TO_RIGHTDOWN, kind 1 LEFTDOWN_TO_RIGHTUP), 0 for a masked-off diagonal and a
+        forbidden hop (equal occupation at the two ends); psi is 0 for a plaquette without any allowed hop; one read-back"""
+        occ = np.ascontiguousarray(nf, dtype=np.int32)
+        psi = np.zeros((self.n, self.cols - 1), dtype=self._ot)
+        val = np.zeros((self.n, self.cols - 1, 2), dtype=self._ot)
+        self._ck(self._l.pepsgpu_nnn_hop_slice_fermion(self._h, row1, occ.size, _ip(occ), diag_mask, _dp(psi), _dp(val)))
+        return psi, val
 
     def onsite_slice(self, orientation, slice_num, site_table, punch_holes=False):
         """one-site moves along a row / column: site_table [d][n_cand] (candidate k of state s); returns (psi [n],
@@ -933,6 +948,24 @@ def diag_suwa_todo(weights, init, words):
     if rc != 0:
         raise RuntimeError("diag_suwa_todo failed: %s" % lib().pepsgpu_last_error(None).decode())
     return out
+
+
+def diag_nnn_hop_slice_calls():
+    """completed pepsgpu_nnn_hop_slice_fermion calls of this process"""
+    return int(lib().pepsgpu_diag_nnn_hop_slice_calls())
+
+
+def diag_fermion_hop_cand(ext, nf, row1, col1):
+    """nnn_hop_cand_kernel alone: ext [n][rows][cols] extended row-major configurations, nf [d]; returns (cand [n][2][4], sign [n][2],
+    flag [n][2]) of the plaquette (row1, col1), entry 0 LEFTUP_TO_RIGHTDOWN, entry 1 LEFTDOWN_TO_RIGHTUP"""
+    e = np.ascontiguousarray(ext, dtype=np.int32)
+    occ = np.ascontiguousarray(nf, dtype=np.int32)
+    n, rows, cols = e.shape
+    cand, sign, flag = np.zeros((n, 2, 4), dtype=np.int32), np.zeros((n, 2), dtype=np.int32), np.zeros((n, 2), dtype=np.int32)
+    rc = lib().pepsgpu_diag_fermion_hop_cand(rows, cols, occ.size, _ip(occ), n, _ip(e), row1, col1, _ip(cand), _ip(sign), _ip(flag))
+    if rc != 0:
+        raise ValueError("diag_fermion_hop_cand: status %d" % rc)
+    return cand, sign, flag
 
 
 def diag_nnn_slice_calls():

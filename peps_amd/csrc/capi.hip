@@ -171,6 +171,44 @@ int pepsgpu_nnn_exchange_slice(pepsgpu_ctx *ctx, int row1, int diag_mask, double
   CTX_CALL(PG_REQUIRE(val_out, 1, "null buffer"); ctx->eng->nnn_exchange_slice(row1, diag_mask, val_out));
 }
 long pepsgpu_diag_nnn_slice_calls(void) { return pepsgpu::nnn_slice_calls().load(); }
+// square_spinless_fermion.h:161-200 / square_tJ_model.h:424-463: the diagonal hops of one row pair of a fermionic state
+int pepsgpu_nnn_hop_slice_fermion(pepsgpu_ctx *ctx, int row1, int d, const int32_t *occ, int diag_mask, double *psi_out, double *val_out) {
+  CTX_CALL(PG_REQUIRE(occ && psi_out && val_out, 1, "null buffer");
+           ctx->eng->nnn_hop_slice_fermion(row1, d, occ, diag_mask, psi_out, val_out));
+}
+long pepsgpu_diag_nnn_hop_slice_calls(void) { return pepsgpu::nnn_hop_slice_calls().load(); }
+// nnn_hop_cand_kernel alone on a caller's extended configurations ext [n][rows][cols] (row-major variants 0 / 1), for the plaquette
+// (row1, col1): cand_out [n][2][4], sign_out [n][2], flag_out [n][2], entry 0 LEFTUP_TO_RIGHTDOWN, entry 1 LEFTDOWN_TO_RIGHTUP
+int pepsgpu_diag_fermion_hop_cand(int rows, int cols, int d, const int32_t *occ, int n, const int32_t *ext, int row1, int col1,
+                                  int32_t *cand_out, int32_t *sign_out, int32_t *flag_out) {
+  return guarded(nullptr, [&]() {
+    PG_REQUIRE(occ && ext && cand_out && sign_out && flag_out, 1, "null buffer");
+    PG_REQUIRE(rows >= 2 && cols >= 2 && d >= 1 && d <= 32 && n >= 1 && (double)n * rows * cols < 2147483648.0, 1, "bad sizes");
+    PG_REQUIRE(row1 >= 0 && row1 + 1 < rows && col1 >= 0 && col1 + 1 < cols, 1, "plaquette outside the lattice");
+    unsigned occ_bits = 0;
+    for (int s = 0; s < d; ++s) {
+      PG_REQUIRE(occ[s] == 0 || occ[s] == 1, 1, "occupation numbers must be 0 or 1");
+      occ_bits |= (unsigned)occ[s] << s;
+    }
+    const int sites = rows * cols;
+    const size_t ne = (size_t)n * sites;
+    for (size_t e = 0; e < ne; ++e) PG_REQUIRE(ext[e] >= 0 && ext[e] < 2 * d, 1, "extended state outside [0, 2 d)");
+    int *dcfg, *dout;
+    PG_CHECK_HIP(hipMalloc(&dcfg, ne * sizeof(int)));
+    PG_CHECK_HIP(hipMalloc(&dout, 12 * (size_t)n * sizeof(int)));
+    int *dc = dout, *ds = dout + 8 * (size_t)n, *df = dout + 10 * (size_t)n;
+    PG_CHECK_HIP(hipMemcpy(dcfg, ext, ne * sizeof(int), hipMemcpyHostToDevice));
+    const int s0 = row1 * cols + col1, s1 = s0 + cols, s2 = s1 + 1, s3 = s0 + 1;
+    hipLaunchKernelGGL(nnn_hop_cand_kernel, dim3((2 * n + 255) / 256), dim3(256), 0, 0, (const int *)dcfg, sites, s0, s1, s2, s3, d, occ_bits,
+                       2, (int)LEFTUP_TO_RIGHTDOWN, (int)LEFTDOWN_TO_RIGHTUP, (int *)nullptr, dc, df, ds, 2L, n);
+    PG_CHECK_HIP(hipGetLastError());
+    PG_CHECK_HIP(hipDeviceSynchronize());
+    PG_CHECK_HIP(hipMemcpy(cand_out, dc, 8 * (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    PG_CHECK_HIP(hipMemcpy(sign_out, ds, 2 * (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    PG_CHECK_HIP(hipMemcpy(flag_out, df, 2 * (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    (void)hipFree(dcfg); (void)hipFree(dout);
+  });
+}
 int pepsgpu_walker_create(pepsgpu_ctx *ctx, int pos, int level, int *walker_out) {
   CTX_CALL(check_pos(pos); PG_REQUIRE(walker_out != nullptr, 1, "null output"); *walker_out = ctx->eng->walker_create(pos, level));
 }

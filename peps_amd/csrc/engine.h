@@ -131,6 +131,7 @@ struct EngineBase {
                                  double *psi_out, double *val_out) = 0;
   // the diagonal bonds of the row pair (row1, row1 + 1) (square_nnn_energy_solver.h:203-265); engine_sweep.h
   virtual void nnn_exchange_slice(int row1, int diag_mask, double *val_out) = 0;
+  virtual void nnn_hop_slice_fermion(int row1, int d, const int32_t *occ, int diag_mask, double *psi_out, double *val_out) = 0;
   // BMPSWalker (bmps_contractor.h:357-646)
   virtual int walker_create(int pos, int level) = 0;
   virtual int walker_clone(int id) = 0;
@@ -970,6 +971,7 @@ class Engine : public EngineBase {
   void energy_slice_impl(int mode, int orient, int slice, int punch_holes, const int32_t *table, int n_cand, int psi_per_bond,
                          double *psi_out, double *val_out) override;
   void nnn_exchange_slice(int row1, int diag_mask, double *val_out) override;
+  void nnn_hop_slice_fermion(int row1, int d, const int32_t *occ, int diag_mask, double *psi_out, double *val_out) override;
   // the parts the slice functions share (engine_sweep.h)
   void begin_slice(const SliceGeom &g, int remain);
   template <typename Moves>

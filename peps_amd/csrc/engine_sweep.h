@@ -497,6 +497,200 @@ void Engine<T>::nnn_exchange_slice(int row1, int diag_mask, double *val_out) {
   nnn_slice_calls() += 1;
 }
 
+// ---- the fermionic diagonal hop of a row pair (square_spinless_fermion.h:161-200, square_tJ_model.h:424-463) ----
+// A fermionic state lives on the device as extended states e = s + d v: physical state s, variant v = parity of the fermion count up
+// to and including the site in row-major order (pepsgpu.h).  The hop along a plaquette diagonal exchanges the physical states of its
+// two ends; the variants of the four plaquette sites under the hopped configuration follow from the four extended states alone.
+// e0 .. e3 = the states of (r, c), (r+1, c), (r+1, c+1), (r, c+1), n_k = occ bit of s_k:
+//   before0 = v0 ^ n0          fermions strictly before (r, c)
+//   mid     = (v1 ^ n1) ^ v3   fermions strictly between (r, c+1) and (r+1, c): the rest of row r and the start of row r+1
+// and with the hopped states s', n' = occ(s'): v0' = before0 ^ n0', v3' = v0' ^ n3', v1' = v3' ^ mid ^ n1', v2' = v1' ^ n2'.
+// Jordan-Wigner sign of the hop: (r, c) <-> (r+1, c+1) crosses (r, c+1) .. (r+1, c), (-1)^(v0 ^ v1); (r+1, c) <-> (r, c+1) crosses
+// the sites between them, (-1)^mid.  The variants of every OTHER site between the two ends flip: the twisted environments of
+// nnn_hop_slice_fermion.
+// own[w][4] = e0 .. e3 (optional); per entry (w, q), kind = q ? kind1 : kind0: cand[w][q][4] the hopped extended states, flag[w][q] = -1
+// where the hop is allowed (occ differs at the two ends; batch_flag convention: -1 has work) else 1, sign[w * sign_stride + kind] =
+// +1 / -1 / 0 (forbidden).
+__global__ void nnn_hop_cand_kernel(const int *__restrict__ cfg, int sites, int s0, int s1, int s2, int s3, int d, unsigned occ_bits,
+                                    int nc, int kind0, int kind1, int *__restrict__ own, int *__restrict__ cand, int *__restrict__ flag,
+                                    int *__restrict__ sign, long sign_stride, int n) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n * nc) return;
+  const int w = e / nc, q = e - w * nc, kind = q ? kind1 : kind0;
+  const long cw = (long)w * sites;
+  const int e0 = cfg[cw + s0], e1 = cfg[cw + s1], e2 = cfg[cw + s2], e3 = cfg[cw + s3];
+  if (own && q == 0) { int *o = own + 4 * (long)w; o[0] = e0; o[1] = e1; o[2] = e2; o[3] = e3; }
+  const int p0 = e0 % d, p1 = e1 % d, p2 = e2 % d, p3 = e3 % d;
+  const int v0 = (e0 / d) & 1, v1 = (e1 / d) & 1, v3 = (e3 / d) & 1;
+  auto occ = [&](int s) { return (int)((occ_bits >> s) & 1u); };
+  const int before0 = v0 ^ occ(p0), mid = (v1 ^ occ(p1)) ^ v3;
+  const bool lurd = kind == LEFTUP_TO_RIGHTDOWN;
+  const int h0 = lurd ? p2 : p0, h1 = lurd ? p1 : p3, h2 = lurd ? p0 : p2, h3 = lurd ? p3 : p1;
+  const int w0 = before0 ^ occ(h0), w3 = w0 ^ occ(h3), w1 = w3 ^ mid ^ occ(h1), w2 = w1 ^ occ(h2);
+  int *c = cand + 4 * (long)e;
+  c[0] = h0 + d * w0; c[1] = h1 + d * w1; c[2] = h2 + d * w2; c[3] = h3 + d * w3;
+  const bool allowed = lurd ? occ(p0) != occ(p2) : occ(p1) != occ(p3);
+  flag[e] = allowed ? -1 : 1;
+  const int par = lurd ? (v0 ^ v1) : mid;
+  sign[(long)w * sign_stride + kind] = allowed ? (par ? -1 : 1) : 0;
+}
+
+// dst = the configuration table with the variant of every site of row `row` flipped: e -> e + d if e / d == 0, else e - d
+__global__ void nnn_flip_row_kernel(const int *__restrict__ cfg, int *__restrict__ dst, int sites, int Lx, int row, int d, int n) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long)n * sites) return;
+  const int s = (int)(e % sites), v = cfg[e];
+  dst[e] = (s / Lx == row) ? (v / d == 0 ? v + d : v - d) : v;
+}
+
+// val[e] *= sign[e] over the value table of the hop slice (complex: both components); sign 0 entries are zeros already
+__global__ void nnn_hop_sign_kernel(double *__restrict__ val, const int *__restrict__ sign, int ko, long n) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  if (sign[e] < 0)
+    for (int z = 0; z < ko; ++z) val[e * ko + z] = -val[e * ko + z];
+}
+
+inline std::atomic<long> &nnn_hop_slice_calls() {   // completed nnn_hop_slice_fermion calls of the process
+  static std::atomic<long> n{0};
+  return n;
+}
+
+// One row pair of the fermionic diagonal hop on the device: the body of the row loop of the host's AddNNNHopEnergyLocal
+// (peps_amd/host/qlpeps_gpu.h) with ONE read-back at the end and no upload.
+//   set 0: GrowFullBTen2(RIGHT, row1, 2, true), InitBTen2(LEFT, row1) under the walkers' own configurations;
+//   set 1: the RIGHT chain with row row1 variant-flipped, the LEFT chain with row row1 + 1 variant-flipped (the two flipped tables are
+//   built once by nnn_flip_row_kernel; switching what the site picks read is a pointer change);
+//   per plaquette psi from the walkers' own four states between the set-0 LEFT and RIGHT, jw psi' of each requested diagonal from
+//   the hopped states (nnn_hop_cand_kernel) between the set-1 LEFT and RIGHT, closed by trace_dot4_kernel into the tables; then both
+//   LEFT chains advance one column.
+// A diagonal that is masked off or forbidden for every walker (host mirror) is no candidate; a plaquette without candidates only
+// advances the chains and keeps psi_out = 0.  psi_out [n][Lx - 1], val_out [n][Lx - 1][2] (complex: interleaved).
+// On return and on any error set 0 is selected and no override is active; set 1 keeps the twisted chains of this row pair.
+template <typename T>
+void Engine<T>::nnn_hop_slice_fermion(int row1, int d, const int32_t *occ, int diag_mask, double *psi_out, double *val_out) {
+  require_ready();
+  PG_REQUIRE(psi_out && val_out && occ, 1, "null buffer");
+  PG_REQUIRE(row1 >= 0 && row1 + 1 < Ly_ && Lx_ >= 2, 1, "hop slice: row pair outside the lattice");
+  PG_REQUIRE(diag_mask >= 1 && diag_mask <= 3, 1, "hop slice: diag_mask must be 1, 2 or 3");
+  PG_REQUIRE(d >= 1 && d <= 32 && 4 * d == dp_, 1, "hop slice: the context's physical dimension must be 4 d (extended states), d <= 32");
+  unsigned occ_bits = 0;
+  for (int s = 0; s < d; ++s) {
+    PG_REQUIRE(occ[s] == 0 || occ[s] == 1, 1, "hop slice: occupation numbers must be 0 or 1");
+    occ_bits |= (unsigned)occ[s] << s;
+  }
+  PG_REQUIRE(!ovr_on_ && bten2_active_ == 0, 3, "hop slice: a configuration override or the second BTen2 set is active");
+  const int row2 = row1 + 1, sites = Ly_ * Lx_, np = Lx_ - 1;
+  (void)bmps_at_slice(UP, row1);                                              // (status 3 before anything is touched)
+  (void)bmps_at_slice(DOWN, row2);
+  for (int w = 0; w < nw_; ++w)
+    for (int r = row1; r <= row2; ++r)
+      for (int c = 0; c < Lx_; ++c)
+        PG_REQUIRE(hcfg_[(size_t)w * sites + r * Lx_ + c] / d < 2, 3, "hop slice: column-major extended states (variant >= 2) in the row pair");
+  auto hocc = [&](int w, int s) { return (occ_bits >> (hcfg_[(size_t)w * sites + s] % d)) & 1u; };
+  const size_t npsi = (size_t)kOut * nw_ * np, nval = 2 * npsi;
+  ArenaBuf<double> dval(arena_, npsi + nval);                                 // psi [n][np], then val [n][np][2]
+  double *dpsi = dval, *dhop = dval + npsi;
+  ArenaBuf<int> dflip(arena_, 2 * (size_t)nw_ * sites);                       // the table with row1 flipped, with row2 flipped
+  int *flip0 = dflip, *flip1 = dflip + (size_t)nw_ * sites;
+  ArenaBuf<int> dcand(arena_, 14 * (size_t)nw_ + 2 * (size_t)nw_ * np);       // own [n][4], candidates [n][2][4], flags [n][2], signs [n][np][2]
+  int *down = dcand, *dhcand = dcand + 4 * (size_t)nw_, *dflag = dcand + 12 * (size_t)nw_, *dsign = dcand + 14 * (size_t)nw_;
+  PG_CHECK_HIP(hipMemsetAsync(dval, 0, sizeof(double) * (npsi + nval), stream_));
+  PG_CHECK_HIP(hipMemsetAsync(dsign, 0, sizeof(int) * 2 * (size_t)nw_ * np, stream_));
+  {
+    const long ne = (long)nw_ * sites;
+    const unsigned gf = (unsigned)((ne + 255) / 256);
+    hipLaunchKernelGGL(nnn_flip_row_kernel, dim3(gf), dim3(256), 0, stream_, (const int *)cfg_, flip0, sites, Lx_, row1, d, nw_);
+    hipLaunchKernelGGL(nnn_flip_row_kernel, dim3(gf), dim3(256), 0, stream_, (const int *)cfg_, flip1, sites, Lx_, row2, d, nw_);
+    PG_CHECK_HIP(hipGetLastError());
+  }
+  struct Restore {
+    Engine<T> &e;
+    ~Restore() {
+      e.ovr_on_ = false; e.ovr_cfg_ = nullptr;
+      if (e.bten2_active_ != 0) { for (int p = 0; p < 4; ++p) std::swap(e.bten2_[p], e.bten2_inactive_[p]); e.bten2_active_ = 0; }
+    }
+  } restore{*this};
+  // BTen2 set `set` active, row `row` read from `tab` (nullptr: the walkers' own table everywhere)
+  auto use = [&](int set, const int *tab, int row) {
+    bten2_select_set(set);
+    ovr_on_ = tab != nullptr; ovr_hor_ = true; ovr_num_ = row; ovr_cfg_ = tab; ovr_tens_ = nullptr; ovr_nt_ = 0;
+  };
+  use(0, nullptr, -1);
+  grow_full_bten2(RIGHT, row1, 2, 1);
+  init_bten2(LEFT, row1);
+  use(1, flip0, row1);
+  grow_full_bten2(RIGHT, row1, 2, 1);
+  use(1, flip1, row2);
+  init_bten2(LEFT, row1);
+  for (int col1 = 0; col1 < np; ++col1) {
+    const int col2 = col1 + 1;
+    const int s0 = row1 * Lx_ + col1, s1 = row2 * Lx_ + col1, s2 = row2 * Lx_ + col2, s3 = row1 * Lx_ + col2;
+    int kinds[2] = {0, 0}, nc = 0;
+    for (int kind = 0; kind < 2; ++kind) {
+      if (!((diag_mask >> kind) & 1)) continue;
+      const int sa = kind == LEFTUP_TO_RIGHTDOWN ? s0 : s1, sb = kind == LEFTUP_TO_RIGHTDOWN ? s2 : s3;
+      bool any = false;
+      for (int w = 0; w < nw_ && !any; ++w) any = hocc(w, sa) != hocc(w, sb);
+      if (any) kinds[nc++] = kind;
+    }
+    if (nc > 0) {      // (set 1 is the active one here)
+      ArenaScope scope(arena_);
+      const int nb = nw_ * nc, kr = Lx_ - 1 - col2;
+      hipLaunchKernelGGL(nnn_hop_cand_kernel, dim3((nb + 255) / 256), dim3(256), 0, stream_, (const int *)cfg_, sites, s0, s1, s2, s3, d,
+                         occ_bits, nc, kinds[0], kinds[nc - 1], down, dhcand, dflag, dsign + 2 * col1, (long)np * 2, nw_);
+      PG_CHECK_HIP(hipGetLastError());
+      const BMPSDev &up = bmps_at_slice(UP, row1), &dn = bmps_at_slice(DOWN, row2);
+      const SitePick t0{row1, col1, 0}, t1{row2, col1, 1}, t2{row2, col2, 2}, t3{row1, col2, 3};
+      for (int set = 0; set < 2; ++set) {
+        const std::vector<BTenDev> &ls = (set == bten2_active_ ? bten2_ : bten2_inactive_)[LEFT];
+        const std::vector<BTenDev> &rs = (set == bten2_active_ ? bten2_ : bten2_inactive_)[RIGHT];
+        PG_REQUIRE((int)ls.size() > col1 && kr >= 0 && kr < (int)rs.size(), 3, "hop slice: BTen2 environment missing");
+        const BTenDev &lb = ls[col1], &rb = rs[kr];
+        const int *tab = set == 0 ? down : dhcand, *fl = set == 0 ? nullptr : dflag;
+        const int ncs = set == 0 ? 1 : nc;
+        double *lsum = zeros_f64();
+        BTenDev a = bten2_step(LEFT, lb, at_logical(up, UP, col1), pick(t0, tab, 4), pick(t1, tab, 4), at_logical(dn, DOWN, col1), ncs, 1,
+                               false, fl);
+        BTenDev b = bten2_step(RIGHT, rb, at_logical(dn, DOWN, col2), pick(t2, tab, 4), pick(t3, tab, 4), at_logical(up, UP, col2), ncs, 1,
+                               false, fl);
+        add_logs(lsum, up.logscale, dn.logscale, lb.logscale, rb.logscale);
+        PG_REQUIRE(a.t.d[0] == b.t.d[3] && a.t.d[1] == b.t.d[2] && a.t.d[2] == b.t.d[1] && a.t.d[3] == b.t.d[0], 3,
+                   "trace: two-row environment bond mismatch");
+        if (set == 0)
+          hipLaunchKernelGGL((trace_dot4_kernel<T, Acc>), dim3(nw_), dim3(256), 0, stream_, (const T *)a.t.p, (const T *)b.t.p, a.t.n,
+                             a.t.d[0], a.t.d[1], a.t.d[2], a.t.d[3], (const double *)lsum, (const int *)nullptr, 1, 0, 0, (long)np,
+                             dpsi + (size_t)kOut * col1);
+        else
+          hipLaunchKernelGGL((trace_dot4_kernel<T, Acc>), dim3(nb), dim3(256), 0, stream_, (const T *)a.t.p, (const T *)b.t.p, a.t.n,
+                             a.t.d[0], a.t.d[1], a.t.d[2], a.t.d[3], (const double *)lsum, (const int *)dflag, nc, kinds[0], kinds[nc - 1],
+                             (long)np * 2, dhop + (size_t)kOut * 2 * col1);
+        PG_CHECK_HIP(hipGetLastError());
+        free_ten(a.t); free_ten(b.t);
+        arena_.free(lsum);
+      }
+    }
+    if (col1 + 2 < Lx_) {      // both LEFT chains advance over column col1 (set 1 under the flipped row row2)
+      grow_bten2_step(LEFT, row1);
+      use(0, nullptr, -1);
+      grow_bten2_step(LEFT, row1);
+      use(1, flip1, row2);
+    }
+  }
+  use(0, nullptr, -1);
+  {
+    const long ne = (long)nw_ * np * 2;
+    hipLaunchKernelGGL(nnn_hop_sign_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream_, dhop, (const int *)dsign, kOut, ne);
+    PG_CHECK_HIP(hipGetLastError());
+  }
+  std::vector<double> h(npsi + nval);
+  PG_CHECK_HIP(hipMemcpyAsync(h.data(), dval, sizeof(double) * h.size(), hipMemcpyDeviceToHost, stream_));
+  PG_CHECK_HIP(hipStreamSynchronize(stream_));
+  std::copy(h.begin(), h.begin() + npsi, psi_out);
+  std::copy(h.begin() + npsi, h.end(), val_out);
+  nnn_hop_slice_calls() += 1;
+}
+
 // ---- three-site exchange (MCUpdateSquareTNN3SiteExchange::TNN3SiteUpdateImpl, square_3site_updater.h:109-158) ----
 // Triple table [dp^3][TNN3_TAB]: entry e1 dp^2 + e2 dp + e3 holds m (the number of distinct permutations of the triple: 1, 3 or 6),
 // init (the position of the triple itself among them) and six slots of three states, the permutations in std::next_permutation order

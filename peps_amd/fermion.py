@@ -199,16 +199,20 @@ def evaluate_amplitude(ctx, state, configs):
     return state.sigma(configs) * ctx.evaluate_amplitude()
 
 
-def tj_energy(ctx, state, configs, t, J, V=0.0, mu=0.0):
-    """E_loc(S) of the t-J-V model (square_tJ_model.h:301-345 + :215-228; states 0 up, 1 down, 2 empty):
-    H = -t sum (c+ c + h.c.) + J sum (S.S - n n / 4) + V sum n n - mu N, nearest neighbours only (t2 = 0)."""
+def tj_energy(ctx, state, configs, t, J, V=0.0, mu=0.0, t2=0.0, bonds=None, nnn="slice"):
+    """E_loc(S) of the t-t'-J-V model (square_tJ_model.h:301-345, :424-463 + :215-228; states 0 up, 1 down, 2 empty):
+    H = -t sum_<ij> (c+ c + h.c.) - t2 sum_<<ij>> (c+ c + h.c.) + J sum (S.S - n n / 4) + V sum n n - mu N.  The diagonal hop moves an
+    electron into a hole (never exchanges two spins); nnn names its path as in spinless_fermion_energy.  `bonds` (a dict) receives
+    the per-bond energies "h", "v" and, with t2, "dr" / "ur"."""
     def bond(c1, c2):
         same = c1 == c2
         hole = (c1 == 2) | (c2 == 2)
         diag = np.where(same, np.where(c1 == 2, 0.0, V), np.where(hole, 0.0, -0.5 * J + V))
         off = np.where(same, 0.0, np.where(hole, -t, 0.5 * J))
         return diag, off
-    e, psis = nn_energy(ctx, state, configs, bond)
+    e, psis = nn_energy(ctx, state, configs, bond, bonds)
+    if t2 != 0.0:
+        e = e + _NNN_PATHS[nnn](ctx, state, configs, t2, bonds)
     return e - mu * np.sum(np.asarray(configs) != 2, axis=(1, 2)), psis
 
 
@@ -217,14 +221,43 @@ def spinless_fermion_energy(ctx, state, configs, t, V=0.0, t2=0.0, bonds=None, n
     (square_spinless_fermion.h:134-200).  Returns (energy [n], psi_list [rows + cols][n]).  The NN hops are local
     replacements inside the row / column pass.  The diagonal hop (t2): nnn = "local" (round 5) reuses the environments of the
     row pass -- a plaquette replacement against parity-twisted BTen2 environments (nnn_hop_energy_local); nnn = "fresh" takes
-    every hopped amplitude from a fresh contraction (nnn_hop_energy, rounds 2-4; kept as the independent check)."""
+    every hopped amplitude from a fresh contraction (nnn_hop_energy, rounds 2-4; kept as the independent check); nnn = "slice" is
+    "local" with one device call per row pair (nnn_hop_energy_slice)."""
     nf = state.nf
     def bond(c1, c2):
         return V * (nf[c1] % 2) * (nf[c2] % 2), np.where(c1 != c2, -t, 0.0)
     e, psis = nn_energy(ctx, state, configs, bond, bonds)
     if t2 != 0.0:
-        e = e + (nnn_hop_energy_local if nnn == "local" else nnn_hop_energy)(ctx, state, configs, t2, bonds)
+        e = e + _NNN_PATHS[nnn](ctx, state, configs, t2, bonds)
     return e, psis
+
+
+def nnn_hop_energy_slice(ctx, state, configs, t2, bonds=None):
+    """nnn_hop_energy_local with the whole row pair in ONE device call (pepsgpu_nnn_hop_slice_fermion): the twisted chains, the
+    candidates, the Jordan-Wigner signs and the closing traces stay on the device, one read-back per row pair.  A hop exists where
+    the occupation state.nf differs at the two ends of a diagonal."""
+    from .capi import UP, DOWN
+    cfg = np.asarray(configs)
+    n, rows, cols = cfg.shape
+    dt = np.complex128 if state.is_complex else np.float64
+    e = np.zeros(n, dt)
+    if bonds is not None:
+        bonds.update(dr=np.zeros((n, rows - 1, cols - 1), dt), ur=np.zeros((n, rows - 1, cols - 1), dt))
+    if cols < 2 or rows < 2:
+        return e
+    nf = np.asarray(state.nf) % 2
+    ctx.set_configs(state.ext_config(cfg, ROW))
+    ctx.generate_bmps_approach(UP)
+    for row in range(rows - 1):
+        psi, val = ctx.nnn_hop_slice_fermion(row, nf, 3)
+        eb = -t2 * np.conj(val / np.where(psi == 0, 1.0, psi)[:, :, None])      # (val is 0 where the hop is forbidden)
+        e += eb.sum(axis=(1, 2))
+        if bonds is not None:
+            bonds["dr"][:, row, :] = eb[:, :, 0]
+            bonds["ur"][:, row, :] = eb[:, :, 1]
+        if row < rows - 2:
+            ctx.shift_bmps_window(DOWN)
+    return e
 
 
 def nnn_hop_energy_local(ctx, state, configs, t2, bonds=None):
@@ -271,7 +304,7 @@ def nnn_hop_energy_local(ctx, state, configs, t2, bonds=None):
                 psi = ctx.replace_plaquette_trace(row, col, own[:, None, :], 0, 0)[:, 0]
                 cands, terms = [], []
                 for key, a, b in (("dr", (row, col), (row + 1, col + 1)), ("ur", (row + 1, col), (row, col + 1))):
-                    differ = cfg[:, a[0], a[1]] != cfg[:, b[0], b[1]]
+                    differ = occ[:, a[0] * cols + a[1]] != occ[:, b[0] * cols + b[1]]      # a hop needs exactly one end occupied
                     ia, ib = sorted((a[0] * cols + a[1], b[0] * cols + b[1]))
                     jw = (-1.0) ** occ[:, ia + 1:ib].sum(axis=1)
                     new = cfg.copy()
@@ -318,7 +351,7 @@ def nnn_hop_energy(ctx, state, configs, t2, bonds=None):
     for row in range(rows - 1):
         for col in range(cols - 1):
             for key, a, b in (("dr", (row, col), (row + 1, col + 1)), ("ur", (row + 1, col), (row, col + 1))):
-                differ = cfg[:, a[0], a[1]] != cfg[:, b[0], b[1]]
+                differ = occ[:, a[0] * cols + a[1]] != occ[:, b[0] * cols + b[1]]          # a hop needs exactly one end occupied
                 if not differ.any():
                     continue
                 ia, ib = sorted((a[0] * cols + a[1], b[0] * cols + b[1]))
@@ -330,6 +363,9 @@ def nnn_hop_energy(ctx, state, configs, t2, bonds=None):
                 if bonds is not None:
                     bonds[key][:, row, col] = eb
     return e
+
+
+_NNN_PATHS = {"local": nnn_hop_energy_local, "fresh": nnn_hop_energy, "slice": nnn_hop_energy_slice}
 
 
 def spinless_fermion_observables(ctx, state, configs, t, V=0.0, t2=0.0):

@@ -312,7 +312,7 @@ void exact_sum_measure_partial_impl(int rows, int cols, int D, int d, int chi, i
 template <typename TenElemT>
 void fermion_energy_impl(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype,
                          const double *sitps_ext_flat, int n, const int32_t *configs, int model, const double *prm,
-                         double *amplitudes_out, double *energies_out, double *psi_out, int *n_psi_out) {
+                         double *amplitudes_out, double *energies_out, double *psi_out, int *n_psi_out, int n_prm = 4) {
   SplitIndexTPST<TenElemT> sitps = make_state_t<TenElemT>(rows, cols, D, 4 * d, sitps_ext_flat);
   FermionDecoration dec;
   dec.nf.assign(nf, nf + d);
@@ -324,7 +324,7 @@ void fermion_energy_impl(int rows, int cols, int D, int d, const int32_t *nf, in
     SquareSpinlessFermion m(prm[0], prm[2], prm[1]);      // (t, t2, V): params = [t, V, t2, -]
     eh = m.CalEnergyAndHoles<false>(sitps, comp);
   } else {
-    SquaretJVModel m(prm[0], 0.0, prm[1], prm[2], prm[3]);
+    SquaretJVModel m(prm[0], n_prm > 4 ? prm[4] : 0.0, prm[1], prm[2], prm[3]);      // [t, J, V, mu, (t2)]
     eh = m.CalEnergyAndHoles<false>(sitps, comp);
   }
   constexpr int z = ElemTraits<TenElemT>::is_complex ? 2 : 1;
@@ -378,7 +378,7 @@ template <typename TenElemT>
 void fermion_measure_energy_impl(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype,
                                  const double *sitps_ext_flat, int n, int32_t *configs, const uint64_t *seeds, int warmup_sweeps,
                                  int n_samples, int sweeps_between, int model, const double *prm, double *energies_out,
-                                 double *accept_out) {
+                                 double *accept_out, int n_prm = 4) {
   SplitIndexTPST<TenElemT> sitps = make_state_t<TenElemT>(rows, cols, D, 4 * d, sitps_ext_flat);
   FermionDecoration dec;
   dec.nf.assign(nf, nf + d);
@@ -391,7 +391,7 @@ void fermion_measure_energy_impl(int rows, int cols, int D, int d, const int32_t
   comp.SetOrder(ROW_MAJOR);
   comp.EvaluateAmplitude();                                  // NormalizeStateOrder1: tps_sample_ = WaveFunctionComponentT(...) (:235-236)
   SquareSpinlessFermion spinless(prm[0], prm[2], prm[1]);     // model 0: (t, t2, V) from [t, V, t2, -]
-  SquaretJVModel tj(prm[0], 0.0, prm[1], prm[2], prm[3]);     // model 1: [t, J, V, mu]
+  SquaretJVModel tj(prm[0], n_prm > 4 ? prm[4] : 0.0, prm[1], prm[2], prm[3]);     // model 1: [t, J, V, mu, (t2)]
   constexpr int z = ElemTraits<TenElemT>::is_complex ? 2 : 1;
   for (int k = 0; k < n_samples; ++k) {
     for (int s = 0; s < sweeps_between; ++s) {
@@ -767,6 +767,39 @@ int pepshost_fermion_measure_energy_c128(int rows, int cols, int D, int d, const
   return guarded([&]() {
     fermion_measure_energy_impl<QLTEN_Complex>(rows, cols, D, d, nf, chi, PEPSGPU_C128, sitps_ext_flat, n, configs, seeds, warmup_sweeps,
                                                n_samples, sweeps_between, model, prm, energies_out, accept_out);
+  });
+}
+
+// The two calls above with a parameter count, every element type in one entry (dtype PEPSGPU_C128: the complex instantiation, interleaved
+// pairs): model 0 params [t, V, t2], model 1 [t, J, V, mu, t2] -- the t-t'-J model; a shorter list leaves the missing parameters 0.
+int pepshost_fermion_energy_prm(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype, const double *sitps_ext_flat,
+                                int n, const int32_t *configs, int model, int n_prm, const double *prm, double *amplitudes_out,
+                                double *energies_out, double *psi_out, int *n_psi_out) {
+  return guarded([&]() {
+    if (n_prm < 0 || n_prm > 5 || (model != 0 && model != 1)) throw std::invalid_argument("pepshost_fermion_energy_prm: model 0 / 1, at most 5 parameters");
+    double p[5] = {0, 0, 0, 0, 0};
+    std::copy(prm, prm + n_prm, p);
+    if (dtype == PEPSGPU_C128)
+      fermion_energy_impl<QLTEN_Complex>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, n, configs, model, p, amplitudes_out, energies_out,
+                                         psi_out, n_psi_out, 5);
+    else
+      fermion_energy_impl<double>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, n, configs, model, p, amplitudes_out, energies_out, psi_out,
+                                  n_psi_out, 5);
+  });
+}
+int pepshost_fermion_measure_energy_prm(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype, const double *sitps_ext_flat,
+                                        int n, int32_t *configs, const uint64_t *seeds, int warmup_sweeps, int n_samples, int sweeps_between,
+                                        int model, int n_prm, const double *prm, double *energies_out, double *accept_out) {
+  return guarded([&]() {
+    if (n_prm < 0 || n_prm > 5 || (model != 0 && model != 1)) throw std::invalid_argument("pepshost_fermion_measure_energy_prm: model 0 / 1, at most 5 parameters");
+    double p[5] = {0, 0, 0, 0, 0};
+    std::copy(prm, prm + n_prm, p);
+    if (dtype == PEPSGPU_C128)
+      fermion_measure_energy_impl<QLTEN_Complex>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, n, configs, seeds, warmup_sweeps, n_samples,
+                                                 sweeps_between, model, p, energies_out, accept_out, 5);
+    else
+      fermion_measure_energy_impl<double>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, n, configs, seeds, warmup_sweeps, n_samples,
+                                          sweeps_between, model, p, energies_out, accept_out, 5);
   });
 }
 

@@ -2255,39 +2255,58 @@ class SpinOneHalfTriJ1J2HeisenbergSqrPEPS : public SpinOneHalfMeasurementHooks {
   PsiSummaryStore last_psi_;
 };
 
-// square_spinless_fermion.h:51-200: H = -t sum_<ij> (c+_i c_j + h.c.) - t2 sum_<<ij>> (c+_i c_j + h.c.) + V sum_<ij> n_i n_j.
-// psi is recomputed with Trace next to psi' (same contraction path, docs/dev/design/math/
-// fermion-sign-in-bmps-contraction.md), the bosonic inv_psi argument is unused.
-// NNN hopping (:161-200, routed through BTen2 / ReplaceNNNSiteTrace in the reference): a diagonal hop is not local in the
-// sign-decorated form (the Jordan-Wigner string of the sites between the two in the row-major mode order changes the components
-// of OTHER sites' decoration), so it is taken from a FRESH amplitude of the hopped configuration, batched over the walkers:
-// 2 (L - 1)^2 extra contractions per sample when t2 != 0 (round 4: the C++ model refused t2 != 0 before; peps_amd/fermion.py
-// has had the same form).  The environment-reusing form stays unbuilt.
-class SquareSpinlessFermion : public SquareNNModelEnergySolver<SquareSpinlessFermion> {
- public:
-  SquareSpinlessFermion(double t, double V) : t_(t), t2_(0.0), V_(V) {}
-  SquareSpinlessFermion(double t, double t2, double V) : t_(t), t2_(t2), V_(V) {}
-  template <bool calchols = true, typename TenElemT = double>
-  EnergyAndHolesT<TenElemT> CalEnergyAndHoles(const SplitIndexTPST<TenElemT> &sitps, TPSWaveFunctionComponentT<TenElemT> &comp,
-                                              bool holes_on_device = false) {
-    EnergyAndHolesT<TenElemT> out =
-        SquareNNModelEnergySolver<SquareSpinlessFermion>::template CalEnergyAndHoles<calchols, TenElemT>(sitps, comp, holes_on_device);
-    // the diagonal hop: with the environments of a row pass (twisted BTen2 sets, round 5); PEPSHOST_NNN_FRESH=1: one fresh batched
-    // contraction per diagonal (rounds 2-4; the independent check)
+// The diagonal (next-nearest-neighbour) hop of the fermionic models, -t2 sum_<<ij>> (c+_i c_j + h.c.): square_spinless_fermion.h:161-200
+// and square_tJ_model.h:424-463.  E_loc += -t2 jw ComplexConjugate(psi(S') / psi(S)) per diagonal with exactly one end occupied
+// (spinless: occupied <-> empty; t-J: an electron moves into a hole, two spins never exchange), S' = S with the two end states
+// exchanged, jw = (-1)^(fermions strictly between the two ends in row-major order).  Three paths:
+//   Slice  one pepsgpu_nnn_hop_slice_fermion call per row pair (the default wherever DeviceSlicesEnabled());
+//   Local  the same contractions driven per plaquette from the host (PEPSHOST_NO_DEVICE_SWEEP=1);
+//   Fresh  one fresh batched contraction per diagonal (PEPSHOST_NNN_FRESH=1; the independent check).
+struct FermionNNNHop {
+  template <typename TenElemT>
+  static void Add(double t2, TPSWaveFunctionComponentT<TenElemT> &comp, std::vector<TenElemT> &energy) {
     static const bool fresh = getenv("PEPSHOST_NNN_FRESH") != nullptr;
-    if (t2_ != 0.0) { if (fresh) AddNNNHopEnergyFresh(comp, out.energy); else AddNNNHopEnergyLocal(comp, out.energy); }
-    return out;
+    if (t2 == 0.0) return;
+    if (fresh) Fresh(t2, comp, energy);
+    else if (DeviceSlicesEnabled()) Slice(t2, comp, energy);
+    else Local(t2, comp, energy);
+  }
+  template <typename TenElemT>
+  static void Slice(double t2, TPSWaveFunctionComponentT<TenElemT> &comp, std::vector<TenElemT> &energy) {
+    if (!comp.fermion) throw std::logic_error("fermionic NNN hopping needs the fermionic decoration of the component");
+    const size_t n = comp.config.walkers(), rows = comp.config.rows(), cols = comp.config.cols();
+    if (rows < 2 || cols < 2) return;
+    const FermionDecoration &fd = *comp.fermion;
+    auto &ct = comp.contractor;
+    comp.SetOrder(ROW_MAJOR);
+    comp.InitDevice();
+    std::vector<int32_t> occ(fd.d());
+    for (size_t s = 0; s < occ.size(); ++s) occ[s] = fd.n((int32_t)s);
+    const size_t np = cols - 1;
+    std::vector<TenElemT> psi(n * np), val(n * np * 2);
+    ct.GenerateBMPSApproach(UP);
+    for (size_t row = 0; row + 1 < rows; ++row) {
+      check_rc(pepsgpu_nnn_hop_slice_fermion(ct.ctx(), (int)row, (int)fd.d(), occ.data(), 3, dptr(psi.data()), dptr(val.data())), ct.ctx());
+      for (size_t w = 0; w < n; ++w)
+        for (size_t col = 0; col < np; ++col) {
+          const SiteIdx q[4] = {{row, col}, {row + 1, col}, {row + 1, col + 1}, {row, col + 1}};
+          for (int diag = 0; diag < 2; ++diag)
+            if (fd.n(comp.config(w, q[diag])) != fd.n(comp.config(w, q[diag + 2])))
+              energy[w] += TenElemT(-t2) * ComplexConjugate(TenElemT(val[(w * np + col) * 2 + diag] / psi[w * np + col]));   // :210 (jw applied on the device)
+        }
+      if (row + 2 < rows) ct.ShiftBMPSWindow(DOWN);
+    }
   }
   // The diagonal hops of every plaquette with the environments of ONE row pass -- the reference's flow (square_spinless_fermion.h:
-  // 161-213 through square_nnn_energy_solver.h:203-265: BTen2 of the row pair, ReplaceNNNSiteTrace per diagonal).  The reference's
+  // 161-213, square_tJ_model.h:424-463 through square_nnn_energy_solver.h:203-265: BTen2 of the row pair, ReplaceNNNSiteTrace per diagonal).  The reference's
   // graded trace carries the signs in the tensor algebra; in the decorated form a hop between a = (r, c) / (r+1, c) and
   // b = (r+1, c+1) / (r, c+1) flips the variant of every site between the two ends in row-major order -- row r right of the
   // plaquette, row r+1 left of it -- so the hopped amplitude is a replacement of the four plaquette tensors against TWISTED
   // environments: the LEFT BTen2 grown with row r+1 under flipped variants, the RIGHT BTen2 with row r flipped (second BTen2 set +
   // slice override of the C ABI).  psi of the plaquette comes from the untwisted set along the same path.
   template <typename TenElemT>
-  void AddNNNHopEnergyLocal(TPSWaveFunctionComponentT<TenElemT> &comp, std::vector<TenElemT> &energy) const {
-    if (!comp.fermion) throw std::logic_error("SquareSpinlessFermion: NNN hopping needs the fermionic decoration of the component");
+  static void Local(double t2, TPSWaveFunctionComponentT<TenElemT> &comp, std::vector<TenElemT> &energy) {
+    if (!comp.fermion) throw std::logic_error("fermionic NNN hopping needs the fermionic decoration of the component");
     const size_t n = comp.config.walkers(), rows = comp.config.rows(), cols = comp.config.cols();
     if (rows < 2 || cols < 2) return;
     const FermionDecoration &fd = *comp.fermion;
@@ -2326,8 +2345,8 @@ class SquareSpinlessFermion : public SquareNNModelEnergySolver<SquareSpinlessFer
           for (int k = 0; k < 4; ++k) own[w * 4 + k] = ext(w, q[k]);
           for (int diag = 0; diag < 2; ++diag) {
             const SiteIdx a = diag == 0 ? q[0] : q[1], b = diag == 0 ? q[2] : q[3];
-            const bool differ = comp.config(w, a) != comp.config(w, b);
-            if (differ) {
+            const bool allowed = fd.n(comp.config(w, a)) != fd.n(comp.config(w, b));      // exactly one end occupied
+            if (allowed) {
               any = true;
               const size_t ia = std::min(a.r * cols + a.c, b.r * cols + b.c), ib = std::max(a.r * cols + a.c, b.r * cols + b.c);
               int between = 0;
@@ -2354,7 +2373,7 @@ class SquareSpinlessFermion : public SquareNNModelEnergySolver<SquareSpinlessFer
           const std::vector<TenElemT> psi_ex = ct.ReplacePlaquetteTrace(q[0], 2, cand, 1, 1);
           for (size_t w = 0; w < n; ++w)
             for (int diag = 0; diag < 2; ++diag)
-              if (jw[w * 2 + diag] != 0.0) energy[w] += TenElemT(-t2_ * jw[w * 2 + diag]) * ComplexConjugate(TenElemT(psi_ex[w * 2 + diag] / psi[w]));   // :210
+              if (jw[w * 2 + diag] != 0.0) energy[w] += TenElemT(-t2 * jw[w * 2 + diag]) * ComplexConjugate(TenElemT(psi_ex[w * 2 + diag] / psi[w]));   // :210
         }
         if (col + 2 < cols) {      // both LEFT chains advance over column col (set 1 under the row+1 override)
           ct.GrowBTen2Step(LEFT, row);
@@ -2373,8 +2392,8 @@ class SquareSpinlessFermion : public SquareNNModelEnergySolver<SquareSpinlessFer
   // sum over the plaquette diagonals of -t2 * jw * psi(S with the two sites exchanged) / psi(S); jw = (-1)^(fermions strictly
   // between the two sites in row-major order).  Leaves comp on its original configuration.
   template <typename TenElemT>
-  void AddNNNHopEnergyFresh(TPSWaveFunctionComponentT<TenElemT> &comp, std::vector<TenElemT> &energy) const {
-    if (!comp.fermion) throw std::logic_error("SquareSpinlessFermion: NNN hopping needs the fermionic decoration of the component");
+  static void Fresh(double t2, TPSWaveFunctionComponentT<TenElemT> &comp, std::vector<TenElemT> &energy) {
+    if (!comp.fermion) throw std::logic_error("fermionic NNN hopping needs the fermionic decoration of the component");
     const size_t n = comp.config.walkers(), rows = comp.config.rows(), cols = comp.config.cols();
     const Configuration orig = comp.config;
     comp.ReplaceGlobalConfig(orig);                       // psi of the original configuration, fresh (row-major order)
@@ -2385,20 +2404,37 @@ class SquareSpinlessFermion : public SquareNNModelEnergySolver<SquareSpinlessFer
           const SiteIdx a = diag == 0 ? SiteIdx{row, col} : SiteIdx{row + 1, col};
           const SiteIdx b = diag == 0 ? SiteIdx{row + 1, col + 1} : SiteIdx{row, col + 1};
           bool any = false;
-          for (size_t w = 0; w < n; ++w) any |= orig(w, a) != orig(w, b);
+          for (size_t w = 0; w < n; ++w) any |= comp.fermion->n(orig(w, a)) != comp.fermion->n(orig(w, b));
           if (!any) continue;
           Configuration hop = orig;
           for (size_t w = 0; w < n; ++w) { hop(w, a) = orig(w, b); hop(w, b) = orig(w, a); }
           comp.ReplaceGlobalConfig(hop);
           const size_t ia = std::min(a.r * cols + a.c, b.r * cols + b.c), ib = std::max(a.r * cols + a.c, b.r * cols + b.c);
           for (size_t w = 0; w < n; ++w) {
-            if (orig(w, a) == orig(w, b)) continue;
+            if (comp.fermion->n(orig(w, a)) == comp.fermion->n(orig(w, b))) continue;
             int between = 0;
             for (size_t q = ia + 1; q < ib; ++q) between += comp.fermion->n(orig(w, {q / cols, q % cols}));
-            energy[w] += TenElemT(-t2_ * ((between & 1) ? -1.0 : 1.0)) * ComplexConjugate(TenElemT(comp.amplitude[w] / psi0[w]));
+            energy[w] += TenElemT(-t2 * ((between & 1) ? -1.0 : 1.0)) * ComplexConjugate(TenElemT(comp.amplitude[w] / psi0[w]));
           }
         }
     comp.ReplaceGlobalConfig(orig);
+  }
+};
+
+// square_spinless_fermion.h:51-200: H = -t sum_<ij> (c+_i c_j + h.c.) - t2 sum_<<ij>> (c+_i c_j + h.c.) + V sum_<ij> n_i n_j.
+// psi is recomputed with Trace next to psi' (same contraction path, docs/dev/design/math/
+// fermion-sign-in-bmps-contraction.md), the bosonic inv_psi argument is unused.  NNN hopping (:161-200): FermionNNNHop above.
+class SquareSpinlessFermion : public SquareNNModelEnergySolver<SquareSpinlessFermion> {
+ public:
+  SquareSpinlessFermion(double t, double V) : t_(t), t2_(0.0), V_(V) {}
+  SquareSpinlessFermion(double t, double t2, double V) : t_(t), t2_(t2), V_(V) {}
+  template <bool calchols = true, typename TenElemT = double>
+  EnergyAndHolesT<TenElemT> CalEnergyAndHoles(const SplitIndexTPST<TenElemT> &sitps, TPSWaveFunctionComponentT<TenElemT> &comp,
+                                              bool holes_on_device = false) {
+    EnergyAndHolesT<TenElemT> out =
+        SquareNNModelEnergySolver<SquareSpinlessFermion>::template CalEnergyAndHoles<calchols, TenElemT>(sitps, comp, holes_on_device);
+    FermionNNNHop::Add(t2_, comp, out.energy);
+    return out;
   }
   double CalDensityImpl(int32_t config) const { return double(1 - config); }   // :95-97
   template <typename TenElemT>
@@ -2437,11 +2473,17 @@ class SquareSpinlessFermion : public SquareNNModelEnergySolver<SquareSpinlessFer
 
 // square_tJ_model.h:301-345 (SquaretJModelMixIn::EvaluateBondEnergy) + :215-228: states 0 up, 1 down, 2 empty
 // (vmc_basic/tj_single_site_state.h:19-23); H = -t sum (c+ c + h.c.) + J sum (S.S - n n / 4) + V sum n n - mu N.
-// NNN hopping t2 must be 0 on the device (see SquareSpinlessFermion).
+// NNN hopping t2 (:424-463): FermionNNNHop above.
 class SquaretJVModel : public SquareNNModelEnergySolver<SquaretJVModel> {
  public:
-  SquaretJVModel(double t, double t2, double J, double V, double mu) : t_(t), J_(J), V_(V), mu_(mu) {
-    if (t2 != 0.0) throw std::invalid_argument("SquaretJVModel: t2 != 0 (NNN hopping) is not implemented on the device");
+  SquaretJVModel(double t, double t2, double J, double V, double mu) : t_(t), t2_(t2), J_(J), V_(V), mu_(mu) {}
+  template <bool calchols = true, typename TenElemT = double>
+  EnergyAndHolesT<TenElemT> CalEnergyAndHoles(const SplitIndexTPST<TenElemT> &sitps, TPSWaveFunctionComponentT<TenElemT> &comp,
+                                              bool holes_on_device = false) {
+    EnergyAndHolesT<TenElemT> out =
+        SquareNNModelEnergySolver<SquaretJVModel>::template CalEnergyAndHoles<calchols, TenElemT>(sitps, comp, holes_on_device);
+    FermionNNNHop::Add(t2_, comp, out.energy);
+    return out;
   }
   template <typename TenElemT>
   std::vector<TenElemT> EvaluateBondEnergy(const SiteIdx &s1, const SiteIdx &s2, BondOrientation orient,
@@ -2484,7 +2526,16 @@ class SquaretJVModel : public SquareNNModelEnergySolver<SquaretJVModel> {
     return -mu_ * double(ele);
   }
  private:
-  double t_, J_, V_, mu_;
+  double t_, t2_, J_, V_, mu_;
+};
+// square_tJ_model.h:613-705: the named models hand V = 0 (and SquaretJNNModel t2 = 0) to the mix-in
+class SquaretJNNModel : public SquaretJVModel {
+ public:
+  SquaretJNNModel(double t, double J, double mu) : SquaretJVModel(t, 0.0, J, 0.0, mu) {}
+};
+class SquaretJNNNModel : public SquaretJVModel {
+ public:
+  SquaretJNNNModel(double t, double t2, double J, double mu) : SquaretJVModel(t, t2, J, 0.0, mu) {}
 };
 
 // transverse_field_ising_square_obc.h:28-247

@@ -16,11 +16,12 @@ SYMBOLS = ["pepshost_last_error", "pepshost_mc_sweeps", "pepshost_energy_and_hol
            "pepshost_energy_and_holes_c128", "pepshost_exact_sum_partial_c128", "pepshost_exact_sum_finish_c128",
            "pepshost_mc_energy_grad_partial_c128", "pepshost_mc_sweeps_c128", "pepshost_load_sitps_c128", "pepshost_dump_sitps_c128",
            "pepshost_mc_engine_warmup", "pepshost_mc_engine_warmup_dist", "pepshost_suwa_todo_chain", "pepshost_load_configuration2", "pepshost_configuration_from_text",
-           "pepshost_fermion_measure_energy", "pepshost_measure_c128", "pepshost_exact_sum_measure_partial_c128", "pepshost_fermion_energy_c128",
+           "pepshost_fermion_measure_energy", "pepshost_fermion_energy_prm", "pepshost_fermion_measure_energy_prm", "pepshost_measure_c128", "pepshost_exact_sum_measure_partial_c128", "pepshost_fermion_energy_c128",
            "pepshost_fermion_exact_sum_partial_c128", "pepshost_fermion_mc_sweeps_c128", "pepshost_fermion_measure_energy_c128",
            "pepshost_fermion_mc_sweeps_updater", "pepshost_tnn3_table"]
 
 _lib = None
+_C128 = 3                                   # PEPSGPU_C128 (include/pepsgpu.h)
 
 # updater ids of the shim: MCUpdateSquareNNExchangeOBC, MCUpdateSquareNNFullSpaceUpdateOBC, MCUpdateSquareTNN3SiteExchange
 UPDATER_ID = {"exchange": 0, "fullspace": 1, "tnn3": 2}
@@ -340,7 +341,14 @@ def fermion_energy(state, configs, chi, t, V=0.0, dtype=1, model="spinless", J=0
     psi = np.zeros((rows + cols, n), et)
     npsi = C.c_int(0)
     prm = np.array([t, V, t2, 0.0] if model == "spinless" else [t, J, V, mu], dtype=np.float64)
-    if cplx:
+    if model != "spinless" and t2 != 0.0:             # the t-t'-J model: the entry with a parameter count carries t2
+        prm = np.array([t, J, V, mu, t2], dtype=np.float64)
+        _ck(lib().pepshost_fermion_energy_prm(rows, cols, D, state.d, _p(nf, C.c_int32), chi, _C128 if cplx else dtype,
+                                              _cp(flat), n, _p(cfg, C.c_int32), 1, prm.size,
+                                              _p(prm, C.c_double), _cp(amps),
+                                              _cp(en), _cp(psi),
+                                              C.byref(npsi)))
+    elif cplx:
         _ck(lib().pepshost_fermion_energy_c128(rows, cols, D, state.d, _p(nf, C.c_int32), chi, _cp(flat), n,
                                                _p(cfg, C.c_int32), 0 if model == "spinless" else 1, _p(prm, C.c_double),
                                                _cp(amps), _cp(en), _cp(psi), C.byref(npsi)))
@@ -395,7 +403,13 @@ def fermion_measure_energy(state, configs, seeds, chi, warmup_sweeps, n_samples,
     sd = np.ascontiguousarray(seeds, dtype=np.uint64)
     prm = np.array([t, J, V, mu] if model == "tj" else [t, V, t2, 0.0], dtype=np.float64)
     en, rates = np.zeros((n_samples, n), et), np.zeros(n)
-    if cplx:
+    if model == "tj" and t2 != 0.0:                   # the t-t'-J model: the entry with a parameter count carries t2
+        prm = np.array([t, J, V, mu, t2], dtype=np.float64)
+        _ck(lib().pepshost_fermion_measure_energy_prm(rows, cols, D, state.d, _p(nf, C.c_int32), chi, _C128 if cplx else dtype,
+                                                      _cp(flat), n, _p(cfg, C.c_int32), _p(sd, C.c_uint64),
+                                                      warmup_sweeps, n_samples, sweeps_between, 1, prm.size, _p(prm, C.c_double),
+                                                      _cp(en), _p(rates, C.c_double)))
+    elif cplx:
         _ck(lib().pepshost_fermion_measure_energy_c128(rows, cols, D, state.d, _p(nf, C.c_int32), chi, _cp(flat), n,
                                                        _p(cfg, C.c_int32), _p(sd, C.c_uint64), warmup_sweeps, n_samples, sweeps_between,
                                                        1 if model == "tj" else 0, _p(prm, C.c_double), _cp(en), _p(rates, C.c_double)))

@@ -183,13 +183,9 @@ int pepsgpu_diag_fermion_hop_cand(int rows, int cols, int d, const int32_t *occ,
                                   int32_t *cand_out, int32_t *sign_out, int32_t *flag_out) {
   return guarded(nullptr, [&]() {
     PG_REQUIRE(occ && ext && cand_out && sign_out && flag_out, 1, "null buffer");
-    PG_REQUIRE(rows >= 2 && cols >= 2 && d >= 1 && d <= 32 && n >= 1 && (double)n * rows * cols < 2147483648.0, 1, "bad sizes");
+    PG_REQUIRE(rows >= 2 && cols >= 2 && n >= 1 && (double)n * rows * cols < 2147483648.0, 1, "bad sizes");
     PG_REQUIRE(row1 >= 0 && row1 + 1 < rows && col1 >= 0 && col1 + 1 < cols, 1, "plaquette outside the lattice");
-    unsigned occ_bits = 0;
-    for (int s = 0; s < d; ++s) {
-      PG_REQUIRE(occ[s] == 0 || occ[s] == 1, 1, "occupation numbers must be 0 or 1");
-      occ_bits |= (unsigned)occ[s] << s;
-    }
+    const unsigned occ_bits = pepsgpu::hop_occ_bits(d, occ);
     const int sites = rows * cols;
     const size_t ne = (size_t)n * sites;
     for (size_t e = 0; e < ne; ++e) PG_REQUIRE(ext[e] >= 0 && ext[e] < 2 * d, 1, "extended state outside [0, 2 d)");

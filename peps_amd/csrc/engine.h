@@ -1483,6 +1483,19 @@ class Engine : public EngineBase {
   }
   BTenDev bten2_step(int post, const BTenDev &bt, const DTen<T> &mps1, const SiteSel &s1, const SiteSel &s2,
                      const DTen<T> &mps2, int ncand, int bt_ncand, bool normalise, const int *entry_flag = nullptr);
+  // One horizontal plaquette (row1, col1) .. (row1 + 1, col1 + 1) between a LEFT and a RIGHT BTen2 under the UP / DOWN row BMPS: the
+  // two half tensors and the log-scale sum of the four environments (plaquette_halves, engine_nnn.h)
+  struct PlaqHalves { BTenDev a, b; double *lsum; };
+  PlaqHalves plaquette_halves(int row1, int col1, const BTenDev &lb, const BTenDev &rb, const int *tab, int ncols, const int cols[4],
+                              int nc, const int *flag = nullptr);
+  void free_halves(PlaqHalves &h) { free_ten(h.a.t); free_ten(h.b.t); arena_.free(h.lsum); }
+  void close_dot4(PlaqHalves &h, int nc, const int *flag, int slot0, int slot1, long w_stride, double *out);
+  // the walk over the plaquettes of a row pair that the diagonal slices share (row_pair_walk, engine_sweep.h).  s = the flat
+  // site indices of (r, c), (r+1, c), (r+1, c+1), (r, c+1); kinds[0 .. nc) = the requested diagonals with work for some walker
+  struct RowPairPlaq { int col1, s[4], kinds[2], nc; };
+  template <typename Differ, typename Begin, typename Plaquette, typename Advance, typename Epilogue>
+  void row_pair_walk(const char *what, int row1, int diag_mask, size_t ntab, double *host_out, Differ &&differ, Begin &&begin,
+                     Plaquette &&plaquette, Advance &&advance, Epilogue &&epilogue);
   void finish_dot4(const DTen<T> &a, const DTen<T> &b, int nc, double *lsum, double *out);
   int *upload_cand(int ncand, int ncols, const int32_t *cand);
   // sel (optional, f32): the kernel of the walkers with at most JR_BR live rows selects / normalises their rows into Vt
@@ -1519,6 +1532,13 @@ class Engine : public EngineBase {
   // tensors between a LEFT environment of one set and a RIGHT environment of the other.
   std::vector<BTenDev> bten2_inactive_[4];
   int bten2_active_ = 0;
+  const std::vector<BTenDev> &bten2_of_set(int set, int pos) const { return (set == bten2_active_ ? bten2_ : bten2_inactive_)[pos]; }
+  void bten2_activate(int set) {      // (set is 0 or 1)
+    if (set == bten2_active_) return;
+    for (int p = 0; p < 4; ++p) std::swap(bten2_[p], bten2_inactive_[p]);
+    bten2_active_ = set;
+  }
+  struct TwistScope;                  // the override-plus-set state of the fermionic hop slice (engine_nnn.h)
   int *cfg_ovr_tab_ = nullptr;       // [walker][Ly * Lx]: the walkers' table with one slice replaced (cfg_override_slice)
   void clear_bten2_sets() {           // every invalidation of the environments drops both sets and the override
     for (int p = 0; p < 4; ++p) {

@@ -3,7 +3,9 @@
 // bmps_contractor_helpers.h:12-180, bmps_contractor_trace.h:207-536; bosonic branches), batched over
 // walkers x candidates.  Everything is one primitive -- the BTen2 growth step of
 // GrowBTen2StepAfterTransposedMPOTens (helpers.h:174-177) with two site selectors -- plus a
-// 4-index dot; the Transpose calls of the reference are strides of the tensor GEMM.
+// 4-index dot; the Transpose calls of the reference are strides of the tensor GEMM.  The horizontal
+// plaquette between a LEFT and a RIGHT BTen2 -- two such steps -- is one stage, plaquette_halves: the
+// per-call traces close it with finish_dot4, the row-pair slices of engine_sweep.h with close_dot4.
 #pragma once
 #include "engine.h"
 
@@ -136,6 +138,29 @@ int *Engine<T>::upload_cand(int ncand, int ncols, const int32_t *cand) {
   return d;
 }
 
+// The plaquette (row1, col1) .. (row1 + 1, col1 + 1) between the LEFT BTen2 lb and the RIGHT BTen2 rb (the caller says of which set)
+// under the row BMPS UP(row1) / DOWN(row1 + 1): a = lb grown over column col1, b = rb over column col1 + 1, lsum = the log-scales of
+// the four environments.  cols[k]: the column of tab [entry][ncols] with the state of site k in the order (r, c), (r+1, c), (r+1, c+1),
+// (r, c+1); < 0: the walker's configuration (or the active override).  A candidate column wins over the configuration override: a
+// replaced site never reads either configuration table.  flag: the entry_flag of bten2_step.
+template <typename T>
+typename Engine<T>::PlaqHalves Engine<T>::plaquette_halves(int row1, int col1, const BTenDev &lb, const BTenDev &rb, const int *tab,
+                                                           int ncols, const int cols[4], int nc, const int *flag) {
+  const int row2 = row1 + 1, col2 = col1 + 1;
+  const BMPSDev &up = bmps_at_slice(UP, row1), &dn = bmps_at_slice(DOWN, row2);
+  const SitePick t0{row1, col1, cols[0]}, t1{row2, col1, cols[1]}, t2{row2, col2, cols[2]}, t3{row1, col2, cols[3]};
+  PlaqHalves h;
+  h.lsum = zeros_f64();
+  h.a = bten2_step(LEFT, lb, at_logical(up, UP, col1), pick(t0, tab, ncols), pick(t1, tab, ncols), at_logical(dn, DOWN, col1), nc, 1,
+                   false, flag);
+  h.b = bten2_step(RIGHT, rb, at_logical(dn, DOWN, col2), pick(t2, tab, ncols), pick(t3, tab, ncols), at_logical(up, UP, col2), nc, 1,
+                   false, flag);
+  add_logs(h.lsum, up.logscale, dn.logscale, lb.logscale, rb.logscale);
+  PG_REQUIRE(h.a.t.d[0] == h.b.t.d[3] && h.a.t.d[1] == h.b.t.d[2] && h.a.t.d[2] == h.b.t.d[1] && h.a.t.d[3] == h.b.t.d[0], 3,
+             "trace: two-row environment bond mismatch");
+  return h;
+}
+
 template <typename T>
 void Engine<T>::init_bten2(int pos, int slice) {   // init.h:130-186
   require_ready();
@@ -216,18 +241,13 @@ void Engine<T>::replace_nnn_trace(int row1, int col1, int dir, int orient, int n
   const int nc = ncand > 0 ? ncand : 1;
   int *dc = upload_cand(ncand, 2, cand);
   const int cl = ncand > 0 ? 0 : -1, cr = ncand > 0 ? 1 : -1;
-  double *lsum = zeros_f64();
-  BTenDev a, b;
   if (orient == HORIZONTAL) {
-    const BMPSDev &up = bmps_at_slice(UP, row1), &dn = bmps_at_slice(DOWN, row2);
     PG_REQUIRE(bten2_size(LEFT) > col1, 3, "ReplaceNNNSiteTrace: LEFT BTen2 missing");
-    const BTenDev &lb = bten2_[LEFT][col1], &rb = bten2_at_slice(RIGHT, col2);
-    SitePick t0, t1, t2, t3;   // (row1,col1), (row2,col1), (row2,col2), (row1,col2)
-    if (dir == LEFTUP_TO_RIGHTDOWN) { t0 = {row1, col1, cl}; t1 = {row2, col1, -1}; t2 = {row2, col2, cr}; t3 = {row1, col2, -1}; }
-    else { t0 = {row1, col1, -1}; t1 = {row2, col1, cl}; t2 = {row2, col2, -1}; t3 = {row1, col2, cr}; }
-    a = bten2_step(LEFT, lb, at_logical(up, UP, col1), pick(t0, dc, 2), pick(t1, dc, 2), at_logical(dn, DOWN, col1), nc, 1, false);
-    b = bten2_step(RIGHT, rb, at_logical(dn, DOWN, col2), pick(t2, dc, 2), pick(t3, dc, 2), at_logical(up, UP, col2), nc, 1, false);
-    add_logs(lsum, up.logscale, dn.logscale, lb.logscale, rb.logscale);
+    const int lurd[4] = {cl, -1, cr, -1}, ldru[4] = {-1, cl, -1, cr};
+    PlaqHalves h = plaquette_halves(row1, col1, bten2_[LEFT][col1], bten2_at_slice(RIGHT, col2), dc, 2,
+                                    dir == LEFTUP_TO_RIGHTDOWN ? lurd : ldru, nc);
+    finish_dot4(h.a.t, h.b.t, nc, h.lsum, out);
+    free_halves(h);
   } else {
     const BMPSDev &lf = bmps_at_slice(LEFT, col1), &rt = bmps_at_slice(RIGHT, col2);
     PG_REQUIRE(bten2_size(UP) > row1, 3, "ReplaceNNNSiteTrace: UP BTen2 missing");
@@ -235,13 +255,14 @@ void Engine<T>::replace_nnn_trace(int row1, int col1, int dir, int orient, int n
     SitePick m0, m1, m2, m3;   // (row2,col1), (row2,col2), (row1,col1), (row1,col2)
     if (dir == LEFTUP_TO_RIGHTDOWN) { m0 = {row2, col1, -1}; m1 = {row2, col2, cr}; m2 = {row1, col1, cl}; m3 = {row1, col2, -1}; }
     else { m0 = {row2, col1, cl}; m1 = {row2, col2, -1}; m2 = {row1, col1, -1}; m3 = {row1, col2, cr}; }
-    a = bten2_step(DOWN, bb, at_logical(lf, LEFT, row2), pick(m0, dc, 2), pick(m1, dc, 2), at_logical(rt, RIGHT, row2), nc, 1, false);
-    b = bten2_step(UP, tb, at_logical(rt, RIGHT, row1), pick(m3, dc, 2), pick(m2, dc, 2), at_logical(lf, LEFT, row1), nc, 1, false);
+    double *lsum = zeros_f64();
+    BTenDev a = bten2_step(DOWN, bb, at_logical(lf, LEFT, row2), pick(m0, dc, 2), pick(m1, dc, 2), at_logical(rt, RIGHT, row2), nc, 1, false);
+    BTenDev b = bten2_step(UP, tb, at_logical(rt, RIGHT, row1), pick(m3, dc, 2), pick(m2, dc, 2), at_logical(lf, LEFT, row1), nc, 1, false);
     add_logs(lsum, lf.logscale, rt.logscale, tb.logscale, bb.logscale);
+    finish_dot4(a.t, b.t, nc, lsum, out);
+    free_ten(a.t); free_ten(b.t);
+    arena_.free(lsum);
   }
-  finish_dot4(a.t, b.t, nc, lsum, out);
-  free_ten(a.t); free_ten(b.t);
-  arena_.free(lsum);
   if (dc) arena_.free(dc);
 }
 
@@ -249,10 +270,23 @@ void Engine<T>::replace_nnn_trace(int row1, int col1, int dir, int orient, int n
 template <typename T>
 void Engine<T>::bten2_select_set(int set) {
   PG_REQUIRE(set == 0 || set == 1, 1, "BTen2 set must be 0 or 1");
-  if (set == bten2_active_) return;
-  for (int p = 0; p < 4; ++p) std::swap(bten2_[p], bten2_inactive_[p]);
-  bten2_active_ = set;
+  bten2_activate(set);
 }
+
+// The state the fermionic hop slice works under: use(set, tab, row) makes BTen2 set `set` the active one and lets row `row` be read
+// from the table tab (nullptr: the walkers' own table everywhere).  Once used, leaving the scope -- by return or by a throw -- turns
+// the override off and selects set 0; set 1 keeps its chains.
+template <typename T>
+struct Engine<T>::TwistScope {
+  Engine<T> &e;
+  bool used = false;
+  void use(int set, const int *tab, int row) {
+    used = true;
+    e.bten2_activate(set);
+    e.ovr_on_ = tab != nullptr; e.ovr_hor_ = true; e.ovr_num_ = row; e.ovr_cfg_ = tab; e.ovr_tens_ = nullptr; e.ovr_nt_ = 0;
+  }
+  ~TwistScope() { if (used) { e.ovr_on_ = false; e.ovr_cfg_ = nullptr; e.bten2_activate(0); } }
+};
 
 // states = [walker][N] extended states of row (HORIZONTAL) / column (VERTICAL) `num`; nullptr clears the override.  While it is
 // set, every kernel that selects a site tensor of that slice by configuration reads this table (the walkers' own table elsewhere).
@@ -294,23 +328,14 @@ void Engine<T>::replace_plaquette_trace(int row1, int col1, int ncand, const int
   PG_REQUIRE((left_set == 0 || left_set == 1) && (right_set == 0 || right_set == 1), 1, "BTen2 set must be 0 or 1");
   const int nc = ncand > 0 ? ncand : 1;
   int *dc = upload_cand(ncand, 4, cand);
-  auto col_of = [&](int k) { return ncand > 0 ? k : -1; };
-  double *lsum = zeros_f64();
-  const std::vector<BTenDev> &ls = (left_set == bten2_active_ ? bten2_ : bten2_inactive_)[LEFT];
-  const std::vector<BTenDev> &rs = (right_set == bten2_active_ ? bten2_ : bten2_inactive_)[RIGHT];
+  const std::vector<BTenDev> &ls = bten2_of_set(left_set, LEFT), &rs = bten2_of_set(right_set, RIGHT);
   const int kr = Lx_ - 1 - col2;
   PG_REQUIRE((int)ls.size() > col1, 3, "plaquette trace: LEFT BTen2 of that set missing");
   PG_REQUIRE(kr >= 0 && kr < (int)rs.size(), 3, "plaquette trace: RIGHT BTen2 of that set missing");
-  const BMPSDev &up = bmps_at_slice(UP, row1), &dn = bmps_at_slice(DOWN, row2);
-  const BTenDev &lb = ls[col1], &rb = rs[kr];
-  const SitePick t0{row1, col1, col_of(0)}, t1{row2, col1, col_of(1)}, t2{row2, col2, col_of(2)}, t3{row1, col2, col_of(3)};
-  // (the candidate table overrides the configuration override: a replaced site never reads either configuration table)
-  BTenDev a = bten2_step(LEFT, lb, at_logical(up, UP, col1), pick(t0, dc, 4), pick(t1, dc, 4), at_logical(dn, DOWN, col1), nc, 1, false);
-  BTenDev b = bten2_step(RIGHT, rb, at_logical(dn, DOWN, col2), pick(t2, dc, 4), pick(t3, dc, 4), at_logical(up, UP, col2), nc, 1, false);
-  add_logs(lsum, up.logscale, dn.logscale, lb.logscale, rb.logscale);
-  finish_dot4(a.t, b.t, nc, lsum, out);
-  free_ten(a.t); free_ten(b.t);
-  arena_.free(lsum);
+  const int own[4] = {-1, -1, -1, -1}, replaced[4] = {0, 1, 2, 3};
+  PlaqHalves h = plaquette_halves(row1, col1, ls[col1], rs[kr], dc, 4, ncand > 0 ? replaced : own, nc);
+  finish_dot4(h.a.t, h.b.t, nc, h.lsum, out);
+  free_halves(h);
   if (dc) arena_.free(dc);
 }
 

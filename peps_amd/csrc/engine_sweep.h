@@ -425,75 +425,92 @@ inline std::atomic<long> &nnn_slice_calls() {   // completed nnn_exchange_slice 
   return n;
 }
 
+// The closure of the row-pair slices, trace_dot4_kernel: out[w * w_stride + (q ? slot1 : slot0)] = a . b exp(lsum[w]) of entry (w, q)
+// (an entry whose flag is >= 0 keeps what the table holds); gives the halves back.
+template <typename T>
+void Engine<T>::close_dot4(PlaqHalves &h, int nc, const int *flag, int slot0, int slot1, long w_stride, double *out) {
+  const DTen<T> &a = h.a.t;
+  hipLaunchKernelGGL((trace_dot4_kernel<T, Acc>), dim3(nw_ * nc), dim3(256), 0, stream_, (const T *)a.p, (const T *)h.b.t.p, a.n, a.d[0],
+                     a.d[1], a.d[2], a.d[3], (const double *)h.lsum, flag, nc, slot0, slot1, w_stride, out);
+  PG_CHECK_HIP(hipGetLastError());
+  free_halves(h);
+}
+
+// The part the diagonal slices of a row pair share.  The row pair and the mask are checked and the row BMPS probed (status 3 before
+// anything is touched); the value table dval [ntab] is zeroed; begin() states the slice's own refusals and sets up its BTen2 chains;
+// per column the requested diagonals whose ends differ for ANY walker (differ(w, sa, sb) on the host mirror) are packed into a
+// RowPairPlaq, plaquette(p, dval) runs under its own ArenaScope where there is one (else nothing is launched and the zeros stay) and
+// advance(col1) moves the chains on, after the last column too; epilogue(dval), then ONE read-back of the table into host_out.
+template <typename T>
+template <typename Differ, typename Begin, typename Plaquette, typename Advance, typename Epilogue>
+void Engine<T>::row_pair_walk(const char *what, int row1, int diag_mask, size_t ntab, double *host_out, Differ &&differ, Begin &&begin,
+                              Plaquette &&plaquette, Advance &&advance, Epilogue &&epilogue) {
+  PG_REQUIRE(row1 >= 0 && row1 + 1 < Ly_ && Lx_ >= 2, 1, std::string(what) + ": row pair outside the lattice");
+  PG_REQUIRE(diag_mask >= 1 && diag_mask <= 3, 1, std::string(what) + ": diag_mask must be 1, 2 or 3");
+  const int row2 = row1 + 1;
+  (void)bmps_at_slice(UP, row1);
+  (void)bmps_at_slice(DOWN, row2);
+  ArenaBuf<double> dval(arena_, ntab);
+  PG_CHECK_HIP(hipMemsetAsync(dval, 0, sizeof(double) * ntab, stream_));
+  begin();
+  for (int col1 = 0; col1 + 1 < Lx_; ++col1) {
+    const int col2 = col1 + 1;
+    RowPairPlaq p{col1, {row1 * Lx_ + col1, row2 * Lx_ + col1, row2 * Lx_ + col2, row1 * Lx_ + col2}, {0, 0}, 0};
+    for (int kind = 0; kind < 2; ++kind) {
+      if (!((diag_mask >> kind) & 1)) continue;
+      const int sa = kind == LEFTUP_TO_RIGHTDOWN ? p.s[0] : p.s[1], sb = kind == LEFTUP_TO_RIGHTDOWN ? p.s[2] : p.s[3];
+      bool any = false;
+      for (int w = 0; w < nw_ && !any; ++w) any = differ(w, sa, sb);
+      if (any) p.kinds[p.nc++] = kind;
+    }
+    if (p.nc > 0) {
+      ArenaScope scope(arena_);
+      plaquette(p, (double *)dval);
+    }
+    advance(col1);
+  }
+  epilogue((double *)dval);
+  PG_CHECK_HIP(hipMemcpyAsync(host_out, dval, sizeof(double) * ntab, hipMemcpyDeviceToHost, stream_));
+  PG_CHECK_HIP(hipStreamSynchronize(stream_));
+}
+
 // One row pair of the diagonal-bond pass on the device: InitBTen2(LEFT, row1), GrowFullBTen2(RIGHT, row1, 2, init), then for every
 // column the amplitudes of the configuration with the ends of each requested diagonal exchanged and ShiftBTen2Window(RIGHT, row1)
-// (after the last column too, as the host loop does) -- ONE read-back at the end.  Bosonic configurations: the walkers' own table, no
-// configuration override active (status 3 otherwise).  diag_mask: bit 0 LEFTUP_TO_RIGHTDOWN, bit 1
+// (after the last column too, as the host loop does) -- ONE read-back at the end (row_pair_walk).  Bosonic configurations: the
+// walkers' own table, no configuration override active (status 3 otherwise).  diag_mask: bit 0 LEFTUP_TO_RIGHTDOWN, bit 1
 // LEFTDOWN_TO_RIGHTUP.  val_out [n][Lx - 1][2] (complex: interleaved): 0.0 for a diagonal that is not in the mask and for an identity
-// move.  The intermediate tensors of a plaquette are those of replace_nnn_trace (one pair of bten2_steps over the candidates); the
+// move.  The intermediate tensors of a plaquette are those of replace_nnn_trace (plaquette_halves over the candidates); the
 // closure is trace_dot4_kernel, which writes psi' = res exp(lsum) straight into the value table.
 // A diagonal that is masked off, or the identity for EVERY walker (the host mirror of the configurations tells), is no candidate at
-// all: it launches nothing and keeps the zero the table starts with (the `any` test of the per-bond hooks); a plaquette without
-// candidates only shifts the window.
+// all (the `any` test of the per-bond hooks); a plaquette without candidates only shifts the window.
 template <typename T>
 void Engine<T>::nnn_exchange_slice(int row1, int diag_mask, double *val_out) {
   require_ready();
   PG_REQUIRE(val_out, 1, "null buffer");
-  PG_REQUIRE(row1 >= 0 && row1 + 1 < Ly_ && Lx_ >= 2, 1, "diagonal slice: row pair outside the lattice");
-  PG_REQUIRE(diag_mask >= 1 && diag_mask <= 3, 1, "diagonal slice: diag_mask must be 1, 2 or 3");
-  const int row2 = row1 + 1, sites = Ly_ * Lx_, np = Lx_ - 1;
-  // (the candidate kernel reads the walkers' own configuration table for all four sites of a plaquette: a configuration override
-  // -- cfg_override_slice, a BMPSWalker operation -- would be ignored where the per-plaquette calls honour it, so it is refused)
-  PG_REQUIRE(!ovr_on_, 3, "diagonal slice: a configuration override is active (bosonic configurations only)");
-  (void)bmps_at_slice(UP, row1);                                              // (status 3 before anything is touched)
-  (void)bmps_at_slice(DOWN, row2);
-  const size_t nval = (size_t)kOut * nw_ * np * 2;
-  ArenaBuf<double> dval(arena_, nval);
+  const int sites = Ly_ * Lx_, np = Lx_ - 1;
   ArenaBuf<int> dcand(arena_, 10 * (size_t)nw_);                              // candidates [n][2][4], flags [n][2]
   int *dflag = dcand + 8 * (size_t)nw_;
-  PG_CHECK_HIP(hipMemsetAsync(dval, 0, sizeof(double) * nval, stream_));
-  init_bten2(LEFT, row1);
-  grow_full_bten2(RIGHT, row1, 2, 1);
-  for (int col1 = 0; col1 < np; ++col1) {
-    const int col2 = col1 + 1;
-    const int s0 = row1 * Lx_ + col1, s1 = row2 * Lx_ + col1, s2 = row2 * Lx_ + col2, s3 = row1 * Lx_ + col2;
-    int kinds[2] = {0, 0}, nc = 0;
-    for (int kind = 0; kind < 2; ++kind) {
-      if (!((diag_mask >> kind) & 1)) continue;
-      const int sa = kind == LEFTUP_TO_RIGHTDOWN ? s0 : s1, sb = kind == LEFTUP_TO_RIGHTDOWN ? s2 : s3;
-      bool any = false;
-      for (int w = 0; w < nw_ && !any; ++w) any = hcfg_[(size_t)w * sites + sa] != hcfg_[(size_t)w * sites + sb];
-      if (any) kinds[nc++] = kind;
-    }
-    if (nc > 0) {
-      ArenaScope scope(arena_);
-      const int nb = nw_ * nc;
-      hipLaunchKernelGGL(nnn_diag_cand_kernel, dim3((nb + 255) / 256), dim3(256), 0, stream_, (const int *)cfg_, sites, s0, s1, s2, s3, nc,
-                         kinds[0], kinds[nc - 1], dcand, dflag, nw_);
-      PG_CHECK_HIP(hipGetLastError());
-      const BMPSDev &up = bmps_at_slice(UP, row1), &dn = bmps_at_slice(DOWN, row2);
-      PG_REQUIRE(bten2_size(LEFT) > col1, 3, "diagonal slice: LEFT BTen2 missing");
-      const BTenDev &lb = bten2_[LEFT][col1], &rb = bten2_at_slice(RIGHT, col2);
-      const SitePick t0{row1, col1, 0}, t1{row2, col1, 1}, t2{row2, col2, 2}, t3{row1, col2, 3};
-      double *lsum = zeros_f64();
-      BTenDev a = bten2_step(LEFT, lb, at_logical(up, UP, col1), pick(t0, dcand, 4), pick(t1, dcand, 4), at_logical(dn, DOWN, col1), nc, 1,
-                             false, dflag);
-      BTenDev b = bten2_step(RIGHT, rb, at_logical(dn, DOWN, col2), pick(t2, dcand, 4), pick(t3, dcand, 4), at_logical(up, UP, col2), nc, 1,
-                             false, dflag);
-      add_logs(lsum, up.logscale, dn.logscale, lb.logscale, rb.logscale);
-      PG_REQUIRE(a.t.d[0] == b.t.d[3] && a.t.d[1] == b.t.d[2] && a.t.d[2] == b.t.d[1] && a.t.d[3] == b.t.d[0], 3,
-                 "trace: two-row environment bond mismatch");
-      hipLaunchKernelGGL((trace_dot4_kernel<T, Acc>), dim3(nb), dim3(256), 0, stream_, (const T *)a.t.p, (const T *)b.t.p, a.t.n, a.t.d[0],
-                         a.t.d[1], a.t.d[2], a.t.d[3], (const double *)lsum, (const int *)dflag, nc, kinds[0], kinds[nc - 1], (long)np * 2,
-                         dval + (size_t)kOut * 2 * col1);
-      PG_CHECK_HIP(hipGetLastError());
-      free_ten(a.t); free_ten(b.t);
-      arena_.free(lsum);
-    }
-    shift_bten2_window(RIGHT, row1);
-  }
-  PG_CHECK_HIP(hipMemcpyAsync(val_out, dval, sizeof(double) * nval, hipMemcpyDeviceToHost, stream_));
-  PG_CHECK_HIP(hipStreamSynchronize(stream_));
+  const int replaced[4] = {0, 1, 2, 3};
+  row_pair_walk(
+      "diagonal slice", row1, diag_mask, (size_t)kOut * nw_ * np * 2, val_out,
+      [&](int w, int sa, int sb) { return hcfg_[(size_t)w * sites + sa] != hcfg_[(size_t)w * sites + sb]; },
+      [&] {
+        // (the candidate kernel reads the walkers' own configuration table for all four sites of a plaquette: a configuration override
+        // -- cfg_override_slice, a BMPSWalker operation -- would be ignored where the per-plaquette calls honour it, so it is refused)
+        PG_REQUIRE(!ovr_on_, 3, "diagonal slice: a configuration override is active (bosonic configurations only)");
+        init_bten2(LEFT, row1);
+        grow_full_bten2(RIGHT, row1, 2, 1);
+      },
+      [&](const RowPairPlaq &p, double *dval) {
+        const int nc = p.nc, k0 = p.kinds[0], k1 = p.kinds[nc - 1];
+        hipLaunchKernelGGL(nnn_diag_cand_kernel, dim3((nw_ * nc + 255) / 256), dim3(256), 0, stream_, (const int *)cfg_, sites, p.s[0],
+                           p.s[1], p.s[2], p.s[3], nc, k0, k1, (int *)dcand, dflag, nw_);
+        PG_CHECK_HIP(hipGetLastError());
+        PG_REQUIRE(bten2_size(LEFT) > p.col1, 3, "diagonal slice: LEFT BTen2 missing");
+        PlaqHalves h = plaquette_halves(row1, p.col1, bten2_[LEFT][p.col1], bten2_at_slice(RIGHT, p.col1 + 1), dcand, 4, replaced, nc, dflag);
+        close_dot4(h, nc, dflag, k0, k1, (long)np * 2, dval + (size_t)kOut * 2 * p.col1);
+      },
+      [&](int) { shift_bten2_window(RIGHT, row1); }, [](double *) {});
   nnn_slice_calls() += 1;
 }
 
@@ -551,6 +568,17 @@ __global__ void nnn_hop_sign_kernel(double *__restrict__ val, const int *__restr
     for (int z = 0; z < ko; ++z) val[e * ko + z] = -val[e * ko + z];
 }
 
+// occ [d] (0 / 1 each, d <= 32) as the bit mask nnn_hop_cand_kernel takes; status 1 otherwise
+inline unsigned hop_occ_bits(int d, const int32_t *occ) {
+  PG_REQUIRE(d >= 1 && d <= 32, 1, "fermionic hop: 1 <= d <= 32 physical states");
+  unsigned bits = 0;
+  for (int s = 0; s < d; ++s) {
+    PG_REQUIRE(occ[s] == 0 || occ[s] == 1, 1, "fermionic hop: occupation numbers must be 0 or 1");
+    bits |= (unsigned)occ[s] << s;
+  }
+  return bits;
+}
+
 inline std::atomic<long> &nnn_hop_slice_calls() {   // completed nnn_hop_slice_fermion calls of the process
   static std::atomic<long> n{0};
   return n;
@@ -571,121 +599,66 @@ template <typename T>
 void Engine<T>::nnn_hop_slice_fermion(int row1, int d, const int32_t *occ, int diag_mask, double *psi_out, double *val_out) {
   require_ready();
   PG_REQUIRE(psi_out && val_out && occ, 1, "null buffer");
-  PG_REQUIRE(row1 >= 0 && row1 + 1 < Ly_ && Lx_ >= 2, 1, "hop slice: row pair outside the lattice");
-  PG_REQUIRE(diag_mask >= 1 && diag_mask <= 3, 1, "hop slice: diag_mask must be 1, 2 or 3");
-  PG_REQUIRE(d >= 1 && d <= 32 && 4 * d == dp_, 1, "hop slice: the context's physical dimension must be 4 d (extended states), d <= 32");
-  unsigned occ_bits = 0;
-  for (int s = 0; s < d; ++s) {
-    PG_REQUIRE(occ[s] == 0 || occ[s] == 1, 1, "hop slice: occupation numbers must be 0 or 1");
-    occ_bits |= (unsigned)occ[s] << s;
-  }
-  PG_REQUIRE(!ovr_on_ && bten2_active_ == 0, 3, "hop slice: a configuration override or the second BTen2 set is active");
+  PG_REQUIRE(d >= 1 && 4 * d == dp_, 1, "hop slice: the context's physical dimension must be 4 d (extended states), d <= 32");
+  const unsigned occ_bits = hop_occ_bits(d, occ);
   const int row2 = row1 + 1, sites = Ly_ * Lx_, np = Lx_ - 1;
-  (void)bmps_at_slice(UP, row1);                                              // (status 3 before anything is touched)
-  (void)bmps_at_slice(DOWN, row2);
-  for (int w = 0; w < nw_; ++w)
-    for (int r = row1; r <= row2; ++r)
-      for (int c = 0; c < Lx_; ++c)
-        PG_REQUIRE(hcfg_[(size_t)w * sites + r * Lx_ + c] / d < 2, 3, "hop slice: column-major extended states (variant >= 2) in the row pair");
   auto hocc = [&](int w, int s) { return (occ_bits >> (hcfg_[(size_t)w * sites + s] % d)) & 1u; };
-  const size_t npsi = (size_t)kOut * nw_ * np, nval = 2 * npsi;
-  ArenaBuf<double> dval(arena_, npsi + nval);                                 // psi [n][np], then val [n][np][2]
-  double *dpsi = dval, *dhop = dval + npsi;
+  const size_t npsi = (size_t)kOut * nw_ * np, nval = 2 * npsi;               // the table: psi [n][np], then val [n][np][2]
   ArenaBuf<int> dflip(arena_, 2 * (size_t)nw_ * sites);                       // the table with row1 flipped, with row2 flipped
   int *flip0 = dflip, *flip1 = dflip + (size_t)nw_ * sites;
   ArenaBuf<int> dcand(arena_, 14 * (size_t)nw_ + 2 * (size_t)nw_ * np);       // own [n][4], candidates [n][2][4], flags [n][2], signs [n][np][2]
   int *down = dcand, *dhcand = dcand + 4 * (size_t)nw_, *dflag = dcand + 12 * (size_t)nw_, *dsign = dcand + 14 * (size_t)nw_;
-  PG_CHECK_HIP(hipMemsetAsync(dval, 0, sizeof(double) * (npsi + nval), stream_));
-  PG_CHECK_HIP(hipMemsetAsync(dsign, 0, sizeof(int) * 2 * (size_t)nw_ * np, stream_));
-  {
-    const long ne = (long)nw_ * sites;
-    const unsigned gf = (unsigned)((ne + 255) / 256);
-    hipLaunchKernelGGL(nnn_flip_row_kernel, dim3(gf), dim3(256), 0, stream_, (const int *)cfg_, flip0, sites, Lx_, row1, d, nw_);
-    hipLaunchKernelGGL(nnn_flip_row_kernel, dim3(gf), dim3(256), 0, stream_, (const int *)cfg_, flip1, sites, Lx_, row2, d, nw_);
-    PG_CHECK_HIP(hipGetLastError());
-  }
-  struct Restore {
-    Engine<T> &e;
-    ~Restore() {
-      e.ovr_on_ = false; e.ovr_cfg_ = nullptr;
-      if (e.bten2_active_ != 0) { for (int p = 0; p < 4; ++p) std::swap(e.bten2_[p], e.bten2_inactive_[p]); e.bten2_active_ = 0; }
-    }
-  } restore{*this};
-  // BTen2 set `set` active, row `row` read from `tab` (nullptr: the walkers' own table everywhere)
-  auto use = [&](int set, const int *tab, int row) {
-    bten2_select_set(set);
-    ovr_on_ = tab != nullptr; ovr_hor_ = true; ovr_num_ = row; ovr_cfg_ = tab; ovr_tens_ = nullptr; ovr_nt_ = 0;
-  };
-  use(0, nullptr, -1);
-  grow_full_bten2(RIGHT, row1, 2, 1);
-  init_bten2(LEFT, row1);
-  use(1, flip0, row1);
-  grow_full_bten2(RIGHT, row1, 2, 1);
-  use(1, flip1, row2);
-  init_bten2(LEFT, row1);
-  for (int col1 = 0; col1 < np; ++col1) {
-    const int col2 = col1 + 1;
-    const int s0 = row1 * Lx_ + col1, s1 = row2 * Lx_ + col1, s2 = row2 * Lx_ + col2, s3 = row1 * Lx_ + col2;
-    int kinds[2] = {0, 0}, nc = 0;
-    for (int kind = 0; kind < 2; ++kind) {
-      if (!((diag_mask >> kind) & 1)) continue;
-      const int sa = kind == LEFTUP_TO_RIGHTDOWN ? s0 : s1, sb = kind == LEFTUP_TO_RIGHTDOWN ? s2 : s3;
-      bool any = false;
-      for (int w = 0; w < nw_ && !any; ++w) any = hocc(w, sa) != hocc(w, sb);
-      if (any) kinds[nc++] = kind;
-    }
-    if (nc > 0) {      // (set 1 is the active one here)
-      ArenaScope scope(arena_);
-      const int nb = nw_ * nc, kr = Lx_ - 1 - col2;
-      hipLaunchKernelGGL(nnn_hop_cand_kernel, dim3((nb + 255) / 256), dim3(256), 0, stream_, (const int *)cfg_, sites, s0, s1, s2, s3, d,
-                         occ_bits, nc, kinds[0], kinds[nc - 1], down, dhcand, dflag, dsign + 2 * col1, (long)np * 2, nw_);
-      PG_CHECK_HIP(hipGetLastError());
-      const BMPSDev &up = bmps_at_slice(UP, row1), &dn = bmps_at_slice(DOWN, row2);
-      const SitePick t0{row1, col1, 0}, t1{row2, col1, 1}, t2{row2, col2, 2}, t3{row1, col2, 3};
-      for (int set = 0; set < 2; ++set) {
-        const std::vector<BTenDev> &ls = (set == bten2_active_ ? bten2_ : bten2_inactive_)[LEFT];
-        const std::vector<BTenDev> &rs = (set == bten2_active_ ? bten2_ : bten2_inactive_)[RIGHT];
-        PG_REQUIRE((int)ls.size() > col1 && kr >= 0 && kr < (int)rs.size(), 3, "hop slice: BTen2 environment missing");
-        const BTenDev &lb = ls[col1], &rb = rs[kr];
-        const int *tab = set == 0 ? down : dhcand, *fl = set == 0 ? nullptr : dflag;
-        const int ncs = set == 0 ? 1 : nc;
-        double *lsum = zeros_f64();
-        BTenDev a = bten2_step(LEFT, lb, at_logical(up, UP, col1), pick(t0, tab, 4), pick(t1, tab, 4), at_logical(dn, DOWN, col1), ncs, 1,
-                               false, fl);
-        BTenDev b = bten2_step(RIGHT, rb, at_logical(dn, DOWN, col2), pick(t2, tab, 4), pick(t3, tab, 4), at_logical(up, UP, col2), ncs, 1,
-                               false, fl);
-        add_logs(lsum, up.logscale, dn.logscale, lb.logscale, rb.logscale);
-        PG_REQUIRE(a.t.d[0] == b.t.d[3] && a.t.d[1] == b.t.d[2] && a.t.d[2] == b.t.d[1] && a.t.d[3] == b.t.d[0], 3,
-                   "trace: two-row environment bond mismatch");
-        if (set == 0)
-          hipLaunchKernelGGL((trace_dot4_kernel<T, Acc>), dim3(nw_), dim3(256), 0, stream_, (const T *)a.t.p, (const T *)b.t.p, a.t.n,
-                             a.t.d[0], a.t.d[1], a.t.d[2], a.t.d[3], (const double *)lsum, (const int *)nullptr, 1, 0, 0, (long)np,
-                             dpsi + (size_t)kOut * col1);
-        else
-          hipLaunchKernelGGL((trace_dot4_kernel<T, Acc>), dim3(nb), dim3(256), 0, stream_, (const T *)a.t.p, (const T *)b.t.p, a.t.n,
-                             a.t.d[0], a.t.d[1], a.t.d[2], a.t.d[3], (const double *)lsum, (const int *)dflag, nc, kinds[0], kinds[nc - 1],
-                             (long)np * 2, dhop + (size_t)kOut * 2 * col1);
-        PG_CHECK_HIP(hipGetLastError());
-        free_ten(a.t); free_ten(b.t);
-        arena_.free(lsum);
-      }
-    }
-    if (col1 + 2 < Lx_) {      // both LEFT chains advance over column col1 (set 1 under the flipped row row2)
-      grow_bten2_step(LEFT, row1);
-      use(0, nullptr, -1);
-      grow_bten2_step(LEFT, row1);
-      use(1, flip1, row2);
-    }
-  }
-  use(0, nullptr, -1);
-  {
-    const long ne = (long)nw_ * np * 2;
-    hipLaunchKernelGGL(nnn_hop_sign_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream_, dhop, (const int *)dsign, kOut, ne);
-    PG_CHECK_HIP(hipGetLastError());
-  }
+  const int replaced[4] = {0, 1, 2, 3};
   std::vector<double> h(npsi + nval);
-  PG_CHECK_HIP(hipMemcpyAsync(h.data(), dval, sizeof(double) * h.size(), hipMemcpyDeviceToHost, stream_));
-  PG_CHECK_HIP(hipStreamSynchronize(stream_));
+  TwistScope twist{*this};
+  row_pair_walk(
+      "hop slice", row1, diag_mask, npsi + nval, h.data(), [&](int w, int sa, int sb) { return hocc(w, sa) != hocc(w, sb); },
+      [&] {
+        PG_REQUIRE(!ovr_on_ && bten2_active_ == 0, 3, "hop slice: a configuration override or the second BTen2 set is active");
+        for (int w = 0; w < nw_; ++w)
+          for (int s = row1 * Lx_; s < (row2 + 1) * Lx_; ++s)
+            PG_REQUIRE(hcfg_[(size_t)w * sites + s] / d < 2, 3, "hop slice: column-major extended states (variant >= 2) in the row pair");
+        PG_CHECK_HIP(hipMemsetAsync(dsign, 0, sizeof(int) * 2 * (size_t)nw_ * np, stream_));
+        const unsigned gf = (unsigned)(((long)nw_ * sites + 255) / 256);
+        hipLaunchKernelGGL(nnn_flip_row_kernel, dim3(gf), dim3(256), 0, stream_, (const int *)cfg_, flip0, sites, Lx_, row1, d, nw_);
+        hipLaunchKernelGGL(nnn_flip_row_kernel, dim3(gf), dim3(256), 0, stream_, (const int *)cfg_, flip1, sites, Lx_, row2, d, nw_);
+        PG_CHECK_HIP(hipGetLastError());
+        twist.use(0, nullptr, -1);
+        grow_full_bten2(RIGHT, row1, 2, 1);
+        init_bten2(LEFT, row1);
+        twist.use(1, flip0, row1);
+        grow_full_bten2(RIGHT, row1, 2, 1);
+        twist.use(1, flip1, row2);
+        init_bten2(LEFT, row1);
+      },
+      [&](const RowPairPlaq &p, double *dval) {      // (set 1 is the active one here)
+        const int nc = p.nc, k0 = p.kinds[0], k1 = p.kinds[nc - 1], col1 = p.col1, kr = Lx_ - 2 - col1;
+        hipLaunchKernelGGL(nnn_hop_cand_kernel, dim3((nw_ * nc + 255) / 256), dim3(256), 0, stream_, (const int *)cfg_, sites, p.s[0], p.s[1],
+                           p.s[2], p.s[3], d, occ_bits, nc, k0, k1, down, dhcand, dflag, dsign + 2 * col1, (long)np * 2, nw_);
+        PG_CHECK_HIP(hipGetLastError());
+        for (int set = 0; set < 2; ++set) {          // psi from the walkers' own four states, then jw psi' from the hopped ones
+          const std::vector<BTenDev> &ls = bten2_of_set(set, LEFT), &rs = bten2_of_set(set, RIGHT);
+          PG_REQUIRE((int)ls.size() > col1 && kr >= 0 && kr < (int)rs.size(), 3, "hop slice: BTen2 environment missing");
+          const int *tab = set == 0 ? down : dhcand, *fl = set == 0 ? nullptr : dflag;
+          PlaqHalves hv = plaquette_halves(row1, col1, ls[col1], rs[kr], tab, 4, replaced, set == 0 ? 1 : nc, fl);
+          if (set == 0) close_dot4(hv, 1, nullptr, 0, 0, (long)np, dval + (size_t)kOut * col1);
+          else close_dot4(hv, nc, dflag, k0, k1, (long)np * 2, dval + npsi + (size_t)kOut * 2 * col1);
+        }
+      },
+      [&](int col1) {
+        if (col1 + 2 >= Lx_) return;
+        grow_bten2_step(LEFT, row1);                 // both LEFT chains advance over column col1 (set 1 under the flipped row row2)
+        twist.use(0, nullptr, -1);
+        grow_bten2_step(LEFT, row1);
+        twist.use(1, flip1, row2);
+      },
+      [&](double *dval) {
+        twist.use(0, nullptr, -1);
+        const long ne = (long)nw_ * np * 2;
+        hipLaunchKernelGGL(nnn_hop_sign_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream_, dval + npsi, (const int *)dsign,
+                           kOut, ne);
+        PG_CHECK_HIP(hipGetLastError());
+      });
   std::copy(h.begin(), h.begin() + npsi, psi_out);
   std::copy(h.begin() + npsi, h.end(), val_out);
   nnn_hop_slice_calls() += 1;

@@ -224,6 +224,36 @@ long pepsgpu_diag_nnn_hop_slice_calls(void);
  * hop; flag_out [n][2] = -1 where the hop is allowed, else 1 (the skip-flag convention of the slice).  Needs a device, no context. */
 int pepsgpu_diag_fermion_hop_cand(int rows, int cols, int d, const int32_t *occ, int n, const int32_t *ext, int row1, int col1,
                                   int32_t *cand_out, int32_t *sign_out, int32_t *flag_out);
+/* The links of a row pair or a column pair on the device, every element type: the bodies of the row-pair loop and of the column-pair
+ * loop of the triangular J1-J2 model (spin_onehalf_triangle_heisenbergJ1J2_sqrpeps.h:350-398, :425-442) with ONE read-back and no
+ * upload.  (r, c) is the upper-left site of the window; bit k of link_mask requests kind k:
+ *   PEPSGPU_HORIZONTAL (slice1 = row r, rows r, r + 1; N = cols)
+ *     0  diagonal (r, c)-(r + 1, c + 1)                   1  diagonal (r + 1, c)-(r, c + 1)
+ *     2  flat link (r, c)-(r + 1, c + 2)                  3  flat link (r + 1, c)-(r, c + 2)
+ *     InitBTen2(LEFT, r), GrowFullBTen2(RIGHT, r, 2, true), then per column ReplaceNNNSiteTrace of each requested diagonal,
+ *     ReplaceSqrt5DistTwoSiteTrace of each requested flat link and ShiftBTen2Window(RIGHT, r), after the last column too.  Needs the UP
+ *     boundary MPS at r and the DOWN one at r + 1.
+ *   PEPSGPU_VERTICAL (slice1 = column c, columns c, c + 1; N = rows >= 3)
+ *     2  steep link (r, c)-(r + 2, c + 1)                 3  steep link (r + 2, c)-(r, c + 1)
+ *     InitBTen2(UP, c), GrowFullBTen2(DOWN, c, 3, true), then per row the ReplaceSqrt5DistTwoSiteTrace of each requested steep link and
+ *     ShiftBTen2Window(DOWN, c) while r + 3 < rows.  Needs the LEFT boundary MPS at c and the RIGHT one at c + 1.
+ *   val_out  [n][N - 1][4] (PEPSGPU_C128: interleaved (re, im)): the amplitude of the configuration with the two end states of link
+ *            `kind` of window position j exchanged; exactly 0.0 for a kind that is not in the mask, for equal end states (the identity:
+ *            the caller decides it from the configuration) and for a position without such a link (the last column / row).
+ * The BTen2 stacks end as the per-call sequence leaves them.  Status PEPSGPU_EINVAL: a bad orientation, slice1 outside the lattice,
+ * link_mask outside 1..15, bit 0 or 1 in a vertical call, a vertical call on fewer than three rows, a NULL buffer; PEPSGPU_ESTATE: a
+ * boundary MPS of the pair is missing, or a configuration override is active (bosonic configurations only, as
+ * pepsgpu_nnn_exchange_slice).  A refused call leaves the context usable. */
+int pepsgpu_link_exchange_slice(pepsgpu_ctx *ctx, int orient, int slice1, int link_mask, double *val_out);
+/* Completed pepsgpu_link_exchange_slice calls of this process (all contexts); pepsgpu_diag_nnn_slice_calls does not count them. */
+long pepsgpu_diag_link_slice_calls(void);
+/* The candidate kernel of the sqrt5 links of pepsgpu_link_exchange_slice alone, on the caller's configurations cfg [n][rows][cols]
+ * (states in [0, phys_dim)) for the window at (row1, col1): 2 x 3 for PEPSGPU_HORIZONTAL, 3 x 2 for PEPSGPU_VERTICAL.  cand_out
+ * [n][2][4]: the states of the window's corners (upper-left, lower-left, lower-right, upper-right) with the ends of link kind 2, then of
+ * kind 3, exchanged; flag_out [n][2] = -1 where the end states differ, else 1 (the skip-flag convention of the slice).  Needs a device,
+ * no context. */
+int pepsgpu_diag_link_cand(int rows, int cols, int phys_dim, int n, const int32_t *cfg, int orient, int row1, int col1, int32_t *cand_out,
+                           int32_t *flag_out);
 
 /* BMPSWalker as an object -- BMPSContractor::GetWalker / class BMPSWalker, bmps_contractor.h:357-646, bmps/impl/bmps_walker.h:13-465.
  * A walker holds the fork of the top BMPS of stack `pos` for every Monte-Carlo walker of the context (deep copy; the stacks are not

@@ -26,7 +26,7 @@ SYMBOLS = [
     "pepsgpu_walkers_set_configs", "pepsgpu_walkers_get_configs", "pepsgpu_n_walkers",
     "pepsgpu_grow_bmps_step", "pepsgpu_grow_full_bmps", "pepsgpu_grow_bmps_for_row", "pepsgpu_grow_bmps_for_col",
     "pepsgpu_shift_bmps_window", "pepsgpu_delete_inner_bmps", "pepsgpu_bmps_park", "pepsgpu_bmps_unpark", "pepsgpu_generate_bmps_approach",
-    "pepsgpu_sweep_slice_exchange", "pepsgpu_sweep_slice_exchange_tab", "pepsgpu_sweep_slice_fullspace", "pepsgpu_sweep_slice_tnn3", "pepsgpu_diag_tnn3_table", "pepsgpu_nn_exchange_slice", "pepsgpu_nn_exchange_slice_tab", "pepsgpu_onsite_slice", "pepsgpu_nnn_exchange_slice", "pepsgpu_diag_nnn_slice_calls", "pepsgpu_nnn_hop_slice_fermion", "pepsgpu_diag_nnn_hop_slice_calls", "pepsgpu_diag_fermion_hop_cand", "pepsgpu_walker_create", "pepsgpu_walker_clone", "pepsgpu_walker_destroy", "pepsgpu_walker_info", "pepsgpu_walker_set_mpo", "pepsgpu_walker_evolve",
+    "pepsgpu_sweep_slice_exchange", "pepsgpu_sweep_slice_exchange_tab", "pepsgpu_sweep_slice_fullspace", "pepsgpu_sweep_slice_tnn3", "pepsgpu_diag_tnn3_table", "pepsgpu_nn_exchange_slice", "pepsgpu_nn_exchange_slice_tab", "pepsgpu_onsite_slice", "pepsgpu_nnn_exchange_slice", "pepsgpu_diag_nnn_slice_calls", "pepsgpu_nnn_hop_slice_fermion", "pepsgpu_diag_nnn_hop_slice_calls", "pepsgpu_diag_fermion_hop_cand", "pepsgpu_link_exchange_slice", "pepsgpu_diag_link_slice_calls", "pepsgpu_diag_link_cand", "pepsgpu_walker_create", "pepsgpu_walker_clone", "pepsgpu_walker_destroy", "pepsgpu_walker_info", "pepsgpu_walker_set_mpo", "pepsgpu_walker_evolve",
     "pepsgpu_walker_evolve_step", "pepsgpu_walker_contract_row", "pepsgpu_walker_init_bten", "pepsgpu_walker_grow_bten_step",
     "pepsgpu_walker_shift_bten_window", "pepsgpu_walker_trace_with_bten", "pepsgpu_walker_clear_bten", "pepsgpu_walker_get_bmps_tensor",
     "pepsgpu_bmps_stack_size", "pepsgpu_get_bmps_tensor", "pepsgpu_init_bten", "pepsgpu_grow_full_bten",
@@ -114,6 +114,10 @@ def load_library(path=LIB_PATH):
     lib.pepsgpu_diag_nnn_hop_slice_calls.argtypes = []
     lib.pepsgpu_diag_nnn_hop_slice_calls.restype = C.c_long
     lib.pepsgpu_diag_fermion_hop_cand.argtypes = [C.c_int, C.c_int, C.c_int, ip, C.c_int, ip, C.c_int, C.c_int, ip, ip, ip]
+    lib.pepsgpu_link_exchange_slice.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp]
+    lib.pepsgpu_diag_link_slice_calls.argtypes = []
+    lib.pepsgpu_diag_link_slice_calls.restype = C.c_long
+    lib.pepsgpu_diag_link_cand.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, ip, ip]
     lib.pepsgpu_diag_dot4.argtypes = [C.c_int, vp, vp, ip, C.c_int, dp, ip, dp]
     lib.pepsgpu_onsite_slice.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, dp, dp]
     lib.pepsgpu_walker_create.argtypes = [vp, C.c_int, C.c_int, ip]
@@ -372,6 +376,17 @@ class Context:
         end states; one read-back"""
         val = np.zeros((self.n, self.cols - 1, 2), dtype=self._ot)
         self._ck(self._l.pepsgpu_nnn_exchange_slice(self._h, row1, diag_mask, _dp(val)))
+        return val
+
+    def link_exchange_slice(self, orient, slice1, link_mask):
+        """the links of the row pair (HORIZONTAL, slice1 = row r) or column pair (VERTICAL, slice1 = column c): [n][N - 1][4] amplitudes
+        with the two end states of link `kind` of the window at position j exchanged (N = cols / rows).  HORIZONTAL kinds: 0 diagonal
+        (r, c)-(r+1, c+1), 1 diagonal (r+1, c)-(r, c+1), 2 flat link (r, c)-(r+1, c+2), 3 flat link (r+1, c)-(r, c+2); VERTICAL kinds: 2
+        steep link (r, c)-(r+2, c+1), 3 steep link (r+2, c)-(r, c+1).  link_mask has one bit per kind; 0 for a masked-off kind, equal end
+        states and a position without such a link; one read-back"""
+        N = self.cols if orient == HORIZONTAL else self.rows
+        val = np.zeros((self.n, max(N - 1, 1), 4), dtype=self._ot)
+        self._ck(self._l.pepsgpu_link_exchange_slice(self._h, orient, slice1, link_mask, _dp(val)))
         return val
 
     def nnn_hop_slice_fermion(self, row1, nf, diag_mask=3):
@@ -966,6 +981,24 @@ def diag_fermion_hop_cand(ext, nf, row1, col1):
     if rc != 0:
         raise ValueError("diag_fermion_hop_cand: status %d" % rc)
     return cand, sign, flag
+
+
+def diag_link_slice_calls():
+    """completed pepsgpu_link_exchange_slice calls of this process"""
+    return int(lib().pepsgpu_diag_link_slice_calls())
+
+
+def diag_link_cand(cfgs, d, orient, row1, col1):
+    """link_sqrt5_cand_kernel alone: cfgs [n][rows][cols] states in [0, d); returns (cand [n][2][4], flag [n][2]) of the 2 x 3
+    (HORIZONTAL) or 3 x 2 (VERTICAL) window at (row1, col1): the corner states (upper-left, lower-left, lower-right, upper-right) with
+    the ends of link kind 2 (entry 0) and kind 3 (entry 1) exchanged, flag -1 where the ends differ else 1"""
+    c = np.ascontiguousarray(cfgs, dtype=np.int32)
+    n, rows, cols = c.shape
+    cand, flag = np.zeros((n, 2, 4), dtype=np.int32), np.zeros((n, 2), dtype=np.int32)
+    rc = lib().pepsgpu_diag_link_cand(rows, cols, int(d), n, _ip(c), orient, row1, col1, _ip(cand), _ip(flag))
+    if rc != 0:
+        raise ValueError("diag_link_cand: status %d" % rc)
+    return cand, flag
 
 
 def diag_nnn_slice_calls():

@@ -205,6 +205,38 @@ int pepsgpu_diag_fermion_hop_cand(int rows, int cols, int d, const int32_t *occ,
     (void)hipFree(dcfg); (void)hipFree(dout);
   });
 }
+// spin_onehalf_triangle_heisenbergJ1J2_sqrpeps.h:350-398 / :425-442: the links of one row pair / column pair
+int pepsgpu_link_exchange_slice(pepsgpu_ctx *ctx, int orient, int slice1, int link_mask, double *val_out) {
+  CTX_CALL(PG_REQUIRE(val_out, 1, "null buffer"); ctx->eng->link_exchange_slice(orient, slice1, link_mask, val_out));
+}
+long pepsgpu_diag_link_slice_calls(void) { return pepsgpu::link_slice_calls().load(); }
+// link_sqrt5_cand_kernel alone on a caller's configurations cfg [n][rows][cols] for the window at (row1, col1): cand_out [n][2][4],
+// flag_out [n][2], entry 0 LEFTUP_TO_RIGHTDOWN (kind 2), entry 1 LEFTDOWN_TO_RIGHTUP (kind 3)
+int pepsgpu_diag_link_cand(int rows, int cols, int phys_dim, int n, const int32_t *cfg, int orient, int row1, int col1, int32_t *cand_out,
+                           int32_t *flag_out) {
+  return guarded(nullptr, [&]() {
+    PG_REQUIRE(cfg && cand_out && flag_out, 1, "null buffer");
+    PG_REQUIRE(orient == HORIZONTAL || orient == VERTICAL, 1, "bad orientation");
+    PG_REQUIRE(rows >= 2 && cols >= 2 && phys_dim >= 1 && n >= 1 && (double)n * rows * cols < 2147483648.0, 1, "bad sizes");
+    const int dr = orient == VERTICAL ? 2 : 1, dc = orient == VERTICAL ? 1 : 2;
+    PG_REQUIRE(row1 >= 0 && row1 + dr < rows && col1 >= 0 && col1 + dc < cols, 1, "window outside the lattice");
+    const int sites = rows * cols;
+    const size_t ne = (size_t)n * sites;
+    for (size_t e = 0; e < ne; ++e) PG_REQUIRE(cfg[e] >= 0 && cfg[e] < phys_dim, 1, "state outside [0, phys_dim)");
+    int *dcfg, *dout;
+    PG_CHECK_HIP(hipMalloc(&dcfg, ne * sizeof(int)));
+    PG_CHECK_HIP(hipMalloc(&dout, 10 * (size_t)n * sizeof(int)));
+    int *dc_ = dout, *df = dout + 8 * (size_t)n;
+    PG_CHECK_HIP(hipMemcpy(dcfg, cfg, ne * sizeof(int), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(link_sqrt5_cand_kernel, dim3((2 * n + 255) / 256), dim3(256), 0, 0, (const int *)dcfg, sites, cols,
+                       orient == VERTICAL ? 1 : 0, row1, col1, 2, (int)LEFTUP_TO_RIGHTDOWN, (int)LEFTDOWN_TO_RIGHTUP, dc_, df, n);
+    PG_CHECK_HIP(hipGetLastError());
+    PG_CHECK_HIP(hipDeviceSynchronize());
+    PG_CHECK_HIP(hipMemcpy(cand_out, dc_, 8 * (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    PG_CHECK_HIP(hipMemcpy(flag_out, df, 2 * (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    (void)hipFree(dcfg); (void)hipFree(dout);
+  });
+}
 int pepsgpu_walker_create(pepsgpu_ctx *ctx, int pos, int level, int *walker_out) {
   CTX_CALL(check_pos(pos); PG_REQUIRE(walker_out != nullptr, 1, "null output"); *walker_out = ctx->eng->walker_create(pos, level));
 }

@@ -131,6 +131,7 @@ struct EngineBase {
                                  double *psi_out, double *val_out) = 0;
   // the diagonal bonds of the row pair (row1, row1 + 1) (square_nnn_energy_solver.h:203-265); engine_sweep.h
   virtual void nnn_exchange_slice(int row1, int diag_mask, double *val_out) = 0;
+  virtual void link_exchange_slice(int orient, int slice1, int link_mask, double *val_out) = 0;
   virtual void nnn_hop_slice_fermion(int row1, int d, const int32_t *occ, int diag_mask, double *psi_out, double *val_out) = 0;
   // BMPSWalker (bmps_contractor.h:357-646)
   virtual int walker_create(int pos, int level) = 0;
@@ -971,6 +972,7 @@ class Engine : public EngineBase {
   void energy_slice_impl(int mode, int orient, int slice, int punch_holes, const int32_t *table, int n_cand, int psi_per_bond,
                          double *psi_out, double *val_out) override;
   void nnn_exchange_slice(int row1, int diag_mask, double *val_out) override;
+  void link_exchange_slice(int orient, int slice1, int link_mask, double *val_out) override;
   void nnn_hop_slice_fermion(int row1, int d, const int32_t *occ, int diag_mask, double *psi_out, double *val_out) override;
   // the parts the slice functions share (engine_sweep.h)
   void begin_slice(const SliceGeom &g, int remain);
@@ -1490,6 +1492,8 @@ class Engine : public EngineBase {
                               int nc, const int *flag = nullptr);
   void free_halves(PlaqHalves &h) { free_ten(h.a.t); free_ten(h.b.t); arena_.free(h.lsum); }
   void close_dot4(PlaqHalves &h, int nc, const int *flag, int slot0, int slot1, long w_stride, double *out);
+  // the 2 x 3 / 3 x 2 window of the sqrt5 links as the same two halves (sqrt5_halves, engine_sweep.h)
+  PlaqHalves sqrt5_halves(int orient, int r, int c, const BTenDev &lo, const BTenDev &hi, const int *tab, int nc, const int *flag);
   // the walk over the plaquettes of a row pair that the diagonal slices share (row_pair_walk, engine_sweep.h).  s = the flat
   // site indices of (r, c), (r+1, c), (r+1, c+1), (r, c+1); kinds[0 .. nc) = the requested diagonals with work for some walker
   struct RowPairPlaq { int col1, s[4], kinds[2], nc; };

@@ -514,6 +514,154 @@ void Engine<T>::nnn_exchange_slice(int row1, int diag_mask, double *val_out) {
   nnn_slice_calls() += 1;
 }
 
+// ---- the links of a row pair and of a column pair (spin_onehalf_triangle_heisenbergJ1J2_sqrpeps.h:350-398, :425-442) ----
+// The sqrt5 links of a window are candidates of ONE replacement of its four corner sites, as the two diagonals are of a plaquette.
+// The window at (r, c) is 2 x 3 for a row pair (the flat links) and 3 x 2 for a column pair (the steep links); its corners in the order
+// upper-left, lower-left, lower-right, upper-right are
+//   HORIZONTAL  (r, c), (r+1, c), (r+1, c+2), (r, c+2)        VERTICAL  (r, c), (r+2, c), (r+2, c+1), (r, c+1).
+// cand[w][q][4] = the corner states with the ends of the q-th requested link exchanged, dir = q ? dir1 : dir0: LEFTUP_TO_RIGHTDOWN
+// exchanges the upper-left and the lower-right corner, LEFTDOWN_TO_RIGHTUP the lower-left and the upper-right one; the other two
+// corners keep their own states.  flag[w][q] (the batch_flag convention of the tensor GEMM): >= 0 where the end states are equal (the
+// move is the identity and has no contraction), -1 where the entry has work.
+__global__ void link_sqrt5_cand_kernel(const int *__restrict__ cfg, int sites, int Lx, int vertical, int r, int c, int nc, int dir0,
+                                       int dir1, int *__restrict__ cand, int *__restrict__ flag, int n) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n * nc) return;
+  const int w = e / nc, q = e - w * nc, dir = q ? dir1 : dir0;
+  const int dr = vertical ? 2 : 1, dc = vertical ? 1 : 2;
+  const long cw = (long)w * sites;
+  const int c0 = cfg[cw + r * Lx + c], c1 = cfg[cw + (r + dr) * Lx + c], c2 = cfg[cw + (r + dr) * Lx + c + dc], c3 = cfg[cw + r * Lx + c + dc];
+  int *o = cand + 4 * (long)e;
+  if (dir == LEFTUP_TO_RIGHTDOWN) { o[0] = c2; o[1] = c1; o[2] = c0; o[3] = c3; flag[e] = c0 == c2 ? 1 : -1; }
+  else { o[0] = c0; o[1] = c3; o[2] = c2; o[3] = c1; flag[e] = c1 == c3 ? 1 : -1; }
+}
+
+inline std::atomic<long> &link_slice_calls() {   // completed link_exchange_slice calls of the process (pepsgpu_diag_link_slice_calls)
+  static std::atomic<long> n{0};
+  return n;
+}
+
+// The 2 x 3 / 3 x 2 window at (r, c) between the two-row environments lo (LEFT / UP, before the window) and hi (RIGHT / DOWN, behind
+// it): the three steps of replace_sqrt5_trace over the candidates tab [entry][4] (the corner order of link_sqrt5_cand_kernel), the
+// middle column / row in the walkers' own states.  HORIZONTAL: a = lo grown over column c, then over column c + 1, b = hi over column
+// c + 2; VERTICAL: a = hi grown over row r + 2, then over row r + 1, b = lo over row r.  The halves have the index structure
+// finish_dot4 and trace_dot4_kernel close.  flag: the entry_flag of bten2_step.
+template <typename T>
+typename Engine<T>::PlaqHalves Engine<T>::sqrt5_halves(int orient, int r, int c, const BTenDev &lo, const BTenDev &hi, const int *tab,
+                                                       int nc, const int *flag) {
+  PlaqHalves h;
+  h.lsum = zeros_f64();
+  BTenDev a;
+  if (orient == HORIZONTAL) {
+    const int r2 = r + 1, c2 = c + 1, c3 = c + 2;
+    const BMPSDev &up = bmps_at_slice(UP, r), &dn = bmps_at_slice(DOWN, r2);
+    const SitePick m0{r, c, 0}, m1{r2, c, 1}, m5{r2, c3, 2}, m4{r, c3, 3}, m2{r, c2, -1}, m3{r2, c2, -1};
+    a = bten2_step(LEFT, lo, at_logical(up, UP, c), pick(m0, tab, 4), pick(m1, tab, 4), at_logical(dn, DOWN, c), nc, 1, false, flag);
+    h.b = bten2_step(RIGHT, hi, at_logical(dn, DOWN, c3), pick(m5, tab, 4), pick(m4, tab, 4), at_logical(up, UP, c3), nc, 1, false, flag);
+    h.a = bten2_step(LEFT, a, at_logical(up, UP, c2), pick(m2, tab, 4), pick(m3, tab, 4), at_logical(dn, DOWN, c2), nc, nc, false, flag);
+    add_logs(h.lsum, up.logscale, dn.logscale, lo.logscale, hi.logscale);
+  } else {
+    const int r2 = r + 1, r3 = r + 2, c2 = c + 1;
+    const BMPSDev &lf = bmps_at_slice(LEFT, c), &rt = bmps_at_slice(RIGHT, c2);
+    const SitePick m4{r, c, 0}, m0{r3, c, 1}, m1{r3, c2, 2}, m5{r, c2, 3}, m2{r2, c, -1}, m3{r2, c2, -1};
+    a = bten2_step(DOWN, hi, at_logical(lf, LEFT, r3), pick(m0, tab, 4), pick(m1, tab, 4), at_logical(rt, RIGHT, r3), nc, 1, false, flag);
+    h.b = bten2_step(UP, lo, at_logical(rt, RIGHT, r), pick(m5, tab, 4), pick(m4, tab, 4), at_logical(lf, LEFT, r), nc, 1, false, flag);
+    h.a = bten2_step(DOWN, a, at_logical(lf, LEFT, r2), pick(m2, tab, 4), pick(m3, tab, 4), at_logical(rt, RIGHT, r2), nc, nc, false, flag);
+    add_logs(h.lsum, lf.logscale, rt.logscale, lo.logscale, hi.logscale);
+  }
+  free_ten(a.t);
+  PG_REQUIRE(h.a.t.d[0] == h.b.t.d[3] && h.a.t.d[1] == h.b.t.d[2] && h.a.t.d[2] == h.b.t.d[1] && h.a.t.d[3] == h.b.t.d[0], 3,
+             "trace: two-row environment bond mismatch");
+  return h;
+}
+
+// One row pair (HORIZONTAL, slice1 = row r) or column pair (VERTICAL, slice1 = column c) of the link pass of the triangular J1-J2 model
+// on the device, ONE read-back at the end and no upload.  link_mask bit k requests kind k:
+//   HORIZONTAL  0 diagonal (r, c)-(r+1, c+1), 1 diagonal (r+1, c)-(r, c+1), 2 flat link (r, c)-(r+1, c+2), 3 flat link (r+1, c)-(r, c+2);
+//   VERTICAL    2 steep link (r, c)-(r+2, c+1), 3 steep link (r+2, c)-(r, c+1)   (bits 0 and 1: status 1).
+// HORIZONTAL: InitBTen2(LEFT, r), GrowFullBTen2(RIGHT, r, 2, init), then per column the diagonals (plaquette_halves, as
+// nnn_exchange_slice), the flat links (sqrt5_halves) and ShiftBTen2Window(RIGHT, r), after the last column too.  VERTICAL (Ly >= 3):
+// InitBTen2(UP, c), GrowFullBTen2(DOWN, c, 3, init), then per row the steep links and ShiftBTen2Window(DOWN, c) while row + 3 < Ly.
+// Every closure is trace_dot4_kernel into the value table.  val_out [n][N - 1][4] (N = Lx / Ly; complex: interleaved): the amplitude
+// with the two end states of the link exchanged; 0.0 for a kind that is masked off, for equal end states and where the window has no
+// such link.  A kind that is the identity for EVERY walker (the host mirror tells) is no candidate, as in row_pair_walk.  Bosonic
+// configurations only: an active configuration override is status 3.
+template <typename T>
+void Engine<T>::link_exchange_slice(int orient, int slice1, int link_mask, double *val_out) {
+  require_ready();
+  PG_REQUIRE(val_out, 1, "null buffer");
+  PG_REQUIRE(orient == HORIZONTAL || orient == VERTICAL, 1, "bad orientation");
+  const bool hor = orient == HORIZONTAL;
+  PG_REQUIRE(link_mask >= 1 && link_mask <= 15, 1, "link slice: link_mask must be in [1, 15]");
+  PG_REQUIRE(hor || !(link_mask & 3), 1, "link slice: the plaquette diagonals have no vertical form");
+  PG_REQUIRE(slice1 >= 0 && slice1 + 1 < (hor ? Ly_ : Lx_), 1, "link slice: slice pair outside the lattice");
+  PG_REQUIRE(hor || Ly_ >= 3, 1, "link slice: a column pair needs three rows");
+  const int N = hor ? Lx_ : Ly_, np = N - 1, sites = Ly_ * Lx_, lo = hor ? LEFT : UP, hi = hor ? RIGHT : DOWN;
+  (void)bmps_at_slice(hor ? UP : LEFT, slice1);
+  (void)bmps_at_slice(hor ? DOWN : RIGHT, slice1 + 1);
+  // (the candidate kernels read the walkers' own configuration table, as in nnn_exchange_slice)
+  PG_REQUIRE(!ovr_on_, 3, "link slice: a configuration override is active (bosonic configurations only)");
+  const size_t ntab = (size_t)kOut * nw_ * np * 4;
+  ArenaBuf<double> dval(arena_, ntab);
+  PG_CHECK_HIP(hipMemsetAsync(dval, 0, sizeof(double) * ntab, stream_));
+  ArenaBuf<int> dcand(arena_, 10 * (size_t)nw_);                              // candidates [n][2][4], flags [n][2]
+  int *dflag = dcand + 8 * (size_t)nw_;
+  const int replaced[4] = {0, 1, 2, 3};
+  // the requested kinds among first, first + 1 whose ends (flat site indices a_q, b_q) differ for some walker
+  struct Pack { int kinds[2], nc; };
+  auto pack = [&](int first, int a0, int b0, int a1, int b1) {
+    Pack p{{0, 0}, 0};
+    for (int q = 0; q < 2; ++q) {
+      if (!((link_mask >> (first + q)) & 1)) continue;
+      const int sa = q ? a1 : a0, sb = q ? b1 : b0;
+      bool any = false;
+      for (int w = 0; w < nw_ && !any; ++w) any = hcfg_[(size_t)w * sites + sa] != hcfg_[(size_t)w * sites + sb];
+      if (any) p.kinds[p.nc++] = first + q;
+    }
+    return p;
+  };
+  const long w_stride = (long)np * 4;
+  init_bten2(lo, slice1);
+  grow_full_bten2(hi, slice1, hor ? 2 : 3, 1);
+  for (int j = 0; j + (hor ? 1 : 2) < N; ++j) {
+    double *out = dval + (size_t)kOut * 4 * j;
+    const int r = hor ? slice1 : j, c = hor ? j : slice1, s0 = r * Lx_ + c;
+    if (hor) {
+      const int s[4] = {s0, s0 + Lx_, s0 + Lx_ + 1, s0 + 1};
+      const Pack p = pack(0, s[0], s[2], s[1], s[3]);
+      if (p.nc > 0) {
+        ArenaScope scope(arena_);
+        const int k0 = p.kinds[0], k1 = p.kinds[p.nc - 1];
+        hipLaunchKernelGGL(nnn_diag_cand_kernel, dim3((nw_ * p.nc + 255) / 256), dim3(256), 0, stream_, (const int *)cfg_, sites, s[0], s[1],
+                           s[2], s[3], p.nc, k0, k1, (int *)dcand, dflag, nw_);
+        PG_CHECK_HIP(hipGetLastError());
+        PG_REQUIRE(bten2_size(LEFT) > c, 3, "link slice: LEFT BTen2 missing");
+        PlaqHalves h = plaquette_halves(r, c, bten2_[LEFT][c], bten2_at_slice(RIGHT, c + 1), dcand, 4, replaced, p.nc, dflag);
+        close_dot4(h, p.nc, dflag, k0, k1, w_stride, out);
+      }
+    }
+    if (j + 2 < N) {
+      const int dr = hor ? 1 : 2, dc = hor ? 2 : 1;
+      const int ul = s0, ll = s0 + dr * Lx_, lr = ll + dc, ur = s0 + dc;
+      const Pack p = pack(2, ul, lr, ll, ur);
+      if (p.nc > 0) {
+        ArenaScope scope(arena_);
+        const int k0 = p.kinds[0], k1 = p.kinds[p.nc - 1];
+        hipLaunchKernelGGL(link_sqrt5_cand_kernel, dim3((nw_ * p.nc + 255) / 256), dim3(256), 0, stream_, (const int *)cfg_, sites, Lx_,
+                           hor ? 0 : 1, r, c, p.nc, k0 - 2, k1 - 2, (int *)dcand, dflag, nw_);
+        PG_CHECK_HIP(hipGetLastError());
+        PG_REQUIRE(bten2_size(lo) > j, 3, "link slice: growing BTen2 missing");
+        PlaqHalves h = sqrt5_halves(orient, r, c, bten2_[lo][j], bten2_at_slice(hi, j + 2), dcand, p.nc, dflag);
+        close_dot4(h, p.nc, dflag, k0, k1, w_stride, out);
+      }
+    }
+    if (hor || j + 3 < N) shift_bten2_window(hi, slice1);
+  }
+  PG_CHECK_HIP(hipMemcpyAsync(val_out, dval, sizeof(double) * ntab, hipMemcpyDeviceToHost, stream_));
+  PG_CHECK_HIP(hipStreamSynchronize(stream_));
+  link_slice_calls() += 1;
+}
+
 // ---- the fermionic diagonal hop of a row pair (square_spinless_fermion.h:161-200, square_tJ_model.h:424-463) ----
 // A fermionic state lives on the device as extended states e = s + d v: physical state s, variant v = parity of the fermion count up
 // to and including the site in row-major order (pepsgpu.h).  The hop along a plaquette diagonal exchanges the physical states of its

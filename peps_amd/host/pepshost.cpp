@@ -126,6 +126,7 @@ template <typename TenElemT>
 void mc_energy_grad_partial_impl(int rows, int cols, int D, int d, int chi, int dtype, const double *sitps_flat, int n,
                                  int32_t *configs, const uint64_t *seeds, int updater, int model, const double *p,
                                  int warmup_sweeps, int n_samples, double *packed_out, double *accept_out) {
+  if (model < 0 || model > 4) throw std::invalid_argument("pepshost_mc_energy_grad_partial: model must be xxz, tfim, j1j2, triangle or trij1j2");
   SplitIndexTPST<TenElemT> sitps = make_state_t<TenElemT>(rows, cols, D, d, sitps_flat);
   BMPSContractorT<TenElemT> contractor(rows, cols, D, d, trunc_params(chi), n, dtype, g_device);
   TPSWaveFunctionComponentT<TenElemT> comp(sitps, make_cfg(n, rows, cols, configs), contractor);
@@ -143,6 +144,8 @@ void mc_energy_grad_partial_impl(int rows, int cols, int D, int d, int chi, int 
   SquareSpinOneHalfXXZModelOBC xxz(p[0], p[1], p[2]);
   SquareSpinOneHalfJ1J2XXZModelOBC j1j2(p[0], p[1], p[2], p[3], p[4]);
   TransverseFieldIsingSquareOBC tfim(p[0]);
+  SpinOneHalfTriHeisenbergSqrPEPS tri;
+  SpinOneHalfTriJ1J2HeisenbergSqrPEPS trij1j2(p[0]);
   GradAccumulatorT<TenElemT> acc(sitps);
   contractor.GradReset();
   for (int k = 0; k < n_samples; ++k) {
@@ -150,6 +153,8 @@ void mc_energy_grad_partial_impl(int rows, int cols, int D, int d, int chi, int 
     for (int w = 0; w < n; ++w) acc_rate[w] += rates[w];
     EnergyAndHolesT<TenElemT> eh = model == 0   ? xxz.CalEnergyAndHoles<true>(sitps, comp, true)
                                    : model == 2 ? j1j2.CalEnergyAndHoles<true>(sitps, comp, true)
+                                   : model == 3 ? tri.CalEnergyAndHoles<true>(sitps, comp, true)
+                                   : model == 4 ? trij1j2.CalEnergyAndHoles<true>(sitps, comp, true)
                                                 : tfim.CalEnergyAndHoles<true>(sitps, comp, true);
     acc.AccumulateDevice(comp, eh, false);
   }

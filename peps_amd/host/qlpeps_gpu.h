@@ -2042,7 +2042,8 @@ class SpinOneHalfTriHeisenbergSqrPEPS : public SquareNNNModelEnergySolver<SpinOn
 // distance sqrt 3: the other plaquette diagonal (r, c)-(r+1, c+1), the flat sqrt5 link (r+1, c)-(r, c+2) of a 2 x 3 window and the steep
 // sqrt5 link (r+2, c)-(r, c+1) of a 3 x 2 window.  The model has its own traversal (CalEnergyAndHolesImpl :304-446): the row pass
 // carries the horizontal bonds on BTen and both diagonals + the flat link on BTen2, the column pass the vertical bonds on BTen and the
-// steep link on BTen2 (GrowFullBTen2(DOWN, col, 3)).  Registry (:65-277): energy, spin_z, bond_energy_h / v / ur (the J2 links only
+// steep link on BTen2 (GrowFullBTen2(DOWN, col, 3)); with the device slices each row, column, row pair and column pair is ONE device
+// call (pepsgpu_nn_exchange_slice_tab, pepsgpu_link_exchange_slice).  Registry (:65-277): energy, spin_z, bond_energy_h / v / ur (the J2 links only
 // enter the energy scalar), SzSz_row / SmSp_row / SpSm_row of the middle row, SzSz_all2all (+-0.25, :449-463).
 class SpinOneHalfTriJ1J2HeisenbergSqrPEPS : public SpinOneHalfMeasurementHooks {
  public:
@@ -2176,13 +2177,51 @@ class SpinOneHalfTriJ1J2HeisenbergSqrPEPS : public SpinOneHalfMeasurementHooks {
       }
       return inv;
     };
+    // With the device slices (DeviceSlicesEnabled(), bosonic component) a row or column of h / v bonds is ONE
+    // pepsgpu_nn_exchange_slice_tab call -- under the condition of SquareNNNModelEnergySolver: no holes, or holes resident on the device
+    // -- and the links of a row pair / column pair are ONE pepsgpu_link_exchange_slice call each: the same operations in the same order
+    // on the device, one read-back each, and on_bond sees the same bonds in the same order.  PEPSHOST_NO_DEVICE_SWEEP=1 keeps the
+    // per-bond path below.
+    const bool link_slice = DeviceSlicesEnabled() && !comp.fermion;
+    const bool nn_slice = link_slice && (!calchols || holes_on_device);
+    // 0.25 for equal spins, else -0.25 + 0.5 conj(psi_ex / psi) with psi_ex = value(w) from a slice's table
+    auto slice_bond = [&](const SiteIdx &s1, const SiteIdx &s2, const std::vector<TenElemT> &inv_psi, auto value) {
+      std::vector<TenElemT> e(n, TenElemT(0.25));
+      for (size_t w = 0; w < n; ++w)
+        if (comp.config(w, s1) != comp.config(w, s2)) e[w] = -0.25 + ComplexConjugate(TenElemT(value(w) * inv_psi[w])) * 0.5;
+      return e;
+    };
+    // the h bonds of row `slice` / the v bonds of column `slice` from the device; returns 1 / psi of the slice
+    auto nn_bonds = [&](BondOrientation dir, size_t slice, bool holes) {
+      const size_t N = dir == HORIZONTAL ? cols : rows;
+      std::vector<TenElemT> psi(n), ex(n * (N - 1));
+      check_rc(pepsgpu_nn_exchange_slice_tab(c.ctx(), dir, (int)slice, holes ? 1 : 0, nullptr, 0, dptr(psi.data()), dptr(ex.data())), c.ctx());
+      out.psi_list.push_back(psi);
+      const std::vector<TenElemT> inv_psi = inverse(psi);
+      for (size_t j = 0; j + 1 < N; ++j) {
+        const SiteIdx s1 = dir == HORIZONTAL ? SiteIdx{slice, j} : SiteIdx{j, slice};
+        const SiteIdx s2 = dir == HORIZONTAL ? SiteIdx{slice, j + 1} : SiteIdx{j + 1, slice};
+        on_bond(dir == HORIZONTAL ? BOND_H : BOND_V, s1, s2, slice_bond(s1, s2, inv_psi, [&](size_t w) { return ex[w * (N - 1) + j]; }));
+      }
+      return inv_psi;
+    };
+    // the link table [n][N - 1][4] of a row pair / column pair (pepsgpu_link_exchange_slice)
+    auto links = [&](BondOrientation dir, size_t slice, int mask) {
+      std::vector<TenElemT> val(n * ((dir == HORIZONTAL ? cols : rows) - 1) * 4);
+      check_rc(pepsgpu_link_exchange_slice(c.ctx(), dir, (int)slice, mask, dptr(val.data())), c.ctx());
+      return val;
+    };
     comp.SetOrder(ROW_MAJOR);
     c.GenerateBMPSApproach(UP);                                              // :317
     for (size_t row = 0; row < rows; row++) {
+      std::vector<TenElemT> inv_psi;
+      if (nn_slice) {
+        inv_psi = nn_bonds(HORIZONTAL, row, calchols);
+      } else {
       c.InitBTen(LEFT, row);                                                 // :320
       c.GrowFullBTen(RIGHT, row, 1, true);
       out.psi_list.push_back(c.Trace({row, 0}, HORIZONTAL));                 // :322
-      const std::vector<TenElemT> inv_psi = inverse(out.psi_list.back());
+      inv_psi = inverse(out.psi_list.back());
       for (size_t col = 0; col < cols; col++) {
         const SiteIdx s1{row, col};
         if (calchols && holes_on_device) {
@@ -2200,7 +2239,17 @@ class SpinOneHalfTriJ1J2HeisenbergSqrPEPS : public SpinOneHalfMeasurementHooks {
           c.ShiftBTenWindow(RIGHT);                                          // :346
         }
       }
-      if (row + 1 < rows) {
+      }
+      if (row + 1 < rows && link_slice) {
+        const std::vector<TenElemT> val = links(HORIZONTAL, row, 1 | 2 | 8);   // both diagonals and the flat link (r+1, c)-(r, c+2)
+        for (size_t col = 0; col + 1 < cols; col++) {
+          auto kind = [&](int k) { return [&val, col, k, np = cols - 1](size_t w) { return val[(w * np + col) * 4 + k]; }; };
+          on_bond(BOND_UR, {row + 1, col}, {row, col + 1}, slice_bond({row + 1, col}, {row, col + 1}, inv_psi, kind(1)));
+          on_bond(BOND_DR, {row, col}, {row + 1, col + 1}, slice_bond({row, col}, {row + 1, col + 1}, inv_psi, kind(0)));
+          if (col + 2 < cols) on_bond(BOND_FLAT, {row + 1, col}, {row, col + 2}, slice_bond({row + 1, col}, {row, col + 2}, inv_psi, kind(3)));
+        }
+        c.ShiftBMPSWindow(DOWN);
+      } else if (row + 1 < rows) {
         c.InitBTen2(LEFT, row);                                              // :350
         c.GrowFullBTen2(RIGHT, row, 2, true);
         for (size_t col = 0; col + 1 < cols; col++) {
@@ -2228,17 +2277,28 @@ class SpinOneHalfTriJ1J2HeisenbergSqrPEPS : public SpinOneHalfMeasurementHooks {
     comp.SetOrder(COL_MAJOR);
     c.GenerateBMPSApproach(LEFT);                                            // :404
     for (size_t col = 0; col < cols; col++) {
+      std::vector<TenElemT> inv_psi;
+      if (nn_slice) {
+        inv_psi = nn_bonds(VERTICAL, col, false);
+      } else {
       c.InitBTen(UP, col);
       c.GrowFullBTen(DOWN, col, 2, true);
       out.psi_list.push_back(c.Trace({0, col}, VERTICAL));
-      const std::vector<TenElemT> inv_psi = inverse(out.psi_list.back());
+      inv_psi = inverse(out.psi_list.back());
       for (size_t row = 0; row + 1 < rows; row++) {
         const SiteIdx s1{row, col}, s2{row + 1, col};
         on_bond(BOND_V, s1, s2, Bond<TenElemT>(comp, s1, s2, inv_psi, [&](const std::vector<int32_t> &cand) {
                   return comp.ReplaceNNSiteTrace(s1, s2, VERTICAL, 1, cand); }));
         if (row + 2 < rows) c.ShiftBTenWindow(DOWN);
       }
-      if (col + 1 < cols) {
+      }
+      if (col + 1 < cols && link_slice && rows >= 3) {
+        const std::vector<TenElemT> val = links(VERTICAL, col, 8);            // the steep link (r+2, c)-(r, c+1)
+        for (size_t row = 0; row + 2 < rows; row++)
+          on_bond(BOND_STEEP, {row + 2, col}, {row, col + 1}, slice_bond({row + 2, col}, {row, col + 1}, inv_psi,
+                  [&](size_t w) { return val[(w * (rows - 1) + row) * 4 + 3]; }));
+        c.ShiftBMPSWindow(RIGHT);
+      } else if (col + 1 < cols) {
         c.InitBTen2(UP, col);                                                // :425
         c.GrowFullBTen2(DOWN, col, 3, true);
         for (size_t row = 0; row + 2 < rows; row++) {                        // :428-442 steep sqrt5 link

@@ -84,8 +84,11 @@ static inline TGemmDesc desc_tt(const SiteDims &d, bool tsw, long wZ1, long wTt,
 }
 
 // M[m,(u,k2)] = sum_{(l,a)} R_i[m,(l,a)] Tt[(l,a),(u,k2)]
+// k2_outer (with tsw, wave-per-tile route): the columns are enumerated as (k2, u), the memory order of Tt[l,a,k2,u] -- the 32
+// lanes of a column tile read 32 consecutive floats of Tt, and the tiles of k2 beyond the live bond are dead as a whole.  M keeps
+// its layout [m,(u,k2)].
 static inline TGemmDesc desc_m(const SiteDims &d, bool tsw, long wR, long wTt, long wM, int nb, const int *mdyn, int mmul,
-                               const int *live_a, const int *live_k2, bool zero_fill) {
+                               const int *live_a, const int *live_k2, bool zero_fill, bool k2_outer = false) {
   TGemmDesc g;
   g.I[2] = d.m; g.sAi[2] = d.la; g.sCi[2] = d.uk;
   g.K[1] = d.l; g.K[2] = d.a; g.sAk[1] = d.a; g.sAk[2] = 1; g.sBk[1] = d.a * d.uk; g.sBk[2] = d.uk;
@@ -95,6 +98,10 @@ static inline TGemmDesc desc_m(const SiteDims &d, bool tsw, long wR, long wTt, l
   g.dynI = mdyn; g.dynI_mul = mmul;
   g.dK[2].p = live_a;
   g.dJ[2].p = live_k2; g.dJ[2].mask = zero_fill;   // the Jacobi reads whole rows of M: dead columns are written as zeros
+  if (tsw && k2_outer) {
+    g.J[1] = d.k2; g.J[2] = d.u; g.sBj[1] = d.u; g.sBj[2] = 1; g.sCj[1] = 1; g.sCj[2] = d.k2;
+    g.dJ[1] = g.dJ[2]; g.dJ[2] = TgDyn();
+  }
   return g;
 }
 

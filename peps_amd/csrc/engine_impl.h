@@ -546,8 +546,10 @@ DTen<T> Engine<T>::carry_times_tt(AbsorbState &s, const SiteDims &d, int i, cons
   const DTen<T> &Ri = s.R[i];
   const int acc64 = acc64_stages();
   DTen<T> M = alloc_ten(d.m, d.uk, 1);
-  TGemmDesc g = desc_m(d, tsw, Ri.n, Tt.n, M.n, nw_, s.mdyn[i], s.mmul[i], s.clive[i], s.kn[i + 1], true);
   dense_site = carry_hint(*s.in, i) > 96 && d.la >= 128 && d.uk >= 128;
+  // (the LDS-tiled and workgroup-per-walker kernels of a dense site keep the (u, k2) enumeration of the columns)
+  const bool k2_outer = sizeof(T) == 4 && !dense_site && !(acc64 & 4) && (tgemm_thin() & TG_THIN_LANES);
+  TGemmDesc g = desc_m(d, tsw, Ri.n, Tt.n, M.n, nw_, s.mdyn[i], s.mmul[i], s.clive[i], s.kn[i + 1], true, k2_outer);
   g.prefer_tiled = dense_site;
   prof_begin(PROF_CONTRACT, 0.0, 2.0 * nw_ * (double)d.m * d.la * (double)d.uk);
   bool mg_done = false;

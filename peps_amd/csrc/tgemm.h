@@ -74,6 +74,10 @@ struct TGemmDesc {
   // f32 chains of 8 products into float64 registers instead, which removed a third of the error only).  For the contractions of the
   // truncation pass whose f32 accumulation shows in the amplitude of a dense state.
   int acc64 = 0;
+  // set by the launchers, never by a caller: the TG_THIN_* items the wave-per-tile bodies apply (tgemm_thin()), and the row span
+  // (floats) of a small shared B operand that tgemm_direct_kernel stages in LDS (0: B is read from global memory)
+  int thin = 0;
+  int stage_span = 0;
 
   __host__ __device__ int Itot() const { return I[0] * I[1] * I[2]; }
   __host__ __device__ int Jtot() const { return J[0] * J[1] * J[2]; }
@@ -571,11 +575,37 @@ __device__ __forceinline__ float4 tg_ldf4(const float *__restrict__ base, const 
 
 constexpr int TG_ZERO_ROW = 0x40000000;   // flag in the C-row offset table: the row exists in C but its A row reads as zero
 
-template <bool AVEC, bool BVEC>
+// Work the result does not need, left out of the wave-per-tile kernels (low-rank sites: ten live values in static extents of
+// sixteen).  PEPSGPU_TGEMM_THIN (read once per process) = 0 restores the kernels without any of it; unset = all of it; another
+// value is the sum of the items to keep, for measuring them one by one.  None of them changes a stored bit: every element of C
+// is its own accumulation chain over k in the order of the k walk, whichever lane, tile or wave holds it.
+enum : int {
+  TG_THIN_LANES = 1,    // desc_m: the columns of M = R Tt enumerated in the memory order of Tt (k2, u) -- a wave's B load is 4 lines, not 16
+  TG_THIN_TILES = 2,    // a tile whose rows or columns are all masked / beyond the extent takes neither loads nor MFMAs
+  TG_THIN_KSTEPS = 4,   // MFMA steps of the last round of a k2 run whose k values are all beyond K2 are not issued
+  TG_THIN_STAGE = 8,    // one-block route, J <= 32: the live rows of a B operand that is strided along the lanes are staged in LDS once
+  TG_THIN_CTILE = 16,   // C strided along the lanes but unit-stride along J[1]: the tile goes through LDS, a store covers runs of J[1]
+  TG_THIN_ALL = 31,
+};
+inline int tgemm_thin() {
+  static const int v = getenv("PEPSGPU_TGEMM_THIN") ? (atoi(getenv("PEPSGPU_TGEMM_THIN")) & TG_THIN_ALL) : TG_THIN_ALL;
+  return v;
+}
+// LDS of the staged B operand: 32 rows of 160 floats at the odd pitch 161 (V of a chi = 32, D = 8 site is 32 x 128); 20.1 KB,
+// six blocks per CU
+constexpr int TG_STAGE_FLOATS = 32 * 161;
+// LDS of the transposed epilogue (the same region; a launch stages B or transposes C): a 32 x 32 tile per wave at the pitch 33
+constexpr int TG_CTILE_FLOATS = 4 * 32 * 33;
+
+// KSTEPS: the body may leave out dead MFMA steps (TG_THIN_KSTEPS).  Only tgemm_direct_kernel asks for it: the tests around the
+// steps cost the chained kernels two spilled registers at six blocks per CU (profiles/lowrank_products_ab.md).
+// CTILE (tile_s: TG_CTILE_FLOATS of LDS; no sumsq): the epilogue stores the tile through LDS with the lanes along J[1] first.
+template <bool AVEC, bool BVEC, bool KSTEPS = false, bool CTILE = false>
 __device__ __forceinline__ void tg_direct_body(const TGemmDesc &d, const float *__restrict__ A, const float *__restrict__ B,
                                                float *__restrict__ C, const int Itot, const int Jtot, const int K2s,
                                                int (*offCi_s)[32], const int tile0, const int tile_step,
-                                               const float scale = 1.f, double *__restrict__ sumsq = nullptr) {
+                                               const float scale = 1.f, double *__restrict__ sumsq = nullptr,
+                                               float *__restrict__ tile_s = nullptr) {
   // scale: multiplies alpha (per-entry scale of an operand that was left unnormalised); sumsq (optional): += squares of the
   // values this lane stores.
   // Instruction budget (SQ counters, round 2: 36 VALU instructions per MFMA in the chained kernel, the launches were
@@ -599,6 +629,17 @@ __device__ __forceinline__ void tg_direct_body(const TGemmDesc &d, const float *
   const float rJ2 = __builtin_amdgcn_rcpf((float)d.J[2]), rJ1 = __builtin_amdgcn_rcpf((float)d.J[1]);
   const int kh = 4 * half;
   const bool accumulate = d.accumulate != 0;
+  const bool skip_tiles = (d.thin & TG_THIN_TILES) != 0, skip_ksteps = KSTEPS && (d.thin & TG_THIN_KSTEPS) != 0;
+  // CTILE: the column of the tile this lane STORES.  J[2] = 2^s < 32: lanes 0 .. 32 / J[2] - 1 take consecutive values of j1 (unit
+  // stride in C) at one j2, the next group the next j2 -- a permutation of the 32 columns of the tile, whatever the extents
+  int cst = l31;
+  if constexpr (CTILE) {
+    const int J2 = d.J[2];
+    if (J2 < 32 && (J2 & (J2 - 1)) == 0) {
+      const int sh = __builtin_ctz(J2);
+      cst = ((l31 & ((32 >> sh) - 1)) << sh) | (l31 >> (5 - sh));
+    }
+  }
 
   for (int t = tile0 + wave; t < ntiles; t += tile_step) {
     int tj;
@@ -606,6 +647,7 @@ __device__ __forceinline__ void tg_direct_body(const TGemmDesc &d, const float *
     const int i = ti * 32 + l31, j = tj * 32 + l31;
     unsigned oab, obb;    // byte offsets of this lane's A row / B column (0 when it does not exist)
     int ocj;              // element offset of column j in C, -1: not stored; TG_ZERO_ROW set: stored as zero
+    bool tile_live = true;   // wave-uniform: some row AND some column of the tile is multiplied (else the epilogue stores its zeros)
     {
       int i2, i1, j2, j1;
       const int qi = tg_fdivmod(i, d.I[2], rI2, i2);
@@ -622,6 +664,14 @@ __device__ __forceinline__ void tg_direct_body(const TGemmDesc &d, const float *
       const int oci = i0 * d.sCi[0] + i1 * d.sCi[1] + i2 * d.sCi[2];
       if (half == 0) offCi_s[wave][l31] = iv ? (oci | (iz ? TG_ZERO_ROW : 0)) : -1;
       ocj = jv ? ((j0 * d.sCj[0] + j1 * d.sCj[1] + j2 * d.sCj[2]) | (jz ? TG_ZERO_ROW : 0)) : -1;
+      if (skip_tiles) tile_live = __any(iv && !iz) && __any(jv && !jz);
+      if constexpr (CTILE) {     // ocj becomes that of the stored column (the loads keep the column l31: obb)
+        const int js = tj * 32 + cst;
+        const int qs = tg_fdivmod(js, d.J[2], rJ2, j2);
+        const int s0 = tg_fdivmod(qs, d.J[1], rJ1, j1);
+        const bool sz = j2 >= d.Jmask[2] || j1 >= d.Jmask[1] || s0 >= d.Jmask[0];
+        ocj = js < Jtot ? ((s0 * d.sCj[0] + j1 * d.sCj[1] + j2 * d.sCj[2]) | (sz ? TG_ZERO_ROW : 0)) : -1;
+      }
     }
     tg_f32x16 acc;
 #pragma unroll
@@ -666,41 +716,72 @@ __device__ __forceinline__ void tg_direct_body(const TGemmDesc &d, const float *
       }
     };
     float a0[4], b0[4], a1[4], b1[4];
-    auto mfma4 = [&](const float (&av)[4], const float (&bv)[4]) {
+    // r8m: the round's position in its k2 run.  Step q of the lower half-wave is k2 = 8 r8m + q (the upper half's is larger):
+    // at or beyond K2 both operands were zeroed by mask_k, the step adds 0 * 0 to accumulators that are never -0
+    auto mfma4 = [&](const int r8m, const float (&av)[4], const float (&bv)[4]) {
+      if constexpr (!KSTEPS) {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q], bv[q], acc, 0, 0, 0);
+        for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q], bv[q], acc, 0, 0, 0);
+        return;
+      }
+      const int left = skip_ksteps ? K2 - 8 * r8m : 4;     // (block-uniform; >= 1)
+      // (one chain of steps, each behind its own uniform test: a separate full-round path doubles the live accumulators -- 20 more
+      // registers, spills at six blocks per CU)
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0], bv[0], acc, 0, 0, 0);
+      if (left > 1) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1], bv[1], acc, 0, 0, 0);
+      if (left > 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[2], bv[2], acc, 0, 0, 0);
+      if (left > 3) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[3], bv[3], acc, 0, 0, 0);
     };
-    if (nrounds > 0) {
+    if (nrounds > 0 && tile_live) {
       load_raw(a0, b0);
       mask_k(0, a0, b0);
-      int rd = 0;
+      int rd = 0, r8h = 0;      // r8h: r8 of the round held in (a0, b0)
       // steady state without a conditional around the loads (the wait counters stay exact: the loads of the next round
       // are in flight while the MFMAs of this one issue)
       for (; rd + 2 < nrounds; rd += 2) {
         advance();
         const int r8b = r8;
         load_raw(a1, b1);
-        mfma4(a0, b0);
+        mfma4(r8h, a0, b0);
         mask_k(r8b, a1, b1);
         advance();
         const int r8a = r8;
         load_raw(a0, b0);
-        mfma4(a1, b1);
+        mfma4(r8b, a1, b1);
         mask_k(r8a, a0, b0);
+        r8h = r8a;
       }
       if (rd + 1 < nrounds) {     // two rounds left
         advance();
         load_raw(a1, b1);
-        mfma4(a0, b0);
+        mfma4(r8h, a0, b0);
         mask_k(r8, a1, b1);
-        mfma4(a1, b1);
+        mfma4(r8, a1, b1);
       } else {
-        mfma4(a0, b0);
+        mfma4(r8h, a0, b0);
       }
     }
     // accumulator r of this lane = row 8 (r / 4) + 4 half + (r % 4), column l31 of the tile
     const bool jzero = (ocj & TG_ZERO_ROW) != 0;
     const int ocj_e = ocj & ~TG_ZERO_ROW;
+    if constexpr (CTILE) {
+      // the wave's tile through LDS (pitch 33: the writes run along a row, the reads along a permutation of a row -- 32 banks
+      // each); then row by row, the lower half-wave the even rows: the same value acc * alpha reaches the same element of C
+      float *tw = tile_s + wave * (32 * 33);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) tw[(8 * (r >> 2) + kh + (r & 3)) * 33 + l31] = acc[r];
+      const int nrow = min(32, Itot - ti * 32);
+      for (int r = half; r < nrow; r += 2) {
+        const int oi = offCi_s[wave][r];
+        if (oi >= 0 && ocj >= 0) {
+          float *p = C + ((oi & ~TG_ZERO_ROW) + ocj_e);
+          float v = ((oi & TG_ZERO_ROW) || jzero) ? 0.f : tw[r * 33 + cst] * alpha;
+          if (accumulate) v += *p;
+          *p = v;
+        }
+      }
+      continue;
+    }
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const int4 o4 = *reinterpret_cast<const int4 *>(&offCi_s[wave][8 * g + kh]);
@@ -879,10 +960,13 @@ __device__ __forceinline__ void tg_direct_body_f64(const TGemmDesc &d, const flo
   if (sumsq) *sumsq += ss;
 }
 
-template <bool AVEC, bool BVEC, bool ACC64 = false>
+// STAGE (f32 body, scalar B loads): 1 -- the small shared B operand goes through LDS once (the route sets TGemmDesc::stage_span);
+// 2 -- the tiles of C go through LDS in the epilogue (TG_THIN_CTILE)
+template <bool AVEC, bool BVEC, bool ACC64 = false, int STAGE = 0>
 __global__ __launch_bounds__(256, ACC64 ? 4 : 6) void tgemm_direct_kernel(TGemmDesc d, const float *__restrict__ Ag,
                                                            const float *__restrict__ Bg, float *__restrict__ Cg) {
   __shared__ __attribute__((aligned(16))) int offCi_s[4][32];
+  __shared__ float s_stage[STAGE == 1 ? TG_STAGE_FLOATS : STAGE == 2 ? TG_CTILE_FLOATS : 1];
   const int b = blockIdx.z;
   if (d.batch_flag && d.batch_flag[b] >= 0) return;
   const int K2s = d.K[2];                     // static extent of k2 (vector loads stay inside it)
@@ -906,9 +990,30 @@ __global__ __launch_bounds__(256, ACC64 ? 4 : 6) void tgemm_direct_kernel(TGemmD
   if constexpr (ACC64)
     tg_direct_body_f64<AVEC, BVEC>(d, Ag + baseA, Bg + baseB, Cg + (long)(b / d.bdivC) * d.wC, Itot, Jtot, K2s, offCi_s,
                                    blockIdx.x * 4, gridDim.x * 4, d.scale_in ? d.scale_in[b] : 1.f, d.scale_out ? &ss : nullptr);
-  else
-    tg_direct_body<AVEC, BVEC>(d, Ag + baseA, Bg + baseB, Cg + (long)(b / d.bdivC) * d.wC, Itot, Jtot, K2s, offCi_s,
-                               blockIdx.x * 4, gridDim.x * 4, d.scale_in ? d.scale_in[b] : 1.f, d.scale_out ? &ss : nullptr);
+  else if constexpr (STAGE == 2)
+    tg_direct_body<AVEC, false, true, true>(d, Ag + baseA, Bg + baseB, Cg + (long)(b / d.bdivC) * d.wC, Itot, Jtot, K2s, offCi_s,
+                                            blockIdx.x * 4, gridDim.x * 4, d.scale_in ? d.scale_in[b] : 1.f, nullptr, s_stage);
+  else if constexpr (STAGE == 1) {
+    // Small shared B operand (Y = Tt V^T: the rows q of V lie 128 floats apart, so every lane of every wave asks for lines of
+    // its own): J = (1, 1, q) fits one column tile, every wave reads the same block -- its live rows are copied once, 16 bytes
+    // per lane and coalesced, into LDS at an odd pitch (the operand reads of the body hit 32 different banks) and the body
+    // walks the same (k0, k1, k2) order on the copy.  The route takes this form only when all static rows fit the buffer.
+    // (no live row: nothing is copied, every column is stored as zero whatever the body reads)
+    const int rows = min(Jtot, d.Jmask[2]), pitch = d.stage_span + 1, nvec = d.stage_span >> 2;
+    const float *Bb = Bg + baseB;
+    for (int e = threadIdx.x; e < rows * nvec; e += 256) {
+      const int r = e / nvec, c = e - r * nvec;
+      const float4 v = *reinterpret_cast<const float4 *>(Bb + (long)r * d.sBj[2] + 4 * c);
+      float *o = s_stage + r * pitch + 4 * c;
+      o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+    }
+    __syncthreads();
+    d.sBj[2] = pitch;
+    tg_direct_body<AVEC, false, true>(d, Ag + baseA, s_stage, Cg + (long)(b / d.bdivC) * d.wC, Itot, Jtot, K2s, offCi_s,
+                                      blockIdx.x * 4, gridDim.x * 4, d.scale_in ? d.scale_in[b] : 1.f, d.scale_out ? &ss : nullptr);
+  } else
+    tg_direct_body<AVEC, BVEC, true>(d, Ag + baseA, Bg + baseB, Cg + (long)(b / d.bdivC) * d.wC, Itot, Jtot, K2s, offCi_s,
+                                     blockIdx.x * 4, gridDim.x * 4, d.scale_in ? d.scale_in[b] : 1.f, d.scale_out ? &ss : nullptr);
   if (d.scale_out) {     // (gridDim.x == 1: this block stored all of C[b])
     __shared__ double s_nred[4];
     double a = ss;
@@ -1278,6 +1383,8 @@ enum TgRouteKind : int {
 struct TgRoute {
   int kind = TG_ROUTE_EMPTY;
   bool avec = false, bvec = false, acc64 = false;   // direct kernel: 16-byte loads of A / B along k2, float64 accumulation
+  int thin = 0, stage_span = 0;                     // direct kernel: TGemmDesc::thin / stage_span of the launch (not exported)
+  bool ctile = false;                               // direct kernel: transposed epilogue (TG_THIN_CTILE; not exported)
   dim3 grid;
   int code = 0;
   const char *msg = nullptr;
@@ -1313,6 +1420,20 @@ TgRoute tgemm_route(const TGemmDesc &d, const void *A, const void *B) {
       if (!(!d.scale_out || (r.grid.x == 1 && d.bdivC == 1 && !d.accumulate && !d.batch_flag)))
         return refuse(5, "tensor GEMM: the norm of the result needs one block per batch entry");
       r.kind = TG_ROUTE_DIRECT;
+      r.thin = tgemm_thin() & (TG_THIN_TILES | TG_THIN_KSTEPS);
+      // staged B: one block per entry, one column tile over a single J sub-index whose rows are strided (not unit-stride along
+      // the lanes), rows of 16-byte pieces at 16-byte offsets; span = the floats of a row the static K extents reach
+      if ((tgemm_thin() & TG_THIN_STAGE) && r.grid.x == 1 && !r.bvec && !r.acc64 && d.J[0] == 1 && d.J[1] == 1 && d.J[2] <= 32 &&
+          !d.dJ[0].p && !d.dJ[1].p && d.sBj[2] > 1 && d.sBk[0] >= 0 && d.sBk[1] >= 0 && d.sBk[2] >= 0 && d.Ktot() > 0) {
+        const long span = 1 + (long)(d.K[0] - 1) * d.sBk[0] + (long)(d.K[1] - 1) * d.sBk[1] + (long)(d.K[2] - 1) * d.sBk[2];
+        auto al4 = [](long v) { return (v & 3) == 0; };
+        if ((span + 1) * d.J[2] <= TG_STAGE_FLOATS && al4(span) && al4(d.sBj[2]) && al4(d.wB) && al4(d.selB_mul) && (((uintptr_t)B) & 15) == 0)
+          r.stage_span = (int)span;
+      }
+      // transposed epilogue: the lanes of a column tile store at a stride (J[2] innermost, sCj[2] > 1) while J[1] is unit-stride
+      // in C and J[2] a power of two below 32, so that a tile holds whole runs of J[1]; no fused norm (its summation order)
+      r.ctile = (tgemm_thin() & TG_THIN_CTILE) && !r.stage_span && !r.bvec && !r.acc64 && !d.scale_out && d.sCj[1] == 1 &&
+                d.sCj[2] > 1 && d.J[1] > 1 && d.J[2] > 1 && d.J[2] < 32 && (d.J[2] & (d.J[2] - 1)) == 0 && !(d.dJ[2].p && !d.dJ[2].mask);
       return r;
     }
   }
@@ -1355,6 +1476,8 @@ void tgemm_launch(hipStream_t s, const TGemmDesc &d_in, const TA *A, const TB *B
   d.flopc = tg_flop_counter;
   d.bytec = tg_byte_counter;
   d.flop_stride = d.nbatch >= 256 ? 64 : 1;   // one atomic per 64 walkers: a same-address atomic per block costs ~10 %
+  d.thin = r.thin;
+  d.stage_span = r.stage_span;
   switch (r.kind) {
     case TG_ROUTE_DIRECT:
       if constexpr (sizeof(TA) == 4 && sizeof(TB) == 4 && sizeof(TC) == 4 && sizeof(TAcc) == 4) {
@@ -1368,6 +1491,10 @@ void tgemm_launch(hipStream_t s, const TGemmDesc &d_in, const TA *A, const TB *B
           else if (bvec) hipLaunchKernelGGL((tgemm_direct_kernel<false, true, true>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
           else hipLaunchKernelGGL((tgemm_direct_kernel<false, false, true>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
         }
+        else if (r.stage_span > 0 && avec) hipLaunchKernelGGL((tgemm_direct_kernel<true, false, false, 1>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
+        else if (r.stage_span > 0) hipLaunchKernelGGL((tgemm_direct_kernel<false, false, false, 1>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
+        else if (r.ctile && avec) hipLaunchKernelGGL((tgemm_direct_kernel<true, false, false, 2>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
+        else if (r.ctile) hipLaunchKernelGGL((tgemm_direct_kernel<false, false, false, 2>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
         else if (avec && bvec) hipLaunchKernelGGL((tgemm_direct_kernel<true, true>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
         else if (avec) hipLaunchKernelGGL((tgemm_direct_kernel<true, false>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
         else if (bvec) hipLaunchKernelGGL((tgemm_direct_kernel<false, true>), gd, dim3(256), 0, s, d, Af, Bf, Cf);
@@ -1405,6 +1532,8 @@ inline int tgemm_chain_launch(hipStream_t s, const TGemmDesc &d1_in, const TGemm
   if (d1.Itot() >= (1 << 22) || d1.Jtot() >= (1 << 22) || d2.Itot() >= (1 << 22) || d2.Jtot() >= (1 << 22)) return 0;
   d1.flopc = tg_flop_counter; d1.bytec = tg_byte_counter;
   d1.flop_stride = d1.nbatch >= 256 ? 64 : 1;
+  d1.thin = d2.thin = tgemm_thin() & TG_THIN_TILES;
+  d1.stage_span = d2.stage_span = 0;
   constexpr bool no_vec = false;
   const bool avec1 = !no_vec && tg_vec_a(d1, A1), bvec1 = !no_vec && tg_vec_b(d1, B1), avec2 = !no_vec && tg_vec_a(d2, A2);
   const dim3 g(d1.nbatch), blk(256);
@@ -1472,6 +1601,8 @@ inline int tgemm_chain3_launch(hipStream_t s, const TGemmDesc &d1_in, const TGem
   if (per1 > ldsf || per2 > ldsf) return 0;
   d1.flopc = tg_flop_counter; d1.bytec = tg_byte_counter;
   d1.flop_stride = d1.nbatch >= 256 ? 64 : 1;
+  d1.thin = d2.thin = d3.thin = tgemm_thin() & TG_THIN_TILES;
+  d1.stage_span = d2.stage_span = d3.stage_span = 0;
   constexpr bool no_vec = false;
   const bool avec1 = !no_vec && tg_vec_a(d1, A1), bvec1 = !no_vec && tg_vec_b(d1, B1), avec2 = !no_vec && tg_vec_a(d2, A2);
   const dim3 g(d1.nbatch), blk(256);

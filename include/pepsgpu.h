@@ -277,6 +277,30 @@ int pepsgpu_walker_destroy(pepsgpu_ctx *ctx, int walker);
 /* GetPosition / GetStackSize / GetBTenLeftCol / GetBTenRightCol (any pointer may be NULL) */
 int pepsgpu_walker_info(pepsgpu_ctx *ctx, int walker, int *pos_out, int *stack_size_out, int *bten_left_col_out, int *bten_right_col_out);
 int pepsgpu_walker_set_mpo(pepsgpu_ctx *ctx, int walker, int num, const int32_t *states, const double *tensors, int n_tensors);
+/* The excited row of the structure-factor measurement (structure_factor_measurement_mixin.h:62-215: the MPO of row y1 with the tensor
+ * of the source site replaced, :127-134) without a host table: the walker's MPO becomes slice `num` under the walkers' current
+ * configurations with the state s of site `col` of that slice replaced, per walker, by state_map[s] (state_map has phys_dim entries,
+ * phys_dim <= 32).  The table the kernels read is built on the device -- a device-to-device copy of the configuration table and a
+ * one-site patch kernel -- with no upload and no synchronisation; open_out [n] (may be NULL) = 1 where state_map[s] != s, from the
+ * host's mirror of the configurations.  Afterwards the walker is exactly as after pepsgpu_walker_set_mpo(.., states, ..) with that row.
+ * UP walkers only.  Status PEPSGPU_EINVAL: NULL state_map, num or col outside the lattice, a walker that is not UP; PEPSGPU_ERANGE: a
+ * map entry outside [0, phys_dim).  A refused call leaves the walker and its MPO as they were. */
+int pepsgpu_walker_set_mpo_excited(pepsgpu_ctx *ctx, int walker, int num, int col, const int32_t *state_map, uint8_t *open_out);
+/* The scan of one target row (structure_factor_measurement_mixin.h:160-194 on bmps_walker.h:216-392) in one call with one read-back, for
+ * the walker's current MPO when that is a row named by configuration or by states (N = cols):
+ *   InitBTenLeft(opp, N), InitBTenRight(opp, N - 1), then for x2 = N - 1 .. 0: TraceWithBTen at x2 with the site's state s replaced by
+ *   site_map[s] (phys_dim entries), and GrowBTenRightStep while x2 > 0.
+ *   out [n][N] (PEPSGPU_C128: interleaved (re, im)): entry (w, x2) is that trace where walker_mask[w] != 0 (NULL: every walker) and
+ *   site_map[s] != s; every other entry is exactly 0.0.  Closed walkers are skipped inside the contraction, a position at which the
+ *   host's mirror of the MPO's states shows no open walker makes no trace launch; the right environment grows at every position.
+ * The caches end as the per-call sequence leaves them: GetBTenLeftCol == N, GetBTenRightCol == 1.  Status PEPSGPU_EINVAL: NULL site_map
+ * or out, a walker that is not UP; PEPSGPU_ERANGE: a map entry outside [0, phys_dim); PEPSGPU_ESTATE: no MPO set, an MPO given as
+ * explicit tensors (it has no state to map), opp_level not in the DOWN stack, an active configuration override.  Every check runs before
+ * a cache of the walker is released: a refused call leaves walker and context usable. */
+int pepsgpu_walker_trace_slice(pepsgpu_ctx *ctx, int walker, int opp_level, const int32_t *site_map, const uint8_t *walker_mask,
+                               double *out);
+/* Completed pepsgpu_walker_trace_slice calls of this process (all contexts).  Needs no device. */
+long pepsgpu_diag_walker_slice_calls(void);
 int pepsgpu_walker_evolve(pepsgpu_ctx *ctx, int walker);                                     /* Evolve(mpo)               :13-21  */
 int pepsgpu_walker_evolve_step(pepsgpu_ctx *ctx, int walker);                                /* EvolveStep()              :23-49  */
 int pepsgpu_walker_contract_row(pepsgpu_ctx *ctx, int walker, int opp_level, double *out);   /* ContractRow(mpo, opp)     :60-214 */

@@ -26,7 +26,7 @@ SYMBOLS = [
     "pepsgpu_walkers_set_configs", "pepsgpu_walkers_get_configs", "pepsgpu_n_walkers",
     "pepsgpu_grow_bmps_step", "pepsgpu_grow_full_bmps", "pepsgpu_grow_bmps_for_row", "pepsgpu_grow_bmps_for_col",
     "pepsgpu_shift_bmps_window", "pepsgpu_delete_inner_bmps", "pepsgpu_bmps_park", "pepsgpu_bmps_unpark", "pepsgpu_generate_bmps_approach",
-    "pepsgpu_sweep_slice_exchange", "pepsgpu_sweep_slice_exchange_tab", "pepsgpu_sweep_slice_fullspace", "pepsgpu_sweep_slice_tnn3", "pepsgpu_diag_tnn3_table", "pepsgpu_nn_exchange_slice", "pepsgpu_nn_exchange_slice_tab", "pepsgpu_onsite_slice", "pepsgpu_nnn_exchange_slice", "pepsgpu_diag_nnn_slice_calls", "pepsgpu_nnn_hop_slice_fermion", "pepsgpu_diag_nnn_hop_slice_calls", "pepsgpu_diag_fermion_hop_cand", "pepsgpu_link_exchange_slice", "pepsgpu_diag_link_slice_calls", "pepsgpu_diag_link_cand", "pepsgpu_walker_create", "pepsgpu_walker_clone", "pepsgpu_walker_destroy", "pepsgpu_walker_info", "pepsgpu_walker_set_mpo", "pepsgpu_walker_evolve",
+    "pepsgpu_sweep_slice_exchange", "pepsgpu_sweep_slice_exchange_tab", "pepsgpu_sweep_slice_fullspace", "pepsgpu_sweep_slice_tnn3", "pepsgpu_diag_tnn3_table", "pepsgpu_nn_exchange_slice", "pepsgpu_nn_exchange_slice_tab", "pepsgpu_onsite_slice", "pepsgpu_nnn_exchange_slice", "pepsgpu_diag_nnn_slice_calls", "pepsgpu_nnn_hop_slice_fermion", "pepsgpu_diag_nnn_hop_slice_calls", "pepsgpu_diag_fermion_hop_cand", "pepsgpu_link_exchange_slice", "pepsgpu_diag_link_slice_calls", "pepsgpu_diag_link_cand", "pepsgpu_walker_create", "pepsgpu_walker_clone", "pepsgpu_walker_destroy", "pepsgpu_walker_info", "pepsgpu_walker_set_mpo", "pepsgpu_walker_set_mpo_excited", "pepsgpu_walker_trace_slice", "pepsgpu_diag_walker_slice_calls", "pepsgpu_walker_evolve",
     "pepsgpu_walker_evolve_step", "pepsgpu_walker_contract_row", "pepsgpu_walker_init_bten", "pepsgpu_walker_grow_bten_step",
     "pepsgpu_walker_shift_bten_window", "pepsgpu_walker_trace_with_bten", "pepsgpu_walker_clear_bten", "pepsgpu_walker_get_bmps_tensor",
     "pepsgpu_bmps_stack_size", "pepsgpu_get_bmps_tensor", "pepsgpu_init_bten", "pepsgpu_grow_full_bten",
@@ -125,6 +125,11 @@ def load_library(path=LIB_PATH):
     lib.pepsgpu_walker_destroy.argtypes = [vp, C.c_int]
     lib.pepsgpu_walker_info.argtypes = [vp, C.c_int, ip, ip, ip, ip]
     lib.pepsgpu_walker_set_mpo.argtypes = [vp, C.c_int, C.c_int, ip, dp, C.c_int]
+    u8p = C.POINTER(C.c_uint8)
+    lib.pepsgpu_walker_set_mpo_excited.argtypes = [vp, C.c_int, C.c_int, C.c_int, ip, u8p]
+    lib.pepsgpu_walker_trace_slice.argtypes = [vp, C.c_int, C.c_int, ip, u8p, dp]
+    lib.pepsgpu_diag_walker_slice_calls.argtypes = []
+    lib.pepsgpu_diag_walker_slice_calls.restype = C.c_long
     lib.pepsgpu_walker_evolve.argtypes = [vp, C.c_int]
     lib.pepsgpu_walker_evolve_step.argtypes = [vp, C.c_int]
     lib.pepsgpu_walker_contract_row.argtypes = [vp, C.c_int, C.c_int, dp]
@@ -1001,6 +1006,11 @@ def diag_link_cand(cfgs, d, orient, row1, col1):
     return cand, flag
 
 
+def diag_walker_slice_calls():
+    """completed pepsgpu_walker_trace_slice calls of this process"""
+    return int(lib().pepsgpu_diag_walker_slice_calls())
+
+
 def diag_nnn_slice_calls():
     """completed pepsgpu_nnn_exchange_slice calls of this process"""
     return int(lib().pepsgpu_diag_nnn_slice_calls())
@@ -1097,6 +1107,30 @@ class Walker:
         t = np.ascontiguousarray(tensors, dtype=c._ot)
         assert t.ndim == 6 and t.shape[2:] == (c.D,) * 4
         c._ck(c._l.pepsgpu_walker_set_mpo(c._h, self.wid, num, None, _dp(t), t.shape[0]))
+
+    def set_mpo_excited(self, num, col, state_map):
+        """the MPO becomes row `num` under the walkers' configurations with the state s of site `col` replaced by state_map[s]
+        (phys_dim entries), built on the device; returns the open mask [n] (bool): state_map[s] != s"""
+        c = self.ctx
+        sm = np.ascontiguousarray(state_map, dtype=np.int32)
+        assert sm.shape == (c.d,), sm.shape
+        op = np.zeros(c.n, dtype=np.uint8)
+        c._ck(c._l.pepsgpu_walker_set_mpo_excited(c._h, self.wid, num, col, _ip(sm), op.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return op.astype(bool)
+
+    def trace_slice(self, opp_level, site_map, mask=None):
+        """InitBTenLeft / InitBTenRight and the right-to-left scan of TraceWithBTen + GrowBTenRightStep over the row of the current
+        MPO in one call: [n][cols], entry (w, x) = the trace with the state s of site x replaced by site_map[s] where mask[w]
+        (None: every walker) and site_map[s] != s, exactly 0 elsewhere"""
+        c = self.ctx
+        sm = np.ascontiguousarray(site_map, dtype=np.int32)
+        assert sm.shape == (c.d,), sm.shape
+        mk = None if mask is None else np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        assert mk is None or mk.shape == (c.n,), mk.shape
+        out = np.zeros((c.n, c.cols), dtype=c._ot)
+        c._ck(c._l.pepsgpu_walker_trace_slice(c._h, self.wid, opp_level, _ip(sm),
+                                              None if mk is None else mk.ctypes.data_as(C.POINTER(C.c_uint8)), _dp(out)))
+        return out
 
     def Evolve(self): self.ctx._ck(self.ctx._l.pepsgpu_walker_evolve(self.ctx._h, self.wid))
     def EvolveStep(self): self.ctx._ck(self.ctx._l.pepsgpu_walker_evolve_step(self.ctx._h, self.wid))

@@ -250,6 +250,15 @@ int pepsgpu_walker_info(pepsgpu_ctx *ctx, int walker, int *pos_out, int *stack_s
 int pepsgpu_walker_set_mpo(pepsgpu_ctx *ctx, int walker, int num, const int32_t *states, const double *tensors, int n_tensors) {
   CTX_CALL(ctx->eng->walker_set_mpo(walker, num, states, tensors, n_tensors));
 }
+// structure_factor_measurement_mixin.h:127-134: the excited row, built on the device from the walkers' configuration table
+int pepsgpu_walker_set_mpo_excited(pepsgpu_ctx *ctx, int walker, int num, int col, const int32_t *state_map, uint8_t *open_out) {
+  CTX_CALL(ctx->eng->walker_set_mpo_excited(walker, num, col, state_map, open_out));
+}
+// structure_factor_measurement_mixin.h:160-194: the scan of one target row
+int pepsgpu_walker_trace_slice(pepsgpu_ctx *ctx, int walker, int opp_level, const int32_t *site_map, const uint8_t *walker_mask, double *out) {
+  CTX_CALL(ctx->eng->walker_trace_slice(walker, opp_level, site_map, walker_mask, out));
+}
+long pepsgpu_diag_walker_slice_calls(void) { return pepsgpu::walker_slice_calls().load(); }
 int pepsgpu_walker_evolve(pepsgpu_ctx *ctx, int walker) { CTX_CALL(ctx->eng->walker_evolve(walker)); }
 int pepsgpu_walker_evolve_step(pepsgpu_ctx *ctx, int walker) { CTX_CALL(ctx->eng->walker_evolve_step(walker)); }
 int pepsgpu_walker_contract_row(pepsgpu_ctx *ctx, int walker, int opp_level, double *out) {

@@ -139,6 +139,7 @@ struct EngineBase {
   virtual void walker_destroy(int id) = 0;
   virtual void walker_info(int id, int *pos, int *stack, int *lcol, int *rcol) = 0;
   virtual void walker_set_mpo(int id, int num, const int32_t *states, const double *tensors, int n_tensors) = 0;
+  virtual void walker_set_mpo_excited(int id, int num, int col, const int32_t *state_map, uint8_t *open_out) = 0;
   virtual void walker_evolve(int id) = 0;
   virtual void walker_evolve_step(int id) = 0;
   virtual void walker_contract_row(int id, int opp_level, double *out) = 0;
@@ -147,6 +148,7 @@ struct EngineBase {
   virtual void walker_shift_bten_window(int id, int opp_level, int side) = 0;
   virtual void walker_trace(int id, int opp_level, int site_col, int two_site, const int32_t *states, const double *tensors,
                             int n_tensors, double *out) = 0;
+  virtual void walker_trace_slice(int id, int opp_level, const int32_t *site_map, const uint8_t *walker_mask, double *out) = 0;
   virtual void walker_clear_bten(int id) = 0;
   virtual void walker_get_tensor(int id, int idx, int *dims, double *out, double *logscale) = 0;
   virtual void profile_enable(int on) = 0;
@@ -985,6 +987,7 @@ class Engine : public EngineBase {
   void walker_destroy(int id) override;
   void walker_info(int id, int *pos, int *stack, int *lcol, int *rcol) override;
   void walker_set_mpo(int id, int num, const int32_t *states, const double *tensors, int n_tensors) override;
+  void walker_set_mpo_excited(int id, int num, int col, const int32_t *state_map, uint8_t *open_out) override;
   void walker_evolve(int id) override;
   void walker_evolve_step(int id) override;
   void walker_contract_row(int id, int opp_level, double *out) override;
@@ -993,6 +996,7 @@ class Engine : public EngineBase {
   void walker_shift_bten_window(int id, int opp_level, int side) override;
   void walker_trace(int id, int opp_level, int site_col, int two_site, const int32_t *states, const double *tensors, int n_tensors,
                     double *out) override;
+  void walker_trace_slice(int id, int opp_level, const int32_t *site_map, const uint8_t *walker_mask, double *out) override;
   void walker_clear_bten(int id) override;
   void walker_get_tensor(int id, int idx, int *dims, double *out, double *logscale) override;
 
@@ -1590,6 +1594,7 @@ class Engine : public EngineBase {
     int lcol = 0, rcol = 0;          // left edge (exclusive upper bound) / right edge (exclusive lower bound)
     int mpo_num = -1;                // the current TransferMPO: slice of the network ...
     int *mpo_cfg = nullptr;          // ... under another configuration table [walker][Ly * Lx] (nullptr: the walkers' own)
+    std::vector<int> mpo_hrow;       // host mirror of mpo_cfg along the slice [walker][N] (empty: no mpo_cfg, or not mirrored)
     T *mpo_tens = nullptr;           // ... or explicit tensors [site along the slice][mpo_nt][D^4 slot]
     int mpo_nt = 0;
   };
@@ -1611,6 +1616,7 @@ class Engine : public EngineBase {
   const BMPSDev &walker_opposite(const WalkerDev &w, int opp_level, const char *what);
   void walker_grow_left(WalkerDev &w, const BMPSDev &opp);
   void walker_grow_right(WalkerDev &w, const BMPSDev &opp);
+  void walker_init_side(WalkerDev &w, const BMPSDev &opp, int side, int target_col);
   SiteSel walker_site(const WalkerDev &w, int col, const int32_t *states, int sstride, const double *tensor, int n_tensors, long tstride,
                       std::vector<void *> &tmp);
 

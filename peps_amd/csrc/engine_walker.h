@@ -12,8 +12,37 @@
 // The row operations support the UP walker / DOWN opposite pair only, as the reference does (bmps_walker.h:114-118).
 #pragma once
 #include "engine.h"
+#include "engine_sweep.h"
 
 namespace pepsgpu {
+
+// A map of the states of one site handed to a kernel by value: the two calls below need no upload of their own for it
+constexpr int WK_MAXDP = 32;
+struct WalkerStateMap { int v[WK_MAXDP]; };
+
+// The site patch of an excited row (walker_set_mpo_excited): state s of site `site` of every walker's table becomes map[s]
+__global__ void walker_excite_site_kernel(int *__restrict__ tab, int sites, int site, WalkerStateMap map, int n) {
+  const int w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= n) return;
+  int *p = tab + (long)w * sites + site;
+  *p = map.v[*p];
+}
+
+// The candidates of one position of walker_trace_slice from the MPO's state table tab [n][sites]: cand[w] = map[s] for the state s of
+// `site`, skip[w] != 0 (the convention of bten_step) where the replacement is the identity or the walker is masked out (mask nullable)
+__global__ void walker_trace_cand_kernel(const int *__restrict__ tab, int sites, int site, WalkerStateMap map,
+                                         const int *__restrict__ mask, int *__restrict__ cand, int *__restrict__ skip, int n) {
+  const int w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= n) return;
+  const int s = tab[(long)w * sites + site], r = map.v[s];
+  cand[w] = r;
+  skip[w] = (r == s || (mask && !mask[w])) ? 1 : 0;
+}
+
+inline std::atomic<long> &walker_slice_calls() {   // completed walker_trace_slice calls of the process (pepsgpu_diag_walker_slice_calls)
+  static std::atomic<long> n{0};
+  return n;
+}
 
 template <typename T>
 typename Engine<T>::BMPSDev Engine<T>::copy_bmps(const BMPSDev &b) {
@@ -58,6 +87,7 @@ void Engine<T>::walker_free_mpo(WalkerDev &w) {
   if (w.mpo_cfg) arena_.free(w.mpo_cfg);
   if (w.mpo_tens) arena_.free(w.mpo_tens);
   w.mpo_cfg = nullptr; w.mpo_tens = nullptr; w.mpo_nt = 0; w.mpo_num = -1;
+  w.mpo_hrow.clear();
 }
 
 template <typename T>
@@ -150,6 +180,7 @@ void Engine<T>::walker_set_mpo(int id, int num, const int32_t *states, const dou
     w.mpo_cfg = (int *)arena_.alloc(sizeof(int) * tab.size());
     PG_CHECK_HIP(hipMemcpyAsync(w.mpo_cfg, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, stream_));
     PG_CHECK_HIP(hipStreamSynchronize(stream_));
+    w.mpo_hrow.assign(states, states + (size_t)nw_ * N);
   } else if (tensors) {
     // host [nt][N][L][D][R][U] zero padded to D^4 -> device [N][nt][slot], compact inside the slot (as the SITPS)
     std::vector<T> buf((size_t)N * n_tensors * slot_, T(0));
@@ -179,6 +210,38 @@ void Engine<T>::walker_set_mpo(int id, int num, const int32_t *states, const dou
     PG_CHECK_HIP(hipStreamSynchronize(stream_));
     ensure_iota();
   }
+}
+
+// The excited row of the structure-factor mixin (structure_factor_measurement_mixin.h:127-134: the row y1 of the network with the
+// tensor of the source site replaced) named without a host table: the walkers' configuration table is copied on the device and the
+// one site patched there, state s -> state_map[s]; no upload, no synchronisation.  open_out[w] = the map changes walker w's state
+// (from the host mirror).  Afterwards the walker is as after walker_set_mpo(states) with that row.
+template <typename T>
+void Engine<T>::walker_set_mpo_excited(int id, int num, int col, const int32_t *state_map, uint8_t *open_out) {
+  require_ready();
+  PG_REQUIRE(state_map, 1, "BMPSWalker: null state map");
+  WalkerDev &w = walker_ref(id);
+  PG_REQUIRE(w.pos == UP, 1, "BMPSWalker: unsupported direction (the excited row is a row below an UP walker)");
+  PG_REQUIRE(num >= 0 && num < Ly_ && col >= 0 && col < Lx_, 1, "BMPSWalker: excited site outside the lattice");
+  PG_REQUIRE(dp_ <= WK_MAXDP, 1, "BMPSWalker: state maps serve physical dimensions up to 32");
+  require_states(state_map, dp_, dp_, "BMPSWalker: mapped state exceeds the physical dimension");
+  WalkerStateMap map{};
+  for (int s = 0; s < dp_; ++s) map.v[s] = state_map[s];
+  const int N = Lx_, sites = Ly_ * Lx_, site = num * Lx_ + col;
+  std::vector<int> hrow((size_t)nw_ * N);
+  for (int wk = 0; wk < nw_; ++wk) {
+    const int *c = hcfg_.data() + (size_t)wk * sites + (size_t)num * Lx_;
+    std::copy(c, c + N, hrow.begin() + (size_t)wk * N);
+    hrow[(size_t)wk * N + col] = map.v[c[col]];
+    if (open_out) open_out[wk] = map.v[c[col]] != c[col];
+  }
+  walker_free_mpo(w);
+  w.mpo_num = num;
+  w.mpo_cfg = (int *)arena_.alloc(sizeof(int) * (size_t)nw_ * sites);
+  PG_CHECK_HIP(hipMemcpyAsync(w.mpo_cfg, cfg_, sizeof(int) * (size_t)nw_ * sites, hipMemcpyDeviceToDevice, stream_));
+  hipLaunchKernelGGL(walker_excite_site_kernel, dim3((nw_ + 255) / 256), dim3(256), 0, stream_, w.mpo_cfg, sites, site, map, nw_);
+  PG_CHECK_HIP(hipGetLastError());
+  w.mpo_hrow.swap(hrow);
 }
 
 template <typename T>
@@ -300,6 +363,12 @@ void Engine<T>::walker_init_bten(int id, int opp_level, int side, int target_col
   WalkerDev &w = walker_ref(id);
   const BMPSDev &opp = walker_opposite(w, opp_level, "InitBTen");
   MpoScope scope(*this, w);
+  walker_init_side(w, opp, side, target_col);
+}
+
+// InitBTenLeft / InitBTenRight (bmps_walker.h:216-272) under the MpoScope of the caller
+template <typename T>
+void Engine<T>::walker_init_side(WalkerDev &w, const BMPSDev &opp, int side, int target_col) {
   PG_REQUIRE(target_col >= 0, 1, "BMPSWalker::InitBTen: negative column");
   const int N = Lx_;
   if (side == LEFT) {
@@ -439,6 +508,76 @@ void Engine<T>::walker_trace(int id, int opp_level, int site_col, int two_site, 
   free_ten(t2.t);
   arena_.free(lsum);
   for (void *p : tmp) arena_.free(p);
+}
+
+// The body of the structure-factor mixin's target-row loop (structure_factor_measurement_mixin.h:160-194) in one call:
+// InitBTenLeft(opp, N), InitBTenRight(opp, N - 1), then for x2 = N - 1 .. 0 TraceWithBTen at x2 with the site's state s replaced by
+// site_map[s] and GrowBTenRightStep while x2 > 0 -- the launches of the per-call sequence in its order, candidates and skip flags
+// built on the device, the values collected in a table on the device, ONE read-back.  out [n][N]: the trace where walker_mask[w] != 0
+// (NULL: every walker) and site_map[s] != s, exactly 0.0 elsewhere (those walkers are skipped inside the contraction, bten_step's
+// `skip`; a position at which the host mirror shows no open walker makes no trace launch at all).
+template <typename T>
+void Engine<T>::walker_trace_slice(int id, int opp_level, const int32_t *site_map, const uint8_t *walker_mask, double *out) {
+  require_ready();
+  PG_REQUIRE(site_map && out, 1, "BMPSWalker::TraceSlice: null buffer");
+  WalkerDev &w = walker_ref(id);
+  const BMPSDev &opp = walker_opposite(w, opp_level, "TraceSlice");
+  PG_REQUIRE(dp_ <= WK_MAXDP, 1, "BMPSWalker: state maps serve physical dimensions up to 32");
+  require_states(site_map, dp_, dp_, "BMPSWalker: mapped state exceeds the physical dimension");
+  PG_REQUIRE(w.mpo_num < 0 || !w.mpo_tens, 3, "BMPSWalker::TraceSlice: the MPO is given as explicit tensors (it has no state to map)");
+  MpoScope scope(*this, w);                  // (no MPO set, configuration override: status 3 before anything is released)
+  const int N = Lx_, sites = Ly_ * Lx_;
+  WalkerStateMap map{};
+  for (int s = 0; s < dp_; ++s) map.v[s] = site_map[s];
+  // the MPO's states along the row as the host knows them: its mirror, or the walkers' own configurations
+  const bool mirrored = !w.mpo_cfg || !w.mpo_hrow.empty();
+  auto hstate = [&](int wk, int x) {
+    return w.mpo_cfg ? w.mpo_hrow[(size_t)wk * N + x] : hcfg_[(size_t)wk * sites + (size_t)w.mpo_num * Lx_ + x];
+  };
+  const int *dstates = w.mpo_cfg ? w.mpo_cfg : cfg_;
+  std::vector<int> hmask;
+  if (walker_mask) hmask.assign(walker_mask, walker_mask + nw_);
+  ArenaBuf<int> dmask(arena_, walker_mask ? (size_t)nw_ : 0);
+  if (dmask) PG_CHECK_HIP(hipMemcpyAsync(dmask, hmask.data(), sizeof(int) * nw_, hipMemcpyHostToDevice, stream_));
+  ArenaBuf<double> dval(arena_, kOut * (size_t)nw_ * N);                  // value table [n][N] of Acc scalars, zero = closed
+  PG_CHECK_HIP(hipMemsetAsync(dval, 0, sizeof(double) * kOut * (size_t)nw_ * N, stream_));
+  ArenaBuf<int> dcand(arena_, 2 * (size_t)nw_);                           // replacement state [n], skip flag [n]
+  int *dskip = dcand + nw_;
+  walker_init_side(w, opp, LEFT, N);
+  walker_init_side(w, opp, RIGHT, N - 1);
+  auto lv = [](const BMPSDev &b, int j) -> const int * { return (int)b.live.size() > j ? b.live[j] : nullptr; };
+  for (int x2 = N - 1; x2 >= 0; --x2) {
+    bool any = !mirrored;
+    for (int wk = 0; wk < nw_ && !any; ++wk) {
+      const int s = hstate(wk, x2);
+      any = map.v[s] != s && (!walker_mask || walker_mask[wk]);
+    }
+    if (any) {
+      ArenaScope ascope(arena_);               // (the temporaries of this trace; the caches grow outside it)
+      hipLaunchKernelGGL(walker_trace_cand_kernel, dim3((nw_ + 255) / 256), dim3(256), 0, stream_, dstates, sites, w.mpo_num * Lx_ + x2, map,
+                         (const int *)dmask, (int *)dcand, dskip, nw_);
+      PG_CHECK_HIP(hipGetLastError());
+      SiteSel sa{w.mpo_num, x2, dcand, 1};
+      sa.base = sitps_ + (long)(w.mpo_num * Lx_ + x2) * dp_ * slot_;
+      const int ja = N - 1 - x2;
+      const BTenDev &lb = w.btl[x2], &rb = w.btr[N - 1 - x2];
+      BTenDev t2 = bten_step(LEFT, lb, w.b.t[ja], sa, opp.t[x2], 1, false, 1, lv(w.b, ja), lv(w.b, ja + 1), lv(opp, x2), lv(opp, x2 + 1),
+                             dskip);
+      double *lsum = zeros_f64();
+      add_logs(lsum, w.b.logscale, opp.logscale, lb.logscale, rb.logscale);
+      Acc *res = finish_dot_device(t2.t, 1, rb.t, 1, 1);
+      // (a skipped walker keeps the zero its entry holds: `same` copies column x2 onto itself)
+      hipLaunchKernelGGL(slice_store_value_kernel<Acc>, dim3((nw_ + 255) / 256), dim3(256), 0, stream_, (const Acc *)res,
+                         (const double *)lsum, (double *)dval, N, x2, 1, (const int *)dskip, x2, nw_);
+      PG_CHECK_HIP(hipGetLastError());
+      free_ten(t2.t);
+      arena_.free(res); arena_.free(lsum);
+    }
+    if (x2 > 0) walker_grow_right(w, opp);
+  }
+  PG_CHECK_HIP(hipMemcpyAsync(out, dval, sizeof(double) * kOut * (size_t)nw_ * N, hipMemcpyDeviceToHost, stream_));
+  PG_CHECK_HIP(hipStreamSynchronize(stream_));
+  walker_slice_calls() += 1;
 }
 
 // ContractRow (bmps_walker.h:60-214): <walker | mpo | opposite>.  The reference multiplies the columns right to left into a

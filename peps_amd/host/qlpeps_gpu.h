@@ -369,7 +369,7 @@ class BMPSContractorT {
   // std::runtime_error conditions (size / direction / cache checks of bmps_walker.h).
   class BMPSWalker {
    public:
-    BMPSWalker(BMPSWalker &&o) noexcept : ctx_(o.ctx_), id_(o.id_), n_(o.n_) { o.id_ = -1; }
+    BMPSWalker(BMPSWalker &&o) noexcept : ctx_(o.ctx_), id_(o.id_), n_(o.n_), cols_(o.cols_) { o.id_ = -1; }
     BMPSWalker(const BMPSWalker &) = delete;
     BMPSWalker &operator=(const BMPSWalker &) = delete;
     ~BMPSWalker() { if (id_ >= 0) (void)pepsgpu_walker_destroy(ctx_, id_); }
@@ -380,6 +380,23 @@ class BMPSContractorT {
     // tensors[q][j][D^4] (leg order L, D, R, U, zero padded to D), n_tensors = 1 (shared) or the number of walkers
     void SetMPOTensors(size_t num, const std::vector<TenElemT> &tensors, size_t n_tensors) {
       check_rc(pepsgpu_walker_set_mpo(ctx_, id_, (int)num, nullptr, dptr(tensors.data()), (int)n_tensors), ctx_);
+    }
+    // The excited row of the structure-factor mixin (structure_factor_measurement_mixin.h:127-134) built on the device: row `num`
+    // under the walkers' configurations with the state s of site `col` replaced by state_map[s]; returns open[w] = the map
+    // changes walker w's state.  Same walker afterwards as SetMPOStates with that row.
+    std::vector<uint8_t> SetMPOExcited(size_t num, size_t col, const std::vector<int32_t> &state_map) {
+      std::vector<uint8_t> open(n_);
+      check_rc(pepsgpu_walker_set_mpo_excited(ctx_, id_, (int)num, (int)col, state_map.data(), open.data()), ctx_);
+      return open;
+    }
+    // The scan of one target row (:160-194) in one call: InitBTenLeft(opp, Lx), InitBTenRight(opp, Lx - 1), then right to left
+    // TraceWithBTen with the site's state s replaced by site_map[s] + GrowBTenRightStep.  [w][x2]: the trace where mask[w] (empty:
+    // every walker) and site_map[s] != s, exactly 0 elsewhere.
+    std::vector<TenElemT> TraceSlice(size_t opp_level, const std::vector<int32_t> &site_map, const std::vector<uint8_t> &mask = {}) {
+      std::vector<TenElemT> out(n_ * cols_);
+      check_rc(pepsgpu_walker_trace_slice(ctx_, id_, (int)opp_level, site_map.data(), mask.empty() ? nullptr : mask.data(), dptr(out.data())),
+               ctx_);
+      return out;
     }
     void Evolve() { check_rc(pepsgpu_walker_evolve(ctx_, id_), ctx_); }
     std::vector<TenElemT> ContractRow(size_t opp_level) const {
@@ -415,7 +432,7 @@ class BMPSContractorT {
     BMPSWalker Clone() const {                      // `auto excited_walker = main_walker;`
       int id = -1;
       check_rc(pepsgpu_walker_clone(ctx_, id_, &id), ctx_);
-      return BMPSWalker(ctx_, id, n_);
+      return BMPSWalker(ctx_, id, n_, cols_);
     }
     size_t GetBTenLeftCol() const { return (size_t)info(2); }
     size_t GetBTenRightCol() const { return (size_t)info(3); }
@@ -424,7 +441,7 @@ class BMPSContractorT {
 
    private:
     friend class BMPSContractorT;
-    BMPSWalker(pepsgpu_ctx *ctx, int id, size_t n) : ctx_(ctx), id_(id), n_(n) {}
+    BMPSWalker(pepsgpu_ctx *ctx, int id, size_t n, size_t cols) : ctx_(ctx), id_(id), n_(n), cols_(cols) {}
     int info(int k) const {
       int v[4];
       check_rc(pepsgpu_walker_info(ctx_, id_, &v[0], &v[1], &v[2], &v[3]), ctx_);
@@ -432,20 +449,20 @@ class BMPSContractorT {
     }
     pepsgpu_ctx *ctx_;
     int id_;
-    size_t n_;
+    size_t n_, cols_;
   };
   // GetWalker(tn, position) (bmps_walker.h:51-58): a detached copy of the top of the stack
   BMPSWalker GetWalker(BMPSPOSITION position) const {
     int id = -1;
     check_rc(pepsgpu_walker_create(ctx_, position, -1, &id), ctx_);
-    return BMPSWalker(ctx_, id, walkers());
+    return BMPSWalker(ctx_, id, walkers(), cols_);
   }
   // BMPSWalker(tn, GetBMPS(position)[level], position, level + 1, trunc_params): the constructor the structure-factor mixin
   // uses on the vacuum (structure_factor_measurement_mixin.h:121-122)
   BMPSWalker MakeWalker(BMPSPOSITION position, size_t level) const {
     int id = -1;
     check_rc(pepsgpu_walker_create(ctx_, position, (int)level, &id), ctx_);
-    return BMPSWalker(ctx_, id, walkers());
+    return BMPSWalker(ctx_, id, walkers(), cols_);
   }
 
   void InitBTen(BTenPOSITION p, size_t slice) { check_rc(pepsgpu_init_bten(ctx_, p, (int)slice), ctx_); }
@@ -1822,17 +1839,27 @@ struct SpinOneHalfMeasurementHooks {
     const size_t n_down = c.BMPSStackSize(DOWN);
     auto main_walker = c.MakeWalker(UP, 0);                    // BMPSWalker(tn, up_stack[0], UP, 1, trunc_params)
     const std::vector<int32_t> spin_down(n, 0);                // GetSiteTensor(y2, x2, 0)
+    // With the device slices the excited row is built on the device (SetMPOExcited) and the scan of a target row is ONE call with
+    // one read-back (TraceSlice: closed walkers skipped inside the contraction, positions closed for every walker not launched);
+    // PEPSHOST_NO_DEVICE_SWEEP=1 keeps the per-call body below.
+    const bool dev_slice = DeviceSlicesEnabled();
+    // S+ at the source: sitps(y1, x1)[1]; S- at the target: component 0 (spin one half: the maps {1, 1} and {0, 0})
+    const std::vector<int32_t> to_up(c.phys_dim(), 1), to_down(c.phys_dim(), 0);
     for (size_t y1 = 0; y1 + 1 < Ly; ++y1) {
       for (size_t x1 = 0; x1 < Lx; ++x1) {
-        std::vector<int32_t> excited(n * Lx);
         std::vector<uint8_t> src_down(n);
-        for (size_t w = 0; w < n; ++w) {
-          for (size_t x = 0; x < Lx; ++x) excited[w * Lx + x] = comp.config(w, {y1, x});
-          src_down[w] = comp.config(w, {y1, x1}) == 0;
-          if (src_down[w]) excited[w * Lx + x1] = 1;            // excited_mpo_ptrs[x1] = sitps(y1, x1)[1]
-        }
         auto excited_walker = main_walker.Clone();
-        excited_walker.SetMPOStates(y1, excited);
+        if (dev_slice) {
+          src_down = excited_walker.SetMPOExcited(y1, x1, to_up);
+        } else {
+          std::vector<int32_t> excited(n * Lx);
+          for (size_t w = 0; w < n; ++w) {
+            for (size_t x = 0; x < Lx; ++x) excited[w * Lx + x] = comp.config(w, {y1, x});
+            src_down[w] = comp.config(w, {y1, x1}) == 0;
+            if (src_down[w]) excited[w * Lx + x1] = 1;          // excited_mpo_ptrs[x1] = sitps(y1, x1)[1]
+          }
+          excited_walker.SetMPOStates(y1, excited);
+        }
         excited_walker.Evolve();                                // absorb the excited row y1
         for (size_t y2 = y1 + 1; y2 < Ly; ++y2) {
           const size_t bottom = Ly - 1 - y2;                    // bottom_env = down_stack[Ly-1-y2]
@@ -1846,19 +1873,24 @@ struct SpinOneHalfMeasurementHooks {
             continue;
           }
           excited_walker.SetMPO(y2);                            // standard_mpo = tn.get_row(y2)
-          excited_walker.InitBTenLeft(bottom, Lx);
-          excited_walker.InitBTenRight(bottom, Lx - 1);
-          std::vector<TenElemT> row(n * Lx, TenElemT(0.0));
-          for (size_t x2r = 0; x2r < Lx; ++x2r) {
-            const size_t x2 = Lx - 1 - x2r;
-            bool any = false;
-            for (size_t w = 0; w < n; ++w) any |= src_down[w] && comp.config(w, {y2, x2}) == 1;
-            if (any) {
-              std::vector<TenElemT> psi_ex = excited_walker.TraceWithBTen(bottom, x2, spin_down);
-              for (size_t w = 0; w < n; ++w)
-                if (src_down[w] && comp.config(w, {y2, x2}) == 1) row[w * Lx + x2] = psi_ex[w];
+          std::vector<TenElemT> row;
+          if (dev_slice) {
+            row = excited_walker.TraceSlice(bottom, to_down, src_down);
+          } else {
+            excited_walker.InitBTenLeft(bottom, Lx);
+            excited_walker.InitBTenRight(bottom, Lx - 1);
+            row.assign(n * Lx, TenElemT(0.0));
+            for (size_t x2r = 0; x2r < Lx; ++x2r) {
+              const size_t x2 = Lx - 1 - x2r;
+              bool any = false;
+              for (size_t w = 0; w < n; ++w) any |= src_down[w] && comp.config(w, {y2, x2}) == 1;
+              if (any) {
+                std::vector<TenElemT> psi_ex = excited_walker.TraceWithBTen(bottom, x2, spin_down);
+                for (size_t w = 0; w < n; ++w)
+                  if (src_down[w] && comp.config(w, {y2, x2}) == 1) row[w * Lx + x2] = psi_ex[w];
+              }
+              if (x2 > 0) excited_walker.GrowBTenRightStep(bottom);
             }
-            if (x2 > 0) excited_walker.GrowBTenRightStep(bottom);
           }
           for (size_t w = 0; w < n; ++w)
             for (size_t x2 = 0; x2 < Lx; ++x2) {

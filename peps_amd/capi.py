@@ -43,7 +43,7 @@ SYMBOLS = [
     "pepsgpu_sr_cg_solve", "pepsgpu_sr_gram", "pepsgpu_sr_weighted_sum", "pepsgpu_sr_copy_samples",
     "pepsgpu_update_local", "pepsgpu_erase_envs_after_update", "pepsgpu_evaluate_amplitude",
     "pepsgpu_walker_flags", "pepsgpu_sync", "pepsgpu_stats", "pepsgpu_profile_enable", "pepsgpu_profile_read",
-    "pepsgpu_diag_tgemm", "pepsgpu_diag_tgemm_desc", "pepsgpu_diag_tgemm_route", "pepsgpu_diag_tgemm_chain", "pepsgpu_diag_tgemm_chain3", "pepsgpu_diag_chol", "pepsgpu_diag_chol_adaptive", "pepsgpu_diag_chol_pivot", "pepsgpu_diag_rows_qr", "pepsgpu_diag_suwa_todo", "pepsgpu_diag_dot4", "pepsgpu_diag_gram_chol", "pepsgpu_diag_gram_cols", "pepsgpu_diag_gram_rows", "pepsgpu_diag_mgemm_dense", "pepsgpu_diag_jacobi", "pepsgpu_version",
+    "pepsgpu_diag_tgemm", "pepsgpu_diag_tgemm_desc", "pepsgpu_diag_tgemm_route", "pepsgpu_diag_tgemm_chain", "pepsgpu_diag_tgemm_chain3", "pepsgpu_diag_chol", "pepsgpu_diag_chol_adaptive", "pepsgpu_diag_chol_pivot", "pepsgpu_diag_rows_qr", "pepsgpu_diag_suwa_todo", "pepsgpu_diag_dot4", "pepsgpu_diag_gram_chol", "pepsgpu_diag_gram_chol_wave", "pepsgpu_diag_gram_cols", "pepsgpu_diag_gram_rows", "pepsgpu_diag_mgemm_dense", "pepsgpu_diag_jacobi", "pepsgpu_version",
 ]
 
 
@@ -875,6 +875,27 @@ def diag_gram_chol(dtype, P):
     rc = lib().pepsgpu_diag_gram_chol(dtype, P.ctypes.data_as(C.c_void_p), K, n, nb, R.ctypes.data_as(C.c_void_p), _ip(ml))
     if rc != 0:
         raise RuntimeError("diag_gram_chol failed: %s" % lib().pepsgpu_last_error(None).decode())
+    return R, ml
+
+
+def diag_gram_chol_wave(P, klive, inner=1, inner_live=None, max_pass=3, form=1, fill=0.0):
+    """One of the two one-wave factor kernels alone (form 0: gram_chol_wave_kernel, 1: gram_chol_wave_split_kernel), then the
+    list kernel for the walkers it hands on; P = [nb][K][n] float32, klive[b] live rows, inner_live[b] (optional) live inner
+    indices of the (outer, inner) columns; returns (R [nb][n][n] float32, `fill` where nothing was stored, mlive)."""
+    P = np.ascontiguousarray(P, dtype=np.float32)
+    nb, K, n = P.shape
+    kl = np.ascontiguousarray(klive, dtype=np.int32)
+    il = None if inner_live is None else np.ascontiguousarray(inner_live, dtype=np.int32)
+    assert kl.shape == (nb,) and (il is None or il.shape == (nb,))
+    R = np.full((nb, n, n), fill, dtype=np.float32)
+    ml = np.zeros(nb, dtype=np.int32)
+    f = lib().pepsgpu_diag_gram_chol_wave
+    fp = C.POINTER(C.c_float)
+    f.argtypes = [fp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, fp,
+                  C.POINTER(C.c_int32)]
+    rc = f(P.ctypes.data_as(fp), K, n, nb, _ip(kl), inner, None if il is None else _ip(il), max_pass, form, R.ctypes.data_as(fp), _ip(ml))
+    if rc != 0:
+        raise RuntimeError("diag_gram_chol_wave failed: %s" % lib().pepsgpu_last_error(None).decode())
     return R, ml
 
 

@@ -799,6 +799,50 @@ extern "C" int pepsgpu_diag_gram_chol(int dtype, const void *P, int K, int n, in
     else diag_gram_chol_t<double, 48>(P, K, n, nbatch, R_out, mlive_out);
   });
 }
+// One of the two one-wave factor kernels alone (form 0: gram_chol_wave_kernel, 1: gram_chol_wave_split_kernel), then the list
+// kernel for the walkers it hands on: P = [nbatch][K][n] f32, klive[b] live rows, columns (outer, inner) with inner_live[b]
+// (optional) live inner indices; mlive_out[b] < 0 where the list kernel declines as well
+extern "C" int pepsgpu_diag_gram_chol_wave(const float *P, int K, int n, int nbatch, const int32_t *klive, int inner,
+                                           const int32_t *inner_live, int max_pass, int form, float *R_out, int32_t *mlive_out) {
+  return guarded(nullptr, [&]() {
+    PG_REQUIRE(K >= 1 && n >= 1 && n <= 256 && nbatch >= 1 && inner >= 1 && n % inner == 0 && max_pass >= 1 && klive, 1, "bad sizes");
+    PG_REQUIRE(form == 0 || form == 1, 1, "form is 0 or 1");
+    const size_t np = (size_t)K * n * nbatch, nr = (size_t)n * n * nbatch;
+    float *dP, *dR;
+    int *dml, *dk, *dil = nullptr, *dl;
+    PG_CHECK_HIP(hipMalloc(&dP, np * sizeof(float)));
+    PG_CHECK_HIP(hipMalloc(&dR, nr * sizeof(float)));
+    PG_CHECK_HIP(hipMalloc(&dml, nbatch * sizeof(int)));
+    PG_CHECK_HIP(hipMalloc(&dk, nbatch * sizeof(int)));
+    PG_CHECK_HIP(hipMalloc(&dl, (nbatch + 1) * sizeof(int)));
+    PG_CHECK_HIP(hipMemcpy(dP, P, np * sizeof(float), hipMemcpyHostToDevice));
+    PG_CHECK_HIP(hipMemcpy(dR, R_out, nr * sizeof(float), hipMemcpyHostToDevice));     // what no kernel stores comes back as it went in
+    PG_CHECK_HIP(hipMemcpy(dk, klive, nbatch * sizeof(int), hipMemcpyHostToDevice));
+    PG_CHECK_HIP(hipMemset(dml, 0xff, nbatch * sizeof(int)));
+    PG_CHECK_HIP(hipMemset(dl, 0, (nbatch + 1) * sizeof(int)));
+    if (inner_live) {
+      PG_CHECK_HIP(hipMalloc(&dil, nbatch * sizeof(int)));
+      PG_CHECK_HIP(hipMemcpy(dil, inner_live, nbatch * sizeof(int), hipMemcpyHostToDevice));
+    }
+    const auto wave_kernel = form ? gram_chol_wave_split_kernel : gram_chol_wave_kernel;
+    hipLaunchKernelGGL(wave_kernel, dim3((nbatch + 3) / 4), dim3(256), 0, 0, (const float *)dP, (long)K * n, n, (const int *)dk, 1, K, dR,
+                       (long)n * n, dml, inner, (const int *)dil, max_pass, nbatch, dl);
+    PG_CHECK_HIP(hipGetLastError());
+    if (n <= 128)
+      hipLaunchKernelGGL((gram_chol_lowrank_list_kernel<float, 96, 128>), dim3(std::min(nbatch, 512)), dim3(128), 0, 0, (const float *)dP,
+                         (long)K * n, n, (const int *)dk, 1, K, dR, (long)n * n, dml, inner, (const int *)dil, 2, max_pass, (const int *)dl,
+                         (const int *)(dl + nbatch));
+    else
+      hipLaunchKernelGGL((gram_chol_lowrank_list_kernel<float, 96, 256>), dim3(std::min(nbatch, 512)), dim3(256), 0, 0, (const float *)dP,
+                         (long)K * n, n, (const int *)dk, 1, K, dR, (long)n * n, dml, inner, (const int *)dil, 2, max_pass, (const int *)dl,
+                         (const int *)(dl + nbatch));
+    PG_CHECK_HIP(hipGetLastError());
+    PG_CHECK_HIP(hipDeviceSynchronize());
+    PG_CHECK_HIP(hipMemcpy(R_out, dR, nr * sizeof(float), hipMemcpyDeviceToHost));
+    PG_CHECK_HIP(hipMemcpy(mlive_out, dml, nbatch * sizeof(int), hipMemcpyDeviceToHost));
+    (void)hipFree(dP); (void)hipFree(dR); (void)hipFree(dml); (void)hipFree(dk); (void)hipFree(dl); if (dil) (void)hipFree(dil);
+  });
+}
 // gram_cols_f64_kernel alone: P = [nbatch][K][n] of type T, klive[b] (optional) = live rows; G_out = [nbatch][n][n] float64,
 // blocks on or above the diagonal (64 x 64 granularity) written, the rest left at zero
 template <typename T>

@@ -1086,6 +1086,236 @@ __global__ __launch_bounds__(256, 2) void gram_chol_wave_kernel(const float *__r
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The same factor with the rows of P placed BY ROW PARITY for the dot products of a pivot step (the loop the kernel above lives
+// in: per row one v_readlane, three conversions and two FMAs, the second column slot of a lane a quarter full on the low-rank
+// sites).  Lane (h, l) = (lane >> 5, lane & 31) holds, for the column slots s = 0 .. S-1 (column l + 32 s, S = ceil(ncols / 32),
+// wave-uniform), the rows k = 2 j + h of the pass: one wave instruction advances the even-row chain g of a column in the lower
+// half of the wave and its odd-row chain h in the upper half, the pivot entry of a row pair is fetched once (ds_bpermute inside
+// each half: the LDS crossbar, no LDS allocation) and converted once, and an empty slot issues nothing (one loop body per (S,
+// slot of the pivot)).  1 + 2 S VALU instructions per row PAIR where the kernel above issues 12.
+// OWNERSHIP is the kernel's above (lane L: columns L and L + 64 -- factor entries, running diagonals, candidates, row norms,
+// stores), and every floating-point operation of every column is the same in the same order: slots 0 / 2 of the lower half and
+// 1 / 3 of the upper half are the lane's own columns, so one v_permlane32_swap of (slot 0, slot 1) and of (slot 2, slot 3)
+// hands each owner the g and h of its two columns, and the same swap of the stored rows gives it rows 2 j and 2 j + 1 of its
+// columns for the diagonals (one chain over k in row order) and takes the folded factor rows of a later pass back.
+__device__ __forceinline__ void gw_swap32(float &a, float &b) {     // a of lanes 32-63 <-> b of lanes 0-31
+  const auto p = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
+  a = __builtin_bit_cast(float, (unsigned)p[0]);
+  b = __builtin_bit_cast(float, (unsigned)p[1]);
+}
+__device__ __forceinline__ void gw_swap32_f64(double &a, double &b) {
+  const auto pl = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
+  const auto ph = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
+  a = __hiloint2double((int)ph[0], (int)pl[0]);
+  b = __hiloint2double((int)ph[1], (int)pl[1]);
+}
+// acc[s] of lane (h, l) += sum_j P[2 j + h][f] P[2 j + h][l + 32 s], s < S; PS = f >> 5, addr = byte address of lane (h, f & 31)
+template <int S, int PS>
+__device__ __forceinline__ void gw_split_dot(const float (&pp)[4][32], const int K, const int addr, double (&acc)[4]) {
+  // the pivot entries travel one chunk of CH row pairs ahead of the FMAs that use them (a ds_bpermute answers after about as
+  // long as one chunk's arithmetic takes to issue; left to itself the scheduler fetches one pair ahead and waits on every pair)
+  constexpr int CH = 4;
+  int pf[2][CH];
+#pragma unroll
+  for (int i = 0; i < CH; ++i) pf[0][i] = __builtin_amdgcn_ds_bpermute(addr, __builtin_bit_cast(int, pp[PS][i]));
+#pragma unroll
+  for (int jb = 0; jb < 32; jb += CH) {
+    if (2 * jb >= K) break;
+    const int cur = (jb / CH) & 1;
+    if (jb + CH < 32) {
+#pragma unroll
+      for (int i = 0; i < CH; ++i) pf[cur ^ 1][i] = __builtin_amdgcn_ds_bpermute(addr, __builtin_bit_cast(int, pp[PS][jb + CH + i]));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+      const double pfd = (double)__builtin_bit_cast(float, pf[cur][i]);
+      double x[S];   // (the conversion is the opaque statement, as above: the columns are loop-invariant over the steps)
+#pragma unroll
+      for (int s = 0; s < S; ++s) asm volatile("v_cvt_f64_f32_e32 %0, %1" : "=v"(x[s]) : "v"(pp[s][jb + i]));
+#pragma unroll
+      for (int s = 0; s < S; ++s) acc[s] = fma(pfd, x[s], acc[s]);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256, 2) void gram_chol_wave_split_kernel(const float *__restrict__ Pg, long wP, int n,
+                                                                    const int *__restrict__ kdyn, int kdyn_mul, int kmax,
+                                                                    float *__restrict__ Rg, long wR, int *__restrict__ mlive_out,
+                                                                    int inner, const int *__restrict__ inner_live, int max_pass,
+                                                                    int nbatch, int *__restrict__ decl_list = nullptr) {
+  constexpr int KC = 64, RC = 16, KH = KC / 2;
+  const int lane = threadIdx.x & 63;
+  const int b = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));   // (wave-uniform: scalar from here on)
+  if (b >= nbatch) return;
+  const int Ktot = kdyn ? max(0, min(kmax, kdyn[b] * kdyn_mul)) : kmax;
+  const int ilive = inner_live ? min(inner, inner_live[b]) : inner;
+  const int ncols = (n / inner) * ilive;
+  if (Ktot > KC + (max_pass - 1) * (KC - RC) || ncols > 128) {
+    if (lane == 0) { mlive_out[b] = -4; if (decl_list) decl_list[atomicAdd(decl_list + nbatch, 1)] = b; }
+    return;
+  }
+  const int nslot = (ncols + 31) >> 5;
+  const float *P = Pg + (long)b * wP;
+  float *Rout = Rg + (long)b * wR;
+  const int c0 = lane, c1 = lane + 64;                  // packed columns this lane owns
+  const bool ok0 = c0 < ncols, ok1 = c1 < ncols;
+  const int r0 = ok0 ? (c0 / ilive) * inner + (c0 % ilive) : 0, r1 = ok1 ? (c1 / ilive) * inner + (c1 % ilive) : 0;
+  const int hp = lane >> 5, lh = lane & 31;             // row parity and column within a slot in the dot-loop layout
+  unsigned rs[4];                                       // column of slot s (a column that does not exist reads column 0)
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const int c = lh + 32 * s;
+    rs[s] = c < ncols ? (unsigned)((c / ilive) * inner + (c % ilive)) : 0u;
+  }
+  const double eT = NOISE_C * (double)Eps<float>::v;
+  float pp[4][KH];                                      // pp[s][j] = P[2 j + hp][lh + 32 s]
+  double q0[RC], q1[RC];                                // own entries of the factor rows
+#pragma unroll
+  for (int j = 0; j < RC; ++j) { q0[j] = 0.0; q1[j] = 0.0; }
+  int nl = 0, k0 = 0;
+  double maxd = 0.0;
+  float nrm_mine = 0.f;                                 // lane j: squared norm of factor row j
+#pragma unroll 1
+  for (int pass = 0;; ++pass) {
+    const int nfr = nl;                                 // rows of the running factor, folded in as the first rows
+    const int npr = min(Ktot - k0, KC - (pass > 0 ? RC : 0));
+    const int K = __builtin_amdgcn_readfirstlane(nfr + npr);   // (uniform, but nl leaves a loop whose exit the compiler takes for divergent)
+    double d0 = 0.0, d1 = 0.0;
+    // (every row requested unconditionally at a clamped address, the predicates applied to the values: see the kernel above)
+    const int klast = max(K - 1, nfr);
+#pragma unroll
+    for (int j = 0; j < KH; ++j) {
+      const unsigned ro = (unsigned)((k0 + min(max(2 * j + hp, nfr), klast) - nfr) * n);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) pp[s][j] = P[ro + rs[s]];
+    }
+    // owner layout for the predicates, the folded factor rows and the diagonals (rows 2 j, 2 j + 1 of column c0 in the registers
+    // of slots 0, 1, of column c1 in those of slots 2, 3), then back
+#pragma unroll
+    for (int j = 0; j < KH; ++j) {
+      gw_swap32(pp[0][j], pp[1][j]);
+      gw_swap32(pp[2][j], pp[3][j]);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int k = 2 * j + h;
+        float x0 = (k < K && ok0) ? pp[h][j] : 0.f, x1 = (k < K && ok1) ? pp[2 + h][j] : 0.f;
+        if (k < RC && k < nfr) { x0 = (float)q0[k < RC ? k : 0]; x1 = (float)q1[k < RC ? k : 0]; }
+        pp[h][j] = x0; pp[2 + h][j] = x1;
+        d0 = fma((double)x0, (double)x0, d0);
+        d1 = fma((double)x1, (double)x1, d1);
+      }
+      gw_swap32(pp[0][j], pp[1][j]);
+      gw_swap32(pp[2][j], pp[3][j]);
+    }
+#pragma unroll
+    for (int j = 0; j < RC; ++j) { q0[j] = 0.0; q1[j] = 0.0; }
+    {
+      double md = fmax(d0, d1);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) md = fmax(md, __shfl_xor(md, o, 64));
+      maxd = md;
+    }
+    const double thresh = fmax((double)n * 2.220446049250313e-16, eT * eT) * maxd;
+    int f = -1;
+    nl = 0;
+    nrm_mine = 0.f;
+#pragma unroll 1
+    for (;;) {
+      int cand = (ok0 && c0 > f && d0 > thresh) ? c0 : ((ok1 && c1 > f && d1 > thresh) ? c1 : 0x7fffffff);
+      cand = wave_min_dpp(cand);
+      if (cand == 0x7fffffff || nl >= K) break;         // the rank cannot exceed the K rows
+      if (nl == RC) {                                   // rank above the cap: the 128-thread kernels redo this walker
+        if (lane == 0) { mlive_out[b] = -4; if (decl_list) decl_list[atomicAdd(decl_list + nbatch, 1)] = b; }
+        return;
+      }
+      f = __builtin_amdgcn_readfirstlane(cand);
+      const int lf = f & 63;
+      double acc[4] = {0.0, 0.0, 0.0, 0.0};
+      {
+        const int addr = ((lane & 32) | (f & 31)) << 2;
+        const int ps = f >> 5;                          // < nslot: f is a live column
+        if (nslot == 3) {
+          if (ps == 0) gw_split_dot<3, 0>(pp, K, addr, acc);
+          else if (ps == 1) gw_split_dot<3, 1>(pp, K, addr, acc);
+          else gw_split_dot<3, 2>(pp, K, addr, acc);
+        } else if (nslot == 2) {
+          if (ps == 0) gw_split_dot<2, 0>(pp, K, addr, acc);
+          else gw_split_dot<2, 1>(pp, K, addr, acc);
+        } else if (nslot == 4) {
+          if (ps == 0) gw_split_dot<4, 0>(pp, K, addr, acc);
+          else if (ps == 1) gw_split_dot<4, 1>(pp, K, addr, acc);
+          else if (ps == 2) gw_split_dot<4, 2>(pp, K, addr, acc);
+          else gw_split_dot<4, 3>(pp, K, addr, acc);
+        } else {
+          gw_split_dot<1, 0>(pp, K, addr, acc);
+        }
+      }
+      gw_swap32_f64(acc[0], acc[1]);                    // every owner: g and h of its column c0 ...
+      gw_swap32_f64(acc[2], acc[3]);                    // ... and of c1
+      double g0 = acc[0], h0 = acc[1], g1 = acc[2], h1 = acc[3], piv;
+      auto qsub = [&](const double (&qq)[RC], const double dd) {
+        piv = gw_readlane_f64(dd, lf);
+#pragma unroll
+        for (int jb = 0; jb < RC; jb += 8) {
+          if (jb < nl) {
+#pragma unroll
+            for (int j = jb; j < jb + 8; ++j) {
+              if (j < nl) {
+                const double rf = gw_readlane_f64(qq[j], lf);
+                g0 = fma(-rf, q0[j], g0);
+                g1 = fma(-rf, q1[j], g1);
+              }
+            }
+          }
+        }
+      };
+      if (f < 64) qsub(q0, d0); else qsub(q1, d1);
+      g0 += h0; g1 += h1;
+      const double inv = jr_rsq64(piv);
+      const double v0 = (ok0 && c0 >= f) ? g0 * inv : 0.0, v1 = (ok1 && c1 >= f) ? g1 * inv : 0.0;
+#pragma unroll
+      for (int jb = 0; jb < RC; jb += 8) {
+        if ((nl & ~7) == jb) {
+#pragma unroll
+          for (int j = jb; j < jb + 8; ++j) { q0[j] = (j == nl) ? v0 : q0[j]; q1[j] = (j == nl) ? v1 : q1[j]; }
+        }
+      }
+      if (c0 > f) d0 -= v0 * v0;
+      if (c1 > f) d1 -= v1 * v1;
+      const float a = wave_sum_dpp((float)(v0 * v0 + v1 * v1));   // row norm^2 for the compaction floor: f32 is ample
+      if (lane == nl) nrm_mine = a;
+      ++nl;
+    }
+    k0 += npr;
+    if (k0 >= Ktot) break;
+  }
+  const float fro = wave_sum_dpp(lane < nl ? nrm_mine : 0.f);
+  const bool keep = lane < nl && (double)nrm_mine > eT * eT * (double)fro;
+  const unsigned long long km = __ballot(keep);
+  const int pos = keep ? __popcll(km & ((1ull << lane) - 1ull)) : -1;
+  if (lane == 0) mlive_out[b] = __popcll(km);
+  const double sc = maxd > 0.0 ? 1.0 / sqrt(maxd) : 1.0;
+#pragma unroll
+  for (int j = 0; j < RC; ++j) {
+    if (j < nl) {
+      const int pj = __builtin_amdgcn_readlane(pos, j);
+      if (pj >= 0) {
+        if (ok0) Rout[(long)pj * n + r0] = (float)(q0[j] * sc);
+        if (ok1) Rout[(long)pj * n + r1] = (float)(q1[j] * sc);
+      }
+    }
+  }
+}
+
+// PEPSGPU_FACTOR_SPLIT (read once per process): 0 = gram_chol_wave_kernel wherever the one-wave factor runs; unset (or another
+// value) = gram_chol_wave_split_kernel.  The two store the same bytes.
+inline bool factor_split() {
+  static const bool v = getenv("PEPSGPU_FACTOR_SPLIT") ? atoi(getenv("PEPSGPU_FACTOR_SPLIT")) != 0 : true;
+  return v;
+}
+
 // (defined in trunc_mid.h) MFMA Gram of the live columns in registers + low-rank Cholesky, one kernel per walker
 template <typename T>
 inline void launch_colgram_chol(hipStream_t s, int nbatch, const T *P, long wP, int n, const int *kdyn, int kdyn_mul, int kmax,
@@ -1127,7 +1357,9 @@ inline void launch_gram_chol_lowrank(hipStream_t s, int nbatch, const T *P, long
         constexpr bool no_list = false;
         int *dl = no_list ? nullptr : scratch_list;
         if (dl) PG_CHECK_HIP(hipMemsetAsync(dl + nbatch, 0, sizeof(int), s));
-        hipLaunchKernelGGL(gram_chol_wave_kernel, dim3((nbatch + 3) / 4), dim3(256), 0, s, (const float *)P, wP, n, kdyn, kdyn_mul, kmax,
+        // (row-parity placement of P for the dot products unless PEPSGPU_FACTOR_SPLIT=0: the same bytes, fewer instructions)
+        const auto wave_kernel = factor_split() ? gram_chol_wave_split_kernel : gram_chol_wave_kernel;
+        hipLaunchKernelGGL(wave_kernel, dim3((nbatch + 3) / 4), dim3(256), 0, s, (const float *)P, wP, n, kdyn, kdyn_mul, kmax,
                            (float *)R, wR, mlive, inner, inner_live, std::max(max_pass, 2), nbatch, dl);
         done = true;
         if (dl && narrow && n <= 128) {     // the handed-on walkers: list kernel, then nothing else to launch

@@ -1015,7 +1015,7 @@ def diag_link_slice_calls():
 
 
 def diag_link_cand(cfgs, d, orient, row1, col1):
-    """link_sqrt5_cand_kernel alone: cfgs [n][rows][cols] states in [0, d); returns (cand [n][2][4], flag [n][2]) of the 2 x 3
+    """corner_exchange_cand_kernel alone: cfgs [n][rows][cols] states in [0, d); returns (cand [n][2][4], flag [n][2]) of the 2 x 3
     (HORIZONTAL) or 3 x 2 (VERTICAL) window at (row1, col1): the corner states (upper-left, lower-left, lower-right, upper-right) with
     the ends of link kind 2 (entry 0) and kind 3 (entry 1) exchanged, flag -1 where the ends differ else 1"""
     c = np.ascontiguousarray(cfgs, dtype=np.int32)

@@ -51,6 +51,18 @@ static int guarded(pepsgpu_ctx *ctx, F &&f) {
   if (!ctx || !ctx->eng) return PEPSGPU_EINVAL;            \
   return guarded(ctx, [&]() { PG_CHECK_HIP(hipSetDevice(ctx->eng->device_id)); body; })
 
+struct DevBufs {     // device allocations of one diagnostic call, freed on every exit
+  std::vector<void *> p;
+  template <typename T> T *alloc(size_t n, const void *init = nullptr) {
+    void *q = nullptr;
+    PG_CHECK_HIP(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
+    p.push_back(q);
+    if (init && n) PG_CHECK_HIP(hipMemcpy(q, init, n * sizeof(T), hipMemcpyHostToDevice));
+    return (T *)q;
+  }
+  ~DevBufs() { for (void *q : p) (void)hipFree(q); }
+};
+
 extern "C" {
 
 const char *pepsgpu_version(void) { return "pepsgpu 0.1 (gfx950)"; }
@@ -189,20 +201,17 @@ int pepsgpu_diag_fermion_hop_cand(int rows, int cols, int d, const int32_t *occ,
     const int sites = rows * cols;
     const size_t ne = (size_t)n * sites;
     for (size_t e = 0; e < ne; ++e) PG_REQUIRE(ext[e] >= 0 && ext[e] < 2 * d, 1, "extended state outside [0, 2 d)");
-    int *dcfg, *dout;
-    PG_CHECK_HIP(hipMalloc(&dcfg, ne * sizeof(int)));
-    PG_CHECK_HIP(hipMalloc(&dout, 12 * (size_t)n * sizeof(int)));
-    int *dc = dout, *ds = dout + 8 * (size_t)n, *df = dout + 10 * (size_t)n;
-    PG_CHECK_HIP(hipMemcpy(dcfg, ext, ne * sizeof(int), hipMemcpyHostToDevice));
+    DevBufs m;
+    const int *dcfg = m.alloc<int>(ne, ext);
+    int *dc = m.alloc<int>(12 * (size_t)n), *ds = dc + 8 * (size_t)n, *df = dc + 10 * (size_t)n;
     const int s0 = row1 * cols + col1, s1 = s0 + cols, s2 = s1 + 1, s3 = s0 + 1;
-    hipLaunchKernelGGL(nnn_hop_cand_kernel, dim3((2 * n + 255) / 256), dim3(256), 0, 0, (const int *)dcfg, sites, s0, s1, s2, s3, d, occ_bits,
+    hipLaunchKernelGGL(nnn_hop_cand_kernel, dim3((2 * n + 255) / 256), dim3(256), 0, 0, dcfg, sites, s0, s1, s2, s3, d, occ_bits,
                        2, (int)LEFTUP_TO_RIGHTDOWN, (int)LEFTDOWN_TO_RIGHTUP, (int *)nullptr, dc, df, ds, 2L, n);
     PG_CHECK_HIP(hipGetLastError());
     PG_CHECK_HIP(hipDeviceSynchronize());
     PG_CHECK_HIP(hipMemcpy(cand_out, dc, 8 * (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
     PG_CHECK_HIP(hipMemcpy(sign_out, ds, 2 * (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
     PG_CHECK_HIP(hipMemcpy(flag_out, df, 2 * (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-    (void)hipFree(dcfg); (void)hipFree(dout);
   });
 }
 // spin_onehalf_triangle_heisenbergJ1J2_sqrpeps.h:350-398 / :425-442: the links of one row pair / column pair
@@ -210,8 +219,8 @@ int pepsgpu_link_exchange_slice(pepsgpu_ctx *ctx, int orient, int slice1, int li
   CTX_CALL(PG_REQUIRE(val_out, 1, "null buffer"); ctx->eng->link_exchange_slice(orient, slice1, link_mask, val_out));
 }
 long pepsgpu_diag_link_slice_calls(void) { return pepsgpu::link_slice_calls().load(); }
-// link_sqrt5_cand_kernel alone on a caller's configurations cfg [n][rows][cols] for the window at (row1, col1): cand_out [n][2][4],
-// flag_out [n][2], entry 0 LEFTUP_TO_RIGHTDOWN (kind 2), entry 1 LEFTDOWN_TO_RIGHTUP (kind 3)
+// corner_exchange_cand_kernel alone on a caller's configurations cfg [n][rows][cols] for the 2 x 3 / 3 x 2 window at (row1, col1):
+// cand_out [n][2][4], flag_out [n][2], entry 0 LEFTUP_TO_RIGHTDOWN (kind 2), entry 1 LEFTDOWN_TO_RIGHTUP (kind 3)
 int pepsgpu_diag_link_cand(int rows, int cols, int phys_dim, int n, const int32_t *cfg, int orient, int row1, int col1, int32_t *cand_out,
                            int32_t *flag_out) {
   return guarded(nullptr, [&]() {
@@ -223,18 +232,16 @@ int pepsgpu_diag_link_cand(int rows, int cols, int phys_dim, int n, const int32_
     const int sites = rows * cols;
     const size_t ne = (size_t)n * sites;
     for (size_t e = 0; e < ne; ++e) PG_REQUIRE(cfg[e] >= 0 && cfg[e] < phys_dim, 1, "state outside [0, phys_dim)");
-    int *dcfg, *dout;
-    PG_CHECK_HIP(hipMalloc(&dcfg, ne * sizeof(int)));
-    PG_CHECK_HIP(hipMalloc(&dout, 10 * (size_t)n * sizeof(int)));
-    int *dc_ = dout, *df = dout + 8 * (size_t)n;
-    PG_CHECK_HIP(hipMemcpy(dcfg, cfg, ne * sizeof(int), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(link_sqrt5_cand_kernel, dim3((2 * n + 255) / 256), dim3(256), 0, 0, (const int *)dcfg, sites, cols,
-                       orient == VERTICAL ? 1 : 0, row1, col1, 2, (int)LEFTUP_TO_RIGHTDOWN, (int)LEFTDOWN_TO_RIGHTUP, dc_, df, n);
+    DevBufs m;
+    const int *dcfg = m.alloc<int>(ne, cfg);
+    int *dc_ = m.alloc<int>(10 * (size_t)n), *df = dc_ + 8 * (size_t)n;
+    const int s0 = row1 * cols + col1, s1 = s0 + dr * cols, s2 = s1 + dc, s3 = s0 + dc;   // upper-left, lower-left, lower-right, upper-right
+    hipLaunchKernelGGL(corner_exchange_cand_kernel, dim3((2 * n + 255) / 256), dim3(256), 0, 0, dcfg, sites, s0, s1, s2, s3, 2,
+                       (int)LEFTUP_TO_RIGHTDOWN, (int)LEFTDOWN_TO_RIGHTUP, dc_, df, n);
     PG_CHECK_HIP(hipGetLastError());
     PG_CHECK_HIP(hipDeviceSynchronize());
     PG_CHECK_HIP(hipMemcpy(cand_out, dc_, 8 * (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
     PG_CHECK_HIP(hipMemcpy(flag_out, df, 2 * (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-    (void)hipFree(dcfg); (void)hipFree(dout);
   });
 }
 int pepsgpu_walker_create(pepsgpu_ctx *ctx, int pos, int level, int *walker_out) {
@@ -541,18 +548,6 @@ static void tgd_dispatch(int types, F &&f) {
     default: throw Error(1, "unsupported element types");
   }
 }
-
-struct DevBufs {     // device allocations of one diagnostic call, freed on every exit
-  std::vector<void *> p;
-  template <typename T> T *alloc(size_t n, const void *init = nullptr) {
-    void *q = nullptr;
-    PG_CHECK_HIP(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
-    p.push_back(q);
-    if (init && n) PG_CHECK_HIP(hipMemcpy(q, init, n * sizeof(T), hipMemcpyHostToDevice));
-    return (T *)q;
-  }
-  ~DevBufs() { for (void *q : p) (void)hipFree(q); }
-};
 
 extern "C" int pepsgpu_diag_tgemm_route(int types, const int *desc_ints, int n_ints, const long *desc_longs, int n_longs,
                                         const double *desc_dbls, int n_dbls, long a_offset, long b_offset, int32_t *route_out) {

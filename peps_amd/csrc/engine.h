@@ -1489,21 +1489,21 @@ class Engine : public EngineBase {
   }
   BTenDev bten2_step(int post, const BTenDev &bt, const DTen<T> &mps1, const SiteSel &s1, const SiteSel &s2,
                      const DTen<T> &mps2, int ncand, int bt_ncand, bool normalise, const int *entry_flag = nullptr);
-  // One horizontal plaquette (row1, col1) .. (row1 + 1, col1 + 1) between a LEFT and a RIGHT BTen2 under the UP / DOWN row BMPS: the
-  // two half tensors and the log-scale sum of the four environments (plaquette_halves, engine_nnn.h)
+  // One two-row window between the BTen2 before it (lo: LEFT / UP) and behind it (hi: RIGHT / DOWN) as two half tensors and the
+  // log-scale sum of the four environments (window_halves, engine_nnn.h); close_dot4 contracts them into a value table.
   struct PlaqHalves { BTenDev a, b; double *lsum; };
-  PlaqHalves plaquette_halves(int row1, int col1, const BTenDev &lb, const BTenDev &rb, const int *tab, int ncols, const int cols[4],
-                              int nc, const int *flag = nullptr);
+  PlaqHalves window_halves(int orient, int span, int r, int c, const BTenDev &lo, const BTenDev &hi, const int *tab, int ncols,
+                           const int cols[4], int nc, const int *flag = nullptr);
   void free_halves(PlaqHalves &h) { free_ten(h.a.t); free_ten(h.b.t); arena_.free(h.lsum); }
   void close_dot4(PlaqHalves &h, int nc, const int *flag, int slot0, int slot1, long w_stride, double *out);
-  // the 2 x 3 / 3 x 2 window of the sqrt5 links as the same two halves (sqrt5_halves, engine_sweep.h)
-  PlaqHalves sqrt5_halves(int orient, int r, int c, const BTenDev &lo, const BTenDev &hi, const int *tab, int nc, const int *flag);
-  // the walk over the plaquettes of a row pair that the diagonal slices share (row_pair_walk, engine_sweep.h).  s = the flat
-  // site indices of (r, c), (r+1, c), (r+1, c+1), (r, c+1); kinds[0 .. nc) = the requested diagonals with work for some walker
-  struct RowPairPlaq { int col1, s[4], kinds[2], nc; };
-  template <typename Differ, typename Begin, typename Plaquette, typename Advance, typename Epilogue>
-  void row_pair_walk(const char *what, int row1, int diag_mask, size_t ntab, double *host_out, Differ &&differ, Begin &&begin,
-                     Plaquette &&plaquette, Advance &&advance, Epilogue &&epilogue);
+  // one window of the walk over a slice pair (pair_walk, engine_sweep.h): position j along the pair, s = the flat site indices of
+  // its corners (upper-left, lower-left, lower-right, upper-right), kinds[0 .. nc) = the requested kinds with work for some walker
+  struct RowPairPlaq { int j, span, s[4], kinds[2], nc; };
+  template <typename Differ, typename Begin, typename Window, typename Advance, typename Epilogue>
+  void pair_walk(const char *what, int orient, int slice1, int mask, int legal, size_t ntab, double *host_out, Differ &&differ,
+                 Begin &&begin, Window &&window, Advance &&advance, Epilogue &&epilogue);
+  // the window body of the exchange slices: the corner-exchange candidates, window_halves, close_dot4 into out
+  void exchange_window(int orient, int slice1, const RowPairPlaq &p, int *dcand, int nk, double *dval);
   void finish_dot4(const DTen<T> &a, const DTen<T> &b, int nc, double *lsum, double *out);
   int *upload_cand(int ncand, int ncols, const int32_t *cand);
   // sel (optional, f32): the kernel of the walkers with at most JR_BR live rows selects / normalises their rows into Vt

@@ -3,9 +3,9 @@
 // bmps_contractor_helpers.h:12-180, bmps_contractor_trace.h:207-536; bosonic branches), batched over
 // walkers x candidates.  Everything is one primitive -- the BTen2 growth step of
 // GrowBTen2StepAfterTransposedMPOTens (helpers.h:174-177) with two site selectors -- plus a
-// 4-index dot; the Transpose calls of the reference are strides of the tensor GEMM.  The horizontal
-// plaquette between a LEFT and a RIGHT BTen2 -- two such steps -- is one stage, plaquette_halves: the
-// per-call traces close it with finish_dot4, the row-pair slices of engine_sweep.h with close_dot4.
+// 4-index dot; the Transpose calls of the reference are strides of the tensor GEMM.  A two-row window
+// between two BTen2 -- two such steps, three for the sqrt(5) windows -- is one stage, window_halves: the
+// per-call traces close it with finish_dot4, the pair slices of engine_sweep.h with close_dot4.
 #pragma once
 #include "engine.h"
 
@@ -138,24 +138,36 @@ int *Engine<T>::upload_cand(int ncand, int ncols, const int32_t *cand) {
   return d;
 }
 
-// The plaquette (row1, col1) .. (row1 + 1, col1 + 1) between the LEFT BTen2 lb and the RIGHT BTen2 rb (the caller says of which set)
-// under the row BMPS UP(row1) / DOWN(row1 + 1): a = lb grown over column col1, b = rb over column col1 + 1, lsum = the log-scales of
-// the four environments.  cols[k]: the column of tab [entry][ncols] with the state of site k in the order (r, c), (r+1, c), (r+1, c+1),
-// (r, c+1); < 0: the walker's configuration (or the active override).  A candidate column wins over the configuration override: a
-// replaced site never reads either configuration table.  flag: the entry_flag of bten2_step.
+// The two-row window at (r, c) between the BTen2 before it (lo: LEFT / UP) and behind it (hi: RIGHT / DOWN), under the BMPS of the
+// slice pair: span 1 the 2 x 2 plaquette, span 2 the 2 x 3 (HORIZONTAL) / 3 x 2 (VERTICAL) window of the sqrt(5) links.  cols[k]: the
+// column of tab [entry][ncols] with the state of corner k in the order upper-left, lower-left, lower-right, upper-right; < 0: the
+// walker's configuration (or the active override).  A candidate column wins over the configuration override: a replaced site never
+// reads either configuration table.  HORIZONTAL: a = lo grown over the left column, b = hi over the right one; VERTICAL: a = hi grown
+// over the lower row, b = lo over the upper one; span 2: a grown once more over the middle column / row in the walkers' own states.
+// lsum = the log-scales of the four environments.  flag: the entry_flag of bten2_step.
 template <typename T>
-typename Engine<T>::PlaqHalves Engine<T>::plaquette_halves(int row1, int col1, const BTenDev &lb, const BTenDev &rb, const int *tab,
-                                                           int ncols, const int cols[4], int nc, const int *flag) {
-  const int row2 = row1 + 1, col2 = col1 + 1;
-  const BMPSDev &up = bmps_at_slice(UP, row1), &dn = bmps_at_slice(DOWN, row2);
-  const SitePick t0{row1, col1, cols[0]}, t1{row2, col1, cols[1]}, t2{row2, col2, cols[2]}, t3{row1, col2, cols[3]};
+typename Engine<T>::PlaqHalves Engine<T>::window_halves(int orient, int span, int r, int c, const BTenDev &lo, const BTenDev &hi,
+                                                        const int *tab, int ncols, const int cols[4], int nc, const int *flag) {
+  const bool hor = orient == HORIZONTAL;
+  const int r2 = r + (hor ? 1 : span), c2 = c + (hor ? span : 1), p1 = hor ? UP : LEFT, p2 = hor ? DOWN : RIGHT;
+  const BMPSDev &e1 = bmps_at_slice(p1, hor ? r : c), &e2 = bmps_at_slice(p2, hor ? r2 : c2);
+  const SitePick ul{r, c, cols[0]}, ll{r2, c, cols[1]}, lr{r2, c2, cols[2]}, ur{r, c2, cols[3]};
+  // one growth step towards `post` over the sites sa, sb at position k along the pair (LEFT / DOWN meet e1 first, RIGHT / UP e2)
+  auto step = [&](int post, const BTenDev &bt, int k, const SitePick &sa, const SitePick &sb, int bt_nc) {
+    const DTen<T> &m1 = at_logical(e1, p1, k), &m2 = at_logical(e2, p2, k);
+    const bool fwd = post == LEFT || post == DOWN;
+    return bten2_step(post, bt, fwd ? m1 : m2, pick(sa, tab, ncols), pick(sb, tab, ncols), fwd ? m2 : m1, nc, bt_nc, false, flag);
+  };
   PlaqHalves h;
   h.lsum = zeros_f64();
-  h.a = bten2_step(LEFT, lb, at_logical(up, UP, col1), pick(t0, tab, ncols), pick(t1, tab, ncols), at_logical(dn, DOWN, col1), nc, 1,
-                   false, flag);
-  h.b = bten2_step(RIGHT, rb, at_logical(dn, DOWN, col2), pick(t2, tab, ncols), pick(t3, tab, ncols), at_logical(up, UP, col2), nc, 1,
-                   false, flag);
-  add_logs(h.lsum, up.logscale, dn.logscale, lb.logscale, rb.logscale);
+  h.a = hor ? step(LEFT, lo, c, ul, ll, 1) : step(DOWN, hi, r2, ll, lr, 1);
+  h.b = hor ? step(RIGHT, hi, c2, lr, ur, 1) : step(UP, lo, r, ur, ul, 1);
+  if (span == 2) {
+    BTenDev first = h.a;
+    h.a = hor ? step(LEFT, first, c + 1, {r, c + 1, -1}, {r2, c + 1, -1}, nc) : step(DOWN, first, r + 1, {r + 1, c, -1}, {r + 1, c2, -1}, nc);
+    free_ten(first.t);
+  }
+  add_logs(h.lsum, e1.logscale, e2.logscale, lo.logscale, hi.logscale);
   PG_REQUIRE(h.a.t.d[0] == h.b.t.d[3] && h.a.t.d[1] == h.b.t.d[2] && h.a.t.d[2] == h.b.t.d[1] && h.a.t.d[3] == h.b.t.d[0], 3,
              "trace: two-row environment bond mismatch");
   return h;
@@ -241,28 +253,14 @@ void Engine<T>::replace_nnn_trace(int row1, int col1, int dir, int orient, int n
   const int nc = ncand > 0 ? ncand : 1;
   int *dc = upload_cand(ncand, 2, cand);
   const int cl = ncand > 0 ? 0 : -1, cr = ncand > 0 ? 1 : -1;
-  if (orient == HORIZONTAL) {
-    PG_REQUIRE(bten2_size(LEFT) > col1, 3, "ReplaceNNNSiteTrace: LEFT BTen2 missing");
-    const int lurd[4] = {cl, -1, cr, -1}, ldru[4] = {-1, cl, -1, cr};
-    PlaqHalves h = plaquette_halves(row1, col1, bten2_[LEFT][col1], bten2_at_slice(RIGHT, col2), dc, 2,
-                                    dir == LEFTUP_TO_RIGHTDOWN ? lurd : ldru, nc);
-    finish_dot4(h.a.t, h.b.t, nc, h.lsum, out);
-    free_halves(h);
-  } else {
-    const BMPSDev &lf = bmps_at_slice(LEFT, col1), &rt = bmps_at_slice(RIGHT, col2);
-    PG_REQUIRE(bten2_size(UP) > row1, 3, "ReplaceNNNSiteTrace: UP BTen2 missing");
-    const BTenDev &tb = bten2_[UP][row1], &bb = bten2_at_slice(DOWN, row2);
-    SitePick m0, m1, m2, m3;   // (row2,col1), (row2,col2), (row1,col1), (row1,col2)
-    if (dir == LEFTUP_TO_RIGHTDOWN) { m0 = {row2, col1, -1}; m1 = {row2, col2, cr}; m2 = {row1, col1, cl}; m3 = {row1, col2, -1}; }
-    else { m0 = {row2, col1, cl}; m1 = {row2, col2, -1}; m2 = {row1, col1, -1}; m3 = {row1, col2, cr}; }
-    double *lsum = zeros_f64();
-    BTenDev a = bten2_step(DOWN, bb, at_logical(lf, LEFT, row2), pick(m0, dc, 2), pick(m1, dc, 2), at_logical(rt, RIGHT, row2), nc, 1, false);
-    BTenDev b = bten2_step(UP, tb, at_logical(rt, RIGHT, row1), pick(m3, dc, 2), pick(m2, dc, 2), at_logical(lf, LEFT, row1), nc, 1, false);
-    add_logs(lsum, lf.logscale, rt.logscale, tb.logscale, bb.logscale);
-    finish_dot4(a.t, b.t, nc, lsum, out);
-    free_ten(a.t); free_ten(b.t);
-    arena_.free(lsum);
-  }
+  const bool hor = orient == HORIZONTAL;
+  const int lo = hor ? LEFT : UP, k = hor ? col1 : row1;
+  PG_REQUIRE(bten2_size(lo) > k, 3, hor ? "ReplaceNNNSiteTrace: LEFT BTen2 missing" : "ReplaceNNNSiteTrace: UP BTen2 missing");
+  const int lurd[4] = {cl, -1, cr, -1}, ldru[4] = {-1, cl, -1, cr};
+  PlaqHalves h = window_halves(orient, 1, row1, col1, bten2_[lo][k], bten2_at_slice(hor ? RIGHT : DOWN, k + 1), dc, 2,
+                               dir == LEFTUP_TO_RIGHTDOWN ? lurd : ldru, nc);
+  finish_dot4(h.a.t, h.b.t, nc, h.lsum, out);
+  free_halves(h);
   if (dc) arena_.free(dc);
 }
 
@@ -333,7 +331,7 @@ void Engine<T>::replace_plaquette_trace(int row1, int col1, int ncand, const int
   PG_REQUIRE((int)ls.size() > col1, 3, "plaquette trace: LEFT BTen2 of that set missing");
   PG_REQUIRE(kr >= 0 && kr < (int)rs.size(), 3, "plaquette trace: RIGHT BTen2 of that set missing");
   const int own[4] = {-1, -1, -1, -1}, replaced[4] = {0, 1, 2, 3};
-  PlaqHalves h = plaquette_halves(row1, col1, ls[col1], rs[kr], dc, 4, ncand > 0 ? replaced : own, nc);
+  PlaqHalves h = window_halves(HORIZONTAL, 1, row1, col1, ls[col1], rs[kr], dc, 4, ncand > 0 ? replaced : own, nc);
   finish_dot4(h.a.t, h.b.t, nc, h.lsum, out);
   free_halves(h);
   if (dc) arena_.free(dc);
@@ -409,40 +407,16 @@ void Engine<T>::replace_sqrt5_trace(int row1, int col1, int dir, int orient, int
   const int nc = ncand > 0 ? ncand : 1;
   int *dc = upload_cand(ncand, 2, cand);
   const int cl = ncand > 0 ? 0 : -1, cr = ncand > 0 ? 1 : -1;
-  double *lsum = zeros_f64();
-  BTenDev a, b, c;
-  if (orient == HORIZONTAL) {
-    const int row2 = row1 + 1, col2 = col1 + 1, col3 = col1 + 2;
-    PG_REQUIRE(row1 >= 0 && col1 >= 0 && row2 < Ly_ && col3 < Lx_, 1, "ReplaceSqrt5DistTwoSiteTrace: sites outside the lattice");
-    const BMPSDev &up = bmps_at_slice(UP, row1), &dn = bmps_at_slice(DOWN, row2);
-    PG_REQUIRE(bten2_size(LEFT) > col1, 3, "ReplaceSqrt5DistTwoSiteTrace: LEFT BTen2 missing");
-    const BTenDev &lb = bten2_[LEFT][col1], &rb = bten2_at_slice(RIGHT, col3);
-    SitePick m0, m1, m4, m5;   // (row1,col1), (row2,col1), (row1,col3), (row2,col3)
-    if (dir == LEFTUP_TO_RIGHTDOWN) { m0 = {row1, col1, cl}; m1 = {row2, col1, -1}; m4 = {row1, col3, -1}; m5 = {row2, col3, cr}; }
-    else { m0 = {row1, col1, -1}; m1 = {row2, col1, cl}; m4 = {row1, col3, cr}; m5 = {row2, col3, -1}; }
-    const SitePick m2{row1, col2, -1}, m3{row2, col2, -1};
-    a = bten2_step(LEFT, lb, at_logical(up, UP, col1), pick(m0, dc, 2), pick(m1, dc, 2), at_logical(dn, DOWN, col1), nc, 1, false);
-    b = bten2_step(RIGHT, rb, at_logical(dn, DOWN, col3), pick(m5, dc, 2), pick(m4, dc, 2), at_logical(up, UP, col3), nc, 1, false);
-    c = bten2_step(LEFT, a, at_logical(up, UP, col2), pick(m2, dc, 2), pick(m3, dc, 2), at_logical(dn, DOWN, col2), nc, nc, false);
-    add_logs(lsum, up.logscale, dn.logscale, lb.logscale, rb.logscale);
-  } else {
-    const int row2 = row1 + 1, row3 = row1 + 2, col2 = col1 + 1;
-    PG_REQUIRE(row1 >= 0 && col1 >= 0 && row3 < Ly_ && col2 < Lx_, 1, "ReplaceSqrt5DistTwoSiteTrace: sites outside the lattice");
-    const BMPSDev &lf = bmps_at_slice(LEFT, col1), &rt = bmps_at_slice(RIGHT, col2);
-    PG_REQUIRE(bten2_size(UP) > row1, 3, "ReplaceSqrt5DistTwoSiteTrace: UP BTen2 missing");
-    const BTenDev &tb = bten2_[UP][row1], &bb = bten2_at_slice(DOWN, row3);
-    SitePick m0, m1, m4, m5;   // (row3,col1), (row3,col2), (row1,col1), (row1,col2)
-    if (dir == LEFTUP_TO_RIGHTDOWN) { m0 = {row3, col1, -1}; m1 = {row3, col2, cr}; m4 = {row1, col1, cl}; m5 = {row1, col2, -1}; }
-    else { m0 = {row3, col1, cl}; m1 = {row3, col2, -1}; m4 = {row1, col1, -1}; m5 = {row1, col2, cr}; }
-    const SitePick m2{row2, col1, -1}, m3{row2, col2, -1};
-    a = bten2_step(DOWN, bb, at_logical(lf, LEFT, row3), pick(m0, dc, 2), pick(m1, dc, 2), at_logical(rt, RIGHT, row3), nc, 1, false);
-    b = bten2_step(UP, tb, at_logical(rt, RIGHT, row1), pick(m5, dc, 2), pick(m4, dc, 2), at_logical(lf, LEFT, row1), nc, 1, false);
-    c = bten2_step(DOWN, a, at_logical(lf, LEFT, row2), pick(m2, dc, 2), pick(m3, dc, 2), at_logical(rt, RIGHT, row2), nc, nc, false);
-    add_logs(lsum, lf.logscale, rt.logscale, tb.logscale, bb.logscale);
-  }
-  finish_dot4(c.t, b.t, nc, lsum, out);
-  free_ten(a.t); free_ten(b.t); free_ten(c.t);
-  arena_.free(lsum);
+  const bool hor = orient == HORIZONTAL;
+  const int lo = hor ? LEFT : UP, k = hor ? col1 : row1;
+  PG_REQUIRE(row1 >= 0 && col1 >= 0 && row1 + (hor ? 1 : 2) < Ly_ && col1 + (hor ? 2 : 1) < Lx_, 1,
+             "ReplaceSqrt5DistTwoSiteTrace: sites outside the lattice");
+  PG_REQUIRE(bten2_size(lo) > k, 3, hor ? "ReplaceSqrt5DistTwoSiteTrace: LEFT BTen2 missing" : "ReplaceSqrt5DistTwoSiteTrace: UP BTen2 missing");
+  const int lurd[4] = {cl, -1, cr, -1}, ldru[4] = {-1, cl, -1, cr};
+  PlaqHalves h = window_halves(orient, 2, row1, col1, bten2_[lo][k], bten2_at_slice(hor ? RIGHT : DOWN, k + 2), dc, 2,
+                               dir == LEFTUP_TO_RIGHTDOWN ? lurd : ldru, nc);
+  finish_dot4(h.a.t, h.b.t, nc, h.lsum, out);
+  free_halves(h);
   if (dc) arena_.free(dc);
 }
 

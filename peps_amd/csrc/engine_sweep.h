@@ -401,15 +401,18 @@ void Engine<T>::energy_slice_impl(int mode, int orient, int slice, int punch_hol
   }
 }
 
-// ---- the diagonal bonds of a row pair (SquareNNNModelEnergySolver::CalEnergyAndHolesImpl, square_nnn_energy_solver.h:203-265) ----
-// Both diagonal exchanges of the plaquette (row1, col1) .. (row2, col2) are candidates of ONE four-site replacement, as
-// replace_plaquette_trace batches candidates: cand[w][q][4] = the states of (row1, col1), (row2, col1), (row2, col2), (row1, col2) with
-// the two ends of the q-th requested diagonal exchanged -- LEFTUP_TO_RIGHTDOWN exchanges (row1, col1) and (row2, col2),
-// LEFTDOWN_TO_RIGHTUP (row2, col1) and (row1, col2) -- and the other two sites in their own states.  flag[w][q] (the batch_flag
-// convention of the tensor GEMM): >= 0 where the move is the identity (equal end states; the reference returns before any
-// contraction, square_spin_onehalf_xxz_obc.h:107-134), -1 where the entry has work.
-__global__ void nnn_diag_cand_kernel(const int *__restrict__ cfg, int sites, int s0, int s1, int s2, int s3, int nc, int kind0, int kind1,
-                                     int *__restrict__ cand, int *__restrict__ flag, int n) {
+// ---- the diagonal bonds of a row pair (SquareNNNModelEnergySolver::CalEnergyAndHolesImpl, square_nnn_energy_solver.h:203-265) and the
+// links of a row / column pair (spin_onehalf_triangle_heisenbergJ1J2_sqrpeps.h:350-398, :425-442) ----
+// Both exchanges across a two-row window are candidates of ONE replacement of its four corner sites, as replace_plaquette_trace
+// batches candidates.  s0 .. s3 = the flat indices of the corners in the order upper-left, lower-left, lower-right, upper-right: of the
+// plaquette (r, c) .. (r+1, c+1), of the 2 x 3 window (r, c) .. (r+1, c+2) of a row pair (the flat sqrt5 links) or of the 3 x 2 window
+// (r, c) .. (r+2, c+1) of a column pair (the steep ones).  cand[w][q][4] = the corner states with the ends of the q-th requested
+// exchange swapped, kind = q ? kind1 : kind0: LEFTUP_TO_RIGHTDOWN swaps the upper-left and the lower-right corner, LEFTDOWN_TO_RIGHTUP
+// the lower-left and the upper-right one; the other two corners keep their own states.  flag[w][q] (the batch_flag convention of the
+// tensor GEMM): >= 0 where the move is the identity (equal end states; the reference returns before any contraction,
+// square_spin_onehalf_xxz_obc.h:107-134), -1 where the entry has work.
+__global__ void corner_exchange_cand_kernel(const int *__restrict__ cfg, int sites, int s0, int s1, int s2, int s3, int nc, int kind0,
+                                            int kind1, int *__restrict__ cand, int *__restrict__ flag, int n) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n * nc) return;
   const int w = e / nc, q = e - w * nc, kind = q ? kind1 : kind0;
@@ -425,7 +428,12 @@ inline std::atomic<long> &nnn_slice_calls() {   // completed nnn_exchange_slice 
   return n;
 }
 
-// The closure of the row-pair slices, trace_dot4_kernel: out[w * w_stride + (q ? slot1 : slot0)] = a . b exp(lsum[w]) of entry (w, q)
+inline std::atomic<long> &link_slice_calls() {   // completed link_exchange_slice calls of the process (pepsgpu_diag_link_slice_calls)
+  static std::atomic<long> n{0};
+  return n;
+}
+
+// The closure of the pair slices, trace_dot4_kernel: out[w * w_stride + (q ? slot1 : slot0)] = a . b exp(lsum[w]) of entry (w, q)
 // (an entry whose flag is >= 0 keeps what the table holds); gives the halves back.
 template <typename T>
 void Engine<T>::close_dot4(PlaqHalves &h, int nc, const int *flag, int slot0, int slot1, long w_stride, double *out) {
@@ -436,63 +444,84 @@ void Engine<T>::close_dot4(PlaqHalves &h, int nc, const int *flag, int slot0, in
   free_halves(h);
 }
 
-// The part the diagonal slices of a row pair share.  The row pair and the mask are checked and the row BMPS probed (status 3 before
-// anything is touched); the value table dval [ntab] is zeroed; begin() states the slice's own refusals and sets up its BTen2 chains;
-// per column the requested diagonals whose ends differ for ANY walker (differ(w, sa, sb) on the host mirror) are packed into a
-// RowPairPlaq, plaquette(p, dval) runs under its own ArenaScope where there is one (else nothing is launched and the zeros stay) and
-// advance(col1) moves the chains on, after the last column too; epilogue(dval), then ONE read-back of the table into host_out.
+// The walk the two-row slices share, over the windows of the row pair (HORIZONTAL) / column pair (VERTICAL) that starts at slice1.
+// Kind k is bit k of the mask: 0 / 1 the diagonals of the plaquette at position j (span 1, a row pair only), 2 / 3 the sqrt5 links of
+// the 2 x 3 / 3 x 2 window at j (span 2, while j + 2 < N); even kinds join the upper-left and the lower-right corner, odd ones the
+// other two.  The pair and the mask (legal: the bits a caller may set) are checked and the BMPS of the pair probed (status 3 before
+// anything is touched); the value table dval [ntab] is zeroed; begin() states the slice's own refusals and sets up its BTen2 chains.
+// Per window the requested kinds whose ends differ for ANY walker (differ(w, sa, sb) on the host mirror) are packed into a
+// RowPairPlaq and window(p, dval) runs under its own ArenaScope where there is one (else nothing is launched and the zeros stay);
+// advance(j) moves the chains on after every position; epilogue(dval), then ONE read-back of the table into host_out.
 template <typename T>
-template <typename Differ, typename Begin, typename Plaquette, typename Advance, typename Epilogue>
-void Engine<T>::row_pair_walk(const char *what, int row1, int diag_mask, size_t ntab, double *host_out, Differ &&differ, Begin &&begin,
-                              Plaquette &&plaquette, Advance &&advance, Epilogue &&epilogue) {
-  PG_REQUIRE(row1 >= 0 && row1 + 1 < Ly_ && Lx_ >= 2, 1, std::string(what) + ": row pair outside the lattice");
-  PG_REQUIRE(diag_mask >= 1 && diag_mask <= 3, 1, std::string(what) + ": diag_mask must be 1, 2 or 3");
-  const int row2 = row1 + 1;
-  (void)bmps_at_slice(UP, row1);
-  (void)bmps_at_slice(DOWN, row2);
+template <typename Differ, typename Begin, typename Window, typename Advance, typename Epilogue>
+void Engine<T>::pair_walk(const char *what, int orient, int slice1, int mask, int legal, size_t ntab, double *host_out, Differ &&differ,
+                          Begin &&begin, Window &&window, Advance &&advance, Epilogue &&epilogue) {
+  const bool hor = orient == HORIZONTAL;
+  const int N = hor ? Lx_ : Ly_;
+  PG_REQUIRE(slice1 >= 0 && slice1 + 1 < (hor ? Ly_ : Lx_), 1, std::string(what) + ": slice pair outside the lattice");
+  PG_REQUIRE(mask >= 1 && !(mask & ~legal), 1, std::string(what) + ": the mask must be non-zero and within " + std::to_string(legal));
+  (void)bmps_at_slice(hor ? UP : LEFT, slice1);
+  (void)bmps_at_slice(hor ? DOWN : RIGHT, slice1 + 1);
   ArenaBuf<double> dval(arena_, ntab);
   PG_CHECK_HIP(hipMemsetAsync(dval, 0, sizeof(double) * ntab, stream_));
   begin();
-  for (int col1 = 0; col1 + 1 < Lx_; ++col1) {
-    const int col2 = col1 + 1;
-    RowPairPlaq p{col1, {row1 * Lx_ + col1, row2 * Lx_ + col1, row2 * Lx_ + col2, row1 * Lx_ + col2}, {0, 0}, 0};
-    for (int kind = 0; kind < 2; ++kind) {
-      if (!((diag_mask >> kind) & 1)) continue;
-      const int sa = kind == LEFTUP_TO_RIGHTDOWN ? p.s[0] : p.s[1], sb = kind == LEFTUP_TO_RIGHTDOWN ? p.s[2] : p.s[3];
-      bool any = false;
-      for (int w = 0; w < nw_ && !any; ++w) any = differ(w, sa, sb);
-      if (any) p.kinds[p.nc++] = kind;
+  for (int j = 0; j + (hor ? 1 : 2) < N; ++j) {
+    for (int span = hor ? 1 : 2; span <= 2 && j + span < N; ++span) {
+      const int s0 = hor ? slice1 * Lx_ + j : j * Lx_ + slice1, down = (hor ? 1 : span) * Lx_, right = hor ? span : 1;
+      RowPairPlaq p{j, span, {s0, s0 + down, s0 + down + right, s0 + right}, {0, 0}, 0};
+      for (int q = 0; q < 2; ++q) {
+        if (!((mask >> (2 * span - 2 + q)) & 1)) continue;
+        bool any = false;
+        for (int w = 0; w < nw_ && !any; ++w) any = differ(w, p.s[q], p.s[q + 2]);
+        if (any) p.kinds[p.nc++] = 2 * span - 2 + q;
+      }
+      if (p.nc > 0) {
+        ArenaScope scope(arena_);
+        window(p, (double *)dval);
+      }
     }
-    if (p.nc > 0) {
-      ArenaScope scope(arena_);
-      plaquette(p, (double *)dval);
-    }
-    advance(col1);
+    advance(j);
   }
   epilogue((double *)dval);
   PG_CHECK_HIP(hipMemcpyAsync(host_out, dval, sizeof(double) * ntab, hipMemcpyDeviceToHost, stream_));
   PG_CHECK_HIP(hipStreamSynchronize(stream_));
 }
 
+// The window body of the two exchange slices: the candidates of corner_exchange_cand_kernel (dcand: candidates [n][2][4], then flags
+// [n][2]) between the growing BTen2 before the window and the one behind it -- the intermediate tensors of replace_nnn_trace /
+// replace_sqrt5_trace over the candidates -- closed by trace_dot4_kernel, which writes psi' = res exp(lsum) straight into slot
+// `kind` of position p.j of the value table dval [n][N - 1][nk].
+template <typename T>
+void Engine<T>::exchange_window(int orient, int slice1, const RowPairPlaq &p, int *dcand, int nk, double *dval) {
+  const bool hor = orient == HORIZONTAL;
+  const int nc = p.nc, k0 = p.kinds[0], k1 = p.kinds[nc - 1], lo = hor ? LEFT : UP, np = (hor ? Lx_ : Ly_) - 1;
+  int *dflag = dcand + 8 * (size_t)nw_;
+  const int replaced[4] = {0, 1, 2, 3};
+  hipLaunchKernelGGL(corner_exchange_cand_kernel, dim3((nw_ * nc + 255) / 256), dim3(256), 0, stream_, (const int *)cfg_, Ly_ * Lx_, p.s[0],
+                     p.s[1], p.s[2], p.s[3], nc, k0 & 1, k1 & 1, dcand, dflag, nw_);
+  PG_CHECK_HIP(hipGetLastError());
+  PG_REQUIRE(bten2_size(lo) > p.j, 3, "exchange slice: growing BTen2 missing");
+  PlaqHalves h = window_halves(orient, p.span, hor ? slice1 : p.j, hor ? p.j : slice1, bten2_[lo][p.j],
+                               bten2_at_slice(hor ? RIGHT : DOWN, p.j + p.span), dcand, 4, replaced, nc, dflag);
+  close_dot4(h, nc, dflag, k0, k1, (long)np * nk, dval + (size_t)kOut * nk * p.j);
+}
+
 // One row pair of the diagonal-bond pass on the device: InitBTen2(LEFT, row1), GrowFullBTen2(RIGHT, row1, 2, init), then for every
 // column the amplitudes of the configuration with the ends of each requested diagonal exchanged and ShiftBTen2Window(RIGHT, row1)
-// (after the last column too, as the host loop does) -- ONE read-back at the end (row_pair_walk).  Bosonic configurations: the
+// (after the last column too, as the host loop does) -- ONE read-back at the end (pair_walk).  Bosonic configurations: the
 // walkers' own table, no configuration override active (status 3 otherwise).  diag_mask: bit 0 LEFTUP_TO_RIGHTDOWN, bit 1
 // LEFTDOWN_TO_RIGHTUP.  val_out [n][Lx - 1][2] (complex: interleaved): 0.0 for a diagonal that is not in the mask and for an identity
-// move.  The intermediate tensors of a plaquette are those of replace_nnn_trace (plaquette_halves over the candidates); the
-// closure is trace_dot4_kernel, which writes psi' = res exp(lsum) straight into the value table.
-// A diagonal that is masked off, or the identity for EVERY walker (the host mirror of the configurations tells), is no candidate at
-// all (the `any` test of the per-bond hooks); a plaquette without candidates only shifts the window.
+// move.  A diagonal that is masked off, or the identity for EVERY walker (the host mirror of the configurations tells), is no
+// candidate at all (the `any` test of the per-bond hooks); a plaquette without candidates only shifts the window.
 template <typename T>
 void Engine<T>::nnn_exchange_slice(int row1, int diag_mask, double *val_out) {
   require_ready();
   PG_REQUIRE(val_out, 1, "null buffer");
-  const int sites = Ly_ * Lx_, np = Lx_ - 1;
-  ArenaBuf<int> dcand(arena_, 10 * (size_t)nw_);                              // candidates [n][2][4], flags [n][2]
-  int *dflag = dcand + 8 * (size_t)nw_;
-  const int replaced[4] = {0, 1, 2, 3};
-  row_pair_walk(
-      "diagonal slice", row1, diag_mask, (size_t)kOut * nw_ * np * 2, val_out,
+  PG_REQUIRE(Lx_ >= 2, 1, "diagonal slice: row pair outside the lattice");
+  const int sites = Ly_ * Lx_;
+  ArenaBuf<int> dcand(arena_, 10 * (size_t)nw_);
+  pair_walk(
+      "diagonal slice", HORIZONTAL, row1, diag_mask, 3, (size_t)kOut * nw_ * (Lx_ - 1) * 2, val_out,
       [&](int w, int sa, int sb) { return hcfg_[(size_t)w * sites + sa] != hcfg_[(size_t)w * sites + sb]; },
       [&] {
         // (the candidate kernel reads the walkers' own configuration table for all four sites of a plaquette: a configuration override
@@ -501,164 +530,40 @@ void Engine<T>::nnn_exchange_slice(int row1, int diag_mask, double *val_out) {
         init_bten2(LEFT, row1);
         grow_full_bten2(RIGHT, row1, 2, 1);
       },
-      [&](const RowPairPlaq &p, double *dval) {
-        const int nc = p.nc, k0 = p.kinds[0], k1 = p.kinds[nc - 1];
-        hipLaunchKernelGGL(nnn_diag_cand_kernel, dim3((nw_ * nc + 255) / 256), dim3(256), 0, stream_, (const int *)cfg_, sites, p.s[0],
-                           p.s[1], p.s[2], p.s[3], nc, k0, k1, (int *)dcand, dflag, nw_);
-        PG_CHECK_HIP(hipGetLastError());
-        PG_REQUIRE(bten2_size(LEFT) > p.col1, 3, "diagonal slice: LEFT BTen2 missing");
-        PlaqHalves h = plaquette_halves(row1, p.col1, bten2_[LEFT][p.col1], bten2_at_slice(RIGHT, p.col1 + 1), dcand, 4, replaced, nc, dflag);
-        close_dot4(h, nc, dflag, k0, k1, (long)np * 2, dval + (size_t)kOut * 2 * p.col1);
-      },
+      [&](const RowPairPlaq &p, double *dval) { exchange_window(HORIZONTAL, row1, p, dcand, 2, dval); },
       [&](int) { shift_bten2_window(RIGHT, row1); }, [](double *) {});
   nnn_slice_calls() += 1;
 }
 
-// ---- the links of a row pair and of a column pair (spin_onehalf_triangle_heisenbergJ1J2_sqrpeps.h:350-398, :425-442) ----
-// The sqrt5 links of a window are candidates of ONE replacement of its four corner sites, as the two diagonals are of a plaquette.
-// The window at (r, c) is 2 x 3 for a row pair (the flat links) and 3 x 2 for a column pair (the steep links); its corners in the order
-// upper-left, lower-left, lower-right, upper-right are
-//   HORIZONTAL  (r, c), (r+1, c), (r+1, c+2), (r, c+2)        VERTICAL  (r, c), (r+2, c), (r+2, c+1), (r, c+1).
-// cand[w][q][4] = the corner states with the ends of the q-th requested link exchanged, dir = q ? dir1 : dir0: LEFTUP_TO_RIGHTDOWN
-// exchanges the upper-left and the lower-right corner, LEFTDOWN_TO_RIGHTUP the lower-left and the upper-right one; the other two
-// corners keep their own states.  flag[w][q] (the batch_flag convention of the tensor GEMM): >= 0 where the end states are equal (the
-// move is the identity and has no contraction), -1 where the entry has work.
-__global__ void link_sqrt5_cand_kernel(const int *__restrict__ cfg, int sites, int Lx, int vertical, int r, int c, int nc, int dir0,
-                                       int dir1, int *__restrict__ cand, int *__restrict__ flag, int n) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n * nc) return;
-  const int w = e / nc, q = e - w * nc, dir = q ? dir1 : dir0;
-  const int dr = vertical ? 2 : 1, dc = vertical ? 1 : 2;
-  const long cw = (long)w * sites;
-  const int c0 = cfg[cw + r * Lx + c], c1 = cfg[cw + (r + dr) * Lx + c], c2 = cfg[cw + (r + dr) * Lx + c + dc], c3 = cfg[cw + r * Lx + c + dc];
-  int *o = cand + 4 * (long)e;
-  if (dir == LEFTUP_TO_RIGHTDOWN) { o[0] = c2; o[1] = c1; o[2] = c0; o[3] = c3; flag[e] = c0 == c2 ? 1 : -1; }
-  else { o[0] = c0; o[1] = c3; o[2] = c2; o[3] = c1; flag[e] = c1 == c3 ? 1 : -1; }
-}
-
-inline std::atomic<long> &link_slice_calls() {   // completed link_exchange_slice calls of the process (pepsgpu_diag_link_slice_calls)
-  static std::atomic<long> n{0};
-  return n;
-}
-
-// The 2 x 3 / 3 x 2 window at (r, c) between the two-row environments lo (LEFT / UP, before the window) and hi (RIGHT / DOWN, behind
-// it): the three steps of replace_sqrt5_trace over the candidates tab [entry][4] (the corner order of link_sqrt5_cand_kernel), the
-// middle column / row in the walkers' own states.  HORIZONTAL: a = lo grown over column c, then over column c + 1, b = hi over column
-// c + 2; VERTICAL: a = hi grown over row r + 2, then over row r + 1, b = lo over row r.  The halves have the index structure
-// finish_dot4 and trace_dot4_kernel close.  flag: the entry_flag of bten2_step.
-template <typename T>
-typename Engine<T>::PlaqHalves Engine<T>::sqrt5_halves(int orient, int r, int c, const BTenDev &lo, const BTenDev &hi, const int *tab,
-                                                       int nc, const int *flag) {
-  PlaqHalves h;
-  h.lsum = zeros_f64();
-  BTenDev a;
-  if (orient == HORIZONTAL) {
-    const int r2 = r + 1, c2 = c + 1, c3 = c + 2;
-    const BMPSDev &up = bmps_at_slice(UP, r), &dn = bmps_at_slice(DOWN, r2);
-    const SitePick m0{r, c, 0}, m1{r2, c, 1}, m5{r2, c3, 2}, m4{r, c3, 3}, m2{r, c2, -1}, m3{r2, c2, -1};
-    a = bten2_step(LEFT, lo, at_logical(up, UP, c), pick(m0, tab, 4), pick(m1, tab, 4), at_logical(dn, DOWN, c), nc, 1, false, flag);
-    h.b = bten2_step(RIGHT, hi, at_logical(dn, DOWN, c3), pick(m5, tab, 4), pick(m4, tab, 4), at_logical(up, UP, c3), nc, 1, false, flag);
-    h.a = bten2_step(LEFT, a, at_logical(up, UP, c2), pick(m2, tab, 4), pick(m3, tab, 4), at_logical(dn, DOWN, c2), nc, nc, false, flag);
-    add_logs(h.lsum, up.logscale, dn.logscale, lo.logscale, hi.logscale);
-  } else {
-    const int r2 = r + 1, r3 = r + 2, c2 = c + 1;
-    const BMPSDev &lf = bmps_at_slice(LEFT, c), &rt = bmps_at_slice(RIGHT, c2);
-    const SitePick m4{r, c, 0}, m0{r3, c, 1}, m1{r3, c2, 2}, m5{r, c2, 3}, m2{r2, c, -1}, m3{r2, c2, -1};
-    a = bten2_step(DOWN, hi, at_logical(lf, LEFT, r3), pick(m0, tab, 4), pick(m1, tab, 4), at_logical(rt, RIGHT, r3), nc, 1, false, flag);
-    h.b = bten2_step(UP, lo, at_logical(rt, RIGHT, r), pick(m5, tab, 4), pick(m4, tab, 4), at_logical(lf, LEFT, r), nc, 1, false, flag);
-    h.a = bten2_step(DOWN, a, at_logical(lf, LEFT, r2), pick(m2, tab, 4), pick(m3, tab, 4), at_logical(rt, RIGHT, r2), nc, nc, false, flag);
-    add_logs(h.lsum, lf.logscale, rt.logscale, lo.logscale, hi.logscale);
-  }
-  free_ten(a.t);
-  PG_REQUIRE(h.a.t.d[0] == h.b.t.d[3] && h.a.t.d[1] == h.b.t.d[2] && h.a.t.d[2] == h.b.t.d[1] && h.a.t.d[3] == h.b.t.d[0], 3,
-             "trace: two-row environment bond mismatch");
-  return h;
-}
-
 // One row pair (HORIZONTAL, slice1 = row r) or column pair (VERTICAL, slice1 = column c) of the link pass of the triangular J1-J2 model
-// on the device, ONE read-back at the end and no upload.  link_mask bit k requests kind k:
+// on the device, ONE read-back at the end and no upload (pair_walk).  link_mask bit k requests kind k:
 //   HORIZONTAL  0 diagonal (r, c)-(r+1, c+1), 1 diagonal (r+1, c)-(r, c+1), 2 flat link (r, c)-(r+1, c+2), 3 flat link (r+1, c)-(r, c+2);
 //   VERTICAL    2 steep link (r, c)-(r+2, c+1), 3 steep link (r+2, c)-(r, c+1)   (bits 0 and 1: status 1).
-// HORIZONTAL: InitBTen2(LEFT, r), GrowFullBTen2(RIGHT, r, 2, init), then per column the diagonals (plaquette_halves, as
-// nnn_exchange_slice), the flat links (sqrt5_halves) and ShiftBTen2Window(RIGHT, r), after the last column too.  VERTICAL (Ly >= 3):
-// InitBTen2(UP, c), GrowFullBTen2(DOWN, c, 3, init), then per row the steep links and ShiftBTen2Window(DOWN, c) while row + 3 < Ly.
-// Every closure is trace_dot4_kernel into the value table.  val_out [n][N - 1][4] (N = Lx / Ly; complex: interleaved): the amplitude
-// with the two end states of the link exchanged; 0.0 for a kind that is masked off, for equal end states and where the window has no
-// such link.  A kind that is the identity for EVERY walker (the host mirror tells) is no candidate, as in row_pair_walk.  Bosonic
-// configurations only: an active configuration override is status 3.
+// HORIZONTAL: InitBTen2(LEFT, r), GrowFullBTen2(RIGHT, r, 2, init), then per column the diagonals, the flat links and
+// ShiftBTen2Window(RIGHT, r), after the last column too.  VERTICAL (Ly >= 3): InitBTen2(UP, c), GrowFullBTen2(DOWN, c, 3, init), then
+// per row the steep links and ShiftBTen2Window(DOWN, c) while row + 3 < Ly.  val_out [n][N - 1][4] (N = Lx / Ly; complex:
+// interleaved): the amplitude with the two end states of the link exchanged; 0.0 for a kind that is masked off, for equal end states
+// and where the window has no such link.  Bosonic configurations only: an active configuration override is status 3.
 template <typename T>
 void Engine<T>::link_exchange_slice(int orient, int slice1, int link_mask, double *val_out) {
   require_ready();
   PG_REQUIRE(val_out, 1, "null buffer");
   PG_REQUIRE(orient == HORIZONTAL || orient == VERTICAL, 1, "bad orientation");
   const bool hor = orient == HORIZONTAL;
-  PG_REQUIRE(link_mask >= 1 && link_mask <= 15, 1, "link slice: link_mask must be in [1, 15]");
-  PG_REQUIRE(hor || !(link_mask & 3), 1, "link slice: the plaquette diagonals have no vertical form");
-  PG_REQUIRE(slice1 >= 0 && slice1 + 1 < (hor ? Ly_ : Lx_), 1, "link slice: slice pair outside the lattice");
   PG_REQUIRE(hor || Ly_ >= 3, 1, "link slice: a column pair needs three rows");
-  const int N = hor ? Lx_ : Ly_, np = N - 1, sites = Ly_ * Lx_, lo = hor ? LEFT : UP, hi = hor ? RIGHT : DOWN;
-  (void)bmps_at_slice(hor ? UP : LEFT, slice1);
-  (void)bmps_at_slice(hor ? DOWN : RIGHT, slice1 + 1);
-  // (the candidate kernels read the walkers' own configuration table, as in nnn_exchange_slice)
-  PG_REQUIRE(!ovr_on_, 3, "link slice: a configuration override is active (bosonic configurations only)");
-  const size_t ntab = (size_t)kOut * nw_ * np * 4;
-  ArenaBuf<double> dval(arena_, ntab);
-  PG_CHECK_HIP(hipMemsetAsync(dval, 0, sizeof(double) * ntab, stream_));
-  ArenaBuf<int> dcand(arena_, 10 * (size_t)nw_);                              // candidates [n][2][4], flags [n][2]
-  int *dflag = dcand + 8 * (size_t)nw_;
-  const int replaced[4] = {0, 1, 2, 3};
-  // the requested kinds among first, first + 1 whose ends (flat site indices a_q, b_q) differ for some walker
-  struct Pack { int kinds[2], nc; };
-  auto pack = [&](int first, int a0, int b0, int a1, int b1) {
-    Pack p{{0, 0}, 0};
-    for (int q = 0; q < 2; ++q) {
-      if (!((link_mask >> (first + q)) & 1)) continue;
-      const int sa = q ? a1 : a0, sb = q ? b1 : b0;
-      bool any = false;
-      for (int w = 0; w < nw_ && !any; ++w) any = hcfg_[(size_t)w * sites + sa] != hcfg_[(size_t)w * sites + sb];
-      if (any) p.kinds[p.nc++] = first + q;
-    }
-    return p;
-  };
-  const long w_stride = (long)np * 4;
-  init_bten2(lo, slice1);
-  grow_full_bten2(hi, slice1, hor ? 2 : 3, 1);
-  for (int j = 0; j + (hor ? 1 : 2) < N; ++j) {
-    double *out = dval + (size_t)kOut * 4 * j;
-    const int r = hor ? slice1 : j, c = hor ? j : slice1, s0 = r * Lx_ + c;
-    if (hor) {
-      const int s[4] = {s0, s0 + Lx_, s0 + Lx_ + 1, s0 + 1};
-      const Pack p = pack(0, s[0], s[2], s[1], s[3]);
-      if (p.nc > 0) {
-        ArenaScope scope(arena_);
-        const int k0 = p.kinds[0], k1 = p.kinds[p.nc - 1];
-        hipLaunchKernelGGL(nnn_diag_cand_kernel, dim3((nw_ * p.nc + 255) / 256), dim3(256), 0, stream_, (const int *)cfg_, sites, s[0], s[1],
-                           s[2], s[3], p.nc, k0, k1, (int *)dcand, dflag, nw_);
-        PG_CHECK_HIP(hipGetLastError());
-        PG_REQUIRE(bten2_size(LEFT) > c, 3, "link slice: LEFT BTen2 missing");
-        PlaqHalves h = plaquette_halves(r, c, bten2_[LEFT][c], bten2_at_slice(RIGHT, c + 1), dcand, 4, replaced, p.nc, dflag);
-        close_dot4(h, p.nc, dflag, k0, k1, w_stride, out);
-      }
-    }
-    if (j + 2 < N) {
-      const int dr = hor ? 1 : 2, dc = hor ? 2 : 1;
-      const int ul = s0, ll = s0 + dr * Lx_, lr = ll + dc, ur = s0 + dc;
-      const Pack p = pack(2, ul, lr, ll, ur);
-      if (p.nc > 0) {
-        ArenaScope scope(arena_);
-        const int k0 = p.kinds[0], k1 = p.kinds[p.nc - 1];
-        hipLaunchKernelGGL(link_sqrt5_cand_kernel, dim3((nw_ * p.nc + 255) / 256), dim3(256), 0, stream_, (const int *)cfg_, sites, Lx_,
-                           hor ? 0 : 1, r, c, p.nc, k0 - 2, k1 - 2, (int *)dcand, dflag, nw_);
-        PG_CHECK_HIP(hipGetLastError());
-        PG_REQUIRE(bten2_size(lo) > j, 3, "link slice: growing BTen2 missing");
-        PlaqHalves h = sqrt5_halves(orient, r, c, bten2_[lo][j], bten2_at_slice(hi, j + 2), dcand, p.nc, dflag);
-        close_dot4(h, p.nc, dflag, k0, k1, w_stride, out);
-      }
-    }
-    if (hor || j + 3 < N) shift_bten2_window(hi, slice1);
-  }
-  PG_CHECK_HIP(hipMemcpyAsync(val_out, dval, sizeof(double) * ntab, hipMemcpyDeviceToHost, stream_));
-  PG_CHECK_HIP(hipStreamSynchronize(stream_));
+  const int N = hor ? Lx_ : Ly_, sites = Ly_ * Lx_, lo = hor ? LEFT : UP, hi = hor ? RIGHT : DOWN;
+  ArenaBuf<int> dcand(arena_, 10 * (size_t)nw_);
+  pair_walk(
+      "link slice", orient, slice1, link_mask, hor ? 15 : 12, (size_t)kOut * nw_ * (N - 1) * 4, val_out,
+      [&](int w, int sa, int sb) { return hcfg_[(size_t)w * sites + sa] != hcfg_[(size_t)w * sites + sb]; },
+      [&] {
+        // (the candidate kernel reads the walkers' own configuration table, as in nnn_exchange_slice)
+        PG_REQUIRE(!ovr_on_, 3, "link slice: a configuration override is active (bosonic configurations only)");
+        init_bten2(lo, slice1);
+        grow_full_bten2(hi, slice1, hor ? 2 : 3, 1);
+      },
+      [&](const RowPairPlaq &p, double *dval) { exchange_window(orient, slice1, p, dcand, 4, dval); },
+      [&](int j) { if (hor || j + 3 < N) shift_bten2_window(hi, slice1); }, [](double *) {});
   link_slice_calls() += 1;
 }
 
@@ -748,6 +653,7 @@ void Engine<T>::nnn_hop_slice_fermion(int row1, int d, const int32_t *occ, int d
   require_ready();
   PG_REQUIRE(psi_out && val_out && occ, 1, "null buffer");
   PG_REQUIRE(d >= 1 && 4 * d == dp_, 1, "hop slice: the context's physical dimension must be 4 d (extended states), d <= 32");
+  PG_REQUIRE(Lx_ >= 2, 1, "hop slice: row pair outside the lattice");
   const unsigned occ_bits = hop_occ_bits(d, occ);
   const int row2 = row1 + 1, sites = Ly_ * Lx_, np = Lx_ - 1;
   auto hocc = [&](int w, int s) { return (occ_bits >> (hcfg_[(size_t)w * sites + s] % d)) & 1u; };
@@ -759,8 +665,8 @@ void Engine<T>::nnn_hop_slice_fermion(int row1, int d, const int32_t *occ, int d
   const int replaced[4] = {0, 1, 2, 3};
   std::vector<double> h(npsi + nval);
   TwistScope twist{*this};
-  row_pair_walk(
-      "hop slice", row1, diag_mask, npsi + nval, h.data(), [&](int w, int sa, int sb) { return hocc(w, sa) != hocc(w, sb); },
+  pair_walk(
+      "hop slice", HORIZONTAL, row1, diag_mask, 3, npsi + nval, h.data(), [&](int w, int sa, int sb) { return hocc(w, sa) != hocc(w, sb); },
       [&] {
         PG_REQUIRE(!ovr_on_ && bten2_active_ == 0, 3, "hop slice: a configuration override or the second BTen2 set is active");
         for (int w = 0; w < nw_; ++w)
@@ -780,7 +686,7 @@ void Engine<T>::nnn_hop_slice_fermion(int row1, int d, const int32_t *occ, int d
         init_bten2(LEFT, row1);
       },
       [&](const RowPairPlaq &p, double *dval) {      // (set 1 is the active one here)
-        const int nc = p.nc, k0 = p.kinds[0], k1 = p.kinds[nc - 1], col1 = p.col1, kr = Lx_ - 2 - col1;
+        const int nc = p.nc, k0 = p.kinds[0], k1 = p.kinds[nc - 1], col1 = p.j, kr = Lx_ - 2 - col1;
         hipLaunchKernelGGL(nnn_hop_cand_kernel, dim3((nw_ * nc + 255) / 256), dim3(256), 0, stream_, (const int *)cfg_, sites, p.s[0], p.s[1],
                            p.s[2], p.s[3], d, occ_bits, nc, k0, k1, down, dhcand, dflag, dsign + 2 * col1, (long)np * 2, nw_);
         PG_CHECK_HIP(hipGetLastError());
@@ -788,7 +694,7 @@ void Engine<T>::nnn_hop_slice_fermion(int row1, int d, const int32_t *occ, int d
           const std::vector<BTenDev> &ls = bten2_of_set(set, LEFT), &rs = bten2_of_set(set, RIGHT);
           PG_REQUIRE((int)ls.size() > col1 && kr >= 0 && kr < (int)rs.size(), 3, "hop slice: BTen2 environment missing");
           const int *tab = set == 0 ? down : dhcand, *fl = set == 0 ? nullptr : dflag;
-          PlaqHalves hv = plaquette_halves(row1, col1, ls[col1], rs[kr], tab, 4, replaced, set == 0 ? 1 : nc, fl);
+          PlaqHalves hv = window_halves(HORIZONTAL, 1, row1, col1, ls[col1], rs[kr], tab, 4, replaced, set == 0 ? 1 : nc, fl);
           if (set == 0) close_dot4(hv, 1, nullptr, 0, 0, (long)np, dval + (size_t)kOut * col1);
           else close_dot4(hv, nc, dflag, k0, k1, (long)np * 2, dval + npsi + (size_t)kOut * 2 * col1);
         }

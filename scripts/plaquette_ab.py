@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B of two builds of libpepsgpu.so on the two-row (BTen2) traces and the row-pair slices: bit identity of every result and
+"""A/B of two builds of libpepsgpu.so on the two-row (BTen2) traces and the row-pair / column-pair slices: bit identity of every result and
 identity of the launch pattern.
 
     python scripts/plaquette_ab.py --ref PATH/TO/OTHER/libpepsgpu.so [--ref-name TEXT] [--out profiles/plaquette_closure_ab.json] [--only SUBSTR]
@@ -12,7 +12,9 @@ by both.  Between the two libraries the script asserts
 Cases, 4 walkers each, f32 / f64 / c128 (see _cases): nnn_exchange_slice and nnn_hop_slice_fermion over every row pair with masks 3, 1
 and 2 (the hop slice followed by the plain plaquette trace and Trace: the restored state), replace_nnn_trace (both orientations, both
 diagonals, ncand 0 and 2), replace_sqrt5_trace (both orientations), replace_plaquette_trace between sets (0, 0) and (1, 1) under a slice
-override.  The hop lattices are 3 x 4 and 4 x 3 with the (D, chi) tests/test_gpu_tj_nnn.py uses for three and for four rows.
+override, link_exchange_slice on the 4 x 5 state of the diagonal slice, HORIZONTAL over every row pair with masks 15, 12, 3, 8 and 4, then
+VERTICAL over every column pair with masks 12, 8 and 4.  The hop lattices are 3 x 4 and 4 x 3 with the (D, chi)
+tests/test_gpu_tj_nnn.py uses for three and for four rows.
 The first failure ends the run.  A "speed" entry already in the output file is kept.
 
     python scripts/plaquette_ab.py --worker CASE_NAME --states DIR      (internal: one case on the library of PEPSGPU_LIB)
@@ -42,6 +44,7 @@ def _cases():
     c = {}
     for dt in DTYPES:
         c["nnn_slice_4x5_" + dt] = ("slice", "rect", dt)
+        c["link_slice_4x5_" + dt] = ("link", "rect", dt)
         for kind in ("spinless", "tj"):
             for shape in HOP_SHAPES:
                 c["hop_slice_%s_%s_%s" % (kind, shape, dt)] = ("hop", "%s_%s" % (kind, shape), dt)
@@ -110,6 +113,19 @@ def _run_slice(ctx, log, cfgs):
             log.add("row %d mask %d" % (row, mask), ctx.nnn_exchange_slice(row, mask))
         if row + 2 < rows:
             ctx.shift_bmps_window(capi.DOWN)
+
+
+def _run_link(ctx, log, cfgs):
+    from peps_amd import capi
+    rows, cols = cfgs.shape[1:]
+    passes = ((capi.HORIZONTAL, "row", rows, capi.UP, capi.DOWN, (15, 12, 3, 8, 4)), (capi.VERTICAL, "col", cols, capi.LEFT, capi.RIGHT, (12, 8, 4)))
+    for orient, what, n, near, far, masks in passes:
+        ctx.generate_bmps_approach(near)
+        for s in range(n - 1):
+            for mask in masks:
+                log.add("%s %d mask %d" % (what, s, mask), ctx.link_exchange_slice(orient, s, mask))
+            if s + 2 < n:
+                ctx.shift_bmps_window(far)
 
 
 def _run_hop(ctx, log, cfgs, nf):
@@ -190,7 +206,7 @@ def worker(name, d):
     if family == "hop":
         D, chi = HOP_SHAPES[stem.split("_")[1]][2:]
     else:
-        D, chi = (3, 7) if family == "slice" else (3, 27) if family == "sets" else (3, 9)
+        D, chi = (3, 7) if family in ("slice", "link") else (3, 27) if family == "sets" else (3, 9)
     ctx = capi.Context(rows, cols, D, flat.shape[2], chi, dtype={"f32": capi.F32, "f64": capi.F64, "c128": capi.C128}[dt], max_walkers=NW)
     ctx.state_upload(flat)
     ctx.set_configs(cfgs)
@@ -198,6 +214,8 @@ def worker(name, d):
     log = _Log(ctx)
     if family == "slice":
         _run_slice(ctx, log, cfgs)
+    elif family == "link":
+        _run_link(ctx, log, cfgs)
     elif family == "hop":
         _run_hop(ctx, log, cfgs, np.load(os.path.join(d, stem + "_nf.npy")))
     elif family == "traces":

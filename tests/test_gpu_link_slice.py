@@ -1,4 +1,4 @@
-"""GPU tests of the device-side link slice of the triangular J1-J2 model: link_sqrt5_cand_kernel alone against numpy,
+"""GPU tests of the device-side link slice of the triangular J1-J2 model: its candidate kernel alone against numpy,
 pepsgpu_link_exchange_slice in both orientations against the per-call traces on the same context (tests/link_slice_ref.py), its error
 paths, and the host-layer paths that use it (trij1j2 energy, measurement registry and gradient samples) against the hook path
 (PEPSHOST_NO_DEVICE_SWEEP=1), end to end."""
@@ -143,6 +143,40 @@ def test_vertical_link_slice_matches_the_per_call_traces(dtype, D, chi, cols):
         if col + 2 < cols:
             ctx.shift_bmps_window(capi.RIGHT)
     assert seen[2:].all() and not seen[:2].any(), seen           # the steep kinds both ways; a column pair has no diagonal kinds
+    ctx.close()
+
+
+@pytest.mark.parametrize("cols", [2, 3])
+def test_link_and_diagonal_slices_on_the_smallest_lattices(cols):
+    """3 x 2 and 3 x 3, f64, D = 3, chi = 7: the lattices at which the loop bounds of the walk bite.  Two columns: a row pair is one
+    plaquette without a sqrt5 window (mask 12 is all zeros); three columns: exactly one sqrt5 window beside two plaquettes; three rows:
+    a column pair is one window and no ShiftBTen2Window.  Every row pair under masks 15, 12 and 3 (mask 3 also against
+    nnn_exchange_slice) and every column pair under masks 12, 8 and 4, against the per-call traces, BTen2 stack sizes included.  Every
+    kind the lattice has occurs with differing and with equal end states."""
+    from peps_amd import capi
+    rows, dtype = 3, "f64"
+    ctx, cfgs = _context(dtype, 3, 7, rows, cols)
+    seen = {HOR: np.zeros((4, 2), dtype=bool), VER: np.zeros((4, 2), dtype=bool)}
+    ctx.generate_bmps_approach(capi.UP)
+    for row in range(rows - 1):
+        got = _check_pair(ctx, cfgs, HOR, row, (15, 12, 3), dtype, seen[HOR])
+        if cols == 2:
+            assert np.all(got[12] == 0.0), row
+        nnn = ctx.nnn_exchange_slice(row, 3)
+        scale = np.max(np.abs(nnn))
+        assert scale > 0 and np.max(np.abs(got[3][..., :2] - nnn)) < TOL[dtype] * scale, row
+        assert np.array_equal(got[3][..., :2] == 0.0, nnn == 0.0)
+        if row + 2 < rows:
+            ctx.shift_bmps_window(capi.DOWN)
+    ctx.generate_bmps_approach(capi.LEFT)
+    for col in range(cols - 1):
+        _check_pair(ctx, cfgs, VER, col, (12, 8, 4), dtype, seen[VER])
+        if col + 2 < cols:
+            ctx.shift_bmps_window(capi.RIGHT)
+    for orient, n in ((HOR, rows), (VER, cols)):
+        exists = np.any([ref.exists_table(cfgs, orient, s) for s in range(n - 1)], axis=(0, 1))
+        assert list(exists) == ([True, True, cols > 2, cols > 2] if orient == HOR else [False, False, True, True])
+        assert seen[orient][exists].all() and not seen[orient][~exists].any(), (orient, seen[orient])
     ctx.close()
 
 

@@ -570,6 +570,12 @@ int pepsgpu_diag_gram_chol_wave(const float *P, int K, int n, int nbatch, const 
 int pepsgpu_diag_chol_adaptive(int dtype_out, const double *G, int n, int nbatch, void *R_out, int32_t *mlive_out);
 int pepsgpu_diag_jacobi(int dtype, void *M, int m, int len, int nbatch, int k, void *Vt_out, void *S_out,
                         int force_global, int *sweeps_out);
+/* the short-row Jacobi with its select epilogue alone (jacobi_rows_tiny4_kernel, the form the low-rank sites launch):
+ * M = [nbatch][m][len] float32 (len <= 128, not written), rows[b] live rows of entry b, k rows of Vt per entry, span != 0 asks for
+ * the span path (JrSelect::span).  Vt_out [nbatch][k][len], klive_out and sweeps_out [nbatch] are read as well: an entry
+ * the kernel does not take (0 or more than 16 live rows) comes back unchanged.  sweeps word: sweeps | live rows << 8 */
+int pepsgpu_diag_trunc_rows(const float *M, int m, int len, int nbatch, const int32_t *rows, int k, int span, float *Vt_out,
+                            int32_t *klive_out, int32_t *sweeps_out);
 const char *pepsgpu_version(void);
 
 #ifdef __cplusplus

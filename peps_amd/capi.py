@@ -43,7 +43,7 @@ SYMBOLS = [
     "pepsgpu_sr_cg_solve", "pepsgpu_sr_gram", "pepsgpu_sr_weighted_sum", "pepsgpu_sr_copy_samples",
     "pepsgpu_update_local", "pepsgpu_erase_envs_after_update", "pepsgpu_evaluate_amplitude",
     "pepsgpu_walker_flags", "pepsgpu_sync", "pepsgpu_stats", "pepsgpu_profile_enable", "pepsgpu_profile_read",
-    "pepsgpu_diag_tgemm", "pepsgpu_diag_tgemm_desc", "pepsgpu_diag_tgemm_route", "pepsgpu_diag_tgemm_chain", "pepsgpu_diag_tgemm_chain3", "pepsgpu_diag_chol", "pepsgpu_diag_chol_adaptive", "pepsgpu_diag_chol_pivot", "pepsgpu_diag_rows_qr", "pepsgpu_diag_suwa_todo", "pepsgpu_diag_dot4", "pepsgpu_diag_gram_chol", "pepsgpu_diag_gram_chol_wave", "pepsgpu_diag_gram_cols", "pepsgpu_diag_gram_rows", "pepsgpu_diag_mgemm_dense", "pepsgpu_diag_jacobi", "pepsgpu_version",
+    "pepsgpu_diag_tgemm", "pepsgpu_diag_tgemm_desc", "pepsgpu_diag_tgemm_route", "pepsgpu_diag_tgemm_chain", "pepsgpu_diag_tgemm_chain3", "pepsgpu_diag_chol", "pepsgpu_diag_chol_adaptive", "pepsgpu_diag_chol_pivot", "pepsgpu_diag_rows_qr", "pepsgpu_diag_suwa_todo", "pepsgpu_diag_dot4", "pepsgpu_diag_gram_chol", "pepsgpu_diag_gram_chol_wave", "pepsgpu_diag_gram_cols", "pepsgpu_diag_gram_rows", "pepsgpu_diag_mgemm_dense", "pepsgpu_diag_jacobi", "pepsgpu_diag_trunc_rows", "pepsgpu_version",
 ]
 
 
@@ -170,6 +170,8 @@ def load_library(path=LIB_PATH):
     lib.pepsgpu_diag_chol_adaptive.argtypes = [C.c_int, dp, C.c_int, C.c_int, vp, ip]
     lib.pepsgpu_diag_gram_chol.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, ip]
     lib.pepsgpu_diag_jacobi.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, ip]
+    if hasattr(lib, "pepsgpu_diag_trunc_rows"):     # (PEPSGPU_LIB may name a build from before the entry: A/B against the parent commit)
+        lib.pepsgpu_diag_trunc_rows.argtypes = [vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_int, vp, ip, ip]
     return lib
 
 
@@ -1089,6 +1091,24 @@ def diag_jacobi(dtype, M, k, force_global=False):
     if rc != 0:
         raise RuntimeError("diag_jacobi failed: %s" % lib().pepsgpu_last_error(None).decode())
     return M, Vt, S, sw & 0xFF      # high bits: diagnostics (rows above the noise floor at entry)
+
+
+def diag_trunc_rows(M, rows, k, span, fill=0.0):
+    """The short-row Jacobi with its select epilogue alone (the launch of a low-rank site): M [nb][m][len] float32, rows[b] live
+    rows, k rows of Vt per entry, span: ask for the span path.  Returns Vt [nb][k][len], klive [nb] and the sweeps words
+    (sweeps | live << 8); entries the kernel does not take (0 or more than 16 live rows) keep `fill` / -1 / -1."""
+    M = np.ascontiguousarray(M, dtype=np.float32)
+    nb, m, ln = M.shape
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    assert rows.shape == (nb,)
+    Vt = np.full((nb, k, ln), fill, dtype=np.float32)
+    kl = np.full(nb, -1, dtype=np.int32)
+    sw = np.full(nb, -1, dtype=np.int32)
+    rc = lib().pepsgpu_diag_trunc_rows(M.ctypes.data_as(C.c_void_p), m, ln, nb, _ip(rows), int(k), int(bool(span)),
+                                       Vt.ctypes.data_as(C.c_void_p), _ip(kl), _ip(sw))
+    if rc != 0:
+        raise RuntimeError("diag_trunc_rows failed: %s" % lib().pepsgpu_last_error(None).decode())
+    return Vt, kl, sw
 
 
 class Walker:

@@ -1149,3 +1149,38 @@ extern "C" int pepsgpu_diag_jacobi(int dtype, void *M, int m, int len, int nbatc
     else diag_jacobi_t<double>(M, m, len, nbatch, k, Vt, S, force_global, sweeps);
   });
 }
+
+// The sel form of the short-row Jacobi alone, as trunc_jacobi launches it on a low-rank site (len <= 64: CPL = 4, else 8).
+extern "C" int pepsgpu_diag_trunc_rows(const float *M, int m, int len, int nbatch, const int32_t *rows, int k, int span, float *Vt,
+                                       int32_t *klive, int32_t *sweeps) {
+  return guarded(nullptr, [&]() {
+    PG_REQUIRE(m >= 1 && len >= 1 && len <= 128 && nbatch >= 1 && k >= 1, 1, "bad sizes");
+    float *dM, *dV;
+    int *dm, *dk, *dsw;
+    const size_t ne = (size_t)m * len * nbatch, nv = (size_t)k * len * nbatch;
+    PG_CHECK_HIP(hipMalloc(&dM, ne * sizeof(float)));
+    PG_CHECK_HIP(hipMalloc(&dV, nv * sizeof(float)));
+    PG_CHECK_HIP(hipMalloc(&dm, nbatch * sizeof(int)));
+    PG_CHECK_HIP(hipMalloc(&dk, nbatch * sizeof(int)));
+    PG_CHECK_HIP(hipMalloc(&dsw, nbatch * sizeof(int)));
+    PG_CHECK_HIP(hipMemcpy(dM, M, ne * sizeof(float), hipMemcpyHostToDevice));
+    PG_CHECK_HIP(hipMemcpy(dV, Vt, nv * sizeof(float), hipMemcpyHostToDevice));
+    PG_CHECK_HIP(hipMemcpy(dm, rows, nbatch * sizeof(int), hipMemcpyHostToDevice));
+    PG_CHECK_HIP(hipMemcpy(dk, klive, nbatch * sizeof(int), hipMemcpyHostToDevice));
+    PG_CHECK_HIP(hipMemcpy(dsw, sweeps, nbatch * sizeof(int), hipMemcpyHostToDevice));
+    JrSelect sel;
+    sel.V = dV; sel.wV = (long)k * len; sel.k = k; sel.klive_out = dk; sel.span = span ? 1 : 0;
+    if (len <= 64)
+      hipLaunchKernelGGL((jacobi_rows_tiny4_kernel<4>), dim3((nbatch + 15) / 16), dim3(256), 0, 0, dM, (long)m * len, m, len, len, 40, dsw,
+                         (const int *)dm, 1, nbatch, sel);
+    else
+      hipLaunchKernelGGL((jacobi_rows_tiny4_kernel<8>), dim3((nbatch + 15) / 16), dim3(256), 0, 0, dM, (long)m * len, m, len, len, 40, dsw,
+                         (const int *)dm, 1, nbatch, sel);
+    PG_CHECK_HIP(hipGetLastError());
+    PG_CHECK_HIP(hipDeviceSynchronize());
+    PG_CHECK_HIP(hipMemcpy(Vt, dV, nv * sizeof(float), hipMemcpyDeviceToHost));
+    PG_CHECK_HIP(hipMemcpy(klive, dk, nbatch * sizeof(int), hipMemcpyDeviceToHost));
+    PG_CHECK_HIP(hipMemcpy(sweeps, dsw, nbatch * sizeof(int), hipMemcpyDeviceToHost));
+    (void)hipFree(dM); (void)hipFree(dV); (void)hipFree(dm); (void)hipFree(dk); (void)hipFree(dsw);
+  });
+}

@@ -661,6 +661,8 @@ void Engine<T>::trunc_jacobi(AbsorbState &s, const SiteDims &d, int i, DTen<T> &
   JrSelect jsel;
   if constexpr (sizeof(T) == 4) {
     if (t.kn_i) { jsel.V = (float *)t.V.p; jsel.wV = t.V.n; jsel.k = t.k; jsel.klive_out = t.kn_i; jsel.trunc_err = trunc_err_; jsel.dmin = chi_min_; }
+    // span-only truncation (PEPSGPU_TRUNC_SPAN=0: the sweeps for every walker); a truncation-error rule needs the singular values
+    jsel.span = trunc_err_ == 0.0 && trunc_span();
   }
   // Size classes of the Jacobi kernels above the carry rank of the row absorbed before (+ margin) are not launched (each
   // is a launch of nw blocks that return at once); the live counts read back at the end of this absorption verify it,
@@ -684,13 +686,18 @@ void Engine<T>::trunc_jacobi(AbsorbState &s, const SiteDims &d, int i, DTen<T> &
   prof_end();
   ++n_jacobi_;
   if (dbg_sweeps_) {   // diagnostics only: per-launch sweep counts (forces a sync)
-    long mx = 0, live = 0, sw_sum = 0, live_mx = 0;
-    for (int v : dbg_read(sweeps_)) { mx = std::max<long>(mx, v & 0xFF); sw_sum += v & 0xFF; live += v >> 8; live_mx = std::max<long>(live_mx, v >> 8); }
+    long mx = 0, live = 0, sw_sum = 0, live_mx = 0, span = 0, span_back = 0;
+    const bool span_asked = t.sel_done && jsel.span;
+    for (int v : dbg_read(sweeps_)) {
+      mx = std::max<long>(mx, v & 0xFF); sw_sum += v & 0xFF; live += v >> 8; live_mx = std::max<long>(live_mx, v >> 8);
+      // span walkers: zero sweeps and live rows; with the path asked for, a short-row walker that swept kept more than k directions
+      if (span_asked && (v >> 8) > 0 && (v >> 8) <= JR_BR) { if ((v & 0xFF) == 0) ++span; else ++span_back; }
+    }
     jacobi_sweeps_sum_ += mx;
     jacobi_sweeps_max_ = std::max(jacobi_sweeps_max_, mx);
     if (getenv("PEPSGPU_DEBUG_VERBOSE"))
-      fprintf(stderr, "[pepsgpu] jacobi m=%d len=%d sweeps max=%ld mean=%.2f live_rows_mean=%.1f live_rows_max=%ld\n", m, uk, mx,
-              (double)sw_sum / nw_, (double)live / nw_, live_mx);
+      fprintf(stderr, "[pepsgpu] jacobi m=%d len=%d sweeps max=%ld mean=%.2f live_rows_mean=%.1f live_rows_max=%ld span=%ld span_fell_back=%ld\n",
+              m, uk, mx, (double)sw_sum / nw_, (double)live / nw_, live_mx, span, span_back);
   }
 }
 

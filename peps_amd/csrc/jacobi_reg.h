@@ -853,6 +853,19 @@ __device__ __forceinline__ int jr_intra16(JrRowT<CPL> (&a)[JR_BR], float (&na)[J
   return rot;
 }
 
+// squared norm of a row in its 16-lane group: the f64 sum of the exact f32 squares, as the select epilogue forms it
+template <int CPL>
+__device__ __forceinline__ double jrx_norm2_f64(const JrRowT<CPL> &x) {
+  double t = 0.0;
+#pragma unroll
+  for (int q = 0; q < CPL; ++q) t = fma((double)x.get(q), (double)x.get(q), t);
+  t += lw_dpp_f64<0xB1>(t);
+  t += lw_dpp_f64<0x4E>(t);
+  t += lw_dpp_f64<0x141>(t);
+  t += lw_dpp_f64<0x140>(t);
+  return t;
+}
+
 template <int CPL>
 __global__ __launch_bounds__(256, CPL <= 4 ? 3 : 2) void jacobi_rows_tiny4_kernel(float *__restrict__ Mg, long wM, int m, int len, int ld,
                                                                                int max_sweeps, int *__restrict__ sweeps_out,
@@ -876,6 +889,79 @@ __global__ __launch_bounds__(256, CPL <= 4 ? 3 : 2) void jacobi_rows_tiny4_kerne
     for (int q = 0; q < CPL; ++q) {
       const int c = CPL * l16 + q;
       a[i].set(q, (i < mm && c < len) ? M[(long)i * ld + c] : 0.f);
+    }
+  }
+  if (sel.V && sel.span && sel.trunc_err == 0.0) {
+    // ---- span path: nothing is truncated on a walker whose kept directions fit k, and only the ROW SPACE of M leaves the site
+    // (Vt and Y = Tt Vt^T carry the same bond gauge) -- an orthonormal basis of the rows instead of the singular vectors.  Rows in
+    // their own order (the pivoted factor has graded them), classical Gram-Schmidt with TWO passes per row (one pass loses
+    // orthogonality on graded rows), a row whose remainder is below the liveness floor of the select epilogue is dropped and
+    // stays behind as a zero row (projecting against it is a no-op: every register index is static).  A walker that keeps more
+    // than k directions truncates for real: it reloads its rows (this form never writes M) and takes the sweeps below. ----
+    double fro2 = 0.0;
+#pragma unroll
+    for (int i = 0; i < JR_BR; ++i)
+      if (i < mm_max) fro2 += jrx_norm2_f64<CPL>(a[i]);       // (rows beyond a walker's count are zero)
+    const double nfloor2 = 4.0 * NOISE_C * NOISE_C * (double)Eps<float>::v * (double)Eps<float>::v * fro2;   // (2 NOISE_C eps |M|_F)^2
+    unsigned keep = 0u;
+    int count = 0;
+#pragma unroll
+    for (int j = 0; j < JR_BR; ++j) {
+      if (j < mm_max) {
+#pragma unroll
+        for (int pass = 0; pass < 2; ++pass) {
+          float c[JR_BR];
+#pragma unroll
+          for (int i = 0; i < j; ++i) c[i] = jg_sum16(jrx_dot<CPL>(a[i], a[j]));    // independent of each other
+#pragma unroll
+          for (int i = 0; i < j; ++i) {
+            const jr_f2 c2 = {-c[i], -c[i]};
+#pragma unroll
+            for (int k = 0; k < CPL / 2; ++k) a[j].p[k] = __builtin_elementwise_fma(c2, a[i].p[k], a[j].p[k]);
+          }
+        }
+        const double n2 = jrx_norm2_f64<CPL>(a[j]);
+        const bool kp = n2 > nfloor2;
+        const float inv = kp ? (float)jr_rsq64(n2) : 0.f;
+        const jr_f2 inv2 = {inv, inv};
+#pragma unroll
+        for (int k = 0; k < CPL / 2; ++k) a[j].p[k] = a[j].p[k] * inv2;
+        keep |= kp ? (1u << j) : 0u;
+        count += kp ? 1 : 0;
+      }
+    }
+    const bool redo = mm > 0 && count > sel.k;
+    if (mm > 0 && !redo) {
+      float *V = sel.V + (long)walker * sel.wV;
+      int r = 0;                                              // rows in order of emission (uniform in the lane group)
+#pragma unroll
+      for (int j = 0; j < JR_BR; ++j) {
+        if ((keep >> j) & 1u) {
+#pragma unroll
+          for (int q = 0; q < CPL; ++q) {
+            const int c = CPL * l16 + q;
+            if (c < len) V[(long)r * len + c] = a[j].get(q);
+          }
+          ++r;
+        }
+      }
+      for (int e = count * len + l16; e < sel.k * len; e += 16) V[e] = 0.f;
+      if (l16 == 0) {
+        if (sel.klive_out) sel.klive_out[walker] = count;
+        if (sweeps_out) sweeps_out[walker] = mm << 8;         // zero sweeps: a span walker
+      }
+    }
+    if (!__any(redo)) return;
+    mm = redo ? mm : 0;                                       // the walkers that are done take no part in the tournament
+    mm_max = max(mm, __shfl_xor(mm, 16, 64));
+    mm_max = max(mm_max, __shfl_xor(mm_max, 32, 64));
+#pragma unroll
+    for (int i = 0; i < JR_BR; ++i) {
+#pragma unroll
+      for (int q = 0; q < CPL; ++q) {
+        const int c = CPL * l16 + q;
+        a[i].set(q, (i < mm && c < len) ? M[(long)i * ld + c] : 0.f);
+      }
     }
   }
 #pragma unroll

@@ -1707,7 +1707,14 @@ struct JrSelect {
   int *klive_out = nullptr;
   double trunc_err = 0.0;
   int dmin = 0;
+  int span = 0;            // trunc_err == 0: an orthonormal basis of the ROW SPACE (two-pass Gram-Schmidt, no sweeps) for every walker whose
+                           // kept directions fit k -- nothing is truncated there, only the span leaves the site (jacobi_rows_tiny4_kernel)
 };
+// PEPSGPU_TRUNC_SPAN=0: no launch asks for the span path (read once per process)
+inline bool trunc_span() {
+  static const bool v = !(getenv("PEPSGPU_TRUNC_SPAN") && atoi(getenv("PEPSGPU_TRUNC_SPAN")) == 0);
+  return v;
+}
 
 
 // ---------------------------------------------------------------------------------------------

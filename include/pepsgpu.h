@@ -442,6 +442,54 @@ int pepsgpu_sr_gram(pepsgpu_ctx *ctx, const void *remote_samples_dev, const int3
 int pepsgpu_sr_weighted_sum(pepsgpu_ctx *ctx, const double *y, double *out);
 int pepsgpu_sr_copy_samples(pepsgpu_ctx *ctx, void *dst_samples_dev, int32_t *dst_configs_dev);
 
+/* Device-resident optimisation step: the first-order update rules of optimizer/optimizer_impl.h and the one-rank SR step on
+ * buffers that stay in HBM.  Master parameters theta, the gradient / direction g and the rule state (velocity, m1, m2, acc, the
+ * Adam timestep) are float64 -- interleaved complex float64 on a PEPSGPU_C128 context; m2 and acc are real there too -- in the
+ * layout of S_O / S_EO, and are freed with the context.  Host buffers of these calls use the padded layout of
+ * pepsgpu_state_upload ([row][col][s][L][D][R][U], float64 / interleaved pairs).  Every call that rewrites the device state
+ * (opt_step, opt_scale_state) leaves the walkers' environments stale exactly as pepsgpu_state_upload does: re-initialise with
+ * pepsgpu_walkers_set_configs.  Status: PEPSGPU_ESTATE before pepsgpu_opt_begin (and for opt_begin without a state, opt_natural_gradient
+ * with an empty sample store, opt_gradient_from_accumulators with nothing accumulated); PEPSGPU_EINVAL for a non-finite or negative
+ * lr, an unknown rule, a wrong n_params, a non-finite or negative rule parameter, an Adam beta outside [0, 1), weight_sum <= 0, a
+ * NULL buffer.  A refused call leaves theta, the rule state and the device state untouched.
+ *   pepsgpu_opt_begin      theta <- double(device state), device to device; clears the rule state.  Call again after a
+ *                          pepsgpu_state_upload to adopt the uploaded state.
+ *   pepsgpu_opt_end        frees the optimizer buffers.
+ *   pepsgpu_opt_gradient_from_accumulators
+ *                          g <- (S_EO - conj(E) S_O) / W with E = e_loc_sum / weight_sum (e_loc_sum: 1 double, 2 on a complex context)
+ *                          from the resident accumulators: GradAccumulatorT::Finish / exact_summation_energy_evaluator.h:286-295 without
+ *                          pepsgpu_grad_read.  energy_out (1 or 2 doubles) and grad_norm_out = sqrt(sum |g|^2) may be NULL.  The norm is a
+ *                          two-stage sum in a fixed order: equal accumulators give bit-identical norms.
+ *   pepsgpu_opt_set_gradient / pepsgpu_opt_get_gradient
+ *                          g from / to the host (what a caller with its own gradient, or a test, needs).
+ *   pepsgpu_opt_clip       optimizer_impl.h:311-316: first the element-wise clip (clip_value > 0: real sign(x) min(|x|, c), complex
+ *                          x min(1, c / |x|)), then ClipByGlobalNorm (split_index_tps_impl.h:573-580; clip_norm > 0: g *= clip_norm / r
+ *                          only if r > clip_norm, r taken after the element-wise clip).  norm_before_out (nullable) = sqrt(sum |g|^2) on entry.
+ *   pepsgpu_opt_natural_gradient
+ *                          StochasticReconfigurationUpdate's solve on one rank (optimizer_impl.h, SR branch): the loop of
+ *                          pepsgpu_sr_cg_solve with b = g, x0 = 0 read and the solution written in HBM, g <- x.
+ *                          direction_norm_out (nullable) = sqrt(sum |x|^2).  Multi-rank: peps_amd/sr.py.
+ *   pepsgpu_opt_step       one fused pass: theta, rule state and device state = T(theta).  rule 0 SGD (optimizer_impl.h:949-990), params
+ *                          (momentum, nesterov != 0, weight_decay); 1 AdaGrad (:1252-1307), params (epsilon, initial_accumulator_value:
+ *                          taken at the first AdaGrad step after opt_begin); 2 Adam (:1327-1396), params (beta1, beta2, epsilon,
+ *                          weight_decay).  ElementWiseInv(eps) = 1 / (x + eps) in both.
+ *   pepsgpu_opt_scale_state theta *= factor, device state = T(theta): the `*= scale_factor_on_site` of NormalizeStateOrder1
+ *                          (monte_carlo_engine.h:206-240).
+ *   pepsgpu_opt_read_state theta to the host. */
+int pepsgpu_opt_begin(pepsgpu_ctx *ctx);
+int pepsgpu_opt_end(pepsgpu_ctx *ctx);
+int pepsgpu_opt_gradient_from_accumulators(pepsgpu_ctx *ctx, const double *e_loc_sum, double weight_sum, double *energy_out,
+                                           double *grad_norm_out);
+int pepsgpu_opt_set_gradient(pepsgpu_ctx *ctx, const double *host);
+int pepsgpu_opt_get_gradient(pepsgpu_ctx *ctx, double *host);
+int pepsgpu_opt_clip(pepsgpu_ctx *ctx, double clip_value, double clip_norm, double *norm_before_out);
+int pepsgpu_opt_natural_gradient(pepsgpu_ctx *ctx, double diag_shift, int max_iter, double relative_tolerance, double absolute_tolerance,
+                                 int residual_recompute_interval, double orthogonality_threshold, double *residual_norm, int *iterations,
+                                 int *reason, double *direction_norm_out);
+int pepsgpu_opt_step(pepsgpu_ctx *ctx, int rule, double lr, const double *params, int n_params);
+int pepsgpu_opt_scale_state(pepsgpu_ctx *ctx, double factor);
+int pepsgpu_opt_read_state(pepsgpu_ctx *ctx, double *host);
+
 /* TPSWaveFunctionComponent::UpdateLocal (wave_function_component.h:345-378) for the walkers with
  * accept_mask[w] != 0 (NULL = all): config(site_k) = new_states[w][k], tn.UpdateSiteTensor,
  * contractor.EraseEnvsAfterUpdate(site_k) (trace.h:538-589).  sites = [n_sites][2] (row, col). */

@@ -41,6 +41,9 @@ SYMBOLS = [
     "pepsgpu_allreduce",
     "pepsgpu_sr_begin", "pepsgpu_sr_append", "pepsgpu_sr_count", "pepsgpu_sr_sum", "pepsgpu_sr_matvec", "pepsgpu_sr_matvec_c128",
     "pepsgpu_sr_cg_solve", "pepsgpu_sr_gram", "pepsgpu_sr_weighted_sum", "pepsgpu_sr_copy_samples",
+    "pepsgpu_opt_begin", "pepsgpu_opt_end", "pepsgpu_opt_gradient_from_accumulators", "pepsgpu_opt_set_gradient",
+    "pepsgpu_opt_get_gradient", "pepsgpu_opt_clip", "pepsgpu_opt_natural_gradient", "pepsgpu_opt_step", "pepsgpu_opt_scale_state",
+    "pepsgpu_opt_read_state",
     "pepsgpu_update_local", "pepsgpu_erase_envs_after_update", "pepsgpu_evaluate_amplitude",
     "pepsgpu_walker_flags", "pepsgpu_sync", "pepsgpu_stats", "pepsgpu_profile_enable", "pepsgpu_profile_read",
     "pepsgpu_diag_tgemm", "pepsgpu_diag_tgemm_desc", "pepsgpu_diag_tgemm_route", "pepsgpu_diag_tgemm_chain", "pepsgpu_diag_tgemm_chain3", "pepsgpu_diag_chol", "pepsgpu_diag_chol_adaptive", "pepsgpu_diag_chol_pivot", "pepsgpu_diag_rows_qr", "pepsgpu_diag_suwa_todo", "pepsgpu_diag_dot4", "pepsgpu_diag_gram_chol", "pepsgpu_diag_gram_chol_wave", "pepsgpu_diag_gram_cols", "pepsgpu_diag_gram_rows", "pepsgpu_diag_mgemm_dense", "pepsgpu_diag_jacobi", "pepsgpu_diag_trunc_rows", "pepsgpu_version",
@@ -149,6 +152,17 @@ def load_library(path=LIB_PATH):
     lib.pepsgpu_sr_gram.argtypes = [vp, vp, vp, C.c_int, dp]
     lib.pepsgpu_sr_weighted_sum.argtypes = [vp, dp, dp]
     lib.pepsgpu_sr_copy_samples.argtypes = [vp, vp, vp]
+    if hasattr(lib, "pepsgpu_opt_begin"):           # (PEPSGPU_LIB may name a build from before these entries: A/B against the parent commit)
+        lib.pepsgpu_opt_begin.argtypes = [vp]
+        lib.pepsgpu_opt_end.argtypes = [vp]
+        lib.pepsgpu_opt_gradient_from_accumulators.argtypes = [vp, dp, C.c_double, dp, dp]
+        lib.pepsgpu_opt_set_gradient.argtypes = [vp, dp]
+        lib.pepsgpu_opt_get_gradient.argtypes = [vp, dp]
+        lib.pepsgpu_opt_clip.argtypes = [vp, C.c_double, C.c_double, dp]
+        lib.pepsgpu_opt_natural_gradient.argtypes = [vp, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, dp, ip, ip, dp]
+        lib.pepsgpu_opt_step.argtypes = [vp, C.c_int, C.c_double, dp, C.c_int]
+        lib.pepsgpu_opt_scale_state.argtypes = [vp, C.c_double]
+        lib.pepsgpu_opt_read_state.argtypes = [vp, dp]
     lib.pepsgpu_update_local.argtypes = [vp, C.c_int, ip, ip, C.POINTER(C.c_uint8)]
     lib.pepsgpu_erase_envs_after_update.argtypes = [vp, C.c_int, C.c_int]
     lib.pepsgpu_evaluate_amplitude.argtypes = [vp, dp]
@@ -564,6 +578,67 @@ class Context:
 
     def sr_copy_samples(self, dst_samples_ptr, dst_configs_ptr):
         self._ck(self._l.pepsgpu_sr_copy_samples(self._h, dst_samples_ptr, dst_configs_ptr))
+
+    # -- device-resident optimisation step: theta, g and the rule state stay in HBM (include/pepsgpu.h, pepsgpu_opt_*) --
+    OPT_SGD, OPT_ADAGRAD, OPT_ADAM = 0, 1, 2
+
+    def _state_shape(self):
+        return (self.rows, self.cols, self.d, self.D, self.D, self.D, self.D)
+
+    def opt_begin(self):
+        self._ck(self._l.pepsgpu_opt_begin(self._h))
+
+    def opt_end(self):
+        self._ck(self._l.pepsgpu_opt_end(self._h))
+
+    def opt_gradient_from_accumulators(self, e_loc_sum, weight_sum):
+        """g <- (S_EO - conj(E) S_O) / W from the resident accumulators; returns (E, |g|)."""
+        es = np.ascontiguousarray([e_loc_sum], dtype=self._ot)
+        e = np.zeros(1, dtype=self._ot)
+        nrm = np.zeros(1, dtype=np.float64)
+        self._ck(self._l.pepsgpu_opt_gradient_from_accumulators(self._h, _dp(es), float(weight_sum), _dp(e), _dp(nrm)))
+        return e[0], float(nrm[0])
+
+    def opt_set_gradient(self, g):
+        g = np.ascontiguousarray(g, dtype=self._ot)
+        if g.shape != self._state_shape():
+            raise ValueError("the gradient has the padded state layout %s" % (self._state_shape(),))
+        self._ck(self._l.pepsgpu_opt_set_gradient(self._h, _dp(g)))
+
+    def opt_get_gradient(self):
+        out = np.zeros(self._state_shape(), dtype=self._ot)
+        self._ck(self._l.pepsgpu_opt_get_gradient(self._h, _dp(out)))
+        return out
+
+    def opt_clip(self, clip_value=0.0, clip_norm=0.0):
+        """element-wise clip, then global-norm clip (a bound <= 0 is off); returns |g| on entry"""
+        nrm = np.zeros(1, dtype=np.float64)
+        self._ck(self._l.pepsgpu_opt_clip(self._h, float(clip_value), float(clip_norm), _dp(nrm)))
+        return float(nrm[0])
+
+    def opt_natural_gradient(self, diag_shift=0.001, max_iter=100, relative_tolerance=1e-4, absolute_tolerance=0.0,
+                             residual_recompute_interval=20, orthogonality_threshold=0.5):
+        """g <- (S + diag_shift)^-1 g on the device; returns (residual_norm, iterations, reason, |direction|)."""
+        res = np.zeros(2, dtype=np.float64)
+        it = np.zeros(2, dtype=np.int32)
+        self._ck(self._l.pepsgpu_opt_natural_gradient(self._h, diag_shift, max_iter, relative_tolerance, absolute_tolerance,
+                                                      residual_recompute_interval, orthogonality_threshold, _dp(res[:1]),
+                                                      _ip(it[:1]), _ip(it[1:]), _dp(res[1:])))
+        return float(res[0]), int(it[0]), int(it[1]), float(res[1])
+
+    def opt_step(self, rule, lr, params):
+        """rule 0 SGD (momentum, nesterov, weight_decay), 1 AdaGrad (epsilon, initial_accumulator_value),
+        2 Adam (beta1, beta2, epsilon, weight_decay)"""
+        p = np.ascontiguousarray(params, dtype=np.float64).ravel()
+        self._ck(self._l.pepsgpu_opt_step(self._h, int(rule), float(lr), _dp(p), p.size))
+
+    def opt_scale_state(self, factor):
+        self._ck(self._l.pepsgpu_opt_scale_state(self._h, float(factor)))
+
+    def opt_read_state(self):
+        out = np.zeros(self._state_shape(), dtype=self._ot)
+        self._ck(self._l.pepsgpu_opt_read_state(self._h, _dp(out)))
+        return out
 
     def grad_reset(self):
         self._ck(self._l.pepsgpu_grad_reset(self._h))

@@ -4,6 +4,7 @@
 #include "engine_impl.h"
 #include "engine_nnn.h"
 #include "engine_sr.h"
+#include "engine_opt.h"
 #include "engine_var.h"
 #include "engine_cplx.h"
 #include "engine_walker.h"
@@ -436,6 +437,38 @@ int pepsgpu_sr_weighted_sum(pepsgpu_ctx *ctx, const double *y, double *out) {
 }
 int pepsgpu_sr_copy_samples(pepsgpu_ctx *ctx, void *dst_samples_dev, int32_t *dst_configs_dev) {
   CTX_CALL(PG_REQUIRE(dst_samples_dev && dst_configs_dev, 1, "null destination"); ctx->eng->sr_copy_samples(dst_samples_dev, dst_configs_dev));
+}
+// ---- device-resident optimisation step (engine_opt.h) ----
+int pepsgpu_opt_begin(pepsgpu_ctx *ctx) { CTX_CALL(ctx->eng->opt_begin()); }
+int pepsgpu_opt_end(pepsgpu_ctx *ctx) { CTX_CALL(ctx->eng->opt_end()); }
+int pepsgpu_opt_gradient_from_accumulators(pepsgpu_ctx *ctx, const double *e_loc_sum, double weight_sum, double *energy_out,
+                                           double *grad_norm_out) {
+  CTX_CALL(PG_REQUIRE(e_loc_sum != nullptr, 1, "null e_loc_sum");
+           ctx->eng->opt_gradient_from_accumulators(e_loc_sum, weight_sum, energy_out, grad_norm_out));
+}
+int pepsgpu_opt_set_gradient(pepsgpu_ctx *ctx, const double *host) {
+  CTX_CALL(PG_REQUIRE(host != nullptr, 1, "null gradient"); ctx->eng->opt_set_gradient(host));
+}
+int pepsgpu_opt_get_gradient(pepsgpu_ctx *ctx, double *host) {
+  CTX_CALL(PG_REQUIRE(host != nullptr, 1, "null output"); ctx->eng->opt_get_gradient(host));
+}
+int pepsgpu_opt_clip(pepsgpu_ctx *ctx, double clip_value, double clip_norm, double *norm_before_out) {
+  CTX_CALL(ctx->eng->opt_clip(clip_value, clip_norm, norm_before_out));
+}
+int pepsgpu_opt_natural_gradient(pepsgpu_ctx *ctx, double diag_shift, int max_iter, double relative_tolerance, double absolute_tolerance,
+                                 int residual_recompute_interval, double orthogonality_threshold, double *residual_norm, int *iterations,
+                                 int *reason, double *direction_norm_out) {
+  CTX_CALL(PG_REQUIRE(residual_norm && iterations && reason, 1, "null argument");
+           PG_REQUIRE(max_iter >= 0 && relative_tolerance >= 0.0 && absolute_tolerance >= 0.0, 1, "bad CG parameters");
+           ctx->eng->opt_natural_gradient(diag_shift, max_iter, relative_tolerance, absolute_tolerance, residual_recompute_interval,
+                                          orthogonality_threshold, residual_norm, iterations, reason, direction_norm_out));
+}
+int pepsgpu_opt_step(pepsgpu_ctx *ctx, int rule, double lr, const double *params, int n_params) {
+  CTX_CALL(ctx->eng->opt_step(rule, lr, params, n_params));
+}
+int pepsgpu_opt_scale_state(pepsgpu_ctx *ctx, double factor) { CTX_CALL(ctx->eng->opt_scale_state(factor)); }
+int pepsgpu_opt_read_state(pepsgpu_ctx *ctx, double *host) {
+  CTX_CALL(PG_REQUIRE(host != nullptr, 1, "null output"); ctx->eng->opt_read_state(host));
 }
 int pepsgpu_update_local(pepsgpu_ctx *ctx, int nsites, const int32_t *sites, const int32_t *ns, const uint8_t *mask) {
   CTX_CALL(ctx->eng->update_local(nsites, sites, ns, mask));

@@ -116,6 +116,19 @@ struct EngineBase {
   virtual void sr_gram(const void *remote_o, const int32_t *remote_cfg, int n_remote, double *out) = 0;
   virtual void sr_weighted_sum(const double *y, double *out) = 0;
   virtual void sr_copy_samples(void *dst_o, int32_t *dst_cfg) = 0;
+  // device-resident optimisation step (engine_opt.h): theta, g and the rule state in HBM in the layout of S_O / S_EO
+  virtual void opt_begin() = 0;
+  virtual void opt_end() = 0;
+  virtual void opt_gradient_from_accumulators(const double *e_loc_sum, double weight_sum, double *energy_out, double *grad_norm_out) = 0;
+  virtual void opt_set_gradient(const double *host) = 0;
+  virtual void opt_get_gradient(double *host) = 0;
+  virtual void opt_clip(double clip_value, double clip_norm, double *norm_before_out) = 0;
+  virtual void opt_natural_gradient(double diag_shift, int max_iter, double rel_tol, double abs_tol, int recompute_interval,
+                                    double ortho_threshold, double *residual_norm, int *iterations, int *reason,
+                                    double *direction_norm_out) = 0;
+  virtual void opt_step(int rule, double lr, const double *params, int n_params) = 0;
+  virtual void opt_scale_state(double factor) = 0;
+  virtual void opt_read_state(double *host) = 0;
   // one row / column of exchange moves (pair_table nullable) and of full-space moves (Suwa-Todo over phys_dim^2 states); engine_sweep.h
   virtual void sweep_slice_exchange(int orient, int slice, int n_uniform, const double *uniforms, const int32_t *pair_table,
                                     double *amp_inout, int32_t *consumed_out, int32_t *accepted_out, int32_t *slice_states_out) = 0;
@@ -829,6 +842,24 @@ class Engine : public EngineBase {
   void sr_copy_samples(void *dst_o, int32_t *dst_cfg) override;
   void sr_release();
   void sr_convert(const double *src, double *dst, bool to_compact) const;
+  void layout_maps();
+  // ---- device-resident optimisation step (engine_opt.h) ----
+  void opt_begin() override;
+  void opt_end() override;
+  void opt_gradient_from_accumulators(const double *e_loc_sum, double weight_sum, double *energy_out, double *grad_norm_out) override;
+  void opt_set_gradient(const double *host) override;
+  void opt_get_gradient(double *host) override;
+  void opt_clip(double clip_value, double clip_norm, double *norm_before_out) override;
+  void opt_natural_gradient(double diag_shift, int max_iter, double rel_tol, double abs_tol, int recompute_interval,
+                            double ortho_threshold, double *residual_norm, int *iterations, int *reason,
+                            double *direction_norm_out) override;
+  void opt_step(int rule, double lr, const double *params, int n_params) override;
+  void opt_scale_state(double factor) override;
+  void opt_read_state(double *host) override;
+  void opt_release();
+  void opt_read(const double *dev, double *host);
+  double opt_norm_sq(const double *x);
+  dim3 opt_grid() const { return dim3((unsigned)((slot_ + 255) / 256), (unsigned)(Ly_ * Lx_ * dp_)); }
 
   // out layout = state upload layout [row][col][s][L][D][R][U] zero padded to D
   void grad_read(double *so, double *seo) override {
@@ -1586,6 +1617,14 @@ class Engine : public EngineBase {
   double *sr_delta_ = nullptr, *sr_v_ = nullptr, *sr_out_ = nullptr;
   int sr_cap_ = 0, sr_n_ = 0;
   std::vector<uint32_t> sr_map_c_, sr_map_p_;   // compact <-> padded element index of every stored tensor element
+  double *sr_cg_dev_ = nullptr;            // sr_cg_solve: a b / x_out equal to this pointer is a device vector (compact layout)
+  // optimizer buffers (engine_opt.h), layout of so_ / seo_: theta, g, velocity, m1 of the element type, m2 and acc real
+  double *opt_theta_ = nullptr, *opt_g_ = nullptr, *opt_vel_ = nullptr, *opt_m1_ = nullptr, *opt_m2_ = nullptr, *opt_acc_ = nullptr;
+  double *opt_part_ = nullptr;             // partial sums of the norm, then its result
+  int *opt_ne_ = nullptr;                  // live elements of a slot per site
+  long opt_t_ = 0;                         // Adam timestep
+  bool opt_acc_ready_ = false;             // acc holds initial_accumulator_value (set by the first AdaGrad step after opt_begin)
+  static constexpr int kOptDotBlocks = 512;
   // ---- BMPSWalker objects (engine_walker.h) ----
   struct WalkerDev {
     BMPSDev b;                       // the forked boundary MPS (all walkers of the context)

@@ -1,0 +1,357 @@
+// Device-resident optimisation step (the first-order update rules of optimizer/optimizer_impl.h and the one-rank SR step):
+// master parameters theta, the gradient / direction g and the rule state live in HBM in the layout of the accumulators
+// S_O / S_EO ([row][col][s][D^4 slot], compact inside the slot, float64 or interleaved complex float64), so that
+// "evaluate -> finish -> clip -> [natural gradient] -> step" never moves a tensor over PCIe.  Every kernel is element-wise and
+// memory bound; the unused tail of a slot is never touched and stays exactly zero in every buffer.
+//   begin     theta <- double(sitps_), rule state cleared
+//   finish    g <- (S_EO - conj(E) S_O) / W                              GradAccumulatorT::Finish, exact_summation_energy_evaluator.h:286-295
+//   norm      sum |g|^2 in two stages of fixed order (no atomics)        SplitIndexTPS::NormSquare
+//   clip      element-wise, then global norm                             optimizer_impl.h:311-316, split_index_tps_impl.h:566-580
+//   step      SGD (:949-990), AdaGrad (:1252-1307), Adam (:1327-1396): one fused pass that also writes sitps_ = T(theta)
+//   scale     theta *= f, sitps_ = T(theta)                              NormalizeStateOrder1, monte_carlo_engine.h:206-240
+// ElementWiseInv(eps) is taken as 1 / (x + eps) in both AdaGrad and Adam ("Unpinned").
+#pragma once
+#include "engine_sr.h"
+
+namespace pepsgpu {
+
+enum { OPT_SGD = 0, OPT_ADAGRAD = 1, OPT_ADAM = 2 };
+
+// scalars of one step, by value
+struct OptStepArgs {
+  double lr;
+  double decay;          // 1 - lr * weight_decay (SGD, Adam); 1: no decay
+  double mu;             // SGD momentum
+  int nesterov;          // SGD
+  double eps;            // AdaGrad, Adam
+  double b1, b2;         // Adam
+  double inv_bc1, inv_bc2;   // Adam: 1 / (1 - beta^t)
+};
+
+template <typename T> __device__ __forceinline__ void opt_store_state(T *s, long k, const double *th) { s[k] = T(th[0]); }
+template <> __device__ __forceinline__ void opt_store_state<c128>(c128 *s, long k, const double *th) { s[k] = c128(th[0], th[1]); }
+template <typename T> __device__ __forceinline__ void opt_load_state(const T *s, long k, double *th) { th[0] = (double)s[k]; }
+template <> __device__ __forceinline__ void opt_load_state<c128>(const c128 *s, long k, double *th) { th[0] = s[k].re; th[1] = s[k].im; }
+
+// Every element-wise kernel below: grid (ceil(slot / 256), sites * dp), one thread per element of one slot; only the live
+// elements (e < ne[site]) are read or written.
+#define OPT_ELEM_PROLOGUE                                                 \
+  const int q = blockIdx.y;                                               \
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;             \
+  if (e >= ne[q / dp]) return;                                            \
+  const long k = (long)q * slot + e;
+
+// theta <- double(sitps_)
+template <typename T>
+__global__ __launch_bounds__(256) void opt_begin_kernel(const T *__restrict__ sitps, double *__restrict__ theta,
+                                                        const int *__restrict__ ne, long slot, int dp) {
+  constexpr int Z = is_cplx<T>::value ? 2 : 1;
+  OPT_ELEM_PROLOGUE
+  double th[Z];
+  opt_load_state<T>(sitps, k, th);
+  for (int z = 0; z < Z; ++z) theta[Z * k + z] = th[z];
+}
+
+// g <- (S_EO - conj(E) S_O) / W        (e_im = -Im E: the conjugate is taken by the caller)
+template <int Z>
+__global__ __launch_bounds__(256) void opt_finish_kernel(const double *__restrict__ so, const double *__restrict__ seo,
+                                                         double e_re, double ec_im, double w, double *__restrict__ g,
+                                                         const int *__restrict__ ne, long slot, int dp) {
+#pragma clang fp contract(off)
+  OPT_ELEM_PROLOGUE
+  if constexpr (Z == 1) {
+    g[k] = (seo[k] - e_re * so[k]) / w;
+  } else {
+    const double sr = so[2 * k], si = so[2 * k + 1];
+    g[2 * k] = (seo[2 * k] - (e_re * sr - ec_im * si)) / w;
+    g[2 * k + 1] = (seo[2 * k + 1] - (e_re * si + ec_im * sr)) / w;
+  }
+}
+
+// element-wise clip: real sign(x) min(|x|, c); complex x min(1, c / |x|)
+template <int Z>
+__global__ __launch_bounds__(256) void opt_clip_value_kernel(double *__restrict__ g, double c, const int *__restrict__ ne,
+                                                             long slot, int dp) {
+#pragma clang fp contract(off)
+  OPT_ELEM_PROLOGUE
+  if constexpr (Z == 1) {
+    const double x = g[k];
+    if (fabs(x) > c) g[k] = copysign(c, x);
+  } else {
+    const double xr = g[2 * k], xi = g[2 * k + 1];
+    const double a = hypot(xr, xi);
+    if (a > c) {
+      const double f = c / a;
+      g[2 * k] = xr * f; g[2 * k + 1] = xi * f;
+    }
+  }
+}
+
+// x *= f on the live elements (global-norm clip of g; with a state pointer: theta *= f, sitps_ = T(theta))
+template <typename T, bool kState>
+__global__ __launch_bounds__(256) void opt_scale_kernel(double *__restrict__ x, double f, T *__restrict__ sitps,
+                                                        const int *__restrict__ ne, long slot, int dp) {
+  constexpr int Z = is_cplx<T>::value ? 2 : 1;
+  OPT_ELEM_PROLOGUE
+  double th[Z];
+  for (int z = 0; z < Z; ++z) { th[z] = x[Z * k + z] * f; x[Z * k + z] = th[z]; }
+  if constexpr (kState) opt_store_state<T>(sitps, k, th);
+}
+
+// acc <- value on the live elements (AdaGrad: initial_accumulator_value)
+__global__ __launch_bounds__(256) void opt_fill_kernel(double *__restrict__ x, double v, const int *__restrict__ ne, long slot,
+                                                       int dp) {
+  OPT_ELEM_PROLOGUE
+  x[k] = v;
+}
+
+// One fused pass per rule: reads theta, g and the rule's state, writes theta, the state and sitps_ = T(theta).
+// s1 = velocity (SGD) / m1 (Adam), element type; s2 = acc (AdaGrad) / m2 (Adam), real.
+// Contraction into fused multiply-adds is off: the result is the separately rounded arithmetic of the host restatement.
+template <typename T, int RULE>
+__global__ __launch_bounds__(256) void opt_step_kernel(OptStepArgs a, double *__restrict__ theta, const double *__restrict__ g,
+                                                       double *__restrict__ s1, double *__restrict__ s2, T *__restrict__ sitps,
+                                                       const int *__restrict__ ne, long slot, int dp) {
+#pragma clang fp contract(off)
+  constexpr int Z = is_cplx<T>::value ? 2 : 1;
+  OPT_ELEM_PROLOGUE
+  double th[Z], gz[Z];
+  double g2 = 0.0;
+  for (int z = 0; z < Z; ++z) {
+    th[z] = theta[Z * k + z];
+    gz[z] = g[Z * k + z];
+    g2 += gz[z] * gz[z];
+  }
+  if constexpr (RULE == OPT_SGD) {
+    for (int z = 0; z < Z; ++z) {
+      if (a.decay != 1.0) th[z] *= a.decay;
+      double upd = gz[z];
+      if (a.mu > 0.0) {
+        const double v = a.mu * s1[Z * k + z] + gz[z];
+        s1[Z * k + z] = v;
+        upd = a.nesterov ? a.mu * v + gz[z] : v;
+      }
+      th[z] += (-a.lr) * upd;
+    }
+  } else if constexpr (RULE == OPT_ADAGRAD) {
+    const double acc = s2[k] + g2;
+    s2[k] = acc;
+    const double rate = 1.0 / (sqrt(acc) + a.eps);
+    for (int z = 0; z < Z; ++z) th[z] += -((rate * gz[z]) * a.lr);
+  } else {
+    const double m2 = a.b2 * s2[k] + (1.0 - a.b2) * g2;
+    s2[k] = m2;
+    const double den = 1.0 / (sqrt(a.inv_bc2 * m2) + a.eps);
+    for (int z = 0; z < Z; ++z) {
+      if (a.decay != 1.0) th[z] *= a.decay;
+      const double m1 = a.b1 * s1[Z * k + z] + (1.0 - a.b1) * gz[z];
+      s1[Z * k + z] = m1;
+      th[z] += -((den * (a.inv_bc1 * m1)) * a.lr);
+    }
+  }
+  for (int z = 0; z < Z; ++z) theta[Z * k + z] = th[z];
+  opt_store_state<T>(sitps, k, th);
+}
+
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+void Engine<T>::opt_release() {
+  for (double *p : {opt_theta_, opt_g_, opt_vel_, opt_m1_, opt_m2_, opt_acc_, opt_part_}) arena_.free(p);
+  arena_.free(opt_ne_);
+  opt_theta_ = opt_g_ = opt_vel_ = opt_m1_ = opt_m2_ = opt_acc_ = opt_part_ = nullptr;
+  opt_ne_ = nullptr;
+  opt_t_ = 0;
+  opt_acc_ready_ = false;
+}
+
+template <typename T>
+void Engine<T>::opt_begin() {
+  PG_REQUIRE(have_state_, 3, "opt_begin: no state uploaded (pepsgpu_state_upload)");
+  const int sites = Ly_ * Lx_;
+  PG_REQUIRE((long)sites * dp_ <= 65535, 1, "opt_begin: rows * cols * phys_dim exceeds the grid y limit");
+  opt_release();
+  layout_maps();
+  try {
+  const size_t n = (size_t)sites * dp_ * slot_;
+  opt_theta_ = (double *)arena_.alloc(sizeof(double) * n * kOut);
+  opt_g_ = (double *)arena_.alloc(sizeof(double) * n * kOut);
+  opt_vel_ = (double *)arena_.alloc(sizeof(double) * n * kOut);
+  opt_m1_ = (double *)arena_.alloc(sizeof(double) * n * kOut);
+  opt_m2_ = (double *)arena_.alloc(sizeof(double) * n);
+  opt_acc_ = (double *)arena_.alloc(sizeof(double) * n);
+  opt_part_ = (double *)arena_.alloc(sizeof(double) * (kOptDotBlocks + 8));
+  opt_ne_ = (int *)arena_.alloc(sizeof(int) * sites);
+  std::vector<int> ne(sites);
+  for (int r = 0; r < Ly_; ++r)
+    for (int c = 0; c < Lx_; ++c) {
+      int dd[4];
+      site_dims(r, c, dd);
+      ne[r * Lx_ + c] = dd[0] * dd[1] * dd[2] * dd[3];
+    }
+  PG_CHECK_HIP(hipMemcpyAsync(opt_ne_, ne.data(), sizeof(int) * sites, hipMemcpyHostToDevice, stream_));
+  for (double *p : {opt_theta_, opt_g_, opt_vel_, opt_m1_}) PG_CHECK_HIP(hipMemsetAsync(p, 0, sizeof(double) * n * kOut, stream_));
+  for (double *p : {opt_m2_, opt_acc_}) PG_CHECK_HIP(hipMemsetAsync(p, 0, sizeof(double) * n, stream_));
+  hipLaunchKernelGGL(opt_begin_kernel<T>, opt_grid(), dim3(256), 0, stream_, (const T *)sitps_, opt_theta_, (const int *)opt_ne_,
+                     slot_, dp_);
+  PG_CHECK_HIP(hipGetLastError());
+  PG_CHECK_HIP(hipStreamSynchronize(stream_));   // (ne is a host temporary)
+  } catch (...) {
+    opt_release();
+    throw;
+  }
+}
+
+template <typename T>
+void Engine<T>::opt_end() {
+  PG_CHECK_HIP(hipStreamSynchronize(stream_));
+  opt_release();
+}
+
+// sum |x|^2 over the n * kOut doubles of an optimizer vector: per-block partial sums, then one wave adds them in a fixed order
+template <typename T>
+double Engine<T>::opt_norm_sq(const double *x) {
+  const long n = (long)Ly_ * Lx_ * dp_ * slot_ * kOut;
+  hipLaunchKernelGGL(sr_dot_kernel, dim3(kOptDotBlocks), dim3(256), 0, stream_, x, x, n, opt_part_);
+  hipLaunchKernelGGL(sr_dot_final_kernel, dim3(1), dim3(64), 0, stream_, (const double *)opt_part_, (int)kOptDotBlocks,
+                     opt_part_ + kOptDotBlocks);
+  PG_CHECK_HIP(hipGetLastError());
+  double out = 0.0;
+  PG_CHECK_HIP(hipMemcpyAsync(&out, opt_part_ + kOptDotBlocks, sizeof(double), hipMemcpyDeviceToHost, stream_));
+  PG_CHECK_HIP(hipStreamSynchronize(stream_));
+  return out;
+}
+
+template <typename T>
+void Engine<T>::opt_gradient_from_accumulators(const double *e_loc_sum, double weight_sum, double *energy_out, double *grad_norm_out) {
+  PG_REQUIRE(opt_theta_ != nullptr, 3, "opt_gradient_from_accumulators: call pepsgpu_opt_begin first");
+  PG_REQUIRE(so_ != nullptr, 3, "opt_gradient_from_accumulators: nothing accumulated");
+  PG_REQUIRE(std::isfinite(weight_sum) && weight_sum > 0.0, 1, "opt_gradient_from_accumulators: weight_sum must be positive");
+  for (int z = 0; z < kOut; ++z) PG_REQUIRE(std::isfinite(e_loc_sum[z]), 1, "opt_gradient_from_accumulators: non-finite e_loc_sum");
+  const double e_re = e_loc_sum[0] / weight_sum, e_im = kCplx ? e_loc_sum[1] / weight_sum : 0.0;
+  hipLaunchKernelGGL(opt_finish_kernel<kOut>, opt_grid(), dim3(256), 0, stream_, (const double *)so_, (const double *)seo_, e_re, -e_im,
+                     weight_sum, opt_g_, (const int *)opt_ne_, slot_, dp_);
+  PG_CHECK_HIP(hipGetLastError());
+  const double nsq = opt_norm_sq(opt_g_);
+  if (energy_out) { energy_out[0] = e_re; if (kCplx) energy_out[1] = e_im; }
+  if (grad_norm_out) *grad_norm_out = std::sqrt(nsq);
+}
+
+template <typename T>
+void Engine<T>::opt_set_gradient(const double *host) {
+  PG_REQUIRE(opt_theta_ != nullptr, 3, "opt_set_gradient: call pepsgpu_opt_begin first");
+  const size_t n = (size_t)Ly_ * Lx_ * dp_ * slot_ * kOut;
+  std::vector<double> h(n);
+  sr_convert(host, h.data(), true);
+  PG_CHECK_HIP(hipMemcpyAsync(opt_g_, h.data(), n * sizeof(double), hipMemcpyHostToDevice, stream_));
+  PG_CHECK_HIP(hipStreamSynchronize(stream_));
+}
+
+template <typename T>
+void Engine<T>::opt_read(const double *dev, double *host) {
+  const size_t n = (size_t)Ly_ * Lx_ * dp_ * slot_ * kOut;
+  std::vector<double> h(n);
+  PG_CHECK_HIP(hipMemcpyAsync(h.data(), dev, n * sizeof(double), hipMemcpyDeviceToHost, stream_));
+  PG_CHECK_HIP(hipStreamSynchronize(stream_));
+  sr_convert(h.data(), host, false);
+}
+template <typename T>
+void Engine<T>::opt_get_gradient(double *host) {
+  PG_REQUIRE(opt_theta_ != nullptr, 3, "opt_get_gradient: call pepsgpu_opt_begin first");
+  opt_read(opt_g_, host);
+}
+template <typename T>
+void Engine<T>::opt_read_state(double *host) {
+  PG_REQUIRE(opt_theta_ != nullptr, 3, "opt_read_state: call pepsgpu_opt_begin first");
+  opt_read(opt_theta_, host);
+}
+
+template <typename T>
+void Engine<T>::opt_clip(double clip_value, double clip_norm, double *norm_before_out) {
+  PG_REQUIRE(opt_theta_ != nullptr, 3, "opt_clip: call pepsgpu_opt_begin first");
+  PG_REQUIRE(!std::isnan(clip_value) && !std::isnan(clip_norm), 1, "opt_clip: NaN bound");
+  double r = std::sqrt(opt_norm_sq(opt_g_));
+  if (norm_before_out) *norm_before_out = r;
+  if (clip_value > 0.0) {
+    hipLaunchKernelGGL(opt_clip_value_kernel<kOut>, opt_grid(), dim3(256), 0, stream_, opt_g_, clip_value, (const int *)opt_ne_, slot_, dp_);
+    PG_CHECK_HIP(hipGetLastError());
+    if (clip_norm > 0.0) r = std::sqrt(opt_norm_sq(opt_g_));
+  }
+  if (clip_norm > 0.0 && r > 0.0 && r > clip_norm) {
+    hipLaunchKernelGGL((opt_scale_kernel<T, false>), opt_grid(), dim3(256), 0, stream_, opt_g_, clip_norm / r, (T *)nullptr,
+                       (const int *)opt_ne_, slot_, dp_);
+    PG_CHECK_HIP(hipGetLastError());
+  }
+  PG_CHECK_HIP(hipStreamSynchronize(stream_));
+}
+
+template <typename T>
+void Engine<T>::opt_natural_gradient(double diag_shift, int max_iter, double rel_tol, double abs_tol, int recompute_interval,
+                                     double ortho_threshold, double *residual_norm, int *iterations, int *reason,
+                                     double *direction_norm_out) {
+  PG_REQUIRE(opt_theta_ != nullptr, 3, "opt_natural_gradient: call pepsgpu_opt_begin first");
+  PG_REQUIRE(sr_o_ != nullptr && sr_n_ > 0, 3, "opt_natural_gradient: the sample store is empty (pepsgpu_sr_begin / pepsgpu_sr_append)");
+  struct DevIO {      // b and x of the solve are this device vector for the length of the call
+    double *&slot; DevIO(double *&s, double *p) : slot(s) { slot = p; } ~DevIO() { slot = nullptr; }
+  } io(sr_cg_dev_, opt_g_);
+  sr_cg_solve(opt_g_, nullptr, diag_shift, max_iter, rel_tol, abs_tol, recompute_interval, ortho_threshold, opt_g_, residual_norm,
+              iterations, reason);
+  if (direction_norm_out) *direction_norm_out = std::sqrt(opt_norm_sq(opt_g_));
+}
+
+template <typename T>
+void Engine<T>::opt_step(int rule, double lr, const double *params, int n_params) {
+  PG_REQUIRE(opt_theta_ != nullptr, 3, "opt_step: call pepsgpu_opt_begin first");
+  PG_REQUIRE(std::isfinite(lr) && lr >= 0.0, 1, "opt_step: the learning rate must be finite and non-negative");
+  PG_REQUIRE(rule == OPT_SGD || rule == OPT_ADAGRAD || rule == OPT_ADAM, 1, "opt_step: unknown rule (0 SGD, 1 AdaGrad, 2 Adam)");
+  static const int want[3] = {3, 2, 4};
+  PG_REQUIRE(n_params == want[rule] && params != nullptr, 1, "opt_step: wrong n_params (SGD 3, AdaGrad 2, Adam 4)");
+  for (int i = 0; i < n_params; ++i) PG_REQUIRE(std::isfinite(params[i]), 1, "opt_step: non-finite rule parameter");
+  OptStepArgs a{};
+  a.lr = lr; a.decay = 1.0;
+  const dim3 grid = opt_grid();
+  if (rule == OPT_SGD) {          // (momentum, nesterov, weight_decay)
+    PG_REQUIRE(params[0] >= 0.0 && params[2] >= 0.0, 1, "opt_step: negative SGD momentum / weight_decay");
+    a.mu = params[0]; a.nesterov = params[1] != 0.0;
+    if (params[2] > 0.0) a.decay = 1.0 - lr * params[2];
+    hipLaunchKernelGGL((opt_step_kernel<T, OPT_SGD>), grid, dim3(256), 0, stream_, a, opt_theta_, (const double *)opt_g_, opt_vel_,
+                       (double *)nullptr, sitps_, (const int *)opt_ne_, slot_, dp_);
+  } else if (rule == OPT_ADAGRAD) {   // (epsilon, initial_accumulator_value)
+    PG_REQUIRE(params[0] >= 0.0 && params[1] >= 0.0, 1, "opt_step: negative AdaGrad epsilon / initial_accumulator_value");
+    a.eps = params[0];
+    if (!opt_acc_ready_) {
+      if (params[1] != 0.0) {
+        hipLaunchKernelGGL(opt_fill_kernel, grid, dim3(256), 0, stream_, opt_acc_, params[1], (const int *)opt_ne_, slot_, dp_);
+        PG_CHECK_HIP(hipGetLastError());
+      }
+      opt_acc_ready_ = true;
+    }
+    hipLaunchKernelGGL((opt_step_kernel<T, OPT_ADAGRAD>), grid, dim3(256), 0, stream_, a, opt_theta_, (const double *)opt_g_,
+                       (double *)nullptr, opt_acc_, sitps_, (const int *)opt_ne_, slot_, dp_);
+  } else {                            // (beta1, beta2, epsilon, weight_decay)
+    PG_REQUIRE(params[0] >= 0.0 && params[0] < 1.0 && params[1] >= 0.0 && params[1] < 1.0, 1, "opt_step: Adam beta outside [0, 1)");
+    PG_REQUIRE(params[2] >= 0.0 && params[3] >= 0.0, 1, "opt_step: negative Adam epsilon / weight_decay");
+    ++opt_t_;
+    a.b1 = params[0]; a.b2 = params[1]; a.eps = params[2];
+    if (params[3] > 0.0) a.decay = 1.0 - lr * params[3];
+    a.inv_bc1 = 1.0 / (1.0 - std::pow(a.b1, (double)opt_t_));
+    a.inv_bc2 = 1.0 / (1.0 - std::pow(a.b2, (double)opt_t_));
+    hipLaunchKernelGGL((opt_step_kernel<T, OPT_ADAM>), grid, dim3(256), 0, stream_, a, opt_theta_, (const double *)opt_g_, opt_m1_,
+                       opt_m2_, sitps_, (const int *)opt_ne_, slot_, dp_);
+  }
+  PG_CHECK_HIP(hipGetLastError());
+  state_adopted();      // sitps_ changed: the walkers' environments are stale as after pepsgpu_state_upload
+}
+
+template <typename T>
+void Engine<T>::opt_scale_state(double factor) {
+  PG_REQUIRE(opt_theta_ != nullptr, 3, "opt_scale_state: call pepsgpu_opt_begin first");
+  PG_REQUIRE(std::isfinite(factor), 1, "opt_scale_state: non-finite factor");
+  hipLaunchKernelGGL((opt_scale_kernel<T, true>), opt_grid(), dim3(256), 0, stream_, opt_theta_, factor, sitps_, (const int *)opt_ne_,
+                     slot_, dp_);
+  PG_CHECK_HIP(hipGetLastError());
+  state_adopted();
+}
+
+#undef OPT_ELEM_PROLOGUE
+
+}  // namespace pepsgpu

@@ -206,18 +206,10 @@ void Engine<T>::sr_convert(const double *src, double *dst, bool to_compact) cons
   }
 }
 
+// sr_map_c_ / sr_map_p_ of sr_convert (a property of the lattice: built once per context)
 template <typename T>
-void Engine<T>::sr_begin(int max_samples) {
-  {
-  PG_REQUIRE(max_samples > 0, 1, "sr_begin: need a positive sample capacity");
-  sr_release();
-  const size_t sites = (size_t)Ly_ * Lx_;
-  sr_o_ = (T *)arena_.alloc(sizeof(T) * (size_t)max_samples * sites * slot_);
-  sr_cfg_ = (int *)arena_.alloc(sizeof(int) * (size_t)max_samples * sites);
-  sr_delta_ = (double *)arena_.alloc(sizeof(double) * (size_t)max_samples * kOut);
-  sr_v_ = (double *)arena_.alloc(sizeof(double) * sites * dp_ * slot_ * kOut);
-  sr_out_ = (double *)arena_.alloc(sizeof(double) * sites * dp_ * slot_ * kOut);
-  sr_map_c_.clear(); sr_map_p_.clear();
+void Engine<T>::layout_maps() {
+  if (!sr_map_c_.empty()) return;
   for (int r = 0; r < Ly_; ++r)
     for (int c = 0; c < Lx_; ++c) {
       int dd[4];
@@ -234,6 +226,20 @@ void Engine<T>::sr_begin(int max_samples) {
               }
       }
     }
+}
+
+template <typename T>
+void Engine<T>::sr_begin(int max_samples) {
+  {
+  PG_REQUIRE(max_samples > 0, 1, "sr_begin: need a positive sample capacity");
+  sr_release();
+  const size_t sites = (size_t)Ly_ * Lx_;
+  sr_o_ = (T *)arena_.alloc(sizeof(T) * (size_t)max_samples * sites * slot_);
+  sr_cfg_ = (int *)arena_.alloc(sizeof(int) * (size_t)max_samples * sites);
+  sr_delta_ = (double *)arena_.alloc(sizeof(double) * (size_t)max_samples * kOut);
+  sr_v_ = (double *)arena_.alloc(sizeof(double) * sites * dp_ * slot_ * kOut);
+  sr_out_ = (double *)arena_.alloc(sizeof(double) * sites * dp_ * slot_ * kOut);
+  layout_maps();
   sr_ne_ = (int *)arena_.alloc(sizeof(int) * sites);
   std::vector<int> ne(sites);
   for (int r = 0; r < Ly_; ++r)
@@ -417,7 +423,9 @@ void Engine<T>::sr_cg_solve(const double *b, const double *x0, double diag_shift
     };
     std::vector<double> h(n2);
     auto upload = [&](const double *src, double *dst) {
-      if (src) {
+      if (src && src == sr_cg_dev_) {      // already on the device, compact (engine_opt.h)
+        PG_CHECK_HIP(hipMemcpyAsync(dst, src, n2 * sizeof(double), hipMemcpyDeviceToDevice, stream_));
+      } else if (src) {
         sr_convert(src, h.data(), true);
         PG_CHECK_HIP(hipMemcpyAsync(dst, h.data(), n2 * sizeof(double), hipMemcpyHostToDevice, stream_));
         PG_CHECK_HIP(hipStreamSynchronize(stream_));   // h is reused
@@ -447,9 +455,10 @@ void Engine<T>::sr_cg_solve(const double *b, const double *x0, double diag_shift
       if (diag_shift != 0.0) axpby(diag_shift, v, 1.0, out);
     };
     auto finish = [&](const double *xsrc, double res_sq, int iters, int why) {
-      PG_CHECK_HIP(hipMemcpyAsync(h.data(), xsrc, n2 * sizeof(double), hipMemcpyDeviceToHost, stream_));
+      const bool dev_out = sr_cg_dev_ && x_out == sr_cg_dev_;
+      PG_CHECK_HIP(hipMemcpyAsync(dev_out ? x_out : h.data(), xsrc, n2 * sizeof(double), dev_out ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream_));
       PG_CHECK_HIP(hipStreamSynchronize(stream_));
-      sr_convert(h.data(), x_out, false);
+      if (!dev_out) sr_convert(h.data(), x_out, false);
       *residual_norm = std::sqrt(res_sq); *iterations = iters; *reason = why;
       for (double *v : {db, dx, dr, dp, dap, dbest, dprev, dmean, dsc, dpart}) arena_.free(v);
     };
@@ -518,7 +527,9 @@ void Engine<T>::sr_cg_solve(const double *b, const double *x0, double diag_shift
   };
   std::vector<double> h(n);
   auto upload = [&](const double *src, double *dst) {
-    if (src) {
+    if (src && src == sr_cg_dev_) {      // already on the device, compact (engine_opt.h)
+      PG_CHECK_HIP(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToDevice, stream_));
+    } else if (src) {
       sr_convert(src, h.data(), true);
       PG_CHECK_HIP(hipMemcpyAsync(dst, h.data(), n * sizeof(double), hipMemcpyHostToDevice, stream_));
       PG_CHECK_HIP(hipStreamSynchronize(stream_));   // h is reused
@@ -549,9 +560,10 @@ void Engine<T>::sr_cg_solve(const double *b, const double *x0, double diag_shift
     if (diag_shift != 0.0) axpby(diag_shift, v, 1.0, out);
   };
   auto finish = [&](const double *xsrc, double res_sq, int iters, int why) {
-    PG_CHECK_HIP(hipMemcpyAsync(h.data(), xsrc, n * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    const bool dev_out = sr_cg_dev_ && x_out == sr_cg_dev_;
+    PG_CHECK_HIP(hipMemcpyAsync(dev_out ? x_out : h.data(), xsrc, n * sizeof(double), dev_out ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream_));
     PG_CHECK_HIP(hipStreamSynchronize(stream_));
-    sr_convert(h.data(), x_out, false);
+    if (!dev_out) sr_convert(h.data(), x_out, false);
     *residual_norm = std::sqrt(res_sq); *iterations = iters; *reason = why;
     for (double *v : {db, dx, dr, dp, dap, dbest, dprev, dmean, dsc, dpart}) arena_.free(v);
   };

@@ -122,6 +122,77 @@ void exact_sum_partial_impl(int rows, int cols, int D, int d, int chi, int dtype
   std::copy(packed.begin(), packed.end(), packed_out);
 }
 
+// Optimizer::IterativeOptimize with the exact-summation evaluator, the whole loop in one call: the state is uploaded once, every
+// iteration evaluates the device-resident state, finishes the gradient, clips and steps in HBM; the state comes back once at the end.
+// rule 0 SGD (momentum, nesterov, weight_decay), 1 AdaGrad (epsilon, initial_accumulator_value), 2 Adam (beta1, beta2, epsilon,
+// weight_decay).  energies_out: iterations + 1 entries (re [, im]); grad_norms_out (nullable): the same count.
+template <typename TenElemT>
+void optimize_exact_sum_impl(int rows, int cols, int D, int d, int chi, int dtype, const double *sitps_flat, const int32_t *all_configs,
+                             int n_configs, int model, const double *p, int rule, double lr, const double *rule_params, int n_rule_params,
+                             int iterations, double clip_value, double clip_norm, int batch, double *energies_out, double *grad_norms_out,
+                             double *state_out) {
+  if (iterations < 0 || n_configs < 1 || batch < 1) throw std::invalid_argument("pepshost_optimize_exact_sum: bad iterations / n_configs / batch");
+  if (model < 0 || model > 4) throw std::invalid_argument("pepshost_optimize_exact_sum: model must be xxz, tfim, j1j2, triangle or trij1j2");
+  static const int want[3] = {3, 2, 4};
+  if (rule < 0 || rule > 2 || n_rule_params != want[rule] || !rule_params)
+    throw std::invalid_argument("pepshost_optimize_exact_sum: rule 0 SGD (3 parameters), 1 AdaGrad (2), 2 Adam (4)");
+  SplitIndexTPST<TenElemT> sitps = make_state_t<TenElemT>(rows, cols, D, d, sitps_flat);
+  BMPSContractorT<TenElemT> contractor(rows, cols, D, d, trunc_params(chi), batch, dtype, g_device);
+  std::vector<std::vector<int32_t>> all(n_configs);
+  for (int i = 0; i < n_configs; ++i) all[i].assign(all_configs + (size_t)i * rows * cols, all_configs + (size_t)(i + 1) * rows * cols);
+  OptimizerParams::BaseParams base((size_t)iterations, 0.0, 0.0, (size_t)iterations + 1, lr);   // the stopping criteria are off
+  if (clip_value > 0.0) base.clip_value = clip_value;
+  if (clip_norm > 0.0) base.clip_norm = clip_norm;
+  const double *q = rule_params;
+  AlgorithmParams algo = rule == 0   ? AlgorithmParams(SGDParams(q[0], q[1] != 0.0, q[2]))
+                         : rule == 1 ? AlgorithmParams(AdaGradParams(q[0], q[1]))
+                                     : AlgorithmParams(AdamParams(q[0], q[1], q[2], q[3]));
+  contractor.UploadState(sitps);
+  Optimizer<TenElemT> opt(OptimizerParams(base, algo), contractor);
+  auto run = [&](auto &m) {
+    return opt.IterativeOptimize([&](BMPSContractorT<TenElemT> &c) { return ExactSumAccumulateResident(sitps, all, c, m, (size_t)batch); });
+  };
+  typename Optimizer<TenElemT>::OptimizationResult res;
+  if (model == 0) { SquareSpinOneHalfXXZModelOBC m(p[0], p[1], p[2]); res = run(m); }
+  else if (model == 2) { SquareSpinOneHalfJ1J2XXZModelOBC m(p[0], p[1], p[2], p[3], p[4]); res = run(m); }
+  else if (model == 3) { SpinOneHalfTriHeisenbergSqrPEPS m; res = run(m); }
+  else if (model == 4) { SpinOneHalfTriJ1J2HeisenbergSqrPEPS m(p[0]); res = run(m); }
+  else { TransverseFieldIsingSquareOBC m(p[0]); res = run(m); }
+  copy_out(res.energy_trajectory, energies_out);
+  if (grad_norms_out) std::copy(res.gradient_norms.begin(), res.gradient_norms.end(), grad_norms_out);
+  copy_out(opt.GetState(rows, cols, d, D).flat(), state_out);
+}
+
+// One SR iteration of Optimizer::IterativeOptimize on a given sample set (weight 1 per sample, no sampling): evaluate, finish, natural
+// gradient on the device, theta -= lr x, closing evaluation.  info_out = [E before, E after, CG iterations, |x|, CG residual norm]
+// (energies: real parts).  TFIM and XXZ models.
+template <typename TenElemT>
+void sr_step_samples_impl(int rows, int cols, int D, int d, int chi, int dtype, const double *sitps_flat, int n, const int32_t *configs,
+                          int model, const double *p, double lr, double diag_shift, int cg_max_iter, double cg_relative_tolerance,
+                          int normalize_update, double *state_out, double *info_out) {
+  if (model != 0 && model != 1) throw std::invalid_argument("pepshost_sr_step_samples: model must be xxz or tfim");
+  if (n < 1 || cg_max_iter < 0) throw std::invalid_argument("pepshost_sr_step_samples: bad sample count / CG iterations");
+  SplitIndexTPST<TenElemT> sitps = make_state_t<TenElemT>(rows, cols, D, d, sitps_flat);
+  BMPSContractorT<TenElemT> contractor(rows, cols, D, d, trunc_params(chi), n, dtype, g_device);
+  const Configuration samples = make_cfg(n, rows, cols, configs);
+  StochasticReconfigurationParams sr;
+  sr.cg_params.max_iter = (size_t)cg_max_iter;
+  sr.cg_params.relative_tolerance = cg_relative_tolerance;
+  sr.diag_shift = diag_shift;
+  sr.normalize_update = normalize_update != 0;
+  contractor.UploadState(sitps);
+  Optimizer<TenElemT> opt(OptimizerParams(OptimizerParams::BaseParams(1, 0.0, 0.0, 2, lr), sr), contractor);
+  typename Optimizer<TenElemT>::OptimizationResult res;
+  auto run = [&](auto &m) {
+    return opt.IterativeOptimize([&](BMPSContractorT<TenElemT> &c) { return SampleSetAccumulateResident(sitps, samples, c, m); });
+  };
+  if (model == 0) { SquareSpinOneHalfXXZModelOBC m(p[0], p[1], p[2]); res = run(m); }
+  else { TransverseFieldIsingSquareOBC m(p[0]); res = run(m); }
+  info_out[0] = std::real(res.energy_trajectory.at(0)); info_out[1] = std::real(res.energy_trajectory.at(1));
+  info_out[2] = (double)res.sr_iterations; info_out[3] = res.sr_natural_grad_norm; info_out[4] = res.sr_residual_norm;
+  copy_out(opt.GetState(rows, cols, d, D).flat(), state_out);
+}
+
 template <typename TenElemT>
 void mc_energy_grad_partial_impl(int rows, int cols, int D, int d, int chi, int dtype, const double *sitps_flat, int n,
                                  int32_t *configs, const uint64_t *seeds, int updater, int model, const double *p,
@@ -607,6 +678,64 @@ int pepshost_exact_sum_measure_partial_c128(int rows, int cols, int D, int d, in
   return guarded([&]() {
     exact_sum_measure_partial_impl<QLTEN_Complex>(rows, cols, D, d, chi, PEPSGPU_C128, sitps_flat, all_configs, n_configs, model, p, rank, size,
                                                   batch, keys_out, keys_cap, values_out, values_cap, values_len);
+  });
+}
+
+// Optimizer::IterativeOptimize + exact summation on the device (see optimize_exact_sum_impl)
+int pepshost_optimize_exact_sum(int rows, int cols, int D, int d, int chi, int dtype, const double *sitps_flat, const int32_t *all_configs,
+                                int n_configs, int model, const double *p, int rule, double lr, const double *rule_params, int n_rule_params,
+                                int iterations, double clip_value, double clip_norm, int batch, double *energies_out, double *grad_norms_out,
+                                double *state_out) {
+  return guarded([&]() {
+    optimize_exact_sum_impl<double>(rows, cols, D, d, chi, dtype, sitps_flat, all_configs, n_configs, model, p, rule, lr, rule_params,
+                                    n_rule_params, iterations, clip_value, clip_norm, batch, energies_out, grad_norms_out, state_out);
+  });
+}
+// QLTEN_Complex: sitps_flat, energies_out and state_out are interleaved (re, im) pairs
+int pepshost_optimize_exact_sum_c128(int rows, int cols, int D, int d, int chi, const double *sitps_flat, const int32_t *all_configs,
+                                     int n_configs, int model, const double *p, int rule, double lr, const double *rule_params,
+                                     int n_rule_params, int iterations, double clip_value, double clip_norm, int batch, double *energies_out,
+                                     double *grad_norms_out, double *state_out) {
+  return guarded([&]() {
+    optimize_exact_sum_impl<QLTEN_Complex>(rows, cols, D, d, chi, PEPSGPU_C128, sitps_flat, all_configs, n_configs, model, p, rule, lr,
+                                           rule_params, n_rule_params, iterations, clip_value, clip_norm, batch, energies_out,
+                                           grad_norms_out, state_out);
+  });
+}
+// Optimizer's SR step on a given sample set (see sr_step_samples_impl)
+int pepshost_sr_step_samples(int rows, int cols, int D, int d, int chi, int dtype, const double *sitps_flat, int n, const int32_t *configs,
+                             int model, const double *p, double lr, double diag_shift, int cg_max_iter, double cg_relative_tolerance,
+                             int normalize_update, double *state_out, double *info_out) {
+  return guarded([&]() {
+    sr_step_samples_impl<double>(rows, cols, D, d, chi, dtype, sitps_flat, n, configs, model, p, lr, diag_shift, cg_max_iter,
+                                 cg_relative_tolerance, normalize_update, state_out, info_out);
+  });
+}
+int pepshost_sr_step_samples_c128(int rows, int cols, int D, int d, int chi, const double *sitps_flat, int n, const int32_t *configs,
+                                  int model, const double *p, double lr, double diag_shift, int cg_max_iter, double cg_relative_tolerance,
+                                  int normalize_update, double *state_out, double *info_out) {
+  return guarded([&]() {
+    sr_step_samples_impl<QLTEN_Complex>(rows, cols, D, d, chi, PEPSGPU_C128, sitps_flat, n, configs, model, p, lr, diag_shift, cg_max_iter,
+                                        cg_relative_tolerance, normalize_update, state_out, info_out);
+  });
+}
+// LearningRateScheduler::GetLearningRate (lr_schedulers.h:40-103): kind 0 ConstantLR (lr), 1 ExponentialDecayLR (initial_lr, decay_rate,
+// decay_steps), 2 StepLR (initial_lr, step_size, gamma)
+int pepshost_lr_schedule(int kind, const double *args, int n_args, long iteration, double *lr_out) {
+  return guarded([&]() {
+    if (!args || !lr_out || iteration < 0) throw std::invalid_argument("pepshost_lr_schedule: null argument or negative iteration");
+    static const int want[3] = {1, 3, 3};
+    if (kind < 0 || kind > 2 || n_args != want[kind]) throw std::invalid_argument("pepshost_lr_schedule: kind 0 (1 argument), 1 (3), 2 (3)");
+    std::unique_ptr<LearningRateScheduler> s;
+    if (kind == 0) s = std::make_unique<ConstantLR>(args[0]);
+    else if (kind == 1) {
+      if (!(args[2] >= 1.0)) throw std::invalid_argument("pepshost_lr_schedule: decay_steps must be >= 1");
+      s = std::make_unique<ExponentialDecayLR>(args[0], args[1], (size_t)args[2]);
+    } else {
+      if (!(args[1] >= 1.0)) throw std::invalid_argument("pepshost_lr_schedule: step_size must be >= 1");
+      s = std::make_unique<StepLR>(args[0], (size_t)args[1], args[2]);
+    }
+    *lr_out = s->GetLearningRate((size_t)iteration, 0.0);
   });
 }
 

@@ -19,6 +19,9 @@
 //   TransverseFieldIsingSquareOBC transverse_field_ising_square_obc.h:28-247
 //   ExactSumEnergyEvaluatorMPI   exact_summation_energy_evaluator.h:173-302
 //   MCEnergyGradEvaluator accumulation  mc_energy_grad_evaluator.h:245-310
+//   SGDParams / AdaGradParams / AdamParams / StochasticReconfigurationParams / OptimizerParams   optimizer/optimizer_params.h
+//   ConstantLR / ExponentialDecayLR / StepLR   optimizer/lr_schedulers.h:40-103
+//   Optimizer                    optimizer/optimizer.h, optimizer_impl.h (first-order rules and the one-rank SR step, on device buffers)
 //
 // Error codes of the ABI are re-raised as the reference's exception types.
 #pragma once
@@ -34,12 +37,14 @@
 #include <iomanip>
 #include <limits>
 #include <map>
+#include <memory>
 #include <numeric>
 #include <random>
 #include <sstream>
 #include <stdexcept>
 #include <optional>
 #include <string>
+#include <variant>
 #include <vector>
 
 #include "../../include/pepsgpu.h"
@@ -623,6 +628,38 @@ class BMPSContractorT {
     so.resize(n); seo.resize(n);
     check_rc(pepsgpu_grad_read(ctx_, dptr(so.data()), dptr(seo.data())), ctx_);
   }
+  // device-resident optimisation step (pepsgpu_opt_*): theta, the gradient / direction and the rule state stay in HBM
+  void OptBegin() { check_rc(pepsgpu_opt_begin(ctx_), ctx_); }
+  void OptEnd() { check_rc(pepsgpu_opt_end(ctx_), ctx_); }
+  // g <- (S_EO - conj(E) S_O) / W from the resident accumulators; returns (E, |g|)
+  std::pair<TenElemT, double> OptGradientFromAccumulators(const TenElemT &e_loc_sum, double weight_sum) {
+    TenElemT e(0.0);
+    double nrm = 0.0;
+    check_rc(pepsgpu_opt_gradient_from_accumulators(ctx_, dptr(&e_loc_sum), weight_sum, dptr(&e), &nrm), ctx_);
+    return {e, nrm};
+  }
+  void OptSetGradient(const SplitIndexTPST<TenElemT> &g) { check_rc(pepsgpu_opt_set_gradient(ctx_, dptr(g.flat().data())), ctx_); }
+  void OptGetGradient(SplitIndexTPST<TenElemT> &g) const { check_rc(pepsgpu_opt_get_gradient(ctx_, dptr(g.flat().data())), ctx_); }
+  double OptClip(double clip_value, double clip_norm) {
+    double nrm = 0.0;
+    check_rc(pepsgpu_opt_clip(ctx_, clip_value, clip_norm, &nrm), ctx_);
+    return nrm;
+  }
+  struct NaturalGradientInfo { double residual_norm = 0.0, direction_norm = 0.0; int iterations = 0, reason = 0; };
+  NaturalGradientInfo OptNaturalGradient(double diag_shift, size_t max_iter, double relative_tolerance, double absolute_tolerance,
+                                         int residual_recompute_interval, double orthogonality_threshold) {
+    NaturalGradientInfo r;
+    check_rc(pepsgpu_opt_natural_gradient(ctx_, diag_shift, (int)max_iter, relative_tolerance, absolute_tolerance, residual_recompute_interval,
+                                          orthogonality_threshold, &r.residual_norm, &r.iterations, &r.reason, &r.direction_norm), ctx_);
+    return r;
+  }
+  void OptStep(int rule, double lr, const std::vector<double> &params) {
+    check_rc(pepsgpu_opt_step(ctx_, rule, lr, params.data(), (int)params.size()), ctx_);
+  }
+  void OptScaleState(double factor) { check_rc(pepsgpu_opt_scale_state(ctx_, factor), ctx_); }
+  void OptReadState(SplitIndexTPST<TenElemT> &s) const { check_rc(pepsgpu_opt_read_state(ctx_, dptr(s.flat().data())), ctx_); }
+  void SRBegin(size_t max_samples) { check_rc(pepsgpu_sr_begin(ctx_, (int)max_samples), ctx_); }
+  void SRAppend(const std::vector<TenElemT> &psi) { check_rc(pepsgpu_sr_append(ctx_, dptr(psi.data())), ctx_); }
   void UpdateLocal(const std::vector<int32_t> &sites, const std::vector<int32_t> &new_states, const std::vector<uint8_t> &mask) {
     check_rc(pepsgpu_update_local(ctx_, (int)(sites.size() / 2), sites.data(), new_states.data(), mask.data()), ctx_);
   }
@@ -796,6 +833,13 @@ struct TPSWaveFunctionComponentT {
     contractor.UploadState(sitps);
     InitDevice();                            // tn = TensorNetwork2D(sitps, config); contractor.Init(tn)  (:159-160)
     EvaluateAmplitude();                     // :161
+  }
+  // the state is already on the device (an optimizer step wrote it there, pepsgpu_opt_step): no upload
+  struct ResidentState {};
+  TPSWaveFunctionComponentT(ResidentState, const Configuration &cfg, BMPSContractorT<TenElemT> &c)
+      : config(cfg), contractor(c), trun_para(c.GetTruncateParams()) {
+    InitDevice();
+    EvaluateAmplitude();
   }
   void InitDevice() { contractor.Init(fermion ? fermion->ExtConfig(config, order) : config); }
   // Row pass (horizontal bonds) <-> column pass (vertical bonds) of a sweep / an energy evaluation: a fermionic
@@ -3277,6 +3321,277 @@ std::pair<TenElemT, SplitIndexTPST<TenElemT>> ExactSumEnergyEvaluator(const Spli
   if (allreduce) allreduce(packed);
   acc.Unpack(packed);
   return acc.Finish();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Optimizer (optimizer/optimizer.h, optimizer_impl.h) on device buffers: the master parameters, the gradient and the rule
+// state live in HBM (pepsgpu_opt_*); an iteration is evaluate -> finish -> clip (first-order rules) -> [natural gradient] ->
+// step with no tensor traffic over PCIe.  In: SGD, AdaGrad, Adam and the one-rank SR step.  Out (host drivers of the reference
+// that stay with the caller): L-BFGS, step selectors / line search, spike detection, checkpoints, CSV / JSONL logs, MinSR
+// (peps_amd/sr.py), multi-rank CG.  Parameter names and defaults: optimizer/optimizer_params.h.
+struct ConjugateGradientParams {               // optimizer_params.h:50-57
+  size_t max_iter = 100;
+  double relative_tolerance = 1e-4;
+  double absolute_tolerance = 0.0;
+  int residual_recompute_interval = 20;
+  double orthogonality_threshold = 0.5;
+};
+struct SGDParams {                             // :69-76
+  double momentum;
+  bool nesterov;
+  double weight_decay;
+  SGDParams(double momentum = 0.0, bool nesterov = false, double weight_decay = 0.0)
+      : momentum(momentum), nesterov(nesterov), weight_decay(weight_decay) {}
+};
+struct AdamParams {                            // :82-90
+  double beta1, beta2, epsilon, weight_decay;
+  AdamParams(double b1 = 0.9, double b2 = 0.999, double eps = 1e-8, double wd = 0.0) : beta1(b1), beta2(b2), epsilon(eps), weight_decay(wd) {}
+};
+struct StochasticReconfigurationParams {       // :98-104 (adaptive_diagonal_shift is carried, not applied: the reference does not read it either)
+  ConjugateGradientParams cg_params;
+  double diag_shift = 0.001;
+  bool normalize_update = false;
+  double adaptive_diagonal_shift = 0.0;
+};
+struct AdaGradParams {                         // :192-198
+  double epsilon;
+  double initial_accumulator_value;
+  AdaGradParams(double epsilon, double initial_accumulator_value) : epsilon(epsilon), initial_accumulator_value(initial_accumulator_value) {}
+};
+
+class LearningRateScheduler {                  // lr_schedulers.h:29-37
+ public:
+  virtual ~LearningRateScheduler() = default;
+  virtual double GetLearningRate(size_t iteration, double current_energy = 0.0) const = 0;
+  virtual void Step() {}
+  virtual std::unique_ptr<LearningRateScheduler> Clone() const = 0;
+  virtual std::string Name() const = 0;
+};
+class ConstantLR : public LearningRateScheduler {           // :40-55
+ public:
+  explicit ConstantLR(double lr) : learning_rate_(lr) {}
+  double GetLearningRate(size_t, double) const override { return learning_rate_; }
+  std::unique_ptr<LearningRateScheduler> Clone() const override { return std::make_unique<ConstantLR>(learning_rate_); }
+  std::string Name() const override { return "ConstantLR"; }
+ private:
+  double learning_rate_;
+};
+class ExponentialDecayLR : public LearningRateScheduler {   // :58-80: lr = initial_lr * decay_rate^(iteration / decay_steps)
+ public:
+  ExponentialDecayLR(double initial_lr, double decay_rate, size_t decay_steps)
+      : initial_lr_(initial_lr), decay_rate_(decay_rate), decay_steps_(decay_steps) {}
+  double GetLearningRate(size_t iteration, double) const override {
+    return initial_lr_ * std::pow(decay_rate_, iteration / static_cast<double>(decay_steps_));
+  }
+  std::unique_ptr<LearningRateScheduler> Clone() const override { return std::make_unique<ExponentialDecayLR>(initial_lr_, decay_rate_, decay_steps_); }
+  std::string Name() const override { return "ExponentialDecayLR"; }
+ private:
+  double initial_lr_, decay_rate_;
+  size_t decay_steps_;
+};
+class StepLR : public LearningRateScheduler {               // :83-105: lr = initial_lr * gamma^floor(iteration / step_size)
+ public:
+  StepLR(double initial_lr, size_t step_size, double gamma = 0.1) : initial_lr_(initial_lr), gamma_(gamma), step_size_(step_size) {}
+  double GetLearningRate(size_t iteration, double) const override { return initial_lr_ * std::pow(gamma_, iteration / step_size_); }
+  std::unique_ptr<LearningRateScheduler> Clone() const override { return std::make_unique<StepLR>(initial_lr_, step_size_, gamma_); }
+  std::string Name() const override { return "StepLR"; }
+ private:
+  double initial_lr_, gamma_;
+  size_t step_size_;
+};
+
+using AlgorithmParams = std::variant<SGDParams, AdamParams, StochasticReconfigurationParams, AdaGradParams>;
+
+struct OptimizerParams {                       // optimizer_params.h:348-473
+  struct BaseParams {                          // :365-425
+    size_t max_iterations;
+    double energy_tolerance;
+    double gradient_tolerance;
+    size_t plateau_patience;
+    double learning_rate;
+    std::unique_ptr<LearningRateScheduler> lr_scheduler;
+    std::optional<double> clip_value;          // per-element magnitude clip, first-order rules only; unset / <= 0: off
+    std::optional<double> clip_norm;           // global L2 norm clip, first-order rules only; unset / <= 0: off
+    BaseParams(size_t max_iter, double energy_tol, double grad_tol, size_t patience, double learning_rate,
+               std::unique_ptr<LearningRateScheduler> scheduler = nullptr)
+        : max_iterations(max_iter), energy_tolerance(energy_tol), gradient_tolerance(grad_tol), plateau_patience(patience),
+          learning_rate(learning_rate), lr_scheduler(std::move(scheduler)) {}
+    BaseParams(const BaseParams &o)
+        : max_iterations(o.max_iterations), energy_tolerance(o.energy_tolerance), gradient_tolerance(o.gradient_tolerance),
+          plateau_patience(o.plateau_patience), learning_rate(o.learning_rate),
+          lr_scheduler(o.lr_scheduler ? o.lr_scheduler->Clone() : nullptr), clip_value(o.clip_value), clip_norm(o.clip_norm) {}
+    BaseParams &operator=(const BaseParams &o) {
+      if (this != &o) { BaseParams t(o); *this = std::move(t); }
+      return *this;
+    }
+    BaseParams(BaseParams &&) = default;
+    BaseParams &operator=(BaseParams &&) = default;
+  };
+  BaseParams base_params;
+  AlgorithmParams algorithm_params;
+  OptimizerParams(const BaseParams &base, const AlgorithmParams &algo) : base_params(base), algorithm_params(algo) {}
+  template <typename T> const T &GetAlgorithmParams() const { return std::get<T>(algorithm_params); }
+  template <typename T> bool IsAlgorithm() const { return std::holds_alternative<T>(algorithm_params); }
+  bool IsFirstOrder() const { return IsAlgorithm<SGDParams>() || IsAlgorithm<AdaGradParams>() || IsAlgorithm<AdamParams>(); }
+};
+
+// what an evaluator leaves behind for the optimizer: S_O / S_EO resident in the contractor's accumulators, the two sums on the host
+template <typename TenElemT>
+struct DeviceEvaluationT {
+  TenElemT e_loc_sum = TenElemT(0.0);
+  double weight_sum = 0.0;
+  double energy_error = 0.0;
+};
+
+template <typename TenElemT>
+class Optimizer {
+ public:
+  using ContractorT = BMPSContractorT<TenElemT>;
+  // evaluates the state the contractor holds; must not upload a state (TPSWaveFunctionComponentT::ResidentState)
+  using Evaluator = std::function<DeviceEvaluationT<TenElemT>(ContractorT &)>;
+  struct OptimizationCallback {
+    std::function<void(size_t, double, double, double)> on_iteration;   // (iteration, energy, gradient norm, learning rate)
+  };
+  struct OptimizationResult {
+    std::vector<TenElemT> energy_trajectory;    // one entry per evaluation: max_iterations + 1 unless a criterion stopped the run
+    std::vector<double> gradient_norms;
+    TenElemT final_energy = TenElemT(0.0);
+    double min_energy = std::numeric_limits<double>::max();
+    size_t total_iterations = 0;                // update steps taken
+    bool converged = false;
+    size_t sr_iterations = 0;                   // of the last SR step
+    double sr_natural_grad_norm = 0.0, sr_residual_norm = 0.0;
+  };
+
+  // adopts the state the contractor holds (UploadState first).  Fermionic components need FoldFermionGradient, a host step: refused.
+  Optimizer(const OptimizerParams &params, ContractorT &contractor, const FermionDecoration *fermion = nullptr)
+      : params_(params), c_(contractor) {
+    if (fermion) throw std::invalid_argument("Optimizer: fermionic states are not supported on the device path (FoldFermionGradient is a host step)");
+    c_.OptBegin();
+  }
+  ~Optimizer() { pepsgpu_opt_end(c_.ctx()); }
+  Optimizer(const Optimizer &) = delete;
+  Optimizer &operator=(const Optimizer &) = delete;
+
+  double GetCurrentLearningRate(size_t iteration, double current_energy) const {
+    return params_.base_params.lr_scheduler ? params_.base_params.lr_scheduler->GetLearningRate(iteration, current_energy)
+                                            : params_.base_params.learning_rate;
+  }
+  // the update rules on the device buffers: theta, the rule state and the device state move, the gradient buffer is read
+  void SGDUpdate(double learning_rate, const SGDParams &p) { c_.OptStep(0, learning_rate, {p.momentum, p.nesterov ? 1.0 : 0.0, p.weight_decay}); }
+  void AdaGradUpdate(double learning_rate) {
+    const auto &p = params_.template GetAlgorithmParams<AdaGradParams>();
+    c_.OptStep(1, learning_rate, {p.epsilon, p.initial_accumulator_value});
+  }
+  void AdamUpdate(double learning_rate, const AdamParams &p) { c_.OptStep(2, learning_rate, {p.beta1, p.beta2, p.epsilon, p.weight_decay}); }
+  // natural gradient from the contractor's sample store (SRBegin / SRAppend), then theta -= lr x  (lr / |x| with normalize_update)
+  typename ContractorT::NaturalGradientInfo StochasticReconfigurationUpdate(double learning_rate, const StochasticReconfigurationParams &p) {
+    const auto &cg = p.cg_params;
+    auto info = c_.OptNaturalGradient(p.diag_shift, cg.max_iter, cg.relative_tolerance, cg.absolute_tolerance, cg.residual_recompute_interval,
+                                      cg.orthogonality_threshold);
+    double step = learning_rate;
+    if (p.normalize_update && info.direction_norm > 0.0) step /= info.direction_norm;
+    c_.OptStep(0, step, {0.0, 0.0, 0.0});
+    return info;
+  }
+  void ClipGradient() {                          // optimizer_impl.h:307-318
+    if (!params_.IsFirstOrder()) return;
+    const double cv = params_.base_params.clip_value.value_or(0.0), cn = params_.base_params.clip_norm.value_or(0.0);
+    if (cv > 0.0 || cn > 0.0) c_.OptClip(cv, cn);
+  }
+  void Update(double lr, OptimizationResult &res) {
+    if (params_.template IsAlgorithm<SGDParams>()) SGDUpdate(lr, params_.template GetAlgorithmParams<SGDParams>());
+    else if (params_.template IsAlgorithm<AdaGradParams>()) AdaGradUpdate(lr);
+    else if (params_.template IsAlgorithm<AdamParams>()) AdamUpdate(lr, params_.template GetAlgorithmParams<AdamParams>());
+    else {
+      auto info = StochasticReconfigurationUpdate(lr, params_.template GetAlgorithmParams<StochasticReconfigurationParams>());
+      res.sr_iterations = (size_t)info.iterations; res.sr_natural_grad_norm = info.direction_norm; res.sr_residual_norm = info.residual_norm;
+    }
+  }
+  bool ShouldStop(double current_energy, double previous_energy, double gradient_norm, size_t iterations_without_improvement) const {   // :1764-1793
+    const auto &b = params_.base_params;
+    return gradient_norm < b.gradient_tolerance || std::abs(current_energy - previous_energy) < b.energy_tolerance ||
+           iterations_without_improvement >= b.plateau_patience;
+  }
+  // evaluate -> finish -> clip -> [natural gradient] -> step, max_iterations times, then one closing evaluation
+  OptimizationResult IterativeOptimize(const Evaluator &evaluator, const OptimizationCallback &callback = OptimizationCallback()) {
+    OptimizationResult res;
+    double previous_energy = 0.0;
+    size_t without_improvement = 0;
+    auto evaluate = [&]() {
+      const DeviceEvaluationT<TenElemT> ev = evaluator(c_);
+      auto eg = c_.OptGradientFromAccumulators(ev.e_loc_sum, ev.weight_sum);
+      res.energy_trajectory.push_back(eg.first);
+      res.gradient_norms.push_back(eg.second);
+      res.final_energy = eg.first;
+      return eg;
+    };
+    for (size_t iter = 0; iter < params_.base_params.max_iterations; ++iter) {
+      const auto eg = evaluate();
+      const double e = std::real(eg.first);
+      if (e < res.min_energy) { res.min_energy = e; without_improvement = 0; } else ++without_improvement;
+      const double lr = GetCurrentLearningRate(iter, iter == 0 ? e : previous_energy);
+      if (callback.on_iteration) callback.on_iteration(iter, e, eg.second, lr);
+      if (iter > 0 && ShouldStop(e, previous_energy, eg.second, without_improvement)) { res.converged = true; return res; }
+      ClipGradient();
+      Update(lr, res);
+      if (params_.base_params.lr_scheduler) params_.base_params.lr_scheduler->Step();
+      previous_energy = e;
+      res.total_iterations = iter + 1;
+    }
+    const auto eg = evaluate();
+    res.min_energy = std::min(res.min_energy, std::real(eg.first));
+    return res;
+  }
+  SplitIndexTPST<TenElemT> GetState(size_t rows, size_t cols, size_t phys_dim, size_t D) const {
+    SplitIndexTPST<TenElemT> s(rows, cols, phys_dim, D);
+    c_.OptReadState(s);
+    return s;
+  }
+
+ private:
+  OptimizerParams params_;
+  ContractorT &c_;
+};
+
+// The accumulation of ExactSumEnergyEvaluator for the state the device holds: S_O / S_EO stay in HBM, the two sums come back.
+// `shape` gives the extents only.  One rank.
+template <typename ModelT, typename TenElemT>
+DeviceEvaluationT<TenElemT> ExactSumAccumulateResident(const SplitIndexTPST<TenElemT> &shape, const std::vector<std::vector<int32_t>> &all_configs,
+                                                      BMPSContractorT<TenElemT> &contractor, ModelT &model, size_t batch) {
+  const size_t rows = shape.rows(), cols = shape.cols();
+  DeviceEvaluationT<TenElemT> ev;
+  contractor.GradReset();
+  for (size_t b0 = 0; b0 < all_configs.size(); b0 += batch) {
+    const size_t nb = std::min(batch, all_configs.size() - b0);
+    Configuration cfg(nb, rows, cols);
+    for (size_t w = 0; w < nb; ++w) std::copy(all_configs[b0 + w].begin(), all_configs[b0 + w].end(), cfg.data() + w * rows * cols);
+    TPSWaveFunctionComponentT<TenElemT> comp(typename TPSWaveFunctionComponentT<TenElemT>::ResidentState(), cfg, contractor);
+    EnergyAndHolesT<TenElemT> eh = model.template CalEnergyAndHoles<true>(shape, comp, /*holes_on_device=*/true);
+    contractor.GradAccumulate(comp.amplitude, eh.energy, true);
+    for (size_t w = 0; w < nb; ++w) {
+      const double wt = AbsSquare(comp.amplitude[w]);
+      ev.weight_sum += wt;
+      ev.e_loc_sum += eh.energy[w] * wt;
+    }
+  }
+  return ev;
+}
+
+// The accumulation of MCEnergyGradEvaluator (mc_energy_grad_evaluator.h:245-278) over a given set of samples with weight 1, for the
+// state the device holds: S_O / S_EO in the accumulators and the O* samples in the SR store (what the SR step solves with), both in HBM.
+template <typename ModelT, typename TenElemT>
+DeviceEvaluationT<TenElemT> SampleSetAccumulateResident(const SplitIndexTPST<TenElemT> &shape, const Configuration &samples,
+                                                       BMPSContractorT<TenElemT> &contractor, ModelT &model) {
+  DeviceEvaluationT<TenElemT> ev;
+  contractor.GradReset();
+  contractor.SRBegin(samples.walkers());
+  TPSWaveFunctionComponentT<TenElemT> comp(typename TPSWaveFunctionComponentT<TenElemT>::ResidentState(), samples, contractor);
+  EnergyAndHolesT<TenElemT> eh = model.template CalEnergyAndHoles<true>(shape, comp, /*holes_on_device=*/true);
+  contractor.GradAccumulate(comp.amplitude, eh.energy, false);
+  contractor.SRAppend(comp.amplitude);
+  for (size_t w = 0; w < samples.walkers(); ++w) { ev.weight_sum += 1.0; ev.e_loc_sum += eh.energy[w]; }
+  return ev;
 }
 
 }  // namespace qlpeps_gpu

@@ -18,7 +18,9 @@ SYMBOLS = ["pepshost_last_error", "pepshost_mc_sweeps", "pepshost_energy_and_hol
            "pepshost_mc_engine_warmup", "pepshost_mc_engine_warmup_dist", "pepshost_suwa_todo_chain", "pepshost_load_configuration2", "pepshost_configuration_from_text",
            "pepshost_fermion_measure_energy", "pepshost_fermion_energy_prm", "pepshost_fermion_measure_energy_prm", "pepshost_measure_c128", "pepshost_exact_sum_measure_partial_c128", "pepshost_fermion_energy_c128",
            "pepshost_fermion_exact_sum_partial_c128", "pepshost_fermion_mc_sweeps_c128", "pepshost_fermion_measure_energy_c128",
-           "pepshost_fermion_mc_sweeps_updater", "pepshost_tnn3_table"]
+           "pepshost_fermion_mc_sweeps_updater", "pepshost_tnn3_table",
+           "pepshost_optimize_exact_sum", "pepshost_optimize_exact_sum_c128", "pepshost_lr_schedule",
+           "pepshost_sr_step_samples", "pepshost_sr_step_samples_c128"]
 
 _lib = None
 _C128 = 3                                   # PEPSGPU_C128 (include/pepsgpu.h)
@@ -201,6 +203,80 @@ def exact_sum_measure_partial(flat, all_configs, chi, model="xxz", params=(1.0, 
         out[key] = seg.view(np.complex128) if cplx else seg
         off += z * int(ln)
     return out, float(vals[0])
+
+
+RULE_ID = {"sgd": 0, "adagrad": 1, "adam": 2}   # rule_params: sgd (momentum, nesterov, weight_decay); adagrad (epsilon, initial_accumulator_value);
+# adam (beta1, beta2, epsilon, weight_decay)
+LR_SCHEDULE_ID = {"constant": 0, "exponential": 1, "step": 2}   # args: (lr,); (initial_lr, decay_rate, decay_steps); (initial_lr, step_size, gamma)
+
+
+def optimize_exact_sum(flat, all_configs, chi, model, params, rule, lr, rule_params, iterations, clip_value=0.0, clip_norm=0.0, dtype=1,
+                       batch=64, return_grad_norms=False):
+    """Optimizer::IterativeOptimize of the C++ host layer with the exact-summation evaluator, the whole loop inside one C++ call: the
+    state is uploaded once, every iteration evaluates, finishes the gradient, clips and steps on the device.  Returns
+    (energies[iterations + 1], final flat state [, gradient norms[iterations + 1]]).  A complex `flat` runs the QLTEN_Complex
+    instantiation (`dtype` is ignored)."""
+    cplx = np.iscomplexobj(flat)
+    flat = np.ascontiguousarray(flat, dtype=np.complex128 if cplx else np.float64)
+    rows, cols, d, D = _dims(flat)
+    cfg = np.ascontiguousarray(all_configs, dtype=np.int32)
+    p = np.array(list(params) + [0.0] * 8, dtype=np.float64)
+    rp = np.ascontiguousarray([float(x) for x in rule_params], dtype=np.float64)
+    rid = RULE_ID[rule] if isinstance(rule, str) else int(rule)
+    energies = np.zeros(iterations + 1, dtype=flat.dtype)
+    norms = np.zeros(iterations + 1)
+    state = np.zeros_like(flat)
+    l = lib()
+    tail = [C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_double, C.POINTER(C.c_double), C.c_int, C.c_int,
+            C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    l.pepshost_optimize_exact_sum.argtypes = [C.c_int] * 6 + [C.POINTER(C.c_double)] + tail
+    l.pepshost_optimize_exact_sum_c128.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_double)] + tail
+    rest = (_p(cfg, C.c_int32), cfg.shape[0], MODEL_ID[model], _p(p, C.c_double), rid, float(lr), _p(rp, C.c_double), rp.size, int(iterations),
+            float(clip_value), float(clip_norm), int(min(batch, cfg.shape[0])))
+    if cplx:
+        _ck(l.pepshost_optimize_exact_sum_c128(rows, cols, D, d, chi, _cp(flat), *rest, _cp(energies), _p(norms, C.c_double), _cp(state)))
+    else:
+        _ck(l.pepshost_optimize_exact_sum(rows, cols, D, d, chi, dtype, _p(flat, C.c_double), *rest, _p(energies, C.c_double),
+                                          _p(norms, C.c_double), _p(state, C.c_double)))
+    return (energies, state, norms) if return_grad_norms else (energies, state)
+
+
+def sr_step_samples(flat, configs, chi, model, params, lr, diag_shift=0.001, cg_max_iter=100, cg_relative_tolerance=1e-4,
+                    normalize_update=False, dtype=1):
+    """One stochastic-reconfiguration iteration of the C++ Optimizer on a given sample set (weight 1 per sample): gradient from the
+    resident accumulators, natural gradient solved on the device, theta -= lr x (lr / |x| with normalize_update).  Returns (state after
+    the step, dict with the energies before / after, CG iterations, |x| and the CG residual norm).  Models: "xxz", "tfim"."""
+    cplx = np.iscomplexobj(flat)
+    flat = np.ascontiguousarray(flat, dtype=np.complex128 if cplx else np.float64)
+    rows, cols, d, D = _dims(flat)
+    cfg = np.ascontiguousarray(configs, dtype=np.int32)
+    p = np.array(list(params) + [0.0] * 8, dtype=np.float64)
+    state, info = np.zeros_like(flat), np.zeros(5)
+    l = lib()
+    tail = [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_int, C.c_double,
+            C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    l.pepshost_sr_step_samples.argtypes = [C.c_int] * 6 + tail
+    l.pepshost_sr_step_samples_c128.argtypes = [C.c_int] * 5 + tail
+    rest = (cfg.shape[0], _p(cfg, C.c_int32), MODEL_ID[model], _p(p, C.c_double), float(lr), float(diag_shift), int(cg_max_iter),
+            float(cg_relative_tolerance), int(bool(normalize_update)), _cp(state), _p(info, C.c_double))
+    if cplx:
+        _ck(l.pepshost_sr_step_samples_c128(rows, cols, D, d, chi, _cp(flat), *rest))
+    else:
+        _ck(l.pepshost_sr_step_samples(rows, cols, D, d, chi, dtype, _cp(flat), *rest))
+    return state, {"energy_before": info[0], "energy_after": info[1], "cg_iterations": int(info[2]), "direction_norm": info[3],
+                   "cg_residual_norm": info[4]}
+
+
+def lr_schedule(kind, args, iteration):
+    """LearningRateScheduler::GetLearningRate of the host layer: kind "constant" (lr,), "exponential" (initial_lr, decay_rate,
+    decay_steps), "step" (initial_lr, step_size, gamma)"""
+    a = np.ascontiguousarray([float(x) for x in args], dtype=np.float64)
+    out = C.c_double(0.0)
+    l = lib()
+    l.pepshost_lr_schedule.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_int, C.c_long, C.POINTER(C.c_double)]
+    _ck(l.pepshost_lr_schedule(LR_SCHEDULE_ID[kind] if isinstance(kind, str) else int(kind), _p(a, C.c_double), a.size, int(iteration),
+                               C.byref(out)))
+    return out.value
 
 
 def exact_sum_finish(packed, shape):

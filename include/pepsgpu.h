@@ -475,7 +475,26 @@ int pepsgpu_sr_copy_samples(pepsgpu_ctx *ctx, void *dst_samples_dev, int32_t *ds
  *                          weight_decay).  ElementWiseInv(eps) = 1 / (x + eps) in both.
  *   pepsgpu_opt_scale_state theta *= factor, device state = T(theta): the `*= scale_factor_on_site` of NormalizeStateOrder1
  *                          (monte_carlo_engine.h:206-240).
- *   pepsgpu_opt_read_state theta to the host. */
+ *   pepsgpu_opt_read_state theta to the host.
+ *
+ * Fermionic states.  A fermionic state lives on the device as 4 d decorated components per site, T''[s + d var] = sigma_var * T[s]
+ * =: E T (peps_amd/fermion.py; sigma_0 = 1, sigma_1 = (-1)^u, sigma_2 = (-1)^base, sigma_3 = (-1)^(base + l), base = u n_s + u + dn r +
+ * l + l u over the bond parities l, dn, r, u of the element and the parity n_s of the stored state; an element is a parameter iff
+ * l + dn + r + u + n_s is even).  pepsgpu_fermion_decoration_set tells the context so: d stored states with parities nf[d] and the
+ * bond parities bond_parity [rows][cols][4][D] (legs L, D, R, U; entries past a leg's true dimension are ignored).  d = 0 clears the
+ * decoration.  PEPSGPU_EINVAL: phys_dim != 4 d, a parity outside {0, 1}, or optimizer buffers exist (pepsgpu_opt_end first).
+ * With a decoration set every optimizer vector stays in the extended layout and in the range of E, and the calls above become
+ *   opt_begin               additionally checks theta == Pi(theta) / 4 element by element (Pi = E mask E^T), exact for a decorated
+ *                           state; otherwise PEPSGPU_EINVAL names the first offending site and no buffer is kept.
+ *   opt_gradient_from_accumulators   g <- Pi (S_EO - conj(E) S_O) / W, i.e. E of the folded gradient (fermion.fold_gradient); grad_norm_out
+ *                           is the norm over the STORED parameters, 1/2 of the extended one.
+ *   opt_set_gradient        takes the derivative with respect to the extended components (padded extended layout) and applies Pi;
+ *   opt_get_gradient / opt_read_state return E g / E theta in the same layout: components 0 .. d - 1 (variant 0) are the stored arrays.
+ *   opt_clip                compares and reports the stored norm; the element-wise clip and the scale factor are unchanged.
+ *   opt_natural_gradient    solves (E^T S_ext E + diag_shift) x = g in the stored parameters: Pi is applied to every S v and the dot
+ *                           products are scaled to the stored ones; residual_norm and direction_norm_out are stored norms.
+ *   opt_step / opt_scale_state   unchanged: element-wise, so a step on (E theta, Pi g) is bit for bit E of the step on (theta, E^T g).
+ * pepsgpu_sr_cg_solve (host vectors) ignores the decoration. */
 int pepsgpu_opt_begin(pepsgpu_ctx *ctx);
 int pepsgpu_opt_end(pepsgpu_ctx *ctx);
 int pepsgpu_opt_gradient_from_accumulators(pepsgpu_ctx *ctx, const double *e_loc_sum, double weight_sum, double *energy_out,
@@ -489,6 +508,7 @@ int pepsgpu_opt_natural_gradient(pepsgpu_ctx *ctx, double diag_shift, int max_it
 int pepsgpu_opt_step(pepsgpu_ctx *ctx, int rule, double lr, const double *params, int n_params);
 int pepsgpu_opt_scale_state(pepsgpu_ctx *ctx, double factor);
 int pepsgpu_opt_read_state(pepsgpu_ctx *ctx, double *host);
+int pepsgpu_fermion_decoration_set(pepsgpu_ctx *ctx, int d, const int32_t *nf, const uint8_t *bond_parity);
 
 /* TPSWaveFunctionComponent::UpdateLocal (wave_function_component.h:345-378) for the walkers with
  * accept_mask[w] != 0 (NULL = all): config(site_k) = new_states[w][k], tn.UpdateSiteTensor,

@@ -43,7 +43,7 @@ SYMBOLS = [
     "pepsgpu_sr_cg_solve", "pepsgpu_sr_gram", "pepsgpu_sr_weighted_sum", "pepsgpu_sr_copy_samples",
     "pepsgpu_opt_begin", "pepsgpu_opt_end", "pepsgpu_opt_gradient_from_accumulators", "pepsgpu_opt_set_gradient",
     "pepsgpu_opt_get_gradient", "pepsgpu_opt_clip", "pepsgpu_opt_natural_gradient", "pepsgpu_opt_step", "pepsgpu_opt_scale_state",
-    "pepsgpu_opt_read_state",
+    "pepsgpu_opt_read_state", "pepsgpu_fermion_decoration_set",
     "pepsgpu_update_local", "pepsgpu_erase_envs_after_update", "pepsgpu_evaluate_amplitude",
     "pepsgpu_walker_flags", "pepsgpu_sync", "pepsgpu_stats", "pepsgpu_profile_enable", "pepsgpu_profile_read",
     "pepsgpu_diag_tgemm", "pepsgpu_diag_tgemm_desc", "pepsgpu_diag_tgemm_route", "pepsgpu_diag_tgemm_chain", "pepsgpu_diag_tgemm_chain3", "pepsgpu_diag_chol", "pepsgpu_diag_chol_adaptive", "pepsgpu_diag_chol_pivot", "pepsgpu_diag_rows_qr", "pepsgpu_diag_suwa_todo", "pepsgpu_diag_dot4", "pepsgpu_diag_gram_chol", "pepsgpu_diag_gram_chol_wave", "pepsgpu_diag_gram_cols", "pepsgpu_diag_gram_rows", "pepsgpu_diag_mgemm_dense", "pepsgpu_diag_jacobi", "pepsgpu_diag_trunc_rows", "pepsgpu_version",
@@ -163,6 +163,8 @@ def load_library(path=LIB_PATH):
         lib.pepsgpu_opt_step.argtypes = [vp, C.c_int, C.c_double, dp, C.c_int]
         lib.pepsgpu_opt_scale_state.argtypes = [vp, C.c_double]
         lib.pepsgpu_opt_read_state.argtypes = [vp, dp]
+    if hasattr(lib, "pepsgpu_fermion_decoration_set"):
+        lib.pepsgpu_fermion_decoration_set.argtypes = [vp, C.c_int, ip, C.POINTER(C.c_uint8)]
     lib.pepsgpu_update_local.argtypes = [vp, C.c_int, ip, ip, C.POINTER(C.c_uint8)]
     lib.pepsgpu_erase_envs_after_update.argtypes = [vp, C.c_int, C.c_int]
     lib.pepsgpu_evaluate_amplitude.argtypes = [vp, dp]
@@ -639,6 +641,26 @@ class Context:
         out = np.zeros(self._state_shape(), dtype=self._ot)
         self._ck(self._l.pepsgpu_opt_read_state(self._h, _dp(out)))
         return out
+
+    def fermion_decoration_set(self, state):
+        """Tells the optimizer calls that the context holds the decorated components of `state` (a fermion.FermionState; the
+        context's phys_dim is 4 * state.d): theta, g and the rule state stay in the extended layout and in the range of the
+        decoration, norms are those of the stored parameters.  None clears the decoration.  Refused while optimizer buffers exist."""
+        if state is None:
+            self._ck(self._l.pepsgpu_fermion_decoration_set(self._h, 0, None, None))
+            return
+        nf = np.ascontiguousarray(state.nf, dtype=np.int32)
+        par = np.zeros((self.rows, self.cols, 4, self.D), dtype=np.uint8)
+        if (state.rows, state.cols) != (self.rows, self.cols) or state.D > self.D:
+            raise ValueError("the state does not fit the context")
+        for r in range(self.rows):
+            for c in range(self.cols):
+                for leg in range(4):
+                    p = np.asarray(state.par[r][c][leg])
+                    if np.any((p < 0) | (p > 255)):
+                        raise ValueError("a bond parity outside {0, 1}")
+                    par[r, c, leg, :len(p)] = p
+        self._ck(self._l.pepsgpu_fermion_decoration_set(self._h, int(state.d), _ip(nf), par.ctypes.data_as(C.POINTER(C.c_uint8))))
 
     def grad_reset(self):
         self._ck(self._l.pepsgpu_grad_reset(self._h))

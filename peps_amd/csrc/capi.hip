@@ -470,6 +470,9 @@ int pepsgpu_opt_scale_state(pepsgpu_ctx *ctx, double factor) { CTX_CALL(ctx->eng
 int pepsgpu_opt_read_state(pepsgpu_ctx *ctx, double *host) {
   CTX_CALL(PG_REQUIRE(host != nullptr, 1, "null output"); ctx->eng->opt_read_state(host));
 }
+int pepsgpu_fermion_decoration_set(pepsgpu_ctx *ctx, int d, const int32_t *nf, const uint8_t *bond_parity) {
+  CTX_CALL(ctx->eng->fermion_decoration_set(d, nf, bond_parity));
+}
 int pepsgpu_update_local(pepsgpu_ctx *ctx, int nsites, const int32_t *sites, const int32_t *ns, const uint8_t *mask) {
   CTX_CALL(ctx->eng->update_local(nsites, sites, ns, mask));
 }

@@ -129,6 +129,7 @@ struct EngineBase {
   virtual void opt_step(int rule, double lr, const double *params, int n_params) = 0;
   virtual void opt_scale_state(double factor) = 0;
   virtual void opt_read_state(double *host) = 0;
+  virtual void fermion_decoration_set(int d, const int32_t *nf, const uint8_t *bond_parity) = 0;
   // one row / column of exchange moves (pair_table nullable) and of full-space moves (Suwa-Todo over phys_dim^2 states); engine_sweep.h
   virtual void sweep_slice_exchange(int orient, int slice, int n_uniform, const double *uniforms, const int32_t *pair_table,
                                     double *amp_inout, int32_t *consumed_out, int32_t *accepted_out, int32_t *slice_states_out) = 0;
@@ -856,6 +857,10 @@ class Engine : public EngineBase {
   void opt_step(int rule, double lr, const double *params, int n_params) override;
   void opt_scale_state(double factor) override;
   void opt_read_state(double *host) override;
+  void fermion_decoration_set(int d, const int32_t *nf, const uint8_t *bond_parity) override;
+  void opt_fermion_project(double *x);     // Pi in place over one optimizer vector (a decoration is set)
+  std::vector<uint8_t> fermion_sign_table() const;
+  dim3 opt_fermion_grid() const { return dim3((unsigned)((slot_ + 255) / 256), (unsigned)(Ly_ * Lx_ * fd_d_)); }
   void opt_release();
   void opt_read(const double *dev, double *host);
   double opt_norm_sq(const double *x);
@@ -1621,7 +1626,12 @@ class Engine : public EngineBase {
   // optimizer buffers (engine_opt.h), layout of so_ / seo_: theta, g, velocity, m1 of the element type, m2 and acc real
   double *opt_theta_ = nullptr, *opt_g_ = nullptr, *opt_vel_ = nullptr, *opt_m1_ = nullptr, *opt_m2_ = nullptr, *opt_acc_ = nullptr;
   double *opt_part_ = nullptr;             // partial sums of the norm, then its result
-  int *opt_ne_ = nullptr;                  // live elements of a slot per site
+  int *opt_ne_ = nullptr;                  // live elements of a slot per site, then two words of the check at opt_begin
+  // fermionic decoration (pepsgpu_fermion_decoration_set): d stored states, their parities, the bond parities [site][4][D]
+  int fd_d_ = 0;
+  std::vector<int> fd_nf_;
+  std::vector<uint8_t> fd_par_;
+  uint8_t *opt_sign_ = nullptr;            // [site][stored state][slot]: bits 0-3 sign bits of the four variants, bit 4 allowed
   long opt_t_ = 0;                         // Adam timestep
   bool opt_acc_ready_ = false;             // acc holds initial_accumulator_value (set by the first AdaGrad step after opt_begin)
   static constexpr int kOptDotBlocks = 512;

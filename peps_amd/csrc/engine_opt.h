@@ -10,6 +10,12 @@
 //   step      SGD (:949-990), AdaGrad (:1252-1307), Adam (:1327-1396): one fused pass that also writes sitps_ = T(theta)
 //   scale     theta *= f, sitps_ = T(theta)                              NormalizeStateOrder1, monte_carlo_engine.h:206-240
 // ElementWiseInv(eps) is taken as 1 / (x + eps) in both AdaGrad and Adam ("Unpinned").
+//
+// Fermionic states (pepsgpu_fermion_decoration_set): the device holds 4 d decorated components per site, T''[s + d var] =
+// sigma_var * T[s] =: E T.  Every optimizer vector stays in that extended layout and in the range of E, so the element-wise rule
+// kernels above run unchanged (negating theta, g, velocity and m1 negates their results exactly; m2 and acc see |g|^2): a step on
+// (E theta, Pi g_ext) is bit for bit E of the step on (theta, E^T g_ext), Pi = E mask E^T.  New for fermions: the sign table, Pi
+// (alone and fused into the finish), the check at begin, the stored norm = 1/2 extended norm (E^T E = 4 mask), the SR hook.
 #pragma once
 #include "engine_sr.h"
 
@@ -105,6 +111,87 @@ __global__ __launch_bounds__(256) void opt_fill_kernel(double *__restrict__ x, d
   x[k] = v;
 }
 
+// ---- fermionic decoration: one byte per (site, stored state, element), bits 0-3 = sign bits of the variants, bit 4 = allowed ----
+// Grid (ceil(slot / 256), sites * d): one thread per stored element, which owns its four decorated copies.
+#define OPT_FERMION_PROLOGUE                                              \
+  const int q = blockIdx.y;                                               \
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;             \
+  const int site = q / d, s = q - site * d;                               \
+  if (e >= ne[site]) return;                                              \
+  const unsigned b = sign[(long)q * slot + e];                            \
+  const long k0 = ((long)site * 4 * d + s) * slot + e, dk = (long)d * slot;
+
+// t = allowed * sum_var sigma_var x_var (var = 0, 1, 2, 3 in this order), x_var <- sigma_var t
+template <int Z>
+__device__ __forceinline__ void opt_fermion_project_elem(double (*x)[Z], unsigned b) {
+#pragma clang fp contract(off)
+  for (int z = 0; z < Z; ++z) {
+    double t = 0.0;
+    for (int var = 0; var < 4; ++var) t += ((b >> var) & 1u) ? -x[var][z] : x[var][z];
+    if (!(b & 16u)) t = 0.0;
+    for (int var = 0; var < 4; ++var) x[var][z] = ((b >> var) & 1u) ? -t : t;
+  }
+}
+
+// x <- Pi x in place
+template <int Z>
+__global__ __launch_bounds__(256) void opt_fermion_project_kernel(double *__restrict__ x, const uint8_t *__restrict__ sign,
+                                                                  const int *__restrict__ ne, long slot, int d) {
+#pragma clang fp contract(off)
+  OPT_FERMION_PROLOGUE
+  double v[4][Z];
+  for (int var = 0; var < 4; ++var)
+    for (int z = 0; z < Z; ++z) v[var][z] = x[Z * (k0 + var * dk) + z];
+  opt_fermion_project_elem<Z>(v, b);
+  for (int var = 0; var < 4; ++var)
+    for (int z = 0; z < Z; ++z) x[Z * (k0 + var * dk) + z] = v[var][z];
+}
+
+// g <- Pi (S_EO - conj(E) S_O) / W: the finish of the four variants and the projection in one pass (8 reads, 4 writes)
+template <int Z>
+__global__ __launch_bounds__(256) void opt_finish_fermion_kernel(const double *__restrict__ so, const double *__restrict__ seo,
+                                                                 double e_re, double ec_im, double w, double *__restrict__ g,
+                                                                 const uint8_t *__restrict__ sign, const int *__restrict__ ne,
+                                                                 long slot, int d) {
+#pragma clang fp contract(off)
+  OPT_FERMION_PROLOGUE
+  double v[4][Z];
+  for (int var = 0; var < 4; ++var) {
+    const long k = k0 + var * dk;
+    if constexpr (Z == 1) {
+      v[var][0] = (seo[k] - e_re * so[k]) / w;
+    } else {
+      const double sr = so[2 * k], si = so[2 * k + 1];
+      v[var][0] = (seo[2 * k] - (e_re * sr - ec_im * si)) / w;
+      v[var][1] = (seo[2 * k + 1] - (e_re * si + ec_im * sr)) / w;
+    }
+  }
+  opt_fermion_project_elem<Z>(v, b);
+  for (int var = 0; var < 4; ++var)
+    for (int z = 0; z < Z; ++z) g[Z * (k0 + var * dk) + z] = v[var][z];
+}
+
+// the check at begin: out[0] += number of stored elements with theta != Pi(theta) / 4 in any copy, out[1] = min of their sites.
+// For a decorated state the comparison is exact: the copies differ by sign flips only and forbidden entries are exactly zero.
+template <int Z>
+__global__ __launch_bounds__(256) void opt_fermion_check_kernel(const double *__restrict__ theta, const uint8_t *__restrict__ sign,
+                                                                const int *__restrict__ ne, long slot, int d, int *__restrict__ out) {
+#pragma clang fp contract(off)
+  OPT_FERMION_PROLOGUE
+  double v[4][Z], p[4][Z];
+  for (int var = 0; var < 4; ++var)
+    for (int z = 0; z < Z; ++z) p[var][z] = v[var][z] = theta[Z * (k0 + var * dk) + z];
+  opt_fermion_project_elem<Z>(p, b);
+  bool bad = false;
+  for (int var = 0; var < 4; ++var)
+    for (int z = 0; z < Z; ++z) bad = bad || !(v[var][z] == 0.25 * p[var][z]);
+  if (bad) {
+    atomicAdd(out, 1);
+    atomicMin(out + 1, site);
+  }
+}
+#undef OPT_FERMION_PROLOGUE
+
 // One fused pass per rule: reads theta, g and the rule's state, writes theta, the state and sitps_ = T(theta).
 // s1 = velocity (SGD) / m1 (Adam), element type; s2 = acc (AdaGrad) / m2 (Adam), real.
 // Contraction into fused multiply-adds is off: the result is the separately rounded arithmetic of the host restatement.
@@ -158,8 +245,10 @@ template <typename T>
 void Engine<T>::opt_release() {
   for (double *p : {opt_theta_, opt_g_, opt_vel_, opt_m1_, opt_m2_, opt_acc_, opt_part_}) arena_.free(p);
   arena_.free(opt_ne_);
+  arena_.free(opt_sign_);
   opt_theta_ = opt_g_ = opt_vel_ = opt_m1_ = opt_m2_ = opt_acc_ = opt_part_ = nullptr;
   opt_ne_ = nullptr;
+  opt_sign_ = nullptr;
   opt_t_ = 0;
   opt_acc_ready_ = false;
 }
@@ -180,20 +269,39 @@ void Engine<T>::opt_begin() {
   opt_m2_ = (double *)arena_.alloc(sizeof(double) * n);
   opt_acc_ = (double *)arena_.alloc(sizeof(double) * n);
   opt_part_ = (double *)arena_.alloc(sizeof(double) * (kOptDotBlocks + 8));
-  opt_ne_ = (int *)arena_.alloc(sizeof(int) * sites);
-  std::vector<int> ne(sites);
+  opt_ne_ = (int *)arena_.alloc(sizeof(int) * (sites + 2));
+  std::vector<int> ne(sites + 2);
+  ne[sites] = 0; ne[sites + 1] = sites;          // the check's count and first offending site
   for (int r = 0; r < Ly_; ++r)
     for (int c = 0; c < Lx_; ++c) {
       int dd[4];
       site_dims(r, c, dd);
       ne[r * Lx_ + c] = dd[0] * dd[1] * dd[2] * dd[3];
     }
-  PG_CHECK_HIP(hipMemcpyAsync(opt_ne_, ne.data(), sizeof(int) * sites, hipMemcpyHostToDevice, stream_));
+  PG_CHECK_HIP(hipMemcpyAsync(opt_ne_, ne.data(), sizeof(int) * (sites + 2), hipMemcpyHostToDevice, stream_));
+  std::vector<uint8_t> sign;                     // (a host temporary too)
+  if (fd_d_ > 0) {
+    sign = fermion_sign_table();
+    opt_sign_ = (uint8_t *)arena_.alloc(sign.size());
+    PG_CHECK_HIP(hipMemcpyAsync(opt_sign_, sign.data(), sign.size(), hipMemcpyHostToDevice, stream_));
+  }
   for (double *p : {opt_theta_, opt_g_, opt_vel_, opt_m1_}) PG_CHECK_HIP(hipMemsetAsync(p, 0, sizeof(double) * n * kOut, stream_));
   for (double *p : {opt_m2_, opt_acc_}) PG_CHECK_HIP(hipMemsetAsync(p, 0, sizeof(double) * n, stream_));
   hipLaunchKernelGGL(opt_begin_kernel<T>, opt_grid(), dim3(256), 0, stream_, (const T *)sitps_, opt_theta_, (const int *)opt_ne_,
                      slot_, dp_);
   PG_CHECK_HIP(hipGetLastError());
+  if (fd_d_ > 0) {
+    hipLaunchKernelGGL(opt_fermion_check_kernel<kOut>, opt_fermion_grid(), dim3(256), 0, stream_, (const double *)opt_theta_,
+                       (const uint8_t *)opt_sign_, (const int *)opt_ne_, slot_, fd_d_, opt_ne_ + sites);
+    PG_CHECK_HIP(hipGetLastError());
+    int bad[2] = {0, 0};
+    PG_CHECK_HIP(hipMemcpyAsync(bad, opt_ne_ + sites, sizeof(bad), hipMemcpyDeviceToHost, stream_));
+    PG_CHECK_HIP(hipStreamSynchronize(stream_));
+    if (bad[0] != 0)
+      throw Error(1, "opt_begin: the device state is not the decoration of a parity-even state: " + std::to_string(bad[0]) +
+                         " stored elements differ from Pi(theta) / 4, the first at site (" + std::to_string(bad[1] / Lx_) + ", " +
+                         std::to_string(bad[1] % Lx_) + ")");
+  }
   PG_CHECK_HIP(hipStreamSynchronize(stream_));   // (ne is a host temporary)
   } catch (...) {
     opt_release();
@@ -218,7 +326,62 @@ double Engine<T>::opt_norm_sq(const double *x) {
   double out = 0.0;
   PG_CHECK_HIP(hipMemcpyAsync(&out, opt_part_ + kOptDotBlocks, sizeof(double), hipMemcpyDeviceToHost, stream_));
   PG_CHECK_HIP(hipStreamSynchronize(stream_));
-  return out;
+  return fd_d_ > 0 ? 0.25 * out : out;      // a vector in the range of E: stored norm^2 = extended norm^2 / 4 (E^T E = 4 mask)
+}
+
+template <typename T>
+void Engine<T>::opt_fermion_project(double *x) {
+  hipLaunchKernelGGL(opt_fermion_project_kernel<kOut>, opt_fermion_grid(), dim3(256), 0, stream_, x, (const uint8_t *)opt_sign_,
+                     (const int *)opt_ne_, slot_, fd_d_);
+  PG_CHECK_HIP(hipGetLastError());
+}
+
+// the sign table of opt_sign_ from nf and the bond parities, in the compact [L][D][R][U] element order of layout_maps()
+template <typename T>
+std::vector<uint8_t> Engine<T>::fermion_sign_table() const {
+  const int sites = Ly_ * Lx_, d = fd_d_;
+  std::vector<uint8_t> tab((size_t)sites * d * slot_, 0);
+  for (int r = 0; r < Ly_; ++r)
+    for (int c = 0; c < Lx_; ++c) {
+      int dd[4];
+      site_dims(r, c, dd);
+      const uint8_t *par = fd_par_.data() + (size_t)(r * Lx_ + c) * 4 * D_;
+      for (int s = 0; s < d; ++s) {
+        uint8_t *row = tab.data() + ((size_t)(r * Lx_ + c) * d + s) * slot_;
+        const int n = fd_nf_[s] & 1;
+        size_t o = 0;
+        for (int a = 0; a < dd[0]; ++a)
+          for (int b = 0; b < dd[1]; ++b)
+            for (int cc = 0; cc < dd[2]; ++cc)
+              for (int e = 0; e < dd[3]; ++e, ++o) {
+                const int l = par[a], dn = par[D_ + b], rr = par[2 * D_ + cc], u = par[3 * D_ + e];
+                const int base = (u * n + u + dn * rr + l + l * u) & 1;
+                const int allowed = ((l + dn + rr + u + n) & 1) == 0;
+                row[o] = (uint8_t)((u << 1) | (base << 2) | (((base + l) & 1) << 3) | (allowed << 4));
+              }
+      }
+    }
+  return tab;
+}
+
+template <typename T>
+void Engine<T>::fermion_decoration_set(int d, const int32_t *nf, const uint8_t *bond_parity) {
+  PG_REQUIRE(opt_theta_ == nullptr, 1, "fermion_decoration_set: optimizer buffers exist (pepsgpu_opt_end first)");
+  PG_REQUIRE(d >= 0, 1, "fermion_decoration_set: negative d");
+  if (d == 0) { fd_d_ = 0; fd_nf_.clear(); fd_par_.clear(); return; }
+  PG_REQUIRE(nf != nullptr && bond_parity != nullptr, 1, "fermion_decoration_set: null argument");
+  PG_REQUIRE(dp_ == 4 * d, 1, "fermion_decoration_set: the context's phys_dim must be 4 * d (the decorated components)");
+  for (int r = 0; r < Ly_; ++r)
+    for (int c = 0; c < Lx_; ++c) {
+      int dd[4];
+      site_dims(r, c, dd);
+      for (int leg = 0; leg < 4; ++leg)
+        for (int i = 0; i < dd[leg]; ++i)
+          PG_REQUIRE(bond_parity[((size_t)(r * Lx_ + c) * 4 + leg) * D_ + i] <= 1, 1, "fermion_decoration_set: a bond parity outside {0, 1}");
+    }
+  fd_d_ = d;
+  fd_nf_.assign(nf, nf + d);
+  fd_par_.assign(bond_parity, bond_parity + (size_t)Ly_ * Lx_ * 4 * D_);
 }
 
 template <typename T>
@@ -228,8 +391,12 @@ void Engine<T>::opt_gradient_from_accumulators(const double *e_loc_sum, double w
   PG_REQUIRE(std::isfinite(weight_sum) && weight_sum > 0.0, 1, "opt_gradient_from_accumulators: weight_sum must be positive");
   for (int z = 0; z < kOut; ++z) PG_REQUIRE(std::isfinite(e_loc_sum[z]), 1, "opt_gradient_from_accumulators: non-finite e_loc_sum");
   const double e_re = e_loc_sum[0] / weight_sum, e_im = kCplx ? e_loc_sum[1] / weight_sum : 0.0;
-  hipLaunchKernelGGL(opt_finish_kernel<kOut>, opt_grid(), dim3(256), 0, stream_, (const double *)so_, (const double *)seo_, e_re, -e_im,
-                     weight_sum, opt_g_, (const int *)opt_ne_, slot_, dp_);
+  if (fd_d_ > 0)
+    hipLaunchKernelGGL(opt_finish_fermion_kernel<kOut>, opt_fermion_grid(), dim3(256), 0, stream_, (const double *)so_,
+                       (const double *)seo_, e_re, -e_im, weight_sum, opt_g_, (const uint8_t *)opt_sign_, (const int *)opt_ne_, slot_, fd_d_);
+  else
+    hipLaunchKernelGGL(opt_finish_kernel<kOut>, opt_grid(), dim3(256), 0, stream_, (const double *)so_, (const double *)seo_, e_re, -e_im,
+                       weight_sum, opt_g_, (const int *)opt_ne_, slot_, dp_);
   PG_CHECK_HIP(hipGetLastError());
   const double nsq = opt_norm_sq(opt_g_);
   if (energy_out) { energy_out[0] = e_re; if (kCplx) energy_out[1] = e_im; }
@@ -243,6 +410,7 @@ void Engine<T>::opt_set_gradient(const double *host) {
   std::vector<double> h(n);
   sr_convert(host, h.data(), true);
   PG_CHECK_HIP(hipMemcpyAsync(opt_g_, h.data(), n * sizeof(double), hipMemcpyHostToDevice, stream_));
+  if (fd_d_ > 0) opt_fermion_project(opt_g_);      // the derivative with respect to the extended components -> Pi g
   PG_CHECK_HIP(hipStreamSynchronize(stream_));
 }
 

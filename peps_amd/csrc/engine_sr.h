@@ -408,6 +408,7 @@ void Engine<T>::sr_cg_solve(const double *b, const double *x0, double diag_shift
     const int sites = Ly_ * Lx_;
     const long n = (long)sites * dp_ * slot_, n2 = 2 * n;
     const double scale = 1.0 / sr_n_;
+    const bool fproj = sr_cg_dev_ != nullptr && fd_d_ > 0 && opt_sign_ != nullptr;   // fermionic opt_natural_gradient (see the real branch)
     auto dvec = [&]() { return (double *)arena_.alloc(sizeof(double) * n2); };
     double *db = dvec(), *dx = dvec(), *dr = dvec(), *dp = dvec(), *dap = dvec(), *dbest = dvec(), *dprev = dvec(), *dmean = dvec();
     double *dsc = (double *)arena_.alloc(sizeof(double) * 16);
@@ -444,6 +445,7 @@ void Engine<T>::sr_cg_solve(const double *b, const double *x0, double diag_shift
     auto read = [&](double *out, int k) {
       PG_CHECK_HIP(hipMemcpyAsync(out, dsc, sizeof(double) * k, hipMemcpyDeviceToHost, stream_));
       PG_CHECK_HIP(hipStreamSynchronize(stream_));
+      if (fproj) for (int q = 0; q < k; ++q) out[q] *= 0.25;
     };
     auto matvec = [&](const double *v, double *out) {
       dotc_into(dmean, v, dsc + 14);   // Ostar_mean * v = sum conj(mean) v
@@ -452,6 +454,7 @@ void Engine<T>::sr_cg_solve(const double *b, const double *x0, double diag_shift
       hipLaunchKernelGGL(sr_accum_cplx_kernel<T>, dim3((unsigned)((slot_ + 255) / 256), sites), dim3(256), 0, stream_, (const T *)sr_o_,
                          (const int *)sr_cfg_, (const double *)sr_delta_, scale, out, sr_n_, sites, slot_, dp_);
       PG_CHECK_HIP(hipGetLastError());
+      if (fproj) opt_fermion_project(out);
       if (diag_shift != 0.0) axpby(diag_shift, v, 1.0, out);
     };
     auto finish = [&](const double *xsrc, double res_sq, int iters, int why) {
@@ -516,6 +519,11 @@ void Engine<T>::sr_cg_solve(const double *b, const double *x0, double diag_shift
   const int sites = Ly_ * Lx_;
   const long n = (long)sites * dp_ * slot_;
   const double scale = 1.0 / sr_n_;
+  // Called from opt_natural_gradient with a fermionic decoration set, the vectors are in the range of E (extended layout) and the
+  // stored-parameter equation (E^T S_ext E + shift) x = g reads Pi(S_ext v) + shift v = g^ on them: Pi is applied to every S v, and
+  // every dot product (4 x the stored one, E^T E = 4 mask) is scaled back, so that the coefficients, the tolerances, the iteration
+  // count and the reported norms are those of the stored-space solve.  Every other call takes the path it always took.
+  const bool fproj = sr_cg_dev_ != nullptr && fd_d_ > 0 && opt_sign_ != nullptr;
   auto dvec = [&]() { return (double *)arena_.alloc(sizeof(double) * n); };
   double *db = dvec(), *dx = dvec(), *dr = dvec(), *dp = dvec(), *dap = dvec(), *dbest = dvec(), *dprev = dvec(), *dmean = dvec();
   double *dsc = (double *)arena_.alloc(sizeof(double) * 8);
@@ -548,6 +556,7 @@ void Engine<T>::sr_cg_solve(const double *b, const double *x0, double diag_shift
     for (auto &pr : pairs) dot_into(pr.first, pr.second, dsc + k++);
     PG_CHECK_HIP(hipMemcpyAsync(out, dsc, sizeof(double) * k, hipMemcpyDeviceToHost, stream_));
     PG_CHECK_HIP(hipStreamSynchronize(stream_));
+    if (fproj) for (int q = 0; q < k; ++q) out[q] *= 0.25;
   };
   // out = S v + diag_shift v     (SRSMatrix::operator*, stochastic_reconfiguration_smatrix.h:37-99)
   auto matvec = [&](const double *v, double *out) {
@@ -557,6 +566,7 @@ void Engine<T>::sr_cg_solve(const double *b, const double *x0, double diag_shift
     hipLaunchKernelGGL(sr_accum_kernel<T>, dim3((unsigned)((slot_ + 255) / 256), sites), dim3(256), 0, stream_, (const T *)sr_o_,
                        (const int *)sr_cfg_, (const double *)sr_delta_, scale, out, sr_n_, sites, slot_, dp_);
     PG_CHECK_HIP(hipGetLastError());
+    if (fproj) opt_fermion_project(out);
     if (diag_shift != 0.0) axpby(diag_shift, v, 1.0, out);
   };
   auto finish = [&](const double *xsrc, double res_sq, int iters, int why) {

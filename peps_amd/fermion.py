@@ -108,6 +108,15 @@ class FermionState:
                 tensors[r][c] = comp
         return FermionState(tensors, par, nf)
 
+    @staticmethod
+    def from_stored(like, stored):
+        """the state with the parity structure of `like` and the stored components `stored` [rows][cols][d][D^4] (legs padded to D),
+        e.g. what hostapi.fermion_optimize_exact_sum returns"""
+        stored = np.asarray(stored)
+        tensors = [[[np.array(stored[(r, c, s) + tuple(slice(0, k) for k in like.tensors[r][c][s].shape)]) for s in range(like.d)]
+                    for c in range(like.cols)] for r in range(like.rows)]
+        return FermionState(tensors, like.par, like.nf)
+
     @property
     def D(self):
         return max(max(t[0].shape) for row in self.tensors for t in row)

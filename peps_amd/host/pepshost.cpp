@@ -426,6 +426,29 @@ void fermion_exact_sum_partial_impl(int rows, int cols, int D, int d, const int3
   ExactSumEnergyEvaluator(sitps, all, contractor, m, rank, size, (size_t)batch, capture, &dec);
   std::copy(packed.begin(), packed.end(), packed_out);
 }
+// ... with the model chosen as fermion_energy_impl chooses it: 0 SquareSpinlessFermion [t, V, t2, -], 1 SquaretJVModel [t, J, V, mu, (t2)]
+template <typename TenElemT>
+void fermion_exact_sum_partial_prm_impl(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype,
+                                        const double *sitps_ext_flat, const int32_t *all_configs, int n_configs, int model,
+                                        const double *prm, int n_prm, int rank, int size, int batch, double *packed_out) {
+  if ((model != 0 && model != 1) || !prm || n_prm < 4) throw std::invalid_argument("pepshost_fermion_exact_sum_partial_prm: model 0 / 1, at least four parameters");
+  SplitIndexTPST<TenElemT> sitps = make_state_t<TenElemT>(rows, cols, D, 4 * d, sitps_ext_flat);
+  FermionDecoration dec;
+  dec.nf.assign(nf, nf + d);
+  BMPSContractorT<TenElemT> contractor(rows, cols, D, 4 * d, trunc_params(chi), batch, dtype, g_device);
+  std::vector<std::vector<int32_t>> all(n_configs);
+  for (int i = 0; i < n_configs; ++i) all[i].assign(all_configs + (size_t)i * rows * cols, all_configs + (size_t)(i + 1) * rows * cols);
+  std::vector<double> packed;
+  auto capture = [&](std::vector<double> &v) { packed = v; };
+  if (model == 0) {
+    SquareSpinlessFermion m(prm[0], prm[2], prm[1]);
+    ExactSumEnergyEvaluator(sitps, all, contractor, m, rank, size, (size_t)batch, capture, &dec);
+  } else {
+    SquaretJVModel m(prm[0], n_prm > 4 ? prm[4] : 0.0, prm[1], prm[2], prm[3]);
+    ExactSumEnergyEvaluator(sitps, all, contractor, m, rank, size, (size_t)batch, capture, &dec);
+  }
+  std::copy(packed.begin(), packed.end(), packed_out);
+}
 
 template <typename TenElemT>
 void fermion_mc_sweeps_impl(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype,
@@ -480,6 +503,82 @@ void fermion_measure_energy_impl(int rows, int cols, int D, int d, const int32_t
   std::copy(comp.config.data(), comp.config.data() + (size_t)n * rows * cols, configs);
   const int total = std::max(1, n_samples * sweeps_between);
   if (accept_out) for (int w = 0; w < n; ++w) accept_out[w] = acc[w] / total;
+}
+// ---- the device-resident Optimizer on a fermionic state (sitps_ext_flat: the 4 d decorated components; bond_parity
+// [rows][cols][4][D]).  model 0: SquareSpinlessFermion, prm = [t, V, t2, -]; model 1: SquaretJVModel, prm = [t, J, V, mu, (t2)].
+// state_out: the d stored components (variant 0), [rows][cols][d][D^4]. ----
+template <typename TenElemT, typename Fn>
+auto with_fermion_model(int model, const double *prm, int n_prm, Fn &&fn) {
+  if (model != 0 && model != 1) throw std::invalid_argument("fermionic optimizer: model must be 0 (spinless) or 1 (tj)");
+  if (!prm || n_prm < 4) throw std::invalid_argument("fermionic optimizer: at least four model parameters");
+  if (model == 0) { SquareSpinlessFermion m(prm[0], prm[2], prm[1]); return fn(m); }
+  SquaretJVModel m(prm[0], n_prm > 4 ? prm[4] : 0.0, prm[1], prm[2], prm[3]);
+  return fn(m);
+}
+inline FermionDecoration make_decoration(int rows, int cols, int D, int d, const int32_t *nf, const uint8_t *bond_parity) {
+  if (d < 1 || !nf || !bond_parity) throw std::invalid_argument("fermionic optimizer: d, nf and bond_parity are required");
+  FermionDecoration dec;
+  dec.nf.assign(nf, nf + d);
+  dec.bond_parity.assign(bond_parity, bond_parity + (size_t)rows * cols * 4 * D);
+  return dec;
+}
+
+template <typename TenElemT>
+void fermion_optimize_exact_sum_impl(int rows, int cols, int D, int d, const int32_t *nf, const uint8_t *bond_parity, int chi, int dtype,
+                                     const double *sitps_ext_flat, const int32_t *all_configs, int n_configs, int model, const double *prm,
+                                     int n_prm, int rule, double lr, const double *rule_params, int n_rule_params, int iterations,
+                                     double clip_value, double clip_norm, int batch, double *energies_out, double *grad_norms_out,
+                                     double *state_out) {
+  if (iterations < 0 || n_configs < 1 || batch < 1) throw std::invalid_argument("pepshost_fermion_optimize_exact_sum: bad iterations / n_configs / batch");
+  static const int want[3] = {3, 2, 4};
+  if (rule < 0 || rule > 2 || n_rule_params != want[rule] || !rule_params)
+    throw std::invalid_argument("pepshost_fermion_optimize_exact_sum: rule 0 SGD (3 parameters), 1 AdaGrad (2), 2 Adam (4)");
+  const FermionDecoration dec = make_decoration(rows, cols, D, d, nf, bond_parity);
+  SplitIndexTPST<TenElemT> sitps = make_state_t<TenElemT>(rows, cols, D, 4 * d, sitps_ext_flat);
+  BMPSContractorT<TenElemT> contractor(rows, cols, D, 4 * d, trunc_params(chi), batch, dtype, g_device);
+  std::vector<std::vector<int32_t>> all(n_configs);
+  for (int i = 0; i < n_configs; ++i) all[i].assign(all_configs + (size_t)i * rows * cols, all_configs + (size_t)(i + 1) * rows * cols);
+  OptimizerParams::BaseParams base((size_t)iterations, 0.0, 0.0, (size_t)iterations + 1, lr);   // the stopping criteria are off
+  if (clip_value > 0.0) base.clip_value = clip_value;
+  if (clip_norm > 0.0) base.clip_norm = clip_norm;
+  const double *q = rule_params;
+  AlgorithmParams algo = rule == 0   ? AlgorithmParams(SGDParams(q[0], q[1] != 0.0, q[2]))
+                         : rule == 1 ? AlgorithmParams(AdaGradParams(q[0], q[1]))
+                                     : AlgorithmParams(AdamParams(q[0], q[1], q[2], q[3]));
+  contractor.UploadState(sitps);
+  Optimizer<TenElemT> opt(OptimizerParams(base, algo), contractor, &dec);
+  typename Optimizer<TenElemT>::OptimizationResult res = with_fermion_model<TenElemT>(model, prm, n_prm, [&](auto &m) {
+    return opt.IterativeOptimize([&](BMPSContractorT<TenElemT> &c) { return ExactSumAccumulateResident(sitps, all, c, m, (size_t)batch, &dec); });
+  });
+  copy_out(res.energy_trajectory, energies_out);
+  if (grad_norms_out) std::copy(res.gradient_norms.begin(), res.gradient_norms.end(), grad_norms_out);
+  copy_out(opt.GetState(rows, cols, d, D).flat(), state_out);
+}
+
+// sr_step_samples_impl on a fermionic state; info_out as there, the norms over the stored parameters
+template <typename TenElemT>
+void fermion_sr_step_samples_impl(int rows, int cols, int D, int d, const int32_t *nf, const uint8_t *bond_parity, int chi, int dtype,
+                                  const double *sitps_ext_flat, int n, const int32_t *configs, int model, const double *prm, int n_prm,
+                                  double lr, double diag_shift, int cg_max_iter, double cg_relative_tolerance, int normalize_update,
+                                  double *state_out, double *info_out) {
+  if (n < 1 || cg_max_iter < 0) throw std::invalid_argument("pepshost_fermion_sr_step_samples: bad sample count / CG iterations");
+  const FermionDecoration dec = make_decoration(rows, cols, D, d, nf, bond_parity);
+  SplitIndexTPST<TenElemT> sitps = make_state_t<TenElemT>(rows, cols, D, 4 * d, sitps_ext_flat);
+  BMPSContractorT<TenElemT> contractor(rows, cols, D, 4 * d, trunc_params(chi), n, dtype, g_device);
+  const Configuration samples = make_cfg(n, rows, cols, configs);
+  StochasticReconfigurationParams sr;
+  sr.cg_params.max_iter = (size_t)cg_max_iter;
+  sr.cg_params.relative_tolerance = cg_relative_tolerance;
+  sr.diag_shift = diag_shift;
+  sr.normalize_update = normalize_update != 0;
+  contractor.UploadState(sitps);
+  Optimizer<TenElemT> opt(OptimizerParams(OptimizerParams::BaseParams(1, 0.0, 0.0, 2, lr), sr), contractor, &dec);
+  typename Optimizer<TenElemT>::OptimizationResult res = with_fermion_model<TenElemT>(model, prm, n_prm, [&](auto &m) {
+    return opt.IterativeOptimize([&](BMPSContractorT<TenElemT> &c) { return SampleSetAccumulateResident(sitps, samples, c, m, &dec); });
+  });
+  info_out[0] = std::real(res.energy_trajectory.at(0)); info_out[1] = std::real(res.energy_trajectory.at(1));
+  info_out[2] = (double)res.sr_iterations; info_out[3] = res.sr_natural_grad_norm; info_out[4] = res.sr_residual_norm;
+  copy_out(opt.GetState(rows, cols, d, D).flat(), state_out);
 }
 }  // namespace
 
@@ -719,6 +818,50 @@ int pepshost_sr_step_samples_c128(int rows, int cols, int D, int d, int chi, con
                                         cg_relative_tolerance, normalize_update, state_out, info_out);
   });
 }
+// Optimizer::IterativeOptimize + exact summation on a fermionic state (see fermion_optimize_exact_sum_impl)
+int pepshost_fermion_optimize_exact_sum(int rows, int cols, int D, int d, const int32_t *nf, const uint8_t *bond_parity, int chi, int dtype,
+                                        const double *sitps_ext_flat, const int32_t *all_configs, int n_configs, int model,
+                                        const double *prm, int n_prm, int rule, double lr, const double *rule_params, int n_rule_params,
+                                        int iterations, double clip_value, double clip_norm, int batch, double *energies_out,
+                                        double *grad_norms_out, double *state_out) {
+  return guarded([&]() {
+    fermion_optimize_exact_sum_impl<double>(rows, cols, D, d, nf, bond_parity, chi, dtype, sitps_ext_flat, all_configs, n_configs, model, prm,
+                                            n_prm, rule, lr, rule_params, n_rule_params, iterations, clip_value, clip_norm, batch,
+                                            energies_out, grad_norms_out, state_out);
+  });
+}
+int pepshost_fermion_optimize_exact_sum_c128(int rows, int cols, int D, int d, const int32_t *nf, const uint8_t *bond_parity, int chi,
+                                             const double *sitps_ext_flat, const int32_t *all_configs, int n_configs, int model,
+                                             const double *prm, int n_prm, int rule, double lr, const double *rule_params,
+                                             int n_rule_params, int iterations, double clip_value, double clip_norm, int batch,
+                                             double *energies_out, double *grad_norms_out, double *state_out) {
+  return guarded([&]() {
+    fermion_optimize_exact_sum_impl<QLTEN_Complex>(rows, cols, D, d, nf, bond_parity, chi, PEPSGPU_C128, sitps_ext_flat, all_configs,
+                                                   n_configs, model, prm, n_prm, rule, lr, rule_params, n_rule_params, iterations,
+                                                   clip_value, clip_norm, batch, energies_out, grad_norms_out, state_out);
+  });
+}
+// Optimizer's SR step on a given sample set of a fermionic state (see fermion_sr_step_samples_impl)
+int pepshost_fermion_sr_step_samples(int rows, int cols, int D, int d, const int32_t *nf, const uint8_t *bond_parity, int chi, int dtype,
+                                     const double *sitps_ext_flat, int n, const int32_t *configs, int model, const double *prm, int n_prm,
+                                     double lr, double diag_shift, int cg_max_iter, double cg_relative_tolerance, int normalize_update,
+                                     double *state_out, double *info_out) {
+  return guarded([&]() {
+    fermion_sr_step_samples_impl<double>(rows, cols, D, d, nf, bond_parity, chi, dtype, sitps_ext_flat, n, configs, model, prm, n_prm, lr,
+                                         diag_shift, cg_max_iter, cg_relative_tolerance, normalize_update, state_out, info_out);
+  });
+}
+int pepshost_fermion_sr_step_samples_c128(int rows, int cols, int D, int d, const int32_t *nf, const uint8_t *bond_parity, int chi,
+                                          const double *sitps_ext_flat, int n, const int32_t *configs, int model, const double *prm,
+                                          int n_prm, double lr, double diag_shift, int cg_max_iter, double cg_relative_tolerance,
+                                          int normalize_update, double *state_out, double *info_out) {
+  return guarded([&]() {
+    fermion_sr_step_samples_impl<QLTEN_Complex>(rows, cols, D, d, nf, bond_parity, chi, PEPSGPU_C128, sitps_ext_flat, n, configs, model, prm,
+                                                n_prm, lr, diag_shift, cg_max_iter, cg_relative_tolerance, normalize_update, state_out,
+                                                info_out);
+  });
+}
+
 // LearningRateScheduler::GetLearningRate (lr_schedulers.h:40-103): kind 0 ConstantLR (lr), 1 ExponentialDecayLR (initial_lr, decay_rate,
 // decay_steps), 2 StepLR (initial_lr, step_size, gamma)
 int pepshost_lr_schedule(int kind, const double *args, int n_args, long iteration, double *lr_out) {
@@ -830,6 +973,19 @@ int pepshost_fermion_exact_sum_partial_c128(int rows, int cols, int D, int d, co
   return guarded([&]() {
     fermion_exact_sum_partial_impl<QLTEN_Complex>(rows, cols, D, d, nf, chi, PEPSGPU_C128, sitps_ext_flat, all_configs, n_configs, t, V, rank,
                                                   size, batch, packed_out);
+  });
+}
+// ... for either fermionic model (see fermion_exact_sum_partial_prm_impl); dtype PEPSGPU_C128 runs the complex instantiation
+int pepshost_fermion_exact_sum_partial_prm(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype,
+                                           const double *sitps_ext_flat, const int32_t *all_configs, int n_configs, int model,
+                                           const double *prm, int n_prm, int rank, int size, int batch, double *packed_out) {
+  return guarded([&]() {
+    if (dtype == PEPSGPU_C128)
+      fermion_exact_sum_partial_prm_impl<QLTEN_Complex>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, all_configs, n_configs, model, prm,
+                                                        n_prm, rank, size, batch, packed_out);
+    else
+      fermion_exact_sum_partial_prm_impl<double>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, all_configs, n_configs, model, prm, n_prm,
+                                                 rank, size, batch, packed_out);
   });
 }
 

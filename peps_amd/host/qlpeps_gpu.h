@@ -629,6 +629,13 @@ class BMPSContractorT {
     check_rc(pepsgpu_grad_read(ctx_, dptr(so.data()), dptr(seo.data())), ctx_);
   }
   // device-resident optimisation step (pepsgpu_opt_*): theta, the gradient / direction and the rule state stay in HBM
+  // d stored states with parities nf, bond parities [rows][cols][4][D]: the optimizer calls below then keep their vectors in the
+  // range of the decoration and report norms over the stored parameters; d = 0 clears it
+  void FermionDecorationSet(const std::vector<int> &nf, const std::vector<uint8_t> &bond_parity) {
+    std::vector<int32_t> n32(nf.begin(), nf.end());
+    check_rc(pepsgpu_fermion_decoration_set(ctx_, (int)n32.size(), n32.data(), bond_parity.data()), ctx_);
+  }
+  void FermionDecorationClear() { check_rc(pepsgpu_fermion_decoration_set(ctx_, 0, nullptr, nullptr), ctx_); }
   void OptBegin() { check_rc(pepsgpu_opt_begin(ctx_), ctx_); }
   void OptEnd() { check_rc(pepsgpu_opt_end(ctx_), ctx_); }
   // g <- (S_EO - conj(E) S_O) / W from the resident accumulators; returns (E, |g|)
@@ -693,6 +700,9 @@ using BMPSContractor = BMPSContractorT<double>;
 enum ModeOrder { ROW_MAJOR = 0, COL_MAJOR = 1 };
 struct FermionDecoration {
   std::vector<int> nf;                         // fermion parity of each physical state (0 = occupied -> 1)
+  // parity of every bond state, [rows][cols][4][D] (legs L, D, R, U; entries past a leg's dimension unused): what the
+  // device-resident Optimizer needs to fold gradients and project in HBM (pepsgpu_fermion_decoration_set); empty elsewhere
+  std::vector<uint8_t> bond_parity;
   size_t d() const { return nf.size(); }
   int n(int32_t state) const { return nf[(size_t)state] & 1; }
   // extended state of `site` for walker w, given the physical configuration
@@ -836,8 +846,8 @@ struct TPSWaveFunctionComponentT {
   }
   // the state is already on the device (an optimizer step wrote it there, pepsgpu_opt_step): no upload
   struct ResidentState {};
-  TPSWaveFunctionComponentT(ResidentState, const Configuration &cfg, BMPSContractorT<TenElemT> &c)
-      : config(cfg), contractor(c), trun_para(c.GetTruncateParams()) {
+  TPSWaveFunctionComponentT(ResidentState, const Configuration &cfg, BMPSContractorT<TenElemT> &c, const FermionDecoration *ferm = nullptr)
+      : config(cfg), contractor(c), trun_para(c.GetTruncateParams()), fermion(ferm) {
     InitDevice();
     EvaluateAmplitude();
   }
@@ -3326,7 +3336,9 @@ std::pair<TenElemT, SplitIndexTPST<TenElemT>> ExactSumEnergyEvaluator(const Spli
 // ---------------------------------------------------------------------------------------------
 // Optimizer (optimizer/optimizer.h, optimizer_impl.h) on device buffers: the master parameters, the gradient and the rule
 // state live in HBM (pepsgpu_opt_*); an iteration is evaluate -> finish -> clip (first-order rules) -> [natural gradient] ->
-// step with no tensor traffic over PCIe.  In: SGD, AdaGrad, Adam and the one-rank SR step.  Out (host drivers of the reference
+// step with no tensor traffic over PCIe.  In: SGD, AdaGrad, Adam and the one-rank SR step, for bosonic and for fermionic states (a
+// FermionDecoration with bond parities: the buffers hold the 4 d decorated components, gradients are folded and projected on the
+// device, norms and the SR solve are those of the stored parameters).  Out (host drivers of the reference
 // that stay with the caller): L-BFGS, step selectors / line search, spike detection, checkpoints, CSV / JSONL logs, MinSR
 // (peps_amd/sr.py), multi-rank CG.  Parameter names and defaults: optimizer/optimizer_params.h.
 struct ConjugateGradientParams {               // optimizer_params.h:50-57
@@ -3463,13 +3475,20 @@ class Optimizer {
     double sr_natural_grad_norm = 0.0, sr_residual_norm = 0.0;
   };
 
-  // adopts the state the contractor holds (UploadState first).  Fermionic components need FoldFermionGradient, a host step: refused.
+  // adopts the state the contractor holds (UploadState first).  Fermionic states: the contractor holds the 4 d decorated components
+  // and `fermion` carries the bond parities; the decoration is set on the context for the life of the optimizer.
   Optimizer(const OptimizerParams &params, ContractorT &contractor, const FermionDecoration *fermion = nullptr)
-      : params_(params), c_(contractor) {
-    if (fermion) throw std::invalid_argument("Optimizer: fermionic states are not supported on the device path (FoldFermionGradient is a host step)");
-    c_.OptBegin();
+      : params_(params), c_(contractor), fermion_(fermion) {
+    if (fermion_) {
+      if (fermion_->bond_parity.empty()) throw std::invalid_argument("Optimizer: the FermionDecoration carries no bond parities");
+      c_.FermionDecorationSet(fermion_->nf, fermion_->bond_parity);
+    }
+    try { c_.OptBegin(); } catch (...) { if (fermion_) pepsgpu_fermion_decoration_set(c_.ctx(), 0, nullptr, nullptr); throw; }
   }
-  ~Optimizer() { pepsgpu_opt_end(c_.ctx()); }
+  ~Optimizer() {
+    pepsgpu_opt_end(c_.ctx());
+    if (fermion_) pepsgpu_fermion_decoration_set(c_.ctx(), 0, nullptr, nullptr);
+  }
   Optimizer(const Optimizer &) = delete;
   Optimizer &operator=(const Optimizer &) = delete;
 
@@ -3543,22 +3562,52 @@ class Optimizer {
     res.min_energy = std::min(res.min_energy, std::real(eg.first));
     return res;
   }
+  // phys_dim: the components of the caller's state -- for a fermionic state the d stored ones (variant 0 of the device's 4 d)
   SplitIndexTPST<TenElemT> GetState(size_t rows, size_t cols, size_t phys_dim, size_t D) const {
-    SplitIndexTPST<TenElemT> s(rows, cols, phys_dim, D);
-    c_.OptReadState(s);
+    if (!fermion_) {
+      SplitIndexTPST<TenElemT> s(rows, cols, phys_dim, D);
+      c_.OptReadState(s);
+      return s;
+    }
+    SplitIndexTPST<TenElemT> ext(rows, cols, 4 * phys_dim, D), s(rows, cols, phys_dim, D);
+    c_.OptReadState(ext);
+    for (size_t r = 0; r < rows; ++r)
+      for (size_t c = 0; c < cols; ++c)
+        for (size_t k = 0; k < phys_dim; ++k) std::copy(ext.component(r, c, k), ext.component(r, c, k) + ext.slot(), s.component(r, c, k));
     return s;
   }
 
  private:
   OptimizerParams params_;
   ContractorT &c_;
+  const FermionDecoration *fermion_ = nullptr;
 };
+
+// what AccumulateDevice of the gradient accumulator hands the device for one batch: bosons the amplitudes, fermions the dense
+// (undecorated-sign) amplitudes sigma * psi and the extended row-major states the holes belong to
+template <typename TenElemT>
+void ResidentGradAccumulate(TPSWaveFunctionComponentT<TenElemT> &comp, const EnergyAndHolesT<TenElemT> &eh, bool exact_sum, bool sr_append) {
+  if (!comp.fermion) {
+    comp.contractor.GradAccumulate(comp.amplitude, eh.energy, exact_sum);
+    if (sr_append) comp.contractor.SRAppend(comp.amplitude);
+    return;
+  }
+  std::vector<TenElemT> dense(comp.amplitude);
+  for (size_t w = 0; w < dense.size(); ++w) dense[w] *= double(comp.fermion->Sigma(comp.config, w));
+  const Configuration ext = comp.fermion->ExtConfig(comp.config, ROW_MAJOR);
+  comp.contractor.GradAccumulate(dense, eh.energy, exact_sum, std::vector<int32_t>(ext.data(), ext.data() + ext.walkers() * ext.rows() * ext.cols()));
+  if (sr_append) {        // the sample store takes the components from the walkers' table: the column pass left the column-major one
+    comp.contractor.Init(ext);
+    comp.contractor.SRAppend(dense);
+  }
+}
 
 // The accumulation of ExactSumEnergyEvaluator for the state the device holds: S_O / S_EO stay in HBM, the two sums come back.
 // `shape` gives the extents only.  One rank.
 template <typename ModelT, typename TenElemT>
 DeviceEvaluationT<TenElemT> ExactSumAccumulateResident(const SplitIndexTPST<TenElemT> &shape, const std::vector<std::vector<int32_t>> &all_configs,
-                                                      BMPSContractorT<TenElemT> &contractor, ModelT &model, size_t batch) {
+                                                      BMPSContractorT<TenElemT> &contractor, ModelT &model, size_t batch,
+                                                      const FermionDecoration *fermion = nullptr) {
   const size_t rows = shape.rows(), cols = shape.cols();
   DeviceEvaluationT<TenElemT> ev;
   contractor.GradReset();
@@ -3566,9 +3615,9 @@ DeviceEvaluationT<TenElemT> ExactSumAccumulateResident(const SplitIndexTPST<TenE
     const size_t nb = std::min(batch, all_configs.size() - b0);
     Configuration cfg(nb, rows, cols);
     for (size_t w = 0; w < nb; ++w) std::copy(all_configs[b0 + w].begin(), all_configs[b0 + w].end(), cfg.data() + w * rows * cols);
-    TPSWaveFunctionComponentT<TenElemT> comp(typename TPSWaveFunctionComponentT<TenElemT>::ResidentState(), cfg, contractor);
+    TPSWaveFunctionComponentT<TenElemT> comp(typename TPSWaveFunctionComponentT<TenElemT>::ResidentState(), cfg, contractor, fermion);
     EnergyAndHolesT<TenElemT> eh = model.template CalEnergyAndHoles<true>(shape, comp, /*holes_on_device=*/true);
-    contractor.GradAccumulate(comp.amplitude, eh.energy, true);
+    ResidentGradAccumulate(comp, eh, true, false);
     for (size_t w = 0; w < nb; ++w) {
       const double wt = AbsSquare(comp.amplitude[w]);
       ev.weight_sum += wt;
@@ -3582,14 +3631,14 @@ DeviceEvaluationT<TenElemT> ExactSumAccumulateResident(const SplitIndexTPST<TenE
 // state the device holds: S_O / S_EO in the accumulators and the O* samples in the SR store (what the SR step solves with), both in HBM.
 template <typename ModelT, typename TenElemT>
 DeviceEvaluationT<TenElemT> SampleSetAccumulateResident(const SplitIndexTPST<TenElemT> &shape, const Configuration &samples,
-                                                       BMPSContractorT<TenElemT> &contractor, ModelT &model) {
+                                                       BMPSContractorT<TenElemT> &contractor, ModelT &model,
+                                                       const FermionDecoration *fermion = nullptr) {
   DeviceEvaluationT<TenElemT> ev;
   contractor.GradReset();
   contractor.SRBegin(samples.walkers());
-  TPSWaveFunctionComponentT<TenElemT> comp(typename TPSWaveFunctionComponentT<TenElemT>::ResidentState(), samples, contractor);
+  TPSWaveFunctionComponentT<TenElemT> comp(typename TPSWaveFunctionComponentT<TenElemT>::ResidentState(), samples, contractor, fermion);
   EnergyAndHolesT<TenElemT> eh = model.template CalEnergyAndHoles<true>(shape, comp, /*holes_on_device=*/true);
-  contractor.GradAccumulate(comp.amplitude, eh.energy, false);
-  contractor.SRAppend(comp.amplitude);
+  ResidentGradAccumulate(comp, eh, false, true);
   for (size_t w = 0; w < samples.walkers(); ++w) { ev.weight_sum += 1.0; ev.e_loc_sum += eh.energy[w]; }
   return ev;
 }

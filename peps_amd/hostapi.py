@@ -20,7 +20,9 @@ SYMBOLS = ["pepshost_last_error", "pepshost_mc_sweeps", "pepshost_energy_and_hol
            "pepshost_fermion_exact_sum_partial_c128", "pepshost_fermion_mc_sweeps_c128", "pepshost_fermion_measure_energy_c128",
            "pepshost_fermion_mc_sweeps_updater", "pepshost_tnn3_table",
            "pepshost_optimize_exact_sum", "pepshost_optimize_exact_sum_c128", "pepshost_lr_schedule",
-           "pepshost_sr_step_samples", "pepshost_sr_step_samples_c128"]
+           "pepshost_sr_step_samples", "pepshost_sr_step_samples_c128",
+           "pepshost_fermion_optimize_exact_sum", "pepshost_fermion_optimize_exact_sum_c128",
+           "pepshost_fermion_sr_step_samples", "pepshost_fermion_sr_step_samples_c128", "pepshost_fermion_exact_sum_partial_prm"]
 
 _lib = None
 _C128 = 3                                   # PEPSGPU_C128 (include/pepsgpu.h)
@@ -496,10 +498,29 @@ def fermion_measure_energy(state, configs, seeds, chi, warmup_sweeps, n_samples,
     return en, cfg, rates
 
 
-def fermion_exact_sum(state, all_configs, chi, t, V=0.0, batch=64, dtype=1):
+def fermion_exact_sum(state, all_configs, chi, t, V=0.0, batch=64, dtype=1, model="spinless", J=0.0, mu=0.0, t2=0.0):
     """ExactSumEnergyEvaluator on a fermionic state: (energy, gradient [rows][cols][d][D^4] with respect to the
-    stored site-tensor components, zero on parity-forbidden entries)."""
+    stored site-tensor components, zero on parity-forbidden entries).  The spinless t-V model, or -- with model="tj" or a
+    diagonal hop t2 -- the models of fermion_energy through the entry that takes a parameter list."""
     from . import fermion
+    if model != "spinless" or t2 != 0.0:
+        cplx = state.is_complex
+        flat = np.ascontiguousarray(state.extended_flat(), dtype=np.complex128 if cplx else np.float64)
+        rows, cols, D = flat.shape[0], flat.shape[1], flat.shape[3]
+        cfg = np.ascontiguousarray(all_configs, dtype=np.int32)
+        nf = np.ascontiguousarray(state.nf, dtype=np.int32)
+        prm = np.array([t, V, t2, 0.0] if model == "spinless" else [t, J, V, mu, t2], dtype=np.float64)
+        packed = np.zeros(4 * flat.size + 5 if cplx else 2 * flat.size + 4)
+        _ck(lib().pepshost_fermion_exact_sum_partial_prm(rows, cols, D, state.d, _p(nf, C.c_int32), chi, _C128 if cplx else dtype, _cp(flat),
+                                                         _p(cfg, C.c_int32), cfg.shape[0], FERMION_MODEL_ID[model], _p(prm, C.c_double),
+                                                         prm.size, 0, 1, batch, _p(packed, C.c_double)))
+        if cplx:
+            e = np.zeros(2)
+            grad = np.zeros(flat.shape, dtype=np.complex128)
+            _ck(lib().pepshost_exact_sum_finish_c128(rows, cols, D, 4 * state.d, _p(packed, C.c_double), _p(e, C.c_double), _cp(grad)))
+            return complex(e[0], e[1]), fermion.fold_gradient(state, grad)
+        e, grad_ext = exact_sum_finish(packed, (rows, cols, 4 * state.d, D))
+        return e, fermion.fold_gradient(state, grad_ext)
     if state.is_complex:                    # QLTEN_Complex: packed = 4 m + 5 doubles, finished by pepshost_exact_sum_finish_c128 on 4 d components
         flat = np.ascontiguousarray(state.extended_flat(), dtype=np.complex128)
         rows, cols, D = flat.shape[0], flat.shape[1], flat.shape[3]
@@ -523,6 +544,89 @@ def fermion_exact_sum(state, all_configs, chi, t, V=0.0, batch=64, dtype=1):
                                                  _p(packed, C.c_double)))
     e, grad_ext = exact_sum_finish(packed, (rows, cols, 4 * state.d, D))
     return e, fermion.fold_gradient(state, grad_ext)
+
+
+FERMION_MODEL_ID = {"spinless": 0, "tj": 1}   # params: spinless (t, V, t2); tj (t, J, V, mu[, t2]) -- as fermion_energy passes them
+
+
+def _fermion_head(state, dtype):
+    """(element type, decorated flat state, leading arguments of the fermionic optimizer shims up to chi)"""
+    cplx = state.is_complex
+    et = np.complex128 if cplx else np.float64
+    flat = np.ascontiguousarray(state.extended_flat(), dtype=et)
+    rows, cols, D = flat.shape[0], flat.shape[1], flat.shape[3]
+    nf = np.ascontiguousarray(state.nf, dtype=np.int32)
+    par = np.zeros((rows, cols, 4, D), dtype=np.uint8)
+    for r in range(rows):
+        for c in range(cols):
+            for leg in range(4):
+                p = np.asarray(state.par[r][c][leg])
+                par[r, c, leg, :len(p)] = p
+    return cplx, flat, nf, par, (rows, cols, D, state.d, _p(nf, C.c_int32), par.ctypes.data_as(C.POINTER(C.c_uint8)))
+
+
+def _fermion_prm(model, params):
+    prm = [float(x) for x in params]
+    if model == "spinless":
+        prm = (prm + [0.0] * 4)[:4]                         # [t, V, t2, -]
+    else:
+        prm = prm + [0.0] * max(0, 4 - len(prm))            # [t, J, V, mu, (t2)]
+    return np.array(prm, dtype=np.float64)
+
+
+def fermion_optimize_exact_sum(state, all_configs, chi, model, params, rule, lr, rule_params, iterations, clip_value=0.0, clip_norm=0.0,
+                               dtype=1, batch=64, return_grad_norms=False):
+    """optimize_exact_sum on a fermionic state (peps_amd.fermion.FermionState): the decorated components are uploaded once, every
+    iteration evaluates, folds and projects the gradient, clips and steps on the device.  model "spinless" (t, V, t2) or "tj"
+    (t, J, V, mu[, t2]).  Returns (energies[iterations + 1], final stored tensors [rows][cols][d][D^4] [, norms of the gradient over
+    the stored parameters]); FermionState.from_stored(state, stored) is the state after the run."""
+    cplx, flat, nf, par, head = _fermion_head(state, dtype)
+    cfg = np.ascontiguousarray(all_configs, dtype=np.int32)
+    prm = _fermion_prm(model, params)
+    rp = np.ascontiguousarray([float(x) for x in rule_params], dtype=np.float64)
+    rid = RULE_ID[rule] if isinstance(rule, str) else int(rule)
+    energies = np.zeros(iterations + 1, dtype=flat.dtype)
+    norms = np.zeros(iterations + 1)
+    stored = np.zeros((flat.shape[0], flat.shape[1], state.d) + flat.shape[3:], dtype=flat.dtype)
+    l = lib()
+    dpt, i32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    tail = [dpt, i32, C.c_int, C.c_int, dpt, C.c_int, C.c_int, C.c_double, dpt, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, dpt, dpt, dpt]
+    lead = [C.c_int] * 4 + [i32, C.POINTER(C.c_uint8), C.c_int]
+    l.pepshost_fermion_optimize_exact_sum.argtypes = lead + [C.c_int] + tail
+    l.pepshost_fermion_optimize_exact_sum_c128.argtypes = lead + tail
+    rest = (_cp(flat), _p(cfg, C.c_int32), cfg.shape[0], FERMION_MODEL_ID[model], _p(prm, C.c_double), prm.size, rid, float(lr),
+            _p(rp, C.c_double), rp.size, int(iterations), float(clip_value), float(clip_norm), int(min(batch, cfg.shape[0])),
+            _cp(energies), _p(norms, C.c_double), _cp(stored))
+    if cplx:
+        _ck(l.pepshost_fermion_optimize_exact_sum_c128(*head, chi, *rest))
+    else:
+        _ck(l.pepshost_fermion_optimize_exact_sum(*head, chi, dtype, *rest))
+    return (energies, stored, norms) if return_grad_norms else (energies, stored)
+
+
+def fermion_sr_step_samples(state, configs, chi, model, params, lr, diag_shift=0.001, cg_max_iter=100, cg_relative_tolerance=1e-4,
+                            normalize_update=False, dtype=1):
+    """sr_step_samples on a fermionic state: the natural gradient is solved in the stored parameters on the device.  Returns (stored
+    tensors after the step [rows][cols][d][D^4], dict as sr_step_samples; the norms are over the stored parameters)."""
+    cplx, flat, nf, par, head = _fermion_head(state, dtype)
+    cfg = np.ascontiguousarray(configs, dtype=np.int32)
+    prm = _fermion_prm(model, params)
+    stored = np.zeros((flat.shape[0], flat.shape[1], state.d) + flat.shape[3:], dtype=flat.dtype)
+    info = np.zeros(5)
+    l = lib()
+    dpt, i32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    tail = [dpt, C.c_int, i32, C.c_int, dpt, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_int, dpt, dpt]
+    lead = [C.c_int] * 4 + [i32, C.POINTER(C.c_uint8), C.c_int]
+    l.pepshost_fermion_sr_step_samples.argtypes = lead + [C.c_int] + tail
+    l.pepshost_fermion_sr_step_samples_c128.argtypes = lead + tail
+    rest = (_cp(flat), cfg.shape[0], _p(cfg, C.c_int32), FERMION_MODEL_ID[model], _p(prm, C.c_double), prm.size, float(lr), float(diag_shift),
+            int(cg_max_iter), float(cg_relative_tolerance), int(bool(normalize_update)), _cp(stored), _p(info, C.c_double))
+    if cplx:
+        _ck(l.pepshost_fermion_sr_step_samples_c128(*head, chi, *rest))
+    else:
+        _ck(l.pepshost_fermion_sr_step_samples(*head, chi, dtype, *rest))
+    return stored, {"energy_before": info[0], "energy_after": info[1], "cg_iterations": int(info[2]), "direction_norm": info[3],
+                    "cg_residual_norm": info[4]}
 
 
 # ---- TenElemT = QLTEN_Complex (std::complex<double>): the same host classes instantiated for the complex element type ----

@@ -224,6 +224,39 @@ long pepsgpu_diag_nnn_hop_slice_calls(void);
  * hop; flag_out [n][2] = -1 where the hop is allowed, else 1 (the skip-flag convention of the slice).  Needs a device, no context. */
 int pepsgpu_diag_fermion_hop_cand(int rows, int cols, int d, const int32_t *occ, int n, const int32_t *ext, int row1, int col1,
                                   int32_t *cand_out, int32_t *sign_out, int32_t *flag_out);
+/* One row (PEPSGPU_HORIZONTAL) or column (PEPSGPU_VERTICAL) of a FERMIONIC state for the measurement of pair operators on its
+ * nearest-neighbour bonds next to the bond energy (square_tJ_model.h:301-345 EvaluateBondEnergy, :546-603 EvaluateBondSC), every element
+ * type, ONE read-back and no per-bond upload.  The walkers' configurations are extended states e = s + d * variant of the mode order of
+ * the pass (row pass: row-major, variants 0 / 1; column pass: column-major, variants 2 / 3), the context's physical dimension is 4 d;
+ * occ [d] (0 / 1) is the fermion number of each physical state.  In order: InitBTen, GrowFullBTen(.., 2, true), then per bond j the Trace
+ * of the window, ONE ReplaceNNSiteTrace over the exchange candidate and the two pair candidates, and ShiftBTenWindow while j + 2 < slice
+ * length -- the BTen stacks end as the per-bond calls leave them.
+ *   pair_table      [d * d][2][2] over PHYSICAL states: candidate k of the states (a, b) on (left / upper, right / lower) site is
+ *                   (a'_k, b'_k) = pair_table[((a * d + b) * 2 + k) * 2 ..], (-1, -1) for none.  A candidate keeps the fermion parity of
+ *                   the pair, so only the variants of the two sites change; the device derives them from occ;
+ *   exchange_table  [phys_dim^2][2] over extended states as for pepsgpu_nn_exchange_slice_tab, or NULL: no exchange candidate, ex_out is
+ *                   not written;
+ *   psi_out   [n][slice length - 1] (PEPSGPU_C128: interleaved (re, im), as every output here): the Trace before bond j's replacement;
+ *   ex_out    [n][slice length - 1]: the amplitude with the exchange move of bond j applied (psi of bond j where it is the identity);
+ *   pair_out  [n][slice length - 1][2]: sign * psi' of pair candidate k of bond j, sign = Sigma(S') / Sigma(S) of the decoration
+ *             Sigma = (-1)^(nf (nf + 1) / 2): -1 where the candidate changes the fermion number by +-2, +1 where it keeps it; exactly 0.0
+ *             for "no candidate".  pair_out / psi_out is the ratio of the graded amplitudes times the Jordan-Wigner sign of the sites
+ *             strictly between the two in row-major order (+1 for a bond along a row).
+ * Status PEPSGPU_EINVAL: bad orientation or slice, a NULL required buffer (ex_out is required with an exchange_table), 4 * d != the
+ * context's physical dimension, an occ entry outside {0, 1}, a pair_table entry outside [-1, d), a candidate with only one -1 or one
+ * that changes the fermion parity of the pair; PEPSGPU_ERANGE: an exchange_table entry outside [0, phys_dim); PEPSGPU_ESTATE: a
+ * boundary MPS of the slice is missing, a configuration override is active, or a state of the slice has a variant of the other mode
+ * order.  A refused call leaves the context usable. */
+int pepsgpu_nn_pair_slice_fermion(pepsgpu_ctx *ctx, int orientation, int slice, int d, const int32_t *occ, const int32_t *pair_table,
+                                  const int32_t *exchange_table, double *psi_out, double *ex_out, double *pair_out);
+/* Completed pepsgpu_nn_pair_slice_fermion calls of this process (all contexts). */
+long pepsgpu_diag_pair_slice_calls(void);
+/* The candidate kernel of pepsgpu_nn_pair_slice_fermion alone, on the caller's extended configurations ext [n][rows][cols] (states in
+ * [0, 4 d), of the mode order of `orientation` on the two sites) for the bond (site1, site2): flat row-major indices of the left / upper
+ * and the right / lower site.  cand_out [n][2][2] the extended states of the two sites under candidate k (the walker's own two states
+ * where it has none); sign_out [n][2] = +1 / -1 as above, 0 for "no candidate".  Needs a device, no context. */
+int pepsgpu_diag_pair_cand(int rows, int cols, int d, const int32_t *occ, const int32_t *pair_table, int n, const int32_t *ext,
+                           int orientation, int site1, int site2, int32_t *cand_out, int32_t *sign_out);
 /* The links of a row pair or a column pair on the device, every element type: the bodies of the row-pair loop and of the column-pair
  * loop of the triangular J1-J2 model (spin_onehalf_triangle_heisenbergJ1J2_sqrpeps.h:350-398, :425-442) with ONE read-back and no
  * upload.  (r, c) is the upper-left site of the window; bit k of link_mask requests kind k:

@@ -26,7 +26,7 @@ SYMBOLS = [
     "pepsgpu_walkers_set_configs", "pepsgpu_walkers_get_configs", "pepsgpu_n_walkers",
     "pepsgpu_grow_bmps_step", "pepsgpu_grow_full_bmps", "pepsgpu_grow_bmps_for_row", "pepsgpu_grow_bmps_for_col",
     "pepsgpu_shift_bmps_window", "pepsgpu_delete_inner_bmps", "pepsgpu_bmps_park", "pepsgpu_bmps_unpark", "pepsgpu_generate_bmps_approach",
-    "pepsgpu_sweep_slice_exchange", "pepsgpu_sweep_slice_exchange_tab", "pepsgpu_sweep_slice_fullspace", "pepsgpu_sweep_slice_tnn3", "pepsgpu_diag_tnn3_table", "pepsgpu_nn_exchange_slice", "pepsgpu_nn_exchange_slice_tab", "pepsgpu_onsite_slice", "pepsgpu_nnn_exchange_slice", "pepsgpu_diag_nnn_slice_calls", "pepsgpu_nnn_hop_slice_fermion", "pepsgpu_diag_nnn_hop_slice_calls", "pepsgpu_diag_fermion_hop_cand", "pepsgpu_link_exchange_slice", "pepsgpu_diag_link_slice_calls", "pepsgpu_diag_link_cand", "pepsgpu_walker_create", "pepsgpu_walker_clone", "pepsgpu_walker_destroy", "pepsgpu_walker_info", "pepsgpu_walker_set_mpo", "pepsgpu_walker_set_mpo_excited", "pepsgpu_walker_trace_slice", "pepsgpu_diag_walker_slice_calls", "pepsgpu_walker_evolve",
+    "pepsgpu_sweep_slice_exchange", "pepsgpu_sweep_slice_exchange_tab", "pepsgpu_sweep_slice_fullspace", "pepsgpu_sweep_slice_tnn3", "pepsgpu_diag_tnn3_table", "pepsgpu_nn_exchange_slice", "pepsgpu_nn_exchange_slice_tab", "pepsgpu_onsite_slice", "pepsgpu_nnn_exchange_slice", "pepsgpu_diag_nnn_slice_calls", "pepsgpu_nnn_hop_slice_fermion", "pepsgpu_diag_nnn_hop_slice_calls", "pepsgpu_diag_fermion_hop_cand", "pepsgpu_nn_pair_slice_fermion", "pepsgpu_diag_pair_slice_calls", "pepsgpu_diag_pair_cand", "pepsgpu_link_exchange_slice", "pepsgpu_diag_link_slice_calls", "pepsgpu_diag_link_cand", "pepsgpu_walker_create", "pepsgpu_walker_clone", "pepsgpu_walker_destroy", "pepsgpu_walker_info", "pepsgpu_walker_set_mpo", "pepsgpu_walker_set_mpo_excited", "pepsgpu_walker_trace_slice", "pepsgpu_diag_walker_slice_calls", "pepsgpu_walker_evolve",
     "pepsgpu_walker_evolve_step", "pepsgpu_walker_contract_row", "pepsgpu_walker_init_bten", "pepsgpu_walker_grow_bten_step",
     "pepsgpu_walker_shift_bten_window", "pepsgpu_walker_trace_with_bten", "pepsgpu_walker_clear_bten", "pepsgpu_walker_get_bmps_tensor",
     "pepsgpu_bmps_stack_size", "pepsgpu_get_bmps_tensor", "pepsgpu_init_bten", "pepsgpu_grow_full_bten",
@@ -117,6 +117,10 @@ def load_library(path=LIB_PATH):
     lib.pepsgpu_diag_nnn_hop_slice_calls.argtypes = []
     lib.pepsgpu_diag_nnn_hop_slice_calls.restype = C.c_long
     lib.pepsgpu_diag_fermion_hop_cand.argtypes = [C.c_int, C.c_int, C.c_int, ip, C.c_int, ip, C.c_int, C.c_int, ip, ip, ip]
+    lib.pepsgpu_nn_pair_slice_fermion.argtypes = [vp, C.c_int, C.c_int, C.c_int, ip, ip, ip, dp, dp, dp]
+    lib.pepsgpu_diag_pair_slice_calls.argtypes = []
+    lib.pepsgpu_diag_pair_slice_calls.restype = C.c_long
+    lib.pepsgpu_diag_pair_cand.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, C.c_int, ip, C.c_int, C.c_int, C.c_int, ip, ip]
     lib.pepsgpu_link_exchange_slice.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp]
     lib.pepsgpu_diag_link_slice_calls.argtypes = []
     lib.pepsgpu_diag_link_slice_calls.restype = C.c_long
@@ -422,6 +426,28 @@ class Context:
         val = np.zeros((self.n, self.cols - 1, 2), dtype=self._ot)
         self._ck(self._l.pepsgpu_nnn_hop_slice_fermion(self._h, row1, occ.size, _ip(occ), diag_mask, _dp(psi), _dp(val)))
         return psi, val
+
+    def nn_pair_slice_fermion(self, orientation, slice_num, nf, pair_table, exchange_table=None):
+        """one row / column of a fermionic state (extended configurations of the pass's mode order; nf [d] the fermion number of each
+        physical state, 4 d = the context's physical dimension): pair_table [d * d][2][2] over physical states, candidate k of the pair
+        (a, b) or (-1, -1); exchange_table [(4 d)^2][2] over extended states or None.  Returns (psi [n][N-1], ex [n][N-1] or None,
+        pair [n][N-1][2]) with pair = sign psi' (sign -1 where the fermion number changes by +-2), exactly 0 for "no candidate"; one
+        read-back"""
+        occ = np.ascontiguousarray(nf, dtype=np.int32)
+        tab = np.ascontiguousarray(pair_table, dtype=np.int32)
+        assert tab.size == occ.size * occ.size * 4, tab.shape
+        N = self.cols if orientation == HORIZONTAL else self.rows
+        psi = np.zeros((self.n, N - 1), dtype=self._ot)
+        pair = np.zeros((self.n, N - 1, 2), dtype=self._ot)
+        xt, ex = None, None
+        if exchange_table is not None:
+            xt = np.ascontiguousarray(exchange_table, dtype=np.int32)
+            assert xt.shape == (self.d * self.d, 2), xt.shape
+            ex = np.zeros((self.n, N - 1), dtype=self._ot)
+        self._ck(self._l.pepsgpu_nn_pair_slice_fermion(self._h, orientation, slice_num, occ.size, _ip(occ), _ip(tab),
+                                                       _ip(xt) if xt is not None else None, _dp(psi),
+                                                       _dp(ex) if ex is not None else None, _dp(pair)))
+        return psi, ex, pair
 
     def onsite_slice(self, orientation, slice_num, site_table, punch_holes=False):
         """one-site moves along a row / column: site_table [d][n_cand] (candidate k of state s); returns (psi [n],
@@ -1106,6 +1132,26 @@ def diag_fermion_hop_cand(ext, nf, row1, col1):
     if rc != 0:
         raise ValueError("diag_fermion_hop_cand: status %d" % rc)
     return cand, sign, flag
+
+
+def diag_pair_slice_calls():
+    """completed pepsgpu_nn_pair_slice_fermion calls of this process"""
+    return int(lib().pepsgpu_diag_pair_slice_calls())
+
+
+def diag_pair_cand(ext, nf, pair_table, orientation, site1, site2):
+    """pair_cand_kernel alone: ext [n][rows][cols] extended configurations of the mode order of `orientation`, nf [d], pair_table
+    [d * d][2][2]; (site1, site2) the flat row-major indices of the bond's left / upper and right / lower site.  Returns
+    (cand [n][2][2], sign [n][2])"""
+    e = np.ascontiguousarray(ext, dtype=np.int32)
+    occ = np.ascontiguousarray(nf, dtype=np.int32)
+    tab = np.ascontiguousarray(pair_table, dtype=np.int32)
+    n, rows, cols = e.shape
+    cand, sign = np.zeros((n, 2, 2), dtype=np.int32), np.zeros((n, 2), dtype=np.int32)
+    rc = lib().pepsgpu_diag_pair_cand(rows, cols, occ.size, _ip(occ), _ip(tab), n, _ip(e), orientation, site1, site2, _ip(cand), _ip(sign))
+    if rc != 0:
+        raise ValueError("diag_pair_cand: status %d" % rc)
+    return cand, sign
 
 
 def diag_link_slice_calls():

@@ -215,6 +215,43 @@ int pepsgpu_diag_fermion_hop_cand(int rows, int cols, int d, const int32_t *occ,
     PG_CHECK_HIP(hipMemcpy(flag_out, df, 2 * (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
   });
 }
+// square_tJ_model.h:546-603 next to :301-345: psi, the exchanged amplitude and the pair candidates of every bond of one row / column
+int pepsgpu_nn_pair_slice_fermion(pepsgpu_ctx *ctx, int orientation, int slice, int d, const int32_t *occ, const int32_t *pair_table,
+                                  const int32_t *exchange_table, double *psi_out, double *ex_out, double *pair_out) {
+  CTX_CALL(PG_REQUIRE(occ && pair_table && psi_out && pair_out && (!exchange_table || ex_out), 1, "null buffer");
+           ctx->eng->nn_pair_slice_fermion(orientation, slice, d, occ, pair_table, exchange_table, psi_out, ex_out, pair_out));
+}
+long pepsgpu_diag_pair_slice_calls(void) { return pepsgpu::pair_slice_calls().load(); }
+// pair_cand_kernel alone on a caller's extended configurations ext [n][rows][cols] for the bond (site1, site2), flat row-major indices
+// of the left / upper and the right / lower site: cand_out [n][2][2], sign_out [n][2]
+int pepsgpu_diag_pair_cand(int rows, int cols, int d, const int32_t *occ, const int32_t *pair_table, int n, const int32_t *ext,
+                           int orientation, int site1, int site2, int32_t *cand_out, int32_t *sign_out) {
+  return guarded(nullptr, [&]() {
+    PG_REQUIRE(occ && pair_table && ext && cand_out && sign_out, 1, "null buffer");
+    PG_REQUIRE(orientation == HORIZONTAL || orientation == VERTICAL, 1, "bad orientation");
+    PG_REQUIRE(rows >= 1 && cols >= 1 && n >= 1 && (double)n * rows * cols < 2147483648.0, 1, "bad sizes");
+    const bool hor = orientation == HORIZONTAL;
+    const int sites = rows * cols;
+    PG_REQUIRE(site1 >= 0 && site2 < sites && site2 == site1 + (hor ? 1 : cols) && (!hor || site1 % cols + 1 < cols), 1,
+               "the two sites are no bond of this orientation");
+    const unsigned occ_bits = pepsgpu::require_pair_tables(d, occ, pair_table);
+    const size_t ne = (size_t)n * sites;
+    for (size_t e = 0; e < ne; ++e) PG_REQUIRE(ext[e] >= 0 && ext[e] < 4 * d, 1, "extended state outside [0, 4 d)");
+    for (int w = 0; w < n; ++w)
+      for (int s : {site1, site2})
+        PG_REQUIRE((ext[(size_t)w * sites + s] / d >= 2) == !hor, 1, "extended states of the other mode order on the bond");
+    DevBufs m;
+    const int *dcfg = m.alloc<int>(ne, ext);
+    const int *dtab = m.alloc<int>(4 * (size_t)d * d, pair_table);
+    int *dc = m.alloc<int>(6 * (size_t)n), *ds = dc + 4 * (size_t)n;
+    hipLaunchKernelGGL(pair_cand_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, dcfg, sites, site1, site2, d, occ_bits, hor ? 0 : 1, dtab,
+                       (const int *)nullptr, 4 * d, dc, (int *)nullptr, ds, n);
+    PG_CHECK_HIP(hipGetLastError());
+    PG_CHECK_HIP(hipDeviceSynchronize());
+    PG_CHECK_HIP(hipMemcpy(cand_out, dc, 4 * (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    PG_CHECK_HIP(hipMemcpy(sign_out, ds, 2 * (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+  });
+}
 // spin_onehalf_triangle_heisenbergJ1J2_sqrpeps.h:350-398 / :425-442: the links of one row pair / column pair
 int pepsgpu_link_exchange_slice(pepsgpu_ctx *ctx, int orient, int slice1, int link_mask, double *val_out) {
   CTX_CALL(PG_REQUIRE(val_out, 1, "null buffer"); ctx->eng->link_exchange_slice(orient, slice1, link_mask, val_out));

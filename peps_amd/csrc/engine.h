@@ -147,6 +147,9 @@ struct EngineBase {
   virtual void nnn_exchange_slice(int row1, int diag_mask, double *val_out) = 0;
   virtual void link_exchange_slice(int orient, int slice1, int link_mask, double *val_out) = 0;
   virtual void nnn_hop_slice_fermion(int row1, int d, const int32_t *occ, int diag_mask, double *psi_out, double *val_out) = 0;
+  // psi, the exchanged amplitude and up to two pair candidates per bond of one row / column of a fermionic context; engine_sweep.h
+  virtual void nn_pair_slice_fermion(int orient, int slice, int d, const int32_t *occ, const int32_t *pair_table,
+                                     const int32_t *exchange_table, double *psi_out, double *ex_out, double *pair_out) = 0;
   // BMPSWalker (bmps_contractor.h:357-646)
   virtual int walker_create(int pos, int level) = 0;
   virtual int walker_clone(int id) = 0;
@@ -1012,6 +1015,8 @@ class Engine : public EngineBase {
   void nnn_exchange_slice(int row1, int diag_mask, double *val_out) override;
   void link_exchange_slice(int orient, int slice1, int link_mask, double *val_out) override;
   void nnn_hop_slice_fermion(int row1, int d, const int32_t *occ, int diag_mask, double *psi_out, double *val_out) override;
+  void nn_pair_slice_fermion(int orient, int slice, int d, const int32_t *occ, const int32_t *pair_table, const int32_t *exchange_table,
+                             double *psi_out, double *ex_out, double *pair_out) override;
   // the parts the slice functions share (engine_sweep.h)
   void begin_slice(const SliceGeom &g, int remain);
   template <typename Moves>

@@ -718,6 +718,173 @@ void Engine<T>::nnn_hop_slice_fermion(int row1, int d, const int32_t *occ, int d
   nnn_hop_slice_calls() += 1;
 }
 
+// ---- pair moves on the nearest-neighbour bonds of a fermionic state (the bond-singlet order of the t-J model,
+// square_tJ_model.h:546-603: the two electrons of a bond removed, or put into an empty bond) ----
+// The two sites of a bond along a row (column) are adjacent in the row-major (column-major) mode order, so a move that keeps the
+// fermion parity of the pair changes the variants of these two sites only (extended state e = s + d v: v = 0 / 1 the parity of the
+// fermions up to and including the site in row-major order, v = 2 / 3 that of the fermions strictly before it in column-major order):
+//   row-major     before = v1 ^ n(a);  e1' = a' + d (before ^ n(a')),      e2' = b' + d (before ^ n(a') ^ n(b'))
+//   column-major  before = v1 & 1;     e1' = a' + d (2 + before),          e2' = b' + d (2 + (before ^ n(a')))
+// the rule of the exchange table of the host layer (TPSWaveFunctionComponent::ExchangeTable) for any (a', b').  ptab [d * d][2][2]
+// over PHYSICAL states: candidate k of the pair (a, b) is (a'_k, b'_k), (-1, -1) for none.  Per walker nc = (xtab ? 1 : 0) + 2 slots
+// cand [n][nc][2]: the exchange slot first when xtab [dp * dp][2] (the table of sweep_swap_cand_kernel over extended states) is given,
+// with same[w] = 1 where that move is the identity, then the two pair slots; a walker without candidate k keeps its own two states
+// in that slot.  sign [n][2] = Sigma(S') / Sigma(S) of the decoration, Sigma = (-1)^(nf (nf + 1) / 2): -1 where the fermion number
+// changes by +-2, +1 where it is unchanged, 0 for "no candidate".
+__global__ void pair_cand_kernel(const int *__restrict__ cfg, int sites, int s1, int s2, int d, unsigned occ_bits, int col_major,
+                                 const int *__restrict__ ptab, const int *__restrict__ xtab, int dp, int *__restrict__ cand,
+                                 int *__restrict__ same, int *__restrict__ sign, int n) {
+  const int w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= n) return;
+  const int e1 = cfg[(long)w * sites + s1], e2 = cfg[(long)w * sites + s2];
+  const int a = e1 % d, b = e2 % d;
+  auto occ = [&](int s) { return (int)((occ_bits >> s) & 1u); };
+  const int before = col_major ? ((e1 / d) & 1) : (((e1 / d) & 1) ^ occ(a));
+  const int slot0 = xtab ? 1 : 0, nc = slot0 + 2;
+  int *c = cand + 2 * (long)w * nc;
+  if (xtab) {
+    const int x1 = xtab[2 * (e1 * dp + e2)], x2 = xtab[2 * (e1 * dp + e2) + 1];
+    c[0] = x1;
+    c[1] = x2;
+    same[w] = (x1 == e1 && x2 == e2);
+  }
+  for (int k = 0; k < 2; ++k) {
+    const int pa = ptab[4 * (a * d + b) + 2 * k], pb = ptab[4 * (a * d + b) + 2 * k + 1];
+    int c1 = e1, c2 = e2, sg = 0;
+    if (pa >= 0) {
+      const int na = occ(pa), nb = occ(pb);
+      c1 = pa + d * (col_major ? 2 + before : before ^ na);
+      c2 = pb + d * (col_major ? 2 + (before ^ na) : before ^ na ^ nb);
+      sg = (na + nb == occ(a) + occ(b)) ? 1 : -1;
+    }
+    c[2 * (slot0 + k)] = c1;
+    c[2 * (slot0 + k) + 1] = c2;
+    sign[2 * w + k] = sg;
+  }
+}
+
+// The values of one bond of the pair slice into the table out [n][stride] of AccT scalars (stored as doubles, complex interleaved):
+// res [n][nc] with lsum [n] from the replacement trace over the slots of pair_cand_kernel.  The exchange slot (same != nullptr) goes
+// to column ex_col -- psi of the bond, already in column psi_col, where the move is the identity; pair slot k goes to column
+// pair_col + k as sign res exp(lsum), exactly 0.0 where sign is 0.
+template <typename AccT>
+__global__ void pair_store_kernel(const AccT *__restrict__ res, const double *__restrict__ lsum, const int *__restrict__ sign,
+                                  const int *__restrict__ same, double *__restrict__ out, int stride, int psi_col, int ex_col,
+                                  int pair_col, int n) {
+  constexpr int ko = (int)(sizeof(AccT) / sizeof(double));
+  const int slot0 = same ? 1 : 0, nc = slot0 + 2;
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n * nc) return;
+  const int w = e / nc, q = e - w * nc;
+  if (q < slot0) {
+    double *o = out + ((long)w * stride + ex_col) * ko;
+    if (same[w]) {
+      const double *src = out + ((long)w * stride + psi_col) * ko;
+      for (int z = 0; z < ko; ++z) o[z] = src[z];
+    } else {
+      sw_put(o, sw_scaled(res[e], exp(lsum[w])));
+    }
+    return;
+  }
+  const int k = q - slot0, sg = sign[2 * w + k];
+  double *o = out + ((long)w * stride + pair_col + k) * ko;
+  if (sg == 0) {
+    for (int z = 0; z < ko; ++z) o[z] = 0.0;
+  } else {
+    sw_put(o, sw_scaled(res[e], (double)sg * exp(lsum[w])));
+  }
+}
+
+// the tables of a pair slice as the host hands them over: occ [d] (status 1 outside {0, 1}); pair_table [d * d][2][2] with entries in
+// [-1, d), a candidate either (-1, -1) or two states that keep the fermion parity of the pair (status 1 otherwise)
+inline unsigned require_pair_tables(int d, const int32_t *occ, const int32_t *pair_table) {
+  const unsigned occ_bits = hop_occ_bits(d, occ);
+  for (int a = 0; a < d; ++a)
+    for (int b = 0; b < d; ++b)
+      for (int k = 0; k < 2; ++k) {
+        const int pa = pair_table[4 * (a * d + b) + 2 * k], pb = pair_table[4 * (a * d + b) + 2 * k + 1];
+        PG_REQUIRE(pa >= -1 && pa < d && pb >= -1 && pb < d, 1, "pair table: entry outside [-1, d)");
+        PG_REQUIRE((pa < 0) == (pb < 0), 1, "pair table: a candidate with only one -1");
+        PG_REQUIRE(pa < 0 || ((occ[pa] + occ[pb] + occ[a] + occ[b]) & 1) == 0, 1, "pair table: a candidate changes the fermion parity of the pair");
+      }
+  return occ_bits;
+}
+
+inline std::atomic<long> &pair_slice_calls() {   // completed nn_pair_slice_fermion calls of the process (pepsgpu_diag_pair_slice_calls)
+  static std::atomic<long> n{0};
+  return n;
+}
+
+// One row / column of a fermionic context for the measurement of pair operators next to the bond energy: the sibling of mode 0 of
+// energy_slice_impl with psi per bond and without holes (GrowFullBTen(.., 2), the window shifted while j + 2 < N).  Per bond one
+// Trace (psi), the candidates of pair_cand_kernel built on the device from the walkers' own configuration table, ONE replacement
+// trace over all of them and pair_store_kernel; ONE read-back at the end, no per-bond upload.  psi_out [n][N - 1], ex_out [n][N - 1]
+// (written when exchange_table is given), pair_out [n][N - 1][2]; complex: interleaved.
+template <typename T>
+void Engine<T>::nn_pair_slice_fermion(int orient, int slice, int d, const int32_t *occ, const int32_t *pair_table,
+                                      const int32_t *exchange_table, double *psi_out, double *ex_out, double *pair_out) {
+  require_ready();
+  const SliceGeom g(orient, slice, Lx_, Ly_);
+  PG_REQUIRE(occ && pair_table && psi_out && pair_out && (!exchange_table || ex_out), 1, "null buffer");
+  PG_REQUIRE(d >= 1 && 4 * d == dp_, 1, "pair slice: the context's physical dimension must be 4 d (extended states), d <= 32");
+  const unsigned occ_bits = require_pair_tables(d, occ, pair_table);
+  const size_t xlen = exchange_table ? 2 * (size_t)dp_ * dp_ : 0;
+  require_states(exchange_table, xlen, dp_, "pair slice: exchange table state out of range");
+  const bool hor = orient == HORIZONTAL;
+  const int N = g.N, sites = Ly_ * Lx_, np = N - 1;
+  (void)bmps_at_slice(hor ? UP : LEFT, slice);
+  (void)bmps_at_slice(hor ? DOWN : RIGHT, slice);
+  // (the candidate kernel reads the walkers' own configuration table: an override would be ignored where the per-bond calls honour it)
+  PG_REQUIRE(!ovr_on_, 3, "pair slice: a configuration override is active");
+  for (int w = 0; w < nw_; ++w)
+    for (int j = 0; j < N; ++j)
+      PG_REQUIRE((hcfg_[(size_t)w * sites + g.site(j)] / d >= 2) == !hor, 3,
+                 "pair slice: extended states of the other mode order in the slice (rows: variants 0 / 1, columns: 2 / 3)");
+  const int slot0 = exchange_table ? 1 : 0, nc = slot0 + 2;
+  // value table [n][stride] of Acc scalars: psi of bond j in column j, its exchanged amplitude in np + j, its pair slots in 2 np + 2 j + k
+  const int stride = 4 * np;
+  ArenaBuf<double> dval(arena_, kOut * (size_t)nw_ * std::max(stride, 1));
+  ArenaBuf<int> dcand(arena_, (2 * (size_t)nc + 3) * (size_t)nw_);           // candidates [n][nc][2], same [n], signs [n][2]
+  int *dsame = dcand + 2 * (size_t)nc * nw_, *dsign = dsame + nw_;
+  ArenaBuf<int> dtab(arena_, 4 * (size_t)d * d + xlen);
+  int *dxtab = exchange_table ? dtab + 4 * (size_t)d * d : nullptr;
+  PG_CHECK_HIP(hipMemcpyAsync(dtab, pair_table, sizeof(int) * 4 * (size_t)d * d, hipMemcpyHostToDevice, stream_));
+  if (dxtab) PG_CHECK_HIP(hipMemcpyAsync(dxtab, exchange_table, sizeof(int) * xlen, hipMemcpyHostToDevice, stream_));
+  begin_slice(g, 2);
+  const int gb = (nw_ + 255) / 256;
+  for (int j = 0; j + 1 < N; ++j) {
+    const int r1 = g.row(j), c1 = g.col(j);
+    {
+      double *lsum = nullptr;
+      Acc *res = nn_trace_device(r1, c1, orient, 1, nullptr, &lsum);
+      hipLaunchKernelGGL(slice_store_value_kernel<Acc>, dim3(gb), dim3(256), 0, stream_, (const Acc *)res, (const double *)lsum, dval,
+                         stride, j, 1, (const int *)nullptr, 0, nw_);
+      PG_CHECK_HIP(hipGetLastError());
+      arena_.free(res); arena_.free(lsum);
+    }
+    hipLaunchKernelGGL(pair_cand_kernel, dim3(gb), dim3(256), 0, stream_, (const int *)cfg_, sites, g.site(j), g.site(j + 1), d, occ_bits,
+                       hor ? 0 : 1, (const int *)dtab, (const int *)dxtab, dp_, dcand, dxtab ? dsame : nullptr, dsign, nw_);
+    PG_CHECK_HIP(hipGetLastError());
+    double *lsum = nullptr;
+    Acc *res = nn_trace_device(r1, c1, orient, nc, dcand, &lsum);
+    hipLaunchKernelGGL(pair_store_kernel<Acc>, dim3((nw_ * nc + 255) / 256), dim3(256), 0, stream_, (const Acc *)res, (const double *)lsum,
+                       (const int *)dsign, dxtab ? (const int *)dsame : nullptr, dval, stride, j, np + j, 2 * np + 2 * j, nw_);
+    PG_CHECK_HIP(hipGetLastError());
+    arena_.free(res); arena_.free(lsum);
+    if (j + 2 < N) shift_bten_window(g.hi);
+  }
+  std::vector<double> h((size_t)kOut * nw_ * stride);
+  if (!h.empty()) PG_CHECK_HIP(hipMemcpyAsync(h.data(), dval, sizeof(double) * h.size(), hipMemcpyDeviceToHost, stream_));
+  PG_CHECK_HIP(hipStreamSynchronize(stream_));
+  for (int w = 0; w < nw_; ++w) {
+    const double *row = h.data() + (size_t)w * stride * kOut;
+    std::copy(row, row + (size_t)np * kOut, psi_out + (size_t)w * np * kOut);
+    if (exchange_table) std::copy(row + (size_t)np * kOut, row + 2 * (size_t)np * kOut, ex_out + (size_t)w * np * kOut);
+    std::copy(row + 2 * (size_t)np * kOut, row + 4 * (size_t)np * kOut, pair_out + 2 * (size_t)w * np * kOut);
+  }
+  pair_slice_calls() += 1;
+}
+
 // ---- three-site exchange (MCUpdateSquareTNN3SiteExchange::TNN3SiteUpdateImpl, square_3site_updater.h:109-158) ----
 // Triple table [dp^3][TNN3_TAB]: entry e1 dp^2 + e2 dp + e3 holds m (the number of distinct permutations of the triple: 1, 3 or 6),
 // init (the position of the triple itself among them) and six slots of three states, the permutations in std::next_permutation order

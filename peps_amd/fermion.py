@@ -392,9 +392,133 @@ def spinless_fermion_observables(ctx, state, configs, t, V=0.0, t2=0.0):
             "bond_energy_ur": bonds["ur"].reshape(n, -1)}, psis
 
 
-def exact_sum_measure(ctx, state, all_configs, t, V=0.0, rank=0, size=1, batch=None, t2=0.0):
+def tj_pair_table():
+    """The configurations a pair operator connects the states (a, b) of a nearest-neighbour bond of the t-J model to (0 up, 1 down,
+    2 empty), [3 * 3][2][2] over physical states, (-1, -1) for none: (empty, empty) -> (up, down), (down, up); (up, down) and
+    (down, up) -> (empty, empty).  The pair table of pepsgpu_nn_pair_slice_fermion."""
+    tab = -np.ones((9, 2, 2), dtype=np.int32)
+    tab[2 * 3 + 2] = ((0, 1), (1, 0))
+    tab[0 * 3 + 1, 0] = (2, 2)
+    tab[1 * 3 + 0, 0] = (2, 2)
+    return tab
+
+
+def exchange_table(state, order):
+    """The exchange of two sites adjacent in the mode order over pairs of extended states, [(4 d)^2][2] (the host layer's
+    TPSWaveFunctionComponent::ExchangeTable): a pair whose variants do not belong to `order` maps to itself."""
+    d = state.d
+    dp = NVAR * d
+    nf = np.asarray(state.nf) % 2
+    e1, e2 = np.meshgrid(np.arange(dp), np.arange(dp), indexing="ij")
+    a1, v1, a2, v2 = e1 % d, e1 // d, e2 % d, e2 // d
+    na, nb = nf[a2], nf[a1]                                   # the exchanged physical states (a, b) = (a2, a1)
+    if order == ROW:
+        ok = (v1 < 2) & (v2 < 2)
+        before = (v1 & 1) ^ nf[a1]
+        c1, c2 = a2 + d * (before ^ na), a1 + d * (before ^ na ^ nb)
+    else:
+        ok = (v1 >= 2) & (v2 >= 2)
+        before = v1 & 1
+        c1, c2 = a2 + d * (2 + before), a1 + d * (2 + (before ^ na))
+    return np.stack([np.where(ok, c1, e1), np.where(ok, c2, e2)], axis=-1).reshape(dp * dp, 2).astype(np.int32)
+
+
+def _pair_slice_by_calls(ctx, state, cfg, orient, order, lo, hi, s, table):
+    """what Context.nn_pair_slice_fermion returns, from per-bond Trace + ReplaceNNSiteTrace calls with the candidates built on the
+    host from ext_config of the changed configurations"""
+    from .capi import HORIZONTAL
+    n = cfg.shape[0]
+    N = cfg.shape[2] if orient == HORIZONTAL else cfg.shape[1]
+    dt = np.complex128 if state.is_complex else np.float64
+    psi, ex, pair = np.zeros((n, N - 1), dt), np.zeros((n, N - 1), dt), np.zeros((n, N - 1, 2), dt)
+    ctx.init_bten(lo, s)
+    ctx.grow_full_bten(hi, s, 2, True)
+    for j in range(N - 1):
+        (r1, c1), (r2, c2) = ((s, j), (s, j + 1)) if orient == HORIZONTAL else ((j, s), (j + 1, s))
+        a, b = cfg[:, r1, c1], cfg[:, r2, c2]
+        pc = table[a * state.d + b]                           # [n][2][2]
+        has = pc[:, :, 0] >= 0
+        cands = []
+        for na, nb in [(b, a)] + [(np.where(has[:, k], pc[:, k, 0], a), np.where(has[:, k], pc[:, k, 1], b)) for k in range(2)]:
+            new = cfg.copy()
+            new[:, r1, c1], new[:, r2, c2] = na, nb
+            ne = state.ext_config(new, order)
+            cands.append(np.stack([ne[:, r1, c1], ne[:, r2, c2]], axis=-1))
+        psi[:, j] = ctx.trace(r1, c1, orient)
+        res = ctx.replace_nn_trace(r1, c1, orient, np.stack(cands, axis=1))
+        ex[:, j] = np.where(a != b, res[:, 0], psi[:, j])
+        nfs = np.asarray(state.nf) % 2
+        for k in range(2):
+            keeps = nfs[np.where(has[:, k], pc[:, k, 0], a)] + nfs[np.where(has[:, k], pc[:, k, 1], b)] == nfs[a] + nfs[b]
+            pair[:, j, k] = np.where(has[:, k], np.where(keeps, 1.0, -1.0) * res[:, 1 + k], 0.0)      # Sigma(S') / Sigma(S)
+        if j + 2 < N:
+            ctx.shift_bten_window(hi)
+    return psi, ex, pair
+
+
+def tj_observables(ctx, state, configs, t, J, V=0.0, mu=0.0, t2=0.0, pair="slice"):
+    """Registry of SquareNNNModelMeasurementSolver<SquaretJVModel>::EvaluateObservables (square_tJ_model.h:546-603, :730-850) for a batch
+    of configurations, driven from Python: energy [n, 1], spin_z, charge [n, rows * cols], bond_energy_h / _v / _dr / _ur and the
+    bond-singlet pairing order SC_bond_singlet_h / _v.  Also returns psi_list [rows + cols][n].
+
+    Convention: |S> = product of c+ over the occupied sites in row-major order; Delta+_ij = (c+_i,up c+_j,down - c+_i,down c+_j,up) /
+    sqrt(2) with i the left / upper site.  With rho(S') = jw psi(S') / psi(S): (empty, empty) gives delta_dag = conj(rho(up, down) -
+    rho(down, up)) / sqrt(2); (up, down) gives delta = conj(rho(empty, empty)) / sqrt(2), (down, up) its negative; the registry value is
+    (conj(delta_dag) + delta) / 2.  Inside a pass the two sites are adjacent modes and rho = -ReplaceNNSiteTrace / Trace: the
+    decoration leaves out Sigma = (-1)^(nf (nf + 1) / 2), which a pair move flips.
+    pair = "slice": one pepsgpu_nn_pair_slice_fermion per row / column; "calls": Trace + ReplaceNNSiteTrace per bond."""
+    from .capi import LEFT, DOWN, RIGHT, UP, HORIZONTAL, VERTICAL
+    if pair not in ("slice", "calls"):
+        raise ValueError("tj_observables: pair must be 'slice' or 'calls'")
+    cfg = np.asarray(configs)
+    n, rows, cols = cfg.shape
+    dt = np.complex128 if state.is_complex else np.float64
+    table, nf = tj_pair_table(), np.asarray(state.nf) % 2
+    out = {"h": np.zeros((n, rows, cols - 1), dt), "v": np.zeros((n, rows - 1, cols), dt),
+           "sc_h": np.zeros((n, rows, cols - 1), dt), "sc_v": np.zeros((n, rows - 1, cols), dt)}
+    psis = []
+    isq2 = 1.0 / np.sqrt(2.0)
+    for orient, order, approach, step, lo, hi, key in ((HORIZONTAL, ROW, UP, DOWN, LEFT, RIGHT, "h"), (VERTICAL, COL, LEFT, RIGHT, UP, DOWN, "v")):
+        S, N = (rows, cols) if orient == HORIZONTAL else (cols, rows)
+        ctx.set_configs(state.ext_config(cfg, order))
+        xtab = exchange_table(state, order)
+        ctx.generate_bmps_approach(approach)
+        for s in range(S):
+            if pair == "slice":
+                psi, ex, pr = ctx.nn_pair_slice_fermion(orient, s, nf, table, xtab)
+            else:
+                psi, ex, pr = _pair_slice_by_calls(ctx, state, cfg, orient, order, lo, hi, s, table)
+            if np.any(psi == 0):
+                raise RuntimeError("Wavefunction amplitude is near zero, causing division by zero.")
+            psis.append(psi[:, 0])
+            for j in range(N - 1):
+                (r1, c1), (r2, c2) = ((s, j), (s, j + 1)) if orient == HORIZONTAL else ((j, s), (j + 1, s))
+                a, b = cfg[:, r1, c1], cfg[:, r2, c2]
+                same, hole = a == b, (a == 2) | (b == 2)
+                ratio = np.conj(ex[:, j] / psi[:, j])
+                e = np.where(same, np.where(a == 2, 0.0, V), np.where(hole, -t * ratio, (-0.5 + 0.5 * ratio) * J + V))
+                rho = pr[:, j, :] / psi[:, j, None]
+                sc = np.where((a == 2) & (b == 2), (rho[:, 0] - rho[:, 1]) * isq2,
+                              np.where((a == 0) & (b == 1), np.conj(rho[:, 0]) * isq2,
+                                       np.where((a == 1) & (b == 0), -np.conj(rho[:, 0]) * isq2, 0.0))) / 2
+                out[key][:, r1, c1], out["sc_" + key][:, r1, c1] = e, sc
+            if s + 1 < S:
+                ctx.shift_bmps_window(step)
+    bonds = {"dr": np.zeros((n, rows - 1, cols - 1), dt), "ur": np.zeros((n, rows - 1, cols - 1), dt)}
+    energy = out["h"].sum(axis=(1, 2)) + out["v"].sum(axis=(1, 2)) - mu * np.sum(cfg != 2, axis=(1, 2))
+    if t2 != 0.0:
+        energy = energy + nnn_hop_energy_slice(ctx, state, cfg, t2, bonds)
+    return {"energy": energy[:, None], "spin_z": np.where(cfg == 0, 0.5, np.where(cfg == 1, -0.5, 0.0)).reshape(n, -1),
+            "charge": (cfg != 2).astype(np.float64).reshape(n, -1), "bond_energy_h": out["h"].reshape(n, -1),
+            "bond_energy_v": out["v"].reshape(n, -1), "bond_energy_dr": bonds["dr"].reshape(n, -1),
+            "bond_energy_ur": bonds["ur"].reshape(n, -1), "SC_bond_singlet_h": out["sc_h"].reshape(n, -1),
+            "SC_bond_singlet_v": out["sc_v"].reshape(n, -1)}, np.array(psis)
+
+
+def exact_sum_measure(ctx, state, all_configs, t, V=0.0, rank=0, size=1, batch=None, t2=0.0, tj=None):
     """ExactSumMeasurerMPI (exact_summation_measurer.h:103-257) on the device: configurations rank, rank + size, ... in
-    batches of walkers; returns (weighted sums by key, weight sum) -- sum both over ranks (all-reduce) and divide."""
+    batches of walkers; returns (weighted sums by key, weight sum) -- sum both over ranks (all-reduce) and divide.
+    tj = (J, mu): the t-J model's registry (tj_observables with t, V and t2 as given) instead of the spinless one."""
     cfgs = np.asarray(all_configs)[rank::size]
     if len(np.asarray(all_configs)) == 0:
         raise ValueError("ExactSumMeasurerMPI: all_configs must not be empty")
@@ -402,7 +526,10 @@ def exact_sum_measure(ctx, state, all_configs, t, V=0.0, rank=0, size=1, batch=N
     wsum, acc = 0.0, {}
     for b0 in range(0, len(cfgs), batch):
         part = cfgs[b0:b0 + batch]
-        obs, psis = spinless_fermion_observables(ctx, state, part, t, V, t2)
+        if tj is None:
+            obs, psis = spinless_fermion_observables(ctx, state, part, t, V, t2)
+        else:
+            obs, psis = tj_observables(ctx, state, part, t, tj[0], V, tj[1], t2)
         w = np.abs(psis[0]) ** 2                           # |psi(S)|^2: the sign decoration drops out
         wsum += float(w.sum())
         for key, vals in obs.items():

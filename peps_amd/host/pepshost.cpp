@@ -504,6 +504,116 @@ void fermion_measure_energy_impl(int rows, int cols, int D, int d, const int32_t
   const int total = std::max(1, n_samples * sweeps_between);
   if (accept_out) for (int w = 0; w < n; ++w) accept_out[w] = acc[w] / total;
 }
+// ---- the measurement solvers of the fermionic models.  model 0: SquareSpinlessFermion [t, V, t2]; 1: SquaretJVModel [t, J, V, mu, t2];
+// 2: SquaretJNNModel [t, J, mu] (the nearest-neighbour form: no diagonal-bond keys).  Output in the format of pepshost_measure: keys
+// "key:len;", every number of a complex state as a (re, im) pair. ----
+template <typename Fn>
+auto with_fermion_measurement_model(const char *who, int model, const double *prm, int n_prm, Fn &&fn) {
+  if (model < 0 || model > 2 || n_prm < 0 || n_prm > 5 || (n_prm > 0 && !prm))
+    throw std::invalid_argument(std::string(who) + ": model 0 (spinless), 1 (tj) or 2 (tjnn), at most 5 parameters");
+  double p[5] = {0, 0, 0, 0, 0};
+  std::copy(prm, prm + n_prm, p);
+  if (model == 0) { SquareSpinlessFermion m(p[0], p[2], p[1]); return fn(m); }
+  if (model == 1) { SquaretJVModel m(p[0], p[4], p[1], p[2], p[3]); return fn(m); }
+  SquaretJNNModel m(p[0], p[1], p[2]);
+  return fn(m);
+}
+struct KeyedValues {            // the output of the three entries below
+  std::string keys;
+  std::vector<double> vals;
+  template <typename V> void push(const V &v) {
+    vals.push_back(std::real(v));
+    if constexpr (!std::is_arithmetic_v<V>) vals.push_back(std::imag(v));
+  }
+  void write(const char *who, char *keys_out, int keys_cap, double *values_out, long values_cap, long *values_len) const {
+    if (!keys_out || !values_out || !values_len) throw std::invalid_argument(std::string(who) + ": null output buffer");
+    if ((int)keys.size() + 1 > keys_cap || (long)vals.size() > values_cap) throw std::out_of_range(std::string(who) + ": output buffer too small");
+    std::copy(keys.begin(), keys.end(), keys_out);
+    keys_out[keys.size()] = 0;
+    std::copy(vals.begin(), vals.end(), values_out);
+    *values_len = (long)vals.size();
+  }
+};
+// EvaluateObservables on a batch of configurations: per key [walker][len], then psi_mean [walker] and psi_rel_err [walker]
+template <typename TenElemT>
+void fermion_observables_impl(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype, const double *sitps_ext_flat, int n,
+                              const int32_t *configs, int model, int n_prm, const double *prm, KeyedValues &out) {
+  SplitIndexTPST<TenElemT> sitps = make_state_t<TenElemT>(rows, cols, D, 4 * d, sitps_ext_flat);
+  FermionDecoration dec;
+  dec.nf.assign(nf, nf + d);
+  BMPSContractorT<TenElemT> contractor(rows, cols, D, 4 * d, trunc_params(chi), n, dtype, g_device);
+  TPSWaveFunctionComponentT<TenElemT> comp(sitps, make_cfg(n, rows, cols, configs), contractor, &dec);
+  with_fermion_measurement_model("pepshost_fermion_observables", model, prm, n_prm, [&](auto &m) {
+    ObservableMapT<TenElemT> obs = m.EvaluateObservables(sitps, comp);
+    for (const auto &kv : obs.values) {
+      out.keys += kv.first + ":" + std::to_string(obs.len(kv.first)) + ";";
+      for (const auto &v : kv.second) out.push(v);
+    }
+    const PsiSummaryT<TenElemT> psi = m.template EvaluatePsiSummaryT<TenElemT>();
+    for (const auto &v : psi.psi_mean) out.push(v);
+    for (double v : psi.psi_rel_err) out.push(TenElemT(v));
+    return 0;
+  });
+}
+// ExactSumMeasurer, the share of one rank: values = [weight | per key the raw weighted sums] (pepshost_exact_sum_measure_partial)
+template <typename TenElemT>
+void fermion_exact_sum_measure_partial_impl(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype, const double *sitps_ext_flat,
+                                            const int32_t *all_configs, int n_configs, int model, int n_prm, const double *prm, int rank,
+                                            int size, int batch, KeyedValues &out) {
+  if (n_configs < 1 || !all_configs || batch < 1 || size < 1 || rank < 0 || rank >= size)
+    throw std::invalid_argument("pepshost_fermion_exact_sum_measure_partial: configurations, batch >= 1 and 0 <= rank < size are required");
+  if (rank >= n_configs) { out.vals.assign(1, 0.0); return; }          // a rank without configurations contributes nothing
+  SplitIndexTPST<TenElemT> sitps = make_state_t<TenElemT>(rows, cols, D, 4 * d, sitps_ext_flat);
+  FermionDecoration dec;
+  dec.nf.assign(nf, nf + d);
+  BMPSContractorT<TenElemT> contractor(rows, cols, D, 4 * d, trunc_params(chi), batch, dtype, g_device);
+  std::vector<std::vector<int32_t>> all(n_configs);
+  for (int i = 0; i < n_configs; ++i) all[i].assign(all_configs + (size_t)i * rows * cols, all_configs + (size_t)(i + 1) * rows * cols);
+  auto capture = [&](std::vector<double> &v) { out.vals = v; v[0] = 1.0; };   // keep the raw sums; normalise in the caller
+  with_fermion_measurement_model("pepshost_fermion_exact_sum_measure_partial", model, prm, n_prm, [&](auto &m) {
+    const auto res = ExactSumMeasurer(sitps, all, contractor, m, rank, size, (size_t)batch, capture, nullptr, &dec);
+    for (const auto &kv : res) out.keys += kv.first + ":" + std::to_string(kv.second.size()) + ";";
+    return 0;
+  });
+}
+// MCPEPSMeasurer with the exchange updater: per key mean [len] and standard error [len] across the walkers, then the psi summary of the
+// last sample.  Warm-up, samples and random streams as fermion_measure_energy_impl (no rescaling of the state), so energy_samples_out
+// [sample][walker] holds the numbers that entry returns.
+template <typename TenElemT>
+void fermion_measure_impl(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype, const double *sitps_ext_flat, int n,
+                          int32_t *configs, const uint64_t *seeds, int warmup_sweeps, int n_samples, int sweeps_between, int model, int n_prm,
+                          const double *prm, KeyedValues &out, double *energy_samples_out, double *accept_out) {
+  if (n_samples < 1 || warmup_sweeps < 0 || sweeps_between < 0 || !seeds || !configs)
+    throw std::invalid_argument("pepshost_fermion_measure: seeds, configurations and n_samples >= 1 are required");
+  SplitIndexTPST<TenElemT> sitps = make_state_t<TenElemT>(rows, cols, D, 4 * d, sitps_ext_flat);
+  FermionDecoration dec;
+  dec.nf.assign(nf, nf + d);
+  BMPSContractorT<TenElemT> contractor(rows, cols, D, 4 * d, trunc_params(chi), n, dtype, g_device);
+  TPSWaveFunctionComponentT<TenElemT> comp(sitps, make_cfg(n, rows, cols, configs), contractor, &dec);
+  std::vector<uint64_t> sd(seeds, seeds + n);
+  MCUpdateSquareNNExchangeOBC ex(sd);
+  MCMeasurementParams mp;
+  mp.num_samples = n_samples; mp.num_warmup_sweeps = warmup_sweeps; mp.sweeps_between_samples = sweeps_between;
+  mp.normalize_state = false;
+  constexpr int z = ElemTraits<TenElemT>::is_complex ? 2 : 1;
+  with_fermion_measurement_model("pepshost_fermion_measure", model, prm, n_prm, [&](auto &m) {
+    MCPEPSMeasurer<MCUpdateSquareNNExchangeOBC, std::decay_t<decltype(m)>, TenElemT> meas(sitps, comp, mp, ex, m);
+    meas.Execute();
+    for (const auto &kv : meas.ObservableRegistry()) {
+      out.keys += kv.first + ":" + std::to_string(kv.second.first.size()) + ";";
+      for (const auto &v : kv.second.first) out.push(v);
+      for (size_t k = 0; k < kv.second.first.size(); ++k) out.push(TenElemT(kv.second.second.empty() ? 0.0 : kv.second.second[k]));
+    }
+    for (int w = 0; w < n; ++w) out.push(meas.PsiSamples().back()[w].first);
+    for (int w = 0; w < n; ++w) out.push(TenElemT(meas.PsiSamples().back()[w].second));
+    if (energy_samples_out)
+      for (size_t k = 0; k < meas.EnergySamples().size(); ++k) copy_out(meas.EnergySamples()[k], energy_samples_out + k * (size_t)n * z);
+    if (accept_out) std::copy(meas.AcceptRates().begin(), meas.AcceptRates().end(), accept_out);
+    return 0;
+  });
+  std::copy(comp.config.data(), comp.config.data() + (size_t)n * rows * cols, configs);
+}
+
 // ---- the device-resident Optimizer on a fermionic state (sitps_ext_flat: the 4 d decorated components; bond_parity
 // [rows][cols][4][D]).  model 0: SquareSpinlessFermion, prm = [t, V, t2, -]; model 1: SquaretJVModel, prm = [t, J, V, mu, (t2)].
 // state_out: the d stored components (variant 0), [rows][cols][d][D^4]. ----
@@ -1090,6 +1200,55 @@ int pepshost_fermion_measure_energy_prm(int rows, int cols, int D, int d, const 
     else
       fermion_measure_energy_impl<double>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, n, configs, seeds, warmup_sweeps, n_samples,
                                           sweeps_between, model, p, energies_out, accept_out, 5);
+  });
+}
+
+// The registry of the fermionic measurement solvers (SquareNNNModelMeasurementSolver on SquareSpinlessFermion / SquaretJVModel /
+// SquaretJNNModel): energy, spin_z, charge, bond_energy_h / _v (/ _dr / _ur) and, for the t-J models, SC_bond_singlet_h / _v.  dtype
+// PEPSGPU_C128 runs the complex instantiation; keys and values as pepshost_measure writes them.
+// ... of a batch of configurations: per key [walker][len], then psi_mean [walker], psi_rel_err [walker]
+int pepshost_fermion_observables(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype, const double *sitps_ext_flat, int n,
+                                 const int32_t *configs, int model, int n_prm, const double *prm, char *keys_out, int keys_cap,
+                                 double *values_out, long values_cap, long *values_len) {
+  return guarded([&]() {
+    KeyedValues out;
+    if (dtype == PEPSGPU_C128) fermion_observables_impl<QLTEN_Complex>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, n, configs, model, n_prm, prm, out);
+    else fermion_observables_impl<double>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, n, configs, model, n_prm, prm, out);
+    out.write("pepshost_fermion_observables", keys_out, keys_cap, values_out, values_cap, values_len);
+  });
+}
+// ... summed with the weights |psi(S)|^2 over the configurations rank, rank + size, ... (ExactSumMeasurerMPI): values = [weight | sums]
+int pepshost_fermion_exact_sum_measure_partial(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype,
+                                               const double *sitps_ext_flat, const int32_t *all_configs, int n_configs, int model, int n_prm,
+                                               const double *prm, int rank, int size, int batch, char *keys_out, int keys_cap,
+                                               double *values_out, long values_cap, long *values_len) {
+  return guarded([&]() {
+    KeyedValues out;
+    if (dtype == PEPSGPU_C128)
+      fermion_exact_sum_measure_partial_impl<QLTEN_Complex>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, all_configs, n_configs, model, n_prm,
+                                                            prm, rank, size, batch, out);
+    else
+      fermion_exact_sum_measure_partial_impl<double>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, all_configs, n_configs, model, n_prm, prm,
+                                                     rank, size, batch, out);
+    out.write("pepshost_fermion_exact_sum_measure_partial", keys_out, keys_cap, values_out, values_cap, values_len);
+  });
+}
+// ... sampled by MCPEPSMeasurer with the exchange updater: per key mean [len] and standard error [len] across the walkers, then the psi
+// summary of the last sample; energy_samples_out [sample][walker] and accept_out [walker] may be NULL.  Warm-up, samples and ONE
+// std::mt19937 stream per walker exactly as pepshost_fermion_measure_energy: the energy samples are that entry's.
+int pepshost_fermion_measure(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype, const double *sitps_ext_flat, int n,
+                             int32_t *configs, const uint64_t *seeds, int warmup_sweeps, int n_samples, int sweeps_between, int model, int n_prm,
+                             const double *prm, char *keys_out, int keys_cap, double *values_out, long values_cap, long *values_len,
+                             double *energy_samples_out, double *accept_out) {
+  return guarded([&]() {
+    KeyedValues out;
+    if (dtype == PEPSGPU_C128)
+      fermion_measure_impl<QLTEN_Complex>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, n, configs, seeds, warmup_sweeps, n_samples,
+                                          sweeps_between, model, n_prm, prm, out, energy_samples_out, accept_out);
+    else
+      fermion_measure_impl<double>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, n, configs, seeds, warmup_sweeps, n_samples, sweeps_between,
+                                   model, n_prm, prm, out, energy_samples_out, accept_out);
+    out.write("pepshost_fermion_measure", keys_out, keys_cap, values_out, values_cap, values_len);
   });
 }
 

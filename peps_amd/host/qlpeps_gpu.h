@@ -1683,11 +1683,161 @@ inline std::vector<TenElemT> MeasureSpinOneHalfOffDiagOrderInRow(TPSWaveFunction
 // ones (EvaluateBondEnergy, EvaluateNNNEnergy, EvaluateTotalOnsiteEnergy) plus
 //   static constexpr bool requires_spin_sz_measurement / requires_density_measurement, CalSpinSzImpl / CalDensityImpl,
 //   EvaluateOffDiagOrderInRow(comp, row, inv_psi, out)   (row hook; may do nothing)
+// A fermionic model (kFermionicModel) takes the fermionic traversal below; one with enable_sc_measurement (the t-J family) also
+// reports the bond-singlet pairing order through EvaluateBondSC / PairTable / BondSCFromPairs.
+template <typename U, typename = void> struct IsFermionicModel : std::false_type {};
+template <typename U> struct IsFermionicModel<U, std::void_t<decltype(U::kFermionicModel)>> : std::bool_constant<U::kFermionicModel> {};
+template <typename U, typename = void> struct HasSCMeasurement : std::false_type {};
+template <typename U> struct HasSCMeasurement<U, std::void_t<decltype(U::enable_sc_measurement)>> : std::bool_constant<U::enable_sc_measurement> {};
+
 template <class ModelType, bool has_nnn_interaction = true>
 class SquareNNNModelMeasurementSolver {
  public:
+  // The registry of a fermionic model (square_nnn_model_measurement_solver.h:33-215 on a fermionic index; square_tJ_model.h:546-603).
+  // Row pass in ROW_MAJOR order, column pass in COL_MAJOR order -- the traversal of the energy solver -- so that the two sites of every
+  // bond are adjacent modes.  Per bond the energy hook and, with enable_sc_measurement, the pair estimator:
+  //   rho(S') = jw psi(S') / psi(S) = sign ReplaceNNSiteTrace / Trace,  sign = Sigma(S') / Sigma(S) = -1 for a move that changes the
+  //   fermion number by +-2 (the decoration leaves Sigma = (-1)^(nf (nf + 1) / 2) out; the column pass's ratio carries jw by itself),
+  //   registry value (conj(delta_dag) + delta) / 2 of BondSCFromPairs.
+  // Slice path (default): ONE pepsgpu_nn_pair_slice_fermion per row / column serves psi, the exchanged amplitude of
+  // BondEnergyFromExchange and the pair candidates from one read-back.  PEPSHOST_NO_DEVICE_SWEEP=1: the per-bond hooks
+  // EvaluateBondEnergy / EvaluateBondSC.  The diagonal bonds (has_nnn_interaction): FermionNNNBondEnergies of the model, zeros where
+  // t2 = 0.
+  template <typename TenElemT>
+  ObservableMapT<TenElemT> EvaluateFermionObservables(TPSWaveFunctionComponentT<TenElemT> &comp) {
+    if (!comp.fermion) throw std::logic_error("EvaluateObservables: a fermionic model needs the fermionic decoration of the component");
+    auto &c = comp.contractor;
+    auto *derived = static_cast<ModelType *>(this);
+    const FermionDecoration &fd = *comp.fermion;
+    const size_t ly = c.rows(), lx = c.cols(), n = comp.config.walkers(), sites = ly * lx;
+    constexpr bool sc = HasSCMeasurement<ModelType>::value;
+    ObservableMapT<TenElemT> out;
+    out.n = n;
+    if constexpr (ModelType::requires_spin_sz_measurement) {
+      auto &sz = out.make("spin_z", sites);
+      for (size_t w = 0; w < n; ++w)
+        for (size_t s = 0; s < sites; ++s) sz[w * sites + s] = derived->CalSpinSzImpl(comp.config(w, {s / lx, s % lx}));
+    }
+    if constexpr (ModelType::requires_density_measurement) {
+      auto &ch = out.make("charge", sites);
+      for (size_t w = 0; w < n; ++w)
+        for (size_t s = 0; s < sites; ++s) ch[w * sites + s] = derived->CalDensityImpl(comp.config(w, {s / lx, s % lx}));
+    }
+    const size_t len_h = ly * (lx - 1), len_v = (ly - 1) * lx;
+    auto &e_h = out.make("bond_energy_h", len_h);
+    auto &e_v = out.make("bond_energy_v", len_v);
+    std::vector<TenElemT> *sc_h = nullptr, *sc_v = nullptr;
+    if constexpr (sc) {
+      sc_h = &out.make("SC_bond_singlet_h", len_h);
+      sc_v = &out.make("SC_bond_singlet_v", len_v);
+    }
+    std::vector<TenElemT> total(n, TenElemT(0.0));
+    std::vector<std::vector<TenElemT>> psi_list;
+    auto nonzero = [](const TenElemT &psi) {
+      if (psi == TenElemT(0.0)) throw std::runtime_error("Wavefunction amplitude is near zero, causing division by zero.");
+    };
+    // bond j of a slice -> its place in the h / v arrays of walker w
+    auto put = [&](BondOrientation dir, size_t slice, size_t j, size_t w, TenElemT e, TenElemT scv) {
+      const size_t k = dir == HORIZONTAL ? w * len_h + slice * (lx - 1) + j : w * len_v + j * lx + slice;
+      (dir == HORIZONTAL ? e_h : e_v)[k] = e;
+      total[w] += e;
+      if constexpr (sc) (*(dir == HORIZONTAL ? sc_h : sc_v))[k] = scv;
+    };
+    bool use_slice = false;
+    if constexpr (HasExchangeBondEnergy<ModelType>::value && HasExchangeBondPsiPerBond<ModelType>::value) use_slice = DeviceSlicesEnabled();
+    std::vector<int32_t> occ(fd.d()), ptab(4 * fd.d() * fd.d(), -1);
+    for (size_t s = 0; s < occ.size(); ++s) occ[s] = fd.n((int32_t)s);
+    if constexpr (sc) ptab = derived->PairTable();
+    auto slice_pass = [&](BondOrientation dir, size_t slice) {
+      if constexpr (HasExchangeBondEnergy<ModelType>::value) {
+        const size_t N = dir == HORIZONTAL ? lx : ly, np = N - 1;
+        std::vector<TenElemT> psi(n * np), ex(n * np), pair(n * np * 2), psi0(n);
+        const std::vector<int32_t> xtab = comp.ExchangeTable();
+        check_rc(pepsgpu_nn_pair_slice_fermion(c.ctx(), dir, (int)slice, (int)fd.d(), occ.data(), ptab.data(), xtab.data(), dptr(psi.data()),
+                                               dptr(ex.data()), dptr(pair.data())), c.ctx());
+        for (size_t w = 0; w < n; ++w) {
+          for (size_t j = 0; j < np; ++j) {
+            const SiteIdx s1 = dir == HORIZONTAL ? SiteIdx{slice, j} : SiteIdx{j, slice};
+            const SiteIdx s2 = dir == HORIZONTAL ? SiteIdx{slice, j + 1} : SiteIdx{j + 1, slice};
+            const size_t k = w * np + j;
+            nonzero(psi[k]);
+            const int32_t c1 = comp.config(w, s1), c2 = comp.config(w, s2);
+            const TenElemT e = derived->BondEnergyFromExchange(c1, c2, ComplexConjugate(TenElemT(ex[k] / psi[k])));
+            TenElemT scv(0.0);
+            if constexpr (sc) {
+              const auto dd = derived->BondSCFromPairs(c1, c2, TenElemT(pair[2 * k] / psi[k]), TenElemT(pair[2 * k + 1] / psi[k]));
+              scv = (ComplexConjugate(dd.first) + dd.second) / TenElemT(2.0);
+            }
+            put(dir, slice, j, w, e, scv);
+          }
+          psi0[w] = np ? psi[w * np] : TenElemT(1.0);         // (the first bond's window is the slice's first window)
+        }
+        psi_list.push_back(psi0);
+      }
+    };
+    auto hook_pass = [&](BondOrientation dir, size_t slice) {
+      const size_t N = dir == HORIZONTAL ? lx : ly;
+      if (dir == HORIZONTAL) { c.InitBTen(LEFT, slice); c.GrowFullBTen(RIGHT, slice, 1, true); }
+      else { c.InitBTen(UP, slice); c.GrowFullBTen(DOWN, slice, 2, true); }
+      psi_list.push_back(c.Trace(dir == HORIZONTAL ? SiteIdx{slice, 0} : SiteIdx{0, slice}, dir));
+      for (const TenElemT &p : psi_list.back()) nonzero(p);
+      const std::vector<TenElemT> unused;                      // (the fermionic hooks take psi from their own Trace)
+      for (size_t j = 0; j + 1 < N; ++j) {
+        const SiteIdx s1 = dir == HORIZONTAL ? SiteIdx{slice, j} : SiteIdx{j, slice};
+        const SiteIdx s2 = dir == HORIZONTAL ? SiteIdx{slice, j + 1} : SiteIdx{j + 1, slice};
+        const std::vector<TenElemT> e = derived->EvaluateBondEnergy(s1, s2, dir, comp, unused);
+        std::vector<TenElemT> scv(n, TenElemT(0.0));
+        if constexpr (sc) {
+          const auto dd = derived->EvaluateBondSC(s1, s2, dir, comp);
+          for (size_t w = 0; w < n; ++w) scv[w] = (ComplexConjugate(dd[w].first) + dd[w].second) / TenElemT(2.0);
+        }
+        for (size_t w = 0; w < n; ++w) put(dir, slice, j, w, e[w], scv[w]);
+        if (dir == HORIZONTAL || j + 2 < N) c.ShiftBTenWindow(dir == HORIZONTAL ? RIGHT : DOWN);
+      }
+    };
+    comp.SetOrder(ROW_MAJOR);
+    c.GenerateBMPSApproach(UP);
+    for (size_t row = 0; row < ly; ++row) {
+      if (use_slice) slice_pass(HORIZONTAL, row); else hook_pass(HORIZONTAL, row);
+      if (row + 1 < ly) c.ShiftBMPSWindow(DOWN);
+    }
+    comp.SetOrder(COL_MAJOR);
+    c.GenerateBMPSApproach(LEFT);
+    for (size_t col = 0; col < lx; ++col) {
+      if (use_slice) slice_pass(VERTICAL, col); else hook_pass(VERTICAL, col);
+      if (col + 1 < lx) c.ShiftBMPSWindow(RIGHT);
+    }
+    // (the same order of additions as the energy solver: bonds, on-site term, diagonal hops)
+    auto &en = out.make("energy", 1);
+    for (size_t w = 0; w < n; ++w) en[w] = total[w] + derived->EvaluateTotalOnsiteEnergy(comp.config, w);
+    if constexpr (has_nnn_interaction) {
+      const size_t len_d = (ly - 1) * (lx - 1);
+      std::vector<TenElemT> both(n * len_d * 2, TenElemT(0.0));
+      derived->FermionNNNBondEnergies(comp, en, &both);
+      auto &e_dr = out.make("bond_energy_dr", len_d);
+      auto &e_ur = out.make("bond_energy_ur", len_d);
+      for (size_t k = 0; k < n * len_d; ++k) { e_dr[k] = both[2 * k]; e_ur[k] = both[2 * k + 1]; }
+    }
+    last_psi_.assign(n);
+    std::vector<TenElemT> one(psi_list.size());
+    for (size_t w = 0; w < n; ++w) {
+      for (size_t k = 0; k < psi_list.size(); ++k) one[k] = psi_list[k][w];
+      auto s = ComputePsiConsistencySummaryAligned(one);
+      last_psi_.psi_mean[w] = s.first;
+      last_psi_.psi_rel_err[w] = s.second;
+    }
+    return out;
+  }
   template <typename TenElemT>
   ObservableMapT<TenElemT> EvaluateObservables(const SplitIndexTPST<TenElemT> &, TPSWaveFunctionComponentT<TenElemT> &comp) {
+    if constexpr (IsFermionicModel<ModelType>::value) {
+      return EvaluateFermionObservables(comp);
+    } else {
+      return EvaluateBosonObservables(comp);
+    }
+  }
+  template <typename TenElemT>
+  ObservableMapT<TenElemT> EvaluateBosonObservables(TPSWaveFunctionComponentT<TenElemT> &comp) {
     auto &c = comp.contractor;
     auto *derived = static_cast<ModelType *>(this);
     const size_t ly = c.rows(), lx = c.cols(), n = comp.config.walkers();
@@ -1837,6 +1987,10 @@ class SquareNNNModelMeasurementSolver {
     if constexpr (has_nnn_interaction) {
       out.push_back({"bond_energy_dr", "Bond energy on diagonal NNN bonds (LeftUp-RightDown)", {ly > 0 ? ly - 1 : 0, lx > 0 ? lx - 1 : 0}, {"bond_y", "bond_x"}});
       out.push_back({"bond_energy_ur", "Bond energy on anti-diagonal NNN bonds (LeftDown-RightUp)", {ly > 0 ? ly - 1 : 0, lx > 0 ? lx - 1 : 0}, {"bond_y", "bond_x"}});
+    }
+    if constexpr (HasSCMeasurement<ModelType>::value) {      // square_tJ_model.h:657-690
+      out.push_back({"SC_bond_singlet_h", "Bond singlet SC (horizontal) avg(conj(delta_dag), delta)", {ly, lx > 0 ? lx - 1 : 0}, {"bond_y", "bond_x"}});
+      out.push_back({"SC_bond_singlet_v", "Bond singlet SC (vertical) avg(conj(delta_dag), delta)", {ly > 0 ? ly - 1 : 0, lx}, {"bond_y", "bond_x"}});
     }
     return out;
   }
@@ -2409,16 +2563,24 @@ class SpinOneHalfTriJ1J2HeisenbergSqrPEPS : public SpinOneHalfMeasurementHooks {
 //   Local  the same contractions driven per plaquette from the host (PEPSHOST_NO_DEVICE_SWEEP=1);
 //   Fresh  one fresh batched contraction per diagonal (PEPSHOST_NNN_FRESH=1; the independent check).
 struct FermionNNNHop {
+  // bonds (optional, zero-filled by the caller): [walker][rows - 1][cols - 1][2] receives the term of every diagonal, entry 0
+  // LEFTUP_TO_RIGHTDOWN, entry 1 LEFTDOWN_TO_RIGHTUP (the measurement registry's bond_energy_dr / _ur)
   template <typename TenElemT>
-  static void Add(double t2, TPSWaveFunctionComponentT<TenElemT> &comp, std::vector<TenElemT> &energy) {
+  static void Add(double t2, TPSWaveFunctionComponentT<TenElemT> &comp, std::vector<TenElemT> &energy, std::vector<TenElemT> *bonds = nullptr) {
     static const bool fresh = getenv("PEPSHOST_NNN_FRESH") != nullptr;
     if (t2 == 0.0) return;
-    if (fresh) Fresh(t2, comp, energy);
-    else if (DeviceSlicesEnabled()) Slice(t2, comp, energy);
-    else Local(t2, comp, energy);
+    if (fresh) Fresh(t2, comp, energy, bonds);
+    else if (DeviceSlicesEnabled()) Slice(t2, comp, energy, bonds);
+    else Local(t2, comp, energy, bonds);
   }
   template <typename TenElemT>
-  static void Slice(double t2, TPSWaveFunctionComponentT<TenElemT> &comp, std::vector<TenElemT> &energy) {
+  static void Put(std::vector<TenElemT> &energy, std::vector<TenElemT> *bonds, size_t w, size_t rows, size_t cols, size_t row, size_t col,
+                  int diag, TenElemT e) {
+    energy[w] += e;
+    if (bonds) (*bonds)[((w * (rows - 1) + row) * (cols - 1) + col) * 2 + diag] = e;
+  }
+  template <typename TenElemT>
+  static void Slice(double t2, TPSWaveFunctionComponentT<TenElemT> &comp, std::vector<TenElemT> &energy, std::vector<TenElemT> *bonds = nullptr) {
     if (!comp.fermion) throw std::logic_error("fermionic NNN hopping needs the fermionic decoration of the component");
     const size_t n = comp.config.walkers(), rows = comp.config.rows(), cols = comp.config.cols();
     if (rows < 2 || cols < 2) return;
@@ -2438,7 +2600,8 @@ struct FermionNNNHop {
           const SiteIdx q[4] = {{row, col}, {row + 1, col}, {row + 1, col + 1}, {row, col + 1}};
           for (int diag = 0; diag < 2; ++diag)
             if (fd.n(comp.config(w, q[diag])) != fd.n(comp.config(w, q[diag + 2])))
-              energy[w] += TenElemT(-t2) * ComplexConjugate(TenElemT(val[(w * np + col) * 2 + diag] / psi[w * np + col]));   // :210 (jw applied on the device)
+              Put(energy, bonds, w, rows, cols, row, col, diag,
+                  TenElemT(TenElemT(-t2) * ComplexConjugate(TenElemT(val[(w * np + col) * 2 + diag] / psi[w * np + col]))));   // :210 (jw applied on the device)
         }
       if (row + 2 < rows) ct.ShiftBMPSWindow(DOWN);
     }
@@ -2451,7 +2614,7 @@ struct FermionNNNHop {
   // environments: the LEFT BTen2 grown with row r+1 under flipped variants, the RIGHT BTen2 with row r flipped (second BTen2 set +
   // slice override of the C ABI).  psi of the plaquette comes from the untwisted set along the same path.
   template <typename TenElemT>
-  static void Local(double t2, TPSWaveFunctionComponentT<TenElemT> &comp, std::vector<TenElemT> &energy) {
+  static void Local(double t2, TPSWaveFunctionComponentT<TenElemT> &comp, std::vector<TenElemT> &energy, std::vector<TenElemT> *bonds = nullptr) {
     if (!comp.fermion) throw std::logic_error("fermionic NNN hopping needs the fermionic decoration of the component");
     const size_t n = comp.config.walkers(), rows = comp.config.rows(), cols = comp.config.cols();
     if (rows < 2 || cols < 2) return;
@@ -2519,7 +2682,9 @@ struct FermionNNNHop {
           const std::vector<TenElemT> psi_ex = ct.ReplacePlaquetteTrace(q[0], 2, cand, 1, 1);
           for (size_t w = 0; w < n; ++w)
             for (int diag = 0; diag < 2; ++diag)
-              if (jw[w * 2 + diag] != 0.0) energy[w] += TenElemT(-t2 * jw[w * 2 + diag]) * ComplexConjugate(TenElemT(psi_ex[w * 2 + diag] / psi[w]));   // :210
+              if (jw[w * 2 + diag] != 0.0)
+                Put(energy, bonds, w, rows, cols, row, col, diag,
+                    TenElemT(TenElemT(-t2 * jw[w * 2 + diag]) * ComplexConjugate(TenElemT(psi_ex[w * 2 + diag] / psi[w]))));   // :210
         }
         if (col + 2 < cols) {      // both LEFT chains advance over column col (set 1 under the row+1 override)
           ct.GrowBTen2Step(LEFT, row);
@@ -2538,7 +2703,7 @@ struct FermionNNNHop {
   // sum over the plaquette diagonals of -t2 * jw * psi(S with the two sites exchanged) / psi(S); jw = (-1)^(fermions strictly
   // between the two sites in row-major order).  Leaves comp on its original configuration.
   template <typename TenElemT>
-  static void Fresh(double t2, TPSWaveFunctionComponentT<TenElemT> &comp, std::vector<TenElemT> &energy) {
+  static void Fresh(double t2, TPSWaveFunctionComponentT<TenElemT> &comp, std::vector<TenElemT> &energy, std::vector<TenElemT> *bonds = nullptr) {
     if (!comp.fermion) throw std::logic_error("fermionic NNN hopping needs the fermionic decoration of the component");
     const size_t n = comp.config.walkers(), rows = comp.config.rows(), cols = comp.config.cols();
     const Configuration orig = comp.config;
@@ -2560,7 +2725,8 @@ struct FermionNNNHop {
             if (comp.fermion->n(orig(w, a)) == comp.fermion->n(orig(w, b))) continue;
             int between = 0;
             for (size_t q = ia + 1; q < ib; ++q) between += comp.fermion->n(orig(w, {q / cols, q % cols}));
-            energy[w] += TenElemT(-t2 * ((between & 1) ? -1.0 : 1.0)) * ComplexConjugate(TenElemT(comp.amplitude[w] / psi0[w]));
+            Put(energy, bonds, w, rows, cols, row, col, diag,
+                TenElemT(TenElemT(-t2 * ((between & 1) ? -1.0 : 1.0)) * ComplexConjugate(TenElemT(comp.amplitude[w] / psi0[w]))));
           }
         }
     comp.ReplaceGlobalConfig(orig);
@@ -2570,8 +2736,17 @@ struct FermionNNNHop {
 // square_spinless_fermion.h:51-200: H = -t sum_<ij> (c+_i c_j + h.c.) - t2 sum_<<ij>> (c+_i c_j + h.c.) + V sum_<ij> n_i n_j.
 // psi is recomputed with Trace next to psi' (same contraction path, docs/dev/design/math/
 // fermion-sign-in-bmps-contraction.md), the bosonic inv_psi argument is unused.  NNN hopping (:161-200): FermionNNNHop above.
-class SquareSpinlessFermion : public SquareNNModelEnergySolver<SquareSpinlessFermion> {
+class SquareSpinlessFermion : public SquareNNModelEnergySolver<SquareSpinlessFermion>,
+                              public SquareNNNModelMeasurementSolver<SquareSpinlessFermion> {
  public:
+  static constexpr bool kFermionicModel = true;
+  static constexpr bool requires_density_measurement = true;   // :55-56
+  static constexpr bool requires_spin_sz_measurement = false;
+  // the diagonal hops of the measurement registry: added to `energy`, per diagonal into `bonds` (FermionNNNHop)
+  template <typename TenElemT>
+  void FermionNNNBondEnergies(TPSWaveFunctionComponentT<TenElemT> &comp, std::vector<TenElemT> &energy, std::vector<TenElemT> *bonds) const {
+    FermionNNNHop::Add(t2_, comp, energy, bonds);
+  }
   SquareSpinlessFermion(double t, double V) : t_(t), t2_(0.0), V_(V) {}
   SquareSpinlessFermion(double t, double t2, double V) : t_(t), t2_(t2), V_(V) {}
   template <bool calchols = true, typename TenElemT = double>
@@ -2620,8 +2795,75 @@ class SquareSpinlessFermion : public SquareNNModelEnergySolver<SquareSpinlessFer
 // square_tJ_model.h:301-345 (SquaretJModelMixIn::EvaluateBondEnergy) + :215-228: states 0 up, 1 down, 2 empty
 // (vmc_basic/tj_single_site_state.h:19-23); H = -t sum (c+ c + h.c.) + J sum (S.S - n n / 4) + V sum n n - mu N.
 // NNN hopping t2 (:424-463): FermionNNNHop above.
-class SquaretJVModel : public SquareNNModelEnergySolver<SquaretJVModel> {
+// Measurement (:546-603, :657-850): the registry of the diagonal-bond traversal with spin_z, charge and the bond-singlet pairing order
+//   Delta+_ij = (c+_i,up c+_j,down - c+_i,down c+_j,up) / sqrt(2)   on the NN bond with i the left / upper, j the right / lower site,
+// in the basis |S> = product of c+ over the occupied sites in row-major order.  SC_singlet_pair_corr is not built.
+class SquaretJVModel : public SquareNNModelEnergySolver<SquaretJVModel>, public SquareNNNModelMeasurementSolver<SquaretJVModel> {
  public:
+  static constexpr bool kFermionicModel = true;
+  static constexpr bool requires_spin_sz_measurement = true;
+  static constexpr bool requires_density_measurement = true;
+  static constexpr bool enable_sc_measurement = true;
+  double CalSpinSzImpl(int32_t config) const { return config == 0 ? 0.5 : (config == 1 ? -0.5 : 0.0); }
+  double CalDensityImpl(int32_t config) const { return config == 2 ? 0.0 : 1.0; }
+  template <typename TenElemT>
+  void FermionNNNBondEnergies(TPSWaveFunctionComponentT<TenElemT> &comp, std::vector<TenElemT> &energy, std::vector<TenElemT> *bonds) const {
+    FermionNNNHop::Add(t2_, comp, energy, bonds);
+  }
+  // The configurations a pair operator connects the states (a, b) of a bond to, [3 * 3][2][2] over physical states ((-1, -1): none):
+  // (empty, empty) -> (up, down), (down, up);  (up, down) and (down, up) -> (empty, empty).  The pair table of
+  // pepsgpu_nn_pair_slice_fermion.
+  static std::vector<int32_t> PairTable() {
+    std::vector<int32_t> tab(9 * 4, -1);
+    auto set = [&](int a, int b, int k, int pa, int pb) { tab[((a * 3 + b) * 2 + k) * 2] = pa; tab[((a * 3 + b) * 2 + k) * 2 + 1] = pb; };
+    set(2, 2, 0, 0, 1);
+    set(2, 2, 1, 1, 0);
+    set(0, 1, 0, 2, 2);
+    set(1, 0, 0, 2, 2);
+    return tab;
+  }
+  // (delta_dag, delta) of one bond (:569-602) from rho_k = jw psi(S'_k) / psi(S) of its two candidates of PairTable
+  template <typename TenElemT>
+  static std::pair<TenElemT, TenElemT> BondSCFromPairs(int32_t c1, int32_t c2, TenElemT rho0, TenElemT rho1) {
+    const double isq2 = 1.0 / std::sqrt(2.0);
+    if (c1 == 2 && c2 == 2) return {TenElemT(ComplexConjugate(TenElemT(rho0 - rho1)) * isq2), TenElemT(0.0)};
+    if (c1 == 0 && c2 == 1) return {TenElemT(0.0), TenElemT(ComplexConjugate(rho0) * isq2)};
+    if (c1 == 1 && c2 == 0) return {TenElemT(0.0), TenElemT(-ComplexConjugate(rho0) * isq2)};
+    return {TenElemT(0.0), TenElemT(0.0)};
+  }
+  // EvaluateBondSC (:195-212): Trace + ONE ReplaceNNSiteTrace over the two candidates of the bond.  The ratio of the decorated
+  // contractions misses Sigma(S') / Sigma(S), which is -1 for a candidate that changes the electron number by +-2.
+  template <typename TenElemT>
+  std::vector<std::pair<TenElemT, TenElemT>> EvaluateBondSC(const SiteIdx &s1, const SiteIdx &s2, BondOrientation orient,
+                                                            TPSWaveFunctionComponentT<TenElemT> &comp) const {
+    const size_t n = comp.config.walkers();
+    const FermionDecoration &fd = *comp.fermion;
+    const std::vector<int32_t> tab = PairTable();
+    std::vector<int32_t> cand(n * 4);
+    std::vector<int> sign(n * 2, 0);
+    bool any = false;
+    for (size_t w = 0; w < n; ++w) {
+      const int32_t c1 = comp.config(w, s1), c2 = comp.config(w, s2);
+      for (int k = 0; k < 2; ++k) {
+        const int32_t pa = tab[((c1 * 3 + c2) * 2 + k) * 2], pb = tab[((c1 * 3 + c2) * 2 + k) * 2 + 1];
+        cand[(w * 2 + k) * 2] = pa < 0 ? c1 : pa;
+        cand[(w * 2 + k) * 2 + 1] = pa < 0 ? c2 : pb;
+        if (pa >= 0) { sign[w * 2 + k] = fd.n(pa) + fd.n(pb) == fd.n(c1) + fd.n(c2) ? 1 : -1; any = true; }
+      }
+    }
+    std::vector<std::pair<TenElemT, TenElemT>> out(n, {TenElemT(0.0), TenElemT(0.0)});
+    if (!any) return out;
+    const std::vector<TenElemT> psi = comp.contractor.Trace(s1, orient);
+    const std::vector<TenElemT> psi_ex = comp.ReplaceNNSiteTrace(s1, s2, orient, 2, cand);
+    for (size_t w = 0; w < n; ++w) {
+      if (sign[w * 2] == 0 && sign[w * 2 + 1] == 0) continue;
+      if (psi[w] == TenElemT(0.0)) throw std::runtime_error("EvaluateBondSingletPairFortJModel: psi is zero.");
+      TenElemT rho[2];
+      for (int k = 0; k < 2; ++k) rho[k] = sign[w * 2 + k] ? TenElemT(double(sign[w * 2 + k]) * psi_ex[w * 2 + k] / psi[w]) : TenElemT(0.0);
+      out[w] = BondSCFromPairs(comp.config(w, s1), comp.config(w, s2), rho[0], rho[1]);
+    }
+    return out;
+  }
   SquaretJVModel(double t, double t2, double J, double V, double mu) : t_(t), t2_(t2), J_(J), V_(V), mu_(mu) {}
   template <bool calchols = true, typename TenElemT = double>
   EnergyAndHolesT<TenElemT> CalEnergyAndHoles(const SplitIndexTPST<TenElemT> &sitps, TPSWaveFunctionComponentT<TenElemT> &comp,
@@ -2675,8 +2917,13 @@ class SquaretJVModel : public SquareNNModelEnergySolver<SquaretJVModel> {
   double t_, t2_, J_, V_, mu_;
 };
 // square_tJ_model.h:613-705: the named models hand V = 0 (and SquaretJNNModel t2 = 0) to the mix-in
-class SquaretJNNModel : public SquaretJVModel {
+// (SquaretJNNModel measures with the nearest-neighbour form, :613-705: no diagonal-bond keys)
+class SquaretJNNModel : public SquaretJVModel, public SquareNNModelMeasurementSolver<SquaretJNNModel> {
  public:
+  using SquareNNModelMeasurementSolver<SquaretJNNModel>::EvaluateObservables;
+  using SquareNNModelMeasurementSolver<SquaretJNNModel>::EvaluatePsiSummary;
+  using SquareNNModelMeasurementSolver<SquaretJNNModel>::EvaluatePsiSummaryT;
+  using SquareNNModelMeasurementSolver<SquaretJNNModel>::DescribeObservables;
   SquaretJNNModel(double t, double J, double mu) : SquaretJVModel(t, 0.0, J, 0.0, mu) {}
 };
 class SquaretJNNNModel : public SquaretJVModel {
@@ -3071,6 +3318,9 @@ class MonteCarloEngine {
 // ranks of other GPUs are merged by the caller from Partial()).
 struct MCMeasurementParams {                       // MonteCarloParams (monte_carlo_peps_params.h)
   size_t num_samples = 1, num_warmup_sweeps = 0, sweeps_between_samples = 1;
+  // false: the warm-up is the plain sweeps followed by a fresh amplitude, without NormalizeStateOrder1's rescaling of the state -- the
+  // chain and the sampled ratios are then those of a caller that sweeps and evaluates by hand (pepshost_fermion_measure_energy)
+  bool normalize_state = true;
 };
 template <class MonteCarloSweepUpdater, class MeasurementSolver, typename TenElemT = double>
 class MCPEPSMeasurer {
@@ -3089,6 +3339,14 @@ class MCPEPSMeasurer {
     // engine_.WarmUp() (monte_carlo_engine.h:146-173): the warm-up sweeps, the amplitude sanity check and NormalizeStateOrder1 -- the
     // measurer's own copy of the state is rescaled to max_w |psi_w| = 1 and the components are rebuilt.  Ratios do not see it; the
     // structure-factor amplitudes (SpSm_cross) do, and the reference's regression vector (K8) is taken after it.
+    if (!params_.normalize_state) {
+      std::vector<double> rates;
+      for (size_t s = 0; s < params_.num_warmup_sweeps; ++s) updater_(sitps_, comp_, rates);
+      comp_.SetOrder(ROW_MAJOR);
+      comp_.EvaluateAmplitude();
+      Measure_();
+      return;
+    }
     MonteCarloParams mc;
     mc.num_warmup_sweeps = params_.num_warmup_sweeps;
     mc.sweeps_between_samples = params_.sweeps_between_samples;
@@ -3108,6 +3366,8 @@ class MCPEPSMeasurer {
     return {e.first[0], e.second.empty() ? 0.0 : e.second[0]};
   }
   const std::vector<double> &AcceptRates() const { return accept_avg_; }
+  // energy_samples[sample][walker]: the "energy" key of every sample (empty when the solver reports none)
+  const std::vector<std::vector<TenElemT>> &EnergySamples() const { return energy_samples_; }
   // psi_samples[sample][walker] = (psi_mean, psi_rel_err)
   const std::vector<std::vector<std::pair<TenElemT, double>>> &PsiSamples() const { return psi_samples_; }
   // stats/<key>_mean.csv + <key>_stderr.csv for two-dimensional observables, stats/<key>.csv ("index,mean,stderr") otherwise,
@@ -3171,6 +3431,7 @@ class MCPEPSMeasurer {
       }
       for (size_t w = 0; w < n; ++w) accept_avg_[w] += acc[w] / double(std::max<size_t>(params_.sweeps_between_samples, 1));
       ObservableMapT<TenElemT> obs = solver_.EvaluateObservables(sitps_, comp_);  // MeasureSample_ (:193-238)
+      if (obs.values.count("energy")) energy_samples_.push_back(obs.values.at("energy"));
       for (const auto &kv : obs.values) {
         auto &dst = sum[kv.first];
         if (dst.empty()) dst.assign(kv.second.size(), TenElemT(0.0));
@@ -3213,6 +3474,7 @@ class MCPEPSMeasurer {
   std::map<std::string, std::pair<std::vector<TenElemT>, std::vector<double>>> registry_stats_;
   std::map<std::string, std::vector<TenElemT>> walker_means_;
   std::vector<std::vector<std::pair<TenElemT, double>>> psi_samples_;
+  std::vector<std::vector<TenElemT>> energy_samples_;
   std::vector<double> accept_avg_;
 };
 
@@ -3246,7 +3508,7 @@ template <typename MeasurementSolverT, typename TenElemT>
 std::map<std::string, std::vector<TenElemT>> ExactSumMeasurer(const SplitIndexTPST<TenElemT> &sitps, const std::vector<std::vector<int32_t>> &all_configs,
                                                               BMPSContractorT<TenElemT> &contractor, MeasurementSolverT &solver, int rank, int size,
                                                               size_t batch, const std::function<void(std::vector<double> &)> &allreduce,
-                                                              double *weight_sum_out = nullptr) {
+                                                              double *weight_sum_out = nullptr, const FermionDecoration *fermion = nullptr) {
   if (all_configs.empty()) throw std::invalid_argument("ExactSumMeasurerMPI: all_configs must not be empty");     // :113-115
   const size_t rows = sitps.rows(), cols = sitps.cols();
   double weight_rank = 0.0;
@@ -3262,7 +3524,7 @@ std::map<std::string, std::vector<TenElemT>> ExactSumMeasurer(const SplitIndexTP
     const size_t nb = std::min(batch, mine.size() - b0);
     Configuration cfg(nb, rows, cols);
     for (size_t w = 0; w < nb; ++w) std::copy(all_configs[mine[b0 + w]].begin(), all_configs[mine[b0 + w]].end(), cfg.data() + w * rows * cols);
-    TPSWaveFunctionComponentT<TenElemT> comp(sitps, cfg, contractor);
+    TPSWaveFunctionComponentT<TenElemT> comp(sitps, cfg, contractor, fermion);
     const std::vector<TenElemT> psi = comp.amplitude;          // the solver's passes may touch comp
     ObservableMapT<TenElemT> obs = solver.EvaluateObservables(sitps, comp);
     for (size_t w = 0; w < nb; ++w) weight_rank += std::norm(psi[w]);                                              // :135-136

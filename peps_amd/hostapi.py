@@ -22,7 +22,8 @@ SYMBOLS = ["pepshost_last_error", "pepshost_mc_sweeps", "pepshost_energy_and_hol
            "pepshost_optimize_exact_sum", "pepshost_optimize_exact_sum_c128", "pepshost_lr_schedule",
            "pepshost_sr_step_samples", "pepshost_sr_step_samples_c128",
            "pepshost_fermion_optimize_exact_sum", "pepshost_fermion_optimize_exact_sum_c128",
-           "pepshost_fermion_sr_step_samples", "pepshost_fermion_sr_step_samples_c128", "pepshost_fermion_exact_sum_partial_prm"]
+           "pepshost_fermion_sr_step_samples", "pepshost_fermion_sr_step_samples_c128", "pepshost_fermion_exact_sum_partial_prm",
+           "pepshost_fermion_observables", "pepshost_fermion_exact_sum_measure_partial", "pepshost_fermion_measure"]
 
 _lib = None
 _C128 = 3                                   # PEPSGPU_C128 (include/pepsgpu.h)
@@ -547,6 +548,86 @@ def fermion_exact_sum(state, all_configs, chi, t, V=0.0, batch=64, dtype=1, mode
 
 
 FERMION_MODEL_ID = {"spinless": 0, "tj": 1}   # params: spinless (t, V, t2); tj (t, J, V, mu[, t2]) -- as fermion_energy passes them
+# the measurement entries also know SquaretJNNModel, the nearest-neighbour form of the registry: tjnn (t, J, mu)
+FERMION_MEASURE_MODEL_ID = {"spinless": 0, "tj": 1, "tjnn": 2}
+
+
+def _fermion_measure_head(state, chi, model, params, dtype):
+    """(is complex, leading arguments rows .. flat of the fermionic measurement shims, the arrays that must stay alive)"""
+    cplx = state.is_complex
+    flat = np.ascontiguousarray(state.extended_flat(), dtype=np.complex128 if cplx else np.float64)
+    rows, cols, D = flat.shape[0], flat.shape[1], flat.shape[3]
+    nf = np.ascontiguousarray(state.nf, dtype=np.int32)
+    prm = np.array([float(x) for x in params], dtype=np.float64)
+    head = (rows, cols, D, state.d, _p(nf, C.c_int32), chi, _C128 if cplx else dtype, _cp(flat))
+    return cplx, head, (FERMION_MEASURE_MODEL_ID[model], prm.size, _p(prm, C.c_double)), (flat, nf, prm)
+
+
+def _keyed(keys, vals, cplx):
+    """[(key, len)] and the value array (complex: every number a (re, im) pair) of an output in the format of pepshost_measure"""
+    items = [(k, int(ln)) for k, ln in (item.split(":") for item in filter(None, keys.value.decode().split(";")))]
+    return items, (vals.view(np.complex128) if cplx else vals)
+
+
+def fermion_observables(state, configs, chi, model="tj", params=(1.0, 0.3, 0.0, 0.0), dtype=1):
+    """Registry of the C++ measurement solver of a fermionic model (SquareNNNModelMeasurementSolver on SquareSpinlessFermion /
+    SquaretJVModel / SquaretJNNModel) on a batch of configurations: dict key -> [walker][len] with energy, charge, bond_energy_h / _v
+    (/ _dr / _ur) and, for the t-J models, spin_z and the bond-singlet pairing order SC_bond_singlet_h / _v; and the psi summary
+    (psi_mean [walker], psi_rel_err [walker]).  params: spinless (t, V, t2), tj (t, J, V, mu, t2), tjnn (t, J, mu)."""
+    cplx, head, tail, keep = _fermion_measure_head(state, chi, model, params, dtype)
+    cfg = np.ascontiguousarray(configs, dtype=np.int32)
+    n, sites = cfg.shape[0], cfg.shape[1] * cfg.shape[2]
+    cap = 2 * (16 * n * sites + 4096)
+    vals, keys, nvals = np.zeros(cap, dtype=np.float64), C.create_string_buffer(4096), C.c_long(0)
+    _ck(lib().pepshost_fermion_observables(*head, n, _p(cfg, C.c_int32), *tail, keys, 4096, _p(vals, C.c_double),
+                                           C.c_long(cap), C.byref(nvals)))
+    items, v = _keyed(keys, vals[:nvals.value], cplx)
+    out, off = {}, 0
+    for key, ln in items:
+        out[key] = v[off:off + n * ln].reshape(n, ln).copy()
+        off += n * ln
+    return out, (v[off:off + n].copy(), np.real(v[off + n:off + 2 * n]).copy())
+
+
+def fermion_exact_sum_measure(state, all_configs, chi, model="tj", params=(1.0, 0.3, 0.0, 0.0), rank=0, size=1, batch=64, dtype=1):
+    """Rank-local part of ExactSumMeasurerMPI on a fermionic state through the C++ measurement solver: (dict key ->
+    sum_S |psi(S)|^2 O_loc(S), sum_S |psi(S)|^2) over the configurations rank, rank + size, ...; sum both over the ranks and divide.
+    Every configuration must have a non-zero amplitude (hand over the parity-allowed ones)."""
+    cplx, head, tail, keep = _fermion_measure_head(state, chi, model, params, dtype)
+    cfg = np.ascontiguousarray(all_configs, dtype=np.int32)
+    cap = 2 * (16 * cfg.shape[1] * cfg.shape[2] + 4096)
+    vals, keys, nvals = np.zeros(cap, dtype=np.float64), C.create_string_buffer(4096), C.c_long(0)
+    _ck(lib().pepshost_fermion_exact_sum_measure_partial(*head, _p(cfg, C.c_int32), cfg.shape[0], *tail, rank, size, batch,
+                                                         keys, 4096, _p(vals, C.c_double), C.c_long(cap), C.byref(nvals)))
+    items, _ = _keyed(keys, vals, False)
+    out, off, z = {}, 1, 2 if cplx else 1
+    for key, ln in items:
+        seg = vals[off:off + z * ln].copy()
+        out[key] = seg.view(np.complex128) if cplx else seg
+        off += z * ln
+    return out, float(vals[0])
+
+
+def fermion_measure(state, configs, seeds, chi, warmup_sweeps, n_samples, sweeps_between=1, model="tj", params=(1.0, 0.3, 0.0, 0.0), dtype=1):
+    """MCPEPSMeasurer with the exchange updater on a fermionic state: dict key -> (mean [len], stderr [len]) across the walkers, the psi
+    summary of the last sample, the energy samples [sample][walker], the final configurations and the accept rates.  Warm-up, samples
+    and ONE std::mt19937 stream per walker as fermion_measure_energy: the energy samples are the numbers that call returns."""
+    cplx, head, tail, keep = _fermion_measure_head(state, chi, model, params, dtype)
+    cfg = np.ascontiguousarray(configs, dtype=np.int32).copy()
+    n, sites = cfg.shape[0], cfg.shape[1] * cfg.shape[2]
+    sd = np.ascontiguousarray(seeds, dtype=np.uint64)
+    cap = 2 * (32 * sites + 2 * n + 4096)
+    vals, keys, nvals = np.zeros(cap, dtype=np.float64), C.create_string_buffer(4096), C.c_long(0)
+    en, rates = np.zeros((n_samples, n), np.complex128 if cplx else np.float64), np.zeros(n)
+    _ck(lib().pepshost_fermion_measure(*head, n, _p(cfg, C.c_int32), _p(sd, C.c_uint64), warmup_sweeps, n_samples,
+                                       sweeps_between, *tail, keys, 4096, _p(vals, C.c_double), C.c_long(cap), C.byref(nvals), _cp(en),
+                                       _p(rates, C.c_double)))
+    items, v = _keyed(keys, vals[:nvals.value], cplx)
+    out, off = {}, 0
+    for key, ln in items:
+        out[key] = (v[off:off + ln].copy(), np.real(v[off + ln:off + 2 * ln]).copy())
+        off += 2 * ln
+    return out, (v[off:off + n].copy(), np.real(v[off + n:off + 2 * n]).copy()), en, cfg, rates
 
 
 def _fermion_head(state, dtype):

@@ -36,7 +36,8 @@ enum {
   PEPSGPU_EHIP = 2,       /* device/runtime failure */
   PEPSGPU_ESTATE = 3,     /* std::logic_error: environment / parameters not ready */
   PEPSGPU_ERANGE = 4,     /* std::out_of_range: configuration value >= physical dim */
-  PEPSGPU_EEMPTY = 5      /* std::runtime_error: empty (zero) tensor, bmps_impl.h:839-843 */
+  PEPSGPU_EEMPTY = 5,     /* std::runtime_error: empty (zero) tensor, bmps_impl.h:839-843 */
+  PEPSGPU_ENOCONV = 6     /* the Jacobi eigensolver of pepsgpu_minsr_direction / pepsgpu_diag_eigh reached its sweep cap */
 };
 /* element type of the device tensors (TenElemT of the reference: QLTEN_Double, QLTEN_Complex).  PEPSGPU_C128 = complex
  * float64 (std::complex<double> layout, interleaved re / im).  For a complex context EVERY scalar or tensor the calls
@@ -542,6 +543,37 @@ int pepsgpu_opt_step(pepsgpu_ctx *ctx, int rule, double lr, const double *params
 int pepsgpu_opt_scale_state(pepsgpu_ctx *ctx, double factor);
 int pepsgpu_opt_read_state(pepsgpu_ctx *ctx, double *host);
 int pepsgpu_fermion_decoration_set(pepsgpu_ctx *ctx, int d, const int32_t *nf, const uint8_t *bond_parity);
+
+/* MinSR inside the device-resident optimizer: Optimizer::CalculateMinSRDirection_ on one rank (optimizer/optimizer_impl.h:1126-1215,
+ * minsr_tmatrix.h:53-147, minsr_eigensolve.h:44-155; parameters = MinSRParams, optimizer_params.h:220-232).  With Ns = pepsgpu_sr_count
+ * samples in the store, everything that scales with Ns^2 or with the parameter count stays in HBM:
+ *   1  raw Gram of the resident O* store (the GEMM of pepsgpu_sr_gram, f64 sums, summed and mirrored on the device);
+ *   2  T_ij = (G_ij - m_i - conj(m_j) + c) / Ns, m_i = sum_j G_ij / Ns, c = sum_i m_i / Ns (minsr_tmatrix.h:141-147);
+ *   3  T = Z diag(w) Z^H by a two-sided parallel Jacobi method in HBM (csrc/eigh_jacobi.h; float64 or complex whatever the context);
+ *   4  ApplyPseudoInverseCutoff (minsr_eigensolve.h:44-78): cutoff = r_pinv max|w| + a_pinv; soft_cutoff != 0: f = w^5 / (w^6 + cutoff^6),
+ *      0 where the denominator is 0; else f = 1 / w where |w| > cutoff, 0 elsewhere;
+ *   5  y = Z f(w) Z^H eps_bar, eps_bar_i = conj(E_i - E) / Ns (optimizer_impl.h:1139-1146);
+ *   6  g <- sum_i y_i O*_i - (sum_i y_i) (sum_i O*_i) / Ns into the optimizer's direction buffer (the kernels of
+ *      pepsgpu_sr_weighted_sum / pepsgpu_sr_sum, device to device);
+ *   7  direction_norm_out (nullable) = sqrt(sum |g|^2), the two-stage fixed-order sum of the optimizer.
+ * eloc = the Ns local energies in the order the samples were appended (Ns doubles, 2 Ns interleaved on a PEPSGPU_C128 context), energy
+ * = their mean (1 or 2 doubles).  info_out (nullable, 4 doubles) = [max|w|, cutoff, number of eigenvalues with |w| > cutoff, Jacobi
+ * sweeps].  pepsgpu_opt_step(ctx, 0, lr, {0, 0, 0}, 3) then applies theta -= lr g, as for the SR step.  Works on PEPSGPU_F32, F64 and C128
+ * contexts (the store has the context's dtype).  The scratch (T and Z: 2 Ns^2 doubles, twice that on a complex context) is allocated on
+ * first use and freed by pepsgpu_opt_end or with the context.
+ * Status: PEPSGPU_ESTATE before pepsgpu_opt_begin or with an empty sample store; PEPSGPU_EINVAL for a NULL eloc / energy, a non-finite
+ * or negative r_pinv / a_pinv, a non-finite energy or local energy, or when a fermionic decoration is set (T in the stored parameters
+ * under the decoration is a follow-up, as is the multi-rank T matrix: peps_amd/sr.py stays the multi-rank path); PEPSGPU_ENOCONV when the
+ * eigensolver reaches its cap of 30 sweeps.  A refused call leaves g, theta and the device state untouched.
+ * The prefix is not pepsgpu_opt_: the set of pepsgpu_opt_* entries is closed.
+ *
+ * pepsgpu_diag_eigh runs the eigensolver alone on the context's device: a = n x n row-major host matrix, real symmetric or (is_complex
+ * != 0, interleaved pairs) complex Hermitian; w_out[n] ascending, z_out = n x n row-major with the eigenvector of w[k] in column k,
+ * sweeps_out (nullable) = sweeps run, the closing one that rotated nothing included.  PEPSGPU_EINVAL: n < 1, a NULL buffer, a
+ * non-finite entry; PEPSGPU_ENOCONV at the sweep cap (the outputs then hold the state reached). */
+int pepsgpu_minsr_direction(pepsgpu_ctx *ctx, const double *eloc, const double *energy, double r_pinv, double a_pinv, int soft_cutoff,
+                            double *direction_norm_out, double *info_out);
+int pepsgpu_diag_eigh(pepsgpu_ctx *ctx, int n, int is_complex, const double *a, double *w_out, double *z_out, int *sweeps_out);
 
 /* TPSWaveFunctionComponent::UpdateLocal (wave_function_component.h:345-378) for the walkers with
  * accept_mask[w] != 0 (NULL = all): config(site_k) = new_states[w][k], tn.UpdateSiteTensor,

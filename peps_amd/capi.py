@@ -43,7 +43,7 @@ SYMBOLS = [
     "pepsgpu_sr_cg_solve", "pepsgpu_sr_gram", "pepsgpu_sr_weighted_sum", "pepsgpu_sr_copy_samples",
     "pepsgpu_opt_begin", "pepsgpu_opt_end", "pepsgpu_opt_gradient_from_accumulators", "pepsgpu_opt_set_gradient",
     "pepsgpu_opt_get_gradient", "pepsgpu_opt_clip", "pepsgpu_opt_natural_gradient", "pepsgpu_opt_step", "pepsgpu_opt_scale_state",
-    "pepsgpu_opt_read_state", "pepsgpu_fermion_decoration_set",
+    "pepsgpu_opt_read_state", "pepsgpu_fermion_decoration_set", "pepsgpu_minsr_direction", "pepsgpu_diag_eigh",
     "pepsgpu_update_local", "pepsgpu_erase_envs_after_update", "pepsgpu_evaluate_amplitude",
     "pepsgpu_walker_flags", "pepsgpu_sync", "pepsgpu_stats", "pepsgpu_profile_enable", "pepsgpu_profile_read",
     "pepsgpu_diag_tgemm", "pepsgpu_diag_tgemm_desc", "pepsgpu_diag_tgemm_route", "pepsgpu_diag_tgemm_chain", "pepsgpu_diag_tgemm_chain3", "pepsgpu_diag_chol", "pepsgpu_diag_chol_adaptive", "pepsgpu_diag_chol_pivot", "pepsgpu_diag_rows_qr", "pepsgpu_diag_suwa_todo", "pepsgpu_diag_dot4", "pepsgpu_diag_gram_chol", "pepsgpu_diag_gram_chol_wave", "pepsgpu_diag_gram_cols", "pepsgpu_diag_gram_rows", "pepsgpu_diag_mgemm_dense", "pepsgpu_diag_jacobi", "pepsgpu_diag_trunc_rows", "pepsgpu_version",
@@ -169,6 +169,9 @@ def load_library(path=LIB_PATH):
         lib.pepsgpu_opt_read_state.argtypes = [vp, dp]
     if hasattr(lib, "pepsgpu_fermion_decoration_set"):
         lib.pepsgpu_fermion_decoration_set.argtypes = [vp, C.c_int, ip, C.POINTER(C.c_uint8)]
+    if hasattr(lib, "pepsgpu_minsr_direction"):     # (PEPSGPU_LIB may name a build from before these entries)
+        lib.pepsgpu_minsr_direction.argtypes = [vp, dp, dp, C.c_double, C.c_double, C.c_int, dp, dp]
+        lib.pepsgpu_diag_eigh.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, ip]
     lib.pepsgpu_update_local.argtypes = [vp, C.c_int, ip, ip, C.POINTER(C.c_uint8)]
     lib.pepsgpu_erase_envs_after_update.argtypes = [vp, C.c_int, C.c_int]
     lib.pepsgpu_evaluate_amplitude.argtypes = [vp, dp]
@@ -667,6 +670,34 @@ class Context:
         out = np.zeros(self._state_shape(), dtype=self._ot)
         self._ck(self._l.pepsgpu_opt_read_state(self._h, _dp(out)))
         return out
+
+    def minsr_direction(self, eloc, energy, r_pinv=1e-12, a_pinv=0.0, soft_cutoff=True):
+        """g <- the MinSR direction of the resident sample store (Gram, centering, eigensolve, cutoff, back-substitution: all on the
+        device); `eloc` = the local energies in the order of the store, `energy` = their mean.  Returns (|g|, dict with lambda_max,
+        cutoff, n_kept, sweeps).  pepsgpu_opt_step with rule 0 applies it."""
+        e = np.ascontiguousarray(eloc, dtype=self._ot).ravel()
+        if self.sr_count() > 0 and e.size != self.sr_count():      # (an empty store is refused by the library)
+            raise ValueError("one local energy per stored sample (%d), got %d" % (self.sr_count(), e.size))
+        en = np.ascontiguousarray([energy], dtype=self._ot)
+        nrm = np.zeros(1, dtype=np.float64)
+        info = np.zeros(4, dtype=np.float64)
+        self._ck(self._l.pepsgpu_minsr_direction(self._h, _dp(e), _dp(en), float(r_pinv), float(a_pinv), int(bool(soft_cutoff)),
+                                                 _dp(nrm), _dp(info)))
+        return float(nrm[0]), {"lambda_max": float(info[0]), "cutoff": float(info[1]), "n_kept": int(info[2]), "sweeps": int(info[3])}
+
+    def diag_eigh(self, a):
+        """the device eigensolver alone: a real symmetric or complex Hermitian matrix -> (w ascending, z with A z[:, k] = w[k] z[:, k],
+        Jacobi sweeps)"""
+        cplx = np.iscomplexobj(a)
+        a = np.ascontiguousarray(a, dtype=np.complex128 if cplx else np.float64)
+        if a.ndim != 2 or a.shape[0] != a.shape[1]:
+            raise ValueError("a square matrix")
+        n = a.shape[0]
+        w = np.zeros(n, dtype=np.float64)
+        z = np.zeros((n, n), dtype=a.dtype)
+        sw = np.zeros(1, dtype=np.int32)
+        self._ck(self._l.pepsgpu_diag_eigh(self._h, n, int(cplx), _dp(a), _dp(w), _dp(z), _ip(sw)))
+        return w, z, int(sw[0])
 
     def fermion_decoration_set(self, state):
         """Tells the optimizer calls that the context holds the decorated components of `state` (a fermion.FermionState; the

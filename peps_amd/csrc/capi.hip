@@ -64,6 +64,27 @@ struct DevBufs {     // device allocations of one diagnostic call, freed on ever
   ~DevBufs() { for (void *q : p) (void)hipFree(q); }
 };
 
+static void diag_eigh_impl(hipStream_t s, int n, int is_complex, const double *a, double *w_out, double *z_out, int *sweeps_out) {
+  PG_REQUIRE(n >= 1 && a && w_out && z_out, 1, "diag_eigh: n < 1 or a null buffer");
+  const int Z = is_complex ? 2 : 1;
+  const size_t nn = (size_t)n * n * Z;
+  for (size_t e = 0; e < nn; ++e) PG_REQUIRE(std::isfinite(a[e]), 1, "diag_eigh: non-finite input");
+  DevBufs bufs;
+  double *da = bufs.alloc<double>(nn, a), *dv = bufs.alloc<double>(nn), *dw = bufs.alloc<double>(n);
+  double *work = bufs.alloc<double>(eigh_work_doubles(n));
+  int sweeps = 0;
+  const bool converged = eigh_jacobi(s, n, is_complex != 0, da, dv, dw, work, &sweeps);
+  PG_CHECK_HIP(hipStreamSynchronize(s));
+  if (sweeps_out) *sweeps_out = sweeps;
+  std::vector<double> zt(nn);
+  PG_CHECK_HIP(hipMemcpy(zt.data(), da, nn * sizeof(double), hipMemcpyDeviceToHost));
+  PG_CHECK_HIP(hipMemcpy(w_out, dw, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  for (int r = 0; r < n; ++r)          // the device keeps Z^T: row k = the eigenvector of w[k]
+    for (int k = 0; k < n; ++k)
+      for (int z = 0; z < Z; ++z) z_out[Z * ((size_t)r * n + k) + z] = zt[Z * ((size_t)k * n + r) + z];
+  if (!converged) throw Error(PEPSGPU_ENOCONV, "diag_eigh: the Jacobi eigensolver reached its sweep cap");
+}
+
 extern "C" {
 
 const char *pepsgpu_version(void) { return "pepsgpu 0.1 (gfx950)"; }
@@ -506,6 +527,14 @@ int pepsgpu_opt_step(pepsgpu_ctx *ctx, int rule, double lr, const double *params
 int pepsgpu_opt_scale_state(pepsgpu_ctx *ctx, double factor) { CTX_CALL(ctx->eng->opt_scale_state(factor)); }
 int pepsgpu_opt_read_state(pepsgpu_ctx *ctx, double *host) {
   CTX_CALL(PG_REQUIRE(host != nullptr, 1, "null output"); ctx->eng->opt_read_state(host));
+}
+int pepsgpu_minsr_direction(pepsgpu_ctx *ctx, const double *eloc, const double *energy, double r_pinv, double a_pinv, int soft_cutoff,
+                            double *direction_norm_out, double *info_out) {
+  CTX_CALL(ctx->eng->minsr_direction(eloc, energy, r_pinv, a_pinv, soft_cutoff, direction_norm_out, info_out));
+}
+// the eigensolver of pepsgpu_minsr_direction alone, on the context's device and stream (eigh_jacobi.h)
+int pepsgpu_diag_eigh(pepsgpu_ctx *ctx, int n, int is_complex, const double *a, double *w_out, double *z_out, int *sweeps_out) {
+  CTX_CALL(diag_eigh_impl((hipStream_t)ctx->eng->stream_handle(), n, is_complex, a, w_out, z_out, sweeps_out));
 }
 int pepsgpu_fermion_decoration_set(pepsgpu_ctx *ctx, int d, const int32_t *nf, const uint8_t *bond_parity) {
   CTX_CALL(ctx->eng->fermion_decoration_set(d, nf, bond_parity));

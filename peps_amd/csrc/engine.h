@@ -129,6 +129,8 @@ struct EngineBase {
   virtual void opt_step(int rule, double lr, const double *params, int n_params) = 0;
   virtual void opt_scale_state(double factor) = 0;
   virtual void opt_read_state(double *host) = 0;
+  virtual void minsr_direction(const double *eloc, const double *energy, double r_pinv, double a_pinv, int soft_cutoff,
+                               double *direction_norm_out, double *info_out) = 0;
   virtual void fermion_decoration_set(int d, const int32_t *nf, const uint8_t *bond_parity) = 0;
   // one row / column of exchange moves (pair_table nullable) and of full-space moves (Suwa-Todo over phys_dim^2 states); engine_sweep.h
   virtual void sweep_slice_exchange(int orient, int slice, int n_uniform, const double *uniforms, const int32_t *pair_table,
@@ -860,6 +862,9 @@ class Engine : public EngineBase {
   void opt_step(int rule, double lr, const double *params, int n_params) override;
   void opt_scale_state(double factor) override;
   void opt_read_state(double *host) override;
+  void minsr_direction(const double *eloc, const double *energy, double r_pinv, double a_pinv, int soft_cutoff,
+                       double *direction_norm_out, double *info_out) override;
+  void sr_gram_device(double *g);          // the raw Gram of the local store, summed and mirrored in HBM (engine_sr.h)
   void fermion_decoration_set(int d, const int32_t *nf, const uint8_t *bond_parity) override;
   void opt_fermion_project(double *x);     // Pi in place over one optimizer vector (a decoration is set)
   std::vector<uint8_t> fermion_sign_table() const;
@@ -1640,6 +1645,9 @@ class Engine : public EngineBase {
   long opt_t_ = 0;                         // Adam timestep
   bool opt_acc_ready_ = false;             // acc holds initial_accumulator_value (set by the first AdaGrad step after opt_begin)
   static constexpr int kOptDotBlocks = 512;
+  // MinSR scratch (minsr_direction): T then Z^T, the rotation accumulator, the eigensolver's workspace and the Ns-long vectors
+  double *minsr_t_ = nullptr, *minsr_v_ = nullptr, *minsr_work_ = nullptr;
+  int minsr_cap_ = 0;                      // sample count the scratch was sized for
   // ---- BMPSWalker objects (engine_walker.h) ----
   struct WalkerDev {
     BMPSDev b;                       // the forked boundary MPS (all walkers of the context)

@@ -16,8 +16,14 @@
 // kernels above run unchanged (negating theta, g, velocity and m1 negates their results exactly; m2 and acc see |g|^2): a step on
 // (E theta, Pi g_ext) is bit for bit E of the step on (theta, E^T g_ext), Pi = E mask E^T.  New for fermions: the sign table, Pi
 // (alone and fused into the finish), the check at begin, the stored norm = 1/2 extended norm (E^T E = 4 mask), the SR hook.
+//
+// MinSR (minsr_direction): Optimizer::CalculateMinSRDirection_ on one rank (optimizer_impl.h:1126-1215, minsr_tmatrix.h:53-147,
+// minsr_eigensolve.h:44-155) with everything that scales with Ns^2 or with the parameter count in HBM: raw Gram of the resident O*
+// store -> four-term centering and 1 / Ns -> Jacobi eigensolver (eigh_jacobi.h) -> pseudo-inverse cutoff -> y = Z f(w) Z^H eps_bar ->
+// g <- sum_i y_i O*_i - (sum_i y_i) (sum_i O*_i) / Ns.  The host sees the Ns local energies on the way in and four scalars on the way out.
 #pragma once
 #include "engine_sr.h"
+#include "eigh_jacobi.h"
 
 namespace pepsgpu {
 
@@ -246,6 +252,9 @@ void Engine<T>::opt_release() {
   for (double *p : {opt_theta_, opt_g_, opt_vel_, opt_m1_, opt_m2_, opt_acc_, opt_part_}) arena_.free(p);
   arena_.free(opt_ne_);
   arena_.free(opt_sign_);
+  for (double *p : {minsr_t_, minsr_v_, minsr_work_}) arena_.free(p);
+  minsr_t_ = minsr_v_ = minsr_work_ = nullptr;
+  minsr_cap_ = 0;
   opt_theta_ = opt_g_ = opt_vel_ = opt_m1_ = opt_m2_ = opt_acc_ = opt_part_ = nullptr;
   opt_ne_ = nullptr;
   opt_sign_ = nullptr;
@@ -464,6 +473,225 @@ void Engine<T>::opt_natural_gradient(double diag_shift, int max_iter, double rel
   sr_cg_solve(opt_g_, nullptr, diag_shift, max_iter, rel_tol, abs_tol, recompute_interval, ortho_threshold, opt_g_, residual_norm,
               iterations, reason);
   if (direction_norm_out) *direction_norm_out = std::sqrt(opt_norm_sq(opt_g_));
+}
+
+// ---- MinSR ----
+// m[i] = sum_j G_ij / Ns      (one wave per row)
+template <int Z>
+__global__ __launch_bounds__(64) void minsr_rowmean_kernel(const double *__restrict__ g, int ns, double *__restrict__ m) {
+  const int i = blockIdx.x;
+  double acc[Z];
+  for (int z = 0; z < Z; ++z) acc[z] = 0.0;
+  for (int j = threadIdx.x; j < ns; j += 64)
+    for (int z = 0; z < Z; ++z) acc[z] += g[Z * ((long)i * ns + j) + z];
+  for (int z = 0; z < Z; ++z) acc[z] = wave_sum(acc[z]);
+  if (threadIdx.x == 0)
+    for (int z = 0; z < Z; ++z) m[Z * i + z] = acc[z] / ns;
+}
+// T_ij = (G_ij - m_i - conj(m_j) + c) / Ns in place, c = sum_i m_i / Ns (minsr_tmatrix.h:141-147).  Every block adds c in the same
+// fixed order; the entry below the diagonal is written as the conjugate of the one above, so T is exactly Hermitian.
+template <int Z>
+__global__ __launch_bounds__(256) void minsr_center_kernel(double *__restrict__ g, const double *__restrict__ m, int ns) {
+#pragma clang fp contract(off)
+  __shared__ double s_red[4][Z];
+  double c[Z];
+  for (int z = 0; z < Z; ++z) c[z] = 0.0;
+  for (int i = threadIdx.x; i < ns; i += 256)
+    for (int z = 0; z < Z; ++z) c[z] += m[Z * i + z];
+  for (int z = 0; z < Z; ++z) c[z] = wave_sum(c[z]);
+  if ((threadIdx.x & 63) == 0)
+    for (int z = 0; z < Z; ++z) s_red[threadIdx.x >> 6][z] = c[z];
+  __syncthreads();
+  for (int z = 0; z < Z; ++z) c[z] = (s_red[0][z] + s_red[1][z] + s_red[2][z] + s_red[3][z]) / ns;
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long)ns * ns) return;
+  const int i = (int)(e / ns), j = (int)(e % ns);
+  if (i > j) return;
+  const long ij = Z * ((long)i * ns + j), ji = Z * ((long)j * ns + i);
+  const double vr = (((g[ij] - m[Z * i]) - m[Z * j]) + c[0]) / ns;
+  g[ij] = vr; g[ji] = vr;
+  if constexpr (Z == 2) {
+    const double vi = i == j ? 0.0 : (((g[ij + 1] - m[2 * i + 1]) + m[2 * j + 1]) + c[1]) / ns;
+    g[ij + 1] = vi; g[ji + 1] = -vi;
+  }
+}
+// ApplyPseudoInverseCutoff (minsr_eigensolve.h:44-78) in one block: cutoff = r_pinv max|w| + a_pinv; soft: w^5 / (w^6 + cutoff^6), 0 where
+// the denominator is 0; hard: 1 / w where |w| > cutoff.  info = [max|w| (NaN when an eigenvalue is not finite), cutoff, #{|w| > cutoff}]
+__global__ __launch_bounds__(256) void minsr_cutoff_kernel(const double *__restrict__ w, int ns, double r_pinv, double a_pinv, int soft,
+                                                           double *__restrict__ fw, double *__restrict__ info) {
+#pragma clang fp contract(off)
+  __shared__ double s_max[256];
+  __shared__ int s_cnt[256];
+  double mx = 0.0;
+  int bad = 0;
+  for (int i = threadIdx.x; i < ns; i += 256) {
+    const double x = fabs(w[i]);
+    if (!(x <= 1.79769313486231570815e308)) bad = 1;
+    mx = fmax(mx, x);
+  }
+  s_max[threadIdx.x] = mx; s_cnt[threadIdx.x] = bad;
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if (threadIdx.x < st) { s_max[threadIdx.x] = fmax(s_max[threadIdx.x], s_max[threadIdx.x + st]); s_cnt[threadIdx.x] |= s_cnt[threadIdx.x + st]; }
+    __syncthreads();
+  }
+  const double lam = s_max[0];
+  const int anybad = s_cnt[0];
+  __syncthreads();
+  const double cutoff = r_pinv * lam + a_pinv;
+  const double c2 = cutoff * cutoff, c6 = c2 * c2 * c2;
+  int kept = 0;
+  for (int i = threadIdx.x; i < ns; i += 256) {
+    const double x = w[i];
+    double f = 0.0;
+    if (soft) {
+      const double x2 = x * x, den = x2 * x2 * x2 + c6;
+      if (den != 0.0) f = x2 * x2 * x / den;
+    } else if (fabs(x) > cutoff) f = 1.0 / x;
+    fw[i] = f;
+    kept += fabs(x) > cutoff ? 1 : 0;
+  }
+  s_cnt[threadIdx.x] = kept;
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if (threadIdx.x < st) s_cnt[threadIdx.x] += s_cnt[threadIdx.x + st];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { info[0] = anybad ? nan("") : lam; info[1] = cutoff; info[2] = (double)s_cnt[0]; }
+}
+// u_k = f(w_k) sum_r conj(Z_rk) eps_bar_r,  eps_bar_r = conj(E_r - E) / Ns (optimizer_impl.h:1139-1146); zt = Z^T, one wave per k
+template <int Z>
+__global__ __launch_bounds__(64) void minsr_project_kernel(const double *__restrict__ zt, const double *__restrict__ fw,
+                                                           const double *__restrict__ eloc, const double *__restrict__ energy, int ns,
+                                                           double *__restrict__ u) {
+  const int k = blockIdx.x;
+  double acc[Z];
+  for (int z = 0; z < Z; ++z) acc[z] = 0.0;
+  for (int r = threadIdx.x; r < ns; r += 64) {
+    const double er = (eloc[Z * r] - energy[0]) / ns, vr = zt[Z * ((long)k * ns + r)];
+    if constexpr (Z == 1) acc[0] += vr * er;
+    else {
+      const double ei = -(eloc[2 * r + 1] - energy[1]) / ns, vi = zt[2 * ((long)k * ns + r) + 1];
+      acc[0] += vr * er + vi * ei;
+      acc[1] += vr * ei - vi * er;
+    }
+  }
+  for (int z = 0; z < Z; ++z) acc[z] = wave_sum(acc[z]);
+  if (threadIdx.x == 0)
+    for (int z = 0; z < Z; ++z) u[Z * k + z] = fw[k] * acc[z];
+}
+// y_r = sum_k Z_rk u_k: one lane per r, lanes along a row of zt
+template <int Z>
+__global__ __launch_bounds__(256) void minsr_expand_kernel(const double *__restrict__ zt, const double *__restrict__ u, int ns,
+                                                          double *__restrict__ y) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= ns) return;
+  double acc[Z];
+  for (int z = 0; z < Z; ++z) acc[z] = 0.0;
+  for (int k = 0; k < ns; ++k) {
+    const double vr = zt[Z * ((long)k * ns + r)], ur = u[Z * k];
+    if constexpr (Z == 1) acc[0] += vr * ur;
+    else {
+      const double vi = zt[2 * ((long)k * ns + r) + 1], ui = u[2 * k + 1];
+      acc[0] += vr * ur - vi * ui;
+      acc[1] += vr * ui + vi * ur;
+    }
+  }
+  for (int z = 0; z < Z; ++z) y[Z * r + z] = acc[z];
+}
+// out = sum_r y_r      (one wave, fixed order)
+template <int Z>
+__global__ __launch_bounds__(64) void minsr_ysum_kernel(const double *__restrict__ y, int ns, double *__restrict__ out) {
+  double acc[Z];
+  for (int z = 0; z < Z; ++z) acc[z] = 0.0;
+  for (int r = threadIdx.x; r < ns; r += 64)
+    for (int z = 0; z < Z; ++z) acc[z] += y[Z * r + z];
+  for (int z = 0; z < Z; ++z) acc[z] = wave_sum(acc[z]);
+  if (threadIdx.x == 0)
+    for (int z = 0; z < Z; ++z) out[z] = acc[z];
+}
+// g <- wsum - ysum * osum / Ns on the live elements      (optimizer_impl.h:1196-1212)
+template <int Z>
+__global__ __launch_bounds__(256) void minsr_combine_kernel(const double *__restrict__ wsum, const double *__restrict__ osum,
+                                                            const double *__restrict__ ysum, int ns, double *__restrict__ g,
+                                                            const int *__restrict__ ne, long slot, int dp) {
+#pragma clang fp contract(off)
+  OPT_ELEM_PROLOGUE
+  if constexpr (Z == 1) {
+    g[k] = wsum[k] - ysum[0] * osum[k] / ns;
+  } else {
+    const double sr = osum[2 * k], si = osum[2 * k + 1];
+    g[2 * k] = wsum[2 * k] - (ysum[0] * sr - ysum[1] * si) / ns;
+    g[2 * k + 1] = wsum[2 * k + 1] - (ysum[0] * si + ysum[1] * sr) / ns;
+  }
+}
+
+template <typename T>
+void Engine<T>::minsr_direction(const double *eloc, const double *energy, double r_pinv, double a_pinv, int soft_cutoff,
+                                double *direction_norm_out, double *info_out) {
+  PG_REQUIRE(opt_theta_ != nullptr, 3, "minsr_direction: call pepsgpu_opt_begin first");
+  PG_REQUIRE(fd_d_ == 0, 1, "minsr_direction: not available with a fermionic decoration (T in the stored parameters is not built)");
+  PG_REQUIRE(sr_o_ != nullptr && sr_n_ > 0, 3, "minsr_direction: the sample store is empty (pepsgpu_sr_begin / pepsgpu_sr_append)");
+  PG_REQUIRE(eloc != nullptr && energy != nullptr, 1, "minsr_direction: null eloc / energy");
+  PG_REQUIRE(std::isfinite(r_pinv) && std::isfinite(a_pinv) && r_pinv >= 0.0 && a_pinv >= 0.0, 1,
+             "minsr_direction: r_pinv and a_pinv must be finite and non-negative");
+  for (int z = 0; z < kOut; ++z) PG_REQUIRE(std::isfinite(energy[z]), 1, "minsr_direction: non-finite energy");
+  const int ns = sr_n_;
+  for (long e = 0; e < (long)ns * kOut; ++e) PG_REQUIRE(std::isfinite(eloc[e]), 1, "minsr_direction: non-finite local energy");
+  const size_t nn = (size_t)ns * ns * kOut, ew = eigh_work_doubles(ns);
+  if (minsr_cap_ < ns) {
+    for (double *p : {minsr_t_, minsr_v_, minsr_work_}) arena_.free(p);
+    minsr_t_ = minsr_v_ = minsr_work_ = nullptr;
+    minsr_cap_ = 0;
+    minsr_t_ = (double *)arena_.alloc(sizeof(double) * nn);
+    minsr_v_ = (double *)arena_.alloc(sizeof(double) * nn);
+    minsr_work_ = (double *)arena_.alloc(sizeof(double) * (ew + (size_t)ns * (2 + 3 * kOut) + 8));
+    minsr_cap_ = ns;
+  }
+  double *w = minsr_work_ + ew, *fw = w + ns, *m = fw + ns, *u = m + (size_t)ns * kOut, *de = u + (size_t)ns * kOut;
+  double *den = de + (size_t)ns * kOut, *ysum = den + 2, *dinfo = ysum + 2;
+  const int sites = Ly_ * Lx_;
+  sr_gram_device(minsr_t_);
+  hipLaunchKernelGGL(minsr_rowmean_kernel<kOut>, dim3(ns), dim3(64), 0, stream_, (const double *)minsr_t_, ns, m);
+  hipLaunchKernelGGL(minsr_center_kernel<kOut>, dim3((unsigned)(((long)ns * ns + 255) / 256)), dim3(256), 0, stream_, minsr_t_,
+                     (const double *)m, ns);
+  PG_CHECK_HIP(hipGetLastError());
+  int sweeps = 0;
+  const bool converged = eigh_jacobi(stream_, ns, kCplx, minsr_t_, minsr_v_, w, minsr_work_, &sweeps);
+  if (!converged) throw Error(6, "minsr_direction: the Jacobi eigensolver reached its sweep cap");
+  hipLaunchKernelGGL(minsr_cutoff_kernel, dim3(1), dim3(256), 0, stream_, (const double *)w, ns, r_pinv, a_pinv, soft_cutoff ? 1 : 0, fw, dinfo);
+  PG_CHECK_HIP(hipGetLastError());
+  double info[3];
+  PG_CHECK_HIP(hipMemcpyAsync(info, dinfo, sizeof(info), hipMemcpyDeviceToHost, stream_));
+  PG_CHECK_HIP(hipStreamSynchronize(stream_));
+  if (!std::isfinite(info[0])) throw Error(2, "minsr_direction: the T matrix has non-finite eigenvalues (non-finite O* samples)");
+  PG_CHECK_HIP(hipMemcpyAsync(de, eloc, sizeof(double) * (size_t)ns * kOut, hipMemcpyHostToDevice, stream_));
+  PG_CHECK_HIP(hipMemcpyAsync(den, energy, sizeof(double) * kOut, hipMemcpyHostToDevice, stream_));
+  hipLaunchKernelGGL(minsr_project_kernel<kOut>, dim3(ns), dim3(64), 0, stream_, (const double *)minsr_t_, (const double *)fw,
+                     (const double *)de, (const double *)den, ns, u);
+  hipLaunchKernelGGL(minsr_expand_kernel<kOut>, dim3((ns + 255) / 256), dim3(256), 0, stream_, (const double *)minsr_t_, (const double *)u,
+                     ns, sr_delta_);
+  hipLaunchKernelGGL(minsr_ysum_kernel<kOut>, dim3(1), dim3(64), 0, stream_, (const double *)sr_delta_, ns, ysum);
+  PG_CHECK_HIP(hipGetLastError());
+  // the back-substitution: the kernels behind pepsgpu_sr_weighted_sum (-> sr_out_) and pepsgpu_sr_sum (-> sr_v_), device to device
+  const dim3 ag((unsigned)((slot_ + 255) / 256), sites);
+  if constexpr (kCplx) {
+    hipLaunchKernelGGL(sr_accum_cplx_kernel<T>, ag, dim3(256), 0, stream_, (const T *)sr_o_, (const int *)sr_cfg_, (const double *)sr_delta_,
+                       1.0, sr_out_, ns, sites, slot_, dp_);
+    hipLaunchKernelGGL(sr_accum_cplx_kernel<T>, ag, dim3(256), 0, stream_, (const T *)sr_o_, (const int *)sr_cfg_, (const double *)nullptr,
+                       1.0, sr_v_, ns, sites, slot_, dp_);
+  } else {
+    hipLaunchKernelGGL(sr_accum_kernel<T>, ag, dim3(256), 0, stream_, (const T *)sr_o_, (const int *)sr_cfg_, (const double *)sr_delta_, 1.0,
+                       sr_out_, ns, sites, slot_, dp_);
+    hipLaunchKernelGGL(sr_accum_kernel<T>, ag, dim3(256), 0, stream_, (const T *)sr_o_, (const int *)sr_cfg_, (const double *)nullptr, 1.0,
+                       sr_v_, ns, sites, slot_, dp_);
+  }
+  hipLaunchKernelGGL(minsr_combine_kernel<kOut>, opt_grid(), dim3(256), 0, stream_, (const double *)sr_out_, (const double *)sr_v_,
+                     (const double *)ysum, ns, opt_g_, (const int *)opt_ne_, slot_, dp_);
+  PG_CHECK_HIP(hipGetLastError());
+  const double nsq = opt_norm_sq(opt_g_);      // (synchronises: eloc / energy have been read)
+  if (direction_norm_out) *direction_norm_out = std::sqrt(nsq);
+  if (info_out) { info_out[0] = info[0]; info_out[1] = info[1]; info_out[2] = info[2]; info_out[3] = (double)sweeps; }
 }
 
 template <typename T>

@@ -775,6 +775,75 @@ void Engine<T>::sr_gram(const void *remote_o, const int32_t *remote_cfg, int n_r
   }
 }
 
+// g[ib + i][jb + j] = sum over the K splits of one Gram block, in the order the host loop of sr_gram adds them, for the entries on and
+// above the diagonal; the entry below is its conjugate, a diagonal entry is real.  Z doubles per entry.
+template <int Z>
+__global__ __launch_bounds__(256) void sr_gram_reduce_kernel(const double *__restrict__ part, int split, int ni, int nj, int ib, int jb,
+                                                             int ns, double *__restrict__ g) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long)ni * nj) return;
+  const int i = ib + (int)(e / nj), j = jb + (int)(e % nj);
+  if (i > j) return;
+  double acc[Z];
+  for (int z = 0; z < Z; ++z) acc[z] = 0.0;
+  for (int sp = 0; sp < split; ++sp)
+    for (int z = 0; z < Z; ++z) acc[z] += part[Z * ((long)sp * ni * nj + e) + z];
+  if (Z == 2 && i == j) acc[Z - 1] = 0.0;
+  for (int z = 0; z < Z; ++z) g[Z * ((long)i * ns + j) + z] = acc[z];
+  if (i != j) {
+    g[Z * ((long)j * ns + i)] = acc[0];
+    if (Z == 2) g[Z * ((long)j * ns + i) + 1] = -acc[Z - 1];
+  }
+}
+
+// sr_gram of the local store against itself with the result left in HBM: the same blocked split-K launches, the partial blocks summed
+// by sr_gram_reduce_kernel in place of the host loop.  g = [sr_n_][sr_n_] doubles (interleaved pairs on a complex context).
+template <typename T>
+void Engine<T>::sr_gram_device(double *g) {
+  PG_REQUIRE(sr_o_ != nullptr && sr_n_ > 0, 3, "sr_gram: no samples");
+  const int sites = Ly_ * Lx_;
+  const long n = (long)sites * dp_ * slot_;
+  const long lim = kCplx ? (1l << 30) : (1l << 31);
+  PG_REQUIRE(n < lim, 1, "sr_gram: parameter count exceeds the 32-bit strides of the tensor GEMM");
+  const int bs = (int)std::min<long>(1024, (lim - 1) / n) & ~63;
+  PG_REQUIRE(bs >= 64, 1, "sr_gram: parameter count too large for the blocked Gram");
+  ArenaBuf<T> ea(arena_, (size_t)sr_n_ * n);
+  hipLaunchKernelGGL(sr_expand_kernel<T>, dim3((unsigned)((slot_ + 255) / 256), sites, sr_n_), dim3(256), 0, stream_, (const T *)sr_o_,
+                     (const int *)sr_cfg_, (T *)ea, sites, slot_, dp_, (const int *)sr_ne_);
+  PG_CHECK_HIP(hipGetLastError());
+  const int groups = sites * dp_;
+  for (int ib = 0; ib < sr_n_; ib += bs) {
+    const int ni = std::min(bs, sr_n_ - ib);
+    for (int jb = ib; jb < sr_n_; jb += bs) {
+      const int nj = std::min(bs, sr_n_ - jb);
+      const long tiles = (long)((ni + 63) / 64) * ((nj + 63) / 64);
+      int split = 1;
+      for (int c = 1; c <= groups; ++c)
+        if (groups % c == 0 && tiles * c <= 2048) split = c;
+      const long chunk = n / split;
+      ArenaBuf<double> d(arena_, (size_t)split * ni * nj * kOut);
+      PG_CHECK_HIP(hipMemsetAsync(d, 0, sizeof(double) * (size_t)split * ni * nj * kOut, stream_));
+      TGemmDesc gd;
+      gd.I[2] = ni; gd.sAi[2] = (int)n; gd.sCi[2] = nj;
+      gd.K[2] = (int)chunk; gd.sAk[2] = 1; gd.sBk[2] = 1;
+      gd.J[2] = nj; gd.sBj[2] = (int)n; gd.sCj[2] = 1;
+      gd.wA = chunk; gd.wB = chunk; gd.wC = (long)ni * nj;
+      gd.nbatch = split;
+      if constexpr (kCplx) {
+        gd.conjA = 1;
+        tgemm_launch<T, T, T, T>(stream_, gd, (T *)ea + (size_t)ib * n, (T *)ea + (size_t)jb * n, (T *)(double *)d);
+      } else {
+        gd.upper_only = ib == jb ? 1 : 0;
+        tgemm_launch<T, T, double, double>(stream_, gd, (T *)ea + (size_t)ib * n, (T *)ea + (size_t)jb * n, (double *)d);
+      }
+      hipLaunchKernelGGL(sr_gram_reduce_kernel<kOut>, dim3((unsigned)(((long)ni * nj + 255) / 256)), dim3(256), 0, stream_,
+                         (const double *)d, split, ni, nj, ib, jb, sr_n_, g);
+      PG_CHECK_HIP(hipGetLastError());
+    }
+  }
+  PG_CHECK_HIP(hipStreamSynchronize(stream_));      // (the blocks go back to the arena here)
+}
+
 template <typename T>
 void Engine<T>::sr_weighted_sum(const double *y, double *out) {
   if constexpr (kCplx) {       // sum_i y_i O*_i with complex weights (interleaved pairs in, interleaved pairs out)

@@ -193,6 +193,38 @@ void sr_step_samples_impl(int rows, int cols, int D, int d, int chi, int dtype, 
   copy_out(opt.GetState(rows, cols, d, D).flat(), state_out);
 }
 
+// The MinSR twin of sr_step_samples_impl: one iteration of Optimizer::IterativeOptimize with MinSRParams on a given sample set.
+// info_out = [E before, E after, |x|, max eigenvalue of T, cutoff, eigenvalues kept, Jacobi sweeps].  exact_sum != 0 evaluates by exact
+// summation over `configs` instead: that evaluator keeps no sample set, so the MinSR update refuses (std::invalid_argument).
+template <typename TenElemT>
+void minsr_step_samples_impl(int rows, int cols, int D, int d, int chi, int dtype, const double *sitps_flat, int n, const int32_t *configs,
+                             int model, const double *p, double lr, double r_pinv, double a_pinv, int soft_cutoff, int exact_sum,
+                             double *state_out, double *info_out) {
+  if (model != 0 && model != 1) throw std::invalid_argument("pepshost_minsr_step_samples: model must be xxz or tfim");
+  if (n < 1) throw std::invalid_argument("pepshost_minsr_step_samples: bad sample count");
+  SplitIndexTPST<TenElemT> sitps = make_state_t<TenElemT>(rows, cols, D, d, sitps_flat);
+  BMPSContractorT<TenElemT> contractor(rows, cols, D, d, trunc_params(chi), n, dtype, g_device);
+  const Configuration samples = make_cfg(n, rows, cols, configs);
+  std::vector<std::vector<int32_t>> all(exact_sum ? n : 0);
+  for (size_t i = 0; i < all.size(); ++i) all[i].assign(configs + i * rows * cols, configs + (i + 1) * rows * cols);
+  contractor.UploadState(sitps);
+  Optimizer<TenElemT> opt(OptimizerParams(OptimizerParams::BaseParams(1, 0.0, 0.0, 2, lr), MinSRParams(r_pinv, a_pinv, soft_cutoff != 0)),
+                          contractor);
+  typename Optimizer<TenElemT>::OptimizationResult res;
+  auto run = [&](auto &m) {
+    return opt.IterativeOptimize([&](BMPSContractorT<TenElemT> &c) {
+      return exact_sum ? ExactSumAccumulateResident(sitps, all, c, m, (size_t)n) : SampleSetAccumulateResident(sitps, samples, c, m);
+    });
+  };
+  if (model == 0) { SquareSpinOneHalfXXZModelOBC m(p[0], p[1], p[2]); res = run(m); }
+  else { TransverseFieldIsingSquareOBC m(p[0]); res = run(m); }
+  const auto &mi = opt.LastMinSRInfo();
+  info_out[0] = std::real(res.energy_trajectory.at(0)); info_out[1] = std::real(res.energy_trajectory.at(1));
+  info_out[2] = res.sr_natural_grad_norm; info_out[3] = mi.lambda_max; info_out[4] = mi.cutoff;
+  info_out[5] = (double)mi.n_kept; info_out[6] = (double)mi.sweeps;
+  copy_out(opt.GetState(rows, cols, d, D).flat(), state_out);
+}
+
 template <typename TenElemT>
 void mc_energy_grad_partial_impl(int rows, int cols, int D, int d, int chi, int dtype, const double *sitps_flat, int n,
                                  int32_t *configs, const uint64_t *seeds, int updater, int model, const double *p,
@@ -926,6 +958,23 @@ int pepshost_sr_step_samples_c128(int rows, int cols, int D, int d, int chi, con
   return guarded([&]() {
     sr_step_samples_impl<QLTEN_Complex>(rows, cols, D, d, chi, PEPSGPU_C128, sitps_flat, n, configs, model, p, lr, diag_shift, cg_max_iter,
                                         cg_relative_tolerance, normalize_update, state_out, info_out);
+  });
+}
+// Optimizer's MinSR step on a given sample set (see minsr_step_samples_impl)
+int pepshost_minsr_step_samples(int rows, int cols, int D, int d, int chi, int dtype, const double *sitps_flat, int n, const int32_t *configs,
+                                int model, const double *p, double lr, double r_pinv, double a_pinv, int soft_cutoff, int exact_sum,
+                                double *state_out, double *info_out) {
+  return guarded([&]() {
+    minsr_step_samples_impl<double>(rows, cols, D, d, chi, dtype, sitps_flat, n, configs, model, p, lr, r_pinv, a_pinv, soft_cutoff, exact_sum,
+                                    state_out, info_out);
+  });
+}
+int pepshost_minsr_step_samples_c128(int rows, int cols, int D, int d, int chi, const double *sitps_flat, int n, const int32_t *configs,
+                                     int model, const double *p, double lr, double r_pinv, double a_pinv, int soft_cutoff, int exact_sum,
+                                     double *state_out, double *info_out) {
+  return guarded([&]() {
+    minsr_step_samples_impl<QLTEN_Complex>(rows, cols, D, d, chi, PEPSGPU_C128, sitps_flat, n, configs, model, p, lr, r_pinv, a_pinv,
+                                           soft_cutoff, exact_sum, state_out, info_out);
   });
 }
 // Optimizer::IterativeOptimize + exact summation on a fermionic state (see fermion_optimize_exact_sum_impl)

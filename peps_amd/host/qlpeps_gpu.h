@@ -660,6 +660,18 @@ class BMPSContractorT {
                                           orthogonality_threshold, &r.residual_norm, &r.iterations, &r.reason, &r.direction_norm), ctx_);
     return r;
   }
+  // g <- the MinSR direction of the sample store (pepsgpu_minsr_direction): Gram, centering, eigensolve, cutoff and back-substitution on
+  // the device; energy_samples in the order the samples were appended
+  struct MinSRInfo { double direction_norm = 0.0, lambda_max = 0.0, cutoff = 0.0; size_t n_kept = 0, sweeps = 0; };
+  MinSRInfo MinSRDirection(const std::vector<TenElemT> &energy_samples, const TenElemT &energy, double r_pinv, double a_pinv, bool soft_cutoff) {
+    MinSRInfo r;
+    double info[4] = {0.0, 0.0, 0.0, 0.0};
+    check_rc(pepsgpu_minsr_direction(ctx_, dptr(energy_samples.data()), dptr(&energy), r_pinv, a_pinv, soft_cutoff ? 1 : 0, &r.direction_norm, info),
+             ctx_);
+    r.lambda_max = info[0]; r.cutoff = info[1]; r.n_kept = (size_t)info[2]; r.sweeps = (size_t)info[3];
+    return r;
+  }
+  size_t SRCount() const { const int n = pepsgpu_sr_count(ctx_); return n > 0 ? (size_t)n : 0; }
   void OptStep(int rule, double lr, const std::vector<double> &params) {
     check_rc(pepsgpu_opt_step(ctx_, rule, lr, params.data(), (int)params.size()), ctx_);
   }
@@ -3600,9 +3612,10 @@ std::pair<TenElemT, SplitIndexTPST<TenElemT>> ExactSumEnergyEvaluator(const Spli
 // state live in HBM (pepsgpu_opt_*); an iteration is evaluate -> finish -> clip (first-order rules) -> [natural gradient] ->
 // step with no tensor traffic over PCIe.  In: SGD, AdaGrad, Adam and the one-rank SR step, for bosonic and for fermionic states (a
 // FermionDecoration with bond parities: the buffers hold the 4 d decorated components, gradients are folded and projected on the
-// device, norms and the SR solve are those of the stored parameters).  Out (host drivers of the reference
+// device, norms and the SR solve are those of the stored parameters); the one-rank MinSR step (MinSRParams: T matrix, eigensolve,
+// cutoff and back-substitution on the device, pepsgpu_minsr_direction) for bosonic states.  Out (host drivers of the reference
 // that stay with the caller): L-BFGS, step selectors / line search, spike detection, checkpoints, CSV / JSONL logs, MinSR
-// (peps_amd/sr.py), multi-rank CG.  Parameter names and defaults: optimizer/optimizer_params.h.
+// over several ranks or on a fermionic state (peps_amd/sr.py), multi-rank CG.  Parameter names and defaults: optimizer/optimizer_params.h.
 struct ConjugateGradientParams {               // optimizer_params.h:50-57
   size_t max_iter = 100;
   double relative_tolerance = 1e-4;
@@ -3674,7 +3687,17 @@ class StepLR : public LearningRateScheduler {               // :83-105: lr = ini
   size_t step_size_;
 };
 
-using AlgorithmParams = std::variant<SGDParams, AdamParams, StochasticReconfigurationParams, AdaGradParams>;
+enum class MinSRSolverMode { kAuto, kReplicated, kDistributed };   // :204-208
+struct MinSRParams {                           // :220-232
+  double r_pinv, a_pinv;                       // cutoff = r_pinv * max|lambda| + a_pinv
+  bool soft_cutoff;                            // lambda^5 / (lambda^6 + cutoff^6) instead of 1 / lambda above the cutoff
+  MinSRSolverMode solver_mode;                 // carried, not read: one rank solves on its own device (pepsgpu_minsr_direction)
+  MinSRParams(double r_pinv = 1e-12, double a_pinv = 0.0, bool soft_cutoff = true, MinSRSolverMode solver_mode = MinSRSolverMode::kAuto)
+      : r_pinv(r_pinv), a_pinv(a_pinv), soft_cutoff(soft_cutoff), solver_mode(solver_mode) {}
+};
+
+// (MinSRParams is the last alternative: the others keep their indices)
+using AlgorithmParams = std::variant<SGDParams, AdamParams, StochasticReconfigurationParams, AdaGradParams, MinSRParams>;
 
 struct OptimizerParams {                       // optimizer_params.h:348-473
   struct BaseParams {                          // :365-425
@@ -3715,6 +3738,7 @@ struct DeviceEvaluationT {
   TenElemT e_loc_sum = TenElemT(0.0);
   double weight_sum = 0.0;
   double energy_error = 0.0;
+  std::vector<TenElemT> energy_samples;     // the local energy of every sample in the SR store, in its order (MinSR); empty: no sample set
 };
 
 template <typename TenElemT>
@@ -3775,20 +3799,40 @@ class Optimizer {
     c_.OptStep(0, step, {0.0, 0.0, 0.0});
     return info;
   }
+  // MinSR direction from the contractor's sample store and the local energies of those samples (CalculateMinSRDirection_,
+  // optimizer_impl.h:1126-1215), then theta -= lr x.  An evaluator that keeps no sample set (exact summation) leaves energy_samples empty.
+  typename ContractorT::MinSRInfo MinSRUpdate(double learning_rate, const MinSRParams &p, const std::vector<TenElemT> &energy_samples,
+                                              const TenElemT &energy) {
+    if (energy_samples.size() != c_.SRCount() || energy_samples.empty())
+      throw std::invalid_argument("Optimizer::MinSRUpdate: " + std::to_string(energy_samples.size()) + " local energies for " +
+                                  std::to_string(c_.SRCount()) + " stored samples (MinSR needs an evaluator that keeps its sample set)");
+    auto info = c_.MinSRDirection(energy_samples, energy, p.r_pinv, p.a_pinv, p.soft_cutoff);
+    c_.OptStep(0, learning_rate, {0.0, 0.0, 0.0});
+    return info;
+  }
   void ClipGradient() {                          // optimizer_impl.h:307-318
     if (!params_.IsFirstOrder()) return;
     const double cv = params_.base_params.clip_value.value_or(0.0), cn = params_.base_params.clip_norm.value_or(0.0);
     if (cv > 0.0 || cn > 0.0) c_.OptClip(cv, cn);
   }
-  void Update(double lr, OptimizationResult &res) {
+  // `ev`, `energy`: the evaluation the gradient buffer was finished from (MinSR reads its local energies and their mean)
+  void Update(double lr, OptimizationResult &res, const DeviceEvaluationT<TenElemT> &ev = DeviceEvaluationT<TenElemT>(),
+              const TenElemT &energy = TenElemT(0.0)) {
     if (params_.template IsAlgorithm<SGDParams>()) SGDUpdate(lr, params_.template GetAlgorithmParams<SGDParams>());
     else if (params_.template IsAlgorithm<AdaGradParams>()) AdaGradUpdate(lr);
     else if (params_.template IsAlgorithm<AdamParams>()) AdamUpdate(lr, params_.template GetAlgorithmParams<AdamParams>());
-    else {
+    else if (params_.template IsAlgorithm<StochasticReconfigurationParams>()) {
       auto info = StochasticReconfigurationUpdate(lr, params_.template GetAlgorithmParams<StochasticReconfigurationParams>());
       res.sr_iterations = (size_t)info.iterations; res.sr_natural_grad_norm = info.direction_norm; res.sr_residual_norm = info.residual_norm;
+    } else if (params_.template IsAlgorithm<MinSRParams>()) {
+      // sr_iterations and sr_residual_norm stay 0: there is no iterative solve (the reference's IterationRecord says the same)
+      last_minsr_ = MinSRUpdate(lr, params_.template GetAlgorithmParams<MinSRParams>(), ev.energy_samples, energy);
+      res.sr_natural_grad_norm = last_minsr_.direction_norm;
+    } else {
+      throw std::logic_error("Optimizer::Update: no update rule for this alternative of AlgorithmParams");
     }
   }
+  const typename ContractorT::MinSRInfo &LastMinSRInfo() const { return last_minsr_; }
   bool ShouldStop(double current_energy, double previous_energy, double gradient_norm, size_t iterations_without_improvement) const {   // :1764-1793
     const auto &b = params_.base_params;
     return gradient_norm < b.gradient_tolerance || std::abs(current_energy - previous_energy) < b.energy_tolerance ||
@@ -3799,8 +3843,9 @@ class Optimizer {
     OptimizationResult res;
     double previous_energy = 0.0;
     size_t without_improvement = 0;
+    DeviceEvaluationT<TenElemT> ev;
     auto evaluate = [&]() {
-      const DeviceEvaluationT<TenElemT> ev = evaluator(c_);
+      ev = evaluator(c_);
       auto eg = c_.OptGradientFromAccumulators(ev.e_loc_sum, ev.weight_sum);
       res.energy_trajectory.push_back(eg.first);
       res.gradient_norms.push_back(eg.second);
@@ -3815,7 +3860,7 @@ class Optimizer {
       if (callback.on_iteration) callback.on_iteration(iter, e, eg.second, lr);
       if (iter > 0 && ShouldStop(e, previous_energy, eg.second, without_improvement)) { res.converged = true; return res; }
       ClipGradient();
-      Update(lr, res);
+      Update(lr, res, ev, eg.first);
       if (params_.base_params.lr_scheduler) params_.base_params.lr_scheduler->Step();
       previous_energy = e;
       res.total_iterations = iter + 1;
@@ -3843,6 +3888,7 @@ class Optimizer {
   OptimizerParams params_;
   ContractorT &c_;
   const FermionDecoration *fermion_ = nullptr;
+  typename ContractorT::MinSRInfo last_minsr_;
 };
 
 // what AccumulateDevice of the gradient accumulator hands the device for one batch: bosons the amplitudes, fermions the dense
@@ -3902,6 +3948,7 @@ DeviceEvaluationT<TenElemT> SampleSetAccumulateResident(const SplitIndexTPST<Ten
   EnergyAndHolesT<TenElemT> eh = model.template CalEnergyAndHoles<true>(shape, comp, /*holes_on_device=*/true);
   ResidentGradAccumulate(comp, eh, false, true);
   for (size_t w = 0; w < samples.walkers(); ++w) { ev.weight_sum += 1.0; ev.e_loc_sum += eh.energy[w]; }
+  ev.energy_samples = eh.energy;
   return ev;
 }
 

@@ -21,6 +21,7 @@ SYMBOLS = ["pepshost_last_error", "pepshost_mc_sweeps", "pepshost_energy_and_hol
            "pepshost_fermion_mc_sweeps_updater", "pepshost_tnn3_table",
            "pepshost_optimize_exact_sum", "pepshost_optimize_exact_sum_c128", "pepshost_lr_schedule",
            "pepshost_sr_step_samples", "pepshost_sr_step_samples_c128",
+           "pepshost_minsr_step_samples", "pepshost_minsr_step_samples_c128",
            "pepshost_fermion_optimize_exact_sum", "pepshost_fermion_optimize_exact_sum_c128",
            "pepshost_fermion_sr_step_samples", "pepshost_fermion_sr_step_samples_c128", "pepshost_fermion_exact_sum_partial_prm",
            "pepshost_fermion_observables", "pepshost_fermion_exact_sum_measure_partial", "pepshost_fermion_measure"]
@@ -268,6 +269,33 @@ def sr_step_samples(flat, configs, chi, model, params, lr, diag_shift=0.001, cg_
         _ck(l.pepshost_sr_step_samples(rows, cols, D, d, chi, dtype, _cp(flat), *rest))
     return state, {"energy_before": info[0], "energy_after": info[1], "cg_iterations": int(info[2]), "direction_norm": info[3],
                    "cg_residual_norm": info[4]}
+
+
+def minsr_step_samples(flat, configs, chi, model, params, lr, r_pinv=1e-12, a_pinv=0.0, soft_cutoff=True, dtype=1, exact_sum=False):
+    """One MinSR iteration of the C++ Optimizer (MinSRParams) on a given sample set (weight 1 per sample): gradient from the resident
+    accumulators, the MinSR direction x from the resident O* store and the samples' local energies on the device, theta -= lr x.
+    Returns (state after the step, dict with the energies before / after, |x|, the largest eigenvalue of T, the cutoff, the number of
+    eigenvalues kept and the Jacobi sweeps).  Models: "xxz", "tfim".  exact_sum=True evaluates by exact summation over `configs`
+    instead: that evaluator keeps no sample set and the update refuses (ValueError)."""
+    cplx = np.iscomplexobj(flat)
+    flat = np.ascontiguousarray(flat, dtype=np.complex128 if cplx else np.float64)
+    rows, cols, d, D = _dims(flat)
+    cfg = np.ascontiguousarray(configs, dtype=np.int32)
+    p = np.array(list(params) + [0.0] * 8, dtype=np.float64)
+    state, info = np.zeros_like(flat), np.zeros(7)
+    l = lib()
+    tail = [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double,
+            C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    l.pepshost_minsr_step_samples.argtypes = [C.c_int] * 6 + tail
+    l.pepshost_minsr_step_samples_c128.argtypes = [C.c_int] * 5 + tail
+    rest = (cfg.shape[0], _p(cfg, C.c_int32), MODEL_ID[model], _p(p, C.c_double), float(lr), float(r_pinv), float(a_pinv),
+            int(bool(soft_cutoff)), int(bool(exact_sum)), _cp(state), _p(info, C.c_double))
+    if cplx:
+        _ck(l.pepshost_minsr_step_samples_c128(rows, cols, D, d, chi, _cp(flat), *rest))
+    else:
+        _ck(l.pepshost_minsr_step_samples(rows, cols, D, d, chi, dtype, _cp(flat), *rest))
+    return state, {"energy_before": info[0], "energy_after": info[1], "direction_norm": info[2], "lambda_max": info[3], "cutoff": info[4],
+                   "n_kept": int(info[5]), "sweeps": int(info[6])}
 
 
 def lr_schedule(kind, args, iteration):

@@ -575,6 +575,50 @@ int pepsgpu_minsr_direction(pepsgpu_ctx *ctx, const double *eloc, const double *
                             double *direction_norm_out, double *info_out);
 int pepsgpu_diag_eigh(pepsgpu_ctx *ctx, int n, int is_complex, const double *a, double *w_out, double *z_out, int *sweeps_out);
 
+/* L-BFGS inside the device-resident optimizer (optimizer/optimizer_impl.h; parameters = LBFGSParams, optimizer_params.h:119-152).  The
+ * history ring of (s_i, y_i), the anchor (theta_a, g_a), the search direction d and the base (theta_b, g_b) of the current line search
+ * live in HBM in the layout of theta; a trial point of a line search costs one element-wise pass and one dot product, the evaluator then
+ * runs on the resident state.  Inner products are RealInnerProduct_ (:1398-1401): the plain dot over the doubles, interleaved pairs on
+ * a PEPSGPU_C128 context; under a fermionic decoration they are those of the stored parameters.  Reductions have a fixed order: the same
+ * call on the same buffers returns the same bytes.
+ *   pepsgpu_lbfgs_begin    allocates and zeroes the buffers for history_size pairs, 1 <= history_size <= 32 (ResetLBFGSState_,
+ *                          :1404-1413; the reference refuses 0).  pepsgpu_lbfgs_end frees them; so do pepsgpu_opt_end and a new pepsgpu_opt_begin.
+ *   pepsgpu_lbfgs_reset    drops history, anchor and pending direction and zeroes the counters; the buffers stay.
+ *   pepsgpu_lbfgs_update   UpdateLBFGSHistoryFromAnchor_ (:1443-1486) from theta and the gradient buffer.  Without an anchor: nothing
+ *                          (*outcome = 0).  Else s = theta - theta_a, y = g - g_a, curvature = <s,y>; curvature <= min_curvature with
+ *                          use_damping and <y,y> > DBL_EPSILON: y += (delta / <y,y>) s, delta = min_curvature - curvature + 1e-15, and the
+ *                          curvature is taken again.  curvature <= min_curvature still: skipped (*outcome = 3), else pushed, evicting
+ *                          the oldest pair beyond history_size (*outcome = 1, 2 after damping).  *curvature = the last value.
+ *   pepsgpu_lbfgs_direction  ComputeLBFGSSearchDirection_ (:1488-1532): two-loop recursion with gamma = <s,y> / <y,y> of the newest pair
+ *                          (1 unless <y,y> > DBL_EPSILON and <s,y> > min_curvature), evaluated in the coefficients of [s_i, y_i, g] on
+ *                          the host in double from the inner products; the norm cap (max_direction_norm > 0: d *= max / |d| beyond
+ *                          it); the descent guard (:620-641): <g,d> >= 0 drops history and anchor and takes d = -g (*was_reset = 1).
+ *                          *dphi0 = <g,d>, *norm = |d|.  Records the base of the search: theta_b <- theta, g_b <- g.
+ *   pepsgpu_lbfgs_trial    theta = theta_b + alpha d and device state = T(theta) in one pass (:1581-1585, ApplyFixedLBFGSStep_
+ *                          :1534-1545); alpha = 0 restores theta_b bit for bit.
+ *   pepsgpu_lbfgs_slope    *dphi = <g, d> of the current gradient buffer (:1590).
+ *   pepsgpu_lbfgs_commit   the anchor becomes (theta_b, g_b) (:847-850; pointer exchange); the direction is consumed.
+ *   pepsgpu_lbfgs_get_direction / pepsgpu_lbfgs_get_pair   d / pair `index` of the history (0 = oldest; either output nullable) to the
+ *                          host in the upload layout, as pepsgpu_opt_get_gradient.
+ *   pepsgpu_lbfgs_counters out4 = [skipped pairs, damped pairs, descent resets, pairs in the history].  The descent-reset counter
+ *                          survives the reset it counts (the reference's own reset zeroes it).
+ * Status: PEPSGPU_ESTATE before pepsgpu_opt_begin (lbfgs_begin) / before pepsgpu_lbfgs_begin (all others), and for trial / slope /
+ * commit without a direction; PEPSGPU_EINVAL for a history_size outside [1, 32], a NaN parameter, a negative or non-finite alpha;
+ * PEPSGPU_ERANGE for an index outside the history.  A refused call leaves theta, g and the history untouched.
+ * The prefix is not pepsgpu_opt_, and L-BFGS is not a rule id of pepsgpu_opt_step: both sets are closed. */
+int pepsgpu_lbfgs_begin(pepsgpu_ctx *ctx, int history_size);
+int pepsgpu_lbfgs_end(pepsgpu_ctx *ctx);
+int pepsgpu_lbfgs_reset(pepsgpu_ctx *ctx);
+int pepsgpu_lbfgs_update(pepsgpu_ctx *ctx, double min_curvature, int use_damping, int *outcome, double *curvature);
+int pepsgpu_lbfgs_direction(pepsgpu_ctx *ctx, double min_curvature, double max_direction_norm, double *dphi0, double *norm,
+                            int *was_reset);
+int pepsgpu_lbfgs_trial(pepsgpu_ctx *ctx, double alpha);
+int pepsgpu_lbfgs_slope(pepsgpu_ctx *ctx, double *dphi);
+int pepsgpu_lbfgs_commit(pepsgpu_ctx *ctx);
+int pepsgpu_lbfgs_get_direction(pepsgpu_ctx *ctx, double *out);
+int pepsgpu_lbfgs_get_pair(pepsgpu_ctx *ctx, int index, double *s_out, double *y_out);
+int pepsgpu_lbfgs_counters(pepsgpu_ctx *ctx, long *out4);
+
 /* TPSWaveFunctionComponent::UpdateLocal (wave_function_component.h:345-378) for the walkers with
  * accept_mask[w] != 0 (NULL = all): config(site_k) = new_states[w][k], tn.UpdateSiteTensor,
  * contractor.EraseEnvsAfterUpdate(site_k) (trace.h:538-589).  sites = [n_sites][2] (row, col). */

@@ -44,6 +44,9 @@ SYMBOLS = [
     "pepsgpu_opt_begin", "pepsgpu_opt_end", "pepsgpu_opt_gradient_from_accumulators", "pepsgpu_opt_set_gradient",
     "pepsgpu_opt_get_gradient", "pepsgpu_opt_clip", "pepsgpu_opt_natural_gradient", "pepsgpu_opt_step", "pepsgpu_opt_scale_state",
     "pepsgpu_opt_read_state", "pepsgpu_fermion_decoration_set", "pepsgpu_minsr_direction", "pepsgpu_diag_eigh",
+    "pepsgpu_lbfgs_begin", "pepsgpu_lbfgs_end", "pepsgpu_lbfgs_reset", "pepsgpu_lbfgs_update", "pepsgpu_lbfgs_direction",
+    "pepsgpu_lbfgs_trial", "pepsgpu_lbfgs_slope", "pepsgpu_lbfgs_commit", "pepsgpu_lbfgs_get_direction", "pepsgpu_lbfgs_get_pair",
+    "pepsgpu_lbfgs_counters",
     "pepsgpu_update_local", "pepsgpu_erase_envs_after_update", "pepsgpu_evaluate_amplitude",
     "pepsgpu_walker_flags", "pepsgpu_sync", "pepsgpu_stats", "pepsgpu_profile_enable", "pepsgpu_profile_read",
     "pepsgpu_diag_tgemm", "pepsgpu_diag_tgemm_desc", "pepsgpu_diag_tgemm_route", "pepsgpu_diag_tgemm_chain", "pepsgpu_diag_tgemm_chain3", "pepsgpu_diag_chol", "pepsgpu_diag_chol_adaptive", "pepsgpu_diag_chol_pivot", "pepsgpu_diag_rows_qr", "pepsgpu_diag_suwa_todo", "pepsgpu_diag_dot4", "pepsgpu_diag_gram_chol", "pepsgpu_diag_gram_chol_wave", "pepsgpu_diag_gram_cols", "pepsgpu_diag_gram_rows", "pepsgpu_diag_mgemm_dense", "pepsgpu_diag_jacobi", "pepsgpu_diag_trunc_rows", "pepsgpu_version",
@@ -172,6 +175,18 @@ def load_library(path=LIB_PATH):
     if hasattr(lib, "pepsgpu_minsr_direction"):     # (PEPSGPU_LIB may name a build from before these entries)
         lib.pepsgpu_minsr_direction.argtypes = [vp, dp, dp, C.c_double, C.c_double, C.c_int, dp, dp]
         lib.pepsgpu_diag_eigh.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, ip]
+    if hasattr(lib, "pepsgpu_lbfgs_begin"):         # (PEPSGPU_LIB may name a build from before these entries)
+        lib.pepsgpu_lbfgs_begin.argtypes = [vp, C.c_int]
+        lib.pepsgpu_lbfgs_end.argtypes = [vp]
+        lib.pepsgpu_lbfgs_reset.argtypes = [vp]
+        lib.pepsgpu_lbfgs_update.argtypes = [vp, C.c_double, C.c_int, ip, dp]
+        lib.pepsgpu_lbfgs_direction.argtypes = [vp, C.c_double, C.c_double, dp, dp, ip]
+        lib.pepsgpu_lbfgs_trial.argtypes = [vp, C.c_double]
+        lib.pepsgpu_lbfgs_slope.argtypes = [vp, dp]
+        lib.pepsgpu_lbfgs_commit.argtypes = [vp]
+        lib.pepsgpu_lbfgs_get_direction.argtypes = [vp, dp]
+        lib.pepsgpu_lbfgs_get_pair.argtypes = [vp, C.c_int, dp, dp]
+        lib.pepsgpu_lbfgs_counters.argtypes = [vp, C.POINTER(C.c_long)]
     lib.pepsgpu_update_local.argtypes = [vp, C.c_int, ip, ip, C.POINTER(C.c_uint8)]
     lib.pepsgpu_erase_envs_after_update.argtypes = [vp, C.c_int, C.c_int]
     lib.pepsgpu_evaluate_amplitude.argtypes = [vp, dp]
@@ -684,6 +699,64 @@ class Context:
         self._ck(self._l.pepsgpu_minsr_direction(self._h, _dp(e), _dp(en), float(r_pinv), float(a_pinv), int(bool(soft_cutoff)),
                                                  _dp(nrm), _dp(info)))
         return float(nrm[0]), {"lambda_max": float(info[0]), "cutoff": float(info[1]), "n_kept": int(info[2]), "sweeps": int(info[3])}
+
+    # -- L-BFGS on the optimizer buffers: history, anchor, direction and the base of the line search stay in HBM (pepsgpu_lbfgs_*) --
+    LBFGS_NONE, LBFGS_PUSHED, LBFGS_PUSHED_DAMPED, LBFGS_SKIPPED = 0, 1, 2, 3
+
+    def lbfgs_begin(self, history_size):
+        self._ck(self._l.pepsgpu_lbfgs_begin(self._h, int(history_size)))
+
+    def lbfgs_end(self):
+        self._ck(self._l.pepsgpu_lbfgs_end(self._h))
+
+    def lbfgs_reset(self):
+        self._ck(self._l.pepsgpu_lbfgs_reset(self._h))
+
+    def lbfgs_update(self, min_curvature=1e-12, use_damping=True):
+        """history update from the anchor, theta and the gradient buffer; returns (outcome, curvature): 0 no anchor, 1 pushed,
+        2 pushed after damping, 3 skipped"""
+        oc = np.zeros(1, dtype=np.int32)
+        cv = np.zeros(1, dtype=np.float64)
+        self._ck(self._l.pepsgpu_lbfgs_update(self._h, float(min_curvature), int(bool(use_damping)), _ip(oc), _dp(cv)))
+        return int(oc[0]), float(cv[0])
+
+    def lbfgs_direction(self, min_curvature=1e-12, max_direction_norm=1e3):
+        """d <- the two-loop direction of the gradient buffer (norm cap, descent guard), base of the search <- (theta, g); returns
+        (<g,d>, |d|, was_reset)"""
+        out = np.zeros(2, dtype=np.float64)
+        rs = np.zeros(1, dtype=np.int32)
+        self._ck(self._l.pepsgpu_lbfgs_direction(self._h, float(min_curvature), float(max_direction_norm), _dp(out[:1]), _dp(out[1:]),
+                                                 _ip(rs)))
+        return float(out[0]), float(out[1]), bool(rs[0])
+
+    def lbfgs_trial(self, alpha):
+        """theta = theta_base + alpha d, device state = T(theta)"""
+        self._ck(self._l.pepsgpu_lbfgs_trial(self._h, float(alpha)))
+
+    def lbfgs_slope(self):
+        out = np.zeros(1, dtype=np.float64)
+        self._ck(self._l.pepsgpu_lbfgs_slope(self._h, _dp(out)))
+        return float(out[0])
+
+    def lbfgs_commit(self):
+        self._ck(self._l.pepsgpu_lbfgs_commit(self._h))
+
+    def lbfgs_get_direction(self):
+        out = np.zeros(self._state_shape(), dtype=self._ot)
+        self._ck(self._l.pepsgpu_lbfgs_get_direction(self._h, _dp(out)))
+        return out
+
+    def lbfgs_get_pair(self, index):
+        """(s, y) of pair `index` of the history, 0 = oldest"""
+        s = np.zeros(self._state_shape(), dtype=self._ot)
+        y = np.zeros(self._state_shape(), dtype=self._ot)
+        self._ck(self._l.pepsgpu_lbfgs_get_pair(self._h, int(index), _dp(s), _dp(y)))
+        return s, y
+
+    def lbfgs_counters(self):
+        out = (C.c_long * 4)()
+        self._ck(self._l.pepsgpu_lbfgs_counters(self._h, out))
+        return {"skip_curvature": int(out[0]), "damping": int(out[1]), "descent_reset": int(out[2]), "history": int(out[3])}
 
     def diag_eigh(self, a):
         """the device eigensolver alone: a real symmetric or complex Hermitian matrix -> (w ascending, z with A z[:, k] = w[k] z[:, k],

@@ -5,6 +5,7 @@
 #include "engine_nnn.h"
 #include "engine_sr.h"
 #include "engine_opt.h"
+#include "engine_lbfgs.h"
 #include "engine_var.h"
 #include "engine_cplx.h"
 #include "engine_walker.h"
@@ -531,6 +532,31 @@ int pepsgpu_opt_read_state(pepsgpu_ctx *ctx, double *host) {
 int pepsgpu_minsr_direction(pepsgpu_ctx *ctx, const double *eloc, const double *energy, double r_pinv, double a_pinv, int soft_cutoff,
                             double *direction_norm_out, double *info_out) {
   CTX_CALL(ctx->eng->minsr_direction(eloc, energy, r_pinv, a_pinv, soft_cutoff, direction_norm_out, info_out));
+}
+// ---- L-BFGS on the optimizer buffers (engine_lbfgs.h) ----
+int pepsgpu_lbfgs_begin(pepsgpu_ctx *ctx, int history_size) { CTX_CALL(ctx->eng->lbfgs_begin(history_size)); }
+int pepsgpu_lbfgs_end(pepsgpu_ctx *ctx) { CTX_CALL(ctx->eng->lbfgs_end()); }
+int pepsgpu_lbfgs_reset(pepsgpu_ctx *ctx) { CTX_CALL(ctx->eng->lbfgs_reset()); }
+int pepsgpu_lbfgs_update(pepsgpu_ctx *ctx, double min_curvature, int use_damping, int *outcome, double *curvature) {
+  CTX_CALL(ctx->eng->lbfgs_update(min_curvature, use_damping, outcome, curvature));
+}
+int pepsgpu_lbfgs_direction(pepsgpu_ctx *ctx, double min_curvature, double max_direction_norm, double *dphi0, double *norm,
+                            int *was_reset) {
+  CTX_CALL(ctx->eng->lbfgs_direction(min_curvature, max_direction_norm, dphi0, norm, was_reset));
+}
+int pepsgpu_lbfgs_trial(pepsgpu_ctx *ctx, double alpha) { CTX_CALL(ctx->eng->lbfgs_trial(alpha)); }
+int pepsgpu_lbfgs_slope(pepsgpu_ctx *ctx, double *dphi) {
+  CTX_CALL(PG_REQUIRE(dphi != nullptr, 1, "null output"); ctx->eng->lbfgs_slope(dphi));
+}
+int pepsgpu_lbfgs_commit(pepsgpu_ctx *ctx) { CTX_CALL(ctx->eng->lbfgs_commit()); }
+int pepsgpu_lbfgs_get_direction(pepsgpu_ctx *ctx, double *out) {
+  CTX_CALL(PG_REQUIRE(out != nullptr, 1, "null output"); ctx->eng->lbfgs_get_direction(out));
+}
+int pepsgpu_lbfgs_get_pair(pepsgpu_ctx *ctx, int index, double *s_out, double *y_out) {
+  CTX_CALL(ctx->eng->lbfgs_get_pair(index, s_out, y_out));
+}
+int pepsgpu_lbfgs_counters(pepsgpu_ctx *ctx, long *out4) {
+  CTX_CALL(PG_REQUIRE(out4 != nullptr, 1, "null output"); ctx->eng->lbfgs_counters(out4));
 }
 // the eigensolver of pepsgpu_minsr_direction alone, on the context's device and stream (eigh_jacobi.h)
 int pepsgpu_diag_eigh(pepsgpu_ctx *ctx, int n, int is_complex, const double *a, double *w_out, double *z_out, int *sweeps_out) {

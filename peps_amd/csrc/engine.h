@@ -132,6 +132,18 @@ struct EngineBase {
   virtual void minsr_direction(const double *eloc, const double *energy, double r_pinv, double a_pinv, int soft_cutoff,
                                double *direction_norm_out, double *info_out) = 0;
   virtual void fermion_decoration_set(int d, const int32_t *nf, const uint8_t *bond_parity) = 0;
+  // L-BFGS on the optimizer buffers (engine_lbfgs.h): history ring, anchor, direction and the base of the line search in HBM
+  virtual void lbfgs_begin(int history_size) = 0;
+  virtual void lbfgs_end() = 0;
+  virtual void lbfgs_reset() = 0;
+  virtual void lbfgs_update(double min_curvature, int use_damping, int *outcome, double *curvature) = 0;
+  virtual void lbfgs_direction(double min_curvature, double max_direction_norm, double *dphi0, double *norm, int *was_reset) = 0;
+  virtual void lbfgs_trial(double alpha) = 0;
+  virtual void lbfgs_slope(double *dphi) = 0;
+  virtual void lbfgs_commit() = 0;
+  virtual void lbfgs_get_direction(double *host) = 0;
+  virtual void lbfgs_get_pair(int index, double *s_host, double *y_host) = 0;
+  virtual void lbfgs_counters(long *out) = 0;
   // one row / column of exchange moves (pair_table nullable) and of full-space moves (Suwa-Todo over phys_dim^2 states); engine_sweep.h
   virtual void sweep_slice_exchange(int orient, int slice, int n_uniform, const double *uniforms, const int32_t *pair_table,
                                     double *amp_inout, int32_t *consumed_out, int32_t *accepted_out, int32_t *slice_states_out) = 0;
@@ -873,6 +885,24 @@ class Engine : public EngineBase {
   void opt_read(const double *dev, double *host);
   double opt_norm_sq(const double *x);
   dim3 opt_grid() const { return dim3((unsigned)((slot_ + 255) / 256), (unsigned)(Ly_ * Lx_ * dp_)); }
+  // ---- L-BFGS (engine_lbfgs.h) ----
+  void lbfgs_begin(int history_size) override;
+  void lbfgs_end() override;
+  void lbfgs_reset() override;
+  void lbfgs_update(double min_curvature, int use_damping, int *outcome, double *curvature) override;
+  void lbfgs_direction(double min_curvature, double max_direction_norm, double *dphi0, double *norm, int *was_reset) override;
+  void lbfgs_trial(double alpha) override;
+  void lbfgs_slope(double *dphi) override;
+  void lbfgs_commit() override;
+  void lbfgs_get_direction(double *host) override;
+  void lbfgs_get_pair(int index, double *s_host, double *y_host) override;
+  void lbfgs_counters(long *out) override;
+  void lbfgs_release();
+  int lbfgs_vec() const { return ((long)slot_ * kOut) % 2 == 0 ? 2 : 1; }      // doubles per load: rows of odd length start unaligned
+  dim3 lbfgs_grid() const;
+  void lbfgs_reduce(int nblocks, int k, double *host_out);
+  void lbfgs_mdot(const double *x, const double *const *vecs, int k, double *host_out);
+  void lbfgs_combine(const double *const *vecs, const double *coef, int k, double cg, double *dd, double *gd);
 
   // out layout = state upload layout [row][col][s][L][D][R][U] zero padded to D
   void grad_read(double *so, double *seo) override {
@@ -1648,6 +1678,19 @@ class Engine : public EngineBase {
   // MinSR scratch (minsr_direction): T then Z^T, the rotation accumulator, the eigensolver's workspace and the Ns-long vectors
   double *minsr_t_ = nullptr, *minsr_v_ = nullptr, *minsr_work_ = nullptr;
   int minsr_cap_ = 0;                      // sample count the scratch was sized for
+  // L-BFGS buffers (engine_lbfgs.h), every vector in the layout of opt_theta_.  The ring has history_size + 1 slots: a new pair is
+  // written into the free one, so that a pair the curvature test skips evicts nothing.
+  int lb_m_ = 0;                           // history_size; 0: no L-BFGS buffers
+  std::vector<double *> lb_s_, lb_y_;      // [lb_m_ + 1] ring slots
+  double *lb_theta_a_ = nullptr, *lb_g_a_ = nullptr;   // anchor
+  double *lb_theta_b_ = nullptr, *lb_g_b_ = nullptr;   // base of the current search
+  double *lb_d_ = nullptr, *lb_part_ = nullptr;
+  int lb_head_ = 0, lb_count_ = 0;         // slot of the oldest pair, live pairs
+  bool lb_has_anchor_ = false, lb_has_dir_ = false;
+  long lb_skip_ = 0, lb_damp_ = 0, lb_descent_reset_ = 0;
+  std::vector<double> lb_rho_, lb_sy_, lb_yy_;   // per ring slot
+  std::vector<double> lb_gram_;            // inner products among the ring vectors, [2 (m + 1)]^2: s of slot p at p, y at m + 1 + p
+  static constexpr int kLbfgsMaxHistory = 32, kLbfgsMaxBlocks = 2048;
   // ---- BMPSWalker objects (engine_walker.h) ----
   struct WalkerDev {
     BMPSDev b;                       // the forked boundary MPS (all walkers of the context)

@@ -249,6 +249,7 @@ __global__ __launch_bounds__(256) void opt_step_kernel(OptStepArgs a, double *__
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 void Engine<T>::opt_release() {
+  lbfgs_release();      // (engine_lbfgs.h: its vectors have the extents of these)
   for (double *p : {opt_theta_, opt_g_, opt_vel_, opt_m1_, opt_m2_, opt_acc_, opt_part_}) arena_.free(p);
   arena_.free(opt_ne_);
   arena_.free(opt_sign_);

@@ -697,6 +697,94 @@ void fermion_optimize_exact_sum_impl(int rows, int cols, int D, int d, const int
   copy_out(opt.GetState(rows, cols, d, D).flat(), state_out);
 }
 
+// ---- L-BFGS (LBFGSParams) with the exact-summation evaluator, the whole loop in one call.  lbfgs = the fourteen fields of LBFGSParams in
+// their order (step_mode 0 fixed, 1 strong Wolfe; the two flags as 0 / 1).  energies_out / grad_norms_out: up to iterations + 1 entries,
+// steps_out: up to iterations; info_out = [energies written, steps written, skipped pairs, damped pairs, descent resets, line-search
+// evaluations, converged].  state_out is written on every exit, a failed line search included (the state is then the base of that search).
+inline LBFGSParams make_lbfgs(const double *q) {
+  if (!q) throw std::invalid_argument("L-BFGS: the parameter array is required");
+  for (int i : {0, 3}) if (!(q[i] >= 0.0 && q[i] < 1e9)) throw std::invalid_argument("L-BFGS: history_size / max_eval out of range");
+  return LBFGSParams((size_t)q[0], q[1], q[2], (size_t)q[3], q[4] != 0.0 ? LBFGSStepMode::kStrongWolfe : LBFGSStepMode::kFixed, q[5], q[6],
+                     q[7], q[8], q[9], q[10] != 0.0, q[11], q[12] != 0.0, q[13]);
+}
+template <typename TenElemT, typename Run>
+void lbfgs_drive(Optimizer<TenElemT> &opt, Run &&run, int rows, int cols, int d, int D, double *energies_out, double *grad_norms_out,
+                 double *steps_out, double *state_out, double *info_out) {
+  typename Optimizer<TenElemT>::OptimizationResult res;
+  try {
+    res = run();
+  } catch (...) {
+    copy_out(opt.GetState(rows, cols, d, D).flat(), state_out);
+    throw;
+  }
+  copy_out(res.energy_trajectory, energies_out);
+  if (grad_norms_out) std::copy(res.gradient_norms.begin(), res.gradient_norms.end(), grad_norms_out);
+  if (steps_out) std::copy(res.learning_rate_trajectory.begin(), res.learning_rate_trajectory.end(), steps_out);
+  copy_out(opt.GetState(rows, cols, d, D).flat(), state_out);
+  if (info_out) {
+    info_out[0] = (double)res.energy_trajectory.size(); info_out[1] = (double)res.learning_rate_trajectory.size();
+    info_out[2] = (double)res.lbfgs_skip_curvature_count; info_out[3] = (double)res.lbfgs_damping_count;
+    info_out[4] = (double)res.lbfgs_descent_reset_count; info_out[5] = (double)res.lbfgs_line_search_evaluations;
+    info_out[6] = res.converged ? 1.0 : 0.0;
+  }
+}
+inline OptimizerParams::BaseParams lbfgs_base(int iterations, double energy_tolerance, double gradient_tolerance, int plateau_patience,
+                                              double lr) {
+  // a patience <= 0 switches the plateau criterion off, as the tolerances of 0 do theirs
+  return OptimizerParams::BaseParams((size_t)iterations, energy_tolerance, gradient_tolerance,
+                                     plateau_patience > 0 ? (size_t)plateau_patience : (size_t)iterations + 1, lr);
+}
+
+template <typename TenElemT>
+void lbfgs_exact_sum_impl(int rows, int cols, int D, int d, int chi, int dtype, const double *sitps_flat, const int32_t *all_configs,
+                          int n_configs, int model, const double *p, double lr, const double *lbfgs, int iterations,
+                          double energy_tolerance, double gradient_tolerance, int plateau_patience, int batch, double *energies_out,
+                          double *grad_norms_out, double *steps_out, double *state_out, double *info_out) {
+  if (iterations < 0 || n_configs < 1 || batch < 1) throw std::invalid_argument("pepshost_lbfgs_exact_sum: bad iterations / n_configs / batch");
+  if (model < 0 || model > 4) throw std::invalid_argument("pepshost_lbfgs_exact_sum: model must be xxz, tfim, j1j2, triangle or trij1j2");
+  const LBFGSParams lp = make_lbfgs(lbfgs);
+  SplitIndexTPST<TenElemT> sitps = make_state_t<TenElemT>(rows, cols, D, d, sitps_flat);
+  BMPSContractorT<TenElemT> contractor(rows, cols, D, d, trunc_params(chi), batch, dtype, g_device);
+  std::vector<std::vector<int32_t>> all(n_configs);
+  for (int i = 0; i < n_configs; ++i) all[i].assign(all_configs + (size_t)i * rows * cols, all_configs + (size_t)(i + 1) * rows * cols);
+  contractor.UploadState(sitps);
+  Optimizer<TenElemT> opt(OptimizerParams(lbfgs_base(iterations, energy_tolerance, gradient_tolerance, plateau_patience, lr), lp), contractor);
+  auto run = [&](auto &m) {
+    return opt.IterativeOptimize([&](BMPSContractorT<TenElemT> &c) { return ExactSumAccumulateResident(sitps, all, c, m, (size_t)batch); });
+  };
+  lbfgs_drive(opt, [&]() {
+    if (model == 0) { SquareSpinOneHalfXXZModelOBC m(p[0], p[1], p[2]); return run(m); }
+    if (model == 2) { SquareSpinOneHalfJ1J2XXZModelOBC m(p[0], p[1], p[2], p[3], p[4]); return run(m); }
+    if (model == 3) { SpinOneHalfTriHeisenbergSqrPEPS m; return run(m); }
+    if (model == 4) { SpinOneHalfTriJ1J2HeisenbergSqrPEPS m(p[0]); return run(m); }
+    TransverseFieldIsingSquareOBC m(p[0]);
+    return run(m);
+  }, rows, cols, d, D, energies_out, grad_norms_out, steps_out, state_out, info_out);
+}
+
+template <typename TenElemT>
+void fermion_lbfgs_exact_sum_impl(int rows, int cols, int D, int d, const int32_t *nf, const uint8_t *bond_parity, int chi, int dtype,
+                                  const double *sitps_ext_flat, const int32_t *all_configs, int n_configs, int model, const double *prm,
+                                  int n_prm, double lr, const double *lbfgs, int iterations, double energy_tolerance,
+                                  double gradient_tolerance, int plateau_patience, int batch, double *energies_out, double *grad_norms_out,
+                                  double *steps_out, double *state_out, double *info_out) {
+  if (iterations < 0 || n_configs < 1 || batch < 1) throw std::invalid_argument("pepshost_fermion_lbfgs_exact_sum: bad iterations / n_configs / batch");
+  const LBFGSParams lp = make_lbfgs(lbfgs);
+  const FermionDecoration dec = make_decoration(rows, cols, D, d, nf, bond_parity);
+  SplitIndexTPST<TenElemT> sitps = make_state_t<TenElemT>(rows, cols, D, 4 * d, sitps_ext_flat);
+  BMPSContractorT<TenElemT> contractor(rows, cols, D, 4 * d, trunc_params(chi), batch, dtype, g_device);
+  std::vector<std::vector<int32_t>> all(n_configs);
+  for (int i = 0; i < n_configs; ++i) all[i].assign(all_configs + (size_t)i * rows * cols, all_configs + (size_t)(i + 1) * rows * cols);
+  contractor.UploadState(sitps);
+  Optimizer<TenElemT> opt(OptimizerParams(lbfgs_base(iterations, energy_tolerance, gradient_tolerance, plateau_patience, lr), lp), contractor,
+                          &dec);
+  lbfgs_drive(opt, [&]() {
+    return with_fermion_model<TenElemT>(model, prm, n_prm, [&](auto &m) {
+      return opt.IterativeOptimize([&](BMPSContractorT<TenElemT> &c) { return ExactSumAccumulateResident(sitps, all, c, m, (size_t)batch, &dec); });
+    });
+  }, rows, cols, d, D, energies_out, grad_norms_out, steps_out, state_out, info_out);
+}
+
 // sr_step_samples_impl on a fermionic state; info_out as there, the norms over the stored parameters
 template <typename TenElemT>
 void fermion_sr_step_samples_impl(int rows, int cols, int D, int d, const int32_t *nf, const uint8_t *bond_parity, int chi, int dtype,
@@ -975,6 +1063,50 @@ int pepshost_minsr_step_samples_c128(int rows, int cols, int D, int d, int chi, 
   return guarded([&]() {
     minsr_step_samples_impl<QLTEN_Complex>(rows, cols, D, d, chi, PEPSGPU_C128, sitps_flat, n, configs, model, p, lr, r_pinv, a_pinv,
                                            soft_cutoff, exact_sum, state_out, info_out);
+  });
+}
+// Optimizer::IterativeOptimize with LBFGSParams + exact summation (see lbfgs_exact_sum_impl)
+int pepshost_lbfgs_exact_sum(int rows, int cols, int D, int d, int chi, int dtype, const double *sitps_flat, const int32_t *all_configs,
+                             int n_configs, int model, const double *p, double lr, const double *lbfgs, int iterations,
+                             double energy_tolerance, double gradient_tolerance, int plateau_patience, int batch, double *energies_out,
+                             double *grad_norms_out, double *steps_out, double *state_out, double *info_out) {
+  return guarded([&]() {
+    lbfgs_exact_sum_impl<double>(rows, cols, D, d, chi, dtype, sitps_flat, all_configs, n_configs, model, p, lr, lbfgs, iterations,
+                                 energy_tolerance, gradient_tolerance, plateau_patience, batch, energies_out, grad_norms_out, steps_out,
+                                 state_out, info_out);
+  });
+}
+int pepshost_lbfgs_exact_sum_c128(int rows, int cols, int D, int d, int chi, const double *sitps_flat, const int32_t *all_configs,
+                                  int n_configs, int model, const double *p, double lr, const double *lbfgs, int iterations,
+                                  double energy_tolerance, double gradient_tolerance, int plateau_patience, int batch,
+                                  double *energies_out, double *grad_norms_out, double *steps_out, double *state_out, double *info_out) {
+  return guarded([&]() {
+    lbfgs_exact_sum_impl<QLTEN_Complex>(rows, cols, D, d, chi, PEPSGPU_C128, sitps_flat, all_configs, n_configs, model, p, lr, lbfgs,
+                                        iterations, energy_tolerance, gradient_tolerance, plateau_patience, batch, energies_out,
+                                        grad_norms_out, steps_out, state_out, info_out);
+  });
+}
+int pepshost_fermion_lbfgs_exact_sum(int rows, int cols, int D, int d, const int32_t *nf, const uint8_t *bond_parity, int chi, int dtype,
+                                     const double *sitps_ext_flat, const int32_t *all_configs, int n_configs, int model, const double *prm,
+                                     int n_prm, double lr, const double *lbfgs, int iterations, double energy_tolerance,
+                                     double gradient_tolerance, int plateau_patience, int batch, double *energies_out,
+                                     double *grad_norms_out, double *steps_out, double *state_out, double *info_out) {
+  return guarded([&]() {
+    fermion_lbfgs_exact_sum_impl<double>(rows, cols, D, d, nf, bond_parity, chi, dtype, sitps_ext_flat, all_configs, n_configs, model, prm,
+                                         n_prm, lr, lbfgs, iterations, energy_tolerance, gradient_tolerance, plateau_patience, batch,
+                                         energies_out, grad_norms_out, steps_out, state_out, info_out);
+  });
+}
+int pepshost_fermion_lbfgs_exact_sum_c128(int rows, int cols, int D, int d, const int32_t *nf, const uint8_t *bond_parity, int chi,
+                                          const double *sitps_ext_flat, const int32_t *all_configs, int n_configs, int model,
+                                          const double *prm, int n_prm, double lr, const double *lbfgs, int iterations,
+                                          double energy_tolerance, double gradient_tolerance, int plateau_patience, int batch,
+                                          double *energies_out, double *grad_norms_out, double *steps_out, double *state_out,
+                                          double *info_out) {
+  return guarded([&]() {
+    fermion_lbfgs_exact_sum_impl<QLTEN_Complex>(rows, cols, D, d, nf, bond_parity, chi, PEPSGPU_C128, sitps_ext_flat, all_configs,
+                                                n_configs, model, prm, n_prm, lr, lbfgs, iterations, energy_tolerance, gradient_tolerance,
+                                                plateau_patience, batch, energies_out, grad_norms_out, steps_out, state_out, info_out);
   });
 }
 // Optimizer::IterativeOptimize + exact summation on a fermionic state (see fermion_optimize_exact_sum_impl)

@@ -676,6 +676,33 @@ class BMPSContractorT {
     check_rc(pepsgpu_opt_step(ctx_, rule, lr, params.data(), (int)params.size()), ctx_);
   }
   void OptScaleState(double factor) { check_rc(pepsgpu_opt_scale_state(ctx_, factor), ctx_); }
+  // L-BFGS on the optimizer buffers (pepsgpu_lbfgs_*): history, anchor, direction and the base of the line search stay in HBM
+  void LBFGSBegin(size_t history_size) { check_rc(pepsgpu_lbfgs_begin(ctx_, (int)std::min<size_t>(history_size, 1u << 20)), ctx_); }
+  void LBFGSReset() { check_rc(pepsgpu_lbfgs_reset(ctx_), ctx_); }
+  struct LBFGSUpdateInfo { int outcome = 0; double curvature = 0.0; };      // outcome: 0 no anchor, 1 pushed, 2 pushed after damping, 3 skipped
+  LBFGSUpdateInfo LBFGSUpdate(double min_curvature, bool use_damping) {
+    LBFGSUpdateInfo r;
+    check_rc(pepsgpu_lbfgs_update(ctx_, min_curvature, use_damping ? 1 : 0, &r.outcome, &r.curvature), ctx_);
+    return r;
+  }
+  struct LBFGSDirectionInfo { double dphi0 = 0.0, norm = 0.0; bool was_reset = false; };
+  LBFGSDirectionInfo LBFGSDirection(double min_curvature, double max_direction_norm) {
+    LBFGSDirectionInfo r;
+    int reset = 0;
+    check_rc(pepsgpu_lbfgs_direction(ctx_, min_curvature, max_direction_norm, &r.dphi0, &r.norm, &reset), ctx_);
+    r.was_reset = reset != 0;
+    return r;
+  }
+  void LBFGSTrial(double alpha) { check_rc(pepsgpu_lbfgs_trial(ctx_, alpha), ctx_); }
+  double LBFGSSlope() { double d = 0.0; check_rc(pepsgpu_lbfgs_slope(ctx_, &d), ctx_); return d; }
+  void LBFGSCommit() { check_rc(pepsgpu_lbfgs_commit(ctx_), ctx_); }
+  void LBFGSGetDirection(SplitIndexTPST<TenElemT> &d) const { check_rc(pepsgpu_lbfgs_get_direction(ctx_, dptr(d.flat().data())), ctx_); }
+  struct LBFGSCounters { size_t skip_curvature = 0, damping = 0, descent_reset = 0, history = 0; };
+  LBFGSCounters LBFGSGetCounters() const {
+    long c[4] = {0, 0, 0, 0};
+    check_rc(pepsgpu_lbfgs_counters(ctx_, c), ctx_);
+    return {(size_t)c[0], (size_t)c[1], (size_t)c[2], (size_t)c[3]};
+  }
   void OptReadState(SplitIndexTPST<TenElemT> &s) const { check_rc(pepsgpu_opt_read_state(ctx_, dptr(s.flat().data())), ctx_); }
   void SRBegin(size_t max_samples) { check_rc(pepsgpu_sr_begin(ctx_, (int)max_samples), ctx_); }
   void SRAppend(const std::vector<TenElemT> &psi) { check_rc(pepsgpu_sr_append(ctx_, dptr(psi.data())), ctx_); }
@@ -3613,9 +3640,12 @@ std::pair<TenElemT, SplitIndexTPST<TenElemT>> ExactSumEnergyEvaluator(const Spli
 // step with no tensor traffic over PCIe.  In: SGD, AdaGrad, Adam and the one-rank SR step, for bosonic and for fermionic states (a
 // FermionDecoration with bond parities: the buffers hold the 4 d decorated components, gradients are folded and projected on the
 // device, norms and the SR solve are those of the stored parameters); the one-rank MinSR step (MinSRParams: T matrix, eigensolve,
-// cutoff and back-substitution on the device, pepsgpu_minsr_direction) for bosonic states.  Out (host drivers of the reference
-// that stay with the caller): L-BFGS, step selectors / line search, spike detection, checkpoints, CSV / JSONL logs, MinSR
-// over several ranks or on a fermionic state (peps_amd/sr.py), multi-rank CG.  Parameter names and defaults: optimizer/optimizer_params.h.
+// cutoff and back-substitution on the device, pepsgpu_minsr_direction) for bosonic states; L-BFGS (LBFGSParams) with the fixed step or
+// the strong-Wolfe line search for bosonic and fermionic states: history, anchor, direction and the base of the search in HBM
+// (pepsgpu_lbfgs_*), every trial point one element-wise pass, one evaluation of the resident state and one dot product.  Out (host
+// drivers of the reference that stay with the caller): step selectors, spike detection and its L-BFGS snapshots, checkpoints, CSV /
+// JSONL logs, MinSR over several ranks or on a fermionic state (peps_amd/sr.py), multi-rank CG and the multi-rank broadcast of the
+// L-BFGS direction.  Parameter names and defaults: optimizer/optimizer_params.h.
 struct ConjugateGradientParams {               // optimizer_params.h:50-57
   size_t max_iter = 100;
   double relative_tolerance = 1e-4;
@@ -3696,8 +3726,32 @@ struct MinSRParams {                           // :220-232
       : r_pinv(r_pinv), a_pinv(a_pinv), soft_cutoff(soft_cutoff), solver_mode(solver_mode) {}
 };
 
-// (MinSRParams is the last alternative: the others keep their indices)
-using AlgorithmParams = std::variant<SGDParams, AdamParams, StochasticReconfigurationParams, AdaGradParams, MinSRParams>;
+enum class LBFGSStepMode { kFixed = 0, kStrongWolfe = 1 };   // :110-113
+struct LBFGSParams {                           // :119-152
+  size_t history_size;                         // pairs kept, 1..32 on the device
+  double tolerance_grad;                       // absolute floor for |phi'(alpha)| in the strong-Wolfe curvature test
+  double tolerance_change;                     // interval / step tolerance of the line search
+  size_t max_eval;                             // evaluations per line search
+  LBFGSStepMode step_mode;
+  double wolfe_c1, wolfe_c2;                   // 0 < c1 < c2 < 1
+  double min_step, max_step;
+  double min_curvature;                        // smallest Re<s,y> of an accepted pair
+  bool use_damping;
+  double max_direction_norm;                   // cap of |d|; <= 0: off
+  bool allow_fallback_to_fixed_step;           // a failed search takes max(min_step, lr * fallback_fixed_step_scale) instead of throwing
+  double fallback_fixed_step_scale;
+  LBFGSParams(size_t hist = 10, double tol_grad = 1e-5, double tol_change = 1e-9, size_t max_eval = 20,
+              LBFGSStepMode step_mode = LBFGSStepMode::kFixed, double wolfe_c1 = 1e-4, double wolfe_c2 = 0.9, double min_step = 1e-8,
+              double max_step = 1.0, double min_curvature = 1e-12, bool use_damping = true, double max_direction_norm = 1e3,
+              bool allow_fallback_to_fixed_step = false, double fallback_fixed_step_scale = 0.2)
+      : history_size(hist), tolerance_grad(tol_grad), tolerance_change(tol_change), max_eval(max_eval), step_mode(step_mode),
+        wolfe_c1(wolfe_c1), wolfe_c2(wolfe_c2), min_step(min_step), max_step(max_step), min_curvature(min_curvature),
+        use_damping(use_damping), max_direction_norm(max_direction_norm), allow_fallback_to_fixed_step(allow_fallback_to_fixed_step),
+        fallback_fixed_step_scale(fallback_fixed_step_scale) {}
+};
+
+// (MinSRParams, then LBFGSParams, were appended: the others keep their indices)
+using AlgorithmParams = std::variant<SGDParams, AdamParams, StochasticReconfigurationParams, AdaGradParams, MinSRParams, LBFGSParams>;
 
 struct OptimizerParams {                       // optimizer_params.h:348-473
   struct BaseParams {                          // :365-425
@@ -3759,6 +3813,10 @@ class Optimizer {
     bool converged = false;
     size_t sr_iterations = 0;                   // of the last SR step
     double sr_natural_grad_norm = 0.0, sr_residual_norm = 0.0;
+    // L-BFGS: the counters of the reference's optimizer, the evaluations its line searches made (they do not enter
+    // energy_trajectory) and the step length of every iteration
+    size_t lbfgs_skip_curvature_count = 0, lbfgs_damping_count = 0, lbfgs_descent_reset_count = 0, lbfgs_line_search_evaluations = 0;
+    std::vector<double> learning_rate_trajectory;
   };
 
   // adopts the state the contractor holds (UploadState first).  Fermionic states: the contractor holds the 4 d decorated components
@@ -3838,8 +3896,133 @@ class Optimizer {
     return gradient_norm < b.gradient_tolerance || std::abs(current_energy - previous_energy) < b.energy_tolerance ||
            iterations_without_improvement >= b.plateau_patience;
   }
+  // StrongWolfeLBFGSStep_ (optimizer_impl.h:1547-1662) on the direction and base the device holds: every trial is one element-wise
+  // pass (theta = theta_base + alpha d), `evaluate_trial` (phi, the gradient buffer) and one dot product (phi').  Returns the
+  // accepted step length with theta at that point, or a negative value with theta wherever the last trial left it.
+  double StrongWolfeLBFGSStep(const std::function<double()> &evaluate_trial, double learning_rate, const LBFGSParams &p, double phi0,
+                              double dphi0, size_t &eval_count) {
+    if (p.wolfe_c1 <= 0.0 || p.wolfe_c1 >= 1.0 || p.wolfe_c2 <= p.wolfe_c1 || p.wolfe_c2 >= 1.0)
+      throw std::invalid_argument("LBFGS strong-Wolfe parameters must satisfy 0 < c1 < c2 < 1");
+    if (p.max_eval == 0) throw std::invalid_argument("LBFGS max_eval must be > 0 for strong-Wolfe mode");
+    if (p.tolerance_grad < 0.0) throw std::invalid_argument("LBFGS tolerance_grad must be >= 0 for strong-Wolfe mode");
+    if (dphi0 >= 0.0) return -1.0;
+    const double curvature_threshold = std::max(-p.wolfe_c2 * dphi0, p.tolerance_grad);
+    eval_count = 0;
+    auto eval_alpha = [&](double alpha, double *phi, double *dphi) {
+      c_.LBFGSTrial(alpha);
+      *phi = evaluate_trial();
+      *dphi = c_.LBFGSSlope();
+      ++eval_count;
+    };
+    auto zoom = [&](double alo, double phi_alo, double ahi) -> double {
+      while (eval_count < p.max_eval) {
+        const double alpha = 0.5 * (alo + ahi);
+        double phi = 0.0, dphi = 0.0;
+        eval_alpha(alpha, &phi, &dphi);
+        if ((phi > phi0 + p.wolfe_c1 * alpha * dphi0) || (phi >= phi_alo)) {
+          ahi = alpha;
+        } else {
+          if (std::abs(dphi) <= curvature_threshold) return alpha;
+          if (dphi * (ahi - alo) >= 0.0) ahi = alo;
+          alo = alpha;
+          phi_alo = phi;
+        }
+        if (std::abs(ahi - alo) <= p.tolerance_change) break;
+      }
+      return -1.0;
+    };
+    double alpha_prev = 0.0, phi_prev = phi0;
+    double alpha = std::clamp(std::max(learning_rate, p.min_step), p.min_step, p.max_step);
+    if (alpha <= 0.0) alpha = p.min_step;
+    for (size_t outer = 0; eval_count < p.max_eval; ++outer) {
+      double phi = 0.0, dphi = 0.0;
+      eval_alpha(alpha, &phi, &dphi);
+      if ((phi > phi0 + p.wolfe_c1 * alpha * dphi0) || (outer > 0 && phi >= phi_prev)) return zoom(alpha_prev, phi_prev, alpha);
+      if (std::abs(dphi) <= curvature_threshold) return alpha;
+      if (dphi >= 0.0) return zoom(alpha, phi, alpha_prev);
+      alpha_prev = alpha;
+      phi_prev = phi;
+      const double next_alpha = std::min(alpha * 2.0, p.max_step);
+      if (next_alpha - alpha <= p.tolerance_change) break;
+      alpha = next_alpha;
+    }
+    return -1.0;
+  }
+  // The L-BFGS schedule of IterativeOptimize (optimizer_impl.h:244-249, 619-675, 847-857): evaluate -> history update from the anchor
+  // -> direction (with the descent reset) -> fixed step or strong-Wolfe search -> the anchor becomes the point the step left.  The
+  // accepted point is evaluated again by the next iteration, as in the reference; the gradient is not clipped (:311 is first-order
+  // only).  A failed search restores theta and throws std::runtime_error unless allow_fallback_to_fixed_step is set.
+  OptimizationResult IterativeOptimizeLBFGS_(const Evaluator &evaluator, const OptimizationCallback &callback) {
+    const LBFGSParams &p = params_.template GetAlgorithmParams<LBFGSParams>();
+    if (p.history_size == 0) throw std::invalid_argument("LBFGS history_size must be > 0");
+    c_.LBFGSBegin(p.history_size);
+    OptimizationResult res;
+    double previous_energy = 0.0;
+    size_t without_improvement = 0;
+    auto counters = [&]() {
+      const auto k = c_.LBFGSGetCounters();
+      res.lbfgs_skip_curvature_count = k.skip_curvature; res.lbfgs_damping_count = k.damping; res.lbfgs_descent_reset_count = k.descent_reset;
+    };
+    auto evaluate = [&]() {
+      const DeviceEvaluationT<TenElemT> ev = evaluator(c_);
+      return c_.OptGradientFromAccumulators(ev.e_loc_sum, ev.weight_sum);
+    };
+    auto record = [&](const std::pair<TenElemT, double> &eg) {
+      res.energy_trajectory.push_back(eg.first);
+      res.gradient_norms.push_back(eg.second);
+      res.final_energy = eg.first;
+    };
+    for (size_t iter = 0; iter < params_.base_params.max_iterations; ++iter) {
+      const auto eg = evaluate();
+      record(eg);
+      const double e = std::real(eg.first);
+      if (e < res.min_energy) { res.min_energy = e; without_improvement = 0; } else ++without_improvement;
+      const double lr = GetCurrentLearningRate(iter, iter == 0 ? e : previous_energy);
+      if (callback.on_iteration) callback.on_iteration(iter, e, eg.second, lr);
+      c_.LBFGSUpdate(p.min_curvature, p.use_damping);
+      if (iter > 0 && ShouldStop(e, previous_energy, eg.second, without_improvement)) { res.converged = true; counters(); return res; }
+      const auto dir = c_.LBFGSDirection(p.min_curvature, p.max_direction_norm);
+      double used_step = 0.0;
+      if (p.step_mode == LBFGSStepMode::kFixed) {
+        used_step = std::max(0.0, lr);                                  // ApplyFixedLBFGSStep_, :1534-1545
+        c_.LBFGSTrial(used_step);
+      } else {
+        size_t evals = 0;
+        double alpha = -1.0;
+        try {
+          alpha = StrongWolfeLBFGSStep([&]() { return std::real(evaluate().first); }, lr, p, e, dir.dphi0, evals);
+        } catch (...) {
+          res.lbfgs_line_search_evaluations += evals;
+          if (evals > 0) c_.LBFGSTrial(0.0);
+          throw;
+        }
+        res.lbfgs_line_search_evaluations += evals;
+        if (alpha >= 0.0) {
+          used_step = alpha;
+        } else if (p.allow_fallback_to_fixed_step) {
+          used_step = std::max(0.0, std::max(p.min_step, lr * p.fallback_fixed_step_scale));
+          c_.LBFGSTrial(used_step);
+        } else {
+          c_.LBFGSTrial(0.0);                                           // theta_base bit for bit
+          throw std::runtime_error("L-BFGS strong-Wolfe line search failed. "
+                                   "Set allow_fallback_to_fixed_step=true for explicit fixed-step fallback.");
+        }
+      }
+      c_.LBFGSCommit();
+      res.learning_rate_trajectory.push_back(used_step);
+      if (params_.base_params.lr_scheduler) params_.base_params.lr_scheduler->Step();
+      previous_energy = e;
+      res.total_iterations = iter + 1;
+    }
+    const auto eg = evaluate();
+    record(eg);
+    res.min_energy = std::min(res.min_energy, std::real(eg.first));
+    counters();
+    return res;
+  }
   // evaluate -> finish -> clip -> [natural gradient] -> step, max_iterations times, then one closing evaluation
   OptimizationResult IterativeOptimize(const Evaluator &evaluator, const OptimizationCallback &callback = OptimizationCallback()) {
+    if (params_.template IsAlgorithm<LBFGSParams>()) return IterativeOptimizeLBFGS_(evaluator, callback);
     OptimizationResult res;
     double previous_energy = 0.0;
     size_t without_improvement = 0;

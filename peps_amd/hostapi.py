@@ -24,6 +24,7 @@ SYMBOLS = ["pepshost_last_error", "pepshost_mc_sweeps", "pepshost_energy_and_hol
            "pepshost_minsr_step_samples", "pepshost_minsr_step_samples_c128",
            "pepshost_fermion_optimize_exact_sum", "pepshost_fermion_optimize_exact_sum_c128",
            "pepshost_fermion_sr_step_samples", "pepshost_fermion_sr_step_samples_c128", "pepshost_fermion_exact_sum_partial_prm",
+           "pepshost_lbfgs_exact_sum", "pepshost_lbfgs_exact_sum_c128", "pepshost_fermion_lbfgs_exact_sum", "pepshost_fermion_lbfgs_exact_sum_c128",
            "pepshost_fermion_observables", "pepshost_fermion_exact_sum_measure_partial", "pepshost_fermion_measure"]
 
 _lib = None
@@ -243,6 +244,84 @@ def optimize_exact_sum(flat, all_configs, chi, model, params, rule, lr, rule_par
         _ck(l.pepshost_optimize_exact_sum(rows, cols, D, d, chi, dtype, _p(flat, C.c_double), *rest, _p(energies, C.c_double),
                                           _p(norms, C.c_double), _p(state, C.c_double)))
     return (energies, state, norms) if return_grad_norms else (energies, state)
+
+
+LBFGS_FIELDS = ("history_size", "tolerance_grad", "tolerance_change", "max_eval", "step_mode", "wolfe_c1", "wolfe_c2", "min_step", "max_step",
+                "min_curvature", "use_damping", "max_direction_norm", "allow_fallback_to_fixed_step", "fallback_fixed_step_scale")
+LBFGS_DEFAULTS = (10, 1e-5, 1e-9, 20, 0, 1e-4, 0.9, 1e-8, 1.0, 1e-12, True, 1e3, False, 0.2)   # LBFGSParams, optimizer_params.h:135-143
+LBFGS_STEP_MODE = {"fixed": 0, "strong_wolfe": 1}
+
+
+class LineSearchError(RuntimeError):
+    """a strong-Wolfe search failed without the fallback; .state = the state the optimizer was left with (the base of that search)"""
+
+
+def _lbfgs_array(lbfgs):
+    """LBFGSParams as the array of the shim: a dict of field names (missing ones take the reference's defaults), a sequence of the
+    fourteen values, or any object with those attributes"""
+    if lbfgs is None:
+        lbfgs = {}
+    if isinstance(lbfgs, dict):
+        unknown = set(lbfgs) - set(LBFGS_FIELDS)
+        if unknown:
+            raise ValueError("unknown LBFGSParams fields: %s" % sorted(unknown))
+        vals = [lbfgs.get(k, dflt) for k, dflt in zip(LBFGS_FIELDS, LBFGS_DEFAULTS)]
+    elif hasattr(lbfgs, LBFGS_FIELDS[0]):
+        vals = [getattr(lbfgs, k) for k in LBFGS_FIELDS]
+    else:
+        vals = list(lbfgs)
+        if len(vals) != len(LBFGS_FIELDS):
+            raise ValueError("LBFGSParams has %d fields" % len(LBFGS_FIELDS))
+    vals = [LBFGS_STEP_MODE[v] if isinstance(v, str) else v for v in vals]
+    return np.array([float(v) for v in vals], dtype=np.float64)
+
+
+def _lbfgs_result(rc, energies, norms, steps, state, info):
+    if rc != 0:
+        try:
+            _ck(rc)
+        except RuntimeError as err:
+            if "line search failed" in str(err):
+                e = LineSearchError(str(err))
+                e.state = state
+                raise e from None
+            raise
+    ne, ns = int(info[0]), int(info[1])
+    return {"energies": energies[:ne].copy(), "grad_norms": norms[:ne].copy(), "steps": steps[:ns].copy(), "state": state,
+            "skip_curvature": int(info[2]), "damping": int(info[3]), "descent_reset": int(info[4]),
+            "line_search_evaluations": int(info[5]), "converged": bool(info[6])}
+
+
+def lbfgs_optimize_exact_sum(flat, cfgs, chi, model, params, lr, lbfgs, iterations, energy_tolerance=0.0, gradient_tolerance=0.0,
+                             plateau_patience=0, dtype=1, batch=64):
+    """Optimizer::IterativeOptimize of the C++ host layer with LBFGSParams and the exact-summation evaluator, the whole loop inside one
+    C++ call: history, anchor, direction and every trial point of the line search stay on the device.  `lbfgs`: see _lbfgs_array.  A
+    tolerance of 0 / a patience of 0 switches that stopping criterion off.  Returns a dict: energies (one per iteration and the closing
+    evaluation; line-search evaluations are not in it), grad_norms, steps (the step length of every iteration), state (final flat
+    state), skip_curvature, damping, descent_reset, line_search_evaluations, converged.  A failed search without the fallback raises
+    LineSearchError.  A complex `flat` runs the QLTEN_Complex instantiation (`dtype` is ignored)."""
+    cplx = np.iscomplexobj(flat)
+    flat = np.ascontiguousarray(flat, dtype=np.complex128 if cplx else np.float64)
+    rows, cols, d, D = _dims(flat)
+    cfg = np.ascontiguousarray(cfgs, dtype=np.int32)
+    p = np.array(list(params) + [0.0] * 8, dtype=np.float64)
+    lb = _lbfgs_array(lbfgs)
+    energies = np.zeros(iterations + 1, dtype=flat.dtype)
+    norms, steps, info = np.zeros(iterations + 1), np.zeros(max(iterations, 1)), np.zeros(8)
+    state = np.zeros_like(flat)
+    l = lib()
+    dpt = C.POINTER(C.c_double)
+    tail = [C.POINTER(C.c_int32), C.c_int, C.c_int, dpt, C.c_double, dpt, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, dpt, dpt, dpt, dpt, dpt]
+    l.pepshost_lbfgs_exact_sum.argtypes = [C.c_int] * 6 + [dpt] + tail
+    l.pepshost_lbfgs_exact_sum_c128.argtypes = [C.c_int] * 5 + [dpt] + tail
+    rest = (_p(cfg, C.c_int32), cfg.shape[0], MODEL_ID[model], _p(p, C.c_double), float(lr), _p(lb, C.c_double), int(iterations),
+            float(energy_tolerance), float(gradient_tolerance), int(plateau_patience), int(min(batch, cfg.shape[0])), _cp(energies),
+            _p(norms, C.c_double), _p(steps, C.c_double), _cp(state), _p(info, C.c_double))
+    if cplx:
+        rc = l.pepshost_lbfgs_exact_sum_c128(rows, cols, D, d, chi, _cp(flat), *rest)
+    else:
+        rc = l.pepshost_lbfgs_exact_sum(rows, cols, D, d, chi, dtype, _p(flat, C.c_double), *rest)
+    return _lbfgs_result(rc, energies, norms, steps, state, info)
 
 
 def sr_step_samples(flat, configs, chi, model, params, lr, diag_shift=0.001, cg_max_iter=100, cg_relative_tolerance=1e-4,
@@ -711,6 +790,34 @@ def fermion_optimize_exact_sum(state, all_configs, chi, model, params, rule, lr,
     else:
         _ck(l.pepshost_fermion_optimize_exact_sum(*head, chi, dtype, *rest))
     return (energies, stored, norms) if return_grad_norms else (energies, stored)
+
+
+def fermion_lbfgs_optimize_exact_sum(state, cfgs, chi, model, params, lr, lbfgs, iterations, energy_tolerance=0.0, gradient_tolerance=0.0,
+                                     plateau_patience=0, dtype=1, batch=64):
+    """lbfgs_optimize_exact_sum on a fermionic state (peps_amd.fermion.FermionState); model and params as fermion_optimize_exact_sum.
+    "state" of the result holds the stored tensors [rows][cols][d][D^4]; the gradient norms and every threshold of LBFGSParams are over
+    the stored parameters."""
+    cplx, flat, nf, par, head = _fermion_head(state, dtype)
+    cfg = np.ascontiguousarray(cfgs, dtype=np.int32)
+    prm = _fermion_prm(model, params)
+    lb = _lbfgs_array(lbfgs)
+    energies = np.zeros(iterations + 1, dtype=flat.dtype)
+    norms, steps, info = np.zeros(iterations + 1), np.zeros(max(iterations, 1)), np.zeros(8)
+    stored = np.zeros((flat.shape[0], flat.shape[1], state.d) + flat.shape[3:], dtype=flat.dtype)
+    l = lib()
+    dpt, i32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    tail = [dpt, i32, C.c_int, C.c_int, dpt, C.c_int, C.c_double, dpt, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, dpt, dpt, dpt, dpt, dpt]
+    lead = [C.c_int] * 4 + [i32, C.POINTER(C.c_uint8), C.c_int]
+    l.pepshost_fermion_lbfgs_exact_sum.argtypes = lead + [C.c_int] + tail
+    l.pepshost_fermion_lbfgs_exact_sum_c128.argtypes = lead + tail
+    rest = (_cp(flat), _p(cfg, C.c_int32), cfg.shape[0], FERMION_MODEL_ID[model], _p(prm, C.c_double), prm.size, float(lr),
+            _p(lb, C.c_double), int(iterations), float(energy_tolerance), float(gradient_tolerance), int(plateau_patience),
+            int(min(batch, cfg.shape[0])), _cp(energies), _p(norms, C.c_double), _p(steps, C.c_double), _cp(stored), _p(info, C.c_double))
+    if cplx:
+        rc = l.pepshost_fermion_lbfgs_exact_sum_c128(*head, chi, *rest)
+    else:
+        rc = l.pepshost_fermion_lbfgs_exact_sum(*head, chi, dtype, *rest)
+    return _lbfgs_result(rc, energies, norms, steps, stored, info)
 
 
 def fermion_sr_step_samples(state, configs, chi, model, params, lr, diag_shift=0.001, cg_max_iter=100, cg_relative_tolerance=1e-4,

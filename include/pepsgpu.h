@@ -745,8 +745,32 @@ int pepsgpu_diag_gram_chol(int dtype, const void *P, int K, int n, int nbatch, v
 int pepsgpu_diag_gram_chol_wave(const float *P, int K, int n, int nbatch, const int32_t *klive, int inner,
                                 const int32_t *inner_live, int max_pass, int form, float *R_out, int32_t *mlive_out);
 int pepsgpu_diag_chol_adaptive(int dtype_out, const double *G, int n, int nbatch, void *R_out, int32_t *mlive_out);
+/* dtype PEPSGPU_C128: the general complex Jacobi (jacobi_rows_cplx_kernel, at most 60 sweeps) and the select; M and Vt_out are
+ * interleaved (re, im), S_out [nbatch][k] stays real float64, force_global is ignored */
 int pepsgpu_diag_jacobi(int dtype, void *M, int m, int len, int nbatch, int k, void *Vt_out, void *S_out,
                         int force_global, int *sweeps_out);
+/* The pieces only the float64 / complex dense truncation routes launch, one launch each; element type float64, or (is_complex != 0)
+ * interleaved complex float64.
+ * pepsgpu_diag_chol_solve_rows: one Cholesky-QR pass X <- L^-1 X, L L^H = S.  S = [nbatch][64][64], upper triangle read; X =
+ *   [nbatch][r_max][len] in place, r_max <= 64.  float64: rows[b] <= r_max rows of entry b; complex: r rows of every entry (rows
+ *   ignored).  run_flag (nullable): entries with run_flag[b] >= 0 are left alone.
+ * pepsgpu_diag_gather_rows: Q[b][j][:] = M[b][piv[b][j]][:] for j < rows[b] (<= min(slots, 64)) where piv >= 0; M = [nbatch][m][len],
+ *   piv = [nbatch][slots], Q = [nbatch][64][len] is read as well: what the kernel leaves comes back unchanged.
+ * pepsgpu_diag_sign_table: the fixed table of +1 / -1 the complex range finder starts from, out = [rows][cols].
+ * pepsgpu_diag_truncate_site: the truncation of ONE interior site of a PEPSGPU_F64 or PEPSGPU_C128 context as a row absorption runs
+ *   it, on nbatch <= max_walkers given matrices M = [nbatch][m][u * k2]; k = min(chi_max, m, u * k2).  rows (float64 only, nullable):
+ *   live rows of M per entry.  route: 0 = the dispatch as shipped (PEPSGPU_F64_PIVOT, PEPSGPU_NO_F64_DENSE_ROUTE,
+ *   PEPSGPU_NO_C128_DENSE_ROUTE as the process read them), 1 = the round-6 form (pivoted rows / range finder), 2 = the round-5
+ *   two-Cholesky form (blocks of more than 128 rows and no more rows than columns; others: general kernels), 3 = general kernels only; 1 .. 3 override the environment for this call.  V_out = [nbatch][k][u * k2];
+ *   klive_out [nbatch] = live rows of V (-1 on a complex context, which keeps static shapes); route_flag_out [nbatch]: < 0 = a dense
+ *   route delivered the entry's rows, >= 0 = the general kernels did.  The context's walkers and environments are not touched. */
+int pepsgpu_diag_chol_solve_rows(int is_complex, const void *S, void *X, int nbatch, int r_max, int len, const int32_t *rows, int r,
+                                 const int32_t *run_flag);
+int pepsgpu_diag_gather_rows(int is_complex, const void *M, int nbatch, int m, int len, const int32_t *piv, int slots,
+                             const int32_t *rows, const int32_t *run_flag, void *Q);
+int pepsgpu_diag_sign_table(int is_complex, int rows, int cols, void *out);
+int pepsgpu_diag_truncate_site(pepsgpu_ctx *ctx, const void *M, int nbatch, int m, int u, int k2, const int32_t *rows, int route,
+                               void *V_out, int32_t *klive_out, int32_t *route_flag_out);
 /* the short-row Jacobi with its select epilogue alone (jacobi_rows_tiny4_kernel, the form the low-rank sites launch):
  * M = [nbatch][m][len] float32 (len <= 128, not written), rows[b] live rows of entry b, k rows of Vt per entry, span != 0 asks for
  * the span path (JrSelect::span).  Vt_out [nbatch][k][len], klive_out and sweeps_out [nbatch] are read as well: an entry

@@ -50,6 +50,7 @@ SYMBOLS = [
     "pepsgpu_update_local", "pepsgpu_erase_envs_after_update", "pepsgpu_evaluate_amplitude",
     "pepsgpu_walker_flags", "pepsgpu_sync", "pepsgpu_stats", "pepsgpu_profile_enable", "pepsgpu_profile_read",
     "pepsgpu_diag_tgemm", "pepsgpu_diag_tgemm_desc", "pepsgpu_diag_tgemm_route", "pepsgpu_diag_tgemm_chain", "pepsgpu_diag_tgemm_chain3", "pepsgpu_diag_chol", "pepsgpu_diag_chol_adaptive", "pepsgpu_diag_chol_pivot", "pepsgpu_diag_rows_qr", "pepsgpu_diag_suwa_todo", "pepsgpu_diag_dot4", "pepsgpu_diag_gram_chol", "pepsgpu_diag_gram_chol_wave", "pepsgpu_diag_gram_cols", "pepsgpu_diag_gram_rows", "pepsgpu_diag_mgemm_dense", "pepsgpu_diag_jacobi", "pepsgpu_diag_trunc_rows", "pepsgpu_version",
+    "pepsgpu_diag_chol_solve_rows", "pepsgpu_diag_gather_rows", "pepsgpu_diag_sign_table", "pepsgpu_diag_truncate_site",
 ]
 
 
@@ -210,6 +211,11 @@ def load_library(path=LIB_PATH):
     lib.pepsgpu_diag_jacobi.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, ip]
     if hasattr(lib, "pepsgpu_diag_trunc_rows"):     # (PEPSGPU_LIB may name a build from before the entry: A/B against the parent commit)
         lib.pepsgpu_diag_trunc_rows.argtypes = [vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_int, vp, ip, ip]
+    if hasattr(lib, "pepsgpu_diag_truncate_site"):  # (PEPSGPU_LIB may name a build from before these entries)
+        lib.pepsgpu_diag_chol_solve_rows.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, ip]
+        lib.pepsgpu_diag_gather_rows.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, ip, ip, vp]
+        lib.pepsgpu_diag_sign_table.argtypes = [C.c_int, C.c_int, C.c_int, vp]
+        lib.pepsgpu_diag_truncate_site.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int, vp, ip, ip]
     return lib
 
 
@@ -260,6 +266,7 @@ class Context:
         self._dead_walkers = []
         self.rows, self.cols, self.D, self.d = rows, cols, D, phys_dim
         self.dtype = dtype
+        self.chi = chi
         self._ot = np.complex128 if dtype == C128 else np.float64      # type of every scalar / tensor the calls return
         h = C.c_void_p()
         rc = self._l.pepsgpu_ctx_create(C.byref(h), device, dtype, rows, cols, D, phys_dim,
@@ -292,6 +299,7 @@ class Context:
     def set_truncate_params(self, chi_min, chi_max, trunc_err=0.0, scheme=0, convergence_tol=0.0, iter_max=0):
         """BMPSContractor::SetTruncateParams (bmps_contractor.h:216); scheme 0 SVD, 1 Variational2Site, 2 Variational1Site."""
         self._ck(self._l.pepsgpu_set_truncate_params(self._h, chi_min, chi_max, trunc_err, scheme, convergence_tol, iter_max))
+        self.chi = chi_max
 
     def state_upload(self, flat):
         flat = np.ascontiguousarray(flat)
@@ -771,6 +779,31 @@ class Context:
         sw = np.zeros(1, dtype=np.int32)
         self._ck(self._l.pepsgpu_diag_eigh(self._h, n, int(cplx), _dp(a), _dp(w), _dp(z), _ip(sw)))
         return w, z, int(sw[0])
+
+    def diag_truncate_site(self, M, u, k2, rows=None, route=0):
+        """the truncation of one interior site as a row absorption of this context (F64 or C128) runs it, on given matrices
+        M [nb][m][u * k2], nb <= max_walkers.  rows (F64 only): live rows of M per entry.  route: 0 the dispatch as shipped, 1 the
+        round-6 form, 2 the round-5 two-Cholesky form, 3 general kernels only (1 .. 3 override the environment for this call).
+        Returns V [nb][k][u * k2] with k = min(chi, m, u * k2), klive [nb] (-1 on a complex context) and route_flag [nb]
+        (< 0: a dense route delivered the entry's rows, >= 0: the general kernels did)."""
+        if self.dtype not in (F64, C128):
+            raise ValueError("diag_truncate_site: F64 and C128 contexts only")
+        t = np.complex128 if self.dtype == C128 else np.float64
+        M = np.ascontiguousarray(M, dtype=t)
+        nb, m, ln = M.shape
+        if ln != u * k2:
+            raise ValueError("M must be [nb][m][u * k2]")
+        k = min(self.chi, m, ln)
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.int32)
+            assert rows.shape == (nb,)
+        V = np.zeros((nb, k, ln), dtype=t)
+        kl = np.zeros(nb, dtype=np.int32)
+        fl = np.zeros(nb, dtype=np.int32)
+        self._ck(self._l.pepsgpu_diag_truncate_site(self._h, M.ctypes.data_as(C.c_void_p), nb, m, int(u), int(k2),
+                                                    None if rows is None else _ip(rows), int(route),
+                                                    V.ctypes.data_as(C.c_void_p), _ip(kl), _ip(fl)))
+        return V, kl, fl
 
     def fermion_decoration_set(self, state):
         """Tells the optimizer calls that the context holds the decorated components of `state` (a fermion.FermionState; the
@@ -1327,17 +1360,69 @@ def diag_mgemm_dense(R, Tt, a_dim, u_dim, k2_dim, tt_u_inner, m_live=None, a_liv
 
 
 def diag_jacobi(dtype, M, k, force_global=False):
-    t = np.float32 if dtype == F32 else np.float64
+    """the general one-sided Jacobi and the select alone.  C128: jacobi_rows_cplx_kernel (force_global is ignored), S stays real"""
+    t = {F32: np.float32, F64: np.float64, C128: np.complex128}[dtype]
     M = np.ascontiguousarray(M, dtype=t).copy()
     nb, m, ln = M.shape
     Vt = np.zeros((nb, k, ln), dtype=t)
-    S = np.zeros((nb, k), dtype=t)
+    S = np.zeros((nb, k), dtype=np.float64 if dtype == C128 else t)
     sw = np.zeros(nb, dtype=np.int32)
     rc = lib().pepsgpu_diag_jacobi(dtype, M.ctypes.data_as(C.c_void_p), m, ln, nb, k, Vt.ctypes.data_as(C.c_void_p),
                                    S.ctypes.data_as(C.c_void_p), int(force_global), _ip(sw))
     if rc != 0:
         raise RuntimeError("diag_jacobi failed: %s" % lib().pepsgpu_last_error(None).decode())
     return M, Vt, S, sw & 0xFF      # high bits: diagnostics (rows above the noise floor at entry)
+
+
+def diag_chol_solve_rows(S, X, rows, run_flag=None):
+    """One Cholesky-QR pass X <- L^-1 X, L L^H = S, as the dense truncation routes launch it: S [nb][64][64] (upper triangle read),
+    X [nb][r_max][len] (returned, the input is not written).  float64 arrays: chol_solve_rows_kernel, rows [nb]; complex128:
+    chol_solve_rows_cplx_kernel, rows a single int.  run_flag [nb]: entries with run_flag[b] >= 0 are left alone."""
+    cplx = np.iscomplexobj(X)
+    t = np.complex128 if cplx else np.float64
+    S = np.ascontiguousarray(S, dtype=t)
+    X = np.ascontiguousarray(X, dtype=t).copy()
+    nb, r_max, ln = X.shape
+    assert S.shape == (nb, 64, 64)
+    if cplx:
+        r, rows_a = int(rows), None
+    else:
+        r, rows_a = 0, np.ascontiguousarray(rows, dtype=np.int32)
+        assert rows_a.shape == (nb,)
+    flag = None if run_flag is None else np.ascontiguousarray(run_flag, dtype=np.int32)
+    rc = lib().pepsgpu_diag_chol_solve_rows(int(cplx), S.ctypes.data_as(C.c_void_p), X.ctypes.data_as(C.c_void_p), nb, r_max, ln,
+                                            None if rows_a is None else _ip(rows_a), r, None if flag is None else _ip(flag))
+    if rc != 0:
+        raise RuntimeError("diag_chol_solve_rows failed: %s" % lib().pepsgpu_last_error(None).decode())
+    return X
+
+
+def diag_gather_rows(M, piv, rows, run_flag=None, fill=0.0):
+    """gather_rows_kernel alone: Q[b][j] = M[b][piv[b][j]] for j < rows[b] where piv >= 0.  M [nb][m][len] float64 or complex128,
+    piv [nb][slots]; returns Q [nb][64][len], `fill` wherever the kernel stores nothing."""
+    cplx = np.iscomplexobj(M)
+    t = np.complex128 if cplx else np.float64
+    M = np.ascontiguousarray(M, dtype=t)
+    nb, m, ln = M.shape
+    piv = np.ascontiguousarray(piv, dtype=np.int32)
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    assert piv.ndim == 2 and piv.shape[0] == nb and rows.shape == (nb,)
+    flag = None if run_flag is None else np.ascontiguousarray(run_flag, dtype=np.int32)
+    Q = np.full((nb, 64, ln), fill, dtype=t)
+    rc = lib().pepsgpu_diag_gather_rows(int(cplx), M.ctypes.data_as(C.c_void_p), nb, m, ln, _ip(piv), piv.shape[1], _ip(rows),
+                                        None if flag is None else _ip(flag), Q.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise RuntimeError("diag_gather_rows failed: %s" % lib().pepsgpu_last_error(None).decode())
+    return Q
+
+
+def diag_sign_table(rows, cols, complex=False):
+    """sign_table_kernel alone: the [rows][cols] table of +1 / -1 the complex range finder starts from"""
+    out = np.zeros((rows, cols), dtype=np.complex128 if complex else np.float64)
+    rc = lib().pepsgpu_diag_sign_table(int(bool(complex)), rows, cols, out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise RuntimeError("diag_sign_table failed: %s" % lib().pepsgpu_last_error(None).decode())
+    return out
 
 
 def diag_trunc_rows(M, rows, k, span, fill=0.0):

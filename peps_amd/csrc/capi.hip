@@ -1269,13 +1269,112 @@ static void diag_jacobi_t(void *M, int m, int len, int nbatch, int k, void *Vt, 
   if (sweeps) PG_CHECK_HIP(hipMemcpy(sweeps, dsw, nbatch * sizeof(int), hipMemcpyDeviceToHost));
   (void)hipFree(dM); (void)hipFree(dV); (void)hipFree(dS); (void)hipFree(dsw);
 }
+// complex float64: the general complex Jacobi as absorb_simple launches it (60 sweeps at most), then the select; S comes back real
+static void diag_jacobi_cplx(void *M, int m, int len, int nbatch, int k, void *Vt, void *S, int *sweeps) {
+  DevBufs bufs;
+  const size_t ne = (size_t)m * len * nbatch, nv = (size_t)k * len * nbatch, ns = (size_t)k * nbatch;
+  c128 *dM = bufs.alloc<c128>(ne, M), *dV = bufs.alloc<c128>(nv), *dS = bufs.alloc<c128>(ns);
+  int *dsw = bufs.alloc<int>(nbatch);
+  hipLaunchKernelGGL(jacobi_rows_cplx_kernel<c128>, dim3(nbatch), dim3(1024), 0, 0, dM, (long)m * len, m, len, len, 60, dsw,
+                     (const int *)nullptr, 1);
+  PG_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(select_rows_kernel<c128>, dim3(nbatch), dim3(256), 0, 0, (const c128 *)dM, (long)m * len, m, len, len, k, dV,
+                     (long)k * len, dS, (long)k, (const int *)nullptr, 1);
+  PG_CHECK_HIP(hipGetLastError());
+  PG_CHECK_HIP(hipDeviceSynchronize());
+  std::vector<c128> hs(ns);
+  PG_CHECK_HIP(hipMemcpy(M, dM, ne * sizeof(c128), hipMemcpyDeviceToHost));
+  PG_CHECK_HIP(hipMemcpy(Vt, dV, nv * sizeof(c128), hipMemcpyDeviceToHost));
+  PG_CHECK_HIP(hipMemcpy(hs.data(), dS, ns * sizeof(c128), hipMemcpyDeviceToHost));
+  for (size_t e = 0; e < ns; ++e) ((double *)S)[e] = hs[e].re;
+  if (sweeps) PG_CHECK_HIP(hipMemcpy(sweeps, dsw, nbatch * sizeof(int), hipMemcpyDeviceToHost));
+}
 extern "C" int pepsgpu_diag_jacobi(int dtype, void *M, int m, int len, int nbatch, int k, void *Vt, void *S, int force_global,
                         int *sweeps) {
   return guarded(nullptr, [&]() {
-    PG_REQUIRE(m <= 1024 && k <= m, 1, "bad sizes");
+    PG_REQUIRE(m >= 1 && len >= 1 && nbatch >= 1 && k >= 1 && m <= 1024 && k <= m, 1, "bad sizes");
     if (dtype == 0) diag_jacobi_t<float>(M, m, len, nbatch, k, Vt, S, force_global, sweeps);
-    else diag_jacobi_t<double>(M, m, len, nbatch, k, Vt, S, force_global, sweeps);
+    else if (dtype == 1) diag_jacobi_t<double>(M, m, len, nbatch, k, Vt, S, force_global, sweeps);
+    else if (dtype == PEPSGPU_C128) diag_jacobi_cplx(M, m, len, nbatch, k, Vt, S, sweeps);
+    else throw Error(1, "unknown dtype");
   });
+}
+
+// ---- the pieces only the float64 / complex dense truncation routes launch (rows_qr.h), one launch each ----
+// One Cholesky-QR pass X <- L^-1 X, L L^H = S: S = [nbatch][64][64] (upper triangle read), X = [nbatch][r_max][len] in place.
+// float64: rows[b] rows per entry (chol_solve_rows_kernel); complex: r rows for every entry (chol_solve_rows_cplx_kernel).
+extern "C" int pepsgpu_diag_chol_solve_rows(int is_complex, const void *S, void *X, int nbatch, int r_max, int len, const int32_t *rows,
+                                            int r, const int32_t *run_flag) {
+  return guarded(nullptr, [&]() {
+    PG_REQUIRE(S && X && nbatch >= 1 && r_max >= 1 && r_max <= CS_K && len >= 1, 1, "diag_chol_solve_rows: bad sizes (r_max <= 64)");
+    if (is_complex) PG_REQUIRE(r >= 0 && r <= r_max, 1, "diag_chol_solve_rows: r must be in [0, r_max]");
+    else {
+      PG_REQUIRE(rows != nullptr, 1, "diag_chol_solve_rows: rows is null");
+      for (int b = 0; b < nbatch; ++b) PG_REQUIRE(rows[b] >= 0 && rows[b] <= r_max, 1, "diag_chol_solve_rows: rows[b] must be in [0, r_max]");
+    }
+    DevBufs bufs;
+    const size_t es = is_complex ? sizeof(c128) : sizeof(double);
+    const size_t nS = (size_t)nbatch * CS_K * CS_K, nX = (size_t)nbatch * r_max * len;
+    char *dS = bufs.alloc<char>(nS * es, S), *dX = bufs.alloc<char>(nX * es, X);
+    int *dflag = run_flag ? bufs.alloc<int>(nbatch, run_flag) : nullptr;
+    if (is_complex) {
+      hipLaunchKernelGGL(chol_solve_rows_cplx_kernel, dim3(nbatch), dim3(256), 0, 0, (const c128 *)dS, (long)CS_K * CS_K, CS_K, (c128 *)dX,
+                         (long)r_max * len, len, r, (const int *)dflag);
+    } else {
+      int *drows = bufs.alloc<int>(nbatch, rows);
+      hipLaunchKernelGGL(chol_solve_rows_kernel, dim3(nbatch), dim3(256), 0, 0, (const double *)dS, (long)CS_K * CS_K, CS_K, (double *)dX,
+                         (long)r_max * len, len, (const int *)drows, (const int *)dflag);
+    }
+    PG_CHECK_HIP(hipGetLastError());
+    PG_CHECK_HIP(hipDeviceSynchronize());
+    PG_CHECK_HIP(hipMemcpy(X, dX, nX * es, hipMemcpyDeviceToHost));
+  });
+}
+// gather_rows_kernel as the pivoted route launches it (64 slots per entry): Q[b][j] = M[b][piv[b][j]] for j < rows[b], piv >= 0;
+// M = [nbatch][m][len], piv = [nbatch][slots], Q = [nbatch][64][len] (read as well: what the kernel leaves comes back unchanged)
+extern "C" int pepsgpu_diag_gather_rows(int is_complex, const void *M, int nbatch, int m, int len, const int32_t *piv, int slots,
+                                        const int32_t *rows, const int32_t *run_flag, void *Q) {
+  return guarded(nullptr, [&]() {
+    PG_REQUIRE(M && piv && rows && Q && nbatch >= 1 && nbatch <= 65535 && m >= 1 && len >= 1 && slots >= 1, 1, "diag_gather_rows: bad sizes");
+    for (int b = 0; b < nbatch; ++b) {
+      PG_REQUIRE(rows[b] >= 0 && rows[b] <= std::min(slots, 64), 1, "diag_gather_rows: rows[b] must be in [0, min(slots, 64)]");
+      for (int j = 0; j < slots; ++j) PG_REQUIRE(piv[(size_t)b * slots + j] < m, 1, "diag_gather_rows: pivot beyond the rows of M");
+    }
+    DevBufs bufs;
+    const size_t es = is_complex ? sizeof(c128) : sizeof(double);
+    const size_t nM = (size_t)nbatch * m * len, nQ = (size_t)nbatch * 64 * len;
+    char *dM = bufs.alloc<char>(nM * es, M), *dQ = bufs.alloc<char>(nQ * es, Q);
+    int *dpiv = bufs.alloc<int>((size_t)nbatch * slots, piv), *drows = bufs.alloc<int>(nbatch, rows);
+    int *dflag = run_flag ? bufs.alloc<int>(nbatch, run_flag) : nullptr;
+    if (is_complex)
+      hipLaunchKernelGGL(gather_rows_kernel<c128>, dim3(64, nbatch), dim3(256), 0, 0, (const c128 *)dM, (long)m * len, len, (const int *)dpiv,
+                         slots, (const int *)drows, (c128 *)dQ, 64L * len, (const int *)dflag);
+    else
+      hipLaunchKernelGGL(gather_rows_kernel<double>, dim3(64, nbatch), dim3(256), 0, 0, (const double *)dM, (long)m * len, len,
+                         (const int *)dpiv, slots, (const int *)drows, (double *)dQ, 64L * len, (const int *)dflag);
+    PG_CHECK_HIP(hipGetLastError());
+    PG_CHECK_HIP(hipDeviceSynchronize());
+    PG_CHECK_HIP(hipMemcpy(Q, dQ, nQ * es, hipMemcpyDeviceToHost));
+  });
+}
+// sign_table_kernel: out = [rows][cols] of +1 / -1 in the element type
+extern "C" int pepsgpu_diag_sign_table(int is_complex, int rows, int cols, void *out) {
+  return guarded(nullptr, [&]() {
+    PG_REQUIRE(out && rows >= 1 && cols >= 1 && (long)rows * cols <= (1L << 24), 1, "diag_sign_table: bad sizes");
+    DevBufs bufs;
+    const size_t es = is_complex ? sizeof(c128) : sizeof(double), n = (size_t)rows * cols;
+    char *d = bufs.alloc<char>(n * es);
+    if (is_complex) hipLaunchKernelGGL(sign_table_kernel<c128>, dim3((n + 255) / 256), dim3(256), 0, 0, (c128 *)d, rows, cols);
+    else hipLaunchKernelGGL(sign_table_kernel<double>, dim3((n + 255) / 256), dim3(256), 0, 0, (double *)d, rows, cols);
+    PG_CHECK_HIP(hipGetLastError());
+    PG_CHECK_HIP(hipDeviceSynchronize());
+    PG_CHECK_HIP(hipMemcpy(out, d, n * es, hipMemcpyDeviceToHost));
+  });
+}
+// the truncation of one interior site of a float64 / complex context on given matrices (Engine::diag_truncate_site)
+extern "C" int pepsgpu_diag_truncate_site(pepsgpu_ctx *ctx, const void *M, int nbatch, int m, int u, int k2, const int32_t *rows, int route,
+                                          void *V_out, int32_t *klive_out, int32_t *route_flag_out) {
+  CTX_CALL(ctx->eng->diag_truncate_site(M, nbatch, m, u, k2, rows, route, V_out, klive_out, route_flag_out));
 }
 
 // The sel form of the short-row Jacobi alone, as trunc_jacobi launches it on a low-rank site (len <= 64: CPL = 4, else 8).

@@ -30,7 +30,9 @@ __global__ __launch_bounds__(256, MINW) void chol_pivot_kernel(const double *__r
                                                                int *__restrict__ mlive_out, int ld, const int *__restrict__ ndyn,
                                                                int ndyn_mul, const int *__restrict__ run_flag,
                                                                double *__restrict__ resid_out = nullptr, double thresh_scale = 1.0,
-                                                               int *__restrict__ piv_out = nullptr) {
+                                                               int *__restrict__ piv_out = nullptr, int kcap_rt = KCAP) {
+  // kcap_rt: the cap the caller asked for when it is below the KCAP of the instantiation (the float64 route at chi < 24 asks for
+  // 2 chi rows): the rounds stop there, so that resid_out prices the rows the caller goes on with and not the instantiation's
   // thresh_scale: multiplies the pivot threshold (0: pivots are taken down to the rounding noise of G -- the caller wants KCAP rows
   // SELECTED, not a factor: piv_out [b][KCAP] then lists the pivot columns in the order taken, -1 beyond the count, and the rows are
   // not compacted by their norm)
@@ -78,7 +80,7 @@ __global__ __launch_bounds__(256, MINW) void chol_pivot_kernel(const double *__r
   // static and the body is one round long.  (The fully unrolled form -- every round its own code, 2000 FMAs + 1600 LDS reads in a
   // row -- came out of the compiler with 256 VGPRs and 300..1600 spilled dwords whatever KCAP.)  Thread-level decisions are selects;
   // what the thread of a candidate column has to publish is taken out of its lane with v_readlane by its whole wave.
-  for (int rd = 0; rd < KCAP / NB; ++rd) {
+  for (int rd = 0; rd < KCAP / NB && rd * NB < kcap_rt; ++rd) {
     // ---- the NB largest remaining diagonals (exact: NB block-wide arg-max reductions; ties go to the lower column) ----
     int cand[NB];
     double dm = d;
@@ -241,11 +243,11 @@ inline void launch_chol_pivot(hipStream_t s, int nbatch, const double *G, long w
   // (piv_out: [nbatch][KCAP of the instantiation taken = 48 / 56 / 64 for kcap <= 48 / <= 56 / else])
   PG_REQUIRE(n <= 256 && (ld == 0 || ld <= 256), 1, "pivoted Cholesky: order above 256");
   if (kcap <= 48)
-    hipLaunchKernelGGL((chol_pivot_kernel<T, 48, 4, 3>), dim3(nbatch), dim3(256), 0, s, G, wG, n, R, wR, mlive_out, ld, ndyn, ndyn_mul, run_flag, resid_out, thresh_scale, piv_out);
+    hipLaunchKernelGGL((chol_pivot_kernel<T, 48, 4, 3>), dim3(nbatch), dim3(256), 0, s, G, wG, n, R, wR, mlive_out, ld, ndyn, ndyn_mul, run_flag, resid_out, thresh_scale, piv_out, kcap);
   else if (kcap <= 56)
-    hipLaunchKernelGGL((chol_pivot_kernel<T, 56, 4, 3>), dim3(nbatch), dim3(256), 0, s, G, wG, n, R, wR, mlive_out, ld, ndyn, ndyn_mul, run_flag, resid_out, thresh_scale, piv_out);
+    hipLaunchKernelGGL((chol_pivot_kernel<T, 56, 4, 3>), dim3(nbatch), dim3(256), 0, s, G, wG, n, R, wR, mlive_out, ld, ndyn, ndyn_mul, run_flag, resid_out, thresh_scale, piv_out, kcap);
   else
-    hipLaunchKernelGGL((chol_pivot_kernel<T, 64, 4, 2>), dim3(nbatch), dim3(256), 0, s, G, wG, n, R, wR, mlive_out, ld, ndyn, ndyn_mul, run_flag, resid_out, thresh_scale, piv_out);
+    hipLaunchKernelGGL((chol_pivot_kernel<T, 64, 4, 2>), dim3(nbatch), dim3(256), 0, s, G, wG, n, R, wR, mlive_out, ld, ndyn, ndyn_mul, run_flag, resid_out, thresh_scale, piv_out, kcap);
   PG_CHECK_HIP(hipGetLastError());
 }
 

@@ -184,6 +184,9 @@ struct EngineBase {
   virtual void walker_get_tensor(int id, int idx, int *dims, double *out, double *logscale) = 0;
   virtual void profile_enable(int on) = 0;
   virtual void profile_read(double *out) = 0;   // [PROF_NCAT = 11][5]: ms, launches, algorithmic flops, executed flops, operand+result bytes
+  // diagnostics (pepsgpu_diag_truncate_site): the truncation of one interior site on given matrices
+  virtual void diag_truncate_site(const void *M, int nb, int m, int u, int k2, const int32_t *rows, int route, void *V_out,
+                                  int32_t *klive_out, int32_t *route_flag_out) = 0;
 };
 
 template <typename T> struct EinView;
@@ -1536,6 +1539,20 @@ class Engine : public EngineBase {
   // complex element type (engine_cplx.h)
   int *trunc_c128_rangefinder(const SiteDims &d, const DTen<T> &M, int k, int kq, DTen<T> &V);
   int *trunc_c128_two_chol(const SiteDims &d, int i, const DTen<T> &M, int k, int kq, DTen<T> &V);
+  DTen<T> truncate_site_simple(const SiteDims &d, int i, DTen<T> &M);
+  void diag_truncate_site(const void *M, int nb, int m, int u, int k2, const int32_t *rows, int route, void *V_out, int32_t *klive_out,
+                          int32_t *route_flag_out) override;
+  // Which dense truncation route a float64 / complex site takes: the environment (read once per process) unless a diagnostic call
+  // set route_override_ (1: the round-6 form, 2: the round-5 two-Cholesky form, 3: general kernels only).
+  struct DenseRouteChoice { bool off; int pivot; };
+  DenseRouteChoice dense_route_choice(bool env_off, int env_pivot) const {
+    if (route_override_ == 0) return {env_off, env_pivot};
+    return {route_override_ == 3, route_override_ == 1 ? 1 : 0};
+  }
+  // the route flag of a site leaves with the diagnostic call before the site frees it (nullptr outside pepsgpu_diag_truncate_site)
+  void diag_keep_route_flag(const int *rflag) {
+    if (diag_flag_out_ && rflag) PG_CHECK_HIP(hipMemcpyAsync(diag_flag_out_, rflag, sizeof(int) * nw_, hipMemcpyDeviceToDevice, stream_));
+  }
   // ---- variational compression schemes (engine_var.h) ----
   BMPSDev absorb_variational(int pos, int num, const BMPSDev &in);
   BMPSDev truncate_bmps(const BMPSDev &in, int kmax);
@@ -1655,6 +1672,8 @@ class Engine : public EngineBase {
   double *holes_ls_ = nullptr;            // its log-scales [walker][site]
   double *so_ = nullptr, *seo_ = nullptr; // gradient accumulators
   int *sweeps_ = nullptr;
+  int route_override_ = 0;                // diagnostics: see dense_route_choice
+  int *diag_flag_out_ = nullptr;          // ... and diag_keep_route_flag
   unsigned long long *flopc_ = nullptr;   // device flop counters [PROF_NCAT] then byte counters [PROF_NCAT]
   T *sr_o_ = nullptr;                      // O* samples [sample][site][D^4]
   int *sr_cfg_ = nullptr;                  // their configurations [sample][site]

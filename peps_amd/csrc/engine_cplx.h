@@ -87,38 +87,8 @@ typename Engine<T>::BMPSDev Engine<T>::absorb_simple(int pos, int num, const BMP
     PG_REQUIRE(s.R[i].d[1] == d.l && s.R[i].d[2] == d.a, 3, "MultiplyMPO: carry dimension mismatch");
     DTen<T> M = alloc_ten(m, uk, 1);
     tgemm_launch<T, T, T, T>(stream_, desc_m(d, false, s.R[i].n, Tt.n, M.n, nw_, nullptr, 1, nullptr, nullptr, false), s.R[i].p, Tt.p, M.p);
-    const int k = std::min(chi_, std::min(m, uk));
-    PG_REQUIRE(m <= 1024, 1, "bond dimension too large for select_rows_kernel");
-    DTen<T> V = alloc_ten(k, d.u, d.k2);
-    // ---- dense sites, complex element type (round 5): the oversampled route of the float64 engine (engine_impl.h has the statement
-    // and the error argument) with the Hermitian forms.  The complex one-sided Jacobi on the 256 x 256 block was 96 % of a dense
-    // amplitude (6.6 amp/s at C4 whatever the batch).  Static shapes (this path has no live extents); walkers a route does not keep
-    // (rflag >= 0) take the general kernel as before.
-    int *rflag = nullptr;
-    if constexpr (kCplx) {
-      static const bool no_route = getenv("PEPSGPU_NO_C128_DENSE_ROUTE") != nullptr;
-      static const int f64_pivot = getenv("PEPSGPU_F64_PIVOT") ? atoi(getenv("PEPSGPU_F64_PIVOT")) : 1;   // 0: the two-Cholesky route of round 5
-      const int kq = std::min(2 * k, (3 * std::min(m, uk)) / 4);
-      const bool route_ok = !no_route && trunc_err_ == 0.0 && m <= 256 && uk <= 256 && kq <= 64 && kq >= k + 8;
-      if (f64_pivot && route_ok && m >= 64) rflag = trunc_c128_rangefinder(d, M, k, kq, V);
-      else if (route_ok && m > 128) rflag = trunc_c128_two_chol(d, i, M, k, kq, V);
-    }
-    // the general kernel: every walker, or -- behind the route -- the walkers that left it (rflag >= 0)
-    if constexpr (kCplx) {
-      hipLaunchKernelGGL(jacobi_rows_cplx_kernel<T>, dim3(nw_), dim3(1024), 0, stream_, M.p, M.n, m, uk, uk, 60, sweeps_,
-                         (const int *)rflag, 0);
-    } else {
-      hipLaunchKernelGGL(jacobi_rows_kernel<T>, dim3(nw_), dim3(1024), 0, stream_, M.p, M.n, m, uk, uk, 60, 0, sweeps_,
-                         (const int *)nullptr, 1, 0);
-    }
-    PG_CHECK_HIP(hipGetLastError());
-    ++n_jacobi_;
-    hipLaunchKernelGGL(select_rows_kernel<T>, dim3(nw_), dim3(256), 0, stream_, (const T *)M.p, M.n, m, uk, uk, k, V.p, V.n,
-                       (T *)nullptr, 0L, (const int *)nullptr, 1, (int *)nullptr, trunc_err_, chi_min_, (double *)nullptr,
-                       (const int *)rflag, rflag ? 0 : 1);
-    PG_CHECK_HIP(hipGetLastError());
-    if (rflag) { arena_.free(rflag); rflag = nullptr; }
-    free_ten(M);
+    DTen<T> V = truncate_site_simple(d, i, M);
+    const int k = V.d[0];
     out.t[i] = V;
     DTen<T> Yn = alloc_ten(d.l, d.a, k);
     // Y[(l,a),q] = sum_{(u,k2)} Tt[(l,a),(u,k2)] conj(Vt[q,(u,k2)])
@@ -135,10 +105,55 @@ typename Engine<T>::BMPSDev Engine<T>::absorb_simple(int pos, int num, const BMP
   return out;
 }
 
+// The truncation of one site of absorb_simple: rows of M -> the k = min(chi, m, uk) largest (sigma_q v_q^H) normalised into V,
+// by a dense route where the site takes one and by the general Jacobi for the walkers no route kept.  Consumes M.
+template <typename T>
+DTen<T> Engine<T>::truncate_site_simple(const SiteDims &d, int i, DTen<T> &M) {
+  const int m = d.m, uk = d.uk;
+  const int k = std::min(chi_, std::min(m, uk));
+  PG_REQUIRE(m <= 1024, 1, "bond dimension too large for select_rows_kernel");
+  DTen<T> V = alloc_ten(k, d.u, d.k2);
+  // ---- dense sites, complex element type (round 5): the oversampled route of the float64 engine (engine_impl.h has the statement
+  // and the error argument) with the Hermitian forms.  The complex one-sided Jacobi on the 256 x 256 block was 96 % of a dense
+  // amplitude (6.6 amp/s at C4 whatever the batch).  Static shapes (this path has no live extents); walkers a route does not keep
+  // (rflag >= 0) take the general kernel as before.
+  int *rflag = nullptr;
+  if constexpr (kCplx) {
+    static const bool no_route_env = getenv("PEPSGPU_NO_C128_DENSE_ROUTE") != nullptr;
+    static const int f64_pivot_env = getenv("PEPSGPU_F64_PIVOT") ? atoi(getenv("PEPSGPU_F64_PIVOT")) : 1;   // 0: the two-Cholesky route of round 5
+    const DenseRouteChoice rc = dense_route_choice(no_route_env, f64_pivot_env);
+    const bool no_route = rc.off;
+    const int f64_pivot = rc.pivot;
+    const int kq = std::min(2 * k, (3 * std::min(m, uk)) / 4);
+    const bool route_ok = !no_route && trunc_err_ == 0.0 && m <= 256 && uk <= 256 && kq <= 64 && kq >= k + 8;
+    if (f64_pivot && route_ok && m >= 64) rflag = trunc_c128_rangefinder(d, M, k, kq, V);
+    else if (route_ok && m > 128 && m <= uk) rflag = trunc_c128_two_chol(d, i, M, k, kq, V);   // (m <= uk: see truncate_site, engine_impl.h)
+  }
+  // the general kernel: every walker, or -- behind the route -- the walkers that left it (rflag >= 0)
+  if constexpr (kCplx) {
+    hipLaunchKernelGGL(jacobi_rows_cplx_kernel<T>, dim3(nw_), dim3(1024), 0, stream_, M.p, M.n, m, uk, uk, 60, sweeps_,
+                       (const int *)rflag, 0);
+  } else {
+    hipLaunchKernelGGL(jacobi_rows_kernel<T>, dim3(nw_), dim3(1024), 0, stream_, M.p, M.n, m, uk, uk, 60, 0, sweeps_,
+                       (const int *)nullptr, 1, 0);
+  }
+  PG_CHECK_HIP(hipGetLastError());
+  ++n_jacobi_;
+  hipLaunchKernelGGL(select_rows_kernel<T>, dim3(nw_), dim3(256), 0, stream_, (const T *)M.p, M.n, m, uk, uk, k, V.p, V.n,
+                     (T *)nullptr, 0L, (const int *)nullptr, 1, (int *)nullptr, trunc_err_, chi_min_, (double *)nullptr,
+                     (const int *)rflag, rflag ? 0 : 1);
+  PG_CHECK_HIP(hipGetLastError());
+  if (rflag) { diag_keep_route_flag(rflag); arena_.free(rflag); rflag = nullptr; }
+  free_ten(M);
+  return V;
+}
+
 // Round 6: the oversampled subspace from a RANDOMISED range finder -- a fixed table of signs times M, three re-orthonormalised steps
 // of subspace iteration (every half step a Cholesky-QR2 in complex float64, chol_solve_rows_cplx_kernel), then the complex
 // Jacobi on Z = U M.  What lies outside the kq = 2 chi directions enters direction chi damped by (sigma_kq+1 / sigma_chi)^6
-// (~2e-8 on a state of the real spectrum): no Gram of M, no factorisation, no Jacobi on a 128 x 128 factor.  (The float64 route
+// (~2e-8 on a state of the real spectrum): no Gram of M, no factorisation, no Jacobi on a 128 x 128 factor.  A spectrum that does not
+// fall like that (flat at kq, or a cliff just behind chi) would be delivered with a visible loss -- 3e-2 of sigma_1 on sigma_j =
+// 10^(-2 j / 256): the guard at the end prices the leakage from the rotated rows of Z and hands such walkers to the general kernel.  (The float64 route
 // selects its start rows by a pivoted factorisation, chol_pivot.h; a complex factor column does not fit a thread's registers.)
 // Returns the route flag (< 0: the walker's rows are in V); the caller frees it.
 template <typename T>
@@ -170,7 +185,8 @@ int *Engine<T>::trunc_c128_rangefinder(const SiteDims &d, const DTen<T> &M, int 
                              Uout.p);
   };
   times_m(Om, 0L, Qz);                          // the sketch: signs times M
-  for (int it = 0; it < 3; ++it) {
+  constexpr int iters = 3;
+  for (int it = 0; it < iters; ++it) {
     orth(Qz, uk);
     times_mh(Qz, Uz);
     orth(Uz, m);
@@ -180,6 +196,18 @@ int *Engine<T>::trunc_c128_rangefinder(const SiteDims &d, const DTen<T> &M, int 
   hipLaunchKernelGGL(select_rows_kernel<T>, dim3(nw_), dim3(256), 0, stream_, (const T *)Qz.p, Qz.n, kq, uk, uk, k, V.p, V.n, (T *)nullptr, 0L,
                      (const int *)nullptr, 1, (int *)nullptr, 0.0, chi_min_, (double *)nullptr, (const int *)rflag, 1);
   PG_CHECK_HIP(hipGetLastError());
+  // guard (rangefinder_guard_kernel): a walker whose spectrum inside the subspace does not price the leakage of the three steps below
+  // the tolerance leaves the route; the caller's general Jacobi and select redo it (they run for rflag >= 0).  1e-11: the loss is at
+  // most 8 x the priced value (tests/test_cpu_trunc_route_ref.py), i.e. below 1e-10, the level of the float64 route's own algorithmic
+  // loss; a spectrum of the real state's shape prices at 1e-13, a flat one or a cliff behind chi at 4e-9 or more.
+  constexpr double guard_tol = 1e-11;
+  hipLaunchKernelGGL(rangefinder_guard_kernel<T>, dim3(nw_), dim3(256), 0, stream_, (const T *)Qz.p, Qz.n, uk, kq, k, iters, guard_tol, rflag);
+  PG_CHECK_HIP(hipGetLastError());
+  if (dbg_verbose()) {   // diagnostics: who stays on the route
+    long on = 0;
+    for (int v : dbg_read(rflag)) on += v < 0;
+    fprintf(stderr, "[pepsgpu] c128 range finder (m = %d, uk = %d, kq = %d): %ld of %d walkers on the route\n", m, uk, kq, on, nw_);
+  }
   free_ten(Om); free_ten(Qz); free_ten(Uz);
   arena_.free(Sq);
   return rflag;

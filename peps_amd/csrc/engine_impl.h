@@ -594,15 +594,21 @@ typename Engine<T>::TruncOut Engine<T>::truncate_site(AbsorbState &s, const Site
   if (rank_adapt()) s.kn[i] = (int *)arena_.alloc(sizeof(int) * nw_);
   t.kn_i = s.kn[i];
   if constexpr (std::is_same<T, double>::value) {
-    static const bool no_route = getenv("PEPSGPU_NO_F64_DENSE_ROUTE") != nullptr;
-    static const int f64_pivot = getenv("PEPSGPU_F64_PIVOT") ? atoi(getenv("PEPSGPU_F64_PIVOT")) : 1;   // 0: the two-Cholesky route of round 5
+    static const bool no_route_env = getenv("PEPSGPU_NO_F64_DENSE_ROUTE") != nullptr;
+    static const int f64_pivot_env = getenv("PEPSGPU_F64_PIVOT") ? atoi(getenv("PEPSGPU_F64_PIVOT")) : 1;   // 0: the two-Cholesky route of round 5
+    const DenseRouteChoice rc = dense_route_choice(no_route_env, f64_pivot_env);
+    const bool no_route = rc.off;
+    const int f64_pivot = rc.pivot;
     // oversampled subspace: 2 chi directions, at most three quarters of the rank M can have (the right-edge sites are 256 x 64);
     // trunc_err > 0 keeps the general path (the truncation rule wants every singular value)
     const int kq = std::min(2 * t.k_full, (3 * std::min(m, uk)) / 4);
     const bool route_ok = !no_route && rank_adapt() && trunc_err_ == 0.0 && m <= 256 && uk <= 256 && kq <= 64 && kq >= t.k_full + 8 && i > 0;
     // pivoted route: blocks of 64 .. 256 rows (measured, real state at 2 048 walkers: 443 amp/s with the route above 128 rows only, 490 from 64)
     if (f64_pivot && route_ok && m > 63 && uk % 4 == 0) trunc_f64_pivot(s, d, i, M, kq, t);
-    else if (route_ok && m > 128) trunc_f64_two_chol(s, d, i, M, kq, t);
+    // (round-5 form: not on blocks with more rows than columns.  Their rank ends at uk by shape, so the unpivoted factor of M M^T
+    // meets dependent rows while directions of weight are still open and decides at the rounding level which rows it keeps; on a
+    // 200 x 128 block with a flat tail of 6e-5 sigma_1 one walker in four lost 6e-8 of sigma_1, and no guard of the route prices it)
+    else if (route_ok && m > 128 && m <= uk) trunc_f64_two_chol(s, d, i, M, kq, t);
   }
   trunc_jacobi(s, d, i, M, mr, t);
   prof_begin(PROF_SELECT, 0.0, 0.0);
@@ -615,6 +621,7 @@ typename Engine<T>::TruncOut Engine<T>::truncate_site(AbsorbState &s, const Site
                        (const int *)(t.route_flag ? t.select_skip : mr.midflag), 0, t.sel_done ? JR_BR : 0);
   PG_CHECK_HIP(hipGetLastError());
   if (t.route_flag) {
+    diag_keep_route_flag(t.route_flag);
     if (t.early) {      // the side stream's walkers: joined before anything reads V / kn of this site
       PG_CHECK_HIP(hipStreamWaitEvent(stream_, ev_join_, 0));
       // (their buffers go back to the arena: it hands them out to launches on stream_ only, which are ordered behind the join)
@@ -1297,6 +1304,71 @@ void Engine<T>::trunc_f64_two_chol(AbsorbState &s, const SiteDims &d, int i, con
   PG_CHECK_HIP(hipGetLastError());
   free_ten(B1); free_ten(B2); free_ten(Wt); free_ten(T1); free_ten(Uq); free_ten(Zt);
   arena_.free(rowsM); arena_.free(mB1); arena_.free(mB2); arena_.free(kW); arena_.free(lvl);
+}
+
+// Diagnostics (pepsgpu_diag_truncate_site): the truncation of ONE interior site -- truncate_site itself (float64) or
+// truncate_site_simple (complex) -- on nb given matrices M [nb][m][u * k2], with the walker count, the route choice and the
+// copy of the route flag set for the duration of the call.  rows (float64 only, nullable): live rows of M per entry.
+template <typename T>
+void Engine<T>::diag_truncate_site(const void *M_host, int nb, int m, int u, int k2, const int32_t *rows, int route, void *V_out,
+                                   int32_t *klive_out, int32_t *route_flag_out) {
+  if constexpr (sizeof(T) == 4) {
+    throw Error(1, "diag_truncate_site: float64 and complex contexts only");
+  } else {
+    PG_REQUIRE(M_host && V_out && klive_out && route_flag_out, 1, "diag_truncate_site: null buffer");
+    PG_REQUIRE(nb >= 1 && nb <= maxw_, 1, "diag_truncate_site: nb must be in [1, max_walkers]");
+    PG_REQUIRE(m >= 1 && m <= 1024 && u >= 1 && k2 >= 1 && (long)u * k2 <= 1024, 1, "diag_truncate_site: bad sizes");
+    PG_REQUIRE(route >= 0 && route <= 3, 1, "diag_truncate_site: route is 0 .. 3");
+    PG_REQUIRE(!(kCplx && rows), 1, "diag_truncate_site: the complex path has no live extents");
+    if (rows)
+      for (int b = 0; b < nb; ++b) PG_REQUIRE(rows[b] >= 0 && rows[b] <= m, 1, "diag_truncate_site: rows[b] must be in [0, m]");
+    ArenaScope scope(arena_);
+    struct Restore {      // the context's own walker count and route choice come back on every way out
+      Engine<T> &e; int nw, route;
+      ~Restore() { e.nw_ = nw; e.route_override_ = route; e.diag_flag_out_ = nullptr; }
+    } restore{*this, nw_, route_override_};
+    nw_ = nb;
+    route_override_ = route;
+    const int uk = u * k2, i = 1;     // (the routes want an interior site: i > 0)
+    SiteDims d;
+    d.u = u; d.k2 = k2; d.m = m; d.uk = uk;
+    ArenaBuf<int> flag(arena_, (size_t)nb);
+    PG_CHECK_HIP(hipMemsetAsync((int *)flag, 0, sizeof(int) * nb, stream_));      // no route launched: the general kernels took everybody
+    diag_flag_out_ = (int *)flag;
+    DTen<T> M = alloc_ten(m, uk, 1);
+    PG_CHECK_HIP(hipMemcpyAsync(M.p, M_host, sizeof(T) * (size_t)M.n * nb, hipMemcpyHostToDevice, stream_));
+    DTen<T> V;
+    std::vector<int32_t> kl(nb, -1);
+    if constexpr (kCplx) {
+      V = truncate_site_simple(d, i, M);
+    } else {
+      BMPSDev in, out;               // (in.depth = 0: no hint of a row absorbed before)
+      AbsorbState s;
+      s.N = 2; s.in = &in; s.out = &out;
+      out.t.resize(2);
+      s.kn.assign(3, nullptr); s.clive.assign(3, nullptr);
+      s.cur_kmax.assign(3, -1); s.kstat.assign(3, 0); s.kfull.assign(3, 0);
+      s.assume_fused.assign(3, 0); s.assume_rows.assign(2, 0);
+      s.R.assign(2, DTen<T>()); s.mdyn.assign(2, nullptr); s.mmul.assign(2, 1); s.R_tri.assign(2, 0);
+      ArenaBuf<int> drows(arena_, rows ? (size_t)nb : 0);
+      if (rows) {
+        PG_CHECK_HIP(hipMemcpyAsync((int *)drows, rows, sizeof(int) * nb, hipMemcpyHostToDevice, stream_));
+        s.mdyn[i] = (int *)drows;
+      }
+      const TruncOut t = truncate_site(s, d, i, M, false);
+      V = t.V;
+      if (t.kn_i) {
+        PG_CHECK_HIP(hipMemcpyAsync(kl.data(), t.kn_i, sizeof(int) * nb, hipMemcpyDeviceToHost, stream_));
+        PG_CHECK_HIP(hipStreamSynchronize(stream_));
+        arena_.free(t.kn_i);
+      }
+    }
+    PG_CHECK_HIP(hipMemcpyAsync(V_out, V.p, sizeof(T) * (size_t)V.n * nb, hipMemcpyDeviceToHost, stream_));
+    PG_CHECK_HIP(hipMemcpyAsync(route_flag_out, (int *)flag, sizeof(int) * nb, hipMemcpyDeviceToHost, stream_));
+    PG_CHECK_HIP(hipStreamSynchronize(stream_));
+    std::copy(kl.begin(), kl.end(), klive_out);
+    free_ten(V);
+  }
 }
 
 }  // namespace pepsgpu

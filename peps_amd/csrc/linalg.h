@@ -1934,6 +1934,45 @@ __global__ __launch_bounds__(256) void f64_pivot_guard_kernel(const TZ *__restri
   }
 }
 
+// Guard of the complex range finder (engine_cplx.h, trunc_c128_rangefinder): the squared norms of the kq rotated rows of Z = U M are
+// the squared singular values z_1 >= .. >= z_kq inside the subspace.  `iters` re-orthonormalised steps of subspace iteration leave of
+// the directions outside the subspace at most (z_kq / z_k)^(2 iters + 1) in the kept direction k; that direction carries the weight
+// z_k / z_1 of the block, so the part of the kept sigma_j v_j the delivered rows miss is priced as
+//     (z_k / z_1) (z_kq / z_k)^(2 iters + 1)
+// (measured on constructed spectra, tests/trunc_route_ref.py: the actual loss is 0.1 .. 6 times this value wherever it is above the
+// rounding floor).  A walker above `tol` leaves the route: a spectrum that is still flat at kq (a random or early-optimisation state),
+// or one with a cliff just behind direction k.  z_kq = 0: the subspace holds all of M, nothing is outside.
+template <typename TZ>
+__global__ __launch_bounds__(256) void rangefinder_guard_kernel(const TZ *__restrict__ Zg, long wZ, int len, int kq, int k, int iters,
+                                                                double tol, int *__restrict__ flag) {
+  const int b = blockIdx.x;
+  if (flag[b] >= 0) return;
+  __shared__ double s_n[64];
+  const int rows = min(kq, 64), lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const TZ *Z = Zg + (long)b * wZ;
+  for (int r = wave; r < rows; r += 4) {
+    double a = 0.0;
+    for (int c = lane; c < len; c += 64) a += abs2_of(Z[(long)r * len + c]);
+    a = wave_sum(a);
+    if (lane == 0) s_n[r] = a;           // squared norms
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s1 = 0.0, slast = 1e300;
+    for (int r = 0; r < rows; ++r) { s1 = fmax(s1, s_n[r]); slast = fmin(slast, s_n[r]); }
+    double sk = 0.0;
+    const int kk = min(k, rows);
+    for (int r = 0; r < rows; ++r) {
+      int larger = 0;
+      for (int q = 0; q < rows; ++q) larger += (s_n[q] > s_n[r]) || (s_n[q] == s_n[r] && q < r);
+      if (larger == kk - 1) sk = s_n[r];
+    }
+    // (squared norms: (z_kq / z_k)^(2 iters + 1) = (slast / sk)^(iters + 1/2))
+    const bool ok = rows >= 1 && s1 > 0.0 && (slast == 0.0 || (sk > 0.0 && sqrt(sk / s1) * pow(slast / sk, (double)iters + 0.5) <= tol));
+    if (!ok) flag[b] = 0;
+  }
+}
+
 // live rows of M for the walkers off the route (the general kernels take them), 0 for the walkers on it.  `early` (optional): the
 // walkers that left at the first check are being handled on the side stream already (early[b] >= 0): they count 0 rows here and
 // `late_flag` (optional) marks what is left for the main stream (0: left the route later, -1: nothing to do)

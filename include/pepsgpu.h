@@ -258,6 +258,53 @@ long pepsgpu_diag_pair_slice_calls(void);
  * where it has none); sign_out [n][2] = +1 / -1 as above, 0 for "no candidate".  Needs a device, no context. */
 int pepsgpu_diag_pair_cand(int rows, int cols, int d, const int32_t *occ, const int32_t *pair_table, int n, const int32_t *ext,
                            int orientation, int site1, int site2, int32_t *cand_out, int32_t *sign_out);
+/* One row / column of a FERMIONIC state for a model whose bond term is up to two hops, the Hubbard model (square_hubbard_model.h:190-262
+ * EvaluateBondEnergy: Trace + ReplaceNNSiteTrace of the hopped pairs, nothing for equal states :200-202): pepsgpu_nn_pair_slice_fermion
+ * without the exchange slot and, with punch_holes != 0, as the row pass of the energy evaluation (square_nn_energy_solver.h: InitBTen,
+ * GrowFullBTen(.., 1, true), per site PunchHole into HBM as pepsgpu_punch_hole with out == NULL does, before that site's bond, and
+ * ShiftBTenWindow after every bond, the last one too).  punch_holes == 0 returns the bytes of pepsgpu_nn_pair_slice_fermion with a
+ * NULL exchange_table.
+ *   hop_table  [d * d][2][2] over PHYSICAL states, the layout and the rules of pair_table above: slot 0 the pair with the up electron
+ *              hopped across the bond, slot 1 with the down electron hopped, (-1, -1) where there is no such hop;
+ *   psi_out    [n][slice length - 1]; hop_out [n][slice length - 1][2] = sign * psi' as pair_out above: sign = -1 where the
+ *              hop changes the number of odd sites by +-2, (up-down, empty) <-> (up, down).
+ * Status codes as for pepsgpu_nn_pair_slice_fermion.  A refused call leaves the context usable. */
+int pepsgpu_nn_hop_slice_fermion(pepsgpu_ctx *ctx, int orientation, int slice, int punch_holes, int d, const int32_t *occ,
+                                 const int32_t *hop_table, double *psi_out, double *hop_out);
+/* Completed pepsgpu_nn_hop_slice_fermion calls of this process (all contexts). */
+long pepsgpu_diag_hop_slice_calls(void);
+/* One row / column of MCUpdateSquareNNUpdateBaseOBC::operator() (square_nn_updater.h:41-55 / :62-76: InitBTen, GrowFullBTen(.., 2, true),
+ * per bond TwoSiteNNUpdateLocalImpl + ShiftBTenWindow while j + 2 < slice length) with the move of MCUpdateSquareNNHubbardU1U1OBC
+ * (square_hubbard_u1u1_updater.h:95-157) on the device, every element type: per bond the candidates of the pair's sector from a table,
+ * ONE ReplaceNNSiteTrace over max_cand slots, the weights |psi_k / psi|^2 (the current state keeps its stored amplitude, :129),
+ * SuwaTodoStateUpdate (suwa_todo_update.h:53-112) and UpdateLocal.
+ *   sector_table [d * d][2 + 2 max_cand] over PHYSICAL states, 1 <= max_cand <= 16: row a * d + b of the states (a, b) on the (left / upper,
+ *                right / lower) site holds m (the size of the sector), init (the slot of (a, b) itself) and max_cand slots (a'_k, b'_k) in
+ *                the order of EnumerateHubbardTwoSiteConfigsWithU1U1 (:57-72; Suwa-Todo depends on it); slots m .. max_cand - 1 are (-1, -1);
+ *   occ          [d] (0 / 1), the fermion number of each physical state: a fermionic context of physical dimension 4 d whose walkers hold
+ *                extended states of the mode order of the pass (as for pepsgpu_nn_pair_slice_fermion); every candidate must keep the
+ *                fermion parity of the pair, the device derives the two variants.  NULL: a bosonic context of physical dimension d;
+ *   engine_words [n][n_words], n_words >= 2 (slice length - 1): the next raw 32-bit outputs of each walker's std::mt19937; a bond with m <= 1
+ *                draws nothing (:114-116), one with m > 1 takes the walker's next two words; consumed_out [n] how many walker w took;
+ *   amplitude_inout [n] psi before / after the slice (PEPSGPU_C128: interleaved; fermions: of the decorated network, as for
+ *                pepsgpu_sweep_slice_exchange_tab); accepted_out [n] moves that changed the pair; slice_states_out [n][slice length] or NULL.
+ * Status PEPSGPU_EINVAL: bad orientation or slice, a NULL required buffer, n_words < 2 (slice length - 1), max_cand outside [1, 16], a
+ * physical dimension that is not 4 d (d with a NULL occ), an occ entry outside {0, 1}, a table row with m outside [1, max_cand], init
+ * outside [0, m), a -1 in a used slot, a state in an unused one, a slot init that is not (a, b), or a candidate that changes the fermion
+ * parity; PEPSGPU_ERANGE: a table state outside [-1, d); PEPSGPU_ESTATE: a boundary MPS of the slice is missing, a configuration override is
+ * active, or a state of the slice has a variant of the other mode order.  A refused call leaves the configuration untouched and the
+ * context usable. */
+int pepsgpu_sweep_slice_sector(pepsgpu_ctx *ctx, int orientation, int slice, int d, const int32_t *occ, int max_cand,
+                               const int32_t *sector_table, int n_words, const uint32_t *engine_words, double *amplitude_inout,
+                               int32_t *consumed_out, int32_t *accepted_out, int32_t *slice_states_out);
+/* Completed pepsgpu_sweep_slice_sector calls of this process (all contexts). */
+long pepsgpu_diag_sector_slice_calls(void);
+/* The candidate kernel of pepsgpu_sweep_slice_sector alone, on the caller's configurations ext [n][rows][cols] (occ given: extended
+ * states in [0, 4 d) of the mode order of `orientation` on the two sites; occ NULL: states in [0, d)) for the bond (site1, site2), flat
+ * row-major indices.  cand_out [n][max_cand][2] the states of the two sites in slot k (the walker's own two states in an unused slot);
+ * meta_out [n][2] = (m, init).  Needs a device, no context. */
+int pepsgpu_diag_sector_cand(int rows, int cols, int d, const int32_t *occ, int max_cand, const int32_t *sector_table, int n,
+                             const int32_t *ext, int orientation, int site1, int site2, int32_t *cand_out, int32_t *meta_out);
 /* The links of a row pair or a column pair on the device, every element type: the bodies of the row-pair loop and of the column-pair
  * loop of the triangular J1-J2 model (spin_onehalf_triangle_heisenbergJ1J2_sqrpeps.h:350-398, :425-442) with ONE read-back and no
  * upload.  (r, c) is the upper-left site of the window; bit k of link_mask requests kind k:
@@ -415,6 +462,12 @@ int pepsgpu_replace_tnn_trace(pepsgpu_ctx *ctx, int row, int col, int mps_orient
  * cand_states = [n][n_cand][2] states on the (left, right) end of the link. */
 int pepsgpu_replace_sqrt5_trace(pepsgpu_ctx *ctx, int row, int col, int link_dir, int mps_orient, int n_cand,
                                 const int32_t *cand_states, double *out_amp);
+/* How pepsgpu_trace and the pepsgpu_replace_nn / one_trace calls scale their result on the way out.  A trace is kept as mantissa x exp(log-scale).
+ * on_device == 0 (the default): the mantissas are read back and multiplied by std::exp(log-scale) on the host.  on_device != 0: they are
+ * multiplied by exp(log-scale) in a kernel, the expression the device-side slices use, so that a per-bond hook path returns the bits of
+ * the slice that replaces it (the two exponentials may differ in the last bit; SquareHubbardModel::EvaluateBondEnergy and the hook of
+ * MCUpdateSquareNNHubbardU1U1OBC switch it on around their calls).  The other trace calls keep the host form. */
+int pepsgpu_trace_scaling(pepsgpu_ctx *ctx, int on_device);
 /* PunchHole(tn, site, mps_orient)  grow.h:150-183.  out = [n][D][D][D][D] float64 (legs L,D,R,U, zero padded). */
 int pepsgpu_punch_hole(pepsgpu_ctx *ctx, int row, int col, int mps_orient, double *out);
 /* out == NULL: the hole of every walker stays on the device (resident hole store) for

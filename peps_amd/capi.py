@@ -26,12 +26,12 @@ SYMBOLS = [
     "pepsgpu_walkers_set_configs", "pepsgpu_walkers_get_configs", "pepsgpu_n_walkers",
     "pepsgpu_grow_bmps_step", "pepsgpu_grow_full_bmps", "pepsgpu_grow_bmps_for_row", "pepsgpu_grow_bmps_for_col",
     "pepsgpu_shift_bmps_window", "pepsgpu_delete_inner_bmps", "pepsgpu_bmps_park", "pepsgpu_bmps_unpark", "pepsgpu_generate_bmps_approach",
-    "pepsgpu_sweep_slice_exchange", "pepsgpu_sweep_slice_exchange_tab", "pepsgpu_sweep_slice_fullspace", "pepsgpu_sweep_slice_tnn3", "pepsgpu_diag_tnn3_table", "pepsgpu_nn_exchange_slice", "pepsgpu_nn_exchange_slice_tab", "pepsgpu_onsite_slice", "pepsgpu_nnn_exchange_slice", "pepsgpu_diag_nnn_slice_calls", "pepsgpu_nnn_hop_slice_fermion", "pepsgpu_diag_nnn_hop_slice_calls", "pepsgpu_diag_fermion_hop_cand", "pepsgpu_nn_pair_slice_fermion", "pepsgpu_diag_pair_slice_calls", "pepsgpu_diag_pair_cand", "pepsgpu_link_exchange_slice", "pepsgpu_diag_link_slice_calls", "pepsgpu_diag_link_cand", "pepsgpu_walker_create", "pepsgpu_walker_clone", "pepsgpu_walker_destroy", "pepsgpu_walker_info", "pepsgpu_walker_set_mpo", "pepsgpu_walker_set_mpo_excited", "pepsgpu_walker_trace_slice", "pepsgpu_diag_walker_slice_calls", "pepsgpu_walker_evolve",
+    "pepsgpu_sweep_slice_exchange", "pepsgpu_sweep_slice_exchange_tab", "pepsgpu_sweep_slice_fullspace", "pepsgpu_sweep_slice_tnn3", "pepsgpu_diag_tnn3_table", "pepsgpu_nn_exchange_slice", "pepsgpu_nn_exchange_slice_tab", "pepsgpu_onsite_slice", "pepsgpu_nnn_exchange_slice", "pepsgpu_diag_nnn_slice_calls", "pepsgpu_nnn_hop_slice_fermion", "pepsgpu_diag_nnn_hop_slice_calls", "pepsgpu_diag_fermion_hop_cand", "pepsgpu_nn_pair_slice_fermion", "pepsgpu_diag_pair_slice_calls", "pepsgpu_diag_pair_cand", "pepsgpu_nn_hop_slice_fermion", "pepsgpu_diag_hop_slice_calls", "pepsgpu_sweep_slice_sector", "pepsgpu_diag_sector_slice_calls", "pepsgpu_diag_sector_cand", "pepsgpu_link_exchange_slice", "pepsgpu_diag_link_slice_calls", "pepsgpu_diag_link_cand", "pepsgpu_walker_create", "pepsgpu_walker_clone", "pepsgpu_walker_destroy", "pepsgpu_walker_info", "pepsgpu_walker_set_mpo", "pepsgpu_walker_set_mpo_excited", "pepsgpu_walker_trace_slice", "pepsgpu_diag_walker_slice_calls", "pepsgpu_walker_evolve",
     "pepsgpu_walker_evolve_step", "pepsgpu_walker_contract_row", "pepsgpu_walker_init_bten", "pepsgpu_walker_grow_bten_step",
     "pepsgpu_walker_shift_bten_window", "pepsgpu_walker_trace_with_bten", "pepsgpu_walker_clear_bten", "pepsgpu_walker_get_bmps_tensor",
     "pepsgpu_bmps_stack_size", "pepsgpu_get_bmps_tensor", "pepsgpu_init_bten", "pepsgpu_grow_full_bten",
     "pepsgpu_grow_bten_step", "pepsgpu_shift_bten_window", "pepsgpu_truncate_bten", "pepsgpu_bten_stack_size",
-    "pepsgpu_trace", "pepsgpu_replace_nn_trace", "pepsgpu_replace_one_trace", "pepsgpu_punch_hole",
+    "pepsgpu_trace", "pepsgpu_replace_nn_trace", "pepsgpu_replace_one_trace", "pepsgpu_trace_scaling", "pepsgpu_punch_hole",
     "pepsgpu_init_bten2", "pepsgpu_grow_full_bten2", "pepsgpu_grow_bten2_step", "pepsgpu_shift_bten2_window",
     "pepsgpu_bten2_stack_size", "pepsgpu_replace_nnn_trace", "pepsgpu_replace_tnn_trace",
     "pepsgpu_bten2_select_set", "pepsgpu_cfg_override_slice", "pepsgpu_replace_plaquette_trace",
@@ -84,6 +84,7 @@ def load_library(path=LIB_PATH):
     lib.pepsgpu_replace_nn_trace.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, dp]
     lib.pepsgpu_replace_one_trace.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, dp]
     lib.pepsgpu_punch_hole.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp]
+    lib.pepsgpu_trace_scaling.argtypes = [vp, C.c_int]
     for name in ("init_bten2", "grow_bten2_step", "shift_bten2_window"):
         getattr(lib, "pepsgpu_" + name).argtypes = [vp, C.c_int, C.c_int]
     lib.pepsgpu_grow_full_bten2.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
@@ -125,6 +126,13 @@ def load_library(path=LIB_PATH):
     lib.pepsgpu_diag_pair_slice_calls.argtypes = []
     lib.pepsgpu_diag_pair_slice_calls.restype = C.c_long
     lib.pepsgpu_diag_pair_cand.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, C.c_int, ip, C.c_int, C.c_int, C.c_int, ip, ip]
+    lib.pepsgpu_nn_hop_slice_fermion.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, dp, dp]
+    lib.pepsgpu_diag_hop_slice_calls.argtypes = []
+    lib.pepsgpu_diag_hop_slice_calls.restype = C.c_long
+    lib.pepsgpu_sweep_slice_sector.argtypes = [vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, ip, C.c_int, C.POINTER(C.c_uint32), dp, ip, ip, ip]
+    lib.pepsgpu_diag_sector_slice_calls.argtypes = []
+    lib.pepsgpu_diag_sector_slice_calls.restype = C.c_long
+    lib.pepsgpu_diag_sector_cand.argtypes = [C.c_int, C.c_int, C.c_int, ip, C.c_int, ip, C.c_int, ip, C.c_int, C.c_int, C.c_int, ip, ip]
     lib.pepsgpu_link_exchange_slice.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp]
     lib.pepsgpu_diag_link_slice_calls.argtypes = []
     lib.pepsgpu_diag_link_slice_calls.restype = C.c_long
@@ -475,6 +483,43 @@ class Context:
                                                        _dp(ex) if ex is not None else None, _dp(pair)))
         return psi, ex, pair
 
+    def nn_hop_slice_fermion(self, orientation, slice_num, nf, hop_table, punch_holes=False):
+        """one row / column of a fermionic state with up to two hop candidates per bond (the Hubbard model): hop_table [d * d][2][2] over
+        physical states as the pair_table of nn_pair_slice_fermion.  punch_holes: the row pass of the energy evaluation, the hole of
+        every site of the slice goes into HBM and the window is shifted after the last bond too.  Returns (psi [n][N-1], hop [n][N-1][2]),
+        hop exactly 0 for "no candidate"; one read-back"""
+        occ = np.ascontiguousarray(nf, dtype=np.int32)
+        tab = np.ascontiguousarray(hop_table, dtype=np.int32)
+        assert tab.size == occ.size * occ.size * 4, tab.shape
+        N = self.cols if orientation == HORIZONTAL else self.rows
+        psi = np.zeros((self.n, N - 1), dtype=self._ot)
+        hop = np.zeros((self.n, N - 1, 2), dtype=self._ot)
+        self._ck(self._l.pepsgpu_nn_hop_slice_fermion(self._h, orientation, slice_num, int(punch_holes), occ.size, _ip(occ), _ip(tab),
+                                                      _dp(psi), _dp(hop)))
+        return psi, hop
+
+    def sweep_slice_sector(self, orientation, slice_num, sector_table, engine_words, amplitude, nf=None):
+        """one row / column of Suwa-Todo moves inside the tabulated sector of each bond (MCUpdateSquareNNHubbardU1U1OBC) on the device:
+        sector_table [d * d][2 + 2 max_cand] over physical states (m, init, max_cand slots, unused ones (-1, -1)); nf [d] the fermion
+        number of each physical state for a fermionic context (4 d = its physical dimension), None for a bosonic one (d = its physical
+        dimension); engine_words [n][n_words] uint32 (n_words >= 2 (N - 1)) = the next raw outputs of each walker's mt19937.  Returns
+        (amplitude [n] after the slice, consumed words [n], accepted moves [n], slice_states [n][N])"""
+        N = self.cols if orientation == HORIZONTAL else self.rows
+        tab = np.ascontiguousarray(sector_table, dtype=np.int32)
+        occ = None if nf is None else np.ascontiguousarray(nf, dtype=np.int32)
+        d = self.d if occ is None else occ.size
+        assert tab.ndim == 2 and tab.shape[0] == d * d and tab.shape[1] >= 4 and tab.shape[1] % 2 == 0, tab.shape
+        wd = np.ascontiguousarray(engine_words, dtype=np.uint32)
+        assert wd.ndim == 2 and wd.shape[0] == self.n, wd.shape
+        amp = np.array(amplitude, dtype=self._ot)
+        assert amp.shape == (self.n,), amp.shape
+        cons, acc = np.zeros(self.n, dtype=np.int32), np.zeros(self.n, dtype=np.int32)
+        st = np.zeros((self.n, N), dtype=np.int32)
+        self._ck(self._l.pepsgpu_sweep_slice_sector(self._h, orientation, slice_num, d, None if occ is None else _ip(occ),
+                                                    (tab.shape[1] - 2) // 2, _ip(tab), wd.shape[1],
+                                                    wd.ctypes.data_as(C.POINTER(C.c_uint32)), _dp(amp), _ip(cons), _ip(acc), _ip(st)))
+        return amp, cons, acc, st
+
     def onsite_slice(self, orientation, slice_num, site_table, punch_holes=False):
         """one-site moves along a row / column: site_table [d][n_cand] (candidate k of state s); returns (psi [n],
         psi_cand [n][N][n_cand])"""
@@ -570,6 +615,11 @@ class Context:
         out = np.zeros((self.n, self.D, self.D, self.D, self.D), dtype=self._ot)
         self._ck(self._l.pepsgpu_punch_hole(self._h, row, col, orient, _dp(out)))
         return out
+
+    def trace_scaling(self, on_device):
+        """trace / replace_nn_trace / replace_one_trace multiply by exp(log-scale) in a kernel, as the device-side slices do (True), or
+        with std::exp on the host (False, the default): the two may differ in the last bit"""
+        self._ck(self._l.pepsgpu_trace_scaling(self._h, int(bool(on_device))))
 
     def punch_hole_store(self, row, col, orient):
         self._ck(self._l.pepsgpu_punch_hole(self._h, row, col, orient, None))
@@ -1289,6 +1339,35 @@ def diag_pair_cand(ext, nf, pair_table, orientation, site1, site2):
     if rc != 0:
         raise ValueError("diag_pair_cand: status %d" % rc)
     return cand, sign
+
+
+def diag_hop_slice_calls():
+    """completed pepsgpu_nn_hop_slice_fermion calls of this process"""
+    return int(lib().pepsgpu_diag_hop_slice_calls())
+
+
+def diag_sector_slice_calls():
+    """completed pepsgpu_sweep_slice_sector calls of this process"""
+    return int(lib().pepsgpu_diag_sector_slice_calls())
+
+
+def diag_sector_cand(cfg, sector_table, orientation, site1, site2, nf=None):
+    """sector_cand_kernel alone: cfg [n][rows][cols] (nf given: extended configurations of the mode order of `orientation`; None: bosonic
+    states), sector_table [d * d][2 + 2 max_cand]; (site1, site2) the flat row-major indices of the bond's left / upper and right / lower
+    site.  Returns (cand [n][max_cand][2], meta [n][2] = (m, init))"""
+    e = np.ascontiguousarray(cfg, dtype=np.int32)
+    tab = np.ascontiguousarray(sector_table, dtype=np.int32)
+    occ = None if nf is None else np.ascontiguousarray(nf, dtype=np.int32)
+    n, rows, cols = e.shape
+    max_cand = (tab.shape[1] - 2) // 2
+    d = int(round(np.sqrt(tab.shape[0])))
+    assert tab.ndim == 2 and d * d == tab.shape[0] and (occ is None or occ.size == d), tab.shape
+    cand, meta = np.zeros((n, max_cand, 2), dtype=np.int32), np.zeros((n, 2), dtype=np.int32)
+    rc = lib().pepsgpu_diag_sector_cand(rows, cols, d, None if occ is None else _ip(occ), max_cand, _ip(tab), n, _ip(e), orientation,
+                                        site1, site2, _ip(cand), _ip(meta))
+    if rc != 0:
+        raise ValueError("diag_sector_cand: status %d" % rc)
+    return cand, meta
 
 
 def diag_link_slice_calls():

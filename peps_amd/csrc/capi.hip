@@ -274,6 +274,57 @@ int pepsgpu_diag_pair_cand(int rows, int cols, int d, const int32_t *occ, const 
     PG_CHECK_HIP(hipMemcpy(sign_out, ds, 2 * (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
   });
 }
+// square_hubbard_model.h:200-262: psi and the two hopped amplitudes of every bond of one row / column, with the holes of the row pass
+int pepsgpu_nn_hop_slice_fermion(pepsgpu_ctx *ctx, int orientation, int slice, int punch_holes, int d, const int32_t *occ,
+                                 const int32_t *hop_table, double *psi_out, double *hop_out) {
+  CTX_CALL(PG_REQUIRE(occ && hop_table && psi_out && hop_out, 1, "null buffer");
+           ctx->eng->nn_hop_slice_fermion(orientation, slice, punch_holes, d, occ, hop_table, psi_out, hop_out));
+}
+long pepsgpu_diag_hop_slice_calls(void) { return pepsgpu::hop_slice_calls().load(); }
+// square_nn_updater.h:41-55 / :62-76 (one slice of MCUpdateSquareNNUpdateBaseOBC::operator()) + square_hubbard_u1u1_updater.h:95-157
+// per bond
+int pepsgpu_sweep_slice_sector(pepsgpu_ctx *ctx, int orientation, int slice, int d, const int32_t *occ, int max_cand,
+                               const int32_t *sector_table, int n_words, const uint32_t *engine_words, double *amplitude_inout,
+                               int32_t *consumed_out, int32_t *accepted_out, int32_t *slice_states_out) {
+  CTX_CALL(PG_REQUIRE(sector_table && engine_words && amplitude_inout && consumed_out && accepted_out, 1, "null buffer");
+           ctx->eng->sweep_slice_sector(orientation, slice, d, occ, max_cand, sector_table, n_words, engine_words, amplitude_inout,
+                                        consumed_out, accepted_out, slice_states_out));
+}
+long pepsgpu_diag_sector_slice_calls(void) { return pepsgpu::sector_slice_calls().load(); }
+// sector_cand_kernel alone on a caller's configurations ext [n][rows][cols] for the bond (site1, site2), flat row-major indices of the
+// left / upper and the right / lower site: cand_out [n][max_cand][2], meta_out [n][2] = (m, init).  occ NULL: a bosonic table over
+// states in [0, d); else extended states in [0, 4 d) of the mode order of `orientation` on the two sites
+int pepsgpu_diag_sector_cand(int rows, int cols, int d, const int32_t *occ, int max_cand, const int32_t *sector_table, int n,
+                             const int32_t *ext, int orientation, int site1, int site2, int32_t *cand_out, int32_t *meta_out) {
+  return guarded(nullptr, [&]() {
+    PG_REQUIRE(sector_table && ext && cand_out && meta_out, 1, "null buffer");
+    PG_REQUIRE(orientation == HORIZONTAL || orientation == VERTICAL, 1, "bad orientation");
+    PG_REQUIRE(rows >= 1 && cols >= 1 && n >= 1 && (double)n * rows * cols < 2147483648.0, 1, "bad sizes");
+    const bool hor = orientation == HORIZONTAL;
+    const int sites = rows * cols;
+    PG_REQUIRE(site1 >= 0 && site2 < sites && site2 == site1 + (hor ? 1 : cols) && (!hor || site1 % cols + 1 < cols), 1,
+               "the two sites are no bond of this orientation");
+    const unsigned occ_bits = pepsgpu::require_sector_table(d, occ, max_cand, sector_table);
+    const int dp = occ ? 4 * d : d;
+    const size_t ne = (size_t)n * sites;
+    for (size_t e = 0; e < ne; ++e) PG_REQUIRE(ext[e] >= 0 && ext[e] < dp, 1, "state outside the physical dimension");
+    if (occ)
+      for (int w = 0; w < n; ++w)
+        for (int s : {site1, site2})
+          PG_REQUIRE((ext[(size_t)w * sites + s] / d >= 2) == !hor, 1, "extended states of the other mode order on the bond");
+    PG_REQUIRE((double)n * max_cand < 1073741824.0, 1, "bad sizes");
+    DevBufs m;
+    const int *dcfg = m.alloc<int>(ne, ext);
+    const int *dtab = m.alloc<int>((size_t)d * d * pepsgpu::sector_row_len(max_cand), sector_table);
+    int *dc = m.alloc<int>((2 * (size_t)max_cand + 2) * n), *dm = dc + 2 * (size_t)max_cand * n;
+    hipLaunchKernelGGL(sector_cand_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, dcfg, sites, site1, site2, d, occ_bits,
+                       !occ ? 0 : hor ? 1 : 2, dtab, max_cand, dc, dm, n);
+    PG_CHECK_HIP(hipGetLastError());
+    PG_CHECK_HIP(hipDeviceSynchronize());
+    PG_CHECK_HIP(hipMemcpy(cand_out, dc, 2 * (size_t)max_cand * n * sizeof(int), hipMemcpyDeviceToHost));
+    PG_CHECK_HIP(hipMemcpy(meta_out, dm, 2 * (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+  });
+}
 // spin_onehalf_triangle_heisenbergJ1J2_sqrpeps.h:350-398 / :425-442: the links of one row pair / column pair
 int pepsgpu_link_exchange_slice(pepsgpu_ctx *ctx, int orient, int slice1, int link_mask, double *val_out) {
   CTX_CALL(PG_REQUIRE(val_out, 1, "null buffer"); ctx->eng->link_exchange_slice(orient, slice1, link_mask, val_out));
@@ -422,6 +473,9 @@ int pepsgpu_replace_sqrt5_trace(pepsgpu_ctx *ctx, int row, int col, int link_dir
   CTX_CALL(PG_REQUIRE((ncand == 0 || cand) && ncand >= 0 && out, 1, "bad candidate table");
            PG_REQUIRE(link_dir == 0 || link_dir == 1, 1, "bad diagonal direction");
            ctx->eng->replace_sqrt5_trace(row, col, link_dir, orient, ncand, cand, out));
+}
+int pepsgpu_trace_scaling(pepsgpu_ctx *ctx, int on_device) {
+  CTX_CALL(ctx->eng->trace_scaling_on_device = on_device != 0);
 }
 int pepsgpu_punch_hole(pepsgpu_ctx *ctx, int row, int col, int orient, double *out) {
   CTX_CALL(ctx->eng->punch_hole(row, col, orient, out));

@@ -37,6 +37,16 @@ __global__ void skip_batch_flag_kernel(const int *__restrict__ skip, int div, in
   if (b < nb) flag[b] = skip[b / div] ? 0 : -1;
 }
 
+// out[i] = res[i] exp(lsum[i / nc]) on the device: the scaling of the slice kernels (slice_store_value_kernel, pair_store_kernel of
+// engine_sweep.h) for the read-back of a per-call trace (Engine::finish_read with trace_scaling_on_device)
+__device__ __forceinline__ double scaled_by(double x, double s) { return x * s; }
+__device__ __forceinline__ cplx<double> scaled_by(const cplx<double> &x, double s) { return cplx<double>(x.re * s, x.im * s); }
+template <typename AccT>
+__global__ void scale_exp_kernel(const AccT *__restrict__ res, const double *__restrict__ lsum, AccT *__restrict__ out, int nb, int nc) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nb) out[i] = scaled_by(AccT(res[i]), exp(lsum[i / nc]));
+}
+
 // kernel categories of the event profile (pepsgpu_profile_read)
 enum { PROF_CONTRACT = 0, PROF_GRAM = 1, PROF_CHOL = 2, PROF_JACOBI = 3, PROF_SELECT = 4, PROF_NORM = 5,
        PROF_ENV = 6, PROF_JACOBI_EDGE = 7, PROF_TRUNC_GRAM = 8, PROF_TRUNC_APPLY = 9,
@@ -48,6 +58,9 @@ struct EngineBase {
   std::string last_error;
   int dtype = 0;
   int device_id = 0;   // every C-ABI call makes this the calling thread's current HIP device first (capi.hip CTX_CALL)
+  // pepsgpu_trace_scaling: the read-back of pepsgpu_trace / pepsgpu_replace_*_trace multiplies by exp(log-scale) in a kernel, as the
+  // slices do, instead of with std::exp on the host (the two exponentials may differ in the last bit); default off
+  bool trace_scaling_on_device = false;
   virtual void *stream_handle() = 0;                                        // hipStream_t of every launch of this context
   virtual void grad_device_ptr(void **so, void **seo, long *n_elems) = 0;   // HBM-resident f64 accumulators (grad_reset)
   // --- contractor surface (all walkers in lockstep) ---
@@ -164,6 +177,13 @@ struct EngineBase {
   // psi, the exchanged amplitude and up to two pair candidates per bond of one row / column of a fermionic context; engine_sweep.h
   virtual void nn_pair_slice_fermion(int orient, int slice, int d, const int32_t *occ, const int32_t *pair_table,
                                      const int32_t *exchange_table, double *psi_out, double *ex_out, double *pair_out) = 0;
+  // the pair slice without the exchange slot, optionally with the holes of the slice (the Hubbard hops: two candidates per bond)
+  virtual void nn_hop_slice_fermion(int orient, int slice, int punch_holes, int d, const int32_t *occ, const int32_t *hop_table,
+                                    double *psi_out, double *hop_out) = 0;
+  // one row / column of Suwa-Todo moves among the tabulated candidates of each bond (MCUpdateSquareNNHubbardU1U1OBC); engine_sweep.h
+  virtual void sweep_slice_sector(int orient, int slice, int d, const int32_t *occ, int max_cand, const int32_t *sector_table,
+                                  int n_words, const uint32_t *words, double *amp_inout, int32_t *consumed_out, int32_t *accepted_out,
+                                  int32_t *slice_states_out) = 0;
   // BMPSWalker (bmps_contractor.h:357-646)
   virtual int walker_create(int pos, int level) = 0;
   virtual int walker_clone(int id) = 0;
@@ -1055,6 +1075,13 @@ class Engine : public EngineBase {
   void nnn_hop_slice_fermion(int row1, int d, const int32_t *occ, int diag_mask, double *psi_out, double *val_out) override;
   void nn_pair_slice_fermion(int orient, int slice, int d, const int32_t *occ, const int32_t *pair_table, const int32_t *exchange_table,
                              double *psi_out, double *ex_out, double *pair_out) override;
+  void nn_hop_slice_fermion(int orient, int slice, int punch_holes, int d, const int32_t *occ, const int32_t *hop_table, double *psi_out,
+                            double *hop_out) override;
+  void nn_pair_slice_body(int orient, int slice, int punch_holes, int d, const int32_t *occ, const int32_t *pair_table,
+                          const int32_t *exchange_table, double *psi_out, double *ex_out, double *pair_out);
+  void sweep_slice_sector(int orient, int slice, int d, const int32_t *occ, int max_cand, const int32_t *sector_table, int n_words,
+                          const uint32_t *words, double *amp_inout, int32_t *consumed_out, int32_t *accepted_out,
+                          int32_t *slice_states_out) override;
   // the parts the slice functions share (engine_sweep.h)
   void begin_slice(const SliceGeom &g, int remain);
   template <typename Moves>
@@ -1259,6 +1286,20 @@ class Engine : public EngineBase {
   void finish_read(const Acc *res, int nb, int nc, const double *lsum, double *out) {
     std::vector<Acc> h(nb);
     std::vector<double> hl(nw_);
+    if (trace_scaling_on_device) {
+      Acc *scaled = (Acc *)arena_.alloc(sizeof(Acc) * (size_t)std::max(nb, 1));
+      hipLaunchKernelGGL(scale_exp_kernel<Acc>, dim3((nb + 255) / 256), dim3(256), 0, stream_, res, lsum, scaled, nb, nc);
+      hipError_t e = hipGetLastError();
+      if (e == hipSuccess) e = hipMemcpyAsync(h.data(), scaled, nb * sizeof(Acc), hipMemcpyDeviceToHost, stream_);
+      if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+      arena_.free(scaled);
+      PG_CHECK_HIP(e);
+      for (int i = 0; i < nb; ++i) {
+        if constexpr (kCplx) { out[2 * i] = h[i].re; out[2 * i + 1] = h[i].im; }
+        else out[i] = h[i];
+      }
+      return;
+    }
     PG_CHECK_HIP(hipMemcpyAsync(h.data(), res, nb * sizeof(Acc), hipMemcpyDeviceToHost, stream_));
     PG_CHECK_HIP(hipMemcpyAsync(hl.data(), lsum, nw_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
     PG_CHECK_HIP(hipStreamSynchronize(stream_));

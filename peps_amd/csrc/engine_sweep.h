@@ -823,6 +823,32 @@ inline std::atomic<long> &pair_slice_calls() {   // completed nn_pair_slice_ferm
 template <typename T>
 void Engine<T>::nn_pair_slice_fermion(int orient, int slice, int d, const int32_t *occ, const int32_t *pair_table,
                                       const int32_t *exchange_table, double *psi_out, double *ex_out, double *pair_out) {
+  nn_pair_slice_body(orient, slice, 0, d, occ, pair_table, exchange_table, psi_out, ex_out, pair_out);
+  pair_slice_calls() += 1;
+}
+
+inline std::atomic<long> &hop_slice_calls() {    // completed nn_hop_slice_fermion calls of the process (pepsgpu_diag_hop_slice_calls)
+  static std::atomic<long> n{0};
+  return n;
+}
+
+// The pair slice without an exchange slot for models whose bond term is up to two hops (the Hubbard model, square_hubbard_model.h:
+// 200-262: Trace + ReplaceNNSiteTrace of the hopped pairs per bond).  punch_holes != 0: the row pass of the energy evaluation,
+// GrowFullBTen(.., 1, true), the hole of every site punched into HBM before that site's bond and the window shifted after the last
+// bond too (mode 0 of energy_slice_impl).
+template <typename T>
+void Engine<T>::nn_hop_slice_fermion(int orient, int slice, int punch_holes, int d, const int32_t *occ, const int32_t *hop_table,
+                                     double *psi_out, double *hop_out) {
+  nn_pair_slice_body(orient, slice, punch_holes, d, occ, hop_table, nullptr, psi_out, nullptr, hop_out);
+  hop_slice_calls() += 1;
+}
+
+// The body of the two entries above.  punch_holes == 0 is the pair slice as described there; punch_holes != 0 grows the shrinking
+// environment down to the last ONE position, punches the hole of site j before bond j (and of the last site after the last bond) and
+// shifts the window after every bond.
+template <typename T>
+void Engine<T>::nn_pair_slice_body(int orient, int slice, int punch_holes, int d, const int32_t *occ, const int32_t *pair_table,
+                                   const int32_t *exchange_table, double *psi_out, double *ex_out, double *pair_out) {
   require_ready();
   const SliceGeom g(orient, slice, Lx_, Ly_);
   PG_REQUIRE(occ && pair_table && psi_out && pair_out && (!exchange_table || ex_out), 1, "null buffer");
@@ -850,10 +876,16 @@ void Engine<T>::nn_pair_slice_fermion(int orient, int slice, int d, const int32_
   int *dxtab = exchange_table ? dtab + 4 * (size_t)d * d : nullptr;
   PG_CHECK_HIP(hipMemcpyAsync(dtab, pair_table, sizeof(int) * 4 * (size_t)d * d, hipMemcpyHostToDevice, stream_));
   if (dxtab) PG_CHECK_HIP(hipMemcpyAsync(dxtab, exchange_table, sizeof(int) * xlen, hipMemcpyHostToDevice, stream_));
-  begin_slice(g, 2);
+  if (punch_holes && !holes_) {
+    holes_ = (T *)arena_.alloc(sizeof(T) * (size_t)maxw_ * Ly_ * Lx_ * slot_);
+    holes_ls_ = (double *)arena_.alloc(sizeof(double) * (size_t)maxw_ * Ly_ * Lx_);
+  }
+  begin_slice(g, punch_holes ? 1 : 2);
   const int gb = (nw_ + 255) / 256;
-  for (int j = 0; j + 1 < N; ++j) {
+  for (int j = 0; j < N; ++j) {
     const int r1 = g.row(j), c1 = g.col(j);
+    if (punch_holes) punch_hole(r1, c1, orient, nullptr);
+    if (j + 1 >= N) break;
     {
       double *lsum = nullptr;
       Acc *res = nn_trace_device(r1, c1, orient, 1, nullptr, &lsum);
@@ -871,7 +903,7 @@ void Engine<T>::nn_pair_slice_fermion(int orient, int slice, int d, const int32_
                        (const int *)dsign, dxtab ? (const int *)dsame : nullptr, dval, stride, j, np + j, 2 * np + 2 * j, nw_);
     PG_CHECK_HIP(hipGetLastError());
     arena_.free(res); arena_.free(lsum);
-    if (j + 2 < N) shift_bten_window(g.hi);
+    if (punch_holes || j + 2 < N) shift_bten_window(g.hi);
   }
   std::vector<double> h((size_t)kOut * nw_ * stride);
   if (!h.empty()) PG_CHECK_HIP(hipMemcpyAsync(h.data(), dval, sizeof(double) * h.size(), hipMemcpyDeviceToHost, stream_));
@@ -882,7 +914,6 @@ void Engine<T>::nn_pair_slice_fermion(int orient, int slice, int d, const int32_
     if (exchange_table) std::copy(row + (size_t)np * kOut, row + 2 * (size_t)np * kOut, ex_out + (size_t)w * np * kOut);
     std::copy(row + 2 * (size_t)np * kOut, row + 4 * (size_t)np * kOut, pair_out + 2 * (size_t)w * np * kOut);
   }
-  pair_slice_calls() += 1;
 }
 
 // ---- three-site exchange (MCUpdateSquareTNN3SiteExchange::TNN3SiteUpdateImpl, square_3site_updater.h:109-158) ----
@@ -1161,6 +1192,170 @@ void Engine<T>::sweep_slice_fullspace(int orient, int slice, int phys_dim, const
       if (j + 2 < g.N) shift_bten_window(g.hi);
     }
   });
+}
+
+// ---- Suwa-Todo moves inside a tabulated sector of each bond (MCUpdateSquareNNHubbardU1U1OBC::TwoSiteNNUpdateLocalImpl,
+// square_hubbard_u1u1_updater.h:95-157: the pairs with the (N_up, N_down) of the bond) ----
+// Sector table [d * d][2 + 2 max_cand] over PHYSICAL states, row a * d + b of the pair (a, b): m (the size of its sector), init (the
+// slot of the pair itself), then max_cand slots (a'_k, b'_k) in the order the updater enumerates them; slots m .. max_cand - 1 are
+// (-1, -1).  sector_row_len is the row length.
+__host__ __device__ inline int sector_row_len(int max_cand) { return 2 + 2 * max_cand; }
+
+// The table as the host hands it over: status 4 for a state outside [-1, d); status 1 for a row with m outside [1, max_cand], init
+// outside [0, m), a -1 in a used slot or a state in an unused one, a slot `init` that is not the pair itself or (fermions: occ given)
+// a candidate that changes the fermion parity of the pair.  Returns the occupation bits (0 for a bosonic table).
+inline unsigned require_sector_table(int d, const int32_t *occ, int max_cand, const int32_t *tab) {
+  PG_REQUIRE(max_cand >= 1 && max_cand <= SW_MAXC, 1, "sector table: 1 <= max_cand <= 16");
+  PG_REQUIRE(d >= 1 && tab, 1, "sector table: d < 1 or a null table");
+  const unsigned occ_bits = occ ? hop_occ_bits(d, occ) : 0u;
+  const int len = sector_row_len(max_cand);
+  for (int a = 0; a < d; ++a)
+    for (int b = 0; b < d; ++b) {
+      const int32_t *t = tab + (size_t)(a * d + b) * len;
+      for (int k = 0; k < 2 * max_cand; ++k) PG_REQUIRE(t[2 + k] >= -1 && t[2 + k] < d, 4, "sector table: state out of range");
+      PG_REQUIRE(t[0] >= 1 && t[0] <= max_cand && t[1] >= 0 && t[1] < t[0], 1, "sector table: bad sector size or initial slot");
+      for (int k = 0; k < max_cand; ++k) {
+        const int pa = t[2 + 2 * k], pb = t[3 + 2 * k];
+        PG_REQUIRE(k < t[0] ? (pa >= 0 && pb >= 0) : (pa < 0 && pb < 0), 1, "sector table: a used slot with -1 or an unused slot with a state");
+        PG_REQUIRE(k >= t[0] || !occ || ((occ[pa] + occ[pb] + occ[a] + occ[b]) & 1) == 0, 1,
+                   "sector table: a candidate changes the fermion parity of the pair");
+      }
+      PG_REQUIRE(t[2 + 2 * t[1]] == a && t[3 + 2 * t[1]] == b, 1, "sector table: the initial slot is not the pair itself");
+    }
+  return occ_bits;
+}
+
+// Per walker: the physical pair (a, b) of the bond (s1, s2) looked up in the sector table -> max_cand candidate slots cand [w][max_cand][2]
+// and meta [w][2] = (m, init).  mode 0: a bosonic table, the slots are the states themselves; mode 1 / 2: a fermionic context in
+// row-major / column-major order, the extended states of the two sites by the rule of pair_cand_kernel (the candidates keep the fermion
+// parity of the pair, so only these two variants change).  A walker without candidate k keeps its own pair in slot k.
+__global__ void sector_cand_kernel(const int *__restrict__ cfg, int sites, int s1, int s2, int d, unsigned occ_bits, int mode,
+                                   const int *__restrict__ tab, int max_cand, int *__restrict__ cand, int *__restrict__ meta, int n) {
+  const int w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= n) return;
+  const int e1 = cfg[(long)w * sites + s1], e2 = cfg[(long)w * sites + s2];
+  const int a = e1 % d, b = e2 % d;
+  auto occ = [&](int s) { return (int)((occ_bits >> s) & 1u); };
+  const int col_major = mode == 2;
+  const int before = mode == 0 ? 0 : col_major ? ((e1 / d) & 1) : (((e1 / d) & 1) ^ occ(a));
+  const int *t = tab + (long)(a * d + b) * sector_row_len(max_cand);
+  const int m = t[0];
+  int *c = cand + 2 * (long)w * max_cand;
+  for (int k = 0; k < max_cand; ++k) {
+    const int pa = t[2 + 2 * k], pb = t[3 + 2 * k];
+    int c1 = e1, c2 = e2;
+    if (k < m && pa >= 0 && pb >= 0) {
+      if (mode == 0) {
+        c1 = pa;
+        c2 = pb;
+      } else {
+        const int na = occ(pa), nb = occ(pb);
+        c1 = pa + d * (col_major ? 2 + before : before ^ na);
+        c2 = pb + d * (col_major ? 2 + (before ^ na) : before ^ na ^ nb);
+      }
+    }
+    c[2 * k] = c1;
+    c[2 * k + 1] = c2;
+  }
+  meta[2 * w] = m;
+  meta[2 * w + 1] = t[1];
+}
+
+// :127-156 for one bond: the weights |psi_k / psi|^2 of the m states of the sector (the current one keeps its stored amplitude, weight
+// 1, as in sweep_suwa_todo_kernel), SuwaTodoStateUpdate with the walker's next two engine words -- taken only when m > 1 (:114-116),
+// the cursor is used[w] -- and the move.
+template <typename AccT>
+__global__ void sector_decide_kernel(int *__restrict__ cfg, int sites, int s1, int s2, const AccT *__restrict__ res,
+                                     const double *__restrict__ lsum, AccT *__restrict__ amp, const int *__restrict__ cand,
+                                     const int *__restrict__ meta, int max_cand, const unsigned *__restrict__ words, int n_words,
+                                     int *__restrict__ used, int *__restrict__ acc, int n) {
+  const int w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= n) return;
+  const int m = meta[2 * w], init = meta[2 * w + 1];
+  if (m <= 1) return;
+  const int q = used[w];
+  if (q + 2 > n_words) return;                              // (never: the host requires two words per bond of the slice)
+  const double sc = exp(lsum[w]);
+  const double pa = sw_abs(amp[w]);
+  double wt[SW_MAXC];
+  for (int k = 0; k < m; ++k) {
+    const double r = (k == init) ? 1.0 : sw_abs(sw_scaled(AccT(res[(long)w * max_cand + k]), sc)) / pa;
+    wt[k] = r * r;
+  }
+  const unsigned *wd = words + (long)w * n_words + q;
+  const int fin = sw_suwa_todo_decide(wt, m, init, wd[0], wd[1]);
+  used[w] = q + 2;
+  if (fin != init) {
+    const int *c = cand + ((long)w * max_cand + fin) * 2;
+    cfg[(long)w * sites + s1] = c[0];
+    cfg[(long)w * sites + s2] = c[1];
+    amp[w] = sw_scaled(AccT(res[(long)w * max_cand + fin]), sc);
+    acc[w] += 1;
+  }
+}
+
+inline std::atomic<long> &sector_slice_calls() {   // completed sweep_slice_sector calls of the process (pepsgpu_diag_sector_slice_calls)
+  static std::atomic<long> n{0};
+  return n;
+}
+
+// One row / column of MCUpdateSquareNNUpdateBaseOBC::operator() (square_nn_updater.h:41-55 / :62-76) with the sector move: InitBTen +
+// GrowFullBTen(.., 2), then per bond the candidates of the sector table, ONE replacement trace over the max_cand slots, the Suwa-Todo
+// decision and the move, and the BTen window shift while j + 2 < N -- one read-back at the end.  occ != nullptr: a fermionic context
+// (4 d == phys_dim, the extended states derived on the device); occ == nullptr: a bosonic one (d == phys_dim).
+template <typename T>
+void Engine<T>::sweep_slice_sector(int orient, int slice, int d, const int32_t *occ, int max_cand, const int32_t *sector_table,
+                                   int n_words, const uint32_t *words, double *amp_inout, int32_t *consumed_out, int32_t *accepted_out,
+                                   int32_t *slice_states_out) {
+  require_ready();
+  const SliceGeom g(orient, slice, Lx_, Ly_);
+  PG_REQUIRE(words && amp_inout && consumed_out && accepted_out && sector_table, 1, "null buffer");
+  PG_REQUIRE(n_words >= 2 * (g.N - 1), 1, "sector slice: two engine words per bond of the slice are needed");
+  PG_REQUIRE(d >= 1 && (occ ? 4 * d == dp_ : d == dp_), 1,
+             "sector slice: the context's physical dimension must be 4 d (fermions: occ given) or d (bosons: occ NULL)");
+  const unsigned occ_bits = require_sector_table(d, occ, max_cand, sector_table);
+  const bool hor = orient == HORIZONTAL;
+  const int sites = Ly_ * Lx_, gb = (nw_ + 255) / 256, N = g.N;
+  (void)bmps_at_slice(hor ? UP : LEFT, slice);
+  (void)bmps_at_slice(hor ? DOWN : RIGHT, slice);
+  // (the candidate kernel reads the walkers' own configuration table)
+  PG_REQUIRE(!ovr_on_, 3, "sector slice: a configuration override is active");
+  if (occ)
+    for (int w = 0; w < nw_; ++w)
+      for (int j = 0; j < N; ++j)
+        PG_REQUIRE((hcfg_[(size_t)w * sites + g.site(j)] / d >= 2) == !hor, 3,
+                   "sector slice: extended states of the other mode order in the slice (rows: variants 0 / 1, columns: 2 / 3)");
+  const int mode = !occ ? 0 : hor ? 1 : 2;
+  const size_t ntab = (size_t)d * d * sector_row_len(max_cand), nwd = (size_t)nw_ * std::max(n_words, 1);
+  ArenaBuf<Acc> damp(arena_, nw_);
+  ArenaBuf<unsigned> dwords(arena_, nwd);
+  ArenaBuf<int> dcnt(arena_, 2 * (size_t)nw_ + 1);                          // used words [n], accepted moves [n], (overrun: never set)
+  ArenaBuf<int> dcand(arena_, (2 * (size_t)max_cand + 2) * (size_t)nw_);    // candidates [n][max_cand][2], meta [n][2]
+  int *dmeta = dcand + 2 * (size_t)max_cand * nw_;
+  ArenaBuf<int> dtab(arena_, ntab);
+  PG_CHECK_HIP(hipMemcpyAsync(damp, amp_inout, sizeof(Acc) * nw_, hipMemcpyHostToDevice, stream_));
+  if (n_words > 0) PG_CHECK_HIP(hipMemcpyAsync(dwords, words, sizeof(unsigned) * (size_t)nw_ * n_words, hipMemcpyHostToDevice, stream_));
+  PG_CHECK_HIP(hipMemcpyAsync(dtab, sector_table, sizeof(int) * ntab, hipMemcpyHostToDevice, stream_));
+  sweep_slice_frame(g, 2, damp, dcnt, amp_inout, consumed_out, accepted_out, slice_states_out, [&] {
+    for (int j = 0; j + 1 < N; ++j) {
+      const int s1 = g.site(j), s2 = g.site(j + 1);
+      hipLaunchKernelGGL(sector_cand_kernel, dim3(gb), dim3(256), 0, stream_, (const int *)cfg_, sites, s1, s2, d, occ_bits, mode,
+                         (const int *)dtab, max_cand, dcand, dmeta, nw_);
+      PG_CHECK_HIP(hipGetLastError());
+      double *lsum = nullptr;
+      Acc *res = nn_trace_device(g.row(j), g.col(j), orient, max_cand, dcand, &lsum);
+      hipLaunchKernelGGL(sector_decide_kernel<Acc>, dim3(gb), dim3(256), 0, stream_, cfg_, sites, s1, s2, (const Acc *)res,
+                         (const double *)lsum, damp, (const int *)dcand, (const int *)dmeta, max_cand, (const unsigned *)dwords, n_words,
+                         dcnt, dcnt + nw_, nw_);
+      PG_CHECK_HIP(hipGetLastError());
+      arena_.free(res);
+      arena_.free(lsum);
+      erase_envs_after_update(g.row(j), g.col(j));
+      erase_envs_after_update(g.row(j + 1), g.col(j + 1));
+      if (j + 2 < N) shift_bten_window(g.hi);
+    }
+  });
+  sector_slice_calls() += 1;
 }
 
 }  // namespace pepsgpu

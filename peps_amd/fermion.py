@@ -515,6 +515,109 @@ def tj_observables(ctx, state, configs, t, J, V=0.0, mu=0.0, t2=0.0, pair="slice
             "SC_bond_singlet_v": out["sc_v"].reshape(n, -1)}, np.array(psis)
 
 
+# ---- the Hubbard model (square_hubbard_model.h; states 0 = up-down, 1 = up, 2 = down, 3 = empty, :18-23) ----
+HUBBARD_NF = (0, 1, 1, 0)                      # fermion parity of each state
+_HUB_UP, _HUB_DN = (1, 1, 0, 0), (1, 0, 1, 0)  # HubbardConfig2SpinCounts, square_hubbard_u1u1_updater.h:30-40
+_HUB_STATE = {(1, 1): 0, (1, 0): 1, (0, 1): 2, (0, 0): 3}
+
+
+def hubbard_sector_table():
+    """The sector table of pepsgpu_sweep_slice_sector for MCUpdateSquareNNHubbardU1U1OBC, [16][2 + 2 * 4] over physical states: row
+    a * 4 + b = (m, init, four slots (a', b')), the pairs with the (N_up, N_down) of (a, b) in the order of
+    EnumerateHubbardTwoSiteConfigsWithU1U1 (square_hubbard_u1u1_updater.h:57-72: a' in the outer loop, b' in the inner one), unused
+    slots (-1, -1); m is 4, 2 or 1."""
+    tab = -np.ones((16, 10), dtype=np.int32)
+    for a in range(4):
+        for b in range(4):
+            nu, nd = _HUB_UP[a] + _HUB_UP[b], _HUB_DN[a] + _HUB_DN[b]
+            sector = [(c1, c2) for c1 in range(4) for c2 in range(4)
+                      if _HUB_UP[c1] + _HUB_UP[c2] == nu and _HUB_DN[c1] + _HUB_DN[c2] == nd]
+            row = tab[a * 4 + b]
+            row[0], row[1] = len(sector), sector.index((a, b))
+            row[2:2 + 2 * len(sector)] = np.array(sector).ravel()
+    return tab
+
+
+def hubbard_hop_table():
+    """The hops of a nearest-neighbour bond of the Hubbard model in the states (a, b), a on the earlier site of the pass's mode order
+    (left / upper): (table [16][2][2], signs [16][2]).  Slot 0: the up electron hopped across the bond, slot 1: the down electron; at
+    most one hop per spin, (-1, -1) and sign 0 where there is none.  The bond energy is -t sum_k signs[k] conj(psi'_k / psi) with
+    s_up = (-1)^(n_down of site 1), s_down = (-1)^(n_up of site 2): the occupation of the one mode the hop passes in the order
+    (site 1 up, site 1 down, site 2 up, site 2 down); this is every branch of square_hubbard_model.h:200-262.  The table is the
+    hop_table of pepsgpu_nn_hop_slice_fermion."""
+    tab = -np.ones((16, 2, 2), dtype=np.int32)
+    sign = np.zeros((16, 2), dtype=np.int64)
+    for a in range(4):
+        for b in range(4):
+            ua, da, ub, db = _HUB_UP[a], _HUB_DN[a], _HUB_UP[b], _HUB_DN[b]
+            if ua != ub:
+                tab[a * 4 + b, 0] = (_HUB_STATE[(ub, da)], _HUB_STATE[(ua, db)])
+                sign[a * 4 + b, 0] = 1 - 2 * da
+            if da != db:
+                tab[a * 4 + b, 1] = (_HUB_STATE[(ua, db)], _HUB_STATE[(ub, da)])
+                sign[a * 4 + b, 1] = 1 - 2 * ub
+    return tab, sign
+
+
+def hubbard_observables(ctx, state, configs, t, U, mu=0.0, hop="slice", punch_holes=False):
+    """Registry of SquareNNModelMeasurementSolver<SquareHubbardModel>::EvaluateObservables (square_hubbard_model.h:127-171) for a batch
+    of configurations, driven from Python: energy [n, 1], charge, spin_z, double_occupancy [n, rows * cols], bond_energy_h / _v.
+    Also returns psi_list [rows + cols][n].  The bond energy is EvaluateBondEnergy (:190-262) by the rule of hubbard_hop_table, the
+    onsite energy U (#doublons) - mu (#electrons) (:101-117).
+    hop = "slice": one pepsgpu_nn_hop_slice_fermion per row / column (punch_holes: the row slices store their holes in HBM);
+    "calls": Trace + ReplaceNNSiteTrace per bond."""
+    from .capi import LEFT, DOWN, RIGHT, UP, HORIZONTAL, VERTICAL
+    if hop not in ("slice", "calls"):
+        raise ValueError("hubbard_observables: hop must be 'slice' or 'calls'")
+    if tuple(int(x) % 2 for x in state.nf) != HUBBARD_NF:
+        raise ValueError("hubbard_observables: the state's parities must be HUBBARD_NF")
+    cfg = np.asarray(configs)
+    n, rows, cols = cfg.shape
+    if rows < 2 or cols < 2:
+        raise ValueError("hubbard_observables: the lattice needs at least 2 rows and 2 columns")
+    dt = np.complex128 if state.is_complex else np.float64
+    table, sign = hubbard_hop_table()
+    nf = np.asarray(HUBBARD_NF)
+    out = {"h": np.zeros((n, rows, cols - 1), dt), "v": np.zeros((n, rows - 1, cols), dt)}
+    psis = []
+    for orient, order, approach, step, lo, hi, key in ((HORIZONTAL, ROW, UP, DOWN, LEFT, RIGHT, "h"), (VERTICAL, COL, LEFT, RIGHT, UP, DOWN, "v")):
+        S, N = (rows, cols) if orient == HORIZONTAL else (cols, rows)
+        ctx.set_configs(state.ext_config(cfg, order))
+        ctx.generate_bmps_approach(approach)
+        for s in range(S):
+            if hop == "slice":
+                psi, pr = ctx.nn_hop_slice_fermion(orient, s, nf, table, punch_holes=punch_holes and orient == HORIZONTAL)
+            else:
+                psi, _, pr = _pair_slice_by_calls(ctx, state, cfg, orient, order, lo, hi, s, table)
+            if np.any(psi == 0):
+                raise RuntimeError("Wavefunction amplitude is near zero, causing division by zero.")
+            psis.append(psi[:, 0])
+            for j in range(N - 1):
+                (r1, c1), (r2, c2) = ((s, j), (s, j + 1)) if orient == HORIZONTAL else ((j, s), (j + 1, s))
+                sg = sign[cfg[:, r1, c1] * 4 + cfg[:, r2, c2]]                  # [n][2]
+                out[key][:, r1, c1] = -t * np.sum(sg * np.conj(pr[:, j, :] / psi[:, j, None]), axis=1)
+            if s + 1 < S:
+                ctx.shift_bmps_window(step)
+    doublon = (cfg == 0).astype(np.float64)
+    charge = np.asarray(_HUB_UP)[cfg] + np.asarray(_HUB_DN)[cfg]
+    energy = out["h"].sum(axis=(1, 2)) + out["v"].sum(axis=(1, 2)) + U * doublon.sum(axis=(1, 2)) - mu * charge.sum(axis=(1, 2))
+    return {"energy": energy[:, None], "spin_z": (0.5 * (np.asarray(_HUB_UP)[cfg] - np.asarray(_HUB_DN)[cfg])).reshape(n, -1),
+            "charge": charge.astype(np.float64).reshape(n, -1), "double_occupancy": doublon.reshape(n, -1),
+            "bond_energy_h": out["h"].reshape(n, -1), "bond_energy_v": out["v"].reshape(n, -1)}, np.array(psis)
+
+
+def hubbard_energy(ctx, state, configs, t, U, mu=0.0, bonds=None, hop="slice", punch_holes=False):
+    """E_loc(S) of H = -t sum_<ij>,s (c+_is c_js + h.c.) + U sum n_up n_down - mu N (square_hubbard_model.h:50-52).  Returns
+    (energy [n], psi_list [rows + cols][n]); `bonds` (a dict) receives the per-bond energies "h" and "v"; hop as in
+    hubbard_observables."""
+    cfg = np.asarray(configs)
+    n, rows, cols = cfg.shape
+    obs, psis = hubbard_observables(ctx, state, cfg, t, U, mu, hop, punch_holes)
+    if bonds is not None:
+        bonds.update(h=obs["bond_energy_h"].reshape(n, rows, cols - 1), v=obs["bond_energy_v"].reshape(n, rows - 1, cols))
+    return obs["energy"][:, 0], psis
+
+
 def exact_sum_measure(ctx, state, all_configs, t, V=0.0, rank=0, size=1, batch=None, t2=0.0, tj=None):
     """ExactSumMeasurerMPI (exact_summation_measurer.h:103-257) on the device: configurations rank, rank + size, ... in
     batches of walkers; returns (weighted sums by key, weight sum) -- sum both over ranks (all-reduce) and divide.

@@ -431,6 +431,9 @@ void fermion_energy_impl(int rows, int cols, int D, int d, const int32_t *nf, in
   if (model == 0) {
     SquareSpinlessFermion m(prm[0], prm[2], prm[1]);      // (t, t2, V): params = [t, V, t2, -]
     eh = m.CalEnergyAndHoles<false>(sitps, comp);
+  } else if (model == 3) {
+    SquareHubbardModel m(prm[0], prm[1], prm[2]);         // [t, U, mu]
+    eh = m.CalEnergyAndHoles<false>(sitps, comp);
   } else {
     SquaretJVModel m(prm[0], n_prm > 4 ? prm[4] : 0.0, prm[1], prm[2], prm[3]);      // [t, J, V, mu, (t2)]
     eh = m.CalEnergyAndHoles<false>(sitps, comp);
@@ -463,7 +466,8 @@ template <typename TenElemT>
 void fermion_exact_sum_partial_prm_impl(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype,
                                         const double *sitps_ext_flat, const int32_t *all_configs, int n_configs, int model,
                                         const double *prm, int n_prm, int rank, int size, int batch, double *packed_out) {
-  if ((model != 0 && model != 1) || !prm || n_prm < 4) throw std::invalid_argument("pepshost_fermion_exact_sum_partial_prm: model 0 / 1, at least four parameters");
+  if ((model != 0 && model != 1 && model != 3) || !prm || n_prm < (model == 3 ? 3 : 4))
+    throw std::invalid_argument("pepshost_fermion_exact_sum_partial_prm: model 0 / 1 with at least four parameters, or 3 (hubbard) with three");
   SplitIndexTPST<TenElemT> sitps = make_state_t<TenElemT>(rows, cols, D, 4 * d, sitps_ext_flat);
   FermionDecoration dec;
   dec.nf.assign(nf, nf + d);
@@ -474,6 +478,9 @@ void fermion_exact_sum_partial_prm_impl(int rows, int cols, int D, int d, const 
   auto capture = [&](std::vector<double> &v) { packed = v; };
   if (model == 0) {
     SquareSpinlessFermion m(prm[0], prm[2], prm[1]);
+    ExactSumEnergyEvaluator(sitps, all, contractor, m, rank, size, (size_t)batch, capture, &dec);
+  } else if (model == 3) {
+    SquareHubbardModel m(prm[0], prm[1], prm[2]);
     ExactSumEnergyEvaluator(sitps, all, contractor, m, rank, size, (size_t)batch, capture, &dec);
   } else {
     SquaretJVModel m(prm[0], n_prm > 4 ? prm[4] : 0.0, prm[1], prm[2], prm[3]);
@@ -494,9 +501,11 @@ void fermion_mc_sweeps_impl(int rows, int cols, int D, int d, const int32_t *nf,
   std::vector<uint64_t> sd(seeds, seeds + n);
   MCUpdateSquareNNExchangeOBC ex(sd);
   MCUpdateSquareTNN3SiteExchange t3(sd);
+  MCUpdateSquareNNHubbardU1U1OBC hub(sd);
   std::vector<double> rates, acc(n, 0.0);
   for (int s = 0; s < n_sweeps; ++s) {
     if (updater == 2) t3(sitps, comp, rates);
+    else if (updater == 3) hub(sitps, comp, rates);
     else ex(sitps, comp, rates);
     for (int w = 0; w < n; ++w) acc[w] += rates[w];
   }
@@ -537,16 +546,18 @@ void fermion_measure_energy_impl(int rows, int cols, int D, int d, const int32_t
   if (accept_out) for (int w = 0; w < n; ++w) accept_out[w] = acc[w] / total;
 }
 // ---- the measurement solvers of the fermionic models.  model 0: SquareSpinlessFermion [t, V, t2]; 1: SquaretJVModel [t, J, V, mu, t2];
-// 2: SquaretJNNModel [t, J, mu] (the nearest-neighbour form: no diagonal-bond keys).  Output in the format of pepshost_measure: keys
+// 2: SquaretJNNModel [t, J, mu] (the nearest-neighbour form: no diagonal-bond keys); 3: SquareHubbardModel [t, U, mu] (with
+// double_occupancy).  Output in the format of pepshost_measure: keys
 // "key:len;", every number of a complex state as a (re, im) pair. ----
 template <typename Fn>
 auto with_fermion_measurement_model(const char *who, int model, const double *prm, int n_prm, Fn &&fn) {
-  if (model < 0 || model > 2 || n_prm < 0 || n_prm > 5 || (n_prm > 0 && !prm))
-    throw std::invalid_argument(std::string(who) + ": model 0 (spinless), 1 (tj) or 2 (tjnn), at most 5 parameters");
+  if (model < 0 || model > 3 || n_prm < 0 || n_prm > 5 || (n_prm > 0 && !prm))
+    throw std::invalid_argument(std::string(who) + ": model 0 (spinless), 1 (tj), 2 (tjnn) or 3 (hubbard), at most 5 parameters");
   double p[5] = {0, 0, 0, 0, 0};
   std::copy(prm, prm + n_prm, p);
   if (model == 0) { SquareSpinlessFermion m(p[0], p[2], p[1]); return fn(m); }
   if (model == 1) { SquaretJVModel m(p[0], p[4], p[1], p[2], p[3]); return fn(m); }
+  if (model == 3) { SquareHubbardModel m(p[0], p[1], p[2]); return fn(m); }      // [t, U, mu]
   SquaretJNNModel m(p[0], p[1], p[2]);
   return fn(m);
 }
@@ -614,9 +625,10 @@ void fermion_exact_sum_measure_partial_impl(int rows, int cols, int D, int d, co
 template <typename TenElemT>
 void fermion_measure_impl(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype, const double *sitps_ext_flat, int n,
                           int32_t *configs, const uint64_t *seeds, int warmup_sweeps, int n_samples, int sweeps_between, int model, int n_prm,
-                          const double *prm, KeyedValues &out, double *energy_samples_out, double *accept_out) {
+                          const double *prm, KeyedValues &out, double *energy_samples_out, double *accept_out, int updater = 0) {
   if (n_samples < 1 || warmup_sweeps < 0 || sweeps_between < 0 || !seeds || !configs)
     throw std::invalid_argument("pepshost_fermion_measure: seeds, configurations and n_samples >= 1 are required");
+  if (updater != 0 && updater != 3) throw std::invalid_argument("pepshost_fermion_measure: updater must be 0 (exchange) or 3 (hubbard_u1u1)");
   SplitIndexTPST<TenElemT> sitps = make_state_t<TenElemT>(rows, cols, D, 4 * d, sitps_ext_flat);
   FermionDecoration dec;
   dec.nf.assign(nf, nf + d);
@@ -624,12 +636,12 @@ void fermion_measure_impl(int rows, int cols, int D, int d, const int32_t *nf, i
   TPSWaveFunctionComponentT<TenElemT> comp(sitps, make_cfg(n, rows, cols, configs), contractor, &dec);
   std::vector<uint64_t> sd(seeds, seeds + n);
   MCUpdateSquareNNExchangeOBC ex(sd);
+  MCUpdateSquareNNHubbardU1U1OBC hub(sd);
   MCMeasurementParams mp;
   mp.num_samples = n_samples; mp.num_warmup_sweeps = warmup_sweeps; mp.sweeps_between_samples = sweeps_between;
   mp.normalize_state = false;
   constexpr int z = ElemTraits<TenElemT>::is_complex ? 2 : 1;
-  with_fermion_measurement_model("pepshost_fermion_measure", model, prm, n_prm, [&](auto &m) {
-    MCPEPSMeasurer<MCUpdateSquareNNExchangeOBC, std::decay_t<decltype(m)>, TenElemT> meas(sitps, comp, mp, ex, m);
+  auto report = [&](auto &meas) {
     meas.Execute();
     for (const auto &kv : meas.ObservableRegistry()) {
       out.keys += kv.first + ":" + std::to_string(kv.second.first.size()) + ";";
@@ -641,6 +653,15 @@ void fermion_measure_impl(int rows, int cols, int D, int d, const int32_t *nf, i
     if (energy_samples_out)
       for (size_t k = 0; k < meas.EnergySamples().size(); ++k) copy_out(meas.EnergySamples()[k], energy_samples_out + k * (size_t)n * z);
     if (accept_out) std::copy(meas.AcceptRates().begin(), meas.AcceptRates().end(), accept_out);
+  };
+  with_fermion_measurement_model("pepshost_fermion_measure", model, prm, n_prm, [&](auto &m) {
+    if (updater == 3) {
+      MCPEPSMeasurer<MCUpdateSquareNNHubbardU1U1OBC, std::decay_t<decltype(m)>, TenElemT> meas(sitps, comp, mp, hub, m);
+      report(meas);
+    } else {
+      MCPEPSMeasurer<MCUpdateSquareNNExchangeOBC, std::decay_t<decltype(m)>, TenElemT> meas(sitps, comp, mp, ex, m);
+      report(meas);
+    }
     return 0;
   });
   std::copy(comp.config.data(), comp.config.data() + (size_t)n * rows * cols, configs);
@@ -651,9 +672,10 @@ void fermion_measure_impl(int rows, int cols, int D, int d, const int32_t *nf, i
 // state_out: the d stored components (variant 0), [rows][cols][d][D^4]. ----
 template <typename TenElemT, typename Fn>
 auto with_fermion_model(int model, const double *prm, int n_prm, Fn &&fn) {
-  if (model != 0 && model != 1) throw std::invalid_argument("fermionic optimizer: model must be 0 (spinless) or 1 (tj)");
-  if (!prm || n_prm < 4) throw std::invalid_argument("fermionic optimizer: at least four model parameters");
+  if (model != 0 && model != 1 && model != 3) throw std::invalid_argument("fermionic optimizer: model must be 0 (spinless), 1 (tj) or 3 (hubbard)");
+  if (!prm || n_prm < (model == 3 ? 3 : 4)) throw std::invalid_argument("fermionic optimizer: at least four model parameters (hubbard: three)");
   if (model == 0) { SquareSpinlessFermion m(prm[0], prm[2], prm[1]); return fn(m); }
+  if (model == 3) { SquareHubbardModel m(prm[0], prm[1], prm[2]); return fn(m); }
   SquaretJVModel m(prm[0], n_prm > 4 ? prm[4] : 0.0, prm[1], prm[2], prm[3]);
   return fn(m);
 }
@@ -1297,14 +1319,20 @@ int pepshost_fermion_mc_sweeps_c128(int rows, int cols, int D, int d, const int3
   });
 }
 
-// The same with the updater named: 0 = MCUpdateSquareNNExchangeOBC (as pepshost_fermion_mc_sweeps), 2 = MCUpdateSquareTNN3SiteExchange
+// The same with the updater named: 0 = MCUpdateSquareNNExchangeOBC (as pepshost_fermion_mc_sweeps), 2 = MCUpdateSquareTNN3SiteExchange,
+// 3 = MCUpdateSquareNNHubbardU1U1OBC; dtype PEPSGPU_C128 runs the complex instantiation (interleaved pairs)
 int pepshost_fermion_mc_sweeps_updater(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype,
                                        const double *sitps_ext_flat, int n, int32_t *configs, const uint64_t *seeds, int updater,
                                        int n_sweeps, double *amplitudes_out, double *accept_out) {
   return guarded([&]() {
-    if (updater != 0 && updater != 2) throw std::invalid_argument("pepshost_fermion_mc_sweeps_updater: updater must be 0 (exchange) or 2 (tnn3)");
-    fermion_mc_sweeps_impl<double>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, n, configs, seeds, n_sweeps, amplitudes_out, accept_out,
-                                   updater);
+    if (updater != 0 && updater != 2 && updater != 3)
+      throw std::invalid_argument("pepshost_fermion_mc_sweeps_updater: updater must be 0 (exchange), 2 (tnn3) or 3 (hubbard_u1u1)");
+    if (dtype == PEPSGPU_C128)
+      fermion_mc_sweeps_impl<QLTEN_Complex>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, n, configs, seeds, n_sweeps, amplitudes_out,
+                                            accept_out, updater);
+    else
+      fermion_mc_sweeps_impl<double>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, n, configs, seeds, n_sweeps, amplitudes_out, accept_out,
+                                     updater);
   });
 }
 
@@ -1352,12 +1380,14 @@ int pepshost_fermion_measure_energy_c128(int rows, int cols, int D, int d, const
 }
 
 // The two calls above with a parameter count, every element type in one entry (dtype PEPSGPU_C128: the complex instantiation, interleaved
-// pairs): model 0 params [t, V, t2], model 1 [t, J, V, mu, t2] -- the t-t'-J model; a shorter list leaves the missing parameters 0.
+// pairs): model 0 params [t, V, t2], model 1 [t, J, V, mu, t2] -- the t-t'-J model --, model 3 [t, U, mu] -- the Hubbard model (energy
+// entry only); a shorter list leaves the missing parameters 0.
 int pepshost_fermion_energy_prm(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype, const double *sitps_ext_flat,
                                 int n, const int32_t *configs, int model, int n_prm, const double *prm, double *amplitudes_out,
                                 double *energies_out, double *psi_out, int *n_psi_out) {
   return guarded([&]() {
-    if (n_prm < 0 || n_prm > 5 || (model != 0 && model != 1)) throw std::invalid_argument("pepshost_fermion_energy_prm: model 0 / 1, at most 5 parameters");
+    if (n_prm < 0 || n_prm > 5 || (model != 0 && model != 1 && model != 3))
+      throw std::invalid_argument("pepshost_fermion_energy_prm: model 0 / 1 / 3 (hubbard: [t, U, mu]), at most 5 parameters");
     double p[5] = {0, 0, 0, 0, 0};
     std::copy(prm, prm + n_prm, p);
     if (dtype == PEPSGPU_C128)
@@ -1430,6 +1460,39 @@ int pepshost_fermion_measure(int rows, int cols, int D, int d, const int32_t *nf
       fermion_measure_impl<double>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, n, configs, seeds, warmup_sweeps, n_samples, sweeps_between,
                                    model, n_prm, prm, out, energy_samples_out, accept_out);
     out.write("pepshost_fermion_measure", keys_out, keys_cap, values_out, values_cap, values_len);
+  });
+}
+
+// The same with the updater named: 0 = MCUpdateSquareNNExchangeOBC (pepshost_fermion_measure), 3 = MCUpdateSquareNNHubbardU1U1OBC
+int pepshost_fermion_measure_updater(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype, const double *sitps_ext_flat,
+                                     int n, int32_t *configs, const uint64_t *seeds, int updater, int warmup_sweeps, int n_samples,
+                                     int sweeps_between, int model, int n_prm, const double *prm, char *keys_out, int keys_cap,
+                                     double *values_out, long values_cap, long *values_len, double *energy_samples_out, double *accept_out) {
+  return guarded([&]() {
+    KeyedValues out;
+    if (dtype == PEPSGPU_C128)
+      fermion_measure_impl<QLTEN_Complex>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, n, configs, seeds, warmup_sweeps, n_samples,
+                                          sweeps_between, model, n_prm, prm, out, energy_samples_out, accept_out, updater);
+    else
+      fermion_measure_impl<double>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, n, configs, seeds, warmup_sweeps, n_samples, sweeps_between,
+                                   model, n_prm, prm, out, energy_samples_out, accept_out, updater);
+    out.write("pepshost_fermion_measure_updater", keys_out, keys_cap, values_out, values_cap, values_len);
+  });
+}
+// The sector table of MCUpdateSquareNNHubbardU1U1OBC (pepsgpu_sweep_slice_sector), out [16][10]; host only
+int pepshost_hubbard_sector_table(int32_t *out) {
+  return guarded([&]() {
+    if (!out) throw std::invalid_argument("pepshost_hubbard_sector_table: null output buffer");
+    const std::vector<int32_t> tab = HubbardSectorTable();
+    std::copy(tab.begin(), tab.end(), out);
+  });
+}
+// The hop table of SquareHubbardModel (pepsgpu_nn_hop_slice_fermion), out [16][2][2]; host only
+int pepshost_hubbard_hop_table(int32_t *out) {
+  return guarded([&]() {
+    if (!out) throw std::invalid_argument("pepshost_hubbard_hop_table: null output buffer");
+    const std::vector<int32_t> tab = SquareHubbardModel::HopTable();
+    std::copy(tab.begin(), tab.end(), out);
   });
 }
 

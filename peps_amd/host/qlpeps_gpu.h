@@ -1198,6 +1198,13 @@ template <typename U> struct HasExchangeBondEnergy<U, std::void_t<decltype(U::kE
 template <typename U, typename = void> struct HasExchangeBondPsiPerBond : std::false_type {};
 template <typename U> struct HasExchangeBondPsiPerBond<U, std::void_t<decltype(U::kExchangeBondPsiPerBond)>> : std::bool_constant<U::kExchangeBondPsiPerBond> {};
 
+// A fermionic model whose bond term is up to two hops (the Hubbard model) opts into the device-side slice with `static constexpr bool
+// kHopBondEnergy = true`, HopTable() (the hop_table of pepsgpu_nn_hop_slice_fermion over its physical states) and the scalar hook
+// TenElemT BondEnergyFromHops(config1, config2, r_up, r_dn), r = ComplexConjugate(psi'_k / psi) of the two candidate slots (0 where the
+// bond has no such hop; psi'_k with Sigma(S') / Sigma(S) applied, as the slice returns it): one pepsgpu_nn_hop_slice_fermion per row and per column, the holes with the row slice when they are resident.
+template <typename U, typename = void> struct HasHopBondEnergy : std::false_type {};
+template <typename U> struct HasHopBondEnergy<U, std::void_t<decltype(U::kHopBondEnergy)>> : std::bool_constant<U::kHopBondEnergy> {};
+
 // `kExchangeNNNEnergy = true` + the scalar hook NNNEnergyFromExchange(config1, config2, ratio), the twin of BondEnergyFromExchange
 // for a diagonal link: the diagonal bonds of a row pair come from ONE pepsgpu_nnn_exchange_slice call.  `kNNNDiagMask` (optional, bit 0
 // LEFTUP_TO_RIGHTDOWN, bit 1 LEFTDOWN_TO_RIGHTUP; default both) names the diagonals that interact: the others contribute exactly 0.
@@ -1358,6 +1365,167 @@ class MCUpdateSquareNNFullSpaceUpdateOBC : public MCUpdateSquareNNUpdateBaseOBC<
   }
 };
 
+// While alive, the per-bond Trace / ReplaceNNSiteTrace of the contractor scale their results in a kernel, as the device-side slices do
+// (pepsgpu_trace_scaling): a hook path inside this scope returns the bits of the slice that replaces it.
+template <typename TenElemT>
+struct DeviceTraceScaling {
+  pepsgpu_ctx *ctx;
+  explicit DeviceTraceScaling(const BMPSContractorT<TenElemT> &c) : ctx(c.ctx()) { check_rc(pepsgpu_trace_scaling(ctx, 1), ctx); }
+  ~DeviceTraceScaling() { (void)pepsgpu_trace_scaling(ctx, 0); }
+  DeviceTraceScaling(const DeviceTraceScaling &) = delete;
+  DeviceTraceScaling &operator=(const DeviceTraceScaling &) = delete;
+};
+
+// The single-site states of the Hubbard model (square_hubbard_model.h:18-45) and the two-site sectors of its U(1) x U(1) updater
+// (square_hubbard_u1u1_updater.h:30-72)
+enum class HubbardSingleSiteState { DoubleOccupancy, SpinUp, SpinDown, Empty };   // 0, 1, 2, 3
+inline double HubbardConfig2Density(size_t config) {
+  switch (HubbardSingleSiteState(config)) {
+    case HubbardSingleSiteState::DoubleOccupancy: return 2;
+    case HubbardSingleSiteState::SpinUp: return 1;
+    case HubbardSingleSiteState::SpinDown: return 1;
+    case HubbardSingleSiteState::Empty: return 0;
+  }
+  return -1;
+}
+inline double HubbardConfig2Spinz(size_t config) {
+  switch (HubbardSingleSiteState(config)) {
+    case HubbardSingleSiteState::SpinUp: return 0.5;
+    case HubbardSingleSiteState::SpinDown: return -0.5;
+    case HubbardSingleSiteState::DoubleOccupancy: case HubbardSingleSiteState::Empty: return 0;
+  }
+  return -1;
+}
+inline std::pair<size_t, size_t> HubbardConfig2SpinCounts(size_t config) {      // (N_up, N_down)
+  switch (HubbardSingleSiteState(config)) {
+    case HubbardSingleSiteState::DoubleOccupancy: return {1, 1};
+    case HubbardSingleSiteState::SpinUp: return {1, 0};
+    case HubbardSingleSiteState::SpinDown: return {0, 1};
+    case HubbardSingleSiteState::Empty: return {0, 0};
+  }
+  throw std::invalid_argument("Invalid Hubbard configuration: " + std::to_string(config));
+}
+inline std::vector<std::pair<size_t, size_t>> EnumerateHubbardTwoSiteConfigsWithU1U1(size_t n_up_total, size_t n_down_total) {
+  std::vector<std::pair<size_t, size_t>> result;
+  for (size_t c1 = 0; c1 < 4; ++c1)
+    for (size_t c2 = 0; c2 < 4; ++c2) {
+      const auto n1 = HubbardConfig2SpinCounts(c1), n2 = HubbardConfig2SpinCounts(c2);
+      if (n1.first + n2.first == n_up_total && n1.second + n2.second == n_down_total) result.emplace_back(c1, c2);
+    }
+  return result;
+}
+// The sector table of pepsgpu_sweep_slice_sector for the updater below, [16][2 + 2 * 4] over physical states: row a * 4 + b = {m, init,
+// four slots (a', b')}: the sector of (a, b) in the enumeration order, init the slot of (a, b) itself, unused slots (-1, -1)
+constexpr int kHubbardSlots = 4, kHubbardSectorRow = 2 + 2 * kHubbardSlots;
+inline std::vector<int32_t> HubbardSectorTable() {
+  std::vector<int32_t> tab(16 * kHubbardSectorRow, -1);
+  for (size_t a = 0; a < 4; ++a)
+    for (size_t b = 0; b < 4; ++b) {
+      const auto na = HubbardConfig2SpinCounts(a), nb = HubbardConfig2SpinCounts(b);
+      const auto valid = EnumerateHubbardTwoSiteConfigsWithU1U1(na.first + nb.first, na.second + nb.second);
+      int32_t *row = tab.data() + (a * 4 + b) * kHubbardSectorRow;
+      row[0] = (int32_t)valid.size();
+      for (size_t k = 0; k < valid.size(); ++k) {
+        row[2 + 2 * k] = (int32_t)valid[k].first;
+        row[3 + 2 * k] = (int32_t)valid[k].second;
+        if (valid[k].first == a && valid[k].second == b) row[1] = (int32_t)k;
+      }
+    }
+  return tab;
+}
+
+// square_hubbard_u1u1_updater.h:90-158: per bond a Suwa-Todo choice among the pairs with the (N_up, N_down) of the bond
+class MCUpdateSquareNNHubbardU1U1OBC : public MCUpdateSquareNNUpdateBaseOBC<MCUpdateSquareNNHubbardU1U1OBC> {
+ public:
+  using MCUpdateSquareNNUpdateBaseOBC<MCUpdateSquareNNHubbardU1U1OBC>::MCUpdateSquareNNUpdateBaseOBC;
+  static constexpr bool kDeviceSliceSweep = true;
+  static constexpr bool kDeviceSliceSweepFermions = true;   // (a move inside the sector keeps the fermion parity of the pair: local in the extended states)
+  // one row / column on the device (pepsgpu_sweep_slice_sector): walker w consumes the next consumed[w] words of its engine, exactly
+  // those TwoSiteNNUpdateLocalImpl would draw (two per bond whose sector has more than one state).  The slice returns decorated
+  // amplitudes (the weights see moduli only); a walker that moved gets its signs back from its new configuration.
+  template <typename TenElemT>
+  void SweepSliceOnDevice(BondOrientation dir, size_t slice, const SplitIndexTPST<TenElemT> &, TPSWaveFunctionComponentT<TenElemT> &comp,
+                          std::vector<size_t> &acc) {
+    auto &c = comp.contractor;
+    RequireHubbardStates(comp);
+    const size_t n = comp.config.walkers(), N = dir == HORIZONTAL ? c.cols() : c.rows(), nwd = 2 * (N - 1);
+    const std::vector<uint32_t> words = words_.PeekAll(engines_, nwd);
+    std::vector<int32_t> consumed(n), accepted(n), states(n * N), occ;
+    if (comp.fermion)
+      for (int32_t s = 0; s < 4; ++s) occ.push_back(comp.fermion->n(s));
+    std::vector<TenElemT> amp = comp.amplitude;
+    check_rc(pepsgpu_sweep_slice_sector(c.ctx(), dir, (int)slice, 4, comp.fermion ? occ.data() : nullptr, kHubbardSlots, Table().data(), (int)nwd,
+                                        words.data(), dptr(amp.data()), consumed.data(), accepted.data(), states.data()), c.ctx());
+    StoreSlice(comp, dir, slice, states, accepted, acc);
+    for (size_t w = 0; w < n; ++w) {
+      words_.Consume(w, (size_t)consumed[w]);
+      if (!comp.fermion) comp.amplitude[w] = amp[w];
+      else if (accepted[w] > 0) comp.amplitude[w] = amp[w] * GradedSign(comp, w);
+    }
+  }
+  // :95-157 batched over the walkers: ONE ReplaceNNSiteTrace over four fixed candidate slots, padded with the walker's own pair, so
+  // that both paths hand the replacement trace the same operands; no trace and no draw when every walker's sector has one state
+  template <typename TenElemT>
+  std::vector<uint8_t> TwoSiteNNUpdateLocalImpl(const SiteIdx &s1, const SiteIdx &s2, BondOrientation dir,
+                                                const SplitIndexTPST<TenElemT> &, TPSWaveFunctionComponentT<TenElemT> &comp) {
+    RequireHubbardStates(comp);
+    const size_t n = comp.config.walkers();
+    const std::vector<int32_t> &tab = Table();
+    std::vector<int32_t> cand(n * kHubbardSlots * 2), meta(n * 2);
+    bool any = false;
+    for (size_t w = 0; w < n; ++w) {
+      const int32_t a = comp.config(w, s1), b = comp.config(w, s2);
+      const int32_t *row = tab.data() + (size_t)(a * 4 + b) * kHubbardSectorRow;
+      for (int k = 0; k < kHubbardSlots; ++k) {
+        cand[(w * kHubbardSlots + k) * 2] = k < row[0] ? row[2 + 2 * k] : a;
+        cand[(w * kHubbardSlots + k) * 2 + 1] = k < row[0] ? row[3 + 2 * k] : b;
+      }
+      meta[2 * w] = row[0];
+      meta[2 * w + 1] = row[1];
+      any |= row[0] > 1;
+    }
+    std::vector<uint8_t> changed(n, 0);
+    if (!any) return changed;                 // every walker's sector has one state (:114-116)
+    const DeviceTraceScaling<TenElemT> scaling(comp.contractor);      // (the amplitudes of the slice, bit for bit)
+    const std::vector<TenElemT> alt = comp.ReplaceNNSiteTrace(s1, s2, dir, kHubbardSlots, cand);
+    std::vector<int32_t> ns(n * 2);
+    std::vector<TenElemT> new_amp(n);
+    for (size_t w = 0; w < n; ++w) {
+      const int m = meta[2 * w], init = meta[2 * w + 1];
+      if (m <= 1) continue;
+      // |psi_k / psi|^2 as the kernel forms it (the ratio of the moduli, squared); the current state keeps its stored amplitude (:129)
+      const double pa = std::abs(comp.amplitude[w]);
+      std::vector<double> weights(m);
+      for (int k = 0; k < m; ++k) {
+        const double r = k == init ? 1.0 : std::abs(alt[w * kHubbardSlots + k]) / pa;
+        weights[k] = r * r;
+      }
+      QueuedEngine eng = Engine(w);
+      const int fin = (int)SuwaTodoStateUpdate((size_t)init, weights, eng);
+      if (fin == init) continue;
+      changed[w] = 1;
+      ns[2 * w] = cand[(w * kHubbardSlots + fin) * 2];
+      ns[2 * w + 1] = cand[(w * kHubbardSlots + fin) * 2 + 1];
+      new_amp[w] = alt[w * kHubbardSlots + fin];
+    }
+    comp.UpdateLocal(new_amp, {s1, s2}, ns, changed);
+    return changed;
+  }
+
+ private:
+  template <typename TenElemT>
+  static void RequireHubbardStates(const TPSWaveFunctionComponentT<TenElemT> &comp) {
+    const size_t d = comp.fermion ? comp.fermion->d() : comp.contractor.phys_dim();
+    if (d != 4) throw std::invalid_argument("MCUpdateSquareNNHubbardU1U1OBC: the state needs the four Hubbard states per site");
+  }
+  const std::vector<int32_t> &Table() {
+    if (tab_.empty()) tab_ = HubbardSectorTable();
+    return tab_;
+  }
+  std::vector<int32_t> tab_;
+};
+using MCUpdateSquareNNHubbardU1U1 = MCUpdateSquareNNHubbardU1U1OBC;   // the reference's backward-compatible alias
+
 // square_3site_updater.h:22-93: sweep schedule of the three-site updaters, CRTP hook TNN3SiteUpdateImpl(site1, site2, site3, dir, sitps,
 // comp) -> changed[w].  Every row (column) starts from the ReplaceTNNSiteTrace of its first window as the amplitude (:39-42, :64-67).
 template <typename MCUpdater>
@@ -1509,8 +1677,30 @@ class SquareNNNModelEnergySolver {
     bool dev_slice = false;
     if constexpr (HasExchangeBondEnergy<ExplicitlyModel>::value)
       dev_slice = DeviceSlicesEnabled() && (!comp.fermion || per_bond) && (!calchols || holes_on_device);
+    if constexpr (HasHopBondEnergy<ExplicitlyModel>::value)
+      dev_slice = DeviceSlicesEnabled() && comp.fermion && (!calchols || holes_on_device);
     auto slice_energy = [&](BondOrientation dir, size_t slice, bool holes) {
-      if constexpr (HasExchangeBondEnergy<ExplicitlyModel>::value) {
+      if constexpr (HasHopBondEnergy<ExplicitlyModel>::value) {
+        const size_t N = dir == HORIZONTAL ? cols : rows, np = N - 1;
+        std::vector<TenElemT> psi(n * np), hop(n * np * 2), psi0(n);
+        const std::vector<int32_t> tab = self->HopTable();
+        std::vector<int32_t> occ(comp.fermion->d());
+        for (size_t s = 0; s < occ.size(); ++s) occ[s] = comp.fermion->n((int32_t)s);
+        check_rc(pepsgpu_nn_hop_slice_fermion(c.ctx(), dir, (int)slice, holes ? 1 : 0, (int)occ.size(), occ.data(), tab.data(), dptr(psi.data()),
+                                              dptr(hop.data())), c.ctx());
+        for (size_t w = 0; w < n; ++w) {
+          psi0[w] = psi[w * np];                              // (the first bond's window is the slice's first window)
+          for (size_t j = 0; j < np; ++j) {
+            const SiteIdx s1 = dir == HORIZONTAL ? SiteIdx{slice, j} : SiteIdx{j, slice};
+            const SiteIdx s2 = dir == HORIZONTAL ? SiteIdx{slice, j + 1} : SiteIdx{j + 1, slice};
+            const size_t k = w * np + j;
+            if (psi[k] == TenElemT(0.0)) throw std::runtime_error("Wavefunction amplitude is near zero, causing division by zero.");
+            out.energy[w] += self->BondEnergyFromHops(comp.config(w, s1), comp.config(w, s2), ComplexConjugate(TenElemT(hop[2 * k] / psi[k])),
+                                                      ComplexConjugate(TenElemT(hop[2 * k + 1] / psi[k])));
+          }
+        }
+        out.psi_list.push_back(psi0);
+      } else if constexpr (HasExchangeBondEnergy<ExplicitlyModel>::value) {
         const size_t N = dir == HORIZONTAL ? cols : rows;
         std::vector<TenElemT> psi(per_bond ? n * (N - 1) : n), ex(n * (N - 1)), psi0(n);
         const std::vector<int32_t> tab = comp.fermion ? comp.ExchangeTable() : std::vector<int32_t>();
@@ -1784,11 +1974,30 @@ class SquareNNNModelMeasurementSolver {
     };
     bool use_slice = false;
     if constexpr (HasExchangeBondEnergy<ModelType>::value && HasExchangeBondPsiPerBond<ModelType>::value) use_slice = DeviceSlicesEnabled();
+    if constexpr (HasHopBondEnergy<ModelType>::value) use_slice = DeviceSlicesEnabled();
     std::vector<int32_t> occ(fd.d()), ptab(4 * fd.d() * fd.d(), -1);
     for (size_t s = 0; s < occ.size(); ++s) occ[s] = fd.n((int32_t)s);
     if constexpr (sc) ptab = derived->PairTable();
     auto slice_pass = [&](BondOrientation dir, size_t slice) {
-      if constexpr (HasExchangeBondEnergy<ModelType>::value) {
+      if constexpr (HasHopBondEnergy<ModelType>::value) {          // (ONE pepsgpu_nn_hop_slice_fermion: psi and the two hops of every bond)
+        const size_t N = dir == HORIZONTAL ? lx : ly, np = N - 1;
+        std::vector<TenElemT> psi(n * np), hop(n * np * 2), psi0(n);
+        const std::vector<int32_t> htab = derived->HopTable();
+        check_rc(pepsgpu_nn_hop_slice_fermion(c.ctx(), dir, (int)slice, 0, (int)fd.d(), occ.data(), htab.data(), dptr(psi.data()),
+                                              dptr(hop.data())), c.ctx());
+        for (size_t w = 0; w < n; ++w) {
+          for (size_t j = 0; j < np; ++j) {
+            const SiteIdx s1 = dir == HORIZONTAL ? SiteIdx{slice, j} : SiteIdx{j, slice};
+            const SiteIdx s2 = dir == HORIZONTAL ? SiteIdx{slice, j + 1} : SiteIdx{j + 1, slice};
+            const size_t k = w * np + j;
+            nonzero(psi[k]);
+            put(dir, slice, j, w, derived->BondEnergyFromHops(comp.config(w, s1), comp.config(w, s2), ComplexConjugate(TenElemT(hop[2 * k] / psi[k])),
+                                                              ComplexConjugate(TenElemT(hop[2 * k + 1] / psi[k]))), TenElemT(0.0));
+          }
+          psi0[w] = np ? psi[w * np] : TenElemT(1.0);
+        }
+        psi_list.push_back(psi0);
+      } else if constexpr (HasExchangeBondEnergy<ModelType>::value) {
         const size_t N = dir == HORIZONTAL ? lx : ly, np = N - 1;
         std::vector<TenElemT> psi(n * np), ex(n * np), pair(n * np * 2), psi0(n);
         const std::vector<int32_t> xtab = comp.ExchangeTable();
@@ -2968,6 +3177,108 @@ class SquaretJNNModel : public SquaretJVModel, public SquareNNModelMeasurementSo
 class SquaretJNNNModel : public SquaretJVModel {
  public:
   SquaretJNNNModel(double t, double t2, double J, double mu) : SquaretJVModel(t, t2, J, 0.0, mu) {}
+};
+
+// square_hubbard_model.h:76-263: H = -t sum_<ij>,s (c+_is c_js + h.c.) + U sum_i n_iup n_idown - mu sum_is n_is; states 0 up-down, 1 up,
+// 2 down, 3 empty (:18-23), fermion parities [0, 1, 1, 0].  EvaluateBondEnergy (:190-262) in one rule: site 1 is the earlier site of the
+// bond in the mode order of the pass (left / upper), a bond contributes -t sum_sigma s_sigma ComplexConjugate(psi'_sigma / psi) with
+// psi'_sigma the amplitude with the sigma electron hopped across the bond (at most one per sigma) and s_up = (-1)^(n_down of site 1),
+// s_down = (-1)^(n_up of site 2): the occupation of the one mode the hop passes in the order (1 up, 1 down, 2 up, 2 down).  The six
+// branches of the reference are this table; tests/test_cpu_hubbard.py pins it to a dense Jordan-Wigner Hamiltonian.
+class SquareHubbardModel : public SquareNNModelEnergySolver<SquareHubbardModel>, public SquareNNModelMeasurementSolver<SquareHubbardModel> {
+ public:
+  static constexpr bool kFermionicModel = true;
+  static constexpr bool requires_density_measurement = true;   // :80-81
+  static constexpr bool requires_spin_sz_measurement = true;
+  static constexpr bool kHopBondEnergy = true;
+  SquareHubbardModel(double t, double U, double mu) : t_(t), U_(U), mu_(mu) {}
+  double CalDensityImpl(int32_t config) const { return HubbardConfig2Density((size_t)config); }   // :119-121
+  double CalSpinSzImpl(int32_t config) const { return HubbardConfig2Spinz((size_t)config); }      // :123-125
+  // slot 0: the up electron hopped, slot 1: the down electron hopped; [16][2][2] over physical states, (-1, -1) for none
+  static std::vector<int32_t> HopTable() {
+    std::vector<int32_t> tab(16 * 4, -1);
+    static const int32_t state_of[2][2] = {{3, 2}, {1, 0}};          // [n_up][n_down]
+    for (size_t a = 0; a < 4; ++a)
+      for (size_t b = 0; b < 4; ++b) {
+        const auto na = HubbardConfig2SpinCounts(a), nb = HubbardConfig2SpinCounts(b);
+        int32_t *row = tab.data() + (a * 4 + b) * 4;
+        if (na.first != nb.first) { row[0] = state_of[nb.first][na.second]; row[1] = state_of[na.first][nb.second]; }
+        if (na.second != nb.second) { row[2] = state_of[na.first][nb.second]; row[3] = state_of[nb.first][na.second]; }
+      }
+    return tab;
+  }
+  // the bond energy of one walker from r_k = ComplexConjugate(psi'_k / psi) of the two slots of HopTable (a slot without a hop adds nothing)
+  template <typename TenElemT>
+  TenElemT BondEnergyFromHops(int32_t c1, int32_t c2, TenElemT r_up, TenElemT r_dn) const {
+    const auto n1 = HubbardConfig2SpinCounts((size_t)c1), n2 = HubbardConfig2SpinCounts((size_t)c2);
+    TenElemT e(0.0);
+    if (n1.first != n2.first) e += TenElemT((n1.second ? t_ : -t_) * r_up);        // -t s_up, s_up = (-1)^(n_down of site 1)
+    if (n1.second != n2.second) e += TenElemT((n2.first ? t_ : -t_) * r_dn);       // -t s_down, s_down = (-1)^(n_up of site 2)
+    return e;
+  }
+  // :190-262 batched over the walkers: Trace + ONE ReplaceNNSiteTrace over the two candidate slots (a walker without candidate k keeps
+  // its own pair there); nothing for a bond on which every walker has equal states (:200-202)
+  template <typename TenElemT>
+  std::vector<TenElemT> EvaluateBondEnergy(const SiteIdx &s1, const SiteIdx &s2, BondOrientation orient,
+                                           TPSWaveFunctionComponentT<TenElemT> &comp, const std::vector<TenElemT> &) {
+    const size_t n = comp.config.walkers();
+    const FermionDecoration &fd = *comp.fermion;
+    const std::vector<int32_t> tab = HopTable();
+    std::vector<int32_t> cand(n * 4);
+    std::vector<double> sign(n * 2, 0.0);
+    std::vector<TenElemT> e(n, TenElemT(0.0));
+    bool any = false;
+    for (size_t w = 0; w < n; ++w) {
+      const int32_t c1 = comp.config(w, s1), c2 = comp.config(w, s2);
+      for (int k = 0; k < 2; ++k) {
+        const int32_t pa = tab[(size_t)(c1 * 4 + c2) * 4 + 2 * k], pb = tab[(size_t)(c1 * 4 + c2) * 4 + 2 * k + 1];
+        cand[(w * 2 + k) * 2] = pa < 0 ? c1 : pa;
+        cand[(w * 2 + k) * 2 + 1] = pa < 0 ? c2 : pb;
+        // Sigma(S') / Sigma(S), which the ratio of the decorated contractions misses: -1 where the hop changes the number of odd
+        // sites by +-2, (up-down, empty) <-> (up, down) -- what pepsgpu_nn_hop_slice_fermion applies on the device
+        if (pa >= 0) { sign[w * 2 + k] = fd.n(pa) + fd.n(pb) == fd.n(c1) + fd.n(c2) ? 1.0 : -1.0; any = true; }
+      }
+    }
+    if (!any) return e;
+    // (scaled as pepsgpu_nn_hop_slice_fermion scales them: the bond energies of the hook are those of the slice, bit for bit)
+    const DeviceTraceScaling<TenElemT> scaling(comp.contractor);
+    const std::vector<TenElemT> psi = comp.contractor.Trace(s1, orient);
+    const std::vector<TenElemT> psi_ex = comp.ReplaceNNSiteTrace(s1, s2, orient, 2, cand);
+    for (size_t w = 0; w < n; ++w) {
+      const int32_t c1 = comp.config(w, s1), c2 = comp.config(w, s2);
+      if (c1 == c2) continue;
+      if (psi[w] == TenElemT(0.0)) throw std::runtime_error("Wavefunction amplitude is near zero, causing division by zero.");
+      e[w] = BondEnergyFromHops(c1, c2, ComplexConjugate(TenElemT(sign[2 * w] * psi_ex[2 * w] / psi[w])),
+                                ComplexConjugate(TenElemT(sign[2 * w + 1] * psi_ex[2 * w + 1] / psi[w])));
+    }
+    return e;
+  }
+  double EvaluateTotalOnsiteEnergy(const Configuration &config, size_t w) const {   // :101-117
+    size_t doublons = 0, electrons = 0;
+    for (size_t r = 0; r < config.rows(); ++r)
+      for (size_t c = 0; c < config.cols(); ++c) {
+        doublons += config(w, {r, c}) == 0;
+        electrons += (size_t)HubbardConfig2Density((size_t)config(w, {r, c}));
+      }
+    return U_ * double(doublons) - mu_ * double(electrons);
+  }
+  // the registry of the nearest-neighbour form plus the doublon indicator (:127-171)
+  std::vector<ObservableMeta> DescribeObservables(size_t ly, size_t lx) const {
+    std::vector<ObservableMeta> out = SquareNNModelMeasurementSolver<SquareHubbardModel>::DescribeObservables(ly, lx);
+    out.push_back({"double_occupancy", "On-site double occupancy indicator (Ly,Lx)", {ly, lx}, {"y", "x"}});
+    return out;
+  }
+  template <typename TenElemT>
+  ObservableMapT<TenElemT> EvaluateObservables(const SplitIndexTPST<TenElemT> &sitps, TPSWaveFunctionComponentT<TenElemT> &comp) {
+    ObservableMapT<TenElemT> out = SquareNNModelMeasurementSolver<SquareHubbardModel>::EvaluateObservables(sitps, comp);
+    const size_t ly = comp.contractor.rows(), lx = comp.contractor.cols(), n = comp.config.walkers();
+    auto &dbl = out.make("double_occupancy", ly * lx);
+    for (size_t w = 0; w < n; ++w)
+      for (size_t s = 0; s < ly * lx; ++s) dbl[w * ly * lx + s] = comp.config(w, {s / lx, s % lx}) == 0 ? 1.0 : 0.0;
+    return out;
+  }
+ private:
+  double t_, U_, mu_;
 };
 
 // transverse_field_ising_square_obc.h:28-247

@@ -25,13 +25,16 @@ SYMBOLS = ["pepshost_last_error", "pepshost_mc_sweeps", "pepshost_energy_and_hol
            "pepshost_fermion_optimize_exact_sum", "pepshost_fermion_optimize_exact_sum_c128",
            "pepshost_fermion_sr_step_samples", "pepshost_fermion_sr_step_samples_c128", "pepshost_fermion_exact_sum_partial_prm",
            "pepshost_lbfgs_exact_sum", "pepshost_lbfgs_exact_sum_c128", "pepshost_fermion_lbfgs_exact_sum", "pepshost_fermion_lbfgs_exact_sum_c128",
-           "pepshost_fermion_observables", "pepshost_fermion_exact_sum_measure_partial", "pepshost_fermion_measure"]
+           "pepshost_fermion_observables", "pepshost_fermion_exact_sum_measure_partial", "pepshost_fermion_measure",
+           "pepshost_fermion_measure_updater", "pepshost_hubbard_sector_table", "pepshost_hubbard_hop_table"]
 
 _lib = None
 _C128 = 3                                   # PEPSGPU_C128 (include/pepsgpu.h)
 
 # updater ids of the shim: MCUpdateSquareNNExchangeOBC, MCUpdateSquareNNFullSpaceUpdateOBC, MCUpdateSquareTNN3SiteExchange
 UPDATER_ID = {"exchange": 0, "fullspace": 1, "tnn3": 2}
+# ... of the fermionic entries: MCUpdateSquareNNExchangeOBC, MCUpdateSquareTNN3SiteExchange, MCUpdateSquareNNHubbardU1U1OBC
+FERMION_UPDATER_ID = {"exchange": 0, "tnn3": 2, "hubbard_u1u1": 3}
 
 
 def _updater_id(updater):
@@ -512,10 +515,13 @@ def configuration_from_text(text, rows, cols):
     return out
 
 
-def fermion_energy(state, configs, chi, t, V=0.0, dtype=1, model="spinless", J=0.0, mu=0.0, t2=0.0):
+def fermion_energy(state, configs, chi, t, V=0.0, dtype=1, model="spinless", J=0.0, mu=0.0, t2=0.0, U=0.0):
     """C++ host layer on a fermionic state (peps_amd.fermion.FermionState): amplitudes (row-major mode order),
-    E_loc of the spinless t-V model (model="spinless") or of the t-J-V model (model="tj"), psi along every route.
+    E_loc of the spinless t-V model (model="spinless"), of the t-J-V model (model="tj") or of the Hubbard model (model="hubbard":
+    t, U, mu), psi along every route.
     A complex state (SplitIndexTPS<QLTEN_Complex, fZ2QN>) runs the complex instantiation in float64 (`dtype` ignored)."""
+    if model not in ("spinless", "tj", "hubbard"):
+        raise ValueError("fermion_energy: model must be 'spinless', 'tj' or 'hubbard'")
     cplx = state.is_complex
     et = np.complex128 if cplx else np.float64
     flat = np.ascontiguousarray(state.extended_flat(), dtype=et)
@@ -527,10 +533,10 @@ def fermion_energy(state, configs, chi, t, V=0.0, dtype=1, model="spinless", J=0
     psi = np.zeros((rows + cols, n), et)
     npsi = C.c_int(0)
     prm = np.array([t, V, t2, 0.0] if model == "spinless" else [t, J, V, mu], dtype=np.float64)
-    if model != "spinless" and t2 != 0.0:             # the t-t'-J model: the entry with a parameter count carries t2
-        prm = np.array([t, J, V, mu, t2], dtype=np.float64)
+    if model == "hubbard" or t2 != 0.0 and model != "spinless":      # the Hubbard and the t-t'-J model: the entry with a parameter count
+        prm = np.array([t, U, mu] if model == "hubbard" else [t, J, V, mu, t2], dtype=np.float64)
         _ck(lib().pepshost_fermion_energy_prm(rows, cols, D, state.d, _p(nf, C.c_int32), chi, _C128 if cplx else dtype,
-                                              _cp(flat), n, _p(cfg, C.c_int32), 1, prm.size,
+                                              _cp(flat), n, _p(cfg, C.c_int32), FERMION_MODEL_ID[model], prm.size,
                                               _p(prm, C.c_double), _cp(amps),
                                               _cp(en), _cp(psi),
                                               C.byref(npsi)))
@@ -546,10 +552,10 @@ def fermion_energy(state, configs, chi, t, V=0.0, dtype=1, model="spinless", J=0
 
 
 def fermion_mc_sweeps(state, configs, seeds, chi, n_sweeps=1, dtype=1, updater="exchange"):
-    """n_sweeps sweeps of a fermionic state; updater "exchange" (MCUpdateSquareNNExchangeOBC) or "tnn3"
-    (MCUpdateSquareTNN3SiteExchange, real element types)"""
-    if updater not in ("exchange", "tnn3"):
-        raise ValueError("fermion_mc_sweeps: updater must be 'exchange' or 'tnn3'")
+    """n_sweeps sweeps of a fermionic state; updater "exchange" (MCUpdateSquareNNExchangeOBC), "tnn3"
+    (MCUpdateSquareTNN3SiteExchange, real element types) or "hubbard_u1u1" (MCUpdateSquareNNHubbardU1U1OBC, every element type)"""
+    if updater not in FERMION_UPDATER_ID:
+        raise ValueError("fermion_mc_sweeps: updater must be 'exchange', 'tnn3' or 'hubbard_u1u1'")
     cplx = state.is_complex
     et = np.complex128 if cplx else np.float64
     flat = np.ascontiguousarray(state.extended_flat(), dtype=et)
@@ -559,12 +565,12 @@ def fermion_mc_sweeps(state, configs, seeds, chi, n_sweeps=1, dtype=1, updater="
     nf = np.ascontiguousarray(state.nf, dtype=np.int32)
     sd = np.ascontiguousarray(seeds, dtype=np.uint64)
     amps, rates = np.zeros(n, et), np.zeros(n)
-    if updater == "tnn3":
-        if cplx:
+    if updater != "exchange":
+        if cplx and updater == "tnn3":
             raise ValueError("fermion_mc_sweeps: the three-site updater takes real fermionic states")
-        _ck(lib().pepshost_fermion_mc_sweeps_updater(rows, cols, D, state.d, _p(nf, C.c_int32), chi, dtype, _p(flat, C.c_double), n,
-                                                     _p(cfg, C.c_int32), _p(sd, C.c_uint64), UPDATER_ID[updater], n_sweeps,
-                                                     _p(amps, C.c_double), _p(rates, C.c_double)))
+        _ck(lib().pepshost_fermion_mc_sweeps_updater(rows, cols, D, state.d, _p(nf, C.c_int32), chi, _C128 if cplx else dtype, _cp(flat), n,
+                                                     _p(cfg, C.c_int32), _p(sd, C.c_uint64), FERMION_UPDATER_ID[updater], n_sweeps,
+                                                     _cp(amps), _p(rates, C.c_double)))
     elif cplx:
         _ck(lib().pepshost_fermion_mc_sweeps_c128(rows, cols, D, state.d, _p(nf, C.c_int32), chi, _cp(flat), n,
                                                   _p(cfg, C.c_int32), _p(sd, C.c_uint64), n_sweeps, _cp(amps), _p(rates, C.c_double)))
@@ -606,7 +612,7 @@ def fermion_measure_energy(state, configs, seeds, chi, warmup_sweeps, n_samples,
     return en, cfg, rates
 
 
-def fermion_exact_sum(state, all_configs, chi, t, V=0.0, batch=64, dtype=1, model="spinless", J=0.0, mu=0.0, t2=0.0):
+def fermion_exact_sum(state, all_configs, chi, t, V=0.0, batch=64, dtype=1, model="spinless", J=0.0, mu=0.0, t2=0.0, U=0.0):
     """ExactSumEnergyEvaluator on a fermionic state: (energy, gradient [rows][cols][d][D^4] with respect to the
     stored site-tensor components, zero on parity-forbidden entries).  The spinless t-V model, or -- with model="tj" or a
     diagonal hop t2 -- the models of fermion_energy through the entry that takes a parameter list."""
@@ -617,7 +623,7 @@ def fermion_exact_sum(state, all_configs, chi, t, V=0.0, batch=64, dtype=1, mode
         rows, cols, D = flat.shape[0], flat.shape[1], flat.shape[3]
         cfg = np.ascontiguousarray(all_configs, dtype=np.int32)
         nf = np.ascontiguousarray(state.nf, dtype=np.int32)
-        prm = np.array([t, V, t2, 0.0] if model == "spinless" else [t, J, V, mu, t2], dtype=np.float64)
+        prm = np.array([t, V, t2, 0.0] if model == "spinless" else [t, U, mu] if model == "hubbard" else [t, J, V, mu, t2], dtype=np.float64)
         packed = np.zeros(4 * flat.size + 5 if cplx else 2 * flat.size + 4)
         _ck(lib().pepshost_fermion_exact_sum_partial_prm(rows, cols, D, state.d, _p(nf, C.c_int32), chi, _C128 if cplx else dtype, _cp(flat),
                                                          _p(cfg, C.c_int32), cfg.shape[0], FERMION_MODEL_ID[model], _p(prm, C.c_double),
@@ -654,9 +660,10 @@ def fermion_exact_sum(state, all_configs, chi, t, V=0.0, batch=64, dtype=1, mode
     return e, fermion.fold_gradient(state, grad_ext)
 
 
-FERMION_MODEL_ID = {"spinless": 0, "tj": 1}   # params: spinless (t, V, t2); tj (t, J, V, mu[, t2]) -- as fermion_energy passes them
+# params: spinless (t, V, t2); tj (t, J, V, mu[, t2]); hubbard (t, U, mu) -- as fermion_energy passes them
+FERMION_MODEL_ID = {"spinless": 0, "tj": 1, "hubbard": 3}
 # the measurement entries also know SquaretJNNModel, the nearest-neighbour form of the registry: tjnn (t, J, mu)
-FERMION_MEASURE_MODEL_ID = {"spinless": 0, "tj": 1, "tjnn": 2}
+FERMION_MEASURE_MODEL_ID = {"spinless": 0, "tj": 1, "tjnn": 2, "hubbard": 3}
 
 
 def _fermion_measure_head(state, chi, model, params, dtype):
@@ -680,7 +687,8 @@ def fermion_observables(state, configs, chi, model="tj", params=(1.0, 0.3, 0.0, 
     """Registry of the C++ measurement solver of a fermionic model (SquareNNNModelMeasurementSolver on SquareSpinlessFermion /
     SquaretJVModel / SquaretJNNModel) on a batch of configurations: dict key -> [walker][len] with energy, charge, bond_energy_h / _v
     (/ _dr / _ur) and, for the t-J models, spin_z and the bond-singlet pairing order SC_bond_singlet_h / _v; and the psi summary
-    (psi_mean [walker], psi_rel_err [walker]).  params: spinless (t, V, t2), tj (t, J, V, mu, t2), tjnn (t, J, mu)."""
+    (psi_mean [walker], psi_rel_err [walker]).  params: spinless (t, V, t2), tj (t, J, V, mu, t2), tjnn (t, J, mu), hubbard (t, U, mu:
+    SquareHubbardModel, with spin_z and double_occupancy)."""
     cplx, head, tail, keep = _fermion_measure_head(state, chi, model, params, dtype)
     cfg = np.ascontiguousarray(configs, dtype=np.int32)
     n, sites = cfg.shape[0], cfg.shape[1] * cfg.shape[2]
@@ -715,10 +723,14 @@ def fermion_exact_sum_measure(state, all_configs, chi, model="tj", params=(1.0, 
     return out, float(vals[0])
 
 
-def fermion_measure(state, configs, seeds, chi, warmup_sweeps, n_samples, sweeps_between=1, model="tj", params=(1.0, 0.3, 0.0, 0.0), dtype=1):
-    """MCPEPSMeasurer with the exchange updater on a fermionic state: dict key -> (mean [len], stderr [len]) across the walkers, the psi
-    summary of the last sample, the energy samples [sample][walker], the final configurations and the accept rates.  Warm-up, samples
-    and ONE std::mt19937 stream per walker as fermion_measure_energy: the energy samples are the numbers that call returns."""
+def fermion_measure(state, configs, seeds, chi, warmup_sweeps, n_samples, sweeps_between=1, model="tj", params=(1.0, 0.3, 0.0, 0.0), dtype=1,
+                    updater="exchange"):
+    """MCPEPSMeasurer with the exchange updater (or updater="hubbard_u1u1") on a fermionic state: dict key -> (mean [len], stderr [len])
+    across the walkers, the psi summary of the last sample, the energy samples [sample][walker], the final configurations and the accept
+    rates.  Warm-up, samples and ONE std::mt19937 stream per walker as fermion_measure_energy: with the exchange updater the energy
+    samples are the numbers that call returns."""
+    if updater not in ("exchange", "hubbard_u1u1"):
+        raise ValueError("fermion_measure: updater must be 'exchange' or 'hubbard_u1u1'")
     cplx, head, tail, keep = _fermion_measure_head(state, chi, model, params, dtype)
     cfg = np.ascontiguousarray(configs, dtype=np.int32).copy()
     n, sites = cfg.shape[0], cfg.shape[1] * cfg.shape[2]
@@ -726,9 +738,14 @@ def fermion_measure(state, configs, seeds, chi, warmup_sweeps, n_samples, sweeps
     cap = 2 * (32 * sites + 2 * n + 4096)
     vals, keys, nvals = np.zeros(cap, dtype=np.float64), C.create_string_buffer(4096), C.c_long(0)
     en, rates = np.zeros((n_samples, n), np.complex128 if cplx else np.float64), np.zeros(n)
-    _ck(lib().pepshost_fermion_measure(*head, n, _p(cfg, C.c_int32), _p(sd, C.c_uint64), warmup_sweeps, n_samples,
-                                       sweeps_between, *tail, keys, 4096, _p(vals, C.c_double), C.c_long(cap), C.byref(nvals), _cp(en),
-                                       _p(rates, C.c_double)))
+    if updater == "exchange":
+        _ck(lib().pepshost_fermion_measure(*head, n, _p(cfg, C.c_int32), _p(sd, C.c_uint64), warmup_sweeps, n_samples,
+                                           sweeps_between, *tail, keys, 4096, _p(vals, C.c_double), C.c_long(cap), C.byref(nvals), _cp(en),
+                                           _p(rates, C.c_double)))
+    else:
+        _ck(lib().pepshost_fermion_measure_updater(*head, n, _p(cfg, C.c_int32), _p(sd, C.c_uint64), FERMION_UPDATER_ID[updater], warmup_sweeps,
+                                                   n_samples, sweeps_between, *tail, keys, 4096, _p(vals, C.c_double), C.c_long(cap),
+                                                   C.byref(nvals), _cp(en), _p(rates, C.c_double)))
     items, v = _keyed(keys, vals[:nvals.value], cplx)
     out, off = {}, 0
     for key, ln in items:
@@ -757,6 +774,8 @@ def _fermion_prm(model, params):
     prm = [float(x) for x in params]
     if model == "spinless":
         prm = (prm + [0.0] * 4)[:4]                         # [t, V, t2, -]
+    elif model == "hubbard":
+        prm = (prm + [0.0] * 3)[:3]                         # [t, U, mu]
     else:
         prm = prm + [0.0] * max(0, 4 - len(prm))            # [t, J, V, mu, (t2)]
     return np.array(prm, dtype=np.float64)
@@ -765,8 +784,8 @@ def _fermion_prm(model, params):
 def fermion_optimize_exact_sum(state, all_configs, chi, model, params, rule, lr, rule_params, iterations, clip_value=0.0, clip_norm=0.0,
                                dtype=1, batch=64, return_grad_norms=False):
     """optimize_exact_sum on a fermionic state (peps_amd.fermion.FermionState): the decorated components are uploaded once, every
-    iteration evaluates, folds and projects the gradient, clips and steps on the device.  model "spinless" (t, V, t2) or "tj"
-    (t, J, V, mu[, t2]).  Returns (energies[iterations + 1], final stored tensors [rows][cols][d][D^4] [, norms of the gradient over
+    iteration evaluates, folds and projects the gradient, clips and steps on the device.  model "spinless" (t, V, t2), "tj"
+    (t, J, V, mu[, t2]) or "hubbard" (t, U, mu).  Returns (energies[iterations + 1], final stored tensors [rows][cols][d][D^4] [, norms of the gradient over
     the stored parameters]); FermionState.from_stored(state, stored) is the state after the run."""
     cplx, flat, nf, par, head = _fermion_head(state, dtype)
     cfg = np.ascontiguousarray(all_configs, dtype=np.int32)
@@ -961,3 +980,13 @@ def tnn3_table(d, nf=None, order=0):
     nfa = None if nf is None else np.ascontiguousarray(nf, dtype=np.int32)
     _ck(l.pepshost_tnn3_table(d, None if nfa is None else _p(nfa, C.c_int32), order, _p(out, C.c_int32)))
     return out
+
+
+def hubbard_tables():
+    """The tables of the Hubbard model as the host layer builds them, without a device: (sector table [16][10] of
+    MCUpdateSquareNNHubbardU1U1OBC, hop table [16][2][2] of SquareHubbardModel) -- peps_amd.fermion.hubbard_sector_table() and
+    hubbard_hop_table() state the same rules."""
+    sec, hop = np.zeros((16, 10), dtype=np.int32), np.zeros((16, 2, 2), dtype=np.int32)
+    _ck(lib().pepshost_hubbard_sector_table(_p(sec, C.c_int32)))
+    _ck(lib().pepshost_hubbard_hop_table(_p(hop, C.c_int32)))
+    return sec, hop

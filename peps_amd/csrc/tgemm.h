@@ -78,6 +78,13 @@ struct TGemmDesc {
   // (floats) of a small shared B operand that tgemm_direct_kernel stages in LDS (0: B is read from global memory)
   int thin = 0;
   int stage_span = 0;
+  // set by tgemm_launch (tg_set_divs), never by a caller, read by tgemm_direct_kernel: the distinct divisors above 1 among the
+  // div / seldiv / bdiv of the descriptor (at most two; tgemm_launch refuses a descriptor with more), and two bits per use that
+  // name the quotient it takes: 0 = b itself, 1 = b / qdiv[0], 2 = b / qdiv[1].  qsel = 0 (the whole amplitude path): no
+  // quotient is formed at all; otherwise the kernel forms the two once.
+  // Uses in order: dI[0..2], dJ[0..2], dK[0..2], seldivA, seldivB, bdivA, bdivB, bdivC.
+  int qsel = 0;
+  int qdiv[2] = {1, 1};
 
   __host__ __device__ int Itot() const { return I[0] * I[1] * I[2]; }
   __host__ __device__ int Jtot() const { return J[0] * J[1] * J[2]; }
@@ -480,7 +487,7 @@ __global__ __launch_bounds__(256) void tgemm_skinny_f64_kernel(TGemmDesc d, cons
   int Itot = d.Itot(), Ktot = d.Ktot();
   if (d.dynI) Itot = max(0, min(Itot, d.dynI[b] * d.dynI_mul));
   if (d.dynK) Ktot = max(0, min(Ktot, d.dynK[b] * d.dynK_mul));
-  if (d.flopc && threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0 && b % d.flop_stride == 0) {
+  if (d.flopc && threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0 && (b & (d.flop_stride - 1)) == 0) {
     atomicAdd(d.flopc, 2ull * d.flop_stride * Itot * d.Jtot() * Ktot);
     if (d.bytec)
       atomicAdd(d.bytec, (unsigned long long)d.flop_stride * ((unsigned long long)Itot * Ktot * sizeof(TA) + (unsigned long long)Ktot * d.Jtot() * sizeof(TB) +
@@ -511,7 +518,7 @@ __global__ __launch_bounds__(256) void tgemm_kernel(TGemmDesc d, const TA *__res
   int Itot = d.Itot(), Ktot = d.Ktot();
   if (d.dynI) Itot = max(0, min(Itot, d.dynI[b] * d.dynI_mul));
   if (d.dynK) Ktot = max(0, min(Ktot, d.dynK[b] * d.dynK_mul));
-  if (d.flopc && threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0 && b % d.flop_stride == 0)
+  if (d.flopc && threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0 && (b & (d.flop_stride - 1)) == 0)
   {
     atomicAdd(d.flopc, (unsigned long long)(d.upper_only ? 1 : 2) * d.flop_stride * Itot * d.Jtot() * Ktot);
     if (d.bytec)
@@ -540,7 +547,141 @@ __global__ __launch_bounds__(256) void tgemm_kernel(TGemmDesc d, const TA *__res
 // the number of memory requests, not bytes (each lane addresses its own row).
 // f32 in / f32 out.  Same descriptor semantics as tgemm_kernel (dynK is not supported here).
 // per-walker live extents replace / mask the static dims of a descriptor (block-uniform)
-__device__ __forceinline__ void tg_apply_extents(TGemmDesc &d, const int b) {
+//
+// Everything a block reads about its own batch entry -- nine live extents, dynI, the two selectors, batch_flag, scale_in -- is
+// fetched at kernel entry as ONE batch of scalar loads: every address is formed first, every load is issued whether its slot is
+// set or not (an unset slot reads tg_neutral_word and its value is dropped by a select), and only then are clamps, masks and
+// multipliers applied.  Written slot by slot (`if (p) e = p[b / div] * mul`), every slot was a basic block of its own with an
+// integer division and two waits for the scalar cache in it: 6-8 dependent round trips before the first operand load of M and Y.
+static __device__ int tg_neutral_word;    // never written: where the unset slots of a descriptor read
+
+struct TgEntry {
+  int e[9];            // the words behind dI[0..2], dJ[0..2], dK[0..2]
+  int dynI, selA, selB, flag;
+  float scale;
+  int bA, bB, bC;      // b / bdivA, b / bdivB, b / bdivC
+};
+
+// the quotient that use `use` of the descriptor takes (TGemmDesc::qsel)
+__device__ __forceinline__ int tg_quot(const int qsel, const int use, const int b, const int q1, const int q2) {
+  const int lo = (qsel >> (2 * use)) & 1, hi = (qsel >> (2 * use + 1)) & 1;     // (arithmetic, not selects: those came out as branches)
+  return b + (q1 - b) * lo + (q2 - b) * hi;
+}
+
+// which of the optional words a kernel uses (the others are neither addressed nor loaded)
+enum : int { TG_EN_DYNI = 1, TG_EN_SELA = 2, TG_EN_SELB = 4, TG_EN_FLAG = 8, TG_EN_SCALE = 16, TG_EN_ALL = 31 };
+
+struct TgEntryAddr {
+  const int *pe[9], *pdyn, *psa, *psb, *pfl;
+  const float *psc;
+  int bA, bB, bC;
+};
+
+// step 1: every index and address of the entry.  The empty asm statements of the three steps only name values as scalar inputs:
+// they hold the compiler to the order addresses / loads / uses (it otherwise sinks each load to its use and interleaves the
+// kernel-argument loads of the pointers with them, one wait per slot again).
+// UNIT: the launcher found no divisor above 1 (TGemmDesc::qsel == 0)
+template <int USE, bool UNIT>
+__device__ __forceinline__ TgEntryAddr tg_entry_addr(const TGemmDesc &d, const int b) {
+  TgEntryAddr a;
+  int ix[9], ixA = b, ixB = b;
+  a.bA = a.bB = a.bC = b;
+#pragma unroll
+  for (int s = 0; s < 9; ++s) ix[s] = b;
+  if constexpr (!UNIT) {
+    const int qs = d.qsel;
+    const int q1 = (int)((unsigned)b / (unsigned)d.qdiv[0]), q2 = (int)((unsigned)b / (unsigned)d.qdiv[1]);
+#pragma unroll
+    for (int s = 0; s < 9; ++s) ix[s] = tg_quot(qs, s, b, q1, q2);
+    ixA = tg_quot(qs, 9, b, q1, q2);
+    ixB = tg_quot(qs, 10, b, q1, q2);
+    a.bA = tg_quot(qs, 11, b, q1, q2);
+    a.bB = tg_quot(qs, 12, b, q1, q2);
+    a.bC = tg_quot(qs, 13, b, q1, q2);
+  }
+  const int *const nz = &tg_neutral_word;
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+    a.pe[s] = d.dI[s].p ? d.dI[s].p + ix[s] : nz;
+    a.pe[3 + s] = d.dJ[s].p ? d.dJ[s].p + ix[3 + s] : nz;
+    a.pe[6 + s] = d.dK[s].p ? d.dK[s].p + ix[6 + s] : nz;
+  }
+  a.pdyn = ((USE & TG_EN_DYNI) && d.dynI) ? d.dynI + b : nz;
+  a.psa = ((USE & TG_EN_SELA) && d.selA) ? d.selA + (long)ixA * d.selA_inc : nz;
+  a.psb = ((USE & TG_EN_SELB) && d.selB) ? d.selB + (long)ixB * d.selB_inc : nz;
+  a.pfl = ((USE & TG_EN_FLAG) && d.batch_flag) ? d.batch_flag + b : nz;
+  a.psc = ((USE & TG_EN_SCALE) && d.scale_in) ? d.scale_in + b : reinterpret_cast<const float *>(nz);
+  asm volatile("" ::"s"(a.pe[0]), "s"(a.pe[1]), "s"(a.pe[2]), "s"(a.pe[3]), "s"(a.pe[4]), "s"(a.pe[5]), "s"(a.pe[6]), "s"(a.pe[7]), "s"(a.pe[8]));
+  if constexpr ((USE & TG_EN_DYNI) != 0) asm volatile("" ::"s"(a.pdyn));
+  if constexpr ((USE & TG_EN_SELA) != 0) asm volatile("" ::"s"(a.psa));
+  if constexpr ((USE & TG_EN_SELB) != 0) asm volatile("" ::"s"(a.psb));
+  if constexpr ((USE & TG_EN_FLAG) != 0) asm volatile("" ::"s"(a.pfl));
+  if constexpr ((USE & TG_EN_SCALE) != 0) asm volatile("" ::"s"(a.psc));
+  return a;
+}
+
+// step 2: the loads, back to back
+template <int USE>
+__device__ __forceinline__ TgEntry tg_entry_fetch(const TgEntryAddr &a) {
+  // (read through the constant address space: a scalar load whatever the compiler can prove about stores around it; none of
+  // these words is written by the launch that reads it before this point)
+  typedef const __attribute__((address_space(4))) int *cint_p;
+  typedef const __attribute__((address_space(4))) float *cfloat_p;
+  TgEntry en;
+#pragma unroll
+  for (int s = 0; s < 9; ++s) en.e[s] = *(cint_p)a.pe[s];
+  en.dynI = (USE & TG_EN_DYNI) ? *(cint_p)a.pdyn : 0;
+  en.selA = (USE & TG_EN_SELA) ? *(cint_p)a.psa : 0;
+  en.selB = (USE & TG_EN_SELB) ? *(cint_p)a.psb : 0;
+  en.flag = (USE & TG_EN_FLAG) ? *(cint_p)a.pfl : 0;
+  en.scale = (USE & TG_EN_SCALE) ? *(cfloat_p)a.psc : 1.f;
+  en.bA = a.bA; en.bB = a.bB; en.bC = a.bC;
+  return en;
+}
+
+// step 3: the one wait for the batch
+template <int USE>
+__device__ __forceinline__ void tg_entry_arrive(const TgEntry &en) {
+  asm volatile("" ::"s"(en.e[0]), "s"(en.e[1]), "s"(en.e[2]), "s"(en.e[3]), "s"(en.e[4]), "s"(en.e[5]), "s"(en.e[6]), "s"(en.e[7]), "s"(en.e[8]));
+  if constexpr ((USE & TG_EN_DYNI) != 0) asm volatile("" ::"s"(en.dynI));
+  if constexpr ((USE & TG_EN_SELA) != 0) asm volatile("" ::"s"(en.selA));
+  if constexpr ((USE & TG_EN_SELB) != 0) asm volatile("" ::"s"(en.selB));
+  if constexpr ((USE & TG_EN_FLAG) != 0) asm volatile("" ::"s"(en.flag));
+  if constexpr ((USE & TG_EN_SCALE) != 0) asm volatile("" ::"s"(en.scale));
+}
+
+// The three steps for a descriptor.  The test for divisors is one uniform scalar branch around two copies of the batch (not
+// around the quotients alone: the indices would then stay live as values of their own beside b).
+template <int USE>
+__device__ __forceinline__ TgEntry tg_entry(const TGemmDesc &d, const int b) {
+  TgEntry en;
+  if (d.qsel == 0) {
+    en = tg_entry_fetch<USE>(tg_entry_addr<USE, true>(d, b));
+    tg_entry_arrive<USE>(en);
+  } else {      // (the candidate batches of the sweeps, never the amplitude path)
+    en = tg_entry_fetch<USE>(tg_entry_addr<USE, false>(d, b));
+    tg_entry_arrive<USE>(en);
+  }
+  return en;
+}
+// per-walker live extents replace / mask the static dims of a descriptor (block-uniform); selects only
+__device__ __forceinline__ void tg_apply_extents(TGemmDesc &d, const TgEntry &en) {
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+    const int ei = max(0, min(d.I[s], en.e[s] * d.dI[s].mul));
+    const int ej = max(0, min(d.J[s], en.e[3 + s] * d.dJ[s].mul));
+    const int ek = max(0, min(d.K[s], en.e[6 + s] * d.dK[s].mul));
+    const bool hi = d.dI[s].p != nullptr, hj = d.dJ[s].p != nullptr, hk = d.dK[s].p != nullptr;
+    d.Imask[s] = (hi && d.dI[s].mask) ? ei : d.Imask[s];
+    d.I[s] = (hi && !d.dI[s].mask) ? ei : d.I[s];
+    d.Jmask[s] = (hj && d.dJ[s].mask) ? ej : d.Jmask[s];
+    d.J[s] = (hj && !d.dJ[s].mask) ? ej : d.J[s];
+    d.K[s] = hk ? ek : d.K[s];
+  }
+}
+// The chained kernels apply their live extents slot by slot, as every kernel did before: batching the words of two and three
+// descriptors was measured (profiles/entry_extents_ab.md) -- the two-stage chain did not move, the three-stage chain lost 6 %.
+__device__ __forceinline__ void tg_apply_extents_serial(TGemmDesc &d, const int b) {
 #pragma unroll
   for (int s = 0; s < 3; ++s) {
     if (d.dI[s].p) { const int e = max(0, min(d.I[s], d.dI[s].p[b / d.dI[s].div] * d.dI[s].mul)); if (d.dI[s].mask) d.Imask[s] = e; else d.I[s] = e; }
@@ -548,6 +689,11 @@ __device__ __forceinline__ void tg_apply_extents(TGemmDesc &d, const int b) {
     if (d.dK[s].p) d.K[s] = max(0, min(d.K[s], d.dK[s].p[b / d.dK[s].div] * d.dK[s].mul));
   }
 }
+__device__ __forceinline__ bool tg_skipped(const TGemmDesc &d, const TgEntry &en) { return d.batch_flag && en.flag >= 0; }
+__device__ __forceinline__ int tg_dyn_rows(const TGemmDesc &d, const TgEntry &en, const int Itot) {
+  return d.dynI ? max(0, min(Itot, en.dynI * d.dynI_mul)) : Itot;
+}
+__device__ __forceinline__ float tg_in_scale(const TGemmDesc &d, const TgEntry &en) { return d.scale_in ? en.scale : 1.f; }
 
 // The tile loop of the direct kernel: the block's four waves walk the 32x32 tiles of C = A B for one batch entry.
 // d has its live extents applied; A, B, C are the entry's operand bases (generic pointers: an operand may live in LDS,
@@ -968,31 +1114,31 @@ __global__ __launch_bounds__(256, ACC64 ? 4 : 6) void tgemm_direct_kernel(TGemmD
   __shared__ __attribute__((aligned(16))) int offCi_s[4][32];
   __shared__ float s_stage[STAGE == 1 ? TG_STAGE_FLOATS : STAGE == 2 ? TG_CTILE_FLOATS : 1];
   const int b = blockIdx.z;
-  if (d.batch_flag && d.batch_flag[b] >= 0) return;
+  const TgEntry en = tg_entry<TG_EN_ALL>(d, b);
+  if (tg_skipped(d, en)) return;
   const int K2s = d.K[2];                     // static extent of k2 (vector loads stay inside it)
-  tg_apply_extents(d, b);
-  int Itot = d.Itot();
+  tg_apply_extents(d, en);
+  const int Itot = tg_dyn_rows(d, en, d.Itot());
   const int Jtot = d.Jtot();
-  if (d.dynI) Itot = max(0, min(Itot, d.dynI[b] * d.dynI_mul));
+  const float in_scale = tg_in_scale(d, en);
   if (Itot <= 0 || Jtot <= 0) {
     if (d.scale_out && threadIdx.x == 0) { d.scale_out[b] = 1.f; if (d.norm_flag) d.norm_flag[b] = 1; }   // nothing stored: zero norm
     return;
   }
-  if (d.flopc && threadIdx.x == 0 && blockIdx.x == 0 && b % d.flop_stride == 0)
+  if (d.flopc && threadIdx.x == 0 && blockIdx.x == 0 && (b & (d.flop_stride - 1)) == 0)     // (flop_stride: 1 or 64)
   {
     atomicAdd(d.flopc, 2ull * d.flop_stride * Itot * Jtot * d.Ktot());
     if (d.bytec) atomicAdd(d.bytec, 4ull * d.flop_stride * ((unsigned long long)Itot * d.Ktot() + (unsigned long long)d.Ktot() * Jtot + (unsigned long long)Itot * Jtot));
   }
-  long baseA = (long)(b / d.bdivA) * d.wA, baseB = (long)(b / d.bdivB) * d.wB;
-  if (d.selA) baseA += (long)d.selA[(long)(b / d.seldivA) * d.selA_inc] * d.selA_mul;
-  if (d.selB) baseB += (long)d.selB[(long)(b / d.seldivB) * d.selB_inc] * d.selB_mul;
+  const long baseA = (long)en.bA * d.wA + (d.selA ? (long)en.selA * d.selA_mul : 0);
+  const long baseB = (long)en.bB * d.wB + (d.selB ? (long)en.selB * d.selB_mul : 0);
   double ss = 0.0;
   if constexpr (ACC64)
-    tg_direct_body_f64<AVEC, BVEC>(d, Ag + baseA, Bg + baseB, Cg + (long)(b / d.bdivC) * d.wC, Itot, Jtot, K2s, offCi_s,
-                                   blockIdx.x * 4, gridDim.x * 4, d.scale_in ? d.scale_in[b] : 1.f, d.scale_out ? &ss : nullptr);
+    tg_direct_body_f64<AVEC, BVEC>(d, Ag + baseA, Bg + baseB, Cg + (long)en.bC * d.wC, Itot, Jtot, K2s, offCi_s,
+                                   blockIdx.x * 4, gridDim.x * 4, in_scale, d.scale_out ? &ss : nullptr);
   else if constexpr (STAGE == 2)
-    tg_direct_body<AVEC, false, true, true>(d, Ag + baseA, Bg + baseB, Cg + (long)(b / d.bdivC) * d.wC, Itot, Jtot, K2s, offCi_s,
-                                            blockIdx.x * 4, gridDim.x * 4, d.scale_in ? d.scale_in[b] : 1.f, nullptr, s_stage);
+    tg_direct_body<AVEC, false, true, true>(d, Ag + baseA, Bg + baseB, Cg + (long)en.bC * d.wC, Itot, Jtot, K2s, offCi_s,
+                                            blockIdx.x * 4, gridDim.x * 4, in_scale, nullptr, s_stage);
   else if constexpr (STAGE == 1) {
     // Small shared B operand (Y = Tt V^T: the rows q of V lie 128 floats apart, so every lane of every wave asks for lines of
     // its own): J = (1, 1, q) fits one column tile, every wave reads the same block -- its live rows are copied once, 16 bytes
@@ -1009,11 +1155,11 @@ __global__ __launch_bounds__(256, ACC64 ? 4 : 6) void tgemm_direct_kernel(TGemmD
     }
     __syncthreads();
     d.sBj[2] = pitch;
-    tg_direct_body<AVEC, false, true>(d, Ag + baseA, s_stage, Cg + (long)(b / d.bdivC) * d.wC, Itot, Jtot, K2s, offCi_s,
-                                      blockIdx.x * 4, gridDim.x * 4, d.scale_in ? d.scale_in[b] : 1.f, d.scale_out ? &ss : nullptr);
+    tg_direct_body<AVEC, false, true>(d, Ag + baseA, s_stage, Cg + (long)en.bC * d.wC, Itot, Jtot, K2s, offCi_s,
+                                      blockIdx.x * 4, gridDim.x * 4, in_scale, d.scale_out ? &ss : nullptr);
   } else
-    tg_direct_body<AVEC, BVEC, true>(d, Ag + baseA, Bg + baseB, Cg + (long)(b / d.bdivC) * d.wC, Itot, Jtot, K2s, offCi_s,
-                                     blockIdx.x * 4, gridDim.x * 4, d.scale_in ? d.scale_in[b] : 1.f, d.scale_out ? &ss : nullptr);
+    tg_direct_body<AVEC, BVEC, true>(d, Ag + baseA, Bg + baseB, Cg + (long)en.bC * d.wC, Itot, Jtot, K2s, offCi_s,
+                                     blockIdx.x * 4, gridDim.x * 4, in_scale, d.scale_out ? &ss : nullptr);
   if (d.scale_out) {     // (gridDim.x == 1: this block stored all of C[b])
     __shared__ double s_nred[4];
     double a = ss;
@@ -1064,8 +1210,8 @@ __global__ __launch_bounds__(256, MINB) void tgemm_chain_kernel(TGemmDesc d1, TG
   const int b = blockIdx.x;
   if (only_flagged && flag[b] >= 0) return;     // second launch (larger buffer, fewer blocks per CU): declined entries only
   const int K2s1 = d1.K[2], K2s2 = d2.K[2];
-  tg_apply_extents(d1, b);
-  tg_apply_extents(d2, b);
+  tg_apply_extents_serial(d1, b);
+  tg_apply_extents_serial(d2, b);
   int I1 = d1.Itot();
   const int J1 = d1.Jtot();
   if (d1.dynI) I1 = max(0, min(I1, d1.dynI[b] * d1.dynI_mul));
@@ -1198,9 +1344,9 @@ __global__ __launch_bounds__(256, MINB) void tgemm_chain3_kernel(TGemmDesc d1, T
   if (skip && skip[b]) return;        // the caller does not need this entry (its C3 stays undefined)
   const int K2s1 = d1.K[2], K2s2 = d2.K[2], K2s3 = d3.K[2];
   const int x_static = mp3.chunkI == 0 ? d3.I[0] : mp3.chunkI == 1 ? d3.I[1] : d3.I[2];
-  tg_apply_extents(d1, b);
-  tg_apply_extents(d2, b);
-  tg_apply_extents(d3, b);
+  tg_apply_extents_serial(d1, b);
+  tg_apply_extents_serial(d2, b);
+  tg_apply_extents_serial(d3, b);
   const int I1 = d1.Itot(), J1 = d1.Jtot(), I2 = d2.Itot(), J2 = d2.Jtot(), J3 = d3.Jtot();
   int jsub = -1;
 #pragma unroll
@@ -1467,6 +1613,30 @@ TgRoute tgemm_route(const TGemmDesc &d, const void *A, const void *B) {
   return r;
 }
 
+// TGemmDesc::qsel / qdiv of a descriptor about to be launched (unset slots and selectors read no divisor); false: more than
+// two distinct divisors above 1, or one below 1
+inline bool tg_set_divs(TGemmDesc &d) {
+  const int dv[14] = {d.dI[0].p ? d.dI[0].div : 1, d.dI[1].p ? d.dI[1].div : 1, d.dI[2].p ? d.dI[2].div : 1,
+                      d.dJ[0].p ? d.dJ[0].div : 1, d.dJ[1].p ? d.dJ[1].div : 1, d.dJ[2].p ? d.dJ[2].div : 1,
+                      d.dK[0].p ? d.dK[0].div : 1, d.dK[1].p ? d.dK[1].div : 1, d.dK[2].p ? d.dK[2].div : 1,
+                      d.selA ? d.seldivA : 1, d.selB ? d.seldivB : 1, d.bdivA, d.bdivB, d.bdivC};
+  d.qsel = 0;
+  d.qdiv[0] = d.qdiv[1] = 1;
+  int n = 0;
+  for (int u = 0; u < 14; ++u) {
+    if (dv[u] == 1) continue;
+    if (dv[u] < 1) return false;
+    int c = 0;
+    while (c < n && d.qdiv[c] != dv[u]) ++c;
+    if (c == n) {
+      if (n == 2) return false;
+      d.qdiv[n++] = dv[u];
+    }
+    d.qsel |= (c + 1) << (2 * u);
+  }
+  return true;
+}
+
 template <typename TA, typename TB, typename TC, typename TAcc>
 void tgemm_launch(hipStream_t s, const TGemmDesc &d_in, const TA *A, const TB *B, TC *C) {
   const TgRoute r = tgemm_route<TA, TB, TC, TAcc>(d_in, A, B);
@@ -1478,6 +1648,7 @@ void tgemm_launch(hipStream_t s, const TGemmDesc &d_in, const TA *A, const TB *B
   d.flop_stride = d.nbatch >= 256 ? 64 : 1;   // one atomic per 64 walkers: a same-address atomic per block costs ~10 %
   d.thin = r.thin;
   d.stage_span = r.stage_span;
+  PG_REQUIRE(tg_set_divs(d), 1, "tensor GEMM: more than two distinct batch divisors in one descriptor");
   switch (r.kind) {
     case TG_ROUTE_DIRECT:
       if constexpr (sizeof(TA) == 4 && sizeof(TB) == 4 && sizeof(TC) == 4 && sizeof(TAcc) == 4) {

@@ -791,8 +791,9 @@ int pepsgpu_diag_suwa_todo(const double *weights, int n, int init, const uint32_
 int pepsgpu_diag_tgemm_chain(const int *dims7, const int32_t *live3_per_entry, int nbatch, const float *R, const float *A,
                              const float *W, float *P_out, int32_t *flags_out);
 int pepsgpu_diag_gram_chol(int dtype, const void *P, int K, int n, int nbatch, void *R_out, int32_t *mlive_out);
-/* one of the two one-wave Gram-free factor kernels alone (form 0: gram_chol_wave_kernel, 1: gram_chol_wave_split_kernel, the
- * row-parity placement), then the list kernel for the walkers it hands on: P = [nbatch][K][n] float32, klive[b] live rows,
+/* one of the two one-wave Gram-free factor kernels alone, launched as the engine launches it (form 0: gram_chol_wave_kernel, four
+ * walkers per 256-thread block; 1: gram_chol_wave_split_kernel, the row-parity placement, one walker per 64-thread block), then the
+ * list kernel for the walkers it hands on: P = [nbatch][K][n] float32, klive[b] live rows,
  * columns (outer, inner) with inner_live[b] live inner indices (NULL: all); R_out [nbatch][n][n] is read as well: what no
  * kernel stores comes back unchanged */
 int pepsgpu_diag_gram_chol_wave(const float *P, int K, int n, int nbatch, const int32_t *klive, int inner,

@@ -1001,9 +1001,8 @@ extern "C" int pepsgpu_diag_gram_chol_wave(const float *P, int K, int n, int nba
       PG_CHECK_HIP(hipMalloc(&dil, nbatch * sizeof(int)));
       PG_CHECK_HIP(hipMemcpy(dil, inner_live, nbatch * sizeof(int), hipMemcpyHostToDevice));
     }
-    const auto wave_kernel = form ? gram_chol_wave_split_kernel : gram_chol_wave_kernel;
-    hipLaunchKernelGGL(wave_kernel, dim3((nbatch + 3) / 4), dim3(256), 0, 0, (const float *)dP, (long)K * n, n, (const int *)dk, 1, K, dR,
-                       (long)n * n, dml, inner, (const int *)dil, max_pass, nbatch, dl);
+    launch_gram_chol_wave(0, form != 0, nbatch, (const float *)dP, (long)K * n, n, (const int *)dk, 1, K, dR, (long)n * n, dml, inner,
+                          (const int *)dil, max_pass, dl);
     PG_CHECK_HIP(hipGetLastError());
     if (n <= 128)
       hipLaunchKernelGGL((gram_chol_lowrank_list_kernel<float, 96, 128>), dim3(std::min(nbatch, 512)), dim3(128), 0, 0, (const float *)dP,

@@ -1140,14 +1140,17 @@ __device__ __forceinline__ void gw_split_dot(const float (&pp)[4][32], const int
   }
 }
 
-__global__ __launch_bounds__(256, 2) void gram_chol_wave_split_kernel(const float *__restrict__ Pg, long wP, int n,
-                                                                    const int *__restrict__ kdyn, int kdyn_mul, int kmax,
-                                                                    float *__restrict__ Rg, long wR, int *__restrict__ mlive_out,
-                                                                    int inner, const int *__restrict__ inner_live, int max_pass,
-                                                                    int nbatch, int *__restrict__ decl_list = nullptr) {
+// One walker per WORKGROUP (64 threads, grid nbatch; launch_gram_chol_wave): the walkers share nothing, and a workgroup is placed on
+// a CU as a whole -- in a 256-thread block the slot of a walker that finishes early (lower rank, one pass instead of two) stays
+// empty until the other three have finished.
+__global__ __launch_bounds__(64, 2) void gram_chol_wave_split_kernel(const float *__restrict__ Pg, long wP, int n,
+                                                                   const int *__restrict__ kdyn, int kdyn_mul, int kmax,
+                                                                   float *__restrict__ Rg, long wR, int *__restrict__ mlive_out,
+                                                                   int inner, const int *__restrict__ inner_live, int max_pass,
+                                                                   int nbatch, int *__restrict__ decl_list = nullptr) {
   constexpr int KC = 64, RC = 16, KH = KC / 2;
-  const int lane = threadIdx.x & 63;
-  const int b = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));   // (wave-uniform: scalar from here on)
+  const int lane = threadIdx.x;
+  const int b = blockIdx.x;                             // (uniform: scalar from here on)
   if (b >= nbatch) return;
   const int Ktot = kdyn ? max(0, min(kmax, kdyn[b] * kdyn_mul)) : kmax;
   const int ilive = inner_live ? min(inner, inner_live[b]) : inner;
@@ -1315,6 +1318,17 @@ inline bool factor_split() {
   static const bool v = getenv("PEPSGPU_FACTOR_SPLIT") ? atoi(getenv("PEPSGPU_FACTOR_SPLIT")) != 0 : true;
   return v;
 }
+// One launch of a one-wave factor kernel: the split form with one walker per 64-thread block, the other with four walkers per
+// 256-thread block (the form the split launch is compared with).
+inline void launch_gram_chol_wave(hipStream_t s, bool split, int nbatch, const float *P, long wP, int n, const int *kdyn, int kdyn_mul,
+                                  int kmax, float *R, long wR, int *mlive, int inner, const int *inner_live, int max_pass, int *decl_list) {
+  if (split)
+    hipLaunchKernelGGL(gram_chol_wave_split_kernel, dim3(nbatch), dim3(64), 0, s, P, wP, n, kdyn, kdyn_mul, kmax, R, wR, mlive, inner,
+                       inner_live, max_pass, nbatch, decl_list);
+  else
+    hipLaunchKernelGGL(gram_chol_wave_kernel, dim3((nbatch + 3) / 4), dim3(256), 0, s, P, wP, n, kdyn, kdyn_mul, kmax, R, wR, mlive, inner,
+                       inner_live, max_pass, nbatch, decl_list);
+}
 
 // (defined in trunc_mid.h) MFMA Gram of the live columns in registers + low-rank Cholesky, one kernel per walker
 template <typename T>
@@ -1358,9 +1372,8 @@ inline void launch_gram_chol_lowrank(hipStream_t s, int nbatch, const T *P, long
         int *dl = no_list ? nullptr : scratch_list;
         if (dl) PG_CHECK_HIP(hipMemsetAsync(dl + nbatch, 0, sizeof(int), s));
         // (row-parity placement of P for the dot products unless PEPSGPU_FACTOR_SPLIT=0: the same bytes, fewer instructions)
-        const auto wave_kernel = factor_split() ? gram_chol_wave_split_kernel : gram_chol_wave_kernel;
-        hipLaunchKernelGGL(wave_kernel, dim3((nbatch + 3) / 4), dim3(256), 0, s, (const float *)P, wP, n, kdyn, kdyn_mul, kmax,
-                           (float *)R, wR, mlive, inner, inner_live, std::max(max_pass, 2), nbatch, dl);
+        launch_gram_chol_wave(s, factor_split(), nbatch, (const float *)P, wP, n, kdyn, kdyn_mul, kmax, (float *)R, wR, mlive, inner,
+                              inner_live, std::max(max_pass, 2), dl);
         done = true;
         if (dl && narrow && n <= 128) {     // the handed-on walkers: list kernel, then nothing else to launch
           hipLaunchKernelGGL((gram_chol_lowrank_list_kernel<T, KCAP, 128>), dim3(std::min(nbatch, 512)), dim3(128), 0, s, P, wP, n, kdyn,

@@ -382,6 +382,52 @@ int pepsgpu_walker_trace_slice(pepsgpu_ctx *ctx, int walker, int opp_level, cons
                                double *out);
 /* Completed pepsgpu_walker_trace_slice calls of this process (all contexts).  Needs no device. */
 long pepsgpu_diag_walker_slice_calls(void);
+/* The singlet-pair correlation <Delta^dag(ref bond) Delta(target bond)> of the t-J models (model_solvers/base/
+ * singlet_pair_correlation_measurement_mixin.h:349-534; its MeasureSingletPairCorrelation :279-297 throws, the algorithm below it is
+ * the one served here) on a FERMIONIC context: physical dimension 4 d, the walkers' configurations extended states e = s + d * variant
+ * with the row-major variants 0 / 1 (the parity of the fermions up to and including the site).  The two sites of a horizontal bond are
+ * adjacent in that order and a pair move keeps the parity of the pair, so only the variants of these two sites change and the rows
+ * below need no change; the device derives them from occ [d] by the rule of pepsgpu_nn_pair_slice_fermion.
+ *
+ * The excited row of the reference bond (:376-401: the MPO of row y1 with the tensors of (x1, x1 + 1) replaced) without a host table:
+ * the walker's MPO becomes row `num` under the walkers' current configurations with the pair (col, col + 1) replaced, per walker, by
+ * candidate `slot` of pair_table ([d * d][2][2] over PHYSICAL states, the layout and the rules of pepsgpu_nn_pair_slice_fermion,
+ * (-1, -1) for none); a walker without that candidate keeps its row.  A device-to-device copy of the configuration table plus ONE
+ * two-site patch kernel, no upload, no synchronisation.  open_out [n] (may be NULL) = 1 where the walker has the candidate; sign_out [n]
+ * (may be NULL) = Sigma(S') / Sigma(S) of the decoration, -1 where the fermion number changes by +-2, +1 where it is kept, 0 for none.
+ * Afterwards the walker is exactly as after pepsgpu_walker_set_mpo(.., states, ..) with that row.  UP walkers only, d <= 8.
+ * Status PEPSGPU_EINVAL: NULL occ or pair_table, a walker that is not UP, 4 * d != the physical dimension, an occ entry outside {0, 1},
+ * slot outside {0, 1}, num outside the lattice or col + 1 outside the row, a table entry outside [-1, d), a candidate with only one -1
+ * or one that changes the fermion parity of the pair; PEPSGPU_ESTATE: a state of the row with a column-major variant (2 / 3).  A refused
+ * call leaves the walker and its MPO as they were. */
+int pepsgpu_walker_set_mpo_excited_pair(pepsgpu_ctx *ctx, int walker, int num, int col, int d, const int32_t *occ, const int32_t *pair_table,
+                                        int slot, uint8_t *open_out, int32_t *sign_out);
+/* The target-row loop (:446-519 on bmps_walker.h:216-463) in one call with one read-back, for the walker's current MPO when that is a
+ * row named by configuration or by states (N = cols >= 2):
+ *   InitBTenLeft(opp, 0), InitBTenRight(opp, 1), then for x2 = 0 .. N - 2: TraceWithTwoSiteBTen at x2 with the states of (x2, x2 + 1)
+ *   replaced by candidate k of pair_table, k = 0, 1, and ShiftBTenWindow(RIGHT) while x2 < N - 2.
+ *   out [n][N - 1][2] (PEPSGPU_C128: interleaved (re, im)): entry (w, x2, k) = sign * trace * exp(log scales) as pair_out of
+ *   pepsgpu_nn_pair_slice_fermion; exactly 0.0 for "no candidate" and where walker_mask[w] == 0 (NULL: every walker).
+ * Every slot is traced with the launches of the per-call sequence in its order (two half steps and a dot, one candidate per walker), so
+ * the numbers are the per-call path's; a slot for which the host's mirror of the MPO's states shows no open walker launches nothing,
+ * closed walkers are skipped inside the chained float32 step and left zero by the store elsewhere; the window shifts at every position.
+ * A table whose slot 0 maps (up, down) and (down, up) to themselves gives the unreplaced trace of those walkers (psi_original :460-476).
+ * The caches end as the per-call sequence leaves them: GetBTenLeftCol == N - 2, GetBTenRightCol == N.
+ * Status PEPSGPU_EINVAL: NULL occ, pair_table or out, a walker that is not UP, the table checks above; PEPSGPU_ESTATE: no MPO set, an
+ * MPO given as explicit tensors, opp_level not in the DOWN stack, an active configuration override, a state of the row with a
+ * column-major variant.  Every check runs before a cache of the walker is released: a refused call leaves walker and context usable. */
+int pepsgpu_walker_pair_trace_slice(pepsgpu_ctx *ctx, int walker, int opp_level, int d, const int32_t *occ, const int32_t *pair_table,
+                                    const uint8_t *walker_mask, double *out);
+/* Completed pepsgpu_walker_pair_trace_slice calls of this process (all contexts).  Needs no device. */
+long pepsgpu_diag_walker_pair_slice_calls(void);
+/* The candidate kernel of pepsgpu_walker_pair_trace_slice and the patch kernel of pepsgpu_walker_set_mpo_excited_pair alone, on the
+ * caller's extended rows ext [n][cols] (states in [0, 2 d)) for the pair (col, col + 1): cand_out [n][2][2] (slot, site) the extended
+ * states under candidate k (the walker's own where it has none), skip_out [2][n] = 1 where the walker has no candidate k or
+ * walker_mask[w] == 0 (NULL: none masked), sign_out [n][2] as above; patched_out [n][cols] the rows after the patch of `slot`.
+ * Needs a device, no context. */
+int pepsgpu_diag_walker_pair_cand(int cols, int d, const int32_t *occ, const int32_t *pair_table, int n, const int32_t *ext, int col,
+                                  int slot, const uint8_t *walker_mask, int32_t *cand_out, int32_t *skip_out, int32_t *sign_out,
+                                  int32_t *patched_out);
 int pepsgpu_walker_evolve(pepsgpu_ctx *ctx, int walker);                                     /* Evolve(mpo)               :13-21  */
 int pepsgpu_walker_evolve_step(pepsgpu_ctx *ctx, int walker);                                /* EvolveStep()              :23-49  */
 int pepsgpu_walker_contract_row(pepsgpu_ctx *ctx, int walker, int opp_level, double *out);   /* ContractRow(mpo, opp)     :60-214 */

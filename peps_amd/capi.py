@@ -26,7 +26,7 @@ SYMBOLS = [
     "pepsgpu_walkers_set_configs", "pepsgpu_walkers_get_configs", "pepsgpu_n_walkers",
     "pepsgpu_grow_bmps_step", "pepsgpu_grow_full_bmps", "pepsgpu_grow_bmps_for_row", "pepsgpu_grow_bmps_for_col",
     "pepsgpu_shift_bmps_window", "pepsgpu_delete_inner_bmps", "pepsgpu_bmps_park", "pepsgpu_bmps_unpark", "pepsgpu_generate_bmps_approach",
-    "pepsgpu_sweep_slice_exchange", "pepsgpu_sweep_slice_exchange_tab", "pepsgpu_sweep_slice_fullspace", "pepsgpu_sweep_slice_tnn3", "pepsgpu_diag_tnn3_table", "pepsgpu_nn_exchange_slice", "pepsgpu_nn_exchange_slice_tab", "pepsgpu_onsite_slice", "pepsgpu_nnn_exchange_slice", "pepsgpu_diag_nnn_slice_calls", "pepsgpu_nnn_hop_slice_fermion", "pepsgpu_diag_nnn_hop_slice_calls", "pepsgpu_diag_fermion_hop_cand", "pepsgpu_nn_pair_slice_fermion", "pepsgpu_diag_pair_slice_calls", "pepsgpu_diag_pair_cand", "pepsgpu_nn_hop_slice_fermion", "pepsgpu_diag_hop_slice_calls", "pepsgpu_sweep_slice_sector", "pepsgpu_diag_sector_slice_calls", "pepsgpu_diag_sector_cand", "pepsgpu_link_exchange_slice", "pepsgpu_diag_link_slice_calls", "pepsgpu_diag_link_cand", "pepsgpu_walker_create", "pepsgpu_walker_clone", "pepsgpu_walker_destroy", "pepsgpu_walker_info", "pepsgpu_walker_set_mpo", "pepsgpu_walker_set_mpo_excited", "pepsgpu_walker_trace_slice", "pepsgpu_diag_walker_slice_calls", "pepsgpu_walker_evolve",
+    "pepsgpu_sweep_slice_exchange", "pepsgpu_sweep_slice_exchange_tab", "pepsgpu_sweep_slice_fullspace", "pepsgpu_sweep_slice_tnn3", "pepsgpu_diag_tnn3_table", "pepsgpu_nn_exchange_slice", "pepsgpu_nn_exchange_slice_tab", "pepsgpu_onsite_slice", "pepsgpu_nnn_exchange_slice", "pepsgpu_diag_nnn_slice_calls", "pepsgpu_nnn_hop_slice_fermion", "pepsgpu_diag_nnn_hop_slice_calls", "pepsgpu_diag_fermion_hop_cand", "pepsgpu_nn_pair_slice_fermion", "pepsgpu_diag_pair_slice_calls", "pepsgpu_diag_pair_cand", "pepsgpu_nn_hop_slice_fermion", "pepsgpu_diag_hop_slice_calls", "pepsgpu_sweep_slice_sector", "pepsgpu_diag_sector_slice_calls", "pepsgpu_diag_sector_cand", "pepsgpu_link_exchange_slice", "pepsgpu_diag_link_slice_calls", "pepsgpu_diag_link_cand", "pepsgpu_walker_create", "pepsgpu_walker_clone", "pepsgpu_walker_destroy", "pepsgpu_walker_info", "pepsgpu_walker_set_mpo", "pepsgpu_walker_set_mpo_excited", "pepsgpu_walker_trace_slice", "pepsgpu_diag_walker_slice_calls", "pepsgpu_walker_set_mpo_excited_pair", "pepsgpu_walker_pair_trace_slice", "pepsgpu_diag_walker_pair_slice_calls", "pepsgpu_diag_walker_pair_cand", "pepsgpu_walker_evolve",
     "pepsgpu_walker_evolve_step", "pepsgpu_walker_contract_row", "pepsgpu_walker_init_bten", "pepsgpu_walker_grow_bten_step",
     "pepsgpu_walker_shift_bten_window", "pepsgpu_walker_trace_with_bten", "pepsgpu_walker_clear_bten", "pepsgpu_walker_get_bmps_tensor",
     "pepsgpu_bmps_stack_size", "pepsgpu_get_bmps_tensor", "pepsgpu_init_bten", "pepsgpu_grow_full_bten",
@@ -149,6 +149,11 @@ def load_library(path=LIB_PATH):
     lib.pepsgpu_walker_trace_slice.argtypes = [vp, C.c_int, C.c_int, ip, u8p, dp]
     lib.pepsgpu_diag_walker_slice_calls.argtypes = []
     lib.pepsgpu_diag_walker_slice_calls.restype = C.c_long
+    lib.pepsgpu_walker_set_mpo_excited_pair.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, C.c_int, u8p, ip]
+    lib.pepsgpu_walker_pair_trace_slice.argtypes = [vp, C.c_int, C.c_int, C.c_int, ip, ip, u8p, dp]
+    lib.pepsgpu_diag_walker_pair_slice_calls.argtypes = []
+    lib.pepsgpu_diag_walker_pair_slice_calls.restype = C.c_long
+    lib.pepsgpu_diag_walker_pair_cand.argtypes = [C.c_int, C.c_int, ip, ip, C.c_int, ip, C.c_int, C.c_int, u8p, ip, ip, ip, ip]
     lib.pepsgpu_walker_evolve.argtypes = [vp, C.c_int]
     lib.pepsgpu_walker_evolve_step.argtypes = [vp, C.c_int]
     lib.pepsgpu_walker_contract_row.argtypes = [vp, C.c_int, C.c_int, dp]
@@ -1393,6 +1398,30 @@ def diag_walker_slice_calls():
     return int(lib().pepsgpu_diag_walker_slice_calls())
 
 
+def diag_walker_pair_slice_calls():
+    """completed pepsgpu_walker_pair_trace_slice calls of this process"""
+    return int(lib().pepsgpu_diag_walker_pair_slice_calls())
+
+
+def diag_walker_pair_cand(ext_rows, nf, pair_table, col, slot=0, mask=None):
+    """walker_pair_cand_kernel and walker_excite_pair_kernel alone: ext_rows [n][cols] extended states of the row-major order, nf [d],
+    pair_table [d * d][2][2], the pair (col, col + 1).  Returns (cand [n][2][2] (slot, site), skip [2][n], sign [n][2],
+    patched [n][cols] = the rows after the patch of `slot`)"""
+    e = np.ascontiguousarray(ext_rows, dtype=np.int32)
+    occ = np.ascontiguousarray(nf, dtype=np.int32)
+    tab = np.ascontiguousarray(pair_table, dtype=np.int32)
+    n, cols = e.shape
+    mk = None if mask is None else np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+    cand, skip = np.zeros((n, 2, 2), dtype=np.int32), np.zeros((2, n), dtype=np.int32)
+    sign, patched = np.zeros((n, 2), dtype=np.int32), np.zeros((n, cols), dtype=np.int32)
+    rc = lib().pepsgpu_diag_walker_pair_cand(cols, occ.size, _ip(occ), _ip(tab), n, _ip(e), col, slot,
+                                             None if mk is None else mk.ctypes.data_as(C.POINTER(C.c_uint8)), _ip(cand), _ip(skip),
+                                             _ip(sign), _ip(patched))
+    if rc != 0:
+        raise ValueError("diag_walker_pair_cand: status %d" % rc)
+    return cand, skip, sign, patched
+
+
 def diag_nnn_slice_calls():
     """completed pepsgpu_nnn_exchange_slice calls of this process"""
     return int(lib().pepsgpu_diag_nnn_slice_calls())
@@ -1582,6 +1611,34 @@ class Walker:
         out = np.zeros((c.n, c.cols), dtype=c._ot)
         c._ck(c._l.pepsgpu_walker_trace_slice(c._h, self.wid, opp_level, _ip(sm),
                                               None if mk is None else mk.ctypes.data_as(C.POINTER(C.c_uint8)), _dp(out)))
+        return out
+
+    def set_mpo_excited_pair(self, num, col, nf, pair_table, slot=0):
+        """the MPO becomes row `num` under the walkers' configurations with the pair (col, col + 1) replaced by candidate `slot` of
+        pair_table ([d * d][2][2] over physical states, nf [d] their fermion numbers), built on the device; returns (open [n] bool,
+        sign [n] = Sigma(S') / Sigma(S), 0 for none)"""
+        c = self.ctx
+        occ = np.ascontiguousarray(nf, dtype=np.int32)
+        tab = np.ascontiguousarray(pair_table, dtype=np.int32)
+        assert tab.size == 4 * occ.size ** 2, tab.shape
+        op, sg = np.zeros(c.n, dtype=np.uint8), np.zeros(c.n, dtype=np.int32)
+        c._ck(c._l.pepsgpu_walker_set_mpo_excited_pair(c._h, self.wid, num, col, occ.size, _ip(occ), _ip(tab), slot,
+                                                       op.ctypes.data_as(C.POINTER(C.c_uint8)), _ip(sg)))
+        return op.astype(bool), sg
+
+    def pair_trace_slice(self, opp_level, nf, pair_table, mask=None):
+        """InitBTenLeft(0) / InitBTenRight(1) and the left-to-right scan of TraceWithTwoSiteBTen + ShiftBTenWindow(RIGHT) over the row
+        of the current MPO in one call: [n][cols - 1][2], entry (w, x, k) = sign * the trace with the states of (x, x + 1) replaced by
+        candidate k of pair_table where mask[w] (None: every walker) and the candidate exists, exactly 0 elsewhere"""
+        c = self.ctx
+        occ = np.ascontiguousarray(nf, dtype=np.int32)
+        tab = np.ascontiguousarray(pair_table, dtype=np.int32)
+        assert tab.size == 4 * occ.size ** 2, tab.shape
+        mk = None if mask is None else np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        assert mk is None or mk.shape == (c.n,), mk.shape
+        out = np.zeros((c.n, c.cols - 1, 2), dtype=c._ot)
+        c._ck(c._l.pepsgpu_walker_pair_trace_slice(c._h, self.wid, opp_level, occ.size, _ip(occ), _ip(tab),
+                                                   None if mk is None else mk.ctypes.data_as(C.POINTER(C.c_uint8)), _dp(out)))
         return out
 
     def Evolve(self): self.ctx._ck(self.ctx._l.pepsgpu_walker_evolve(self.ctx._h, self.wid))

@@ -377,6 +377,50 @@ int pepsgpu_walker_trace_slice(pepsgpu_ctx *ctx, int walker, int opp_level, cons
   CTX_CALL(ctx->eng->walker_trace_slice(walker, opp_level, site_map, walker_mask, out));
 }
 long pepsgpu_diag_walker_slice_calls(void) { return pepsgpu::walker_slice_calls().load(); }
+// singlet_pair_correlation_measurement_mixin.h:376-401: the row of the reference bond with the pair injected, patched on the device
+int pepsgpu_walker_set_mpo_excited_pair(pepsgpu_ctx *ctx, int walker, int num, int col, int d, const int32_t *occ, const int32_t *pair_table,
+                                        int slot, uint8_t *open_out, int32_t *sign_out) {
+  CTX_CALL(ctx->eng->walker_set_mpo_excited_pair(walker, num, col, d, occ, pair_table, slot, open_out, sign_out));
+}
+// :446-519: the two-site traces of one target row
+int pepsgpu_walker_pair_trace_slice(pepsgpu_ctx *ctx, int walker, int opp_level, int d, const int32_t *occ, const int32_t *pair_table,
+                                    const uint8_t *walker_mask, double *out) {
+  CTX_CALL(ctx->eng->walker_pair_trace_slice(walker, opp_level, d, occ, pair_table, walker_mask, out));
+}
+long pepsgpu_diag_walker_pair_slice_calls(void) { return pepsgpu::walker_pair_slice_calls().load(); }
+// walker_pair_cand_kernel and walker_excite_pair_kernel alone on a caller's extended rows ext [n][cols] (row-major variants 0 / 1) for
+// the pair (col, col + 1): cand_out [n][2][2], skip_out [2][n], sign_out [n][2]; patched_out [n][cols] = the rows after the patch of `slot`
+int pepsgpu_diag_walker_pair_cand(int cols, int d, const int32_t *occ, const int32_t *pair_table, int n, const int32_t *ext, int col,
+                                  int slot, const uint8_t *walker_mask, int32_t *cand_out, int32_t *skip_out, int32_t *sign_out,
+                                  int32_t *patched_out) {
+  return guarded(nullptr, [&]() {
+    PG_REQUIRE(ext && cand_out && skip_out && sign_out && patched_out, 1, "null buffer");
+    PG_REQUIRE(cols >= 2 && n >= 1 && (double)n * cols < 2147483648.0, 1, "bad sizes");
+    PG_REQUIRE(col >= 0 && col + 1 < cols, 1, "the pair is outside the row");
+    PG_REQUIRE(slot == 0 || slot == 1, 1, "pair slot outside {0, 1}");
+    pepsgpu::WalkerPairMap maps[2] = {};
+    const unsigned occ_bits = pepsgpu::walker_pair_maps(d, 4 * d, occ, pair_table, &maps[0], &maps[1]);
+    const size_t ne = (size_t)n * cols;
+    for (size_t e = 0; e < ne; ++e) PG_REQUIRE(ext[e] >= 0 && ext[e] < 2 * d, 1, "extended state outside [0, 2 d)");
+    std::vector<int> hmask;
+    if (walker_mask) hmask.assign(walker_mask, walker_mask + n);
+    DevBufs m;
+    int *dtab = m.alloc<int>(ne, ext);
+    const int *dmask = walker_mask ? m.alloc<int>((size_t)n, hmask.data()) : nullptr;
+    int *dc = m.alloc<int>(8 * (size_t)n), *dk = dc + 4 * (size_t)n, *ds = dk + 2 * (size_t)n;
+    const dim3 grid((n + 255) / 256), block(256);
+    hipLaunchKernelGGL(pepsgpu::walker_pair_cand_kernel, grid, block, 0, 0, (const int *)dtab, cols, col, d, occ_bits, maps[0], maps[1],
+                       dmask, dc, dk, ds, n);
+    PG_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(pepsgpu::walker_excite_pair_kernel, grid, block, 0, 0, dtab, cols, col, d, occ_bits, maps[slot], n);
+    PG_CHECK_HIP(hipGetLastError());
+    PG_CHECK_HIP(hipDeviceSynchronize());
+    PG_CHECK_HIP(hipMemcpy(cand_out, dc, 4 * (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    PG_CHECK_HIP(hipMemcpy(skip_out, dk, 2 * (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    PG_CHECK_HIP(hipMemcpy(sign_out, ds, 2 * (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    PG_CHECK_HIP(hipMemcpy(patched_out, dtab, ne * sizeof(int), hipMemcpyDeviceToHost));
+  });
+}
 int pepsgpu_walker_evolve(pepsgpu_ctx *ctx, int walker) { CTX_CALL(ctx->eng->walker_evolve(walker)); }
 int pepsgpu_walker_evolve_step(pepsgpu_ctx *ctx, int walker) { CTX_CALL(ctx->eng->walker_evolve_step(walker)); }
 int pepsgpu_walker_contract_row(pepsgpu_ctx *ctx, int walker, int opp_level, double *out) {

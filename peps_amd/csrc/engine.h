@@ -191,6 +191,8 @@ struct EngineBase {
   virtual void walker_info(int id, int *pos, int *stack, int *lcol, int *rcol) = 0;
   virtual void walker_set_mpo(int id, int num, const int32_t *states, const double *tensors, int n_tensors) = 0;
   virtual void walker_set_mpo_excited(int id, int num, int col, const int32_t *state_map, uint8_t *open_out) = 0;
+  virtual void walker_set_mpo_excited_pair(int id, int num, int col, int d, const int32_t *occ, const int32_t *pair_table, int slot,
+                                           uint8_t *open_out, int32_t *sign_out) = 0;
   virtual void walker_evolve(int id) = 0;
   virtual void walker_evolve_step(int id) = 0;
   virtual void walker_contract_row(int id, int opp_level, double *out) = 0;
@@ -200,6 +202,8 @@ struct EngineBase {
   virtual void walker_trace(int id, int opp_level, int site_col, int two_site, const int32_t *states, const double *tensors,
                             int n_tensors, double *out) = 0;
   virtual void walker_trace_slice(int id, int opp_level, const int32_t *site_map, const uint8_t *walker_mask, double *out) = 0;
+  virtual void walker_pair_trace_slice(int id, int opp_level, int d, const int32_t *occ, const int32_t *pair_table,
+                                       const uint8_t *walker_mask, double *out) = 0;
   virtual void walker_clear_bten(int id) = 0;
   virtual void walker_get_tensor(int id, int idx, int *dims, double *out, double *logscale) = 0;
   virtual void profile_enable(int on) = 0;
@@ -1094,6 +1098,8 @@ class Engine : public EngineBase {
   void walker_info(int id, int *pos, int *stack, int *lcol, int *rcol) override;
   void walker_set_mpo(int id, int num, const int32_t *states, const double *tensors, int n_tensors) override;
   void walker_set_mpo_excited(int id, int num, int col, const int32_t *state_map, uint8_t *open_out) override;
+  void walker_set_mpo_excited_pair(int id, int num, int col, int d, const int32_t *occ, const int32_t *pair_table, int slot,
+                                   uint8_t *open_out, int32_t *sign_out) override;
   void walker_evolve(int id) override;
   void walker_evolve_step(int id) override;
   void walker_contract_row(int id, int opp_level, double *out) override;
@@ -1103,6 +1109,8 @@ class Engine : public EngineBase {
   void walker_trace(int id, int opp_level, int site_col, int two_site, const int32_t *states, const double *tensors, int n_tensors,
                     double *out) override;
   void walker_trace_slice(int id, int opp_level, const int32_t *site_map, const uint8_t *walker_mask, double *out) override;
+  void walker_pair_trace_slice(int id, int opp_level, int d, const int32_t *occ, const int32_t *pair_table, const uint8_t *walker_mask,
+                               double *out) override;
   void walker_clear_bten(int id) override;
   void walker_get_tensor(int id, int idx, int *dims, double *out, double *logscale) override;
 

@@ -39,6 +39,87 @@ __global__ void walker_trace_cand_kernel(const int *__restrict__ tab, int sites,
   skip[w] = (r == s || (mask && !mask[w])) ? 1 : 0;
 }
 
+// ---- pair moves on a walker's row (the singlet-pair correlation, singlet_pair_correlation_measurement_mixin.h:349-534) ----
+// One slot of a pair table over PHYSICAL states (the layout of pepsgpu_nn_pair_slice_fermion: [d * d][2][2], (-1, -1) for none) handed
+// to a kernel by value, as WalkerStateMap: v[(a * d + b) * 2 + site] of the slot, d <= WK_MAXD.  No upload of its own.
+constexpr int WK_MAXD = WK_MAXDP / 4;
+struct WalkerPairMap { signed char v[2 * WK_MAXD * WK_MAXD]; };
+
+// The candidate of the pair (e1, e2) of extended states on two sites adjacent in row-major order, by the rule of pair_cand_kernel
+// (engine_sweep.h): before = v1 ^ n(a), e1' = a' + d (before ^ n(a')), e2' = b' + d (before ^ n(a') ^ n(b')).  Returns the sign
+// Sigma(S') / Sigma(S) (+1: fermion number kept, -1: changed by +-2), 0 and (e1, e2) themselves for "no candidate".
+__device__ __host__ inline int walker_pair_apply(const WalkerPairMap &m, int d, unsigned occ_bits, int e1, int e2, int *c1, int *c2) {
+  const int a = e1 % d, b = e2 % d;
+  const int pa = m.v[2 * (a * d + b)], pb = m.v[2 * (a * d + b) + 1];
+  *c1 = e1; *c2 = e2;
+  if (pa < 0) return 0;
+  const int oa = (int)((occ_bits >> a) & 1u), ob = (int)((occ_bits >> b) & 1u);
+  const int na = (int)((occ_bits >> pa) & 1u), nb = (int)((occ_bits >> pb) & 1u);
+  const int before = ((e1 / d) & 1) ^ oa;
+  *c1 = pa + d * (before ^ na);
+  *c2 = pb + d * (before ^ na ^ nb);
+  return (na + nb == oa + ob) ? 1 : -1;
+}
+
+// The two-site patch of an excited row (walker_set_mpo_excited_pair): sites `site`, `site + 1` of every walker's table become the
+// candidate of the slot; a walker without it keeps its two states
+__global__ void walker_excite_pair_kernel(int *__restrict__ tab, int sites, int site, int d, unsigned occ_bits, WalkerPairMap map, int n) {
+  const int w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= n) return;
+  int *p = tab + (long)w * sites + site;
+  int c1, c2;
+  if (walker_pair_apply(map, d, occ_bits, p[0], p[1], &c1, &c2) != 0) { p[0] = c1; p[1] = c2; }
+}
+
+// The candidates of one position of walker_pair_trace_slice from the MPO's state table tab [n][sites]: for the sites `site`,
+// `site + 1` and the slots k = 0, 1 cand [n][2][2] (slot, site), sign [n][2], skip [2][n] != 0 (the convention of bten_step) where
+// the walker has no candidate k or is masked out (mask nullable)
+__global__ void walker_pair_cand_kernel(const int *__restrict__ tab, int sites, int site, int d, unsigned occ_bits, WalkerPairMap map0,
+                                        WalkerPairMap map1, const int *__restrict__ mask, int *__restrict__ cand,
+                                        int *__restrict__ skip, int *__restrict__ sign, int n) {
+  const int w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= n) return;
+  const int e1 = tab[(long)w * sites + site], e2 = tab[(long)w * sites + site + 1];
+  const bool off = mask && !mask[w];
+  for (int k = 0; k < 2; ++k) {
+    int c1, c2;
+    const int sg = walker_pair_apply(k ? map1 : map0, d, occ_bits, e1, e2, &c1, &c2);
+    cand[4 * (long)w + 2 * k] = c1;
+    cand[4 * (long)w + 2 * k + 1] = c2;
+    sign[2 * (long)w + k] = sg;
+    skip[(long)k * n + w] = (sg == 0 || off) ? 1 : 0;
+  }
+}
+
+// out[w][col] = sign[w * sstride] res[w] exp(lsum[w]) into a ZEROED [n][stride] table of AccT scalars (stored as doubles, complex
+// interleaved); a skipped walker keeps the zero of its entry
+template <typename AccT>
+__global__ void walker_pair_store_kernel(const AccT *__restrict__ res, const double *__restrict__ lsum, const int *__restrict__ sign,
+                                         int sstride, const int *__restrict__ skip, double *__restrict__ out, int stride, int col, int n) {
+  constexpr int ko = (int)(sizeof(AccT) / sizeof(double));
+  const int w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= n || skip[w]) return;
+  sw_put(out + ((long)w * stride + col) * ko, sw_scaled(res[w], (double)sign[(long)w * sstride] * exp(lsum[w])));
+}
+
+inline std::atomic<long> &walker_pair_slice_calls() {   // completed walker_pair_trace_slice calls (pepsgpu_diag_walker_pair_slice_calls)
+  static std::atomic<long> n{0};
+  return n;
+}
+
+// occ [d] and a pair table checked as require_pair_tables does (status 1); its two slots as kernel arguments m0 / m1
+inline unsigned walker_pair_maps(int d, int dp, const int32_t *occ, const int32_t *pair_table, WalkerPairMap *m0, WalkerPairMap *m1) {
+  PG_REQUIRE(occ && pair_table, 1, "BMPSWalker: null pair table");
+  PG_REQUIRE(d >= 1 && 4 * d == dp && d <= WK_MAXD, 1, "BMPSWalker: the context's physical dimension must be 4 d (extended states), d <= 8");
+  const unsigned occ_bits = require_pair_tables(d, occ, pair_table);
+  for (int ab = 0; ab < d * d; ++ab)
+    for (int q = 0; q < 2; ++q) {
+      m0->v[2 * ab + q] = (signed char)pair_table[4 * ab + q];
+      m1->v[2 * ab + q] = (signed char)pair_table[4 * ab + 2 + q];
+    }
+  return occ_bits;
+}
+
 inline std::atomic<long> &walker_slice_calls() {   // completed walker_trace_slice calls of the process (pepsgpu_diag_walker_slice_calls)
   static std::atomic<long> n{0};
   return n;
@@ -240,6 +321,46 @@ void Engine<T>::walker_set_mpo_excited(int id, int num, int col, const int32_t *
   w.mpo_cfg = (int *)arena_.alloc(sizeof(int) * (size_t)nw_ * sites);
   PG_CHECK_HIP(hipMemcpyAsync(w.mpo_cfg, cfg_, sizeof(int) * (size_t)nw_ * sites, hipMemcpyDeviceToDevice, stream_));
   hipLaunchKernelGGL(walker_excite_site_kernel, dim3((nw_ + 255) / 256), dim3(256), 0, stream_, w.mpo_cfg, sites, site, map, nw_);
+  PG_CHECK_HIP(hipGetLastError());
+  w.mpo_hrow.swap(hrow);
+}
+
+// The excited row of the singlet-pair correlation (singlet_pair_correlation_measurement_mixin.h:376-401: the MPO of row y1 with the
+// tensors of the reference bond replaced) as walker_set_mpo_excited names its row: the configuration table copied on the device and
+// ONE two-site patch, the extended states of the pair derived there; no upload, no synchronisation.  open_out / sign_out [n] from the
+// host mirror (nullable).  Afterwards the walker is as after walker_set_mpo(states) with that row.
+template <typename T>
+void Engine<T>::walker_set_mpo_excited_pair(int id, int num, int col, int d, const int32_t *occ, const int32_t *pair_table, int slot,
+                                            uint8_t *open_out, int32_t *sign_out) {
+  require_ready();
+  WalkerDev &w = walker_ref(id);
+  PG_REQUIRE(w.pos == UP, 1, "BMPSWalker: unsupported direction (the excited row is a row below an UP walker)");
+  PG_REQUIRE(num >= 0 && num < Ly_ && col >= 0 && col + 1 < Lx_, 1, "BMPSWalker: excited bond outside the row");
+  PG_REQUIRE(slot == 0 || slot == 1, 1, "BMPSWalker: pair slot outside {0, 1}");
+  WalkerPairMap maps[2] = {};
+  const unsigned occ_bits = walker_pair_maps(d, dp_, occ, pair_table, &maps[0], &maps[1]);
+  const WalkerPairMap &map = maps[slot];
+  const int N = Lx_, sites = Ly_ * Lx_, site = num * Lx_ + col;
+  std::vector<int> hrow((size_t)nw_ * N);
+  for (int wk = 0; wk < nw_; ++wk) {
+    const int *c = hcfg_.data() + (size_t)wk * sites + (size_t)num * Lx_;
+    for (int j = 0; j < N; ++j)
+      PG_REQUIRE(c[j] / d < 2, 3, "BMPSWalker: extended states of the column-major order in the row (rows: variants 0 / 1)");
+    std::copy(c, c + N, hrow.begin() + (size_t)wk * N);
+  }
+  for (int wk = 0; wk < nw_; ++wk) {
+    int *r = hrow.data() + (size_t)wk * N + col;
+    int c1, c2;
+    const int sg = walker_pair_apply(map, d, occ_bits, r[0], r[1], &c1, &c2);
+    r[0] = c1; r[1] = c2;
+    if (open_out) open_out[wk] = sg != 0;
+    if (sign_out) sign_out[wk] = sg;
+  }
+  walker_free_mpo(w);
+  w.mpo_num = num;
+  w.mpo_cfg = (int *)arena_.alloc(sizeof(int) * (size_t)nw_ * sites);
+  PG_CHECK_HIP(hipMemcpyAsync(w.mpo_cfg, cfg_, sizeof(int) * (size_t)nw_ * sites, hipMemcpyDeviceToDevice, stream_));
+  hipLaunchKernelGGL(walker_excite_pair_kernel, dim3((nw_ + 255) / 256), dim3(256), 0, stream_, w.mpo_cfg, sites, site, d, occ_bits, map, nw_);
   PG_CHECK_HIP(hipGetLastError());
   w.mpo_hrow.swap(hrow);
 }
@@ -578,6 +699,95 @@ void Engine<T>::walker_trace_slice(int id, int opp_level, const int32_t *site_ma
   PG_CHECK_HIP(hipMemcpyAsync(out, dval, sizeof(double) * kOut * (size_t)nw_ * N, hipMemcpyDeviceToHost, stream_));
   PG_CHECK_HIP(hipStreamSynchronize(stream_));
   walker_slice_calls() += 1;
+}
+
+// The target-row loop of the singlet-pair correlation (singlet_pair_correlation_measurement_mixin.h:446-519 on bmps_walker.h:216-463)
+// in one call: InitBTenLeft(opp, 0), InitBTenRight(opp, 1), then for x2 = 0 .. N - 2 TraceWithTwoSiteBTen at x2 with the states of
+// (x2, x2 + 1) replaced by candidate k of the pair table, k = 0, 1, and ShiftBTenWindow(RIGHT) while x2 < N - 2.  Each slot is the
+// two half steps and the dot of walker_trace, one candidate per walker -- the launches of the per-call sequence in its order, so the
+// f32 steps stay on the chained kernels and the numbers are the per-call path's; a slot for which the host mirror shows no open walker
+// (for the measurement: slot 1 always) launches nothing.  out [n][N - 1][2] = sign trace exp(log scales), exactly 0.0 for "no
+// candidate" and for masked walkers.  The caches end as the per-call sequence leaves them: lcol = N - 2, rcol = N (N >= 2).
+template <typename T>
+void Engine<T>::walker_pair_trace_slice(int id, int opp_level, int d, const int32_t *occ, const int32_t *pair_table,
+                                        const uint8_t *walker_mask, double *out) {
+  require_ready();
+  PG_REQUIRE(out, 1, "BMPSWalker::PairTraceSlice: null buffer");
+  WalkerDev &w = walker_ref(id);
+  WalkerPairMap maps[2] = {};
+  const unsigned occ_bits = walker_pair_maps(d, dp_, occ, pair_table, &maps[0], &maps[1]);
+  const BMPSDev &opp = walker_opposite(w, opp_level, "PairTraceSlice");
+  PG_REQUIRE(w.mpo_num < 0 || !w.mpo_tens, 3, "BMPSWalker::PairTraceSlice: the MPO is given as explicit tensors (it has no state to map)");
+  MpoScope scope(*this, w);                  // (no MPO set, configuration override: status 3 before anything is released)
+  const int N = Lx_, sites = Ly_ * Lx_, np = N - 1;
+  PG_REQUIRE(N >= 2, 1, "BMPSWalker::PairTraceSlice: a row of one site has no bond");
+  const bool mirrored = !w.mpo_cfg || !w.mpo_hrow.empty();
+  PG_REQUIRE(mirrored, 3, "BMPSWalker::PairTraceSlice: the MPO's states are not mirrored on the host");
+  auto hstate = [&](int wk, int x) {
+    return w.mpo_cfg ? w.mpo_hrow[(size_t)wk * N + x] : hcfg_[(size_t)wk * sites + (size_t)w.mpo_num * Lx_ + x];
+  };
+  for (int wk = 0; wk < nw_; ++wk)
+    for (int x = 0; x < N; ++x)
+      PG_REQUIRE(hstate(wk, x) / d < 2, 3, "BMPSWalker: extended states of the column-major order in the row (rows: variants 0 / 1)");
+  const int *dstates = w.mpo_cfg ? w.mpo_cfg : cfg_;
+  std::vector<int> hmask;
+  if (walker_mask) hmask.assign(walker_mask, walker_mask + nw_);
+  ArenaBuf<int> dmask(arena_, walker_mask ? (size_t)nw_ : 0);
+  if (dmask) PG_CHECK_HIP(hipMemcpyAsync(dmask, hmask.data(), sizeof(int) * nw_, hipMemcpyHostToDevice, stream_));
+  const size_t nval = kOut * (size_t)nw_ * np * 2;
+  ArenaBuf<double> dval(arena_, nval);                                    // value table [n][N - 1][2] of Acc scalars, zero = closed
+  PG_CHECK_HIP(hipMemsetAsync(dval, 0, sizeof(double) * nval, stream_));
+  ArenaBuf<int> dcand(arena_, 8 * (size_t)nw_);                           // candidates [n][2][2], skip [2][n], sign [n][2]
+  int *dskip = dcand + 4 * (size_t)nw_, *dsign = dskip + 2 * (size_t)nw_;
+  walker_init_side(w, opp, LEFT, 0);
+  walker_init_side(w, opp, RIGHT, 1);
+  auto lv = [](const BMPSDev &b, int j) -> const int * { return (int)b.live.size() > j ? b.live[j] : nullptr; };
+  const int gb = (nw_ + 255) / 256;
+  for (int x2 = 0; x2 < np; ++x2) {
+    bool any[2] = {false, false};
+    for (int k = 0; k < 2; ++k)
+      for (int wk = 0; wk < nw_ && !any[k]; ++wk) {
+        if (walker_mask && !walker_mask[wk]) continue;
+        int c1, c2;
+        any[k] = walker_pair_apply(maps[k], d, occ_bits, hstate(wk, x2), hstate(wk, x2 + 1), &c1, &c2) != 0;
+      }
+    if (any[0] || any[1]) {
+      hipLaunchKernelGGL(walker_pair_cand_kernel, dim3(gb), dim3(256), 0, stream_, dstates, sites, w.mpo_num * Lx_ + x2, d, occ_bits, maps[0],
+                         maps[1], (const int *)dmask, (int *)dcand, dskip, dsign, nw_);
+      PG_CHECK_HIP(hipGetLastError());
+    }
+    for (int k = 0; k < 2; ++k) {
+      if (!any[k]) continue;
+      ArenaScope ascope(arena_);               // (the temporaries of this trace; the caches grow outside it)
+      const int *skip = dskip + (size_t)k * nw_;
+      SiteSel sa{w.mpo_num, x2, dcand + 2 * k, 4}, sb{w.mpo_num, x2 + 1, dcand + 2 * k + 1, 4};
+      sa.base = sitps_ + (long)(w.mpo_num * Lx_ + x2) * dp_ * slot_;
+      sb.base = sitps_ + (long)(w.mpo_num * Lx_ + x2 + 1) * dp_ * slot_;
+      const int ja = N - 1 - x2, jb = N - 2 - x2;
+      const BTenDev &lb = w.btl[x2], &rb = w.btr[N - 2 - x2];
+      BTenDev t2 = bten_step(LEFT, lb, w.b.t[ja], sa, opp.t[x2], 1, false, 1, lv(w.b, ja), lv(w.b, ja + 1), lv(opp, x2), lv(opp, x2 + 1),
+                             skip);
+      BTenDev t3 = bten_step(LEFT, t2, w.b.t[jb], sb, opp.t[x2 + 1], 1, false, 1, lv(w.b, jb), lv(w.b, jb + 1), lv(opp, x2 + 1),
+                             lv(opp, x2 + 2), skip);
+      free_ten(t2.t);
+      double *lsum = zeros_f64();
+      add_logs(lsum, w.b.logscale, opp.logscale, lb.logscale, rb.logscale);
+      Acc *res = finish_dot_device(t3.t, 1, rb.t, 1, 1);
+      hipLaunchKernelGGL(walker_pair_store_kernel<Acc>, dim3(gb), dim3(256), 0, stream_, (const Acc *)res, (const double *)lsum,
+                         (const int *)dsign + k, 2, skip, (double *)dval, 2 * np, 2 * x2 + k, nw_);
+      PG_CHECK_HIP(hipGetLastError());
+      free_ten(t3.t);
+      arena_.free(res); arena_.free(lsum);
+    }
+    if (x2 < np - 1) {                         // ShiftBTenWindow(RIGHT)
+      arena_.free(w.btr.back().t.p); arena_.free(w.btr.back().logscale);
+      w.btr.pop_back(); w.rcol++;
+      walker_grow_left(w, opp);
+    }
+  }
+  PG_CHECK_HIP(hipMemcpyAsync(out, dval, sizeof(double) * nval, hipMemcpyDeviceToHost, stream_));
+  PG_CHECK_HIP(hipStreamSynchronize(stream_));
+  walker_pair_slice_calls() += 1;
 }
 
 // ContractRow (bmps_walker.h:60-214): <walker | mpo | opposite>.  The reference multiplies the columns right to left into a

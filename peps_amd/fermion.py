@@ -515,6 +515,169 @@ def tj_observables(ctx, state, configs, t, J, V=0.0, mu=0.0, t2=0.0, pair="slice
             "SC_bond_singlet_v": out["sc_v"].reshape(n, -1)}, np.array(psis)
 
 
+# ---- the singlet-pair correlation of the t-J models (model_solvers/base/singlet_pair_correlation_measurement_mixin.h) ----
+def sc_pair_corr_ref_bonds(rows, cols, ref_bonds=()):
+    """the reference bonds (y, x) measured, in output order (:193-212): all horizontal bonds of the rows above the last one, or the
+    selection without its out-of-lattice members sorted by (y, x)"""
+    if rows < 2 or cols < 2:
+        return []
+    if len(ref_bonds) == 0:
+        return [(y, x) for y in range(rows - 1) for x in range(cols - 1)]
+    return sorted((int(y), int(x)) for y, x in ref_bonds if 0 <= y < rows - 1 and 0 <= x < cols - 1)
+
+
+def sc_pair_corr_mapping(rows, cols, ref_bonds=()):
+    """GenerateSCPairCorrIndexMapping (:176-215): [(ref_y, ref_x, 0, tgt_y, tgt_x, 0)] per value of SC_singlet_pair_corr"""
+    return [(y1, x1, 0, y2, x2, 0) for y1, x1 in sc_pair_corr_ref_bonds(rows, cols, ref_bonds)
+            for y2 in range(y1 + 1, rows) for x2 in range(cols - 1)]
+
+
+def tj_pair_inject_table():
+    """(empty, empty) -> slot 0 (up, down), slot 1 (down, up): Delta+ on the reference bond"""
+    tab = -np.ones((9, 2, 2), dtype=np.int32)
+    tab[2 * 3 + 2] = ((0, 1), (1, 0))
+    return tab
+
+
+def tj_pair_remove_table():
+    """(up, down), (down, up) -> slot 0 (empty, empty): Delta on the target bond"""
+    tab = -np.ones((9, 2, 2), dtype=np.int32)
+    tab[0 * 3 + 1, 0] = (2, 2)
+    tab[1 * 3 + 0, 0] = (2, 2)
+    return tab
+
+
+def tj_pair_identity_table():
+    """(up, down), (down, up) -> slot 0 themselves: the unreplaced two-site trace of the target bond (psi_original)"""
+    tab = -np.ones((9, 2, 2), dtype=np.int32)
+    tab[0 * 3 + 1, 0] = (0, 1)
+    tab[1 * 3 + 0, 0] = (1, 0)
+    return tab
+
+
+def _pair_scan_by_calls(walker, bottom, ext_row, cfg_row, state, table):
+    """what Walker.pair_trace_slice returns without a mask, from InitBTenLeft / InitBTenRight / TraceWithTwoSiteBTen /
+    ShiftBTenWindow calls with the candidates built on the host; ext_row / cfg_row [n][cols] the extended / physical states of the
+    MPO's row"""
+    from .capi import RIGHT
+    n, cols = cfg_row.shape
+    d, nfs = state.d, np.asarray(state.nf) % 2
+    out = np.zeros((n, cols - 1, 2), dtype=np.complex128 if state.is_complex else np.float64)
+    walker.InitBTenLeft(bottom, 0)
+    walker.InitBTenRight(bottom, 1)
+    for x in range(cols - 1):
+        a, b = cfg_row[:, x], cfg_row[:, x + 1]
+        e1 = ext_row[:, x]
+        before = ((e1 // d) & 1) ^ nfs[a]
+        pc = table[a * d + b]                                 # [n][2][2]
+        for k in range(2):
+            has = pc[:, k, 0] >= 0
+            if not has.any():
+                continue
+            pa, pb = np.where(has, pc[:, k, 0], a), np.where(has, pc[:, k, 1], b)
+            c1, c2 = pa + d * (before ^ nfs[pa]), pb + d * (before ^ nfs[pa] ^ nfs[pb])
+            sign = np.where(nfs[pa] + nfs[pb] == nfs[a] + nfs[b], 1.0, -1.0)
+            tr = walker.TraceWithTwoSiteBTen(bottom, x, states=np.stack([c1, c2], axis=-1))
+            out[:, x, k] = np.where(has, sign * tr, 0.0)
+        if x < cols - 2:
+            walker.ShiftBTenWindow(bottom, RIGHT)
+    return out
+
+
+def tj_pair_correlation(ctx, state, configs, ref_bonds=(), scan="slice"):
+    """SC_singlet_pair_corr of MeasureSingletPairCorrelation (singlet_pair_correlation_measurement_mixin.h:349-534) for a batch of
+    configurations, driven from Python: [n][number of bond pairs] in the order of sc_pair_corr_mapping.
+
+    Convention (tj_observables): for the reference bond (y1, x1)-(y1, x1 + 1) and the target bond (y2, x2)-(y2, x2 + 1), y2 > y1, the
+    value is non-zero only for an (empty, empty) reference and an (up, down) / (down, up) target:
+        1/2 conj(rho_ud - rho_du) * (+1 for (up, down), -1 for (down, up)),  rho_x = psi(S: ref -> x, target -> (empty, empty)) / psi(S);
+    its |psi|^2-weighted mean is <Delta+_ref Delta_tgt>.  Both bonds are adjacent modes of the row-major order, so each move changes the
+    components of its two sites only and rho is the ratio of two-site traces of three walkers forked from up_stack[y1]: two evolved
+    through the row y1 with the pair injected, one through the row itself (psi(S) along the same path; shared by the reference bonds
+    of one y1).  Sigma(S') / Sigma(S) is -1 for the injection and -1 for the removal.
+    scan = "slice": set_mpo_excited_pair + one pair_trace_slice per walker and target row; "calls": set_mpo_states and the per-call
+    entries.  A reference bond that is (empty, empty) for no configuration of the batch creates no excited walker."""
+    from .capi import DOWN, UP
+    if scan not in ("slice", "calls"):
+        raise ValueError("tj_pair_correlation: scan must be 'slice' or 'calls'")
+    cfg = np.asarray(configs)
+    n, rows, cols = cfg.shape
+    dt = np.complex128 if state.is_complex else np.float64
+    bonds = sc_pair_corr_ref_bonds(rows, cols, ref_bonds)
+    mapping = sc_pair_corr_mapping(rows, cols, ref_bonds)
+    out = np.zeros((n, len(mapping)), dtype=dt)
+    if not bonds:
+        return out
+    nf = np.asarray(state.nf) % 2
+    inject, remove, ident = tj_pair_inject_table(), tj_pair_remove_table(), tj_pair_identity_table()
+    ext = state.ext_config(cfg, ROW)
+    ctx.set_configs(ext)
+    ctx.generate_bmps_approach(UP)
+    ctx.grow_full_bmps(UP)
+    max_ref_y = max(y for y, _ in bonds)
+    if ctx.bmps_stack_size(UP) <= max_ref_y:
+        raise RuntimeError("MeasureSingletPairCorrelation: UP BMPS stack insufficient.")
+    if ctx.bmps_stack_size(DOWN) < rows:
+        raise RuntimeError("MeasureSingletPairCorrelation: DOWN BMPS stack insufficient.")
+    is_pair = ((cfg[:, :, :-1] == 0) & (cfg[:, :, 1:] == 1)) | ((cfg[:, :, :-1] == 1) & (cfg[:, :, 1:] == 0))     # [n][rows][cols - 1]
+    tgt_sign = np.where(cfg[:, :, :-1] == 0, 1.0, -1.0)
+
+    def scan_rows(walker, y1, table, mask):
+        """the walker has absorbed rows [0, y1]: {y2: [n][cols - 1] slot 0 of the scan of row y2}"""
+        res = {}
+        for y2 in range(y1 + 1, rows):
+            if y2 > y1 + 1:
+                walker.set_mpo(y2 - 1)
+                walker.Evolve()
+            walker.set_mpo(y2)
+            if scan == "slice":
+                res[y2] = walker.pair_trace_slice(rows - 1 - y2, nf, table, mask)[:, :, 0]
+            else:
+                res[y2] = np.where(mask[:, None], _pair_scan_by_calls(walker, rows - 1 - y2, ext[:, y2, :], cfg[:, y2, :], state, table)[:, :, 0], 0.0)
+            walker.ClearBTen()
+        return res
+
+    pos = 0
+    psi_y1, psi_orig = -1, None
+    for y1, x1 in bonds:
+        npair = (rows - 1 - y1) * (cols - 1)
+        ref_valid = (cfg[:, y1, x1] == 2) & (cfg[:, y1, x1 + 1] == 2)
+        if not ref_valid.any():
+            pos += npair
+            continue
+        if psi_y1 != y1:                                      # the original walker: its numbers do not depend on x1
+            with ctx.get_walker(UP, level=y1) as w:
+                w.set_mpo(y1)
+                w.Evolve()
+                psi_orig, psi_y1 = scan_rows(w, y1, ident, np.ones(n, dtype=bool)), y1
+        over = []
+        for k in range(2):
+            with ctx.get_walker(UP, level=y1) as w:
+                if scan == "slice":
+                    opened, sign = w.set_mpo_excited_pair(y1, x1, nf, inject, slot=k)
+                    assert np.array_equal(opened, ref_valid) and np.all(sign[ref_valid] == -1)
+                else:
+                    new = cfg[:, y1, :].copy()
+                    new[ref_valid, x1], new[ref_valid, x1 + 1] = inject[8, k]
+                    full = cfg.copy()
+                    full[:, y1, :] = new
+                    w.set_mpo_states(y1, state.ext_config(full, ROW)[:, y1, :])
+                w.Evolve()
+                tr = scan_rows(w, y1, remove, ref_valid)      # sign of the removal applied; the injection's -1 here
+                over.append({y2: -v for y2, v in tr.items()})
+        for y2 in range(y1 + 1, rows):
+            open_ = ref_valid[:, None] & is_pair[:, y2, :]
+            psi = psi_orig[y2]
+            if np.any(psi[open_] == 0):
+                raise RuntimeError("MeasureSingletPairCorrelation: psi_original = 0 for sampled configuration.")
+            safe = np.where(open_, psi, 1.0)
+            val = 0.5 * np.conj((over[0][y2] - over[1][y2]) / safe) * tgt_sign[:, y2, :]
+            out[:, pos:pos + cols - 1] = np.where(open_, val, 0.0)
+            pos += cols - 1
+    assert pos == len(mapping)
+    return out
+
+
 # ---- the Hubbard model (square_hubbard_model.h; states 0 = up-down, 1 = up, 2 = down, 3 = empty, :18-23) ----
 HUBBARD_NF = (0, 1, 1, 0)                      # fermion parity of each state
 _HUB_UP, _HUB_DN = (1, 1, 0, 0), (1, 0, 1, 0)  # HubbardConfig2SpinCounts, square_hubbard_u1u1_updater.h:30-40

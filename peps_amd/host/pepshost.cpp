@@ -549,17 +549,37 @@ void fermion_measure_energy_impl(int rows, int cols, int D, int d, const int32_t
 // 2: SquaretJNNModel [t, J, mu] (the nearest-neighbour form: no diagonal-bond keys); 3: SquareHubbardModel [t, U, mu] (with
 // double_occupancy).  Output in the format of pepshost_measure: keys
 // "key:len;", every number of a complex state as a (re, im) pair. ----
+// SC_singlet_pair_corr of the t-J models (SingletPairCorrelationMixin): the switch and the selected reference bonds [n_bonds][2] = (y, x)
+// of the left site (none: every horizontal bond above the last row); the *_sc entries hand it over, the others leave it off
+struct SCPairArgs {
+  int on = 0, n_bonds = 0;
+  const int32_t *bonds = nullptr;
+  std::vector<std::pair<size_t, size_t>> selected(const char *who) const {
+    if (n_bonds < 0 || (n_bonds > 0 && !bonds)) throw std::invalid_argument(std::string(who) + ": reference bonds missing");
+    std::vector<std::pair<size_t, size_t>> out;
+    for (int k = 0; k < n_bonds; ++k) {
+      if (bonds[2 * k] < 0 || bonds[2 * k + 1] < 0) throw std::invalid_argument(std::string(who) + ": negative reference bond coordinate");
+      out.emplace_back((size_t)bonds[2 * k], (size_t)bonds[2 * k + 1]);
+    }
+    return out;
+  }
+};
 template <typename Fn>
-auto with_fermion_measurement_model(const char *who, int model, const double *prm, int n_prm, Fn &&fn) {
+auto with_fermion_measurement_model(const char *who, int model, const double *prm, int n_prm, Fn &&fn, const SCPairArgs &sc = {}) {
   if (model < 0 || model > 3 || n_prm < 0 || n_prm > 5 || (n_prm > 0 && !prm))
     throw std::invalid_argument(std::string(who) + ": model 0 (spinless), 1 (tj), 2 (tjnn) or 3 (hubbard), at most 5 parameters");
+  if (sc.on && model != 1 && model != 2) throw std::invalid_argument(std::string(who) + ": SC_singlet_pair_corr is an observable of the t-J models");
   double p[5] = {0, 0, 0, 0, 0};
   std::copy(prm, prm + n_prm, p);
+  auto with_sc = [&](auto &m) {
+    if (sc.on) { m.SetEnableSingletPairCorrelation(true); m.SetSelectedRefBonds(sc.selected(who)); }
+    return fn(m);
+  };
   if (model == 0) { SquareSpinlessFermion m(p[0], p[2], p[1]); return fn(m); }
-  if (model == 1) { SquaretJVModel m(p[0], p[4], p[1], p[2], p[3]); return fn(m); }
+  if (model == 1) { SquaretJVModel m(p[0], p[4], p[1], p[2], p[3]); return with_sc(m); }
   if (model == 3) { SquareHubbardModel m(p[0], p[1], p[2]); return fn(m); }      // [t, U, mu]
   SquaretJNNModel m(p[0], p[1], p[2]);
-  return fn(m);
+  return with_sc(m);
 }
 struct KeyedValues {            // the output of the three entries below
   std::string keys;
@@ -580,7 +600,7 @@ struct KeyedValues {            // the output of the three entries below
 // EvaluateObservables on a batch of configurations: per key [walker][len], then psi_mean [walker] and psi_rel_err [walker]
 template <typename TenElemT>
 void fermion_observables_impl(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype, const double *sitps_ext_flat, int n,
-                              const int32_t *configs, int model, int n_prm, const double *prm, KeyedValues &out) {
+                              const int32_t *configs, int model, int n_prm, const double *prm, KeyedValues &out, const SCPairArgs &sc = {}) {
   SplitIndexTPST<TenElemT> sitps = make_state_t<TenElemT>(rows, cols, D, 4 * d, sitps_ext_flat);
   FermionDecoration dec;
   dec.nf.assign(nf, nf + d);
@@ -596,13 +616,13 @@ void fermion_observables_impl(int rows, int cols, int D, int d, const int32_t *n
     for (const auto &v : psi.psi_mean) out.push(v);
     for (double v : psi.psi_rel_err) out.push(TenElemT(v));
     return 0;
-  });
+  }, sc);
 }
 // ExactSumMeasurer, the share of one rank: values = [weight | per key the raw weighted sums] (pepshost_exact_sum_measure_partial)
 template <typename TenElemT>
 void fermion_exact_sum_measure_partial_impl(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype, const double *sitps_ext_flat,
                                             const int32_t *all_configs, int n_configs, int model, int n_prm, const double *prm, int rank,
-                                            int size, int batch, KeyedValues &out) {
+                                            int size, int batch, KeyedValues &out, const SCPairArgs &sc = {}) {
   if (n_configs < 1 || !all_configs || batch < 1 || size < 1 || rank < 0 || rank >= size)
     throw std::invalid_argument("pepshost_fermion_exact_sum_measure_partial: configurations, batch >= 1 and 0 <= rank < size are required");
   if (rank >= n_configs) { out.vals.assign(1, 0.0); return; }          // a rank without configurations contributes nothing
@@ -617,7 +637,7 @@ void fermion_exact_sum_measure_partial_impl(int rows, int cols, int D, int d, co
     const auto res = ExactSumMeasurer(sitps, all, contractor, m, rank, size, (size_t)batch, capture, nullptr, &dec);
     for (const auto &kv : res) out.keys += kv.first + ":" + std::to_string(kv.second.size()) + ";";
     return 0;
-  });
+  }, sc);
 }
 // MCPEPSMeasurer with the exchange updater: per key mean [len] and standard error [len] across the walkers, then the psi summary of the
 // last sample.  Warm-up, samples and random streams as fermion_measure_energy_impl (no rescaling of the state), so energy_samples_out
@@ -625,7 +645,8 @@ void fermion_exact_sum_measure_partial_impl(int rows, int cols, int D, int d, co
 template <typename TenElemT>
 void fermion_measure_impl(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype, const double *sitps_ext_flat, int n,
                           int32_t *configs, const uint64_t *seeds, int warmup_sweeps, int n_samples, int sweeps_between, int model, int n_prm,
-                          const double *prm, KeyedValues &out, double *energy_samples_out, double *accept_out, int updater = 0) {
+                          const double *prm, KeyedValues &out, double *energy_samples_out, double *accept_out, int updater = 0,
+                          const SCPairArgs &sc = {}) {
   if (n_samples < 1 || warmup_sweeps < 0 || sweeps_between < 0 || !seeds || !configs)
     throw std::invalid_argument("pepshost_fermion_measure: seeds, configurations and n_samples >= 1 are required");
   if (updater != 0 && updater != 3) throw std::invalid_argument("pepshost_fermion_measure: updater must be 0 (exchange) or 3 (hubbard_u1u1)");
@@ -663,7 +684,7 @@ void fermion_measure_impl(int rows, int cols, int D, int d, const int32_t *nf, i
       report(meas);
     }
     return 0;
-  });
+  }, sc);
   std::copy(comp.config.data(), comp.config.data() + (size_t)n * rows * cols, configs);
 }
 
@@ -1477,6 +1498,70 @@ int pepshost_fermion_measure_updater(int rows, int cols, int D, int d, const int
       fermion_measure_impl<double>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, n, configs, seeds, warmup_sweeps, n_samples, sweeps_between,
                                    model, n_prm, prm, out, energy_samples_out, accept_out, updater);
     out.write("pepshost_fermion_measure_updater", keys_out, keys_cap, values_out, values_cap, values_len);
+  });
+}
+// The three entries above with SC_singlet_pair_corr of the t-J models (model 1 / 2; SingletPairCorrelationMixin): sc_pair_corr != 0
+// enables it, ref_bonds [n_ref_bonds][2] = (y, x) of the left site of the selected reference bonds (n_ref_bonds == 0: all).  With
+// sc_pair_corr == 0 they are the entries above.
+int pepshost_fermion_observables_sc(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype, const double *sitps_ext_flat, int n,
+                                    const int32_t *configs, int model, int n_prm, const double *prm, char *keys_out, int keys_cap,
+                                    double *values_out, long values_cap, long *values_len, int sc_pair_corr, int n_ref_bonds,
+                                    const int32_t *ref_bonds) {
+  return guarded([&]() {
+    KeyedValues out;
+    const SCPairArgs sc{sc_pair_corr, n_ref_bonds, ref_bonds};
+    if (dtype == PEPSGPU_C128) fermion_observables_impl<QLTEN_Complex>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, n, configs, model, n_prm, prm, out, sc);
+    else fermion_observables_impl<double>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, n, configs, model, n_prm, prm, out, sc);
+    out.write("pepshost_fermion_observables_sc", keys_out, keys_cap, values_out, values_cap, values_len);
+  });
+}
+int pepshost_fermion_exact_sum_measure_partial_sc(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype,
+                                                  const double *sitps_ext_flat, const int32_t *all_configs, int n_configs, int model, int n_prm,
+                                                  const double *prm, int rank, int size, int batch, char *keys_out, int keys_cap,
+                                                  double *values_out, long values_cap, long *values_len, int sc_pair_corr, int n_ref_bonds,
+                                                  const int32_t *ref_bonds) {
+  return guarded([&]() {
+    KeyedValues out;
+    const SCPairArgs sc{sc_pair_corr, n_ref_bonds, ref_bonds};
+    if (dtype == PEPSGPU_C128)
+      fermion_exact_sum_measure_partial_impl<QLTEN_Complex>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, all_configs, n_configs, model, n_prm,
+                                                            prm, rank, size, batch, out, sc);
+    else
+      fermion_exact_sum_measure_partial_impl<double>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, all_configs, n_configs, model, n_prm, prm,
+                                                     rank, size, batch, out, sc);
+    out.write("pepshost_fermion_exact_sum_measure_partial_sc", keys_out, keys_cap, values_out, values_cap, values_len);
+  });
+}
+int pepshost_fermion_measure_sc(int rows, int cols, int D, int d, const int32_t *nf, int chi, int dtype, const double *sitps_ext_flat, int n,
+                                int32_t *configs, const uint64_t *seeds, int warmup_sweeps, int n_samples, int sweeps_between, int model,
+                                int n_prm, const double *prm, char *keys_out, int keys_cap, double *values_out, long values_cap,
+                                long *values_len, double *energy_samples_out, double *accept_out, int sc_pair_corr, int n_ref_bonds,
+                                const int32_t *ref_bonds) {
+  return guarded([&]() {
+    KeyedValues out;
+    const SCPairArgs sc{sc_pair_corr, n_ref_bonds, ref_bonds};
+    if (dtype == PEPSGPU_C128)
+      fermion_measure_impl<QLTEN_Complex>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, n, configs, seeds, warmup_sweeps, n_samples,
+                                          sweeps_between, model, n_prm, prm, out, energy_samples_out, accept_out, 0, sc);
+    else
+      fermion_measure_impl<double>(rows, cols, D, d, nf, chi, dtype, sitps_ext_flat, n, configs, seeds, warmup_sweeps, n_samples, sweeps_between,
+                                   model, n_prm, prm, out, energy_samples_out, accept_out, 0, sc);
+    out.write("pepshost_fermion_measure_sc", keys_out, keys_cap, values_out, values_cap, values_len);
+  });
+}
+// GenerateSCPairCorrIndexMapping: out [n_pairs][6] = (ref_y, ref_x, 0, tgt_y, tgt_x, 0) in the order of the values; *n_pairs is set even
+// when out is NULL or cap (in pairs) is too small (then nothing is written and the status is out of range); host only
+int pepshost_sc_pair_corr_mapping(int rows, int cols, int n_ref_bonds, const int32_t *ref_bonds, int32_t *out, long cap, long *n_pairs) {
+  return guarded([&]() {
+    if (rows < 0 || cols < 0 || !n_pairs) throw std::invalid_argument("pepshost_sc_pair_corr_mapping: bad sizes or null count");
+    const SCPairArgs sc{1, n_ref_bonds, ref_bonds};
+    const auto mapping = SingletPairCorrelationMixin<SquaretJVModel>::GenerateSCPairCorrIndexMapping((size_t)rows, (size_t)cols,
+                                                                                                      sc.selected("pepshost_sc_pair_corr_mapping"));
+    *n_pairs = (long)mapping.size();
+    if (!out) return;
+    if ((long)mapping.size() > cap) throw std::out_of_range("pepshost_sc_pair_corr_mapping: output buffer too small");
+    for (size_t i = 0; i < mapping.size(); ++i)
+      for (size_t q = 0; q < 6; ++q) out[6 * i + q] = (int32_t)mapping[i][q];
   });
 }
 // The sector table of MCUpdateSquareNNHubbardU1U1OBC (pepsgpu_sweep_slice_sector), out [16][10]; host only

@@ -403,6 +403,29 @@ class BMPSContractorT {
                ctx_);
       return out;
     }
+    // The excited row of the singlet-pair correlation (singlet_pair_correlation_measurement_mixin.h:376-401) built on the device: row
+    // `num` of a fermionic context with the pair (col, col + 1) replaced by candidate `slot` of pair_table ([d * d][2][2] over
+    // physical states, occ [d] their fermion numbers).  Returns open[w] = the walker has the candidate; sign (optional) receives
+    // Sigma(S') / Sigma(S) per walker, 0 for none.  Same walker afterwards as SetMPOStates with that row.
+    std::vector<uint8_t> SetMPOExcitedPair(size_t num, size_t col, const std::vector<int32_t> &occ, const std::vector<int32_t> &pair_table,
+                                           int slot, std::vector<int32_t> *sign = nullptr) {
+      std::vector<uint8_t> open(n_);
+      std::vector<int32_t> sg(n_);
+      check_rc(pepsgpu_walker_set_mpo_excited_pair(ctx_, id_, (int)num, (int)col, (int)occ.size(), occ.data(), pair_table.data(), slot,
+                                                   open.data(), sg.data()), ctx_);
+      if (sign) sign->swap(sg);
+      return open;
+    }
+    // The scan of one target row (:446-519) in one call: InitBTenLeft(opp, 0), InitBTenRight(opp, 1), then left to right
+    // TraceWithTwoSiteBTen with the pair's states replaced by candidate k of pair_table + ShiftBTenWindow(RIGHT).  [w][x2][k]: sign *
+    // trace where mask[w] (empty: every walker) and the candidate exists, exactly 0 elsewhere.
+    std::vector<TenElemT> PairTraceSlice(size_t opp_level, const std::vector<int32_t> &occ, const std::vector<int32_t> &pair_table,
+                                         const std::vector<uint8_t> &mask = {}) {
+      std::vector<TenElemT> out(n_ * (cols_ - 1) * 2);
+      check_rc(pepsgpu_walker_pair_trace_slice(ctx_, id_, (int)opp_level, (int)occ.size(), occ.data(), pair_table.data(),
+                                               mask.empty() ? nullptr : mask.data(), dptr(out.data())), ctx_);
+      return out;
+    }
     void Evolve() { check_rc(pepsgpu_walker_evolve(ctx_, id_), ctx_); }
     std::vector<TenElemT> ContractRow(size_t opp_level) const {
       std::vector<TenElemT> out(n_);
@@ -1827,6 +1850,7 @@ struct ObservableMeta {                                        // model_measurem
   std::string key, description;
   std::vector<size_t> shape;
   std::vector<std::string> index_labels;
+  std::function<std::string(size_t, size_t)> coord_generator = {};   // (ly, lx) -> the text of stats/<key>_coords.txt, or empty
 };
 // per walker (model_measurement_solver.h:95-98; PsiConsistencySummary<TenElemT>: psi_mean has the element type, psi_rel_err is real)
 template <typename TenElemT>
@@ -1918,6 +1942,10 @@ template <typename U, typename = void> struct IsFermionicModel : std::false_type
 template <typename U> struct IsFermionicModel<U, std::void_t<decltype(U::kFermionicModel)>> : std::bool_constant<U::kFermionicModel> {};
 template <typename U, typename = void> struct HasSCMeasurement : std::false_type {};
 template <typename U> struct HasSCMeasurement<U, std::void_t<decltype(U::enable_sc_measurement)>> : std::bool_constant<U::enable_sc_measurement> {};
+// ... and one with the SingletPairCorrelationMixin reports SC_singlet_pair_corr when that is enabled (off by default: nothing changes)
+template <typename U, typename = void> struct HasSCPairCorrelation : std::false_type {};
+template <typename U>
+struct HasSCPairCorrelation<U, std::void_t<decltype(std::declval<const U &>().IsSingletPairCorrelationEnabled())>> : std::true_type {};
 
 template <class ModelType, bool has_nnn_interaction = true>
 class SquareNNNModelMeasurementSolver {
@@ -2045,6 +2073,15 @@ class SquareNNNModelMeasurementSolver {
     };
     comp.SetOrder(ROW_MAJOR);
     c.GenerateBMPSApproach(UP);
+    if constexpr (HasSCPairCorrelation<ModelType>::value) {
+      // SC_singlet_pair_corr inside the row-major phase: its walkers fork from every level of the UP stack and close on every level of
+      // the DOWN stack, so the UP stack is grown in full for it and cut back to the vacuum the row pass starts from
+      if (derived->IsSingletPairCorrelationEnabled()) {
+        c.GrowFullBMPS(UP);
+        derived->MeasureSingletPairCorrelation(comp, out);
+        c.DeleteInnerBMPS(UP);
+      }
+    }
     for (size_t row = 0; row < ly; ++row) {
       if (use_slice) slice_pass(HORIZONTAL, row); else hook_pass(HORIZONTAL, row);
       if (row + 1 < ly) c.ShiftBMPSWindow(DOWN);
@@ -2240,6 +2277,7 @@ class SquareNNNModelMeasurementSolver {
       out.push_back({"SC_bond_singlet_h", "Bond singlet SC (horizontal) avg(conj(delta_dag), delta)", {ly, lx > 0 ? lx - 1 : 0}, {"bond_y", "bond_x"}});
       out.push_back({"SC_bond_singlet_v", "Bond singlet SC (vertical) avg(conj(delta_dag), delta)", {ly > 0 ? ly - 1 : 0, lx}, {"bond_y", "bond_x"}});
     }
+    if constexpr (HasSCPairCorrelation<ModelType>::value) static_cast<const ModelType *>(this)->DescribeSingletPairCorrelation(out, ly, lx);
     return out;
   }
  private:
@@ -3040,13 +3078,230 @@ class SquareSpinlessFermion : public SquareNNModelEnergySolver<SquareSpinlessFer
   double t_, t2_, V_;
 };
 
+// SingletPairCorrelationMixin (base/singlet_pair_correlation_measurement_mixin.h): SC_singlet_pair_corr, the pair-pair correlation
+// <Delta+(ref bond) Delta(target bond)> between the horizontal reference bond (y1, x1)-(y1, x1 + 1) and every horizontal target bond
+// (y2, x2)-(y2, x2 + 1) with y2 > y1; t-J states 0 up, 1 down, 2 empty.  The reference's MeasureSingletPairCorrelation throws ("Fermion
+// sign is NOT correctly handled", :279-297: its graded contraction traces out the parity indices); the algorithm below the throw
+// (:349-534) runs here unchanged, because a fermionic state is an ordinary contraction of sign-decorated components times
+// Sigma(N_f) and both bonds are pairs of modes adjacent in the row-major order: a pair move changes the components of its two sites
+// only and keeps the parity behind them, so the rows below need no change.
+//   value = 1/2 conj(rho_ud - rho_du) * (+1 for a target (up, down), -1 for (down, up)),
+//   rho_x = psi(S with ref -> x, target -> (empty, empty)) / psi(S) = (-1)(-1) excited trace / original trace
+// for an (empty, empty) reference bond and an (up, down) / (down, up) target, 0 otherwise: Sigma(S') / Sigma(S) is -1 for the
+// injection and -1 for the removal.  tests/test_cpu_pair_corr.py pins the value to the dense Delta+_ref Delta_tgt.
+// Schedule: per reference bond two excited walkers forked from up_stack[y1] and evolved through the row with the pair injected; the
+// original walker (psi(S) along the same path, so that truncation errors cancel in the ratio) is shared by the reference bonds of
+// one y1 -- its numbers do not depend on x1.  A reference bond that is (empty, empty) for no walker of the batch creates no walker.
+// Device slices: SetMPOExcitedPair + ONE PairTraceSlice per walker and target row; PEPSHOST_NO_DEVICE_SWEEP=1: SetMPOStates,
+// InitBTenLeft / InitBTenRight, TraceWithTwoSiteBTen, ShiftBTenWindow.
+template <class Model>
+class SingletPairCorrelationMixin {
+ public:
+  void SetEnableSingletPairCorrelation(bool enable) { enable_singlet_pair_correlation_ = enable; }
+  bool IsSingletPairCorrelationEnabled() const { return enable_singlet_pair_correlation_; }
+  void SetSelectedRefBonds(std::vector<std::pair<size_t, size_t>> bonds) { selected_ref_bonds_ = std::move(bonds); }   // (y, x) of the left site
+  const std::vector<std::pair<size_t, size_t>> &GetSelectedRefBonds() const { return selected_ref_bonds_; }
+  // the reference bonds measured, in output order (:193-212): all of them, or the selection without its out-of-lattice members sorted
+  static std::vector<std::pair<size_t, size_t>> ValidRefBonds(size_t Ly, size_t Lx, const std::vector<std::pair<size_t, size_t>> &ref_bonds = {}) {
+    std::vector<std::pair<size_t, size_t>> out;
+    if (Ly < 2 || Lx < 2) return out;
+    if (ref_bonds.empty()) {
+      for (size_t y1 = 0; y1 + 1 < Ly; ++y1)
+        for (size_t x1 = 0; x1 + 1 < Lx; ++x1) out.emplace_back(y1, x1);
+      return out;
+    }
+    for (const auto &b : ref_bonds)
+      if (b.first < Ly - 1 && b.second < Lx - 1) out.push_back(b);
+    std::sort(out.begin(), out.end());
+    return out;
+  }
+  static size_t ComputeNumSCPairs(size_t Ly, size_t Lx, const std::vector<std::pair<size_t, size_t>> &ref_bonds = {}) {   // :136-160
+    size_t count = 0;
+    for (const auto &b : ValidRefBonds(Ly, Lx, ref_bonds)) count += (Ly - 1 - b.first) * (Lx - 1);
+    return count;
+  }
+  // {ref_y, ref_x, 0, tgt_y, tgt_x, 0} per value (:176-215)
+  static std::vector<std::array<size_t, 6>> GenerateSCPairCorrIndexMapping(size_t Ly, size_t Lx,
+                                                                           const std::vector<std::pair<size_t, size_t>> &ref_bonds = {}) {
+    std::vector<std::array<size_t, 6>> mapping;
+    for (const auto &b : ValidRefBonds(Ly, Lx, ref_bonds))
+      for (size_t y2 = b.first + 1; y2 < Ly; ++y2)
+        for (size_t x2 = 0; x2 + 1 < Lx; ++x2) mapping.push_back({b.first, b.second, 0, y2, x2, 0});
+    return mapping;
+  }
+  static std::string GenerateSCPairCorrCoordString(size_t Ly, size_t Lx, const std::vector<std::pair<size_t, size_t>> &ref_bonds = {}) {   // :233-245
+    const auto mapping = GenerateSCPairCorrIndexMapping(Ly, Lx, ref_bonds);
+    std::ostringstream oss;
+    oss << "# idx ref_y ref_x ref_orient tgt_y tgt_x tgt_orient\n";
+    for (size_t i = 0; i < mapping.size(); ++i) {
+      const auto &m = mapping[i];
+      oss << i << " " << m[0] << " " << m[1] << " " << m[2] << " " << m[3] << " " << m[4] << " " << m[5] << "\n";
+    }
+    return oss.str();
+  }
+  void DescribeSingletPairCorrelation(std::vector<ObservableMeta> &out, size_t ly, size_t lx) const {   // square_tJ_model.h:677-683
+    if (!enable_singlet_pair_correlation_) return;
+    const auto ref_bonds = selected_ref_bonds_;
+    out.push_back({"SC_singlet_pair_corr", "Singlet pair correlation <Delta^dag Delta> values.", {ComputeNumSCPairs(ly, lx, ref_bonds)},
+                   {"pair_idx"}, [ref_bonds](size_t ly_, size_t lx_) { return GenerateSCPairCorrCoordString(ly_, lx_, ref_bonds); }});
+  }
+  // pair tables over physical states ([3 * 3][2][2], (-1, -1) for none): Delta+ on an (empty, empty) bond (slot 0 (up, down), slot 1
+  // (down, up)); Delta on an (up, down) / (down, up) bond (slot 0); the identity on those two (slot 0: psi_original)
+  static std::vector<int32_t> PairTableOf(int kind) {
+    std::vector<int32_t> tab(9 * 4, -1);
+    auto set = [&](int a, int b, int k, int pa, int pb) { tab[((a * 3 + b) * 2 + k) * 2] = pa; tab[((a * 3 + b) * 2 + k) * 2 + 1] = pb; };
+    if (kind == 0) { set(2, 2, 0, 0, 1); set(2, 2, 1, 1, 0); }
+    else if (kind == 1) { set(0, 1, 0, 2, 2); set(1, 0, 0, 2, 2); }
+    else { set(0, 1, 0, 0, 1); set(1, 0, 0, 1, 0); }
+    return tab;
+  }
+  // The component is in ROW_MAJOR order, the UP stack reaches the last reference row and the DOWN stack is full.
+  template <typename TenElemT>
+  void MeasureSingletPairCorrelation(TPSWaveFunctionComponentT<TenElemT> &comp, ObservableMapT<TenElemT> &out) const {
+    if (!enable_singlet_pair_correlation_) return;
+    auto &c = comp.contractor;
+    const size_t Ly = c.rows(), Lx = c.cols(), n = comp.config.walkers();
+    const auto bonds = ValidRefBonds(Ly, Lx, selected_ref_bonds_);
+    if (bonds.empty()) { out.make("SC_singlet_pair_corr", 0); return; }   // (the key DescribeObservables announces, with its shape {0})
+    if (!comp.fermion || comp.order != ROW_MAJOR)
+      throw std::logic_error("MeasureSingletPairCorrelation: needs the fermionic decoration in row-major order");
+    const FermionDecoration &fd = *comp.fermion;
+    if (fd.d() != 3) throw std::logic_error("MeasureSingletPairCorrelation: the t-J states (up, down, empty) are expected");
+    const size_t per = ComputeNumSCPairs(Ly, Lx, selected_ref_bonds_), np = Lx - 1, d = fd.d();
+    auto &corr = out.make("SC_singlet_pair_corr", per);
+    const size_t max_ref_y = bonds.back().first, n_up = c.BMPSStackSize(UP), n_down = c.BMPSStackSize(DOWN);
+    if (n_up <= max_ref_y)
+      throw std::runtime_error("MeasureSingletPairCorrelation: UP BMPS stack insufficient. Need depth " + std::to_string(max_ref_y + 1) +
+                               ", got " + std::to_string(n_up) +
+                               ". Call contractor.GrowFullBMPS(tn, UP) after setting truncation params before measurement.");
+    const bool dev_slice = DeviceSlicesEnabled();
+    std::vector<int32_t> occ(fd.d());
+    for (size_t s = 0; s < occ.size(); ++s) occ[s] = fd.n((int32_t)s);
+    const std::vector<int32_t> inject = PairTableOf(0), remove = PairTableOf(1), ident = PairTableOf(2);
+    auto is_pair = [&](size_t w, size_t y, size_t x) {
+      const int32_t a = comp.config(w, {y, x}), b = comp.config(w, {y, x + 1});
+      return (a == 0 && b == 1) || (a == 1 && b == 0);
+    };
+    // slot 0 of the scan of row y2 for the walkers of `mask`: sign * two-site trace [w][x2], 0 where the table has no candidate
+    auto scan_row = [&](typename BMPSContractorT<TenElemT>::BMPSWalker &walker, size_t y2, const std::vector<int32_t> &table,
+                        const std::vector<uint8_t> &mask) {
+      const size_t bottom = Ly - 1 - y2;
+      if (bottom >= n_down)
+        throw std::runtime_error("MeasureSingletPairCorrelation: DOWN BMPS stack insufficient. Need depth " + std::to_string(bottom + 1) +
+                                 ", got " + std::to_string(n_down) +
+                                 ". Call contractor.GrowFullBMPS(tn, DOWN) after setting truncation params before measurement.");
+      walker.SetMPO(y2);
+      std::vector<TenElemT> row(n * np, TenElemT(0.0));
+      if (dev_slice) {
+        const std::vector<TenElemT> both = walker.PairTraceSlice(bottom, occ, table, mask);
+        for (size_t k = 0; k < n * np; ++k) row[k] = both[2 * k];
+      } else {
+        const DeviceTraceScaling<TenElemT> scaling(c);          // (scaled as the slice scales them: the same bytes on both paths)
+        walker.InitBTenLeft(bottom, 0);
+        walker.InitBTenRight(bottom, 1);
+        for (size_t x2 = 0; x2 < np; ++x2) {
+          const SiteIdx s1{y2, x2}, s2{y2, x2 + 1};
+          std::vector<int32_t> cand(n * 2);
+          std::vector<int> sign(n, 0);
+          bool any = false;
+          for (size_t w = 0; w < n; ++w) {
+            const int32_t a = comp.config(w, s1), b = comp.config(w, s2);
+            const int32_t pa = table[((a * d + b) * 2) * 2], pb = table[((a * d + b) * 2) * 2 + 1];
+            cand[2 * w] = pa < 0 ? a : pa;
+            cand[2 * w + 1] = pa < 0 ? b : pb;
+            if (pa >= 0 && mask[w]) { sign[w] = fd.n(pa) + fd.n(pb) == fd.n(a) + fd.n(b) ? 1 : -1; any = true; }
+          }
+          if (any) {
+            const std::vector<TenElemT> tr = walker.TraceWithTwoSiteBTen(bottom, x2, comp.DeviceStatesNN(s1, s2, 1, cand));
+            for (size_t w = 0; w < n; ++w)
+              if (sign[w]) row[w * np + x2] = TenElemT(double(sign[w]) * tr[w]);
+          }
+          if (x2 + 1 < np) walker.ShiftBTenWindow(bottom, RIGHT);
+        }
+      }
+      walker.ClearBTen();
+      return row;
+    };
+    // all target rows of a walker that has absorbed the rows [0, y1]
+    auto scan_rows = [&](typename BMPSContractorT<TenElemT>::BMPSWalker &walker, size_t y1, const std::vector<int32_t> &table,
+                         const std::vector<uint8_t> &mask) {
+      std::vector<std::vector<TenElemT>> rows;
+      for (size_t y2 = y1 + 1; y2 < Ly; ++y2) {
+        if (y2 > y1 + 1) { walker.SetMPO(y2 - 1); walker.Evolve(); }
+        rows.push_back(scan_row(walker, y2, table, mask));
+      }
+      return rows;
+    };
+    const std::vector<uint8_t> everyone(n, 1);
+    std::vector<std::vector<TenElemT>> psi_orig;
+    size_t psi_y1 = Ly, pos = 0;
+    for (const auto &bond : bonds) {
+      const size_t y1 = bond.first, x1 = bond.second, npair = (Ly - 1 - y1) * np;
+      std::vector<uint8_t> ref_valid(n);
+      bool any = false;
+      for (size_t w = 0; w < n; ++w) {
+        ref_valid[w] = comp.config(w, {y1, x1}) == 2 && comp.config(w, {y1, x1 + 1}) == 2;
+        any |= ref_valid[w] != 0;
+      }
+      if (!any) { pos += npair; continue; }
+      if (psi_y1 != y1) {
+        auto original_walker = c.MakeWalker(UP, y1);
+        original_walker.SetMPO(y1);
+        original_walker.Evolve();
+        psi_orig = scan_rows(original_walker, y1, ident, everyone);
+        psi_y1 = y1;
+      }
+      std::vector<std::vector<TenElemT>> over[2];
+      for (int k = 0; k < 2; ++k) {
+        auto excited_walker = c.MakeWalker(UP, y1);
+        if (dev_slice) {
+          excited_walker.SetMPOExcitedPair(y1, x1, occ, inject, k);
+        } else {
+          Configuration changed = comp.config;
+          for (size_t w = 0; w < n; ++w)
+            if (ref_valid[w]) { changed(w, {y1, x1}) = k == 0 ? 0 : 1; changed(w, {y1, x1 + 1}) = k == 0 ? 1 : 0; }
+          const Configuration ext = fd.ExtConfig(changed, ROW_MAJOR);
+          std::vector<int32_t> excited(n * Lx);
+          for (size_t w = 0; w < n; ++w)
+            for (size_t x = 0; x < Lx; ++x) excited[w * Lx + x] = ext(w, {y1, x});
+          excited_walker.SetMPOStates(y1, excited);
+        }
+        excited_walker.Evolve();
+        over[k] = scan_rows(excited_walker, y1, remove, ref_valid);
+      }
+      for (size_t y2 = y1 + 1; y2 < Ly; ++y2) {
+        const size_t r = y2 - y1 - 1;
+        for (size_t w = 0; w < n; ++w)
+          for (size_t x2 = 0; x2 < np; ++x2) {
+            if (!ref_valid[w] || !is_pair(w, y2, x2)) continue;
+            const TenElemT psi = psi_orig[r][w * np + x2];
+            if (psi == TenElemT(0.0))
+              throw std::runtime_error("MeasureSingletPairCorrelation: psi_original = 0 for sampled configuration. "
+                                       "This indicates a bug in sampling or tensor network contraction.");
+            // (the removal's sign is in the scan; the injection's -1 here)
+            const TenElemT ratio_ud = TenElemT(-over[0][r][w * np + x2] / psi), ratio_du = TenElemT(-over[1][r][w * np + x2] / psi);
+            const double tgt = comp.config(w, {y2, x2}) == 0 ? 1.0 : -1.0;
+            corr[w * per + pos + r * np + x2] = TenElemT(0.5 * tgt) * ComplexConjugate(TenElemT(ratio_ud - ratio_du));
+          }
+      }
+      pos += npair;
+    }
+  }
+
+ protected:
+  bool enable_singlet_pair_correlation_ = false;
+  std::vector<std::pair<size_t, size_t>> selected_ref_bonds_;
+};
+
 // square_tJ_model.h:301-345 (SquaretJModelMixIn::EvaluateBondEnergy) + :215-228: states 0 up, 1 down, 2 empty
 // (vmc_basic/tj_single_site_state.h:19-23); H = -t sum (c+ c + h.c.) + J sum (S.S - n n / 4) + V sum n n - mu N.
 // NNN hopping t2 (:424-463): FermionNNNHop above.
 // Measurement (:546-603, :657-850): the registry of the diagonal-bond traversal with spin_z, charge and the bond-singlet pairing order
 //   Delta+_ij = (c+_i,up c+_j,down - c+_i,down c+_j,up) / sqrt(2)   on the NN bond with i the left / upper, j the right / lower site,
-// in the basis |S> = product of c+ over the occupied sites in row-major order.  SC_singlet_pair_corr is not built.
-class SquaretJVModel : public SquareNNModelEnergySolver<SquaretJVModel>, public SquareNNNModelMeasurementSolver<SquaretJVModel> {
+// in the basis |S> = product of c+ over the occupied sites in row-major order.  SC_singlet_pair_corr: the mixin above, off by default
+// (SquaretJNNModel and SquaretJNNNModel inherit it).
+class SquaretJVModel : public SquareNNModelEnergySolver<SquaretJVModel>, public SquareNNNModelMeasurementSolver<SquaretJVModel>,
+                       public SingletPairCorrelationMixin<SquaretJVModel> {
  public:
   static constexpr bool kFermionicModel = true;
   static constexpr bool requires_spin_sz_measurement = true;
@@ -3760,6 +4015,9 @@ class MCPEPSMeasurer {
         for (size_t k = 0; k < vals.size(); ++k) ofs << k << "," << csv(vals[k]) << "," << csv(k < errs.size() ? errs[k] : 0.0) << "\n";
       }
     }
+    for (const auto &m : observables_meta_)          // stats/<key>_coords.txt of an observable with a coordinate generator (impl.h:339-345)
+      if (m.coord_generator && registry_stats_.count(m.key))
+        std::ofstream(base + "stats/" + m.key + "_coords.txt") << m.coord_generator(comp_.contractor.rows(), comp_.contractor.cols());
     std::ofstream ofs(base + "samples/psi.csv");
     ofs << "sample,walker,psi_mean,psi_rel_err\n";
     for (size_t k = 0; k < psi_samples_.size(); ++k)

@@ -26,7 +26,9 @@ SYMBOLS = ["pepshost_last_error", "pepshost_mc_sweeps", "pepshost_energy_and_hol
            "pepshost_fermion_sr_step_samples", "pepshost_fermion_sr_step_samples_c128", "pepshost_fermion_exact_sum_partial_prm",
            "pepshost_lbfgs_exact_sum", "pepshost_lbfgs_exact_sum_c128", "pepshost_fermion_lbfgs_exact_sum", "pepshost_fermion_lbfgs_exact_sum_c128",
            "pepshost_fermion_observables", "pepshost_fermion_exact_sum_measure_partial", "pepshost_fermion_measure",
-           "pepshost_fermion_measure_updater", "pepshost_hubbard_sector_table", "pepshost_hubbard_hop_table"]
+           "pepshost_fermion_measure_updater", "pepshost_hubbard_sector_table", "pepshost_hubbard_hop_table",
+           "pepshost_fermion_observables_sc", "pepshost_fermion_exact_sum_measure_partial_sc", "pepshost_fermion_measure_sc",
+           "pepshost_sc_pair_corr_mapping"]
 
 _lib = None
 _C128 = 3                                   # PEPSGPU_C128 (include/pepsgpu.h)
@@ -683,19 +685,47 @@ def _keyed(keys, vals, cplx):
     return items, (vals.view(np.complex128) if cplx else vals)
 
 
-def fermion_observables(state, configs, chi, model="tj", params=(1.0, 0.3, 0.0, 0.0), dtype=1):
+def _ref_bonds(ref_bonds):
+    """the selected reference bonds of SC_singlet_pair_corr as the trailing arguments (count, [n][2] int32 or NULL) of the *_sc shims"""
+    rb = np.ascontiguousarray(np.asarray(ref_bonds, dtype=np.int32).reshape(-1, 2))
+    return rb.shape[0], (_p(rb, C.c_int32) if rb.shape[0] else None), rb
+
+
+def sc_pair_corr_mapping(rows, cols, ref_bonds=()):
+    """GenerateSCPairCorrIndexMapping of the host layer's SingletPairCorrelationMixin: [n_pairs][6] = (ref_y, ref_x, 0, tgt_y, tgt_x, 0)
+    per value of SC_singlet_pair_corr; ref_bonds = selected reference bonds (y, x) of the left site, none: all.  Needs no device."""
+    nb, pb, keep = _ref_bonds(ref_bonds)
+    count = C.c_long(0)
+    _ck(lib().pepshost_sc_pair_corr_mapping(rows, cols, nb, pb, None, C.c_long(0), C.byref(count)))
+    out = np.zeros((count.value, 6), dtype=np.int32)
+    _ck(lib().pepshost_sc_pair_corr_mapping(rows, cols, nb, pb, _p(out, C.c_int32), C.c_long(count.value), C.byref(count)))
+    return out
+
+
+def _sc_pairs(rows, cols, sc_pair_corr, ref_bonds):
+    return int(sc_pair_corr_mapping(rows, cols, ref_bonds).shape[0]) if sc_pair_corr else 0
+
+
+def fermion_observables(state, configs, chi, model="tj", params=(1.0, 0.3, 0.0, 0.0), dtype=1, sc_pair_corr=False, ref_bonds=()):
     """Registry of the C++ measurement solver of a fermionic model (SquareNNNModelMeasurementSolver on SquareSpinlessFermion /
     SquaretJVModel / SquaretJNNModel) on a batch of configurations: dict key -> [walker][len] with energy, charge, bond_energy_h / _v
     (/ _dr / _ur) and, for the t-J models, spin_z and the bond-singlet pairing order SC_bond_singlet_h / _v; and the psi summary
     (psi_mean [walker], psi_rel_err [walker]).  params: spinless (t, V, t2), tj (t, J, V, mu, t2), tjnn (t, J, mu), hubbard (t, U, mu:
-    SquareHubbardModel, with spin_z and double_occupancy)."""
+    SquareHubbardModel, with spin_z and double_occupancy).  sc_pair_corr (t-J models): also SC_singlet_pair_corr, the pair-pair
+    correlation of the selected horizontal reference bonds ref_bonds = [(y, x)] (none: all) with every horizontal bond of the rows
+    below, in the order of sc_pair_corr_mapping."""
     cplx, head, tail, keep = _fermion_measure_head(state, chi, model, params, dtype)
     cfg = np.ascontiguousarray(configs, dtype=np.int32)
     n, sites = cfg.shape[0], cfg.shape[1] * cfg.shape[2]
-    cap = 2 * (16 * n * sites + 4096)
+    cap = 2 * (16 * n * sites + n * _sc_pairs(cfg.shape[1], cfg.shape[2], sc_pair_corr, ref_bonds) + 4096)
     vals, keys, nvals = np.zeros(cap, dtype=np.float64), C.create_string_buffer(4096), C.c_long(0)
-    _ck(lib().pepshost_fermion_observables(*head, n, _p(cfg, C.c_int32), *tail, keys, 4096, _p(vals, C.c_double),
-                                           C.c_long(cap), C.byref(nvals)))
+    if sc_pair_corr:
+        nb, pb, keep_rb = _ref_bonds(ref_bonds)
+        _ck(lib().pepshost_fermion_observables_sc(*head, n, _p(cfg, C.c_int32), *tail, keys, 4096, _p(vals, C.c_double),
+                                                  C.c_long(cap), C.byref(nvals), 1, nb, pb))
+    else:
+        _ck(lib().pepshost_fermion_observables(*head, n, _p(cfg, C.c_int32), *tail, keys, 4096, _p(vals, C.c_double),
+                                               C.c_long(cap), C.byref(nvals)))
     items, v = _keyed(keys, vals[:nvals.value], cplx)
     out, off = {}, 0
     for key, ln in items:
@@ -704,16 +734,22 @@ def fermion_observables(state, configs, chi, model="tj", params=(1.0, 0.3, 0.0, 
     return out, (v[off:off + n].copy(), np.real(v[off + n:off + 2 * n]).copy())
 
 
-def fermion_exact_sum_measure(state, all_configs, chi, model="tj", params=(1.0, 0.3, 0.0, 0.0), rank=0, size=1, batch=64, dtype=1):
+def fermion_exact_sum_measure(state, all_configs, chi, model="tj", params=(1.0, 0.3, 0.0, 0.0), rank=0, size=1, batch=64, dtype=1,
+                              sc_pair_corr=False, ref_bonds=()):
     """Rank-local part of ExactSumMeasurerMPI on a fermionic state through the C++ measurement solver: (dict key ->
     sum_S |psi(S)|^2 O_loc(S), sum_S |psi(S)|^2) over the configurations rank, rank + size, ...; sum both over the ranks and divide.
     Every configuration must have a non-zero amplitude (hand over the parity-allowed ones)."""
     cplx, head, tail, keep = _fermion_measure_head(state, chi, model, params, dtype)
     cfg = np.ascontiguousarray(all_configs, dtype=np.int32)
-    cap = 2 * (16 * cfg.shape[1] * cfg.shape[2] + 4096)
+    cap = 2 * (16 * cfg.shape[1] * cfg.shape[2] + _sc_pairs(cfg.shape[1], cfg.shape[2], sc_pair_corr, ref_bonds) + 4096)
     vals, keys, nvals = np.zeros(cap, dtype=np.float64), C.create_string_buffer(4096), C.c_long(0)
-    _ck(lib().pepshost_fermion_exact_sum_measure_partial(*head, _p(cfg, C.c_int32), cfg.shape[0], *tail, rank, size, batch,
-                                                         keys, 4096, _p(vals, C.c_double), C.c_long(cap), C.byref(nvals)))
+    if sc_pair_corr:
+        nb, pb, keep_rb = _ref_bonds(ref_bonds)
+        _ck(lib().pepshost_fermion_exact_sum_measure_partial_sc(*head, _p(cfg, C.c_int32), cfg.shape[0], *tail, rank, size, batch,
+                                                                keys, 4096, _p(vals, C.c_double), C.c_long(cap), C.byref(nvals), 1, nb, pb))
+    else:
+        _ck(lib().pepshost_fermion_exact_sum_measure_partial(*head, _p(cfg, C.c_int32), cfg.shape[0], *tail, rank, size, batch,
+                                                             keys, 4096, _p(vals, C.c_double), C.c_long(cap), C.byref(nvals)))
     items, _ = _keyed(keys, vals, False)
     out, off, z = {}, 1, 2 if cplx else 1
     for key, ln in items:
@@ -724,21 +760,28 @@ def fermion_exact_sum_measure(state, all_configs, chi, model="tj", params=(1.0, 
 
 
 def fermion_measure(state, configs, seeds, chi, warmup_sweeps, n_samples, sweeps_between=1, model="tj", params=(1.0, 0.3, 0.0, 0.0), dtype=1,
-                    updater="exchange"):
+                    updater="exchange", sc_pair_corr=False, ref_bonds=()):
     """MCPEPSMeasurer with the exchange updater (or updater="hubbard_u1u1") on a fermionic state: dict key -> (mean [len], stderr [len])
     across the walkers, the psi summary of the last sample, the energy samples [sample][walker], the final configurations and the accept
     rates.  Warm-up, samples and ONE std::mt19937 stream per walker as fermion_measure_energy: with the exchange updater the energy
     samples are the numbers that call returns."""
     if updater not in ("exchange", "hubbard_u1u1"):
         raise ValueError("fermion_measure: updater must be 'exchange' or 'hubbard_u1u1'")
+    if sc_pair_corr and updater != "exchange":
+        raise ValueError("fermion_measure: SC_singlet_pair_corr is measured with the exchange updater (t-J models)")
     cplx, head, tail, keep = _fermion_measure_head(state, chi, model, params, dtype)
     cfg = np.ascontiguousarray(configs, dtype=np.int32).copy()
     n, sites = cfg.shape[0], cfg.shape[1] * cfg.shape[2]
     sd = np.ascontiguousarray(seeds, dtype=np.uint64)
-    cap = 2 * (32 * sites + 2 * n + 4096)
+    cap = 2 * (32 * sites + 2 * _sc_pairs(cfg.shape[1], cfg.shape[2], sc_pair_corr, ref_bonds) + 2 * n + 4096)
     vals, keys, nvals = np.zeros(cap, dtype=np.float64), C.create_string_buffer(4096), C.c_long(0)
     en, rates = np.zeros((n_samples, n), np.complex128 if cplx else np.float64), np.zeros(n)
-    if updater == "exchange":
+    if sc_pair_corr:
+        nb, pb, keep_rb = _ref_bonds(ref_bonds)
+        _ck(lib().pepshost_fermion_measure_sc(*head, n, _p(cfg, C.c_int32), _p(sd, C.c_uint64), warmup_sweeps, n_samples,
+                                              sweeps_between, *tail, keys, 4096, _p(vals, C.c_double), C.c_long(cap), C.byref(nvals), _cp(en),
+                                              _p(rates, C.c_double), 1, nb, pb))
+    elif updater == "exchange":
         _ck(lib().pepshost_fermion_measure(*head, n, _p(cfg, C.c_int32), _p(sd, C.c_uint64), warmup_sweeps, n_samples,
                                            sweeps_between, *tail, keys, 4096, _p(vals, C.c_double), C.c_long(cap), C.byref(nvals), _cp(en),
                                            _p(rates, C.c_double)))

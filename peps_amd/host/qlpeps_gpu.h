@@ -1099,6 +1099,42 @@ struct SliceSites {
   BTenPOSITION hi() const { return dir == HORIZONTAL ? RIGHT : DOWN; }
 };
 
+// psi as a divisor: a zero amplitude is the error of the reference's solvers
+template <typename TenElemT>
+inline const TenElemT &NonZeroPsi(const TenElemT &psi) {
+  if (psi == TenElemT(0.0)) throw std::runtime_error("Wavefunction amplitude is near zero, causing division by zero.");
+  return psi;
+}
+template <typename TenElemT>
+inline std::vector<TenElemT> InversePsi(const std::vector<TenElemT> &psi) {
+  std::vector<TenElemT> inv(psi.size());
+  for (size_t w = 0; w < psi.size(); ++w) inv[w] = TenElemT(1.0) / NonZeroPsi(psi[w]);
+  return inv;
+}
+
+// Where the holes of a row pass go: nowhere (!wanted: the measurements), into HBM (on_device: PunchHoleStore), else conjugated --
+// hole_res(site) = Dag(hole), square_nnn_energy_solver.h:163 -- into host [walker][row][col][slot], which is sized here
+template <typename TenElemT>
+struct HoleDest {
+  bool wanted = false, on_device = false;
+  size_t slot = 0;
+  std::vector<TenElemT> *host = nullptr;
+  HoleDest() = default;
+  HoleDest(bool calchols, bool holes_on_device, size_t slot_, const TPSWaveFunctionComponentT<TenElemT> &comp, std::vector<TenElemT> &out)
+      : wanted(calchols), on_device(holes_on_device), slot(slot_), host(&out) {
+    if (wanted && !on_device) out.assign(comp.config.walkers() * comp.contractor.rows() * comp.contractor.cols() * slot, TenElemT(0.0));
+  }
+  // the hole of site s of the current row window
+  void Punch(BMPSContractorT<TenElemT> &c, const SiteIdx &s) const {
+    if (!wanted) return;
+    if (on_device) { c.PunchHoleStore(s, HORIZONTAL); return; }
+    const std::vector<TenElemT> h = c.PunchHole(s, HORIZONTAL);
+    for (size_t w = 0; w * slot < h.size(); ++w)
+      std::transform(h.begin() + w * slot, h.begin() + (w + 1) * slot, host->begin() + ((w * c.rows() + s.r) * c.cols() + s.c) * slot,
+                     [](const TenElemT &x) { return ComplexConjugate(x); });
+  }
+};
+
 // MonteCarloSweepUpdaterBase (monte_carlo_sweep_updater_base.h:18-47): one std::mt19937 per walker
 class MonteCarloSweepUpdaterBase {
  public:
@@ -1256,6 +1292,191 @@ void NNNSliceEnergies(Model &model, TPSWaveFunctionComponentT<TenElemT> &comp, s
         e2 = model.NNNEnergyFromExchange(comp.config(w, {row + 1, col}), comp.config(w, {row, col + 1}), ComplexConjugate(TenElemT(v[1] * inv_psi[w])));
       sink(w, col, e1, e2);
     }
+}
+// The diagonal bonds of the row pair (row, row + 1), square_nnn_energy_solver.h:203-265: sink(w, col, e1, e2) as above, from ONE
+// pepsgpu_nnn_exchange_slice (nnn_slice: a model with the scalar hook NNNEnergyFromExchange on a bosonic component; a fermionic diagonal hop
+// keeps its twisted-environment path through the hooks), else from the hooks EvaluateNNNEnergy over the BTen2 of the pair.  Either way
+// it needs the BMPS pair of the row and inv_psi only: unlike the NN slices it does not depend on where the holes go.
+template <class Model, typename TenElemT, class Sink>
+void NNNBondEnergies(Model &model, TPSWaveFunctionComponentT<TenElemT> &comp, bool nnn_slice, size_t row, const std::vector<TenElemT> &inv_psi,
+                     Sink &&sink) {
+  auto &c = comp.contractor;
+  if (row + 1 >= c.rows()) return;
+  if (nnn_slice) {
+    if constexpr (HasExchangeNNNEnergy<Model>::value) NNNSliceEnergies(model, comp, row, inv_psi, sink);
+    return;
+  }
+  c.InitBTen2(LEFT, row);
+  c.GrowFullBTen2(RIGHT, row, 2, true);
+  for (size_t col = 0; col + 1 < c.cols(); col++) {
+    const std::vector<TenElemT> e1 = model.EvaluateNNNEnergy({row, col}, {row + 1, col + 1}, LEFTUP_TO_RIGHTDOWN, comp, inv_psi);
+    const std::vector<TenElemT> e2 = model.EvaluateNNNEnergy({row + 1, col}, {row, col + 1}, LEFTDOWN_TO_RIGHTUP, comp, inv_psi);
+    for (size_t w = 0; w < e1.size(); ++w) sink(w, col, e1[w], e2[w]);   // LEFTDOWN anchor mapped to the top cell (:155)
+    c.ShiftBTen2Window(RIGHT, row);
+  }
+}
+
+// What ONE device call returned for the np = N - 1 bonds of a row / column: psi [walker] -- [walker][np] when the slice reports the psi of
+// every bond's own window (per_bond) --, the exchanged amplitude of every bond ex [walker][np], and two further candidates per bond
+// two [walker][np][2]: the hops of pepsgpu_nn_hop_slice_fermion, the pair candidates of pepsgpu_nn_pair_slice_fermion
+template <typename TenElemT>
+struct BondSlice {
+  size_t n, np;
+  bool per_bond;
+  std::vector<TenElemT> psi, ex, two;
+  BondSlice(size_t n_, const SliceSites &s, bool per_bond_, bool with_ex, bool with_two)
+      : n(n_), np(s.N - 1), per_bond(per_bond_), psi(per_bond_ ? n_ * np : n_), ex(with_ex ? n_ * np : 0), two(with_two ? n_ * np * 2 : 0) {}
+  const TenElemT &Psi(size_t w, size_t j) const { return psi[per_bond ? w * np + j : w]; }
+  // psi of the slice (per bond: the first bond's window is the slice's first window)
+  std::vector<TenElemT> Psi0() const {
+    std::vector<TenElemT> psi0(n);
+    for (size_t w = 0; w < n; ++w) psi0[w] = per_bond && np == 0 ? TenElemT(1.0) : Psi(w, 0);
+    return psi0;
+  }
+};
+inline std::vector<int32_t> OccupationTable(const FermionDecoration &fd) {
+  std::vector<int32_t> occ(fd.d());
+  for (size_t s = 0; s < occ.size(); ++s) occ[s] = fd.n((int32_t)s);
+  return occ;
+}
+// pepsgpu_nn_exchange_slice_tab: psi, the exchanged amplitude of every bond and -- holes: resident in HBM -- the holes of the row, one
+// read-back, instead of a ReplaceNNSiteTrace round trip per bond.  Real and complex; a fermionic component through its ExchangeTable.
+template <typename TenElemT>
+BondSlice<TenElemT> ExchangeSlice(TPSWaveFunctionComponentT<TenElemT> &comp, const SliceSites &s, bool holes, bool per_bond) {
+  auto &c = comp.contractor;
+  BondSlice<TenElemT> sl(comp.config.walkers(), s, per_bond, true, false);
+  const std::vector<int32_t> tab = comp.fermion ? comp.ExchangeTable() : std::vector<int32_t>();
+  check_rc(pepsgpu_nn_exchange_slice_tab(c.ctx(), s.dir, (int)s.num, holes ? 1 : 0, tab.empty() ? nullptr : tab.data(), per_bond ? 1 : 0,
+                                         dptr(sl.psi.data()), dptr(sl.ex.data())), c.ctx());
+  return sl;
+}
+// pepsgpu_nn_hop_slice_fermion: psi per bond and the two hops of hop_table of every bond (the holes with a row when they are resident)
+template <typename TenElemT>
+BondSlice<TenElemT> HopSlice(TPSWaveFunctionComponentT<TenElemT> &comp, const SliceSites &s, bool holes, const std::vector<int32_t> &hop_table) {
+  auto &c = comp.contractor;
+  BondSlice<TenElemT> sl(comp.config.walkers(), s, true, false, true);
+  const std::vector<int32_t> occ = OccupationTable(*comp.fermion);
+  check_rc(pepsgpu_nn_hop_slice_fermion(c.ctx(), s.dir, (int)s.num, holes ? 1 : 0, (int)occ.size(), occ.data(), hop_table.data(), dptr(sl.psi.data()),
+                                        dptr(sl.two.data())), c.ctx());
+  return sl;
+}
+// pepsgpu_nn_pair_slice_fermion: psi per bond, the exchanged amplitude and the two pair candidates of pair_table of every bond
+template <typename TenElemT>
+BondSlice<TenElemT> PairSlice(TPSWaveFunctionComponentT<TenElemT> &comp, const SliceSites &s, const std::vector<int32_t> &pair_table) {
+  auto &c = comp.contractor;
+  BondSlice<TenElemT> sl(comp.config.walkers(), s, true, true, true);
+  const std::vector<int32_t> occ = OccupationTable(*comp.fermion), xtab = comp.ExchangeTable();
+  check_rc(pepsgpu_nn_pair_slice_fermion(c.ctx(), s.dir, (int)s.num, (int)occ.size(), occ.data(), pair_table.data(), xtab.data(), dptr(sl.psi.data()),
+                                         dptr(sl.ex.data()), dptr(sl.two.data())), c.ctx());
+  return sl;
+}
+
+// How the solvers of the square-lattice models evaluate NN bond j of a slice, per walker: e = the bond energy and, with_sc (the fermionic
+// registry of a model with enable_sc_measurement), sc = the registry value (conj(delta_dag) + delta) / 2 of the bond-singlet pairing.
+//   Read + FromSlice  the model's device slice: BondEnergyFromHops on the hop slice (kHopBondEnergy), else BondEnergyFromExchange on the
+//                     exchange slice, psi per bond for kExchangeBondPsiPerBond -- pair_slice (the fermionic registry): on the pair slice,
+//                     which also serves BondSCFromPairs with rho(S') = sign ReplaceNNSiteTrace / Trace from the same read-back;
+//   Hook              EvaluateBondEnergy / EvaluateBondSC, a ReplaceNNSiteTrace round trip per bond.
+template <typename TenElemT> struct BondValues { std::vector<TenElemT> e, sc; };
+template <class Model, typename TenElemT, bool pair_slice, bool with_sc>
+struct SquareModelBonds {
+  Model &model;
+  TPSWaveFunctionComponentT<TenElemT> &comp;
+  std::vector<int32_t> pair_table;
+  SquareModelBonds(Model &model_, TPSWaveFunctionComponentT<TenElemT> &comp_) : model(model_), comp(comp_) {
+    if constexpr (with_sc) pair_table = model.PairTable();
+    else if constexpr (pair_slice) pair_table.assign(4 * comp.fermion->d() * comp.fermion->d(), -1);
+  }
+  BondSlice<TenElemT> Read(const SliceSites &s, bool holes) const {
+    if constexpr (HasHopBondEnergy<Model>::value) return HopSlice(comp, s, holes, model.HopTable());
+    else if constexpr (pair_slice) return PairSlice(comp, s, pair_table);
+    else return ExchangeSlice(comp, s, holes, HasExchangeBondPsiPerBond<Model>::value);
+  }
+  BondValues<TenElemT> FromSlice(const SliceSites &s, size_t j, const BondSlice<TenElemT> &sl, const std::vector<TenElemT> &inv_psi) const {
+    BondValues<TenElemT> v{std::vector<TenElemT>(sl.n), std::vector<TenElemT>(with_sc ? sl.n : 0)};
+    for (size_t w = 0; w < sl.n; ++w) {
+      const int32_t c1 = comp.config(w, s.at(j)), c2 = comp.config(w, s.at(j + 1));
+      const size_t k = w * sl.np + j;
+      if constexpr (HasHopBondEnergy<Model>::value) {
+        const TenElemT psi = NonZeroPsi(sl.Psi(w, j));
+        v.e[w] = model.BondEnergyFromHops(c1, c2, ComplexConjugate(TenElemT(sl.two[2 * k] / psi)), ComplexConjugate(TenElemT(sl.two[2 * k + 1] / psi)));
+      } else if constexpr (HasExchangeBondEnergy<Model>::value) {
+        v.e[w] = model.BondEnergyFromExchange(c1, c2, sl.per_bond ? ComplexConjugate(TenElemT(sl.ex[k] / NonZeroPsi(sl.Psi(w, j))))
+                                                                   : ComplexConjugate(TenElemT(sl.ex[k] * inv_psi[w])));
+        if constexpr (with_sc) {
+          const auto dd = model.BondSCFromPairs(c1, c2, TenElemT(sl.two[2 * k] / sl.Psi(w, j)), TenElemT(sl.two[2 * k + 1] / sl.Psi(w, j)));
+          v.sc[w] = (ComplexConjugate(dd.first) + dd.second) / TenElemT(2.0);
+        }
+      } else {
+        throw std::logic_error("the model has no device-side bond slice");
+      }
+    }
+    return v;
+  }
+  BondValues<TenElemT> Hook(const SliceSites &s, size_t j, const std::vector<TenElemT> &inv_psi) const {
+    BondValues<TenElemT> v{model.EvaluateBondEnergy(s.at(j), s.at(j + 1), s.dir, comp, inv_psi), {}};
+    if constexpr (with_sc) {
+      for (const auto &dd : model.EvaluateBondSC(s.at(j), s.at(j + 1), s.dir, comp))
+        v.sc.push_back((ComplexConjugate(dd.first) + dd.second) / TenElemT(2.0));
+    }
+    return v;
+  }
+};
+
+// The bond traversal of the energy and measurement solvers (square_nnn_energy_solver.h:116-200 + BondTraversalMixin::TraverseVerticalBonds,
+// bond_traversal_mixin.h:113-144): every row under the row-major mode order (fermions: the two sites of a bond are adjacent modes of
+// its pass, and the holes are those of the row-major decorated network), then every column under the column-major one.
+//   dev_slice   a row / column is ONE device call, bonds.Read(sites, holes), evaluated by bonds.FromSlice(sites, j, slice, inv_psi):
+//               the same operations in the same order on the device as the hook pass, same numbers.  The caller decides; wherever
+//               PEPSHOST_NO_DEVICE_SWEEP=1 (DeviceSlicesEnabled()) enters its condition, that keeps the hook pass;
+//   else        the hook pass: Trace, then bonds.Hook(sites, j, inv_psi) per bond, in a row behind the hole of every site.  A row
+//               shifts the BTen window behind every bond, the last included; a column only while a bond follows.
+// on_bond(sites, j, value) gets every bond in traversal order, after_slice(sites, inv_psi) runs before the BMPS window moves on (the
+// diagonal bonds and links of a row pair / column pair hang there), before_rows() between GenerateBMPSApproach(UP) and the first row.
+// Returns psi of every row and column in that order.
+struct NoOp { void operator()() const {} };
+template <typename TenElemT, class Bonds, class OnBond, class AfterSlice, class BeforeRows = NoOp>
+std::vector<std::vector<TenElemT>> TraverseNNBonds(TPSWaveFunctionComponentT<TenElemT> &comp, bool dev_slice, const HoleDest<TenElemT> &holes,
+                                                   const Bonds &bonds, OnBond &&on_bond, AfterSlice &&after_slice,
+                                                   BeforeRows &&before_rows = BeforeRows()) {
+  auto &c = comp.contractor;
+  std::vector<std::vector<TenElemT>> psi_list;
+  auto pass = [&](const SliceSites &s) {
+    const bool row = s.dir == HORIZONTAL;
+    std::vector<TenElemT> inv_psi;
+    if (dev_slice) {
+      const auto sl = bonds.Read(s, row && holes.wanted);
+      psi_list.push_back(sl.Psi0());
+      inv_psi = InversePsi(psi_list.back());
+      for (size_t j = 0; j + 1 < s.N; ++j) on_bond(s, j, bonds.FromSlice(s, j, sl, inv_psi));
+    } else {
+      c.InitBTen(s.lo(), s.num);                                             // :142
+      c.GrowFullBTen(s.hi(), s.num, row ? 1 : 2, true);                      // :143
+      psi_list.push_back(c.Trace(s.at(0), s.dir));                           // :147
+      inv_psi = InversePsi(psi_list.back());
+      for (size_t j = 0; j < s.N; ++j) {
+        if (row) holes.Punch(c, s.at(j));                                    // :163
+        if (j + 1 == s.N) break;
+        on_bond(s, j, bonds.Hook(s, j, inv_psi));
+        if (row || j + 2 < s.N) c.ShiftBTenWindow(s.hi());                   // :200
+      }
+    }
+    after_slice(s, inv_psi);
+  };
+  comp.SetOrder(ROW_MAJOR);
+  c.GenerateBMPSApproach(UP);                                                // :116
+  before_rows();
+  for (size_t row = 0; row < c.rows(); row++) {
+    pass(SliceSites(c, HORIZONTAL, row));
+    if (row + 1 < c.rows()) c.ShiftBMPSWindow(DOWN);                         // :126
+  }
+  comp.SetOrder(COL_MAJOR);
+  c.GenerateBMPSApproach(LEFT);                                              // bond_traversal_mixin.h:120
+  for (size_t col = 0; col < c.cols(); col++) {
+    pass(SliceSites(c, VERTICAL, col));
+    if (col + 1 < c.cols()) c.ShiftBMPSWindow(RIGHT);
+  }
+  return psi_list;
 }
 
 // square_nn_updater.h:25-83: sweep schedule, CRTP hook TwoSiteNNUpdateLocalImpl(site1, site2, dir, sitps, comp) -> accepted[w]
@@ -1684,143 +1905,32 @@ class SquareNNNModelEnergySolver {
   template <bool calchols = true, typename TenElemT = double>
   EnergyAndHolesT<TenElemT> CalEnergyAndHoles(const SplitIndexTPST<TenElemT> &sitps, TPSWaveFunctionComponentT<TenElemT> &comp,
                                               bool holes_on_device = false) {
-    auto &c = comp.contractor;
-    const size_t rows = c.rows(), cols = c.cols(), n = comp.config.walkers(), slot = sitps.slot();
+    const size_t n = comp.config.walkers();
     EnergyAndHolesT<TenElemT> out;
     out.energy.assign(n, TenElemT(0.0));
-    if (calchols && !holes_on_device) out.holes.assign(n * rows * cols * slot, TenElemT(0.0));
     auto *self = static_cast<ExplicitlyModel *>(this);
-    // A model whose NN off-diagonal term exchanges the two site states (it declares kExchangeBondEnergy and the scalar hook
-    // BondEnergyFromExchange) gets a whole row / column from ONE device call (pepsgpu_nn_exchange_slice_tab: psi, the exchanged
-    // amplitudes of every bond and -- with holes resident in HBM -- the holes of the row, one read-back) instead of a
-    // ReplaceNNSiteTrace round trip per bond; same operations in the same order on the device, same numbers.  Real and complex;
-    // fermionic components for the models with kExchangeBondPsiPerBond (the exchange as ExchangeTable, psi per bond).
-    // PEPSHOST_NO_DEVICE_SWEEP=1 keeps the per-bond hook path.
-    constexpr bool per_bond = HasExchangeBondPsiPerBond<ExplicitlyModel>::value;
+    // The NN bonds of a row / column come from ONE device call for a model whose off-diagonal term exchanges the two site states
+    // (kExchangeBondEnergy: real and complex components; fermionic ones for the models with kExchangeBondPsiPerBond) or hops between
+    // them (kHopBondEnergy, fermionic components) -- when the holes are not wanted on the host: the slice leaves them in HBM.
     bool dev_slice = false;
     if constexpr (HasExchangeBondEnergy<ExplicitlyModel>::value)
-      dev_slice = DeviceSlicesEnabled() && (!comp.fermion || per_bond) && (!calchols || holes_on_device);
+      dev_slice = DeviceSlicesEnabled() && (!comp.fermion || HasExchangeBondPsiPerBond<ExplicitlyModel>::value) && (!calchols || holes_on_device);
     if constexpr (HasHopBondEnergy<ExplicitlyModel>::value)
       dev_slice = DeviceSlicesEnabled() && comp.fermion && (!calchols || holes_on_device);
-    auto slice_energy = [&](BondOrientation dir, size_t slice, bool holes) {
-      if constexpr (HasHopBondEnergy<ExplicitlyModel>::value) {
-        const size_t N = dir == HORIZONTAL ? cols : rows, np = N - 1;
-        std::vector<TenElemT> psi(n * np), hop(n * np * 2), psi0(n);
-        const std::vector<int32_t> tab = self->HopTable();
-        std::vector<int32_t> occ(comp.fermion->d());
-        for (size_t s = 0; s < occ.size(); ++s) occ[s] = comp.fermion->n((int32_t)s);
-        check_rc(pepsgpu_nn_hop_slice_fermion(c.ctx(), dir, (int)slice, holes ? 1 : 0, (int)occ.size(), occ.data(), tab.data(), dptr(psi.data()),
-                                              dptr(hop.data())), c.ctx());
-        for (size_t w = 0; w < n; ++w) {
-          psi0[w] = psi[w * np];                              // (the first bond's window is the slice's first window)
-          for (size_t j = 0; j < np; ++j) {
-            const SiteIdx s1 = dir == HORIZONTAL ? SiteIdx{slice, j} : SiteIdx{j, slice};
-            const SiteIdx s2 = dir == HORIZONTAL ? SiteIdx{slice, j + 1} : SiteIdx{j + 1, slice};
-            const size_t k = w * np + j;
-            if (psi[k] == TenElemT(0.0)) throw std::runtime_error("Wavefunction amplitude is near zero, causing division by zero.");
-            out.energy[w] += self->BondEnergyFromHops(comp.config(w, s1), comp.config(w, s2), ComplexConjugate(TenElemT(hop[2 * k] / psi[k])),
-                                                      ComplexConjugate(TenElemT(hop[2 * k + 1] / psi[k])));
+    out.psi_list = TraverseNNBonds(
+        comp, dev_slice, HoleDest<TenElemT>(calchols, holes_on_device, sitps.slot(), comp, out.holes),
+        SquareModelBonds<ExplicitlyModel, TenElemT, false, false>(*self, comp),
+        [&](const SliceSites &, size_t, const BondValues<TenElemT> &v) {
+          for (size_t w = 0; w < n; ++w) out.energy[w] += v.e[w];
+        },
+        [&](const SliceSites &s, const std::vector<TenElemT> &inv_psi) {
+          if constexpr (has_nnn_interaction) {
+            bool nnn_slice = false;
+            if constexpr (HasExchangeNNNEnergy<ExplicitlyModel>::value) nnn_slice = DeviceSlicesEnabled() && !comp.fermion;
+            if (s.dir == HORIZONTAL)
+              NNNBondEnergies(*self, comp, nnn_slice, s.num, inv_psi, [&](size_t w, size_t, TenElemT e1, TenElemT e2) { out.energy[w] += e1 + e2; });
           }
-        }
-        out.psi_list.push_back(psi0);
-      } else if constexpr (HasExchangeBondEnergy<ExplicitlyModel>::value) {
-        const size_t N = dir == HORIZONTAL ? cols : rows;
-        std::vector<TenElemT> psi(per_bond ? n * (N - 1) : n), ex(n * (N - 1)), psi0(n);
-        const std::vector<int32_t> tab = comp.fermion ? comp.ExchangeTable() : std::vector<int32_t>();
-        check_rc(pepsgpu_nn_exchange_slice_tab(c.ctx(), dir, (int)slice, holes ? 1 : 0, tab.empty() ? nullptr : tab.data(), per_bond ? 1 : 0,
-                                               dptr(psi.data()), dptr(ex.data())), c.ctx());
-        for (size_t w = 0; w < n; ++w) {
-          psi0[w] = psi[per_bond ? w * (N - 1) : w];          // (per bond: the first bond's window is the slice's first window)
-          if (psi0[w] == TenElemT(0.0)) throw std::runtime_error("Wavefunction amplitude is near zero, causing division by zero.");
-          const TenElemT inv = TenElemT(1.0) / psi0[w];
-          for (size_t j = 0; j + 1 < N; ++j) {
-            const SiteIdx s1 = dir == HORIZONTAL ? SiteIdx{slice, j} : SiteIdx{j, slice};
-            const SiteIdx s2 = dir == HORIZONTAL ? SiteIdx{slice, j + 1} : SiteIdx{j + 1, slice};
-            const size_t k = w * (N - 1) + j;
-            const TenElemT ratio = per_bond ? ComplexConjugate(TenElemT(ex[k] / psi[k])) : ComplexConjugate(TenElemT(ex[k] * inv));
-            out.energy[w] += self->BondEnergyFromExchange(comp.config(w, s1), comp.config(w, s2), ratio);
-          }
-        }
-        out.psi_list.push_back(psi0);
-      }
-    };
-    comp.SetOrder(ROW_MAJOR);                // fermions: holes are those of the row-major decorated network
-    c.GenerateBMPSApproach(UP);                                              // :116
-    for (size_t row = 0; row < rows; row++) {
-      std::vector<TenElemT> inv_psi(n);
-      if (dev_slice) {
-        slice_energy(HORIZONTAL, row, calchols);
-        for (size_t w = 0; w < n; ++w) inv_psi[w] = TenElemT(1.0) / out.psi_list.back()[w];     // (for the NNN pass below)
-      } else {
-      c.InitBTen(LEFT, row);                                                 // :142
-      c.GrowFullBTen(RIGHT, row, 1, true);                                   // :143
-      std::vector<TenElemT> psi = c.Trace({row, 0}, HORIZONTAL);             // :147
-      for (size_t w = 0; w < n; ++w) {
-        if (psi[w] == TenElemT(0.0)) throw std::runtime_error("Wavefunction amplitude is near zero, causing division by zero.");
-        inv_psi[w] = TenElemT(1.0) / psi[w];
-      }
-      out.psi_list.push_back(psi);
-      for (size_t col = 0; col < cols; col++) {
-        if (calchols && holes_on_device) {
-          c.PunchHoleStore({row, col}, HORIZONTAL);                           // :163, hole kept in HBM
-        } else if (calchols) {
-          std::vector<TenElemT> h = c.PunchHole({row, col}, HORIZONTAL);      // :163 hole_res(site) = Dag(hole)
-          for (size_t w = 0; w < n; ++w)
-            std::transform(h.begin() + w * slot, h.begin() + (w + 1) * slot, out.holes.begin() + ((w * rows + row) * cols + col) * slot,
-                           [](const TenElemT &x) { return ComplexConjugate(x); });
-        }
-        if (col + 1 < cols) {
-          std::vector<TenElemT> e = self->EvaluateBondEnergy({row, col}, {row, col + 1}, HORIZONTAL, comp, inv_psi);
-          for (size_t w = 0; w < n; ++w) out.energy[w] += e[w];
-          c.ShiftBTenWindow(RIGHT);                                           // :200
-        }
-      }
-      }
-      if constexpr (has_nnn_interaction) {                                    // :203-265
-        // (the diagonal bonds of the row pair: ONE pepsgpu_nnn_exchange_slice for a model with the scalar hook NNNEnergyFromExchange;
-        // a fermionic diagonal hop keeps its twisted-environment path through the hooks.  The slice needs the BMPS pair of the row and
-        // inv_psi only, both there on either branch above: unlike dev_slice it does not depend on where the holes go.)
-        bool nnn_slice = false;
-        if constexpr (HasExchangeNNNEnergy<ExplicitlyModel>::value) nnn_slice = DeviceSlicesEnabled() && !comp.fermion;
-        if (row + 1 < rows && nnn_slice) {
-          if constexpr (HasExchangeNNNEnergy<ExplicitlyModel>::value)
-            NNNSliceEnergies(*self, comp, row, inv_psi, [&](size_t w, size_t, TenElemT e1, TenElemT e2) { out.energy[w] += e1 + e2; });
-        } else if (row + 1 < rows) {
-          c.InitBTen2(LEFT, row);
-          c.GrowFullBTen2(RIGHT, row, 2, true);
-          for (size_t col = 0; col + 1 < cols; col++) {
-            std::vector<TenElemT> e1 = self->EvaluateNNNEnergy({row, col}, {row + 1, col + 1}, LEFTUP_TO_RIGHTDOWN, comp, inv_psi);
-            std::vector<TenElemT> e2 = self->EvaluateNNNEnergy({row + 1, col}, {row, col + 1}, LEFTDOWN_TO_RIGHTUP, comp, inv_psi);
-            for (size_t w = 0; w < n; ++w) out.energy[w] += e1[w] + e2[w];
-            c.ShiftBTen2Window(RIGHT, row);
-          }
-        }
-      }
-      if (row + 1 < rows) c.ShiftBMPSWindow(DOWN);                            // :126
-    }
-    comp.SetOrder(COL_MAJOR);
-    c.GenerateBMPSApproach(LEFT);                                            // bond_traversal_mixin.h:120
-    for (size_t col = 0; col < cols; col++) {
-      if (dev_slice) {
-        slice_energy(VERTICAL, col, false);
-      } else {
-        c.InitBTen(UP, col);
-        c.GrowFullBTen(DOWN, col, 2, true);
-        std::vector<TenElemT> psi = c.Trace({0, col}, VERTICAL);
-        std::vector<TenElemT> inv_psi(n);
-        for (size_t w = 0; w < n; ++w) {
-          if (psi[w] == TenElemT(0.0)) throw std::runtime_error("Wavefunction amplitude is near zero, causing division by zero.");
-          inv_psi[w] = TenElemT(1.0) / psi[w];
-        }
-        out.psi_list.push_back(psi);
-        for (size_t row = 0; row + 1 < rows; row++) {
-          std::vector<TenElemT> e = self->EvaluateBondEnergy({row, col}, {row + 1, col}, VERTICAL, comp, inv_psi);
-          for (size_t w = 0; w < n; ++w) out.energy[w] += e[w];
-          if (row + 2 < rows) c.ShiftBTenWindow(DOWN);
-        }
-      }
-      if (col + 1 < cols) c.ShiftBMPSWindow(RIGHT);
-    }
+        });
     for (size_t w = 0; w < n; ++w) out.energy[w] += self->EvaluateTotalOnsiteEnergy(comp.config, w);   // :99-101
     return out;
   }
@@ -1856,11 +1966,25 @@ struct ObservableMeta {                                        // model_measurem
 template <typename TenElemT>
 struct PsiSummaryT { std::vector<TenElemT> psi_mean; std::vector<double> psi_rel_err; };
 using PsiSummary = PsiSummaryT<double>;
+template <typename TenElemT>
+inline std::pair<TenElemT, double> ComputePsiConsistencySummaryAligned(const std::vector<TenElemT> &psi_list);
 // what a (non-templated) solver object keeps of its last sample; As<TenElemT>() hands it back in the caller's element type
 struct PsiSummaryStore {
   std::vector<std::complex<double>> psi_mean;
   std::vector<double> psi_rel_err;
-  void assign(size_t n) { psi_mean.assign(n, 0.0); psi_rel_err.assign(n, 0.0); }
+  // per walker the summary of its amplitudes along the passes of a traversal, psi_list [pass][walker]
+  template <typename TenElemT>
+  void Fill(size_t n, const std::vector<std::vector<TenElemT>> &psi_list) {
+    psi_mean.assign(n, 0.0);
+    psi_rel_err.assign(n, 0.0);
+    std::vector<TenElemT> one(psi_list.size());
+    for (size_t w = 0; w < n; ++w) {
+      for (size_t k = 0; k < one.size(); ++k) one[k] = psi_list[k][w];
+      const auto s = ComputePsiConsistencySummaryAligned(one);
+      psi_mean[w] = s.first;
+      psi_rel_err[w] = s.second;
+    }
+  }
   template <typename TenElemT>
   PsiSummaryT<TenElemT> As() const {
     PsiSummaryT<TenElemT> out;
@@ -1950,151 +2074,53 @@ struct HasSCPairCorrelation<U, std::void_t<decltype(std::declval<const U &>().Is
 template <class ModelType, bool has_nnn_interaction = true>
 class SquareNNNModelMeasurementSolver {
  public:
-  // The registry of a fermionic model (square_nnn_model_measurement_solver.h:33-215 on a fermionic index; square_tJ_model.h:546-603).
-  // Row pass in ROW_MAJOR order, column pass in COL_MAJOR order -- the traversal of the energy solver -- so that the two sites of every
-  // bond are adjacent modes.  Per bond the energy hook and, with enable_sc_measurement, the pair estimator:
+  // The registry of a fermionic model (square_nnn_model_measurement_solver.h:33-215 on a fermionic index; square_tJ_model.h:546-603) over
+  // TraverseNNBonds, the traversal of the energy solver.  Per bond the energy hook and, with enable_sc_measurement, the pair estimator:
   //   rho(S') = jw psi(S') / psi(S) = sign ReplaceNNSiteTrace / Trace,  sign = Sigma(S') / Sigma(S) = -1 for a move that changes the
   //   fermion number by +-2 (the decoration leaves Sigma = (-1)^(nf (nf + 1) / 2) out; the column pass's ratio carries jw by itself),
   //   registry value (conj(delta_dag) + delta) / 2 of BondSCFromPairs.
-  // Slice path (default): ONE pepsgpu_nn_pair_slice_fermion per row / column serves psi, the exchanged amplitude of
-  // BondEnergyFromExchange and the pair candidates from one read-back.  PEPSHOST_NO_DEVICE_SWEEP=1: the per-bond hooks
-  // EvaluateBondEnergy / EvaluateBondSC.  The diagonal bonds (has_nnn_interaction): FermionNNNBondEnergies of the model, zeros where
-  // t2 = 0.
+  // Slice path (default): ONE pepsgpu_nn_pair_slice_fermion (kHopBondEnergy: pepsgpu_nn_hop_slice_fermion) per row / column.
+  // PEPSHOST_NO_DEVICE_SWEEP=1: the per-bond hooks EvaluateBondEnergy / EvaluateBondSC.  The diagonal bonds (has_nnn_interaction):
+  // FermionNNNBondEnergies of the model, zeros where t2 = 0.
   template <typename TenElemT>
   ObservableMapT<TenElemT> EvaluateFermionObservables(TPSWaveFunctionComponentT<TenElemT> &comp) {
     if (!comp.fermion) throw std::logic_error("EvaluateObservables: a fermionic model needs the fermionic decoration of the component");
     auto &c = comp.contractor;
     auto *derived = static_cast<ModelType *>(this);
-    const FermionDecoration &fd = *comp.fermion;
-    const size_t ly = c.rows(), lx = c.cols(), n = comp.config.walkers(), sites = ly * lx;
+    const size_t ly = c.rows(), lx = c.cols(), n = comp.config.walkers();
     constexpr bool sc = HasSCMeasurement<ModelType>::value;
-    ObservableMapT<TenElemT> out;
-    out.n = n;
-    if constexpr (ModelType::requires_spin_sz_measurement) {
-      auto &sz = out.make("spin_z", sites);
-      for (size_t w = 0; w < n; ++w)
-        for (size_t s = 0; s < sites; ++s) sz[w * sites + s] = derived->CalSpinSzImpl(comp.config(w, {s / lx, s % lx}));
-    }
-    if constexpr (ModelType::requires_density_measurement) {
-      auto &ch = out.make("charge", sites);
-      for (size_t w = 0; w < n; ++w)
-        for (size_t s = 0; s < sites; ++s) ch[w * sites + s] = derived->CalDensityImpl(comp.config(w, {s / lx, s % lx}));
-    }
-    const size_t len_h = ly * (lx - 1), len_v = (ly - 1) * lx;
-    auto &e_h = out.make("bond_energy_h", len_h);
-    auto &e_v = out.make("bond_energy_v", len_v);
+    ObservableMapT<TenElemT> out = SiteObservables(comp);
+    NNBondMaps<TenElemT> maps(out, ly, lx);
     std::vector<TenElemT> *sc_h = nullptr, *sc_v = nullptr;
     if constexpr (sc) {
-      sc_h = &out.make("SC_bond_singlet_h", len_h);
-      sc_v = &out.make("SC_bond_singlet_v", len_v);
+      sc_h = &out.make("SC_bond_singlet_h", ly * (lx - 1));
+      sc_v = &out.make("SC_bond_singlet_v", (ly - 1) * lx);
     }
-    std::vector<TenElemT> total(n, TenElemT(0.0));
-    std::vector<std::vector<TenElemT>> psi_list;
-    auto nonzero = [](const TenElemT &psi) {
-      if (psi == TenElemT(0.0)) throw std::runtime_error("Wavefunction amplitude is near zero, causing division by zero.");
-    };
-    // bond j of a slice -> its place in the h / v arrays of walker w
-    auto put = [&](BondOrientation dir, size_t slice, size_t j, size_t w, TenElemT e, TenElemT scv) {
-      const size_t k = dir == HORIZONTAL ? w * len_h + slice * (lx - 1) + j : w * len_v + j * lx + slice;
-      (dir == HORIZONTAL ? e_h : e_v)[k] = e;
-      total[w] += e;
-      if constexpr (sc) (*(dir == HORIZONTAL ? sc_h : sc_v))[k] = scv;
-    };
     bool use_slice = false;
     if constexpr (HasExchangeBondEnergy<ModelType>::value && HasExchangeBondPsiPerBond<ModelType>::value) use_slice = DeviceSlicesEnabled();
     if constexpr (HasHopBondEnergy<ModelType>::value) use_slice = DeviceSlicesEnabled();
-    std::vector<int32_t> occ(fd.d()), ptab(4 * fd.d() * fd.d(), -1);
-    for (size_t s = 0; s < occ.size(); ++s) occ[s] = fd.n((int32_t)s);
-    if constexpr (sc) ptab = derived->PairTable();
-    auto slice_pass = [&](BondOrientation dir, size_t slice) {
-      if constexpr (HasHopBondEnergy<ModelType>::value) {          // (ONE pepsgpu_nn_hop_slice_fermion: psi and the two hops of every bond)
-        const size_t N = dir == HORIZONTAL ? lx : ly, np = N - 1;
-        std::vector<TenElemT> psi(n * np), hop(n * np * 2), psi0(n);
-        const std::vector<int32_t> htab = derived->HopTable();
-        check_rc(pepsgpu_nn_hop_slice_fermion(c.ctx(), dir, (int)slice, 0, (int)fd.d(), occ.data(), htab.data(), dptr(psi.data()),
-                                              dptr(hop.data())), c.ctx());
-        for (size_t w = 0; w < n; ++w) {
-          for (size_t j = 0; j < np; ++j) {
-            const SiteIdx s1 = dir == HORIZONTAL ? SiteIdx{slice, j} : SiteIdx{j, slice};
-            const SiteIdx s2 = dir == HORIZONTAL ? SiteIdx{slice, j + 1} : SiteIdx{j + 1, slice};
-            const size_t k = w * np + j;
-            nonzero(psi[k]);
-            put(dir, slice, j, w, derived->BondEnergyFromHops(comp.config(w, s1), comp.config(w, s2), ComplexConjugate(TenElemT(hop[2 * k] / psi[k])),
-                                                              ComplexConjugate(TenElemT(hop[2 * k + 1] / psi[k]))), TenElemT(0.0));
-          }
-          psi0[w] = np ? psi[w * np] : TenElemT(1.0);
-        }
-        psi_list.push_back(psi0);
-      } else if constexpr (HasExchangeBondEnergy<ModelType>::value) {
-        const size_t N = dir == HORIZONTAL ? lx : ly, np = N - 1;
-        std::vector<TenElemT> psi(n * np), ex(n * np), pair(n * np * 2), psi0(n);
-        const std::vector<int32_t> xtab = comp.ExchangeTable();
-        check_rc(pepsgpu_nn_pair_slice_fermion(c.ctx(), dir, (int)slice, (int)fd.d(), occ.data(), ptab.data(), xtab.data(), dptr(psi.data()),
-                                               dptr(ex.data()), dptr(pair.data())), c.ctx());
-        for (size_t w = 0; w < n; ++w) {
-          for (size_t j = 0; j < np; ++j) {
-            const SiteIdx s1 = dir == HORIZONTAL ? SiteIdx{slice, j} : SiteIdx{j, slice};
-            const SiteIdx s2 = dir == HORIZONTAL ? SiteIdx{slice, j + 1} : SiteIdx{j + 1, slice};
-            const size_t k = w * np + j;
-            nonzero(psi[k]);
-            const int32_t c1 = comp.config(w, s1), c2 = comp.config(w, s2);
-            const TenElemT e = derived->BondEnergyFromExchange(c1, c2, ComplexConjugate(TenElemT(ex[k] / psi[k])));
-            TenElemT scv(0.0);
-            if constexpr (sc) {
-              const auto dd = derived->BondSCFromPairs(c1, c2, TenElemT(pair[2 * k] / psi[k]), TenElemT(pair[2 * k + 1] / psi[k]));
-              scv = (ComplexConjugate(dd.first) + dd.second) / TenElemT(2.0);
+    const std::vector<std::vector<TenElemT>> psi_list = TraverseNNBonds(
+        comp, use_slice, HoleDest<TenElemT>(), SquareModelBonds<ModelType, TenElemT, true, sc>(*derived, comp),
+        [&](const SliceSites &s, size_t j, const BondValues<TenElemT> &v) {
+          maps.Put(s, j, v.e);
+          if constexpr (sc)
+            for (size_t w = 0; w < n; ++w) (*(s.dir == HORIZONTAL ? sc_h : sc_v))[maps.Index(s, j, w)] = v.sc[w];
+        },
+        [](const SliceSites &, const std::vector<TenElemT> &) {},
+        [&] {
+          // SC_singlet_pair_corr inside the row-major phase: its walkers fork from every level of the UP stack and close on every level
+          // of the DOWN stack, so the UP stack is grown in full for it and cut back to the vacuum the row pass starts from
+          if constexpr (HasSCPairCorrelation<ModelType>::value) {
+            if (derived->IsSingletPairCorrelationEnabled()) {
+              c.GrowFullBMPS(UP);
+              derived->MeasureSingletPairCorrelation(comp, out);
+              c.DeleteInnerBMPS(UP);
             }
-            put(dir, slice, j, w, e, scv);
           }
-          psi0[w] = np ? psi[w * np] : TenElemT(1.0);         // (the first bond's window is the slice's first window)
-        }
-        psi_list.push_back(psi0);
-      }
-    };
-    auto hook_pass = [&](BondOrientation dir, size_t slice) {
-      const size_t N = dir == HORIZONTAL ? lx : ly;
-      if (dir == HORIZONTAL) { c.InitBTen(LEFT, slice); c.GrowFullBTen(RIGHT, slice, 1, true); }
-      else { c.InitBTen(UP, slice); c.GrowFullBTen(DOWN, slice, 2, true); }
-      psi_list.push_back(c.Trace(dir == HORIZONTAL ? SiteIdx{slice, 0} : SiteIdx{0, slice}, dir));
-      for (const TenElemT &p : psi_list.back()) nonzero(p);
-      const std::vector<TenElemT> unused;                      // (the fermionic hooks take psi from their own Trace)
-      for (size_t j = 0; j + 1 < N; ++j) {
-        const SiteIdx s1 = dir == HORIZONTAL ? SiteIdx{slice, j} : SiteIdx{j, slice};
-        const SiteIdx s2 = dir == HORIZONTAL ? SiteIdx{slice, j + 1} : SiteIdx{j + 1, slice};
-        const std::vector<TenElemT> e = derived->EvaluateBondEnergy(s1, s2, dir, comp, unused);
-        std::vector<TenElemT> scv(n, TenElemT(0.0));
-        if constexpr (sc) {
-          const auto dd = derived->EvaluateBondSC(s1, s2, dir, comp);
-          for (size_t w = 0; w < n; ++w) scv[w] = (ComplexConjugate(dd[w].first) + dd[w].second) / TenElemT(2.0);
-        }
-        for (size_t w = 0; w < n; ++w) put(dir, slice, j, w, e[w], scv[w]);
-        if (dir == HORIZONTAL || j + 2 < N) c.ShiftBTenWindow(dir == HORIZONTAL ? RIGHT : DOWN);
-      }
-    };
-    comp.SetOrder(ROW_MAJOR);
-    c.GenerateBMPSApproach(UP);
-    if constexpr (HasSCPairCorrelation<ModelType>::value) {
-      // SC_singlet_pair_corr inside the row-major phase: its walkers fork from every level of the UP stack and close on every level of
-      // the DOWN stack, so the UP stack is grown in full for it and cut back to the vacuum the row pass starts from
-      if (derived->IsSingletPairCorrelationEnabled()) {
-        c.GrowFullBMPS(UP);
-        derived->MeasureSingletPairCorrelation(comp, out);
-        c.DeleteInnerBMPS(UP);
-      }
-    }
-    for (size_t row = 0; row < ly; ++row) {
-      if (use_slice) slice_pass(HORIZONTAL, row); else hook_pass(HORIZONTAL, row);
-      if (row + 1 < ly) c.ShiftBMPSWindow(DOWN);
-    }
-    comp.SetOrder(COL_MAJOR);
-    c.GenerateBMPSApproach(LEFT);
-    for (size_t col = 0; col < lx; ++col) {
-      if (use_slice) slice_pass(VERTICAL, col); else hook_pass(VERTICAL, col);
-      if (col + 1 < lx) c.ShiftBMPSWindow(RIGHT);
-    }
+        });
     // (the same order of additions as the energy solver: bonds, on-site term, diagonal hops)
     auto &en = out.make("energy", 1);
-    for (size_t w = 0; w < n; ++w) en[w] = total[w] + derived->EvaluateTotalOnsiteEnergy(comp.config, w);
+    for (size_t w = 0; w < n; ++w) en[w] = maps.total[w] + derived->EvaluateTotalOnsiteEnergy(comp.config, w);
     if constexpr (has_nnn_interaction) {
       const size_t len_d = (ly - 1) * (lx - 1);
       std::vector<TenElemT> both(n * len_d * 2, TenElemT(0.0));
@@ -2103,14 +2129,7 @@ class SquareNNNModelMeasurementSolver {
       auto &e_ur = out.make("bond_energy_ur", len_d);
       for (size_t k = 0; k < n * len_d; ++k) { e_dr[k] = both[2 * k]; e_ur[k] = both[2 * k + 1]; }
     }
-    last_psi_.assign(n);
-    std::vector<TenElemT> one(psi_list.size());
-    for (size_t w = 0; w < n; ++w) {
-      for (size_t k = 0; k < psi_list.size(); ++k) one[k] = psi_list[k][w];
-      auto s = ComputePsiConsistencySummaryAligned(one);
-      last_psi_.psi_mean[w] = s.first;
-      last_psi_.psi_rel_err[w] = s.second;
-    }
+    last_psi_.Fill(n, psi_list);
     return out;
   }
   template <typename TenElemT>
@@ -2121,143 +2140,44 @@ class SquareNNNModelMeasurementSolver {
       return EvaluateBosonObservables(comp);
     }
   }
+  // The registry of a bosonic model over the same traversal.  A model of the diagonal-bond traversal with both scalar hooks
+  // (BondEnergyFromExchange, NNNEnergyFromExchange) on a bosonic component takes the device slices of the energy solver:
+  // pepsgpu_nn_exchange_slice_tab per row / column (no holes) and pepsgpu_nnn_exchange_slice per row pair.
+  // MeasureSpinOneHalfOffDiagOrderInRow continues from the BTen stacks the row's bonds leave.  The slice (GrowFullBTen(RIGHT, row, 2)
+  // and no shift behind the last bond) ends with LEFT over [0, lx - 2) where the hook loop ends with LEFT over [0, lx - 1), both with the
+  // RIGHT stack down to its vacuum; the routine's UpdateLocal at column lx / 4 cuts LEFT back to [0, lx / 4) either way (lx / 4 <=
+  // lx - 2 whenever a row has a bond), so it grows the same tensors from the same state.
   template <typename TenElemT>
   ObservableMapT<TenElemT> EvaluateBosonObservables(TPSWaveFunctionComponentT<TenElemT> &comp) {
     auto &c = comp.contractor;
     auto *derived = static_cast<ModelType *>(this);
     const size_t ly = c.rows(), lx = c.cols(), n = comp.config.walkers();
-    ObservableMapT<TenElemT> out;
-    out.n = n;
-    if constexpr (ModelType::requires_spin_sz_measurement) {
-      auto &sz = out.make("spin_z", ly * lx);
-      for (size_t w = 0; w < n; ++w)
-        for (size_t r = 0; r < ly; ++r)
-          for (size_t cc = 0; cc < lx; ++cc) sz[w * ly * lx + r * lx + cc] = derived->CalSpinSzImpl(comp.config(w, {r, cc}));
-    }
-    if constexpr (ModelType::requires_density_measurement) {
-      auto &ch = out.make("charge", ly * lx);
-      for (size_t w = 0; w < n; ++w)
-        for (size_t r = 0; r < ly; ++r)
-          for (size_t cc = 0; cc < lx; ++cc) ch[w * ly * lx + r * lx + cc] = derived->CalDensityImpl(comp.config(w, {r, cc}));
-    }
-    auto &e_h = out.make("bond_energy_h", ly * (lx - 1));
-    auto &e_v = out.make("bond_energy_v", (ly - 1) * lx);
+    ObservableMapT<TenElemT> out = SiteObservables(comp);
+    NNBondMaps<TenElemT> maps(out, ly, lx);
     std::vector<TenElemT> *e_dr = nullptr, *e_ur = nullptr;
     if constexpr (has_nnn_interaction) {
       e_dr = &out.make("bond_energy_dr", (ly - 1) * (lx - 1));
       e_ur = &out.make("bond_energy_ur", (ly - 1) * (lx - 1));
     }
-    std::vector<TenElemT> total(n, TenElemT(0.0));
-    std::vector<std::vector<TenElemT>> psi_list;
-    auto inverse = [&](const std::vector<TenElemT> &psi) {
-      std::vector<TenElemT> inv(n);
-      for (size_t w = 0; w < n; ++w) {
-        if (psi[w] == TenElemT(0.0)) throw std::runtime_error("Wavefunction amplitude is near zero, causing division by zero.");
-        inv[w] = TenElemT(1.0) / psi[w];
-      }
-      return inv;
-    };
-    // A model of the diagonal-bond traversal with both scalar hooks (BondEnergyFromExchange, NNNEnergyFromExchange) on a bosonic
-    // component takes the device slices of the energy solver: pepsgpu_nn_exchange_slice_tab per row / column (no holes) and
-    // pepsgpu_nnn_exchange_slice per row pair -- the same operations in the same order, one read-back each.
-    // PEPSHOST_NO_DEVICE_SWEEP=1 keeps the hooks.
-    // MeasureSpinOneHalfOffDiagOrderInRow continues from the BTen stacks the row's bonds leave.  The slice (GrowFullBTen(RIGHT, row, 2)
-    // and no shift behind the last bond) ends with LEFT over [0, lx - 2) where the hook loop ends with LEFT over [0, lx - 1), both with the
-    // RIGHT stack down to its vacuum; the routine's UpdateLocal at column lx / 4 cuts LEFT back to [0, lx / 4) either way (lx / 4 <=
-    // lx - 2 whenever a row has a bond), so it grows the same tensors from the same state.
     bool meas_slice = false;
     if constexpr (has_nnn_interaction && HasExchangeBondEnergy<ModelType>::value && HasExchangeNNNEnergy<ModelType>::value)
       meas_slice = DeviceSlicesEnabled() && !comp.fermion;
-    // psi of the slice into psi_list, the bond energies through put(w, j, e)
-    auto slice_bonds = [&](BondOrientation dir, size_t slice, auto &&put) {
-      if constexpr (HasExchangeBondEnergy<ModelType>::value) {
-        const size_t N = dir == HORIZONTAL ? lx : ly;
-        std::vector<TenElemT> psi(n), ex(n * (N - 1));
-        check_rc(pepsgpu_nn_exchange_slice_tab(c.ctx(), dir, (int)slice, 0, nullptr, 0, dptr(psi.data()), dptr(ex.data())), c.ctx());
-        psi_list.push_back(psi);
-        const std::vector<TenElemT> inv = inverse(psi);
-        for (size_t w = 0; w < n; ++w)
-          for (size_t j = 0; j + 1 < N; ++j) {
-            const SiteIdx s1 = dir == HORIZONTAL ? SiteIdx{slice, j} : SiteIdx{j, slice};
-            const SiteIdx s2 = dir == HORIZONTAL ? SiteIdx{slice, j + 1} : SiteIdx{j + 1, slice};
-            const TenElemT e = derived->BondEnergyFromExchange(comp.config(w, s1), comp.config(w, s2),
-                                                               ComplexConjugate(TenElemT(ex[w * (N - 1) + j] * inv[w])));
-            put(w, j, e);
-            total[w] += e;
-          }
-      }
-    };
-    comp.SetOrder(ROW_MAJOR);
-    c.GenerateBMPSApproach(UP);
-    for (size_t row = 0; row < ly; ++row) {
-      if (meas_slice) {
-        slice_bonds(HORIZONTAL, row, [&](size_t w, size_t col, TenElemT e) { e_h[w * ly * (lx - 1) + row * (lx - 1) + col] = e; });
-      } else {
-        c.InitBTen(LEFT, row);
-        c.GrowFullBTen(RIGHT, row, 1, true);
-        psi_list.push_back(c.Trace({row, 0}, HORIZONTAL));
-      }
-      const std::vector<TenElemT> inv_psi = inverse(psi_list.back());
-      for (size_t col = 0; !meas_slice && col + 1 < lx; ++col) {
-        std::vector<TenElemT> e = derived->EvaluateBondEnergy({row, col}, {row, col + 1}, HORIZONTAL, comp, inv_psi);
-        for (size_t w = 0; w < n; ++w) { e_h[w * ly * (lx - 1) + row * (lx - 1) + col] = e[w]; total[w] += e[w]; }
-        c.ShiftBTenWindow(RIGHT);
-      }
-      if constexpr (has_nnn_interaction) {
-        if (row + 1 < ly && meas_slice) {
-          if constexpr (HasExchangeNNNEnergy<ModelType>::value)
-            NNNSliceEnergies(*derived, comp, row, inv_psi, [&](size_t w, size_t col, TenElemT e1, TenElemT e2) {
-              const size_t k = w * (ly - 1) * (lx - 1) + row * (lx - 1) + col;
+    const std::vector<std::vector<TenElemT>> psi_list = TraverseNNBonds(
+        comp, meas_slice, HoleDest<TenElemT>(), SquareModelBonds<ModelType, TenElemT, false, false>(*derived, comp),
+        [&](const SliceSites &s, size_t j, const BondValues<TenElemT> &v) { maps.Put(s, j, v.e); },
+        [&](const SliceSites &s, const std::vector<TenElemT> &inv_psi) {
+          if (s.dir != HORIZONTAL) return;
+          if constexpr (has_nnn_interaction)
+            NNNBondEnergies(*derived, comp, meas_slice, s.num, inv_psi, [&](size_t w, size_t col, TenElemT e1, TenElemT e2) {
+              const size_t k = w * (ly - 1) * (lx - 1) + s.num * (lx - 1) + col;
               (*e_dr)[k] = e1; (*e_ur)[k] = e2;
-              total[w] += e1 + e2;
+              maps.total[w] += e1 + e2;
             });
-        } else if (row + 1 < ly) {
-          c.InitBTen2(LEFT, row);
-          c.GrowFullBTen2(RIGHT, row, 2, true);
-          for (size_t col = 0; col + 1 < lx; ++col) {
-            std::vector<TenElemT> e1 = derived->EvaluateNNNEnergy({row, col}, {row + 1, col + 1}, LEFTUP_TO_RIGHTDOWN, comp, inv_psi);
-            std::vector<TenElemT> e2 = derived->EvaluateNNNEnergy({row + 1, col}, {row, col + 1}, LEFTDOWN_TO_RIGHTUP, comp, inv_psi);
-            for (size_t w = 0; w < n; ++w) {
-              const size_t k = w * (ly - 1) * (lx - 1) + row * (lx - 1) + col;   // LEFTDOWN anchor mapped to the top cell (:155)
-              (*e_dr)[k] = e1[w]; (*e_ur)[k] = e2[w];
-              total[w] += e1[w] + e2[w];
-            }
-            c.ShiftBTen2Window(RIGHT, row);
-          }
-        }
-      }
-      derived->EvaluateOffDiagOrderInRow(comp, row, inv_psi, out);
-      if (row + 1 < ly) c.ShiftBMPSWindow(DOWN);
-    }
-    comp.SetOrder(COL_MAJOR);
-    c.GenerateBMPSApproach(LEFT);
-    for (size_t col = 0; col < lx; ++col) {
-      if (meas_slice) {
-        slice_bonds(VERTICAL, col, [&](size_t w, size_t row, TenElemT e) { e_v[w * (ly - 1) * lx + row * lx + col] = e; });
-        if (col + 1 < lx) c.ShiftBMPSWindow(RIGHT);
-        continue;
-      }
-      c.InitBTen(UP, col);
-      c.GrowFullBTen(DOWN, col, 2, true);
-      psi_list.push_back(c.Trace({0, col}, VERTICAL));
-      const std::vector<TenElemT> inv_psi = inverse(psi_list.back());
-      for (size_t row = 0; row + 1 < ly; ++row) {
-        std::vector<TenElemT> e = derived->EvaluateBondEnergy({row, col}, {row + 1, col}, VERTICAL, comp, inv_psi);
-        for (size_t w = 0; w < n; ++w) { e_v[w * (ly - 1) * lx + row * lx + col] = e[w]; total[w] += e[w]; }
-        if (row + 2 < ly) c.ShiftBTenWindow(DOWN);
-      }
-      if (col + 1 < lx) c.ShiftBMPSWindow(RIGHT);
-    }
+          derived->EvaluateOffDiagOrderInRow(comp, s.num, inv_psi, out);
+        });
     auto &en = out.make("energy", 1);
-    last_psi_.assign(n);
-    std::vector<TenElemT> one(psi_list.size());
-    for (size_t w = 0; w < n; ++w) {
-      en[w] = total[w] + derived->EvaluateTotalOnsiteEnergy(comp.config, w);
-      for (size_t k = 0; k < psi_list.size(); ++k) one[k] = psi_list[k][w];
-      auto s = ComputePsiConsistencySummaryAligned(one);
-      last_psi_.psi_mean[w] = s.first;
-      last_psi_.psi_rel_err[w] = s.second;
-    }
+    for (size_t w = 0; w < n; ++w) en[w] = maps.total[w] + derived->EvaluateTotalOnsiteEnergy(comp.config, w);
+    last_psi_.Fill(n, psi_list);
     return out;
   }
   // psi summary of the sample the last EvaluateObservables call saw (model_measurement_solver.h:101-118, cached path)
@@ -2281,6 +2201,40 @@ class SquareNNNModelMeasurementSolver {
     return out;
   }
  private:
+  // a registry with the per-site observables of the configuration: spin_z, charge
+  template <typename TenElemT>
+  ObservableMapT<TenElemT> SiteObservables(const TPSWaveFunctionComponentT<TenElemT> &comp) {
+    auto *derived = static_cast<ModelType *>(this);
+    const size_t lx = comp.contractor.cols(), sites = comp.contractor.rows() * lx;
+    ObservableMapT<TenElemT> out;
+    out.n = comp.config.walkers();
+    if constexpr (ModelType::requires_spin_sz_measurement) {
+      auto &sz = out.make("spin_z", sites);
+      for (size_t w = 0; w < out.n; ++w)
+        for (size_t s = 0; s < sites; ++s) sz[w * sites + s] = derived->CalSpinSzImpl(comp.config(w, {s / lx, s % lx}));
+    }
+    if constexpr (ModelType::requires_density_measurement) {
+      auto &ch = out.make("charge", sites);
+      for (size_t w = 0; w < out.n; ++w)
+        for (size_t s = 0; s < sites; ++s) ch[w * sites + s] = derived->CalDensityImpl(comp.config(w, {s / lx, s % lx}));
+    }
+    return out;
+  }
+  // bond_energy_h / _v of a registry and the running total per walker; Index: bond j of a slice -> its place in the h / v arrays
+  template <typename TenElemT>
+  struct NNBondMaps {
+    size_t ly, lx;
+    std::vector<TenElemT> &e_h, &e_v, total;
+    NNBondMaps(ObservableMapT<TenElemT> &out, size_t ly_, size_t lx_)
+        : ly(ly_), lx(lx_), e_h(out.make("bond_energy_h", ly * (lx - 1))), e_v(out.make("bond_energy_v", (ly - 1) * lx)), total(out.n, TenElemT(0.0)) {}
+    size_t Index(const SliceSites &s, size_t j, size_t w) const {
+      return s.dir == HORIZONTAL ? w * ly * (lx - 1) + s.num * (lx - 1) + j : w * (ly - 1) * lx + j * lx + s.num;
+    }
+    void Put(const SliceSites &s, size_t j, const std::vector<TenElemT> &e) {
+      auto &dst = s.dir == HORIZONTAL ? e_h : e_v;
+      for (size_t w = 0; w < e.size(); ++w) { dst[Index(s, j, w)] = e[w]; total[w] += e[w]; }
+    }
+  };
   PsiSummaryStore last_psi_;
 };
 template <class ModelType>
@@ -2643,14 +2597,7 @@ class SpinOneHalfTriJ1J2HeisenbergSqrPEPS : public SpinOneHalfMeasurementHooks {
         for (size_t j = i; j < N; ++j)
           all[k++] = comp.config(w, {i / lx, i % lx}) == comp.config(w, {j / lx, j % lx}) ? 0.25 : -0.25;
     }
-    last_psi_.assign(n);
-    std::vector<TenElemT> one(scratch.psi_list.size());
-    for (size_t w = 0; w < n; ++w) {
-      for (size_t k = 0; k < one.size(); ++k) one[k] = scratch.psi_list[k][w];
-      auto s = ComputePsiConsistencySummaryAligned(one);
-      last_psi_.psi_mean[w] = s.first;
-      last_psi_.psi_rel_err[w] = s.second;
-    }
+    last_psi_.Fill(n, scratch.psi_list);
     return out;
   }
   PsiSummary EvaluatePsiSummary() const { return last_psi_.As<double>(); }
@@ -2689,153 +2636,104 @@ class SpinOneHalfTriJ1J2HeisenbergSqrPEPS : public SpinOneHalfMeasurementHooks {
       if (comp.config(w, s1) != comp.config(w, s2)) e[w] = -0.25 + ComplexConjugate(TenElemT(psi_ex[w] * inv_psi[w])) * 0.5;
     return e;
   }
+  // ... with psi_ex = value(w) from a slice's table
+  template <typename TenElemT, class Value>
+  static std::vector<TenElemT> SliceBond(const TPSWaveFunctionComponentT<TenElemT> &comp, const SiteIdx &s1, const SiteIdx &s2,
+                                         const std::vector<TenElemT> &inv_psi, Value value) {
+    std::vector<TenElemT> e(inv_psi.size(), TenElemT(0.25));
+    for (size_t w = 0; w < e.size(); ++w)
+      if (comp.config(w, s1) != comp.config(w, s2)) e[w] = -0.25 + ComplexConjugate(TenElemT(value(w) * inv_psi[w])) * 0.5;
+    return e;
+  }
+  // the h / v bonds for TraverseNNBonds: the exchange slice, or a ReplaceNNSiteTrace per bond
+  template <typename TenElemT>
+  struct NNBonds {
+    TPSWaveFunctionComponentT<TenElemT> &comp;
+    BondSlice<TenElemT> Read(const SliceSites &s, bool holes) const { return ExchangeSlice(comp, s, holes, false); }
+    std::vector<TenElemT> FromSlice(const SliceSites &s, size_t j, const BondSlice<TenElemT> &sl, const std::vector<TenElemT> &inv_psi) const {
+      return SliceBond(comp, s.at(j), s.at(j + 1), inv_psi, [&](size_t w) { return sl.ex[w * sl.np + j]; });
+    }
+    std::vector<TenElemT> Hook(const SliceSites &s, size_t j, const std::vector<TenElemT> &inv_psi) const {
+      const SiteIdx s1 = s.at(j), s2 = s.at(j + 1);
+      return Bond<TenElemT>(comp, s1, s2, inv_psi, [&](const std::vector<int32_t> &cand) { return comp.ReplaceNNSiteTrace(s1, s2, s.dir, 1, cand); });   // :338-345
+    }
+  };
+  // on_bond(kind, site1, site2, e [walker]) for every bond and link in the order of CalEnergyAndHolesImpl (:304-446); the holes and the
+  // psi list into out.  The h / v bonds are those of TraverseNNBonds (under the device-slice condition of SquareNNNModelEnergySolver:
+  // no holes, or holes resident on the device); the links of a row pair / column pair hang behind the row / column: ONE
+  // pepsgpu_link_exchange_slice each with the device slices (bosonic component; they do not depend on where the holes go), else a
+  // trace per link over the BTen2 of the pair.
   template <typename TenElemT, class OnBond>
   void Traverse(const SplitIndexTPST<TenElemT> &sitps, TPSWaveFunctionComponentT<TenElemT> &comp, bool calchols, bool holes_on_device,
                 EnergyAndHolesT<TenElemT> &out, OnBond on_bond) {
     auto &c = comp.contractor;
-    const size_t rows = c.rows(), cols = c.cols(), n = comp.config.walkers(), slot = sitps.slot();
-    if (calchols && !holes_on_device) out.holes.assign(n * rows * cols * slot, TenElemT(0.0));
-    auto inverse = [&](const std::vector<TenElemT> &psi) {
-      std::vector<TenElemT> inv(n);
-      for (size_t w = 0; w < n; ++w) {
-        if (psi[w] == TenElemT(0.0)) throw std::runtime_error("Wavefunction amplitude is near zero, causing division by zero.");
-        inv[w] = TenElemT(1.0) / psi[w];
-      }
-      return inv;
-    };
-    // With the device slices (DeviceSlicesEnabled(), bosonic component) a row or column of h / v bonds is ONE
-    // pepsgpu_nn_exchange_slice_tab call -- under the condition of SquareNNNModelEnergySolver: no holes, or holes resident on the device
-    // -- and the links of a row pair / column pair are ONE pepsgpu_link_exchange_slice call each: the same operations in the same order
-    // on the device, one read-back each, and on_bond sees the same bonds in the same order.  PEPSHOST_NO_DEVICE_SWEEP=1 keeps the
-    // per-bond path below.
+    const size_t rows = c.rows(), cols = c.cols(), n = comp.config.walkers();
     const bool link_slice = DeviceSlicesEnabled() && !comp.fermion;
     const bool nn_slice = link_slice && (!calchols || holes_on_device);
-    // 0.25 for equal spins, else -0.25 + 0.5 conj(psi_ex / psi) with psi_ex = value(w) from a slice's table
-    auto slice_bond = [&](const SiteIdx &s1, const SiteIdx &s2, const std::vector<TenElemT> &inv_psi, auto value) {
-      std::vector<TenElemT> e(n, TenElemT(0.25));
-      for (size_t w = 0; w < n; ++w)
-        if (comp.config(w, s1) != comp.config(w, s2)) e[w] = -0.25 + ComplexConjugate(TenElemT(value(w) * inv_psi[w])) * 0.5;
-      return e;
-    };
-    // the h bonds of row `slice` / the v bonds of column `slice` from the device; returns 1 / psi of the slice
-    auto nn_bonds = [&](BondOrientation dir, size_t slice, bool holes) {
-      const size_t N = dir == HORIZONTAL ? cols : rows;
-      std::vector<TenElemT> psi(n), ex(n * (N - 1));
-      check_rc(pepsgpu_nn_exchange_slice_tab(c.ctx(), dir, (int)slice, holes ? 1 : 0, nullptr, 0, dptr(psi.data()), dptr(ex.data())), c.ctx());
-      out.psi_list.push_back(psi);
-      const std::vector<TenElemT> inv_psi = inverse(psi);
-      for (size_t j = 0; j + 1 < N; ++j) {
-        const SiteIdx s1 = dir == HORIZONTAL ? SiteIdx{slice, j} : SiteIdx{j, slice};
-        const SiteIdx s2 = dir == HORIZONTAL ? SiteIdx{slice, j + 1} : SiteIdx{j + 1, slice};
-        on_bond(dir == HORIZONTAL ? BOND_H : BOND_V, s1, s2, slice_bond(s1, s2, inv_psi, [&](size_t w) { return ex[w * (N - 1) + j]; }));
-      }
-      return inv_psi;
-    };
-    // the link table [n][N - 1][4] of a row pair / column pair (pepsgpu_link_exchange_slice)
+    // the link table [n][N - 1][4] of a row pair / column pair
     auto links = [&](BondOrientation dir, size_t slice, int mask) {
       std::vector<TenElemT> val(n * ((dir == HORIZONTAL ? cols : rows) - 1) * 4);
       check_rc(pepsgpu_link_exchange_slice(c.ctx(), dir, (int)slice, mask, dptr(val.data())), c.ctx());
       return val;
     };
-    comp.SetOrder(ROW_MAJOR);
-    c.GenerateBMPSApproach(UP);                                              // :317
-    for (size_t row = 0; row < rows; row++) {
-      std::vector<TenElemT> inv_psi;
-      if (nn_slice) {
-        inv_psi = nn_bonds(HORIZONTAL, row, calchols);
-      } else {
-      c.InitBTen(LEFT, row);                                                 // :320
-      c.GrowFullBTen(RIGHT, row, 1, true);
-      out.psi_list.push_back(c.Trace({row, 0}, HORIZONTAL));                 // :322
-      inv_psi = inverse(out.psi_list.back());
-      for (size_t col = 0; col < cols; col++) {
-        const SiteIdx s1{row, col};
-        if (calchols && holes_on_device) {
-          c.PunchHoleStore(s1, HORIZONTAL);
-        } else if (calchols) {
-          std::vector<TenElemT> h = c.PunchHole(s1, HORIZONTAL);             // :329 hole_res(site) = Dag(hole)
-          for (size_t w = 0; w < n; ++w)
-            std::transform(h.begin() + w * slot, h.begin() + (w + 1) * slot, out.holes.begin() + ((w * rows + row) * cols + col) * slot,
-                           [](const TenElemT &x) { return ComplexConjugate(x); });
-        }
-        if (col + 1 < cols) {
-          const SiteIdx s2{row, col + 1};
-          on_bond(BOND_H, s1, s2, Bond<TenElemT>(comp, s1, s2, inv_psi, [&](const std::vector<int32_t> &cand) {
-                    return comp.ReplaceNNSiteTrace(s1, s2, HORIZONTAL, 1, cand); }));
-          c.ShiftBTenWindow(RIGHT);                                          // :346
-        }
-      }
-      }
-      if (row + 1 < rows && link_slice) {
+    auto row_links = [&](size_t row, const std::vector<TenElemT> &inv_psi) {
+      if (row + 1 >= rows) return;
+      if (link_slice) {
         const std::vector<TenElemT> val = links(HORIZONTAL, row, 1 | 2 | 8);   // both diagonals and the flat link (r+1, c)-(r, c+2)
         for (size_t col = 0; col + 1 < cols; col++) {
-          auto kind = [&](int k) { return [&val, col, k, np = cols - 1](size_t w) { return val[(w * np + col) * 4 + k]; }; };
-          on_bond(BOND_UR, {row + 1, col}, {row, col + 1}, slice_bond({row + 1, col}, {row, col + 1}, inv_psi, kind(1)));
-          on_bond(BOND_DR, {row, col}, {row + 1, col + 1}, slice_bond({row, col}, {row + 1, col + 1}, inv_psi, kind(0)));
-          if (col + 2 < cols) on_bond(BOND_FLAT, {row + 1, col}, {row, col + 2}, slice_bond({row + 1, col}, {row, col + 2}, inv_psi, kind(3)));
+          auto kind = [&val, col, np = cols - 1](int k) { return [&val, col, k, np](size_t w) { return val[(w * np + col) * 4 + k]; }; };
+          on_bond(BOND_UR, {row + 1, col}, {row, col + 1}, SliceBond(comp, {row + 1, col}, {row, col + 1}, inv_psi, kind(1)));
+          on_bond(BOND_DR, {row, col}, {row + 1, col + 1}, SliceBond(comp, {row, col}, {row + 1, col + 1}, inv_psi, kind(0)));
+          if (col + 2 < cols) on_bond(BOND_FLAT, {row + 1, col}, {row, col + 2}, SliceBond(comp, {row + 1, col}, {row, col + 2}, inv_psi, kind(3)));
         }
-        c.ShiftBMPSWindow(DOWN);
-      } else if (row + 1 < rows) {
-        c.InitBTen2(LEFT, row);                                              // :350
-        c.GrowFullBTen2(RIGHT, row, 2, true);
-        for (size_t col = 0; col + 1 < cols; col++) {
-          const SiteIdx lu{row, col};
-          {
-            const SiteIdx s1{row + 1, col}, s2{row, col + 1};                // :355-367 J1 diagonal
-            on_bond(BOND_UR, s1, s2, Bond<TenElemT>(comp, s1, s2, inv_psi, [&](const std::vector<int32_t> &cand) {
-                      return c.ReplaceNNNSiteTrace(lu, LEFTDOWN_TO_RIGHTUP, HORIZONTAL, 1, cand); }));
-          }
-          {
-            const SiteIdx s1{row, col}, s2{row + 1, col + 1};                // :369-381 J2 diagonal
-            on_bond(BOND_DR, s1, s2, Bond<TenElemT>(comp, s1, s2, inv_psi, [&](const std::vector<int32_t> &cand) {
-                      return c.ReplaceNNNSiteTrace(lu, LEFTUP_TO_RIGHTDOWN, HORIZONTAL, 1, cand); }));
-          }
-          if (col + 2 < cols) {                                              // :383-397 flat sqrt5 link
-            const SiteIdx s1{row + 1, col}, s2{row, col + 2};
-            on_bond(BOND_FLAT, s1, s2, Bond<TenElemT>(comp, s1, s2, inv_psi, [&](const std::vector<int32_t> &cand) {
-                      return c.ReplaceSqrt5DistTwoSiteTrace(lu, LEFTDOWN_TO_RIGHTUP, HORIZONTAL, 1, cand); }));
-          }
-          c.ShiftBTen2Window(RIGHT, row);                                    // :398
+        return;
+      }
+      c.InitBTen2(LEFT, row);                                                // :350
+      c.GrowFullBTen2(RIGHT, row, 2, true);
+      for (size_t col = 0; col + 1 < cols; col++) {
+        const SiteIdx lu{row, col};
+        {
+          const SiteIdx s1{row + 1, col}, s2{row, col + 1};                  // :355-367 J1 diagonal
+          on_bond(BOND_UR, s1, s2, Bond<TenElemT>(comp, s1, s2, inv_psi, [&](const std::vector<int32_t> &cand) {
+                    return c.ReplaceNNNSiteTrace(lu, LEFTDOWN_TO_RIGHTUP, HORIZONTAL, 1, cand); }));
         }
-        c.ShiftBMPSWindow(DOWN);                                             // :400
+        {
+          const SiteIdx s1{row, col}, s2{row + 1, col + 1};                  // :369-381 J2 diagonal
+          on_bond(BOND_DR, s1, s2, Bond<TenElemT>(comp, s1, s2, inv_psi, [&](const std::vector<int32_t> &cand) {
+                    return c.ReplaceNNNSiteTrace(lu, LEFTUP_TO_RIGHTDOWN, HORIZONTAL, 1, cand); }));
+        }
+        if (col + 2 < cols) {                                                // :383-397 flat sqrt5 link
+          const SiteIdx s1{row + 1, col}, s2{row, col + 2};
+          on_bond(BOND_FLAT, s1, s2, Bond<TenElemT>(comp, s1, s2, inv_psi, [&](const std::vector<int32_t> &cand) {
+                    return c.ReplaceSqrt5DistTwoSiteTrace(lu, LEFTDOWN_TO_RIGHTUP, HORIZONTAL, 1, cand); }));
+        }
+        c.ShiftBTen2Window(RIGHT, row);                                      // :398
       }
-    }
-    comp.SetOrder(COL_MAJOR);
-    c.GenerateBMPSApproach(LEFT);                                            // :404
-    for (size_t col = 0; col < cols; col++) {
-      std::vector<TenElemT> inv_psi;
-      if (nn_slice) {
-        inv_psi = nn_bonds(VERTICAL, col, false);
-      } else {
-      c.InitBTen(UP, col);
-      c.GrowFullBTen(DOWN, col, 2, true);
-      out.psi_list.push_back(c.Trace({0, col}, VERTICAL));
-      inv_psi = inverse(out.psi_list.back());
-      for (size_t row = 0; row + 1 < rows; row++) {
-        const SiteIdx s1{row, col}, s2{row + 1, col};
-        on_bond(BOND_V, s1, s2, Bond<TenElemT>(comp, s1, s2, inv_psi, [&](const std::vector<int32_t> &cand) {
-                  return comp.ReplaceNNSiteTrace(s1, s2, VERTICAL, 1, cand); }));
-        if (row + 2 < rows) c.ShiftBTenWindow(DOWN);
-      }
-      }
-      if (col + 1 < cols && link_slice && rows >= 3) {
+    };
+    auto column_links = [&](size_t col, const std::vector<TenElemT> &inv_psi) {
+      if (col + 1 >= cols) return;
+      if (link_slice && rows >= 3) {
         const std::vector<TenElemT> val = links(VERTICAL, col, 8);            // the steep link (r+2, c)-(r, c+1)
         for (size_t row = 0; row + 2 < rows; row++)
-          on_bond(BOND_STEEP, {row + 2, col}, {row, col + 1}, slice_bond({row + 2, col}, {row, col + 1}, inv_psi,
+          on_bond(BOND_STEEP, {row + 2, col}, {row, col + 1}, SliceBond(comp, {row + 2, col}, {row, col + 1}, inv_psi,
                   [&](size_t w) { return val[(w * (rows - 1) + row) * 4 + 3]; }));
-        c.ShiftBMPSWindow(RIGHT);
-      } else if (col + 1 < cols) {
-        c.InitBTen2(UP, col);                                                // :425
-        c.GrowFullBTen2(DOWN, col, 3, true);
-        for (size_t row = 0; row + 2 < rows; row++) {                        // :428-442 steep sqrt5 link
-          const SiteIdx s1{row + 2, col}, s2{row, col + 1};
-          on_bond(BOND_STEEP, s1, s2, Bond<TenElemT>(comp, s1, s2, inv_psi, [&](const std::vector<int32_t> &cand) {
-                    return c.ReplaceSqrt5DistTwoSiteTrace({row, col}, LEFTDOWN_TO_RIGHTUP, VERTICAL, 1, cand); }));
-          if (row + 3 < rows) c.ShiftBTen2Window(DOWN, col);
-        }
-        c.ShiftBMPSWindow(RIGHT);
+        return;
       }
-    }
+      c.InitBTen2(UP, col);                                                  // :425
+      c.GrowFullBTen2(DOWN, col, 3, true);
+      for (size_t row = 0; row + 2 < rows; row++) {                          // :428-442 steep sqrt5 link
+        const SiteIdx s1{row + 2, col}, s2{row, col + 1};
+        on_bond(BOND_STEEP, s1, s2, Bond<TenElemT>(comp, s1, s2, inv_psi, [&](const std::vector<int32_t> &cand) {
+                  return c.ReplaceSqrt5DistTwoSiteTrace({row, col}, LEFTDOWN_TO_RIGHTUP, VERTICAL, 1, cand); }));
+        if (row + 3 < rows) c.ShiftBTen2Window(DOWN, col);
+      }
+    };
+    out.psi_list = TraverseNNBonds(
+        comp, nn_slice, HoleDest<TenElemT>(calchols, holes_on_device, sitps.slot(), comp, out.holes), NNBonds<TenElemT>{comp},
+        [&](const SliceSites &s, size_t j, const std::vector<TenElemT> &e) { on_bond(s.dir == HORIZONTAL ? BOND_H : BOND_V, s.at(j), s.at(j + 1), e); },
+        [&](const SliceSites &s, const std::vector<TenElemT> &inv_psi) {
+          if (s.dir == HORIZONTAL) row_links(s.num, inv_psi); else column_links(s.num, inv_psi);
+        });
   }
   double j2_;
   PsiSummaryStore last_psi_;
@@ -3502,9 +3400,9 @@ class SquareHubbardModel : public SquareNNModelEnergySolver<SquareHubbardModel>,
     for (size_t w = 0; w < n; ++w) {
       const int32_t c1 = comp.config(w, s1), c2 = comp.config(w, s2);
       if (c1 == c2) continue;
-      if (psi[w] == TenElemT(0.0)) throw std::runtime_error("Wavefunction amplitude is near zero, causing division by zero.");
-      e[w] = BondEnergyFromHops(c1, c2, ComplexConjugate(TenElemT(sign[2 * w] * psi_ex[2 * w] / psi[w])),
-                                ComplexConjugate(TenElemT(sign[2 * w + 1] * psi_ex[2 * w + 1] / psi[w])));
+      const TenElemT &p = NonZeroPsi(psi[w]);
+      e[w] = BondEnergyFromHops(c1, c2, ComplexConjugate(TenElemT(sign[2 * w] * psi_ex[2 * w] / p)),
+                                ComplexConjugate(TenElemT(sign[2 * w + 1] * psi_ex[2 * w + 1] / p)));
     }
     return e;
   }
@@ -3551,112 +3449,47 @@ class TransverseFieldIsingSquareOBC {
   template <bool calchols = true, typename TenElemT = double>
   EnergyAndHolesT<TenElemT> CalEnergyAndHoles(const SplitIndexTPST<TenElemT> &sitps, TPSWaveFunctionComponentT<TenElemT> &comp,
                                               bool holes_on_device = false) {   // :211-247
-    auto &c = comp.contractor;
-    const size_t rows = c.rows(), cols = c.cols(), n = comp.config.walkers(), slot = sitps.slot();
+    const size_t n = comp.config.walkers();
     EnergyAndHolesT<TenElemT> out;
     out.energy.assign(n, TenElemT(0.0));
-    if (calchols && !holes_on_device) out.holes.assign(n * rows * cols * slot, TenElemT(0.0));
-    // a whole row from ONE device call (pepsgpu_onsite_slice with the flip table; holes kept in HBM) when the holes are not wanted on
-    // the host; PEPSHOST_NO_DEVICE_SWEEP=1 keeps the per-site hook path
-    const bool dev_slice = DeviceSlicesEnabled() && (!calchols || holes_on_device);
-    c.GenerateBMPSApproach(UP);
-    for (size_t row = 0; row < rows; row++) {
-      if (dev_slice) {
-        std::vector<TenElemT> psi, psi_ex;
-        FlipSlice(c, row, calchols, psi, psi_ex);
-        out.psi_list.push_back(psi);
-        for (size_t col = 0; col < cols; col++)
-          for (size_t w = 0; w < n; ++w) out.energy[w] += (-h_) * ComplexConjugate(TenElemT(psi_ex[w * cols + col] / psi[w]));
-        if (row + 1 < rows) c.ShiftBMPSWindow(DOWN);
-        continue;
-      }
-      c.InitBTen(LEFT, row);
-      c.GrowFullBTen(RIGHT, row, 1, true);
-      std::vector<TenElemT> psi = c.Trace({row, 0}, HORIZONTAL);
-      out.psi_list.push_back(psi);
-      for (size_t col = 0; col < cols; col++) {
-        if (calchols && holes_on_device) {
-          c.PunchHoleStore({row, col}, HORIZONTAL);
-        } else if (calchols) {
-          std::vector<TenElemT> h = c.PunchHole({row, col}, HORIZONTAL);
-          for (size_t w = 0; w < n; ++w)
-            std::transform(h.begin() + w * slot, h.begin() + (w + 1) * slot, out.holes.begin() + ((w * rows + row) * cols + col) * slot,
-                           [](const TenElemT &x) { return ComplexConjugate(x); });     // Dag(hole)
-        }
-        std::vector<int32_t> cand(n);
-        for (size_t w = 0; w < n; ++w) cand[w] = 1 - comp.config(w, {row, col});
-        std::vector<TenElemT> psi_ex = c.ReplaceOneSiteTrace({row, col}, HORIZONTAL, 1, cand);    // :195-203
-        for (size_t w = 0; w < n; ++w) out.energy[w] += (-h_) * ComplexConjugate(TenElemT(psi_ex[w] / psi[w]));
-        if (col + 1 < cols) c.ShiftBTenWindow(RIGHT);
-      }
-      if (row + 1 < rows) c.ShiftBMPSWindow(DOWN);
-    }
+    // the device slice (holes kept in HBM) when the holes are not wanted on the host
+    out.psi_list = RowPass(comp, DeviceSlicesEnabled() && (!calchols || holes_on_device),
+                           HoleDest<TenElemT>(calchols, holes_on_device, sitps.slot(), comp, out.holes),
+                           [&](size_t, size_t, const std::vector<TenElemT> &ex) {
+                             for (size_t w = 0; w < n; ++w) out.energy[w] += ex[w];
+                           });
     for (size_t w = 0; w < n; ++w) out.energy[w] += CalDiagTermEnergy(comp.config, w);
     return out;
   }
   // Registry of the model (:60-152): energy, spin_z, sigma_x per site (= -off-diagonal term / h; 0 for h = 0), SzSz_row along the
-  // middle row (x0 = lx / 4, i = 1 .. lx / 2).  Same row pass as the energy.  (Round 4: the oracle form is pinned on the reference's
-  // exact-sum measurer numbers at 1e-10, tests/test_oracle_measure.py; round 5: the device form runs the same registries in
+  // middle row (x0 = lx / 4, i = 1 .. lx / 2).  Same row pass as the energy.  (The oracle form is pinned on the reference's
+  // exact-sum measurer numbers at 1e-10, tests/test_oracle_measure.py; the device form runs the same registries in
   // tests/test_gpu_measure.py, real and complex.)
   template <typename TenElemT>
   ObservableMapT<TenElemT> EvaluateObservables(const SplitIndexTPST<TenElemT> &, TPSWaveFunctionComponentT<TenElemT> &comp) {
-    auto &c = comp.contractor;
-    const size_t ly = c.rows(), lx = c.cols(), n = comp.config.walkers(), half = lx / 2;
+    const size_t ly = comp.contractor.rows(), lx = comp.contractor.cols(), n = comp.config.walkers(), half = lx / 2, row = ly / 2;
     ObservableMapT<TenElemT> out;
     out.n = n;
     auto &sx = out.make("sigma_x", ly * lx);
     auto &sz = out.make("spin_z", ly * lx);
     auto &en = out.make("energy", 1);
-    std::vector<std::vector<TenElemT>> psi_list;
-    const bool dev_slice = DeviceSlicesEnabled();
-    c.GenerateBMPSApproach(UP);
-    for (size_t row = 0; row < ly; ++row) {
-      std::vector<TenElemT> row_ex;                     // (device slice: the flipped amplitudes of the whole row, [walker][col])
-      if (dev_slice) {
-        psi_list.emplace_back();
-        FlipSlice(c, row, false, psi_list.back(), row_ex);
-      } else {
-        c.InitBTen(LEFT, row);
-        c.GrowFullBTen(RIGHT, row, 1, true);
-        psi_list.push_back(c.Trace({row, 0}, HORIZONTAL));
+    last_psi_.Fill(n, RowPass(comp, DeviceSlicesEnabled(), HoleDest<TenElemT>(), [&](size_t r, size_t col, const std::vector<TenElemT> &ex) {
+      for (size_t w = 0; w < n; ++w) {
+        en[w] += ex[w];
+        sx[w * ly * lx + r * lx + col] = h_ != 0.0 ? TenElemT(-ex[w] / h_) : TenElemT(0.0);                 // :96
       }
-      const std::vector<TenElemT> &psi = psi_list.back();
-      for (size_t col = 0; col < lx; ++col) {
-        std::vector<TenElemT> psi_ex(n);
-        if (dev_slice) {
-          for (size_t w = 0; w < n; ++w) psi_ex[w] = row_ex[w * lx + col];
-        } else {
-          std::vector<int32_t> cand(n);
-          for (size_t w = 0; w < n; ++w) cand[w] = 1 - comp.config(w, {row, col});
-          psi_ex = c.ReplaceOneSiteTrace({row, col}, HORIZONTAL, 1, cand);                             // :195-203
-        }
-        for (size_t w = 0; w < n; ++w) {
-          if (psi[w] == TenElemT(0.0)) throw std::runtime_error("Wavefunction amplitude is near zero, causing division by zero.");
-          const TenElemT ex = (-h_) * ComplexConjugate(TenElemT(psi_ex[w] / psi[w]));                 // :202
-          en[w] += ex;
-          sx[w * ly * lx + row * lx + col] = h_ != 0.0 ? TenElemT(-ex / h_) : TenElemT(0.0);          // :96
-        }
-        if (col + 1 < lx && !dev_slice) c.ShiftBTenWindow(RIGHT);
+    }));
+    if (half > 0) {                                                                                         // :101-110
+      auto &szsz = out.make("SzSz_row", half);
+      for (size_t w = 0; w < n; ++w) {
+        const double sz1 = double(comp.config(w, {row, lx / 4})) - 0.5;
+        for (size_t i = 1; i <= half; ++i) szsz[w * half + i - 1] = sz1 * (double(comp.config(w, {row, lx / 4 + i})) - 0.5);
       }
-      if (row == ly / 2 && half > 0) {                                                                  // :101-110
-        auto &szsz = out.make("SzSz_row", half);
-        for (size_t w = 0; w < n; ++w) {
-          const double sz1 = double(comp.config(w, {row, lx / 4})) - 0.5;
-          for (size_t i = 1; i <= half; ++i) szsz[w * half + i - 1] = sz1 * (double(comp.config(w, {row, lx / 4 + i})) - 0.5);
-        }
-      }
-      if (row + 1 < ly) c.ShiftBMPSWindow(DOWN);
     }
-    last_psi_.assign(n);
-    std::vector<TenElemT> one(psi_list.size());
     for (size_t w = 0; w < n; ++w) {
       en[w] += CalDiagTermEnergy(comp.config, w);
       for (size_t r = 0; r < ly; ++r)
         for (size_t cc = 0; cc < lx; ++cc) sz[w * ly * lx + r * lx + cc] = double(comp.config(w, {r, cc})) - 0.5;
-      for (size_t k = 0; k < one.size(); ++k) one[k] = psi_list[k][w];
-      auto st = ComputePsiConsistencySummaryAligned(one);
-      last_psi_.psi_mean[w] = st.first;
-      last_psi_.psi_rel_err[w] = st.second;
     }
     return out;
   }
@@ -3678,6 +3511,44 @@ class TransverseFieldIsingSquareOBC {
     psi.assign(n, TenElemT(0.0));
     psi_ex.assign(n * cols, TenElemT(0.0));
     check_rc(pepsgpu_onsite_slice(c.ctx(), HORIZONTAL, (int)row, holes ? 1 : 0, 1, flip, dptr(psi.data()), dptr(psi_ex.data())), c.ctx());
+  }
+  // The row pass of the energy and of the registry (the model has no column pass: its bond term is diagonal): on_site(row, col, ex) with
+  // ex[w] = -h conj(psi(spin flipped at the site) / psi) (:195-203), in a row behind the hole of the site.  dev_slice: a whole row from
+  // ONE FlipSlice; PEPSHOST_NO_DEVICE_SWEEP=1 keeps the per-site ReplaceOneSiteTrace.  Returns psi of every row.
+  template <typename TenElemT, class OnSite>
+  std::vector<std::vector<TenElemT>> RowPass(TPSWaveFunctionComponentT<TenElemT> &comp, bool dev_slice, const HoleDest<TenElemT> &holes,
+                                             OnSite &&on_site) const {
+    auto &c = comp.contractor;
+    const size_t rows = c.rows(), cols = c.cols(), n = comp.config.walkers();
+    std::vector<std::vector<TenElemT>> psi_list;
+    c.GenerateBMPSApproach(UP);
+    for (size_t row = 0; row < rows; row++) {
+      std::vector<TenElemT> psi, row_ex;                  // (device slice: the flipped amplitudes of the whole row, [walker][col])
+      if (dev_slice) {
+        FlipSlice(c, row, holes.wanted, psi, row_ex);
+      } else {
+        c.InitBTen(LEFT, row);
+        c.GrowFullBTen(RIGHT, row, 1, true);
+        psi = c.Trace({row, 0}, HORIZONTAL);
+      }
+      psi_list.push_back(psi);
+      for (size_t col = 0; col < cols; col++) {
+        std::vector<TenElemT> psi_ex(n), ex(n);
+        if (dev_slice) {
+          for (size_t w = 0; w < n; ++w) psi_ex[w] = row_ex[w * cols + col];
+        } else {
+          holes.Punch(c, {row, col});
+          std::vector<int32_t> cand(n);
+          for (size_t w = 0; w < n; ++w) cand[w] = 1 - comp.config(w, {row, col});
+          psi_ex = c.ReplaceOneSiteTrace({row, col}, HORIZONTAL, 1, cand);
+        }
+        for (size_t w = 0; w < n; ++w) ex[w] = (-h_) * ComplexConjugate(TenElemT(psi_ex[w] / NonZeroPsi(psi[w])));   // :202
+        on_site(row, col, ex);
+        if (!dev_slice && col + 1 < cols) c.ShiftBTenWindow(RIGHT);
+      }
+      if (row + 1 < rows) c.ShiftBMPSWindow(DOWN);
+    }
+    return psi_list;
   }
   double h_;
   PsiSummaryStore last_psi_;

@@ -643,6 +643,22 @@ int pepsgpu_opt_scale_state(pepsgpu_ctx *ctx, double factor);
 int pepsgpu_opt_read_state(pepsgpu_ctx *ctx, double *host);
 int pepsgpu_fermion_decoration_set(pepsgpu_ctx *ctx, int d, const int32_t *nf, const uint8_t *bond_parity);
 
+/* The lowest-energy parameters of a VMC run, kept in HBM: VMCPEPSOptimizer's tps_lowest_ (vmc_peps_optimizer_impl.h:118-121), which
+ * the reference copies on the host whenever an iteration's energy is below the minimum so far.
+ *   pepsgpu_vmc_snapshot_save   device-to-device copy of theta (the master parameters of pepsgpu_opt_begin) into a buffer of its own,
+ *                               allocated on first use; a later save overwrites it.  The buffer is freed by pepsgpu_opt_end, by a new
+ *                               pepsgpu_opt_begin and with the context.  Neither theta, the rule state nor the device state is touched.
+ *   pepsgpu_vmc_snapshot_read   the snapshot to the host in the layout of pepsgpu_opt_read_state (padded [row][col][s][L][D][R][U],
+ *                               float64 / interleaved pairs); under a fermionic decoration it is E theta as saved, components 0 .. d - 1
+ *                               (variant 0) are the stored arrays, exactly as pepsgpu_opt_read_state returns theta.
+ *   pepsgpu_vmc_snapshot_clear  frees the buffer (no snapshot afterwards; clearing twice is fine).
+ * Status: PEPSGPU_ESTATE before pepsgpu_opt_begin (all three) and for a read without a snapshot; PEPSGPU_EINVAL for a NULL buffer.  A
+ * refused call leaves the context usable and a held snapshot untouched.
+ * The prefix is not pepsgpu_opt_: the set of pepsgpu_opt_* entries is closed. */
+int pepsgpu_vmc_snapshot_save(pepsgpu_ctx *ctx);
+int pepsgpu_vmc_snapshot_read(pepsgpu_ctx *ctx, double *host);
+int pepsgpu_vmc_snapshot_clear(pepsgpu_ctx *ctx);
+
 /* MinSR inside the device-resident optimizer: Optimizer::CalculateMinSRDirection_ on one rank (optimizer/optimizer_impl.h:1126-1215,
  * minsr_tmatrix.h:53-147, minsr_eigensolve.h:44-155; parameters = MinSRParams, optimizer_params.h:220-232).  With Ns = pepsgpu_sr_count
  * samples in the store, everything that scales with Ns^2 or with the parameter count stays in HBM:

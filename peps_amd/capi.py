@@ -44,6 +44,7 @@ SYMBOLS = [
     "pepsgpu_opt_begin", "pepsgpu_opt_end", "pepsgpu_opt_gradient_from_accumulators", "pepsgpu_opt_set_gradient",
     "pepsgpu_opt_get_gradient", "pepsgpu_opt_clip", "pepsgpu_opt_natural_gradient", "pepsgpu_opt_step", "pepsgpu_opt_scale_state",
     "pepsgpu_opt_read_state", "pepsgpu_fermion_decoration_set", "pepsgpu_minsr_direction", "pepsgpu_diag_eigh",
+    "pepsgpu_vmc_snapshot_save", "pepsgpu_vmc_snapshot_read", "pepsgpu_vmc_snapshot_clear",
     "pepsgpu_lbfgs_begin", "pepsgpu_lbfgs_end", "pepsgpu_lbfgs_reset", "pepsgpu_lbfgs_update", "pepsgpu_lbfgs_direction",
     "pepsgpu_lbfgs_trial", "pepsgpu_lbfgs_slope", "pepsgpu_lbfgs_commit", "pepsgpu_lbfgs_get_direction", "pepsgpu_lbfgs_get_pair",
     "pepsgpu_lbfgs_counters",
@@ -184,6 +185,9 @@ def load_library(path=LIB_PATH):
         lib.pepsgpu_opt_step.argtypes = [vp, C.c_int, C.c_double, dp, C.c_int]
         lib.pepsgpu_opt_scale_state.argtypes = [vp, C.c_double]
         lib.pepsgpu_opt_read_state.argtypes = [vp, dp]
+        lib.pepsgpu_vmc_snapshot_save.argtypes = [vp]
+        lib.pepsgpu_vmc_snapshot_read.argtypes = [vp, dp]
+        lib.pepsgpu_vmc_snapshot_clear.argtypes = [vp]
     if hasattr(lib, "pepsgpu_fermion_decoration_set"):
         lib.pepsgpu_fermion_decoration_set.argtypes = [vp, C.c_int, ip, C.POINTER(C.c_uint8)]
     if hasattr(lib, "pepsgpu_minsr_direction"):     # (PEPSGPU_LIB may name a build from before these entries)
@@ -748,6 +752,20 @@ class Context:
         out = np.zeros(self._state_shape(), dtype=self._ot)
         self._ck(self._l.pepsgpu_opt_read_state(self._h, _dp(out)))
         return out
+
+    # -- the lowest-energy parameters of a VMC run, kept in HBM (include/pepsgpu.h, pepsgpu_vmc_snapshot_*) --
+    def vmc_snapshot_save(self):
+        """device-to-device copy of theta into the snapshot buffer (allocated on first use, freed by opt_end)"""
+        self._ck(self._l.pepsgpu_vmc_snapshot_save(self._h))
+
+    def vmc_snapshot_read(self):
+        """the snapshot in the layout of opt_read_state"""
+        out = np.zeros(self._state_shape(), dtype=self._ot)
+        self._ck(self._l.pepsgpu_vmc_snapshot_read(self._h, _dp(out)))
+        return out
+
+    def vmc_snapshot_clear(self):
+        self._ck(self._l.pepsgpu_vmc_snapshot_clear(self._h))
 
     def minsr_direction(self, eloc, energy, r_pinv=1e-12, a_pinv=0.0, soft_cutoff=True):
         """g <- the MinSR direction of the resident sample store (Gram, centering, eigensolve, cutoff, back-substitution: all on the

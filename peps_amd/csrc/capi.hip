@@ -627,6 +627,12 @@ int pepsgpu_opt_scale_state(pepsgpu_ctx *ctx, double factor) { CTX_CALL(ctx->eng
 int pepsgpu_opt_read_state(pepsgpu_ctx *ctx, double *host) {
   CTX_CALL(PG_REQUIRE(host != nullptr, 1, "null output"); ctx->eng->opt_read_state(host));
 }
+// ---- the lowest-energy parameters of a VMC run, kept in HBM (engine_opt.h) ----
+int pepsgpu_vmc_snapshot_save(pepsgpu_ctx *ctx) { CTX_CALL(ctx->eng->vmc_snapshot_save()); }
+int pepsgpu_vmc_snapshot_read(pepsgpu_ctx *ctx, double *host) {
+  CTX_CALL(PG_REQUIRE(host != nullptr, 1, "null output"); ctx->eng->vmc_snapshot_read(host));
+}
+int pepsgpu_vmc_snapshot_clear(pepsgpu_ctx *ctx) { CTX_CALL(ctx->eng->vmc_snapshot_clear()); }
 int pepsgpu_minsr_direction(pepsgpu_ctx *ctx, const double *eloc, const double *energy, double r_pinv, double a_pinv, int soft_cutoff,
                             double *direction_norm_out, double *info_out) {
   CTX_CALL(ctx->eng->minsr_direction(eloc, energy, r_pinv, a_pinv, soft_cutoff, direction_norm_out, info_out));

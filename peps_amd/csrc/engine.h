@@ -142,6 +142,10 @@ struct EngineBase {
   virtual void opt_step(int rule, double lr, const double *params, int n_params) = 0;
   virtual void opt_scale_state(double factor) = 0;
   virtual void opt_read_state(double *host) = 0;
+  // the lowest-energy parameters of a VMC run (VMCPEPSOptimizer's tps_lowest_): a copy of theta in HBM
+  virtual void vmc_snapshot_save() = 0;
+  virtual void vmc_snapshot_read(double *host) = 0;
+  virtual void vmc_snapshot_clear() = 0;
   virtual void minsr_direction(const double *eloc, const double *energy, double r_pinv, double a_pinv, int soft_cutoff,
                                double *direction_norm_out, double *info_out) = 0;
   virtual void fermion_decoration_set(int d, const int32_t *nf, const uint8_t *bond_parity) = 0;
@@ -901,6 +905,9 @@ class Engine : public EngineBase {
   void opt_step(int rule, double lr, const double *params, int n_params) override;
   void opt_scale_state(double factor) override;
   void opt_read_state(double *host) override;
+  void vmc_snapshot_save() override;
+  void vmc_snapshot_read(double *host) override;
+  void vmc_snapshot_clear() override;
   void minsr_direction(const double *eloc, const double *energy, double r_pinv, double a_pinv, int soft_cutoff,
                        double *direction_norm_out, double *info_out) override;
   void sr_gram_device(double *g);          // the raw Gram of the local store, summed and mirrored in HBM (engine_sr.h)
@@ -1734,6 +1741,7 @@ class Engine : public EngineBase {
   // optimizer buffers (engine_opt.h), layout of so_ / seo_: theta, g, velocity, m1 of the element type, m2 and acc real
   double *opt_theta_ = nullptr, *opt_g_ = nullptr, *opt_vel_ = nullptr, *opt_m1_ = nullptr, *opt_m2_ = nullptr, *opt_acc_ = nullptr;
   double *opt_part_ = nullptr;             // partial sums of the norm, then its result
+  double *vmc_snap_ = nullptr;             // pepsgpu_vmc_snapshot_save: a copy of theta, allocated on first use
   int *opt_ne_ = nullptr;                  // live elements of a slot per site, then two words of the check at opt_begin
   // fermionic decoration (pepsgpu_fermion_decoration_set): d stored states, their parities, the bond parities [site][4][D]
   int fd_d_ = 0;

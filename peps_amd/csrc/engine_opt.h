@@ -253,6 +253,8 @@ void Engine<T>::opt_release() {
   for (double *p : {opt_theta_, opt_g_, opt_vel_, opt_m1_, opt_m2_, opt_acc_, opt_part_}) arena_.free(p);
   arena_.free(opt_ne_);
   arena_.free(opt_sign_);
+  arena_.free(vmc_snap_);
+  vmc_snap_ = nullptr;
   for (double *p : {minsr_t_, minsr_v_, minsr_work_}) arena_.free(p);
   minsr_t_ = minsr_v_ = minsr_work_ = nullptr;
   minsr_cap_ = 0;
@@ -441,6 +443,30 @@ template <typename T>
 void Engine<T>::opt_read_state(double *host) {
   PG_REQUIRE(opt_theta_ != nullptr, 3, "opt_read_state: call pepsgpu_opt_begin first");
   opt_read(opt_theta_, host);
+}
+
+// The parameters of the lowest energy so far (vmc_peps_optimizer_impl.h:118-121, tps_lowest_ = state) without a host hop: theta is
+// copied device to device into a buffer of its own, which lives until opt_end / a new opt_begin / the context goes.
+template <typename T>
+void Engine<T>::vmc_snapshot_save() {
+  PG_REQUIRE(opt_theta_ != nullptr, 3, "vmc_snapshot_save: call pepsgpu_opt_begin first");
+  const size_t bytes = sizeof(double) * (size_t)Ly_ * Lx_ * dp_ * slot_ * kOut;
+  double *dst = vmc_snap_ ? vmc_snap_ : (double *)arena_.alloc(bytes);
+  PG_CHECK_HIP(hipMemcpyAsync(dst, opt_theta_, bytes, hipMemcpyDeviceToDevice, stream_));
+  vmc_snap_ = dst;
+}
+template <typename T>
+void Engine<T>::vmc_snapshot_read(double *host) {
+  PG_REQUIRE(opt_theta_ != nullptr, 3, "vmc_snapshot_read: call pepsgpu_opt_begin first");
+  PG_REQUIRE(vmc_snap_ != nullptr, 3, "vmc_snapshot_read: no snapshot (pepsgpu_vmc_snapshot_save)");
+  opt_read(vmc_snap_, host);
+}
+template <typename T>
+void Engine<T>::vmc_snapshot_clear() {
+  PG_REQUIRE(opt_theta_ != nullptr, 3, "vmc_snapshot_clear: call pepsgpu_opt_begin first");
+  PG_CHECK_HIP(hipStreamSynchronize(stream_));
+  arena_.free(vmc_snap_);
+  vmc_snap_ = nullptr;
 }
 
 template <typename T>

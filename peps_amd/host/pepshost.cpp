@@ -853,6 +853,238 @@ void fermion_sr_step_samples_impl(int rows, int cols, int D, int d, const int32_
   info_out[2] = (double)res.sr_iterations; info_out[3] = res.sr_natural_grad_norm; info_out[4] = res.sr_residual_norm;
   copy_out(opt.GetState(rows, cols, d, D).flat(), state_out);
 }
+
+// ---- Monte-Carlo VMC on the resident state: MCEnergyGradEvaluator and VMCPEPSOptimizer (qlpeps_gpu.h) ----
+// One description for the bosonic and the fermionic entries: nf == nullptr is a bosonic state ([rows][cols][d][D^4], models xxz 0, tfim 1,
+// j1j2 2; updaters exchange 0, fullspace 1, tnn3 2); else sitps_flat holds the 4 d decorated components and bond_parity the bond parities
+// (models spinless 0, tj 1, hubbard 3; updaters exchange 0, tnn3 2, hubbard_u1u1 3).
+// algo: 0 SGD (momentum, nesterov, weight_decay), 1 AdaGrad (epsilon, initial_accumulator_value), 2 Adam (beta1, beta2, epsilon,
+// weight_decay), 3 SR (diag_shift, cg_max_iter, cg_relative_tolerance, normalize_update), 4 MinSR (r_pinv, a_pinv, soft_cutoff),
+// 5 L-BFGS (the fourteen fields of LBFGSParams).
+struct VMCSpec {
+  int warmup_sweeps = 0, samples_per_walker = 1, sweeps_between = 1;
+  int algo = 0, n_rule_params = 0, iterations = 0;
+  double lr = 0.0, clip_value = 0.0, clip_norm = 0.0;
+  const double *rule_params = nullptr;
+};
+inline AlgorithmParams make_vmc_algo(const VMCSpec &v) {
+  static const int want[6] = {3, 2, 4, 4, 3, 14};
+  if (v.algo < 0 || v.algo > 5 || !v.rule_params || v.n_rule_params != want[v.algo])
+    throw std::invalid_argument("vmc: algo 0 SGD (3 parameters), 1 AdaGrad (2), 2 Adam (4), 3 SR (4), 4 MinSR (3), 5 L-BFGS (14)");
+  const double *q = v.rule_params;
+  if (v.algo == 0) return SGDParams(q[0], q[1] != 0.0, q[2]);
+  if (v.algo == 1) return AdaGradParams(q[0], q[1]);
+  if (v.algo == 2) return AdamParams(q[0], q[1], q[2], q[3]);
+  if (v.algo == 3) {
+    if (!(q[1] >= 0.0 && q[1] < 1e9)) throw std::invalid_argument("vmc: SR cg_max_iter out of range");
+    StochasticReconfigurationParams sr;
+    sr.diag_shift = q[0]; sr.cg_params.max_iter = (size_t)q[1]; sr.cg_params.relative_tolerance = q[2]; sr.normalize_update = q[3] != 0.0;
+    return sr;
+  }
+  if (v.algo == 4) return MinSRParams(q[0], q[1], q[2] != 0.0);
+  return make_lbfgs(q);
+}
+inline VMCPEPSOptimizerParams make_vmc_params(const VMCSpec &v, int chi, const char *tps_base, const char *energy_dir, const char *config_dir) {
+  if (v.iterations < 0 || v.warmup_sweeps < 0 || v.sweeps_between < 0 || v.samples_per_walker < 0)
+    throw std::invalid_argument("vmc: negative iterations / sweeps / samples");
+  OptimizerParams::BaseParams base((size_t)v.iterations, 0.0, 0.0, (size_t)v.iterations + 1, v.lr);   // the stopping criteria are off
+  if (v.clip_value > 0.0) base.clip_value = v.clip_value;
+  if (v.clip_norm > 0.0) base.clip_norm = v.clip_norm;
+  MonteCarloParams mc;
+  mc.num_warmup_sweeps = (size_t)v.warmup_sweeps; mc.sweeps_between_samples = (size_t)v.sweeps_between;
+  mc.samples_per_walker = (size_t)v.samples_per_walker;
+  mc.config_dump_path = config_dir ? config_dir : "";
+  VMCPEPSOptimizerParams vp(OptimizerParams(base, make_vmc_algo(v)), mc, trunc_params(chi), tps_base ? tps_base : "");
+  vp.energy_dump_dir = energy_dir ? energy_dir : "";
+  return vp;
+}
+// (updater, model) of the ids -> fn(updater object, model object); dry: CheckModelUpdaterPair only, no object is built.  A pair that
+// CheckModelUpdaterPair refuses is not instantiated.
+template <class U, class M>
+constexpr bool kVMCPairBuilt = !(std::is_same<U, MCUpdateSquareNNHubbardU1U1OBC>::value && !std::is_same<M, SquareHubbardModel>::value) &&
+                               !(std::is_same<M, TransverseFieldIsingSquareOBC>::value && !std::is_same<U, MCUpdateSquareNNFullSpaceUpdateOBC>::value) &&
+                               !(IsFermionicModel<M>::value && std::is_same<U, MCUpdateSquareNNFullSpaceUpdateOBC>::value);
+template <class U, class M, typename Fn>
+void vmc_pair(const std::vector<uint64_t> &sd, M &m, bool dry, Fn &&fn) {
+  CheckModelUpdaterPair<U, M>(IsFermionicModel<M>::value);
+  if constexpr (kVMCPairBuilt<U, M>) {
+    if (dry) return;
+    U u(sd);
+    fn(u, m);
+  }
+}
+template <typename Fn>
+void with_vmc_pair(bool fermion, int updater, int model, const double *p, int n_prm, const std::vector<uint64_t> &sd, bool dry, Fn &&fn) {
+  auto on_model = [&](auto &m) {
+    using M = std::decay_t<decltype(m)>;
+    if (updater == 0) vmc_pair<MCUpdateSquareNNExchangeOBC, M>(sd, m, dry, fn);
+    else if (updater == 1) vmc_pair<MCUpdateSquareNNFullSpaceUpdateOBC, M>(sd, m, dry, fn);
+    else if (updater == 2) vmc_pair<MCUpdateSquareTNN3SiteExchange, M>(sd, m, dry, fn);
+    else if (updater == 3) vmc_pair<MCUpdateSquareNNHubbardU1U1OBC, M>(sd, m, dry, fn);
+    else throw std::invalid_argument("vmc: updater must be 0 (exchange), 1 (fullspace), 2 (tnn3) or 3 (hubbard_u1u1)");
+    return 0;
+  };
+  if (!p) throw std::invalid_argument("vmc: the model parameters are required");
+  if (fermion) { with_fermion_model<double>(model, p, n_prm, on_model); return; }
+  if (model == 0) { SquareSpinOneHalfXXZModelOBC m(p[0], p[1], p[2]); on_model(m); }
+  else if (model == 1) { TransverseFieldIsingSquareOBC m(p[0]); on_model(m); }
+  else if (model == 2) { SquareSpinOneHalfJ1J2XXZModelOBC m(p[0], p[1], p[2], p[3], p[4]); on_model(m); }
+  else throw std::invalid_argument("vmc: a bosonic model must be 0 (xxz), 1 (tfim) or 2 (j1j2)");
+}
+// the d stored components of an extended state (variant 0), or the state itself
+template <typename TenElemT>
+void copy_stored_out(const SplitIndexTPST<TenElemT> &ext, size_t d_stored, double *out) {
+  if (!out) return;
+  constexpr size_t z = ElemTraits<TenElemT>::is_complex ? 2 : 1;
+  for (size_t r = 0; r < ext.rows(); ++r)
+    for (size_t c = 0; c < ext.cols(); ++c)
+      for (size_t k = 0; k < d_stored; ++k) {
+        const double *src = dptr(ext.component(r, c, k));
+        std::copy(src, src + z * ext.slot(), out + z * (((r * ext.cols() + c) * d_stored + k) * ext.slot()));
+      }
+}
+
+// VMCPEPSOptimizer::Execute in one call.  Outputs ([iterations + 1] = one entry per evaluation): energies (re [, im]), their binned
+// errors, gradient norms, accept [evaluation][walker]; state_out / lowest_out: the d stored components of GetState / GetLowestState;
+// info_out (7 doubles) = [evaluations, GetMinEnergy, max_w |psi_w| of the walkers at return, GetCurrentEnergy (re), seconds in the
+// evaluator, in IterativeOptimize, in all (GetTimings)]; configs: the final configurations.  finalize == 0 stops before the closing RefreshWavefunctionComponent + NormalizeStateOrder1 (theta as the last step
+// left it).  probe_iteration >= 0: an OptimizationCallback reads GetState() into probe_state_out at that iteration.
+template <typename TenElemT>
+void vmc_optimize_impl(int rows, int cols, int D, int d, const int32_t *nf, const uint8_t *bond_parity, int chi, int dtype,
+                       const double *sitps_flat, int n, int32_t *configs, const uint64_t *seeds, int n_seeds, int updater, int model,
+                       const double *p, int n_prm, const VMCSpec &spec, int finalize, int probe_iteration, const char *tps_base,
+                       const char *energy_dir, const char *config_dir, double *energies_out, double *errors_out, double *grad_norms_out,
+                       double *accept_out, double *state_out, double *lowest_out, double *probe_state_out, double *info_out) {
+  // every refusal that needs no device comes first
+  if (n < 0 || n_seeds < 0 || (n > 0 && !configs) || (n_seeds > 0 && !seeds) || !sitps_flat) throw std::invalid_argument("vmc: null / negative argument");
+  const VMCPEPSOptimizerParams vp = make_vmc_params(spec, chi, tps_base, energy_dir, config_dir);
+  vp.Validate((size_t)n, (size_t)n_seeds);
+  const bool fermion = nf != nullptr;
+  const std::vector<uint64_t> sd(seeds, seeds + n_seeds);
+  with_vmc_pair(fermion, updater, model, p, n_prm, sd, /*dry=*/true, [](auto &, auto &) {});
+  FermionDecoration dec;
+  if (fermion) dec = make_decoration(rows, cols, D, d, nf, bond_parity);
+  const int dev_d = fermion ? 4 * d : d;
+  SplitIndexTPST<TenElemT> sitps = make_state_t<TenElemT>(rows, cols, D, dev_d, sitps_flat);
+  BMPSContractorT<TenElemT> contractor(rows, cols, D, dev_d, vp.peps_params, n, dtype, g_device);
+  contractor.UploadState(sitps);
+  TPSWaveFunctionComponentT<TenElemT> comp(typename TPSWaveFunctionComponentT<TenElemT>::ResidentState(), make_cfg(n, rows, cols, configs),
+                                           contractor, fermion ? &dec : nullptr);
+  with_vmc_pair(fermion, updater, model, p, n_prm, sd, /*dry=*/false, [&](auto &upd, auto &m) {
+    VMCPEPSOptimizer<std::decay_t<decltype(upd)>, std::decay_t<decltype(m)>, TenElemT> exe(vp, comp, upd, m, sd.size(), (size_t)D);
+    if (probe_iteration >= 0 && probe_state_out) {
+      typename Optimizer<TenElemT>::OptimizationCallback cb;
+      cb.on_iteration = [&](size_t it, double, double, double) {
+        if ((long)it == (long)probe_iteration) copy_out(exe.GetState().flat(), probe_state_out);
+      };
+      exe.SetOptimizationCallback(cb);
+    }
+    if (finalize) exe.Execute();
+    else { exe.WarmUpAndOptimize(); exe.DumpData(); }
+    copy_out(exe.GetEnergyTrajectory(), energies_out);
+    const size_t ne = exe.GetEnergyTrajectory().size();
+    if (errors_out) std::copy(exe.GetEnergyErrorTrajectory().begin(), exe.GetEnergyErrorTrajectory().end(), errors_out);
+    if (grad_norms_out) std::copy(exe.GetGradientNormTrajectory().begin(), exe.GetGradientNormTrajectory().end(), grad_norms_out);
+    if (accept_out)
+      for (size_t k = 0; k < ne; ++k) {
+        const auto &a = exe.GetAcceptRatesTrajectory()[k];
+        for (size_t w = 0; w < (size_t)n; ++w) accept_out[k * n + w] = w < a.size() ? a[w] : 0.0;
+      }
+    copy_out(exe.GetState().flat(), state_out);
+    copy_out(exe.GetLowestState().flat(), lowest_out);
+    if (info_out) {
+      double mx = 0.0;
+      for (const auto &a : comp.amplitude) mx = std::max(mx, (double)std::abs(a));
+      info_out[0] = (double)ne; info_out[1] = exe.GetMinEnergy(); info_out[2] = mx; info_out[3] = std::real(exe.GetCurrentEnergy());
+      info_out[4] = exe.GetTimings().evaluation_s; info_out[5] = exe.GetTimings().optimize_s; info_out[6] = exe.GetTimings().total_s;
+    }
+  });
+  std::copy(comp.config.data(), comp.config.data() + (size_t)n * rows * cols, configs);
+}
+
+// MCEnergyGradEvaluator::Evaluate alone, n_evaluates times on one engine with no step between them (the chains persist), for tests.
+// Warm-up: normalize != 0 is MonteCarloEngine::WarmUp (sweeps + NormalizeStateOrder1 on the device), else the plain sweeps.  Per
+// evaluation k: energy_samples_out [k][sample][walker], so_out / seo_out [k][state size] (pepsgpu_grad_read), scalars_out [k][5] =
+// (e_loc_sum re, im, weight_sum, energy_error, samples in the SR store), accept_out [k][walker].  spec.algo >= 0 with state_out: after the
+// last evaluation the step is composed by hand on the contractor -- finish, clip (first-order rules), [natural gradient | MinSR
+// direction], step -- and theta is read back (the d stored components); step_info_out = [energy re, gradient norm].
+template <typename TenElemT>
+void mc_evaluate_resident_impl(int rows, int cols, int D, int d, const int32_t *nf, const uint8_t *bond_parity, int chi, int dtype,
+                               const double *sitps_flat, int n, int32_t *configs, const uint64_t *seeds, int updater, int model,
+                               const double *p, int n_prm, int warmup_sweeps, int normalize, int n_samples, int n_evaluates, int collect_sr,
+                               const VMCSpec &spec, double *energy_samples_out, double *so_out, double *seo_out, double *scalars_out,
+                               double *accept_out, double *state_out, double *step_info_out) {
+  if (n < 1 || !configs || !seeds || !sitps_flat || n_samples < 1 || n_evaluates < 1 || warmup_sweeps < 0)
+    throw std::invalid_argument("pepshost_mc_evaluate_resident: walkers, seeds, n_samples >= 1 and n_evaluates >= 1 are required");
+  const bool fermion = nf != nullptr, step = spec.algo >= 0 && state_out;
+  const std::vector<uint64_t> sd(seeds, seeds + n);
+  with_vmc_pair(fermion, updater, model, p, n_prm, sd, /*dry=*/true, [](auto &, auto &) {});
+  AlgorithmParams algo = SGDParams();
+  if (step) algo = make_vmc_algo(spec);
+  if (step && spec.algo == 5) throw std::invalid_argument("pepshost_mc_evaluate_resident: the hand-composed step covers SGD, AdaGrad, Adam, SR and MinSR");
+  FermionDecoration dec;
+  if (fermion) dec = make_decoration(rows, cols, D, d, nf, bond_parity);
+  const int dev_d = fermion ? 4 * d : d;
+  SplitIndexTPST<TenElemT> sitps = make_state_t<TenElemT>(rows, cols, D, dev_d, sitps_flat);
+  BMPSContractorT<TenElemT> contractor(rows, cols, D, dev_d, trunc_params(chi), n, dtype, g_device);
+  contractor.UploadState(sitps);
+  TPSWaveFunctionComponentT<TenElemT> comp(typename TPSWaveFunctionComponentT<TenElemT>::ResidentState(), make_cfg(n, rows, cols, configs),
+                                           contractor, fermion ? &dec : nullptr);
+  // (the Optimizer object is only the RAII holder of pepsgpu_opt_begin / _end and of the decoration; no method of it steps here)
+  Optimizer<TenElemT> opt(OptimizerParams(OptimizerParams::BaseParams(0, 0.0, 0.0, 1, 0.0), algo), contractor, fermion ? &dec : nullptr);
+  MonteCarloParams mc;
+  mc.num_warmup_sweeps = (size_t)warmup_sweeps; mc.samples_per_walker = (size_t)n_samples;
+  constexpr size_t z = ElemTraits<TenElemT>::is_complex ? 2 : 1;
+  with_vmc_pair(fermion, updater, model, p, n_prm, sd, /*dry=*/false, [&](auto &upd, auto &m) {
+    using U = std::decay_t<decltype(upd)>;
+    using M = std::decay_t<decltype(m)>;
+    MonteCarloEngine<U, TenElemT> engine(typename TPSWaveFunctionComponentT<TenElemT>::ResidentState(), sitps, comp, mc, upd);
+    if (normalize) engine.WarmUp();
+    else for (int s = 0; s < warmup_sweeps; ++s) (void)engine.StepSweep(1);
+    MCEnergyGradEvaluator<U, M, TenElemT> evaluator(engine, m, mc, collect_sr != 0 || (step && (spec.algo == 3 || spec.algo == 4)),
+                                                    fermion ? &dec : nullptr);
+    const size_t ns = (size_t)n * n_samples, sz = sitps.flat().size();
+    DeviceEvaluationT<TenElemT> ev;
+    for (int k = 0; k < n_evaluates; ++k) {
+      ev = evaluator.Evaluate(contractor);
+      if (energy_samples_out) copy_out(ev.energy_samples, energy_samples_out + z * ns * k);
+      if (so_out && seo_out) {
+        std::vector<TenElemT> so, seo;
+        contractor.GradRead(so, seo);
+        copy_out(so, so_out + z * sz * k);
+        copy_out(seo, seo_out + z * sz * k);
+      }
+      if (scalars_out) {
+        double *sc = scalars_out + 5 * k;
+        sc[0] = std::real(ev.e_loc_sum); sc[1] = std::imag(ev.e_loc_sum); sc[2] = ev.weight_sum; sc[3] = ev.energy_error;
+        sc[4] = (double)contractor.SRCount();
+      }
+      if (accept_out) std::copy(ev.accept_rates_avg.begin(), ev.accept_rates_avg.end(), accept_out + (size_t)n * k);
+    }
+    if (step) {
+      const auto eg = contractor.OptGradientFromAccumulators(ev.e_loc_sum, ev.weight_sum);
+      const double *q = spec.rule_params;
+      if (spec.algo <= 2 && (spec.clip_value > 0.0 || spec.clip_norm > 0.0)) contractor.OptClip(spec.clip_value, spec.clip_norm);
+      if (spec.algo == 0) contractor.OptStep(0, spec.lr, {q[0], q[1] != 0.0 ? 1.0 : 0.0, q[2]});
+      else if (spec.algo == 1) contractor.OptStep(1, spec.lr, {q[0], q[1]});
+      else if (spec.algo == 2) contractor.OptStep(2, spec.lr, {q[0], q[1], q[2], q[3]});
+      else if (spec.algo == 3) {
+        const ConjugateGradientParams cg;
+        const auto info = contractor.OptNaturalGradient(q[0], (size_t)q[1], q[2], cg.absolute_tolerance, cg.residual_recompute_interval,
+                                                        cg.orthogonality_threshold);
+        contractor.OptStep(0, q[3] != 0.0 && info.direction_norm > 0.0 ? spec.lr / info.direction_norm : spec.lr, {0.0, 0.0, 0.0});
+      } else {
+        contractor.MinSRDirection(ev.energy_samples, eg.first, q[0], q[1], q[2] != 0.0);
+        contractor.OptStep(0, spec.lr, {0.0, 0.0, 0.0});
+      }
+      SplitIndexTPST<TenElemT> theta(rows, cols, dev_d, D);
+      contractor.OptReadState(theta);
+      copy_stored_out(theta, (size_t)d, state_out);
+      if (step_info_out) { step_info_out[0] = std::real(eg.first); step_info_out[1] = eg.second; }
+    }
+  });
+  std::copy(comp.config.data(), comp.config.data() + (size_t)n * rows * cols, configs);
+}
 }  // namespace
 
 extern "C" {
@@ -1198,6 +1430,103 @@ int pepshost_fermion_sr_step_samples_c128(int rows, int cols, int D, int d, cons
 
 // LearningRateScheduler::GetLearningRate (lr_schedulers.h:40-103): kind 0 ConstantLR (lr), 1 ExponentialDecayLR (initial_lr, decay_rate,
 // decay_steps), 2 StepLR (initial_lr, step_size, gamma)
+// ---- Monte-Carlo VMC on the resident state (see vmc_optimize_impl / mc_evaluate_resident_impl) ----
+// mc = [warmup_sweeps, samples_per_walker, sweeps_between_samples]; opt = [algo, lr, iterations, clip_value, clip_norm, finalize,
+// probe_iteration]
+static VMCSpec vmc_spec(const double *mc, const double *opt, const double *rule_params, int n_rule_params) {
+  if (!mc || !opt) throw std::invalid_argument("vmc: the mc / opt arrays are required");
+  for (int i = 0; i < 3; ++i) if (!(mc[i] >= 0.0 && mc[i] < 1e9)) throw std::invalid_argument("vmc: sweeps / samples out of range");
+  if (!(opt[2] >= 0.0 && opt[2] < 1e9)) throw std::invalid_argument("vmc: iterations out of range");
+  VMCSpec v;
+  v.warmup_sweeps = (int)mc[0]; v.samples_per_walker = (int)mc[1]; v.sweeps_between = (int)mc[2];
+  v.algo = (int)opt[0]; v.lr = opt[1]; v.iterations = (int)opt[2]; v.clip_value = opt[3]; v.clip_norm = opt[4];
+  v.rule_params = rule_params; v.n_rule_params = n_rule_params;
+  return v;
+}
+int pepshost_vmc_optimize(int rows, int cols, int D, int d, int chi, int dtype, const double *sitps_flat, int n, int32_t *configs,
+                          const uint64_t *seeds, int n_seeds, int updater, int model, const double *p, const double *mc, const double *opt,
+                          const double *rule_params, int n_rule_params, const char *tps_base, const char *energy_dir, const char *config_dir,
+                          double *energies_out, double *errors_out, double *grad_norms_out, double *accept_out, double *state_out,
+                          double *lowest_out, double *probe_state_out, double *info_out) {
+  return guarded([&]() {
+    const VMCSpec v = vmc_spec(mc, opt, rule_params, n_rule_params);
+    vmc_optimize_impl<double>(rows, cols, D, d, nullptr, nullptr, chi, dtype, sitps_flat, n, configs, seeds, n_seeds, updater, model, p, 8, v,
+                              (int)opt[5], (int)opt[6], tps_base, energy_dir, config_dir, energies_out, errors_out, grad_norms_out, accept_out,
+                              state_out, lowest_out, probe_state_out, info_out);
+  });
+}
+// QLTEN_Complex: sitps_flat, energies_out and the states are interleaved (re, im) pairs
+int pepshost_vmc_optimize_c128(int rows, int cols, int D, int d, int chi, const double *sitps_flat, int n, int32_t *configs,
+                               const uint64_t *seeds, int n_seeds, int updater, int model, const double *p, const double *mc,
+                               const double *opt, const double *rule_params, int n_rule_params, const char *tps_base, const char *energy_dir,
+                               const char *config_dir, double *energies_out, double *errors_out, double *grad_norms_out, double *accept_out,
+                               double *state_out, double *lowest_out, double *probe_state_out, double *info_out) {
+  return guarded([&]() {
+    const VMCSpec v = vmc_spec(mc, opt, rule_params, n_rule_params);
+    vmc_optimize_impl<QLTEN_Complex>(rows, cols, D, d, nullptr, nullptr, chi, PEPSGPU_C128, sitps_flat, n, configs, seeds, n_seeds, updater,
+                                     model, p, 8, v, (int)opt[5], (int)opt[6], tps_base, energy_dir, config_dir, energies_out, errors_out,
+                                     grad_norms_out, accept_out, state_out, lowest_out, probe_state_out, info_out);
+  });
+}
+// a fermionic state: sitps_ext_flat = the 4 d decorated components, bond_parity [rows][cols][4][D]; the states come back as the d stored
+// components; dtype PEPSGPU_C128 runs the QLTEN_Complex instantiation
+int pepshost_fermion_vmc_optimize(int rows, int cols, int D, int d, const int32_t *nf, const uint8_t *bond_parity, int chi, int dtype,
+                                  const double *sitps_ext_flat, int n, int32_t *configs, const uint64_t *seeds, int n_seeds, int updater,
+                                  int model, const double *prm, int n_prm, const double *mc, const double *opt, const double *rule_params,
+                                  int n_rule_params, const char *tps_base, const char *energy_dir, const char *config_dir,
+                                  double *energies_out, double *errors_out, double *grad_norms_out, double *accept_out, double *state_out,
+                                  double *lowest_out, double *probe_state_out, double *info_out) {
+  return guarded([&]() {
+    if (!nf || !bond_parity) throw std::invalid_argument("pepshost_fermion_vmc_optimize: nf and bond_parity are required");
+    const VMCSpec v = vmc_spec(mc, opt, rule_params, n_rule_params);
+    if (dtype == PEPSGPU_C128)
+      vmc_optimize_impl<QLTEN_Complex>(rows, cols, D, d, nf, bond_parity, chi, dtype, sitps_ext_flat, n, configs, seeds, n_seeds, updater, model,
+                                       prm, n_prm, v, (int)opt[5], (int)opt[6], tps_base, energy_dir, config_dir, energies_out, errors_out,
+                                       grad_norms_out, accept_out, state_out, lowest_out, probe_state_out, info_out);
+    else
+      vmc_optimize_impl<double>(rows, cols, D, d, nf, bond_parity, chi, dtype, sitps_ext_flat, n, configs, seeds, n_seeds, updater, model, prm,
+                                n_prm, v, (int)opt[5], (int)opt[6], tps_base, energy_dir, config_dir, energies_out, errors_out, grad_norms_out,
+                                accept_out, state_out, lowest_out, probe_state_out, info_out);
+  });
+}
+// nf == NULL: a bosonic state; dtype PEPSGPU_C128 runs the QLTEN_Complex instantiation.  opt may be NULL (no step).
+int pepshost_mc_evaluate_resident(int rows, int cols, int D, int d, const int32_t *nf, const uint8_t *bond_parity, int chi, int dtype,
+                                  const double *sitps_flat, int n, int32_t *configs, const uint64_t *seeds, int updater, int model,
+                                  const double *p, int n_prm, int warmup_sweeps, int normalize, int n_samples, int n_evaluates,
+                                  int collect_sr, const double *opt, const double *rule_params, int n_rule_params,
+                                  double *energy_samples_out, double *so_out, double *seo_out, double *scalars_out, double *accept_out,
+                                  double *state_out, double *step_info_out) {
+  return guarded([&]() {
+    VMCSpec v;
+    v.algo = -1;
+    if (opt) { v.algo = (int)opt[0]; v.lr = opt[1]; v.clip_value = opt[3]; v.clip_norm = opt[4]; v.rule_params = rule_params; v.n_rule_params = n_rule_params; }
+    if (dtype == PEPSGPU_C128)
+      mc_evaluate_resident_impl<QLTEN_Complex>(rows, cols, D, d, nf, bond_parity, chi, dtype, sitps_flat, n, configs, seeds, updater, model, p,
+                                               n_prm, warmup_sweeps, normalize, n_samples, n_evaluates, collect_sr, v, energy_samples_out,
+                                               so_out, seo_out, scalars_out, accept_out, state_out, step_info_out);
+    else
+      mc_evaluate_resident_impl<double>(rows, cols, D, d, nf, bond_parity, chi, dtype, sitps_flat, n, configs, seeds, updater, model, p, n_prm,
+                                        warmup_sweeps, normalize, n_samples, n_evaluates, collect_sr, v, energy_samples_out, so_out, seo_out,
+                                        scalars_out, accept_out, state_out, step_info_out);
+  });
+}
+// MeanAndBinnedErrorSqrtNUniformBin on a host array samples [n_samples][n_walkers] (interleaved pairs when is_complex); no device.
+// mean_out: 1 or 2 doubles.
+int pepshost_binned_energy_stat(const double *samples, int n_samples, int n_walkers, int is_complex, double *mean_out, double *err_out) {
+  return guarded([&]() {
+    if (!samples || !mean_out || !err_out || n_samples < 0 || n_walkers < 1) throw std::invalid_argument("pepshost_binned_energy_stat: bad arguments");
+    const size_t cnt = (size_t)n_samples * n_walkers;
+    if (is_complex) {
+      const QLTEN_Complex *src = reinterpret_cast<const QLTEN_Complex *>(samples);
+      const auto r = MeanAndBinnedErrorSqrtNUniformBin(std::vector<QLTEN_Complex>(src, src + cnt), (size_t)n_walkers);
+      mean_out[0] = r.first.real(); mean_out[1] = r.first.imag(); *err_out = r.second;
+    } else {
+      const auto r = MeanAndBinnedErrorSqrtNUniformBin(std::vector<double>(samples, samples + cnt), (size_t)n_walkers);
+      mean_out[0] = r.first; *err_out = r.second;
+    }
+  });
+}
+
 int pepshost_lr_schedule(int kind, const double *args, int n_args, long iteration, double *lr_out) {
   return guarded([&]() {
     if (!args || !lr_out || iteration < 0) throw std::invalid_argument("pepshost_lr_schedule: null argument or negative iteration");

@@ -29,6 +29,7 @@
 
 #include <algorithm>
 #include <array>
+#include <chrono>
 #include <cmath>
 #include <complex>
 #include <cstdint>
@@ -727,6 +728,10 @@ class BMPSContractorT {
     return {(size_t)c[0], (size_t)c[1], (size_t)c[2], (size_t)c[3]};
   }
   void OptReadState(SplitIndexTPST<TenElemT> &s) const { check_rc(pepsgpu_opt_read_state(ctx_, dptr(s.flat().data())), ctx_); }
+  // the lowest-energy parameters of a VMC run, kept in HBM (pepsgpu_vmc_snapshot_*): a device-to-device copy of theta
+  void VMCSnapshotSave() { check_rc(pepsgpu_vmc_snapshot_save(ctx_), ctx_); }
+  void VMCSnapshotRead(SplitIndexTPST<TenElemT> &s) const { check_rc(pepsgpu_vmc_snapshot_read(ctx_, dptr(s.flat().data())), ctx_); }
+  void VMCSnapshotClear() { check_rc(pepsgpu_vmc_snapshot_clear(ctx_), ctx_); }
   void SRBegin(size_t max_samples) { check_rc(pepsgpu_sr_begin(ctx_, (int)max_samples), ctx_); }
   void SRAppend(const std::vector<TenElemT> &psi) { check_rc(pepsgpu_sr_append(ctx_, dptr(psi.data())), ctx_); }
   void UpdateLocal(const std::vector<int32_t> &sites, const std::vector<int32_t> &new_states, const std::vector<uint8_t> &mask) {
@@ -3673,6 +3678,8 @@ struct ConfigurationRescueParams {                 // psi_consistency.h:59-85
 struct MonteCarloParams {                          // monte_carlo_peps_params.h
   size_t num_warmup_sweeps = 0, sweeps_between_samples = 1;
   bool is_warmed_up = false;
+  size_t samples_per_walker = 1;                   // num_samples of a rank (a walker plays the rank): MCEnergyGradEvaluator, VMCPEPSOptimizer
+  std::string config_dump_path;                    // VMCPEPSOptimizer::DumpData: configuration<walker> files; empty = no dump
 };
 template <typename TenElemT>
 inline bool CheckWaveFunctionAmplitudeValidity(const TenElemT &amplitude, double min_threshold, double max_threshold) {   // wave_function_component.h:393-402
@@ -3689,6 +3696,28 @@ class MonteCarloEngine {
       : sitps_(sitps), comp_(comp), params_(params), updater_(updater), rescue_(rescue), max_over_ranks_(std::move(max_over_ranks)),
         exchange_valid_config_(std::move(exchange_valid_config)), warm_up_(params.is_warmed_up) {
     EnsureConfigurationValidity();                 // the constructor's last step (:112-113)
+  }
+  // Resident mode: the state lives on the device as the master parameters of an Optimizer (pepsgpu_opt_begin) and never crosses PCIe:
+  // NormalizeStateOrder1 scales it there (pepsgpu_opt_scale_state).  `shape` gives the extents only (fermions: the 4 d decorated
+  // components); `comp` was built on the resident state (TPSWaveFunctionComponentT::ResidentState).  One rank.
+  MonteCarloEngine(typename TPSWaveFunctionComponentT<TenElemT>::ResidentState, SplitIndexTPST<TenElemT> &shape,
+                   TPSWaveFunctionComponentT<TenElemT> &comp, const MonteCarloParams &params, MonteCarloSweepUpdater &updater,
+                   const ConfigurationRescueParams &rescue = ConfigurationRescueParams())
+      : sitps_(shape), comp_(comp), params_(params), updater_(updater), rescue_(rescue), warm_up_(params.is_warmed_up), resident_(true) {
+    EnsureConfigurationValidity();
+  }
+  bool IsResident() const { return resident_; }
+  TPSWaveFunctionComponentT<TenElemT> &WavefuncComp() { return comp_; }
+  const TPSWaveFunctionComponentT<TenElemT> &WavefuncComp() const { return comp_; }
+  // the host state; in resident mode the extents only (the tensors are the device's)
+  const SplitIndexTPST<TenElemT> &State() const { return sitps_; }
+  const MonteCarloParams &Params() const { return params_; }
+  // RefreshWavefunctionComponent (monte_carlo_engine.h, used at mc_energy_grad_evaluator.h:164): the walkers' environments are rebuilt on
+  // the state the device now holds and the amplitudes are taken afresh; the configurations and the updater's mt19937 engines stay.
+  void RefreshWavefunctionComponent() {
+    comp_.order = ROW_MAJOR;
+    comp_.InitDevice();
+    comp_.EvaluateAmplitude();
   }
   bool IsWarmedUp() const { return warm_up_; }
   size_t RescuedWalkers() const { return n_rescued_; }
@@ -3717,8 +3746,12 @@ class MonteCarloEngine {
     if (!(max_abs > 0.0) || std::isinf(max_abs)) throw std::runtime_error("MonteCarloEngine::NormalizeStateOrder1: no finite non-zero amplitude");
     last_scale_ = 1.0 / max_abs;
     const double on_site = std::pow(last_scale_, 1.0 / double(comp_.contractor.rows() * comp_.contractor.cols()));
-    for (auto &x : sitps_.flat()) x *= on_site;    // split_index_tps_ *= scale_factor_on_site
-    comp_.contractor.UploadState(sitps_);          // tps_sample_ = WaveFunctionComponentT(split_index_tps_, config, trun_para)
+    if (resident_) {
+      comp_.contractor.OptScaleState(on_site);     // theta *= scale_factor_on_site, device state = T(theta): no state crosses PCIe
+    } else {
+      for (auto &x : sitps_.flat()) x *= on_site;  // split_index_tps_ *= scale_factor_on_site
+      comp_.contractor.UploadState(sitps_);        // tps_sample_ = WaveFunctionComponentT(split_index_tps_, config, trun_para)
+    }
     comp_.InitDevice();
     comp_.EvaluateAmplitude();
   }
@@ -3784,6 +3817,7 @@ class MonteCarloEngine {
   bool warm_up_;
   size_t n_rescued_ = 0;
   double last_scale_ = 1.0;
+  bool resident_ = false;
 };
 
 // GenerateAllPermutationConfigs (exact_summation_energy_evaluator.h:74-95) for one walker batch layout
@@ -4233,6 +4267,7 @@ struct DeviceEvaluationT {
   double weight_sum = 0.0;
   double energy_error = 0.0;
   std::vector<TenElemT> energy_samples;     // the local energy of every sample in the SR store, in its order (MinSR); empty: no sample set
+  std::vector<double> accept_rates_avg;     // Monte-Carlo evaluators: mean acceptance rate of every walker over the evaluation's sweeps
 };
 
 template <typename TenElemT>
@@ -4574,5 +4609,293 @@ DeviceEvaluationT<TenElemT> SampleSetAccumulateResident(const SplitIndexTPST<Ten
   ev.energy_samples = eh.energy;
   return ev;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Monte-Carlo VMC on the resident state: the evaluator of the reference's example programs and the executor around the Optimizer.
+
+// MeanAndBinnedErrorSqrtNUniformBin (vmc_basic/monte_carlo_tools/statistics.h:146-225) with a walker in the role of an MPI rank.
+// samples: [sample][walker] (sample-major, walker-minor: the order MCEnergyGradEvaluator fills energy_samples).  Per walker the bin
+// size is max(1, floor(sqrt(S))), trailing samples that fill no bin are dropped (:159-162); the bin means are gathered walker-major
+// (:203-207); their mean is the energy and their standard error the error, one bin in total gives an infinite error (:213-222).
+template <typename TenElemT>
+inline std::pair<TenElemT, double> MeanAndBinnedErrorSqrtNUniformBin(const std::vector<TenElemT> &samples, size_t n_walkers) {
+  if (n_walkers == 0 || samples.size() % n_walkers != 0)
+    throw std::invalid_argument("MeanAndBinnedErrorSqrtNUniformBin: samples must be [sample][walker] with at least one walker");
+  const size_t S = samples.size() / n_walkers;
+  std::vector<TenElemT> bins;
+  if (S > 0) {
+    const size_t bin_size = std::max<size_t>(1, static_cast<size_t>(std::sqrt((double)S)));
+    const size_t num_bins = S / bin_size;
+    bins.reserve(num_bins * n_walkers);
+    for (size_t w = 0; w < n_walkers; ++w)
+      for (size_t i = 0; i < num_bins; ++i) {
+        TenElemT bin_sum(0.0);
+        for (size_t k = i * bin_size; k < (i + 1) * bin_size; ++k) bin_sum += samples[k * n_walkers + w];
+        bins.push_back(bin_sum / double(bin_size));
+      }
+  }
+  TenElemT mean(0.0);
+  double err = 0.0;
+  if (!bins.empty()) {
+    for (const auto &b : bins) mean += b;                        // Mean (:51-59)
+    mean /= double(bins.size());
+    if (bins.size() > 1) {
+      double sq = 0.0;
+      for (const auto &b : bins) sq += std::norm(b - mean);      // Variance (:61-81), StandardError (:88-96)
+      err = std::sqrt(sq / double(bins.size()) / (double(bins.size()) - 1.0));
+    } else {
+      err = std::numeric_limits<double>::infinity();
+    }
+  }
+  return {mean, err};
+}
+
+// MCEnergyGradEvaluator (algorithm/vmc_update/mc_energy_grad_evaluator.h:152-330) for the state the device holds.  It owns nothing
+// but references: the engine (resident mode), the model, the decoration of a fermionic state and the Monte-Carlo parameters.
+// Evaluate(contractor) is an Optimizer::Evaluator: S_O / S_EO stay in the contractor's accumulators, the O* samples in its SR store
+// (collect_sr_buffers: SR, MinSR), the energies come back.  The chains persist from one Evaluate to the next: configurations and the
+// updater's engines are never re-seeded; only the environments are rebuilt on the stepped state (RefreshWavefunctionComponent, :164).
+// One rank; a walker plays the role of an MPI rank in the statistics.  Not built (they belong with spike handling): the
+// acceptance-rate anomaly check (:289), the energy-error anomaly check (:319) and the psi-consistency warning policy (:219-244).
+template <class MonteCarloSweepUpdater, class Model, typename TenElemT = double>
+class MCEnergyGradEvaluator {
+ public:
+  using ContractorT = BMPSContractorT<TenElemT>;
+  using EngineT = MonteCarloEngine<MonteCarloSweepUpdater, TenElemT>;
+  MCEnergyGradEvaluator(EngineT &engine, Model &model, const MonteCarloParams &params, bool collect_sr_buffers,
+                        const FermionDecoration *fermion = nullptr)
+      : engine_(engine), model_(model), fermion_(fermion), params_(params), collect_sr_buffers_(collect_sr_buffers) {
+    if (params_.samples_per_walker == 0) throw std::invalid_argument("MCEnergyGradEvaluator: samples_per_walker must be positive");
+    if (engine_.WavefuncComp().fermion != fermion_)
+      throw std::invalid_argument("MCEnergyGradEvaluator: the decoration is not the one of the engine's wave-function component");
+    if (IsFermionicModel<Model>::value != (fermion_ != nullptr))
+      throw std::invalid_argument("MCEnergyGradEvaluator: a fermionic model needs a FermionDecoration, a bosonic one takes none");
+  }
+  DeviceEvaluationT<TenElemT> Evaluate(ContractorT &contractor) {
+    auto &comp = engine_.WavefuncComp();
+    if (&contractor != &comp.contractor) throw std::invalid_argument("MCEnergyGradEvaluator: not the contractor of the engine's walkers");
+    const size_t n = comp.config.walkers(), S = params_.samples_per_walker;
+    engine_.RefreshWavefunctionComponent();        // :164 -- do NOT normalise here: that would rescale the gradient
+    contractor.GradReset();
+    if (collect_sr_buffers_) contractor.SRBegin(n * S);
+    DeviceEvaluationT<TenElemT> ev;
+    ev.energy_samples.reserve(n * S);
+    ev.accept_rates_avg.assign(n, 0.0);
+    for (size_t k = 0; k < S; ++k) {               // :205-282
+      const std::vector<double> rates = engine_.StepSweep();
+      for (size_t w = 0; w < n && w < rates.size(); ++w) ev.accept_rates_avg[w] += rates[w];
+      EnergyAndHolesT<TenElemT> eh = model_.template CalEnergyAndHoles<true>(engine_.State(), comp, /*holes_on_device=*/true);
+      ResidentGradAccumulate(comp, eh, false, collect_sr_buffers_);
+      ev.energy_samples.insert(ev.energy_samples.end(), eh.energy.begin(), eh.energy.end());   // sample-major, walker-minor: the store's order
+    }
+    for (auto &r : ev.accept_rates_avg) r /= double(S);                                       // :285-286
+    const auto stat = MeanAndBinnedErrorSqrtNUniformBin(ev.energy_samples, n);                 // :292
+    ev.weight_sum = double(n * S);
+    // As in the reference (:292-298) the gradient is formed with the BINNED energy, which drops the trailing samples of every walker,
+    // while the O* sums run over all samples: grad = S_EO / W - conj(E_binned) S_O / W.  The optimizer finishes the gradient with
+    // E = e_loc_sum / weight_sum, so hand it E_binned * W instead of the plain sum of the local energies.
+    ev.e_loc_sum = stat.first * ev.weight_sum;
+    ev.energy_error = stat.second;
+    return ev;
+  }
+  DeviceEvaluationT<TenElemT> operator()(ContractorT &contractor) { return Evaluate(contractor); }
+  bool CollectsSRBuffers() const { return collect_sr_buffers_; }
+
+ private:
+  EngineT &engine_;
+  Model &model_;
+  const FermionDecoration *fermion_;
+  const MonteCarloParams &params_;
+  bool collect_sr_buffers_;
+};
+
+// a model / updater pair that does not belong together: the U(1)xU(1) sector updater moves Hubbard states only; the transverse-field
+// Ising model does not conserve S^z, so its chain needs the full-space updater; a fermionic model needs a decorated state
+template <class MonteCarloSweepUpdater, class Model>
+inline void CheckModelUpdaterPair(bool fermionic_state) {
+  if (std::is_same<MonteCarloSweepUpdater, MCUpdateSquareNNHubbardU1U1OBC>::value && !std::is_same<Model, SquareHubbardModel>::value)
+    throw std::invalid_argument("VMCPEPSOptimizer: MCUpdateSquareNNHubbardU1U1OBC belongs to SquareHubbardModel only");
+  if (std::is_same<Model, TransverseFieldIsingSquareOBC>::value && !std::is_same<MonteCarloSweepUpdater, MCUpdateSquareNNFullSpaceUpdateOBC>::value)
+    throw std::invalid_argument("VMCPEPSOptimizer: TransverseFieldIsingSquareOBC does not conserve S^z: it needs MCUpdateSquareNNFullSpaceUpdateOBC");
+  if (IsFermionicModel<Model>::value != fermionic_state)
+    throw std::invalid_argument("VMCPEPSOptimizer: a fermionic model needs a fermionic state (FermionDecoration), a bosonic model a bosonic one");
+  if (fermionic_state && std::is_same<MonteCarloSweepUpdater, MCUpdateSquareNNFullSpaceUpdateOBC>::value)
+    throw std::invalid_argument("VMCPEPSOptimizer: MCUpdateSquareNNFullSpaceUpdateOBC changes the particle number: not an updater of a fermionic model");
+}
+
+// VMCPEPSOptimizerParams (vmc_peps_optimizer_params.h): {OptimizerParams, MonteCarloParams, BMPSTruncateParams, tps_dump_base_name}.
+// The reference hard-codes "./energy" for the trajectory; here the directory is a field with that default (empty: no CSV).
+struct VMCPEPSOptimizerParams {
+  OptimizerParams optimizer_params;
+  MonteCarloParams mc_params;
+  BMPSTruncateParams peps_params;
+  std::string tps_dump_base_name;
+  std::string energy_dump_dir = "./energy";
+  VMCPEPSOptimizerParams(const OptimizerParams &opt, const MonteCarloParams &mc, const BMPSTruncateParams &trunc, const std::string &base = "")
+      : optimizer_params(opt), mc_params(mc), peps_params(trunc), tps_dump_base_name(base) {}
+  // no device call: run it before anything is built on the GPU
+  void Validate(size_t n_walkers, size_t n_seeds) const {
+    if (n_walkers == 0) throw std::invalid_argument("VMCPEPSOptimizerParams: at least one walker is required");
+    if (mc_params.samples_per_walker == 0) throw std::invalid_argument("VMCPEPSOptimizerParams: samples_per_walker must be positive");
+    if (n_seeds != n_walkers)
+      throw std::invalid_argument("VMCPEPSOptimizerParams: " + std::to_string(n_seeds) + " seeds for " + std::to_string(n_walkers) +
+                                  " walkers (one mt19937 engine per walker)");
+    if (optimizer_params.IsAlgorithm<LBFGSParams>() &&
+        optimizer_params.GetAlgorithmParams<LBFGSParams>().step_mode == LBFGSStepMode::kStrongWolfe)
+      throw std::invalid_argument("VMCPEPSOptimizerParams: the strong-Wolfe line search on Monte-Carlo energies is not built (its trial "
+                                  "evaluations are no iterations of the trajectory); use the fixed L-BFGS step");
+  }
+};
+
+// VMCPEPSOptimizer (algorithm/vmc_update/vmc_peps_optimizer.h, vmc_peps_optimizer_impl.h:106-207, 470-542) on the resident state:
+// Execute = WarmUp (normalises once) -> Optimizer::IterativeOptimize with MCEnergyGradEvaluator -> RefreshWavefunctionComponent +
+// NormalizeStateOrder1 -> DumpData.  The caller builds the contractor, uploads the state and builds the component on it
+// (TPSWaveFunctionComponentT::ResidentState), as for every class of this layer; the executor owns the Optimizer (pepsgpu_opt_begin
+// adopts the uploaded state), the engine in resident mode and the evaluator.  tps_lowest_ / en_min_ (:118-121): whenever an
+// evaluation's energy is below the minimum so far theta is copied device to device (pepsgpu_vmc_snapshot_save); the closing
+// evaluation counts.  Not built: step selectors, spike recovery, checkpoints, the JSONL log, more than one rank.
+template <class MonteCarloSweepUpdater, class Model, typename TenElemT = double>
+class VMCPEPSOptimizer {
+ public:
+  using ContractorT = BMPSContractorT<TenElemT>;
+  using OptimizerT = Optimizer<TenElemT>;
+  using Evaluator = typename OptimizerT::Evaluator;
+  using EngineT = MonteCarloEngine<MonteCarloSweepUpdater, TenElemT>;
+  // `phys_dim`: the components of the caller's state (fermions: the d stored ones; the contractor holds 4 d)
+  VMCPEPSOptimizer(const VMCPEPSOptimizerParams &params, TPSWaveFunctionComponentT<TenElemT> &comp, MonteCarloSweepUpdater &updater,
+                   Model &model, size_t n_seeds, size_t D, const ConfigurationRescueParams &rescue = ConfigurationRescueParams())
+      : params_((params.Validate(comp.config.walkers(), n_seeds), CheckModelUpdaterPair<MonteCarloSweepUpdater, Model>(comp.fermion != nullptr),
+                 params)),
+        comp_(comp), D_(D), shape_(comp.contractor.rows(), comp.contractor.cols(), comp.contractor.phys_dim(), D),
+        optimizer_(params_.optimizer_params, comp.contractor, comp.fermion),
+        engine_(typename TPSWaveFunctionComponentT<TenElemT>::ResidentState(), shape_, comp, params_.mc_params, updater, rescue),
+        needs_sr_buffers_(params_.optimizer_params.template IsAlgorithm<StochasticReconfigurationParams>() ||
+                          params_.optimizer_params.template IsAlgorithm<MinSRParams>()),
+        evaluator_(engine_, model, params_.mc_params, needs_sr_buffers_, comp.fermion) {}
+
+  void SetOptimizationCallback(const typename OptimizerT::OptimizationCallback &cb) { user_callback_ = cb; }
+  void SetEnergyEvaluator(const Evaluator &ev) { custom_evaluator_ = ev; }
+
+  // WarmUp + IterativeOptimize; theta is the state after the last step (not yet normalised)
+  typename OptimizerT::OptimizationResult WarmUpAndOptimize() {
+    engine_.WarmUp();                              // :108 (normalises once)
+    energy_trajectory_.clear(); energy_error_traj_.clear(); grad_norm_.clear(); accept_rates_traj_.clear();
+    en_min_ = std::numeric_limits<double>::max();
+    has_lowest_ = false;
+    timings_ = Timings();
+    const auto t_begin = std::chrono::steady_clock::now();
+    auto wrapped = [this](ContractorT &c) {
+      const auto t0 = std::chrono::steady_clock::now();
+      DeviceEvaluationT<TenElemT> ev = custom_evaluator_ ? custom_evaluator_(c) : evaluator_.Evaluate(c);
+      timings_.evaluation_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();   // (ends in host read-backs)
+      const TenElemT energy = ev.e_loc_sum / ev.weight_sum;
+      energy_trajectory_.push_back(energy);
+      energy_error_traj_.push_back(ev.energy_error);
+      accept_rates_traj_.push_back(ev.accept_rates_avg);
+      if (std::real(energy) < en_min_) {           // :118-121, in HBM
+        en_min_ = std::real(energy);
+        c.VMCSnapshotSave();
+        has_lowest_ = true;
+      }
+      return ev;
+    };
+    const auto t_opt = std::chrono::steady_clock::now();
+    result_ = optimizer_.IterativeOptimize(wrapped, user_callback_);
+    const auto t_end = std::chrono::steady_clock::now();
+    timings_.optimize_s = std::chrono::duration<double>(t_end - t_opt).count();
+    timings_.total_s = std::chrono::duration<double>(t_end - t_begin).count();
+    grad_norm_ = result_.gradient_norms;
+    return result_;
+  }
+  // :202-203
+  void FinalizeState() {
+    engine_.RefreshWavefunctionComponent();
+    engine_.NormalizeStateOrder1();
+  }
+  void Execute() {
+    const auto t0 = std::chrono::steady_clock::now();
+    WarmUpAndOptimize();
+    FinalizeState();
+    DumpData();
+    timings_.total_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  }
+  // host-clock seconds of the last run: inside the evaluator (sampling), inside IterativeOptimize (sampling + finish / clip / step) and
+  // in all (warm-up, closing normalisation and dumps included); every part ends in a call that synchronises the stream
+  struct Timings { double evaluation_s = 0.0, optimize_s = 0.0, total_s = 0.0; };
+  const Timings &GetTimings() const { return timings_; }
+
+  SplitIndexTPST<TenElemT> GetState() const { return optimizer_.GetState(shape_.rows(), shape_.cols(), StoredPhysDim(), D_); }
+  // the parameters of the lowest energy as they were when it was evaluated (not rescaled by the closing normalisation)
+  SplitIndexTPST<TenElemT> GetLowestState() const {
+    if (!has_lowest_) throw std::logic_error("VMCPEPSOptimizer::GetLowestState: no evaluation yet");
+    SplitIndexTPST<TenElemT> ext(shape_.rows(), shape_.cols(), shape_.PhysicalDim(), D_);
+    comp_.contractor.VMCSnapshotRead(ext);
+    if (!comp_.fermion) return ext;
+    SplitIndexTPST<TenElemT> s(shape_.rows(), shape_.cols(), StoredPhysDim(), D_);      // variant 0 = the stored arrays
+    for (size_t r = 0; r < s.rows(); ++r)
+      for (size_t c = 0; c < s.cols(); ++c)
+        for (size_t k = 0; k < s.PhysicalDim(); ++k) std::copy(ext.component(r, c, k), ext.component(r, c, k) + ext.slot(), s.component(r, c, k));
+    return s;
+  }
+  double GetMinEnergy() const { return en_min_; }
+  TenElemT GetCurrentEnergy() const { return energy_trajectory_.empty() ? TenElemT(0.0) : energy_trajectory_.back(); }
+  const std::vector<TenElemT> &GetEnergyTrajectory() const { return energy_trajectory_; }
+  const std::vector<double> &GetEnergyErrorTrajectory() const { return energy_error_traj_; }
+  const std::vector<double> &GetGradientNormTrajectory() const { return grad_norm_; }
+  const std::vector<std::vector<double>> &GetAcceptRatesTrajectory() const { return accept_rates_traj_; }
+  const typename OptimizerT::OptimizationResult &GetResult() const { return result_; }
+  OptimizerT &GetOptimizer() { return optimizer_; }
+  EngineT &GetEngine() { return engine_; }
+
+  void DumpData() const { DumpData(params_.tps_dump_base_name, params_.energy_dump_dir); }
+  // :512-542: base + "final" / base + "lowest" (nothing when base is empty), the walkers' configurations to config_dump_path
+  // (configuration<walker>, empty: no dump), <energy_dir>/energy_trajectory.csv (empty: no CSV)
+  void DumpData(const std::string &tps_base_name, const std::string &energy_dir = "./energy") const {
+    if (!tps_base_name.empty()) {
+      EnsureDirectoryExists(tps_base_name + "final");
+      GetState().Dump(tps_base_name + "final");
+      if (has_lowest_) {
+        EnsureDirectoryExists(tps_base_name + "lowest");
+        GetLowestState().Dump(tps_base_name + "lowest");
+      }
+    }
+    if (!params_.mc_params.config_dump_path.empty())
+      for (size_t w = 0; w < comp_.config.walkers(); ++w) DumpConfiguration(comp_.config, w, params_.mc_params.config_dump_path, w);
+    if (!energy_dir.empty()) {
+      EnsureDirectoryExists(energy_dir);
+      WriteEnergyTrajectoryCsv_(energy_dir + "/energy_trajectory.csv");
+    }
+  }
+
+ private:
+  size_t StoredPhysDim() const { return comp_.fermion ? comp_.fermion->d() : shape_.PhysicalDim(); }
+  void WriteEnergyTrajectoryCsv_(const std::string &csv_path) const {      // :475-501
+    std::ofstream csv(csv_path);
+    if (!csv) throw std::ios_base::failure("VMCPEPSOptimizer: failed to open " + csv_path);
+    csv << "iteration,energy,energy_error,gradient_norm\n";
+    for (size_t i = 0; i < energy_trajectory_.size(); ++i) {
+      const double err = i < energy_error_traj_.size() ? energy_error_traj_[i] : 0.0, gnorm = i < grad_norm_.size() ? grad_norm_[i] : 0.0;
+      csv << i << "," << std::setprecision(17) << std::real(energy_trajectory_[i]) << "," << err << "," << gnorm << "\n";
+    }
+    if (!csv) throw std::ios_base::failure("VMCPEPSOptimizer: failed to write " + csv_path);
+  }
+  VMCPEPSOptimizerParams params_;
+  TPSWaveFunctionComponentT<TenElemT> &comp_;
+  size_t D_;
+  SplitIndexTPST<TenElemT> shape_;                 // extents only
+  OptimizerT optimizer_;
+  EngineT engine_;
+  bool needs_sr_buffers_;
+  MCEnergyGradEvaluator<MonteCarloSweepUpdater, Model, TenElemT> evaluator_;
+  Evaluator custom_evaluator_;
+  typename OptimizerT::OptimizationCallback user_callback_;
+  typename OptimizerT::OptimizationResult result_;
+  std::vector<TenElemT> energy_trajectory_;
+  std::vector<double> energy_error_traj_, grad_norm_;
+  std::vector<std::vector<double>> accept_rates_traj_;
+  double en_min_ = std::numeric_limits<double>::max();
+  bool has_lowest_ = false;
+  Timings timings_;
+};
 
 }  // namespace qlpeps_gpu

@@ -28,7 +28,9 @@ SYMBOLS = ["pepshost_last_error", "pepshost_mc_sweeps", "pepshost_energy_and_hol
            "pepshost_fermion_observables", "pepshost_fermion_exact_sum_measure_partial", "pepshost_fermion_measure",
            "pepshost_fermion_measure_updater", "pepshost_hubbard_sector_table", "pepshost_hubbard_hop_table",
            "pepshost_fermion_observables_sc", "pepshost_fermion_exact_sum_measure_partial_sc", "pepshost_fermion_measure_sc",
-           "pepshost_sc_pair_corr_mapping"]
+           "pepshost_sc_pair_corr_mapping",
+           "pepshost_vmc_optimize", "pepshost_vmc_optimize_c128", "pepshost_fermion_vmc_optimize", "pepshost_mc_evaluate_resident",
+           "pepshost_binned_energy_stat"]
 
 _lib = None
 _C128 = 3                                   # PEPSGPU_C128 (include/pepsgpu.h)
@@ -905,6 +907,174 @@ def fermion_sr_step_samples(state, configs, chi, model, params, lr, diag_shift=0
         _ck(l.pepshost_fermion_sr_step_samples(*head, chi, dtype, *rest))
     return stored, {"energy_before": info[0], "energy_after": info[1], "cg_iterations": int(info[2]), "direction_norm": info[3],
                     "cg_residual_norm": info[4]}
+
+
+# ---- Monte-Carlo VMC on the resident state: MCEnergyGradEvaluator and VMCPEPSOptimizer of the host layer ----
+VMC_ALGO_ID = {"sgd": 0, "adagrad": 1, "adam": 2, "sr": 3, "minsr": 4, "lbfgs": 5}   # rule_params: sgd / adagrad / adam as RULE_ID;
+# sr (diag_shift, cg_max_iter, cg_relative_tolerance, normalize_update); minsr (r_pinv, a_pinv, soft_cutoff); lbfgs: a dict of LBFGS_FIELDS
+
+
+def binned_energy_stat(samples):
+    """MeanAndBinnedErrorSqrtNUniformBin of the host layer on samples[sample][walker] (a walker plays the role of an MPI rank): per
+    walker bins of max(1, floor(sqrt(S))) samples, trailing samples dropped, bin means gathered walker-major; returns (mean of the bin
+    means, their standard error; inf for one bin in total).  Needs no device."""
+    cplx = np.iscomplexobj(samples)
+    a = np.ascontiguousarray(samples, dtype=np.complex128 if cplx else np.float64)
+    if a.ndim != 2:
+        raise ValueError("samples must be [sample][walker]")
+    mean, err = np.zeros(2), C.c_double(0.0)
+    l = lib()
+    l.pepshost_binned_energy_stat.argtypes = [C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    _ck(l.pepshost_binned_energy_stat(_cp(a), a.shape[0], a.shape[1], int(cplx), _p(mean, C.c_double), C.byref(err)))
+    return (complex(mean[0], mean[1]) if cplx else float(mean[0])), err.value
+
+
+def _vmc_rule(algo, rule_params):
+    aid = VMC_ALGO_ID[algo] if isinstance(algo, str) else int(algo)
+    rp = _lbfgs_array(rule_params) if aid == 5 else np.ascontiguousarray([float(x) for x in rule_params], dtype=np.float64)
+    return aid, rp
+
+
+def _vmc_result(energies, errors, norms, accept, state, lowest, probe, info, cfg):
+    ne = int(info[0])
+    return {"energies": energies[:ne], "energy_errors": errors[:ne], "grad_norms": norms[:ne], "accept_rates": accept[:ne], "state": state,
+            "lowest_state": lowest, "min_energy": float(info[1]), "max_abs_psi": float(info[2]), "current_energy": float(info[3]),
+            "configs": cfg, "probe_state": probe,
+            "timings": {"evaluation_s": float(info[4]), "optimize_s": float(info[5]), "total_s": float(info[6])}}
+
+
+def _vmc_paths(tps_dump_base_name, energy_dir, config_dump_path):
+    return tuple((x or "").encode() for x in (tps_dump_base_name, energy_dir, config_dump_path))
+
+
+def vmc_optimize(flat, configs, seeds, chi, model, params, updater, algo, lr, rule_params, iterations, warmup_sweeps=0, samples_per_walker=1,
+                 sweeps_between_samples=1, clip_value=0.0, clip_norm=0.0, dtype=1, finalize=True, probe_iteration=-1, tps_dump_base_name="",
+                 energy_dir="", config_dump_path=""):
+    """VMCPEPSOptimizer::Execute of the C++ host layer in one call: the state is uploaded once; WarmUp (sweeps, one normalisation on the
+    device), then Optimizer::IterativeOptimize with MCEnergyGradEvaluator on persistent chains (one mt19937 per walker, `seeds`), the
+    closing refresh + normalisation and DumpData.  Returns a dict: energies / energy_errors / grad_norms [iterations + 1], accept_rates
+    [iterations + 1][walker], state (final), lowest_state (the parameters of the lowest energy, snapshotted in HBM), min_energy,
+    max_abs_psi (over the walkers at return), configs (final).  A complex `flat` runs the QLTEN_Complex instantiation.  finalize=False
+    stops before the closing normalisation; probe_iteration >= 0 reads the state inside an OptimizationCallback at that iteration.
+    energy_dir="" writes no energy_trajectory.csv (the reference writes ./energy)."""
+    cplx = np.iscomplexobj(flat)
+    flat = np.ascontiguousarray(flat, dtype=np.complex128 if cplx else np.float64)
+    rows, cols, d, D = _dims(flat)
+    cfg = np.ascontiguousarray(configs, dtype=np.int32).reshape(-1, rows, cols).copy()
+    n = cfg.shape[0]
+    sd = np.ascontiguousarray(seeds, dtype=np.uint64).ravel()
+    p = np.array(list(params) + [0.0] * 8, dtype=np.float64)
+    aid, rp = _vmc_rule(algo, rule_params)
+    mc = np.array([warmup_sweeps, samples_per_walker, sweeps_between_samples], dtype=np.float64)
+    opt = np.array([aid, lr, iterations, clip_value, clip_norm, int(bool(finalize)), probe_iteration], dtype=np.float64)
+    ne = int(iterations) + 1
+    energies = np.zeros(ne, dtype=flat.dtype)
+    errors, norms, accept, info = np.zeros(ne), np.zeros(ne), np.zeros((ne, max(n, 1))), np.zeros(8)
+    state, lowest = np.zeros_like(flat), np.zeros_like(flat)
+    probe = np.zeros_like(flat) if probe_iteration >= 0 else None
+    l = lib()
+    dpt, i32, cs = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_char_p
+    tail = [dpt, C.c_int, i32, C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_int, dpt, dpt, dpt, dpt, C.c_int, cs, cs, cs] + [dpt] * 8
+    l.pepshost_vmc_optimize.argtypes = [C.c_int] * 6 + tail
+    l.pepshost_vmc_optimize_c128.argtypes = [C.c_int] * 5 + tail
+    rest = (_cp(flat), n, _p(cfg, C.c_int32), _p(sd, C.c_uint64), sd.size, UPDATER_ID[updater], MODEL_ID[model], _p(p, C.c_double),
+            _p(mc, C.c_double), _p(opt, C.c_double), _p(rp, C.c_double), rp.size, *_vmc_paths(tps_dump_base_name, energy_dir, config_dump_path),
+            _cp(energies), _p(errors, C.c_double), _p(norms, C.c_double), _p(accept, C.c_double), _cp(state), _cp(lowest),
+            _cp(probe) if probe is not None else None, _p(info, C.c_double))
+    if cplx:
+        _ck(l.pepshost_vmc_optimize_c128(rows, cols, D, d, chi, *rest))
+    else:
+        _ck(l.pepshost_vmc_optimize(rows, cols, D, d, chi, dtype, *rest))
+    return _vmc_result(energies, errors, norms, accept, state, lowest, probe, info, cfg)
+
+
+def fermion_vmc_optimize(state, configs, seeds, chi, model, params, updater, algo, lr, rule_params, iterations, warmup_sweeps=0,
+                         samples_per_walker=1, sweeps_between_samples=1, clip_value=0.0, clip_norm=0.0, dtype=1, finalize=True,
+                         probe_iteration=-1, tps_dump_base_name="", energy_dir="", config_dump_path=""):
+    """vmc_optimize on a fermionic state (peps_amd.fermion.FermionState): model "spinless" / "tj" / "hubbard" with params as
+    fermion_optimize_exact_sum, updater "exchange", "tnn3" or (Hubbard only) "hubbard_u1u1".  The states of the result are the stored
+    tensors [rows][cols][d][D^4]."""
+    cplx, flat, nf, par, head = _fermion_head(state, dtype)
+    rows, cols = flat.shape[0], flat.shape[1]
+    cfg = np.ascontiguousarray(configs, dtype=np.int32).reshape(-1, rows, cols).copy()
+    n = cfg.shape[0]
+    sd = np.ascontiguousarray(seeds, dtype=np.uint64).ravel()
+    prm = _fermion_prm(model, params)
+    aid, rp = _vmc_rule(algo, rule_params)
+    mc = np.array([warmup_sweeps, samples_per_walker, sweeps_between_samples], dtype=np.float64)
+    opt = np.array([aid, lr, iterations, clip_value, clip_norm, int(bool(finalize)), probe_iteration], dtype=np.float64)
+    ne = int(iterations) + 1
+    energies = np.zeros(ne, dtype=flat.dtype)
+    errors, norms, accept, info = np.zeros(ne), np.zeros(ne), np.zeros((ne, max(n, 1))), np.zeros(8)
+    shape = (rows, cols, state.d) + flat.shape[3:]
+    stored, lowest = np.zeros(shape, dtype=flat.dtype), np.zeros(shape, dtype=flat.dtype)
+    probe = np.zeros(shape, dtype=flat.dtype) if probe_iteration >= 0 else None
+    l = lib()
+    dpt, i32, cs = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_char_p
+    l.pepshost_fermion_vmc_optimize.argtypes = ([C.c_int] * 4 + [i32, C.POINTER(C.c_uint8), C.c_int, C.c_int, dpt, C.c_int, i32, C.POINTER(C.c_uint64),
+                                                 C.c_int, C.c_int, C.c_int, dpt, C.c_int, dpt, dpt, dpt, C.c_int, cs, cs, cs] + [dpt] * 8)
+    _ck(l.pepshost_fermion_vmc_optimize(*head, chi, _C128 if cplx else dtype, _cp(flat), n, _p(cfg, C.c_int32), _p(sd, C.c_uint64), sd.size,
+                                        FERMION_UPDATER_ID[updater], FERMION_MODEL_ID[model], _p(prm, C.c_double), prm.size, _p(mc, C.c_double),
+                                        _p(opt, C.c_double), _p(rp, C.c_double), rp.size,
+                                        *_vmc_paths(tps_dump_base_name, energy_dir, config_dump_path), _cp(energies), _p(errors, C.c_double),
+                                        _p(norms, C.c_double), _p(accept, C.c_double), _cp(stored), _cp(lowest),
+                                        _cp(probe) if probe is not None else None, _p(info, C.c_double)))
+    return _vmc_result(energies, errors, norms, accept, stored, lowest, probe, info, cfg)
+
+
+def mc_evaluate_resident(state, configs, seeds, chi, model, params, updater="exchange", warmup_sweeps=0, n_samples=1, n_evaluates=1,
+                         normalize=False, collect_sr=False, dtype=1, step=None):
+    """MCEnergyGradEvaluator::Evaluate alone on the resident state, `n_evaluates` times on one engine with no step between them (the
+    chains persist).  `state`: a flat bosonic array (real or complex) or a peps_amd.fermion.FermionState.  Warm-up: the plain sweeps, or
+    MonteCarloEngine::WarmUp (with its normalisation on the device) when normalize.  Returns a dict with, per evaluation: energy_samples
+    [k][sample][walker], S_O / S_EO [k][...] (pepsgpu_grad_read), e_loc_sum, weight_sum, energy_error, sr_count, accept_rates [k][walker];
+    configs (final).  step = dict(algo, lr, rule_params[, clip_value, clip_norm]): after the last evaluation the optimizer step is composed
+    by hand on the contractor (finish, clip, natural gradient / MinSR direction, step); "state" is then theta read back, "step_energy" and
+    "step_grad_norm" what the finish returned."""
+    fermion = hasattr(state, "extended_flat")
+    if fermion:
+        cplx, flat, nf, par, head = _fermion_head(state, dtype)
+        rows, cols, D, d = flat.shape[0], flat.shape[1], flat.shape[3], state.d
+        prm = _fermion_prm(model, params)
+        uid, mid = FERMION_UPDATER_ID[updater], FERMION_MODEL_ID[model]
+        nfp, parp = _p(nf, C.c_int32), par.ctypes.data_as(C.POINTER(C.c_uint8))
+    else:
+        cplx = np.iscomplexobj(state)
+        flat = np.ascontiguousarray(state, dtype=np.complex128 if cplx else np.float64)
+        rows, cols, d, D = _dims(flat)
+        prm = np.array(list(params) + [0.0] * 8, dtype=np.float64)
+        uid, mid = UPDATER_ID[updater], MODEL_ID[model]
+        nfp, parp = None, None
+    cfg = np.ascontiguousarray(configs, dtype=np.int32).reshape(-1, rows, cols).copy()
+    n = cfg.shape[0]
+    sd = np.ascontiguousarray(seeds, dtype=np.uint64).ravel()
+    if sd.size != n:
+        raise ValueError("one seed per walker")
+    et = flat.dtype
+    es = np.zeros((n_evaluates, n_samples, n), dtype=et)
+    so, seo = np.zeros((n_evaluates,) + flat.shape, dtype=et), np.zeros((n_evaluates,) + flat.shape, dtype=et)
+    sc, acc = np.zeros((n_evaluates, 5)), np.zeros((n_evaluates, n))
+    opt = rp = theta = None
+    sinfo = np.zeros(2)
+    if step is not None:
+        aid, rp = _vmc_rule(step["algo"], step["rule_params"])
+        opt = np.array([aid, step["lr"], 0, step.get("clip_value", 0.0), step.get("clip_norm", 0.0)], dtype=np.float64)
+        theta = np.zeros((rows, cols, d) + flat.shape[3:], dtype=et)
+    l = lib()
+    dpt, i32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    l.pepshost_mc_evaluate_resident.argtypes = ([C.c_int] * 4 + [i32, C.POINTER(C.c_uint8), C.c_int, C.c_int, dpt, C.c_int, i32, C.POINTER(C.c_uint64),
+                                                 C.c_int, C.c_int, dpt] + [C.c_int] * 6 + [dpt, dpt, C.c_int] + [dpt] * 7)
+    _ck(l.pepshost_mc_evaluate_resident(rows, cols, D, d, nfp, parp, chi, _C128 if cplx else dtype, _cp(flat), n, _p(cfg, C.c_int32),
+                                        _p(sd, C.c_uint64), uid, mid, _p(prm, C.c_double), prm.size, int(warmup_sweeps), int(bool(normalize)),
+                                        int(n_samples), int(n_evaluates), int(bool(collect_sr)), _p(opt, C.c_double), _p(rp, C.c_double),
+                                        rp.size if rp is not None else 0, _cp(es), _cp(so), _cp(seo), _p(sc, C.c_double), _p(acc, C.c_double),
+                                        _cp(theta) if theta is not None else None, _p(sinfo, C.c_double)))
+    e_sum = sc[:, 0] + 1j * sc[:, 1] if cplx else sc[:, 0].copy()
+    out = {"energy_samples": es, "S_O": so, "S_EO": seo, "e_loc_sum": e_sum, "weight_sum": sc[:, 2].copy(), "energy_error": sc[:, 3].copy(),
+           "sr_count": sc[:, 4].astype(int), "accept_rates": acc, "configs": cfg}
+    if step is not None:
+        out.update(state=theta, step_energy=float(sinfo[0]), step_grad_norm=float(sinfo[1]))
+    return out
 
 
 # ---- TenElemT = QLTEN_Complex (std::complex<double>): the same host classes instantiated for the complex element type ----

@@ -659,6 +659,31 @@ int pepsgpu_vmc_snapshot_save(pepsgpu_ctx *ctx);
 int pepsgpu_vmc_snapshot_read(pepsgpu_ctx *ctx, double *host);
 int pepsgpu_vmc_snapshot_clear(pepsgpu_ctx *ctx);
 
+/* The base of a step, kept in HBM: what the spike rollback and the step selectors of the reference's Optimizer do with host copies
+ * of the SplitIndexTPS.  One more vector with the extents of theta; no tensor crosses PCIe.
+ *   pepsgpu_guard_base_save     `prev_accepted_state_ = current_state` (optimizer_impl.h:838-841) and the base of the selector trials
+ *                               (:320-542): device-to-device copy of theta into a buffer of its own, allocated on first use; a later
+ *                               save overwrites it.  Freed by pepsgpu_opt_end, by a new pepsgpu_opt_begin and with the context.
+ *   pepsgpu_guard_base_restore  `current_state = prev_accepted_state_` (the rollback, :1868-1973) and the end of a selector trial:
+ *                               theta <- base, device state = T(base) in one pass.  The gradient buffer is not an operand: after a
+ *                               spike it may hold Inf / NaN.  theta is bit for bit the saved one and the device state is what
+ *                               pepsgpu_opt_begin or a step would have written for it.  The rule state is not touched.
+ *   pepsgpu_guard_base_clear    `has_prev_state_ = false`: no base afterwards; the buffer stays.
+ *   pepsgpu_guard_preview       SGDPreviewUpdate_ (:1001): theta <- the SGD rule of pepsgpu_opt_step applied to the *base* with the
+ *                               current g, device state = T(theta).  The velocity is read and not written.  rule must be 0; params
+ *                               (momentum, nesterov != 0, weight_decay) as for pepsgpu_opt_step.  With (0, 0, 0) it is
+ *                               base - lr g: the trial along the SR / MinSR direction that pepsgpu_opt_natural_gradient /
+ *                               pepsgpu_minsr_direction left in g.  On the same base it leaves theta and the device state bit for
+ *                               bit as pepsgpu_opt_step(0, lr, params) leaves them (one device function holds the arithmetic).
+ * Status: PEPSGPU_ESTATE before pepsgpu_opt_begin (all four) and for a restore / preview without a saved base; PEPSGPU_EINVAL for a
+ * rule other than 0 and for the parameter errors of pepsgpu_opt_step.  A refused call leaves the context and a saved base untouched.
+ * Under a fermionic decoration the base is E theta as saved and both passes run unchanged.
+ * The prefix is not pepsgpu_opt_: the set of pepsgpu_opt_* entries is closed. */
+int pepsgpu_guard_base_save(pepsgpu_ctx *ctx);
+int pepsgpu_guard_base_restore(pepsgpu_ctx *ctx);
+int pepsgpu_guard_base_clear(pepsgpu_ctx *ctx);
+int pepsgpu_guard_preview(pepsgpu_ctx *ctx, int rule, double lr, const double *params, int n_params);
+
 /* MinSR inside the device-resident optimizer: Optimizer::CalculateMinSRDirection_ on one rank (optimizer/optimizer_impl.h:1126-1215,
  * minsr_tmatrix.h:53-147, minsr_eigensolve.h:44-155; parameters = MinSRParams, optimizer_params.h:220-232).  With Ns = pepsgpu_sr_count
  * samples in the store, everything that scales with Ns^2 or with the parameter count stays in HBM:

@@ -45,6 +45,7 @@ SYMBOLS = [
     "pepsgpu_opt_get_gradient", "pepsgpu_opt_clip", "pepsgpu_opt_natural_gradient", "pepsgpu_opt_step", "pepsgpu_opt_scale_state",
     "pepsgpu_opt_read_state", "pepsgpu_fermion_decoration_set", "pepsgpu_minsr_direction", "pepsgpu_diag_eigh",
     "pepsgpu_vmc_snapshot_save", "pepsgpu_vmc_snapshot_read", "pepsgpu_vmc_snapshot_clear",
+    "pepsgpu_guard_base_save", "pepsgpu_guard_base_restore", "pepsgpu_guard_base_clear", "pepsgpu_guard_preview",
     "pepsgpu_lbfgs_begin", "pepsgpu_lbfgs_end", "pepsgpu_lbfgs_reset", "pepsgpu_lbfgs_update", "pepsgpu_lbfgs_direction",
     "pepsgpu_lbfgs_trial", "pepsgpu_lbfgs_slope", "pepsgpu_lbfgs_commit", "pepsgpu_lbfgs_get_direction", "pepsgpu_lbfgs_get_pair",
     "pepsgpu_lbfgs_counters",
@@ -188,6 +189,11 @@ def load_library(path=LIB_PATH):
         lib.pepsgpu_vmc_snapshot_save.argtypes = [vp]
         lib.pepsgpu_vmc_snapshot_read.argtypes = [vp, dp]
         lib.pepsgpu_vmc_snapshot_clear.argtypes = [vp]
+    if hasattr(lib, "pepsgpu_guard_base_save"):     # (PEPSGPU_LIB may name a build from before these entries)
+        lib.pepsgpu_guard_base_save.argtypes = [vp]
+        lib.pepsgpu_guard_base_restore.argtypes = [vp]
+        lib.pepsgpu_guard_base_clear.argtypes = [vp]
+        lib.pepsgpu_guard_preview.argtypes = [vp, C.c_int, C.c_double, dp, C.c_int]
     if hasattr(lib, "pepsgpu_fermion_decoration_set"):
         lib.pepsgpu_fermion_decoration_set.argtypes = [vp, C.c_int, ip, C.POINTER(C.c_uint8)]
     if hasattr(lib, "pepsgpu_minsr_direction"):     # (PEPSGPU_LIB may name a build from before these entries)
@@ -766,6 +772,25 @@ class Context:
 
     def vmc_snapshot_clear(self):
         self._ck(self._l.pepsgpu_vmc_snapshot_clear(self._h))
+
+    # -- the base of a step: rollback and step-selector trials in HBM (include/pepsgpu.h, pepsgpu_guard_*) --
+    def opt_base_save(self):
+        """base <- theta, device to device (allocated on first use, freed by opt_end)"""
+        self._ck(self._l.pepsgpu_guard_base_save(self._h))
+
+    def opt_base_restore(self):
+        """theta <- base and device state = T(base); the gradient buffer is not read"""
+        self._ck(self._l.pepsgpu_guard_base_restore(self._h))
+
+    def opt_base_clear(self):
+        """no base afterwards; the buffer stays"""
+        self._ck(self._l.pepsgpu_guard_base_clear(self._h))
+
+    def opt_preview(self, rule, lr, params):
+        """theta <- the SGD rule (rule 0; momentum, nesterov, weight_decay) applied to the saved base with the current g; the
+        velocity is read and not written.  (0, 0, 0) is base - lr g, the trial along an SR / MinSR direction."""
+        p = np.ascontiguousarray(params, dtype=np.float64).ravel()
+        self._ck(self._l.pepsgpu_guard_preview(self._h, int(rule), float(lr), _dp(p), p.size))
 
     def minsr_direction(self, eloc, energy, r_pinv=1e-12, a_pinv=0.0, soft_cutoff=True):
         """g <- the MinSR direction of the resident sample store (Gram, centering, eigensolve, cutoff, back-substitution: all on the

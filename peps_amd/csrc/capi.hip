@@ -6,6 +6,7 @@
 #include "engine_sr.h"
 #include "engine_opt.h"
 #include "engine_lbfgs.h"
+#include "engine_guard.h"
 #include "engine_var.h"
 #include "engine_cplx.h"
 #include "engine_walker.h"
@@ -633,6 +634,13 @@ int pepsgpu_vmc_snapshot_read(pepsgpu_ctx *ctx, double *host) {
   CTX_CALL(PG_REQUIRE(host != nullptr, 1, "null output"); ctx->eng->vmc_snapshot_read(host));
 }
 int pepsgpu_vmc_snapshot_clear(pepsgpu_ctx *ctx) { CTX_CALL(ctx->eng->vmc_snapshot_clear()); }
+// ---- the base of a step: rollback and step-selector trials in HBM (engine_guard.h) ----
+int pepsgpu_guard_base_save(pepsgpu_ctx *ctx) { CTX_CALL(ctx->eng->opt_base_save()); }
+int pepsgpu_guard_base_restore(pepsgpu_ctx *ctx) { CTX_CALL(ctx->eng->opt_base_restore()); }
+int pepsgpu_guard_base_clear(pepsgpu_ctx *ctx) { CTX_CALL(ctx->eng->opt_base_clear()); }
+int pepsgpu_guard_preview(pepsgpu_ctx *ctx, int rule, double lr, const double *params, int n_params) {
+  CTX_CALL(ctx->eng->opt_preview(rule, lr, params, n_params));
+}
 int pepsgpu_minsr_direction(pepsgpu_ctx *ctx, const double *eloc, const double *energy, double r_pinv, double a_pinv, int soft_cutoff,
                             double *direction_norm_out, double *info_out) {
   CTX_CALL(ctx->eng->minsr_direction(eloc, energy, r_pinv, a_pinv, soft_cutoff, direction_norm_out, info_out));

@@ -30,6 +30,7 @@ namespace pepsgpu {
 enum { LEFT = 0, DOWN = 1, RIGHT = 2, UP = 3 };      // include/qlpeps/basic.h:58-63
 enum { HORIZONTAL = 0, VERTICAL = 1 };               // include/qlpeps/basic.h:19-22
 struct SliceGeom;                                    // one row / column as the slice functions walk it (engine_sweep.h)
+struct OptStepArgs;                                  // scalars of one optimizer step (engine_opt.h)
 
 // batch_flag of the tensor GEMM from a per-walker skip mask: entry b (walker b / div) runs only when skip[b / div] == 0
 __global__ void skip_batch_flag_kernel(const int *__restrict__ skip, int div, int *__restrict__ flag, int nb) {
@@ -142,6 +143,11 @@ struct EngineBase {
   virtual void opt_step(int rule, double lr, const double *params, int n_params) = 0;
   virtual void opt_scale_state(double factor) = 0;
   virtual void opt_read_state(double *host) = 0;
+  // the base of a step (engine_guard.h): a copy of theta in HBM for the spike rollback and the step-selector trials
+  virtual void opt_base_save() = 0;
+  virtual void opt_base_restore() = 0;
+  virtual void opt_base_clear() = 0;
+  virtual void opt_preview(int rule, double lr, const double *params, int n_params) = 0;
   // the lowest-energy parameters of a VMC run (VMCPEPSOptimizer's tps_lowest_): a copy of theta in HBM
   virtual void vmc_snapshot_save() = 0;
   virtual void vmc_snapshot_read(double *host) = 0;
@@ -905,6 +911,11 @@ class Engine : public EngineBase {
   void opt_step(int rule, double lr, const double *params, int n_params) override;
   void opt_scale_state(double factor) override;
   void opt_read_state(double *host) override;
+  void opt_base_save() override;
+  void opt_base_restore() override;
+  void opt_base_clear() override;
+  void opt_preview(int rule, double lr, const double *params, int n_params) override;
+  OptStepArgs opt_sgd_args(const char *who, double lr, const double *params, int n_params) const;
   void vmc_snapshot_save() override;
   void vmc_snapshot_read(double *host) override;
   void vmc_snapshot_clear() override;
@@ -1742,6 +1753,8 @@ class Engine : public EngineBase {
   double *opt_theta_ = nullptr, *opt_g_ = nullptr, *opt_vel_ = nullptr, *opt_m1_ = nullptr, *opt_m2_ = nullptr, *opt_acc_ = nullptr;
   double *opt_part_ = nullptr;             // partial sums of the norm, then its result
   double *vmc_snap_ = nullptr;             // pepsgpu_vmc_snapshot_save: a copy of theta, allocated on first use
+  double *opt_base_ = nullptr;             // pepsgpu_opt_base_save: the base of a step, allocated on first use (engine_guard.h)
+  bool opt_base_saved_ = false;            // has_prev_state_ of the reference
   int *opt_ne_ = nullptr;                  // live elements of a slot per site, then two words of the check at opt_begin
   // fermionic decoration (pepsgpu_fermion_decoration_set): d stored states, their parities, the bond parities [site][4][D]
   int fd_d_ = 0;

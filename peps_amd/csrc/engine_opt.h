@@ -9,6 +9,7 @@
 //   clip      element-wise, then global norm                             optimizer_impl.h:311-316, split_index_tps_impl.h:566-580
 //   step      SGD (:949-990), AdaGrad (:1252-1307), Adam (:1327-1396): one fused pass that also writes sitps_ = T(theta)
 //   scale     theta *= f, sitps_ = T(theta)                              NormalizeStateOrder1, monte_carlo_engine.h:206-240
+//   (the base of a step -- save, restore, SGD preview -- for the spike rollback and the step selectors: engine_guard.h)
 // ElementWiseInv(eps) is taken as 1 / (x + eps) in both AdaGrad and Adam ("Unpinned").
 //
 // Fermionic states (pepsgpu_fermion_decoration_set): the device holds 4 d decorated components per site, T''[s + d var] =
@@ -198,6 +199,22 @@ __global__ __launch_bounds__(256) void opt_fermion_check_kernel(const double *__
 }
 #undef OPT_FERMION_PROLOGUE
 
+// One double of the SGD rule (:949-990): the new theta from (theta, g, velocity); with momentum *vel_new is the new velocity.
+// The rule acts on the real and the imaginary part alike.  opt_step_kernel<T, OPT_SGD> stores the velocity, the preview of
+// engine_guard.h (SGDPreviewUpdate_, :1001) drops it: the arithmetic of the two is this one function.
+__device__ __forceinline__ double opt_sgd_elem(const OptStepArgs &a, double th, double gz, double vel, double *vel_new) {
+#pragma clang fp contract(off)
+  if (a.decay != 1.0) th *= a.decay;
+  double upd = gz;
+  if (a.mu > 0.0) {
+    const double v = a.mu * vel + gz;
+    *vel_new = v;
+    upd = a.nesterov ? a.mu * v + gz : v;
+  }
+  th += (-a.lr) * upd;
+  return th;
+}
+
 // One fused pass per rule: reads theta, g and the rule's state, writes theta, the state and sitps_ = T(theta).
 // s1 = velocity (SGD) / m1 (Adam), element type; s2 = acc (AdaGrad) / m2 (Adam), real.
 // Contraction into fused multiply-adds is off: the result is the separately rounded arithmetic of the host restatement.
@@ -217,14 +234,9 @@ __global__ __launch_bounds__(256) void opt_step_kernel(OptStepArgs a, double *__
   }
   if constexpr (RULE == OPT_SGD) {
     for (int z = 0; z < Z; ++z) {
-      if (a.decay != 1.0) th[z] *= a.decay;
-      double upd = gz[z];
-      if (a.mu > 0.0) {
-        const double v = a.mu * s1[Z * k + z] + gz[z];
-        s1[Z * k + z] = v;
-        upd = a.nesterov ? a.mu * v + gz[z] : v;
-      }
-      th[z] += (-a.lr) * upd;
+      double v = 0.0;
+      th[z] = opt_sgd_elem(a, th[z], gz[z], a.mu > 0.0 ? s1[Z * k + z] : 0.0, &v);
+      if (a.mu > 0.0) s1[Z * k + z] = v;
     }
   } else if constexpr (RULE == OPT_ADAGRAD) {
     const double acc = s2[k] + g2;
@@ -255,6 +267,9 @@ void Engine<T>::opt_release() {
   arena_.free(opt_sign_);
   arena_.free(vmc_snap_);
   vmc_snap_ = nullptr;
+  arena_.free(opt_base_);
+  opt_base_ = nullptr;
+  opt_base_saved_ = false;
   for (double *p : {minsr_t_, minsr_v_, minsr_work_}) arena_.free(p);
   minsr_t_ = minsr_v_ = minsr_work_ = nullptr;
   minsr_cap_ = 0;
@@ -721,6 +736,20 @@ void Engine<T>::minsr_direction(const double *eloc, const double *energy, double
   if (info_out) { info_out[0] = info[0]; info_out[1] = info[1]; info_out[2] = info[2]; info_out[3] = (double)sweeps; }
 }
 
+// the scalars of an SGD step from (momentum, nesterov, weight_decay): one reading for opt_step and opt_preview
+template <typename T>
+OptStepArgs Engine<T>::opt_sgd_args(const char *who, double lr, const double *params, int n_params) const {
+  PG_REQUIRE(std::isfinite(lr) && lr >= 0.0, 1, std::string(who) + ": the learning rate must be finite and non-negative");
+  PG_REQUIRE(n_params == 3 && params != nullptr, 1, std::string(who) + ": wrong n_params (SGD 3, AdaGrad 2, Adam 4)");
+  for (int i = 0; i < n_params; ++i) PG_REQUIRE(std::isfinite(params[i]), 1, std::string(who) + ": non-finite rule parameter");
+  PG_REQUIRE(params[0] >= 0.0 && params[2] >= 0.0, 1, std::string(who) + ": negative SGD momentum / weight_decay");
+  OptStepArgs a{};
+  a.lr = lr; a.decay = 1.0;
+  a.mu = params[0]; a.nesterov = params[1] != 0.0;
+  if (params[2] > 0.0) a.decay = 1.0 - lr * params[2];
+  return a;
+}
+
 template <typename T>
 void Engine<T>::opt_step(int rule, double lr, const double *params, int n_params) {
   PG_REQUIRE(opt_theta_ != nullptr, 3, "opt_step: call pepsgpu_opt_begin first");
@@ -732,10 +761,8 @@ void Engine<T>::opt_step(int rule, double lr, const double *params, int n_params
   OptStepArgs a{};
   a.lr = lr; a.decay = 1.0;
   const dim3 grid = opt_grid();
-  if (rule == OPT_SGD) {          // (momentum, nesterov, weight_decay)
-    PG_REQUIRE(params[0] >= 0.0 && params[2] >= 0.0, 1, "opt_step: negative SGD momentum / weight_decay");
-    a.mu = params[0]; a.nesterov = params[1] != 0.0;
-    if (params[2] > 0.0) a.decay = 1.0 - lr * params[2];
+  if (rule == OPT_SGD) {
+    a = opt_sgd_args("opt_step", lr, params, n_params);
     hipLaunchKernelGGL((opt_step_kernel<T, OPT_SGD>), grid, dim3(256), 0, stream_, a, opt_theta_, (const double *)opt_g_, opt_vel_,
                        (double *)nullptr, sitps_, (const int *)opt_ne_, slot_, dp_);
   } else if (rule == OPT_ADAGRAD) {   // (epsilon, initial_accumulator_value)

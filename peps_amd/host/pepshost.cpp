@@ -1085,6 +1085,223 @@ void mc_evaluate_resident_impl(int rows, int cols, int D, int d, const int32_t *
   });
   std::copy(comp.config.data(), comp.config.data() + (size_t)n * rows * cols, configs);
 }
+
+// ---- spike recovery, step selectors and checkpoints around the Optimizer (qlpeps_gpu.h: SpikeGuard, OptimizerParams) ----
+// guard = 24 doubles: [0] enable_auto_recover, [1] redo_mc_max_retries, [2] factor_err, [3] factor_grad, [4] factor_ngrad,
+// [5] sr_min_iters_suspicious, [6] enable_rollback, [7] ema_window, [8] sigma_k; [9] initial selector enabled, [10] max_line_search_steps,
+// [11] enable_in_deterministic; [12] periodic selector enabled, [13] every_n_steps, [14] phase_switch_ratio, [15] enable_in_deterministic;
+// [16] checkpoint every_n_steps; [17] lr_scheduler (0 none, 1 ConstantLR at lr); [18] energy_tolerance, [19] gradient_tolerance,
+// [20] plateau_patience (<= 0: off); [21] probe_iteration (< 0: none); [22] capacity of events_out in events; [23] unused.
+// The OptimizerParams are built with the four-argument constructor: enable_auto_recover is what [0] says.
+struct GuardSpec {
+  const double *g = nullptr;
+  const char *csv_path = nullptr, *checkpoint_path = nullptr;
+  const double *error_override = nullptr, *energy_shift = nullptr;   // the schedule, one entry per evaluator call
+  int n_schedule = 0;                                                // 0: no schedule, the evaluator is not wrapped
+};
+inline size_t guard_count(double x, const char *what) {
+  if (!(x >= 0.0 && x < 1e9)) throw std::invalid_argument(std::string("guard: ") + what + " out of range");
+  return (size_t)x;
+}
+inline SpikeRecoveryParams make_spike_params(const double *g, const char *csv_path) {
+  if (!g) throw std::invalid_argument("guard: the parameter array is required");
+  SpikeRecoveryParams sp;
+  sp.enable_auto_recover = g[0] != 0.0; sp.redo_mc_max_retries = guard_count(g[1], "redo_mc_max_retries");
+  sp.factor_err = g[2]; sp.factor_grad = g[3]; sp.factor_ngrad = g[4];
+  sp.sr_min_iters_suspicious = guard_count(g[5], "sr_min_iters_suspicious");
+  sp.enable_rollback = g[6] != 0.0; sp.ema_window = guard_count(g[7], "ema_window"); sp.sigma_k = g[8];
+  sp.log_trigger_csv_path = csv_path ? csv_path : "";
+  return sp;
+}
+inline OptimizerParams make_guarded_params(const GuardSpec &gs, int iterations, double lr, double clip_value, double clip_norm,
+                                           const AlgorithmParams &algo) {
+  const double *g = gs.g;
+  const SpikeRecoveryParams sp = make_spike_params(g, gs.csv_path);
+  if (iterations < 0) throw std::invalid_argument("guard: negative iterations");
+  std::unique_ptr<LearningRateScheduler> sched;
+  if (g[17] != 0.0) sched = std::make_unique<ConstantLR>(lr);
+  OptimizerParams::BaseParams base((size_t)iterations, g[18], g[19], g[20] > 0.0 ? guard_count(g[20], "plateau_patience") : (size_t)iterations + 1, lr,
+                                   std::move(sched));
+  if (clip_value > 0.0) base.clip_value = clip_value;
+  if (clip_norm > 0.0) base.clip_norm = clip_norm;
+  base.initial_step_selector.enabled = g[9] != 0.0;
+  base.initial_step_selector.max_line_search_steps = guard_count(g[10], "max_line_search_steps");
+  base.initial_step_selector.enable_in_deterministic = g[11] != 0.0;
+  base.periodic_step_selector.enabled = g[12] != 0.0;
+  base.periodic_step_selector.every_n_steps = guard_count(g[13], "every_n_steps");
+  base.periodic_step_selector.phase_switch_ratio = g[14];
+  base.periodic_step_selector.enable_in_deterministic = g[15] != 0.0;
+  CheckpointParams ck;
+  ck.every_n_steps = guard_count(g[16], "checkpoint every_n_steps");
+  ck.base_path = gs.checkpoint_path ? gs.checkpoint_path : "";
+  return OptimizerParams(base, algo, ck, sp);
+}
+// The schedule around an evaluator: at its k-th call error_override[k] (unless NaN) replaces the error bar and energy_shift[k] *
+// weight_sum is added to e_loc_sum, which moves the energy and, through the finish, the gradient.  One call more than the schedule is
+// long throws, so that no scripted run can loop.
+template <typename TenElemT>
+typename Optimizer<TenElemT>::Evaluator wrap_schedule(typename Optimizer<TenElemT>::Evaluator inner, const GuardSpec &gs,
+                                                      std::shared_ptr<size_t> calls) {
+  if (gs.n_schedule <= 0) return inner;
+  return [inner, gs, calls](BMPSContractorT<TenElemT> &c) {
+    const size_t k = (*calls)++;
+    if (k >= (size_t)gs.n_schedule)
+      throw std::runtime_error("guard: evaluator call " + std::to_string(k) + " is beyond the schedule of " + std::to_string(gs.n_schedule));
+    DeviceEvaluationT<TenElemT> ev = inner(c);
+    if (gs.error_override && !std::isnan(gs.error_override[k])) ev.energy_error = gs.error_override[k];
+    if (gs.energy_shift) ev.e_loc_sum += TenElemT(gs.energy_shift[k] * ev.weight_sum);
+    return ev;
+  };
+}
+inline void write_events(const SpikeStatistics &st, size_t cap, double *events_out, double *counts_out) {
+  const size_t n = std::min(cap, st.event_log.size());
+  if (events_out)
+    for (size_t i = 0; i < n; ++i) {
+      const auto &e = st.event_log[i];
+      double *o = events_out + 6 * i;
+      o[0] = (double)e.step; o[1] = (double)e.attempt; o[2] = (double)(int)e.signal; o[3] = (double)(int)e.action; o[4] = e.value; o[5] = e.threshold;
+    }
+  if (counts_out) {
+    counts_out[0] = (double)st.event_log.size(); counts_out[1] = (double)st.total_resamples; counts_out[2] = (double)st.total_rollbacks;
+    counts_out[3] = (double)st.total_forced_accepts;
+  }
+}
+// info_out (16 doubles) = [accepted evaluations, events, resamples, rollbacks, forced accepts, evaluator calls, energy-only calls,
+// total_iterations, converged, min_energy, sr_iterations, sr_natural_grad_norm, sr_residual_norm, entries of selected_eta, lowest valid, -]
+template <typename TenElemT>
+void write_guarded_result(const typename Optimizer<TenElemT>::OptimizationResult &res, const GuardSpec &gs, double *energies_out,
+                          double *errors_out, double *grad_norms_out, double *selected_eta_out, double *events_out, double *info_out) {
+  copy_out(res.energy_trajectory, energies_out);
+  if (errors_out) std::copy(res.energy_error_trajectory.begin(), res.energy_error_trajectory.end(), errors_out);
+  if (grad_norms_out) std::copy(res.gradient_norms.begin(), res.gradient_norms.end(), grad_norms_out);
+  if (selected_eta_out) std::copy(res.selected_eta.begin(), res.selected_eta.end(), selected_eta_out);
+  if (info_out) {
+    info_out[0] = (double)res.energy_trajectory.size();
+    write_events(res.spike_stats, guard_count(gs.g[22], "events capacity"), events_out, info_out + 1);
+    info_out[5] = (double)res.evaluator_calls; info_out[6] = (double)res.energy_only_calls; info_out[7] = (double)res.total_iterations;
+    info_out[8] = res.converged ? 1.0 : 0.0; info_out[9] = res.min_energy; info_out[10] = (double)res.sr_iterations;
+    info_out[11] = res.sr_natural_grad_norm; info_out[12] = res.sr_residual_norm; info_out[13] = (double)res.selected_eta.size();
+  }
+}
+
+// Optimizer::IterativeOptimize with spike recovery, step selectors and checkpoints, on a fixed set of configurations.  algo as
+// make_vmc_algo.  First-order rules and L-BFGS evaluate by exact summation over all_configs (optimize_exact_sum_impl); SR and MinSR
+// need the sample store, so they take all_configs as a sample set of weight 1 (sr_step_samples_impl).  nf != NULL: a fermionic state
+// (fermion_optimize_exact_sum_impl).  state_out is written on every exit, a throw from the loop included; lowest_out: theta at the
+// lowest accepted energy (pepsgpu_vmc_snapshot_save); probe_state_out: theta when on_iteration reports iteration guard[21].
+template <typename TenElemT>
+void guarded_optimize_exact_sum_impl(int rows, int cols, int D, int d, const int32_t *nf, const uint8_t *bond_parity, int chi, int dtype,
+                                     const double *sitps_flat, const int32_t *all_configs, int n_configs, int model, const double *prm,
+                                     int n_prm, const VMCSpec &spec, int batch, const GuardSpec &gs, double *energies_out, double *errors_out,
+                                     double *grad_norms_out, double *selected_eta_out, double *events_out, double *state_out,
+                                     double *lowest_out, double *probe_state_out, double *info_out) {
+  // every refusal that needs no device comes first
+  if (n_configs < 1 || batch < 1 || !all_configs || !sitps_flat || !prm) throw std::invalid_argument("pepshost_guarded_optimize_exact_sum: bad arguments");
+  const OptimizerParams op = make_guarded_params(gs, spec.iterations, spec.lr, spec.clip_value, spec.clip_norm, make_vmc_algo(spec));
+  op.ValidateGuards();
+  const bool fermion = nf != nullptr, sample_set = spec.algo == 3 || spec.algo == 4;
+  if (!fermion && (model < 0 || model > 4)) throw std::invalid_argument("pepshost_guarded_optimize_exact_sum: model must be xxz, tfim, j1j2, triangle or trij1j2");
+  FermionDecoration dec;
+  if (fermion) dec = make_decoration(rows, cols, D, d, nf, bond_parity);
+  const FermionDecoration *decp = fermion ? &dec : nullptr;
+  const int dev_d = fermion ? 4 * d : d;
+  SplitIndexTPST<TenElemT> sitps = make_state_t<TenElemT>(rows, cols, D, dev_d, sitps_flat);
+  BMPSContractorT<TenElemT> contractor(rows, cols, D, dev_d, trunc_params(chi), sample_set ? n_configs : batch, dtype, g_device);
+  std::vector<std::vector<int32_t>> all(n_configs);
+  for (int i = 0; i < n_configs; ++i) all[i].assign(all_configs + (size_t)i * rows * cols, all_configs + (size_t)(i + 1) * rows * cols);
+  const Configuration samples = make_cfg(n_configs, rows, cols, all_configs);
+  contractor.UploadState(sitps);
+  Optimizer<TenElemT> opt(op, contractor, decp);
+  auto calls = std::make_shared<size_t>(0);
+  double lowest = std::numeric_limits<double>::max();
+  bool has_lowest = false;
+  typename Optimizer<TenElemT>::OptimizationCallback cb;
+  cb.on_evaluation_accepted = [&](const DeviceEvaluationT<TenElemT> &, const TenElemT &e, size_t) {
+    if (std::real(e) < lowest) { lowest = std::real(e); contractor.VMCSnapshotSave(); has_lowest = true; }
+  };
+  const long probe = (long)gs.g[21];
+  if (probe >= 0 && probe_state_out)
+    cb.on_iteration = [&](size_t it, double, double, double) {
+      if ((long)it == probe) copy_out(opt.GetState(rows, cols, d, D).flat(), probe_state_out);
+    };
+  auto run = [&](auto &m) {
+    typename Optimizer<TenElemT>::Evaluator inner = [&](BMPSContractorT<TenElemT> &c) {
+      return sample_set ? SampleSetAccumulateResident(sitps, samples, c, m, decp) : ExactSumAccumulateResident(sitps, all, c, m, (size_t)batch, decp);
+    };
+    return opt.IterativeOptimize(wrap_schedule<TenElemT>(inner, gs, calls), cb);
+  };
+  typename Optimizer<TenElemT>::OptimizationResult res;
+  try {
+    if (fermion) res = with_fermion_model<TenElemT>(model, prm, n_prm, run);
+    else if (model == 0) { SquareSpinOneHalfXXZModelOBC m(prm[0], prm[1], prm[2]); res = run(m); }
+    else if (model == 2) { SquareSpinOneHalfJ1J2XXZModelOBC m(prm[0], prm[1], prm[2], prm[3], prm[4]); res = run(m); }
+    else if (model == 3) { SpinOneHalfTriHeisenbergSqrPEPS m; res = run(m); }
+    else if (model == 4) { SpinOneHalfTriJ1J2HeisenbergSqrPEPS m(prm[0]); res = run(m); }
+    else { TransverseFieldIsingSquareOBC m(prm[0]); res = run(m); }
+  } catch (...) {
+    copy_out(opt.GetState(rows, cols, d, D).flat(), state_out);
+    if (info_out) info_out[5] = (double)*calls;
+    throw;
+  }
+  write_guarded_result<TenElemT>(res, gs, energies_out, errors_out, grad_norms_out, selected_eta_out, events_out, info_out);
+  copy_out(opt.GetState(rows, cols, d, D).flat(), state_out);
+  if (has_lowest && lowest_out) {
+    SplitIndexTPST<TenElemT> snap(rows, cols, dev_d, D);
+    contractor.VMCSnapshotRead(snap);
+    copy_stored_out(snap, (size_t)d, lowest_out);
+  }
+  if (info_out) info_out[14] = has_lowest ? 1.0 : 0.0;
+}
+
+// vmc_optimize_impl with spike recovery, step selectors and checkpoints; the schedule wraps the executor's own evaluator
+// (SetEnergyEvaluator).  No closing normalisation, no dumps.  accept_out [accepted evaluation][walker].
+template <typename TenElemT>
+void guarded_vmc_optimize_impl(int rows, int cols, int D, int d, const int32_t *nf, const uint8_t *bond_parity, int chi, int dtype,
+                               const double *sitps_flat, int n, int32_t *configs, const uint64_t *seeds, int n_seeds, int updater, int model,
+                               const double *p, int n_prm, const VMCSpec &spec, const GuardSpec &gs, double *energies_out, double *errors_out,
+                               double *grad_norms_out, double *selected_eta_out, double *events_out, double *accept_out, double *state_out,
+                               double *lowest_out, double *info_out) {
+  if (n < 0 || n_seeds < 0 || (n > 0 && !configs) || (n_seeds > 0 && !seeds) || !sitps_flat) throw std::invalid_argument("vmc: null / negative argument");
+  VMCPEPSOptimizerParams vp = make_vmc_params(spec, chi, "", "", "");
+  vp.optimizer_params = make_guarded_params(gs, spec.iterations, spec.lr, spec.clip_value, spec.clip_norm, make_vmc_algo(spec));
+  vp.Validate((size_t)n, (size_t)n_seeds);
+  const bool fermion = nf != nullptr;
+  const std::vector<uint64_t> sd(seeds, seeds + n_seeds);
+  with_vmc_pair(fermion, updater, model, p, n_prm, sd, /*dry=*/true, [](auto &, auto &) {});
+  FermionDecoration dec;
+  if (fermion) dec = make_decoration(rows, cols, D, d, nf, bond_parity);
+  const int dev_d = fermion ? 4 * d : d;
+  SplitIndexTPST<TenElemT> sitps = make_state_t<TenElemT>(rows, cols, D, dev_d, sitps_flat);
+  BMPSContractorT<TenElemT> contractor(rows, cols, D, dev_d, vp.peps_params, n, dtype, g_device);
+  contractor.UploadState(sitps);
+  TPSWaveFunctionComponentT<TenElemT> comp(typename TPSWaveFunctionComponentT<TenElemT>::ResidentState(), make_cfg(n, rows, cols, configs),
+                                           contractor, fermion ? &dec : nullptr);
+  auto calls = std::make_shared<size_t>(0);
+  with_vmc_pair(fermion, updater, model, p, n_prm, sd, /*dry=*/false, [&](auto &upd, auto &m) {
+    VMCPEPSOptimizer<std::decay_t<decltype(upd)>, std::decay_t<decltype(m)>, TenElemT> exe(vp, comp, upd, m, sd.size(), (size_t)D);
+    if (gs.n_schedule > 0) {
+      exe.SetEnergyEvaluator(wrap_schedule<TenElemT>([&exe](BMPSContractorT<TenElemT> &c) { return exe.GetEvaluator().Evaluate(c); }, gs, calls));
+      exe.SetEnergyOnlyEvaluator([&exe](BMPSContractorT<TenElemT> &c) { return exe.GetEvaluator().EvaluateEnergyOnly(c); });
+    }
+    const auto res = exe.WarmUpAndOptimize();
+    write_guarded_result<TenElemT>(res, gs, nullptr, nullptr, grad_norms_out, selected_eta_out, events_out, info_out);
+    copy_out(exe.GetEnergyTrajectory(), energies_out);           // the executor's own bookkeeping: accepted evaluations only
+    const size_t ne = exe.GetEnergyTrajectory().size();
+    if (errors_out) std::copy(exe.GetEnergyErrorTrajectory().begin(), exe.GetEnergyErrorTrajectory().end(), errors_out);
+    if (accept_out)
+      for (size_t k = 0; k < ne; ++k) {
+        const auto &a = exe.GetAcceptRatesTrajectory()[k];
+        for (size_t w = 0; w < (size_t)n; ++w) accept_out[k * n + w] = w < a.size() ? a[w] : 0.0;
+      }
+    copy_out(exe.GetState().flat(), state_out);
+    copy_out(exe.GetLowestState().flat(), lowest_out);
+    if (info_out) {
+      info_out[0] = (double)ne; info_out[9] = exe.GetMinEnergy(); info_out[14] = 1.0;
+      write_events(exe.GetSpikeStatistics(), guard_count(gs.g[22], "events capacity"), nullptr, info_out + 1);
+    }
+  });
+  std::copy(comp.config.data(), comp.config.data() + (size_t)n * rows * cols, configs);
+}
 }  // namespace
 
 extern "C" {
@@ -1524,6 +1741,177 @@ int pepshost_binned_energy_stat(const double *samples, int n_samples, int n_walk
       const auto r = MeanAndBinnedErrorSqrtNUniformBin(std::vector<double>(samples, samples + cnt), (size_t)n_walkers);
       mean_out[0] = r.first; *err_out = r.second;
     }
+  });
+}
+
+// ---- spike recovery and step selectors: the decision code alone, on the host (no device) ----
+// EMATracker over series[n]: mean_out / var_out after every Update; reset_at >= 0: Reset() before that observation
+int pepshost_ema_track(const double *series, int n, long window, int reset_at, double *mean_out, double *var_out) {
+  return guarded([&]() {
+    if (!series || !mean_out || !var_out || n < 0 || window < 0) throw std::invalid_argument("pepshost_ema_track: bad arguments");
+    EMATracker t((size_t)window);
+    for (int i = 0; i < n; ++i) {
+      if (i == reset_at) {
+        t.Reset();
+        if (t.IsInitialized() || t.Mean() != 0.0 || t.Var() != 0.0) throw std::logic_error("pepshost_ema_track: Reset left state behind");
+      }
+      t.Update(series[i]);
+      mean_out[i] = t.Mean(); var_out[i] = t.Var();
+    }
+  });
+}
+// The SpikeGuard of Optimizer::IterativeOptimize driven by a scripted series: records [n][5] = (energy, error, grad_norm, ngrad_norm,
+// cg_iters), one per evaluation in the order the optimizer would make them; algo as make_vmc_algo (3 SR: S3 with the CG iterations,
+// 4 MinSR: S3 on the norm only, others: no S3).  guard: the nine spike fields.  A rejected record (resample, rollback) is followed by
+// the next record at the same iteration.  actions_out [n]: the verdict per record (SpikeAction; accepted with a warning = 3);
+// iters_out [n]: the iteration it was judged at; ema_out [n][8]: mean and var of the four trackers after the record; events_out
+// [cap][6] and counts_out [4] as write_events; csv_out (cap csv_cap): the trigger CSV of the event log.
+int pepshost_spike_replay(const double *records, int n, int algo, const double *guard, int32_t *actions_out, int32_t *iters_out,
+                          double *ema_out, double *events_out, int events_cap, double *counts_out, char *csv_out, long csv_cap) {
+  return guarded([&]() {
+    if (!records || n < 0 || !guard || !actions_out || events_cap < 0) throw std::invalid_argument("pepshost_spike_replay: bad arguments");
+    SpikeGuard sg(make_spike_params(guard, nullptr), /*log_to_stdout=*/false);
+    const bool is_sr = algo == 3, is_minsr = algo == 4;
+    size_t iter = 0, attempts = 0;
+    for (int k = 0; k < n; ++k) {
+      const double *r = records + 5 * (size_t)k;
+      if (iters_out) iters_out[k] = (int32_t)iter;
+      bool warned = false;
+      auto rejected = [&](SpikeAction a) {
+        if (a == SpikeAction::kAcceptWithWarning) warned = true;
+        if (a == SpikeAction::kResample) { ++attempts; return true; }
+        if (a == SpikeAction::kRollback) { sg.TakeBase(); attempts = 0; return true; }
+        return false;
+      };
+      SpikeAction a = sg.JudgeEvaluation(iter, attempts, r[1], r[2]);
+      bool out = rejected(a);
+      if (!out && (is_sr || is_minsr) && sg.Params().enable_auto_recover) {
+        a = sg.JudgeDirection(iter, attempts, r[3], is_minsr ? std::numeric_limits<size_t>::max() : (size_t)r[4]);
+        out = rejected(a);
+      }
+      if (!out) { a = sg.JudgeEnergy(iter, attempts, r[0]); out = rejected(a); }
+      if (!out) {
+        sg.Accept(r[0], r[1], r[2], (is_sr || is_minsr) ? r + 3 : nullptr);
+        if (sg.Params().enable_rollback) sg.MarkBaseSaved();
+        a = warned ? SpikeAction::kAcceptWithWarning : SpikeAction::kAccept;
+        ++iter; attempts = 0;
+      }
+      actions_out[k] = (int32_t)a;
+      if (ema_out) {
+        double *o = ema_out + 8 * (size_t)k;
+        const EMATracker *t[4] = {&sg.EnergyEMA(), &sg.ErrorEMA(), &sg.GradNormEMA(), &sg.NaturalGradNormEMA()};
+        for (int j = 0; j < 4; ++j) { o[2 * j] = t[j]->Mean(); o[2 * j + 1] = t[j]->Var(); }
+      }
+    }
+    write_events(sg.Statistics(), (size_t)events_cap, events_out, counts_out);
+    if (csv_out && csv_cap > 0) {
+      std::ostringstream os;
+      SpikeGuard::WriteTriggerCsv(os, sg.Statistics());
+      const std::string t = os.str();
+      if ((long)t.size() + 1 > csv_cap) throw std::out_of_range("pepshost_spike_replay: csv_out too small");
+      std::memcpy(csv_out, t.c_str(), t.size() + 1);
+    }
+  });
+}
+// AcceptanceRateCheck: flags_out[w] = 1 for a walker whose rate is below half the maximum over the walkers
+int pepshost_acceptance_rate_check(const double *rates, int n, int32_t *flags_out) {
+  return guarded([&]() {
+    if (n < 0 || (n > 0 && (!rates || !flags_out))) throw std::invalid_argument("pepshost_acceptance_rate_check: bad arguments");
+    std::fill(flags_out, flags_out + n, 0);
+    for (const size_t w : AcceptanceRateCheck(std::vector<double>(rates, rates + n))) flags_out[w] = 1;
+  });
+}
+// The selection rule of a step selector: kind 0 initial, 1 periodic; results [n][3] = (eta, energy, error) of the trials;
+// out = [selected eta, the selector's base learning rate afterwards].  Non-finite trial values throw as in the optimizer.
+int pepshost_step_select(int kind, const double *results, int n, long iter, long max_iterations, double base_lr, double phase_switch_ratio,
+                         double *out) {
+  return guarded([&]() {
+    if ((kind != 0 && kind != 1) || !results || !out || iter < 0 || max_iterations < 0) throw std::invalid_argument("pepshost_step_select: bad arguments");
+    if (n < 1 || (kind == 1 && n != 2)) throw std::invalid_argument("pepshost_step_select: the initial rule takes >= 1 trials, the periodic rule 2");
+    std::vector<StepCandidateResult> r;
+    for (int i = 0; i < n; ++i) {
+      CheckStepCandidate(results[3 * i + 1], results[3 * i + 2]);
+      r.push_back({results[3 * i], results[3 * i + 1], results[3 * i + 2]});
+    }
+    out[0] = kind == 0 ? SelectInitialStep(r) : SelectPeriodicStep(r, (size_t)iter, (size_t)max_iterations, phase_switch_ratio);
+    out[1] = NextSelectorBaseLR(kind == 0, base_lr, out[0]);
+  });
+}
+// the candidates a selector tries from base_lr: kind 0 -> base_lr * 1 .. max_line_search_steps, kind 1 -> (base_lr, base_lr / 2)
+int pepshost_step_candidates(int kind, double base_lr, int max_line_search_steps, double *out, int cap, int *n_out) {
+  return guarded([&]() {
+    if ((kind != 0 && kind != 1) || !out || !n_out || max_line_search_steps < 0) throw std::invalid_argument("pepshost_step_candidates: bad arguments");
+    const std::vector<double> c = StepCandidates(kind == 0, base_lr, (size_t)max_line_search_steps);
+    if ((int)c.size() > cap) throw std::out_of_range("pepshost_step_candidates: out too small");
+    std::copy(c.begin(), c.end(), out);
+    *n_out = (int)c.size();
+  });
+}
+// OptimizerParams::ValidateGuards and VMCPEPSOptimizerParams::Validate for (algo, guard) with no device: what the guarded entries
+// below refuse first.  n_walkers < 0: the optimizer's check alone.
+int pepshost_validate_guards(int algo, const double *rule_params, int n_rule_params, double lr, const double *guard, int n_walkers, int n_seeds,
+                             int samples_per_walker) {
+  return guarded([&]() {
+    VMCSpec v;
+    v.algo = algo; v.rule_params = rule_params; v.n_rule_params = n_rule_params; v.lr = lr; v.samples_per_walker = samples_per_walker;
+    GuardSpec gs;
+    gs.g = guard;
+    if (n_walkers < 0) { make_guarded_params(gs, 1, lr, 0.0, 0.0, make_vmc_algo(v)).ValidateGuards(); return; }
+    VMCPEPSOptimizerParams vp = make_vmc_params(v, 8, "", "", "");
+    vp.optimizer_params = make_guarded_params(gs, 1, lr, 0.0, 0.0, make_vmc_algo(v));
+    vp.Validate((size_t)n_walkers, (size_t)n_seeds);
+  });
+}
+// ---- ... and around the device-resident Optimizer (guarded_optimize_exact_sum_impl / guarded_vmc_optimize_impl) ----
+// nf == NULL: a bosonic state; dtype PEPSGPU_C128 runs the QLTEN_Complex instantiation.  opt = [algo, lr, iterations, clip_value,
+// clip_norm]; guard as GuardSpec; error_override / energy_shift [n_schedule] (n_schedule 0: no schedule).
+int pepshost_guarded_optimize_exact_sum(int rows, int cols, int D, int d, const int32_t *nf, const uint8_t *bond_parity, int chi, int dtype,
+                                        const double *sitps_flat, const int32_t *all_configs, int n_configs, int model, const double *prm,
+                                        int n_prm, const double *opt, const double *rule_params, int n_rule_params, int batch,
+                                        const double *guard, const char *csv_path, const char *checkpoint_path, const double *error_override,
+                                        const double *energy_shift, int n_schedule, double *energies_out, double *errors_out,
+                                        double *grad_norms_out, double *selected_eta_out, double *events_out, double *state_out,
+                                        double *lowest_out, double *probe_state_out, double *info_out) {
+  return guarded([&]() {
+    if (!opt || !guard) throw std::invalid_argument("pepshost_guarded_optimize_exact_sum: the opt / guard arrays are required");
+    if (!(opt[2] >= 0.0 && opt[2] < 1e9)) throw std::invalid_argument("pepshost_guarded_optimize_exact_sum: iterations out of range");
+    VMCSpec v;
+    v.algo = (int)opt[0]; v.lr = opt[1]; v.iterations = (int)opt[2]; v.clip_value = opt[3]; v.clip_norm = opt[4];
+    v.rule_params = rule_params; v.n_rule_params = n_rule_params;
+    GuardSpec gs;
+    gs.g = guard; gs.csv_path = csv_path; gs.checkpoint_path = checkpoint_path; gs.error_override = error_override;
+    gs.energy_shift = energy_shift; gs.n_schedule = n_schedule;
+    if (dtype == PEPSGPU_C128)
+      guarded_optimize_exact_sum_impl<QLTEN_Complex>(rows, cols, D, d, nf, bond_parity, chi, dtype, sitps_flat, all_configs, n_configs, model, prm,
+                                                     n_prm, v, batch, gs, energies_out, errors_out, grad_norms_out, selected_eta_out, events_out,
+                                                     state_out, lowest_out, probe_state_out, info_out);
+    else
+      guarded_optimize_exact_sum_impl<double>(rows, cols, D, d, nf, bond_parity, chi, dtype, sitps_flat, all_configs, n_configs, model, prm,
+                                              n_prm, v, batch, gs, energies_out, errors_out, grad_norms_out, selected_eta_out, events_out,
+                                              state_out, lowest_out, probe_state_out, info_out);
+  });
+}
+int pepshost_guarded_vmc_optimize(int rows, int cols, int D, int d, const int32_t *nf, const uint8_t *bond_parity, int chi, int dtype,
+                                  const double *sitps_flat, int n, int32_t *configs, const uint64_t *seeds, int n_seeds, int updater, int model,
+                                  const double *prm, int n_prm, const double *mc, const double *opt, const double *rule_params,
+                                  int n_rule_params, const double *guard, const char *csv_path, const char *checkpoint_path,
+                                  const double *error_override, const double *energy_shift, int n_schedule, double *energies_out,
+                                  double *errors_out, double *grad_norms_out, double *selected_eta_out, double *events_out, double *accept_out,
+                                  double *state_out, double *lowest_out, double *info_out) {
+  return guarded([&]() {
+    if (!guard) throw std::invalid_argument("pepshost_guarded_vmc_optimize: the guard array is required");
+    const VMCSpec v = vmc_spec(mc, opt, rule_params, n_rule_params);
+    GuardSpec gs;
+    gs.g = guard; gs.csv_path = csv_path; gs.checkpoint_path = checkpoint_path; gs.error_override = error_override;
+    gs.energy_shift = energy_shift; gs.n_schedule = n_schedule;
+    if (dtype == PEPSGPU_C128)
+      guarded_vmc_optimize_impl<QLTEN_Complex>(rows, cols, D, d, nf, bond_parity, chi, dtype, sitps_flat, n, configs, seeds, n_seeds, updater,
+                                               model, prm, n_prm, v, gs, energies_out, errors_out, grad_norms_out, selected_eta_out, events_out,
+                                               accept_out, state_out, lowest_out, info_out);
+    else
+      guarded_vmc_optimize_impl<double>(rows, cols, D, d, nf, bond_parity, chi, dtype, sitps_flat, n, configs, seeds, n_seeds, updater, model,
+                                        prm, n_prm, v, gs, energies_out, errors_out, grad_norms_out, selected_eta_out, events_out, accept_out,
+                                        state_out, lowest_out, info_out);
   });
 }
 

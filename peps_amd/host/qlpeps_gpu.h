@@ -22,6 +22,8 @@
 //   SGDParams / AdaGradParams / AdamParams / StochasticReconfigurationParams / OptimizerParams   optimizer/optimizer_params.h
 //   ConstantLR / ExponentialDecayLR / StepLR   optimizer/lr_schedulers.h:40-103
 //   Optimizer                    optimizer/optimizer.h, optimizer_impl.h (first-order rules and the one-rank SR step, on device buffers)
+//   EMATracker / SpikeSignal / SpikeAction / SpikeEventRecord / SpikeStatistics   optimizer/spike_detection.h
+//   SpikeRecoveryParams / CheckpointParams / InitialStepSelectorParams / PeriodicStepSelectorParams   optimizer/optimizer_params.h:155-313
 //
 // Error codes of the ABI are re-raised as the reference's exception types.
 #pragma once
@@ -36,6 +38,7 @@
 #include <fstream>
 #include <functional>
 #include <iomanip>
+#include <iostream>
 #include <limits>
 #include <map>
 #include <memory>
@@ -351,6 +354,7 @@ class BMPSContractorT {
   size_t cols() const { return cols_; }
   size_t walkers() const { return (size_t)pepsgpu_n_walkers(ctx_); }
   size_t phys_dim() const { return d_; }                  // states per site on the device (fermions: the 4 d extended states)
+  size_t bond_dim() const { return D_; }
   const BMPSTruncateParams &GetTruncateParams() const { return trunc_; }
 
   void UploadState(const SplitIndexTPST<TenElemT> &s) { check_rc(pepsgpu_state_upload(ctx_, dptr(s.flat().data()), ElemTraits<TenElemT>::host_dtype), ctx_); }
@@ -700,6 +704,14 @@ class BMPSContractorT {
     check_rc(pepsgpu_opt_step(ctx_, rule, lr, params.data(), (int)params.size()), ctx_);
   }
   void OptScaleState(double factor) { check_rc(pepsgpu_opt_scale_state(ctx_, factor), ctx_); }
+  // the base of a step, kept in HBM (pepsgpu_guard_*): prev_accepted_state_ of the spike rollback and the base of the selector trials
+  void OptBaseSave() { check_rc(pepsgpu_guard_base_save(ctx_), ctx_); }
+  void OptBaseRestore() { check_rc(pepsgpu_guard_base_restore(ctx_), ctx_); }
+  void OptBaseClear() { check_rc(pepsgpu_guard_base_clear(ctx_), ctx_); }
+  // theta <- the SGD rule on (base, g, velocity), the velocity untouched; params (0, 0, 0): base - lr g
+  void OptPreview(double lr, const std::vector<double> &params) {
+    check_rc(pepsgpu_guard_preview(ctx_, 0, lr, params.data(), (int)params.size()), ctx_);
+  }
   // L-BFGS on the optimizer buffers (pepsgpu_lbfgs_*): history, anchor, direction and the base of the line search stay in HBM
   void LBFGSBegin(size_t history_size) { check_rc(pepsgpu_lbfgs_begin(ctx_, (int)std::min<size_t>(history_size, 1u << 20)), ctx_); }
   void LBFGSReset() { check_rc(pepsgpu_lbfgs_reset(ctx_), ctx_); }
@@ -4116,9 +4128,10 @@ std::pair<TenElemT, SplitIndexTPST<TenElemT>> ExactSumEnergyEvaluator(const Spli
 // device, norms and the SR solve are those of the stored parameters); the one-rank MinSR step (MinSRParams: T matrix, eigensolve,
 // cutoff and back-substitution on the device, pepsgpu_minsr_direction) for bosonic states; L-BFGS (LBFGSParams) with the fixed step or
 // the strong-Wolfe line search for bosonic and fermionic states: history, anchor, direction and the base of the search in HBM
-// (pepsgpu_lbfgs_*), every trial point one element-wise pass, one evaluation of the resident state and one dot product.  Out (host
-// drivers of the reference that stay with the caller): step selectors, spike detection and its L-BFGS snapshots, checkpoints, CSV /
-// JSONL logs, MinSR over several ranks or on a fermionic state (peps_amd/sr.py), multi-rank CG and the multi-rank broadcast of the
+// (pepsgpu_lbfgs_*), every trial point one element-wise pass, one evaluation of the resident state and one dot product; spike
+// recovery (S1-S4 with resampling and rollback), the initial and the periodic step selector and checkpoints, with the base of a step,
+// the selector trials and the restored state formed in HBM (pepsgpu_guard_*).  Out (host drivers of the reference that stay with
+// the caller): the L-BFGS ring snapshot for a rollback, the JSONL log, MinSR over several ranks or on a fermionic state (peps_amd/sr.py), multi-rank CG and the multi-rank broadcast of the
 // L-BFGS direction.  Parameter names and defaults: optimizer/optimizer_params.h.
 struct ConjugateGradientParams {               // optimizer_params.h:50-57
   size_t max_iter = 100;
@@ -4224,6 +4237,242 @@ struct LBFGSParams {                           // :119-152
         fallback_fixed_step_scale(fallback_fixed_step_scale) {}
 };
 
+// ---- step selectors, checkpoints and spike recovery: names and defaults of optimizer_params.h:155-313 ----
+struct PeriodicStepSelectorParams {            // :164-169
+  bool enabled = false;
+  size_t every_n_steps = 10;                   // trials at iterations k * every_n_steps, k >= 1
+  double phase_switch_ratio = 0.3;             // early / late rule boundary as a fraction of max_iterations
+  bool enable_in_deterministic = false;        // run although the evaluator reports no error bar
+};
+struct InitialStepSelectorParams {             // :180-184
+  bool enabled = false;
+  size_t max_line_search_steps = 3;            // candidates lr * 1 .. lr * max_line_search_steps at iteration 0
+  bool enable_in_deterministic = false;
+};
+struct CheckpointParams {                      // :278-283
+  size_t every_n_steps = 0;                    // 0: off
+  std::string base_path;                       // base_path/step_{k}/
+  bool IsEnabled() const { return every_n_steps > 0 && !base_path.empty(); }
+};
+struct SpikeRecoveryParams {                   // :299-313
+  bool enable_auto_recover = true;             // S1-S3: evaluate again
+  size_t redo_mc_max_retries = 2;              // evaluations repeated per iteration before the last resort
+  double factor_err = 100.0;                   // S1: error > factor_err * EMA(error)
+  double factor_grad = 1e10;                   // S2: |g| > factor_grad * EMA(|g|)
+  double factor_ngrad = 10.0;                  // S3: |x| > factor_ngrad * EMA(|x|), x the natural-gradient direction
+  size_t sr_min_iters_suspicious = 1;          // S3: a CG solve of at most this many iterations
+  bool enable_rollback = false;                // S4 and the rollback after exhausted retries
+  size_t ema_window = 50;
+  double sigma_k = 10.0;                       // S4: E - EMA(E) > sigma_k * EMA_std(E)
+  std::string log_trigger_csv_path;            // empty: no CSV
+};
+
+// ---- spike detection (optimizer/spike_detection.h) ----
+enum class SpikeSignal { kNone, kS1_ErrorbarSpike, kS2_GradientNormSpike, kS3_NaturalGradientAnomaly, kS4_EMAEnergySpikeUpward };   // :29-35
+enum class SpikeAction { kAccept, kResample, kRollback, kAcceptWithWarning };                                                        // :40-45
+struct SpikeEventRecord {                      // :50-57
+  size_t step, attempt;
+  SpikeSignal signal;
+  SpikeAction action;
+  double value, threshold;
+};
+struct SpikeStatistics {                       // :62-67
+  size_t total_resamples = 0, total_rollbacks = 0, total_forced_accepts = 0;
+  std::vector<SpikeEventRecord> event_log;
+};
+// exponential moving average with a variance estimate (:80-114): alpha = 2 / (window + 1); the first observation sets the mean and
+// var = 0; then delta = x - mean, mean += alpha delta, var = (1 - alpha) (var + alpha delta^2)
+class EMATracker {
+ public:
+  explicit EMATracker(size_t window = 50) : alpha_(2.0 / (static_cast<double>(window) + 1.0)) {}
+  void Update(double x) {
+    if (!initialized_) { ema_ = x; var_ = 0.0; initialized_ = true; return; }
+    const double delta = x - ema_;
+    ema_ += alpha_ * delta;
+    var_ = (1.0 - alpha_) * (var_ + alpha_ * delta * delta);
+  }
+  double Mean() const { return ema_; }
+  double Var() const { return var_; }
+  double Std() const { return std::sqrt(var_); }
+  bool IsInitialized() const { return initialized_; }
+  void Reset() { ema_ = 0.0; var_ = 0.0; initialized_ = false; }
+ private:
+  double alpha_, ema_ = 0.0, var_ = 0.0;
+  bool initialized_ = false;
+};
+inline const char *SignalName(SpikeSignal s) {   // :116-125
+  switch (s) {
+    case SpikeSignal::kNone: return "NONE";
+    case SpikeSignal::kS1_ErrorbarSpike: return "S1_ERRORBAR";
+    case SpikeSignal::kS2_GradientNormSpike: return "S2_GRAD_NORM";
+    case SpikeSignal::kS3_NaturalGradientAnomaly: return "S3_NGRAD_ANOMALY";
+    case SpikeSignal::kS4_EMAEnergySpikeUpward: return "S4_ENERGY_SPIKE";
+  }
+  return "UNKNOWN";
+}
+inline const char *ActionName(SpikeAction a) {   // :127-135
+  switch (a) {
+    case SpikeAction::kAccept: return "ACCEPT";
+    case SpikeAction::kResample: return "RESAMPLE";
+    case SpikeAction::kRollback: return "ROLLBACK";
+    case SpikeAction::kAcceptWithWarning: return "ACCEPT_WARN";
+  }
+  return "UNKNOWN";
+}
+
+// The host side of spike recovery, with no device call in it: the four trackers, detection (DetectS1S2_ / DetectS3_ / DetectS4_,
+// optimizer_impl.h:1871-1919), the decision (DecideAction_, :1921-1944), the event log and its counters (LogSpikeEvent_, :1955-1973)
+// and the trigger CSV (:1841-1856).  Optimizer::IterativeOptimize drives it with device results and acts on the verdicts (evaluate
+// again; restore the base); pepshost_spike_replay drives the same object with a scripted series.  "A base is saved" is tracked here
+// because the decision reads it (has_prev_state_).
+class SpikeGuard {
+ public:
+  explicit SpikeGuard(const SpikeRecoveryParams &cfg, bool log_to_stdout = true)
+      : cfg_(cfg), ema_energy_(cfg.ema_window), ema_error_(cfg.ema_window), ema_grad_norm_(cfg.ema_window), ema_ngrad_norm_(cfg.ema_window),
+        log_to_stdout_(log_to_stdout) {}
+  SpikeSignal DetectS1S2(double error, double grad_norm) const {
+    if (ema_error_.IsInitialized() && ema_error_.Mean() > 0.0 && error > cfg_.factor_err * ema_error_.Mean())
+      return SpikeSignal::kS1_ErrorbarSpike;
+    if (ema_grad_norm_.IsInitialized() && ema_grad_norm_.Mean() > 0.0 && grad_norm > cfg_.factor_grad * ema_grad_norm_.Mean())
+      return SpikeSignal::kS2_GradientNormSpike;
+    return SpikeSignal::kNone;
+  }
+  // a solve that ends within sr_min_iters_suspicious iterations is a signal on its own; MinSR passes SIZE_MAX
+  SpikeSignal DetectS3(double ngrad_norm, size_t sr_iters) const {
+    if (ema_ngrad_norm_.IsInitialized() && ema_ngrad_norm_.Mean() > 0.0 && ngrad_norm > cfg_.factor_ngrad * ema_ngrad_norm_.Mean())
+      return SpikeSignal::kS3_NaturalGradientAnomaly;
+    if (sr_iters <= cfg_.sr_min_iters_suspicious) return SpikeSignal::kS3_NaturalGradientAnomaly;
+    return SpikeSignal::kNone;
+  }
+  // upward only, and only once the energies have a spread
+  SpikeSignal DetectS4(double energy) const {
+    if (!ema_energy_.IsInitialized()) return SpikeSignal::kNone;
+    const double delta = energy - ema_energy_.Mean();
+    if (delta > 0.0 && ema_energy_.Std() > 0.0 && delta > cfg_.sigma_k * ema_energy_.Std()) return SpikeSignal::kS4_EMAEnergySpikeUpward;
+    return SpikeSignal::kNone;
+  }
+  SpikeAction DecideAction(SpikeSignal signal, size_t attempts, size_t step) const {
+    if (signal == SpikeSignal::kNone) return SpikeAction::kAccept;
+    if (signal == SpikeSignal::kS4_EMAEnergySpikeUpward) return SpikeAction::kRollback;
+    if (attempts < cfg_.redo_mc_max_retries) return SpikeAction::kResample;
+    if (cfg_.enable_rollback && has_base_ && step > 0) return SpikeAction::kRollback;
+    return SpikeAction::kAcceptWithWarning;
+  }
+  void LogSpikeEvent(size_t step, size_t attempt, SpikeSignal signal, SpikeAction action, double value, double threshold) {
+    if (log_to_stdout_) {
+      std::ostringstream os;
+      os << "[SPIKE] Step " << step << " attempt " << attempt << " | " << SignalName(signal) << " | value=" << std::scientific
+         << std::setprecision(3) << value << " threshold=" << threshold << " | -> " << ActionName(action);
+      std::cout << os.str() << std::endl;
+    }
+    if (action == SpikeAction::kResample) ++stats_.total_resamples;
+    else if (action == SpikeAction::kRollback) ++stats_.total_rollbacks;
+    else if (action == SpikeAction::kAcceptWithWarning) ++stats_.total_forced_accepts;
+    stats_.event_log.push_back({step, attempt, signal, action, value, threshold});
+  }
+  // The three stages of one evaluation, in the order of optimizer_impl.h:251-297, 683-729, 731-763: detect, decide, log.  The caller
+  // evaluates again on kResample (attempts + 1) and on kRollback (after TakeBase, attempts = 0), and goes on otherwise.
+  SpikeAction JudgeEvaluation(size_t step, size_t attempts, double error, double grad_norm) {
+    if (!cfg_.enable_auto_recover || step == 0) return SpikeAction::kAccept;
+    const SpikeSignal signal = DetectS1S2(error, grad_norm);
+    if (signal == SpikeSignal::kNone) return SpikeAction::kAccept;
+    const SpikeAction action = DecideAction(signal, attempts, step);
+    const bool s1 = signal == SpikeSignal::kS1_ErrorbarSpike;
+    LogSpikeEvent(step, attempts, signal, action, s1 ? error : grad_norm,
+                  s1 ? cfg_.factor_err * ema_error_.Mean() : cfg_.factor_grad * ema_grad_norm_.Mean());
+    return action;
+  }
+  SpikeAction JudgeDirection(size_t step, size_t attempts, double ngrad_norm, size_t sr_iters) {
+    if (!cfg_.enable_auto_recover || step == 0) return SpikeAction::kAccept;
+    const SpikeSignal signal = DetectS3(ngrad_norm, sr_iters);
+    if (signal == SpikeSignal::kNone) return SpikeAction::kAccept;
+    const SpikeAction action = DecideAction(signal, attempts, step);
+    LogSpikeEvent(step, attempts, signal, action, ngrad_norm, cfg_.factor_ngrad * ema_ngrad_norm_.Mean());
+    return action;
+  }
+  SpikeAction JudgeEnergy(size_t step, size_t attempts, double energy) {
+    if (!cfg_.enable_rollback || step == 0) return SpikeAction::kAccept;
+    const SpikeSignal signal = DetectS4(energy);
+    if (signal == SpikeSignal::kNone) return SpikeAction::kAccept;
+    LogSpikeEvent(step, attempts, signal, SpikeAction::kRollback, energy, ema_energy_.Mean() + cfg_.sigma_k * ema_energy_.Std());
+    return SpikeAction::kRollback;
+  }
+  // an accepted evaluation: the only thing the trackers ever see (:765-774)
+  void Accept(double energy, double error, double grad_norm, const double *ngrad_norm) {
+    ema_energy_.Update(energy);
+    ema_error_.Update(error);
+    ema_grad_norm_.Update(grad_norm);
+    if (ngrad_norm) ema_ngrad_norm_.Update(*ngrad_norm);
+  }
+  void MarkBaseSaved() { has_base_ = true; }
+  // a rollback consumes the base (has_prev_state_ = false): true when there was one to restore
+  bool TakeBase() { const bool had = has_base_; has_base_ = false; return had; }
+  bool HasBase() const { return has_base_; }
+  const SpikeRecoveryParams &Params() const { return cfg_; }
+  const SpikeStatistics &Statistics() const { return stats_; }
+  const EMATracker &EnergyEMA() const { return ema_energy_; }
+  const EMATracker &ErrorEMA() const { return ema_error_; }
+  const EMATracker &GradNormEMA() const { return ema_grad_norm_; }
+  const EMATracker &NaturalGradNormEMA() const { return ema_ngrad_norm_; }
+  static void WriteTriggerCsv(std::ostream &csv, const SpikeStatistics &stats) {
+    csv << "step,attempt,signal,action,value,threshold\n";
+    for (const auto &ev : stats.event_log)
+      csv << ev.step << "," << ev.attempt << "," << SignalName(ev.signal) << "," << ActionName(ev.action) << "," << std::scientific
+          << std::setprecision(6) << ev.value << "," << ev.threshold << "\n";
+  }
+  // nothing is written when no event was logged, as in the reference
+  void WriteTriggerCsvFile() const {
+    if (cfg_.log_trigger_csv_path.empty() || stats_.event_log.empty()) return;
+    std::ofstream csv(cfg_.log_trigger_csv_path);
+    if (csv) WriteTriggerCsv(csv, stats_);
+  }
+ private:
+  SpikeRecoveryParams cfg_;
+  EMATracker ema_energy_, ema_error_, ema_grad_norm_, ema_ngrad_norm_;
+  SpikeStatistics stats_;
+  bool has_base_ = false;
+  bool log_to_stdout_;
+};
+
+// ---- the selection rules of the step selectors (optimizer_impl.h:489-538), with no device call in them ----
+struct StepCandidateResult { double eta, energy, error; };
+constexpr double kSelectorLateSigma = 1.0;
+// the lowest trial energy; the first of equal ones
+inline double SelectInitialStep(const std::vector<StepCandidateResult> &r) {
+  double selected = r.front().eta, best = r.front().energy;
+  for (const auto &c : r)
+    if (c.energy < best) { best = c.energy; selected = c.eta; }
+  return selected;
+}
+// r = {eta, eta / 2}.  Early phase (iter < phase_switch_ratio * max_iterations): the half step when its energy is lower at all;
+// late phase: only when it is lower by more than kSelectorLateSigma * max(error_eta, error_half)
+inline double SelectPeriodicStep(const std::vector<StepCandidateResult> &r, size_t iter, size_t max_iterations, double phase_switch_ratio) {
+  const bool early = static_cast<double>(iter) < phase_switch_ratio * static_cast<double>(max_iterations);
+  if (early) return r[1].energy < r[0].energy ? r[1].eta : r[0].eta;
+  return r[0].energy - r[1].energy > kSelectorLateSigma * std::max(r[0].error, r[1].error) ? r[1].eta : r[0].eta;
+}
+inline std::vector<double> StepCandidates(bool initial, double base_lr, size_t max_line_search_steps) {
+  std::vector<double> etas;
+  if (initial) {
+    for (size_t i = 1; i <= max_line_search_steps; ++i) etas.push_back(base_lr * static_cast<double>(i));
+  } else {
+    if (base_lr * 0.5 <= 0.0) throw std::invalid_argument("Auto step selector requires positive candidate step sizes");
+    etas = {base_lr, base_lr * 0.5};
+  }
+  return etas;
+}
+// the selector's base learning rate after a selection: the initial selector sets it, the periodic one never raises it
+inline double NextSelectorBaseLR(bool initial, double base_lr, double selected_eta) {
+  return initial ? selected_eta : std::min(base_lr, selected_eta);
+}
+// a trial's energy and error must be finite (:391-418)
+inline void CheckStepCandidate(double energy, double error) {
+  const bool bad_e = !std::isfinite(energy), bad_err = !std::isfinite(error);
+  if (bad_e && bad_err) throw std::runtime_error("Step selector candidate evaluation produced non-finite energy and energy error");
+  if (bad_e) throw std::runtime_error("Step selector candidate evaluation produced non-finite energy");
+  if (bad_err) throw std::runtime_error("Step selector candidate evaluation produced non-finite energy error");
+}
+
 // (MinSRParams, then LBFGSParams, were appended: the others keep their indices)
 using AlgorithmParams = std::variant<SGDParams, AdamParams, StochasticReconfigurationParams, AdaGradParams, MinSRParams, LBFGSParams>;
 
@@ -4237,6 +4486,8 @@ struct OptimizerParams {                       // optimizer_params.h:348-473
     std::unique_ptr<LearningRateScheduler> lr_scheduler;
     std::optional<double> clip_value;          // per-element magnitude clip, first-order rules only; unset / <= 0: off
     std::optional<double> clip_norm;           // global L2 norm clip, first-order rules only; unset / <= 0: off
+    InitialStepSelectorParams initial_step_selector;     // off by default
+    PeriodicStepSelectorParams periodic_step_selector;   // off by default
     BaseParams(size_t max_iter, double energy_tol, double grad_tol, size_t patience, double learning_rate,
                std::unique_ptr<LearningRateScheduler> scheduler = nullptr)
         : max_iterations(max_iter), energy_tolerance(energy_tol), gradient_tolerance(grad_tol), plateau_patience(patience),
@@ -4244,7 +4495,8 @@ struct OptimizerParams {                       // optimizer_params.h:348-473
     BaseParams(const BaseParams &o)
         : max_iterations(o.max_iterations), energy_tolerance(o.energy_tolerance), gradient_tolerance(o.gradient_tolerance),
           plateau_patience(o.plateau_patience), learning_rate(o.learning_rate),
-          lr_scheduler(o.lr_scheduler ? o.lr_scheduler->Clone() : nullptr), clip_value(o.clip_value), clip_norm(o.clip_norm) {}
+          lr_scheduler(o.lr_scheduler ? o.lr_scheduler->Clone() : nullptr), clip_value(o.clip_value), clip_norm(o.clip_norm),
+          initial_step_selector(o.initial_step_selector), periodic_step_selector(o.periodic_step_selector) {}
     BaseParams &operator=(const BaseParams &o) {
       if (this != &o) { BaseParams t(o); *this = std::move(t); }
       return *this;
@@ -4254,7 +4506,36 @@ struct OptimizerParams {                       // optimizer_params.h:348-473
   };
   BaseParams base_params;
   AlgorithmParams algorithm_params;
-  OptimizerParams(const BaseParams &base, const AlgorithmParams &algo) : base_params(base), algorithm_params(algo) {}
+  CheckpointParams checkpoint_params;          // off by default
+  SpikeRecoveryParams spike_recovery_params;
+  // Deviation from the reference: this constructor switches enable_auto_recover OFF (there S1-S3 stay on).  Runs written against this
+  // tree before spike recovery existed must not change, and an SR solve that ends in <= 1 CG iteration is an S3 signal.  The
+  // four-argument constructor takes the SpikeRecoveryParams as given; a default-constructed one has the reference's defaults.
+  OptimizerParams(const BaseParams &base, const AlgorithmParams &algo) : base_params(base), algorithm_params(algo) {
+    spike_recovery_params.enable_auto_recover = false;
+  }
+  OptimizerParams(const BaseParams &base, const AlgorithmParams &algo, const CheckpointParams &ckpt, const SpikeRecoveryParams &spike)
+      : base_params(base), algorithm_params(algo), checkpoint_params(ckpt), spike_recovery_params(spike) {}
+  // Every refusal that needs no device (optimizer_impl.h:149-175, and L-BFGS with rollback: the ring snapshot is not built)
+  void ValidateGuards() const {
+    const bool initial = base_params.initial_step_selector.enabled, periodic = base_params.periodic_step_selector.enabled;
+    if (initial || periodic) {
+      if (!(IsAlgorithm<SGDParams>() || IsAlgorithm<StochasticReconfigurationParams>() || IsAlgorithm<MinSRParams>()))
+        throw std::invalid_argument("Step selectors only support SGD, SR, and MinSR in IterativeOptimize");
+      if (base_params.lr_scheduler) throw std::invalid_argument("Step selectors cannot be used together with lr_scheduler in v1");
+    }
+    if (initial && base_params.initial_step_selector.max_line_search_steps == 0)
+      throw std::invalid_argument("Initial step selector max_line_search_steps must be > 0");
+    if (periodic) {
+      if (base_params.periodic_step_selector.every_n_steps == 0) throw std::invalid_argument("Auto step selector every_n_steps must be > 0");
+      const double ratio = base_params.periodic_step_selector.phase_switch_ratio;
+      if (!(ratio >= 0.0 && ratio <= 1.0)) throw std::invalid_argument("Auto step selector phase_switch_ratio must be within [0, 1]");
+    }
+    if ((initial || periodic) && base_params.learning_rate <= 0.0)
+      throw std::invalid_argument("Step selectors require a positive base learning_rate");
+    if (IsAlgorithm<LBFGSParams>() && spike_recovery_params.enable_rollback)
+      throw std::invalid_argument("Spike rollback is not available with L-BFGS: the snapshot of the history ring is not built");
+  }
   template <typename T> const T &GetAlgorithmParams() const { return std::get<T>(algorithm_params); }
   template <typename T> bool IsAlgorithm() const { return std::holds_alternative<T>(algorithm_params); }
   bool IsFirstOrder() const { return IsAlgorithm<SGDParams>() || IsAlgorithm<AdaGradParams>() || IsAlgorithm<AdamParams>(); }
@@ -4268,6 +4549,9 @@ struct DeviceEvaluationT {
   double energy_error = 0.0;
   std::vector<TenElemT> energy_samples;     // the local energy of every sample in the SR store, in its order (MinSR); empty: no sample set
   std::vector<double> accept_rates_avg;     // Monte-Carlo evaluators: mean acceptance rate of every walker over the evaluation's sweeps
+  // what the evaluator's own anomaly checks found (AcceptanceRateCheck_, DetectEnergyErrorAnomaly_); empty: nothing
+  std::vector<size_t> low_acceptance_walkers;      // walkers whose rate is below half the maximum over the walkers
+  std::vector<size_t> nonfinite_sample_indices;    // the first (at most 5) samples of energy_samples that are not finite
 };
 
 template <typename TenElemT>
@@ -4278,6 +4562,11 @@ class Optimizer {
   using Evaluator = std::function<DeviceEvaluationT<TenElemT>(ContractorT &)>;
   struct OptimizationCallback {
     std::function<void(size_t, double, double, double)> on_iteration;   // (iteration, energy, gradient norm, learning rate)
+    // every evaluation that enters the trajectory, the closing one included, before the state moves: (the evaluation, its energy,
+    // iteration).  Evaluations that spike recovery rejected and selector trials never get here.
+    std::function<void(const DeviceEvaluationT<TenElemT> &, const TenElemT &, size_t)> on_evaluation_accepted;
+    // after the step of an iteration: (iteration, energy, energy error) -> true ends the run without a closing evaluation (:888)
+    std::function<bool(size_t, double, double)> should_stop;
   };
   struct OptimizationResult {
     std::vector<TenElemT> energy_trajectory;    // one entry per evaluation: max_iterations + 1 unless a criterion stopped the run
@@ -4292,6 +4581,12 @@ class Optimizer {
     // energy_trajectory) and the step length of every iteration
     size_t lbfgs_skip_curvature_count = 0, lbfgs_damping_count = 0, lbfgs_descent_reset_count = 0, lbfgs_line_search_evaluations = 0;
     std::vector<double> learning_rate_trajectory;
+    // spike recovery and step selectors.  The trajectories above hold accepted evaluations only.
+    SpikeStatistics spike_stats;
+    std::vector<double> energy_error_trajectory;    // one entry per entry of energy_trajectory
+    std::vector<uint8_t> selector_triggered;        // per iteration: a step selector ran
+    std::vector<double> selected_eta;               // per iteration: the learning rate it chose (0 where none ran)
+    size_t evaluator_calls = 0, energy_only_calls = 0;   // calls of the evaluator (rejected ones, full-evaluator trials) / of the energy-only one
   };
 
   // adopts the state the contractor holds (UploadState first).  Fermionic states: the contractor holds the 4 d decorated components
@@ -4343,6 +4638,27 @@ class Optimizer {
     c_.OptStep(0, learning_rate, {0.0, 0.0, 0.0});
     return info;
   }
+  // The two updates above in two halves, for spike recovery and the step selectors: the direction is left in the gradient buffer
+  // (what S3 judges and the selector trials move along), and is applied later -- or never, when the evaluation is rejected.
+  typename ContractorT::NaturalGradientInfo StochasticReconfigurationDirection(const StochasticReconfigurationParams &p) {
+    const auto &cg = p.cg_params;
+    return c_.OptNaturalGradient(p.diag_shift, cg.max_iter, cg.relative_tolerance, cg.absolute_tolerance, cg.residual_recompute_interval,
+                                 cg.orthogonality_threshold);
+  }
+  typename ContractorT::MinSRInfo MinSRDirection(const MinSRParams &p, const std::vector<TenElemT> &energy_samples, const TenElemT &energy) {
+    if (energy_samples.size() != c_.SRCount() || energy_samples.empty())
+      throw std::invalid_argument("Optimizer::MinSRUpdate: " + std::to_string(energy_samples.size()) + " local energies for " +
+                                  std::to_string(c_.SRCount()) + " stored samples (MinSR needs an evaluator that keeps its sample set)");
+    return c_.MinSRDirection(energy_samples, energy, p.r_pinv, p.a_pinv, p.soft_cutoff);
+  }
+  // lr / |x| under normalize_update (SR only), once
+  double AppliedDirectionStep(double learning_rate, double direction_norm) const {
+    if (params_.template IsAlgorithm<StochasticReconfigurationParams>() &&
+        params_.template GetAlgorithmParams<StochasticReconfigurationParams>().normalize_update && direction_norm > 0.0)
+      return learning_rate / direction_norm;
+    return learning_rate;
+  }
+  void ApplyDirection(double applied_step) { c_.OptStep(0, applied_step, {0.0, 0.0, 0.0}); }
   void ClipGradient() {                          // optimizer_impl.h:307-318
     if (!params_.IsFirstOrder()) return;
     const double cv = params_.base_params.clip_value.value_or(0.0), cn = params_.base_params.clip_norm.value_or(0.0);
@@ -4438,24 +4754,41 @@ class Optimizer {
       const auto k = c_.LBFGSGetCounters();
       res.lbfgs_skip_curvature_count = k.skip_curvature; res.lbfgs_damping_count = k.damping; res.lbfgs_descent_reset_count = k.descent_reset;
     };
+    // Spike recovery (deviation from the reference, which judges after its history update and restores the ring): S1 / S2 are judged
+    // before LBFGSUpdate, so a rejected evaluation never reaches the ring and evaluating again needs no restore.  The trials of the
+    // line search bypass detection, as in the reference.  Rollback is refused (OptimizerParams::ValidateGuards).
+    SpikeGuard guard(params_.spike_recovery_params);
+    DeviceEvaluationT<TenElemT> ev;
     auto evaluate = [&]() {
-      const DeviceEvaluationT<TenElemT> ev = evaluator(c_);
+      ev = evaluator(c_);
+      ++res.evaluator_calls;
       return c_.OptGradientFromAccumulators(ev.e_loc_sum, ev.weight_sum);
     };
-    auto record = [&](const std::pair<TenElemT, double> &eg) {
+    auto record = [&](const std::pair<TenElemT, double> &eg, size_t iter) {
       res.energy_trajectory.push_back(eg.first);
       res.gradient_norms.push_back(eg.second);
+      res.energy_error_trajectory.push_back(ev.energy_error);
       res.final_energy = eg.first;
+      if (callback.on_evaluation_accepted) callback.on_evaluation_accepted(ev, eg.first, iter);
+    };
+    auto finish = [&]() {
+      counters();
+      res.spike_stats = guard.Statistics();
+      guard.WriteTriggerCsvFile();
     };
     for (size_t iter = 0; iter < params_.base_params.max_iterations; ++iter) {
-      const auto eg = evaluate();
-      record(eg);
+      auto eg = evaluate();
+      for (size_t attempts = 0; guard.JudgeEvaluation(iter, attempts, ev.energy_error, eg.second) == SpikeAction::kResample; ++attempts)
+        eg = evaluate();
+      guard.Accept(std::real(eg.first), ev.energy_error, eg.second, nullptr);
+      record(eg, iter);
       const double e = std::real(eg.first);
       if (e < res.min_energy) { res.min_energy = e; without_improvement = 0; } else ++without_improvement;
       const double lr = GetCurrentLearningRate(iter, iter == 0 ? e : previous_energy);
       if (callback.on_iteration) callback.on_iteration(iter, e, eg.second, lr);
       c_.LBFGSUpdate(p.min_curvature, p.use_damping);
-      if (iter > 0 && ShouldStop(e, previous_energy, eg.second, without_improvement)) { res.converged = true; counters(); return res; }
+      if (iter > 0 && ShouldStop(e, previous_energy, eg.second, without_improvement)) { res.converged = true; finish(); return res; }
+      const double accepted_error = ev.energy_error;      // (the line search evaluates through `ev`)
       const auto dir = c_.LBFGSDirection(p.min_curvature, p.max_direction_norm);
       double used_step = 0.0;
       if (p.step_mode == LBFGSStepMode::kFixed) {
@@ -4488,44 +4821,213 @@ class Optimizer {
       if (params_.base_params.lr_scheduler) params_.base_params.lr_scheduler->Step();
       previous_energy = e;
       res.total_iterations = iter + 1;
+      if (callback.should_stop && callback.should_stop(iter, e, accepted_error)) { finish(); return res; }
+      SaveCheckpoint_(iter, res.energy_trajectory, res.energy_error_trajectory);
     }
     const auto eg = evaluate();
-    record(eg);
+    record(eg, params_.base_params.max_iterations);
     res.min_energy = std::min(res.min_energy, std::real(eg.first));
-    counters();
+    finish();
     return res;
   }
-  // evaluate -> finish -> clip -> [natural gradient] -> step, max_iterations times, then one closing evaluation
-  OptimizationResult IterativeOptimize(const Evaluator &evaluator, const OptimizationCallback &callback = OptimizationCallback()) {
+  // evaluate -> finish -> clip -> [natural gradient] -> step, max_iterations times, then one closing evaluation.  Around that, all
+  // off by default: spike recovery (S1-S4 with resampling and rollback), the step selectors and checkpoints, in the order of
+  // optimizer_impl.h:233-900.  With the three off the device calls are exactly the line above.
+  //   1. evaluate, finish (energy, |g|)                    2. S1 / S2: evaluate again, or restore the base and evaluate again
+  //   3. learning rate                                     4. SR / MinSR: the direction only
+  //   5. S3 on |x| and the CG iterations                   6. S4: always a rollback
+  //   7. clip; step selector: trials theta_base - eta d, each restored
+  //   8. accept: trackers, trajectories, lowest energy, stopping, callbacks, base <- theta, THEN the rule kernel / the direction
+  //      applied, checkpoint
+  // Deviations from the reference, each on purpose:
+  //   - The rule kernel runs after the S4 decision (the reference computes updated_state before S3 / S4 and so advances the Adam /
+  //     AdaGrad / momentum state for a step it then throws away; it lists that as a known limitation).  Here no rejected evaluation
+  //     touches rule state, and an S3 resample cannot update it twice.
+  //   - A selector trial never moves theta for good: OptPreview forms the trial from the saved base on the device and OptBaseRestore
+  //     puts the base back bit for bit; the real step then starts from it.  A trial with the full evaluator overwrites the
+  //     accumulators but not the gradient buffer, so the direction (precomputed_natural_direction) is still there to apply.
+  //   - S3 and S4 are judged before the selector's trials, not after them.  Neither verdict reads anything the trials produce, so the
+  //     accepted trajectory is the same; a rejected evaluation costs no trials and does not move the selector's base learning rate,
+  //     and the one base buffer in HBM is free for the trials exactly when no rollback can follow in the same pass.
+  //   - The closing evaluation after the last step bypasses detection and the trackers; it is recorded as before.
+  // `energy_only_evaluator` (optional) serves the selector trials; it leaves only e_loc_sum, weight_sum and energy_error.
+  OptimizationResult IterativeOptimize(const Evaluator &evaluator, const OptimizationCallback &callback = OptimizationCallback(),
+                                       const Evaluator &energy_only_evaluator = Evaluator()) {
+    params_.ValidateGuards();                      // before any device call
     if (params_.template IsAlgorithm<LBFGSParams>()) return IterativeOptimizeLBFGS_(evaluator, callback);
+    const auto &b = params_.base_params;
+    const auto &spike = params_.spike_recovery_params;
+    const bool is_sgd = params_.template IsAlgorithm<SGDParams>(), is_sr = params_.template IsAlgorithm<StochasticReconfigurationParams>(),
+               is_minsr = params_.template IsAlgorithm<MinSRParams>();
+    const bool any_selector = b.initial_step_selector.enabled || b.periodic_step_selector.enabled;
+    double selector_base_lr = b.learning_rate;
+    SpikeGuard guard(spike);
     OptimizationResult res;
     double previous_energy = 0.0;
     size_t without_improvement = 0;
     DeviceEvaluationT<TenElemT> ev;
     auto evaluate = [&]() {
       ev = evaluator(c_);
-      auto eg = c_.OptGradientFromAccumulators(ev.e_loc_sum, ev.weight_sum);
+      ++res.evaluator_calls;
+      return c_.OptGradientFromAccumulators(ev.e_loc_sum, ev.weight_sum);
+    };
+    auto record = [&](const std::pair<TenElemT, double> &eg, size_t iter) {
       res.energy_trajectory.push_back(eg.first);
       res.gradient_norms.push_back(eg.second);
+      res.energy_error_trajectory.push_back(ev.energy_error);
       res.final_energy = eg.first;
-      return eg;
+      if (callback.on_evaluation_accepted) callback.on_evaluation_accepted(ev, eg.first, iter);
     };
-    for (size_t iter = 0; iter < params_.base_params.max_iterations; ++iter) {
-      const auto eg = evaluate();
-      const double e = std::real(eg.first);
-      if (e < res.min_energy) { res.min_energy = e; without_improvement = 0; } else ++without_improvement;
-      const double lr = GetCurrentLearningRate(iter, iter == 0 ? e : previous_energy);
-      if (callback.on_iteration) callback.on_iteration(iter, e, eg.second, lr);
-      if (iter > 0 && ShouldStop(e, previous_energy, eg.second, without_improvement)) { res.converged = true; return res; }
-      ClipGradient();
-      Update(lr, res, ev, eg.first);
-      if (params_.base_params.lr_scheduler) params_.base_params.lr_scheduler->Step();
-      previous_energy = e;
-      res.total_iterations = iter + 1;
+    auto finish = [&]() {
+      res.spike_stats = guard.Statistics();
+      guard.WriteTriggerCsvFile();
+    };
+    // one trial of a selector: the energy (and error) of the state the device holds
+    auto trial_energy = [&]() {
+      DeviceEvaluationT<TenElemT> t;
+      if (energy_only_evaluator) { t = energy_only_evaluator(c_); ++res.energy_only_calls; }
+      else { t = evaluator(c_); ++res.evaluator_calls; }       // (its gradient stays in the accumulators, unfinished)
+      return std::make_pair(std::real(t.e_loc_sum / t.weight_sum), t.energy_error);
+    };
+    for (size_t iter = 0; iter < b.max_iterations; ++iter) {
+      size_t attempts = 0;
+      for (;;) {
+        const auto eg = evaluate();
+        const double e = std::real(eg.first);
+        // rollback: theta <- the last accepted state, which is then evaluated again; with no base saved just evaluate again
+        auto rollback = [&]() {
+          if (guard.TakeBase()) { c_.OptBaseRestore(); c_.OptBaseClear(); }
+          attempts = 0;
+        };
+        SpikeAction action = guard.JudgeEvaluation(iter, attempts, ev.energy_error, eg.second);
+        if (action == SpikeAction::kResample) { ++attempts; continue; }
+        if (action == SpikeAction::kRollback) { rollback(); continue; }
+        double lr = any_selector ? selector_base_lr : GetCurrentLearningRate(iter, iter == 0 ? e : previous_energy);
+        bool clipped = false, have_direction = false;
+        auto clip_once = [&]() { if (!clipped) { ClipGradient(); clipped = true; } };
+        typename ContractorT::NaturalGradientInfo sr_info;
+        double direction_norm = 0.0;
+        auto direction_once = [&]() {
+          if (have_direction) return;
+          if (is_sr) {
+            sr_info = StochasticReconfigurationDirection(params_.template GetAlgorithmParams<StochasticReconfigurationParams>());
+            direction_norm = sr_info.direction_norm;
+          } else {
+            last_minsr_ = MinSRDirection(params_.template GetAlgorithmParams<MinSRParams>(), ev.energy_samples, eg.first);
+            direction_norm = last_minsr_.direction_norm;
+          }
+          have_direction = true;
+        };
+        if ((is_sr || is_minsr) && spike.enable_auto_recover) {
+          direction_once();
+          action = guard.JudgeDirection(iter, attempts, direction_norm, is_minsr ? std::numeric_limits<size_t>::max() : (size_t)sr_info.iterations);
+          if (action == SpikeAction::kResample) { ++attempts; continue; }
+          if (action == SpikeAction::kRollback) { rollback(); continue; }
+        }
+        if (guard.JudgeEnergy(iter, attempts, e) == SpikeAction::kRollback) { rollback(); continue; }
+        const bool initial_triggered = b.initial_step_selector.enabled && iter == 0;
+        const bool periodic_triggered = b.periodic_step_selector.enabled && iter > 0 && iter % b.periodic_step_selector.every_n_steps == 0;
+        const bool selector_triggered = initial_triggered || periodic_triggered;
+        if (selector_triggered) {
+          const bool need_error = initial_triggered ? !b.initial_step_selector.enable_in_deterministic
+                                                    : !b.periodic_step_selector.enable_in_deterministic;
+          if (need_error && ev.energy_error <= 0.0)
+            throw std::invalid_argument(std::string(initial_triggered ? "Initial" : "Auto") +
+                                        " step selector requires positive energy error in MC mode. "
+                                        "Set enable_in_deterministic=true to allow deterministic evaluators.");
+          const std::vector<double> etas = StepCandidates(initial_triggered, selector_base_lr, b.initial_step_selector.max_line_search_steps);
+          std::vector<double> sgd;
+          if (is_sgd) {
+            const auto &p = params_.template GetAlgorithmParams<SGDParams>();
+            sgd = {p.momentum, p.nesterov ? 1.0 : 0.0, p.weight_decay};
+            clip_once();
+          } else {
+            sgd = {0.0, 0.0, 0.0};
+            direction_once();
+          }
+          c_.OptBaseSave();
+          std::vector<StepCandidateResult> results;
+          try {
+            for (const double eta : etas) {
+              c_.OptPreview(is_sgd ? eta : AppliedDirectionStep(eta, direction_norm), sgd);
+              const auto t = trial_energy();
+              CheckStepCandidate(t.first, t.second);
+              results.push_back({eta, t.first, t.second});
+            }
+          } catch (...) {
+            c_.OptBaseRestore();
+            if (!guard.HasBase()) c_.OptBaseClear();
+            throw;
+          }
+          c_.OptBaseRestore();
+          if (!guard.HasBase()) c_.OptBaseClear();      // (the trials' base is no rollback target)
+          const double selected = initial_triggered ? SelectInitialStep(results)
+                                                    : SelectPeriodicStep(results, iter, b.max_iterations, b.periodic_step_selector.phase_switch_ratio);
+          if (initial_triggered && selected != selector_base_lr)
+            std::cout << "[INITIAL_STEP] Iter 0: selected step size " << selector_base_lr << " -> " << selected << std::endl;
+          if (periodic_triggered && selected < selector_base_lr)
+            std::cout << "[PERIODIC_STEP] Iter " << iter << ": step size halved " << selector_base_lr << " -> " << selected << std::endl;
+          selector_base_lr = NextSelectorBaseLR(initial_triggered, selector_base_lr, selected);
+          lr = selector_base_lr;
+        }
+        // ---- accepted ----
+        guard.Accept(e, ev.energy_error, eg.second, have_direction ? &direction_norm : nullptr);
+        record(eg, iter);
+        if (e < res.min_energy) { res.min_energy = e; without_improvement = 0; } else ++without_improvement;
+        if (callback.on_iteration) callback.on_iteration(iter, e, eg.second, lr);
+        if (iter > 0 && ShouldStop(e, previous_energy, eg.second, without_improvement)) { res.converged = true; finish(); return res; }
+        if (spike.enable_rollback) { c_.OptBaseSave(); guard.MarkBaseSaved(); }
+        clip_once();
+        if (have_direction) {
+          ApplyDirection(AppliedDirectionStep(lr, direction_norm));
+          res.sr_natural_grad_norm = direction_norm;
+          if (is_sr) { res.sr_iterations = (size_t)sr_info.iterations; res.sr_residual_norm = sr_info.residual_norm; }
+        } else {
+          Update(lr, res, ev, eg.first);
+        }
+        res.selector_triggered.push_back(selector_triggered ? 1 : 0);
+        res.selected_eta.push_back(selector_triggered ? lr : 0.0);
+        if (b.lr_scheduler) params_.base_params.lr_scheduler->Step();
+        previous_energy = e;
+        res.total_iterations = iter + 1;
+        if (callback.should_stop && callback.should_stop(iter, e, ev.energy_error)) { finish(); return res; }
+        SaveCheckpoint_(iter, res.energy_trajectory, res.energy_error_trajectory);
+        break;
+      }
     }
     const auto eg = evaluate();
+    record(eg, b.max_iterations);
     res.min_energy = std::min(res.min_energy, std::real(eg.first));
+    finish();
     return res;
+  }
+  // SaveCheckpoint_ / WriteTrajectoryCsv_ (optimizer_impl.h:1980-2049): base_path/step_{k}/ holds the state after step k (read from
+  // theta; fermionic states: the stored tensors), checkpoint_meta.txt and trajectory_snapshot.csv; base_path/energy_trajectory.csv is
+  // rewritten every time.  The extents are the contractor's.
+  void SaveCheckpoint_(size_t step, const std::vector<TenElemT> &energy_traj, const std::vector<double> &error_traj) const {
+    const auto &cfg = params_.checkpoint_params;
+    if (!cfg.IsEnabled() || step == 0 || step % cfg.every_n_steps != 0) return;
+    const std::string dir = cfg.base_path + "/step_" + std::to_string(step);
+    EnsureDirectoryExists(dir);
+    GetState(c_.rows(), c_.cols(), fermion_ ? c_.phys_dim() / 4 : c_.phys_dim(), c_.bond_dim()).Dump(dir);
+    {
+      std::ofstream meta(dir + "/checkpoint_meta.txt");
+      if (!meta) throw std::ios_base::failure("Optimizer: failed to open " + dir + "/checkpoint_meta.txt");
+      meta << "step " << step << "\n";
+      if (!energy_traj.empty()) meta << "energy " << std::setprecision(17) << std::real(energy_traj.back()) << "\n";
+      if (!error_traj.empty()) meta << "error " << std::setprecision(17) << error_traj.back() << "\n";
+    }
+    WriteTrajectoryCsv_(dir + "/trajectory_snapshot.csv", energy_traj, error_traj);
+    WriteTrajectoryCsv_(cfg.base_path + "/energy_trajectory.csv", energy_traj, error_traj);
+    std::cout << "[CHECKPOINT] Saved step " << step << " to " << dir << std::endl;
+  }
+  static void WriteTrajectoryCsv_(const std::string &path, const std::vector<TenElemT> &energy_traj, const std::vector<double> &error_traj) {
+    std::ofstream csv(path);
+    if (!csv) throw std::runtime_error("Failed to write trajectory CSV file '" + path + "'");
+    csv << "iteration,energy,energy_error\n";
+    for (size_t i = 0; i < energy_traj.size(); ++i)
+      csv << i << "," << std::setprecision(17) << std::real(energy_traj[i]) << "," << (i < error_traj.size() ? error_traj[i] : 0.0) << "\n";
+    if (!csv) throw std::runtime_error("Failed to write trajectory CSV file '" + path + "'");
   }
   // phys_dim: the components of the caller's state -- for a fermionic state the d stored ones (variant 0 of the device's 4 d)
   SplitIndexTPST<TenElemT> GetState(size_t rows, size_t cols, size_t phys_dim, size_t D) const {
@@ -4650,13 +5152,41 @@ inline std::pair<TenElemT, double> MeanAndBinnedErrorSqrtNUniformBin(const std::
   return {mean, err};
 }
 
+// AcceptanceRateCheck_ (mc_energy_grad_evaluator.h:401-420) with a walker in the role of an MPI rank: the walkers whose mean
+// acceptance rate is below half the maximum over the walkers
+inline std::vector<size_t> AcceptanceRateCheck(const std::vector<double> &rates) {
+  std::vector<size_t> flagged;
+  if (rates.empty()) return flagged;
+  const double mx = *std::max_element(rates.begin(), rates.end());
+  for (size_t w = 0; w < rates.size(); ++w)
+    if (rates[w] < 0.5 * mx) flagged.push_back(w);
+  return flagged;
+}
+// DetectEnergyErrorAnomaly_ (:437-470): an infinite error although the binning had more than one bin to work with; returns the
+// indices of the first (at most 5) non-finite samples
+template <typename TenElemT>
+inline std::vector<size_t> DetectEnergyErrorAnomaly(double energy_error, size_t samples_per_walker, size_t n_walkers,
+                                                    const std::vector<TenElemT> &energy_samples, bool *anomalous = nullptr) {
+  std::vector<size_t> bad;
+  if (anomalous) *anomalous = false;
+  if (!std::isinf(energy_error)) return bad;
+  const size_t bin_size = std::max<size_t>(1, static_cast<size_t>(std::sqrt((double)samples_per_walker)));
+  if (n_walkers * (samples_per_walker / bin_size) <= 1) return bad;
+  if (anomalous) *anomalous = true;
+  for (size_t i = 0; i < energy_samples.size() && bad.size() < 5; ++i)
+    if (!std::isfinite(std::real(energy_samples[i])) || !std::isfinite(std::imag(energy_samples[i]))) bad.push_back(i);
+  return bad;
+}
+
 // MCEnergyGradEvaluator (algorithm/vmc_update/mc_energy_grad_evaluator.h:152-330) for the state the device holds.  It owns nothing
 // but references: the engine (resident mode), the model, the decoration of a fermionic state and the Monte-Carlo parameters.
 // Evaluate(contractor) is an Optimizer::Evaluator: S_O / S_EO stay in the contractor's accumulators, the O* samples in its SR store
 // (collect_sr_buffers: SR, MinSR), the energies come back.  The chains persist from one Evaluate to the next: configurations and the
 // updater's engines are never re-seeded; only the environments are rebuilt on the stepped state (RefreshWavefunctionComponent, :164).
-// One rank; a walker plays the role of an MPI rank in the statistics.  Not built (they belong with spike handling): the
-// acceptance-rate anomaly check (:289), the energy-error anomaly check (:319) and the psi-consistency warning policy (:219-244).
+// One rank; a walker plays the role of an MPI rank in the statistics and in the acceptance-rate anomaly check (:289, :382), whose
+// findings and those of the energy-error anomaly check (:319) come back in the evaluation and go to std::cerr, at most
+// kMaxAnomalyReports times per evaluator.  EvaluateEnergyOnly (:343-392) serves the step selectors' trials: sweeps and local energies
+// only, no accumulators, no sample store.  Not built: the psi-consistency warning policy (:219-244).
 template <class MonteCarloSweepUpdater, class Model, typename TenElemT = double>
 class MCEnergyGradEvaluator {
  public:
@@ -4696,6 +5226,38 @@ class MCEnergyGradEvaluator {
     // E = e_loc_sum / weight_sum, so hand it E_binned * W instead of the plain sum of the local energies.
     ev.e_loc_sum = stat.first * ev.weight_sum;
     ev.energy_error = stat.second;
+    ReportLowAcceptance_(ev);                                                                  // :289
+    bool anomalous = false;                                                                    // :319
+    ev.nonfinite_sample_indices = DetectEnergyErrorAnomaly(ev.energy_error, S, n, ev.energy_samples, &anomalous);
+    if (anomalous && reports_++ < kMaxAnomalyReports) {
+      std::cerr << "Energy error is infinite with " << n << " walkers x " << S << " samples: NaNs or identical samples.";
+      for (const size_t i : ev.nonfinite_sample_indices) std::cerr << " non-finite energy_samples[" << i << "] = " << ev.energy_samples[i] << ";";
+      std::cerr << std::endl;
+    }
+    return ev;
+  }
+  // the energy and its error of the state the device holds, for a step-selector trial: the chains go on from where they are
+  DeviceEvaluationT<TenElemT> EvaluateEnergyOnly(ContractorT &contractor) {
+    auto &comp = engine_.WavefuncComp();
+    if (&contractor != &comp.contractor) throw std::invalid_argument("MCEnergyGradEvaluator: not the contractor of the engine's walkers");
+    const size_t n = comp.config.walkers(), S = params_.samples_per_walker;
+    engine_.RefreshWavefunctionComponent();
+    DeviceEvaluationT<TenElemT> ev;
+    std::vector<TenElemT> samples;
+    samples.reserve(n * S);
+    ev.accept_rates_avg.assign(n, 0.0);
+    for (size_t k = 0; k < S; ++k) {
+      const std::vector<double> rates = engine_.StepSweep();
+      for (size_t w = 0; w < n && w < rates.size(); ++w) ev.accept_rates_avg[w] += rates[w];
+      EnergyAndHolesT<TenElemT> eh = model_.template CalEnergyAndHoles<false>(engine_.State(), comp);
+      samples.insert(samples.end(), eh.energy.begin(), eh.energy.end());
+    }
+    for (auto &r : ev.accept_rates_avg) r /= double(S);
+    const auto stat = MeanAndBinnedErrorSqrtNUniformBin(samples, n);
+    ev.weight_sum = double(n * S);
+    ev.e_loc_sum = stat.first * ev.weight_sum;
+    ev.energy_error = stat.second;
+    ReportLowAcceptance_(ev);                                                                  // :382
     return ev;
   }
   DeviceEvaluationT<TenElemT> operator()(ContractorT &contractor) { return Evaluate(contractor); }
@@ -4707,6 +5269,16 @@ class MCEnergyGradEvaluator {
   const FermionDecoration *fermion_;
   const MonteCarloParams &params_;
   bool collect_sr_buffers_;
+  static constexpr size_t kMaxAnomalyReports = 20;
+  size_t reports_ = 0;
+  void ReportLowAcceptance_(DeviceEvaluationT<TenElemT> &ev) {
+    ev.low_acceptance_walkers = AcceptanceRateCheck(ev.accept_rates_avg);
+    if (ev.low_acceptance_walkers.empty() || reports_++ >= kMaxAnomalyReports) return;
+    const double mx = *std::max_element(ev.accept_rates_avg.begin(), ev.accept_rates_avg.end());
+    for (const size_t w : ev.low_acceptance_walkers)
+      std::cerr << "Walker " << w << ": Acceptance rate = " << ev.accept_rates_avg[w] << " is too small compared to the maximum over walkers "
+                << mx << std::endl;
+  }
 };
 
 // a model / updater pair that does not belong together: the U(1)xU(1) sector updater moves Hubbard states only; the transverse-field
@@ -4744,6 +5316,7 @@ struct VMCPEPSOptimizerParams {
         optimizer_params.GetAlgorithmParams<LBFGSParams>().step_mode == LBFGSStepMode::kStrongWolfe)
       throw std::invalid_argument("VMCPEPSOptimizerParams: the strong-Wolfe line search on Monte-Carlo energies is not built (its trial "
                                   "evaluations are no iterations of the trajectory); use the fixed L-BFGS step");
+    optimizer_params.ValidateGuards();             // the selector combinations and L-BFGS with rollback
   }
 };
 
@@ -4753,7 +5326,10 @@ struct VMCPEPSOptimizerParams {
 // (TPSWaveFunctionComponentT::ResidentState), as for every class of this layer; the executor owns the Optimizer (pepsgpu_opt_begin
 // adopts the uploaded state), the engine in resident mode and the evaluator.  tps_lowest_ / en_min_ (:118-121): whenever an
 // evaluation's energy is below the minimum so far theta is copied device to device (pepsgpu_vmc_snapshot_save); the closing
-// evaluation counts.  Not built: step selectors, spike recovery, checkpoints, the JSONL log, more than one rank.
+// evaluation counts.  Spike recovery, the step selectors and checkpoints are the Optimizer's (OptimizerParams); the executor hands it
+// the evaluator's energy-only variant for the selector trials and keeps its own trajectories and the lowest-state snapshot in
+// on_evaluation_accepted, so an evaluation that spike recovery rejected is neither recorded nor ever "the lowest".  Not built: the
+// JSONL log, more than one rank.
 template <class MonteCarloSweepUpdater, class Model, typename TenElemT = double>
 class VMCPEPSOptimizer {
  public:
@@ -4775,6 +5351,9 @@ class VMCPEPSOptimizer {
 
   void SetOptimizationCallback(const typename OptimizerT::OptimizationCallback &cb) { user_callback_ = cb; }
   void SetEnergyEvaluator(const Evaluator &ev) { custom_evaluator_ = ev; }
+  // the evaluator of the step selectors' trials; with a custom evaluator and none given here the trials use the custom evaluator
+  void SetEnergyOnlyEvaluator(const Evaluator &ev) { custom_energy_only_ = ev; }
+  MCEnergyGradEvaluator<MonteCarloSweepUpdater, Model, TenElemT> &GetEvaluator() { return evaluator_; }
 
   // WarmUp + IterativeOptimize; theta is the state after the last step (not yet normalised)
   typename OptimizerT::OptimizationResult WarmUpAndOptimize() {
@@ -4788,19 +5367,33 @@ class VMCPEPSOptimizer {
       const auto t0 = std::chrono::steady_clock::now();
       DeviceEvaluationT<TenElemT> ev = custom_evaluator_ ? custom_evaluator_(c) : evaluator_.Evaluate(c);
       timings_.evaluation_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();   // (ends in host read-backs)
+      return ev;
+    };
+    Evaluator energy_only;
+    if (custom_energy_only_ || !custom_evaluator_) energy_only = [this](ContractorT &c) {
+      const auto t0 = std::chrono::steady_clock::now();
+      DeviceEvaluationT<TenElemT> ev = custom_energy_only_ ? custom_energy_only_(c) : evaluator_.EvaluateEnergyOnly(c);
+      timings_.evaluation_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      return ev;
+    };
+    // theta is still the evaluated state when an evaluation is accepted: the step comes after
+    typename OptimizerT::OptimizationCallback cb = user_callback_;
+    cb.on_evaluation_accepted = [this](const DeviceEvaluationT<TenElemT> &ev, const TenElemT &accepted_energy, size_t iter) {
+      // the quotient of the sums, as before: the finished energy is the same real part and, for complex states, the same pair
       const TenElemT energy = ev.e_loc_sum / ev.weight_sum;
+      (void)accepted_energy;
       energy_trajectory_.push_back(energy);
       energy_error_traj_.push_back(ev.energy_error);
       accept_rates_traj_.push_back(ev.accept_rates_avg);
       if (std::real(energy) < en_min_) {           // :118-121, in HBM
         en_min_ = std::real(energy);
-        c.VMCSnapshotSave();
+        comp_.contractor.VMCSnapshotSave();
         has_lowest_ = true;
       }
-      return ev;
+      if (user_callback_.on_evaluation_accepted) user_callback_.on_evaluation_accepted(ev, accepted_energy, iter);
     };
     const auto t_opt = std::chrono::steady_clock::now();
-    result_ = optimizer_.IterativeOptimize(wrapped, user_callback_);
+    result_ = optimizer_.IterativeOptimize(wrapped, cb, energy_only);
     const auto t_end = std::chrono::steady_clock::now();
     timings_.optimize_s = std::chrono::duration<double>(t_end - t_opt).count();
     timings_.total_s = std::chrono::duration<double>(t_end - t_begin).count();
@@ -4844,6 +5437,7 @@ class VMCPEPSOptimizer {
   const std::vector<double> &GetGradientNormTrajectory() const { return grad_norm_; }
   const std::vector<std::vector<double>> &GetAcceptRatesTrajectory() const { return accept_rates_traj_; }
   const typename OptimizerT::OptimizationResult &GetResult() const { return result_; }
+  const SpikeStatistics &GetSpikeStatistics() const { return result_.spike_stats; }
   OptimizerT &GetOptimizer() { return optimizer_; }
   EngineT &GetEngine() { return engine_; }
 
@@ -4887,7 +5481,7 @@ class VMCPEPSOptimizer {
   EngineT engine_;
   bool needs_sr_buffers_;
   MCEnergyGradEvaluator<MonteCarloSweepUpdater, Model, TenElemT> evaluator_;
-  Evaluator custom_evaluator_;
+  Evaluator custom_evaluator_, custom_energy_only_;
   typename OptimizerT::OptimizationCallback user_callback_;
   typename OptimizerT::OptimizationResult result_;
   std::vector<TenElemT> energy_trajectory_;

@@ -30,7 +30,9 @@ SYMBOLS = ["pepshost_last_error", "pepshost_mc_sweeps", "pepshost_energy_and_hol
            "pepshost_fermion_observables_sc", "pepshost_fermion_exact_sum_measure_partial_sc", "pepshost_fermion_measure_sc",
            "pepshost_sc_pair_corr_mapping",
            "pepshost_vmc_optimize", "pepshost_vmc_optimize_c128", "pepshost_fermion_vmc_optimize", "pepshost_mc_evaluate_resident",
-           "pepshost_binned_energy_stat"]
+           "pepshost_binned_energy_stat",
+           "pepshost_ema_track", "pepshost_spike_replay", "pepshost_acceptance_rate_check", "pepshost_step_select", "pepshost_step_candidates",
+           "pepshost_validate_guards", "pepshost_guarded_optimize_exact_sum", "pepshost_guarded_vmc_optimize"]
 
 _lib = None
 _C128 = 3                                   # PEPSGPU_C128 (include/pepsgpu.h)
@@ -1074,6 +1076,276 @@ def mc_evaluate_resident(state, configs, seeds, chi, model, params, updater="exc
            "sr_count": sc[:, 4].astype(int), "accept_rates": acc, "configs": cfg}
     if step is not None:
         out.update(state=theta, step_energy=float(sinfo[0]), step_grad_norm=float(sinfo[1]))
+    return out
+
+
+# ---- spike recovery, step selectors and checkpoints (qlpeps_gpu.h: SpikeGuard, OptimizerParams; pepshost.cpp: GuardSpec) ----
+SPIKE_SIGNALS = ("NONE", "S1_ERRORBAR", "S2_GRAD_NORM", "S3_NGRAD_ANOMALY", "S4_ENERGY_SPIKE")      # SignalName
+SPIKE_ACTIONS = ("ACCEPT", "RESAMPLE", "ROLLBACK", "ACCEPT_WARN")                                    # ActionName
+# SpikeRecoveryParams, optimizer_params.h:299-313 (the reference's defaults)
+SPIKE_DEFAULTS = dict(enable_auto_recover=True, redo_mc_max_retries=2, factor_err=100.0, factor_grad=1e10, factor_ngrad=10.0,
+                      sr_min_iters_suspicious=1, enable_rollback=False, ema_window=50, sigma_k=10.0, log_trigger_csv_path="")
+# InitialStepSelectorParams / PeriodicStepSelectorParams, :164-184
+SELECTOR_DEFAULTS = dict(initial=dict(enabled=False, max_line_search_steps=3, enable_in_deterministic=False),
+                         periodic=dict(enabled=False, every_n_steps=10, phase_switch_ratio=0.3, enable_in_deterministic=False))
+
+
+def _guard_array(spike, selectors, checkpoint, scheduler=None, energy_tolerance=0.0, gradient_tolerance=0.0, plateau_patience=0,
+                 probe_iteration=-1, events_cap=0):
+    """the 24 doubles of the shim's GuardSpec and the two paths.  spike=None: recovery off (what the two-argument OptimizerParams
+    constructor of this tree gives); a dict: the reference's defaults with the given fields replaced."""
+    sp = dict(SPIKE_DEFAULTS)
+    if spike is None:
+        sp["enable_auto_recover"] = False
+    else:
+        unknown = set(spike) - set(sp)
+        if unknown:
+            raise ValueError("unknown spike fields %s" % sorted(unknown))
+        sp.update(spike)
+    sel = {k: dict(v) for k, v in SELECTOR_DEFAULTS.items()}
+    for k, v in (selectors or {}).items():
+        if k not in sel or set(v) - set(sel[k]):
+            raise ValueError("selectors = dict(initial=dict(...), periodic=dict(...)) with the fields of %s" % (SELECTOR_DEFAULTS,))
+        sel[k].update(v)
+        if "enabled" not in v:                              # naming a selector enables it
+            sel[k]["enabled"] = True
+    ck = dict(every_n_steps=0, base_path="")
+    ck.update(checkpoint or {})
+    ini, per = sel["initial"], sel["periodic"]
+    g = np.array([sp["enable_auto_recover"], sp["redo_mc_max_retries"], sp["factor_err"], sp["factor_grad"], sp["factor_ngrad"],
+                  sp["sr_min_iters_suspicious"], sp["enable_rollback"], sp["ema_window"], sp["sigma_k"],
+                  ini["enabled"], ini["max_line_search_steps"], ini["enable_in_deterministic"],
+                  per["enabled"], per["every_n_steps"], per["phase_switch_ratio"], per["enable_in_deterministic"],
+                  ck["every_n_steps"], 1.0 if scheduler else 0.0, energy_tolerance, gradient_tolerance, plateau_patience, probe_iteration,
+                  events_cap, 0.0], dtype=np.float64)
+    return g, sp["log_trigger_csv_path"].encode(), ck["base_path"].encode()
+
+
+def _schedule_arrays(schedule):
+    if not schedule:
+        return None, None, 0
+    eo, es = schedule.get("error_override"), schedule.get("energy_shift")
+    n = len(eo) if eo is not None else len(es)
+    eo = np.full(n, np.nan) if eo is None else np.ascontiguousarray(eo, dtype=np.float64)
+    es = np.zeros(n) if es is None else np.ascontiguousarray(es, dtype=np.float64)
+    if eo.size != n or es.size != n:
+        raise ValueError("error_override and energy_shift have one entry per evaluator call")
+    return eo, es, n
+
+
+def _events(ev, n):
+    return [dict(step=int(e[0]), attempt=int(e[1]), signal=SPIKE_SIGNALS[int(e[2])], action=SPIKE_ACTIONS[int(e[3])], value=float(e[4]),
+                 threshold=float(e[5])) for e in ev[:n]]
+
+
+def ema_track(series, window, reset_at=-1):
+    """EMATracker(window) of the host layer fed with `series`: (mean, var) after every Update.  reset_at >= 0 calls Reset() before that
+    observation.  Needs no device."""
+    a = np.ascontiguousarray(series, dtype=np.float64).ravel()
+    mean, var = np.zeros(a.size), np.zeros(a.size)
+    l = lib()
+    dpt = C.POINTER(C.c_double)
+    l.pepshost_ema_track.argtypes = [dpt, C.c_int, C.c_long, C.c_int, dpt, dpt]
+    _ck(l.pepshost_ema_track(_p(a, C.c_double), a.size, int(window), int(reset_at), _p(mean, C.c_double), _p(var, C.c_double)))
+    return mean, var
+
+
+def spike_replay(records, algo, spike_params=None):
+    """The optimizer's own detect / decide / EMA code (SpikeGuard) on a scripted list of evaluations (energy, error, grad_norm,
+    ngrad_norm, cg_iters), in the order IterativeOptimize would make them: a rejected evaluation is followed by the next record at the
+    same iteration.  algo "sr" judges S3 with the CG iterations, "minsr" on the norm only, any other rule has no S3.  Returns a dict:
+    actions / iterations per record, ema [record][energy, error, grad, ngrad][mean, var], events, total_resamples / total_rollbacks /
+    total_forced_accepts, csv (the trigger CSV as text).  Needs no device."""
+    rec = np.ascontiguousarray(records, dtype=np.float64).reshape(-1, 5)
+    n = rec.shape[0]
+    aid = VMC_ALGO_ID[algo] if isinstance(algo, str) else int(algo)
+    g, _, _ = _guard_array(dict(spike_params or {}), None, None)
+    actions, iters = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    ema, cap = np.zeros((n, 4, 2)), 3 * n + 8
+    ev, counts = np.zeros((cap, 6)), np.zeros(4)
+    csv = C.create_string_buffer(256 * (cap + 1))
+    l = lib()
+    dpt, i32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    l.pepshost_spike_replay.argtypes = [dpt, C.c_int, C.c_int, dpt, i32, i32, dpt, dpt, C.c_int, dpt, C.c_char_p, C.c_long]
+    _ck(l.pepshost_spike_replay(_p(rec, C.c_double), n, aid, _p(g, C.c_double), _p(actions, C.c_int32), _p(iters, C.c_int32),
+                                _p(ema, C.c_double), _p(ev, C.c_double), cap, _p(counts, C.c_double), csv, len(csv)))
+    return {"actions": [SPIKE_ACTIONS[a] for a in actions], "iterations": iters, "ema": ema, "events": _events(ev, int(counts[0])),
+            "total_resamples": int(counts[1]), "total_rollbacks": int(counts[2]), "total_forced_accepts": int(counts[3]),
+            "csv": csv.value.decode()}
+
+
+def acceptance_rate_check(rates):
+    """AcceptanceRateCheck of the evaluator (a walker plays the rank): the indices of the walkers whose rate is below half the maximum."""
+    a = np.ascontiguousarray(rates, dtype=np.float64).ravel()
+    flags = np.zeros(max(a.size, 1), dtype=np.int32)
+    l = lib()
+    l.pepshost_acceptance_rate_check.argtypes = [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int32)]
+    _ck(l.pepshost_acceptance_rate_check(_p(a, C.c_double), a.size, _p(flags, C.c_int32)))
+    return [int(w) for w in np.nonzero(flags[:a.size])[0]]
+
+
+def step_select(kind, results, iter, max_iter, base_lr, ratio=0.3):
+    """The selection rule of the "initial" / "periodic" step selector on trial results [(eta, energy, error), ...]; returns (selected
+    eta, the selector's base learning rate afterwards).  Needs no device."""
+    r = np.ascontiguousarray(results, dtype=np.float64).reshape(-1, 3)
+    out = np.zeros(2)
+    l = lib()
+    dpt = C.POINTER(C.c_double)
+    l.pepshost_step_select.argtypes = [C.c_int, dpt, C.c_int, C.c_long, C.c_long, C.c_double, C.c_double, dpt]
+    _ck(l.pepshost_step_select({"initial": 0, "periodic": 1}[kind], _p(r, C.c_double), r.shape[0], int(iter), int(max_iter), float(base_lr),
+                               float(ratio), _p(out, C.c_double)))
+    return float(out[0]), float(out[1])
+
+
+def step_candidates(kind, base_lr, max_line_search_steps=3):
+    """the learning rates a selector tries from base_lr: "initial" base_lr * 1 .. max_line_search_steps, "periodic" (base_lr, base_lr / 2)"""
+    out, n = np.zeros(max(int(max_line_search_steps), 2)), C.c_int(0)
+    l = lib()
+    l.pepshost_step_candidates.argtypes = [C.c_int, C.c_double, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int)]
+    _ck(l.pepshost_step_candidates({"initial": 0, "periodic": 1}[kind], float(base_lr), int(max_line_search_steps), _p(out, C.c_double),
+                                   out.size, C.byref(n)))
+    return out[:n.value].copy()
+
+
+def validate_guards(algo, lr, rule_params, spike=None, selectors=None, scheduler=None, n_walkers=None, n_seeds=None, samples_per_walker=1):
+    """OptimizerParams::ValidateGuards (n_walkers None) or VMCPEPSOptimizerParams::Validate for these settings: raises ValueError with the
+    optimizer's message, before and without any device call."""
+    aid, rp = _vmc_rule(algo, rule_params)
+    g, _, _ = _guard_array(spike, selectors, None, scheduler=scheduler)
+    l = lib()
+    dpt = C.POINTER(C.c_double)
+    l.pepshost_validate_guards.argtypes = [C.c_int, dpt, C.c_int, C.c_double, dpt, C.c_int, C.c_int, C.c_int]
+    nw = -1 if n_walkers is None else int(n_walkers)
+    _ck(l.pepshost_validate_guards(aid, _p(rp, C.c_double), rp.size, float(lr), _p(g, C.c_double), nw,
+                                   nw if n_seeds is None else int(n_seeds), int(samples_per_walker)))
+
+
+def _guarded_result(energies, errors, norms, eta, ev, state, lowest, probe, info):
+    ne, nev = int(info[0]), int(info[1])
+    out = {"energies": energies[:ne], "energy_errors": errors[:ne], "grad_norms": norms[:ne], "selected_eta": eta[:int(info[13])],
+           "events": _events(ev, min(nev, ev.shape[0])), "n_events": nev, "total_resamples": int(info[2]), "total_rollbacks": int(info[3]),
+           "total_forced_accepts": int(info[4]), "evaluator_calls": int(info[5]), "energy_only_calls": int(info[6]),
+           "total_iterations": int(info[7]), "converged": bool(info[8]), "min_energy": float(info[9]), "sr_iterations": int(info[10]),
+           "sr_natural_grad_norm": float(info[11]), "sr_residual_norm": float(info[12]), "state": state,
+           "lowest_state": lowest if info[14] else None, "probe_state": probe}
+    return out
+
+
+class GuardedRunError(RuntimeError):
+    """the guarded loop threw (a non-finite selector trial, an exhausted schedule): .state = theta as the optimizer was left with,
+    .evaluator_calls = evaluator calls made"""
+
+
+def _guarded_exact_sum(head, fermion, cplx, dtype, flat, stored_shape, cfgs, chi, mid, prm, algo, lr, rule_params, iterations, clip_value,
+                       clip_norm, batch, spike, selectors, checkpoint, schedule, scheduler, energy_tolerance, gradient_tolerance,
+                       plateau_patience, probe_iteration):
+    cfg = np.ascontiguousarray(cfgs, dtype=np.int32)
+    aid, rp = _vmc_rule(algo, rule_params)
+    eo, es, ns = _schedule_arrays(schedule)
+    cap = 4 * (int(iterations) + ns) + 16
+    g, csv, ckp = _guard_array(spike, selectors, checkpoint, scheduler, energy_tolerance, gradient_tolerance, plateau_patience, probe_iteration, cap)
+    opt = np.array([aid, lr, iterations, clip_value, clip_norm], dtype=np.float64)
+    ne = int(iterations) + 1
+    et = flat.dtype
+    energies = np.zeros(ne, dtype=et)
+    errors, norms, eta, ev, info = np.zeros(ne), np.zeros(ne), np.zeros(ne), np.zeros((cap, 6)), np.zeros(16)
+    state, lowest = np.zeros(stored_shape, dtype=et), np.zeros(stored_shape, dtype=et)
+    probe = np.zeros(stored_shape, dtype=et) if probe_iteration >= 0 else None
+    l = lib()
+    dpt, i32, cs = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_char_p
+    l.pepshost_guarded_optimize_exact_sum.argtypes = ([C.c_int] * 4 + [i32, C.POINTER(C.c_uint8), C.c_int, C.c_int, dpt, i32, C.c_int, C.c_int, dpt,
+                                                       C.c_int, dpt, dpt, C.c_int, C.c_int, dpt, cs, cs, dpt, dpt, C.c_int] + [dpt] * 9)
+    rc = l.pepshost_guarded_optimize_exact_sum(*head, chi, _C128 if cplx else dtype, _cp(flat), _p(cfg, C.c_int32), cfg.shape[0], mid,
+                                               _p(prm, C.c_double), prm.size, _p(opt, C.c_double), _p(rp, C.c_double), rp.size,
+                                               int(min(batch, cfg.shape[0])), _p(g, C.c_double), csv, ckp, _p(eo, C.c_double),
+                                               _p(es, C.c_double), ns, _cp(energies), _p(errors, C.c_double), _p(norms, C.c_double),
+                                               _p(eta, C.c_double), _p(ev, C.c_double), _cp(state), _cp(lowest),
+                                               _cp(probe) if probe is not None else None, _p(info, C.c_double))
+    if rc not in (0, 1):                                    # (1: a refusal before the loop, nothing to report)
+        err = GuardedRunError("pepshost error %d: %s" % (rc, l.pepshost_last_error().decode()))
+        err.state, err.evaluator_calls = state, int(info[5])
+        raise err
+    _ck(rc)
+    return _guarded_result(energies, errors, norms, eta, ev, state, lowest, probe, info)
+
+
+def guarded_optimize_exact_sum(flat, all_configs, chi, model, params, algo, lr, rule_params, iterations, spike=None, selectors=None,
+                               checkpoint=None, schedule=None, clip_value=0.0, clip_norm=0.0, dtype=1, batch=64, scheduler=None,
+                               energy_tolerance=0.0, gradient_tolerance=0.0, plateau_patience=0, probe_iteration=-1):
+    """Optimizer::IterativeOptimize with spike recovery, step selectors and checkpoints on a fixed set of configurations, the whole loop in
+    one C++ call.  algo "sgd" / "adagrad" / "adam" / "lbfgs" evaluate by exact summation over all_configs (optimize_exact_sum); "sr" /
+    "minsr" take all_configs as a sample set of weight 1 (sr_step_samples, minsr_step_samples).  A complex `flat` runs the QLTEN_Complex
+    instantiation.
+      spike      None: recovery off; dict(...): SpikeRecoveryParams, the reference's defaults with these fields replaced
+      selectors  dict(initial=dict(...), periodic=dict(...)): naming one enables it
+      checkpoint dict(every_n_steps, base_path)
+      schedule   dict(error_override=[...], energy_shift=[...]), one entry per evaluator call: the error bar is replaced where the entry
+                 is not NaN, energy_shift * weight_sum is added to e_loc_sum (energy and gradient move); a call beyond the schedule raises
+      scheduler  True: a ConstantLR scheduler at lr (what a step selector refuses)
+    Returns a dict: energies / energy_errors / grad_norms of the accepted evaluations, selected_eta per iteration (0 where no selector
+    ran), events (dicts step, attempt, signal, action, value, threshold) and the three counters, evaluator_calls, state (final),
+    lowest_state, min_energy, probe_state (theta at on_iteration of probe_iteration), SR diagnostics.  A throw from the loop raises
+    GuardedRunError carrying the state."""
+    cplx = np.iscomplexobj(flat)
+    flat = np.ascontiguousarray(flat, dtype=np.complex128 if cplx else np.float64)
+    rows, cols, d, D = _dims(flat)
+    prm = np.array(list(params) + [0.0] * 8, dtype=np.float64)
+    return _guarded_exact_sum((rows, cols, D, d, None, None), False, cplx, dtype, flat, flat.shape, all_configs, chi, MODEL_ID[model], prm, algo,
+                              lr, rule_params, iterations, clip_value, clip_norm, batch, spike, selectors, checkpoint, schedule, scheduler,
+                              energy_tolerance, gradient_tolerance, plateau_patience, probe_iteration)
+
+
+def fermion_guarded_optimize_exact_sum(state, all_configs, chi, model, params, algo, lr, rule_params, iterations, spike=None, selectors=None,
+                                       checkpoint=None, schedule=None, clip_value=0.0, clip_norm=0.0, dtype=1, batch=64, scheduler=None,
+                                       energy_tolerance=0.0, gradient_tolerance=0.0, plateau_patience=0, probe_iteration=-1):
+    """guarded_optimize_exact_sum on a fermionic state (peps_amd.fermion.FermionState); model and params as fermion_optimize_exact_sum;
+    the states of the result are the stored tensors [rows][cols][d][D^4]."""
+    cplx, flat, nf, par, head = _fermion_head(state, dtype)
+    shape = (flat.shape[0], flat.shape[1], state.d) + flat.shape[3:]
+    return _guarded_exact_sum(head, True, cplx, dtype, flat, shape, all_configs, chi, FERMION_MODEL_ID[model], _fermion_prm(model, params), algo,
+                              lr, rule_params, iterations, clip_value, clip_norm, batch, spike, selectors, checkpoint, schedule, scheduler,
+                              energy_tolerance, gradient_tolerance, plateau_patience, probe_iteration)
+
+
+def guarded_vmc_optimize(flat, configs, seeds, chi, model, params, updater, algo, lr, rule_params, iterations, warmup_sweeps=0,
+                         samples_per_walker=1, sweeps_between_samples=1, spike=None, selectors=None, checkpoint=None, schedule=None,
+                         clip_value=0.0, clip_norm=0.0, dtype=1, scheduler=None):
+    """VMCPEPSOptimizer::WarmUpAndOptimize with spike recovery, step selectors and checkpoints (no closing normalisation, no dumps);
+    spike / selectors / checkpoint / schedule / scheduler as guarded_optimize_exact_sum.  The schedule wraps the executor's own
+    evaluator; the selector trials use its energy-only variant.  Every refusal of VMCPEPSOptimizerParams::Validate is raised before
+    any device call.  Returns the dict of guarded_optimize_exact_sum plus accept_rates [accepted evaluation][walker] and configs; the
+    trajectories, lowest_state and min_energy are the executor's own (accepted evaluations only)."""
+    cplx = np.iscomplexobj(flat)
+    flat = np.ascontiguousarray(flat, dtype=np.complex128 if cplx else np.float64)
+    rows, cols, d, D = _dims(flat)
+    cfg = np.ascontiguousarray(configs, dtype=np.int32).reshape(-1, rows, cols).copy()
+    n = cfg.shape[0]
+    sd = np.ascontiguousarray(seeds, dtype=np.uint64).ravel()
+    p = np.array(list(params) + [0.0] * 8, dtype=np.float64)
+    aid, rp = _vmc_rule(algo, rule_params)
+    eo, es, ns = _schedule_arrays(schedule)
+    cap = 4 * (int(iterations) + ns) + 16
+    g, csv, ckp = _guard_array(spike, selectors, checkpoint, scheduler, events_cap=cap)
+    mc = np.array([warmup_sweeps, samples_per_walker, sweeps_between_samples], dtype=np.float64)
+    opt = np.array([aid, lr, iterations, clip_value, clip_norm, 0, -1], dtype=np.float64)
+    ne = int(iterations) + 1
+    energies = np.zeros(ne, dtype=flat.dtype)
+    errors, norms, eta, ev, info = np.zeros(ne), np.zeros(ne), np.zeros(ne), np.zeros((cap, 6)), np.zeros(16)
+    accept = np.zeros((ne, max(n, 1)))
+    state, lowest = np.zeros_like(flat), np.zeros_like(flat)
+    l = lib()
+    dpt, i32, cs = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_char_p
+    l.pepshost_guarded_vmc_optimize.argtypes = ([C.c_int] * 4 + [i32, C.POINTER(C.c_uint8), C.c_int, C.c_int, dpt, C.c_int, i32, C.POINTER(C.c_uint64),
+                                                 C.c_int, C.c_int, C.c_int, dpt, C.c_int, dpt, dpt, dpt, C.c_int, dpt, cs, cs, dpt, dpt, C.c_int]
+                                                + [dpt] * 9)
+    _ck(l.pepshost_guarded_vmc_optimize(rows, cols, D, d, None, None, chi, _C128 if cplx else dtype, _cp(flat), n, _p(cfg, C.c_int32),
+                                        _p(sd, C.c_uint64), sd.size, UPDATER_ID[updater], MODEL_ID[model], _p(p, C.c_double), 8,
+                                        _p(mc, C.c_double), _p(opt, C.c_double), _p(rp, C.c_double), rp.size, _p(g, C.c_double), csv, ckp,
+                                        _p(eo, C.c_double), _p(es, C.c_double), ns, _cp(energies), _p(errors, C.c_double),
+                                        _p(norms, C.c_double), _p(eta, C.c_double), _p(ev, C.c_double), _p(accept, C.c_double), _cp(state),
+                                        _cp(lowest), _p(info, C.c_double)))
+    out = _guarded_result(energies, errors, norms, eta, ev, state, lowest, None, info)
+    out.update(accept_rates=accept[:int(info[0])], configs=cfg)
     return out
 
 

@@ -877,6 +877,16 @@ int pepsgpu_diag_suwa_todo(const double *weights, int n, int init, const uint32_
 /* forward contraction pair of an absorption through the LDS-chained kernel (tgemm_chain_kernel); see capi.hip */
 int pepsgpu_diag_tgemm_chain(const int *dims7, const int32_t *live3_per_entry, int nbatch, const float *R, const float *A,
                              const float *W, float *P_out, int32_t *flags_out);
+/* the forward pair (backward = 0: P = W (R A)) or the backward pair (1: Tt = W (A Y)) of an absorption with the engine's descriptors,
+ * the site tensor reached through a selector table; opts & 1 asks for the leg-8 kernel (tgemm_d8.h) where its shape contract holds,
+ * else tgemm_chain_kernel runs; info_out = {launcher's return, 1 when the leg-8 kernel ran}; see capi.hip */
+int pepsgpu_diag_tgemm_chain_pair(int backward, const int *dims8, const int *site_strides4, long slot, int nslots, const int32_t *sel,
+                                  const int32_t *live3_per_entry, int nbatch, int opts, const float *scale_in, const float *op1,
+                                  const float *op2, const float *site, float *out, int32_t *flags_out, int32_t *info_out);
+/* launches of the leg-8 chained-pair kernel by this process (PEPSGPU_CHAIN_D8=0 keeps it at zero) */
+long pepsgpu_diag_chain_d8_launches(void);
+/* PEPSGPU_CHAIN_D8_STATS=1: out2 = {walkers the leg-8 kernel computed, of them walked in chunks of the intermediate}; else zeros */
+int pepsgpu_diag_chain_d8_stats(unsigned long long *out2);
 int pepsgpu_diag_gram_chol(int dtype, const void *P, int K, int n, int nbatch, void *R_out, int32_t *mlive_out);
 /* one of the two one-wave Gram-free factor kernels alone, launched as the engine launches it (form 0: gram_chol_wave_kernel, four
  * walkers per 256-thread block; 1: gram_chol_wave_split_kernel, the row-parity placement, one walker per 64-thread block), then the

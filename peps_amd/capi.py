@@ -53,6 +53,7 @@ SYMBOLS = [
     "pepsgpu_walker_flags", "pepsgpu_sync", "pepsgpu_stats", "pepsgpu_profile_enable", "pepsgpu_profile_read",
     "pepsgpu_diag_tgemm", "pepsgpu_diag_tgemm_desc", "pepsgpu_diag_tgemm_route", "pepsgpu_diag_tgemm_chain", "pepsgpu_diag_tgemm_chain3", "pepsgpu_diag_chol", "pepsgpu_diag_chol_adaptive", "pepsgpu_diag_chol_pivot", "pepsgpu_diag_rows_qr", "pepsgpu_diag_suwa_todo", "pepsgpu_diag_dot4", "pepsgpu_diag_gram_chol", "pepsgpu_diag_gram_chol_wave", "pepsgpu_diag_gram_cols", "pepsgpu_diag_gram_rows", "pepsgpu_diag_mgemm_dense", "pepsgpu_diag_jacobi", "pepsgpu_diag_trunc_rows", "pepsgpu_version",
     "pepsgpu_diag_chol_solve_rows", "pepsgpu_diag_gather_rows", "pepsgpu_diag_sign_table", "pepsgpu_diag_truncate_site",
+    "pepsgpu_diag_tgemm_chain_pair", "pepsgpu_diag_chain_d8_launches", "pepsgpu_diag_chain_d8_stats",
 ]
 
 
@@ -1201,6 +1202,65 @@ def diag_tgemm_chain(R, A, W, live):
     if rc != 0:
         raise RuntimeError("diag_tgemm_chain failed: %s" % lib().pepsgpu_last_error(None).decode())
     return P, fl
+
+
+def diag_tgemm_chain_pair(backward, dims, site_strides, site, slot, sel, op1, op2, live, out_init, d8=True, tsw=False,
+                          zero_fill=False, f64=False, scale_in=None):
+    """The forward pair P = W (R A) (backward False: op1 = R [nb, m, l, a], op2 = A [nb, a, p, a2], live = per entry (m, a, a2),
+    out = P [nb, m, u, l2, a2]) or the backward pair Tt = W (A Y) (True: op1 = A, op2 = Y [nb, l2, a2, k2], live = (a, a2, k2),
+    out = Tt [nb, l, a, u, k2], [nb, l, a, k2, u] with tsw) with the engine's descriptors.  dims = (m, a, a2, k2, l, p, l2, u);
+    site = flat store of slot-element site tensors with the legs (l, p, l2, u) at site_strides, entry b uses tensor sel[b].
+    d8 asks for the leg-8 kernel where its contract holds, else the generic chained kernel runs.
+    Returns (out, flags, launched, ran_d8)."""
+    d8v = np.ascontiguousarray(dims, dtype=np.int32)
+    st = np.ascontiguousarray(site_strides, dtype=np.int32)
+    sel = np.ascontiguousarray(sel, dtype=np.int32)
+    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32).ravel()   # noqa: E731
+    o1, o2, sv = f32(op1), f32(op2), f32(site)
+    out = np.ascontiguousarray(out_init, dtype=np.float32).copy()
+    nb = int(out.shape[0])
+    lv = np.ascontiguousarray(live, dtype=np.int32)
+    m, a, a2, k2, l, p, l2, u = (int(v) for v in d8v)
+    n1, n2, no = ((a * p * a2, l2 * a2 * k2, l * a * u * k2) if backward else (m * l * a, a * p * a2, m * u * l2 * a2))
+    if o1.size != n1 * nb or o2.size != n2 * nb or out.size != no * nb or lv.size != 3 * nb or sel.size != nb or d8v.size != 8:
+        raise ValueError("diag_tgemm_chain_pair: operand sizes do not match dims")
+    if sv.size % slot or int(sel.min()) < 0 or (int(sel.max()) + 1) * slot > sv.size:
+        raise ValueError("diag_tgemm_chain_pair: selector or site store too small")
+    reach = sum((e - 1) * int(s) for e, s in zip((l, p, l2, u), st))
+    if reach >= slot or int(st.min()) < 0:
+        raise ValueError("diag_tgemm_chain_pair: site strides reach beyond a slot")
+    sc = None if scale_in is None else np.ascontiguousarray(scale_in, dtype=np.float32)
+    flags = np.full(nb, 7, dtype=np.int32)
+    info = np.zeros(2, dtype=np.int32)
+    vpp = lambda x: x.ctypes.data_as(C.c_void_p)   # noqa: E731
+    f = lib().pepsgpu_diag_tgemm_chain_pair
+    f.argtypes = [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_long, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                  C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
+                  C.POINTER(C.c_int32)]
+    opts = (1 if d8 else 0) | (2 if tsw else 0) | (4 if zero_fill else 0) | (8 if f64 else 0)
+    rc = f(1 if backward else 0, _ip(d8v), _ip(st), slot, sv.size // slot, _ip(sel), _ip(lv), nb, opts,
+           None if sc is None else vpp(sc), vpp(o1), vpp(o2), vpp(sv), vpp(out), _ip(flags), _ip(info))
+    if rc != 0:
+        raise RuntimeError("diag_tgemm_chain_pair failed: %s" % lib().pepsgpu_last_error(None).decode())
+    return out, flags, int(info[0]), bool(info[1])
+
+
+def diag_chain_d8_launches():
+    """Launches of the leg-8 chained-pair kernel by this process."""
+    f = lib().pepsgpu_diag_chain_d8_launches
+    f.argtypes = []
+    f.restype = C.c_long
+    return int(f())
+
+
+def diag_chain_d8_stats():
+    """(walkers the leg-8 kernel computed, of them walked in chunks) under PEPSGPU_CHAIN_D8_STATS=1; zeros when it is unset."""
+    out = (C.c_ulonglong * 2)()
+    f = lib().pepsgpu_diag_chain_d8_stats
+    f.argtypes = [C.POINTER(C.c_ulonglong)]
+    if f(out) != 0:
+        raise RuntimeError("diag_chain_d8_stats failed: %s" % lib().pepsgpu_last_error(None).decode())
+    return int(out[0]), int(out[1])
 
 
 def diag_chol(dtype_out, G):

@@ -950,6 +950,86 @@ extern "C" int pepsgpu_diag_tgemm_chain(const int *dims, const int32_t *live, in
   });
 }
 
+// The forward pair (P = W (R A)) or the backward pair (Tt = W (A Y)) of an absorption through tgemm_chain_launch, with the
+// descriptors of Engine::forward_pair / backward_pair (absorb_desc.h) and the site tensor reached through a selector table:
+//   dims8 = {m, a, a2, k2, l, p, l2, u} (static); site_strides4 = element strides of the legs (l, p, l2, u) of one site tensor,
+//   `nslots` tensors of `slot` elements in `site`, entry b uses tensor sel[b]
+//   forward:  op1 = R [nbatch][m][l][a], op2 = A [nbatch][a][p][a2], live3 = per entry {m, a, a2}, out = P [nbatch][m][u][l2][a2]
+//   backward: op1 = A [nbatch][a][p][a2], op2 = Y [nbatch][l2][a2][k2], live3 = per entry {a, a2, k2},
+//             out = Tt [nbatch][l][a][u][k2] ([l][a][k2][u] with opts & 2); scale_in (nullable) = per-entry input scale
+//   opts: 1 the leg-8 kernel where its contract holds (else tgemm_chain_kernel), 2 tsw, 4 the zero-filling (masked) k2 extent of
+//         the first site, 8 the float64-accumulating form
+// out holds the initial contents (what no kernel stores comes back unchanged).  flags_out[b] = the kernel's flag;
+// info_out = {the launcher's return, 1 when the leg-8 kernel ran}.
+extern "C" int pepsgpu_diag_tgemm_chain_pair(int backward, const int *dims8, const int *site_strides4, long slot, int nslots,
+                                             const int32_t *sel, const int32_t *live3, int nbatch, int opts, const float *scale_in,
+                                             const float *op1, const float *op2, const float *site, float *out, int32_t *flags_out,
+                                             int32_t *info_out) {
+  return guarded(nullptr, [&]() {
+    PG_REQUIRE(nbatch > 0 && nslots > 0 && slot > 0 && dims8 && site_strides4 && sel && live3 && op1 && op2 && site && out, 1, "bad arguments");
+    SiteDims d;
+    d.m = dims8[0]; d.a = dims8[1]; d.a2 = dims8[2]; d.k2 = dims8[3]; d.l = dims8[4]; d.p = dims8[5]; d.l2 = dims8[6]; d.u = dims8[7];
+    d.ll = 0; d.lp = 1; d.lr = 2; d.lu = 3;
+    for (int q = 0; q < 4; ++q) d.st[q] = site_strides4[q];
+    d.la = d.l * d.a; d.uk = d.u * d.k2;
+    for (int b = 0; b < nbatch; ++b) PG_REQUIRE(sel[b] >= 0 && sel[b] < nslots, 1, "selector beyond the site store");
+    const long n1 = backward ? (long)d.a * d.p * d.a2 : (long)d.m * d.l * d.a;
+    const long n2 = backward ? (long)d.l2 * d.a2 * d.k2 : (long)d.a * d.p * d.a2;
+    const long no = backward ? (long)d.l * d.a * d.u * d.k2 : (long)d.m * d.u * d.l2 * d.a2;
+    DevBufs mb;
+    const float *d1p = mb.alloc<float>(n1 * nbatch, op1), *d2p = mb.alloc<float>(n2 * nbatch, op2);
+    const float *dsite = mb.alloc<float>((size_t)slot * nslots, site);
+    float *dout = mb.alloc<float>(no * nbatch, out);
+    const int *dsel = mb.alloc<int>(nbatch, sel);
+    const float *dscale = scale_in ? mb.alloc<float>(nbatch, scale_in) : nullptr;
+    int *dflag = mb.alloc<int>(nbatch, flags_out);
+    std::vector<int> hl(3 * (size_t)nbatch);
+    for (int b = 0; b < nbatch; ++b)
+      for (int q = 0; q < 3; ++q) hl[(size_t)q * nbatch + b] = live3[3 * b + q];
+    const int *dl = mb.alloc<int>(hl.size(), hl.data());
+    const int *v0 = dl, *v1 = dl + nbatch, *v2 = dl + 2 * (size_t)nbatch;
+    TGemmDesc g1, g2;
+    if (backward) {
+      g1 = desc_z1(d, n1, n2, 0, nbatch, v0, v1, v2);
+      g1.scale_in = dscale;
+      g2 = desc_tt(d, (opts & 2) != 0, 0, no, nbatch, v0, v2, (opts & 4) != 0);
+    } else {
+      g1 = desc_x(d, n1, n2, 0, nbatch, v0, 1, v1, v2);
+      g2 = desc_p(d, 0, no, nbatch, v0, 1, v2);
+    }
+    g2.selA = dsel; g2.selA_mul = slot; g2.selA_inc = 1; g2.seldivA = 1; g2.wA = 0;
+    TGemmChainMap mp;
+    mp.mapK[1] = 2; mp.mapK[2] = 4;
+    mp.mapJ[1] = 1; mp.mapJ[2] = 5;
+    const long before = tg_chain_d8_count.load();
+    tg_chain_d8_force = (opts & 1) ? 1 : 0;
+    int rc = 0;
+    try {
+      rc = tgemm_chain_launch(0, g1, g2, mp, d1p, d2p, dsite, dout, dflag, 1, 0, (opts & 8) ? 1 : 0);
+    } catch (...) { tg_chain_d8_force = -1; throw; }
+    tg_chain_d8_force = -1;
+    PG_REQUIRE(rc != 0, 1, "chain launch refused");
+    PG_CHECK_HIP(hipDeviceSynchronize());
+    info_out[0] = rc;
+    info_out[1] = tg_chain_d8_count.load() != before ? 1 : 0;
+    PG_CHECK_HIP(hipMemcpy(out, dout, no * nbatch * sizeof(float), hipMemcpyDeviceToHost));
+    PG_CHECK_HIP(hipMemcpy(flags_out, dflag, nbatch * sizeof(int), hipMemcpyDeviceToHost));
+  });
+}
+
+// launches of the leg-8 chained-pair kernel by this process
+extern "C" long pepsgpu_diag_chain_d8_launches(void) { return tg_chain_d8_count.load(); }
+// the counters of PEPSGPU_CHAIN_D8_STATS=1: out2 = {walkers the leg-8 kernel computed, of them walked in chunks}; zeros when unset
+extern "C" int pepsgpu_diag_chain_d8_stats(unsigned long long *out2) {
+  return guarded(nullptr, [&]() {
+    out2[0] = out2[1] = 0;
+    if (const unsigned long long *p = tgemm_chain_d8_stats()) {
+      PG_CHECK_HIP(hipDeviceSynchronize());
+      PG_CHECK_HIP(hipMemcpy(out2, p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    }
+  });
+}
+
 template <typename T>
 static void diag_chol_t(const double *G, int n, int nbatch, void *Rout) {
   double *dG;

@@ -14,6 +14,7 @@
 // matrices) -> v_mfma_f64_16x16x4_f64; 64x64x16 LDS tiles, 4 waves, register-prefetched
 // global loads.  A VALU path (PEPSGPU_NO_MFMA=1) exists only to cross-check the MFMA lane maps.
 #pragma once
+#include <atomic>
 #include "common.h"
 #include "cplx.h"
 
@@ -1431,6 +1432,34 @@ __global__ __launch_bounds__(256, MINB) void tgemm_chain3_kernel(TGemmDesc d1, T
   }
 }
 
+// The leg-8 specialisation of the chained pair (tgemm_d8.h): tgemm_chain_launch takes it where its shape contract holds.
+// PEPSGPU_CHAIN_D8 = 0 (read once per process) keeps every chained pair on tgemm_chain_kernel.
+inline bool tgemm_chain_d8_enabled() {
+  static const bool v = !(getenv("PEPSGPU_CHAIN_D8") && atoi(getenv("PEPSGPU_CHAIN_D8")) == 0);
+  return v;
+}
+// per-thread override for the diagnostics entry: -1 the switch decides, 0 the generic kernel, 1 the leg-8 kernel where its contract holds
+inline thread_local int tg_chain_d8_force = -1;
+// launches of the leg-8 kernel by this process (pepsgpu_diag_chain_d8_launches)
+inline std::atomic<long> tg_chain_d8_count{0};
+// diagnostics, PEPSGPU_CHAIN_D8_STATS=1 (read once per process): two device counters the leg-8 kernel adds to -- the walkers it
+// computed and, of them, those whose intermediate exceeded the buffer and was walked in chunks (pepsgpu_diag_chain_d8_stats)
+inline unsigned long long *tgemm_chain_d8_stats() {
+  static unsigned long long *p = []() -> unsigned long long * {
+    const char *e = getenv("PEPSGPU_CHAIN_D8_STATS");
+    if (!e || !atoi(e)) return nullptr;
+    unsigned long long *q = nullptr;
+    if (hipMalloc(&q, 2 * sizeof(unsigned long long)) != hipSuccess) return nullptr;
+    (void)hipMemset(q, 0, 2 * sizeof(unsigned long long));
+    return q;
+  }();
+  return p;
+}
+inline bool tgemm_chain_d8_accepts(const TGemmDesc &d1, const TGemmDesc &d2, const TGemmChainMap &mp, const float *A1, int allow_chunks,
+                                   int dense, int f64acc);
+inline int tgemm_chain_d8_launch(hipStream_t s, const TGemmDesc &d1, const TGemmDesc &d2, const float *A1, const float *B1, const float *A2,
+                                 float *C2, int *flag);
+
 // stage 2 of the chain must read exactly what stage 1 wrote: same live extents on the shared sub-indices (the caller
 // sets the same TgDyn on both), no masks on them.  Returns false when the static shapes rule the chain out.
 // Returns 0 when the static shapes rule the chain out, 1 when launched (entries may be declined: flag -1), 2 when launched and
@@ -1705,6 +1734,9 @@ inline int tgemm_chain_launch(hipStream_t s, const TGemmDesc &d1_in, const TGemm
   d1.flop_stride = d1.nbatch >= 256 ? 64 : 1;
   d1.thin = d2.thin = tgemm_thin() & TG_THIN_TILES;
   d1.stage_span = d2.stage_span = 0;
+  if ((tg_chain_d8_force >= 0 ? tg_chain_d8_force != 0 : tgemm_chain_d8_enabled()) &&
+      tgemm_chain_d8_accepts(d1, d2, mp, A1, allow_chunks, dense, f64acc))
+    return tgemm_chain_d8_launch(s, d1, d2, A1, B1, A2, C2, flag);
   constexpr bool no_vec = false;
   const bool avec1 = !no_vec && tg_vec_a(d1, A1), bvec1 = !no_vec && tg_vec_b(d1, B1), avec2 = !no_vec && tg_vec_a(d2, A2);
   const dim3 g(d1.nbatch), blk(256);
@@ -1795,3 +1827,5 @@ inline int tgemm_chain3_launch(hipStream_t s, const TGemmDesc &d1_in, const TGem
 }
 
 }  // namespace pepsgpu
+
+#include "tgemm_d8.h"

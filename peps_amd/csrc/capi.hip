@@ -574,10 +574,10 @@ int pepsgpu_sr_append(pepsgpu_ctx *ctx, const double *psi) { CTX_CALL(PG_REQUIRE
 int pepsgpu_sr_count(pepsgpu_ctx *ctx) { return (ctx && ctx->eng) ? ctx->eng->sr_count() : -1; }
 int pepsgpu_sr_sum(pepsgpu_ctx *ctx, double *out) { CTX_CALL(PG_REQUIRE(out, 1, "null output"); ctx->eng->sr_sum(out)); }
 int pepsgpu_sr_matvec_c128(pepsgpu_ctx *ctx, const double *v, double mean_dot_v_re, double mean_dot_v_im, double scale, double *out) {
-  CTX_CALL(PG_REQUIRE(v && out, 1, "null vector"); ctx->eng->sr_matvec_cplx(v, mean_dot_v_re, mean_dot_v_im, scale, out));
+  CTX_CALL(PG_REQUIRE(v && out, 1, "null vector"); ctx->eng->sr_matvec(v, mean_dot_v_re, mean_dot_v_im, scale, out));
 }
 int pepsgpu_sr_matvec(pepsgpu_ctx *ctx, const double *v, double mean_dot_v, double scale, double *out) {
-  CTX_CALL(PG_REQUIRE(v && out, 1, "null vector"); ctx->eng->sr_matvec(v, mean_dot_v, scale, out));
+  CTX_CALL(PG_REQUIRE(v && out, 1, "null vector"); ctx->eng->sr_matvec(v, mean_dot_v, 0.0, scale, out));
 }
 int pepsgpu_sr_cg_solve(pepsgpu_ctx *ctx, const double *b, const double *x0, double diag_shift, int max_iter,
                         double relative_tolerance, double absolute_tolerance, int residual_recompute_interval,

@@ -122,8 +122,7 @@ struct EngineBase {
   virtual void sr_append(const double *psi) = 0;
   virtual int sr_count() const = 0;
   virtual void sr_sum(double *out) = 0;
-  virtual void sr_matvec(const double *v, double mean_dot_v, double scale, double *out) = 0;
-  virtual void sr_matvec_cplx(const double *v, double mean_dot_v_re, double mean_dot_v_im, double scale, double *out) = 0;
+  virtual void sr_matvec(const double *v, double mean_dot_v_re, double mean_dot_v_im, double scale, double *out) = 0;
   virtual void sr_cg_solve(const double *b, const double *x0, double diag_shift, int max_iter, double rel_tol, double abs_tol,
                            int recompute_interval, double ortho_threshold, double *x_out, double *residual_norm,
                            int *iterations, int *reason) = 0;
@@ -887,8 +886,7 @@ class Engine : public EngineBase {
   void sr_append(const double *psi) override;
   int sr_count() const override { return sr_n_; }
   void sr_sum(double *out) override;
-  void sr_matvec(const double *v, double mean_dot_v, double scale, double *out) override;
-  void sr_matvec_cplx(const double *v, double mean_dot_v_re, double mean_dot_v_im, double scale, double *out) override;
+  void sr_matvec(const double *v, double mean_dot_v_re, double mean_dot_v_im, double scale, double *out) override;
   void sr_cg_solve(const double *b, const double *x0, double diag_shift, int max_iter, double rel_tol, double abs_tol,
                    int recompute_interval, double ortho_threshold, double *x_out, double *residual_norm, int *iterations,
                    int *reason) override;
@@ -922,6 +920,8 @@ class Engine : public EngineBase {
   void minsr_direction(const double *eloc, const double *energy, double r_pinv, double a_pinv, int soft_cutoff,
                        double *direction_norm_out, double *info_out) override;
   void sr_gram_device(double *g);          // the raw Gram of the local store, summed and mirrored in HBM (engine_sr.h)
+  template <typename Sum>
+  void sr_gram_walk(const void *remote_o, const int32_t *remote_cfg, int nb, Sum &&sum);      // the blocked split-K walk behind both
   void fermion_decoration_set(int d, const int32_t *nf, const uint8_t *bond_parity) override;
   void opt_fermion_project(double *x);     // Pi in place over one optimizer vector (a decoration is set)
   std::vector<uint8_t> fermion_sign_table() const;

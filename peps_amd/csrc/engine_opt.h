@@ -346,8 +346,8 @@ void Engine<T>::opt_end() {
 template <typename T>
 double Engine<T>::opt_norm_sq(const double *x) {
   const long n = (long)Ly_ * Lx_ * dp_ * slot_ * kOut;
-  hipLaunchKernelGGL(sr_dot_kernel, dim3(kOptDotBlocks), dim3(256), 0, stream_, x, x, n, opt_part_);
-  hipLaunchKernelGGL(sr_dot_final_kernel, dim3(1), dim3(64), 0, stream_, (const double *)opt_part_, (int)kOptDotBlocks,
+  hipLaunchKernelGGL(sr_dot_kernel<1>, dim3(kOptDotBlocks), dim3(256), 0, stream_, x, x, n, opt_part_);
+  hipLaunchKernelGGL(sr_dot_final_kernel<1>, dim3(1), dim3(64), 0, stream_, (const double *)opt_part_, (int)kOptDotBlocks,
                      opt_part_ + kOptDotBlocks);
   PG_CHECK_HIP(hipGetLastError());
   double out = 0.0;
@@ -717,17 +717,10 @@ void Engine<T>::minsr_direction(const double *eloc, const double *energy, double
   PG_CHECK_HIP(hipGetLastError());
   // the back-substitution: the kernels behind pepsgpu_sr_weighted_sum (-> sr_out_) and pepsgpu_sr_sum (-> sr_v_), device to device
   const dim3 ag((unsigned)((slot_ + 255) / 256), sites);
-  if constexpr (kCplx) {
-    hipLaunchKernelGGL(sr_accum_cplx_kernel<T>, ag, dim3(256), 0, stream_, (const T *)sr_o_, (const int *)sr_cfg_, (const double *)sr_delta_,
-                       1.0, sr_out_, ns, sites, slot_, dp_);
-    hipLaunchKernelGGL(sr_accum_cplx_kernel<T>, ag, dim3(256), 0, stream_, (const T *)sr_o_, (const int *)sr_cfg_, (const double *)nullptr,
-                       1.0, sr_v_, ns, sites, slot_, dp_);
-  } else {
-    hipLaunchKernelGGL(sr_accum_kernel<T>, ag, dim3(256), 0, stream_, (const T *)sr_o_, (const int *)sr_cfg_, (const double *)sr_delta_, 1.0,
-                       sr_out_, ns, sites, slot_, dp_);
-    hipLaunchKernelGGL(sr_accum_kernel<T>, ag, dim3(256), 0, stream_, (const T *)sr_o_, (const int *)sr_cfg_, (const double *)nullptr, 1.0,
-                       sr_v_, ns, sites, slot_, dp_);
-  }
+  hipLaunchKernelGGL(sr_accum_kernel<T>, ag, dim3(256), 0, stream_, (const T *)sr_o_, (const int *)sr_cfg_, (const double *)sr_delta_, 1.0,
+                     sr_out_, ns, sites, slot_, dp_);
+  hipLaunchKernelGGL(sr_accum_kernel<T>, ag, dim3(256), 0, stream_, (const T *)sr_o_, (const int *)sr_cfg_, (const double *)nullptr, 1.0,
+                     sr_v_, ns, sites, slot_, dp_);
   hipLaunchKernelGGL(minsr_combine_kernel<kOut>, opt_grid(), dim3(256), 0, stream_, (const double *)sr_out_, (const double *)sr_v_,
                      (const double *)ysum, ns, opt_g_, (const int *)opt_ne_, slot_, dp_);
   PG_CHECK_HIP(hipGetLastError());

@@ -17,7 +17,7 @@ def _collect(ctx, cfgs, L, D):
     psi = ctx.evaluate_amplitude()
     ctx.set_configs(cfgs)
     ctx.generate_bmps_approach(UP)
-    ostar = np.zeros((n, L, L, 2, D, D, D, D))
+    ostar = np.zeros((n, L, L, 2, D, D, D, D), dtype=psi.dtype)
     for row in range(L):
         ctx.init_bten(LEFT, row)
         ctx.grow_full_bten(RIGHT, row, 1, True)
@@ -25,7 +25,7 @@ def _collect(ctx, cfgs, L, D):
             h = ctx.punch_hole(row, col, HORIZONTAL)
             ctx.punch_hole_store(row, col, HORIZONTAL)
             for w in range(n):
-                ostar[w, row, col, cfgs[w, row, col]] = h[w] / psi[w]
+                ostar[w, row, col, cfgs[w, row, col]] = np.conj(h[w]) / np.conj(psi[w])      # conj(1 / psi) Dag(hole); real: hole / psi
             if col < L - 1:
                 ctx.shift_bten_window(RIGHT)
         if row < L - 1:
@@ -66,10 +66,13 @@ def test_sr_matvec_and_cg(dt, tol):
 
 
 def _store(dt, L=4, D=3, chi=9, nb=24, batches=2):
+    """the resident store of `dt`; c128: the state of test_sr_matvec_complex_vs_oracle (random phases on the same moduli)"""
     from peps_amd import capi
-    sitps = synthetic.make_sitps(L, D)
-    ctx = capi.Context(L, L, D, 2, chi, dtype=capi.F32 if dt == "f32" else capi.F64, max_walkers=nb)
-    ctx.state_upload(synthetic.sitps_to_flat(sitps, D))
+    flat = synthetic.sitps_to_flat(synthetic.make_sitps(L, D), D)
+    if dt == "c128":
+        flat = flat * np.exp(2j * np.pi * np.random.default_rng(12).random(flat.shape)) * (np.abs(flat) > 0)
+    ctx = capi.Context(L, L, D, 2, chi, dtype={"f32": capi.F32, "f64": capi.F64, "c128": capi.C128}[dt], max_walkers=nb)
+    ctx.state_upload(flat)
     ctx.sr_begin(nb * batches)
     samples = []
     for batch in range(batches):
@@ -250,3 +253,71 @@ def test_sr_matvec_complex_vs_oracle():
     assert why_h == osr.K_CONVERGED and abs(ih - idv) <= 1 and np.max(np.abs(xh - xd)) < 1e-4 * np.max(np.abs(xd))
     assert np.linalg.norm((osr.SRSMatrix(samples, mean, 1, 1e-2) * xh.ravel()) - b.ravel()) <= 1.5e-5 * np.linalg.norm(b.ravel())
     ctx.close()
+
+
+# ---- exits of the device solver that the solves above do not reach, and the two C entries of the product ----
+# residual norms: the tolerance of each dtype in the tests above (f32, f64: test_device_resident_cg_follows_the_reference_solver; c128:
+# test_sr_matvec_complex_vs_oracle)
+RES_TOL = {"f32": 2e-3, "f64": 1e-5, "c128": 1e-9}
+
+
+@pytest.fixture(scope="module", params=["f32", "f64", "c128"])
+def exit_case(request):
+    """one store per dtype, the oracle's S on its host samples and a right-hand side on the tensor elements"""
+    dt = request.param
+    ctx, samples = _store(dt, nb=16 if dt == "c128" else 24)
+    mean = np.mean(samples, axis=0)
+    rng = np.random.default_rng(21)
+    b = rng.standard_normal(mean.shape) * _structural_mask()
+    if dt == "c128":
+        b = b + 1j * rng.standard_normal(mean.shape) * _structural_mask()
+    yield dt, ctx, samples, mean, b
+    ctx.close()
+
+
+def _both_solvers(ctx, samples, mean, b, shift, max_iter):
+    ref = osr.SRSMatrix(samples, mean, 1, shift)
+    want = osr.conjugate_gradient_full(lambda y: ref * y, b.ravel(), np.zeros(b.size, dtype=b.dtype), max_iter, 1e-8, 0.0, 20, 0.5)
+    return ctx.sr_cg_solve(b, None, shift, max_iter, 1e-8, 0.0, 20, 0.5), want
+
+
+def test_cg_zero_right_hand_side_converges_at_once(exit_case):
+    dt, ctx, samples, mean, b = exit_case
+    (x, res, it, why), (xo, reso, ito, whyo) = _both_solvers(ctx, samples, mean, np.zeros_like(b), 1e-3, 50)
+    assert (ito, whyo) == (0, osr.K_CONVERGED) and reso == 0.0 and not np.any(xo)
+    assert (it, why) == (ito, whyo) and res == 0.0 and not np.any(x)
+
+
+def test_cg_no_iterations_returns_the_start_vector(exit_case):
+    dt, ctx, samples, mean, b = exit_case
+    (x, res, it, why), (xo, reso, ito, whyo) = _both_solvers(ctx, samples, mean, b, 1e-3, 0)
+    assert (ito, whyo) == (0, osr.K_MAX_ITERATIONS) and not np.any(xo) and abs(reso / np.linalg.norm(b.ravel()) - 1) < 1e-14
+    assert (it, why) == (ito, whyo) and not np.any(x)
+    assert abs(res / reso - 1) < RES_TOL[dt]
+
+
+def test_cg_indefinite_system_exits_at_the_first_step(exit_case):
+    """diag_shift = -2 sum_i |O*_i|^2 / n is below -lambda_max(S) (S is positive semi-definite with trace <= sum_i |O*_i|^2 / n), so
+    p * (A p) < 0 at the first step: detail::pap_is_valid fails, the best iterate is the start vector"""
+    dt, ctx, samples, mean, b = exit_case
+    shift = -2.0 * float(sum(np.vdot(s.ravel(), s.ravel()).real for s in samples)) / len(samples)
+    (x, res, it, why), (xo, reso, ito, whyo) = _both_solvers(ctx, samples, mean, b, shift, 50)
+    assert (ito, whyo) == (0, osr.K_INDEFINITE) and not np.any(xo)
+    assert (it, why) == (ito, whyo) and not np.any(x)
+    assert abs(res / reso - 1) < RES_TOL[dt]
+
+
+def test_the_two_c_entries_of_the_product(exit_case):
+    """pepsgpu_sr_matvec and pepsgpu_sr_matvec_c128 through the raw library handle: on a real context the _c128 entry with a zero
+    imaginary part is the real entry and refuses a non-zero one; on a complex context the real entry is the _c128 entry with a real mean"""
+    from peps_amd.capi import _dp
+    dt, ctx, samples, mean, b = exit_case
+    v = np.ascontiguousarray(b)
+    m, scale = 0.375, 1.0 / len(samples)
+    plain, c128 = np.zeros_like(v), np.zeros_like(v)
+    ctx._ck(ctx._l.pepsgpu_sr_matvec(ctx._h, _dp(v), m, scale, _dp(plain)))
+    ctx._ck(ctx._l.pepsgpu_sr_matvec_c128(ctx._h, _dp(v), m, 0.0, scale, _dp(c128)))
+    assert np.any(plain) and plain.tobytes() == c128.tobytes()
+    if dt != "c128":
+        with pytest.raises(ValueError, match="sr_matvec: a real context takes a real mean_dot_v"):
+            ctx._ck(ctx._l.pepsgpu_sr_matvec_c128(ctx._h, _dp(v), m, 0.25, scale, _dp(c128)))
